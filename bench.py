@@ -82,6 +82,9 @@ def parse():
     ap.add_argument("--dry_launch", action="store_true",
                     help="exercise only the launcher: the ranks form a gloo group on the CPU, all-reduce one word and rank 0 "
                          "prints {n_gpus, n_ranks_seen}; nothing touches a GPU (tests/test_bench_launch_cpu.py)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step computed (rank 0) as DIR/<name>.npy, float32 / "
+                         "float64, at most 64 MiB in all: losses, logits, sampled node sets, sampler logits, updated weights")
     return ap.parse_args()
 
 
@@ -482,6 +485,48 @@ def reference_shaped_ms(b, args, steps):
 _REAL_STDOUT = 1
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(out, models):
+    """-> {name: host array}: what a caller of the captured step receives from one step (GraphedTrainer's result dict) — the
+    losses, the classifier's logits over the sampled node set and that set, each hop's kept ids and the sampler logits of its
+    candidates (read through nb_local, as the draw reads them), and the three nets' parameters after both Adam steps.  Device
+    buffers are cut to their live rows; ids and counts are stored as float64 (exact), everything else as float32."""
+    def host(t):
+        a = t.detach().cpu().numpy()
+        return a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+    d = {k: host(out[k]) for k in ("loss_c", "loss_gfn", "log_z", "tot_log_prob", "hop_stats") if out.get(k) is not None}
+    n_all = int(out["n_all"].item())
+    d["all_nodes"] = host(out["all_nodes"][:n_all])
+    d["logits"] = host(out["logits"][:n_all])
+    for h, (kept, cnt) in enumerate(zip(out["kept"], out["kept_counts"])):
+        d[f"kept_hop{h}"] = host(kept.reshape(-1)[:int(cnt.item())])
+    for h, (lg, nbl, d_nn) in enumerate(zip(out["hop_logits"], out["nb_local"], out["sizes"])):
+        lg, rows = host(lg.reshape(-1)), nbl.reshape(-1)[:int(d_nn.item())].cpu().numpy().astype(np.int64)
+        if rows.size and not (0 <= rows.min() and rows.max() < lg.size):
+            raise RuntimeError(f"hop {h}: nb_local outside the sampler logits ({lg.size} rows)")
+        d[f"sampler_logits_hop{h}"] = lg[rows]
+    for net, m in zip(("classifier", "sampler", "log_z_net"), models):
+        for k, v in m.state_dict().items():
+            d[f"{net}.{k}"] = host(v)
+    return d
+
+
+def write_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """np.save every array as path/<name>.npy.  Should the whole exceed `limit`, each array larger than an equal share of it
+    is replaced by a fixed sample of its rows (seed 0, sorted row order), so that the files stay comparable run to run."""
+    os.makedirs(path, exist_ok=True)
+    share = limit // max(1, len(arrays))
+    over = sum(a.nbytes for a in arrays.values()) > limit
+    rng = np.random.default_rng(0)
+    for name, a in sorted(arrays.items()):
+        if over and a.ndim and a.nbytes > share:
+            keep = max(1, a.shape[0] * share // a.nbytes)
+            a = a[np.sort(rng.choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _emit(res):
     sys.stdout.flush()
     os.write(_REAL_STDOUT, (json.dumps(res) + "\n").encode())       # the ONE line of this program's stdout
@@ -568,6 +613,7 @@ class Bench:
         self.train_idx = torch.randperm(N, device=dev, generator=gen)[:self.n_train]
         self.graph_bytes = self.rowptr.numel() * 8 + self.col.numel() * 4 + self.X.numel() * 4
         self.setup_s = time.time() - t0
+        self.outputs = {}                                         # mode -> step_outputs() of its last timed step (--dump-outputs)
         self.e_cap = min(args.e_cap if args.e_cap > 0 else {"reddit": 1 << 19, "papers100m": 1 << 18}.get(args.workload, 1 << 17),
                          self.col.numel() + 1)
 
@@ -660,6 +706,8 @@ class Bench:
             if int(st_all.item()) and not int(g.status.item()):
                 raise RuntimeError(f"another rank overflowed a capacity (status {int(st_all.item())}): raise --e_cap")
         trainer.check()                               # capacity overflow would have been flagged on the device
+        if args.dump_outputs and rank == 0:           # host copies now: the phases after this one replay the same buffers
+            self.outputs[mode] = step_outputs(out, models)
         # per graph build: edges x the aggregations that ran over it
         ev = (trainer.edge_totals - last_warm + out["agg_counts"].to(torch.int64)).cpu()    # + the last step's, not yet added
         wv = torch.tensor(out["agg_weights"], dtype=torch.int64)
@@ -884,6 +932,8 @@ def main():
         os._exit(3)
     results[primary] = res
     state["primary"] = primary
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, b.outputs[primary])
     trainer, g, models = kept[primary]
     state["extra"] = {"hbm": dict(graph_and_features_GiB=round(b.graph_bytes / 2**30, 2),
                                   peak_allocated_GiB=round(torch.cuda.max_memory_allocated(dev) / 2**30, 2),
