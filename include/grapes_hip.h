@@ -452,7 +452,15 @@ int grapes_slab_reduce_sets(int32_t nsets, const float* const* slabs, float* con
  * over up to four row sets that share the weights (what torch autograd computes for d(head)/d(W1, b1, W2) given
  * d head_out = row_scale and W2 = col_vec; w1 / b1 are the layer's current parameters, [f_out][f_in] dense and [f_out]).
  * bf16x3 kernels only: GRAPES_EINVAL where grapes_split_gemm_available(n, f_in, f_out) is 0.  x rows may be strided
- * (x_stride[h] floats, 0 / NULL = dense).  Workspace: grapes_linear_bwd_weight_gated_workspace_bytes(1, f_in, f_out). */
+ * (x_stride[h] floats, 0 / NULL = dense).  Workspace: grapes_linear_bwd_weight_gated_workspace_bytes(1, f_in, f_out).
+ * Range of the bf16x3 weight gradient (these entries and the rank-1 gated ones on the split kernel; tests/
+ * test_split_dw_accuracy_gpu.py): each product v = row_scale[r] x[r][k] is formed in fp32 and split into three bf16 terms.
+ *   - |v| >= 3.3962e38 (finite in fp32) rounds to bf16 inf: the lower terms become -inf and NaN, and column k of dW1 is NaN
+ *     for EVERY unit (a 0 of the mask times inf is NaN too), with dW2 of the gate-word form (derived from dW1's sums);
+ *     db1 and the other columns are unaffected.  The fp32 kernels give a finite answer there.  Not guarded: activations
+ *     that large mean training has already diverged.
+ *   - |v| below about 2^-109 (1.6e-33) is held by the three terms only to bf16's smallest subnormal step, 2^-133 (an error
+ *     of at most 2^-134 per product instead of 2^-24 |v|); the matrix pipe keeps bf16 subnormals. */
 int grapes_linear_relu_head_fwd_bits(const float* x, int32_t x_stride, const float* w, const float* bias,
                                      const float* head_w, uint32_t* gate_bits, float* head_out, int32_t n,
                                      const int32_t* d_n, int32_t f_in, int32_t f_out, grapes_stream_t stream);

@@ -1,0 +1,246 @@
+"""TEST INFRASTRUCTURE — the element-wise accuracy criterion of the fp32-accuracy GEMMs, and the data they are judged on.
+
+The matrix-pipe GEMMs split every fp32 operand exactly into three bf16 planes and sum the cross products in fp32
+(grapes_amd/csrc/gemm_kernels.hip: split3 / split3_pair).  A norm-wise tolerance such as
+``max|got - ref| <= 2e-5 max|ref|`` cannot see the lowest plane: it carries about 2^-16 of each product.  The criterion
+here can.  Each output is judged against an fp64 reference relative to ITS OWN magnitude, the fp64 sum of |a||b| of the
+terms it adds up:
+
+    e = |got - ref| / mag          (where mag == 0 the output must be exactly 0: e = 0 if it is, inf if not)
+
+and the max and rms of e must stay within RMS_FACTOR / MAX_FACTOR of the same two numbers for a host fp32 baseline: the same
+product over the same fp32 operands, summed in fp32 in ONE fixed order (fp32_contract: blocks of BLOCK terms added one after
+the other, the block sums then added in block order) — where a kernel forms a product before it splits it, as
+gemm_dw_split_k forms rs * x, the baseline forms that product in fp32 first.  The order is written out here rather than left
+to a BLAS: a BLAS sums a long contraction in an order of its own choosing, and the same fp32 matmul was measured 10x more
+accurate (rms) on one host than on another, which made the criterion depend on the machine running the test.  So "fp32
+accuracy" means: no worse than a plain blocked fp32 sum of the same products, by a small factor that leaves room for
+another summation order.
+
+The data generators below are shared by tests/test_accuracy_criterion_cpu.py (a CPU emulation of the split kernels,
+faithful and with defects, which shows the criterion rejects a lost plane) and tests/test_split_dw_accuracy_gpu.py (the
+kernels themselves), so the two cannot drift apart.  Only tests import this module.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+RMS_FACTOR = 3.0
+MAX_FACTOR = 6.0
+# the baseline's error can be exactly 0 (a unit live in one row, an output of one term): below FLOOR the ratios are taken
+# against FLOOR instead — 2^-30 of an output's magnitude is 1/64 ulp of it, far below any defect the criterion is for
+FLOOR = 2.0 ** -30
+
+# (n, K, H) of the weight-gradient GEMM gemm_dw_split_k: the sampler nets' first layer (K = 100 / 104 features +
+# indicators, H = 256), the log-Z net's narrow form (K = 64, H = 96) and the 160-column form (K = 128 / 132 / 144;
+# 144 is its widest: 8 (K / 4) + 32 staging tasks <= 320).
+DW_SHAPES = [(37500, 104, 256), (5000, 100, 256), (2500, 64, 96), (37000, 132, 256), (5000, 128, 256), (3000, 144, 128)]
+# (n, K, H) of the forward GEMM with the fused head (test_hip_parity.py: test_forward_gemm_with_fused_head_projection)
+FWD_SHAPES = [(37501, 104, 256), (5000, 100, 256), (2100, 64, 96), (700, 104, 256)]
+KINDS = ("normal", "mixed", "zeros")
+DEAD_UNIT, ONE_ROW_UNIT = 0, 1          # units of every generated layer: gated off in every row / live in exactly one row
+
+
+def elementwise(got, ref, mag) -> Tuple[float, float]:
+    """(max, rms) of |got - ref| / mag over all outputs; an output with mag == 0 must be exactly 0 (else inf)."""
+    got = torch.as_tensor(got).double().cpu().reshape(-1)
+    ref = torch.as_tensor(ref).double().cpu().reshape(-1)
+    mag = torch.as_tensor(mag).double().cpu().reshape(-1)
+    if got.numel() == 0:
+        return 0.0, 0.0
+    zero = mag == 0
+    e = (got - ref).abs() / torch.where(zero, torch.ones_like(mag), mag)
+    e = torch.where(zero, torch.where(got == 0, torch.zeros_like(e), torch.full_like(e, float("inf"))), e)
+    e = torch.where(torch.isnan(e), torch.full_like(e, float("inf")), e)
+    return float(e.max()), float((e ** 2).mean().sqrt())
+
+
+class Accuracy:
+    """Element-wise errors of one output tensor and of its host fp32 baseline."""
+
+    def __init__(self, got, ref, mag, base):
+        self.max, self.rms = elementwise(got, ref, mag)
+        self.base_max, self.base_rms = elementwise(base, ref, mag)
+
+    @property
+    def rms_ratio(self) -> float:
+        return self.rms / max(self.base_rms, FLOOR)
+
+    @property
+    def max_ratio(self) -> float:
+        return self.max / max(self.base_max, FLOOR)
+
+    def ok(self, rms_factor: float = RMS_FACTOR, max_factor: float = MAX_FACTOR) -> bool:
+        return self.rms_ratio <= rms_factor and self.max_ratio <= max_factor
+
+    def __repr__(self):
+        return (f"max {self.max:.3e} (fp32 {self.base_max:.3e}, x{self.max_ratio:.2f}), "
+                f"rms {self.rms:.3e} (fp32 {self.base_rms:.3e}, x{self.rms_ratio:.2f})")
+
+
+def assert_fp32_accuracy(got, ref, mag, base, what: str = "") -> Accuracy:
+    a = Accuracy(got, ref, mag, base)
+    print(f"[accuracy] {what}: {a}")
+    assert a.ok(), f"{what}: {a}"
+    return a
+
+
+# ------------------------------------------------------------------------------------------------------------- data
+def layer_problem(n: int, K: int, H: int, kind: str, seed: int, n_pad: int = 0) -> Dict[str, np.ndarray]:
+    """One row set of the layer  x -> ReLU(x w^T + b) -> 1-wide head w2  and the head's gradient rs, fp32:
+    x [n, ceil4(K)] (zero pad columns), rs [n], w [H, ceil4(K)], b [H], w2 [H].  kind:
+      normal  N(0,1) rows;
+      mixed   row r of x at 10^a_r and rs_r at 10^(-a_r + c_r), a in [-20, 20], c in [-3, 3]: every output of the
+              weight gradient sums terms of very different sizes (the products rs x stay finite);
+      zeros   N(0,1) with exact zeros: whole rows of x, entries of rs, single entries, a whole column of x.
+    Every kind has unit DEAD_UNIT gated off in every row (w row 0, b = -1) and unit ONE_ROW_UNIT live in exactly one row
+    (x column 0 is zero except x[n // 2, 0] = 1, w row = e_0, b = -0.5: its pre-activation is +-0.5 exactly)."""
+    rng = np.random.default_rng(seed)
+    Kp = (K + 3) // 4 * 4
+    x = rng.standard_normal((n, Kp))
+    rs = rng.standard_normal(n)
+    if kind == "mixed":
+        a = rng.uniform(-20, 20, n)
+        x *= 10.0 ** a[:, None]
+        rs *= 10.0 ** (-a + rng.uniform(-3, 3, n))
+    elif kind == "zeros" and n:
+        x[rng.integers(0, n, max(1, n // 50))] = 0.0
+        rs[rng.integers(0, n, max(1, n // 50))] = 0.0
+        x[rng.integers(0, n, n), rng.integers(0, K, n)] = 0.0
+        x[:, K // 2] = 0.0
+    elif kind not in KINDS:
+        raise ValueError(kind)
+    x[:, K:] = 0.0
+    x[:, 0] = 0.0
+    if n:
+        x[n // 2, 0] = 1.0
+    w = rng.standard_normal((H, Kp)) * 0.2
+    w[:, K:] = 0.0
+    b = rng.standard_normal(H) * 0.1
+    w[DEAD_UNIT] = 0.0; b[DEAD_UNIT] = -1.0
+    w[ONE_ROW_UNIT] = 0.0; w[ONE_ROW_UNIT, 0] = 1.0; b[ONE_ROW_UNIT] = -0.5
+    w2 = rng.standard_normal(H) * 0.3
+    f = lambda v: np.ascontiguousarray(v, dtype=np.float32)
+    if n_pad:       # rows beyond the live count: NaN (a kernel that reads them poisons its outputs)
+        x = np.concatenate([x, np.full((n_pad, Kp), np.nan)])
+        rs = np.concatenate([rs, np.full(n_pad, np.nan)])
+    return {"x": f(x), "rs": f(rs), "w": f(w), "b": f(b), "w2": f(w2)}
+
+
+def host_mask(x: np.ndarray, w: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """[n, H] bool: the ReLU gate of the fp64 pre-activation (the CPU emulation's mask; the GPU tests take the device's)."""
+    return (x.astype(np.float64) @ w.astype(np.float64).T + b.astype(np.float64)) > 0
+
+
+# ------------------------------------------------------------------------------------------------------- references
+BLOCK = 128     # terms per block of the baseline's fixed summation order (a workgroup's share of rows is of this order)
+
+
+def _f32(a) -> torch.Tensor:
+    return torch.as_tensor(np.asarray(a, dtype=np.float32))
+
+
+def fp32_contract(a, b) -> torch.Tensor:
+    """aᵀ b for a [n, M], b [n, N] in fp32, in a fixed order that does not depend on the host: the n terms of each output in
+    blocks of BLOCK, each block summed term by term (product rounded to fp32, then added in fp32), then the block sums added in
+    block order.  Element-wise torch ops only, no BLAS."""
+    a, b = _f32(a), _f32(b)
+    n, M, N = a.shape[0], a.shape[1], b.shape[1]
+    nb = max(1, -(-n // BLOCK))
+    A = torch.cat([a, torch.zeros(nb * BLOCK - n, M)]).view(nb, BLOCK, M)
+    B = torch.cat([b, torch.zeros(nb * BLOCK - n, N)]).view(nb, BLOCK, N)
+    part = torch.zeros(nb, M, N)
+    for j in range(min(BLOCK, n)):
+        part += A[:, j, :, None] * B[:, j, None, :]
+    out = torch.zeros(M, N)
+    for z in range(nb):
+        out += part[z]
+    return out
+
+
+def _t64(a):
+    return torch.as_tensor(np.asarray(a)).double()
+
+
+def dw_reference(segs: Sequence[Tuple[np.ndarray, np.ndarray, np.ndarray]], cv, w1=None, b1=None,
+                 prev: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
+    """fp64 reference, fp64 magnitude and host fp32 baseline of the rank-1 gated weight gradient over row sets
+    segs = [(mask [n, H] bool, x [n, K] fp32, rs [n] fp32), ...]:
+        dw[m][k] = cv[m] S[m][k],  db[m] = cv[m] T[m],  S = sum_r mask rs x,  T = sum_r mask rs
+    and with w1, b1 the gate-word form's head gradient  dwh[m] = <S[m], w1[m]> + b1[m] T[m]  (= sum_r rs relu(z) on the mask).
+    The baseline forms rs * x in fp32 (as the kernel does before splitting) and sums with fp32_contract; its dwh adds the K
+    products of <S, w1> term by term in fp32.
+    prev: the buffers accumulated onto ({"dw", "db", "dwh"}).  -> {name: (ref, mag, base)}"""
+    cv64, cv32 = _t64(cv), torch.as_tensor(np.asarray(cv, dtype=np.float32))
+    H = cv64.numel()
+    K = segs[0][1].shape[1]
+    S, Sa, T, Ta = (torch.zeros(H, K, dtype=torch.float64), torch.zeros(H, K, dtype=torch.float64),
+                    torch.zeros(H, dtype=torch.float64), torch.zeros(H, dtype=torch.float64))
+    S32, T32 = torch.zeros(H, K), torch.zeros(H)
+    for mask, x, rs in segs:
+        if len(rs) == 0:
+            continue
+        m64 = torch.as_tensor(np.asarray(mask)).double()
+        x64, rs64 = _t64(x), _t64(rs)
+        v = rs64[:, None] * x64                                    # exact: a product of two fp32 values
+        S += m64.T @ v; Sa += m64.T @ v.abs(); T += m64.T @ rs64; Ta += m64.T @ rs64.abs()
+        x32, rs32 = _f32(x), _f32(rs)
+        ST = fp32_contract(m64.float(), torch.cat([rs32[:, None] * x32, rs32[:, None]], 1))
+        S32 += ST[:, :K]; T32 += ST[:, K]
+    out = {"dw": [cv64[:, None] * S, cv64.abs()[:, None] * Sa, cv32[:, None] * S32],
+           "db": [cv64 * T, cv64.abs() * Ta, cv32 * T32]}
+    if w1 is not None:
+        w64, b64 = _t64(w1)[:, :K], _t64(b1)
+        w32, b32 = _f32(w1)[:, :K], _f32(b1)
+        h32 = torch.zeros(H)
+        for k in range(K):
+            h32 += S32[:, k] * w32[:, k]
+        h32 += b32 * T32
+        out["dwh"] = [(S * w64).sum(1) + b64 * T, (Sa * w64.abs()).sum(1) + b64.abs() * Ta, h32]
+    for k in out:
+        if prev is not None and k in prev:
+            p64, p32 = _t64(prev[k]), torch.as_tensor(np.asarray(prev[k], dtype=np.float32))
+            out[k] = [out[k][0] + p64, out[k][1] + p64.abs(), out[k][2] + p32]
+    return {k: tuple(v) for k, v in out.items()}
+
+
+def head_reference(segs: Sequence[Tuple[np.ndarray, np.ndarray]], prev=None):
+    """The activation form's head gradient  dwh[m] = sum_r rs[r] act[r][m]  over segs = [(act [n, H], rs [n]), ...]
+    -> (ref, mag, base)."""
+    ref = mag = base = None
+    for act, rs in segs:
+        a64, r64 = _t64(act), _t64(rs)
+        parts = (r64 @ a64, r64.abs() @ a64.abs(), fp32_contract(_f32(rs)[:, None], act).view(-1))
+        ref, mag, base = parts if ref is None else (ref + parts[0], mag + parts[1], base + parts[2])
+    if prev is not None:
+        p64 = _t64(prev)
+        ref, mag, base = ref + p64, mag + p64.abs(), base + torch.as_tensor(np.asarray(prev, dtype=np.float32))
+    return ref, mag, base
+
+
+def matmul_reference(a, b) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """a [n, K] @ b [K, N]: (fp64 reference, fp64 sum |a||b|, host fp32 baseline)."""
+    a64, b64 = _t64(a), _t64(b)
+    return a64 @ b64, a64.abs() @ b64.abs(), fp32_contract(_f32(a).T.contiguous(), b)
+
+
+# ------------------------------------------------------------------------------------------------------- domain edges
+def domain_edge_row_scale(n: int) -> np.ndarray:
+    """rs for the domain-edge cases: U(0.5, 1) (|rs| <= 1 keeps rs * x finite next to an x of 3.4e38; not all ones, whose
+    integer sums an fp32 baseline would add exactly), rs[5] = 1."""
+    rs = np.random.default_rng(5).uniform(0.5, 1.0, n).astype(np.float32)
+    rs[5] = 1.0
+    return rs
+
+
+def within_split_resolution(dw, ref_dw, mask, cv) -> bool:
+    """|dw - ref| <= |cv| (live rows) 2^-134 + 2^-20 mag per output: each product rs x held to half of bf16's smallest
+    subnormal step, plus an fp32 sum's rounding — what the three-plane split guarantees for products below ~2^-109."""
+    ref, mag = ref_dw[0], ref_dw[1]
+    live = torch.from_numpy(np.asarray(mask).sum(0).astype(np.float64))
+    bound = torch.from_numpy(np.asarray(cv, dtype=np.float64)).abs() * live * 2.0 ** -134
+    err = (torch.as_tensor(dw).double() - ref).abs()
+    return bool((err <= bound[:, None] + 2.0 ** -20 * mag).all())

@@ -9,6 +9,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from oracle import accuracy as accuracy_criterion
 from oracle import grapes_oracle as O
 from oracle import portable_math as pm
 
@@ -887,7 +888,9 @@ def test_captured_step_matches_eager_step(capture, reinforce, forms, monkeypatch
 def test_gate_bits_layer_pair_matches_activation_form(n, cap, K, H, strided):
     """layer -> ReLU -> 1-wide head with 32 bytes of gate bits per row instead of the activations (include/grapes_hip.h):
     same head output bit for bit, bits = (activation > 0) in the documented layout, and dW1 / db1 / dW2 against the
-    activation-based kernels and against fp64 torch autograd of the same expression (modules/gcn.py:31-36, [H, 1])."""
+    activation-based kernels and against fp64 torch autograd of the same expression (modules/gcn.py:31-36, [H, 1]).  Also
+    element-wise on the decoded mask (oracle/accuracy.py); measured max / rms ratio to the fp32 baseline, worst shape:
+    gate words dW1 1.01 / 0.86, db1 1.16 / 0.84, dW2 1.01 / 0.78; activation form 1.08 / 1.30, 1.06 / 1.11, 0.91 / 0.78."""
     _cuda()
     from grapes_amd import ops
     torch.manual_seed(n + K)
@@ -942,6 +945,15 @@ def test_gate_bits_layer_pair_matches_activation_form(n, cap, K, H, strided):
             (() if wide_k else ((outs[0][2], w2d.grad.view(-1)),)):
         scale = max(1.0, float(ref.abs().max()))
         assert float((got.double() - ref).abs().max()) <= 2e-5 * scale
+    # element-wise on the device's own mask (oracle/accuracy.py): each output against fp64 relative to its own sum |a||b|
+    x_np, rs_np, act_np = x[:n].cpu().numpy(), rs[:n].cpu().numpy(), act[:n].cpu().numpy()
+    refs = accuracy_criterion.dw_reference([(dec, x_np, rs_np)], w2.view(-1).cpu().numpy(), w.cpu().numpy(), b.cpu().numpy())
+    for form, o in enumerate(outs):
+        if o is None:
+            continue
+        for got, k in zip(o, ("dw", "db", "dwh")):
+            ref = accuracy_criterion.head_reference([(act_np, rs_np)]) if (form == 0 and k == "dwh") else refs[k]
+            accuracy_criterion.assert_fp32_accuracy(got.cpu(), *ref, what=f"{('act', 'bits')[form]} {k}")
     # two row sets sharing the weights, accumulated on top of existing gradients
     n2 = n // 3
     d_n2 = torch.tensor([n2], dtype=torch.int32, device="cuda")
@@ -1490,7 +1502,8 @@ def test_gated_dw_gemm_with_rank1_operand_and_head_gradient(n, fi, fo):
     """Backward of  first layer -> ReLU -> 1-wide head  in ONE split-K GEMM (step_graph._head_bwd): with
     dAct = dh2 ⊗ w2 formed on load and masked by the ReLU output,  dW1 = (dAct ⊙ [act>0])ᵀ ax,  db1 = its column sums,
     and the head's own  dW2 = dh2ᵀ act  gathered from the same gate tiles; against fp64, incl. accumulation and a
-    device-side row count below the capacity."""
+    device-side row count below the capacity.  Also element-wise (oracle/accuracy.py); measured max / rms ratio to the
+    fp32 baseline: dW1 1.14 / 1.26, db1 1.28 / 1.20, dW2 1.11 / 0.82."""
     _cuda()
     from grapes_amd import ops
     rng = np.random.default_rng(n + fo)
@@ -1508,6 +1521,13 @@ def test_gated_dw_gemm_with_rank1_operand_and_head_gradient(n, fi, fo):
     ref_dw, ref_db, ref_h = 0.5 + Ag.T @ X, -1.0 + Ag.sum(0), 2.0 + dh2[:n].double() @ G
     for got, ref in ((dw, ref_dw), (db, ref_db), (dwh, ref_h)):
         assert float((got.double() - ref).abs().max()) <= 2e-5 * max(1.0, float(ref.abs().max()))
+    # element-wise on the same mask (oracle/accuracy.py), the buffers accumulated onto included
+    prev = {"dw": np.full((fo, fi), 0.5, np.float32), "db": np.full(fo, -1.0, np.float32)}
+    act_np, rs_np = act[:n].cpu().numpy(), dh2[:n].cpu().numpy()
+    refs = accuracy_criterion.dw_reference([(act_np > 0, ax[:n].cpu().numpy(), rs_np)], w2.cpu().numpy(), prev=prev)
+    refs["dwh"] = accuracy_criterion.head_reference([(act_np, rs_np)], prev=np.full(fo, 2.0, np.float32))
+    for got, k in ((dw, "dw"), (db, "db"), (dwh, "dwh")):
+        accuracy_criterion.assert_fp32_accuracy(got.cpu(), *refs[k], what=k)
     dw2 = torch.empty_like(dw); db2 = torch.empty_like(db); dwh2 = torch.empty_like(dwh)
     ops.linear_bwd_weight_gated(None, ax, gate=act, d_n=d_n, dw=dw2, dbias=db2, accumulate=False, row_scale=dh2, col_vec=w2,
                                 dw_head=dwh2)
@@ -1866,7 +1886,8 @@ def test_forward_gemm_with_fused_head_projection(n, cap, K, N):
     """out = ReLU(x Wᵀ + b) and head = out · w2 from the same launch (summed from the output tiles in registers): the
     activations equal the plain entry point's bit for bit, the head equals out @ w2 in fp64 at 1e-5; rows beyond the
     device-side count are not written.  Covers a partial last panel, idle wavefronts (N < 256) and the two-launch
-    fallback for few rows."""
+    fallback for few rows.  The head also element-wise (oracle/accuracy.py): measured max / rms ratio to the fp32
+    baseline 0.61 / 1.00 at worst."""
     _cuda()
     from grapes_amd import ops
     rng = np.random.default_rng(n + N)
@@ -1879,6 +1900,9 @@ def test_forward_gemm_with_fused_head_projection(n, cap, K, N):
     assert torch.equal(out[:n], ref_out[:n])
     ref_head = out[:n].double() @ w2.double().T
     assert float((head[:n].double() - ref_head).abs().max()) <= 1e-5 * max(1.0, float(ref_head.abs().max()))
+    # element-wise against the fp64 product of the device's own activations (oracle/accuracy.py)
+    accuracy_criterion.assert_fp32_accuracy(head[:n].cpu(), *accuracy_criterion.matmul_reference(out[:n].cpu().numpy(), w2.cpu().numpy().T),
+                                            what="head")
     # determinism: the same launch twice gives the same bits
     out2, head2 = ops.linear_bias_act_head_fwd(x, w, b, True, w2, d_n=d_n)
     assert torch.equal(head[:n], head2[:n])
