@@ -61,6 +61,11 @@ SIGNATURES = {
     "grapes_linear_bwd_weight_gathered_split": (I32, [P, P, I32, I32, P, P, U32, P, I32, U32, P, I32, P, I32, I32, P, P]),
     "grapes_csr_build_workspace_bytes": (C.c_size_t, [I64, I32]),
     "grapes_csr_build": (I32, [P, P, I64, I32, P, P, P, P, P, P]),
+    "grapes_csr_symmetric_check": (I32, [P, P, I32, P, P]),
+    "grapes_csr_transpose": (I32, [P, P, I64, I32, P, P, P, P, P]),
+    "grapes_gcn_large_prepare": (I32, [P, P, I32, I32, P, P, P]),
+    "grapes_gcn_large_aggregate_workspace_bytes": (C.c_size_t, [I32, I32, I32]),
+    "grapes_gcn_large_aggregate": (I32, [P, I64, P, P, P, I32, I32, P, I32, I32, P, I32, P, I64, I32, I32, P, P, P]),
     "grapes_kernel_clock_enable": (I32, [P, I64]),
     "grapes_kernel_clock_launches": (I32, []),
     "grapes_kernel_clock_entry": (I32, [I32, P, P, P]),

@@ -290,6 +290,37 @@ __global__ __launch_bounds__(256) void csr_place_k(const int64_t* __restrict__ r
     }
 }
 
+// per-row sort / de-duplication of the raw row segments (col_raw at rowptr_raw), then the final row pointer and placement
+static int csr_sort_place(int64_t num_edges, int32_t num_nodes, size_t N, int32_t* col_raw, const int64_t* rowptr_raw,
+                          unsigned* udeg, int64_t* tiles, int32_t* long_rows, int32_t* n_long, int long_cap, int64_t* rowptr,
+                          int32_t* col, int32_t* status, hipStream_t s) {
+    hipError_t e;
+    long long nwin = (num_edges + CSR_WIN - 1) / CSR_WIN; if (nwin < 1) nwin = 1;
+    int wgrid = (int)(nwin > 65536 ? 65536 : nwin);
+    const size_t win_lds = (size_t)CSR_CAP * (sizeof(unsigned long long) + sizeof(int));
+    {   // 96 KB of dynamic LDS: set on every call (cheap, per device, no shared flag), after checking that the device has it
+        int dev = 0, max_lds = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) return (int)hipGetLastError();
+        if ((size_t)max_lds < win_lds + 256) return GRAPES_EINVAL;          // gfx950 has 160 KB per workgroup; 64 KB parts are not a target
+        e = hipFuncSetAttribute((const void*)csr_window_sort_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)win_lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(csr_window_sort_k, dim3(wgrid), dim3(512), win_lds, s, rowptr_raw, num_nodes, col_raw, udeg, long_rows,
+                       n_long, long_cap, status);
+    GRAPES_LAUNCH_CHECK();
+    hipLaunchKernelGGL(csr_long_sort_k, dim3(512), dim3(1024), 0, s, rowptr_raw, col_raw, udeg,
+                       (const int32_t*)long_rows, (const int32_t*)n_long, long_cap);
+    GRAPES_LAUNCH_CHECK();
+    int rc = scan_u32_to_i64(udeg, (long long)N, rowptr, rowptr + N, tiles, s);
+    if (rc) return rc;
+    int pgrid = grapes_div_up((int64_t)N, 4); if (pgrid > 65536) pgrid = 65536;
+    hipLaunchKernelGGL(csr_place_k, dim3(pgrid), dim3(256), 0, s, rowptr_raw, (const int64_t*)rowptr,
+                       (const unsigned*)udeg, (const int32_t*)col_raw, col, num_nodes);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}
+
 static inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 extern "C" size_t grapes_csr_build_workspace_bytes(int64_t num_edges, int32_t num_nodes) {
     const size_t E = (size_t)(num_edges > 0 ? num_edges : 1), N = (size_t)(num_nodes > 0 ? num_nodes : 1);
@@ -330,29 +361,70 @@ extern "C" int grapes_csr_build(const int64_t* edge_src, const int64_t* edge_dst
     hipLaunchKernelGGL(csr_scatter_k, dim3(grid), dim3(256), 0, s, edge_src, edge_dst, (long long)num_edges, num_nodes,
                        (const int64_t*)rowptr_raw, deg, col_raw);
     GRAPES_LAUNCH_CHECK();
-    long long nwin = (num_edges + CSR_WIN - 1) / CSR_WIN; if (nwin < 1) nwin = 1;
-    int wgrid = (int)(nwin > 65536 ? 65536 : nwin);
-    const size_t win_lds = (size_t)CSR_CAP * (sizeof(unsigned long long) + sizeof(int));
-    {   // 96 KB of dynamic LDS: set on every call (cheap, per device, no shared flag), after checking that the device has it
-        int dev = 0, max_lds = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) return (int)hipGetLastError();
-        if ((size_t)max_lds < win_lds + 256) return GRAPES_EINVAL;          // gfx950 has 160 KB per workgroup; 64 KB parts are not a target
-        e = hipFuncSetAttribute((const void*)csr_window_sort_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)win_lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL(csr_window_sort_k, dim3(wgrid), dim3(512), win_lds, s, (const int64_t*)rowptr_raw, num_nodes, col_raw, udeg, long_rows,
-                       n_long, long_cap, status);
-    GRAPES_LAUNCH_CHECK();
-    hipLaunchKernelGGL(csr_long_sort_k, dim3(512), dim3(1024), 0, s, (const int64_t*)rowptr_raw, col_raw, udeg,
-                       (const int32_t*)long_rows, (const int32_t*)n_long, long_cap);
-    GRAPES_LAUNCH_CHECK();
-    rc = scan_u32_to_i64(udeg, (long long)N, rowptr, rowptr + N, tiles, s);
+    rc = csr_sort_place(num_edges, num_nodes, N, col_raw, rowptr_raw, udeg, tiles, long_rows, n_long, long_cap, rowptr, col, status, s);
     if (rc) return rc;
-    int pgrid = grapes_div_up((int64_t)N, 4); if (pgrid > 65536) pgrid = 65536;
-    hipLaunchKernelGGL(csr_place_k, dim3(pgrid), dim3(256), 0, s, (const int64_t*)rowptr_raw, (const int64_t*)rowptr,
-                       (const unsigned*)udeg, (const int32_t*)col_raw, col, num_nodes);
-    GRAPES_LAUNCH_CHECK();
     if (hipMemcpyAsync(d_nnz, rowptr + N, sizeof(int64_t), hipMemcpyDeviceToDevice, s) != hipSuccess) return (int)hipGetLastError();
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- transpose of a device CSR
+// (r, c) -> (c, r): the CSR by target of a directed graph for full-batch message passing above 2^31 entries (N1; spmm_large.hip).
+// The same counting placement as the build, read from the CSR itself (one wavefront per row), then the same per-row sort.
+__global__ __launch_bounds__(256) void csr_t_hist_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N,
+                                                    unsigned* __restrict__ deg, int32_t* status) {
+    const int lane = threadIdx.x & 63;
+    const long long nw = ((long long)gridDim.x * blockDim.x) >> 6;
+    bool bad = false;
+    for (long long row = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; row < N; row += nw)
+        for (long long j = rowptr[row] + lane; j < rowptr[row + 1]; j += 64) {
+            const int c = col[j];
+            if (c < 0 || c >= N) { bad = true; continue; }
+            atomicAdd(&deg[c], 1u);
+        }
+    if (bad && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+}
+__global__ __launch_bounds__(256) void csr_t_scatter_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N,
+                                                       const int64_t* __restrict__ rowptr_raw, unsigned* __restrict__ cursor,
+                                                       int32_t* __restrict__ col_raw) {
+    const int lane = threadIdx.x & 63;
+    const long long nw = ((long long)gridDim.x * blockDim.x) >> 6;
+    for (long long row = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; row < N; row += nw)
+        for (long long j = rowptr[row] + lane; j < rowptr[row + 1]; j += 64) {
+            const int c = col[j];
+            if (c < 0 || c >= N) continue;
+            const unsigned p = atomicAdd(&cursor[c], 1u);
+            col_raw[rowptr_raw[c] + p] = (int32_t)row;
+        }
+}
+
+/* rowptr_t int64[N+1], col_t int32[capacity nnz]; workspace: grapes_csr_build_workspace_bytes(nnz, N), 256-byte aligned. */
+extern "C" int grapes_csr_transpose(const int64_t* rowptr, const int32_t* col, int64_t nnz, int32_t num_nodes, int64_t* rowptr_t,
+                                    int32_t* col_t, void* workspace, int32_t* status, grapes_stream_t stream) {
+    if (nnz < 0 || num_nodes <= 0 || !rowptr || !rowptr_t || !workspace || (nnz > 0 && (!col || !col_t))) return GRAPES_EINVAL;
+    if (((uintptr_t)workspace & 255) != 0) return GRAPES_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t E = (size_t)(nnz > 0 ? nnz : 1), N = (size_t)num_nodes;
+    char* w = (char*)workspace;
+    int32_t* col_raw = (int32_t*)w; w += al256(E * 4);
+    int64_t* rowptr_raw = (int64_t*)w; w += al256((N + 1) * 8);
+    unsigned* deg = (unsigned*)w; w += al256(N * 4);
+    unsigned* udeg = (unsigned*)w; w += al256(N * 4);
+    const size_t ntiles = (N + SCAN_TILE - 1) / SCAN_TILE + 1;
+    int64_t* tiles = (int64_t*)w; w += al256(ntiles * 8);
+    const int long_cap = (int)(E / CSR_WIN + 2);
+    int32_t* long_rows = (int32_t*)w; w += al256((size_t)long_cap * 4);
+    int32_t* n_long = (int32_t*)w;
+    hipError_t e;
+    if ((e = grapes_zero_async(deg, N * 4, s)) != hipSuccess) return (int)e;
+    if ((e = grapes_zero_async(udeg, N * 4, s)) != hipSuccess) return (int)e;
+    if ((e = grapes_zero_async(n_long, 64, s)) != hipSuccess) return (int)e;
+    int grid = grapes_div_up((int64_t)N, 4); if (grid > 65536) grid = 65536;
+    hipLaunchKernelGGL(csr_t_hist_k, dim3(grid), dim3(256), 0, s, rowptr, col, num_nodes, deg, status);
+    GRAPES_LAUNCH_CHECK();
+    int rc = scan_u32_to_i64(deg, (long long)N, rowptr_raw, rowptr_raw + N, tiles, s);
+    if (rc) return rc;
+    if ((e = grapes_zero_async(deg, N * 4, s)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(csr_t_scatter_k, dim3(grid), dim3(256), 0, s, rowptr, col, num_nodes, (const int64_t*)rowptr_raw, deg, col_raw);
+    GRAPES_LAUNCH_CHECK();
+    return csr_sort_place(nnz, num_nodes, N, col_raw, rowptr_raw, udeg, tiles, long_rows, n_long, long_cap, rowptr_t, col_t, status, s);
 }

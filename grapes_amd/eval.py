@@ -18,7 +18,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import ops
+from . import full_graph, ops
 from .graph import DeviceGraph, as_device_graph
 
 
@@ -65,12 +65,15 @@ def _captured_evaluator(g, x, xkey, y, gcn_c, gcn_gf, args, num_ind, batches):
 @torch.inference_mode()
 def evaluate(gcn_c, gcn_gf, data, args, adjacency, node_map=None, num_indicators: Optional[int] = None, device=None,
              mask: Optional[torch.Tensor] = None, eval_on_cpu: bool = True, loader=None, full_batch: bool = False,
-             return_predictions: bool = False, captured: bool = True) -> Tuple[float, float]:
+             return_predictions: bool = False, captured: bool = True, large_graph: Optional[bool] = None) -> Tuple[float, float]:
     """Same call shape as the reference's evaluate() (eval.py:12-24).  `data` needs .x, .y; `args` needs
     .sampling_hops, .num_samples, .use_indicators; `adjacency` is a DeviceGraph or the SciPy CSR;
     `loader` yields (target_nodes,) batches covering the masked nodes in order (main.py:129,132).
     return_predictions (not in the reference): also return the predictions the metrics were computed from — argmax classes
-    (eval.py:52,154), or the `logit > 0` matrix for multi-label targets (eval.py:58) — as a third element."""
+    (eval.py:52,154), or the `logit > 0` matrix for multi-label targets (eval.py:58) — as a third element.
+    large_graph (full_batch only): None = automatic — graphs with 2^31 or more entries take the row-blocked 64-bit path of
+    full_graph.py (the last layer over the mask rows only, reduced block by block), smaller ones the whole-graph pass below;
+    True forces the row-blocked path on any graph (`args.eval_block_rows`, if set, is its row block)."""
     g: DeviceGraph = as_device_graph(adjacency)
     dev = g.device
     x = data.x.to(dev).contiguous()
@@ -78,6 +81,9 @@ def evaluate(gcn_c, gcn_gf, data, args, adjacency, node_map=None, num_indicators
     if mask is None:
         mask = torch.ones(g.num_nodes, dtype=torch.bool, device=dev)
     mask = mask.to(dev)
+    if full_batch and full_graph.use_large_path(g, large_graph):
+        return full_graph.evaluate_rows(gcn_c, x, g, y, mask, return_predictions,
+                                        block_rows=getattr(args, "eval_block_rows", None))   # eval.py:47-70, row-blocked
     if full_batch:
         logits, _ = gcn_c(x, g)                                                     # eval.py:50
         m = _metrics(logits[mask], y[mask])

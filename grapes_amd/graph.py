@@ -171,6 +171,30 @@ class DeviceGraph(EpochSpace):
             self._prepared = ops.PreparedGraph.from_csr(rp_t, c_t, N, rp_s, c_s)
         return self._prepared
 
+    def full_graph_plan(self, hub_chunk: int = 1024):
+        """LargeGraphPlan of the WHOLE adjacency for full-batch message passing with 64-bit offsets (full_graph.py; any entry
+        count, the only form above 2^31): the symmetry check (cached), the CSR by target — the graph itself when symmetric,
+        else its transpose, built once (its HBM checked against the free memory first) —, dinv and the hub-item count (rows
+        longer than hub_chunk entries are cut into items of that length; the first call fixes it).  gcn_prepared() is
+        unaffected.  Cached."""
+        if getattr(self, "_full_plan", None) is not None:
+            return self._full_plan
+        from . import full_graph, ops
+        N = self.num_nodes
+        if getattr(self, "_symmetric", None) is None:
+            flag = ops.csr_symmetric_check(self.rowptr, self.col, N)
+            if flag & 2:
+                raise _lib.GrapesHipError("full_graph_plan: a column id is outside [0, num_nodes)")
+            self._symmetric = flag == 0
+        if self._symmetric:
+            rowptr_t, col_t = self.rowptr, self.col
+        else:
+            need = ops.csr_transpose_bytes(self.nnz, N)
+            full_graph.check_fits(need, {"transpose": need}, self.device, "full_graph_plan (directed graph)")
+            rowptr_t, col_t = ops.csr_transpose(self.rowptr, self.col, N)
+        self._full_plan = ops.LargeGraphPlan(rowptr_t, col_t, N, self._symmetric, hub_chunk)
+        return self._full_plan
+
     def check_status(self, what: str = "hop pipeline"):
         """Host-side check of the device status word (synchronises).  Raises on overflow/bad ids."""
         s = int(self.status.item())

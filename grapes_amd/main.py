@@ -100,9 +100,13 @@ def synthetic_data(name: str, seed: int = 0, device="cuda") -> SimpleNamespace:
         raise ValueError(f"unknown dataset {name!r}: synthetic stand-ins exist for {sorted(synth.CONFIGS)} "
                          "(or pass module:function)")
     N, deg, maxdeg, F, C, *_ = synth.CONFIGS[key]
-    rowptr, col = synth.synth_graph_device(N, deg, maxdeg, seed=seed, device=device)
     gen = torch.Generator(device=device); gen.manual_seed(seed + 1)
-    x = torch.randn(N, F, device=device, generator=gen)
+    if N > (1 << 26):     # papers100M: chunked endpoint draws + the library's CSR ingest, features in row chunks (as bench.py)
+        rowptr, col = synth.synth_graph_device_chunked(N, deg, maxdeg, seed=seed, device=device)
+        x = synth.randn_rows_(torch.empty(N, F, device=device), generator=gen)
+    else:
+        rowptr, col = synth.synth_graph_device(N, deg, maxdeg, seed=seed, device=device)
+        x = torch.randn(N, F, device=device, generator=gen)
     y = torch.randint(0, C, (N,), device=device, generator=gen)
     perm = torch.randperm(N, device=device, generator=gen)
     ftr, fva = (0.08, 0.02) if key == "products" else (0.10, 0.05)

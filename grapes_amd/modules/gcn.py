@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import math
 from collections import OrderedDict
-from typing import Union
+from typing import Optional, Union
 
 import torch
 
@@ -15,7 +15,7 @@ from .._lib import diag_switch as _sw      # A/B switches: the default unless GR
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ops
+from .. import full_graph, ops
 
 _PREP_CACHE: "OrderedDict[int, tuple]" = OrderedDict()
 _PREP_CACHE_SIZE = 16
@@ -46,6 +46,16 @@ def prepare_edges(edge_index, n: int) -> ops.PreparedGraph:
     while len(_PREP_CACHE) > _PREP_CACHE_SIZE:
         _PREP_CACHE.popitem(last=False)
     return prep
+
+
+def _large(edge_index, large_graph: Optional[bool]) -> bool:
+    """True when a whole-graph call goes through full_graph.py; with autograd on such a graph it raises."""
+    if not hasattr(edge_index, "full_graph_plan") or not full_graph.use_large_path(edge_index, large_graph):
+        return False
+    if torch.is_grad_enabled():
+        raise ValueError("full-graph training over a graph with 2^31 or more entries is not built: the full-graph pass there "
+                         "is inference only (call it under torch.no_grad() / torch.inference_mode())")
+    return True
 
 
 def clear_prepare_cache():
@@ -101,9 +111,11 @@ class GCNConv(nn.Module):
             self.lin.weight.uniform_(-a, a)
             self.bias.zero_()
 
-    def forward(self, x, edge_index, relu: bool = False):
+    def forward(self, x, edge_index, relu: bool = False, large_graph: Optional[bool] = None):
         if not x.is_cuda:
             raise ops._lib.GrapesHipError("GCNConv input must be a cuda tensor (grapes_amd has no CPU path)")
+        if _large(edge_index, large_graph):                    # a DeviceGraph with 2^31+ entries (or forced): full_graph.py
+            return full_graph.conv_forward(self, x, edge_index, relu)
         x = x.contiguous()
         if x.dtype != torch.float32:
             x = x.float()
@@ -207,7 +219,11 @@ class GCN(nn.Module):
             return _PhiloxDropoutFn.apply(x, float(self.dropout), seed, offset)
         return F.dropout(x, p=self.dropout, training=self.training)
 
-    def forward(self, x: torch.Tensor, edge_index: Union[torch.Tensor, "list[torch.Tensor]"]):
+    def forward(self, x: torch.Tensor, edge_index: Union[torch.Tensor, "list[torch.Tensor]"], large_graph: Optional[bool] = None):
+        """large_graph: None = automatic — a DeviceGraph with 2^31 or more entries runs the row-blocked 64-bit pass of
+        full_graph.py (inference only); True forces that pass on any DeviceGraph."""
+        if _large(edge_index, large_graph):                                   # eval.py:50 on papers100M-sized graphs
+            return full_graph.gcn_forward(self, x, edge_index), _memory_allocated_mb()
         layerwise_adjacency = type(edge_index) == list
         # (the reference slices the ModuleList, gcn.py:31: a slice builds a NEW ModuleList on every call — add_module and its
         # hasattr probes, ~0.1 ms per layer of host time; iterate by index instead)

@@ -1717,6 +1717,87 @@ def csr_build(edge_index, num_nodes, status=None):
     return rowptr, col[:k].clone() if k < col.numel() // 2 else col[:k]
 
 
+# ------------------------------------------------------------------------------- full graph above 2^31 entries (N1)
+def _aligned_ws(nbytes: int, device) -> "tuple[torch.Tensor, int]":
+    ws = _tmp(torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device))
+    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256
+
+
+def csr_symmetric_check(rowptr, col, n) -> int:
+    """Device flag of grapes_csr_symmetric_check: 0 = every (r, c), r != c, has (c, r); bit 1 = not symmetric; bit 2 = a bad id.
+    One host read."""
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col")
+    flag = torch.empty(1, dtype=_i32, device=rowptr.device)
+    _lib.check(lib().grapes_csr_symmetric_check(_p(rowptr), _p(col), int(n), _p(flag), _stream()), "csr_symmetric_check")
+    return int(flag.item())
+
+
+def csr_transpose_bytes(nnz: int, n: int) -> int:
+    """HBM the transpose allocates: its rowptr + col and the build's workspace."""
+    return 8 * (n + 1) + 4 * max(nnz, 1) + int(lib().grapes_csr_build_workspace_bytes(nnz, n)) + 256
+
+
+def csr_transpose(rowptr, col, n, status=None):
+    """(rowptr_t int64[N+1], col_t int32[nnz]): the CSR of (c, r) for every stored (r, c), rows ascending."""
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(status, _i32, "status", True)
+    dev, nnz = rowptr.device, col.numel()
+    rowptr_t = torch.empty(n + 1, dtype=_i64, device=dev)
+    col_t = torch.empty(max(nnz, 1), dtype=_i32, device=dev)
+    ws, base = _aligned_ws(lib().grapes_csr_build_workspace_bytes(nnz, n), dev)
+    _lib.check(lib().grapes_csr_transpose(_p(rowptr), _p(col), nnz, int(n), _p(rowptr_t), _p(col_t), base, _p(status), _stream()),
+               "csr_transpose")
+    del ws
+    return rowptr_t, col_t
+
+
+class LargeGraphPlan:
+    """The by-target CSR, dinv and hub-item count of a whole graph for full-batch message passing with 64-bit offsets
+    (DeviceGraph.full_graph_plan): rowptr_t / col_t are the graph's own arrays when it is symmetric, else its transpose."""
+
+    __slots__ = ("n", "rowptr_t", "col_t", "dinv", "chunk", "item_cap", "symmetric")
+
+    def __init__(self, rowptr_t, col_t, n, symmetric, chunk=1024):
+        """chunk: rows with more entries are cut into work items of this many entries (a multiple of 64)."""
+        _chk(rowptr_t, _i64, "rowptr_t"); _chk(col_t, _i32, "col_t")
+        self.n, self.rowptr_t, self.col_t, self.symmetric, self.chunk = int(n), rowptr_t, col_t, bool(symmetric), int(chunk)
+        self.dinv = torch.empty(max(self.n, 1), dtype=_f32, device=rowptr_t.device)
+        d_items = torch.empty(1, dtype=_i64, device=rowptr_t.device)
+        _lib.check(lib().grapes_gcn_large_prepare(_p(rowptr_t), _p(col_t), self.n, self.chunk, _p(self.dinv), _p(d_items), _stream()),
+                   "gcn_large_prepare")
+        self.item_cap = int(d_items.item())
+        if self.item_cap >= 2 ** 31:
+            raise ValueError("full_graph_plan: more than 2^31 hub-row work items")
+
+
+def gcn_large_aggregate_workspace_bytes(plan: LargeGraphPlan, m: int, f: int) -> int:
+    return int(lib().grapes_gcn_large_aggregate_workspace_bytes(int(m), plan.item_cap, int(f))) + 256
+
+
+def gcn_large_aggregate(h, plan: LargeGraphPlan, prescaled: bool, r0=0, m=None, rows=None, bias=None, relu=False, out=None,
+                        status=None):
+    """out[i] = Â h [row i] + bias (+ReLU) for the rows r0 .. r0+m-1, or for rows[i] (int32): the gather-SpMM with 64-bit row
+    offsets.  h [N, ldh] with ldh % 4 == 0 (the width f = h.shape[1] must be a multiple of 4: callers pad), out [m, f]."""
+    _chk(h, _f32, "h"); _chk(bias, _f32, "bias", True); _chk(rows, _i32, "rows", True); _chk(status, _i32, "status", True)
+    n, f = h.shape
+    if n != plan.n:
+        raise ValueError("gcn_large_aggregate: h must hold every node's row")
+    if rows is not None:
+        m = rows.numel()
+    elif m is None or r0 < 0 or r0 + m > n:
+        raise ValueError("gcn_large_aggregate: row range outside the graph")
+    if out is None:
+        out = torch.empty((m, f), dtype=_f32, device=h.device)
+    elif out.shape[0] < m or out.shape[1] != f or out.stride(1) != 1:
+        raise ValueError("gcn_large_aggregate: out must be [m, f] with unit column stride")
+    ws, base = _aligned_ws(lib().grapes_gcn_large_aggregate_workspace_bytes(m, plan.item_cap, f), h.device)
+    _lib.check(lib().grapes_gcn_large_aggregate(_p(h), h.stride(0), _p(plan.rowptr_t), _p(plan.col_t), _p(plan.dinv),
+                                                1 if prescaled else 0, int(r0), _p(rows), int(m), int(f), _p(bias),
+                                                1 if relu else 0, _p(out), out.stride(0), plan.chunk, plan.item_cap, base, _p(status),
+                                                _stream()), "gcn_large_aggregate")
+    del ws
+    return out
+
+
 # ------------------------------------------------------------------------------- 1-D partition exchange (§8e)
 def exchange_pack_query(ids32, d_n, cap, query):
     """query[cap + 1] <- [ids | padding | live count] in one launch."""

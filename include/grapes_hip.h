@@ -46,7 +46,8 @@ extern "C" {
  * grapes_linear_bwd_weight_bits_multi / _pair (-> _multi_cols / _pair_cols with dw_cols = 0), grapes_sampler_head_bwd_multi (-> _multi_phase, phase 0),
  * grapes_gate_bits_words;
  * 301: grapes_linear_fwd_row_scaled (full-batch inference: the dinv row scaling in the transform GEMM's epilogue);
- * 302: grapes_eval_predict. */
+ * 302: grapes_eval_predict; added within 302 (no signature of an earlier entry point changed): the full-batch path above 2^31
+ * entries — grapes_csr_symmetric_check, grapes_csr_transpose, grapes_gcn_large_prepare, grapes_gcn_large_aggregate(_workspace_bytes). */
 #define GRAPES_ABI_VERSION 302
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1006,6 +1007,40 @@ size_t grapes_csr_build_workspace_bytes(int64_t num_edges, int32_t num_nodes);
 int grapes_csr_build(const int64_t* edge_src, const int64_t* edge_dst, int64_t num_edges, int32_t num_nodes,
                      int64_t* rowptr, int32_t* col, int64_t* d_nnz, void* workspace, int32_t* status,
                      grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ N1 above 2^31 entries: full-batch message passing over a
+ * graph whose CSR needs 64-bit offsets (ogbn-papers100M: 3.2e9 symmetrised entries).  The int32 forms above
+ * (grapes_gcn_prepare_from_csr, grapes_gcn_aggregate_fwd[_prescaled]) stay the path below 2^31; these read the graph's own
+ * int64 rowptr / int32 col in place (no edge-list copy).  Replace, for such graphs: eval.py:47-70 (evaluate(full_batch=True))
+ * and modules/gcn.py:32,36 (the GCNConv calls of GCN.forward on the whole adjacency, inference only).
+ *
+ * Symmetry check: *d_flag = 0 when every stored (r, c) with r != c has a stored (c, r) (binary search; columns ascend), bit 1
+ * when one is missing, bit 2 when a column id is outside [0, n).  The CSR by target is then the graph itself. */
+int grapes_csr_symmetric_check(const int64_t* rowptr, const int32_t* col, int32_t n, int32_t* d_flag, grapes_stream_t stream);
+/* Transpose (r, c) -> (c, r) of a device CSR (the CSR by target of a directed graph): counting placement + the per-row sort of
+ * grapes_csr_build (rows ascend, duplicates collapse).  rowptr_t int64[N+1], col_t int32[capacity nnz]; workspace:
+ * grapes_csr_build_workspace_bytes(nnz, N), 256-byte aligned.  Not for use inside a stream capture. */
+int grapes_csr_transpose(const int64_t* rowptr, const int32_t* col, int64_t nnz, int32_t num_nodes, int64_t* rowptr_t,
+                         int32_t* col_t, void* workspace, int32_t* status, grapes_stream_t stream);
+/* gcn_norm over the CSR by target (rowptr_t int64, col_t int32): dinv[r] = (1 + #entries of row r other than r)^-1/2 (stored
+ * self-loops are skipped, the unit loop added: PyG's self-loop replacement) and *d_items (int64, device) = the number of
+ * hub-row work items of the whole graph — rows with more than `chunk` entries (a multiple of 64), one item per `chunk` —
+ * the item_cap that bounds every grapes_gcn_large_aggregate launch over distinct rows with the same chunk. */
+int grapes_gcn_large_prepare(const int64_t* rowptr_t, const int32_t* col_t, int32_t n, int32_t chunk, float* dinv,
+                             int64_t* d_items, grapes_stream_t stream);
+/* out[i, :f] = dinv[r] (sum_{s in row r, s != r} w_s h[s] + w_r h[r]) + bias (+ReLU), r = rows ? rows[i] : r0 + i, i < m:
+ * prescaled != 0 — h's rows are pre-scaled by their own dinv (w = 1, as grapes_gcn_aggregate_fwd_prescaled); else w_s = dinv[s].
+ * One wavefront per row; rows with more than `chunk` entries are cut into items (one workgroup each, partials in `workspace`)
+ * added in chunk order: two runs give bit-identical output.  f % 4 == 0, f <= 4096; ldh, ldo (row pitches in floats) >= f and
+ * multiples of 4; h, out, bias 16-byte aligned; bias may be NULL.  item_cap: grapes_gcn_large_prepare's item count (0: every
+ * row by its own wavefront); rows whose items no longer fit below item_cap (only a row list with repeats needs more) are
+ * walked by their own wavefront — same value, another summation order — and raise GRAPES_STATUS_NODE_OVERFLOW in *status
+ * (optional); no item slot is ever left unwritten.  workspace: grapes_gcn_large_aggregate_workspace_bytes, 256-byte aligned. */
+size_t grapes_gcn_large_aggregate_workspace_bytes(int32_t m, int32_t item_cap, int32_t f);
+int grapes_gcn_large_aggregate(const float* h, int64_t ldh, const int64_t* rowptr_t, const int32_t* col_t, const float* dinv,
+                               int32_t prescaled, int32_t r0, const int32_t* rows, int32_t m, int32_t f, const float* bias,
+                               int32_t relu, float* out, int64_t ldo, int32_t chunk, int32_t item_cap, void* workspace,
+                               int32_t* status, grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:
