@@ -66,6 +66,13 @@ SIGNATURES = {
     "grapes_gcn_large_prepare": (I32, [P, P, I32, I32, P, P, P]),
     "grapes_gcn_large_aggregate_workspace_bytes": (C.c_size_t, [I32, I32, I32]),
     "grapes_gcn_large_aggregate": (I32, [P, I64, P, P, P, I32, I32, P, I32, I32, P, I32, P, I64, I32, I32, P, P, P]),
+    "grapes_rowlist_transpose_workspace_bytes": (C.c_size_t, [I64, I32]),
+    "grapes_rowlist_transpose": (I32, [P, P, I32, P, I32, I64, P, P, P, P, P, P, P]),
+    "grapes_rowlist_gather_t_workspace_bytes": (C.c_size_t, [I32, I32, I32]),
+    "grapes_rowlist_gather_t": (I32, [P, I64, P, P, P, P, I32, I32, P, I64, I32, I32, P, P, P]),
+    "grapes_dropout_rows": (I32, [P, I64, P, I64, I32, P, I32, I32, I64, F32, U64, U64, P]),
+    "grapes_rowlist_loss_workspace_bytes": (C.c_size_t, [I32, I32]),
+    "grapes_rowlist_loss": (I32, [P, I64, I32, P, I32, P, P, P, F32, U64, U64, P, I64, I32, P, P, P, P, P]),
     "grapes_kernel_clock_enable": (I32, [P, I64]),
     "grapes_kernel_clock_launches": (I32, []),
     "grapes_kernel_clock_entry": (I32, [I32, P, P, P]),

@@ -428,3 +428,114 @@ extern "C" int grapes_csr_transpose(const int64_t* rowptr, const int32_t* col, i
     GRAPES_LAUNCH_CHECK();
     return csr_sort_place(nnz, num_nodes, N, col_raw, rowptr_raw, udeg, tiles, long_rows, n_long, long_cap, rowptr_t, col_t, status, s);
 }
+
+// ---------------------------------------------------------------------------------------------- row-list transpose
+// The backward pass of full-batch training (full-batch.py:100-105, loss over the train rows R): the gradient of Â T on the rows
+// R reaches T only on the sources of R's CSR-by-target entries.  For rows[p] = r (ascending, distinct) the entries (s, p) are
+// every stored s of row r other than r itself, plus (r, p) — PyG's self-loop replacement, as lg_prepare_k counts it.  The
+// same counting placement and per-row sort as the transpose above give, per source, its positions p in ascending order;
+// the sources that have any are then compacted (a flag scan).
+__global__ __launch_bounds__(256) void rl_t_hist_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N,
+                                                   const int32_t* __restrict__ rows, int m, unsigned* __restrict__ deg,
+                                                   int32_t* status) {
+    const int lane = threadIdx.x & 63;
+    const long long nw = ((long long)gridDim.x * blockDim.x) >> 6;
+    bool bad = false;
+    for (long long p = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; p < m; p += nw) {
+        const int r = rows[p];
+        if (r < 0 || r >= N) { bad = true; continue; }
+        if (lane == 0) atomicAdd(&deg[r], 1u);
+        for (long long j = rowptr[r] + lane; j < rowptr[r + 1]; j += 64) {
+            const int c = col[j];
+            if (c == r) continue;
+            if (c < 0 || c >= N) { bad = true; continue; }
+            atomicAdd(&deg[c], 1u);
+        }
+    }
+    if (bad && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+}
+__global__ __launch_bounds__(256) void rl_t_scatter_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N,
+                                                      const int32_t* __restrict__ rows, int m, const int64_t* __restrict__ rowptr_raw,
+                                                      unsigned* __restrict__ cursor, int32_t* __restrict__ col_raw) {
+    const int lane = threadIdx.x & 63;
+    const long long nw = ((long long)gridDim.x * blockDim.x) >> 6;
+    for (long long p = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6; p < m; p += nw) {
+        const int r = rows[p];
+        if (r < 0 || r >= N) continue;
+        if (lane == 0) { const unsigned q = atomicAdd(&cursor[r], 1u); col_raw[rowptr_raw[r] + q] = (int32_t)p; }
+        for (long long j = rowptr[r] + lane; j < rowptr[r + 1]; j += 64) {
+            const int c = col[j];
+            if (c == r || c < 0 || c >= N) continue;
+            const unsigned q = atomicAdd(&cursor[c], 1u);
+            col_raw[rowptr_raw[c] + q] = (int32_t)p;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void rl_t_flags_k(const unsigned* __restrict__ udeg, int N, unsigned* __restrict__ flag) {
+    for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < N; s += (long long)gridDim.x * blockDim.x)
+        flag[s] = udeg[s] ? 1u : 0u;
+}
+__global__ __launch_bounds__(256) void rl_t_compact_k(const unsigned* __restrict__ udeg, const int64_t* __restrict__ idx,
+                                                      const int64_t* __restrict__ rowptr_full, int N, int32_t* __restrict__ srcs,
+                                                      int64_t* __restrict__ src_off) {
+    for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < N; s += (long long)gridDim.x * blockDim.x)
+        if (udeg[s]) { const long long k = idx[s]; srcs[k] = (int32_t)s; src_off[k] = rowptr_full[s]; }
+}
+// counts[0] = |S| (the scan's total), counts[1] = entries; src_off[|S|] = entries
+__global__ void rl_t_tail_k(const int64_t* __restrict__ rowptr_full, int N, int64_t* __restrict__ counts, int64_t* __restrict__ src_off) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) { counts[1] = rowptr_full[N]; src_off[counts[0]] = rowptr_full[N]; }
+}
+
+extern "C" size_t grapes_rowlist_transpose_workspace_bytes(int64_t e_cap, int32_t num_nodes) {
+    const size_t N = (size_t)(num_nodes > 0 ? num_nodes : 1);
+    return grapes_csr_build_workspace_bytes(e_cap, num_nodes) + al256((N + 1) * 8) /* rowptr by source, all N */ + 256;
+}
+
+extern "C" int grapes_rowlist_transpose(const int64_t* rowptr_t, const int32_t* col_t, int32_t num_nodes, const int32_t* rows,
+                                        int32_t m, int64_t e_cap, int32_t* srcs, int64_t* src_off, int32_t* pos, int64_t* counts,
+                                        void* workspace, int32_t* status, grapes_stream_t stream) {
+    if (num_nodes <= 0 || m < 0 || m > num_nodes || e_cap < (int64_t)m || !rowptr_t || !col_t || !srcs || !src_off || !counts ||
+        !workspace || (m > 0 && (!rows || !pos)))
+        return GRAPES_EINVAL;
+    if (((uintptr_t)workspace & 255) != 0) return GRAPES_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t E = (size_t)(e_cap > 0 ? e_cap : 1), N = (size_t)num_nodes;
+    char* w = (char*)workspace;
+    int32_t* col_raw = (int32_t*)w; w += al256(E * 4);
+    int64_t* rowptr_raw = (int64_t*)w; w += al256((N + 1) * 8);
+    unsigned* deg = (unsigned*)w; w += al256(N * 4);
+    unsigned* udeg = (unsigned*)w; w += al256(N * 4);
+    const size_t ntiles = (N + SCAN_TILE - 1) / SCAN_TILE + 1;
+    int64_t* tiles = (int64_t*)w; w += al256(ntiles * 8);
+    const int long_cap = (int)(E / CSR_WIN + 2);
+    int32_t* long_rows = (int32_t*)w; w += al256((size_t)long_cap * 4);
+    int32_t* n_long = (int32_t*)w; w += 512;
+    int64_t* rowptr_full = (int64_t*)w;
+    hipError_t e;
+    if ((e = grapes_zero_async(deg, N * 4, s)) != hipSuccess) return (int)e;
+    if ((e = grapes_zero_async(udeg, N * 4, s)) != hipSuccess) return (int)e;
+    if ((e = grapes_zero_async(n_long, 64, s)) != hipSuccess) return (int)e;
+    int grid = grapes_div_up((int64_t)(m > 0 ? m : 1), 4); if (grid > 65536) grid = 65536;
+    hipLaunchKernelGGL(rl_t_hist_k, dim3(grid), dim3(256), 0, s, rowptr_t, col_t, num_nodes, rows, m, deg, status);
+    GRAPES_LAUNCH_CHECK();
+    int rc = scan_u32_to_i64(deg, (long long)N, rowptr_raw, rowptr_raw + N, tiles, s);
+    if (rc) return rc;
+    // (entries beyond e_cap cannot be placed: the caller sizes e_cap as sum over rows of (row length + 1), an upper bound)
+    if ((e = grapes_zero_async(deg, N * 4, s)) != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(rl_t_scatter_k, dim3(grid), dim3(256), 0, s, rowptr_t, col_t, num_nodes, rows, m, (const int64_t*)rowptr_raw,
+                       deg, col_raw);
+    GRAPES_LAUNCH_CHECK();
+    rc = csr_sort_place(e_cap, num_nodes, N, col_raw, rowptr_raw, udeg, tiles, long_rows, n_long, long_cap, rowptr_full, pos, status, s);
+    if (rc) return rc;
+    int ngrid = grapes_div_up((int64_t)N, 256); if (ngrid > 65536) ngrid = 65536;
+    hipLaunchKernelGGL(rl_t_flags_k, dim3(ngrid), dim3(256), 0, s, (const unsigned*)udeg, num_nodes, deg);
+    GRAPES_LAUNCH_CHECK();
+    rc = scan_u32_to_i64(deg, (long long)N, rowptr_raw, counts, tiles, s);          // rowptr_raw: free again, now idx[s]
+    if (rc) return rc;
+    hipLaunchKernelGGL(rl_t_compact_k, dim3(ngrid), dim3(256), 0, s, (const unsigned*)udeg, (const int64_t*)rowptr_raw,
+                       (const int64_t*)rowptr_full, num_nodes, srcs, src_off);
+    GRAPES_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rl_t_tail_k, dim3(1), dim3(64), 0, s, (const int64_t*)rowptr_full, num_nodes, counts, src_off);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}

@@ -643,3 +643,153 @@ extern "C" int grapes_adam_step_slabs(const void* d_desc, int32_t n_tensors, int
     }
     return adam_launch(d_desc, n_tensors, max_numel, d_ticket, sb, stream);
 }
+
+// ---------------------------------------------------------------------------------------------- full-batch training loss
+// full-batch.py:101-104 on a row list of any length (M <= 2^31 - 1; grapes_classifier_loss stops at 4096 rows):
+//   Zd = dropout(Z) on the rows (modules/gcn.py:37; keep iff philox_uniform(seed, offset, r * C + c) >= p, the mask of
+//        grapes_dropout_fwd on the whole N x C logits), loss = mean CrossEntropy (int64 labels) or mean BCEWithLogits (fp32
+//        [N, C] labels) over the rows,
+//   dZ = d loss / d Z (dropout's backward applied),  g[i] = dinv[rows[i]] * dZ[i]  (columns C .. ldg zeroed),  dcol = sum_i dZ[i].
+// Workgroup b takes rows [b * RL_ROWS, ...); its wavefronts take every 4th row of that range and keep their column sums and
+// row losses in registers, combined in wavefront order, then one workgroup per column adds the workgroups' partials in a
+// fixed tree: no float atomics, two calls give bit-identical results.  z and g may be the same array (in place).
+#define RL_ROWS 256
+#define RL_MAX_KC 16                                        // C <= 64 * RL_MAX_KC
+#include "philox.h"
+
+__global__ __launch_bounds__(256) void rl_loss_rows_k(const float* z, long long ldz, int C, int ldg_cols, const int32_t* __restrict__ rows,
+                                                      int M, const int64_t* __restrict__ labels, const float* __restrict__ labels_f,
+                                                      const float* __restrict__ dinv, float p, uint64_t seed, uint64_t offset,
+                                                      float* g, long long ldg, float* __restrict__ part_col,
+                                                      double* __restrict__ part_loss, int32_t* status) {
+    __shared__ float scol[4][64 * RL_MAX_KC];
+    __shared__ double sloss[4];
+    const int lane = lane_id(), wid = threadIdx.x >> 6;
+    const int KC = (ldg_cols + 63) >> 6;
+    const bool multi = labels_f != nullptr;
+    const float inv = multi ? 1.0f / ((float)M * (float)C) : 1.0f / (float)M;
+    const float sc = p < 1.0f ? 1.0f / (1.0f - p) : 0.f;
+    float acc[RL_MAX_KC];
+#pragma unroll
+    for (int k = 0; k < RL_MAX_KC; ++k) acc[k] = 0.f;
+    double lacc = 0.0;
+    const long long i_end = ((long long)blockIdx.x + 1) * RL_ROWS < M ? ((long long)blockIdx.x + 1) * RL_ROWS : M;
+    for (long long i = (long long)blockIdx.x * RL_ROWS + wid; i < i_end; i += 4) {
+        const long long r = rows[i];
+        const float* zr = z + i * ldz;
+        float zd[RL_MAX_KC]; bool kp[RL_MAX_KC];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < RL_MAX_KC; ++k) {
+            const int c = lane + 64 * k;
+            zd[k] = 0.f; kp[k] = false;
+            if (k < KC && c < C) {
+                kp[k] = p > 0.f ? philox_uniform_at(seed, offset, r * C + c) >= p : true;
+                const float v = zr[c];
+                zd[k] = p > 0.f ? (kp[k] ? v * sc : 0.f) : v;
+                mx = fmaxf(mx, zd[k]);
+            }
+        }
+        float dz[RL_MAX_KC];
+        float lrow;
+        if (!multi) {
+            const long long y = labels[r];
+            if ((y < 0 || y >= C) && lane == 0 && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+            mx = wave_max(mx);
+            float se = 0.f;
+#pragma unroll
+            for (int k = 0; k < RL_MAX_KC; ++k) { const int c = lane + 64 * k; if (k < KC && c < C) se += expf(zd[k] - mx); }
+            se = wave_sum(se);
+            const float lse = mx + logf(se);
+            float ly = 0.f;
+#pragma unroll
+            for (int k = 0; k < RL_MAX_KC; ++k) {
+                const int c = lane + 64 * k;
+                dz[k] = 0.f;
+                if (k < KC && c < C) {
+                    const float t = c == y ? 1.0f : 0.f;
+                    if (c == y) ly = lse - zd[k];
+                    dz[k] = (expf(zd[k] - lse) - t) * inv;
+                }
+            }
+            lrow = wave_sum(ly);
+        } else {
+            float l = 0.f;
+#pragma unroll
+            for (int k = 0; k < RL_MAX_KC; ++k) {
+                const int c = lane + 64 * k;
+                dz[k] = 0.f;
+                if (k < KC && c < C) {
+                    const float x = zd[k], t = labels_f[r * C + c];
+                    l += fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
+                    dz[k] = (1.0f / (1.0f + expf(-x)) - t) * inv;
+                }
+            }
+            lrow = wave_sum(l);
+        }
+        const float ds = dinv[r];
+#pragma unroll
+        for (int k = 0; k < RL_MAX_KC; ++k) {
+            const int c = lane + 64 * k;
+            if (k < KC && c < ldg_cols) {
+                const float d = c < C && kp[k] ? (p > 0.f ? dz[k] * sc : dz[k]) : 0.f;
+                acc[k] += d;
+                g[i * ldg + c] = ds * d;
+            }
+        }
+        lacc += (double)lrow;
+    }
+#pragma unroll
+    for (int k = 0; k < RL_MAX_KC; ++k) if (k < KC) scol[wid][lane + 64 * k] = acc[k];
+    if (lane == 0) sloss[wid] = lacc;
+    __syncthreads();
+    for (int c = threadIdx.x; c < ldg_cols; c += blockDim.x)
+        part_col[(long long)blockIdx.x * ldg_cols + c] = ((scol[0][c] + scol[1][c]) + scol[2][c]) + scol[3][c];
+    if (threadIdx.x == 0) part_loss[blockIdx.x] = ((sloss[0] + sloss[1]) + sloss[2]) + sloss[3];
+}
+
+// workgroup c < cols: dcol[c] = sum over b of part_col[b][c]; workgroup `cols`: *loss = sum of part_loss / (M or M C)
+__global__ __launch_bounds__(256) void rl_loss_reduce_k(const float* __restrict__ part_col, const double* __restrict__ part_loss,
+                                                        int nblk, int cols, double denom, float* __restrict__ dcol,
+                                                        float* __restrict__ loss_out) {
+    __shared__ double red[4];
+    const int c = blockIdx.x;
+    double acc = 0.0;
+    if (c < cols) { for (int b = threadIdx.x; b < nblk; b += blockDim.x) acc += (double)part_col[(long long)b * cols + c]; }
+    else { for (int b = threadIdx.x; b < nblk; b += blockDim.x) acc += part_loss[b]; }
+    acc = wave_sum_d(acc);
+    if (lane_id() == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double t = ((red[0] + red[1]) + red[2]) + red[3];
+        if (c < cols) dcol[c] = (float)t; else *loss_out = (float)(t / denom);
+    }
+}
+
+extern "C" size_t grapes_rowlist_loss_workspace_bytes(int32_t m, int32_t ldg_cols) {
+    const size_t nblk = (size_t)((m > 0 ? m : 1) + RL_ROWS - 1) / RL_ROWS;
+    return ((nblk * (size_t)(ldg_cols > 0 ? ldg_cols : 1) * 4 + 255) & ~(size_t)255) + nblk * 8 + 256;
+}
+
+extern "C" int grapes_rowlist_loss(const float* z, int64_t ldz, int32_t C, const int32_t* rows, int32_t m, const int64_t* labels,
+                                   const float* labels_f, const float* dinv, float p, uint64_t philox_seed, uint64_t philox_offset,
+                                   float* g, int64_t ldg, int32_t ldg_cols, float* dcol, float* loss_out, void* workspace,
+                                   int32_t* status, grapes_stream_t stream) {
+    if (C <= 0 || m <= 0 || ldg_cols < C || ldg_cols > 64 * RL_MAX_KC || ldz < C || ldg < ldg_cols || !(p >= 0.f && p <= 1.f))
+        return GRAPES_EINVAL;
+    if (!z || !rows || !dinv || !g || !dcol || !loss_out || !workspace || ((labels == nullptr) == (labels_f == nullptr)))
+        return GRAPES_EINVAL;
+    if ((uintptr_t)workspace & 255) return GRAPES_EALIGN;
+    const int nblk = (m + RL_ROWS - 1) / RL_ROWS;
+    float* part_col = (float*)workspace;
+    double* part_loss = (double*)((char*)workspace + (((size_t)nblk * ldg_cols * 4 + 255) & ~(size_t)255));
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(rl_loss_rows_k, dim3(nblk), dim3(256), 0, s, z, (long long)ldz, C, ldg_cols, rows, m, labels, labels_f, dinv,
+                       p, philox_seed, philox_offset, g, (long long)ldg, part_col, part_loss, status);
+    GRAPES_LAUNCH_CHECK();
+    const double denom = labels_f ? (double)m * (double)C : (double)m;
+    hipLaunchKernelGGL(rl_loss_reduce_k, dim3(ldg_cols + 1), dim3(256), 0, s, (const float*)part_col, (const double*)part_loss, nblk,
+                       ldg_cols, denom, dcol, loss_out);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}

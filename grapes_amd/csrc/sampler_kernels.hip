@@ -7,6 +7,7 @@
 // keys — and therefore the sampled index sets — are bit-identical on the CPU oracle and on gfx950.
 #include "common.h"
 #include "narrow.h"
+#include "philox.h"
 GRAPES_STAMP_SETTER(grapes_stamp_set_sampler)
 #include <cstdlib>
 
@@ -114,30 +115,6 @@ __device__ __forceinline__ uint32_t order_key_prob(float p) {
     return order_key(p);
 }
 __device__ __forceinline__ uint32_t order_key_of(float key, int mode) { return mode == 1 ? order_key_prob(key) : order_key(key); }
-
-// ---------------------------------------------------------------------------- Philox4x32-10
-struct Philox4 { uint32_t v[4]; };
-__device__ __forceinline__ Philox4 philox4x32_10(uint64_t ctr, uint64_t seed) {
-    uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0u, c3 = 0u;
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
-        const uint32_t n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        const uint32_t n3 = (uint32_t)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    Philox4 r; r.v[0] = c0; r.v[1] = c1; r.v[2] = c2; r.v[3] = c3;
-    return r;
-}
-__device__ __forceinline__ float philox_uniform_at(uint64_t seed, uint64_t offset, long long i) {
-    const Philox4 p = philox4x32_10(offset + (uint64_t)(i >> 2), seed);
-    return (float)(p.v[i & 3] >> 8) * 5.9604644775390625e-08f;   // 2^-24
-}
 
 __global__ void philox_uniform_k(float* __restrict__ out, long long n, uint64_t seed, uint64_t offset) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;

@@ -10,6 +10,7 @@
 //                     adds in chunk order.  Every sum has a fixed order: two runs are bit-identical.
 // All entry offsets and row addresses are 64-bit (col is 12.8 GB and X 57 GB at papers100M: no 32-bit buffer offset covers them).
 #include "common.h"
+#include "philox.h"
 
 // Hub rows: rows with more than `chunk` entries (a multiple of 64; 1024 from Python by default) are split into items of `chunk`.
 
@@ -64,13 +65,19 @@ struct LgArgs {
     int chunk;                                                      // hub-row item length (entries)
     const int32_t* items; const unsigned long long* d_items; int item_cap;      // items[2 * it] = launch row index i, [2 * it + 1] = chunk
     const int32_t* item_start; float* partials;                     // item_start[i]: first item of hub row i (or -1)
+    const int32_t* srcs;                                            // LG_TRANSPOSED: source id of structure row i (its dinv)
 };
+
+// Forms of the gather: LG_WEIGHTED w_s = dinv[s] dinv[r] and self term dinv[r]^2 h[r]; LG_PRESCALED rows of h pre-scaled
+// (w = 1, dinv[r] (sum + h[r])); LG_TRANSPOSED the row-list transpose of the backward pass (rl_t_*: rowptr = per-source
+// offsets, col = positions into h = G, self entries stored): no entry skipped, no self term, out = dinv[srcs[i]] * sum.
+enum { LG_WEIGHTED = 0, LG_PRESCALED = 1, LG_TRANSPOSED = 2 };
 
 __device__ __forceinline__ int lg_row(const LgArgs& a, int i) { return a.rows ? a.rows[i] : a.r0 + i; }
 
 // sum over entries [beg, end) of row `row` (self-loop skipped) of w_s * h[s, f .. f+4): slot `slot` of `slots` takes every
-// slots-th entry, U entries in flight; PRE: rows pre-scaled (w_s = 1), else w_s = dinv[s] * dc
-template <int U, bool PRE>
+// slots-th entry, U entries in flight; MODE: see LG_WEIGHTED / LG_PRESCALED / LG_TRANSPOSED
+template <int U, int MODE>
 __device__ __forceinline__ float4 lg_accumulate(const LgArgs& a, int row, long long beg, long long end, float dc, int f, int slot,
                                                 int slots, bool live) {
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -80,8 +87,8 @@ __device__ __forceinline__ float4 lg_accumulate(const LgArgs& a, int row, long l
         for (int u = 0; u < U; ++u) { const long long jj = j + (long long)u * slots; s[u] = a.col[jj < end ? jj : end - 1]; }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            const bool in = j + (long long)u * slots < end && s[u] != row;
-            w[u] = in ? (PRE ? 1.0f : a.dinv[s[u]] * dc) : 0.f;
+            const bool in = j + (long long)u * slots < end && (MODE == LG_TRANSPOSED || s[u] != row);
+            w[u] = in ? (MODE != LG_WEIGHTED ? 1.0f : a.dinv[s[u]] * dc) : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
@@ -128,7 +135,7 @@ __global__ __launch_bounds__(256) void lg_items_k(LgArgs a, int32_t* __restrict_
 }
 
 // one workgroup per item: 4 wavefronts take a quarter of the chunk each, their sums are added in wavefront order
-template <int LPR, bool PRE>
+template <int LPR, int MODE>
 __global__ __launch_bounds__(256) void lg_chunks_k(LgArgs a) {
     constexpr int U = LPR >= 64 ? 8 : 4;
     constexpr int SLOTS = 64 / LPR;
@@ -146,11 +153,11 @@ __global__ __launch_bounds__(256) void lg_chunks_k(LgArgs a) {
         const long long end = beg + a.chunk < rend ? beg + a.chunk : rend;
         const long long wb = beg + (long long)wid * (a.chunk / 4);
         const long long we = wb + a.chunk / 4 < end ? wb + a.chunk / 4 : end;
-        const float dc = a.dinv[row];
+        const float dc = MODE == LG_WEIGHTED ? a.dinv[row] : 0.f;
         for (int fb = 0; fb < a.f; fb += 4 * LPR) {
             const int f = fb + 4 * sub;
             const bool live = f < a.f;
-            const float4 acc = lg_combine_slots<LPR>(lg_accumulate<U, PRE>(a, row, wb, we, dc, f, slot, SLOTS, live));
+            const float4 acc = lg_combine_slots<LPR>(lg_accumulate<U, MODE>(a, row, wb, we, dc, f, slot, SLOTS, live));
             if (slot == 0) part[wid][sub] = acc;
             __syncthreads();
             if (wid == 0 && slot == 0 && live) {
@@ -163,7 +170,7 @@ __global__ __launch_bounds__(256) void lg_chunks_k(LgArgs a) {
     }
 }
 
-template <int LPR, bool PRE>
+template <int LPR, int MODE>
 __global__ __launch_bounds__(256) void lg_aggregate_k(LgArgs a) {
     constexpr int U = LPR >= 64 ? 8 : 4;
     constexpr int SLOTS = 64 / LPR;
@@ -174,14 +181,14 @@ __global__ __launch_bounds__(256) void lg_aggregate_k(LgArgs a) {
     for (int i = wave; i < a.m; i += nwaves) {
         const int row = lg_row(a, i);
         const long long beg = a.rowptr[row], end = a.rowptr[row + 1];
-        const float dc = a.dinv[row];
+        const float dc = MODE == LG_TRANSPOSED ? a.dinv[a.srcs[i]] : a.dinv[row];
         const int it0 = (end - beg > a.chunk && a.item_start) ? a.item_start[i] : -1;
         for (int fb = 0; fb < a.f; fb += 4 * LPR) {
             const int f = fb + 4 * sub;
             const bool live = f < a.f;
             float4 acc;
             if (it0 < 0) {
-                acc = lg_combine_slots<LPR>(lg_accumulate<U, PRE>(a, row, beg, end, dc, f, slot, SLOTS, live));
+                acc = lg_combine_slots<LPR>(lg_accumulate<U, MODE>(a, row, beg, end, dc, f, slot, SLOTS, live));
             } else {                                                         // the row's item partials, in chunk order
                 acc = make_float4(0.f, 0.f, 0.f, 0.f);
                 const int nc = (int)((end - beg + a.chunk - 1) / a.chunk);
@@ -191,10 +198,13 @@ __global__ __launch_bounds__(256) void lg_aggregate_k(LgArgs a) {
                         acc.x += p.x; acc.y += p.y; acc.z += p.z; acc.w += p.w;
                     }
             }
-            if (slot == 0 && live) {
+            if (MODE == LG_TRANSPOSED) {
+                if (slot == 0 && live)
+                    *reinterpret_cast<float4*>(a.out + (long long)i * a.ldo + f) = make_float4(dc * acc.x, dc * acc.y, dc * acc.z, dc * acc.w);
+            } else if (slot == 0 && live) {
                 const float4 sv = *reinterpret_cast<const float4*>(a.h + (long long)row * a.ldh + f);
                 const float w = dc * dc;
-                float4 r = PRE ? make_float4(dc * (acc.x + sv.x), dc * (acc.y + sv.y), dc * (acc.z + sv.z), dc * (acc.w + sv.w))
+                float4 r = MODE == LG_PRESCALED ? make_float4(dc * (acc.x + sv.x), dc * (acc.y + sv.y), dc * (acc.z + sv.z), dc * (acc.w + sv.w))
                                : make_float4(fmaf(w, sv.x, acc.x), fmaf(w, sv.y, acc.y), fmaf(w, sv.z, acc.z), fmaf(w, sv.w, acc.w));
                 if (a.bias) { const float4 b = *reinterpret_cast<const float4*>(a.bias + f); r.x += b.x; r.y += b.y; r.z += b.z; r.w += b.w; }
                 if (a.relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
@@ -204,22 +214,27 @@ __global__ __launch_bounds__(256) void lg_aggregate_k(LgArgs a) {
     }
 }
 
-template <int LPR>
-static int lg_launch(const LgArgs& a, int prescaled, bool with_items, hipStream_t s) {
+template <int LPR, int MODE>
+static int lg_launch_mode(const LgArgs& a, bool with_items, hipStream_t s) {
     if (with_items) {
         int cgrid = a.item_cap < 8192 ? a.item_cap : 8192;
-        if (prescaled) hipLaunchKernelGGL((lg_chunks_k<LPR, true>), dim3(cgrid), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((lg_chunks_k<LPR, false>), dim3(cgrid), dim3(256), 0, s, a);
+        hipLaunchKernelGGL((lg_chunks_k<LPR, MODE>), dim3(cgrid), dim3(256), 0, s, a);
         GRAPES_LAUNCH_CHECK();
     }
     int grid = grapes_div_up(a.m, 4); if (grid > 16384) grid = 16384;
-    if (prescaled) hipLaunchKernelGGL((lg_aggregate_k<LPR, true>), dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((lg_aggregate_k<LPR, false>), dim3(grid), dim3(256), 0, s, a);
+    hipLaunchKernelGGL((lg_aggregate_k<LPR, MODE>), dim3(grid), dim3(256), 0, s, a);
     GRAPES_LAUNCH_CHECK();
     return 0;
 }
+template <int LPR>
+static int lg_launch(const LgArgs& a, int mode, bool with_items, hipStream_t s) {
+    if (mode == LG_TRANSPOSED) return lg_launch_mode<LPR, LG_TRANSPOSED>(a, with_items, s);
+    if (mode == LG_PRESCALED) return lg_launch_mode<LPR, LG_PRESCALED>(a, with_items, s);
+    return lg_launch_mode<LPR, LG_WEIGHTED>(a, with_items, s);
+}
 
 static inline size_t lg_al256(size_t x) { return (x + 255) & ~(size_t)255; }
+static int lg_run(LgArgs a, int mode, void* workspace, int32_t* status, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------- C-ABI
 extern "C" int grapes_gcn_large_prepare(const int64_t* rowptr_t, const int32_t* col_t, int32_t n, int32_t chunk, float* dinv,
@@ -262,9 +277,13 @@ extern "C" int grapes_gcn_large_aggregate(const float* h, int64_t ldh, const int
     if (!h || !rowptr_t || !col_t || !dinv || !out || (item_cap > 0 && !workspace)) return GRAPES_EINVAL;
     if (((uintptr_t)h & 15) || ((uintptr_t)out & 15) || (bias && ((uintptr_t)bias & 15)) || ((uintptr_t)workspace & 255))
         return GRAPES_EALIGN;
-    hipStream_t s = (hipStream_t)stream;
     LgArgs a{h, (long long)ldh, rowptr_t, col_t, dinv, r0, rows, m, f, bias, relu, out, (long long)ldo, chunk,
-             nullptr, nullptr, item_cap, nullptr, nullptr};
+             nullptr, nullptr, item_cap, nullptr, nullptr, nullptr};
+    return lg_run(a, prescaled ? LG_PRESCALED : LG_WEIGHTED, workspace, status, (hipStream_t)stream);
+}
+
+static int lg_run(LgArgs a, int mode, void* workspace, int32_t* status, hipStream_t s) {
+    const int m = a.m, f = a.f, item_cap = a.item_cap;
     const bool with_items = item_cap > 0;
     if (with_items) {
         char* w = (char*)workspace;
@@ -279,11 +298,64 @@ extern "C" int grapes_gcn_large_aggregate(const float* h, int64_t ldh, const int
         GRAPES_LAUNCH_CHECK();
     }
     const int f4 = f >> 2;                                   // lanes per row: the smallest power of two >= f / 4, at most 64
-    if (f4 <= 1) return lg_launch<1>(a, prescaled, with_items, s);
-    if (f4 <= 2) return lg_launch<2>(a, prescaled, with_items, s);
-    if (f4 <= 4) return lg_launch<4>(a, prescaled, with_items, s);
-    if (f4 <= 8) return lg_launch<8>(a, prescaled, with_items, s);
-    if (f4 <= 16) return lg_launch<16>(a, prescaled, with_items, s);
-    if (f4 <= 32) return lg_launch<32>(a, prescaled, with_items, s);
-    return lg_launch<64>(a, prescaled, with_items, s);
+    if (f4 <= 1) return lg_launch<1>(a, mode, with_items, s);
+    if (f4 <= 2) return lg_launch<2>(a, mode, with_items, s);
+    if (f4 <= 4) return lg_launch<4>(a, mode, with_items, s);
+    if (f4 <= 8) return lg_launch<8>(a, mode, with_items, s);
+    if (f4 <= 16) return lg_launch<16>(a, mode, with_items, s);
+    if (f4 <= 32) return lg_launch<32>(a, mode, with_items, s);
+    return lg_launch<64>(a, mode, with_items, s);
+}
+
+// ---------------------------------------------------------------------------------------------- full-batch training (full-batch.py:100-105)
+// Transposed gather over the row-list transpose (grapes_rowlist_transpose): out[j] = dinv[srcs[j]] * sum of g[pos[k]] over
+// k in [src_off[j], src_off[j+1]) — the gradient of dinv ⊙ (Â T) restricted to the loss rows, taken back to dU = dinv ⊙ dT on the
+// sources.  Positions ascend within a source; a source with more than `chunk` entries is cut into items whose partials are
+// added in chunk order (lg_chunks_k), so two runs are bit-identical.  item_cap bounds the items: 2 * entries / chunk + 1.
+extern "C" size_t grapes_rowlist_gather_t_workspace_bytes(int32_t n_src, int32_t item_cap, int32_t f) {
+    return grapes_gcn_large_aggregate_workspace_bytes(n_src, item_cap, f);
+}
+extern "C" int grapes_rowlist_gather_t(const float* g, int64_t ldg, const int32_t* srcs, const int64_t* src_off, const int32_t* pos,
+                                       const float* dinv, int32_t n_src, int32_t f, float* out, int64_t ldo, int32_t chunk,
+                                       int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream) {
+    if (n_src < 0 || f <= 0 || (f & 3) || f > 4096 || ldg < f || ldo < f || (ldg & 3) || (ldo & 3) || item_cap < 0 ||
+        chunk < 64 || (chunk & 63))
+        return GRAPES_EINVAL;
+    if (n_src == 0) return 0;
+    if (!g || !srcs || !src_off || !pos || !dinv || !out || (item_cap > 0 && !workspace)) return GRAPES_EINVAL;
+    if (((uintptr_t)g & 15) || ((uintptr_t)out & 15) || ((uintptr_t)workspace & 255)) return GRAPES_EALIGN;
+    LgArgs a{g, (long long)ldg, src_off, pos, dinv, 0, nullptr, n_src, f, nullptr, 0, out, (long long)ldo, chunk,
+             nullptr, nullptr, item_cap, nullptr, nullptr, srcs};
+    return lg_run(a, LG_TRANSPOSED, workspace, status, (hipStream_t)stream);
+}
+
+// Dropout of a row list of an N x width matrix (modules/gcn.py:33,37 inside full-batch.py:101): element (i, c), c < f, of the
+// m x f block belongs to row r = rows ? rows[i] : r0 + i and is kept iff philox_uniform(seed, offset, r * width + c) >= p — the
+// mask grapes_dropout_fwd draws on the whole contiguous N x width matrix — then scaled by 1 / (1 - p); dropped elements are 0.
+// y may be x (in place).  Columns f .. of the block are not touched.
+__global__ __launch_bounds__(256) void lg_dropout_rows_k(const float* x, long long ldx, float* y, long long ldy, int r0,
+                                                         const int32_t* __restrict__ rows, int m, int f, long long width, float p,
+                                                         uint64_t seed, uint64_t offset) {
+    const float scale = p < 1.0f ? 1.0f / (1.0f - p) : 0.f;
+    const long long total = (long long)m * f;
+    for (long long it = (long long)blockIdx.x * blockDim.x + threadIdx.x; it < total; it += (long long)gridDim.x * blockDim.x) {
+        const long long i = it / f;
+        const int c = (int)(it - i * f);
+        const long long r = rows ? (long long)rows[i] : (long long)r0 + i;
+        const bool keep = philox_uniform_at(seed, offset, r * width + c) >= p;
+        const float v = x[i * ldx + c];
+        y[i * ldy + c] = keep ? v * scale : 0.f;
+    }
+}
+extern "C" int grapes_dropout_rows(const float* x, int64_t ldx, float* y, int64_t ldy, int32_t r0, const int32_t* rows, int32_t m,
+                                   int32_t f, int64_t width, float p, uint64_t philox_seed, uint64_t philox_offset,
+                                   grapes_stream_t stream) {
+    if (m < 0 || f <= 0 || (int64_t)f > width || ldx < f || ldy < f || r0 < 0 || !(p >= 0.f && p <= 1.f)) return GRAPES_EINVAL;
+    if (m == 0) return 0;
+    if (!x || !y) return GRAPES_EINVAL;
+    long long grid = ((long long)m * f + 255) / 256; if (grid > 16384) grid = 16384;
+    hipLaunchKernelGGL(lg_dropout_rows_k, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, x, (long long)ldx, y,
+                       (long long)ldy, r0, rows, m, f, (long long)width, p, philox_seed, philox_offset);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
 }

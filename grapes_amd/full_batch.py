@@ -1,0 +1,128 @@
+"""Full-batch GCN training driver: the baseline every GRAPES result is compared against (reference full-batch.py).
+
+    python -m grapes_amd.full_batch --dataset cora --max_epochs 30 --runs 10
+
+* Flags and defaults of the reference's `Arguments` (full-batch.py:26-50) — they differ from main.py's (`eval_on_cpu`,
+  `eval_full_batch` false, `log_wandb` true).  `--config_file` is read first and the command line wins (full-batch.py:146-150).
+  Flags that change nothing here are accepted and ignored: `log_wandb`, `notes`, `eval_on_cpu`, `eval_full_batch` and the
+  sampler's (`sampling_hops`, `num_samples`, `use_indicators`, `lr_gf`, `loss_coef`, `log_z_init`, `reg_param`, `batch_size`).
+  Added: `--seed` (the synthetic data and the weights) and `--large_graph auto|true|false` (the row-blocked 64-bit path of
+  full_graph.train_step: automatic from 2^31 CSR entries on).
+* Model `GCN(F, [hidden_dim, C], dropout)` and `Adam(lr=lr_gc)` (full-batch.py:72-76).  Each epoch is one full_graph.train_step
+  over the whole graph — mean CrossEntropy, or mean BCEWithLogits for 2-D labels, on the train rows — then `step()`
+  (full-batch.py:100-107).
+* Validation when (epoch + 1) % eval_frequency == 0, on THIS epoch's training logits of the validation rows, taken before the
+  optimiser step (full-batch.py:116-120).  Test: one more forward pass over the whole graph (full-batch.py:130-134).  Then
+  `Acc: mean ± std` of 100 * test_f1 over the runs (full-batch.py:152-157).
+* Kept from the reference: the module is never put in .eval(), so dropout is active in the validation logits and in the test
+  pass.  Changed: the reference logs `loss_c=0.000000` (acc_loss_c is never updated); the real loss is printed.  For
+  multi-label targets the reference's accuracy_score raises; the TP / FP / FN micro-F1 of eval.py:57-70 is reported instead.
+
+Datasets as in grapes_amd.main: a synthetic stand-in by name, or `module:function`.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+import time
+from typing import Optional, Sequence
+
+import torch
+
+from .main import _bool, load_data, read_config_file
+
+# (name, type, default) — full-batch.py:26-50
+_FLAGS = [
+    ("dataset", str, "cora"), ("sampling_hops", int, 2), ("num_samples", int, 16), ("lr_gc", float, 1e-3),
+    ("use_indicators", bool, True), ("lr_gf", float, 1e-4), ("loss_coef", float, 1e4), ("log_z_init", float, 0.0),
+    ("reg_param", float, 0.0), ("dropout", float, 0.0), ("model_type", str, "gcn"), ("hidden_dim", int, 256),
+    ("max_epochs", int, 30), ("batch_size", int, 512), ("eval_frequency", int, 5), ("eval_on_cpu", bool, False),
+    ("eval_full_batch", bool, False), ("runs", int, 10), ("notes", str, None), ("log_wandb", bool, True),
+    ("config_file", str, None),
+]
+# additions of this driver (not in the reference)
+_EXTRA = [("seed", int, None), ("large_graph", str, "auto")]
+
+
+def _parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="grapes_amd.full_batch", description=__doc__.split("\n\n")[0])
+    for name, typ, default in _FLAGS + _EXTRA:
+        if name == "large_graph":
+            ap.add_argument("--large_graph", choices=["auto", "true", "false"], default=default)
+        else:
+            ap.add_argument(f"--{name}", type=_bool if typ is bool else typ, default=default)
+    return ap
+
+
+def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
+    """full-batch.py:143-150: with --config_file the file's flags are read first and the command line is parsed on top."""
+    argv = list(sys.argv[1:] if argv is None else argv)
+    ap = _parser()
+    args = ap.parse_args(argv)
+    if args.config_file is not None:
+        args = ap.parse_args(read_config_file(args.config_file) + argv)
+    if args.model_type != "gcn":
+        raise NotImplementedError("only model_type=gcn is built (full-batch.py:72-73 builds no other model)")
+    return args
+
+
+def _large_flag(v: str) -> Optional[bool]:
+    return {"auto": None, "true": True, "false": False}[v]
+
+
+def train(args, device=None, log=print) -> float:
+    from . import full_graph
+    from .eval import _metrics
+    from .graph import DeviceGraph
+    from .modules.gcn import GCN
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    data = load_data(args, device)
+    if getattr(data, "rowptr", None) is not None:
+        g = DeviceGraph(data.rowptr, data.col, data.num_nodes)
+    else:
+        g = DeviceGraph.from_edge_index(data.edge_index.to(device), data.num_nodes)
+    if args.seed is not None:
+        torch.manual_seed(args.seed)
+    x = data.x.to(device).contiguous()
+    y = data.y.to(device)
+    large = _large_flag(args.large_graph)
+    gcn_c = GCN(x.shape[1], hidden_dims=[args.hidden_dim, data.num_classes], dropout=args.dropout).to(device)  # full-batch.py:73
+    optimizer_c = torch.optim.Adam(gcn_c.parameters(), lr=args.lr_gc)                                        # full-batch.py:76
+    train_mask, val_mask, test_mask = (m.to(device) for m in (data.train_mask, data.val_mask, data.test_mask))
+    val_idx = val_mask.nonzero().squeeze(1)
+    for epoch in range(1, args.max_epochs + 1):
+        t0 = time.time()
+        evaluating = (epoch + 1) % args.eval_frequency == 0
+        optimizer_c.zero_grad()                                                                               # full-batch.py:103
+        loss_c, val_logits = full_graph.train_step(gcn_c, x, g, y, train_mask, eval_rows=val_idx if evaluating else None,
+                                                   large_graph=large)                                         # full-batch.py:100-104
+        optimizer_c.step()                                                                                    # full-batch.py:105
+        log(f"epoch {epoch}: loss_c={float(loss_c):.6f}, {time.time() - t0:.2f}s")
+        if evaluating:                                                                                        # full-batch.py:116-126
+            _, f1 = _metrics(val_logits, y[val_idx])
+            log(f"loss_c={float(loss_c):.6f}, valid_f1={f1:.3f}")
+    test_idx = test_mask.nonzero().squeeze(1)                                                                 # full-batch.py:130-134
+    if full_graph.use_large_path(g, large):
+        with torch.no_grad():
+            test_acc, test_f1 = full_graph.evaluate_rows(gcn_c, x, g, y, test_mask, False)
+    else:
+        with torch.no_grad():
+            logits, _ = gcn_c(x, g, large_graph=False)
+            test_acc, test_f1 = _metrics(logits[test_idx], y[test_idx])
+            del logits
+    log(f"test_accuracy={test_acc:.3f}, test_f1={test_f1:.3f}")
+    return test_f1
+
+
+def main(argv: Optional[Sequence[str]] = None) -> float:
+    args = parse_args(argv)
+    results = torch.empty(args.runs)
+    for r in range(args.runs):                                                                                # full-batch.py:152-155
+        results[r] = train(args)
+    std = float(results.std()) if args.runs > 1 else 0.0
+    print(f"Acc: {100 * float(results.mean()):.2f} ± {100 * std:.2f}")                                       # full-batch.py:157
+    return float(results.mean())
+
+
+if __name__ == "__main__":
+    main()

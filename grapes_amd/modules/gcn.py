@@ -53,8 +53,9 @@ def _large(edge_index, large_graph: Optional[bool]) -> bool:
     if not hasattr(edge_index, "full_graph_plan") or not full_graph.use_large_path(edge_index, large_graph):
         return False
     if torch.is_grad_enabled():
-        raise ValueError("full-graph training over a graph with 2^31 or more entries is not built: the full-graph pass there "
-                         "is inference only (call it under torch.no_grad() / torch.inference_mode())")
+        raise ValueError("full-graph training over a graph with 2^31 or more entries is not built into GCN.forward: the "
+                         "full-graph pass there is inference only (call it under torch.no_grad() / torch.inference_mode()); "
+                         "train with grapes_amd.full_graph.train_step")
     return True
 
 

@@ -1885,6 +1885,101 @@ def exchange_note_rows(loc, ids, pos, base, d_n=None, node_map=None, batch=None,
 
 
 # ------------------------------------------------------------------------------- losses + Adam (§8f N2)
+# ------------------------------------------------------------------------------- full-batch training above 2^31 entries
+def rowlist_transpose_bytes(plan: LargeGraphPlan, e_cap: int) -> int:
+    """HBM grapes_rowlist_transpose allocates: its outputs (srcs, src_off, pos, counts) and its workspace."""
+    n = plan.n
+    return (4 * n + 8 * (n + 1) + 4 * max(int(e_cap), 1) + 64 +
+            int(lib().grapes_rowlist_transpose_workspace_bytes(int(e_cap), n)) + 256)
+
+
+def rowlist_entries_cap(plan: LargeGraphPlan, rows) -> int:
+    """Upper bound of the row-list transpose's entries: sum over rows of (row length + 1).  One host read."""
+    rp = plan.rowptr_t
+    r = rows.long()
+    return int((rp[r + 1] - rp[r]).sum().item()) + rows.numel()
+
+
+def rowlist_transpose(plan: LargeGraphPlan, rows, e_cap: int, status=None):
+    """(srcs int32[n_src], src_off int64[n_src + 1], pos int32[entries]) of grapes_rowlist_transpose over the plan's CSR by
+    target and the ascending, distinct int32 `rows`.  One host read (the two counts)."""
+    _chk(rows, _i32, "rows"); _chk(status, _i32, "status", True)
+    dev, n, m = rows.device, plan.n, rows.numel()
+    srcs = torch.empty(max(n, 1), dtype=_i32, device=dev)
+    src_off = torch.empty(n + 1, dtype=_i64, device=dev)
+    pos = torch.empty(max(int(e_cap), 1), dtype=_i32, device=dev)
+    counts = torch.zeros(2, dtype=_i64, device=dev)
+    ws, base = _aligned_ws(lib().grapes_rowlist_transpose_workspace_bytes(int(e_cap), n), dev)
+    _lib.check(lib().grapes_rowlist_transpose(_p(plan.rowptr_t), _p(plan.col_t), n, _p(rows), m, int(e_cap), _p(srcs), _p(src_off),
+                                              _p(pos), _p(counts), base, _p(status), _stream()), "rowlist_transpose")
+    del ws
+    n_src, entries = (int(v) for v in counts.tolist())
+    return srcs[:n_src], src_off[:n_src + 1], pos[:entries]
+
+
+def rowlist_gather_t_item_cap(entries: int, chunk: int) -> int:
+    return 2 * int(entries) // int(chunk) + 1
+
+
+def rowlist_gather_t_workspace_bytes(n_src: int, item_cap: int, f: int) -> int:
+    return int(lib().grapes_rowlist_gather_t_workspace_bytes(int(n_src), int(item_cap), int(f))) + 256
+
+
+def rowlist_gather_t(g, srcs, src_off, pos, dinv, chunk: int, out=None, status=None):
+    """out[j] = dinv[srcs[j]] * sum of g[pos[k]] over source j's entries (grapes_rowlist_gather_t).  g [M, f], f % 4 == 0."""
+    _chk(g, _f32, "g"); _chk(srcs, _i32, "srcs"); _chk(src_off, _i64, "src_off"); _chk(pos, _i32, "pos"); _chk(dinv, _f32, "dinv")
+    _chk(status, _i32, "status", True)
+    n_src, f = srcs.numel(), g.shape[1]
+    if out is None:
+        out = torch.empty((n_src, f), dtype=_f32, device=g.device)
+    elif out.shape[0] < n_src or out.shape[1] != f or out.stride(1) != 1:
+        raise ValueError("rowlist_gather_t: out must be [n_src, f] with unit column stride")
+    cap = rowlist_gather_t_item_cap(pos.numel(), chunk)
+    if cap >= 2 ** 31:
+        raise ValueError("rowlist_gather_t: more than 2^31 work items")
+    ws, base = _aligned_ws(lib().grapes_rowlist_gather_t_workspace_bytes(n_src, cap, f), g.device)
+    _lib.check(lib().grapes_rowlist_gather_t(_p(g), g.stride(0), _p(srcs), _p(src_off), _p(pos), _p(dinv), n_src, f, _p(out),
+                                             out.stride(0), int(chunk), cap, base, _p(status), _stream()), "rowlist_gather_t")
+    del ws
+    return out
+
+
+def dropout_rows(x, width: int, p: float, seed: int, offset: int, r0: int = 0, rows=None, f=None, out=None):
+    """Dropout of rows r0.. (or rows[i]) of an N x width matrix with the mask grapes_dropout_fwd draws on the whole matrix
+    (element r * width + c of the stream (seed, offset)); columns f.. untouched.  out may be x (in place)."""
+    _chk(rows, _i32, "rows", True)
+    if x.dtype != _f32 or not x.is_cuda or x.dim() != 2 or x.stride(1) != 1:
+        raise _lib.GrapesHipError("dropout_rows: expected a CUDA fp32 matrix with unit column stride")
+    m = x.shape[0]
+    f = int(width if f is None else f)
+    if out is None:
+        out = torch.empty_like(x)
+    _lib.check(lib().grapes_dropout_rows(_p(x), x.stride(0), _p(out), out.stride(0), int(r0), _p(rows), m, f, int(width), float(p),
+                                         int(seed), int(offset), _stream()), "dropout_rows")
+    return out
+
+
+def rowlist_loss(z, C: int, rows, labels, dinv, p: float = 0.0, seed: int = 0, offset: int = 0, g=None, status=None):
+    """(loss [1], g [M, ldg_cols] = dinv[rows] ⊙ dloss/dZ, dcol [ldg_cols] = column sums of dloss/dZ) of grapes_rowlist_loss over
+    the pre-dropout logits z [M, >= C] of `rows`.  labels: int64 [N] (CrossEntropy) or fp32 [N, C] (BCEWithLogits).  g may be z."""
+    _chk(rows, _i32, "rows"); _chk(dinv, _f32, "dinv"); _chk(status, _i32, "status", True)
+    if z.dtype != _f32 or not z.is_cuda or z.dim() != 2 or z.stride(1) != 1:
+        raise _lib.GrapesHipError("rowlist_loss: expected a CUDA fp32 matrix with unit column stride")
+    multi = labels.dim() == 2
+    _chk(labels, _f32 if multi else _i64, "labels")
+    M, cols = z.shape
+    if g is None:
+        g = torch.empty((M, cols), dtype=_f32, device=z.device)
+    dcol = torch.empty(cols, dtype=_f32, device=z.device)
+    loss = torch.empty(1, dtype=_f32, device=z.device)
+    ws, base = _aligned_ws(lib().grapes_rowlist_loss_workspace_bytes(M, cols), z.device)
+    _lib.check(lib().grapes_rowlist_loss(_p(z), z.stride(0), int(C), _p(rows), M, None if multi else _p(labels),
+                                         _p(labels) if multi else None, _p(dinv), float(p), int(seed), int(offset), _p(g),
+                                         g.stride(0), cols, _p(dcol), _p(loss), base, _p(status), _stream()), "rowlist_loss")
+    del ws
+    return loss, g, dcol
+
+
 def classifier_loss(logits, local_rows, target_ids, labels, out_grad=None):
     """(loss_c [1], d loss_c / d logits [n_rows, C]) — main.py:260,267.  labels: int64 [N] or fp32 [N, C]."""
     _chk(logits, _f32, "logits"); _chk(local_rows, _i32, "local_rows"); _chk(target_ids, _i32, "target_ids")

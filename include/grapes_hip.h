@@ -47,7 +47,9 @@ extern "C" {
  * grapes_gate_bits_words;
  * 301: grapes_linear_fwd_row_scaled (full-batch inference: the dinv row scaling in the transform GEMM's epilogue);
  * 302: grapes_eval_predict; added within 302 (no signature of an earlier entry point changed): the full-batch path above 2^31
- * entries — grapes_csr_symmetric_check, grapes_csr_transpose, grapes_gcn_large_prepare, grapes_gcn_large_aggregate(_workspace_bytes). */
+ * entries — grapes_csr_symmetric_check, grapes_csr_transpose, grapes_gcn_large_prepare, grapes_gcn_large_aggregate(_workspace_bytes);
+ * and full-batch training over such graphs — grapes_rowlist_transpose(_workspace_bytes), grapes_rowlist_gather_t(_workspace_bytes),
+ * grapes_dropout_rows, grapes_rowlist_loss(_workspace_bytes). */
 #define GRAPES_ABI_VERSION 302
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1041,6 +1043,44 @@ int grapes_gcn_large_aggregate(const float* h, int64_t ldh, const int64_t* rowpt
                                int32_t prescaled, int32_t r0, const int32_t* rows, int32_t m, int32_t f, const float* bias,
                                int32_t relu, float* out, int64_t ldo, int32_t chunk, int32_t item_cap, void* workspace,
                                int32_t* status, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ full-batch training over the same graphs
+ * Replace full-batch.py:100-105 (logits = gcn_c(x, edge_index) on the whole graph, loss_fn on the train rows, backward) for a
+ * two-layer GCN, row-blocked with 64-bit offsets (grapes_amd/full_graph.py train_step).  Deterministic: fixed summation orders,
+ * no float atomics.
+ *
+ * Row-list transpose of the CSR by target restricted to rows[0..m) (ascending, distinct): for rows[p] = r the entries (s, p) are
+ * every stored s of row r with s != r, plus (r, p) (the unit self-loop).  Output, per source s that has any, in ascending s:
+ * srcs[j] = s (capacity num_nodes), its entries' positions p ascending in pos[src_off[j] .. src_off[j+1]) (src_off capacity
+ * num_nodes + 1; pos capacity e_cap), counts[0] = sources, counts[1] = entries (int64, device).  e_cap must be at least
+ * sum over rows of (row length + 1).  workspace: grapes_rowlist_transpose_workspace_bytes(e_cap, num_nodes), 256-byte aligned. */
+size_t grapes_rowlist_transpose_workspace_bytes(int64_t e_cap, int32_t num_nodes);
+int grapes_rowlist_transpose(const int64_t* rowptr_t, const int32_t* col_t, int32_t num_nodes, const int32_t* rows, int32_t m,
+                             int64_t e_cap, int32_t* srcs, int64_t* src_off, int32_t* pos, int64_t* counts, void* workspace,
+                             int32_t* status, grapes_stream_t stream);
+/* Transposed gather over that structure (the backward of the last aggregation on the loss rows):
+ * out[j, :f] = dinv[srcs[j]] * sum_{k in [src_off[j], src_off[j+1])} g[pos[k], :f].  Sources with more than `chunk` entries are cut
+ * into items (partials added in chunk order); item_cap >= 2 * entries / chunk + 1.  f % 4 == 0, ldg / ldo multiples of 4, g and
+ * out 16-byte aligned; workspace: grapes_rowlist_gather_t_workspace_bytes(n_src, item_cap, f), 256-byte aligned. */
+size_t grapes_rowlist_gather_t_workspace_bytes(int32_t n_src, int32_t item_cap, int32_t f);
+int grapes_rowlist_gather_t(const float* g, int64_t ldg, const int32_t* srcs, const int64_t* src_off, const int32_t* pos,
+                            const float* dinv, int32_t n_src, int32_t f, float* out, int64_t ldo, int32_t chunk, int32_t item_cap,
+                            void* workspace, int32_t* status, grapes_stream_t stream);
+/* Dropout (modules/gcn.py:33,37) on rows of an N x width matrix: y[i, c] = x[i, c] / (1 - p) if
+ * philox_uniform(seed, offset, r * width + c) >= p else 0, r = rows ? rows[i] : r0 + i, c < f — the mask grapes_dropout_fwd
+ * draws on the whole contiguous matrix, whatever the row block.  y may be x. */
+int grapes_dropout_rows(const float* x, int64_t ldx, float* y, int64_t ldy, int32_t r0, const int32_t* rows, int32_t m, int32_t f,
+                        int64_t width, float p, uint64_t philox_seed, uint64_t philox_offset, grapes_stream_t stream);
+/* full-batch.py:101 loss_fn(logits[train_mask], y[train_mask]) on m rows (z: their pre-dropout logits, row pitch ldz): dropout
+ * with (p, seed, offset) on the N x C logits as grapes_dropout_rows draws it, then mean CrossEntropy (labels int64[N]) or mean
+ * BCEWithLogits (labels_f fp32[N, C]).  *loss_out = the loss; g[i, c] = dinv[rows[i]] * dloss/dZ[i, c] (dropout's backward
+ * applied; columns C .. ldg_cols - 1 written 0); dcol[c] = sum_i dloss/dZ[i, c] (the bias gradient), c < ldg_cols.
+ * C <= ldg_cols <= 1024; g may be z.  workspace: grapes_rowlist_loss_workspace_bytes(m, ldg_cols), 256-byte aligned. */
+size_t grapes_rowlist_loss_workspace_bytes(int32_t m, int32_t ldg_cols);
+int grapes_rowlist_loss(const float* z, int64_t ldz, int32_t C, const int32_t* rows, int32_t m, const int64_t* labels,
+                        const float* labels_f, const float* dinv, float p, uint64_t philox_seed, uint64_t philox_offset, float* g,
+                        int64_t ldg, int32_t ldg_cols, float* dcol, float* loss_out, void* workspace, int32_t* status,
+                        grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:
