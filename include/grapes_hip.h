@@ -929,7 +929,17 @@ int grapes_linear_bwd_weight_gathered(const float* dh, const float* X, int32_t F
  * product, fp32 accumulation; csrc/gemm_tiled_split.hip): 128 x 256 output tiles, both operands streamed through split-plane
  * LDS images in K steps of 32.  The forward takes W as a pre-split IMAGE (grapes_weight_split_image, once per step, from the
  * [f_out, k] parameter itself: no padded copy); f_out <= 256, a multiple of 4.  GRAPES_GEMM_SPLIT=0 disables them
- * (grapes_split_gathered_available). */
+ * (grapes_split_gathered_available).
+ * Range (these entries, the split-K / split-tail / several-problem forms below; tests/test_tsplit_accuracy_gpu.py:
+ * test_tiled_split_range_edges): each OPERAND is split on its own — a gathered entry, a weight, a dH entry — not a product.
+ *   - an entry >= 3.3962e38 (finite in fp32) rounds to bf16 inf: its m term is -inf and its l term NaN, so every output that
+ *     contracts over it is NaN — the whole forward row of a gathered row holding it (every column, 0 x NaN included), the
+ *     whole dW column of that feature (every unit).  A weight or a dH entry that large goes through the same split and
+ *     takes its forward column / dW row the same way (untested).  Other rows / columns are unaffected.  The fp32 kernels give a finite answer there.  Not guarded: inputs that large
+ *     mean training has already diverged.
+ *   - an entry below about 2^-110 (1e-33) is held by its three terms only to bf16's smallest subnormal step, 2^-133 (an
+ *     error of at most 2^-134 per entry instead of 2^-24 relative): measured at X = 1e-35 (fails the element-wise fp32
+ *     criterion) against 1e-28 (meets it); the matrix pipe keeps bf16 subnormals. */
 int32_t grapes_split_gathered_available(int32_t f_out);
 size_t grapes_weight_split_image_bytes(int32_t k);
 int grapes_weight_split_image(const float* w, int32_t ldw, int32_t f_out, int32_t k, void* image, grapes_stream_t stream);

@@ -18,8 +18,10 @@ accuracy" means: no worse than a plain blocked fp32 sum of the same products, by
 another summation order.
 
 The data generators below are shared by tests/test_accuracy_criterion_cpu.py (a CPU emulation of the split kernels,
-faithful and with defects, which shows the criterion rejects a lost plane) and tests/test_split_dw_accuracy_gpu.py (the
-kernels themselves), so the two cannot drift apart.  Only tests import this module.
+faithful and with defects, which shows the criterion rejects a lost plane) and tests/test_split_dw_accuracy_gpu.py /
+tests/test_tsplit_accuracy_gpu.py (the kernels themselves), so the two cannot drift apart.  The emulations of the tiled
+gathered-operand GEMMs (emulate_tsplit_fwd / emulate_tsplit_dw) live here too: the GPU tests check an output that exceeds
+the factors against them.  Only tests import this module.
 """
 from __future__ import annotations
 
@@ -244,3 +246,208 @@ def within_split_resolution(dw, ref_dw, mask, cv) -> bool:
     bound = torch.from_numpy(np.asarray(cv, dtype=np.float64)).abs() * live * 2.0 ** -134
     err = (torch.as_tensor(dw).double() - ref).abs()
     return bool((err <= bound[:, None] + 2.0 ** -20 * mag).all())
+
+
+# ------------------------------------------------------------------------------------- tiled gathered-operand GEMMs
+# grapes_amd/csrc/gemm_tiled_split.hip: H = feat(ids) Wᵀ and dW = dHᵀ feat(ids), feat(ids[r]) = [X[ids[r], :F] | indicator bits | 0]
+TS_BM, TS_BK = 128, 32                  # rows of a forward tile; K step (two k16 MFMA sub-steps)
+TS_TAIL_GRID = 256                      # resident workgroups of the split-tail forward
+TS_DW_WGS = 768                         # workgroups the weight gradient aims at
+
+
+def split3(v) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """fp32 -> three fp32 tensors holding bf16 values, h + m + l = v (split3 / ts_split3_pair: round-to-nearest-even
+    conversions, as v_cvt_pk_bf16_f32 rounds)."""
+    v = torch.as_tensor(v, dtype=torch.float32)
+    h = v.bfloat16().float()
+    r1 = v - h
+    m = r1.bfloat16().float()
+    return h, m, (r1 - m).bfloat16().float()
+
+
+def _cross_terms(a, b, defect):
+    """The six cross products of one k16 sub-step in the kernels' order (ts_mfma_stage: lh, hl, mm, mh, hm, hh; a = the A
+    image's planes, b = the B image's)."""
+    (ah, am, al), (bh, bm, bl) = a, b
+    terms = [(al, bh), (ah, bl), (am, bm), (am, bh), (ah, bm), (ah, bh)]
+    if defect == "drop_mm":
+        del terms[2]
+    elif defect == "drop_hl_lh":
+        del terms[:2]
+    elif defect == "drop_lh":
+        del terms[0]
+    return terms
+
+
+def emulate_tsplit_fwd(x, w, defect=None, k_pieces=None) -> torch.Tensor:
+    """gemm_tsplit_fwd_k's x wᵀ on the CPU, x [n, K] (the gathered operand), w [N, K]: K in steps of 32, each two k16
+    sub-steps, per sub-step the six cross terms in the kernel's order into ONE fp32 accumulator.  k_pieces: [(j0, j1), ...]
+    ranges of K steps summed separately and added in piece order (the split-K form, grapes_linear_fwd_gathered_split_k, and
+    the split tail's cut tiles); None = one piece.  defect: None, "drop_mm", "drop_hl_lh", "lost_l" (the l plane of the
+    gathered operand zero)."""
+    x, w = torch.as_tensor(x, dtype=torch.float32), torch.as_tensor(w, dtype=torch.float32)
+    n, K = x.shape
+    nk = -(-K // TS_BK)
+    pad = nk * TS_BK - K
+    xs = [torch.nn.functional.pad(p, (0, pad)) for p in split3(x)]
+    ws = [torch.nn.functional.pad(p, (0, pad)) for p in split3(w)]
+    if defect == "lost_l":
+        xs[2] = torch.zeros_like(xs[2])
+    out = None
+    for j0, j1 in (k_pieces or [(0, nk)]):
+        acc = torch.zeros(n, w.shape[0])
+        for k in range(TS_BK * j0, TS_BK * j1, 16):
+            s = slice(k, k + 16)
+            for a, b in _cross_terms([p[:, s] for p in xs], [p[:, s] for p in ws], defect):
+                acc = acc + a @ b.T
+        out = acc if out is None else out + acc
+    return out
+
+
+def tsplit_fwd_pieces(n: int, kp: int):
+    """The split-K form's K pieces at n rows (ts_fwd_slabs): [(j0, j1), ...]."""
+    ntiles, nk = -(-n // TS_BM), -(-kp // TS_BK)
+    want = max(1, 256 // max(ntiles, 1))
+    if want > nk // 2:
+        want = max(nk // 2, 1)
+    want = min(want, 16)
+    kper = -(-nk // want)
+    return [(j, min(j + kper, nk)) for j in range(0, nk, kper)]
+
+
+def tsplit_tail_cut(n: int, nprob: int, kp: int):
+    """The split tail's cut tiles (gemm_tsplit_fwd_tail_k, ts_tail_of) at n rows and nprob nets:
+    ({(tile, net): [(j0, j1), ...]} for every cut unit, S)."""
+    ntiles, nk = -(-n // TS_BM), -(-kp // TS_BK)
+    units, G = ntiles * nprob, TS_TAIL_GRID
+    t_full = units // G * G
+    R = units - t_full
+    S = G // R if R > 0 else 1
+    S = max(1, min(S, nk // 2, 8))
+    kper = -(-nk // S)
+    S = -(-nk // kper)
+    if S <= 1:
+        return {}, S
+    pieces = [(j, min(j + kper, nk)) for j in range(0, nk, kper)]
+    return {divmod(u, nprob): pieces for u in range(t_full, units)}, S
+
+
+def tsplit_dw_slabs(cap: int, f_out: int, kp: int, wgs: int = TS_DW_WGS) -> int:
+    """Slabs of grapes_linear_bwd_weight_gathered_split[_ld] at a row CAPACITY cap (ts_dw_slabs, the product's default form: the
+    swapped tile where it needs no more tiles); the kernels share the LIVE rows' steps out over them."""
+    swapped = 128 < f_out <= 256 and -(-kp // 128) <= -(-f_out // 128) * -(-kp // 256)
+    tiles = -(-kp // 128) if swapped else -(-f_out // 128) * -(-kp // 256)
+    ns = min(wgs // tiles, -(-(-(-cap // TS_BK)) // 4))
+    return max(ns, 1)
+
+
+def tsplit_multi_per(kps: Sequence[int], lives: Sequence[int]) -> int:
+    """K steps per slab of grapes_linear_bwd_weight_gathered_split_multi (ts_dw_partition) at these live row counts."""
+    ct = -(-max(kps) // 128)
+    nslab = max(768 // ct, 4 + 4)
+    steps = [-(-n // TS_BK) for n in lives]
+    avail = nslab - len(lives)
+    per = max(-(-sum(steps) // avail), 4)
+    return per
+
+
+def emulate_tsplit_dw(dh, feat, nslab=None, defect=None, per=None, lost_slab=None) -> torch.Tensor:
+    """gemm_tsplit_dw_k / gemm_tsplit_dw_sw_k + ts_slab_sum_k on the CPU: dW = dhᵀ feat (dh [n, M], feat [n, K]).  The row
+    space in 32-row steps is cut into slabs of `per` steps (per = ceil(steps / nslab), as the kernels derive it); each slab
+    sums its 16-row sub-steps, the six cross terms in the kernels' order (dH.l x.h, dH.h x.l, m m, dH.m x.h, dH.h x.m, h h),
+    into one fp32 accumulator; the slabs are added in index order.  defect: None, "drop_mm", "drop_hl_lh", "drop_lh",
+    "lost_l" (the l plane of feat zero), "lost_l_slab" (that plane zero in slab lost_slab only)."""
+    dh, feat = torch.as_tensor(dh, dtype=torch.float32), torch.as_tensor(feat, dtype=torch.float32)
+    n, M = dh.shape
+    K = feat.shape[1]
+    steps = -(-n // TS_BK)
+    if per is None:
+        per = -(-steps // nslab)
+    ns = max(1, -(-steps // per))
+    rows = ns * per * TS_BK
+    a = [torch.nn.functional.pad(p, (0, 0, 0, rows - n)).view(ns, per * TS_BK, M) for p in split3(dh)]
+    b = [torch.nn.functional.pad(p, (0, 0, 0, rows - n)).view(ns, per * TS_BK, K) for p in split3(feat)]
+    if defect == "lost_l":
+        b[2] = torch.zeros_like(b[2])
+    elif defect == "lost_l_slab":
+        b[2] = b[2].clone()
+        b[2][lost_slab] = 0.0
+    accs = torch.zeros(ns, M, K)
+    for t in range(0, per * TS_BK, 16):
+        s = slice(t, t + 16)
+        for pa, pb in _cross_terms([p[:, s] for p in a], [p[:, s] for p in b], defect):
+            accs = accs + torch.bmm(pa.transpose(1, 2), pb)
+    out = torch.zeros(M, K)
+    for z in range(ns):
+        out = out + accs[z]
+    return out
+
+
+NAN_ROW = -1        # the last row of every generated X: NaN, read only through the capacity rows' ids
+
+
+def gathered_problem(N: int, F: int, num_ind: int, f_out: int, n: int, cap: int, kind: str, seed: int,
+                     epoch: int = 77, rows_seed: Optional[int] = None) -> Dict[str, np.ndarray]:
+    """One transform-first first layer over n gathered rows (capacity cap >= n):
+      X [N, ceil4(F)] fp32 (zero pad columns, as pad_features leaves them; its last row NaN in [:F]);
+      ids [cap] int32: live rows in [0, N - 1) (with repeats), capacity rows -> the NaN row;
+      code [N] int32 indicator words (epoch << 8 | bits; every fourth node a stale epoch with all bits set, which reads 0);
+      w [f_out, F + num_ind] N(0,1) / sqrt(K), a view of wide [f_out, F + num_ind + 5] whose extra columns are +inf (a
+      weight read past its K poisons the output);
+      dh [cap, f_out] N(0,1), capacity rows NaN.
+    kind: normal; mixed (row g of X at 10^a_g, a in [-20, 20]: outputs of very different sizes in one tile — and dh row r
+    at 10^(-a_ids[r] + c_r), c in [-3, 3], as layer_problem's rs); zeros (whole zero rows of X and of dh, single zero entries,
+    a zero column of X).  X, code and w depend on (N, F, num_ind, f_out, kind, seed) only; ids and dh on rows_seed
+    (default seed + 1) as well: problems that share X draw their rows with different rows_seed."""
+    rng = np.random.default_rng(seed)
+    K, ldx = F + num_ind, (F + 3) // 4 * 4
+    X = np.zeros((N, ldx))
+    X[:, :F] = rng.standard_normal((N, F))
+    a = rng.uniform(-20, 20, N) if kind == "mixed" else np.zeros(N)
+    X[:, :F] *= 10.0 ** a[:, None]
+    if kind == "zeros":
+        X[rng.integers(0, N - 1, max(1, N // 50))] = 0.0
+        X[rng.integers(0, N - 1, N), rng.integers(0, F, N)] = 0.0
+        X[:, F // 2] = 0.0
+    elif kind not in KINDS:
+        raise ValueError(kind)
+    X[NAN_ROW, :F] = np.nan
+    code = ((epoch << 8) | rng.integers(0, 1 << max(num_ind, 1), N)).astype(np.int64)
+    code[::4] = ((epoch - 1) << 8) | 0xff
+    wide = np.full((f_out, K + 5), np.inf)
+    wide[:, :K] = rng.standard_normal((f_out, K)) / np.sqrt(K)
+    rr = np.random.default_rng(seed + 1 if rows_seed is None else rows_seed)
+    ids = np.full(cap, N - 1, np.int64)
+    ids[:n] = rr.integers(0, N - 1, n)
+    dh = rr.standard_normal((cap, f_out))
+    if kind == "mixed":
+        dh *= 10.0 ** (-a[ids] + rr.uniform(-3, 3, cap))[:, None]
+    elif kind == "zeros":
+        dh[rr.integers(0, cap, max(1, cap // 50))] = 0.0
+        dh[rr.integers(0, cap, cap), rr.integers(0, f_out, cap)] = 0.0
+    dh[n:] = np.nan
+    f = lambda v: np.ascontiguousarray(v, dtype=np.float32)
+    return {"X": f(X), "ids": ids.astype(np.int32), "code": code.astype(np.int32), "wide": f(wide), "w": f(wide[:, :K]),
+            "dh": f(dh), "epoch": epoch, "F": F, "num_ind": num_ind, "n": n}
+
+
+def gathered_feat(p: Dict[str, np.ndarray], rows=None, ind_mask: int = 0) -> np.ndarray:
+    """feat(ids[r]) of gathered_problem p for the live rows (or `rows` of them), fp32 [len, F + num_ind]: X's columns, then the
+    indicator bits of the node's word where its epoch is current, under ind_mask (0 = all bits)."""
+    F, ni = p["F"], p["num_ind"]
+    ids = p["ids"][:p["n"]] if rows is None else p["ids"][rows]
+    out = np.zeros((len(ids), F + ni), np.float32)
+    out[:, :F] = p["X"][ids, :F]
+    if ni:
+        cd = p["code"][ids].astype(np.int64) & 0xffffffff
+        bits = np.where((cd >> 8) == p["epoch"], cd & 0xff, 0) & (ind_mask if ind_mask else 0xff)
+        out[:, F:] = (bits[:, None] >> np.arange(ni)) & 1
+    return out
+
+
+def within_tiled_split_resolution(got, ref, other_abs) -> bool:
+    """|got - ref| <= 2^-134 other_abs + 2^-20 mag per output of a tiled GEMM whose one operand is tiny: each of its entries
+    held to half of bf16's smallest subnormal step, plus an fp32 sum's rounding.  other_abs: per output the sum of |.| of the
+    other operand's terms (forward over tiny rows: sum_k |w[c][k]| broadcast over rows), broadcastable to got."""
+    err = (torch.as_tensor(got).double() - ref[0]).abs()
+    return bool((err <= 2.0 ** -134 * torch.as_tensor(other_abs).double() + 2.0 ** -20 * ref[1]).all())

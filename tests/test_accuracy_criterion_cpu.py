@@ -1,7 +1,7 @@
 """The element-wise accuracy criterion (oracle/accuracy.py) has teeth: a CPU emulation of the split-bf16 GEMMs' arithmetic
 passes it when faithful and fails it when one plane of the split is lost, misplaced or mispaired — defects that the
 norm-wise tolerance of the older parity tests (2e-5 of max|ref|) lets through.  Same shapes and data generators as the
-GPU tests (tests/test_split_dw_accuracy_gpu.py)."""
+GPU tests (tests/test_split_dw_accuracy_gpu.py, tests/test_tsplit_accuracy_gpu.py)."""
 import numpy as np
 import pytest
 import torch
@@ -11,13 +11,7 @@ from oracle import accuracy as acc
 DW_BLOCKS, DS_MINROWS = 256, 128      # gemm_kernels.hip: workgroups, the gate-word form's share floor
 
 
-def split3(v: torch.Tensor):
-    """fp32 -> three fp32 tensors holding bf16 values, h + m + l = v (split3 / split3_pair: round-to-nearest-even
-    conversions, as v_cvt_pk_bf16_f32 rounds)."""
-    h = v.bfloat16().float()
-    r1 = v - h
-    m = r1.bfloat16().float()
-    return h, m, (r1 - m).bfloat16().float()
+split3 = acc.split3
 
 
 def emulate_split_dw(mask, x, rs, cv, defect=None):
@@ -159,3 +153,109 @@ def test_split_holds_tiny_products_only_to_the_bf16_subnormal_step():
         dw = emulate_split_dw(mask, x, rs, p["w2"])[0]
         assert acc.Accuracy(dw, *ref["dw"]).ok() == inside, scale
         assert acc.within_split_resolution(dw, ref["dw"], mask, p["w2"])
+
+
+# ------------------------------------------------------------------------------------- tiled gathered-operand GEMMs
+def _old_fwd_bound(got, ref) -> float:
+    """test_widths_gpu.py's forward bound: max|err| relative to the LARGEST output magnitude (it asserts <= 5e-7)."""
+    return float((got.double() - ref[0]).abs().max()) / float(ref[1].max())
+
+
+def _old_dw_bounds(got, ref):
+    """The dW bounds of test_widths_gpu.py (max|err| <= 1e-6 max mag) and of the several-problem test in test_hip_parity.py
+    (|err| <= 1e-6 of each output's own mag): both numbers."""
+    e = (got.double() - ref[0]).abs()
+    return float(e.max()) / float(ref[1].max()), float((e / ref[1].clamp_min(1e-300)).max())
+
+
+# (n, F, num_ind, f_out, kind, form): K = 605 -> 608 (Reddit's sampler net), 1436 (Cora), 602 -> 604 (the log-Z net); form:
+# "plain" one K piece (n >= 8192), "splitk" the few-row form's pieces (ts_fwd_slabs at n rows)
+TS_FWD_CASES = [(9000, 602, 3, 256, "normal", "plain"), (700, 1433, 3, 256, "normal", "splitk"),
+                (700, 1433, 3, 256, "mixed", "splitk"), (2708, 1433, 3, 64, "mixed", "splitk"),
+                (129, 602, 0, 132, "zeros", "splitk"), (1500, 602, 3, 256, "zeros", "splitk")]
+
+
+@pytest.mark.parametrize("n,F,ni,fo,kind,form", TS_FWD_CASES)
+def test_criterion_accepts_the_faithful_tiled_forward_and_rejects_a_lost_plane(n, F, ni, fo, kind, form):
+    """gemm_tsplit_fwd_k's arithmetic, emulated (emulate_tsplit_fwd): the faithful order passes the criterion; without the mm
+    term, without hl + lh, or with the gathered operand's l plane lost it fails.  At the Cora shape of the older test
+    (test_gathered_operand_gemms_on_the_bf16_pipe: 700 rows x 1436, split-K) the lost plane stays inside its bound
+    max|err| <= 5e-7 max(sum |a||b|) on either data (3.0e-7 - 4.0e-7): only the element-wise criterion sees it.  The other two
+    sit at that bound's edge (without mm 3.7e-7 - 5.1e-7 depending on the draw, without hl + lh 5.4e-7).  Measured on the emulation, faithful: max / rms within 3.8x / 1.9x of the fp32
+    baseline (9000 rows x 605), 1.2x / 1.3x elsewhere; each defect 3.3x - 78x."""
+    p = acc.gathered_problem(4000, F, ni, fo, n, n, kind, seed=n + F + fo)
+    feat = acc.gathered_feat(p)
+    ref = acc.matmul_reference(feat, p["w"].T)
+    kp = (F + ni + 3) // 4 * 4
+    pieces = acc.tsplit_fwd_pieces(n, kp) if form == "splitk" else None
+    assert form == "plain" or len(pieces) > 1
+    acc.assert_fp32_accuracy(acc.emulate_tsplit_fwd(feat, p["w"], k_pieces=pieces), *ref, what=f"faithful tiled forward {n}x{F + ni}")
+    for defect in ("drop_mm", "drop_hl_lh", "lost_l"):
+        got = acc.emulate_tsplit_fwd(feat, p["w"], defect, pieces)
+        a = acc.Accuracy(got, *ref)
+        assert not a.ok(), f"{defect}: {a}"
+        if (n, F) == (700, 1433) and defect == "lost_l":
+            assert _old_fwd_bound(got, ref) <= 5e-7, defect
+
+
+# (n, F, num_ind, f_out, kind): Cora's 2,700 rows x 1436 -> 256, Reddit-like 16k rows x 605 -> 128 (gemm_tsplit_dw_k<8>) and
+# 20k rows x 605 -> 256 (the swapped tile)
+TS_DW_CASES = [(2700, 1433, 3, 256, "normal"), (2700, 1433, 3, 256, "mixed"), (16000, 602, 3, 128, "normal"),
+               (20000, 602, 3, 256, "mixed"), (2700, 1433, 3, 256, "zeros")]
+
+
+@pytest.mark.parametrize("n,F,ni,fo,kind", TS_DW_CASES)
+def test_criterion_accepts_the_faithful_tiled_dw_and_rejects_a_lost_plane(n, F, ni, fo, kind):
+    """The weight gradient dW = dHᵀ feat in slabs of 32-row steps, emulated (emulate_tsplit_dw, with the product's slab count):
+    faithful passes the criterion; without mm, without hl + lh, or with feat's l plane lost it fails.  On N(0,1) data every
+    defect stays inside both older bounds (1e-6 of the largest magnitude, and 1e-6 of each output's own — the several-problem
+    test's): only the element-wise criterion sees them.  Measured on the emulation, faithful: within 1.2x / 0.9x
+    (max / rms); each defect at 1.5x - 19x max and 7.4x - 16x rms."""
+    p = acc.gathered_problem(8000, F, ni, fo, n, n, kind, seed=n + F + fo)
+    feat, dh = acc.gathered_feat(p), p["dh"][:n]
+    ref = acc.matmul_reference(dh.T, feat)
+    ns = acc.tsplit_dw_slabs(n, fo, (F + ni + 3) // 4 * 4)
+    assert ns > 1
+    acc.assert_fp32_accuracy(acc.emulate_tsplit_dw(dh, feat, ns), *ref, what=f"faithful tiled dW {n} rows, {ns} slabs")
+    for defect in ("drop_mm", "drop_hl_lh", "lost_l"):
+        got = acc.emulate_tsplit_dw(dh, feat, ns, defect)
+        a = acc.Accuracy(got, *ref)
+        assert not a.ok(), f"{defect}: {a}"
+        if kind == "normal":
+            scaled, own = _old_dw_bounds(got, ref)
+            assert scaled <= 1e-6 and own <= 1e-6, (defect, scaled, own)
+
+
+def test_criterion_rejects_one_slab_of_the_tiled_dw_losing_a_plane():
+    """One slab's l plane of feat lost (the other slabs faithful): rejected where the slab holds a fifth of the rows (600 rows,
+    5 slabs: rms 4.5x - 5.6x), for every one of the slabs.  (One slab of Cora's 22 moves the rms 2.5x only: under the factor —
+    a defect confined to so few rows is below what the criterion resolves.)"""
+    n, F, ni, fo = 600, 602, 3, 128
+    p = acc.gathered_problem(4000, F, ni, fo, n, n, "normal", seed=n + F + fo)
+    feat, dh = acc.gathered_feat(p), p["dh"][:n]
+    ref = acc.matmul_reference(dh.T, feat)
+    ns = acc.tsplit_dw_slabs(n, fo, 608)
+    assert ns == 5
+    acc.assert_fp32_accuracy(acc.emulate_tsplit_dw(dh, feat, ns), *ref, what="faithful")
+    for z in range(ns):
+        a = acc.Accuracy(acc.emulate_tsplit_dw(dh, feat, ns, "lost_l_slab", lost_slab=z), *ref)
+        assert not a.ok(), (z, a)
+
+
+def test_tiled_split_holds_tiny_operands_only_to_the_bf16_subnormal_step():
+    """The lower edge of the tiled GEMMs' range (include/grapes_hip.h, beside grapes_linear_fwd_gathered_split): each operand is
+    split on its own, so X rows at 1e-28 are held to 24 bits and pass the criterion; at 1e-35 the l plane (and for the smallest
+    entries the m plane) falls below bf16's smallest subnormal step 2^-133: each entry is held only to 2^-134 and the criterion
+    fails, while every output stays within 2^-134 sum_k |w| + 2^-20 mag.  The GPU test test_tiled_split_range_edges pins the
+    kernels to the same outcomes."""
+    n, F, ni, fo = 700, 602, 3, 256
+    p = acc.gathered_problem(2000, F, ni, fo, n, n, "normal", seed=5)
+    feat = acc.gathered_feat(p)
+    for scale, inside in ((1e-28, True), (1e-35, False)):
+        x = feat.copy()
+        x[:, :F] = (x[:, :F] * scale).astype(np.float32)
+        x[:, F:] = 0.0                                     # (indicators are 1.0: they would hold the outputs' scale up)
+        ref = acc.matmul_reference(x, p["w"].T)
+        got = acc.emulate_tsplit_fwd(x, p["w"], k_pieces=acc.tsplit_fwd_pieces(n, 608))
+        assert acc.Accuracy(got, *ref).ok() == inside, scale
+        assert acc.within_tiled_split_resolution(got, ref, torch.from_numpy(np.abs(p["w"]).astype(np.float64).sum(1))[None, :])

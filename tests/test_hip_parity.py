@@ -2752,6 +2752,12 @@ def test_weight_gradients_of_several_problems_in_one_launch():
             torch.cuda.synchronize()
             ref_gf = torch.zeros((fo, F + ni), dtype=torch.float64); mag_gf = torch.zeros_like(ref_gf)
             ref_z = torch.zeros((fo, F), dtype=torch.float64); mag_z = torch.zeros_like(ref_z)
+            # the element-wise criterion of oracle/accuracy.py on a seeded subset of columns (the indicator and last ones
+            # included): its fp32 baseline sums each problem in a fixed order
+            crng = np.random.default_rng(5)
+            cols = {"gf": np.unique(np.concatenate([crng.integers(0, F + ni, 64), np.arange(F - 1, F + ni)])),
+                    "z": np.unique(np.concatenate([crng.integers(0, F, 64), [F - 1]]))}
+            base = {"gf": torch.zeros((fo, len(cols["gf"]))), "z": torch.zeros((fo, len(cols["z"])))}
             for q, ((ids, dh, _), n) in enumerate(zip(probs_np, lives_now)):
                 if n == 0:
                     continue
@@ -2764,6 +2770,8 @@ def test_weight_gradients_of_several_problems_in_one_launch():
                     ref_z += d.t() @ feat; mag_z += d.abs().t() @ feat.abs()
                 else:
                     ref_gf += d.t() @ feat; mag_gf += d.abs().t() @ feat.abs()
+                g = "z" if q == 2 else "gf"
+                base[g] += accuracy_criterion.fp32_contract(dh[:n], feat[:, cols[g]].float())
             for name, got_a, got_b, ref, mag in (("gf", a_gf, b_gf, ref_gf, mag_gf), ("z", a_z, b_z, ref_z, mag_z)):
                 K = ref.shape[1]
                 assert bool(torch.isfinite(got_a).all())
@@ -2773,6 +2781,9 @@ def test_weight_gradients_of_several_problems_in_one_launch():
                 ea = float(((got_a[:, :K].cpu().double() - ref).abs() / mg).max())
                 eb = float(((got_b[:, :K].cpu().double() - ref).abs() / mg).max())
                 assert ea < 1e-6 and ea <= 1.1 * eb + 2e-8, (name, layout, lives_now, ea, eb)
+                c = cols[name]
+                accuracy_criterion.assert_fp32_accuracy(got_a.cpu()[:, c], ref[:, c], mag[:, c], base[name],
+                                                        what=f"multi {name} {layout} {lives_now}")
 
 
 def test_adam_with_pending_slab_sums_when_no_row_is_live():
