@@ -73,6 +73,10 @@ SIGNATURES = {
     "grapes_dropout_rows": (I32, [P, I64, P, I64, I32, P, I32, I32, I64, F32, U64, U64, P]),
     "grapes_rowlist_loss_workspace_bytes": (C.c_size_t, [I32, I32]),
     "grapes_rowlist_loss": (I32, [P, I64, I32, P, I32, P, P, P, F32, U64, U64, P, I64, I32, P, P, P, P, P]),
+    "grapes_saint_walk_nodes": (I32, [P, P, I32, I32, I32, P, P, U64, U64, P, P, P, P, P, P, P]),
+    "grapes_saint_subgraph_workspace_bytes": (SZ, [I32]),
+    "grapes_saint_subgraph": (I32, [P, P, P, P, P, I32, I32, P, P, P, P, P, P, P]),
+    "grapes_saint_masked_loss": (I32, [P, I64, I32, P, P, I32, P, P, P, P, I64, P, P, P, P]),
     "grapes_kernel_clock_enable": (I32, [P, I64]),
     "grapes_kernel_clock_launches": (I32, []),
     "grapes_kernel_clock_entry": (I32, [I32, P, P, P]),

@@ -1,0 +1,312 @@
+// GraphSAINT random-walk sampling and the masked batch loss (reference graphsaint.py:104 GraphSAINTRandomWalkSampler with
+// batch_size B, walk_length L, num_steps 1, sample_coverage 0; graphsaint.py:31-34 the loss over the batch's train rows).
+//
+//   saint_walk_nodes_k   ONE workgroup: B walks of L steps (torch_cluster random_walk, p = q = 1), then the ascending
+//                        duplicate-free node set of the B (L + 1) visited ids (walks.view(-1).unique()), sorted in LDS, its
+//                        count and node_map[node_idx[i]] = i; advances the device Philox offset last.
+//   saint_edge_count_k   one wavefront per local row: entries of the row whose column is in the node set
+//   saint_edge_scan_k    ONE workgroup: exclusive scan of those counts -> local row pointers, edge count (clamped to e_cap)
+//   saint_edge_write_k   one wavefront per local row: the induced edges (local row, local column) in CSR order
+//   saint_masked_loss_k  ONE workgroup: mean CE / BCE over the batch rows that are training rows, and d loss / d logits
+//
+// No kernel waits on another workgroup of its own launch.
+//
+// RNG contract (stream (seed, off), off = *d_offset when given): word i of the stream is word i & 3 of
+// philox4x32_10(off + i / 4, seed).  Root b (b < B) is (uint64(word b) * N) >> 32 — all 32 bits, so every node of a graph with
+// up to 2^32 nodes can be drawn.  The uniform of walk b's step t (t < L) is philox_uniform_at(seed, off, B + b L + t): 24 bits,
+// like torch.rand.  The launch advances *d_offset by ceil(B (L + 1) / 4) counters.
+//
+// Membership of the node set is tested as a sparse set: v is in the set iff m = node_map[v] < count and node_idx[m] == v, so
+// node_map needs no clearing (stale entries of other nodes are never trusted).
+#include "common.h"
+#include "philox.h"
+
+#define SAINT_THREADS 1024
+#define SAINT_MAX_IDS 16384          // B (L + 1) <= this: the node set is sorted in 64 KiB of LDS
+
+// inclusive scan of one value per thread over the whole workgroup (blockDim.x == SAINT_THREADS); *total = the sum
+__device__ __forceinline__ int saint_block_scan(int v, int* wsum, int* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int inc = wave_incl_scan(v);
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    if (w == 0) {
+        int s = lane < nw ? wsum[lane] : 0;
+        int si = wave_incl_scan(s);
+        if (lane < nw) wsum[lane] = si - s;          // exclusive prefix of the wavefront totals
+        if (lane == nw - 1) wsum[SAINT_THREADS / 64] = si;
+    }
+    __syncthreads();
+    inc += wsum[w];
+    *total = wsum[SAINT_THREADS / 64];
+    __syncthreads();
+    return inc;
+}
+
+// torch_cluster random_walk step (CPU, p = q = 1): a node without neighbours stays; otherwise
+// next = col[rowptr[v] + int64(u * deg)] with the product in fp32.  For deg > 2^24 the product can round up to deg: the index is
+// clamped to deg - 1.
+__device__ __forceinline__ int saint_step(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int v, float u) {
+    const int64_t a = rowptr[v], deg = rowptr[v + 1] - a;
+    if (deg <= 0) return v;
+    const float prod = u * (float)deg;
+    int64_t k = (int64_t)prod;
+    if (k > deg - 1) k = deg - 1;
+    return col[a + k];
+}
+
+__global__ __launch_bounds__(SAINT_THREADS) void saint_walk_nodes_k(
+        const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N, int B, int L, const int32_t* __restrict__ roots,
+        const float* __restrict__ uniforms, uint64_t seed, uint64_t offset, uint64_t* d_offset, int32_t* __restrict__ walks,
+        int32_t* __restrict__ node_idx, int32_t* __restrict__ d_count, int32_t* __restrict__ node_map, int P, int32_t* status) {
+    __shared__ int32_t ids[SAINT_MAX_IDS];
+    __shared__ int wsum[SAINT_THREADS / 64 + 1];
+    const int tid = threadIdx.x;
+    const uint64_t off = d_offset ? *d_offset : offset;
+    const int W = L + 1, M = B * W;
+    for (int b = tid; b < B; b += blockDim.x) {
+        int v;
+        if (roots) {
+            v = roots[b];
+            if ((unsigned)v >= (unsigned)N) { atomicOr(status, GRAPES_STATUS_BAD_INDEX); v = 0; }
+        } else {
+            const uint32_t word = philox4x32_10(off + (uint64_t)(b >> 2), seed).v[b & 3];
+            v = (int)(((uint64_t)word * (uint64_t)N) >> 32);
+        }
+        walks[(int64_t)b * W] = v;
+        ids[b * W] = v;
+        for (int t = 0; t < L; ++t) {
+            const int64_t ui = (int64_t)b * L + t;
+            const float u = uniforms ? uniforms[ui] : philox_uniform_at(seed, off, (long long)B + ui);
+            v = saint_step(rowptr, col, v, u);
+            walks[(int64_t)b * W + t + 1] = v;
+            ids[b * W + t + 1] = v;
+        }
+    }
+    for (int i = M + tid; i < P; i += blockDim.x) ids[i] = 0x7fffffff;       // padding sorts last
+    __syncthreads();
+    // bitonic sort of the P (a power of two) ids
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += blockDim.x) {
+                const int p = i ^ j;
+                if (p > i) {
+                    const int a = ids[i], c = ids[p];
+                    const bool up = (i & k) == 0;
+                    if ((a > c) == up) { ids[i] = c; ids[p] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // unique: thread t owns the contiguous chunk [t * per, (t + 1) * per)
+    const int per = (P + SAINT_THREADS - 1) / SAINT_THREADS;
+    const int lo = tid * per, hi = min(lo + per, M);
+    int heads = 0;
+    for (int i = lo; i < hi; ++i) heads += (i == 0 || ids[i] != ids[i - 1]) ? 1 : 0;
+    int total;
+    int pos = saint_block_scan(heads, wsum, &total) - heads;
+    for (int i = lo; i < hi; ++i) {
+        if (i == 0 || ids[i] != ids[i - 1]) {
+            const int v = ids[i];
+            node_idx[pos] = v;
+            node_map[v] = pos;
+            ++pos;
+        }
+    }
+    if (tid == 0) {
+        *d_count = total;
+        if (d_offset) *d_offset = off + (uint64_t)((M + 3) >> 2);
+    }
+}
+
+// one wavefront per local row i < count: cnt[i] = entries of node_idx[i]'s CSR row whose column is in the node set
+__global__ __launch_bounds__(256) void saint_edge_count_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                          const int32_t* __restrict__ node_idx, const int32_t* __restrict__ d_count,
+                                                          const int32_t* __restrict__ node_map, int n_cap, int32_t* __restrict__ cnt) {
+    const int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (i >= n_cap) return;
+    const int n = eff_count(d_count, n_cap);
+    if (i >= n) { if (lane == 0) cnt[i] = 0; return; }
+    const int v = node_idx[i];
+    const int64_t a = rowptr[v], e = rowptr[v + 1];
+    int c = 0;
+    for (int64_t j = a + lane; j < e; j += 64) {
+        const int u = col[j];
+        const int m = node_map[u];
+        c += ((unsigned)m < (unsigned)n && node_idx[m] == u) ? 1 : 0;
+    }
+    for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d, 64);
+    if (lane == 0) cnt[i] = c;
+}
+
+// ONE workgroup: rowptr_l[i] = sum of cnt[0 .. i) for i <= n_cap (rows at or past the count are empty); *d_e = min(total, e_cap)
+__global__ __launch_bounds__(SAINT_THREADS) void saint_edge_scan_k(const int32_t* __restrict__ cnt, const int32_t* __restrict__ d_count,
+                                                                   int n_cap, int e_cap, int32_t* __restrict__ rowptr_l,
+                                                                   int32_t* __restrict__ d_e, int32_t* status) {
+    __shared__ int wsum[SAINT_THREADS / 64 + 1];
+    const int n = eff_count(d_count, n_cap);
+    const int per = (n_cap + SAINT_THREADS - 1) / SAINT_THREADS;
+    const int lo = threadIdx.x * per, hi = min(lo + per, n);
+    int s = 0;
+    for (int i = lo; i < hi; ++i) s += cnt[i];
+    int total;
+    int run = saint_block_scan(s, wsum, &total) - s;
+    for (int i = lo; i < min(lo + per, n_cap); ++i) {
+        rowptr_l[i] = i < n ? run : total;
+        if (i < n) run += cnt[i];
+    }
+    if (threadIdx.x == 0) {
+        rowptr_l[n_cap] = total;
+        *d_e = total < e_cap ? total : e_cap;
+        if (total > e_cap && status) atomicOr(status, GRAPES_STATUS_EDGE_OVERFLOW);
+    }
+}
+
+// one wavefront per local row: the row's member entries, in CSR order, at rowptr_l[i] ..; nothing at or past e_cap is written
+__global__ __launch_bounds__(256) void saint_edge_write_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                          const int32_t* __restrict__ node_idx, const int32_t* __restrict__ d_count,
+                                                          const int32_t* __restrict__ node_map, int n_cap,
+                                                          const int32_t* __restrict__ rowptr_l, int e_cap,
+                                                          int32_t* __restrict__ src, int32_t* __restrict__ dst) {
+    const int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (i >= n_cap) return;
+    const int n = eff_count(d_count, n_cap);
+    if (i >= n) return;
+    const int v = node_idx[i];
+    const int64_t a = rowptr[v], e = rowptr[v + 1];
+    int base = rowptr_l[i];
+    for (int64_t j0 = a; j0 < e; j0 += 64) {
+        const int64_t j = j0 + lane;
+        int m = -1;
+        if (j < e) {
+            const int u = col[j];
+            const int mm = node_map[u];
+            if ((unsigned)mm < (unsigned)n && node_idx[mm] == u) m = mm;
+        }
+        const uint64_t bal = __ballot(m >= 0);
+        const int rank = __popcll(bal & ((1ull << lane) - 1ull));
+        const int p = base + rank;
+        if (m >= 0 && p < e_cap) { src[p] = i; dst[p] = m; }
+        base += __popcll(bal);
+        if (base >= e_cap) break;
+    }
+}
+
+// ONE workgroup.  Rows i < count of z [n_cap, ldz] are the batch's logits (row i = node node_idx[i]); the training rows are those
+// with train_mask[node_idx[i]] != 0, T of them.  CE (labels int64[N]): loss = sum_train (lse - z[y]) / T,
+// g = (softmax - onehot) / T.  BCE (labels_f fp32[N, C]): loss = sum_train sum_c (max(z, 0) - z y + log1p(exp(-|z|))) / (T C),
+// g = (sigmoid(z) - y) / (T C).  Other rows (and rows >= count) get g = 0.  T = 0: loss = 0 / 0 = NaN and g = 0, as torch's
+// mean over an empty selection.  Wavefront w sums rows w, w + 16, ... in double in that order; the 16 sums are added in wavefront
+// order: a fixed summation order, no float atomics.
+__global__ __launch_bounds__(SAINT_THREADS) void saint_masked_loss_k(
+        const float* __restrict__ z, int64_t ldz, int C, const int32_t* __restrict__ node_idx, const int32_t* __restrict__ d_count,
+        int n_cap, const uint8_t* __restrict__ train_mask, const int64_t* __restrict__ labels, const float* __restrict__ labels_f,
+        float* __restrict__ g, int64_t ldg, float* __restrict__ loss_out, int32_t* __restrict__ d_train, int32_t* status) {
+    __shared__ int wsum[SAINT_THREADS / 64 + 1];
+    __shared__ double lsum[SAINT_THREADS / 64];
+    const int n = eff_count(d_count, n_cap);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6;
+    int t = 0;
+    for (int i = tid; i < n; i += blockDim.x) t += train_mask[node_idx[i]] ? 1 : 0;
+    int T;
+    (void)saint_block_scan(t, wsum, &T);
+    const double denom = labels_f ? (double)T * (double)C : (double)T;
+    const float inv = T > 0 ? (float)(1.0 / denom) : 0.f;
+    double acc = 0.0;
+    for (int i = w; i < n_cap; i += nw) {
+        float* gr = g + (int64_t)i * ldg;
+        const int v = i < n ? node_idx[i] : -1;
+        if (v < 0 || !train_mask[v]) {
+            for (int c = lane; c < C; c += 64) gr[c] = 0.f;
+            continue;
+        }
+        const float* zr = z + (int64_t)i * ldz;
+        if (labels_f) {
+            const float* yr = labels_f + (int64_t)v * C;
+            float rl = 0.f;
+            for (int c = lane; c < C; c += 64) {
+                const float x = zr[c], y = yr[c];
+                rl += fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));
+                gr[c] = (1.f / (1.f + expf(-x)) - y) * inv;
+            }
+            acc += (double)wave_sum(rl);
+        } else {
+            const int64_t y = labels[v];
+            if (y < 0 || y >= C) {
+                if (lane == 0 && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+                for (int c = lane; c < C; c += 64) gr[c] = 0.f;
+                continue;
+            }
+            float mx = -INFINITY;
+            for (int c = lane; c < C; c += 64) mx = fmaxf(mx, zr[c]);
+            for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, 64));
+            float se = 0.f;
+            for (int c = lane; c < C; c += 64) se += expf(zr[c] - mx);
+            se = wave_sum(se);
+            const float lse = mx + logf(se);
+            for (int c = lane; c < C; c += 64) gr[c] = (expf(zr[c] - lse) - (c == y ? 1.f : 0.f)) * inv;
+            acc += (double)(lse - zr[y]);
+        }
+    }
+    if (lane == 0) lsum[w] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int q = 0; q < nw; ++q) s += lsum[q];
+        *loss_out = (float)(s / denom);             // T = 0: 0 / 0 = NaN
+        if (d_train) *d_train = T;
+    }
+}
+
+static int saint_pow2(int m) { int p = 64; while (p < m) p <<= 1; return p; }
+
+extern "C" int grapes_saint_walk_nodes(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, int32_t B, int32_t L,
+                                       const int32_t* roots, const float* uniforms, uint64_t philox_seed, uint64_t philox_offset,
+                                       uint64_t* d_philox_offset, int32_t* walks, int32_t* node_idx, int32_t* d_count,
+                                       int32_t* node_map, int32_t* status, grapes_stream_t stream) {
+    if (num_nodes <= 0 || B <= 0 || L < 0 || (int64_t)B * (L + 1) > SAINT_MAX_IDS) return GRAPES_EINVAL;
+    if (!rowptr || !col || !walks || !node_idx || !d_count || !node_map || (roots && !status)) return GRAPES_EINVAL;
+    hipLaunchKernelGGL(saint_walk_nodes_k, dim3(1), dim3(SAINT_THREADS), 0, (hipStream_t)stream, rowptr, col, num_nodes, B, L, roots,
+                       uniforms, philox_seed, philox_offset, d_philox_offset, walks, node_idx, d_count, node_map,
+                       saint_pow2(B * (L + 1)), status);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t grapes_saint_subgraph_workspace_bytes(int32_t n_cap) {
+    return (size_t)(n_cap > 0 ? n_cap : 1) * 4;
+}
+
+extern "C" int grapes_saint_subgraph(const int64_t* rowptr, const int32_t* col, const int32_t* node_idx, const int32_t* d_count,
+                                     const int32_t* node_map, int32_t n_cap, int32_t e_cap, int32_t* rowptr_l, int32_t* edge_src,
+                                     int32_t* edge_dst, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream) {
+    if (n_cap <= 0 || n_cap > SAINT_MAX_IDS || e_cap <= 0) return GRAPES_EINVAL;
+    if (!rowptr || !col || !node_idx || !d_count || !node_map || !rowptr_l || !edge_src || !edge_dst || !d_e || !workspace)
+        return GRAPES_EINVAL;
+    if ((uintptr_t)workspace & 3) return GRAPES_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    int32_t* cnt = (int32_t*)workspace;
+    const int grid = grapes_div_up((int64_t)n_cap * 64, 256);
+    hipLaunchKernelGGL(saint_edge_count_k, dim3(grid), dim3(256), 0, s, rowptr, col, node_idx, d_count, node_map, n_cap, cnt);
+    GRAPES_LAUNCH_CHECK();
+    hipLaunchKernelGGL(saint_edge_scan_k, dim3(1), dim3(SAINT_THREADS), 0, s, (const int32_t*)cnt, d_count, n_cap, e_cap, rowptr_l,
+                       d_e, status);
+    GRAPES_LAUNCH_CHECK();
+    hipLaunchKernelGGL(saint_edge_write_k, dim3(grid), dim3(256), 0, s, rowptr, col, node_idx, d_count, node_map, n_cap,
+                       (const int32_t*)rowptr_l, e_cap, edge_src, edge_dst);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int grapes_saint_masked_loss(const float* z, int64_t ldz, int32_t C, const int32_t* node_idx, const int32_t* d_count,
+                                        int32_t n_cap, const uint8_t* train_mask, const int64_t* labels, const float* labels_f,
+                                        float* g, int64_t ldg, float* loss_out, int32_t* d_train, int32_t* status,
+                                        grapes_stream_t stream) {
+    if (C <= 0 || n_cap <= 0 || ldz < C || ldg < C) return GRAPES_EINVAL;
+    if (!z || !node_idx || !train_mask || !g || !loss_out || ((labels == nullptr) == (labels_f == nullptr))) return GRAPES_EINVAL;
+    hipLaunchKernelGGL(saint_masked_loss_k, dim3(1), dim3(SAINT_THREADS), 0, (hipStream_t)stream, z, ldz, C, node_idx, d_count, n_cap,
+                       train_mask, labels, labels_f, g, ldg, loss_out, d_train, status);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}

@@ -1,0 +1,140 @@
+"""GraphSAINT random-walk baseline driver (reference graphsaint.py).
+
+    python -m grapes_amd.graphsaint --dataset cora --max_epoch 50 --runs 1
+
+* Flags and defaults of graphsaint.py:13-20: --use_normalization (accepted, unused as in the reference), --hidden_dim 256,
+  --dataset, --runs 1, --lr 0.01, --max_epoch 50, --embed_nodes, --node_emb_dim 64.  Added: --batch_size 256 and --walk_length 2
+  (graphsaint.py:104 hard-codes them), --num_steps 1, --seed, --engine graph|eager (saint.GraphedSaintTrainer /
+  saint.EagerSaintTrainer), --e_cap (edge capacity of a batch) and --large_graph auto|true|false (the row-blocked 64-bit
+  evaluation of full_graph.py; automatic from 2^31 CSR entries on).
+* Per run: GCN(F, [hidden_dim, C]) without dropout, Adam(params + embeddings, lr) (graphsaint.py:115-116); per epoch one step per
+  batch, then one full-graph forward that yields val and test: accuracy for 1-D labels, TP / FP / FN micro-F1 for multi-label
+  (graphsaint.py:46-88).  It prints `Epoch: .., Loss: .., Val: .., Test: ..`; a run's result is its last epoch's val metric, and
+  the driver ends with `Acc: mean ± std` over the runs (graphsaint.py:119-127).
+* Reference defects not reproduced: `print(data.x.grad.mean())` (graphsaint.py:38) raises without --embed_nodes — not printed;
+  `model.cpu()` in test() (graphsaint.py:47) moves the model off the GPU after epoch 1 — evaluation stays on the device;
+  `--embed_nodes` is parsed with type=bool, so "False" is True — parsed with main._bool here; with one run the std is NaN —
+  printed as 0.00 (as full_batch.py does).
+
+Datasets as in grapes_amd.main: a synthetic stand-in by name, or `module:function`.
+"""
+from __future__ import annotations
+
+import argparse
+import sys
+from typing import Optional, Sequence
+
+import torch
+
+from .main import _bool, load_data
+
+
+def _parser() -> argparse.ArgumentParser:
+    ap = argparse.ArgumentParser(prog="grapes_amd.graphsaint", description=__doc__.split("\n\n")[0])
+    ap.add_argument("--use_normalization", action="store_true")                     # graphsaint.py:13 (unused)
+    ap.add_argument("--hidden_dim", default=256, type=int)
+    ap.add_argument("--dataset", type=str)
+    ap.add_argument("--runs", default=1, type=int)
+    ap.add_argument("--lr", default=0.01, type=float)
+    ap.add_argument("--max_epoch", default=50, type=int)
+    ap.add_argument("--embed_nodes", default=False, type=_bool)
+    ap.add_argument("--node_emb_dim", default=64, type=int)
+    # additions of this driver
+    ap.add_argument("--batch_size", default=256, type=int)
+    ap.add_argument("--walk_length", default=2, type=int)
+    ap.add_argument("--num_steps", default=1, type=int)
+    ap.add_argument("--seed", default=None, type=int)
+    ap.add_argument("--engine", default="graph", choices=["graph", "eager"])
+    ap.add_argument("--e_cap", default=None, type=int)
+    ap.add_argument("--large_graph", default="auto", choices=["auto", "true", "false"])
+    return ap
+
+
+def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
+    args = _parser().parse_args(list(sys.argv[1:] if argv is None else argv))
+    if args.dataset is None:
+        raise SystemExit("--dataset is required")
+    return args
+
+
+def evaluate(model, x, g, y, val_mask, test_mask, large_graph: Optional[bool]):
+    """(val, test) of graphsaint.py:46-88 from ONE full-graph forward."""
+    from . import full_graph
+    from .eval import _metrics
+    with torch.no_grad():
+        if full_graph.use_large_path(g, large_graph):
+            both = val_mask | test_mask
+            _, _, pred = full_graph.evaluate_rows(model, x, g, y, both, True)
+            rows = torch.nonzero(both, as_tuple=False).reshape(-1)
+            out = []
+            for m in (val_mask, test_mask):
+                sel = m[rows]
+                p, t = pred[sel], y[rows[sel]]
+                if y.dim() == 1:
+                    out.append(float((p == t).float().mean().item()) if t.numel() else 0.0)
+                else:
+                    out.append(_f1(p, t > 0.5))
+            return tuple(out)
+        logits, _ = model(x, g, large_graph=False)
+        return tuple(_metrics(logits[m], y[m])[0] for m in (val_mask, test_mask))
+
+
+def _f1(y_pred, y_true) -> float:
+    tp = int((y_true & y_pred).sum()); fp = int((~y_true & y_pred).sum()); fn = int((y_true & ~y_pred).sum())
+    try:
+        precision, recall = tp / (tp + fp), tp / (tp + fn)
+        return 2 * (precision * recall) / (precision + recall)
+    except ZeroDivisionError:
+        return 0.0
+
+
+def _large_flag(v: str) -> Optional[bool]:
+    return {"auto": None, "true": True, "false": False}[v]
+
+
+def run(args, device=None, log=print) -> float:
+    from . import saint
+    from .graph import DeviceGraph
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    data = load_data(args, device)
+    if getattr(data, "rowptr", None) is not None:
+        g = DeviceGraph(data.rowptr, data.col, data.num_nodes)
+    else:
+        g = DeviceGraph.from_edge_index(data.edge_index.to(device), data.num_nodes)
+    if args.seed is not None:
+        torch.manual_seed(args.seed)
+    emb = []
+    if args.embed_nodes:                                                                     # graphsaint.py:94-101
+        log("Using learned node embeddings for features")
+        e = torch.empty(data.num_nodes, args.node_emb_dim)
+        torch.nn.init.normal_(e)
+        x = torch.nn.Parameter(e.to(device), requires_grad=True)
+        emb.append(x)
+    else:
+        x = data.x.to(device).contiguous()
+    y = data.y.to(device)
+    train_mask, val_mask, test_mask = (m.to(device) for m in (data.train_mask, data.val_mask, data.test_mask))
+    model = saint.build_model(x.shape[1], args.hidden_dim, data.num_classes, device)
+    tr = saint.make_trainer(args.engine, g, x, y, train_mask, model, args.lr, emb, batch_size=args.batch_size,
+                            walk_length=args.walk_length, num_steps=args.num_steps, seed=args.seed, e_cap=args.e_cap)
+    large = _large_flag(args.large_graph)
+    val = 0.0
+    for epoch in range(1, args.max_epoch + 1):                                               # graphsaint.py:118-121
+        loss = tr.epoch()
+        val, test = evaluate(model, x.detach(), g, y, val_mask, test_mask, large)
+        log(f"Epoch: {epoch:02d}, Loss: {loss:.4f}, Val: {val:.4f}, Test: {test:.4f}")
+    return val                                                                               # graphsaint.py:123
+
+
+def main(argv: Optional[Sequence[str]] = None) -> float:
+    args = parse_args(argv)
+    results = torch.empty(args.runs)
+    for r in range(args.runs):
+        results[r] = run(args)
+    std = float(results.std()) if args.runs > 1 else 0.0
+    print(f"Acc: {100 * float(results.mean()):.2f} ± {100 * std:.2f}")                    # graphsaint.py:124
+    return float(results.mean())
+
+
+if __name__ == "__main__":
+    main()

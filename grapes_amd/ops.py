@@ -1980,6 +1980,76 @@ def rowlist_loss(z, C: int, rows, labels, dinv, p: float = 0.0, seed: int = 0, o
     return loss, g, dcol
 
 
+# ------------------------------------------------------------------------------- GraphSAINT random walks (graphsaint.py:104)
+SAINT_MAX_IDS = 16384     # B (L + 1) of one batch: its node set is sorted in one workgroup's LDS
+
+
+def saint_walk_nodes(rowptr, col, num_nodes: int, batch_size: int, walk_length: int, roots=None, uniforms=None,
+                     philox_seed: int = 0, philox_offset: int = 0, d_philox_offset=None, node_map=None, status=None, out=None):
+    """(walks int32 [B, L + 1], node_idx int32 [B (L + 1)], count int32 [1]) of grapes_saint_walk_nodes: B random walks of L steps
+    and their ascending duplicate-free node set (the first *count entries of node_idx); node_map[node_idx[i]] = i.  roots int32 [B]
+    / uniforms fp32 [B L] replace the Philox draws.  out: the three tensors to write (captured steps)."""
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(roots, _i32, "roots", True); _chk(uniforms, _f32, "uniforms", True)
+    _chk(d_philox_offset, _i64, "d_philox_offset", True); _chk(node_map, _i32, "node_map"); _chk(status, _i32, "status", True)
+    B, L = int(batch_size), int(walk_length)
+    if B <= 0 or L < 0 or B * (L + 1) > SAINT_MAX_IDS:
+        raise ValueError(f"saint_walk_nodes: batch_size * (walk_length + 1) must be in 1 .. {SAINT_MAX_IDS}")
+    if roots is not None and roots.numel() < B:
+        raise ValueError("roots shorter than batch_size")
+    if uniforms is not None and uniforms.numel() < B * L:
+        raise ValueError("uniforms shorter than batch_size * walk_length")
+    dev = rowptr.device
+    if roots is not None and status is None:
+        status = torch.zeros(1, dtype=_i32, device=dev)
+    if out is None:
+        out = (torch.empty((B, L + 1), dtype=_i32, device=dev), torch.empty(B * (L + 1), dtype=_i32, device=dev),
+               torch.empty(1, dtype=_i32, device=dev))
+    walks, node_idx, count = out
+    _lib.check(lib().grapes_saint_walk_nodes(_p(rowptr), _p(col), int(num_nodes), B, L, _p(roots), _p(uniforms),
+                                             int(philox_seed) & (2 ** 64 - 1), int(philox_offset), _p(d_philox_offset), _p(walks),
+                                             _p(node_idx), _p(count), _p(node_map), _p(status), _stream()), "saint_walk_nodes")
+    return walks, node_idx, count
+
+
+def saint_subgraph(rowptr, col, node_idx, count, node_map, e_cap: int, status=None, out=None):
+    """(edge_src, edge_dst int32 [e_cap], e_count int32 [1], rowptr_l int32 [n_cap + 1]) of grapes_saint_subgraph: the subgraph
+    induced by the first *count ids of node_idx, relabelled to local ids, in CSR order.  Overflow of e_cap sets a status bit."""
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(node_idx, _i32, "node_idx"); _chk(count, _i32, "count")
+    _chk(node_map, _i32, "node_map"); _chk(status, _i32, "status", True)
+    n_cap, dev = node_idx.numel(), node_idx.device
+    if out is None:
+        out = (torch.empty(max(int(e_cap), 1), dtype=_i32, device=dev), torch.empty(max(int(e_cap), 1), dtype=_i32, device=dev),
+               torch.empty(1, dtype=_i32, device=dev), torch.empty(n_cap + 1, dtype=_i32, device=dev))
+    src, dst, d_e, rowptr_l = out
+    ws = _ws(lib().grapes_saint_subgraph_workspace_bytes(n_cap), dev)
+    _lib.check(lib().grapes_saint_subgraph(_p(rowptr), _p(col), _p(node_idx), _p(count), _p(node_map), n_cap, int(e_cap),
+                                           _p(rowptr_l), _p(src), _p(dst), _p(d_e), _p(ws), _p(status), _stream()),
+               "saint_subgraph")
+    return src, dst, d_e, rowptr_l
+
+
+def saint_masked_loss(z, C: int, node_idx, count, train_mask, labels, g=None, loss=None, d_train=None, status=None):
+    """(loss [1], g = d loss / d z [n_cap, C]) of grapes_saint_masked_loss: mean CrossEntropy (labels int64 [N]) or BCEWithLogits
+    (fp32 [N, C]) over the batch rows whose node is a training node; no training row: loss NaN, g = 0."""
+    _chk(node_idx, _i32, "node_idx"); _chk(count, _i32, "count", True); _chk(d_train, _i32, "d_train", True)
+    _chk(status, _i32, "status", True)
+    if z.dtype != _f32 or not z.is_cuda or z.dim() != 2 or z.stride(1) != 1:
+        raise _lib.GrapesHipError("saint_masked_loss: expected a CUDA fp32 matrix with unit column stride")
+    if not train_mask.is_cuda or train_mask.dtype not in (torch.bool, torch.uint8):
+        raise _lib.GrapesHipError("saint_masked_loss: train_mask must be a cuda bool / uint8 vector")
+    multi = labels.dim() == 2
+    _chk(labels, _f32 if multi else _i64, "labels")
+    n_cap = z.shape[0]
+    if g is None:
+        g = torch.empty((n_cap, int(C)), dtype=_f32, device=z.device)
+    if loss is None:
+        loss = torch.empty(1, dtype=_f32, device=z.device)
+    _lib.check(lib().grapes_saint_masked_loss(_p(z), z.stride(0), int(C), _p(node_idx), _p(count), n_cap, _p(train_mask),
+                                              None if multi else _p(labels), _p(labels) if multi else None, _p(g), g.stride(0),
+                                              _p(loss), _p(d_train), _p(status), _stream()), "saint_masked_loss")
+    return loss, g
+
+
 def classifier_loss(logits, local_rows, target_ids, labels, out_grad=None):
     """(loss_c [1], d loss_c / d logits [n_rows, C]) — main.py:260,267.  labels: int64 [N] or fp32 [N, C]."""
     _chk(logits, _f32, "logits"); _chk(local_rows, _i32, "local_rows"); _chk(target_ids, _i32, "target_ids")

@@ -1,0 +1,200 @@
+"""GraphSAINT random-walk training of a two-layer GCN (reference graphsaint.py:22-43, 104-121), in two forms.
+
+* EagerSaintTrainer — the readable form: modules.saint.GraphSAINTRandomWalkSampler batches, the GCN module with autograd and
+  torch.optim.Adam, exactly the reference's loop body.  Two host reads per step (the batch's node and edge counts).
+* GraphedSaintTrainer — the whole step as one captured hipGraph: walk + node set (one launch), induced subgraph, feature-row
+  gather, both GCN layers forward and backward, the masked loss, the embedding-row gradient (--embed_nodes) and FusedAdam.
+  Buffers are sized for n_cap = B (L + 1) nodes and e_cap edges; every kernel reads the live counts on the device, so a step
+  reads nothing back.  The status word (edge overflow, bad ids) is read once per epoch by check().
+
+Both draw from the same Philox stream (seed, device offset), so from one seed they sample the same batches.
+
+The loss of a batch without a training row is NaN with gradients exactly zero (torch's mean over an empty selection), and the
+optimiser still steps — as in the reference.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from . import ops
+from .modules.gcn import GCN
+from .modules.saint import GraphSAINTRandomWalkSampler
+
+
+class _GatherX(torch.autograd.Function):
+    """X[node_idx[:count]] (rows past the count are left as they are).  Backward: with into_grad the rows' gradients are added
+    into X.grad in place (node_idx is duplicate-free) and nothing is returned; otherwise a dense [N, F] gradient is returned."""
+
+    @staticmethod
+    def forward(ctx, X, node_idx, count, out, into_grad):
+        ctx.save_for_backward(node_idx)
+        ctx.count, ctx.X, ctx.into_grad = count, X, into_grad
+        return ops.gather_rows(X.detach(), node_idx, d_n=count, out=out)
+
+    @staticmethod
+    def backward(ctx, dx):
+        (node_idx,) = ctx.saved_tensors
+        X = ctx.X
+        dx = dx.contiguous()
+        if ctx.into_grad and X.grad is not None:
+            ops.scatter_rows(X.grad, node_idx, dx, d_n=ctx.count, accumulate=True)
+            return None, None, None, None, None
+        g = torch.zeros(X.shape, dtype=torch.float32, device=dx.device)
+        ops.scatter_rows(g, node_idx, dx, d_n=ctx.count)
+        return g, None, None, None, None
+
+
+class _MaskedLoss(torch.autograd.Function):
+    """graphsaint.py:31-34 on the device count of training rows (ops.saint_masked_loss)."""
+
+    @staticmethod
+    def forward(ctx, z, node_idx, count, train_mask, y, g, loss):
+        loss, g = ops.saint_masked_loss(z.contiguous(), z.shape[1], node_idx, count, train_mask, y, g=g, loss=loss)
+        ctx.g = g
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gl):
+        return ctx.g * gl, None, None, None, None, None, None
+
+
+def masked_loss(logits, node_idx, count, train_mask, y, g=None, loss=None):
+    """Mean CE (1-D y) / BCEWithLogits (2-D y) over the rows of `logits` whose node (node_idx) is a training node."""
+    return _MaskedLoss.apply(logits, node_idx, count, train_mask, y, g, loss)
+
+
+class EagerSaintTrainer:
+    def __init__(self, graph, x, y, train_mask, model: GCN, optimizer, batch_size=256, walk_length=2, num_steps=1, seed=None,
+                 e_cap=None):
+        self.loader = GraphSAINTRandomWalkSampler(graph, batch_size, walk_length, num_steps, seed=seed, e_cap=e_cap)
+        self.x, self.y, self.train_mask, self.model, self.optimizer = x, y, train_mask, model, optimizer
+
+    def step(self, roots=None, uniforms=None):
+        """One step (graphsaint.py:26-36); returns (loss tensor, batch)."""
+        b = self.loader.batch(roots, uniforms)
+        ids = b.node_idx.to(torch.int32)
+        self.optimizer.zero_grad()                                                          # graphsaint.py:29
+        x = _GatherX.apply(self.x, ids, None, None, False)                                  # batch.x (data.x gathered)
+        out = self.model(x, b.edge_index)                                                   # graphsaint.py:31
+        loss = masked_loss(out[0], ids, None, self.train_mask, self.y)                      # graphsaint.py:32-34
+        loss.backward()                                                                     # graphsaint.py:36
+        self.optimizer.step()                                                               # graphsaint.py:37
+        return loss.detach(), b
+
+    def epoch(self):
+        """Mean of the epoch's step losses (graphsaint.py:39-41; every batch counts data.num_nodes)."""
+        tot = 0.0
+        for _ in range(self.loader.num_steps):
+            loss, _ = self.step()
+            tot += float(loss)
+        return tot / self.loader.num_steps
+
+    def check(self):
+        self.loader.check()
+
+
+class GraphedSaintTrainer:
+    """The step of EagerSaintTrainer as one captured graph; the optimizer must be torch.optim.Adam(capturable=True) — its state
+    is stepped by ops.FusedAdam."""
+
+    def __init__(self, graph, x, y, train_mask, model: GCN, optimizer, batch_size=256, walk_length=2, num_steps=1, seed=None,
+                 e_cap=None):
+        self.loader = GraphSAINTRandomWalkSampler(graph, batch_size, walk_length, num_steps, seed=seed, e_cap=e_cap)
+        L = self.loader
+        g = L.graph
+        dev = g.device
+        self.x, self.y, self.train_mask, self.model, self.optimizer = x, y, train_mask, model, optimizer
+        self.n_cap, self.e_cap = L.n_cap, L.e_cap
+        C = model.gcn_layers[-1].out_channels
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.walk_out = (torch.zeros((L.batch_size, L.walk_length + 1), **i32), torch.zeros(self.n_cap, **i32), torch.zeros(1, **i32))
+        self.sub_out = (torch.zeros(self.e_cap, **i32), torch.zeros(self.e_cap, **i32), torch.zeros(1, **i32),
+                        torch.zeros(self.n_cap + 1, **i32))
+        self.xbuf = torch.zeros((self.n_cap, x.shape[1]), dtype=torch.float32, device=dev)
+        self.gbuf = torch.zeros((self.n_cap, C), dtype=torch.float32, device=dev)
+        self.lossbuf = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.loss_sum = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.embed = isinstance(x, torch.nn.Parameter) and x.requires_grad
+        self.params = [p for p in model.parameters()] + ([x] if self.embed else [])
+        self.fused = ops.FusedAdam([optimizer])          # creates .grad (zeros) and the Adam state in place
+        self.graph = None
+
+    def _body(self):
+        L = self.loader
+        g = L.graph
+        walks, node_idx, count = ops.saint_walk_nodes(g.rowptr, g.col, g.num_nodes, L.batch_size, L.walk_length,
+                                                      philox_seed=L.seed, d_philox_offset=L.philox_offset, node_map=g.node_map,
+                                                      status=L.status, out=self.walk_out)
+        src, dst, d_e, _ = ops.saint_subgraph(g.rowptr, g.col, node_idx, count, g.node_map, self.e_cap, status=L.status,
+                                              out=self.sub_out)
+        if self.n_cap <= ops._SMALL_GRAPH:
+            prep = ops.PreparedGraph.small_batch([(src, dst, d_e)], self.n_cap, d_n=count, status=L.status)[0]
+        else:
+            prep = ops.PreparedGraph(src, dst, self.n_cap, d_n=count, d_e=d_e, status=L.status, src_grouped=True)
+        for p in self.params:
+            p.grad.zero_()
+        xb = _GatherX.apply(self.x, node_idx, count, self.xbuf, True)
+        out = self.model(xb, prep)
+        loss = masked_loss(out[0], node_idx, count, self.train_mask, self.y, g=self.gbuf, loss=self.lossbuf)
+        loss.backward()
+        self.fused.step()
+        self.loss_sum.add_(self.lossbuf)
+
+    def capture(self):
+        """Captures the step.  One uncounted forward / backward runs first on a side stream (lazy initialisation); the weights,
+        the optimiser state and the Philox offset are as before it."""
+        L = self.loader
+        off0 = L.philox_offset.clone()
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            saved = [p.detach().clone() for p in self.params]
+            st = [(t.clone()) for p in self.params for t in self.optimizer.state[p].values()]
+            self._body()
+            for p, v in zip(self.params, saved):
+                p.data.copy_(v)
+            it = iter(st)
+            for p in self.params:
+                for t in self.optimizer.state[p].values():
+                    t.copy_(next(it))
+            L.philox_offset.copy_(off0)
+            self.loss_sum.zero_()
+        torch.cuda.current_stream().wait_stream(s)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._body()
+        return self
+
+    def step(self):
+        if self.graph is None:
+            self.capture()
+        self.graph.replay()
+
+    def epoch(self):
+        """num_steps replays; returns the mean step loss (one host read) after check()."""
+        self.loss_sum.zero_()
+        for _ in range(self.loader.num_steps):
+            self.step()
+        self.check()
+        return float(self.loss_sum.item()) / self.loader.num_steps
+
+    def check(self):
+        self.loader.check()
+
+
+def build_model(F: int, hidden_dim: int, C: int, device) -> GCN:
+    return GCN(F, hidden_dims=[hidden_dim, C]).to(device)                                   # graphsaint.py:115
+
+
+def make_trainer(engine: str, graph, x, y, train_mask, model, lr: float, embedding_params=(), **kw):
+    """graphsaint.py:116: Adam(model.parameters() + embedding_params, lr)."""
+    params = list(model.parameters()) + list(embedding_params)
+    if engine == "graph":
+        opt = torch.optim.Adam(params, lr=lr, capturable=True)
+        return GraphedSaintTrainer(graph, x, y, train_mask, model, opt, **kw)
+    if engine == "eager":
+        opt = torch.optim.Adam(params, lr=lr)
+        return EagerSaintTrainer(graph, x, y, train_mask, model, opt, **kw)
+    raise ValueError(f"engine must be graph or eager, not {engine!r}")

@@ -49,7 +49,8 @@ extern "C" {
  * 302: grapes_eval_predict; added within 302 (no signature of an earlier entry point changed): the full-batch path above 2^31
  * entries — grapes_csr_symmetric_check, grapes_csr_transpose, grapes_gcn_large_prepare, grapes_gcn_large_aggregate(_workspace_bytes);
  * and full-batch training over such graphs — grapes_rowlist_transpose(_workspace_bytes), grapes_rowlist_gather_t(_workspace_bytes),
- * grapes_dropout_rows, grapes_rowlist_loss(_workspace_bytes). */
+ * grapes_dropout_rows, grapes_rowlist_loss(_workspace_bytes); GraphSAINT random-walk training — grapes_saint_walk_nodes,
+ * grapes_saint_subgraph(_workspace_bytes), grapes_saint_masked_loss. */
 #define GRAPES_ABI_VERSION 302
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1091,6 +1092,32 @@ int grapes_rowlist_loss(const float* z, int64_t ldz, int32_t C, const int32_t* r
                         const float* labels_f, const float* dinv, float p, uint64_t philox_seed, uint64_t philox_offset, float* g,
                         int64_t ldg, int32_t ldg_cols, float* dcol, float* loss_out, void* workspace, int32_t* status,
                         grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ GraphSAINT random-walk sampling (graphsaint.py:104)
+ * GraphSAINTRandomWalkSampler(data, batch_size=B, walk_length=L) with num_steps 1, sample_coverage 0 (csrc/saint_kernels.hip).
+ * Stream (seed, off), off = *d_philox_offset when non-NULL, else philox_offset: root b = (uint64(word b) * N) >> 32 of the raw
+ * 32-bit Philox words (all 32 bits); walk b's step t uses philox_uniform(seed, off, B + b L + t) (24 bits, as torch.rand).
+ * A step from v: v itself if deg(v) = 0, else col[rowptr[v] + min(int64(u * deg), deg - 1)], the product in fp32 (torch_cluster
+ * random_walk, p = q = 1; the clamp only acts for deg > 2^24).  roots (int32[B]) / uniforms (fp32[B * L]), when non-NULL, replace
+ * the draws (tests); a root outside [0, N) ORs GRAPES_STATUS_BAD_INDEX into status (required then) and walks from node 0.
+ * ONE workgroup: walks int32[B, L + 1]; node_idx int32[>= B (L + 1)] = walks.view(-1).unique() (ascending), *d_count its size;
+ * node_map[node_idx[i]] = i (other entries untouched: membership is node_map[v] < count && node_idx[node_map[v]] == v).
+ * *d_philox_offset advances by ceil(B (L + 1) / 4).  B (L + 1) <= 16384. */
+int grapes_saint_walk_nodes(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, int32_t B, int32_t L, const int32_t* roots, const float* uniforms, uint64_t philox_seed, uint64_t philox_offset, uint64_t* d_philox_offset, int32_t* walks, int32_t* node_idx, int32_t* d_count, int32_t* node_map, int32_t* status, grapes_stream_t stream);
+/* graphsaint.py:104 adj.saint_subgraph(node_idx): the induced subgraph on the *d_count (<= n_cap <= 16384) ids of node_idx with
+ * node_map as written by grapes_saint_walk_nodes.  Edges (edge_src[k], edge_dst[k]) = (local row, local column) in CSR order —
+ * local row ascending, then the graph's column order (ascending for a sorted CSR); stored self-loops stay.  rowptr_l
+ * int32[n_cap + 1]: the local row pointers (rows at or past the count are empty).  *d_e = min(edges, e_cap); more than e_cap
+ * edges ORs GRAPES_STATUS_EDGE_OVERFLOW into status and only the first e_cap are written.  Three launches (per-row counts,
+ * one-workgroup scan, per-row writes).  workspace: grapes_saint_subgraph_workspace_bytes(n_cap), 4-byte aligned. */
+size_t grapes_saint_subgraph_workspace_bytes(int32_t n_cap);
+int grapes_saint_subgraph(const int64_t* rowptr, const int32_t* col, const int32_t* node_idx, const int32_t* d_count, const int32_t* node_map, int32_t n_cap, int32_t e_cap, int32_t* rowptr_l, int32_t* edge_src, int32_t* edge_dst, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream);
+/* graphsaint.py:31-34 loss_fn(out[0][train_idx], y[train_idx]), train_idx = batch.train_mask.nonzero(): over rows i < *d_count of
+ * the batch logits z [n_cap, ldz] (row i = node node_idx[i]) with train_mask[node_idx[i]] != 0 (uint8 / bool [N]), T of them
+ * (counted on the device; *d_train = T when non-NULL).  Mean CrossEntropy (labels int64[N]) or mean BCEWithLogits (labels_f
+ * fp32[N, C]).  g [n_cap, ldg] = d loss / d z (0 on other rows).  T = 0: *loss_out = NaN and g = 0 (torch's mean over an empty
+ * selection).  ONE workgroup, fixed summation order. */
+int grapes_saint_masked_loss(const float* z, int64_t ldz, int32_t C, const int32_t* node_idx, const int32_t* d_count, int32_t n_cap, const uint8_t* train_mask, const int64_t* labels, const float* labels_f, float* g, int64_t ldg, float* loss_out, int32_t* d_train, int32_t* status, grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:
