@@ -77,6 +77,12 @@ SIGNATURES = {
     "grapes_saint_subgraph_workspace_bytes": (SZ, [I32]),
     "grapes_saint_subgraph": (I32, [P, P, P, P, P, I32, I32, P, P, P, P, P, P, P]),
     "grapes_saint_masked_loss": (I32, [P, I64, I32, P, P, I32, P, P, P, P, I64, P, P, P, P]),
+    # GATConv aggregation (modules/gcn.py:45-72)
+    "grapes_gat_scores": (I32, [P, P, P, P, P, I32, P, I32, P]),
+    "grapes_gat_aggregate_workspace_bytes": (SZ, [I32, I32]),
+    "grapes_gat_aggregate_fwd": (I32, [P, P, P, P, P, P, P, P, I32, P, I32, I32, P, P, I32, P, P, P]),
+    "grapes_gat_aggregate_bwd_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_gat_aggregate_bwd": (I32, [P] * 18 + [I32, P, I32, P, P, P, P, I32, P, P, P]),
     "grapes_kernel_clock_enable": (I32, [P, I64]),
     "grapes_kernel_clock_launches": (I32, []),
     "grapes_kernel_clock_entry": (I32, [I32, P, P, P]),

@@ -20,6 +20,7 @@ import torch
 
 from . import full_graph, ops
 from .graph import DeviceGraph, as_device_graph
+from .modules.gcn import GCN, classifier_logits
 
 
 def _metrics(logits: torch.Tensor, y: torch.Tensor) -> Tuple[float, float]:
@@ -43,6 +44,8 @@ def _captured_evaluator(g, x, xkey, y, gcn_c, gcn_gf, args, num_ind, batches):
     indicator settings the trainer does not express)."""
     from .step_graph import GraphedTrainer
     if not batches or not isinstance(g, DeviceGraph) or y.dim() != 1:
+        return None
+    if not isinstance(gcn_c, GCN):               # (a GAT classifier, modules/gcn.py:45-72: the captured step is GCN only)
         return None
     B = int(batches[0][0].numel())
     hops, K = args.sampling_hops, args.num_samples
@@ -81,11 +84,13 @@ def evaluate(gcn_c, gcn_gf, data, args, adjacency, node_map=None, num_indicators
     if mask is None:
         mask = torch.ones(g.num_nodes, dtype=torch.bool, device=dev)
     mask = mask.to(dev)
+    if full_batch and not isinstance(gcn_c, GCN) and full_graph.use_large_path(g, large_graph):
+        raise ValueError("full-batch evaluation over a graph with 2^31 or more entries (the row-blocked path) takes a GCN classifier")
     if full_batch and full_graph.use_large_path(g, large_graph):
         return full_graph.evaluate_rows(gcn_c, x, g, y, mask, return_predictions,
                                         block_rows=getattr(args, "eval_block_rows", None))   # eval.py:47-70, row-blocked
     if full_batch:
-        logits, _ = gcn_c(x, g)                                                     # eval.py:50
+        logits, _ = classifier_logits(gcn_c, x, g)                                  # eval.py:50
         m = _metrics(logits[mask], y[mask])
         if return_predictions:
             return m + ((torch.argmax(logits, dim=1)[mask] if y.dim() == 1 else (logits[mask] > 0)),)
@@ -162,7 +167,7 @@ def evaluate(gcn_c, gcn_gf, data, args, adjacency, node_map=None, num_indicators
             b = ops.tensormap_map(g.node_map, kdst[:m].contiguous())
             preps.append(ops.PreparedGraph(a, b, n_all, status=g.status, src_grouped=True))          # eval.py:150
         xc = ops.gather_rows(x, alln[:n_all].contiguous())                          # eval.py:152
-        logits, _ = gcn_c(xc, preps)                                                # eval.py:153
+        logits, _ = classifier_logits(gcn_c, xc, preps)                             # eval.py:153
         lt = ops.tensormap_map(g.node_map, targets).long()
         preds.append(torch.argmax(logits, dim=1)[lt])                               # eval.py:154-155
     if cap is not None:

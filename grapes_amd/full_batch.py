@@ -6,7 +6,8 @@
   `eval_full_batch` false, `log_wandb` true).  `--config_file` is read first and the command line wins (full-batch.py:146-150).
   Flags that change nothing here are accepted and ignored: `log_wandb`, `notes`, `eval_on_cpu`, `eval_full_batch` and the
   sampler's (`sampling_hops`, `num_samples`, `use_indicators`, `lr_gf`, `loss_coef`, `log_z_init`, `reg_param`, `batch_size`).
-  Added: `--seed` (the synthetic data and the weights) and `--large_graph auto|true|false` (the row-blocked 64-bit path of
+  Added: `--classifier gcn|gat` (gat: the reference's GAT, modules/gcn.py:45-72, trained by autograd over the whole graph;
+  below 2^31 entries, no dropout), `--seed` (the synthetic data and the weights) and `--large_graph auto|true|false` (the row-blocked 64-bit path of
   full_graph.train_step: automatic from 2^31 CSR entries on).
 * Model `GCN(F, [hidden_dim, C], dropout)` and `Adam(lr=lr_gc)` (full-batch.py:72-76).  Each epoch is one full_graph.train_step
   over the whole graph — mean CrossEntropy, or mean BCEWithLogits for 2-D labels, on the train rows — then `step()`
@@ -29,7 +30,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from .main import _bool, load_data, read_config_file
+from .main import _bool, check_classifier, load_data, read_config_file
 
 # (name, type, default) — full-batch.py:26-50
 _FLAGS = [
@@ -41,7 +42,7 @@ _FLAGS = [
     ("config_file", str, None),
 ]
 # additions of this driver (not in the reference)
-_EXTRA = [("seed", int, None), ("large_graph", str, "auto")]
+_EXTRA = [("seed", int, None), ("large_graph", str, "auto"), ("classifier", str, "gcn")]
 
 
 def _parser() -> argparse.ArgumentParser:
@@ -49,6 +50,9 @@ def _parser() -> argparse.ArgumentParser:
     for name, typ, default in _FLAGS + _EXTRA:
         if name == "large_graph":
             ap.add_argument("--large_graph", choices=["auto", "true", "false"], default=default)
+        elif name == "classifier":
+            # (absent from the namespace unless given: a plain run's arguments stay the reference's + seed, large_graph)
+            ap.add_argument("--classifier", choices=["gcn", "gat"], default=argparse.SUPPRESS)
         else:
             ap.add_argument(f"--{name}", type=_bool if typ is bool else typ, default=default)
     return ap
@@ -63,6 +67,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
         args = ap.parse_args(read_config_file(args.config_file) + argv)
     if args.model_type != "gcn":
         raise NotImplementedError("only model_type=gcn is built (full-batch.py:72-73 builds no other model)")
+    if getattr(args, "classifier", "gcn") == "gat":
+        check_classifier(args)
     return args
 
 
@@ -74,7 +80,7 @@ def train(args, device=None, log=print) -> float:
     from . import full_graph
     from .eval import _metrics
     from .graph import DeviceGraph
-    from .modules.gcn import GCN
+    from .modules.gcn import GAT, GCN
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     data = load_data(args, device)
     if getattr(data, "rowptr", None) is not None:
@@ -86,7 +92,13 @@ def train(args, device=None, log=print) -> float:
     x = data.x.to(device).contiguous()
     y = data.y.to(device)
     large = _large_flag(args.large_graph)
-    gcn_c = GCN(x.shape[1], hidden_dims=[args.hidden_dim, data.num_classes], dropout=args.dropout).to(device)  # full-batch.py:73
+    gat = getattr(args, "classifier", "gcn") == "gat"
+    if gat:
+        if full_graph.use_large_path(g, large):
+            raise ValueError("--classifier gat: graphs with 2^31 or more entries (the row-blocked path) take a GCN classifier")
+        gcn_c = GAT(x.shape[1], hidden_dims=[args.hidden_dim, data.num_classes]).to(device)                  # modules/gcn.py:45-72
+    else:
+        gcn_c = GCN(x.shape[1], hidden_dims=[args.hidden_dim, data.num_classes], dropout=args.dropout).to(device)  # full-batch.py:73
     optimizer_c = torch.optim.Adam(gcn_c.parameters(), lr=args.lr_gc)                                        # full-batch.py:76
     train_mask, val_mask, test_mask = (m.to(device) for m in (data.train_mask, data.val_mask, data.test_mask))
     val_idx = val_mask.nonzero().squeeze(1)
@@ -94,8 +106,15 @@ def train(args, device=None, log=print) -> float:
         t0 = time.time()
         evaluating = (epoch + 1) % args.eval_frequency == 0
         optimizer_c.zero_grad()                                                                               # full-batch.py:103
-        loss_c, val_logits = full_graph.train_step(gcn_c, x, g, y, train_mask, eval_rows=val_idx if evaluating else None,
-                                                   large_graph=large)                                         # full-batch.py:100-104
+        if gat:                                                                                               # (autograd over the whole graph)
+            logits = gcn_c(x, g)
+            loss_c = full_graph._autograd_loss(logits[train_mask], y[train_mask])
+            loss_c.backward()
+            loss_c, val_logits = loss_c.detach(), (logits.detach()[val_idx] if evaluating else None)
+            del logits
+        else:
+            loss_c, val_logits = full_graph.train_step(gcn_c, x, g, y, train_mask, eval_rows=val_idx if evaluating else None,
+                                                       large_graph=large)                                     # full-batch.py:100-104
         optimizer_c.step()                                                                                    # full-batch.py:105
         log(f"epoch {epoch}: loss_c={float(loss_c):.6f}, {time.time() - t0:.2f}s")
         if evaluating:                                                                                        # full-batch.py:116-126
@@ -107,7 +126,7 @@ def train(args, device=None, log=print) -> float:
             test_acc, test_f1 = full_graph.evaluate_rows(gcn_c, x, g, y, test_mask, False)
     else:
         with torch.no_grad():
-            logits, _ = gcn_c(x, g, large_graph=False)
+            logits = gcn_c(x, g) if gat else gcn_c(x, g, large_graph=False)[0]
             test_acc, test_f1 = _metrics(logits[test_idx], y[test_idx])
             del logits
     log(f"test_accuracy={test_acc:.3f}, test_f1={test_f1:.3f}")

@@ -11,7 +11,8 @@
 * The training iteration is grapes_amd's: GraphedTrainer (one captured hipGraph per step) for the GFlowNet sampler,
   its REINFORCE variant, `--random_sampling`, `--reg_param`, `--dropout` (masks from the sampler's Philox stream) and
   `--embed_nodes` (learned node embeddings in place of data.x, optimised by optimizer_c: main.py:89-100,116);
-  `--engine eager` selects GrapesTrainer.
+  `--engine eager` selects GrapesTrainer.  `--classifier gat` (not in the reference's flags) makes the classifier
+  modules/gcn.py:45-72's GAT: eager engine, no dropout; the sampler and log-Z nets stay GCN (main.py:110-115).
 
 Datasets are outside this repository's scope (no dataset files and no network on the build machines): `--dataset`
 names a SYNTHETIC graph with the statistics of the corresponding benchmark (grapes_amd.synth.CONFIGS — cora,
@@ -43,7 +44,21 @@ _FLAGS = [
     ("notes", str, None), ("log_wandb", bool, False), ("config_file", str, None), ("reinforce_baseline", bool, False),
 ]
 # additions of this driver (not in the reference)
-_EXTRA = [("e_cap", int, 1 << 17), ("max_steps", int, None), ("engine", str, "auto"), ("pipeline", bool, True)]
+_EXTRA = [("e_cap", int, 1 << 17), ("max_steps", int, None), ("engine", str, "auto"), ("pipeline", bool, True),
+          ("classifier", str, "gcn")]
+_CLASSIFIERS = ("gcn", "gat")       # --classifier gat: the classifier is modules/gcn.py:45-72's GAT (the sampler nets stay GCN)
+
+
+def check_classifier(args) -> None:
+    """--classifier gat runs on the eager engine and has no dropout (modules/gcn.py:45-72)."""
+    classifier = getattr(args, "classifier", "gcn")
+    if classifier not in _CLASSIFIERS:
+        raise ValueError(f"--classifier must be one of {_CLASSIFIERS}, got {classifier!r}")
+    if classifier == "gat":
+        if getattr(args, "engine", "auto") == "graph":
+            raise ValueError("--classifier gat runs on the eager engine: the captured step (--engine graph) is GCN only")
+        if args.dropout:
+            raise ValueError("--classifier gat takes no --dropout: the reference's GAT has none (modules/gcn.py:45-72)")
 
 _DATASET_ALIASES = {"ogbn-arxiv": "arxiv", "ogbn-products": "products", "reddit2": "reddit"}
 
@@ -85,6 +100,7 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
         args = ap.parse_args(read_config_file(args.config_file) + argv)
     if args.model_type != "gcn":
         raise NotImplementedError("only model_type=gcn is built (the reference's other model classes are dead code)")
+    check_classifier(args)
     return args
 
 
@@ -137,7 +153,7 @@ def _batches(idx: torch.Tensor, batch_size: int):
 def train(args, device=None, log=print):
     from .eval import evaluate
     from .graph import DeviceGraph
-    from .modules.gcn import GCN
+    from .modules.gcn import GAT, GCN
     from .step import GrapesTrainer
     from .step_graph import GraphedTrainer
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
@@ -163,7 +179,10 @@ def train(args, device=None, log=print):
         x = data.x.to(device).contiguous()
     F, C = x.shape[1], data.num_classes
     num_ind = args.sampling_hops + 1 if args.use_indicators else 0                                 # main.py:104-107
-    gcn_c = GCN(F, hidden_dims=[args.hidden_dim, C], dropout=args.dropout).to(device)              # main.py:110
+    if getattr(args, "classifier", "gcn") == "gat":
+        gcn_c = GAT(F, hidden_dims=[args.hidden_dim, C]).to(device)                                # modules/gcn.py:45-72
+    else:
+        gcn_c = GCN(F, hidden_dims=[args.hidden_dim, C], dropout=args.dropout).to(device)          # main.py:110
     gcn_gf = GCN(F + num_ind, hidden_dims=[args.hidden_dim, 1]).to(device)                          # main.py:112-113
     gcn_z = GCN(F, hidden_dims=[args.hidden_dim, 1]).to(device)                                     # main.py:114
     opt_c = torch.optim.Adam(list(gcn_c.parameters()) + embedding_params, lr=args.lr_gc, capturable=True)   # main.py:116
@@ -172,7 +191,7 @@ def train(args, device=None, log=print):
     val_idx, test_idx = data.val_mask.nonzero().squeeze(1), data.test_mask.nonzero().squeeze(1)
     engine = args.engine
     if engine == "auto":
-        engine = "graph"
+        engine = "eager" if getattr(args, "classifier", "gcn") == "gat" else "graph"
     common = dict(sampling_hops=args.sampling_hops, num_samples=args.num_samples, use_indicators=args.use_indicators,
                   loss_coef=args.loss_coef, log_z_init=args.log_z_init, reinforce_baseline=args.reinforce_baseline,
                   optimizer_c=opt_c, optimizer_gf=opt_gf, philox_seed=args.seed or 0)

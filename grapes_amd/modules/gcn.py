@@ -1,7 +1,8 @@
-"""Drop-in ``GCN`` (reference modules/gcn.py:9-42) whose layers run the gfx950 GCNConv kernels.
+"""Drop-in ``GCN`` (reference modules/gcn.py:9-42) and ``GAT`` (modules/gcn.py:45-72) whose layers run the gfx950 kernels.
 
 state_dict keys match PyG's GCNConv inside the reference module: ``gcn_layers.{i}.lin.weight``
-([out,in]) and ``gcn_layers.{i}.bias``.
+([out,in]) and ``gcn_layers.{i}.bias``; for GAT [PyG-recall: torch_geometric 2.5.2 GATConv] ``gat_layers.{i}.lin.weight``,
+``.att_src`` / ``.att_dst`` ([1, 1, out]) and ``.bias``.
 """
 from __future__ import annotations
 
@@ -239,3 +240,111 @@ class GCN(nn.Module):
         logits = self._drop(logits)                                            # gcn.py:37
         memory_alloc = _memory_allocated_mb()                                  # gcn.py:40
         return logits, memory_alloc
+
+
+# ------------------------------------------------------------------------------------------------ GAT (modules/gcn.py:45-72)
+class _GATConvFn(torch.autograd.Function):
+    """out = softmax-weighted gather of H = X Wᵀ (+ b, ReLU): grapes_linear_fwd, grapes_gat_scores, grapes_gat_aggregate_fwd.
+    The backward recomputes the attention weights from the saved scores and (row max, log sum): nothing is stored per edge."""
+
+    @staticmethod
+    def forward(ctx, x, weight, att_src, att_dst, bias, prep, relu):
+        h = ops.linear_fwd(x, weight, d_n=prep.d_n)                           # H = X W^T   (MFMA fp32)
+        a_src, a_dst = att_src.reshape(-1), att_dst.reshape(-1)
+        s_src, s_dst = ops.gat_scores(h, a_src, a_dst, d_n=prep.d_n)
+        out, row_ms = ops.gat_aggregate_fwd(h, s_src, s_dst, prep, bias, relu)
+        ctx.prep, ctx.relu = prep, relu
+        ctx.save_for_backward(x, weight, att_src, att_dst, bias, h, s_src, s_dst, row_ms, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight, att_src, att_dst, bias, h, s_src, s_dst, row_ms, out = ctx.saved_tensors
+        prep = ctx.prep
+        dh, da_src, da_dst, dbias = ops.gat_aggregate_bwd(dout.contiguous(), out, h, s_src, s_dst, row_ms, att_src.reshape(-1),
+                                                          att_dst.reshape(-1), prep, bias, ctx.relu)
+        dw = ops.linear_bwd_weight(dh, x, d_n=prep.d_n)
+        dx = ops.linear_bwd_input(dh, weight, d_n=prep.d_n) if ctx.needs_input_grad[0] else None
+        return dx, dw, da_src.view_as(att_src), da_dst.view_as(att_dst), dbias, None, None
+
+
+def _gat_graph(edge_index, n: int) -> ops.PreparedGraph:
+    """The layer's graph: a PreparedGraph, an edge-index tensor, or a DeviceGraph below 2^31 entries."""
+    if hasattr(edge_index, "full_graph_plan") and full_graph.use_large_path(edge_index, None):
+        raise ValueError("GAT over a graph with 2^31 or more entries is not built: the row-blocked 64-bit path of "
+                         "full_graph.py is GCN only")
+    return prepare_edges(edge_index, n)
+
+
+class GATConv(nn.Module):
+    """PyG GATConv(in_channels, out_channels) with every other argument at its default, as modules/gcn.py:53-57 builds it
+    [PyG-recall]: one head, LeakyReLU slope 0.2, self-loops re-added, no attention dropout, bias."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, dropout: float = 0.0, edge_dim=None):
+        super().__init__()
+        if heads != 1:
+            raise NotImplementedError("GATConv: only heads=1 is built (the reference passes no other value)")
+        if dropout:
+            raise NotImplementedError("GATConv: attention dropout is not built (the reference leaves it at 0)")
+        if edge_dim is not None:
+            raise NotImplementedError("GATConv: edge features (edge_dim) are not built")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.lin = nn.Linear(in_channels, out_channels, bias=False)
+        self.att_src = nn.Parameter(torch.empty(1, 1, out_channels))
+        self.att_dst = nn.Parameter(torch.empty(1, 1, out_channels))
+        self.bias = nn.Parameter(torch.zeros(out_channels))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        a = math.sqrt(6.0 / (self.in_channels + self.out_channels))    # PyG glorot
+        b = math.sqrt(6.0 / (1 + self.out_channels))                   # glorot on [1, 1, C]: fan = size(-2) + size(-1)
+        with torch.no_grad():
+            self.lin.weight.uniform_(-a, a)
+            self.att_src.uniform_(-b, b)
+            self.att_dst.uniform_(-b, b)
+            self.bias.zero_()
+
+    def forward(self, x, edge_index, relu: bool = False):
+        if not x.is_cuda:
+            raise ops._lib.GrapesHipError("GATConv input must be a cuda tensor (grapes_amd has no CPU path)")
+        x = x.contiguous()
+        if x.dtype != torch.float32:
+            x = x.float()
+        prep = _gat_graph(edge_index, x.shape[0])
+        return _GATConvFn.apply(x, self.lin.weight, self.att_src, self.att_dst, self.bias, prep, relu)
+
+
+class GAT(nn.Module):
+    """modules/gcn.py:45-72: the same layer-wise adjacency routing as GCN, no dropout, and logits ONLY (gcn.py:72)."""
+
+    def __init__(self, in_features: int, hidden_dims: "list[int]"):
+        super(GAT, self).__init__()
+        dims = [in_features] + hidden_dims
+        gat_layers = []
+        for i in range(len(hidden_dims) - 1):
+            gat_layers.append(GATConv(in_channels=dims[i], out_channels=dims[i + 1]))
+        gat_layers.append(GATConv(in_channels=dims[-2], out_channels=dims[-1]))
+        self.gat_layers = nn.ModuleList(gat_layers)
+
+    def forward(self, x: torch.Tensor, edge_index: Union[torch.Tensor, "list[torch.Tensor]"]) -> torch.Tensor:
+        if not x.is_cuda:
+            raise ops._lib.GrapesHipError("GAT input must be a cuda tensor (grapes_amd has no CPU path)")
+        layerwise_adjacency = type(edge_index) == list
+        n_layers = len(self.gat_layers)
+        for i in range(1, n_layers):
+            edges = edge_index[-i] if layerwise_adjacency else edge_index      # gcn.py:65
+            x = self.gat_layers[i - 1](x, edges, relu=True)                    # gcn.py:66-67 (ReLU fused)
+        edges = edge_index[0] if layerwise_adjacency else edge_index           # gcn.py:69
+        return self.gat_layers[n_layers - 1](x, edges)                         # gcn.py:70,72
+
+
+def classifier_layers(model) -> nn.ModuleList:
+    """The conv layers of a classifier, GCN (gcn_layers) or GAT (gat_layers)."""
+    return model.gat_layers if isinstance(model, GAT) else model.gcn_layers
+
+
+def classifier_logits(model, x, edge_index):
+    """(logits, allocated MiB): GCN.forward returns the pair (gcn.py:42), GAT.forward the logits alone (gcn.py:72)."""
+    if isinstance(model, GAT):
+        return model(x, edge_index), _memory_allocated_mb()
+    return model(x, edge_index)

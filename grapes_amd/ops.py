@@ -1492,6 +1492,75 @@ def gcn_aggregate_bwd(dout, prep: PreparedGraph, relu_out=None, want_bias=True, 
     return dh, dbias
 
 
+# ------------------------------------------------------------------------------- GATConv aggregation (modules/gcn.py:45-72)
+def _gat_width(f: int):
+    if f < 1 or f > 1024 or (f > 256 and f % 4):
+        raise ValueError(f"GAT aggregation: width {f} is not built (any width up to 256, multiples of 4 up to 1024)")
+
+
+def gat_scores(h, a_src, a_dst, d_n=None):
+    """(s_src, s_dst) = (H a_src, H a_dst): the per-node halves of GATConv's attention logits, one read of H."""
+    _chk(h, _f32, "h"); _chk(a_src, _f32, "a_src"); _chk(a_dst, _f32, "a_dst")
+    n, f = h.shape
+    _gat_width(f)
+    if a_src.numel() != f or a_dst.numel() != f:
+        raise ValueError("a_src / a_dst must hold one value per column of h")
+    s_src = torch.empty(max(n, 1), dtype=_f32, device=h.device)
+    s_dst = torch.empty(max(n, 1), dtype=_f32, device=h.device)
+    _lib.check(lib().grapes_gat_scores(_p(h), _p(a_src), _p(a_dst), _p(s_src), _p(s_dst), n, _p(d_n), f, _stream()), "gat_scores")
+    return s_src, s_dst
+
+
+def gat_aggregate_fwd(h, s_src, s_dst, prep: PreparedGraph, bias=None, relu=False, out=None):
+    """(out, row_ms): out_i = sum_j softmax_j(LeakyReLU(s_src[j] + s_dst[i])) H_j + bias (+ReLU) over prep's by-target CSR plus
+    one unit self-loop per node; row_ms [n, 2] = (row maximum, log of the softmax sum), what gat_aggregate_bwd recomputes the
+    attention weights from."""
+    _chk(h, _f32, "h"); _chk(s_src, _f32, "s_src"); _chk(s_dst, _f32, "s_dst"); _chk(bias, _f32, "bias", True)
+    n, f = h.shape
+    _gat_width(f)
+    if n != prep.n or s_src.numel() < n or s_dst.numel() < n:
+        raise ValueError("h, s_src and s_dst need one row per node of the prepared graph")
+    if out is None:
+        out = torch.empty_like(h)
+    row_ms = torch.empty((max(n, 1), 2), dtype=_f32, device=h.device)
+    use_items = prep.items_fwd and prep.n > _SMALL_GRAPH
+    ws = _ws(lib().grapes_gat_aggregate_workspace_bytes(prep.item_cap, f), h.device) if use_items else None
+    _lib.check(lib().grapes_gat_aggregate_fwd(_p(h), _p(s_src), _p(s_dst), _p(prep.rowptr_t), _p(prep.csr_src), _p(bias), _p(out),
+                                              _p(row_ms), n, _p(prep.d_n), f, 1 if relu else 0,
+                                              _p(prep.items_t) if use_items else None,
+                                              _p(prep.n_items_t) if use_items else None,
+                                              prep.item_cap if use_items else 0, _p(ws), _p(prep.status), _stream()),
+               "gat_aggregate_fwd")
+    return out, row_ms
+
+
+def gat_aggregate_bwd(dout, out, h, s_src, s_dst, row_ms, a_src, a_dst, prep: PreparedGraph, bias=None, relu=False):
+    """Returns (dh, da_src, da_dst, dbias) for gat_aggregate_fwd + gat_scores (dh includes the scores' share, ds_src a_src +
+    ds_dst a_dst).  `out` is the forward's output; dout is not modified."""
+    for t, name in ((dout, "dout"), (out, "out"), (h, "h"), (s_src, "s_src"), (s_dst, "s_dst"), (row_ms, "row_ms"),
+                    (a_src, "a_src"), (a_dst, "a_dst")):
+        _chk(t, _f32, name)
+    _chk(bias, _f32, "bias", True)
+    n, f = dout.shape
+    _gat_width(f)
+    if n != prep.n or out.shape != dout.shape or h.shape != dout.shape:
+        raise ValueError("dout, out and h must be [n, f] over the prepared graph's nodes")
+    dev = dout.device
+    dh = torch.empty_like(dout)
+    da_src = torch.empty(f, dtype=_f32, device=dev); da_dst = torch.empty(f, dtype=_f32, device=dev)
+    dbias = torch.empty(f, dtype=_f32, device=dev)
+    use_items = prep.n > _SMALL_GRAPH
+    cap = prep.item_cap if use_items else 0
+    ws = _ws(lib().grapes_gat_aggregate_bwd_workspace_bytes(n, cap, f), dev)
+    _lib.check(lib().grapes_gat_aggregate_bwd(_p(dout), _p(out), _p(bias), 1 if relu else 0, _p(h), _p(s_src), _p(s_dst), _p(row_ms),
+                                              _p(a_src), _p(a_dst), _p(prep.rowptr_t), _p(prep.csr_src), _p(prep.rowptr_s),
+                                              _p(prep.csr_dst), _p(dh), _p(da_src), _p(da_dst), _p(dbias), n, _p(prep.d_n), f,
+                                              _p(prep.items_t) if use_items else None, _p(prep.n_items_t) if use_items else None,
+                                              _p(prep.items_s) if use_items else None, _p(prep.n_items_s) if use_items else None,
+                                              cap, _p(ws), _p(prep.status), _stream()), "gat_aggregate_bwd")
+    return dh, da_src, da_dst, dbias
+
+
 # ------------------------------------------------------------------------------- sampler
 def gumbel_topk(logits, k, uniforms=None, logit_index=None, candidate_ids=None, n=None, d_n=None, mode=0,
                 philox_seed=0, philox_offset=0, d_philox_offset=None, want_log_prob=True, want_keys=False,

@@ -20,6 +20,7 @@ import torch.nn as nn
 
 from . import ops
 from .graph import DeviceGraph
+from .modules.gcn import classifier_layers, classifier_logits
 from .modules.utils import sample_neighborhoods_from_probs
 
 
@@ -231,8 +232,8 @@ class GrapesTrainer:
             return out
         preps = [ops.PreparedGraph(a, b, n_all, status=g.status, src_grouped=True) for a, b, _ in edge_lists]
         xc = self._features(all_nodes, differentiable=True)                           # main.py:256
-        logits, mem = self.gcn_c(xc, preps)                                          # main.py:257
-        n_layers = len(self.gcn_c.gcn_layers)
+        logits, mem = classifier_logits(self.gcn_c, xc, preps)                       # main.py:257 (GCN or GAT classifier)
+        n_layers = len(classifier_layers(self.gcn_c))
         used = [preps[-i] for i in range(1, n_layers)] + [preps[0]]                  # gcn.py:31,35
         agg_counts += [p.rowptr_t[n_all] for p in used]
         tgt = self.y[targets.long()]

@@ -135,6 +135,9 @@ class GraphedTrainer:
         # greedy draws (top-k of the inclusion probabilities, eval.py:126-130, no noise), slice_adjacency with its arguments
         # swapped (rows = previous_nodes, cols = the new layer: eval.py:140-142), the classifier's forward pass and the targets'
         # predicted classes (eval.py:153-155); no log-Z net, no loss, no backward pass, no optimiser.  out["pred"] = int64[B].
+        if not hasattr(gcn_c, "gcn_layers"):
+            raise NotImplementedError(f"the captured step takes a GCN classifier, not {type(gcn_c).__name__} (modules/gcn.py:45-72's "
+                                      "GAT trains through the eager GrapesTrainer)")
         self.evaluate = bool(evaluate)
         if self.evaluate:
             gcn_z, optimizer_c, optimizer_gf, pipeline = None, None, None, False

@@ -50,7 +50,8 @@ extern "C" {
  * entries — grapes_csr_symmetric_check, grapes_csr_transpose, grapes_gcn_large_prepare, grapes_gcn_large_aggregate(_workspace_bytes);
  * and full-batch training over such graphs — grapes_rowlist_transpose(_workspace_bytes), grapes_rowlist_gather_t(_workspace_bytes),
  * grapes_dropout_rows, grapes_rowlist_loss(_workspace_bytes); GraphSAINT random-walk training — grapes_saint_walk_nodes,
- * grapes_saint_subgraph(_workspace_bytes), grapes_saint_masked_loss. */
+ * grapes_saint_subgraph(_workspace_bytes), grapes_saint_masked_loss; the GAT classifier (modules/gcn.py:45-72) — grapes_gat_scores,
+ * grapes_gat_aggregate_fwd / _bwd (+ _workspace_bytes each). */
 #define GRAPES_ABI_VERSION 302
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -638,6 +639,46 @@ int grapes_gcn_aggregate_bwd(const float* dout, const float* relu_out, const int
                              const int32_t* d_n, int32_t f, const int32_t* long_items,
                              const int32_t* d_n_items, int32_t item_cap, void* workspace,
                              uint32_t* d_ticket, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ GATConv aggregation (csrc/gat_kernels.hip)
+ * modules/gcn.py:45-72: GAT stacks GATConv(in_channels, out_channels) layers with PyG's defaults (torch_geometric 2.5.2, not in
+ * the reference tree: heads = 1, negative_slope = 0.2, add_self_loops, no attention dropout).  With H = X W^T (grapes_linear_fwd):
+ *   e_ij = LeakyReLU(s_src[j] + s_dst[i], 0.2)   alpha_ij = softmax over the edges j -> i   out_i = sum_j alpha_ij H_j + bias
+ * over the edge set of grapes_gcn_prepare: stored self-loops dropped, one unit self-loop per node implied, duplicates kept.
+ * Widths: any f <= 256; f % 4 == 0 with 16-byte aligned rows up to 1024.  Every sum has a fixed order (no floating-point
+ * atomics): results are bit-identical from run to run.  status: GRAPES_STATUS_BAD_INDEX when a CSR entry is outside [0, n)
+ * (the entry is dropped). */
+/* modules/gcn.py:66,70 (the attention scores inside GATConv): s_src[r] = H[r] . a_src, s_dst[r] = H[r] . a_dst  (a_* [f]). */
+int grapes_gat_scores(const float* h, const float* a_src, const float* a_dst, float* s_src, float* s_dst, int32_t n,
+                      const int32_t* d_n, int32_t f, grapes_stream_t stream);
+/* modules/gcn.py:66-67,70 (GATConv's propagate, + the ReLU of gcn.py:67 when relu != 0): edge softmax and weighted gather in
+ * ONE pass over the by-target CSR (online softmax: running maximum, rescaled sum and accumulator in registers), bias and ReLU in
+ * the epilogue.  row_ms [n][2] receives (row maximum, log of the softmax sum) for the backward.  long_items / d_n_items /
+ * item_cap / workspace as grapes_gcn_aggregate_fwd (by-target half of gcn_prepare's item table; NULL: every row by one group of
+ * lanes): rows longer than GRAPES_LONG_ROW are cut into items whose (max, sum, accumulator) are merged in chunk order.
+ * workspace: grapes_gat_aggregate_workspace_bytes(item_cap, f), 16-byte aligned.  bias may be NULL. */
+size_t grapes_gat_aggregate_workspace_bytes(int32_t item_cap, int32_t f);
+int grapes_gat_aggregate_fwd(const float* h, const float* s_src, const float* s_dst, const int32_t* rowptr_t,
+                             const int32_t* csr_src, const float* bias, float* out, float* row_ms, int32_t n,
+                             const int32_t* d_n, int32_t f, int32_t relu, const int32_t* long_items,
+                             const int32_t* d_n_items, int32_t item_cap, void* workspace, int32_t* status,
+                             grapes_stream_t stream);
+/* Backward of the above (autograd through modules/gcn.py:66-67,70).  With G = dout (gated by out > 0 when relu != 0),
+ * c_i = G_i . (out_i - bias), slope_ij = 1 if s_src[j] + s_dst[i] > 0 else 0.2 and g_ij = alpha_ij (G_i . H_j - c_i) slope_ij:
+ *   ds_src[j] = sum_i g_ij   ds_dst[i] = sum_j g_ij   dh[j] = sum_i alpha_ij G_i + ds_src[j] a_src + ds_dst[j] a_dst
+ *   da_src = sum_j ds_src[j] H_j   da_dst = sum_i ds_dst[i] H_i   dbias = sum_i G_i        (each may be NULL)
+ * alpha is recomputed from the scores and row_ms in a pass over the by-target CSR (ds_dst) and one over the by-source CSR
+ * (dh, ds_src); the three column sums are per-workgroup partials added in a fixed tree.  out: the forward's output.
+ * items_t / items_s: the two halves of gcn_prepare's item table with their counts (NULL: no row splitting).
+ * workspace: grapes_gat_aggregate_bwd_workspace_bytes(n, item_cap, f), 16-byte aligned. */
+size_t grapes_gat_aggregate_bwd_workspace_bytes(int32_t n, int32_t item_cap, int32_t f);
+int grapes_gat_aggregate_bwd(const float* dout, const float* out, const float* bias, int32_t relu, const float* h,
+                             const float* s_src, const float* s_dst, const float* row_ms, const float* a_src,
+                             const float* a_dst, const int32_t* rowptr_t, const int32_t* csr_src,
+                             const int32_t* rowptr_s, const int32_t* csr_dst, float* dh, float* da_src, float* da_dst,
+                             float* dbias, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_t,
+                             const int32_t* d_n_items_t, const int32_t* items_s, const int32_t* d_n_items_s,
+                             int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
 
 /* ------------------------------------------------------------------ A2: sampler
  * modules/utils.py:13-71.  One launch: keys = log(sigmoid(l)) + Gumbel(u) with the portable
