@@ -83,6 +83,14 @@ SIGNATURES = {
     "grapes_gat_aggregate_fwd": (I32, [P, P, P, P, P, P, P, P, I32, P, I32, I32, P, P, I32, P, P, P]),
     "grapes_gat_aggregate_bwd_workspace_bytes": (SZ, [I32, I32, I32]),
     "grapes_gat_aggregate_bwd": (I32, [P] * 18 + [I32, P, I32, P, P, P, P, I32, P, P, P]),
+    # GCN2Conv propagation and blend (modules/gcn.py:76-117)
+    "grapes_gcn2_loop_counts": (I32, [P, P, I32, P, P, I32, P, P, P]),
+    "grapes_gcn2_loop_counts_csr": (I32, [P, P, I32, P, P]),
+    "grapes_gcn2_propagate_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_gcn2_propagate_fwd": (I32, [P, P, P, P, P, F32, P, P, I32, P, I32, P, P, I32, P, P, P]),
+    "grapes_gcn2_propagate_bwd": (I32, [P, P, I32, P, P, P, P, F32, P, P, I32, I32, P, I32, P, P, I32, P, P, P]),
+    "grapes_gcn2_mix_fwd": (I32, [P, P, P, F32, F32, F32, I32, P, I32, P, I32, P]),
+    "grapes_gcn2_mix_bwd": (I32, [P, P, I32, F32, F32, F32, P, P, P, I32, P, I32, P]),
     "grapes_kernel_clock_enable": (I32, [P, I64]),
     "grapes_kernel_clock_launches": (I32, []),
     "grapes_kernel_clock_entry": (I32, [I32, P, P, P]),

@@ -20,7 +20,7 @@ import torch
 
 from . import full_graph, ops
 from .graph import DeviceGraph, as_device_graph
-from .modules.gcn import GCN, classifier_logits
+from .modules.gcn import GCN, classifier_logits, classifier_needs_loops
 
 
 def _metrics(logits: torch.Tensor, y: torch.Tensor) -> Tuple[float, float]:
@@ -45,7 +45,7 @@ def _captured_evaluator(g, x, xkey, y, gcn_c, gcn_gf, args, num_ind, batches):
     from .step_graph import GraphedTrainer
     if not batches or not isinstance(g, DeviceGraph) or y.dim() != 1:
         return None
-    if not isinstance(gcn_c, GCN):               # (a GAT classifier, modules/gcn.py:45-72: the captured step is GCN only)
+    if not isinstance(gcn_c, GCN):               # (a GAT or GCN2 classifier, modules/gcn.py:45-117: the captured step is GCN only)
         return None
     B = int(batches[0][0].numel())
     hops, K = args.sampling_hops, args.num_samples
@@ -166,6 +166,8 @@ def evaluate(gcn_c, gcn_gf, data, args, adjacency, node_map=None, num_indicators
             a = ops.tensormap_map(g.node_map, ksrc[:m].contiguous())
             b = ops.tensormap_map(g.node_map, kdst[:m].contiguous())
             preps.append(ops.PreparedGraph(a, b, n_all, status=g.status, src_grouped=True))          # eval.py:150
+            if classifier_needs_loops(gcn_c):
+                ops.gcn2_attach_loops(preps[-1], a, b)
         xc = ops.gather_rows(x, alln[:n_all].contiguous())                          # eval.py:152
         logits, _ = classifier_logits(gcn_c, xc, preps)                             # eval.py:153
         lt = ops.tensormap_map(g.node_map, targets).long()

@@ -13,6 +13,8 @@
   `--embed_nodes` (learned node embeddings in place of data.x, optimised by optimizer_c: main.py:89-100,116);
   `--engine eager` selects GrapesTrainer.  `--classifier gat` (not in the reference's flags) makes the classifier
   modules/gcn.py:45-72's GAT: eager engine, no dropout; the sampler and log-Z nets stay GCN (main.py:110-115).
+  `--classifier gcn2` makes it modules/gcn.py:76-117's GCN2 (GCNII), one GCN2Conv per sampling hop, with `--gcn2_alpha` (0.1),
+  `--gcn2_theta` (0.5), `--gcn2_shared_weights` (true) and `--dropout`: eager engine as well.
 
 Datasets are outside this repository's scope (no dataset files and no network on the build machines): `--dataset`
 names a SYNTHETIC graph with the statistics of the corresponding benchmark (grapes_amd.synth.CONFIGS — cora,
@@ -45,12 +47,14 @@ _FLAGS = [
 ]
 # additions of this driver (not in the reference)
 _EXTRA = [("e_cap", int, 1 << 17), ("max_steps", int, None), ("engine", str, "auto"), ("pipeline", bool, True),
-          ("classifier", str, "gcn")]
-_CLASSIFIERS = ("gcn", "gat")       # --classifier gat: the classifier is modules/gcn.py:45-72's GAT (the sampler nets stay GCN)
+          ("classifier", str, "gcn"),
+          # --classifier gcn2 (modules/gcn.py:76-117; the reference never constructs the model: the defaults of PyG's GCNII example [PyG-recall])
+          ("gcn2_alpha", float, 0.1), ("gcn2_theta", float, 0.5), ("gcn2_shared_weights", bool, True)]
+_CLASSIFIERS = ("gcn", "gat", "gcn2")   # gat / gcn2: the classifier is modules/gcn.py:45-72's GAT / :76-117's GCN2 (the sampler nets stay GCN)
 
 
 def check_classifier(args) -> None:
-    """--classifier gat runs on the eager engine and has no dropout (modules/gcn.py:45-72)."""
+    """--classifier gat / gcn2 run on the eager engine; gat has no dropout (modules/gcn.py:45-72), gcn2 has one (:76-117)."""
     classifier = getattr(args, "classifier", "gcn")
     if classifier not in _CLASSIFIERS:
         raise ValueError(f"--classifier must be one of {_CLASSIFIERS}, got {classifier!r}")
@@ -59,6 +63,17 @@ def check_classifier(args) -> None:
             raise ValueError("--classifier gat runs on the eager engine: the captured step (--engine graph) is GCN only")
         if args.dropout:
             raise ValueError("--classifier gat takes no --dropout: the reference's GAT has none (modules/gcn.py:45-72)")
+    if classifier == "gcn2" and getattr(args, "engine", "auto") == "graph":
+        raise ValueError("--classifier gcn2 runs on the eager engine: the captured step (--engine graph) is GCN only")
+
+
+def build_gcn2(args, F: int, C: int, hops: int):
+    """GCN2(F, [hidden_dim, C] + [C] * (hops - 2), ...): one GCN2Conv per sampling hop at width hidden_dim and lins[1]: hidden_dim -> C
+    (modules/gcn.py:83-94 reads hidden_dims[0], hidden_dims[1] and len(hidden_dims) only)."""
+    from .modules.gcn import GCN2
+    return GCN2(F, [args.hidden_dim, C] + [C] * (max(hops, 2) - 2), alpha=getattr(args, "gcn2_alpha", 0.1),
+                theta=getattr(args, "gcn2_theta", 0.5), shared_weights=getattr(args, "gcn2_shared_weights", True),
+                dropout=args.dropout)
 
 _DATASET_ALIASES = {"ogbn-arxiv": "arxiv", "ogbn-products": "products", "reddit2": "reddit"}
 
@@ -181,6 +196,8 @@ def train(args, device=None, log=print):
     num_ind = args.sampling_hops + 1 if args.use_indicators else 0                                 # main.py:104-107
     if getattr(args, "classifier", "gcn") == "gat":
         gcn_c = GAT(F, hidden_dims=[args.hidden_dim, C]).to(device)                                # modules/gcn.py:45-72
+    elif getattr(args, "classifier", "gcn") == "gcn2":
+        gcn_c = build_gcn2(args, F, C, args.sampling_hops).to(device)                              # modules/gcn.py:76-117
     else:
         gcn_c = GCN(F, hidden_dims=[args.hidden_dim, C], dropout=args.dropout).to(device)          # main.py:110
     gcn_gf = GCN(F + num_ind, hidden_dims=[args.hidden_dim, 1]).to(device)                          # main.py:112-113
@@ -191,7 +208,7 @@ def train(args, device=None, log=print):
     val_idx, test_idx = data.val_mask.nonzero().squeeze(1), data.test_mask.nonzero().squeeze(1)
     engine = args.engine
     if engine == "auto":
-        engine = "eager" if getattr(args, "classifier", "gcn") == "gat" else "graph"
+        engine = "eager" if getattr(args, "classifier", "gcn") in ("gat", "gcn2") else "graph"
     common = dict(sampling_hops=args.sampling_hops, num_samples=args.num_samples, use_indicators=args.use_indicators,
                   loss_coef=args.loss_coef, log_z_init=args.log_z_init, reinforce_baseline=args.reinforce_baseline,
                   optimizer_c=opt_c, optimizer_gf=opt_gf, philox_seed=args.seed or 0)

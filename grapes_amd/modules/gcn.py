@@ -1,8 +1,10 @@
-"""Drop-in ``GCN`` (reference modules/gcn.py:9-42) and ``GAT`` (modules/gcn.py:45-72) whose layers run the gfx950 kernels.
+"""Drop-in ``GCN`` (reference modules/gcn.py:9-42), ``GAT`` (modules/gcn.py:45-72) and ``GCN2`` (modules/gcn.py:76-117) whose layers
+run the gfx950 kernels.
 
 state_dict keys match PyG's GCNConv inside the reference module: ``gcn_layers.{i}.lin.weight``
 ([out,in]) and ``gcn_layers.{i}.bias``; for GAT [PyG-recall: torch_geometric 2.5.2 GATConv] ``gat_layers.{i}.lin.weight``,
-``.att_src`` / ``.att_dst`` ([1, 1, out]) and ``.bias``.
+``.att_src`` / ``.att_dst`` ([1, 1, out]) and ``.bias``; for GCN2 [PyG-recall: GCN2Conv, Linear] ``lins.{0,1}.weight`` / ``.bias``
+and ``conv.{i}.weight1`` (``.weight2`` with ``shared_weights=False``).
 """
 from __future__ import annotations
 
@@ -338,13 +340,212 @@ class GAT(nn.Module):
         return self.gat_layers[n_layers - 1](x, edges)                         # gcn.py:70,72
 
 
+# ------------------------------------------------------------------------------------------------ GCN2 (modules/gcn.py:76-117)
+class _LinearFn(torch.autograd.Function):
+    """act(x Wᵀ + b): one GEMM with the bias and the ReLU in its epilogue; the backward gates by the saved output."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        out = ops.linear_bias_act_fwd(x, weight, bias, relu)
+        ctx.relu = relu
+        ctx.save_for_backward(x, weight, out if relu else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, weight, out = ctx.saved_tensors
+        dout = dout.contiguous()
+        dw, dbias = ops.linear_bwd_weight_gated(dout, x, gate=out if ctx.relu else None)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            g = ops.gcn2_mix_bwd(dout, out, True, 1.0)[0] if ctx.relu else dout
+            dx = ops.linear_bwd_input(g, weight)
+        return dx, dw, dbias, None
+
+
+class Linear(nn.Module):
+    """PyG's Linear(in_channels, out_channels) as modules/gcn.py:84-85 builds it [PyG-recall: bias=True, the initial distribution of
+    nn.Linear]: keys `weight` [out, in] and `bias`."""
+
+    def __init__(self, in_channels: int, out_channels: int):
+        super().__init__()
+        if out_channels < 2:
+            raise ValueError("Linear: out_channels >= 2 (the fused GEMM epilogue is not built for one column)")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels))
+        self.bias = nn.Parameter(torch.empty(out_channels))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        bound = 1.0 / math.sqrt(self.in_channels) if self.in_channels > 0 else 0.0
+        nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, x, relu: bool = False):
+        if not x.is_cuda:
+            raise ops._lib.GrapesHipError("Linear input must be a cuda tensor (grapes_amd has no CPU path)")
+        x = x.contiguous()
+        if x.dtype != torch.float32:
+            x = x.float()
+        return _LinearFn.apply(x, self.weight, self.bias, relu)
+
+
+class _GCN2ConvFn(torch.autograd.Function):
+    """out = act((1-β) S + β S W1) with S = (1-α)(A x) + α x0 (shared weights), or the two-weight form: grapes_gcn2_propagate_fwd,
+    the GEMM entry points on the square weights as stored (S W = linear_bwd_input, G Wᵀ = linear_fwd, Sᵀ G = linear_bwd_weight)
+    and grapes_gcn2_mix_fwd / _bwd.  Saved for the backward: S (or P' and x0) and, with ReLU, the output; nothing of size e."""
+
+    @staticmethod
+    def forward(ctx, x, x0, w1, w2, prep, alpha, beta, relu):
+        d_n = prep.d_n
+        s, p = ops.gcn2_propagate_fwd(x, x0, prep, alpha, want_p=w2 is not None)
+        if w2 is None:
+            t1 = ops.linear_bwd_input(s, w1, d_n=d_n)                               # S W1
+            out = ops.gcn2_mix_fwd(s, t1, 1.0 - beta, beta, relu=relu, d_n=d_n)
+            ctx.save_for_backward(s, w1, out if relu else None)
+        else:
+            t1 = ops.linear_bwd_input(p, w1, d_n=d_n)                               # (1-α) P W1
+            t2 = ops.linear_bwd_input(x0, w2, d_n=d_n)                              # x0 W2
+            out = ops.gcn2_mix_fwd(s, t1, 1.0 - beta, beta, t2=t2, c2=beta * alpha, relu=relu, d_n=d_n)
+            ctx.save_for_backward(p, x0, w1, w2, out if relu else None)
+        ctx.prep, ctx.alpha, ctx.beta, ctx.relu, ctx.shared = prep, alpha, beta, relu, w2 is None
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        prep, alpha, beta, d_n = ctx.prep, ctx.alpha, ctx.beta, ctx.prep.d_n
+        dout = dout.contiguous()
+        if ctx.shared:
+            s, w1, out = ctx.saved_tensors
+            g0, g1, _ = ops.gcn2_mix_bwd(dout, out, ctx.relu, 1.0 - beta, beta, d_n=d_n)
+            dw1 = ops.linear_bwd_weight(s, g1, d_n=d_n)                             # Sᵀ (β dO')
+            z = ops.linear_fwd(g1, w1, d_n=d_n)                                     # (β dO') W1ᵀ
+            dx, dx0 = ops.gcn2_propagate_bwd(g0, prep, alpha, ds_add=z)
+            return dx, dx0, dw1, None, None, None, None, None
+        p, x0, w1, w2, out = ctx.saved_tensors
+        g0, g1, g2 = ops.gcn2_mix_bwd(dout, out, ctx.relu, 1.0 - beta, beta, beta * alpha, d_n=d_n)
+        dw1 = ops.linear_bwd_weight(p, g1, d_n=d_n)
+        dw2 = ops.linear_bwd_weight(x0, g2, d_n=d_n)
+        z1 = ops.linear_fwd(g1, w1, d_n=d_n)                                        # d P'
+        z2 = ops.linear_fwd(g2, w2, d_n=d_n)                                        # the x0 W2 term's share of d x0
+        dx, dx0 = ops.gcn2_propagate_bwd(g0, prep, alpha, ds_add=z1, add_is_p=True, dx0_add=z2)
+        return dx, dx0, dw1, dw2, None, None, None, None
+
+
+def _gcn2_graph(edge_index, n: int) -> ops.PreparedGraph:
+    """The layer's graph WITH its stored-self-loop counts: a PreparedGraph that carries them (ops.gcn2_attach_loops), an
+    edge-index tensor (counted once, cached beside the prepared graph) or a DeviceGraph below 2^31 entries (counted from its CSR)."""
+    if hasattr(edge_index, "full_graph_plan"):                 # graph.DeviceGraph
+        if full_graph.use_large_path(edge_index, None):
+            raise ValueError("GCN2 over a graph with 2^31 or more entries is not built: the row-blocked 64-bit path of "
+                             "full_graph.py is GCN only")
+        prep = edge_index.gcn_prepared()
+        if getattr(prep, "loops", None) is None:
+            prep.loops = ops.gcn2_loop_counts_csr(edge_index.rowptr, edge_index.col, edge_index.num_nodes)
+        return prep
+    prep = prepare_edges(edge_index, n)
+    if getattr(prep, "loops", None) is None and torch.is_tensor(edge_index):
+        ei = edge_index.to(torch.int32)
+        ops.gcn2_attach_loops(prep, ei[0].contiguous(), ei[1].contiguous())
+    return prep
+
+
+class GCN2Conv(nn.Module):
+    """PyG GCN2Conv(channels, alpha, theta, layer, shared_weights, normalize=False) as modules/gcn.py:91-92 builds it [PyG-recall]:
+    beta = log(theta / layer + 1) (1.0 when both are None), weight1 [C, C] (glorot) and, unshared, weight2; no bias.  normalize=False
+    means the adjacency is used as stored: every edge once per occurrence, stored self-loops included, no loop added."""
+
+    def __init__(self, channels: int, alpha: float, theta: Optional[float] = None, layer: Optional[int] = None,
+                 shared_weights: bool = True, cached: bool = False, add_self_loops: bool = True, normalize: bool = False):
+        super().__init__()
+        if normalize:
+            raise NotImplementedError("GCN2Conv: normalize=True (gcn_norm) is not built (the reference passes normalize=False)")
+        if cached:
+            raise NotImplementedError("GCN2Conv: cached=True is not built (it only matters with normalize=True)")
+        if not add_self_loops:
+            raise NotImplementedError("GCN2Conv: add_self_loops=False is not built (the reference leaves the default, which "
+                                      "normalize=False ignores)")
+        self.channels, self.alpha = channels, float(alpha)
+        self.beta = 1.0 if (theta is None or layer is None) else math.log(theta / layer + 1)
+        self.weight1 = nn.Parameter(torch.empty(channels, channels))
+        if shared_weights:
+            self.register_parameter("weight2", None)
+        else:
+            self.weight2 = nn.Parameter(torch.empty(channels, channels))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        a = math.sqrt(6.0 / (2 * self.channels))                      # PyG glorot
+        with torch.no_grad():
+            self.weight1.uniform_(-a, a)
+            if self.weight2 is not None:
+                self.weight2.uniform_(-a, a)
+
+    def forward(self, x, x_0, edge_index, relu: bool = False):
+        if not x.is_cuda or not x_0.is_cuda:
+            raise ops._lib.GrapesHipError("GCN2Conv inputs must be cuda tensors (grapes_amd has no CPU path)")
+        if x.shape != x_0.shape:
+            raise ValueError(f"GCN2Conv: x {tuple(x.shape)} and x_0 {tuple(x_0.shape)} must have the same rows and width "
+                             "(the only case modules/gcn.py:104-113 produces)")
+        if x.shape[1] != self.channels:
+            raise ValueError(f"GCN2Conv: width {x.shape[1]} != channels {self.channels}")
+        x, x_0 = x.contiguous(), x_0.contiguous()
+        if x.dtype != torch.float32:
+            x = x.float()
+        if x_0.dtype != torch.float32:
+            x_0 = x_0.float()
+        prep = _gcn2_graph(edge_index, x.shape[0])
+        return _GCN2ConvFn.apply(x, x_0, self.weight1, self.weight2, prep, self.alpha, self.beta, relu)
+
+
+class GCN2(nn.Module):
+    """modules/gcn.py:76-117, line by line: lins[0] + ReLU gives x = x_0, len(hidden_dims) GCN2Conv layers of width hidden_dims[0]
+    with the layer-wise adjacency routing of GCN, dropout in front of lins[0] and of every conv, lins[1], logits ONLY (gcn.py:117).
+    Only hidden_dims[0], hidden_dims[1] and len(hidden_dims) are read (as in the reference)."""
+
+    def __init__(self, in_features: int, hidden_dims: "list[int]", alpha: float, theta: float, shared_weights=True, dropout=0.0):
+        super(GCN2, self).__init__()
+        self.lins = nn.ModuleList([Linear(in_features, hidden_dims[0]), Linear(hidden_dims[0], hidden_dims[1])])   # gcn.py:83-86
+        self.conv = nn.ModuleList([GCN2Conv(hidden_dims[0], alpha, theta, layer + 1, shared_weights, normalize=False)
+                                   for layer in range(len(hidden_dims))])                                       # gcn.py:88-94
+        self.dropout = dropout
+        self.philox_dropout = None          # as GCN: a callable n_elements -> (seed, offset) set by step.GrapesTrainer
+
+    _drop = GCN._drop
+
+    def forward(self, x: torch.Tensor, edge_index: Union[torch.Tensor, "list[torch.Tensor]"]) -> torch.Tensor:
+        if not x.is_cuda:
+            raise ops._lib.GrapesHipError("GCN2 input must be a cuda tensor (grapes_amd has no CPU path)")
+        layerwise_adjacency = type(edge_index) == list
+        x = self._drop(x)                                                      # gcn.py:103
+        x = x_0 = self.lins[0](x, relu=True)                                   # gcn.py:104
+        n_conv = len(self.conv)
+        for i in range(1, n_conv):
+            edges = edge_index[-i] if layerwise_adjacency else edge_index      # gcn.py:107
+            x = self._drop(x)                                                  # gcn.py:108
+            x = self.conv[i - 1](x, x_0, edges, relu=True)                     # gcn.py:109 (ReLU fused)
+        edges = edge_index[0] if layerwise_adjacency else edge_index           # gcn.py:111
+        x = self._drop(x)                                                      # gcn.py:112
+        x = self.conv[n_conv - 1](x, x_0, edges)                               # gcn.py:113
+        return self.lins[1](x)                                                 # gcn.py:115-117
+
+
 def classifier_layers(model) -> nn.ModuleList:
-    """The conv layers of a classifier, GCN (gcn_layers) or GAT (gat_layers)."""
+    """The conv layers of a classifier: GCN (gcn_layers), GAT (gat_layers) or GCN2 (conv)."""
+    if isinstance(model, GCN2):
+        return model.conv
     return model.gat_layers if isinstance(model, GAT) else model.gcn_layers
 
 
+def classifier_needs_loops(model) -> bool:
+    """True when the classifier counts stored self-loops (GCN2Conv, normalize=False): its PreparedGraphs then need
+    ops.gcn2_attach_loops (the graph build drops the loops)."""
+    return isinstance(model, GCN2)
+
+
 def classifier_logits(model, x, edge_index):
-    """(logits, allocated MiB): GCN.forward returns the pair (gcn.py:42), GAT.forward the logits alone (gcn.py:72)."""
-    if isinstance(model, GAT):
+    """(logits, allocated MiB): GCN.forward returns the pair (gcn.py:42), GAT.forward and GCN2.forward the logits alone
+    (gcn.py:72,117)."""
+    if isinstance(model, (GAT, GCN2)):
         return model(x, edge_index), _memory_allocated_mb()
     return model(x, edge_index)

@@ -521,7 +521,7 @@ class PreparedGraph:
 
     __slots__ = ("n", "e", "d_n", "d_e", "rowptr_t", "csr_src", "rowptr_s", "csr_dst", "dinv", "status",
                  "long_items", "n_long", "item_cap", "items_t", "items_s", "n_items_t", "n_items_s",
-                 "items_fwd", "row_head", "head_ids", "head_local")
+                 "items_fwd", "row_head", "head_ids", "head_local", "loops")
 
     @staticmethod
     def scratch(n, e, device):
@@ -1559,6 +1559,115 @@ def gat_aggregate_bwd(dout, out, h, s_src, s_dst, row_ms, a_src, a_dst, prep: Pr
                                               _p(prep.items_s) if use_items else None, _p(prep.n_items_s) if use_items else None,
                                               cap, _p(ws), _p(prep.status), _stream()), "gat_aggregate_bwd")
     return dh, da_src, da_dst, dbias
+
+
+# ------------------------------------------------------------------------------- GCN2Conv propagation (modules/gcn.py:76-117)
+def _gcn2_width(f: int):
+    if f < 1 or f > 1024:
+        raise ValueError(f"GCN2 propagation: width {f} is not built (any width up to 1024)")
+
+
+def gcn2_loop_counts(edge_src, edge_dst, n, d_n=None, d_e=None, node_map=None):
+    """int32[n]: loops[i] = number of stored edges (i, i) of the edge list a PreparedGraph is built from (the build drops them;
+    GCN2Conv(normalize=False) counts them like any edge)."""
+    _chk(edge_src, _i32, "edge_src"); _chk(edge_dst, _i32, "edge_dst"); _chk(node_map, _i32, "node_map", True)
+    loops = torch.empty(max(n, 1), dtype=_i32, device=edge_src.device)
+    _lib.check(lib().grapes_gcn2_loop_counts(_p(edge_src), _p(edge_dst), edge_src.numel(), _p(d_e), _p(node_map), n, _p(d_n),
+                                             _p(loops), _stream()), "gcn2_loop_counts")
+    return loops
+
+
+def gcn2_loop_counts_csr(rowptr, col, n):
+    """The same from a DeviceGraph's CSR (int64 row pointers): 0 or 1 per node when the rows are de-duplicated."""
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col")
+    loops = torch.empty(max(n, 1), dtype=_i32, device=col.device)
+    _lib.check(lib().grapes_gcn2_loop_counts_csr(_p(rowptr), _p(col), n, _p(loops), _stream()), "gcn2_loop_counts_csr")
+    return loops
+
+
+def gcn2_attach_loops(prep: "PreparedGraph", edge_src, edge_dst, node_map=None) -> "PreparedGraph":
+    """Counts the stored self-loops of the edge list `prep` was built from and keeps them beside it (prep.loops)."""
+    prep.loops = gcn2_loop_counts(edge_src, edge_dst, prep.n, d_n=prep.d_n, d_e=prep.d_e, node_map=node_map)
+    return prep
+
+
+def gcn2_loops(prep: "PreparedGraph") -> torch.Tensor:
+    loops = getattr(prep, "loops", None)
+    if loops is None:
+        raise _lib.GrapesHipError("GCN2 propagation: this PreparedGraph carries no stored-self-loop counts (the build drops the "
+                                  "loops GCN2Conv counts): call ops.gcn2_attach_loops(prep, edge_src, edge_dst) with its edge list")
+    return loops
+
+
+def gcn2_propagate_fwd(x, x0, prep: PreparedGraph, alpha: float, want_p: bool = False):
+    """(S, P'): S = (1 - alpha) (A x + loops * x) + alpha x0 over prep's by-target CSR, P' = S's first term (want_p)."""
+    _chk(x, _f32, "x"); _chk(x0, _f32, "x0")
+    n, f = x.shape
+    _gcn2_width(f)
+    if n != prep.n or tuple(x0.shape) != (n, f):
+        raise ValueError("x and x0 must be [n, f] over the prepared graph's nodes")
+    loops = gcn2_loops(prep)
+    s_out = torch.empty_like(x)
+    p_out = torch.empty_like(x) if want_p else None
+    use_items = prep.items_fwd and prep.n > _SMALL_GRAPH
+    cap = prep.item_cap if use_items else 0
+    ws = _ws(lib().grapes_gcn2_propagate_workspace_bytes(0, cap, f), x.device) if use_items else None
+    _lib.check(lib().grapes_gcn2_propagate_fwd(_p(x), _p(x0), _p(loops), _p(prep.rowptr_t), _p(prep.csr_src), float(alpha), _p(s_out),
+                                               _p(p_out), n, _p(prep.d_n), f, _p(prep.items_t) if use_items else None,
+                                               _p(prep.n_items_t) if use_items else None, cap, _p(ws), _p(prep.status),
+                                               _stream()), "gcn2_propagate_fwd")
+    return s_out, p_out
+
+
+def gcn2_propagate_bwd(ds, prep: PreparedGraph, alpha: float, ds_add=None, add_is_p: bool = False, dx0_add=None, dx0=None,
+                       want_x0: bool = True):
+    """(dx, dx0) of gcn2_propagate_fwd from ds = d S (+ ds_add: a second share of d S, or d P' when add_is_p; + dx0_add: a gradient
+    that reaches x0 directly).  A dx0 tensor passed in is accumulated into."""
+    _chk(ds, _f32, "ds"); _chk(ds_add, _f32, "ds_add", True); _chk(dx0_add, _f32, "dx0_add", True); _chk(dx0, _f32, "dx0", True)
+    n, f = ds.shape
+    _gcn2_width(f)
+    if n != prep.n:
+        raise ValueError("ds must be [n, f] over the prepared graph's nodes")
+    loops = gcn2_loops(prep)
+    dx = torch.empty_like(ds)
+    accumulate = dx0 is not None
+    if dx0 is None and want_x0:
+        dx0 = torch.empty_like(ds)
+    use_items = prep.n > _SMALL_GRAPH
+    cap = prep.item_cap if use_items else 0
+    two = ds_add is not None or dx0_add is not None
+    ws = _ws(lib().grapes_gcn2_propagate_workspace_bytes(n if two else 0, cap, f), ds.device) if (two or use_items) else None
+    _lib.check(lib().grapes_gcn2_propagate_bwd(_p(ds), _p(ds_add), 1 if add_is_p else 0, _p(dx0_add), _p(loops), _p(prep.rowptr_s),
+                                               _p(prep.csr_dst), float(alpha), _p(dx), _p(dx0), 1 if accumulate else 0, n,
+                                               _p(prep.d_n), f, _p(prep.items_s) if use_items else None,
+                                               _p(prep.n_items_s) if use_items else None, cap, _p(ws), _p(prep.status),
+                                               _stream()), "gcn2_propagate_bwd")
+    return dx, dx0
+
+
+def gcn2_mix_fwd(s, t1, c0: float, c1: float, t2=None, c2: float = 0.0, relu: bool = False, d_n=None):
+    """act(c0 s + c1 t1 [+ c2 t2]): GCN2Conv's identity-mapping blend (+ the ReLU behind it) in one launch."""
+    _chk(s, _f32, "s"); _chk(t1, _f32, "t1"); _chk(t2, _f32, "t2", True)
+    n, f = s.shape
+    if t1.shape != s.shape or (t2 is not None and t2.shape != s.shape):
+        raise ValueError("gcn2_mix_fwd: operands of one shape")
+    out = torch.empty_like(s)
+    _lib.check(lib().grapes_gcn2_mix_fwd(_p(s), _p(t1), _p(t2), float(c0), float(c1), float(c2), 1 if relu else 0, _p(out), n,
+                                         _p(d_n), f, _stream()), "gcn2_mix_fwd")
+    return out
+
+
+def gcn2_mix_bwd(dout, out, relu: bool, c0: float, c1=None, c2=None, d_n=None):
+    """(c0 g, c1 g, c2 g) with g = dout gated by out > 0 (relu): one read of dout and out; a coefficient None gives no output."""
+    _chk(dout, _f32, "dout"); _chk(out, _f32, "out", not relu)
+    n, f = dout.shape
+    g0 = torch.empty_like(dout)
+    g1 = torch.empty_like(dout) if c1 is not None else None
+    g2 = torch.empty_like(dout) if c2 is not None else None
+    _lib.check(lib().grapes_gcn2_mix_bwd(_p(dout), _p(out) if relu else None, 1 if relu else 0, float(c0), float(c1 or 0.0),
+                                         float(c2 or 0.0), _p(g0), _p(g1), _p(g2), n, _p(d_n), f, _stream()), "gcn2_mix_bwd")
+    return g0, g1, g2
+
 
 
 # ------------------------------------------------------------------------------- sampler

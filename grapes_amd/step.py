@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from . import ops
 from .graph import DeviceGraph
-from .modules.gcn import classifier_layers, classifier_logits
+from .modules.gcn import classifier_layers, classifier_logits, classifier_needs_loops
 from .modules.utils import sample_neighborhoods_from_probs
 
 
@@ -231,8 +231,11 @@ class GrapesTrainer:
         if self.gcn_c is None:
             return out
         preps = [ops.PreparedGraph(a, b, n_all, status=g.status, src_grouped=True) for a, b, _ in edge_lists]
+        if classifier_needs_loops(self.gcn_c):        # GCN2Conv(normalize=False) counts the stored self-loops the build drops
+            for p, (a, b, _) in zip(preps, edge_lists):
+                ops.gcn2_attach_loops(p, a, b)
         xc = self._features(all_nodes, differentiable=True)                           # main.py:256
-        logits, mem = classifier_logits(self.gcn_c, xc, preps)                       # main.py:257 (GCN or GAT classifier)
+        logits, mem = classifier_logits(self.gcn_c, xc, preps)                       # main.py:257 (GCN, GAT or GCN2 classifier)
         n_layers = len(classifier_layers(self.gcn_c))
         used = [preps[-i] for i in range(1, n_layers)] + [preps[0]]                  # gcn.py:31,35
         agg_counts += [p.rowptr_t[n_all] for p in used]

@@ -137,7 +137,7 @@ class GraphedTrainer:
         # predicted classes (eval.py:153-155); no log-Z net, no loss, no backward pass, no optimiser.  out["pred"] = int64[B].
         if not hasattr(gcn_c, "gcn_layers"):
             raise NotImplementedError(f"the captured step takes a GCN classifier, not {type(gcn_c).__name__} (modules/gcn.py:45-72's "
-                                      "GAT trains through the eager GrapesTrainer)")
+                                      "GAT and modules/gcn.py:76-117's GCN2 train through the eager GrapesTrainer)")
         self.evaluate = bool(evaluate)
         if self.evaluate:
             gcn_z, optimizer_c, optimizer_gf, pipeline = None, None, None, False

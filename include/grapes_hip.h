@@ -51,7 +51,8 @@ extern "C" {
  * and full-batch training over such graphs — grapes_rowlist_transpose(_workspace_bytes), grapes_rowlist_gather_t(_workspace_bytes),
  * grapes_dropout_rows, grapes_rowlist_loss(_workspace_bytes); GraphSAINT random-walk training — grapes_saint_walk_nodes,
  * grapes_saint_subgraph(_workspace_bytes), grapes_saint_masked_loss; the GAT classifier (modules/gcn.py:45-72) — grapes_gat_scores,
- * grapes_gat_aggregate_fwd / _bwd (+ _workspace_bytes each). */
+ * grapes_gat_aggregate_fwd / _bwd (+ _workspace_bytes each); the GCN2 classifier (modules/gcn.py:76-117) —
+ * grapes_gcn2_loop_counts(_csr), grapes_gcn2_propagate_fwd / _bwd (+ _workspace_bytes), grapes_gcn2_mix_fwd / _bwd. */
 #define GRAPES_ABI_VERSION 302
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -679,6 +680,56 @@ int grapes_gat_aggregate_bwd(const float* dout, const float* out, const float* b
                              float* dbias, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_t,
                              const int32_t* d_n_items_t, const int32_t* items_s, const int32_t* d_n_items_s,
                              int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ GCN2Conv / GCNII (csrc/gcn2_kernels.hip)
+ * modules/gcn.py:76-117: GCN2 stacks GCN2Conv(channels, alpha, theta, layer, shared_weights, normalize=False) layers
+ * (torch_geometric 2.5.2, not in the reference tree).  normalize=False: no gcn_norm and no added loop; with
+ *   P_i = sum over the stored edges (j -> i) of x_j   (every occurrence counts: duplicates by multiplicity, a stored (i, i) like
+ *   any edge, an isolated row gives 0),   S = (1 - alpha) P + alpha x0,   beta = log(theta / layer + 1)
+ * the layer is  out = (1 - beta) S + beta S W1  (shared weights) or
+ *   out = (1 - beta) S + beta ((1 - alpha) P W1 + alpha x0 W2)  (shared_weights=False), W1 / W2 [c][c] applied untransposed.
+ * The edge set is grapes_gcn_prepare's, which drops stored self-loops: they come back as loops[i] x_i.  Widths: any f <= 1024
+ * (float4 columns when f % 4 == 0 and the rows are 16-byte aligned, scalar columns otherwise).  Every sum has a fixed order (no
+ * floating-point atomics): results are bit-identical from run to run.  status: GRAPES_STATUS_BAD_INDEX when a CSR entry is
+ * outside [0, n) (the entry is dropped).  The products with W1 / W2 are grapes_linear_bwd_input (S W), grapes_linear_fwd (G W^T)
+ * and grapes_linear_bwd_weight (S^T G): the square weights are read as stored, no transposed copy. */
+/* loops[i] = number of stored edges (i, i), i < n, from the edge list grapes_gcn_prepare takes (same d_e / node_map / d_n). */
+int grapes_gcn2_loop_counts(const int32_t* edge_src, const int32_t* edge_dst, int32_t e, const int32_t* d_e,
+                            const int32_t* node_map, int32_t n, const int32_t* d_n, int32_t* loops, grapes_stream_t stream);
+/* The same from a CSR with 64-bit row pointers (graph.DeviceGraph): loops[i] = number of entries of row i equal to i. */
+int grapes_gcn2_loop_counts_csr(const int64_t* rowptr, const int32_t* col, int32_t n, int32_t* loops, grapes_stream_t stream);
+/* modules/gcn.py:109,113 (GCN2Conv's propagate and its initial residual):
+ *   s_out[i] = (1 - alpha) (sum_{j in row i of the by-target CSR} x[j] + loops[i] x[i]) + alpha x0[i]
+ *   p_out[i] = the first term alone (optional: what W1 multiplies when shared_weights=False)
+ * in ONE pass: a group of lanes per row, the sum in registers.  loops may be NULL (no stored loops).  long_items / d_n_items /
+ * item_cap / workspace as grapes_gcn_aggregate_fwd (NULL: every row by one group): rows longer than GRAPES_LONG_ROW are cut into
+ * items whose partial sums are merged in chunk order.  workspace: grapes_gcn2_propagate_workspace_bytes(n, item_cap, f),
+ * 16-byte aligned.  s_out / p_out must not alias x or x0 (x and x0 may be the same matrix). */
+size_t grapes_gcn2_propagate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f);
+int grapes_gcn2_propagate_fwd(const float* x, const float* x0, const int32_t* loops, const int32_t* rowptr_t,
+                              const int32_t* csr_src, float alpha, float* s_out, float* p_out, int32_t n, const int32_t* d_n,
+                              int32_t f, const int32_t* long_items, const int32_t* d_n_items, int32_t item_cap,
+                              void* workspace, int32_t* status, grapes_stream_t stream);
+/* Backward of the above (autograd through modules/gcn.py:109,113).  With D = ds + ds_add (ds_add optional):
+ *   dx[j]  = (1 - alpha) (sum_{i in row j of the by-source CSR} D[i] + loops[j] D[j])
+ *   dx0[i] (+)= alpha D'[i] + dx0_add[i]      D' = D, or ds alone when add_is_p != 0; accumulate_x0: x0 feeds every layer
+ * ds is the gradient of s_out; ds_add is a second share of it (add_is_p == 0: the identity-mapping GEMM's) or the gradient of
+ * p_out (add_is_p != 0: it reaches x only); dx0_add (optional) is a gradient that reaches x0 directly (that of x0 W2).  A gather
+ * over rowptr_s / csr_dst with the by-source items; with ds_add or dx0_add one streaming pass forms D and dx0 first.  dx0 may
+ * be NULL.  workspace as for the forward (required with ds_add / dx0_add). */
+int grapes_gcn2_propagate_bwd(const float* ds, const float* ds_add, int32_t add_is_p, const float* dx0_add, const int32_t* loops,
+                              const int32_t* rowptr_s, const int32_t* csr_dst, float alpha, float* dx, float* dx0,
+                              int32_t accumulate_x0, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_s,
+                              const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status,
+                              grapes_stream_t stream);
+/* The identity-mapping blend (inside GCN2Conv.forward, + the torch.relu of gcn.py:109 when relu != 0):
+ *   out = act(c0 s + c1 t1 + c2 t2)     t2 optional; shared weights: (c0, c1) = (1 - beta, beta), t1 = S W1. */
+int grapes_gcn2_mix_fwd(const float* s, const float* t1, const float* t2, float c0, float c1, float c2, int32_t relu, float* out,
+                        int32_t n, const int32_t* d_n, int32_t f, grapes_stream_t stream);
+/* Its backward in one read of dout and out: g = dout gated by out > 0 (relu != 0), g0 = c0 g, g1 = c1 g, g2 = c2 g
+ * (g1, g2 optional; out may be NULL when relu == 0). */
+int grapes_gcn2_mix_bwd(const float* dout, const float* out, int32_t relu, float c0, float c1, float c2, float* g0, float* g1,
+                        float* g2, int32_t n, const int32_t* d_n, int32_t f, grapes_stream_t stream);
 
 /* ------------------------------------------------------------------ A2: sampler
  * modules/utils.py:13-71.  One launch: keys = log(sigmoid(l)) + Gumbel(u) with the portable
