@@ -451,3 +451,290 @@ def within_tiled_split_resolution(got, ref, other_abs) -> bool:
     other operand's terms (forward over tiny rows: sum_k |w[c][k]| broadcast over rows), broadcastable to got."""
     err = (torch.as_tensor(got).double() - ref[0]).abs()
     return bool((err <= 2.0 ** -134 * torch.as_tensor(other_abs).double() + 2.0 ** -20 * ref[1]).all())
+
+
+# ------------------------------------------------------------------------------------------- sparse aggregation (GCN)
+# grapes_amd/csrc/spmm_kernels.hip: out = Â h (+ b, ReLU), its transpose, the column sums and the rank-1 backward.  The same
+# criterion as above, each output relative to the fp64 sum of |w||h| of ITS OWN terms, against a host fp32 baseline that adds a
+# row's entries in CSR order.  A hard cap stands beside the ratio test (assert_aggregate_accuracy): the textbook bound of an
+# (L + 1)-term fp32 sum, so that a poor baseline can never excuse a kernel.
+AGG_KINDS = ("normal", "mixed", "zeros", "striped")
+# every row-length boundary of the aggregation kernels, on both sides: 0; 1-4 (inside a head record); 5, 8, 9 (the record's second
+# group); GRAPES_HUB_ROW = 16 (sequential up to it, eight chains above); GRAPES_LONG_ROW = 64 (chunk + combine above it on graphs
+# of more than 2048 nodes); 127-129 (two chunks / a third begun); 200; 1000.  The hubs are named per problem.
+AGG_ROW_LENGTHS = (0, 1, 2, 4, 5, 8, 9, 15, 16, 17, 24, 63, 64, 65, 127, 128, 129, 200, 1000)
+AGG_FILL_LENGTHS = (0, 1, 2, 3, 4, 5, 8, 9, 15, 16, 17, 24)     # what the rows that are not named cycle through
+AGG_LOOP_ROWS = 64      # the baseline walks rows up to this length by position-in-row, longer ones by a sequential accumulate
+U32 = 2.0 ** -24        # unit roundoff of fp32
+
+
+def _seq_sum_f32(terms: np.ndarray) -> np.ndarray:
+    """The sequential fp32 sum ((t_0 + t_1) + t_2) + ... of the rows of terms [L, f] (fp32): numpy's add.accumulate keeps the
+    dtype and adds in order (r_i = r_{i-1} + t_i), which a reduce (pairwise) and torch.cumsum (a double accumulator) do not."""
+    if terms.shape[0] == 0:
+        return np.zeros(terms.shape[1], np.float32)
+    return np.add.accumulate(terms, axis=0, dtype=np.float32)[-1]
+
+
+def _spmm64(rows, cols, w, h64, n):
+    a = torch.sparse_coo_tensor(torch.stack([rows, cols]), w, (n, h64.shape[0]), dtype=torch.float64)
+    return torch.sparse.mm(a, h64)
+
+
+def aggregate_sums(rowptr, csr, dinv, h, self_loop=True, prescaled=False, order=None):
+    """The aggregation before bias and ReLU: (ref fp64, mag fp64, base fp32 numpy), see aggregate_reference; aggregate_finish
+    adds a bias and the ReLU, so that one set of sums serves every bias / ReLU combination of a case."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    n = len(rowptr) - 1
+    csr = np.asarray(csr, dtype=np.int64)[:rowptr[-1]]
+    d32 = np.asarray(dinv, dtype=np.float32)
+    h32 = np.ascontiguousarray(np.asarray(h, dtype=np.float32))
+    f = h32.shape[1]
+    lens = np.diff(rowptr)
+    # ---- fp64 reference and magnitude (capacity rows of h, which no entry names, are zeroed: they are NaN)
+    named = np.zeros(h32.shape[0], bool); named[csr] = True; named[:n] = True
+    h64 = torch.from_numpy(np.where(named[:, None], h32, np.float32(0)).astype(np.float64))
+    d64 = torch.from_numpy(d32.astype(np.float64))
+    tr, tc = torch.from_numpy(np.repeat(np.arange(n), lens)), torch.from_numpy(csr)
+    w64 = d64[tc] * d64[tr]
+    ref = _spmm64(tr, tc, w64, h64, n)
+    mag = _spmm64(tr, tc, w64, h64.abs(), n)
+    if self_loop:
+        ref = ref + (d64[:n] ** 2)[:, None] * h64[:n]
+        mag = mag + (d64[:n] ** 2)[:, None] * h64[:n].abs()
+    # ---- fp32 baseline: a row's terms in CSR order
+    m = min(len(d32), h32.shape[0])
+    src = (h32[:m] * d32[:m, None]).astype(np.float32) if prescaled else h32        # prescaled: hs = fl32(dinv h)
+
+    def terms(rows, s):         # the fp32 products of entries s of `rows` (one entry per row, or one row's entries)
+        return src[s] if prescaled else ((d32[s] * d32[rows])[:, None] * src[s]).astype(np.float32)
+
+    acc = np.zeros((n, f), np.float32)
+    if order is None:
+        # rows of up to AGG_LOOP_ROWS entries, all together: step j adds entry j of every row that has one
+        for j in range(min(AGG_LOOP_ROWS, int(lens.max()) if n else 0)):
+            rows = np.nonzero((lens > j) & (lens <= AGG_LOOP_ROWS))[0]
+            acc[rows] += terms(rows, csr[rowptr[rows] + j])
+        long_rows = np.nonzero(lens > AGG_LOOP_ROWS)[0]
+    else:
+        long_rows = np.arange(n)
+    for r in long_rows:         # longer rows one by one: the same chain through add.accumulate (or the order under test)
+        t = np.ascontiguousarray(terms(r, csr[rowptr[r]:rowptr[r + 1]]), dtype=np.float32)
+        acc[r] = _seq_sum_f32(t) if order is None else order(t)
+    dc = d32[:n, None]
+    if prescaled:
+        base = dc * (acc + src[:n]) if self_loop else dc * acc
+    else:
+        base = acc + (dc * dc) * src[:n] if self_loop else acc
+    return ref, mag, base.astype(np.float32)
+
+
+def aggregate_finish(sums, bias=None, relu=False):
+    """(ref, mag, base) of aggregate_sums' result with the bias added (mag gains |b|) and the ReLU applied."""
+    ref, mag, base = sums
+    if bias is not None:
+        b32 = np.asarray(bias, dtype=np.float32)
+        ref = ref + torch.from_numpy(b32.astype(np.float64))
+        mag = mag + torch.from_numpy(np.abs(b32).astype(np.float64))
+        base = base + b32
+    if relu:
+        ref = ref.clamp(min=0)
+        base = np.maximum(base, np.float32(0))
+    return ref, mag, torch.from_numpy(np.ascontiguousarray(base, dtype=np.float32))
+
+
+def aggregate_reference(rowptr, csr, dinv, h, bias=None, relu=False, self_loop=True, prescaled=False, order=None):
+    """out[c] = sum_j dinv[s_j] dinv[c] h[s_j] + dinv[c]^2 h[c] + b (then max(., 0)) over the rows c = 0 .. len(rowptr) - 2 of
+    the CSR (rowptr, csr); the transpose (backward) is the same function over rowptr_s / csr_dst.  dinv is the fp32 array the
+    graph build produced, taken as given and widened, so the aggregation alone is judged.  h may hold more rows than the CSR
+    (capacity rows: never read by a correct kernel, and not read here).  -> (ref, mag, base):
+      ref   fp64;  mag  fp64, the same sum over absolute values (+ |b|);
+      base  fp32 in ONE fixed order, element-wise ops only: w = fl32(dinv[s] dinv[c]), the products fl32(w h[s]) added in CSR
+            order, then the self-loop with fl32(dc dc), then the bias, then ReLU.  prescaled: the two roundings of that form,
+            hs = fl32(dinv[s] h[s]), out = fl32(dc (sum + hs[c])) (+ b).
+    order (tests of the criterion): a function (terms [L, f] fp32) -> [f] fp32 that replaces the sequential sum of a row's
+    entries, for emulations of the kernels' other orders.
+    What carries the test where: the baseline's MAX error is set by its longest row (a sequential sum of 20000 terms errs far more
+    than the kernels' eight chains and chunks, which sit at 0.1-0.3 of it), so on graphs with a hub the max ratio bounds the hubs
+    and little else; the short rows are held by the rms ratio, which every output enters, and by the hard cap
+    (hard_cap_excess), which is per output and knows each row's own length."""
+    return aggregate_finish(aggregate_sums(rowptr, csr, dinv, h, self_loop, prescaled, order), bias, relu)
+
+
+def colsum_reference(src, gate=None, row_scale=None, prior=None):
+    """out[c] = sum_r row_scale[r] [gate[r][c] > 0] src[r][c] (+ prior[c]) over the rows given (the bias gradient / masked
+    column sums) -> (ref, mag, base); the baseline adds the rows in row order in fp32 (products rounded first)."""
+    s32 = np.asarray(src, dtype=np.float32)
+    if gate is not None:
+        s32 = np.where(np.asarray(gate) > 0, s32, np.float32(0))
+    s64 = s32.astype(np.float64)
+    if row_scale is not None:
+        r32 = np.asarray(row_scale, dtype=np.float32)
+        s64 = r32.astype(np.float64)[:, None] * s64
+        s32 = (r32[:, None] * s32).astype(np.float32)
+    ref, mag, base = s64.sum(0), np.abs(s64).sum(0), _seq_sum_f32(np.ascontiguousarray(s32))
+    if prior is not None:
+        p32 = np.asarray(prior, dtype=np.float32)
+        ref, mag, base = ref + p32.astype(np.float64), mag + np.abs(p32.astype(np.float64)), (p32 + base).astype(np.float32)
+    return torch.from_numpy(ref), torch.from_numpy(mag), torch.from_numpy(base)
+
+
+def rank1_reference(rowptr_s, csr_dst, dinv, act, dh2, w2, gate=None, prior_dw=None, prior_db=None):
+    """grapes_gcn_aggregate_bwd_rank1[_bits] over the live rows 0 .. len(rowptr_s) - 2:
+        dpre[r][m] = [gate[r][m] > 0] dh2[r] w2[m]   (gate = act unless the gate bits are given as a 0/1 array),
+        dh = Âᵀ dpre,  dw_head = dh2ᵀ act,  dbias = colsum(dpre)
+    -> {"dh" | "dw_head" | "dbias": (ref, mag, base)}.  The baseline forms fl32(dh2 w2) first, as the kernel does; the fp64
+    reference takes that product exactly (one more rounding per term than the plain aggregation: the hard cap's L + 5)."""
+    n = len(rowptr_s) - 1
+    a32, d32, w32 = (np.asarray(v, dtype=np.float32) for v in (act, dh2, w2))
+    g = (a32 if gate is None else np.asarray(gate))[:n] > 0
+    dpre64 = np.where(g, d32[:n, None].astype(np.float64) * w32.astype(np.float64), 0.0)
+    dpre32 = np.where(g, (d32[:n, None] * w32).astype(np.float32), np.float32(0))
+    pad = np.zeros((a32.shape[0] - n, a32.shape[1]))
+    exact = _agg64(rowptr_s, csr_dst, dinv, np.concatenate([dpre64, pad]))
+    base = aggregate_reference(rowptr_s, csr_dst, dinv, np.concatenate([dpre32, pad.astype(np.float32)]))[2]
+    out = {"dh": (exact[0], exact[1], base),
+           "dw_head": colsum_reference(a32[:n], row_scale=d32[:n], prior=prior_dw)}
+    db64 = dpre64.sum(0); dbm = np.abs(dpre64).sum(0); db32 = _seq_sum_f32(np.ascontiguousarray(dpre32))
+    if prior_db is not None:
+        p32 = np.asarray(prior_db, dtype=np.float32)
+        db64, dbm, db32 = db64 + p32.astype(np.float64), dbm + np.abs(p32.astype(np.float64)), (p32 + db32).astype(np.float32)
+    out["dbias"] = (torch.from_numpy(db64), torch.from_numpy(dbm), torch.from_numpy(db32))
+    return out
+
+
+def _agg64(rowptr, csr, dinv, h64np):
+    """(ref, mag) of the aggregation over an fp64 operand (rank1_reference's exact products)."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)
+    n = len(rowptr) - 1
+    csr = np.asarray(csr, dtype=np.int64)[:rowptr[-1]]
+    d64 = torch.from_numpy(np.asarray(dinv, dtype=np.float32).astype(np.float64))
+    h64 = torch.from_numpy(np.ascontiguousarray(h64np, dtype=np.float64))
+    tr, tc = torch.from_numpy(np.repeat(np.arange(n), np.diff(rowptr))), torch.from_numpy(csr)
+    w64 = d64[tc] * d64[tr]
+    loop = (d64[:n] ** 2)[:, None]
+    return _spmm64(tr, tc, w64, h64, n) + loop * h64[:n], _spmm64(tr, tc, w64, h64.abs(), n) + loop * h64[:n].abs()
+
+
+def aggregate_problem(kind: str, n: int, row_lengths: Sequence[int], f: int, seed: int, n_pad: int = 0) -> Dict[str, np.ndarray]:
+    """A graph over n live nodes (capacity n + n_pad) and the operands of every aggregation entry point.
+    Graph: the destination rows named by row_lengths (placed at seeded rows) have exactly that many entries, the others cycle
+    through AGG_FILL_LENGTHS; a row's sources are drawn WITH repeats (duplicate edges: a 6000-entry hub fits a 1500-node graph)
+    from the nodes other than itself, three popular sources among them (in about 1/2, 1/8 and 1/20 of the rows: sources with
+    hundreds of out-edges, so the transpose has long rows of its own); every seventh row also has a self-loop in the edge list,
+    which the build drops (the unit loop replaces it) and which therefore does not count.  The edge list is sorted by
+    (source, destination): grouped by source, as the source-grouped builds require, sources ascending within a destination row.
+      src, dst int32 [e];  lens int64 [n] expected entries per destination row;  n, cap
+    Operands (fp32): h, dout, act [cap, f], dh2 [cap], bias, w2 [f]; act >= 0 with about half its entries 0 (a ReLU output).
+      normal   N(0,1);
+      mixed    row r of h, dout at 10^a_r, a in [-12, 12] (each its own a); act row r at 10^a_r and dh2_r at 10^(-a_r + c_r),
+               c in [-3, 3], as layer_problem does;
+      zeros    N(0,1) with whole zero rows, single zero entries and a zero column (h, dout, act), zero entries of dh2;
+      striped  row s of h, dout, act is nonzero only in the columns c with c % G == s % G, G = min(f, 64): an output (r, c) sums
+               only the entries of row r whose source falls in its stripe, so most outputs of rows up to a few hundred entries
+               hold zero or one term — a lost term leaves an exact zero where a value belongs, a term read twice doubles it.
+    Rows past the live count are NaN in every operand."""
+    if kind not in AGG_KINDS:
+        raise ValueError(kind)
+    rng = np.random.default_rng(seed)
+    cap = n + n_pad
+    lens = np.array([AGG_FILL_LENGTHS[i % len(AGG_FILL_LENGTHS)] for i in range(n)], dtype=np.int64)
+    named = rng.permutation(np.arange(3, n))[:len(row_lengths)]
+    lens[named] = np.asarray(row_lengths, dtype=np.int64)
+    e = int(lens.sum())
+    dst = np.repeat(np.arange(n), lens)
+    src = rng.integers(0, n - 1, e)
+    src = src + (src >= dst)                                                   # never the row itself: draws are over n - 1 nodes
+    first = np.concatenate([[True], dst[1:] != dst[:-1]]) if e else np.zeros(0, bool)
+    u = rng.random(e)
+    popular = np.where(u < 0.5, 0, np.where(u < 0.625, 1, 2))                  # (at most once per row: its first draw)
+    src = np.where(first & (u < 0.675) & (popular != dst), popular, src)
+    loops = np.arange(0, n, 7)
+    src, dst = np.concatenate([src, loops]), np.concatenate([dst, loops])
+    o = np.lexsort((dst, src))
+    src, dst = src[o], dst[o]
+    G = min(f, 64)
+
+    def rows(scale=None):
+        x = rng.standard_normal((cap, f))
+        if scale is not None:
+            x *= 10.0 ** scale[:, None]
+        if kind == "zeros":
+            x[rng.integers(0, n, max(1, n // 50))] = 0.0
+            x[rng.integers(0, n, n), rng.integers(0, f, n)] = 0.0
+            x[:, f // 2] = 0.0
+        elif kind == "striped":
+            x *= (np.arange(f)[None, :] % G) == (np.arange(cap)[:, None] % G)
+        x[n:] = np.nan
+        return x
+
+    mixed = kind == "mixed"
+    h = rows(rng.uniform(-12, 12, cap) if mixed else None)
+    dout = rows(rng.uniform(-12, 12, cap) if mixed else None)
+    a = rng.uniform(-12, 12, cap) if mixed else None
+    act = np.maximum(rows(a), 0.0)
+    act[n:] = np.nan
+    dh2 = rng.standard_normal(cap)
+    if mixed:
+        dh2 *= 10.0 ** (-a + rng.uniform(-3, 3, cap))
+    elif kind == "zeros":
+        dh2[rng.integers(0, n, max(1, n // 50))] = 0.0
+    dh2[n:] = np.nan
+    c = lambda v: np.ascontiguousarray(v, dtype=np.float32)
+    return {"src": src.astype(np.int32), "dst": dst.astype(np.int32), "lens": lens, "named": named, "n": n, "cap": cap,
+            "h": c(h), "dout": c(dout), "act": c(act), "dh2": c(dh2),
+            "bias": c(rng.standard_normal(f) * 0.1), "w2": c(rng.standard_normal(f) * 0.3)}
+
+
+def host_csr(src, dst, n):
+    """(rowptr_t, csr_src, rowptr_s, csr_dst, dinv fp32) of an edge list as the graph build leaves them: self-loops dropped,
+    duplicates kept, a row's entries ascending; dinv = fl32(1 / sqrt(in-degree + 1)) from fp64.  For the CPU tests; the GPU tests
+    read the device's arrays."""
+    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    keep = src != dst
+    src, dst = src[keep], dst[keep]
+    o = np.lexsort((src, dst))
+    rowptr_t = np.concatenate([[0], np.cumsum(np.bincount(dst, minlength=n))])
+    o2 = np.lexsort((dst, src))
+    rowptr_s = np.concatenate([[0], np.cumsum(np.bincount(src, minlength=n))])
+    dinv = (1.0 / np.sqrt(np.diff(rowptr_t) + 1.0)).astype(np.float32)
+    return rowptr_t, src[o], rowptr_s, dst[o2], dinv
+
+
+def hard_cap_excess(got, ref, mag, lens, extra: int = 4) -> float:
+    """max over the outputs of |got - ref| / ((L_r + extra) 2^-24 mag), L_r the entry count of the output's row (lens [n], or a
+    scalar for column sums): <= 1 is the textbook bound of an (L + 1)-term fp32 sum with one rounding in each weight (extra = 4;
+    the prescaled and rank-1 forms round once more per term: extra = 5).  An output with mag == 0 must be 0."""
+    got, ref, mag = (torch.as_tensor(v).double().cpu() for v in (got, ref, mag))
+    L = torch.as_tensor(np.asarray(lens, dtype=np.float64))
+    if got.dim() == 2 and L.dim() == 1:
+        L = L[:, None]
+    bound = (L + extra) * U32 * mag
+    err = (got - ref).abs()
+    err = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err)
+    if err.numel() == 0:
+        return 0.0
+    q = torch.where(bound > 0, err / torch.where(bound > 0, bound, torch.ones_like(bound)),
+                    torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, float("inf"))))
+    return float(q.max())
+
+
+def assert_aggregate_accuracy(got, ref, mag, base, lens, what: str = "", extra: int = 4) -> Accuracy:
+    """The ratio criterion (assert_fp32_accuracy) and, beside it, the hard cap |got - ref| <= (L_r + extra) 2^-24 mag."""
+    x = hard_cap_excess(got, ref, mag, lens, extra)
+    print(f"[cap] {what}: worst |err| / ((L + {extra}) u mag) = {x:.3f}")
+    a = assert_fp32_accuracy(got, ref, mag, base, what)
+    assert x <= 1.0, f"{what}: an output exceeds the (L + {extra}) 2^-24 mag bound by x{x:.3f}"
+    return a
+
+
+# the graphs the CPU test of the criterion and the GPU test of the kernels share: (live nodes, capacity rows past them, hubs)
+#   small   <= 2048 nodes: every row by one wavefront whatever its length (no work items);
+#   large   > 2048 nodes: rows above GRAPES_LONG_ROW become chunk items; a 20000-entry hub;
+#   rows9k  > 8192 rows: the backward's two-launch column sums instead of the one-launch ticket form.
+AGG_GRAPHS = {"small": (1500, 37, (6000,)), "large": (2600, 41, (5000, 20000)), "rows9k": (9000, 23, (5000,))}
+
+
+def aggregate_case(size: str, kind: str, f: int, seed: int = 0, pad: bool = True) -> Dict[str, np.ndarray]:
+    n, n_pad, hubs = AGG_GRAPHS[size]
+    return aggregate_problem(kind, n, tuple(AGG_ROW_LENGTHS) + tuple(hubs), f, seed, n_pad=n_pad if pad else 0)
