@@ -91,6 +91,11 @@ SIGNATURES = {
     "grapes_gcn2_propagate_bwd": (I32, [P, P, I32, P, P, P, P, F32, P, P, I32, I32, P, I32, P, P, I32, P, P, P]),
     "grapes_gcn2_mix_fwd": (I32, [P, P, P, F32, F32, F32, I32, P, I32, P, I32, P]),
     "grapes_gcn2_mix_bwd": (I32, [P, P, I32, F32, F32, F32, P, P, P, I32, P, I32, P]),
+    "grapes_pna_aggregate_fwd_workspace_bytes": (SZ, [I32, I32]),
+    "grapes_pna_aggregate_fwd": (I32, [P, P, P, I32, P, P, P, I32, I32, I32, I32, F32, F32, P, P, I32, P, I32, P, P, I32, P, P, P]),
+    "grapes_pna_aggregate_bwd_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_pna_aggregate_bwd": (I32, [P, P, I32, P, P, P, P, P, I32, I32, I32, I32, F32, F32, P, P, I32, I32, P, I32, P, P, I32, P, P, P]),
+    "grapes_pna_add_input_grad": (I32, [P, P, I32, I32, P, I32, P]),
     "grapes_kernel_clock_enable": (I32, [P, I64]),
     "grapes_kernel_clock_launches": (I32, []),
     "grapes_kernel_clock_entry": (I32, [I32, P, P, P]),

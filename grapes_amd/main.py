@@ -15,6 +15,9 @@
   modules/gcn.py:45-72's GAT: eager engine, no dropout; the sampler and log-Z nets stay GCN (main.py:110-115).
   `--classifier gcn2` makes it modules/gcn.py:76-117's GCN2 (GCNII), one GCN2Conv per sampling hop, with `--gcn2_alpha` (0.1),
   `--gcn2_theta` (0.5), `--gcn2_shared_weights` (true) and `--dropout`: eager engine as well.
+  `--classifier pna` makes it modules/gcn.py:120-149's PNA, PNAConv(F -> hidden_dim -> C) with `--pna_aggregators`
+  (mean,min,max,std), `--pna_scalers` (identity,amplification,attenuation), `--dropout` and the in-degree histogram of the loaded
+  graph as `deg`: eager engine as well.
 
 Datasets are outside this repository's scope (no dataset files and no network on the build machines): `--dataset`
 names a SYNTHETIC graph with the statistics of the corresponding benchmark (grapes_amd.synth.CONFIGS — cora,
@@ -49,12 +52,16 @@ _FLAGS = [
 _EXTRA = [("e_cap", int, 1 << 17), ("max_steps", int, None), ("engine", str, "auto"), ("pipeline", bool, True),
           ("classifier", str, "gcn"),
           # --classifier gcn2 (modules/gcn.py:76-117; the reference never constructs the model: the defaults of PyG's GCNII example [PyG-recall])
-          ("gcn2_alpha", float, 0.1), ("gcn2_theta", float, 0.5), ("gcn2_shared_weights", bool, True)]
-_CLASSIFIERS = ("gcn", "gat", "gcn2")   # gat / gcn2: the classifier is modules/gcn.py:45-72's GAT / :76-117's GCN2 (the sampler nets stay GCN)
+          ("gcn2_alpha", float, 0.1), ("gcn2_theta", float, 0.5), ("gcn2_shared_weights", bool, True),
+          # --classifier pna (modules/gcn.py:120-149; never constructed by the reference: the PNA paper's / PyG example's sets [PyG-recall])
+          ("pna_aggregators", str, "mean,min,max,std"), ("pna_scalers", str, "identity,amplification,attenuation")]
+# gat / gcn2 / pna: the classifier is modules/gcn.py:45-72's GAT / :76-117's GCN2 / :120-149's PNA (the sampler nets stay GCN)
+_CLASSIFIERS = ("gcn", "gat", "gcn2", "pna")
+_EAGER_CLASSIFIERS = ("gat", "gcn2", "pna")
 
 
 def check_classifier(args) -> None:
-    """--classifier gat / gcn2 run on the eager engine; gat has no dropout (modules/gcn.py:45-72), gcn2 has one (:76-117)."""
+    """--classifier gat / gcn2 / pna run on the eager engine; gat has no dropout (modules/gcn.py:45-72), gcn2 and pna have one."""
     classifier = getattr(args, "classifier", "gcn")
     if classifier not in _CLASSIFIERS:
         raise ValueError(f"--classifier must be one of {_CLASSIFIERS}, got {classifier!r}")
@@ -65,6 +72,25 @@ def check_classifier(args) -> None:
             raise ValueError("--classifier gat takes no --dropout: the reference's GAT has none (modules/gcn.py:45-72)")
     if classifier == "gcn2" and getattr(args, "engine", "auto") == "graph":
         raise ValueError("--classifier gcn2 runs on the eager engine: the captured step (--engine graph) is GCN only")
+    if classifier == "pna":
+        if getattr(args, "engine", "auto") == "graph":
+            raise ValueError("--classifier pna runs on the eager engine: the captured step (--engine graph) is GCN only")
+        from . import ops
+        ops.PNAConfig(_name_list(getattr(args, "pna_aggregators", "mean,min,max,std")),
+                      _name_list(getattr(args, "pna_scalers", "identity,amplification,attenuation")), 1.0, 1.0)   # (names refused here)
+
+
+def _name_list(v) -> "List[str]":
+    return [t.strip() for t in str(v).split(",") if t.strip()]
+
+
+def build_pna(args, F: int, C: int, hops: int, g):
+    """PNA(F, [hidden_dim] * (hops - 1) + [C], ...): one PNAConv per sampling hop; deg = the in-degree histogram of the loaded graph."""
+    from .modules.gcn import PNA, pna_degree_histogram
+    return PNA(F, [args.hidden_dim] * (max(hops, 1) - 1) + [C],
+               aggregators=_name_list(getattr(args, "pna_aggregators", "mean,min,max,std")),
+               scalers=_name_list(getattr(args, "pna_scalers", "identity,amplification,attenuation")),
+               deg=pna_degree_histogram(g), dropout=args.dropout)
 
 
 def build_gcn2(args, F: int, C: int, hops: int):
@@ -198,6 +224,8 @@ def train(args, device=None, log=print):
         gcn_c = GAT(F, hidden_dims=[args.hidden_dim, C]).to(device)                                # modules/gcn.py:45-72
     elif getattr(args, "classifier", "gcn") == "gcn2":
         gcn_c = build_gcn2(args, F, C, args.sampling_hops).to(device)                              # modules/gcn.py:76-117
+    elif getattr(args, "classifier", "gcn") == "pna":
+        gcn_c = build_pna(args, F, C, args.sampling_hops, g).to(device)                            # modules/gcn.py:120-149
     else:
         gcn_c = GCN(F, hidden_dims=[args.hidden_dim, C], dropout=args.dropout).to(device)          # main.py:110
     gcn_gf = GCN(F + num_ind, hidden_dims=[args.hidden_dim, 1]).to(device)                          # main.py:112-113
@@ -208,7 +236,7 @@ def train(args, device=None, log=print):
     val_idx, test_idx = data.val_mask.nonzero().squeeze(1), data.test_mask.nonzero().squeeze(1)
     engine = args.engine
     if engine == "auto":
-        engine = "eager" if getattr(args, "classifier", "gcn") in ("gat", "gcn2") else "graph"
+        engine = "eager" if getattr(args, "classifier", "gcn") in _EAGER_CLASSIFIERS else "graph"
     common = dict(sampling_hops=args.sampling_hops, num_samples=args.num_samples, use_indicators=args.use_indicators,
                   loss_coef=args.loss_coef, log_z_init=args.log_z_init, reinforce_baseline=args.reinforce_baseline,
                   optimizer_c=opt_c, optimizer_gf=opt_gf, philox_seed=args.seed or 0)

@@ -1,10 +1,11 @@
-"""Drop-in ``GCN`` (reference modules/gcn.py:9-42), ``GAT`` (modules/gcn.py:45-72) and ``GCN2`` (modules/gcn.py:76-117) whose layers
-run the gfx950 kernels.
+"""Drop-in ``GCN`` (reference modules/gcn.py:9-42), ``GAT`` (modules/gcn.py:45-72), ``GCN2`` (modules/gcn.py:76-117) and ``PNA``
+(modules/gcn.py:120-149) whose layers run the gfx950 kernels.
 
 state_dict keys match PyG's GCNConv inside the reference module: ``gcn_layers.{i}.lin.weight``
 ([out,in]) and ``gcn_layers.{i}.bias``; for GAT [PyG-recall: torch_geometric 2.5.2 GATConv] ``gat_layers.{i}.lin.weight``,
 ``.att_src`` / ``.att_dst`` ([1, 1, out]) and ``.bias``; for GCN2 [PyG-recall: GCN2Conv, Linear] ``lins.{0,1}.weight`` / ``.bias``
-and ``conv.{i}.weight1`` (``.weight2`` with ``shared_weights=False``).
+and ``conv.{i}.weight1`` (``.weight2`` with ``shared_weights=False``); for PNA [PyG-recall: PNAConv] ``conv.{i}.pre_nn`` / ``.post_nn`` /
+``.lin`` ``.weight`` / ``.bias`` and ``lins.weight`` / ``.bias``.
 """
 from __future__ import annotations
 
@@ -530,22 +531,183 @@ class GCN2(nn.Module):
         return self.lins[1](x)                                                 # gcn.py:115-117
 
 
+# ------------------------------------------------------------------------------------------------ PNA (modules/gcn.py:120-149)
+def pna_degree_histogram(graph, num_nodes: Optional[int] = None) -> torch.Tensor:
+    """int64[max in-degree + 1]: entry d = number of nodes whose in-degree is d — the `deg` argument of PNAConv, as PyG's
+    PNAConv.get_degree_histogram builds it from a loader [PyG-recall].  graph: a graph.DeviceGraph (rows are sources, columns
+    targets; stored loops count) or an edge index [2, e] (row 1 = targets; every occurrence counts)."""
+    if hasattr(graph, "rowptr") and hasattr(graph, "col"):
+        dst, n = graph.col.long(), int(graph.num_nodes)
+    else:
+        ei = torch.as_tensor(graph)
+        dst = ei[1].long().reshape(-1)
+        n = int(num_nodes) if num_nodes is not None else (int(ei.max().item()) + 1 if ei.numel() else 0)
+    return torch.bincount(torch.bincount(dst, minlength=n)).to(torch.int64).cpu()
+
+
+def pna_degree_averages(deg) -> "tuple[float, float]":
+    """(avg_log, avg_lin) = (Σ_d log(d + 1) deg[d], Σ_d d deg[d]) / Σ_d deg[d] of a degree histogram [PyG-recall:
+    DegreeScalerAggregation's avg_deg]."""
+    deg = torch.as_tensor(deg).detach().cpu().to(torch.float64).reshape(-1)
+    total = float(deg.sum())
+    if total <= 0:
+        raise ValueError("PNAConv: the degree histogram is empty")
+    bins = torch.arange(deg.numel(), dtype=torch.float64)
+    return float(((bins + 1).log() * deg).sum()) / total, float((bins * deg).sum()) / total
+
+
+class _PNAConvFn(torch.autograd.Function):
+    """out = act(lin(post_nn([x_i | scaled aggregates of pre_nn([x_i | x_j])]))).  pre_nn is linear, so the messages are a_i + b_j
+    with [a | b] = x [W_i ; W_j]ᵀ + [bias | 0] — ONE GEMM; grapes_pna_aggregate_fwd writes post_nn's operand in one gather pass,
+    then two GEMMs with the bias (and the ReLU) in their epilogues.  Saved: x, [a | b], post_nn's operand, the statistics of b
+    ([n, 6, f]), post_nn's output and, with ReLU, the output; nothing of size e."""
+
+    @staticmethod
+    def forward(ctx, x, w_pre, b_pre, w_post, b_post, w_lin, b_lin, prep, cfg, relu):
+        d_n, f = prep.d_n, x.shape[1]
+        w2 = torch.cat([w_pre[:, :f], w_pre[:, f:]], 0)                           # [W_i ; W_j]: [2f, f]
+        bias2 = torch.cat([b_pre, torch.zeros_like(b_pre)])
+        ab = ops.linear_bias_act_fwd(x, w2, bias2, False, d_n=d_n)                 # [a | b]
+        z, stats = ops.pna_aggregate_fwd(x, ab, prep, cfg)
+        h = ops.linear_bias_act_fwd(z, w_post, b_post, False, d_n=d_n)             # post_nn
+        out = ops.linear_bias_act_fwd(h, w_lin, b_lin, relu, d_n=d_n)              # lin (+ the model's ReLU)
+        ctx.prep, ctx.cfg, ctx.relu = prep, cfg, relu
+        ctx.save_for_backward(x, w2, w_post, w_lin, ab, z, stats, h, out if relu else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w2, w_post, w_lin, ab, z, stats, h, out = ctx.saved_tensors
+        prep, cfg, d_n, f = ctx.prep, ctx.cfg, ctx.prep.d_n, x.shape[1]
+        dout = dout.contiguous()
+        dw_lin, db_lin = ops.linear_bwd_weight_gated(dout, h, gate=out if ctx.relu else None, d_n=d_n)
+        g = ops.gcn2_mix_bwd(dout, out, True, 1.0, d_n=d_n)[0] if ctx.relu else dout
+        dh = ops.linear_bwd_input(g, w_lin, d_n=d_n)
+        dw_post, db_post = ops.linear_bwd_weight_gated(dh, z, d_n=d_n)
+        dz = ops.linear_bwd_input(dh, w_post, d_n=d_n)
+        dab = ops.pna_aggregate_bwd(dz, ab, stats, prep, cfg)                      # [da | db]
+        dw2, db2 = ops.linear_bwd_weight_gated(dab, x, d_n=d_n)
+        dw_pre = torch.cat([dw2[:f], dw2[f:]], 1)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = ops.pna_add_input_grad(ops.linear_bwd_input(dab, w2, d_n=d_n), dz, d_n=d_n)
+        return dx, dw_pre, db2[:f].contiguous(), dw_post, db_post, dw_lin, db_lin, None, None, None
+
+
+def _pna_graph(edge_index, n: int) -> ops.PreparedGraph:
+    """The layer's graph with its stored-self-loop counts (PNAConv aggregates the adjacency as stored, like GCN2Conv)."""
+    if hasattr(edge_index, "full_graph_plan") and full_graph.use_large_path(edge_index, None):
+        raise ValueError("PNA over a graph with 2^31 or more entries is not built: the row-blocked 64-bit path of "
+                         "full_graph.py is GCN only")
+    return _gcn2_graph(edge_index, n)
+
+
+class PNAConv(nn.Module):
+    """PyG PNAConv(in_channels, out_channels, aggregators, scalers, deg) as modules/gcn.py:130-131 builds it, every other
+    argument at its default [PyG-recall]: one tower, pre_nn = Linear(2 F, F) on [x_i | x_j] per stored edge (j -> i), the
+    aggregators over the incoming messages, each scaler applied to all of them, post_nn = Linear((|agg| |scal| + 1) F, C) on
+    [x_i | scaled aggregates], then lin = Linear(C, C).  Keys: pre_nn / post_nn / lin .weight / .bias (PyG nests the first two as
+    pre_nns.0.0 / post_nns.0.0).  The adjacency is used as stored: duplicates by multiplicity, stored loops counted, none added."""
+
+    def __init__(self, in_channels: int, out_channels: int, aggregators, scalers, deg, edge_dim=None, towers: int = 1,
+                 pre_layers: int = 1, post_layers: int = 1, divide_input: bool = False, act="relu", act_kwargs=None,
+                 train_norm: bool = False):
+        super().__init__()
+        if edge_dim is not None:
+            raise NotImplementedError("PNAConv: edge features (edge_dim) are not built")
+        if towers != 1 or divide_input:
+            raise NotImplementedError("PNAConv: only towers=1, divide_input=False is built (the reference passes no other value)")
+        if pre_layers != 1 or post_layers != 1:
+            raise NotImplementedError("PNAConv: only pre_layers=1 and post_layers=1 are built (one Linear each, no activation)")
+        if train_norm:
+            raise NotImplementedError("PNAConv: train_norm=True (learned degree averages) is not built")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.aggregators, self.scalers = list(aggregators), list(scalers)
+        avg_log, avg_lin = pna_degree_averages(deg)
+        self.cfg = ops.PNAConfig(self.aggregators, self.scalers, avg_log, avg_lin)
+        self.avg_deg = {"log": avg_log, "lin": avg_lin}
+        self.pre_nn = Linear(2 * in_channels, in_channels)
+        self.post_nn = Linear(self.cfg.blocks * in_channels, out_channels)
+        self.lin = Linear(out_channels, out_channels)
+
+    def reset_parameters(self):
+        for m in (self.pre_nn, self.post_nn, self.lin):
+            m.reset_parameters()
+
+    def forward(self, x, edge_index, relu: bool = False):
+        if not x.is_cuda:
+            raise ops._lib.GrapesHipError("PNAConv input must be a cuda tensor (grapes_amd has no CPU path)")
+        if x.shape[1] != self.in_channels:
+            raise ValueError(f"PNAConv: width {x.shape[1]} != in_channels {self.in_channels}")
+        x = x.contiguous()
+        if x.dtype != torch.float32:
+            x = x.float()
+        prep = _pna_graph(edge_index, x.shape[0])
+        return _PNAConvFn.apply(x, self.pre_nn.weight, self.pre_nn.bias, self.post_nn.weight, self.post_nn.bias, self.lin.weight,
+                                self.lin.bias, prep, self.cfg, relu)
+
+
+class PNA(nn.Module):
+    """modules/gcn.py:120-149 with its constructor signature, its `conv` ModuleList (PNAConv(dims[i], dims[i + 1], ...), gcn.py:127-132)
+    and its `lins = Linear(in_features, hidden_dims[-1])` (gcn.py:134), so a state dict has the reference's names.  The reference's
+    forward cannot run (self.drop_input, self.dropout and self.convs are never set; lins maps in_features -> hidden_dims[-1] in
+    front of a conv that expects in_features), so forward has its evident intent: dropout on the input when drop_input, for all but
+    the last layer relu(conv[i - 1](x, edge_index[-i])) then dropout, the last conv on edge_index[0] (the routing of GCN / GAT /
+    GCN2), logits ONLY.  Deviations from the reference text:
+      * `lins` is kept as a parameter but not applied;
+      * drop_input and dropout are set from the constructor's arguments;
+      * batch_norm=True and residual=True are refused (the reference accepts and ignores them);
+      * dropout draws from the Philox stream when a trainer hands out counters, as GCN._drop."""
+
+    def __init__(self, in_features: int, hidden_dims: "list[int]", aggregators: "list[str]", scalers: "list[str]", deg: torch.Tensor,
+                 dropout: float = 0.0, drop_input: bool = True, batch_norm: bool = False, residual: bool = False, device=None):
+        super(PNA, self).__init__()
+        if batch_norm:
+            raise NotImplementedError("PNA: batch_norm=True is not built (the reference accepts the flag and ignores it)")
+        if residual:
+            raise NotImplementedError("PNA: residual=True is not built (the reference accepts the flag and ignores it)")
+        dims = [in_features] + list(hidden_dims)
+        self.conv = nn.ModuleList([PNAConv(in_channels=dims[i], out_channels=dims[i + 1], aggregators=aggregators, scalers=scalers,
+                                           deg=deg) for i in range(len(hidden_dims))])                     # gcn.py:127-132
+        self.lins = Linear(in_features, hidden_dims[-1])                                                  # gcn.py:134 (not applied)
+        self.dropout, self.drop_input = dropout, bool(drop_input)
+        self.philox_dropout = None          # as GCN: a callable n_elements -> (seed, offset) set by step.GrapesTrainer
+        if device is not None:
+            self.to(device)
+
+    _drop = GCN._drop
+
+    def forward(self, x: torch.Tensor, edge_index: Union[torch.Tensor, "list[torch.Tensor]"], *args) -> torch.Tensor:
+        if not x.is_cuda:
+            raise ops._lib.GrapesHipError("PNA input must be a cuda tensor (grapes_amd has no CPU path)")
+        layerwise_adjacency = type(edge_index) == list
+        if self.drop_input:
+            x = self._drop(x)                                                  # gcn.py:139-140
+        n_conv = len(self.conv)
+        for i in range(1, n_conv):
+            edges = edge_index[-i] if layerwise_adjacency else edge_index      # gcn.py:143
+            x = self.conv[i - 1](x, edges, relu=True)                          # gcn.py:145 (ReLU fused)
+            x = self._drop(x)                                                  # gcn.py:146
+        edges = edge_index[0] if layerwise_adjacency else edge_index           # (gcn.py:148 reads edge_index[-1]: see the docstring)
+        return self.conv[n_conv - 1](x, edges)
+
+
 def classifier_layers(model) -> nn.ModuleList:
-    """The conv layers of a classifier: GCN (gcn_layers), GAT (gat_layers) or GCN2 (conv)."""
-    if isinstance(model, GCN2):
+    """The conv layers of a classifier: GCN (gcn_layers), GAT (gat_layers), GCN2 or PNA (conv)."""
+    if isinstance(model, (GCN2, PNA)):
         return model.conv
     return model.gat_layers if isinstance(model, GAT) else model.gcn_layers
 
 
 def classifier_needs_loops(model) -> bool:
-    """True when the classifier counts stored self-loops (GCN2Conv, normalize=False): its PreparedGraphs then need
+    """True when the classifier counts stored self-loops (GCN2Conv with normalize=False, PNAConv): its PreparedGraphs then need
     ops.gcn2_attach_loops (the graph build drops the loops)."""
-    return isinstance(model, GCN2)
+    return isinstance(model, (GCN2, PNA))
 
 
 def classifier_logits(model, x, edge_index):
-    """(logits, allocated MiB): GCN.forward returns the pair (gcn.py:42), GAT.forward and GCN2.forward the logits alone
-    (gcn.py:72,117)."""
-    if isinstance(model, (GAT, GCN2)):
+    """(logits, allocated MiB): GCN.forward returns the pair (gcn.py:42), GAT.forward, GCN2.forward and PNA.forward the logits alone
+    (gcn.py:72,117,149)."""
+    if isinstance(model, (GAT, GCN2, PNA)):
         return model(x, edge_index), _memory_allocated_mb()
     return model(x, edge_index)

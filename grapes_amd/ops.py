@@ -1669,6 +1669,91 @@ def gcn2_mix_bwd(dout, out, relu: bool, c0: float, c1=None, c2=None, d_n=None):
     return g0, g1, g2
 
 
+# ------------------------------------------------------------------------------- PNAConv aggregation (modules/gcn.py:120-149)
+PNA_AGGREGATORS = ("mean", "min", "max", "std", "var", "sum")                       # the kernels' aggregator codes, by position
+PNA_SCALERS = ("identity", "amplification", "attenuation", "linear", "inverse_linear")
+PNA_NSTAT = 6                                                                       # mean, min, max, var, ties_min, ties_max
+
+
+class PNAConfig:
+    """The aggregator / scaler lists of a PNAConv as the kernels take them (3-bit codes, the first entry in the low bits) and the
+    two averages of the degree histogram."""
+
+    __slots__ = ("aggregators", "scalers", "n_agg", "agg_code", "n_scal", "scal_code", "avg_log", "avg_lin")
+
+    def __init__(self, aggregators, scalers, avg_log: float, avg_lin: float):
+        self.aggregators, self.scalers = tuple(aggregators), tuple(scalers)
+        for name in self.aggregators:
+            if name not in PNA_AGGREGATORS:
+                raise NotImplementedError(f"PNA aggregator {name!r} is not built (built: {', '.join(PNA_AGGREGATORS)})")
+        for name in self.scalers:
+            if name not in PNA_SCALERS:
+                raise NotImplementedError(f"PNA scaler {name!r} is not built (built: {', '.join(PNA_SCALERS)})")
+        if not (1 <= len(self.aggregators) <= 6) or not (1 <= len(self.scalers) <= 5):
+            raise ValueError("PNA: 1..6 aggregators and 1..5 scalers")
+        self.n_agg, self.n_scal = len(self.aggregators), len(self.scalers)
+        self.agg_code = sum(PNA_AGGREGATORS.index(a) << (3 * k) for k, a in enumerate(self.aggregators))
+        self.scal_code = sum(PNA_SCALERS.index(s) << (3 * k) for k, s in enumerate(self.scalers))
+        self.avg_log, self.avg_lin = float(avg_log), float(avg_lin)
+
+    @property
+    def blocks(self) -> int:
+        return 1 + self.n_agg * self.n_scal
+
+
+def pna_aggregate_fwd(x, ab, prep: PreparedGraph, cfg: PNAConfig):
+    """(z, stats): z[i] = [x_i | scaler_1(aggs) | scaler_2(aggs) | ...] ([n, cfg.blocks * f], post_nn's operand) of the messages
+    m_ij = a_i + b_j over prep's by-target CSR (+ its stored loops), ab = [a | b] ([n, 2 f]); stats [n, 6, f] for the backward."""
+    _chk(x, _f32, "x"); _chk(ab, _f32, "ab")
+    n, f = x.shape
+    if n != prep.n or tuple(ab.shape) != (n, 2 * f):
+        raise ValueError("x must be [n, f] and ab [n, 2 f] over the prepared graph's nodes")
+    loops = gcn2_loops(prep)
+    z = torch.empty((n, cfg.blocks * f), dtype=_f32, device=x.device)
+    stats = torch.empty((n, PNA_NSTAT, f), dtype=_f32, device=x.device)
+    use_items = prep.items_fwd and prep.n > _SMALL_GRAPH
+    cap = prep.item_cap if use_items else 0
+    ws = _ws(lib().grapes_pna_aggregate_fwd_workspace_bytes(cap, f), x.device) if use_items else None
+    _lib.check(lib().grapes_pna_aggregate_fwd(_p(x), _p(ab), ab.data_ptr() + 4 * f, 2 * f, _p(loops), _p(prep.rowptr_t),
+                                              _p(prep.csr_src), cfg.n_agg, cfg.agg_code, cfg.n_scal, cfg.scal_code, cfg.avg_log,
+                                              cfg.avg_lin, _p(z), _p(stats), n, _p(prep.d_n), f,
+                                              _p(prep.items_t) if use_items else None, _p(prep.n_items_t) if use_items else None,
+                                              cap, _p(ws), _p(prep.status), _stream()), "pna_aggregate_fwd")
+    return z, stats
+
+
+def pna_aggregate_bwd(dz, ab, stats, prep: PreparedGraph, cfg: PNAConfig):
+    """dab = [da | db] ([n, 2 f]) of pna_aggregate_fwd from dz = d z (its first f columns, the gradient of the copy of x, are not
+    read: pna_add_input_grad)."""
+    _chk(dz, _f32, "dz"); _chk(ab, _f32, "ab"); _chk(stats, _f32, "stats")
+    n, f2 = ab.shape
+    f = f2 // 2
+    if n != prep.n or tuple(dz.shape) != (n, cfg.blocks * f) or tuple(stats.shape) != (n, PNA_NSTAT, f):
+        raise ValueError("dz must be [n, blocks * f] and stats [n, 6, f] over the prepared graph's nodes")
+    loops = gcn2_loops(prep)
+    dab = torch.empty_like(ab)
+    use_items = prep.n > _SMALL_GRAPH
+    cap = prep.item_cap if use_items else 0
+    ws = _ws(lib().grapes_pna_aggregate_bwd_workspace_bytes(n, cap, f), dz.device)
+    _lib.check(lib().grapes_pna_aggregate_bwd(_p(dz), ab.data_ptr() + 4 * f, 2 * f, _p(stats), _p(loops), _p(prep.rowptr_t),
+                                              _p(prep.rowptr_s), _p(prep.csr_dst), cfg.n_agg, cfg.agg_code, cfg.n_scal,
+                                              cfg.scal_code, cfg.avg_log, cfg.avg_lin, _p(dab), dab.data_ptr() + 4 * f, 2 * f, n,
+                                              _p(prep.d_n), f, _p(prep.items_s) if use_items else None,
+                                              _p(prep.n_items_s) if use_items else None, cap, _p(ws), _p(prep.status), _stream()),
+               "pna_aggregate_bwd")
+    return dab
+
+
+def pna_add_input_grad(dx, dz, d_n=None):
+    """dx += dz[:, :f] in place (the gradient that reaches x through its copy in post_nn's operand)."""
+    _chk(dx, _f32, "dx"); _chk(dz, _f32, "dz")
+    n, f = dx.shape
+    if dz.shape[0] != n or dz.shape[1] < f:
+        raise ValueError("dz must be [n, >= f]")
+    _lib.check(lib().grapes_pna_add_input_grad(_p(dx), _p(dz), dz.shape[1], n, _p(d_n), f, _stream()), "pna_add_input_grad")
+    return dx
+
+
 
 # ------------------------------------------------------------------------------- sampler
 def gumbel_topk(logits, k, uniforms=None, logit_index=None, candidate_ids=None, n=None, d_n=None, mode=0,

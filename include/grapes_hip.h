@@ -52,7 +52,8 @@ extern "C" {
  * grapes_dropout_rows, grapes_rowlist_loss(_workspace_bytes); GraphSAINT random-walk training — grapes_saint_walk_nodes,
  * grapes_saint_subgraph(_workspace_bytes), grapes_saint_masked_loss; the GAT classifier (modules/gcn.py:45-72) — grapes_gat_scores,
  * grapes_gat_aggregate_fwd / _bwd (+ _workspace_bytes each); the GCN2 classifier (modules/gcn.py:76-117) —
- * grapes_gcn2_loop_counts(_csr), grapes_gcn2_propagate_fwd / _bwd (+ _workspace_bytes), grapes_gcn2_mix_fwd / _bwd. */
+ * grapes_gcn2_loop_counts(_csr), grapes_gcn2_propagate_fwd / _bwd (+ _workspace_bytes), grapes_gcn2_mix_fwd / _bwd; the PNA
+ * classifier (modules/gcn.py:120-149) — grapes_pna_aggregate_fwd / _bwd (+ _workspace_bytes each), grapes_pna_add_input_grad. */
 #define GRAPES_ABI_VERSION 302
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -730,6 +731,49 @@ int grapes_gcn2_mix_fwd(const float* s, const float* t1, const float* t2, float 
  * (g1, g2 optional; out may be NULL when relu == 0). */
 int grapes_gcn2_mix_bwd(const float* dout, const float* out, int32_t relu, float c0, float c1, float c2, float* g0, float* g1,
                         float* g2, int32_t n, const int32_t* d_n, int32_t f, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ PNAConv (csrc/pna_kernels.hip)
+ * modules/gcn.py:120-149: PNA stacks PNAConv(in_channels, out_channels, aggregators, scalers, deg) layers, every other argument
+ * at its default (torch_geometric 2.5.2, not in the reference tree): towers = 1, pre_nn = Linear(2 f, f), post_nn =
+ * Linear((n_agg n_scal + 1) f, c), lin = Linear(c, c).  The message of a stored edge (j -> i) is pre_nn([x_i | x_j]) =
+ * a_i + b_j with a = x W_i^T + bias, b = x W_j^T (two GEMM outputs sharing the pitch ld; W_pre = [W_i | W_j]): no per-edge
+ * tensor is formed.  Every occurrence of a stored edge counts, a stored (i, i) comes back through loops[i]
+ * (grapes_gcn2_loop_counts), no loop is added, nothing is normalised.  With d_i = row length + loops[i], per feature:
+ *   mean = sum m / max(d, 1);  min, max (0 when d = 0);  var = relu(mean(m^2) - mean(m)^2) computed CENTRED (Welford per entry,
+ *   Chan's update across work items);  std = sqrt(var + 1e-5);  sum
+ * Aggregator codes: 0 mean, 1 min, 2 max, 3 std, 4 var, 5 sum.  Scaler codes: 0 identity, 1 amplification log(d + 1) / avg_log,
+ * 2 attenuation avg_log / log(max(d, 1) + 1), 3 linear d / avg_lin, 4 inverse_linear avg_lin / max(d, 1).  agg_code / scal_code
+ * hold n_agg <= 6 / n_scal <= 5 codes of 3 bits each, the first in the low bits.  Any f >= 1 (float4 columns when f % 4 == 0,
+ * ld % 4 == 0 and the rows are 16-byte aligned).  No floating-point atomics: results are bit-identical from run to run. */
+/* z[i] = [x_i | scaler_1(agg_1 .. agg_k) | scaler_2(...) | ...]  ([n][(1 + n_agg n_scal) f]: post_nn's operand, written once),
+ * stats[i] = [mean | min | max | var | ties_min | ties_max] of b over row i ([n][6][f]; ties = number of entries equal to the
+ * extreme) for the backward.  ONE gather pass over the by-target CSR: a group of lanes per row, the statistics in registers.
+ * long_items / d_n_items / item_cap / workspace as grapes_gcn2_propagate_fwd (NULL: every row by one group); workspace:
+ * grapes_pna_aggregate_fwd_workspace_bytes(item_cap, f), 16-byte aligned.  z and stats must not alias the inputs. */
+size_t grapes_pna_aggregate_fwd_workspace_bytes(int32_t item_cap, int32_t f);
+int grapes_pna_aggregate_fwd(const float* x, const float* a, const float* b, int32_t ld, const int32_t* loops,
+                             const int32_t* rowptr_t, const int32_t* csr_src, int32_t n_agg, int32_t agg_code, int32_t n_scal,
+                             int32_t scal_code, float avg_log, float avg_lin, float* z, float* stats, int32_t n,
+                             const int32_t* d_n, int32_t f, const int32_t* long_items, const int32_t* d_n_items, int32_t item_cap,
+                             void* workspace, int32_t* status, grapes_stream_t stream);
+/* Backward of the above from dz = d z.  A row-local pass folds the scalers and the aggregators into four coefficients per (row,
+ * feature) and writes  da[i] = gmean + gmin + gmax  (0 when d_i = 0); a gather over the by-source CSR (items_s as
+ * grapes_gcn2_propagate_bwd) then writes
+ *   db[j] = sum_{i <- j} gmean_i / d_i + 2 gvar_i (b_j - mean_i) / d_i + gmax_i [b_j == max_i] / ties_max_i
+ *           + gmin_i [b_j == min_i] / ties_min_i          (+ loops[j] times the term with i = j)
+ * gvar_i is gated by var_i > 0.  Bit-equal extremes share the gradient evenly.  da / db: [n][ld_d] (two halves of one matrix, or
+ * two matrices with one pitch).  The columns dz[:, :f] (the gradient of the copy of x) are not read: grapes_pna_add_input_grad.
+ * workspace (required): grapes_pna_aggregate_bwd_workspace_bytes(n, item_cap, f), 16-byte aligned. */
+size_t grapes_pna_aggregate_bwd_workspace_bytes(int32_t n, int32_t item_cap, int32_t f);
+int grapes_pna_aggregate_bwd(const float* dz, const float* b, int32_t ld, const float* stats, const int32_t* loops,
+                             const int32_t* rowptr_t, const int32_t* rowptr_s, const int32_t* csr_dst, int32_t n_agg,
+                             int32_t agg_code, int32_t n_scal, int32_t scal_code, float avg_log, float avg_lin, float* da,
+                             float* db, int32_t ld_d, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_s,
+                             const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status,
+                             grapes_stream_t stream);
+/* dx[i][:f] += dz[i][:f] over the first n rows (dz with the pitch ld_z): the gradient that reaches x through its copy in z. */
+int grapes_pna_add_input_grad(float* dx, const float* dz, int32_t ld_z, int32_t n, const int32_t* d_n, int32_t f,
+                              grapes_stream_t stream);
 
 /* ------------------------------------------------------------------ A2: sampler
  * modules/utils.py:13-71.  One launch: keys = log(sigmoid(l)) + Gumbel(u) with the portable
