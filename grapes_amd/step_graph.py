@@ -17,10 +17,13 @@ draws its masks from the same Philox stream as the sampler (two small launches p
 Capacities: every hop may expand up to `e_cap` edges and touch up to `e_cap + B + K` nodes; if a
 batch exceeds them the kernels drop the excess and raise the device status word, which
 `check()` turns into an exception — nothing is silently truncated.
+
+The step body is `GraphedTrainer._step_impl` = `_main(_prelude())`: phase methods that hand a `_Step` to one another.
 """
 from __future__ import annotations
 
 import contextlib
+import copy
 from typing import Dict, List, Optional
 
 import os
@@ -55,6 +58,7 @@ class _FirstLayer:
         # a hidden_dim that is not a multiple of 4, a one-layer classifier with an odd class count — aggregates first)
         self.agg_first = legacy or self.K < conv.out_channels or conv.out_channels % 4 != 0
         self.padded = self.Kp != self.K
+        self.direct = False                # a backward launch writes the parameter's own gradient (grad_direct): nothing to publish
         w = conv.lin.weight
         if self.padded:
             self.W = torch.zeros((w.shape[0], self.Kp), dtype=w.dtype, device=w.device)
@@ -87,12 +91,12 @@ class _FirstLayer:
         return self.conv.lin.weight.grad
 
     def publish_grad(self):
-        if self.padded and not self.split and not getattr(self, "direct", False):
+        if self.publishes:
             self.conv.lin.weight.grad.copy_(self.dW[:, :self.K])
 
     @property
     def publishes(self):          # a strided copy of the padded gradient follows the backward passes
-        return self.padded and not self.split and not getattr(self, "direct", False)
+        return self.padded and not self.split and not self.direct
 
 
 class _StepSet:
@@ -102,10 +106,32 @@ class _StepSet:
         self.g, self.targets, self.epoch_t, self.ctr = g, targets, epoch_t, ctr
         self.out: Dict[str, torch.Tensor] = {}
         self.G = None                     # capture.SegmentedGraph: this set's main part + the other set's prelude riding in it
-        self.gen = None
+        self.state = None                 # _Step of this set's RECORDED prelude: the owner of its buffers (_capture_pipeline)
+        self.scratch = None               # ... and of the workspaces its launches use (ops.rider_keep)
         self.program = -1                 # rider program of this set's prelude (include/grapes_hip.h)
         self.riders = (0, 0)
-        self.handoff = None
+
+
+class _Step:
+    """What the phases of ONE step hand to one another (GraphedTrainer._prelude -> _main): plain fields, no behaviour.  The
+    fields a prelude fills are the owners of its buffers — those nobody reads again included."""
+    __slots__ = (
+        "fused", "staged", "counted", "defer_draw", "with_ext", "halo_reuse",       # the forms chosen for this trace
+        "pbuf", "hc", "hbs", "tgt_ext", "hop_stats",                                # alternating bitmaps, hop counters, statistics
+        "src", "dst", "d_e", "eoff", "previous", "d_m",                             # the current expansion
+        "kept_list", "slices", "stages", "neigh_list", "nbl_list", "dnn_list", "dnb_list",      # one entry per hop
+        "hop_state", "zstate", "agg_w", "agg_x", "kept_halo",
+        # what a hop's graph phase leaves for its sampling and advance phases
+        "batch", "neigh", "nbl", "counts", "cand_pos", "hid", "prep", "ax_pre", "pscr", "bsum", "sstage", "rm_lists",
+        "marked", "halo", "halo_code",          # the last expansion made the next hop's marks; the last halo fetch; its indicator words
+        # the classifier: all_nodes, its graphs, activations, losses
+        "alln", "d_na", "preps", "layers", "used", "first_relu", "first_fused", "acts", "keeps", "logits",
+        "loss_c", "dl", "loss_gfn", "gscale", "log_z", "tot")
+
+    def __init__(self):
+        for k in self.__slots__:
+            setattr(self, k, None)
+        self.marked = False
 
 
 class _StepChain:
@@ -196,7 +222,6 @@ class GraphedTrainer:
             self.n_cap = min(self.n_cap, graph.num_nodes + 1)
         self.nall_cap = batch_size + sampling_hops * num_samples + 1
         self.seed = int(philox_seed)
-        self._halo_code = None
         self.grad_sync = grad_sync
         dev = graph.device
         self.targets = torch.zeros(batch_size, dtype=torch.int32, device=dev)          # static input
@@ -212,28 +237,19 @@ class GraphedTrainer:
             raise ValueError("learned node embeddings on several GPUs are not built (the dense N x F gradient would join the "
                              "all-reduce); use one GPU")
         if grad_sync is not None and hasattr(grad_sync, "make_bucket"):
-            # the gradients live inside the all-reduce bucket from the start (same order as the sync call in _step_impl)
+            # the gradients live inside the all-reduce bucket from the start (same order as the sync call in _finish)
             grad_sync.make_bucket([p for m in self._models for p in m.parameters()])
         for m in self._models:
             for p in m.parameters():
                 if p.grad is None:
                     p.grad = torch.zeros_like(p)
         self.out: Dict[str, torch.Tensor] = {}
-        # the prelude pipeline (attach_loader + _run_pipelined): a self-feeding captured step over a plain DeviceGraph
-        # (not with learned embeddings: hop 0's gather-SpMM reads X, which the optimiser then changes — the prelude would not be
-        # weight-independent)
-        self._pipeline_ok = (bool(pipeline) and capture and not self.partitioned and isinstance(graph, DeviceGraph) and
-                             not self.embed and _sw("GRAPES_PRELUDE_PIPELINE", "1") != "0")
-        self._prelude_lane = 0             # (attach_loader gives a pipelined trainer a scratch lane of its own)
-        self._sets = None
-        self._chains: Dict = {}                            # (parity of the first step, steps) -> _StepChain (run_steps)
-        self.graph_obj = None
-        self._want_capture = capture
-        self.steps_done = 0
-        self.eager_steps = 3 if self.partitioned else 2    # warm-up (+ one step with the calibrated slot size)
+        self._init_capture(capture, pipeline)
         self.auto_calibrate = auto_calibrate
-        self._halo = None
         self._fused_adam = None
+        self._pending_slabs = None         # the classifier's deferred slab sums, for the optimiser launch (_classifier_backward)
+        self._iota = None                  # 0, 1, 2, ...: head ids of the transform-first hop graphs (_hop_graph)
+        self._side = None                  # side stream of the GRAPES_BWD_FORK form
         self._mirrored, self._mirrors_current = set(), False      # weights whose padded copy / image the optimiser launch maintains
         # resident features with 16-byte aligned rows (a zero-padded copy when F % 4 != 0), and the first layers' weight images
         # X as peer.PeerFeatures: a 1-D row partition over the GPUs of the node, every shard mapped into this process — the fused
@@ -264,6 +280,27 @@ class GraphedTrainer:
         # cross-queue dependencies of a replayed hipGraph cost more than 5-50 us kernels overlap) and shared the per-device
         # ticket / sync scratch words between concurrent kernels, so that form was removed in round 2.
 
+    def _init_capture(self, capture, pipeline):
+        """The bookkeeping of capture, the loader, step chains and the prelude pipeline."""
+        # the prelude pipeline (attach_loader + _run_pipelined): a self-feeding captured step over a plain DeviceGraph
+        # (not with learned embeddings: hop 0's gather-SpMM reads X, which the optimiser then changes — the prelude would not be
+        # weight-independent)
+        self._pipeline_ok = (bool(pipeline) and capture and not self.partitioned and isinstance(self.g, DeviceGraph) and
+                             not self.embed and _sw("GRAPES_PRELUDE_PIPELINE", "1") != "0")
+        self._prelude_lane = 0             # (attach_loader gives a pipelined trainer a scratch lane of its own)
+        self._sets = None
+        self._cursor = self.edge_totals = None             # attach_loader
+        self._chains: Dict = {}                            # (parity of the first step, steps) -> _StepChain (run_steps)
+        self._chains_off = False                           # the chain builder met a node it does not copy: one launch per step
+        self.graph_obj = None
+        self._want_capture = capture
+        self.steps_done = 0
+        self.eager_steps = 3 if self.partitioned else 2    # warm-up (+ one step with the calibrated slot size)
+        self._bytes_per_step = 0                           # partitioned: bytes one captured step exchanges
+        self._rec_pool = None                              # the recorded preludes' allocations (_capture_pipeline)
+        self._primed = False                               # the first pipelined step has launched its own prelude
+        self._rider_hook = self._rider_end_hook = None     # set while a pipelined step is captured (_capture_pipeline)
+
     # ------------------------------------------------------------------ GCNConv, explicit fwd / bwd
     @staticmethod
     def _conv_fwd(conv, x, prep, relu):
@@ -282,11 +319,11 @@ class GraphedTrainer:
         return ops.linear_bwd_input(dh, conv.lin.weight, d_n=prep.d_n) if need_dx else None
 
     # ---- first layers (input = data rows): see _FirstLayer
-    def _first_fwd(self, conv, ids, prep, num_ind, ep, halo=None, head=None, relu=True, defer_head=False, pair=None, ax=None,
+    def _first_fwd(self, s, conv, ids, prep, num_ind, ep, halo=None, head=None, relu=True, defer_head=False, pair=None, ax=None,
                    h_pre=None, keep=None, x_rows=None):
         """-> (state, act[, head output]).  state = the aggregated input Â[X|ind] (aggregate-first: the operand of the dW
         GEMM) or the id list (transform-first: dW re-reads the rows through it).  ax: Â[X|ind] when the step's prelude has
-        formed it already (it depends on the batch only, not on the weights)."""
+        formed it already (it depends on the batch only, not on the weights).  s: the step — a halo fetch is left in s.halo."""
         st = self._fl[id(conv)]
         code = self.g.ind_code if num_ind else None
         dep = ep if num_ind else None
@@ -318,10 +355,10 @@ class GraphedTrainer:
         elif self.partitioned:
             if halo is None:
                 halo = self.g.fetch_halo(ids, d_n=prep.d_n, keep=keep)                     # halo rows (all-to-all)
-                self._halo = halo
+                s.halo = halo
             if self._halo_in_place and prep.head_ids is not None:
                 # Â [X | ind] straight from the exchanged rows: the head records were built on their positions in `back`
-                ax = ops.gcn_aggregate_gather(halo["back"].view(-1, self.F), prep.head_ids, prep, self._halo_code if num_ind else None,
+                ax = ops.gcn_aggregate_gather(halo["back"].view(-1, self.F), prep.head_ids, prep, s.halo_code if num_ind else None,
                                               0, num_ind, d_epoch=dep, F=self.F)
             else:
                 x = self.g.assemble(halo, ind_code=self.g.ind_code, d_epoch=ep, num_ind=num_ind)
@@ -370,8 +407,12 @@ class GraphedTrainer:
                                       accumulate_bias=accumulate)
         ops.linear_bwd_weight_gathered(dh, self.Xp, self.F, state, st.grad, self.g.ind_code if num_ind else None, 0, num_ind,
                                        d_epoch=ep if num_ind else None, d_n=prep.d_n, accumulate=accumulate, split=st.split,
-                                       # the indicator bits this hop's forward pass saw (main.py:168,191): later hops add theirs
-                                       ind_mask=(((1 << (hop + 1)) - 1) | (1 << (num_ind - 1))) if (num_ind and hop is not None) else 0)
+                                       ind_mask=self._ind_mask(num_ind, hop))
+
+    @staticmethod
+    def _ind_mask(num_ind, hop):
+        """the indicator bits hop `hop`'s forward pass saw (main.py:168,191): later hops add theirs"""
+        return (((1 << (hop + 1)) - 1) | (1 << (num_ind - 1))) if (num_ind and hop is not None) else 0
 
     def _r1_ok(self, conv1, act1):
         """the rank-1 gate-bit form of _head_bwd applies (transform-first layer whose forward kept gate bits)"""
@@ -400,7 +441,7 @@ class GraphedTrainer:
             if dh is None:
                 dh = ops.gcn_aggregate_bwd_rank1(act1, dh2.view(-1), conv2.lin.weight.view(-1), prep, dw_head=w2g.view(-1), dbias=b1g,
                                                  accumulate=accumulate, gate_bits=getattr(act1, "_gate_bits", None))
-            mask = (((1 << (hop + 1)) - 1) | (1 << (num_ind - 1))) if (num_ind and hop is not None) else 0
+            mask = self._ind_mask(num_ind, hop)
             if dw_batch is not None:       # the caller issues the nets' weight-gradient GEMMs together (one launch, one slab sum)
                 dw_batch.append(dict(dh=dh, ids=ax, dw=st.grad, ind_code=self.g.ind_code if num_ind else None, num_ind=num_ind,
                                      d_n=prep.d_n, accumulate=accumulate, ind_mask=mask, split=st.split, ep=ep if num_ind else None))
@@ -460,7 +501,7 @@ class GraphedTrainer:
                     self._mirrored = {id(w) for w in mirrors}
                 except ValueError:
                     self._fused_adam = False
-        pend, self._pending_slabs = getattr(self, "_pending_slabs", None), None
+        pend, self._pending_slabs = self._pending_slabs, None
         if self._fused_adam:
             self._fused_adam.step(slabs=pend)            # (the classifier's deferred slab sums happen inside the update launch)
             self._mirrors_current = True                 # (from now on the mirrored copies follow the weights by themselves)
@@ -470,16 +511,16 @@ class GraphedTrainer:
             for o in opts:
                 o.step()
 
-    def _expand(self, rows, d_m, mark=False, prev_buf=None, remark=None, count=None, stage=None, hop_count=None, finish=None,
+    def _expand(self, s, rows, d_m, mark=False, prev_buf=None, remark=None, count=None, stage=None, hop_count=None, finish=None,
                 ext=None, ext_out=None):
         """get_neighborhoods of `rows`; in the one-launch form also the next hop's bitmap marks (into prev_buf / g.bits,
-        both clean at that point of the step) and the slice re-mark of the current hop (`remark`)."""
+        both clean at that point of the step) and the slice re-mark of the current hop (`remark`); s.marked says whether."""
         g = self.g
-        self._marked = False
+        s.marked = False
         if self.part_adj:
             return g.expand(rows, self.e_cap, d_m=d_m, cap=rows.numel(), want_eoff=True)
         if rows.numel() <= 2048:
-            self._marked = mark
+            s.marked = mark
             return ops.frontier_expand_fused(self._rp, self._cl, rows, self.e_cap, d_m=d_m, status=g.status,
                                              mark_prev_bits=prev_buf if mark else None, mark_bits=g.bits if mark else None,
                                              num_nodes=g.num_nodes, remark=remark,
@@ -512,19 +553,30 @@ class GraphedTrainer:
 
     # ------------------------------------------------------------------ the step body (captured once)
     def _step_impl(self):
-        for _ in self._step_gen():
-            pass
+        self._main(self._prelude())
 
-    def _step_gen(self):
-        """The step as a generator that yields ONCE, at the end of its PRELUDE: the next batch (step_begin), hop 0's expansion,
-        compaction and graph build and — for aggregate-first first layers — hop 0's Â[X|ind].  Nothing before the yield reads
-        a weight, so the prelude of step t + 1 may run while step t is still training (the prelude pipeline, `_run_pipelined`:
-        the two halves are captured as two hipGraphs and replayed on two streams); run straight through it is the whole step."""
-        g, N, B, K, hops, num_ind = self.g, self.g.num_nodes, self.B, self.K, self.hops, self.num_ind
+    def _nets(self):
+        """-> (gf1, gf2, st_gf, z1, z2, st_z): the sampler net's and the log-Z net's layers and first-layer records (None where
+        the mode runs without them: random_sampling neither net, evaluate no log-Z net)."""
+        if self.random_sampling:
+            return (None,) * 6
+        gf1, gf2 = self.gcn_gf.gcn_layers
+        if self.evaluate:
+            return gf1, gf2, self._fl[id(gf1)], None, None, None
+        z1, z2 = self.gcn_z.gcn_layers
+        return gf1, gf2, self._fl[id(gf1)], z1, z2, self._fl[id(z1)]
+
+    def _prelude(self) -> _Step:
+        """The step's PRELUDE: the next batch (step_begin), hop 0's expansion, compaction and graph build and — for
+        aggregate-first first layers — hop 0's Â[X|ind].  Nothing in it reads a weight, so the prelude of step t + 1 may run
+        while step t is still training (the prelude pipeline, `_capture_pipeline`: step t + 1's prelude is recorded once and
+        rides in step t's hipGraph); `_main` right behind it is the whole step.  Every buffer it makes is reachable from the
+        returned state, which is what owns them."""
+        g, B, hops, num_ind = self.g, self.B, self.hops, self.num_ind
         e_cap, n_cap = self.e_cap, self.n_cap
-        st = g.status
         targets = self.targets
         ep = self.epoch_t
+        s = _Step()
         ops.set_scratch_lane(self._prelude_lane)          # (the prelude's one-launch scans may run beside another step's)
         if self._loader is not None:      # the step feeds itself: next batch, epoch, target indicators, edge totals (one launch)
             ids, stride, offset = self._loader
@@ -534,251 +586,306 @@ class GraphedTrainer:
         elif num_ind:                                                                      # main.py:167-168 (new epoch)
             ops.indicator_mark(g.ind_code, targets, 0, num_ind - 1, d_epoch=ep, advance_epoch=True)
         rnd = self.random_sampling
-        ev = self.evaluate
-        if not rnd:
-            st_gf = self._fl[id(self.gcn_gf.gcn_layers[0])]
-            st_z = None if ev else self._fl[id(self.gcn_z.gcn_layers[0])]
-        previous, d_m = targets, None                                                      # main.py:163
+        s.previous, s.d_m = targets, None                                                  # main.py:163
         # one-launch expansions carry the bitmap marks and the slice re-marks; they alternate two previous-node bitmaps so
         # that a launch can set the next hop's previous set while it clears this hop's
-        fused, staged, counted = self._hop_modes()
-        if ev:
-            staged = False       # (the evaluation's slices come from each hop's OWN expansion, filtered after its draw: below)
+        s.fused, s.staged, s.counted = self._hop_modes()
+        if self.evaluate:
+            s.staged = False     # (the evaluation's slices come from each hop's OWN expansion, filtered after its draw: _hop_advance)
         # the draw's last launch without a tail: its log-prob sum and histogram reset ride in the expansion that follows it
         # (one-launch expansions only; A/B: GRAPES_DRAW_DEFER=0)
-        defer_draw = fused and self.B + self.K * self.hops <= 2048 and _sw("GRAPES_DRAW_DEFER", "1") != "0"
+        s.defer_draw = s.fused and self.B + self.K * self.hops <= 2048 and _sw("GRAPES_DRAW_DEFER", "1") != "0"
         # RCCL request / reply form: the hops' exchanged rows are kept side by side and the classifier's features (main.py:256) are
         # found among them — all_nodes are targets + kept nodes, batch rows of the hops' fetches — instead of being requested
         # again: two collectives per step less (A/B: GRAPES_HALO_REUSE=0)
-        halo_reuse = (self.partitioned and self._halo_in_place and not rnd and not self.embed and
-                      getattr(g, "can_reuse_rows", False) and _sw("GRAPES_HALO_REUSE", "1") != "0")
-        kept_halo = None
-        pbuf = [g.prev_bits, g.prev_bits_b] if fused else [g.prev_bits, g.prev_bits]
-        hc = g.hop_counters() if counted else None
-        hbs = [ops.HopBuild(n_cap, e_cap, targets.device, counters=self._ctr[h]) for h in range(hops)] if counted else None
+        s.halo_reuse = (self.partitioned and self._halo_in_place and not rnd and not self.embed and
+                        getattr(g, "can_reuse_rows", False) and _sw("GRAPES_HALO_REUSE", "1") != "0")
+        s.pbuf = [g.prev_bits, g.prev_bits_b] if s.fused else [g.prev_bits, g.prev_bits]
+        s.hc = g.hop_counters() if s.counted else None
+        s.hbs = [ops.HopBuild(n_cap, e_cap, targets.device, counters=self._ctr[h]) for h in range(hops)] if s.counted else None
         # the query lists' ROW EXTENTS travel with their ids (round 5): hop 0's expansion leaves the targets' (rowptr[id], rowptr[id + 1]),
         # every draw writes its kept nodes' next to the ids of  cat(targets, kept)  — the expansions of hops >= 1 then read ids and
         # extents in one round trip instead of two dependent ones (A/B: GRAPES_EXPAND_EXT=0)
-        with_ext = fused and defer_draw and previous.numel() <= 2048 and _sw("GRAPES_EXPAND_EXT", "1") != "0"
-        tgt_ext = torch.empty(2 * B, dtype=torch.int64, device=targets.device) if with_ext else None
-        src, dst, d_e, eoff = self._expand(previous, d_m, mark=True, prev_buf=pbuf[0],     # main.py:180 (hop 0) + its marks
-                                           hop_count=(hc, hbs[0]) if counted else None, ext_out=tgt_ext)
-        hop_state: List[Dict] = []
-        hop_stats = torch.empty((hops, 6), dtype=torch.float32, device=targets.device)     # one statistics row per hop
-        kept_list, slices, neigh_list, nbl_list, dnn_list, dnb_list = [], [], [], [], [], []
-        stages = []
-        # device counters of every graph build in one table: column 2 = edges one aggregation over that graph sums
-        ctr = self._ctr
-        agg_w = [0] * (2 * hops)                                                           # aggregations per graph
-        agg_x = [0] * (2 * hops)                          # ... of which run as aggregation launches (see `reuse` below)
+        s.with_ext = s.fused and s.defer_draw and s.previous.numel() <= 2048 and _sw("GRAPES_EXPAND_EXT", "1") != "0"
+        s.tgt_ext = torch.empty(2 * B, dtype=torch.int64, device=targets.device) if s.with_ext else None
+        s.src, s.dst, s.d_e, s.eoff = self._expand(s, s.previous, s.d_m, mark=True, prev_buf=s.pbuf[0],   # main.py:180 (hop 0) + its marks
+                                                   hop_count=(s.hc, s.hbs[0]) if s.counted else None, ext_out=s.tgt_ext)
+        s.hop_state = []
+        s.hop_stats = torch.empty((hops, 6), dtype=torch.float32, device=targets.device)   # one statistics row per hop
+        s.kept_list, s.slices, s.neigh_list, s.nbl_list, s.dnn_list, s.dnb_list = [], [], [], [], [], []
+        s.stages = []
+        s.agg_w = [0] * (2 * hops)                                                         # aggregations per graph
+        s.agg_x = [0] * (2 * hops)                        # ... of which run as aggregation launches (see `reuse` in _hop_sample)
+        self._hop_graph(s, 0)
+        # ---- end of the PRELUDE: nothing above reads a weight
+        ops.set_scratch_lane(0)
+        return s
+
+    def _hop_graph(self, s, hop):
+        """Graph phase of a hop (main.py:183-195): its marks if the expansion has not made them, the compaction, the halo
+        positions, the hop graph's build and — hop 0, aggregate-first sampler net — Â[X|ind].  Reads no weight."""
+        g, N, num_ind = self.g, self.g.num_nodes, self.num_ind
+        e_cap, n_cap = self.e_cap, self.n_cap
+        st = g.status
+        targets = self.targets
+        ep = self.epoch_t
+        rnd, ev = self.random_sampling, self.evaluate
+        st_gf = self._nets()[2]
+        fused, staged, counted = s.fused, s.staged, s.counted
+        cur_prev = s.pbuf[hop % 2]
+        if not s.marked:      # (the fused expansion of the previous iteration has done this hop's marks)
+            ops.bitmap_mark_hop(cur_prev, g.bits, g.bits1, s.previous, s.eoff, s.dst, N, d_m=s.d_m, d_e=s.d_e, status=st)
+        # (the compaction also clears the scratch of the graph build that follows it: one launch less per hop)
+        # ... and, with the one-launch expansions, applies the slice marks of this hop (un-mark older samples, mark the
+        # newer ones: main.py:241-243 keeps the columns `previous` = targets + the samples of the hop before; the targets
+        # stay marked for the whole step, the last marks go when all_nodes is built) and zeroes the survivor counters the
+        # hop's expansion fills for slice_filter
+        pscr = ops.PreparedGraph.scratch(n_cap, s.src.numel(), targets.device) if (n_cap > 2048 and not rnd and not counted) else None
+        bsum = torch.empty(max(int(ops.lib().grapes_slice_filter_workspace_bytes(e_cap)) // 4, 1), dtype=torch.int32,
+                           device=targets.device) if (fused and not staged and not ev) else None
+        s.pscr, s.bsum = pscr, bsum
+        s.sstage = ops.slice_stage(e_cap, targets.device) if staged else None
+        s.rm_lists = dict(mult=g.mult, unmark=s.kept_list[hop - 2] if hop >= 2 else None,
+                          mark=(targets, None) if hop == 0 else s.kept_list[hop - 1])
+        hbs = s.hbs
+        s.batch, s.neigh, s.nbl, s.counts, s.cand_pos = ops.frontier_compact(
+            g.bits, g.bits1, cur_prev, N, n_cap, node_map=g.node_map, status=st,
+            ind_code=g.ind_code if num_ind else None, d_epoch=ep, ind_bit=hop, want_cand_pos=True,
+            zero=(list(pscr[2]) if pscr is not None else []) + ([(hbs[hop].csr_dst, e_cap)] if counted else []) +
+                 ([(bsum, bsum.numel())] if bsum is not None else []),
+            remark=s.rm_lists if (fused and not ev) else None,                             # main.py:183-194 (+ 191)
+            degrees=(s.hc, hbs[hop]) if counted else None)
+        batch = s.batch
+        d_nb, d_nn = s.counts[0:1], s.counts[1:2]
+        s.neigh_list.append(s.neigh); s.nbl_list.append(s.nbl); s.dnn_list.append(d_nn); s.dnb_list.append(d_nb)
+        hid = batch
+        if (not rnd) and self.partitioned:
+            hid = None
+            if self._halo_in_place:            # where this hop's rows will sit in the exchanged buffer (+ their indicator words)
+                hid, s.halo_code, _ = g.halo_positions(batch, d_nb, batch.numel(), ind_code=g.ind_code if num_ind else None,
+                                                       tag="h%d" % hop)
+        prep = ax_pre = None
         if not rnd:
-            gf1, gf2 = self.gcn_gf.gcn_layers
-            z1, z2 = (None, None) if ev else self.gcn_z.gcn_layers
-        zstate = None
-        for hop in range(hops):                                                            # main.py:178
-            cur_prev = pbuf[hop % 2]
-            if not self._marked:      # (the fused expansion of the previous iteration has done this hop's marks)
-                ops.bitmap_mark_hop(cur_prev, g.bits, g.bits1, previous, eoff, dst, N, d_m=d_m, d_e=d_e, status=st)
-            # (the compaction also clears the scratch of the graph build that follows it: one launch less per hop)
-            # ... and, with the one-launch expansions, applies the slice marks of this hop (un-mark older samples, mark the
-            # newer ones: main.py:241-243 keeps the columns `previous` = targets + the samples of the hop before; the targets
-            # stay marked for the whole step, the last marks go when all_nodes is built) and zeroes the survivor counters the
-            # hop's expansion fills for slice_filter
-            pscr = ops.PreparedGraph.scratch(n_cap, src.numel(), targets.device) if (n_cap > 2048 and not rnd and not counted) else None
-            bsum = torch.empty(max(int(ops.lib().grapes_slice_filter_workspace_bytes(e_cap)) // 4, 1), dtype=torch.int32,
-                               device=targets.device) if (fused and not staged and not ev) else None
-            sstage = ops.slice_stage(e_cap, targets.device) if staged else None
-            rm_lists = dict(mult=g.mult, unmark=kept_list[hop - 2] if hop >= 2 else None,
-                            mark=(targets, None) if hop == 0 else kept_list[hop - 1])
-            batch, neigh, nbl, counts, cand_pos = ops.frontier_compact(
-                g.bits, g.bits1, cur_prev, N, n_cap, node_map=g.node_map, status=st,
-                ind_code=g.ind_code if num_ind else None, d_epoch=ep, ind_bit=hop, want_cand_pos=True,
-                zero=(list(pscr[2]) if pscr is not None else []) + ([(hbs[hop].csr_dst, e_cap)] if counted else []) +
-                     ([(bsum, bsum.numel())] if bsum is not None else []),
-                remark=rm_lists if (fused and not ev) else None,                           # main.py:183-194 (+ 191)
-                degrees=(hc, hbs[hop]) if counted else None)
-            d_nb, d_nn = counts[0:1], counts[1:2]
-            neigh_list.append(neigh); nbl_list.append(nbl); dnn_list.append(d_nn); dnb_list.append(d_nb)
-            hid = batch
-            if (not rnd) and self.partitioned:
-                hid = None
-                if self._halo_in_place:            # where this hop's rows will sit in the exchanged buffer (+ their indicator words)
-                    hid, self._halo_code, _ = g.halo_positions(batch, d_nb, batch.numel(), ind_code=g.ind_code if num_ind else None,
-                                                               tag="h%d" % hop)
-            prep = ax_pre = None
-            if not rnd:
-                pf_rows = (self._prefetch_X, self.F) if (self._prefetch_X is not None and hid is batch and st_gf.agg_first) else None
-                # transform-first layers aggregate [n, hidden] activations, not rows of X: their graph's head records are taken over
-                # LOCAL ids (head_ids = 0, 1, 2, ...) and drive the record form of that aggregation (one dependent trip per row)
-                local_heads = (hid is batch) and not st_gf.agg_first
-                if local_heads:
-                    if getattr(self, "_iota", None) is None:
-                        self._iota = torch.arange(n_cap, dtype=torch.int32, device=targets.device)
-                    hid = self._iota
-                if counted:
-                    prep = ops.PreparedGraph.counted(src, dst, hbs[hop], n_cap, d_nb, d_e, g.node_map, status=st, head_ids=hid,
-                                                     prefetch=pf_rows, head_local=local_heads)
-                else:
-                    prep = ops.PreparedGraph(src, dst, n_cap, d_n=d_nb, d_e=d_e, status=st, src_grouped=True,
-                                             items_fwd=False, node_map=g.node_map,                 # main.py:195 relabel inside
-                                             head_ids=hid, counters=ctr[hop], scratch=pscr, head_local=local_heads,
-                                             # the rows of X the fused gather-SpMM reads ~20 us later, fetched into the Infinity
-                                             # Cache by spare workgroups of the build's first launch
-                                             prefetch=pf_rows)
-                if hop == 0 and st_gf.agg_first and not self.partitioned:
-                    # main.py:199-204 + the aggregation of the sampler net's first layer: Â [X | ind | 0] of hop 0 depends on the
-                    # batch only — the last launch of the prelude
-                    ax_pre = ops.gcn_aggregate_gather(self.Xp, batch, prep, g.ind_code if num_ind else None, 0, num_ind,
-                                                      d_epoch=ep if num_ind else None, F=self.F)
-            if hop == 0:
-                # ---- end of the PRELUDE: nothing above reads a weight (see _step_gen's docstring)
-                ops.set_scratch_lane(0)
-                yield
-                fls = list(self._fl.values())              # weight images of the first layers (strided copies; no-ops when
-                if self._mirrors_current:                  # (kept current by the optimiser launch: _optim_step)
-                    fls = [fl for fl in fls if id(fl.conv.lin.weight) not in self._mirrored]
-                sp = [fl for fl in fls if fl.split]        # F + num_ind is a multiple of 4)
-                if 2 <= len(sp) <= 4 and _sw("GRAPES_IMAGES_ONE_LAUNCH", "1") != "0":
-                    ops.weight_split_images([fl.conv.lin.weight.detach() for fl in sp], [fl.image for fl in sp],
-                                        [fl.W if fl.padded else None for fl in sp])
-                    fls = [fl for fl in fls if not fl.split]
-                for fl in fls:
-                    fl.refresh()
-                if self.embed:
-                    ops.fill(self.X.grad.view(-1), 0.0)                  # optimizer_c.zero_grad() (main.py:263) for the embeddings
-            if rnd:
-                # main.py:206-220 with constant logits: the hop graph is never built (no net reads it), the draw is uniform
-                res = ops.gumbel_topk(self._rnd_logits, K, logit_index=nbl, candidate_ids=neigh, n=n_cap, d_n=d_nn,
-                                      philox_seed=self.seed, d_philox_offset=self.philox_off, want_stats=True,
-                                      prefix_ids=targets, stats_out=hop_stats[hop], defer_finish=defer_draw,
-                                      ext=(self._rp, tgt_ext) if with_ext else None)
-                kept_list.append((res["kept_ids"], res["kept_count"]))                     # main.py:221
-            if not rnd:
-                fuse_keys = _sw("GRAPES_FUSED_KEYS", "0") != "0"     # measured: 23.7 + 25.2 us vs 4.9 + 14.8 + 23.4 unfused — off
-                # main.py:227: at hop 0 the log-Z net sees data.x[batch_nodes] — the rows the sampler net aggregates, minus the
-                # indicator columns — so its  Â X  is the leading F columns of the sampler net's  Â [X | ind]: read in place (row
-                # stride F + ind) instead of a second gather-SpMM over the same rows (columns F .. ceil4(F) of that view hold
-                # aggregated indicator values; the log-Z weight image is zero there)
-                reuse = ((not ev) and hop == 0 and (not self.partitioned or self._halo_in_place) and st_gf.agg_first and st_z.agg_first and
-                         _sw("GRAPES_FUSED_HEAD", "1") != "0" and
-                         ops.split_gemm_available(n_cap, st_z.Kp, z1.lin.weight.shape[0]) and
-                         # (f_in > 112 — arxiv, papers100M — has the gate-word backward only: the strided view needs it)
-                         (st_z.Kp <= 112 or _sw("GRAPES_GATE_BITS", "1") != "0"))
-                # ... and the two nets' 1-wide heads are then aggregated over the hop graph by ONE launch
-                pair_heads = reuse and not fuse_keys and _sw("GRAPES_HEAD_PAIR", "1") != "0"
-                gemm_pair = pair_heads and _sw("GRAPES_GEMM_PAIR", "1") != "0"
-                # transform-first nets (Reddit, Cora's wide frontiers): at hop 0 the sampler net's and the log-Z net's X Wᵀ read the
-                # same rows — one launch over both, its last partial round cut along K (A/B: GRAPES_TSPLIT_FWD_DUAL=0)
-                h_gf = h_z = None
-                if ((not ev) and hop == 0 and not st_gf.agg_first and not st_z.agg_first and st_gf.image is not None and st_z.image is not None and
-                        gf1.out_channels == z1.out_channels and gf1.out_channels % 4 == 0 and batch.numel() >= int(_sw("GRAPES_TSPLIT_FWD_DUAL_MIN", "8192")) and
-                        not self.partitioned and self.peers is None and _sw("GRAPES_TSPLIT_FWD_DUAL", "1") != "0" and
-                        (self.F + num_ind + 31) // 32 == (self.F + 31) // 32):      # (the nets share the K steps)
-                    h_gf, h_z = ops.linear_fwd_gathered_tail(self.Xp, self.F, batch, [st_gf.image, st_z.image], gf1.out_channels,
-                                                             [self.g.ind_code if num_ind else None, None], [num_ind, 0],
-                                                             d_epoch=ep if num_ind else None, d_n=prep.d_n)
-                ff = self._first_fwd(gf1, batch, prep, num_ind, ep, head=gf2, defer_head=fuse_keys or pair_heads,   # main.py:199-210
-                                     pair=(st_z, z1, z2) if gemm_pair else None, ax=ax_pre, h_pre=h_gf,
-                                     keep=(hop, hops) if halo_reuse else None)
-                if halo_reuse:
-                    kept_halo = self._halo
-                    if "base" not in kept_halo:
-                        halo_reuse, kept_halo = False, None        # (a first layer that did not fetch through fetch_halo)
-                    elif hop == 0:                                 # the targets are batch rows of hop 0 (node_map: its relabel)
-                        g.note_rows(kept_halo, targets, None, hid, node_map=g.node_map, batch=batch, d_n_batch=d_nb)
-                x, act1, logit = ff[:3]
-                agg_w[hop] += 2
-                agg_x[hop] += 2
-                z_pre = None
-                if pair_heads and isinstance(logit, tuple):
-                    xz = x[:, :st_z.Kp]
-                    if len(ff) == 4:                   # both nets' first layers came out of ONE launch
-                        xz, zact, zhw = ff[3]
-                    elif self._gate_bits(xz, st_z, z1):
-                        zact, zhw = ops.linear_relu_head_fwd_bits(xz, st_z.weight, z1.bias, z2.lin.weight, d_n=prep.d_n)
-                    else:
-                        zact, zhw = ops.linear_bias_act_head_fwd_strided(xz, st_z.weight, z1.bias, True, z2.lin.weight, d_n=prep.d_n)
-                    logit, zout = ops.gcn_aggregate_narrow_pair(logit[1], zhw, prep, gf2.bias, z2.bias)    # Â (act w2ᵀ) + b2, twice
-                    z_pre = (xz, zact, zout)
-                # exact-k draw over the neighbour candidates (main.py:213-220); logits are read through nb_local
-                agg = None
-                if isinstance(logit, tuple):       # logits = Â (act w2ᵀ) + b2 formed by the draw's first launch, with the keys
-                    agg, logit = (logit[1].view(-1), prep, gf2.bias, cand_pos), None
-                res = ops.gumbel_topk(None if agg is not None else logit.view(-1), K, logit_index=nbl, candidate_ids=neigh, n=n_cap,
-                                      d_n=d_nn, philox_seed=self.seed, d_philox_offset=self.philox_off, want_stats=True,
-                                      prefix_ids=targets, stats_out=hop_stats[hop], agg=agg, defer_finish=defer_draw and agg is None,
-                                      mode=1 if ev else 0,                                     # (eval.py:126-130: greedy)
-                                      ext=(self._rp, tgt_ext) if (with_ext and agg is None) else None)
-                if agg is not None:
-                    logit = res["logits"]                                                      # [n_cap, 1]
-                kept_list.append((res["kept_ids"], res["kept_count"]))                         # main.py:221
-                if halo_reuse:                  # the kept nodes are candidates, i.e. batch rows, of this hop's fetch
-                    g.note_rows(kept_halo, res["kept_ids"], res["kept_count"], hid, idx_a=res["kept_pos"], idx_b=nbl)
-                if hop == 0 and not ev:                                                        # main.py:223-228
-                    if z_pre is not None:
-                        xz, zact, zout = z_pre
-                    elif reuse:
-                        xz = x[:, :st_z.Kp]
-                        if self._gate_bits(xz, st_z, z1):
-                            zact, zhw = ops.linear_relu_head_fwd_bits(xz, st_z.weight, z1.bias, z2.lin.weight, d_n=prep.d_n)
-                        else:
-                            zact, zhw = ops.linear_bias_act_head_fwd_strided(xz, st_z.weight, z1.bias, True, z2.lin.weight,
-                                                                             d_n=prep.d_n)
-                        zout = ops.gcn_aggregate_fwd(zhw, prep, z2.bias, False)
-                    else:
-                        xz, zact, zout = self._first_fwd(z1, batch, prep, 0, ep, halo=self._halo if self.partitioned else None,
-                                                         head=z2, h_pre=h_z)              # zout's mean: in step_losses
-                    zstate = dict(x=xz, act=zact, prep=prep, d_nb=d_nb, batch=batch, zout=zout)
-                    agg_w[hop] += 2
-                    agg_x[hop] += 1 if reuse else 2
-                hop_state.append(dict(x=x, act1=act1, logit=logit, prep=prep, nbl=nbl, mask=res["mask"], d_nn=d_nn, cand_pos=cand_pos,
-                                      stats=res["stats"]))
-            batch_next, d_m_next = res["union_ids"], res["union_count"]                    # main.py:236-238
-            # main.py:241-243: the columns kept are `previous` = targets + the samples of the hop before.  The targets stay
-            # marked for the whole step; the older samples are un-marked and the newer ones marked in one launch (they are
-            # disjoint); the last marks go when all_nodes is built below.  The hop's prev_bits are done with, too.
-            if hop + 1 == hops and getattr(self, "_rider_hook", None) is not None:
-                # from here on the step's launches are the classifier's: a handful of workgroups each on an idle chip — the NEXT
-                # step's recorded prelude rides in them (_capture_pipeline)
-                self._rider_hook()
-            if ev:
-                # eval.py:140-142: slice_adjacency(rows = previous_nodes, cols = the new layer) — this hop's OWN expansion (still
-                # in src / dst), filtered by membership in batch_next: mark, ordered filter, un-mark (no host read)
-                ops.slice_mark(g.mult, batch_next, d_c=d_m_next)
-                ev_slice = ops.slice_filter(g.mult, src, dst, min(e_cap, (B + K) * (B + K)), d_e=d_e, status=st)
-                if not fused:
-                    ops.slice_mark(g.mult, batch_next, unmark=True, d_c=d_m_next)
-            if fused:                 # the expansion of the next previous_nodes also clears this hop's previous-set bitmap
-                # and counts the slice survivors of its own edges against the marks made at the top of the hop
-                # (evaluation: the un-mark of the slice just taken rides here instead — this launch reads no mark)
-                src, dst, d_e, eoff = self._expand(batch_next, d_m_next, mark=hop + 1 < hops, prev_buf=pbuf[(hop + 1) % 2],
-                                                   remark=dict(mult=g.mult if ev else None, unmark=(batch_next, d_m_next) if ev else None,
-                                                               clear=(previous, d_m), clear_bits=cur_prev),
-                                                   count=None if ev else (g.mult, bsum), stage=sstage,     # (the last one only feeds the slice)
-                                                   hop_count=(hc, hbs[hop + 1]) if (counted and hop + 1 < hops) else None,
-                                                   finish=res.get("finish"),               # (+ the end of this hop's draw)
-                                                   ext=res.get("union_ext"))
+            pf_rows = (self._prefetch_X, self.F) if (self._prefetch_X is not None and hid is batch and st_gf.agg_first) else None
+            # transform-first layers aggregate [n, hidden] activations, not rows of X: their graph's head records are taken over
+            # LOCAL ids (head_ids = 0, 1, 2, ...) and drive the record form of that aggregation (one dependent trip per row)
+            local_heads = (hid is batch) and not st_gf.agg_first
+            if local_heads:
+                if self._iota is None:
+                    self._iota = torch.arange(n_cap, dtype=torch.int32, device=targets.device)
+                hid = self._iota
+            if counted:
+                prep = ops.PreparedGraph.counted(s.src, s.dst, hbs[hop], n_cap, d_nb, s.d_e, g.node_map, status=st, head_ids=hid,
+                                                 prefetch=pf_rows, head_local=local_heads)
             else:
-                ops.slice_remark(g.mult, unmark=rm_lists["unmark"], mark=rm_lists["mark"], clear=(previous, d_m),
-                                 clear_bits=cur_prev)
-                src, dst, d_e, eoff = self._expand(batch_next, d_m_next, mark=hop + 1 < hops, prev_buf=cur_prev)
-            if staged:                # outputs of the classifier's graph build below (which assembles them from the stage)
-                kcap = min(e_cap, (B + K) * (B + K))
-                ksrc = torch.empty(kcap, dtype=torch.int32, device=targets.device)
-                kdst = torch.empty(kcap, dtype=torch.int32, device=targets.device)
-                kcnt = torch.empty(1, dtype=torch.int32, device=targets.device)
-                stages.append((sstage, d_e, e_cap))
-            elif ev:
-                ksrc, kdst, kcnt = ev_slice
+                prep = ops.PreparedGraph(s.src, s.dst, n_cap, d_n=d_nb, d_e=s.d_e, status=st, src_grouped=True,
+                                         items_fwd=False, node_map=g.node_map,                 # main.py:195 relabel inside
+                                         head_ids=hid, counters=self._ctr[hop], scratch=pscr, head_local=local_heads,
+                                         # the rows of X the fused gather-SpMM reads ~20 us later, fetched into the Infinity
+                                         # Cache by spare workgroups of the build's first launch
+                                         prefetch=pf_rows)
+            if hop == 0 and st_gf.agg_first and not self.partitioned:
+                # main.py:199-204 + the aggregation of the sampler net's first layer: Â [X | ind | 0] of hop 0 depends on the
+                # batch only — the last launch of the prelude
+                ax_pre = ops.gcn_aggregate_gather(self.Xp, batch, prep, g.ind_code if num_ind else None, 0, num_ind,
+                                                  d_epoch=ep if num_ind else None, F=self.F)
+        s.hid, s.prep, s.ax_pre = hid, prep, ax_pre
+
+    def _refresh_weights(self):
+        """Top of the main part: the first layers' weight images the optimiser launch does not maintain, and
+        optimizer_c.zero_grad() for learned embeddings."""
+        fls = list(self._fl.values())              # weight images of the first layers (strided copies; no-ops when
+        if self._mirrors_current:                  # (kept current by the optimiser launch: _optim_step)
+            fls = [fl for fl in fls if id(fl.conv.lin.weight) not in self._mirrored]
+        sp = [fl for fl in fls if fl.split]        # F + num_ind is a multiple of 4)
+        if 2 <= len(sp) <= 4 and _sw("GRAPES_IMAGES_ONE_LAUNCH", "1") != "0":
+            ops.weight_split_images([fl.conv.lin.weight.detach() for fl in sp], [fl.image for fl in sp],
+                                [fl.W if fl.padded else None for fl in sp])
+            fls = [fl for fl in fls if not fl.split]
+        for fl in fls:
+            fl.refresh()
+        if self.embed:
+            ops.fill(self.X.grad.view(-1), 0.0)                  # optimizer_c.zero_grad() (main.py:263) for the embeddings
+
+    def _z_first_strided(self, xz, prep):
+        """-> (act, act w2ᵀ): the log-Z net's first layer and the X W step of its head over xz, the leading columns of the
+        sampler net's Â[X|ind] read in place (row stride F + ind)."""
+        _, _, _, z1, z2, st_z = self._nets()
+        if self._gate_bits(xz, st_z, z1):
+            return ops.linear_relu_head_fwd_bits(xz, st_z.weight, z1.bias, z2.lin.weight, d_n=prep.d_n)
+        return ops.linear_bias_act_head_fwd_strided(xz, st_z.weight, z1.bias, True, z2.lin.weight, d_n=prep.d_n)
+
+    def _hop_sample(self, s, hop):
+        """Sampling phase of a hop (main.py:199-228): the sampler net over the hop graph, at hop 0 the log-Z net, the exact-k
+        draw.  -> the draw's result."""
+        g, K, hops, num_ind, n_cap = self.g, self.K, self.hops, self.num_ind, self.n_cap
+        targets = self.targets
+        ep = self.epoch_t
+        ev = self.evaluate
+        batch, prep, neigh, nbl, cand_pos, hid = s.batch, s.prep, s.neigh, s.nbl, s.cand_pos, s.hid
+        d_nb, d_nn = s.dnb_list[hop], s.dnn_list[hop]
+        if self.random_sampling:
+            # main.py:206-220 with constant logits: the hop graph is never built (no net reads it), the draw is uniform
+            res = ops.gumbel_topk(self._rnd_logits, K, logit_index=nbl, candidate_ids=neigh, n=n_cap, d_n=d_nn,
+                                  philox_seed=self.seed, d_philox_offset=self.philox_off, want_stats=True,
+                                  prefix_ids=targets, stats_out=s.hop_stats[hop], defer_finish=s.defer_draw,
+                                  ext=(self._rp, s.tgt_ext) if s.with_ext else None)
+            s.kept_list.append((res["kept_ids"], res["kept_count"]))                       # main.py:221
+            return res
+        gf1, gf2, st_gf, z1, z2, st_z = self._nets()
+        fuse_keys = _sw("GRAPES_FUSED_KEYS", "0") != "0"     # measured: 23.7 + 25.2 us vs 4.9 + 14.8 + 23.4 unfused — off
+        # main.py:227: at hop 0 the log-Z net sees data.x[batch_nodes] — the rows the sampler net aggregates, minus the
+        # indicator columns — so its  Â X  is the leading F columns of the sampler net's  Â [X | ind]: read in place (row
+        # stride F + ind) instead of a second gather-SpMM over the same rows (columns F .. ceil4(F) of that view hold
+        # aggregated indicator values; the log-Z weight image is zero there)
+        reuse = ((not ev) and hop == 0 and (not self.partitioned or self._halo_in_place) and st_gf.agg_first and st_z.agg_first and
+                 _sw("GRAPES_FUSED_HEAD", "1") != "0" and
+                 ops.split_gemm_available(n_cap, st_z.Kp, z1.lin.weight.shape[0]) and
+                 # (f_in > 112 — arxiv, papers100M — has the gate-word backward only: the strided view needs it)
+                 (st_z.Kp <= 112 or _sw("GRAPES_GATE_BITS", "1") != "0"))
+        # ... and the two nets' 1-wide heads are then aggregated over the hop graph by ONE launch
+        pair_heads = reuse and not fuse_keys and _sw("GRAPES_HEAD_PAIR", "1") != "0"
+        gemm_pair = pair_heads and _sw("GRAPES_GEMM_PAIR", "1") != "0"
+        # transform-first nets (Reddit, Cora's wide frontiers): at hop 0 the sampler net's and the log-Z net's X Wᵀ read the
+        # same rows — one launch over both, its last partial round cut along K (A/B: GRAPES_TSPLIT_FWD_DUAL=0)
+        h_gf = h_z = None
+        if ((not ev) and hop == 0 and not st_gf.agg_first and not st_z.agg_first and st_gf.image is not None and st_z.image is not None and
+                gf1.out_channels == z1.out_channels and gf1.out_channels % 4 == 0 and batch.numel() >= int(_sw("GRAPES_TSPLIT_FWD_DUAL_MIN", "8192")) and
+                not self.partitioned and self.peers is None and _sw("GRAPES_TSPLIT_FWD_DUAL", "1") != "0" and
+                (self.F + num_ind + 31) // 32 == (self.F + 31) // 32):      # (the nets share the K steps)
+            h_gf, h_z = ops.linear_fwd_gathered_tail(self.Xp, self.F, batch, [st_gf.image, st_z.image], gf1.out_channels,
+                                                     [self.g.ind_code if num_ind else None, None], [num_ind, 0],
+                                                     d_epoch=ep if num_ind else None, d_n=prep.d_n)
+        ff = self._first_fwd(s, gf1, batch, prep, num_ind, ep, head=gf2, defer_head=fuse_keys or pair_heads,   # main.py:199-210
+                             pair=(st_z, z1, z2) if gemm_pair else None, ax=s.ax_pre, h_pre=h_gf,
+                             keep=(hop, hops) if s.halo_reuse else None)
+        if s.halo_reuse:
+            s.kept_halo = s.halo
+            if "base" not in s.kept_halo:
+                s.halo_reuse, s.kept_halo = False, None        # (a first layer that did not fetch through fetch_halo)
+            elif hop == 0:                                 # the targets are batch rows of hop 0 (node_map: its relabel)
+                g.note_rows(s.kept_halo, targets, None, hid, node_map=g.node_map, batch=batch, d_n_batch=d_nb)
+        x, act1, logit = ff[:3]
+        s.agg_w[hop] += 2
+        s.agg_x[hop] += 2
+        z_pre = None
+        if pair_heads and isinstance(logit, tuple):
+            if len(ff) == 4:                   # both nets' first layers came out of ONE launch
+                xz, zact, zhw = ff[3]
             else:
-                ksrc, kdst, kcnt = ops.slice_filter(g.mult, src, dst, min(e_cap, (B + K) * (B + K)), d_e=d_e, status=st,
-                                                    bsum=bsum if fused else None)
-            slices.append((ksrc, kdst, kcnt))
-            previous, d_m = batch_next, d_m_next                                           # main.py:247
-        # ---- final relabel + classifier (main.py:252-261)
-        marks = [(targets, None)] + [(kept, cnt) for kept, cnt in kept_list]                # main.py:221,252
+                xz = x[:, :st_z.Kp]
+                zact, zhw = self._z_first_strided(xz, prep)
+            logit, zout = ops.gcn_aggregate_narrow_pair(logit[1], zhw, prep, gf2.bias, z2.bias)    # Â (act w2ᵀ) + b2, twice
+            z_pre = (xz, zact, zout)
+        # exact-k draw over the neighbour candidates (main.py:213-220); logits are read through nb_local
+        agg = None
+        if isinstance(logit, tuple):       # logits = Â (act w2ᵀ) + b2 formed by the draw's first launch, with the keys
+            agg, logit = (logit[1].view(-1), prep, gf2.bias, cand_pos), None
+        res = ops.gumbel_topk(None if agg is not None else logit.view(-1), K, logit_index=nbl, candidate_ids=neigh, n=n_cap,
+                              d_n=d_nn, philox_seed=self.seed, d_philox_offset=self.philox_off, want_stats=True,
+                              prefix_ids=targets, stats_out=s.hop_stats[hop], agg=agg, defer_finish=s.defer_draw and agg is None,
+                              mode=1 if ev else 0,                                     # (eval.py:126-130: greedy)
+                              ext=(self._rp, s.tgt_ext) if (s.with_ext and agg is None) else None)
+        if agg is not None:
+            logit = res["logits"]                                                      # [n_cap, 1]
+        s.kept_list.append((res["kept_ids"], res["kept_count"]))                       # main.py:221
+        if s.halo_reuse:                # the kept nodes are candidates, i.e. batch rows, of this hop's fetch
+            g.note_rows(s.kept_halo, res["kept_ids"], res["kept_count"], hid, idx_a=res["kept_pos"], idx_b=nbl)
+        if hop == 0 and not ev:                                                        # main.py:223-228
+            if z_pre is not None:
+                xz, zact, zout = z_pre
+            elif reuse:
+                xz = x[:, :st_z.Kp]
+                zact, zhw = self._z_first_strided(xz, prep)
+                zout = ops.gcn_aggregate_fwd(zhw, prep, z2.bias, False)
+            else:
+                xz, zact, zout = self._first_fwd(s, z1, batch, prep, 0, ep, halo=s.halo if self.partitioned else None,
+                                                 head=z2, h_pre=h_z)              # zout's mean: in step_losses
+            s.zstate = dict(x=xz, act=zact, prep=prep, d_nb=d_nb, batch=batch, zout=zout)
+            s.agg_w[hop] += 2
+            s.agg_x[hop] += 1 if reuse else 2
+        s.hop_state.append(dict(x=x, act1=act1, logit=logit, prep=prep, nbl=nbl, mask=res["mask"], d_nn=d_nn, cand_pos=cand_pos,
+                                stats=res["stats"]))
+        return res
+
+    def _hop_advance(self, s, hop, res):
+        """Advance phase of a hop (main.py:236-247): the evaluation's slice, the expansion of the next previous_nodes (or the
+        slice re-mark and a plain expansion), this hop's slice of the classifier's adjacency."""
+        g, B, K, hops, e_cap = self.g, self.B, self.K, self.hops, self.e_cap
+        st = g.status
+        targets = self.targets
+        ev = self.evaluate
+        fused, staged, counted = s.fused, s.staged, s.counted
+        cur_prev = s.pbuf[hop % 2]
+        batch_next, d_m_next = res["union_ids"], res["union_count"]                    # main.py:236-238
+        # main.py:241-243: the columns kept are `previous` = targets + the samples of the hop before.  The targets stay
+        # marked for the whole step; the older samples are un-marked and the newer ones marked in one launch (they are
+        # disjoint); the last marks go when all_nodes is built (_classifier_graphs).  The hop's prev_bits are done with, too.
+        if hop + 1 == hops and self._rider_hook is not None:
+            # from here on the step's launches are the classifier's: a handful of workgroups each on an idle chip — the NEXT
+            # step's recorded prelude rides in them (_capture_pipeline)
+            self._rider_hook()
+        if ev:
+            # eval.py:140-142: slice_adjacency(rows = previous_nodes, cols = the new layer) — this hop's OWN expansion (still
+            # in src / dst), filtered by membership in batch_next: mark, ordered filter, un-mark (no host read)
+            ops.slice_mark(g.mult, batch_next, d_c=d_m_next)
+            ev_slice = ops.slice_filter(g.mult, s.src, s.dst, min(e_cap, (B + K) * (B + K)), d_e=s.d_e, status=st)
+            if not fused:
+                ops.slice_mark(g.mult, batch_next, unmark=True, d_c=d_m_next)
+        if fused:                 # the expansion of the next previous_nodes also clears this hop's previous-set bitmap
+            # and counts the slice survivors of its own edges against the marks made at the top of the hop
+            # (evaluation: the un-mark of the slice just taken rides here instead — this launch reads no mark)
+            s.src, s.dst, s.d_e, s.eoff = self._expand(
+                s, batch_next, d_m_next, mark=hop + 1 < hops, prev_buf=s.pbuf[(hop + 1) % 2],
+                remark=dict(mult=g.mult if ev else None, unmark=(batch_next, d_m_next) if ev else None,
+                            clear=(s.previous, s.d_m), clear_bits=cur_prev),
+                count=None if ev else (g.mult, s.bsum), stage=s.sstage,                # (the last one only feeds the slice)
+                hop_count=(s.hc, s.hbs[hop + 1]) if (counted and hop + 1 < hops) else None,
+                finish=res.get("finish"),                                              # (+ the end of this hop's draw)
+                ext=res.get("union_ext"))
+        else:
+            ops.slice_remark(g.mult, unmark=s.rm_lists["unmark"], mark=s.rm_lists["mark"], clear=(s.previous, s.d_m),
+                             clear_bits=cur_prev)
+            s.src, s.dst, s.d_e, s.eoff = self._expand(s, batch_next, d_m_next, mark=hop + 1 < hops, prev_buf=cur_prev)
+        if staged:                # outputs of the classifier's graph build (which assembles them from the stage)
+            kcap = min(e_cap, (B + K) * (B + K))
+            ksrc = torch.empty(kcap, dtype=torch.int32, device=targets.device)
+            kdst = torch.empty(kcap, dtype=torch.int32, device=targets.device)
+            kcnt = torch.empty(1, dtype=torch.int32, device=targets.device)
+            s.stages.append((s.sstage, s.d_e, e_cap))
+        elif ev:
+            ksrc, kdst, kcnt = ev_slice
+        else:
+            ksrc, kdst, kcnt = ops.slice_filter(g.mult, s.src, s.dst, min(e_cap, (B + K) * (B + K)), d_e=s.d_e, status=st,
+                                                bsum=s.bsum if fused else None)
+        s.slices.append((ksrc, kdst, kcnt))
+        s.previous, s.d_m = batch_next, d_m_next                                       # main.py:247
+
+    def _main(self, s):
+        """The step's MAIN part, given its prelude's state: everything that reads a weight."""
+        self._refresh_weights()
+        for hop in range(self.hops):                                                   # main.py:178
+            if hop:
+                self._hop_graph(s, hop)
+            self._hop_advance(s, hop, self._hop_sample(s, hop))
+        self._classifier_graphs(s)
+        self._classifier_forward(s)
+        if self.evaluate:
+            self._eval_outputs(s)
+            return
+        self._losses(s)
+        self._backward(s)
+        self._finish(s)
+
+    def _classifier_graphs(self, s):
+        """Final relabel (main.py:252-254): all_nodes = the union of the targets and the kept nodes, and the classifier's
+        per-layer graphs over it."""
+        g, N, hops = self.g, self.g.num_nodes, self.hops
+        st = g.status
+        marks = [(self.targets, None)] + [(kept, cnt) for kept, cnt in s.kept_list]        # main.py:221,252
         if len(marks) <= 4 and sum(m_[0].numel() for m_ in marks) <= 4096:     # a thousand ids: sort them in one workgroup
-            alln, counts = ops.union_sorted(marks, N, self.nall_cap, node_map=g.node_map, status=st, unmark_mult=None if ev else g.mult)
+            alln, counts = ops.union_sorted(marks, N, self.nall_cap, node_map=g.node_map, status=st,
+                                            unmark_mult=None if self.evaluate else g.mult)
         else:
             for i in range(0, len(marks), 4):
                 ops.bitmap_mark_lists(g.bits, g.bits1, marks[i:i + 4], N, status=st, unmark_mult=g.mult)
@@ -786,17 +893,22 @@ class GraphedTrainer:
                                                       status=st)
         d_na = counts[0:1]
         hid = None if self.partitioned else alln
-        if self.nall_cap <= 2048 and len(slices) <= 8:      # the per-layer subgraphs of the classifier in ONE launch
-            preps = ops.PreparedGraph.small_batch(slices, self.nall_cap, d_n=d_na, status=st, node_map=g.node_map,   # main.py:254
-                                                  head_ids=hid, counters=ctr[hops:], stages=stages if staged else None)
+        if self.nall_cap <= 2048 and len(s.slices) <= 8:      # the per-layer subgraphs of the classifier in ONE launch
+            preps = ops.PreparedGraph.small_batch(s.slices, self.nall_cap, d_n=d_na, status=st, node_map=g.node_map,   # main.py:254
+                                                  head_ids=hid, counters=self._ctr[hops:], stages=s.stages if s.staged else None)
         else:
             preps = [ops.PreparedGraph(ksrc, kdst, self.nall_cap, d_n=d_na, d_e=kcnt, status=st, src_grouped=True,
-                                       node_map=g.node_map, head_ids=hid, counters=ctr[hops + i])
-                     for i, (ksrc, kdst, kcnt) in enumerate(slices)]
+                                       node_map=g.node_map, head_ids=hid, counters=self._ctr[hops + i])
+                     for i, (ksrc, kdst, kcnt) in enumerate(s.slices)]
         layers = list(self.gcn_c.gcn_layers)
-        used = [preps[-i] for i in range(1, len(layers))] + [preps[0]]                     # gcn.py:31,35
-        first_relu = len(layers) > 1
-        first_fused = (not self.partitioned) or (len(layers) > 1 and self.F < layers[0].out_channels)
+        s.alln, s.d_na, s.preps, s.layers = alln, d_na, preps, layers
+        s.used = [preps[-i] for i in range(1, len(layers))] + [preps[0]]                   # gcn.py:31,35
+        s.first_relu = len(layers) > 1
+        s.first_fused = (not self.partitioned) or (len(layers) > 1 and self.F < layers[0].out_channels)
+
+    def _classifier_forward(self, s):
+        """The classifier over all_nodes (main.py:256-257) with its dropout."""
+        layers, used, alln, d_na = s.layers, s.used, s.alln, s.d_na
         # modules/gcn.py:33,37: F.dropout on every layer's output, the logits included, from the sampler's Philox stream (the
         # eager step's module draws the same masks: modules/gcn.py GCN.philox_dropout)
         pdrop = self.dropout
@@ -809,9 +921,9 @@ class GraphedTrainer:
             y, keep = ops.dropout_fwd(t, pdrop, philox_seed=self.seed, d_philox_offset=self.philox_off, d_n=d_na)
             keeps.append(keep)
             return y
-        x_rows = self.g.rows_from_kept(kept_halo, alln, d_na) if (halo_reuse and kept_halo is not None) else None
-        if first_fused:
-            xc, a1 = self._first_fwd(layers[0], alln, used[0], 0, ep, relu=first_relu, x_rows=x_rows)     # main.py:256-257
+        x_rows = self.g.rows_from_kept(s.kept_halo, alln, d_na) if (s.halo_reuse and s.kept_halo is not None) else None
+        if s.first_fused:
+            xc, a1 = self._first_fwd(s, layers[0], alln, used[0], 0, self.epoch_t, relu=s.first_relu, x_rows=x_rows)     # main.py:256-257
             acts = [xc, drop(a1)]
         elif x_rows is not None:
             acts = [x_rows]
@@ -820,79 +932,100 @@ class GraphedTrainer:
         for li in range(len(acts) - 1, len(layers)):
             acts.append(drop(self._conv_fwd(layers[li], acts[-1], used[li], li < len(layers) - 1)))
         for p in used:
-            agg_w[hops + next(i for i, q in enumerate(preps) if q is p)] += 1
-            agg_x[hops + next(i for i, q in enumerate(preps) if q is p)] += 1
-        logits = acts[-1]
-        if ev:
-            # eval.py:154-155: predictions = argmax(logits)[node_map.map(target_nodes)] (multi-label: the logit > 0 rows, eval.py:58)
-            # (one launch: map, row copy, argmax — rows beyond the live count of `logits` are never addressed by a target)
-            pred, rows = ops.eval_predict(logits, g.node_map, targets, status=st)
-            self.out = dict(pred=pred if self.y.dim() == 1 else (rows > 0), target_logits=rows, n_all=d_na,
-                            all_nodes=alln, logits=logits, kept=[k for k, _ in kept_list], kept_counts=[c for _, c in kept_list],
-                            sizes=dnn_list, agg_counts=ctr[:, 2], agg_weights=tuple(agg_w), agg_executed=tuple(agg_x),
-                            hop_logits=[hs["logit"] for hs in hop_state], nb_local=nbl_list, neighbor_nodes=neigh_list)
-            return
-        # ---- both losses in one launch: main.py:259-260 (+ the gradient loss_c.backward() starts from), the mean of the
-        # log-Z head (main.py:228) and the GFlowNet loss (main.py:272-282)
+            i = self.hops + next(i for i, q in enumerate(s.preps) if q is p)
+            s.agg_w[i] += 1
+            s.agg_x[i] += 1
+        s.acts, s.keeps, s.logits = acts, keeps, acts[-1]
+
+    def _eval_outputs(self, s):
+        """eval.py:154-155: predictions = argmax(logits)[node_map.map(target_nodes)] (multi-label: the logit > 0 rows, eval.py:58)
+        (one launch: map, row copy, argmax — rows beyond the live count of `logits` are never addressed by a target)."""
+        g = self.g
+        pred, rows = ops.eval_predict(s.logits, g.node_map, self.targets, status=g.status)
+        self.out = dict(pred=pred if self.y.dim() == 1 else (rows > 0), target_logits=rows, n_all=s.d_na,
+                        all_nodes=s.alln, logits=s.logits, kept=[k for k, _ in s.kept_list], kept_counts=[c for _, c in s.kept_list],
+                        sizes=s.dnn_list, agg_counts=self._ctr[:, 2], agg_weights=tuple(s.agg_w), agg_executed=tuple(s.agg_x),
+                        hop_logits=[hs["logit"] for hs in s.hop_state], nb_local=s.nbl_list, neighbor_nodes=s.neigh_list)
+
+    def _losses(self, s):
+        """Both losses in one launch: main.py:259-260 (+ the gradient loss_c.backward() starts from), the mean of the
+        log-Z head (main.py:228) and the GFlowNet loss (main.py:272-282)."""
+        rnd, logits, d_na = self.random_sampling, s.logits, s.d_na
         # main.py:260-261: + reg_param * sum of the rows' logit variances — part of loss_c and of the GFlowNet cost (main.py:274)
         reg_term = ops.logit_var_reg(logits, self.reg_param, d_n=d_na) if self.reg_param else None
-        loss_c, dl, out4 = ops.step_losses(logits, g.node_map, targets, self.y, hop_stats, self.loss_coef,
-                                           z_out=None if rnd else zstate["zout"].view(-1),
-                                           d_nz=None if rnd else zstate["d_nb"],
-                                           log_z_init=self.log_z_init, reinforce=self.reinforce, loss_extra=reg_term)
+        s.loss_c, s.dl, out4 = ops.step_losses(logits, self.g.node_map, self.targets, self.y, s.hop_stats, self.loss_coef,
+                                               z_out=None if rnd else s.zstate["zout"].view(-1),
+                                               d_nz=None if rnd else s.zstate["d_nb"],
+                                               log_z_init=self.log_z_init, reinforce=self.reinforce, loss_extra=reg_term)
         if self.reg_param:
-            ops.logit_var_reg(logits, self.reg_param, d_n=d_na, dlogits=dl)
-        loss_gfn, s, log_z, tot = out4[0], out4[1:2], out4[2], out4[3]
-        def classifier_backward():                                                         # main.py:267
-            d = dl
-            # the layers' few-row weight gradients leave their slab sums to ONE launch at the end (ops.DeferredSlabs)
-            deferred = ops.DeferredSlabs() if _sw("GRAPES_DEFER_SLABS", "1") != "0" else None
-            for i in range(len(layers) - 1, -1, -1):
-                if keeps[i] is not None:                   # d (layer i's output before dropout)
-                    d = ops.dropout_bwd(d, keeps[i], pdrop, d_n=d_na)
-                if i == 0 and first_fused:
-                    self._first_bwd(layers[0], acts[0], acts[1], d, used[0], False, relu=first_relu, defer=deferred)
-                    if self.embed:
-                        # d loss_c / d X[all_nodes] = Âᵀ((d ⊙ [act > 0]) W) = (Âᵀ(d ⊙ [act > 0])) W  (main.py:256,267 through
-                        # data.x[all_nodes]); all_nodes is duplicate-free and X.grad was zeroed above: plain row stores
-                        fl0 = self._fl[id(layers[0])]
-                        if not fl0.agg_first:
-                            raise NotImplementedError("embedding gradient through a transform-first classifier layer")
-                        t, _ = ops.gcn_aggregate_bwd(d, used[0], relu_out=acts[1] if first_relu else None, want_bias=False)
-                        dxr = ops.linear_bwd_input(t, fl0.weight, d_n=used[0].d_n)
-                        ops.scatter_rows(self.X.grad, alln, dxr, d_n=d_na, F=self.F)
-                else:
-                    d = self._conv_bwd(layers[i], acts[i], acts[i + 1], d, used[i], i < len(layers) - 1, i > 0, False,
-                                       defer=deferred)
-            if deferred is not None:
-                # one GPU, fused Adam, no padded first-layer gradient to publish: the slab sums ride in the optimiser launch
-                if (self.grad_sync is None and self._fused_adam is not False and self.opt_c is not None and
-                        not any(fl.publishes for fl in self._fl.values()) and not self.reinforce and
-                        _sw("GRAPES_ADAM_SLABS", "1") != "0"):
-                    self._pending_slabs = deferred
-                else:
-                    deferred.flush()
-        # A/B (GRAPES_BWD_FORK=1): the classifier's backward chain and the sampler / log-Z nets' backward chain depend on the
-        # losses only, not on each other — as two branches of the graph (fork after the loss launch, join before Adam)
+            ops.logit_var_reg(logits, self.reg_param, d_n=d_na, dlogits=s.dl)
+        s.loss_gfn, s.gscale, s.log_z, s.tot = out4[0], out4[1:2], out4[2], out4[3]
+
+    def _classifier_backward(self, s):                                                     # main.py:267
+        layers, acts, used, keeps, alln, d_na = s.layers, s.acts, s.used, s.keeps, s.alln, s.d_na
+        d = s.dl
+        # the layers' few-row weight gradients leave their slab sums to ONE launch at the end (ops.DeferredSlabs)
+        deferred = ops.DeferredSlabs() if _sw("GRAPES_DEFER_SLABS", "1") != "0" else None
+        for i in range(len(layers) - 1, -1, -1):
+            if keeps[i] is not None:                   # d (layer i's output before dropout)
+                d = ops.dropout_bwd(d, keeps[i], self.dropout, d_n=d_na)
+            if i == 0 and s.first_fused:
+                self._first_bwd(layers[0], acts[0], acts[1], d, used[0], False, relu=s.first_relu, defer=deferred)
+                if self.embed:
+                    # d loss_c / d X[all_nodes] = Âᵀ((d ⊙ [act > 0]) W) = (Âᵀ(d ⊙ [act > 0])) W  (main.py:256,267 through
+                    # data.x[all_nodes]); all_nodes is duplicate-free and X.grad was zeroed above: plain row stores
+                    fl0 = self._fl[id(layers[0])]
+                    if not fl0.agg_first:
+                        raise NotImplementedError("embedding gradient through a transform-first classifier layer")
+                    t, _ = ops.gcn_aggregate_bwd(d, used[0], relu_out=acts[1] if s.first_relu else None, want_bias=False)
+                    dxr = ops.linear_bwd_input(t, fl0.weight, d_n=used[0].d_n)
+                    ops.scatter_rows(self.X.grad, alln, dxr, d_n=d_na, F=self.F)
+            else:
+                d = self._conv_bwd(layers[i], acts[i], acts[i + 1], d, used[i], i < len(layers) - 1, i > 0, False,
+                                   defer=deferred)
+        if deferred is not None:
+            # one GPU, fused Adam, no padded first-layer gradient to publish: the slab sums ride in the optimiser launch
+            if (self.grad_sync is None and self._fused_adam is not False and self.opt_c is not None and
+                    not any(fl.publishes for fl in self._fl.values()) and not self.reinforce and
+                    _sw("GRAPES_ADAM_SLABS", "1") != "0"):
+                self._pending_slabs = deferred
+            else:
+                deferred.flush()
+
+    def _backward(self, s):
+        """Both backward passes (main.py:267 and main.py:287): they depend on the losses only, not on each other."""
+        rnd = self.random_sampling
+        # A/B (GRAPES_BWD_FORK=1): the classifier's backward chain and the sampler / log-Z nets' backward chain as two branches
+        # of the graph (fork after the loss launch, join before Adam)
         fork = (not rnd) and _sw("GRAPES_BWD_FORK", "0") != "0"
         if fork:
             main_s = torch.cuda.current_stream()
-            if getattr(self, "_side", None) is None:
+            if self._side is None:
                 self._side = torch.cuda.Stream()
             self._side.wait_stream(main_s)
             with torch.cuda.stream(self._side):
-                classifier_backward()
-        multi = False
-        z_done = False
-        cb_done = False
+                self._classifier_backward(s)
         # A/B (GRAPES_BWD_CARRY=0): the classifier's backward aggregations as launches of their own, after the sampler nets'
         carry_bwd = (not fork) and (not self.embed) and _sw("GRAPES_BWD_CARRY", "1") != "0"
-        if not rnd:
-            fi_, fo_ = st_gf.Kp, gf1.out_channels
-            multi = hops <= 4 and st_gf.agg_first and fi_ % 4 == 0 and fi_ % 128 != 0 and fo_ % 4 == 0
+        cb_done = (not rnd) and self._nets_backward(s, carry_bwd)
+        if fork:
+            main_s.wait_stream(self._side)
+        elif not cb_done:
+            self._classifier_backward(s)                                                   # main.py:267
+
+    def _nets_backward(self, s, carry_bwd) -> bool:
+        """Backward of the sampler net over every hop and of the log-Z net (main.py:287).  carry_bwd: the classifier's backward
+        runs inside the heads' two launches when that form applies.  -> whether it did."""
+        hops, num_ind, ep = self.hops, self.num_ind, self.epoch_t
+        gf1, gf2, st_gf, z1, z2, st_z = self._nets()
+        hop_state, zstate, gscale = s.hop_state, s.zstate, s.gscale
+        z_done = False
+        cb_done = False
+        fi_, fo_ = st_gf.Kp, gf1.out_channels
+        multi = hops <= 4 and st_gf.agg_first and fi_ % 4 == 0 and fi_ % 128 != 0 and fo_ % 4 == 0
         # the heads' part of the backward pass for every hop (and the log-Z head) in two launches also when the layers' own
         # weight gradients stay per hop (transform-first layers: Reddit) — instead of zero fill + d logits + aggregation per hop
-        heads = multi or ((not rnd) and hops <= 4 and all(hs.get("cand_pos") is not None for hs in hop_state) and
+        heads = multi or (hops <= 4 and all(hs.get("cand_pos") is not None for hs in hop_state) and
                           _sw("GRAPES_HEAD_BWD_MULTI", "1") != "0")
         dh2s, z_dh2 = None, None
         if heads:
@@ -906,17 +1039,16 @@ class GraphedTrainer:
                                          [hs["mask"] for hs in hop_state] + [None for _ in zs],
                                          [hs["cand_pos"] for hs in hop_state] + [None for _ in zs],
                                          [hs["prep"] for hs in hop_state] + [z["prep"] for z in zs],
-                                         d_grad_scale=s, sum_out=gf2.bias.grad, accumulate_sum=False,
+                                         d_grad_scale=gscale, sum_out=gf2.bias.grad, accumulate_sum=False,
                                          mean_sum_out=z2.bias.grad if z_rides else None)
             if carry_bwd:
                 # main.py:267 and main.py:287 depend on the losses only: the classifier's few-row backward aggregations ride as
                 # extra workgroups of these two launches (ops.carry_backward_aggregations), its GEMMs run between them
-                end_riders = getattr(self, "_rider_end_hook", None)
-                if end_riders is not None:
-                    end_riders()          # (the next step's prelude has been carried by the classifier's forward: detach it)
+                if self._rider_end_hook is not None:
+                    self._rider_end_hook()    # (the next step's prelude has been carried by the classifier's forward: detach it)
                 ops.carry_backward_aggregations([lambda: hb.launch(1), lambda: hb.launch(2)])
                 try:
-                    classifier_backward()
+                    self._classifier_backward(s)
                 finally:
                     ops.flush_backward_hosts()
                 cb_done = True
@@ -951,7 +1083,7 @@ class GraphedTrainer:
         dh_r1s, z_r1 = [None] * len(hop_state), None
         if (dh2s is not None and not multi and _sw("GRAPES_R1_MULTI", "1") != "0" and
                 all(self._r1_ok(gf1, hs["act1"]) for hs in hop_state)):
-            z_in = (z_dh2 is not None and not (self.reinforce or rnd or z_done) and self._r1_ok(z1, zstate["act"]) and
+            z_in = (z_dh2 is not None and not (self.reinforce or z_done) and self._r1_ok(z1, zstate["act"]) and
                     zstate["act"].shape[1] == hop_state[0]["act1"].shape[1])
             probs = [dict(act=hs["act1"], dh2=dh2s[h].view(-1), w2=gf2.lin.weight.view(-1), prep=hs["prep"],
                           gate_bits=hs["act1"]._gate_bits, dw_head=gf2.lin.weight.grad.view(-1), dbias=gf1.bias.grad, accumulate=h > 0)
@@ -966,7 +1098,7 @@ class GraphedTrainer:
                 z_r1 = outs[len(hop_state)] if z_in else None
         # ... and the weight-gradient GEMMs that follow them (the sampler net's per hop, the log-Z net's) as ONE launch + one slab
         # sum: the slab budget dealt out by the live rows instead of 768 workgroups' worth per launch (A/B: GRAPES_DW_MULTI=0)
-        dw_batch = [] if (all(d is not None for d in dh_r1s) and dh_r1s and self._fl[id(gf1)].split and
+        dw_batch = [] if (all(d is not None for d in dh_r1s) and dh_r1s and st_gf.split and
                           _sw("GRAPES_DW_MULTI", "1") != "0") else None
         for h, hs in enumerate(hop_state if not multi else []):
             acc = h > 0                           # hop 0 writes the .grad buffers; later hops accumulate
@@ -975,18 +1107,18 @@ class GraphedTrainer:
                                num_ind=num_ind, ep=ep, hop=h, dh_r1=dh_r1s[h], dw_batch=dw_batch)
                 continue
             dlog = torch.zeros_like(hs["logit"])
-            ops.bernoulli_logprob_bwd(hs["logit"].view(-1), hs["mask"], d_grad_scale=s, logit_index=hs["nbl"],
+            ops.bernoulli_logprob_bwd(hs["logit"].view(-1), hs["mask"], d_grad_scale=gscale, logit_index=hs["nbl"],
                                       out=dlog.view(-1), d_n=hs["d_nn"], accumulate_sum=acc,
                                       sum_out=gf2.bias.grad)                                # db2 = sum(dlog)
             self._head_bwd(gf1, gf2, hs["x"], hs["act1"], dlog, hs["prep"], acc, db2_done=True, num_ind=num_ind, ep=ep, hop=h)
-        if self.reinforce or rnd or z_done:
-            pass                                          # (reinforce: the log-Z net takes no part, its gradients are zeroed below)
+        if self.reinforce or z_done:
+            pass                                          # (reinforce: the log-Z net takes no part, its gradients are zeroed in _finish)
         elif z_dh2 is not None:                 # d mean / d pred_z and its aggregation came with the hops' (above)
             self._head_bwd(z1, z2, zstate["x"], zstate["act"], None, zstate["prep"], False, db2_done=True, dh2=z_dh2, dh_r1=z_r1,
-                           dw_batch=dw_batch if (z_r1 is not None and self._fl[id(z1)].split) else None)
+                           dw_batch=dw_batch if (z_r1 is not None and st_z.split) else None)
         else:
             dz = torch.empty_like(zstate["zout"].reshape(-1, 1))          # (the activations may be kept as gate bits only)
-            ops.fill(dz.view(-1), d_n=zstate["d_nb"], d_value=s, scale_by_inv_n=1.0,       # d mean / d pred_z
+            ops.fill(dz.view(-1), d_n=zstate["d_nb"], d_value=gscale, scale_by_inv_n=1.0,  # d mean / d pred_z
                      sum_out=z2.bias.grad)
             self._head_bwd(z1, z2, zstate["x"], zstate["act"], dz, zstate["prep"], False, db2_done=True)
         if dw_batch:
@@ -997,10 +1129,11 @@ class GraphedTrainer:
                     ops.linear_bwd_weight_gathered(q["dh"], self.Xp, self.F, q["ids"], q["dw"], q["ind_code"], 0, q["num_ind"],
                                                    d_epoch=q["ep"], d_n=q["d_n"], accumulate=q["accumulate"], split=q["split"],
                                                    ind_mask=q["ind_mask"])
-        if fork:
-            main_s.wait_stream(self._side)
-        elif not cb_done:
-            classifier_backward()                                                          # main.py:267
+        return cb_done
+
+    def _finish(self, s):
+        """The gradients published and synchronised, both Adam updates (main.py:268,289), the step's `out`."""
+        rnd = self.random_sampling
         for fl in self._fl.values():
             fl.publish_grad()
         if self.reinforce and not rnd:
@@ -1010,14 +1143,14 @@ class GraphedTrainer:
             self.grad_sync([p for m in self._models for p in m.parameters()])
         self._optim_step()                                                                 # main.py:268,289
         # (random_sampling: main.py:272 skips the GFlowNet loss, batch_loss_gfn stays 0 and log_z stays at its initial 0)
-        self.out = dict(loss_c=loss_c.detach(), loss_gfn=None if rnd else loss_gfn.detach().reshape(()),
-                        log_z=None if rnd else log_z.reshape(()),
-                        tot_log_prob=tot, agg_counts=ctr[:, 2], agg_weights=tuple(agg_w), agg_executed=tuple(agg_x),
-                        n_all=d_na, kept=[k for k, _ in kept_list], kept_counts=[c for _, c in kept_list],
-                        all_nodes=alln, logits=logits, sizes=dnn_list,
-                        batch_counts=dnb_list, classifier_layers=len(layers),
-                        hop_logits=[hs["logit"] for hs in hop_state], nb_local=nbl_list,
-                        neighbor_nodes=neigh_list, hop_stats=hop_stats)
+        self.out = dict(loss_c=s.loss_c.detach(), loss_gfn=None if rnd else s.loss_gfn.detach().reshape(()),
+                        log_z=None if rnd else s.log_z.reshape(()),
+                        tot_log_prob=s.tot, agg_counts=self._ctr[:, 2], agg_weights=tuple(s.agg_w), agg_executed=tuple(s.agg_x),
+                        n_all=s.d_na, kept=[k for k, _ in s.kept_list], kept_counts=[c for _, c in s.kept_list],
+                        all_nodes=s.alln, logits=s.logits, sizes=s.dnn_list,
+                        batch_counts=s.dnb_list, classifier_layers=len(s.layers),
+                        hop_logits=[hs["logit"] for hs in s.hop_state], nb_local=s.nbl_list,
+                        neighbor_nodes=s.neigh_list, hop_stats=s.hop_stats)
 
     # ------------------------------------------------------------------ public
     def attach_loader(self, train_ids: torch.Tensor, stride: int = 1, offset: int = 0, epochs: bool = False):
@@ -1091,7 +1224,7 @@ class GraphedTrainer:
     # collectives stay host-issued, but the LAST segment of step t and the FIRST segment of step t + 1 have nothing between them —
     # they go out as one hipGraphLaunch (a two-segment chain), one launch boundary per step less.
     def _boundary_ready(self) -> bool:
-        if self._sets is None or self._sets[0].G is None or not self._primed or getattr(self, "_chains_off", False):
+        if self._sets is None or self._sets[0].G is None or not self._primed or self._chains_off:
             return False
         for st in self._sets:
             it = st.G.items
@@ -1155,7 +1288,7 @@ class GraphedTrainer:
 
     def _chain_ready(self, n: int) -> int:
         """Steps (0: none) the next chain launch may cover: the step is captured, primed and free of collectives."""
-        if n < 2 or self.partitioned or self.grad_sync is not None or getattr(self, "_chains_off", False):
+        if n < 2 or self.partitioned or self.grad_sync is not None or self._chains_off:
             return 0
         if self._sets is not None:
             if self._sets[0].G is None or not self._primed:
@@ -1258,24 +1391,24 @@ class GraphedTrainer:
         torch.cuda.synchronize()
         for st in self._sets:
             self._activate(st)
-            st.gen = self._step_gen()
             ops._lib.check(lib.grapes_rider_record_begin(), "rider_record_begin")
             ops.rider_keep(True)
             # every allocation made while recording stays reserved for the trainer's lifetime: the recorded launches are
             # baked into the OTHER set's hipGraph with raw pointers; a block that returned to the caching allocator could be handed to
-            # someone else and every replay would write into it.  (The locals' snapshot below keeps the tensors too: belt and braces.)
-            if getattr(self, "_rec_pool", None) is None:
+            # someone else and every replay would write into it.  The pool is NOT what owns them, though — both sets record into it,
+            # so a block set 0 let go of could be handed out while set 1 records: st.state, referenced for the trainer's lifetime, is
+            # the owner of every buffer of the recorded prelude (and st.scratch of the wrappers' workspaces).
+            if self._rec_pool is None:
                 self._rec_pool = torch.cuda.MemPool() if hasattr(torch.cuda, "MemPool") else None
             pool_ctx = torch.cuda.use_mem_pool(self._rec_pool) if self._rec_pool is not None else contextlib.nullcontext()
             try:
                 with pool_ctx:
-                    next(st.gen)               # allocates the prelude's buffers, launches nothing
+                    st.state = self._prelude()     # allocates the prelude's buffers, launches nothing
             finally:
                 st.program = int(lib.grapes_rider_record_end())
                 st.scratch = ops.rider_keep(False)      # (the wrappers' workspaces: the recorded launches use them every step)
             if st.program < 0:
                 raise ops._lib.GrapesHipError("rider recording failed")
-            st.handoff = dict(st.gen.gi_frame.f_locals)
         pool = torch.cuda.graph_pool_handle()
         for st, other in ((self._sets[0], self._sets[1]), (self._sets[1], self._sets[0])):
             self._activate(st)
@@ -1290,7 +1423,7 @@ class GraphedTrainer:
                 ops._lib.check(lib.grapes_rider_attach(other.program, 1, ops._stream()), "rider_attach")
                 released = []
 
-                def hook():           # ... the rest from the last expansion on (called by _step_gen in front of it)
+                def hook():           # ... the rest from the last expansion on (called by _hop_advance in front of it)
                     ops._lib.check(lib.grapes_rider_release(ops._stream()), "rider_release")
                     released.append(True)
                 self._rider_hook = hook
@@ -1304,10 +1437,10 @@ class GraphedTrainer:
                     paired = C.c_int32(0)
                     alone = lib.grapes_rider_detach(ops._stream(), C.byref(paired))
                     ended.append((int(paired.value), int(alone)))
-                self._rider_end_hook = end        # (called by _step_gen once the classifier's forward is through, if it needs the riders)
+                self._rider_end_hook = end        # (called by _nets_backward once the classifier's forward is through, if it needs the riders)
                 try:
-                    for _ in st.gen:
-                        pass
+                    # (on a copy: the later hops replace the per-hop fields, and st.state goes on holding all the prelude left)
+                    self._main(copy.copy(st.state))
                 finally:
                     self._rider_hook = None
                     self._rider_end_hook = None
@@ -1317,7 +1450,6 @@ class GraphedTrainer:
                 st.riders = ended[0]              # launches of the other set's prelude that rode / ran on their own
             st.G.record(body)
             st.out = self.out
-            st.gen = None
         self.graph_obj = self._sets[0].G
         self._primed = False
 
