@@ -15,6 +15,8 @@
     } while (0)
 
 static inline int grapes_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+static inline bool grapes_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+static inline size_t grapes_round16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 // A/B and tuning switches (GRAPES_* environment variables: forms that lost their measurement, grid sizes, thresholds) exist in the
 // DIAGNOSTIC build only (make diag -> libgrapes_hip_diag.so, -DGRAPES_DIAG; profiles/ and the tests that compare forms use it).

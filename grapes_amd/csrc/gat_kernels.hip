@@ -20,60 +20,13 @@
 // two scores and row_ms, which is what lets each of them walk its own CSR without an edge permutation between the two orders.
 // No floating-point atomics: every sum has a fixed order (butterflies inside a group, chunk order across work items, a fixed
 // tree across partials), so results are bit-identical from run to run.  No kernel waits on another workgroup.
-#include "common.h"
+#include "row_gather.h"
 
 #define GAT_SLOPE 0.2f
 #define GAT_PARAM_BLOCKS 512
 
 __device__ __forceinline__ float gat_leaky(float x) { return x > 0.f ? x : GAT_SLOPE * x; }
 
-template <int LPR>
-__device__ __forceinline__ float grp_sum(float v) {
-#pragma unroll
-    for (int d = LPR / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, LPR);
-    return v;
-}
-template <int LPR>
-__device__ __forceinline__ float grp_max(float v) {
-#pragma unroll
-    for (int d = LPR / 2; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, LPR));
-    return v;
-}
-
-// lane l of a group holds columns (s LPR + l) VEC ... + VEC of a row, s < NS; columns at or beyond F read as zero
-template <int VEC, int LPR, int NS>
-__device__ __forceinline__ void gat_load_row(const float* __restrict__ base, long long row, int F, int l, float (&r)[NS][VEC]) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int f = (s * LPR + l) * VEC;
-        if (f < F) {
-            if (VEC == 4) {
-                const float4 t = *reinterpret_cast<const float4*>(base + row * F + f);
-                r[s][0] = t.x; r[s][VEC > 1 ? 1 : 0] = t.y; r[s][VEC > 2 ? 2 : 0] = t.z; r[s][VEC > 3 ? 3 : 0] = t.w;
-            } else {
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) r[s][v] = base[row * F + f + v];
-            }
-        } else {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) r[s][v] = 0.f;
-        }
-    }
-}
-template <int VEC, int LPR, int NS>
-__device__ __forceinline__ void gat_store_row(float* __restrict__ base, long long row, int F, int l, const float (&r)[NS][VEC]) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int f = (s * LPR + l) * VEC;
-        if (f < F) {
-            if (VEC == 4) *reinterpret_cast<float4*>(base + row * F + f) = make_float4(r[s][0], r[s][VEC > 1 ? 1 : 0], r[s][VEC > 2 ? 2 : 0], r[s][VEC > 3 ? 3 : 0]);
-            else {
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) base[row * F + f + v] = r[s][v];
-            }
-        }
-    }
-}
 template <int VEC, int NS>
 __device__ __forceinline__ float gat_dot(const float (&a)[NS][VEC], const float (&b)[NS][VEC]) {
     float d = 0.f;
@@ -90,11 +43,10 @@ __device__ __forceinline__ bool gat_entry(const int32_t* __restrict__ csr, int t
                                           int32_t* status) {
     idx = row;
     if (t >= end) return false;
-    if (t >= beg) {
-        const int c = csr[t];
-        if ((unsigned)c >= (unsigned)n) { if (status) atomicOr(status, GRAPES_STATUS_BAD_INDEX); return false; }
-        idx = c;
-    }
+    if (t < beg) return true;
+    const int c = batch_entry(csr, t, end, n, status);
+    if (c < 0) return false;
+    idx = c;
     return true;
 }
 
@@ -128,7 +80,7 @@ __device__ __forceinline__ void gat_fwd_range(const float* __restrict__ h, const
             for (int u = 0; u < U; ++u) {
                 const int ik = __shfl(idx, k + u, LPR);
                 pk[u] = __shfl(p, k + u, LPR);
-                gat_load_row<VEC, LPR, NS>(h, ik, F, l, hv[u]);
+                row_load<VEC, LPR, NS>(h, ik, F, l, hv[u]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -167,7 +119,7 @@ __global__ __launch_bounds__(256) void gat_fwd_k(const float* __restrict__ h, co
                 if (bias && f < F) r += bias[f];
                 acc[s][v] = relu ? fmaxf(r, 0.f) : r;
             }
-        gat_store_row<VEC, LPR, NS>(out, row, F, l, acc);
+        row_store<VEC, LPR, NS>(out, row, F, l, acc);
         if (l == 0) { row_ms[2 * (long long)row] = m; row_ms[2 * (long long)row + 1] = logf(sum); }
     }
 }
@@ -181,22 +133,20 @@ __global__ __launch_bounds__(256) void gat_fwd_chunks_k(const float* __restrict_
                                                         int item_cap, float* __restrict__ pacc, float* __restrict__ pms,
                                                         int32_t* status) {
     const int n = eff_count(d_n, n_host);
-    int n_items = *d_n_items; if (n_items > item_cap) n_items = item_cap;
+    const int n_items = item_count(d_n_items, item_cap);
     const int l = threadIdx.x % LPR, G = 256 / LPR;
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
-        const int row = items[2 * it], chunk = items[2 * it + 1];
+        int row, beg, end;
         float m = -INFINITY, sum = 0.f, acc[NS][VEC];
 #pragma unroll
         for (int s = 0; s < NS; ++s)
 #pragma unroll
             for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
-        if ((unsigned)row < (unsigned)n) {
-            const int rend = rowptr[row + 1];
-            const int beg = rowptr[row] + chunk * GRAPES_LONG_ROW;
-            const int end = beg + GRAPES_LONG_ROW < rend ? beg + GRAPES_LONG_ROW : rend;
+        item_range(items, it, rowptr, n, row, beg, end);
+        if (beg < end) {
             gat_fwd_range<VEC, LPR, NS>(h, s_src, csr, row, n, s_dst[row], beg, end, false, F, l, m, sum, acc, status);
         }
-        gat_store_row<VEC, LPR, NS>(pacc, it, F, l, acc);
+        row_store<VEC, LPR, NS>(pacc, it, F, l, acc);
         if (l == 0) { pms[2 * (long long)it] = m; pms[2 * (long long)it + 1] = sum; }
     }
 }
@@ -213,15 +163,11 @@ __global__ __launch_bounds__(256) void gat_fwd_combine_k(const float* __restrict
                                                          const float* __restrict__ pms) {
     __shared__ float red[4], part[4][64], total;
     const int n = eff_count(d_n, n_host);
-    int n_items = *d_n_items; if (n_items > item_cap) n_items = item_cap;
+    const int n_items = item_count(d_n_items, item_cap);
     const int g = threadIdx.x >> 6, l = threadIdx.x & 63;
     for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
-        if (items[2 * it + 1] != 0) continue;
-        const int row = items[2 * it];
-        if ((unsigned)row >= (unsigned)n) continue;
-        const int len = rowptr[row + 1] - rowptr[row];
-        int nc = (len + GRAPES_LONG_ROW - 1) / GRAPES_LONG_ROW;
-        if (it + nc > n_items) nc = n_items - it;
+        int row, nc;
+        if (!item_leads(items, it, n_items, rowptr, n, row, nc)) continue;
         const float e_self = gat_leaky(s_src[row] + s_dst[row]);
         float mx = e_self;
         for (int c = threadIdx.x; c < nc; c += 256) mx = fmaxf(mx, pms[2 * (long long)(it + c)]);
@@ -268,11 +214,11 @@ __global__ __launch_bounds__(256) void gat_scores_k(const float* __restrict__ h,
     const int n = eff_count(d_n, n_host);
     const int l = threadIdx.x % LPR, G = 256 / LPR;
     float as[NS][VEC], ad[NS][VEC];
-    gat_load_row<VEC, LPR, NS>(a_src, 0, F, l, as);
-    gat_load_row<VEC, LPR, NS>(a_dst, 0, F, l, ad);
+    row_load<VEC, LPR, NS>(a_src, 0, F, l, as);
+    row_load<VEC, LPR, NS>(a_dst, 0, F, l, ad);
     for (int row = blockIdx.x * G + threadIdx.x / LPR; row < n; row += gridDim.x * G) {
         float hv[NS][VEC];
-        gat_load_row<VEC, LPR, NS>(h, row, F, l, hv);
+        row_load<VEC, LPR, NS>(h, row, F, l, hv);
         const float ss = grp_sum<LPR>(gat_dot<VEC, NS>(hv, as)), sd = grp_sum<LPR>(gat_dot<VEC, NS>(hv, ad));
         if (l == 0) { s_src[row] = ss; s_dst[row] = sd; }
     }
@@ -289,7 +235,7 @@ __global__ __launch_bounds__(256) void gat_bwd_rows_k(const float* __restrict__ 
     const int n = eff_count(d_n, n_host);
     const int l = threadIdx.x % LPR, G = 256 / LPR;
     float bv[NS][VEC];
-    if (bias) gat_load_row<VEC, LPR, NS>(bias, 0, F, l, bv);
+    if (bias) row_load<VEC, LPR, NS>(bias, 0, F, l, bv);
     else {
 #pragma unroll
         for (int s = 0; s < NS; ++s)
@@ -298,8 +244,8 @@ __global__ __launch_bounds__(256) void gat_bwd_rows_k(const float* __restrict__ 
     }
     for (int row = blockIdx.x * G + threadIdx.x / LPR; row < n; row += gridDim.x * G) {
         float g[NS][VEC], o[NS][VEC];
-        gat_load_row<VEC, LPR, NS>(dout, row, F, l, g);
-        gat_load_row<VEC, LPR, NS>(out, row, F, l, o);
+        row_load<VEC, LPR, NS>(dout, row, F, l, g);
+        row_load<VEC, LPR, NS>(out, row, F, l, o);
         float c = 0.f;
 #pragma unroll
         for (int s = 0; s < NS; ++s)
@@ -309,7 +255,7 @@ __global__ __launch_bounds__(256) void gat_bwd_rows_k(const float* __restrict__ 
                 c = fmaf(g[s][v], o[s][v] - bv[s][v], c);
             }
         c = grp_sum<LPR>(c);
-        if (relu) gat_store_row<VEC, LPR, NS>(gbuf, row, F, l, g);
+        if (relu) row_store<VEC, LPR, NS>(gbuf, row, F, l, g);
         if (l == 0) row_q[row] = make_float4(s_dst[row], row_ms[2 * (long long)row], row_ms[2 * (long long)row + 1], c);
     }
 }
@@ -331,7 +277,7 @@ __device__ __forceinline__ float gat_bwd_dst_range(const float* __restrict__ h, 
         for (int k = 0; k < cnt; k += U) {
             float hv[U][NS][VEC], d[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) gat_load_row<VEC, LPR, NS>(h, __shfl(idx, k + u, LPR), F, l, hv[u]);
+            for (int u = 0; u < U; ++u) row_load<VEC, LPR, NS>(h, __shfl(idx, k + u, LPR), F, l, hv[u]);
 #pragma unroll
             for (int u = 0; u < U; ++u) d[u] = gat_dot<VEC, NS>(g, hv[u]);
 #pragma unroll
@@ -359,7 +305,7 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_k(const float* __restrict__ h
         int end = rowptr[row + 1];
         if (skip_long && end - beg > GRAPES_LONG_ROW) end = beg;
         float g[NS][VEC];
-        gat_load_row<VEC, LPR, NS>(gmat, row, F, l, g);
+        row_load<VEC, LPR, NS>(gmat, row, F, l, g);
         const float ds = grp_sum<LPR>(gat_bwd_dst_range<VEC, LPR, NS>(h, s_src, csr, row, n, row_q[row], g, beg, end, true, F, l, status));
         if (l == 0) ds_dst[row] = ds;
     }
@@ -372,17 +318,15 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_chunks_k(const float* __restr
                                                             const int32_t* __restrict__ items, const int32_t* __restrict__ d_n_items,
                                                             int item_cap, float* __restrict__ pds, int32_t* status) {
     const int n = eff_count(d_n, n_host);
-    int n_items = *d_n_items; if (n_items > item_cap) n_items = item_cap;
+    const int n_items = item_count(d_n_items, item_cap);
     const int l = threadIdx.x % LPR, G = 256 / LPR;
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
-        const int row = items[2 * it], chunk = items[2 * it + 1];
+        int row, beg, end;
         float ds = 0.f;
-        if ((unsigned)row < (unsigned)n) {
-            const int rend = rowptr[row + 1];
-            const int beg = rowptr[row] + chunk * GRAPES_LONG_ROW;
-            const int end = beg + GRAPES_LONG_ROW < rend ? beg + GRAPES_LONG_ROW : rend;
+        item_range(items, it, rowptr, n, row, beg, end);
+        if (beg < end) {
             float g[NS][VEC];
-            gat_load_row<VEC, LPR, NS>(gmat, row, F, l, g);
+            row_load<VEC, LPR, NS>(gmat, row, F, l, g);
             ds = grp_sum<LPR>(gat_bwd_dst_range<VEC, LPR, NS>(h, s_src, csr, row, n, row_q[row], g, beg, end, false, F, l, status));
         }
         if (l == 0) pds[it] = ds;
@@ -394,13 +338,10 @@ __global__ __launch_bounds__(256) void gat_bwd_dst_combine_k(const int32_t* __re
                                                              const int32_t* __restrict__ d_n_items, int item_cap,
                                                              const float* __restrict__ pds) {
     const int n = eff_count(d_n, n_host);
-    int n_items = *d_n_items; if (n_items > item_cap) n_items = item_cap;
+    const int n_items = item_count(d_n_items, item_cap);
     for (int it = blockIdx.x * 256 + threadIdx.x; it < n_items; it += gridDim.x * 256) {
-        if (items[2 * it + 1] != 0) continue;
-        const int row = items[2 * it];
-        if ((unsigned)row >= (unsigned)n) continue;
-        int nc = (rowptr[row + 1] - rowptr[row] + GRAPES_LONG_ROW - 1) / GRAPES_LONG_ROW;
-        if (it + nc > n_items) nc = n_items - it;
+        int row, nc;
+        if (!item_leads(items, it, n_items, rowptr, n, row, nc)) continue;
         float ds = ds_dst[row];
         for (int c = 0; c < nc; ++c) ds += pds[it + c];
         ds_dst[row] = ds;
@@ -429,7 +370,7 @@ __device__ __forceinline__ float gat_bwd_src_range(const float* __restrict__ gma
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 ak[u] = __shfl(alpha, k + u, LPR);
-                gat_load_row<VEC, LPR, NS>(gmat, __shfl(idx, k + u, LPR), F, l, gv[u]);
+                row_load<VEC, LPR, NS>(gmat, __shfl(idx, k + u, LPR), F, l, gv[u]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -455,8 +396,8 @@ template <int VEC, int LPR, int NS>
 __device__ __forceinline__ void gat_bwd_src_epilogue(float (&acc)[NS][VEC], float dss, float dsd, const float* __restrict__ a_src,
                                                      const float* __restrict__ a_dst, int F, int l) {
     float as[NS][VEC], ad[NS][VEC];
-    gat_load_row<VEC, LPR, NS>(a_src, 0, F, l, as);
-    gat_load_row<VEC, LPR, NS>(a_dst, 0, F, l, ad);
+    row_load<VEC, LPR, NS>(a_src, 0, F, l, as);
+    row_load<VEC, LPR, NS>(a_dst, 0, F, l, ad);
 #pragma unroll
     for (int s = 0; s < NS; ++s)
 #pragma unroll
@@ -480,14 +421,14 @@ __global__ __launch_bounds__(256) void gat_bwd_src_k(const float* __restrict__ h
         const bool is_long = skip_long && end - beg > GRAPES_LONG_ROW;
         if (is_long) end = beg;
         float hreg[NS][VEC], acc[NS][VEC];
-        gat_load_row<VEC, LPR, NS>(h, row, F, l, hreg);
+        row_load<VEC, LPR, NS>(h, row, F, l, hreg);
 #pragma unroll
         for (int s = 0; s < NS; ++s)
 #pragma unroll
             for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
         const float ds = grp_sum<LPR>(gat_bwd_src_range<VEC, LPR, NS>(gmat, row_q, csr, row, n, s_src[row], hreg, beg, end, true, F, l, acc, status));
         if (!is_long) gat_bwd_src_epilogue<VEC, LPR, NS>(acc, ds, ds_dst[row], a_src, a_dst, F, l);
-        gat_store_row<VEC, LPR, NS>(dh, row, F, l, acc);
+        row_store<VEC, LPR, NS>(dh, row, F, l, acc);
         if (l == 0) ds_src[row] = ds;
     }
 }
@@ -500,24 +441,22 @@ __global__ __launch_bounds__(256) void gat_bwd_src_chunks_k(const float* __restr
                                                             int item_cap, float* __restrict__ pacc, float* __restrict__ pds,
                                                             int32_t* status) {
     const int n = eff_count(d_n, n_host);
-    int n_items = *d_n_items; if (n_items > item_cap) n_items = item_cap;
+    const int n_items = item_count(d_n_items, item_cap);
     const int l = threadIdx.x % LPR, G = 256 / LPR;
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
-        const int row = items[2 * it], chunk = items[2 * it + 1];
+        int row, beg, end;
         float ds = 0.f, acc[NS][VEC];
 #pragma unroll
         for (int s = 0; s < NS; ++s)
 #pragma unroll
             for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
-        if ((unsigned)row < (unsigned)n) {
-            const int rend = rowptr[row + 1];
-            const int beg = rowptr[row] + chunk * GRAPES_LONG_ROW;
-            const int end = beg + GRAPES_LONG_ROW < rend ? beg + GRAPES_LONG_ROW : rend;
+        item_range(items, it, rowptr, n, row, beg, end);
+        if (beg < end) {
             float hreg[NS][VEC];
-            gat_load_row<VEC, LPR, NS>(h, row, F, l, hreg);
+            row_load<VEC, LPR, NS>(h, row, F, l, hreg);
             ds = grp_sum<LPR>(gat_bwd_src_range<VEC, LPR, NS>(gmat, row_q, csr, row, n, s_src[row], hreg, beg, end, false, F, l, acc, status));
         }
-        gat_store_row<VEC, LPR, NS>(pacc, it, F, l, acc);
+        row_store<VEC, LPR, NS>(pacc, it, F, l, acc);
         if (l == 0) pds[it] = ds;
     }
 }
@@ -530,13 +469,10 @@ __global__ __launch_bounds__(256) void gat_bwd_src_combine_k(const int32_t* __re
                                                              const int32_t* __restrict__ d_n_items, int item_cap,
                                                              const float* __restrict__ pacc, const float* __restrict__ pds) {
     const int n = eff_count(d_n, n_host);
-    int n_items = *d_n_items; if (n_items > item_cap) n_items = item_cap;
+    const int n_items = item_count(d_n_items, item_cap);
     for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
-        if (items[2 * it + 1] != 0) continue;
-        const int row = items[2 * it];
-        if ((unsigned)row >= (unsigned)n) continue;
-        int nc = (rowptr[row + 1] - rowptr[row] + GRAPES_LONG_ROW - 1) / GRAPES_LONG_ROW;
-        if (it + nc > n_items) nc = n_items - it;
+        int row, nc;
+        if (!item_leads(items, it, n_items, rowptr, n, row, nc)) continue;
         float ds = ds_src[row];                                   // (every thread: the same sum in the same order)
         for (int c = 0; c < nc; ++c) ds += pds[it + c];
         const float dsd = ds_dst[row];
@@ -603,28 +539,6 @@ __global__ __launch_bounds__(256) void gat_bwd_params_final_k(const float* __res
 
 // ------------------------------------------------------------------------------------------------------------ host side
 
-static inline bool gat_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-static inline size_t gat_round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-// lanes per row and slabs per lane by width: float4 columns (f % 4 == 0, 16-byte aligned rows) up to 1024, scalar ones up to 256
-#define GAT_LAUNCH(KERNEL, vec, f, grid32, grid64, s, ...)                                                                  \
-    do {                                                                                                                    \
-        if (vec) {                                                                                                          \
-            if ((f) <= 128) hipLaunchKernelGGL((KERNEL<4, 32, 1>), dim3(grid32), dim3(256), 0, s, __VA_ARGS__);              \
-            else if ((f) <= 256) hipLaunchKernelGGL((KERNEL<4, 64, 1>), dim3(grid64), dim3(256), 0, s, __VA_ARGS__);         \
-            else hipLaunchKernelGGL((KERNEL<4, 64, 4>), dim3(grid64), dim3(256), 0, s, __VA_ARGS__);                         \
-        } else {                                                                                                            \
-            if ((f) <= 32) hipLaunchKernelGGL((KERNEL<1, 32, 1>), dim3(grid32), dim3(256), 0, s, __VA_ARGS__);               \
-            else if ((f) <= 64) hipLaunchKernelGGL((KERNEL<1, 64, 1>), dim3(grid64), dim3(256), 0, s, __VA_ARGS__);          \
-            else hipLaunchKernelGGL((KERNEL<1, 64, 4>), dim3(grid64), dim3(256), 0, s, __VA_ARGS__);                         \
-        }                                                                                                                   \
-        GRAPES_LAUNCH_CHECK();                                                                                              \
-    } while (0)
-
-static inline int gat_grid(int rows, int lanes) {
-    int g = grapes_div_up(rows > 0 ? rows : 1, 256 / lanes);
-    return g > 16384 ? 16384 : g;
-}
 // 0: float4 columns, 1: scalar columns, negative: not covered
 static inline int gat_shape(int f, bool aligned) {
     if (f < 1) return GRAPES_EINVAL;
@@ -636,18 +550,18 @@ static inline int gat_shape(int f, bool aligned) {
 extern "C" int grapes_gat_scores(const float* h, const float* a_src, const float* a_dst, float* s_src, float* s_dst, int32_t n,
                                  const int32_t* d_n, int32_t f, grapes_stream_t stream) {
     if (!h || !a_src || !a_dst || !s_src || !s_dst || n < 0) return GRAPES_EINVAL;
-    const int shape = gat_shape(f, gat_aligned16(h) && gat_aligned16(a_src) && gat_aligned16(a_dst));
+    const int shape = gat_shape(f, grapes_aligned16(h) && grapes_aligned16(a_src) && grapes_aligned16(a_dst));
     if (shape < 0) return shape;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const bool vec = shape == 0;
-    GAT_LAUNCH(gat_scores_k, vec, f, gat_grid(n, 32), gat_grid(n, 64), s, h, a_src, a_dst, s_src, s_dst, n, d_n, f);
+    ROW_LAUNCH(gat_scores_k, 4, vec, f, n, s, h, a_src, a_dst, s_src, s_dst, n, d_n, f);
     return 0;
 }
 
 extern "C" size_t grapes_gat_aggregate_workspace_bytes(int32_t item_cap, int32_t f) {
     const size_t items = item_cap > 0 ? (size_t)item_cap : 0;
-    return gat_round16(items * (size_t)(f > 0 ? f : 1) * sizeof(float)) + gat_round16(items * 2 * sizeof(float)) + 16;
+    return grapes_round16(items * (size_t)(f > 0 ? f : 1) * sizeof(float)) + grapes_round16(items * 2 * sizeof(float)) + 16;
 }
 
 extern "C" int grapes_gat_aggregate_fwd(const float* h, const float* s_src, const float* s_dst, const int32_t* rowptr_t,
@@ -657,18 +571,18 @@ extern "C" int grapes_gat_aggregate_fwd(const float* h, const float* s_src, cons
                                         grapes_stream_t stream) {
     if (!h || !s_src || !s_dst || !rowptr_t || !csr_src || !out || !row_ms || n < 0) return GRAPES_EINVAL;
     const int skip = (long_items && d_n_items && workspace && item_cap > 0) ? 1 : 0;
-    if (skip && !gat_aligned16(workspace)) return GRAPES_EALIGN;
-    const int shape = gat_shape(f, gat_aligned16(h) && gat_aligned16(out) && (!bias || gat_aligned16(bias)));
+    if (skip && !grapes_aligned16(workspace)) return GRAPES_EALIGN;
+    const int shape = gat_shape(f, grapes_aligned16(h) && grapes_aligned16(out) && (!bias || grapes_aligned16(bias)));
     if (shape < 0) return shape;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const bool vec = shape == 0;
-    GAT_LAUNCH(gat_fwd_k, vec, f, gat_grid(n, 32), gat_grid(n, 64), s, h, s_src, s_dst, rowptr_t, csr_src, bias, out, row_ms, n,
+    ROW_LAUNCH(gat_fwd_k, 4, vec, f, n, s, h, s_src, s_dst, rowptr_t, csr_src, bias, out, row_ms, n,
                d_n, f, relu, skip, status);
     if (skip) {
         float* pacc = (float*)workspace;
-        float* pms = (float*)((char*)workspace + gat_round16((size_t)item_cap * f * sizeof(float)));
-        GAT_LAUNCH(gat_fwd_chunks_k, vec, f, gat_grid(item_cap, 32), gat_grid(item_cap, 64), s, h, s_src, s_dst, rowptr_t, csr_src,
+        float* pms = (float*)((char*)workspace + grapes_round16((size_t)item_cap * f * sizeof(float)));
+        ROW_LAUNCH(gat_fwd_chunks_k, 4, vec, f, item_cap, s, h, s_src, s_dst, rowptr_t, csr_src,
                    n, d_n, f, long_items, d_n_items, item_cap, pacc, pms, status);
         const int g2 = item_cap < 2048 ? item_cap : 2048;
         hipLaunchKernelGGL(gat_fwd_combine_k, dim3(g2), dim3(256), 0, s, h, s_src, s_dst, rowptr_t, bias, out, row_ms, n, d_n, f,
@@ -684,13 +598,13 @@ static inline GatBwdWs gat_bwd_ws(int32_t n, int32_t item_cap, int32_t f) {
     const size_t N = n > 0 ? (size_t)n : 1, I = item_cap > 0 ? (size_t)item_cap : 0, F = f > 0 ? (size_t)f : 1;
     GatBwdWs w;
     w.g = 0;
-    w.q = w.g + gat_round16(N * F * sizeof(float));
-    w.dss = w.q + gat_round16(N * 4 * sizeof(float));
-    w.dsd = w.dss + gat_round16(N * sizeof(float));
-    w.pacc = w.dsd + gat_round16(N * sizeof(float));
-    w.pds = w.pacc + gat_round16(I * F * sizeof(float));
-    w.part = w.pds + gat_round16(I * sizeof(float));
-    w.total = w.part + gat_round16((size_t)GAT_PARAM_BLOCKS * 3 * F * sizeof(float));
+    w.q = w.g + grapes_round16(N * F * sizeof(float));
+    w.dss = w.q + grapes_round16(N * 4 * sizeof(float));
+    w.dsd = w.dss + grapes_round16(N * sizeof(float));
+    w.pacc = w.dsd + grapes_round16(N * sizeof(float));
+    w.pds = w.pacc + grapes_round16(I * F * sizeof(float));
+    w.part = w.pds + grapes_round16(I * sizeof(float));
+    w.total = w.part + grapes_round16((size_t)GAT_PARAM_BLOCKS * 3 * F * sizeof(float));
     return w;
 }
 extern "C" size_t grapes_gat_aggregate_bwd_workspace_bytes(int32_t n, int32_t item_cap, int32_t f) {
@@ -707,9 +621,9 @@ extern "C" int grapes_gat_aggregate_bwd(const float* dout, const float* out, con
     if (!dout || !out || !h || !s_src || !s_dst || !row_ms || !a_src || !a_dst || !rowptr_t || !csr_src || !rowptr_s || !csr_dst ||
         !dh || !workspace || n < 0)
         return GRAPES_EINVAL;
-    if (!gat_aligned16(workspace)) return GRAPES_EALIGN;
-    const int shape = gat_shape(f, gat_aligned16(dout) && gat_aligned16(out) && gat_aligned16(h) && gat_aligned16(dh) &&
-                                       gat_aligned16(a_src) && gat_aligned16(a_dst) && (!bias || gat_aligned16(bias)));
+    if (!grapes_aligned16(workspace)) return GRAPES_EALIGN;
+    const int shape = gat_shape(f, grapes_aligned16(dout) && grapes_aligned16(out) && grapes_aligned16(h) && grapes_aligned16(dh) &&
+                                       grapes_aligned16(a_src) && grapes_aligned16(a_dst) && (!bias || grapes_aligned16(bias)));
     if (shape < 0) return shape;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -725,24 +639,22 @@ extern "C" int grapes_gat_aggregate_bwd(const float* dout, const float* out, con
     float* pds = (float*)(base + w.pds);
     float* part = (float*)(base + w.part);
     const float* gmat = relu ? gbuf : dout;
-    const int g32 = gat_grid(n, 32), g64 = gat_grid(n, 64);
-    const int i32 = gat_grid(item_cap, 32), i64 = gat_grid(item_cap, 64);
 
-    GAT_LAUNCH(gat_bwd_rows_k, vec, f, g32, g64, s, dout, out, bias, relu, s_dst, row_ms, gbuf, row_q, n, d_n, f);
-    GAT_LAUNCH(gat_bwd_dst_k, vec, f, g32, g64, s, h, s_src, gmat, (const float4*)row_q, rowptr_t, csr_src, ds_dst, n, d_n, f, skip_t,
+    ROW_LAUNCH(gat_bwd_rows_k, 4, vec, f, n, s, dout, out, bias, relu, s_dst, row_ms, gbuf, row_q, n, d_n, f);
+    ROW_LAUNCH(gat_bwd_dst_k, 4, vec, f, n, s, h, s_src, gmat, (const float4*)row_q, rowptr_t, csr_src, ds_dst, n, d_n, f, skip_t,
                status);
     if (skip_t) {
-        GAT_LAUNCH(gat_bwd_dst_chunks_k, vec, f, i32, i64, s, h, s_src, gmat, (const float4*)row_q, rowptr_t, csr_src, n, d_n, f,
+        ROW_LAUNCH(gat_bwd_dst_chunks_k, 4, vec, f, item_cap, s, h, s_src, gmat, (const float4*)row_q, rowptr_t, csr_src, n, d_n, f,
                    items_t, d_n_items_t, item_cap, pds, status);
         int g2 = grapes_div_up(item_cap, 256); if (g2 > 2048) g2 = 2048;
         hipLaunchKernelGGL(gat_bwd_dst_combine_k, dim3(g2), dim3(256), 0, s, rowptr_t, ds_dst, n, d_n, items_t, d_n_items_t, item_cap,
                            (const float*)pds);
         GRAPES_LAUNCH_CHECK();
     }
-    GAT_LAUNCH(gat_bwd_src_k, vec, f, g32, g64, s, h, s_src, gmat, (const float4*)row_q, (const float*)ds_dst, a_src, a_dst, rowptr_s,
+    ROW_LAUNCH(gat_bwd_src_k, 4, vec, f, n, s, h, s_src, gmat, (const float4*)row_q, (const float*)ds_dst, a_src, a_dst, rowptr_s,
                csr_dst, dh, ds_src, n, d_n, f, skip_s, status);
     if (skip_s) {
-        GAT_LAUNCH(gat_bwd_src_chunks_k, vec, f, i32, i64, s, h, s_src, gmat, (const float4*)row_q, rowptr_s, csr_dst, n, d_n, f,
+        ROW_LAUNCH(gat_bwd_src_chunks_k, 4, vec, f, item_cap, s, h, s_src, gmat, (const float4*)row_q, rowptr_s, csr_dst, n, d_n, f,
                    items_s, d_n_items_s, item_cap, pacc, pds, status);
         const int g2 = item_cap < 2048 ? item_cap : 2048;
         hipLaunchKernelGGL(gat_bwd_src_combine_k, dim3(g2), dim3(256), 0, s, rowptr_s, (const float*)ds_dst, a_src, a_dst, dh, ds_src,

@@ -19,44 +19,9 @@
 // The backward propagation is the SAME gather over the by-source CSR (dx_j = (1 - alpha) (sum_{j -> i} D_i + loops[j] D_j)):
 // no floating-point atomics anywhere, every sum has a fixed order (entry order inside a row, chunk order across work items), so
 // two runs are bit-identical.  No kernel waits on another workgroup.
-#include "common.h"
+#include "row_gather.h"
 
 template <int NS> struct G2Unroll { static constexpr int U = NS == 1 ? 4 : (NS <= 4 ? 2 : 1); };
-
-// lane l of a group holds columns (s LPR + l) VEC ... + VEC of a row, s < NS; columns at or beyond F read as zero
-template <int VEC, int LPR, int NS>
-__device__ __forceinline__ void g2_load_row(const float* __restrict__ base, long long row, int F, int l, float (&r)[NS][VEC]) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int f = (s * LPR + l) * VEC;
-        if (f < F) {
-            if (VEC == 4) {
-                const float4 t = *reinterpret_cast<const float4*>(base + row * F + f);
-                r[s][0] = t.x; r[s][VEC > 1 ? 1 : 0] = t.y; r[s][VEC > 2 ? 2 : 0] = t.z; r[s][VEC > 3 ? 3 : 0] = t.w;
-            } else {
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) r[s][v] = base[row * F + f + v];
-            }
-        } else {
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) r[s][v] = 0.f;
-        }
-    }
-}
-template <int VEC, int LPR, int NS>
-__device__ __forceinline__ void g2_store_row(float* __restrict__ base, long long row, int F, int l, const float (&r)[NS][VEC]) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-        const int f = (s * LPR + l) * VEC;
-        if (f < F) {
-            if (VEC == 4) *reinterpret_cast<float4*>(base + row * F + f) = make_float4(r[s][0], r[s][VEC > 1 ? 1 : 0], r[s][VEC > 2 ? 2 : 0], r[s][VEC > 3 ? 3 : 0]);
-            else {
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) base[row * F + f + v] = r[s][v];
-            }
-        }
-    }
-}
 
 // acc += sum of the rows m[csr[t]], t in [beg, end).  An index outside [0, n) raises GRAPES_STATUS_BAD_INDEX and the entry is
 // dropped (its lane keeps the row itself with weight 0, so the loads below need no predicate).
@@ -65,13 +30,9 @@ __device__ __forceinline__ void g2_gather(const float* __restrict__ m, const int
                                           int end, int F, int l, float (&acc)[NS][VEC], int32_t* status) {
     constexpr int U = G2Unroll<NS>::U;
     for (int b = beg; b < end; b += LPR) {
-        int idx = row;
-        float w = 0.f;
-        if (b + l < end) {
-            const int c = csr[b + l];
-            if ((unsigned)c < (unsigned)n) { idx = c; w = 1.f; }
-            else if (status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
-        }
+        const int c = batch_entry(csr, b + l, end, n, status);
+        const int idx = c < 0 ? row : c;
+        const float w = c < 0 ? 0.f : 1.f;
         const int cnt = end - b < LPR ? end - b : LPR;
         for (int k = 0; k < cnt; k += U) {
             float hv[U][NS][VEC], wk[U];
@@ -79,7 +40,7 @@ __device__ __forceinline__ void g2_gather(const float* __restrict__ m, const int
             for (int u = 0; u < U; ++u) {
                 const int ik = __shfl(idx, k + u, LPR);
                 wk[u] = __shfl(w, k + u, LPR);
-                g2_load_row<VEC, LPR, NS>(m, ik, F, l, hv[u]);
+                row_load<VEC, LPR, NS>(m, ik, F, l, hv[u]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -109,7 +70,7 @@ __device__ __forceinline__ void g2_finish(const G2Epi& e, float (&acc)[NS][VEC],
     const int lp = e.loops ? e.loops[row] : 0;
     if (lp != 0) {
         float xr[NS][VEC];
-        g2_load_row<VEC, LPR, NS>(e.src, row, F, l, xr);
+        row_load<VEC, LPR, NS>(e.src, row, F, l, xr);
         const float lf = (float)lp;
 #pragma unroll
         for (int s = 0; s < NS; ++s)
@@ -120,16 +81,16 @@ __device__ __forceinline__ void g2_finish(const G2Epi& e, float (&acc)[NS][VEC],
     for (int s = 0; s < NS; ++s)
 #pragma unroll
         for (int v = 0; v < VEC; ++v) acc[s][v] *= e.c_acc;
-    if (e.out2) g2_store_row<VEC, LPR, NS>(e.out2, row, F, l, acc);
+    if (e.out2) row_store<VEC, LPR, NS>(e.out2, row, F, l, acc);
     if (e.self_mat) {
         float x0[NS][VEC];
-        g2_load_row<VEC, LPR, NS>(e.self_mat, row, F, l, x0);
+        row_load<VEC, LPR, NS>(e.self_mat, row, F, l, x0);
 #pragma unroll
         for (int s = 0; s < NS; ++s)
 #pragma unroll
             for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(e.c_self, x0[s][v], acc[s][v]);
     }
-    g2_store_row<VEC, LPR, NS>(e.out1, row, F, l, acc);
+    row_store<VEC, LPR, NS>(e.out1, row, F, l, acc);
 }
 
 // rows longer than GRAPES_LONG_ROW (skip_long): only the row-local aux term here, the sum by gcn2_chunks_k / gcn2_combine_k
@@ -142,13 +103,13 @@ __global__ __launch_bounds__(256) void gcn2_rows_k(G2Epi e, const int32_t* __res
         const int beg = rowptr[row], end = rowptr[row + 1];
         if (e.aux) {
             float d[NS][VEC], a[NS][VEC];
-            g2_load_row<VEC, LPR, NS>(e.src, row, F, l, d);
-            if (e.aux_accumulate) g2_load_row<VEC, LPR, NS>(e.aux, row, F, l, a);
+            row_load<VEC, LPR, NS>(e.src, row, F, l, d);
+            if (e.aux_accumulate) row_load<VEC, LPR, NS>(e.aux, row, F, l, a);
 #pragma unroll
             for (int s = 0; s < NS; ++s)
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) d[s][v] = e.aux_accumulate ? fmaf(e.c_aux, d[s][v], a[s][v]) : e.c_aux * d[s][v];
-            g2_store_row<VEC, LPR, NS>(e.aux, row, F, l, d);
+            row_store<VEC, LPR, NS>(e.aux, row, F, l, d);
         }
         if (skip_long && end - beg > GRAPES_LONG_ROW) continue;
         float acc[NS][VEC];
@@ -168,25 +129,18 @@ __global__ __launch_bounds__(256) void gcn2_chunks_k(const float* __restrict__ m
                                                      const int32_t* __restrict__ items, const int32_t* __restrict__ d_n_items,
                                                      int item_cap, float* __restrict__ pacc, int32_t* status) {
     const int n = eff_count(d_n, n_host);
-    int n_items = *d_n_items; if (n_items > item_cap) n_items = item_cap;
+    const int n_items = item_count(d_n_items, item_cap);
     const int l = threadIdx.x % LPR, G = 256 / LPR;
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
-        const int row = items[2 * it], chunk = items[2 * it + 1];
+        int row, beg, end;
         float acc[NS][VEC];
 #pragma unroll
         for (int s = 0; s < NS; ++s)
 #pragma unroll
             for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
-        if ((unsigned)row < (unsigned)n && chunk >= 0) {
-            const int rbeg = rowptr[row], rend = rowptr[row + 1];
-            const long long cb = (long long)rbeg + (long long)chunk * GRAPES_LONG_ROW;
-            if (cb < rend) {
-                const int beg = (int)cb;
-                const int end = beg + GRAPES_LONG_ROW < rend ? beg + GRAPES_LONG_ROW : rend;
-                g2_gather<VEC, LPR, NS>(m, csr, row, n, beg, end, F, l, acc, status);
-            }
-        }
-        g2_store_row<VEC, LPR, NS>(pacc, it, F, l, acc);
+        item_range(items, it, rowptr, n, row, beg, end);
+        if (beg < end) g2_gather<VEC, LPR, NS>(m, csr, row, n, beg, end, F, l, acc, status);
+        row_store<VEC, LPR, NS>(pacc, it, F, l, acc);
     }
 }
 
@@ -197,13 +151,10 @@ __global__ __launch_bounds__(256) void gcn2_combine_k(G2Epi e, const int32_t* __
                                                       const int32_t* __restrict__ d_n_items, int item_cap,
                                                       const float* __restrict__ pacc) {
     const int n = eff_count(d_n, n_host);
-    int n_items = *d_n_items; if (n_items > item_cap) n_items = item_cap;
+    const int n_items = item_count(d_n_items, item_cap);
     for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
-        if (items[2 * it + 1] != 0) continue;
-        const int row = items[2 * it];
-        if ((unsigned)row >= (unsigned)n) continue;
-        int nc = (rowptr[row + 1] - rowptr[row] + GRAPES_LONG_ROW - 1) / GRAPES_LONG_ROW;
-        if (it + nc > n_items) nc = n_items - it;
+        int row, nc;
+        if (!item_leads(items, it, n_items, rowptr, n, row, nc)) continue;
         const float lf = e.loops ? (float)e.loops[row] : 0.f;
         for (int f = threadIdx.x; f < F; f += 256) {
             float a = 0.f;
@@ -334,34 +285,6 @@ __global__ __launch_bounds__(256) void gcn2_loops_csr_k(const int64_t* __restric
 
 // ------------------------------------------------------------------------------------------------------------ host side
 
-static inline bool g2_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-static inline size_t g2_round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-// lanes per row and slabs per lane by width: float4 columns (f % 4 == 0, 16-byte aligned rows) or scalar ones, any f <= 1024
-#define G2_LAUNCH(KERNEL, vec, f, grid32, grid64, s, ...)                                                                   \
-    do {                                                                                                                    \
-        if (vec) {                                                                                                          \
-            if ((f) <= 128) hipLaunchKernelGGL((KERNEL<4, 32, 1>), dim3(grid32), dim3(256), 0, s, __VA_ARGS__);              \
-            else if ((f) <= 256) hipLaunchKernelGGL((KERNEL<4, 64, 1>), dim3(grid64), dim3(256), 0, s, __VA_ARGS__);         \
-            else hipLaunchKernelGGL((KERNEL<4, 64, 4>), dim3(grid64), dim3(256), 0, s, __VA_ARGS__);                         \
-        } else {                                                                                                            \
-            if ((f) <= 32) hipLaunchKernelGGL((KERNEL<1, 32, 1>), dim3(grid32), dim3(256), 0, s, __VA_ARGS__);               \
-            else if ((f) <= 64) hipLaunchKernelGGL((KERNEL<1, 64, 1>), dim3(grid64), dim3(256), 0, s, __VA_ARGS__);          \
-            else if ((f) <= 256) hipLaunchKernelGGL((KERNEL<1, 64, 4>), dim3(grid64), dim3(256), 0, s, __VA_ARGS__);         \
-            else hipLaunchKernelGGL((KERNEL<1, 64, 16>), dim3(grid64), dim3(256), 0, s, __VA_ARGS__);                        \
-        }                                                                                                                   \
-        GRAPES_LAUNCH_CHECK();                                                                                              \
-    } while (0)
-
-static inline int g2_grid(int rows, int lanes) {
-    int g = grapes_div_up(rows > 0 ? rows : 1, 256 / lanes);
-    return g > 16384 ? 16384 : g;
-}
-static inline int g2_flat_grid(int64_t n, int64_t f, int vec) {
-    int64_t g = (n * f / vec + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
-
 extern "C" int grapes_gcn2_loop_counts(const int32_t* edge_src, const int32_t* edge_dst, int32_t e, const int32_t* d_e,
                                        const int32_t* node_map, int32_t n, const int32_t* d_n, int32_t* loops,
                                        grapes_stream_t stream) {
@@ -390,7 +313,7 @@ extern "C" int grapes_gcn2_loop_counts_csr(const int64_t* rowptr, const int32_t*
 // workspace: [pacc item_cap f] [D n f]
 extern "C" size_t grapes_gcn2_propagate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f) {
     const size_t N = n > 0 ? (size_t)n : 0, I = item_cap > 0 ? (size_t)item_cap : 0, F = f > 0 ? (size_t)f : 1;
-    return g2_round16(I * F * sizeof(float)) + g2_round16(N * F * sizeof(float)) + 16;
+    return grapes_round16(I * F * sizeof(float)) + grapes_round16(N * F * sizeof(float)) + 16;
 }
 
 // the launches of a propagation over (rowptr, csr): rows, and for long rows chunks + combine
@@ -398,9 +321,9 @@ static int g2_propagate(const G2Epi& epi, const int32_t* rowptr, const int32_t* 
                         bool vec, const int32_t* items, const int32_t* d_n_items, int32_t item_cap, float* pacc, int32_t* status,
                         hipStream_t s) {
     const int skip = (items && d_n_items && pacc && item_cap > 0) ? 1 : 0;
-    G2_LAUNCH(gcn2_rows_k, vec, f, g2_grid(n, 32), g2_grid(n, 64), s, epi, rowptr, csr, n, d_n, f, skip, status);
+    ROW_LAUNCH(gcn2_rows_k, 16, vec, f, n, s, epi, rowptr, csr, n, d_n, f, skip, status);
     if (skip) {
-        G2_LAUNCH(gcn2_chunks_k, vec, f, g2_grid(item_cap, 32), g2_grid(item_cap, 64), s, epi.src, rowptr, csr, n, d_n, f, items,
+        ROW_LAUNCH(gcn2_chunks_k, 16, vec, f, item_cap, s, epi.src, rowptr, csr, n, d_n, f, items,
                   d_n_items, item_cap, pacc, status);
         const int g2 = item_cap < 2048 ? item_cap : 2048;
         hipLaunchKernelGGL(gcn2_combine_k, dim3(g2), dim3(256), 0, s, epi, rowptr, n, d_n, f, items, d_n_items, item_cap,
@@ -417,9 +340,9 @@ extern "C" int grapes_gcn2_propagate_fwd(const float* x, const float* x0, const 
     if (!x || !x0 || !rowptr_t || !csr_src || !s_out || n < 0 || f < 1 || f > 1024) return GRAPES_EINVAL;
     if (s_out == x || s_out == x0 || (p_out && (p_out == x || p_out == x0 || p_out == s_out))) return GRAPES_EINVAL;
     const bool use_items = long_items && d_n_items && workspace && item_cap > 0;
-    if (use_items && !g2_aligned16(workspace)) return GRAPES_EALIGN;
+    if (use_items && !grapes_aligned16(workspace)) return GRAPES_EALIGN;
     if (n == 0) return 0;
-    const bool vec = f % 4 == 0 && g2_aligned16(x) && g2_aligned16(x0) && g2_aligned16(s_out) && (!p_out || g2_aligned16(p_out));
+    const bool vec = f % 4 == 0 && grapes_aligned16(x) && grapes_aligned16(x0) && grapes_aligned16(s_out) && (!p_out || grapes_aligned16(p_out));
     G2Epi epi;
     epi.src = x; epi.self_mat = x0; epi.loops = loops; epi.out1 = s_out; epi.out2 = p_out; epi.aux = nullptr;
     epi.c_acc = 1.f - alpha; epi.c_self = alpha; epi.c_aux = 0.f; epi.aux_accumulate = 0;
@@ -437,20 +360,20 @@ extern "C" int grapes_gcn2_propagate_bwd(const float* ds, const float* ds_add, i
     const bool two = ds_add || dx0_add;
     const bool use_items = items_s && d_n_items_s && workspace && item_cap > 0;
     if (two && !workspace) return GRAPES_EINVAL;
-    if ((two || use_items) && !g2_aligned16(workspace)) return GRAPES_EALIGN;
+    if ((two || use_items) && !grapes_aligned16(workspace)) return GRAPES_EALIGN;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = f % 4 == 0 && g2_aligned16(ds) && g2_aligned16(dx) && (!ds_add || g2_aligned16(ds_add)) &&
-                     (!dx0_add || g2_aligned16(dx0_add)) && (!dx0 || g2_aligned16(dx0));
+    const bool vec = f % 4 == 0 && grapes_aligned16(ds) && grapes_aligned16(dx) && (!ds_add || grapes_aligned16(ds_add)) &&
+                     (!dx0_add || grapes_aligned16(dx0_add)) && (!dx0 || grapes_aligned16(dx0));
     float* pacc = (float*)workspace;
-    float* dsum = (float*)((char*)workspace + g2_round16((size_t)(item_cap > 0 ? item_cap : 0) * f * sizeof(float)));
+    float* dsum = (float*)((char*)workspace + grapes_round16((size_t)(item_cap > 0 ? item_cap : 0) * f * sizeof(float)));
     G2Epi epi;
     epi.src = ds; epi.self_mat = nullptr; epi.loops = loops; epi.out1 = dx; epi.out2 = nullptr;
     epi.aux = dx0; epi.c_acc = 1.f - alpha; epi.c_self = 0.f; epi.c_aux = alpha; epi.aux_accumulate = accumulate_x0 ? 1 : 0;
     if (two) {
-        if (vec) hipLaunchKernelGGL(gcn2_bwd_sum_k<4>, dim3(g2_flat_grid(n, f, 4)), dim3(256), 0, s, ds, ds_add, add_is_p ? 1 : 0,
+        if (vec) hipLaunchKernelGGL(gcn2_bwd_sum_k<4>, dim3(flat_grid(n, f, 4)), dim3(256), 0, s, ds, ds_add, add_is_p ? 1 : 0,
                                     dx0_add, alpha, dsum, dx0, accumulate_x0 ? 1 : 0, n, d_n, f);
-        else hipLaunchKernelGGL(gcn2_bwd_sum_k<1>, dim3(g2_flat_grid(n, f, 1)), dim3(256), 0, s, ds, ds_add, add_is_p ? 1 : 0,
+        else hipLaunchKernelGGL(gcn2_bwd_sum_k<1>, dim3(flat_grid(n, f, 1)), dim3(256), 0, s, ds, ds_add, add_is_p ? 1 : 0,
                                 dx0_add, alpha, dsum, dx0, accumulate_x0 ? 1 : 0, n, d_n, f);
         GRAPES_LAUNCH_CHECK();
         epi.src = dsum; epi.aux = nullptr;
@@ -463,9 +386,9 @@ extern "C" int grapes_gcn2_mix_fwd(const float* s_in, const float* t1, const flo
     if (!s_in || !t1 || !out || n < 0 || f < 1) return GRAPES_EINVAL;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = f % 4 == 0 && g2_aligned16(s_in) && g2_aligned16(t1) && g2_aligned16(out) && (!t2 || g2_aligned16(t2));
-    if (vec) hipLaunchKernelGGL(gcn2_mix_fwd_k<4>, dim3(g2_flat_grid(n, f, 4)), dim3(256), 0, s, s_in, t1, t2, c0, c1, c2, relu, out, n, d_n, f);
-    else hipLaunchKernelGGL(gcn2_mix_fwd_k<1>, dim3(g2_flat_grid(n, f, 1)), dim3(256), 0, s, s_in, t1, t2, c0, c1, c2, relu, out, n, d_n, f);
+    const bool vec = f % 4 == 0 && grapes_aligned16(s_in) && grapes_aligned16(t1) && grapes_aligned16(out) && (!t2 || grapes_aligned16(t2));
+    if (vec) hipLaunchKernelGGL(gcn2_mix_fwd_k<4>, dim3(flat_grid(n, f, 4)), dim3(256), 0, s, s_in, t1, t2, c0, c1, c2, relu, out, n, d_n, f);
+    else hipLaunchKernelGGL(gcn2_mix_fwd_k<1>, dim3(flat_grid(n, f, 1)), dim3(256), 0, s, s_in, t1, t2, c0, c1, c2, relu, out, n, d_n, f);
     GRAPES_LAUNCH_CHECK();
     return 0;
 }
@@ -475,10 +398,10 @@ extern "C" int grapes_gcn2_mix_bwd(const float* dout, const float* out, int32_t 
     if (!dout || !g0 || (relu && !out) || n < 0 || f < 1) return GRAPES_EINVAL;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = f % 4 == 0 && g2_aligned16(dout) && g2_aligned16(g0) && (!g1 || g2_aligned16(g1)) && (!out || g2_aligned16(out)) &&
-                     (!g2 || g2_aligned16(g2));
-    if (vec) hipLaunchKernelGGL(gcn2_mix_bwd_k<4>, dim3(g2_flat_grid(n, f, 4)), dim3(256), 0, s, dout, out, relu, c0, c1, c2, g0, g1, g2, n, d_n, f);
-    else hipLaunchKernelGGL(gcn2_mix_bwd_k<1>, dim3(g2_flat_grid(n, f, 1)), dim3(256), 0, s, dout, out, relu, c0, c1, c2, g0, g1, g2, n, d_n, f);
+    const bool vec = f % 4 == 0 && grapes_aligned16(dout) && grapes_aligned16(g0) && (!g1 || grapes_aligned16(g1)) && (!out || grapes_aligned16(out)) &&
+                     (!g2 || grapes_aligned16(g2));
+    if (vec) hipLaunchKernelGGL(gcn2_mix_bwd_k<4>, dim3(flat_grid(n, f, 4)), dim3(256), 0, s, dout, out, relu, c0, c1, c2, g0, g1, g2, n, d_n, f);
+    else hipLaunchKernelGGL(gcn2_mix_bwd_k<1>, dim3(flat_grid(n, f, 1)), dim3(256), 0, s, dout, out, relu, c0, c1, c2, g0, g1, g2, n, d_n, f);
     GRAPES_LAUNCH_CHECK();
     return 0;
 }

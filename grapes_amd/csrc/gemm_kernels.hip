@@ -1319,7 +1319,6 @@ static int launch_skinny(const float* A, const float* B, float* C, int M, const 
 
 #ifndef GRAPES_ALIGNED16_DEFINED
 #define GRAPES_ALIGNED16_DEFINED
-static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 #endif
 
 template <bool AK, bool BK_>
@@ -1330,8 +1329,8 @@ static int launch_gemm(const float* A, const float* B, float* C, int M, int N, i
     // With fewer than 8 row panels the padded XCD-aware map would leave most launched blocks idle AND put
     // all working ones on the same one or two XCDs (blocks are dealt round-robin over the 8 XCDs).
     const int grid_x = mt < 8 ? mt * nt : grapes_div_up(mt, 8) * 8 * nt;
-    const bool vec = aligned16(A) && aligned16(B) && (lda % 4 == 0) && (ldb % 4 == 0) &&
-                     (!ex.gate_a || aligned16(ex.gate_a));
+    const bool vec = grapes_aligned16(A) && grapes_aligned16(B) && (lda % 4 == 0) && (ldb % 4 == 0) &&
+                     (!ex.gate_a || grapes_aligned16(ex.gate_a));
     if (!vec && (ex.gate_a || ex.colsum || ex.gather)) return GRAPES_EALIGN;   // fused extras exist for the aligned path only
     if (ex.colsum && (N % GB_N == 0 || N % 4 != 0)) return GRAPES_EINVAL;   // needs a free padding column
     dim3 grid(grid_x, nslab);
@@ -2711,7 +2710,7 @@ static inline bool dw_rank1_ok(int f_in, int f_out) {
 }
 
 static inline bool fused_dw_ok(const float* dout, const float* gate, const float* x, int f_in, int f_out) {
-    return aligned16(dout) && aligned16(x) && (!gate || aligned16(gate)) && f_in % 4 == 0 && f_out % 4 == 0 &&
+    return grapes_aligned16(dout) && grapes_aligned16(x) && (!gate || grapes_aligned16(gate)) && f_in % 4 == 0 && f_out % 4 == 0 &&
            f_in % GB_N != 0;
 }
 
@@ -2850,7 +2849,7 @@ extern "C" int grapes_linear_bwd_weight_gated(const float* dout, const float* ga
     float* w_dpre = w_dh + (size_t)nslab * f_out;
     float* w_cs = w_dpre + (size_t)n * f_out;
     int grid = grapes_div_up(slab, 64); if (grid > 4096) grid = 4096;
-    if (rank1 && !(fused_dw_ok(dout, gate, x, f_in, f_out) && aligned16(col_vec))) return GRAPES_EALIGN;
+    if (rank1 && !(fused_dw_ok(dout, gate, x, f_in, f_out) && grapes_aligned16(col_vec))) return GRAPES_EALIGN;
     if (rank1 && dw_rank1_ok(f_in, f_out) && DW_BLOCKS <= nslab) {       // dW-stationary kernel (one hop)
         const float* g1[1] = {gate}; const float* x1[1] = {x}; const float* r1[1] = {row_scale};
         const int32_t* d1[1] = {d_n}; const int32_t c1[1] = {n};
@@ -2906,7 +2905,7 @@ extern "C" int grapes_linear_bwd_weight_gated_multi(int32_t nseg, const float* c
         if (!gate[h] || !x[h] || !row_scale[h] || n_cap[h] <= 0) return GRAPES_EINVAL;
         if (!fused_dw_ok(gate[h], gate[h], x[h], f_in, f_out)) return GRAPES_EALIGN;
     }
-    if (!aligned16(col_vec)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(col_vec)) return GRAPES_EALIGN;
     hipStream_t s = (hipStream_t)stream;
     static int use_stationary = -1;
     if (use_stationary < 0) { const char* e = grapes_tune_env("GRAPES_DW_STATIONARY"); use_stationary = e ? atoi(e) : 1; }
@@ -2959,7 +2958,7 @@ extern "C" size_t grapes_linear_gathered_workspace_bytes(int32_t n_cap, int32_t 
 }
 static inline int gathered_args_ok(const float* X, int F, int x_stride, const int32_t* ids, const uint32_t* code, int num_ind) {
     if (!X || !ids || F <= 0 || num_ind < 0 || num_ind > 8 || x_stride < F || (x_stride & 3) || (num_ind > 0 && !code)) return GRAPES_EINVAL;
-    if (!aligned16(X)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(X)) return GRAPES_EALIGN;
     return 0;
 }
 extern "C" int grapes_linear_fwd_gathered(const float* X, int32_t F, int32_t x_stride, const int32_t* ids,
@@ -2971,7 +2970,7 @@ extern "C" int grapes_linear_fwd_gathered(const float* X, int32_t F, int32_t x_s
     int rc = gathered_args_ok(X, F, x_stride, ids, ind_code, num_ind);
     if (rc) return rc;
     const int kp = (F + num_ind + 3) & ~3;
-    if (!aligned16(w) || !aligned16(h)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(w) || !grapes_aligned16(h)) return GRAPES_EALIGN;
     hipStream_t s = (hipStream_t)stream;
     GemmEx ex{nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0};
     ex.gather = 1; ex.ga = GatherOp{ids, ind_code, d_epoch, epoch, F, 0xffu};
@@ -3005,7 +3004,7 @@ extern "C" int grapes_linear_bwd_weight_gathered(const float* dh, const float* X
         return 0;
     }
     if (!dh || !workspace) return GRAPES_EINVAL;
-    if (!aligned16(dh) || (f_out & 3)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(dh) || (f_out & 3)) return GRAPES_EALIGN;
     GemmEx ex{nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0};
     ex.gather = 2; ex.ga = GatherOp{ids, ind_code, d_epoch, epoch, F, ind_mask ? (ind_mask & 0xffu) : 0xffu};
     const int nslab = dw_nslab(f_out, kp);
@@ -3060,7 +3059,7 @@ extern "C" int grapes_linear_bwd_weight_gated_strided(const float* gate, const f
                                                       grapes_stream_t stream) {
     if (n <= 0 || !gate || !x || !row_scale || !col_vec || !dw || !workspace || x_stride < f_in || (x_stride & 3)) return GRAPES_EINVAL;
     if (!grapes_split_gemm_available(n, f_in, f_out)) return GRAPES_EINVAL;
-    if (!aligned16(gate) || !aligned16(x) || !aligned16(col_vec)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(gate) || !grapes_aligned16(x) || !grapes_aligned16(col_vec)) return GRAPES_EALIGN;
     const float* g1[1] = {gate}; const float* x1[1] = {x}; const float* r1[1] = {row_scale};
     const int32_t* d1[1] = {d_n}; const int32_t c1[1] = {n}; const int32_t s1[1] = {x_stride};
     return launch_dw_rank1(1, g1, x1, r1, d1, c1, col_vec, dw, dbias, dw_head, f_in, f_out, accumulate, workspace,
@@ -3104,10 +3103,10 @@ extern "C" int grapes_linear_bwd_weight_bits_multi_cols(int32_t nseg, const uint
     for (int h = 0; h < nseg; ++h) {
         if (!gate_bits[h] || !x[h] || !row_scale[h] || n_cap[h] <= 0) return GRAPES_EINVAL;
         if (x_stride && x_stride[h] > 0 && (x_stride[h] < f_in || (x_stride[h] & 3))) return GRAPES_EINVAL;
-        if (!aligned16(x[h])) return GRAPES_EALIGN;
+        if (!grapes_aligned16(x[h])) return GRAPES_EALIGN;
         nmax = n_cap[h] > nmax ? n_cap[h] : nmax;
     }
-    if (!aligned16(col_vec)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(col_vec)) return GRAPES_EALIGN;
     if (!grapes_split_gemm_available(nmax > 2048 ? nmax : 2048, f_in, f_out)) return GRAPES_EINVAL;
     if (dw_cols > 0 && dw_cols != f_in && !dw_split_ok(f_in, f_out, true)) return GRAPES_EINVAL;      // (only the slab-sum form writes a pitch)
     return launch_dw_rank1(nseg, nullptr, x, row_scale, d_n, n_cap, col_vec, dw, dbias, dw_head, f_in, f_out, accumulate, workspace,
@@ -3134,10 +3133,10 @@ extern "C" int grapes_linear_bwd_weight_bits_pair_cols(int32_t nseg, const uint3
         const int fi = h < nseg ? f_in : f_in_b;
         if (!gate_bits[h] || !x[h] || !row_scale[h] || n_cap[h] <= 0) return GRAPES_EINVAL;
         if (x_stride && x_stride[h] > 0 && (x_stride[h] < fi || (x_stride[h] & 3))) return GRAPES_EINVAL;
-        if (!aligned16(x[h])) return GRAPES_EALIGN;
+        if (!grapes_aligned16(x[h])) return GRAPES_EALIGN;
         nmax = n_cap[h] > nmax ? n_cap[h] : nmax;
     }
-    if (!aligned16(col_vec) || !aligned16(col_vec_b)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(col_vec) || !grapes_aligned16(col_vec_b)) return GRAPES_EALIGN;
     if (!grapes_split_gemm_available(nmax > 2048 ? nmax : 2048, f_in, f_out) ||
         !grapes_split_gemm_available(nmax > 2048 ? nmax : 2048, f_in_b, f_out)) return GRAPES_EINVAL;
     // the second problem's rows are read with ITS stride: a dense x of layer b has rows f_in_b apart

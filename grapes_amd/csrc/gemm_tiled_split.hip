@@ -1258,7 +1258,6 @@ __global__ __launch_bounds__(256) void ts_fwd_slab_sum_k(const float4* __restric
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static inline bool ts_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
 // Pre-split planes of a resident feature matrix (TsGather::planes) — DIAGNOSTIC BUILD ONLY: measured SLOWER than splitting the
 // gathered rows in the K loop (Reddit 1.418 against 1.366 ms/step, same box, profiles/r04_workloads.txt): the kernels are bound by
@@ -1278,7 +1277,7 @@ static const unsigned char* ts_planes_of(const float* X, int ldx) {
 extern "C" size_t grapes_feature_planes_bytes(int64_t n, int32_t x_stride) { return (size_t)(n > 0 ? n : 0) * 6u * (size_t)(x_stride > 0 ? x_stride : 0); }
 extern "C" int grapes_feature_split_planes(const float* X, int64_t n, int32_t x_stride, void* planes, grapes_stream_t stream) {
     if (!X || !planes || n <= 0 || x_stride <= 0 || (x_stride & 3)) return GRAPES_EINVAL;
-    if (!ts_aligned16(X) || (((uintptr_t)planes) & 7)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(X) || (((uintptr_t)planes) & 7)) return GRAPES_EALIGN;
     long long blocks = (n * (x_stride >> 2) + 255) / 256; if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(ts_split_planes_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, X, (long long)n, x_stride,
                        (unsigned char*)planes);
@@ -1369,7 +1368,7 @@ extern "C" int grapes_weight_split_images(int32_t count, const float* const* w, 
         const int lp = (wp && ld_pad) ? ld_pad[q] : 0;
         if (!w[q] || !image[q] || f_out[q] <= 0 || f_out[q] > TS_BN || k[q] <= 0 || ldw[q] < k[q]) return GRAPES_EINVAL;
         if (wp && (lp < k[q] || lp > grapes_div_up(k[q], TS_BK) * TS_BK)) return GRAPES_EINVAL;
-        if (!ts_aligned16(image[q])) return GRAPES_EALIGN;
+        if (!grapes_aligned16(image[q])) return GRAPES_EALIGN;
         const int nk = grapes_div_up(k[q], TS_BK);
         im.W[q] = w[q]; im.ldw[q] = ldw[q]; im.N[q] = f_out[q]; im.K[q] = k[q]; im.img[q] = (uint4*)image[q]; im.nk[q] = nk;
         im.w_pad[q] = wp; im.ld_pad[q] = lp;
@@ -1395,7 +1394,7 @@ extern "C" int grapes_linear_fwd_gathered_split(const float* X, int32_t F, int32
     if (n < 0 || !grapes_split_gathered_available(f_out) || !w_image || !h) return GRAPES_EINVAL;
     if (n == 0) return 0;
     if (!X || !ids || F <= 0 || num_ind < 0 || num_ind > 8 || x_stride < F || (x_stride & 3) || (num_ind > 0 && !ind_code)) return GRAPES_EINVAL;
-    if (!ts_aligned16(X) || !ts_aligned16(w_image)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(X) || !grapes_aligned16(w_image)) return GRAPES_EALIGN;
     int rc = ts_set_lds();
     if (rc) return rc;
     const int kp = (F + num_ind + 3) & ~3;
@@ -1434,7 +1433,7 @@ extern "C" int grapes_linear_fwd_gathered_split_tail(const float* X, int32_t F, 
         return GRAPES_EINVAL;
     if (n == 0) return 0;
     if (!X || !ids || F <= 0 || x_stride < F || (x_stride & 3)) return GRAPES_EINVAL;
-    if (!ts_aligned16(X) || !ts_aligned16(workspace)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(X) || !grapes_aligned16(workspace)) return GRAPES_EALIGN;
     int rc = ts_set_lds();
     if (rc) return rc;
     static bool attr = false;
@@ -1449,7 +1448,7 @@ extern "C" int grapes_linear_fwd_gathered_split_tail(const float* X, int32_t F, 
     for (int q = 0; q < 2; ++q) {
         const int p = q < nprob ? q : 0;
         if (num_ind[p] < 0 || num_ind[p] > 8 || (num_ind[p] > 0 && !ind_code[p]) || !w_image[p] || !h[p]) return GRAPES_EINVAL;
-        if (!ts_aligned16(w_image[p]) || !ts_aligned16(h[p])) return GRAPES_EALIGN;
+        if (!grapes_aligned16(w_image[p]) || !grapes_aligned16(h[p])) return GRAPES_EALIGN;
         const int kp = (F + num_ind[p] + 3) & ~3;
         const int nkq = grapes_div_up(kp, TS_BK);
         if (q == 0) nk = nkq; else if (nkq != nk) return GRAPES_EINVAL;          // (the nets share the K steps)
@@ -1486,7 +1485,7 @@ extern "C" int grapes_linear_fwd_gathered_split_k(const float* X, int32_t F, int
     if (n < 0 || !grapes_split_gathered_available(f_out) || !w_image || !h || !workspace) return GRAPES_EINVAL;
     if (n == 0) return 0;
     if (!X || !ids || F <= 0 || num_ind < 0 || num_ind > 8 || x_stride < F || (x_stride & 3) || (num_ind > 0 && !ind_code)) return GRAPES_EINVAL;
-    if (!ts_aligned16(X) || !ts_aligned16(w_image) || !ts_aligned16(workspace) || !ts_aligned16(h)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(X) || !grapes_aligned16(w_image) || !grapes_aligned16(workspace) || !grapes_aligned16(h)) return GRAPES_EALIGN;
     int rc = ts_set_lds();
     if (rc) return rc;
     const int kp = (F + num_ind + 3) & ~3;
@@ -1584,7 +1583,7 @@ extern "C" int grapes_linear_bwd_weight_gathered_split_ld(const float* dh, const
         return 0;
     }
     if (!dh || !workspace) return GRAPES_EINVAL;
-    if (!ts_aligned16(X) || !ts_aligned16(dh)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(X) || !grapes_aligned16(dh)) return GRAPES_EALIGN;
     int rc = ts_set_lds();
     if (rc) return rc;
     TsGather ga{X, x_stride, F, ids, ind_code, d_epoch, epoch, ind_mask ? (ind_mask & 0xffu) : 0xffu, ts_planes_of(X, x_stride)};
@@ -1635,13 +1634,13 @@ extern "C" int grapes_linear_bwd_weight_gathered_split_multi(int32_t count, cons
     if (count < 1 || count > TS_DW_MAXP || !dh || !ids || !ind_code || !num_ind || !ind_mask || !dw || !dw_ld || !n || !d_n || !accumulate)
         return GRAPES_EINVAL;
     if (!X || F <= 0 || x_stride < F || (x_stride & 3) || !workspace || !grapes_split_gathered_available(f_out)) return GRAPES_EINVAL;
-    if (!ts_aligned16(X) || !ts_aligned16(workspace)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(X) || !grapes_aligned16(workspace)) return GRAPES_EALIGN;
     TsDwMulti mp{};
     TsDwOuts outs{};
     int kp_max = 0;
     for (int q = 0; q < count; ++q) {
         if (n[q] < 0 || !dw[q] || !ids[q] || !dh[q] || num_ind[q] < 0 || num_ind[q] > 8 || (num_ind[q] > 0 && !ind_code[q])) return GRAPES_EINVAL;
-        if (!ts_aligned16(dh[q])) return GRAPES_EALIGN;
+        if (!grapes_aligned16(dh[q])) return GRAPES_EALIGN;
         const int kp = (F + num_ind[q] + 3) & ~3;
         if (dw_ld[q] != 0 && dw_ld[q] != F + num_ind[q] && dw_ld[q] != kp) return GRAPES_EINVAL;
         if (!ts_dw_swapped(f_out, kp)) return GRAPES_EINVAL;                 // (grapes_..._multi_available says so beforehand)

@@ -26,7 +26,7 @@
 // Variance: centred (Welford per entry, Chan across chunks and for a loop of multiplicity c), never E[b^2] - E[b]^2.  Ties: an
 // entry bit-equal to the row's max (min) gets 1 / (number of such entries) of its gradient, so the weights of a row sum to one.
 // No floating-point atomics, every reduction has a fixed order: two runs are bit-identical.  No kernel waits on another workgroup.
-#include "common.h"
+#include "row_gather.h"
 
 #include <math.h>
 
@@ -50,21 +50,6 @@ __device__ __forceinline__ float pna_scaler(int kind, int d, float avg_log, floa
         case PNA_INVERSE_LINEAR: return avg_lin / d1;
         default: return 1.f;
     }
-}
-
-template <int VEC>
-__device__ __forceinline__ void pv_load(const float* __restrict__ p, float (&r)[VEC]) {
-    if constexpr (VEC == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(p);
-        r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w;
-    } else {
-        r[0] = *p;
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void pv_store(float* __restrict__ p, const float (&r)[VEC]) {
-    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
-    else *p = r[0];
 }
 
 // the running statistics of one lane's VEC features
@@ -130,9 +115,9 @@ __device__ __forceinline__ void pna_emit(const PnaFwd& p, int row, int f0, int d
     float* __restrict__ zr = p.z + (long long)row * ldz + f0;
     float* __restrict__ sr = p.stats + (long long)row * PNA_NSTAT * F + f0;
     float xr[VEC], ar[VEC], val[6][VEC], st[PNA_NSTAT][VEC];
-    pv_load<VEC>(p.x + (long long)row * F + f0, xr);
-    pv_store<VEC>(zr, xr);
-    pv_load<VEC>(p.a + (long long)row * p.ld + f0, ar);
+    vec_load<VEC>(p.x + (long long)row * F + f0, xr);
+    vec_store<VEC>(zr, xr);
+    vec_load<VEC>(p.a + (long long)row * p.ld + f0, ar);
     const float df = (float)d;
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
@@ -150,7 +135,7 @@ __device__ __forceinline__ void pna_emit(const PnaFwd& p, int row, int f0, int d
         }
     }
 #pragma unroll
-    for (int q = 0; q < PNA_NSTAT; ++q) pv_store<VEC>(sr + (long long)q * F, st[q]);
+    for (int q = 0; q < PNA_NSTAT; ++q) vec_store<VEC>(sr + (long long)q * F, st[q]);
     for (int s = 0; s < p.c.n_scal; ++s) {
         const float sc = pna_scaler(pna_code(p.c.scal_code, s), d, p.c.avg_log, p.c.avg_lin);
         for (int k = 0; k < p.c.n_agg; ++k) {
@@ -163,7 +148,7 @@ __device__ __forceinline__ void pna_emit(const PnaFwd& p, int row, int f0, int d
                 for (int q = 1; q < 6; ++q) t = kind == q ? val[q][v] : t;       // (a select chain: no dynamically indexed registers)
                 o[v] = sc * t;
             }
-            pv_store<VEC>(zr + (long long)(1 + s * p.c.n_agg + k) * F, o);
+            vec_store<VEC>(zr + (long long)(1 + s * p.c.n_agg + k) * F, o);
         }
     }
 }
@@ -175,12 +160,7 @@ __device__ __forceinline__ void pna_gather(const float* __restrict__ b, int ld, 
                                            int f0, bool active, int l, PnaAcc<VEC>& acc, int32_t* status) {
     constexpr int U = 4;
     for (int t0 = beg; t0 < end; t0 += LPR) {
-        int idx = -1;
-        if (t0 + l < end) {
-            const int c = csr[t0 + l];
-            if ((unsigned)c < (unsigned)n) idx = c;
-            else if (status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
-        }
+        const int idx = batch_entry(csr, t0 + l, end, n, status);
         const int cnt = end - t0 < LPR ? end - t0 : LPR;
         for (int k = 0; k < cnt; k += U) {
             float hv[U][VEC];
@@ -191,7 +171,7 @@ __device__ __forceinline__ void pna_gather(const float* __restrict__ b, int ld, 
                 ik[u] = k + u < cnt ? src : -1;
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) hv[u][v] = 0.f;
-                if (ik[u] >= 0 && active) pv_load<VEC>(b + (long long)ik[u] * ld + f0, hv[u]);
+                if (ik[u] >= 0 && active) vec_load<VEC>(b + (long long)ik[u] * ld + f0, hv[u]);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -218,7 +198,7 @@ __global__ __launch_bounds__(256) void pna_rows_k(PnaFwd p, const int32_t* __res
             if (active) {
                 if (lp > 0) {
                     float br[VEC];
-                    pv_load<VEC>(p.b + (long long)row * p.ld + f0, br);
+                    vec_load<VEC>(p.b + (long long)row * p.ld + f0, br);
                     acc.push_copies(br, lp);
                 }
                 pna_emit<VEC>(p, row, f0, end - beg + (lp > 0 ? lp : 0), acc);
@@ -234,19 +214,11 @@ __global__ __launch_bounds__(256) void pna_chunks_k(const float* __restrict__ b,
                                                     const int32_t* __restrict__ items, const int32_t* __restrict__ d_n_items,
                                                     int item_cap, float* __restrict__ pacc, int32_t* __restrict__ pcnt, int32_t* status) {
     const int n = eff_count(d_n, n_host);
-    int n_items = *d_n_items; if (n_items > item_cap) n_items = item_cap;
+    const int n_items = item_count(d_n_items, item_cap);
     const int l = threadIdx.x % LPR, G = 256 / LPR;
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
-        const int row = items[2 * it], chunk = items[2 * it + 1];
-        int beg = 0, end = 0;
-        if ((unsigned)row < (unsigned)n && chunk >= 0) {
-            const int rbeg = rowptr[row], rend = rowptr[row + 1];
-            const long long cb = (long long)rbeg + (long long)chunk * GRAPES_LONG_ROW;
-            if (cb < rend) {
-                beg = (int)cb;
-                end = beg + GRAPES_LONG_ROW < rend ? beg + GRAPES_LONG_ROW : rend;
-            }
-        }
+        int row, beg, end;
+        item_range(items, it, rowptr, n, row, beg, end);
         for (int c0 = 0; c0 < F; c0 += LPR * VEC) {
             const int f0 = c0 + l * VEC;
             const bool active = f0 < F;
@@ -255,8 +227,8 @@ __global__ __launch_bounds__(256) void pna_chunks_k(const float* __restrict__ b,
             pna_gather<VEC, LPR>(b, ld, csr, n, beg, end, f0, active, l, acc, status);
             if (active) {
                 float* __restrict__ pr = pacc + (long long)it * PNA_NSTAT * F + f0;
-                pv_store<VEC>(pr, acc.mean); pv_store<VEC>(pr + F, acc.mn); pv_store<VEC>(pr + 2LL * F, acc.mx);
-                pv_store<VEC>(pr + 3LL * F, acc.m2); pv_store<VEC>(pr + 4LL * F, acc.tn); pv_store<VEC>(pr + 5LL * F, acc.tx);
+                vec_store<VEC>(pr, acc.mean); vec_store<VEC>(pr + F, acc.mn); vec_store<VEC>(pr + 2LL * F, acc.mx);
+                vec_store<VEC>(pr + 3LL * F, acc.m2); vec_store<VEC>(pr + 4LL * F, acc.tn); vec_store<VEC>(pr + 5LL * F, acc.tx);
             }
             if (c0 == 0 && l == 0) pcnt[it] = acc.cnt;
         }
@@ -270,14 +242,11 @@ __global__ __launch_bounds__(256) void pna_combine_k(PnaFwd p, const int32_t* __
                                                      int item_cap, const float* __restrict__ pacc, const int32_t* __restrict__ pcnt) {
     const int n = eff_count(d_n, n_host);
     const int F = p.F;
-    int n_items = *d_n_items; if (n_items > item_cap) n_items = item_cap;
+    const int n_items = item_count(d_n_items, item_cap);
     for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
-        if (items[2 * it + 1] != 0) continue;
-        const int row = items[2 * it];
-        if ((unsigned)row >= (unsigned)n) continue;
+        int row, nc;
+        if (!item_leads(items, it, n_items, rowptr, n, row, nc)) continue;
         const int len = rowptr[row + 1] - rowptr[row];
-        int nc = (len + GRAPES_LONG_ROW - 1) / GRAPES_LONG_ROW;
-        if (it + nc > n_items) nc = n_items - it;
         const int lp = p.loops ? p.loops[row] : 0;
         for (int f = threadIdx.x; f < F; f += 256) {
             PnaAcc<1> acc;
@@ -359,8 +328,8 @@ __device__ __forceinline__ void pna_bwd_term(const PnaBwd& p, int i, int f0, con
     const float* __restrict__ cr = p.coef + (long long)i * 4 * p.F + f0;
     const float* __restrict__ sr = p.stats + (long long)i * PNA_NSTAT * p.F + f0;
     float gm[VEC], gv[VEC], gn[VEC], gx[VEC], mean[VEC], mn[VEC], mx[VEC];
-    pv_load<VEC>(cr, gm); pv_load<VEC>(cr + p.F, gv); pv_load<VEC>(cr + 2LL * p.F, gn); pv_load<VEC>(cr + 3LL * p.F, gx);
-    pv_load<VEC>(sr, mean); pv_load<VEC>(sr + p.F, mn); pv_load<VEC>(sr + 2LL * p.F, mx);
+    vec_load<VEC>(cr, gm); vec_load<VEC>(cr + p.F, gv); vec_load<VEC>(cr + 2LL * p.F, gn); vec_load<VEC>(cr + 3LL * p.F, gx);
+    vec_load<VEC>(sr, mean); vec_load<VEC>(sr + p.F, mn); vec_load<VEC>(sr + 2LL * p.F, mx);
 #pragma unroll
     for (int v = 0; v < VEC; ++v) {
         float t = fmaf(gv[v], bj[v] - mean[v], gm[v]);
@@ -374,12 +343,7 @@ template <int VEC, int LPR>
 __device__ __forceinline__ void pna_bwd_gather(const PnaBwd& p, const int32_t* __restrict__ csr, int n, int beg, int end, int f0,
                                                bool active, int l, const float (&bj)[VEC], float (&acc)[VEC], int32_t* status) {
     for (int t0 = beg; t0 < end; t0 += LPR) {
-        int idx = -1;
-        if (t0 + l < end) {
-            const int c = csr[t0 + l];
-            if ((unsigned)c < (unsigned)n) idx = c;
-            else if (status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
-        }
+        const int idx = batch_entry(csr, t0 + l, end, n, status);
         const int cnt = end - t0 < LPR ? end - t0 : LPR;
         for (int k = 0; k < cnt; ++k) {
             const int i = __shfl(idx, k, LPR);
@@ -403,11 +367,11 @@ __global__ __launch_bounds__(256) void pna_bwd_rows_k(PnaBwd p, const int32_t* _
             float bj[VEC], acc[VEC];
 #pragma unroll
             for (int v = 0; v < VEC; ++v) { bj[v] = 0.f; acc[v] = 0.f; }
-            if (active) pv_load<VEC>(p.b + (long long)row * p.ld + f0, bj);
+            if (active) vec_load<VEC>(p.b + (long long)row * p.ld + f0, bj);
             pna_bwd_gather<VEC, LPR>(p, csr, n, beg, end, f0, active, l, bj, acc, status);
             if (active) {
                 if (lp > 0) pna_bwd_term<VEC>(p, row, f0, bj, (float)lp, acc);
-                pv_store<VEC>(p.db + (long long)row * p.ld_d + f0, acc);
+                vec_store<VEC>(p.db + (long long)row * p.ld_d + f0, acc);
             }
         }
     }
@@ -419,29 +383,20 @@ __global__ __launch_bounds__(256) void pna_bwd_chunks_k(PnaBwd p, const int32_t*
                                                         const int32_t* __restrict__ d_n_items, int item_cap, float* __restrict__ pacc,
                                                         int32_t* status) {
     const int n = eff_count(d_n, n_host);
-    int n_items = *d_n_items; if (n_items > item_cap) n_items = item_cap;
+    const int n_items = item_count(d_n_items, item_cap);
     const int l = threadIdx.x % LPR, G = 256 / LPR;
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
-        const int row = items[2 * it], chunk = items[2 * it + 1];
-        int beg = 0, end = 0;
-        const bool ok = (unsigned)row < (unsigned)n && chunk >= 0;
-        if (ok) {
-            const int rbeg = rowptr[row], rend = rowptr[row + 1];
-            const long long cb = (long long)rbeg + (long long)chunk * GRAPES_LONG_ROW;
-            if (cb < rend) {
-                beg = (int)cb;
-                end = beg + GRAPES_LONG_ROW < rend ? beg + GRAPES_LONG_ROW : rend;
-            }
-        }
+        int row, beg, end;
+        const bool ok = item_range(items, it, rowptr, n, row, beg, end);
         for (int c0 = 0; c0 < p.F; c0 += LPR * VEC) {
             const int f0 = c0 + l * VEC;
             const bool active = f0 < p.F;
             float bj[VEC], acc[VEC];
 #pragma unroll
             for (int v = 0; v < VEC; ++v) { bj[v] = 0.f; acc[v] = 0.f; }
-            if (active && ok) pv_load<VEC>(p.b + (long long)row * p.ld + f0, bj);
+            if (active && ok) vec_load<VEC>(p.b + (long long)row * p.ld + f0, bj);
             pna_bwd_gather<VEC, LPR>(p, csr, n, beg, end, f0, active, l, bj, acc, status);
-            if (active) pv_store<VEC>(pacc + (long long)it * p.F + f0, acc);
+            if (active) vec_store<VEC>(pacc + (long long)it * p.F + f0, acc);
         }
     }
 }
@@ -451,13 +406,10 @@ __global__ __launch_bounds__(256) void pna_bwd_combine_k(PnaBwd p, const int32_t
                                                          int item_cap, const float* __restrict__ pacc) {
     const int n = eff_count(d_n, n_host);
     const int F = p.F;
-    int n_items = *d_n_items; if (n_items > item_cap) n_items = item_cap;
+    const int n_items = item_count(d_n_items, item_cap);
     for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
-        if (items[2 * it + 1] != 0) continue;
-        const int row = items[2 * it];
-        if ((unsigned)row >= (unsigned)n) continue;
-        int nc = (rowptr[row + 1] - rowptr[row] + GRAPES_LONG_ROW - 1) / GRAPES_LONG_ROW;
-        if (it + nc > n_items) nc = n_items - it;
+        int row, nc;
+        if (!item_leads(items, it, n_items, rowptr, n, row, nc)) continue;
         const int lp = p.loops ? p.loops[row] : 0;
         for (int f = threadIdx.x; f < F; f += 256) {
             float acc[1] = {0.f};
@@ -483,32 +435,6 @@ __global__ __launch_bounds__(256) void pna_add_k(float* __restrict__ dst, const 
 
 // ------------------------------------------------------------------------------------------------------------ host side
 
-static inline bool pna_aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
-static inline size_t pna_round16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-// lanes per row by width: float4 columns (f % 4 == 0, 16-byte aligned rows) or scalar ones; a row wider than the group's tile
-// (LPR * VEC columns) is walked once per tile, so any f >= 1 works
-#define PNA_LAUNCH(KERNEL, vec, f, rows, s, ...)                                                                                \
-    do {                                                                                                                        \
-        if (vec) {                                                                                                              \
-            if ((f) <= 128) hipLaunchKernelGGL((KERNEL<4, 32>), dim3(pna_grid(rows, 32)), dim3(256), 0, s, __VA_ARGS__);         \
-            else hipLaunchKernelGGL((KERNEL<4, 64>), dim3(pna_grid(rows, 64)), dim3(256), 0, s, __VA_ARGS__);                    \
-        } else {                                                                                                                \
-            if ((f) <= 32) hipLaunchKernelGGL((KERNEL<1, 32>), dim3(pna_grid(rows, 32)), dim3(256), 0, s, __VA_ARGS__);          \
-            else hipLaunchKernelGGL((KERNEL<1, 64>), dim3(pna_grid(rows, 64)), dim3(256), 0, s, __VA_ARGS__);                    \
-        }                                                                                                                       \
-        GRAPES_LAUNCH_CHECK();                                                                                                  \
-    } while (0)
-
-static inline int pna_grid(int rows, int lanes) {
-    int g = grapes_div_up(rows > 0 ? rows : 1, 256 / lanes);
-    return g > 16384 ? 16384 : g;
-}
-static inline int pna_flat_grid(int64_t n, int64_t f) {
-    int64_t g = (n * f + 255) / 256;
-    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
-
 static bool pna_cfg(int32_t n_agg, int32_t agg_code, int32_t n_scal, int32_t scal_code, float avg_log, float avg_lin, PnaCfg* c) {
     if (n_agg < 1 || n_agg > 6 || n_scal < 1 || n_scal > 5) return false;
     for (int k = 0; k < n_agg; ++k)
@@ -526,7 +452,7 @@ static bool pna_cfg(int32_t n_agg, int32_t agg_code, int32_t n_scal, int32_t sca
 // workspace: [pacc item_cap PNA_NSTAT f] [pcnt item_cap]
 extern "C" size_t grapes_pna_aggregate_fwd_workspace_bytes(int32_t item_cap, int32_t f) {
     const size_t I = item_cap > 0 ? (size_t)item_cap : 0, F = f > 0 ? (size_t)f : 1;
-    return pna_round16(I * PNA_NSTAT * F * sizeof(float)) + pna_round16(I * sizeof(int32_t)) + 16;
+    return grapes_round16(I * PNA_NSTAT * F * sizeof(float)) + grapes_round16(I * sizeof(int32_t)) + 16;
 }
 
 extern "C" int grapes_pna_aggregate_fwd(const float* x, const float* a, const float* b, int32_t ld, const int32_t* loops,
@@ -541,17 +467,17 @@ extern "C" int grapes_pna_aggregate_fwd(const float* x, const float* a, const fl
     if ((int64_t)(1 + n_agg * n_scal) * f > INT32_MAX) return GRAPES_EINVAL;
     if (z == x || z == a || z == b || stats == z) return GRAPES_EINVAL;
     const bool use_items = long_items && d_n_items && workspace && item_cap > 0;
-    if (use_items && !pna_aligned16(workspace)) return GRAPES_EALIGN;
+    if (use_items && !grapes_aligned16(workspace)) return GRAPES_EALIGN;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const bool vec = f % 4 == 0 && ld % 4 == 0 && pna_aligned16(x) && pna_aligned16(a) && pna_aligned16(b) && pna_aligned16(z) &&
-                     pna_aligned16(stats);
+    const bool vec = f % 4 == 0 && ld % 4 == 0 && grapes_aligned16(x) && grapes_aligned16(a) && grapes_aligned16(b) && grapes_aligned16(z) &&
+                     grapes_aligned16(stats);
     p.x = x; p.a = a; p.b = b; p.loops = loops; p.z = z; p.stats = stats; p.ld = ld; p.F = f;
-    PNA_LAUNCH(pna_rows_k, vec, f, n, s, p, rowptr_t, csr_src, n, d_n, use_items ? 1 : 0, status);
+    ROW_LAUNCH_TILED(pna_rows_k, vec, f, n, s, p, rowptr_t, csr_src, n, d_n, use_items ? 1 : 0, status);
     if (use_items) {
         float* pacc = (float*)workspace;
-        int32_t* pcnt = (int32_t*)((char*)workspace + pna_round16((size_t)item_cap * PNA_NSTAT * f * sizeof(float)));
-        PNA_LAUNCH(pna_chunks_k, vec, f, item_cap, s, b, ld, f, rowptr_t, csr_src, n, d_n, long_items, d_n_items, item_cap, pacc, pcnt,
+        int32_t* pcnt = (int32_t*)((char*)workspace + grapes_round16((size_t)item_cap * PNA_NSTAT * f * sizeof(float)));
+        ROW_LAUNCH_TILED(pna_chunks_k, vec, f, item_cap, s, b, ld, f, rowptr_t, csr_src, n, d_n, long_items, d_n_items, item_cap, pacc, pcnt,
                    status);
         const int g2 = item_cap < 2048 ? item_cap : 2048;
         hipLaunchKernelGGL(pna_combine_k, dim3(g2), dim3(256), 0, s, p, rowptr_t, n, d_n, long_items, d_n_items, item_cap,
@@ -564,7 +490,7 @@ extern "C" int grapes_pna_aggregate_fwd(const float* x, const float* a, const fl
 // workspace: [coef n 4 f] [pacc item_cap f]
 extern "C" size_t grapes_pna_aggregate_bwd_workspace_bytes(int32_t n, int32_t item_cap, int32_t f) {
     const size_t N = n > 0 ? (size_t)n : 0, I = item_cap > 0 ? (size_t)item_cap : 0, F = f > 0 ? (size_t)f : 1;
-    return pna_round16(N * 4 * F * sizeof(float)) + pna_round16(I * F * sizeof(float)) + 16;
+    return grapes_round16(N * 4 * F * sizeof(float)) + grapes_round16(I * F * sizeof(float)) + 16;
 }
 
 extern "C" int grapes_pna_aggregate_bwd(const float* dz, const float* b, int32_t ld, const float* stats, const int32_t* loops,
@@ -578,20 +504,20 @@ extern "C" int grapes_pna_aggregate_bwd(const float* dz, const float* b, int32_t
         return GRAPES_EINVAL;
     if (!pna_cfg(n_agg, agg_code, n_scal, scal_code, avg_log, avg_lin, &c)) return GRAPES_EINVAL;
     if ((int64_t)(1 + n_agg * n_scal) * f > INT32_MAX) return GRAPES_EINVAL;
-    if (!pna_aligned16(workspace)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(workspace)) return GRAPES_EALIGN;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     const bool use_items = items_s && d_n_items_s && item_cap > 0;
     float* coef = (float*)workspace;
-    float* pacc = (float*)((char*)workspace + pna_round16((size_t)n * 4 * f * sizeof(float)));
-    hipLaunchKernelGGL(pna_fold_k, dim3(pna_flat_grid(n, f)), dim3(256), 0, s, dz, stats, rowptr_t, loops, c, coef, da, ld_d, n, d_n, f);
+    float* pacc = (float*)((char*)workspace + grapes_round16((size_t)n * 4 * f * sizeof(float)));
+    hipLaunchKernelGGL(pna_fold_k, dim3(flat_grid(n, f, 1)), dim3(256), 0, s, dz, stats, rowptr_t, loops, c, coef, da, ld_d, n, d_n, f);
     GRAPES_LAUNCH_CHECK();
-    const bool vec = f % 4 == 0 && ld % 4 == 0 && ld_d % 4 == 0 && pna_aligned16(b) && pna_aligned16(stats) && pna_aligned16(db);
+    const bool vec = f % 4 == 0 && ld % 4 == 0 && ld_d % 4 == 0 && grapes_aligned16(b) && grapes_aligned16(stats) && grapes_aligned16(db);
     PnaBwd p;
     p.b = b; p.stats = stats; p.coef = coef; p.loops = loops; p.db = db; p.ld = ld; p.ld_d = ld_d; p.F = f;
-    PNA_LAUNCH(pna_bwd_rows_k, vec, f, n, s, p, rowptr_s, csr_dst, n, d_n, use_items ? 1 : 0, status);
+    ROW_LAUNCH_TILED(pna_bwd_rows_k, vec, f, n, s, p, rowptr_s, csr_dst, n, d_n, use_items ? 1 : 0, status);
     if (use_items) {
-        PNA_LAUNCH(pna_bwd_chunks_k, vec, f, item_cap, s, p, rowptr_s, csr_dst, n, d_n, items_s, d_n_items_s, item_cap, pacc, status);
+        ROW_LAUNCH_TILED(pna_bwd_chunks_k, vec, f, item_cap, s, p, rowptr_s, csr_dst, n, d_n, items_s, d_n_items_s, item_cap, pacc, status);
         const int g2 = item_cap < 2048 ? item_cap : 2048;
         hipLaunchKernelGGL(pna_bwd_combine_k, dim3(g2), dim3(256), 0, s, p, rowptr_s, n, d_n, items_s, d_n_items_s, item_cap,
                            (const float*)pacc);
@@ -604,7 +530,7 @@ extern "C" int grapes_pna_add_input_grad(float* dx, const float* dz, int32_t ld_
                                          grapes_stream_t stream) {
     if (!dx || !dz || n < 0 || f < 1 || ld_z < f) return GRAPES_EINVAL;
     if (n == 0) return 0;
-    hipLaunchKernelGGL(pna_add_k, dim3(pna_flat_grid(n, f)), dim3(256), 0, (hipStream_t)stream, dx, dz, (long long)ld_z, n, d_n, f);
+    hipLaunchKernelGGL(pna_add_k, dim3(flat_grid(n, f, 1)), dim3(256), 0, (hipStream_t)stream, dx, dz, (long long)ld_z, n, d_n, f);
     GRAPES_LAUNCH_CHECK();
     return 0;
 }

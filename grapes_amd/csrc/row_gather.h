@@ -1,0 +1,167 @@
+// The scaffold the row-gather aggregations share (gat_kernels.hip, gcn2_kernels.hip, pna_kernels.hip): a new aggregation starts
+// here and adds only its own arithmetic.  Every one of them walks the CSRs grapes_gcn_prepare builds with the same three kernels:
+//
+//   *_rows_k      a group of LPR lanes (half a wavefront or a whole one) owns a row; per batch of LPR entries every lane reads ONE
+//                 column index (batch_entry), then the batch's rows are gathered with the indices broadcast from their lanes
+//   *_chunks_k    rows longer than GRAPES_LONG_ROW: one group per work item (row, chunk) of the prepared item list (item_range)
+//   *_combine_k   one workgroup per long row, led by its chunk-0 item (item_leads), merges the row's items in chunk order
+//
+// Device side: the slab layout of a row over a group's lanes, the group butterflies, the item-list readers and the batch-entry
+// reader.  Host side: the grids and the launch-by-width dispatch.  What a kernel accumulates, and its epilogue, stay in its file.
+#pragma once
+#include "common.h"
+
+template <int LPR>
+__device__ __forceinline__ float grp_sum(float v) {
+#pragma unroll
+    for (int d = LPR / 2; d > 0; d >>= 1) v += __shfl_xor(v, d, LPR);
+    return v;
+}
+template <int LPR>
+__device__ __forceinline__ float grp_max(float v) {
+#pragma unroll
+    for (int d = LPR / 2; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, LPR));
+    return v;
+}
+
+// VEC consecutive floats, VEC 4 (one 16-byte access, p aligned) or 1
+template <int VEC>
+__device__ __forceinline__ void vec_load(const float* __restrict__ p, float (&r)[VEC]) {
+    if constexpr (VEC == 4) {
+        const float4 t = *reinterpret_cast<const float4*>(p);
+        r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w;
+    } else {
+        r[0] = *p;
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void vec_store(float* __restrict__ p, const float (&r)[VEC]) {
+    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
+    else *p = r[0];
+}
+
+// lane l of a group holds columns (s LPR + l) VEC ... + VEC of a row, s < NS; columns at or beyond F read as zero
+template <int VEC, int LPR, int NS>
+__device__ __forceinline__ void row_load(const float* __restrict__ base, long long row, int F, int l, float (&r)[NS][VEC]) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int f = (s * LPR + l) * VEC;
+        if (f < F) {
+            if (VEC == 4) {
+                const float4 t = *reinterpret_cast<const float4*>(base + row * F + f);
+                r[s][0] = t.x; r[s][VEC > 1 ? 1 : 0] = t.y; r[s][VEC > 2 ? 2 : 0] = t.z; r[s][VEC > 3 ? 3 : 0] = t.w;
+            } else {
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) r[s][v] = base[row * F + f + v];
+            }
+        } else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) r[s][v] = 0.f;
+        }
+    }
+}
+template <int VEC, int LPR, int NS>
+__device__ __forceinline__ void row_store(float* __restrict__ base, long long row, int F, int l, const float (&r)[NS][VEC]) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int f = (s * LPR + l) * VEC;
+        if (f < F) {
+            if (VEC == 4) *reinterpret_cast<float4*>(base + row * F + f) = make_float4(r[s][0], r[s][VEC > 1 ? 1 : 0], r[s][VEC > 2 ? 2 : 0], r[s][VEC > 3 ? 3 : 0]);
+            else {
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) base[row * F + f + v] = r[s][v];
+            }
+        }
+    }
+}
+
+// the live length of a long-row item list: the device count, at most the list's capacity
+__device__ __forceinline__ int item_count(const int32_t* __restrict__ d_n_items, int item_cap) {
+    const int n_items = *d_n_items;
+    return n_items > item_cap ? item_cap : n_items;
+}
+
+// Work item `it` = (row, chunk): entries [beg, end) of the row, GRAPES_LONG_ROW of them at most.  False for an item that names no
+// row below n or a negative chunk; a chunk that starts at or past the row's end (formed in 64 bits) is an empty range.
+__device__ __forceinline__ bool item_range(const int32_t* __restrict__ items, int it, const int32_t* __restrict__ rowptr, int n,
+                                           int& row, int& beg, int& end) {
+    row = items[2 * it];
+    const int chunk = items[2 * it + 1];
+    beg = 0; end = 0;
+    if (!((unsigned)row < (unsigned)n && chunk >= 0)) return false;
+    const int rbeg = rowptr[row], rend = rowptr[row + 1];
+    const long long cb = (long long)rbeg + (long long)chunk * GRAPES_LONG_ROW;
+    if (cb < rend) {
+        beg = (int)cb;
+        end = beg + GRAPES_LONG_ROW < rend ? beg + GRAPES_LONG_ROW : rend;
+    }
+    return true;
+}
+
+// The item with chunk 0 leads its row: its nc items are contiguous and in chunk order (nc stays inside the list).  True for such
+// an item of a row below n.
+__device__ __forceinline__ bool item_leads(const int32_t* __restrict__ items, int it, int n_items, const int32_t* __restrict__ rowptr,
+                                           int n, int& row, int& nc) {
+    if (items[2 * it + 1] != 0) return false;
+    row = items[2 * it];
+    if ((unsigned)row >= (unsigned)n) return false;
+    nc = (rowptr[row + 1] - rowptr[row] + GRAPES_LONG_ROW - 1) / GRAPES_LONG_ROW;
+    if (it + nc > n_items) nc = n_items - it;
+    return true;
+}
+
+// Entry t of a walk that ends at `end`: its column index, or -1 past the end and for an index outside [0, n), which raises
+// GRAPES_STATUS_BAD_INDEX (the entry is dropped).  Lane l of a group calls it with t = b + l for the batch at b.
+__device__ __forceinline__ int batch_entry(const int32_t* __restrict__ csr, int t, int end, int n, int32_t* status) {
+    int idx = -1;
+    if (t < end) {
+        const int c = csr[t];
+        if ((unsigned)c < (unsigned)n) idx = c;
+        else if (status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+    }
+    return idx;
+}
+
+// ------------------------------------------------------------------------------------------------------------ host side
+
+static inline int row_grid(int rows, int lanes) {
+    int g = grapes_div_up(rows > 0 ? rows : 1, 256 / lanes);
+    return g > 16384 ? 16384 : g;
+}
+static inline int flat_grid(int64_t n, int64_t f, int vec) {
+    int64_t g = (n * f / vec + 255) / 256;
+    return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
+}
+
+// KERNEL<VEC, LPR, NS> over `rows` rows or work items, a group of LPR lanes each: lanes per row and slabs per lane by width —
+// float4 columns (vec: f % 4 == 0, 16-byte aligned rows) up to 1024, scalar ones up to 256 and, with NS_WIDE slabs, beyond
+// (NS_WIDE = 4: the caller refuses those widths, and nothing wider than <1, 64, 4> is instantiated).
+#define ROW_LAUNCH(KERNEL, NS_WIDE, vec, f, rows, s, ...)                                                                   \
+    do {                                                                                                                    \
+        const dim3 g32_(row_grid(rows, 32)), g64_(row_grid(rows, 64));                                                      \
+        if (vec) {                                                                                                          \
+            if ((f) <= 128) hipLaunchKernelGGL((KERNEL<4, 32, 1>), g32_, dim3(256), 0, s, __VA_ARGS__);                      \
+            else if ((f) <= 256) hipLaunchKernelGGL((KERNEL<4, 64, 1>), g64_, dim3(256), 0, s, __VA_ARGS__);                 \
+            else hipLaunchKernelGGL((KERNEL<4, 64, 4>), g64_, dim3(256), 0, s, __VA_ARGS__);                                 \
+        } else {                                                                                                            \
+            if ((f) <= 32) hipLaunchKernelGGL((KERNEL<1, 32, 1>), g32_, dim3(256), 0, s, __VA_ARGS__);                       \
+            else if ((f) <= 64) hipLaunchKernelGGL((KERNEL<1, 64, 1>), g64_, dim3(256), 0, s, __VA_ARGS__);                  \
+            else if ((f) <= 256) hipLaunchKernelGGL((KERNEL<1, 64, 4>), g64_, dim3(256), 0, s, __VA_ARGS__);                 \
+            else hipLaunchKernelGGL((KERNEL<1, 64, NS_WIDE>), g64_, dim3(256), 0, s, __VA_ARGS__);                           \
+        }                                                                                                                   \
+        GRAPES_LAUNCH_CHECK();                                                                                              \
+    } while (0)
+
+// KERNEL<VEC, LPR> for kernels that walk a row once per column tile of LPR * VEC features: any f >= 1
+#define ROW_LAUNCH_TILED(KERNEL, vec, f, rows, s, ...)                                                                      \
+    do {                                                                                                                    \
+        const dim3 g32_(row_grid(rows, 32)), g64_(row_grid(rows, 64));                                                      \
+        if (vec) {                                                                                                          \
+            if ((f) <= 128) hipLaunchKernelGGL((KERNEL<4, 32>), g32_, dim3(256), 0, s, __VA_ARGS__);                         \
+            else hipLaunchKernelGGL((KERNEL<4, 64>), g64_, dim3(256), 0, s, __VA_ARGS__);                                    \
+        } else {                                                                                                            \
+            if ((f) <= 32) hipLaunchKernelGGL((KERNEL<1, 32>), g32_, dim3(256), 0, s, __VA_ARGS__);                          \
+            else hipLaunchKernelGGL((KERNEL<1, 64>), g64_, dim3(256), 0, s, __VA_ARGS__);                                    \
+        }                                                                                                                   \
+        GRAPES_LAUNCH_CHECK();                                                                                              \
+    } while (0)

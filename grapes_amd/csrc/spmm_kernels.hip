@@ -1627,7 +1627,6 @@ __global__ __launch_bounds__(256) void gcn_aggregate_narrow_multi_k(NarrowSegs s
 
 #ifndef GRAPES_ALIGNED16_DEFINED
 #define GRAPES_ALIGNED16_DEFINED
-static inline bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 #endif
 
 static int narrow_lane_rows_cfg() {     // rows up to this length are walked by ONE lane (GRAPES_NARROW_LANE_ROWS)
@@ -1650,7 +1649,7 @@ static int launch_aggregate_t(const float* h, const int32_t* rowptr, const int32
         return 0;
     }
     int grid = grapes_div_up(n, 4); if (grid > 16384) grid = 16384;
-    const bool vec = (f % 4 == 0) && aligned16(h) && aligned16(out) && (!bias || aligned16(bias)) && (!partials || aligned16(partials));
+    const bool vec = (f % 4 == 0) && grapes_aligned16(h) && grapes_aligned16(out) && (!bias || grapes_aligned16(bias)) && (!partials || grapes_aligned16(partials));
     if (PRE && !vec) return GRAPES_EALIGN;
     const int skip = (items && d_n_items && partials && item_cap > 0) ? 1 : 0;
     // item-scheduled (full-graph) aggregation of rows narrower than 1 KiB: lanes in slots (gcn_aggregate_lpr_k)
@@ -1740,7 +1739,7 @@ extern "C" int grapes_scale_rows(const float* h, const float* dinv, float* hs, i
     if (n < 0 || f <= 0 || (f & 3)) return GRAPES_EINVAL;
     if (n == 0) return 0;
     if (!h || !dinv || !hs) return GRAPES_EINVAL;
-    if (!aligned16(h) || !aligned16(hs)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(h) || !grapes_aligned16(hs)) return GRAPES_EALIGN;
     long long blocks = (n * (f >> 2) + 255) / 256; if (blocks > 16384) blocks = 16384;
     hipLaunchKernelGGL(scale_rows_k, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const float4*)h, dinv, (float4*)hs,
                        (long long)n, f >> 2);
@@ -2096,7 +2095,7 @@ extern "C" int grapes_gcn_aggregate_fwd_head(const float* h, const int32_t* rowp
     if (gate_bits && (f > 256 || !relu)) return GRAPES_EINVAL;
     if (n == 0) return 0;
     if (!h || !rowptr_t || !dinv || !out || !head_w || !head_out) return GRAPES_EINVAL;
-    if (!aligned16(h) || !aligned16(out) || (bias && !aligned16(bias)) || !aligned16(head_w)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(h) || !grapes_aligned16(out) || (bias && !grapes_aligned16(bias)) || !grapes_aligned16(head_w)) return GRAPES_EALIGN;
     int grid = grapes_div_up(n, 4); if (grid > 16384) grid = 16384;
     hipLaunchKernelGGL((gcn_aggregate_k<4, 3>), dim3(grid), dim3(256), 0, (hipStream_t)stream, h, rowptr_t, csr_src, dinv, bias, out,
                        n, d_n, f, relu, 0, f >= 64 ? grapes_clock_reserve("gcn_aggregate_k<4>", grid, 4) : nullptr,
@@ -2115,7 +2114,7 @@ extern "C" int grapes_gcn_aggregate_fwd_rec(const float* h, const int32_t* row_h
     if (gate_bits && (!relu || !head_w)) return GRAPES_EINVAL;
     if (n == 0) return 0;
     if (!h || !row_head || !rowptr_t || !csr_src || !dinv || !out || (head_w && !head_out)) return GRAPES_EINVAL;
-    if (!aligned16(h) || !aligned16(out) || !aligned16(row_head) || (bias && !aligned16(bias)) || (head_w && !aligned16(head_w))) return GRAPES_EALIGN;
+    if (!grapes_aligned16(h) || !grapes_aligned16(out) || !grapes_aligned16(row_head) || (bias && !grapes_aligned16(bias)) || (head_w && !grapes_aligned16(head_w))) return GRAPES_EALIGN;
     // resident wavefronts that loop over pairs of rows: up to 2048 workgroups of 4 wavefronts (sweep 768 .. 4096 on Reddit: profiles/r04_workloads.txt)
     static int gcap = 0;
     if (!gcap) { const char* e = grapes_tune_env("GRAPES_AGG_REC_GRID"); gcap = e ? atoi(e) : 2048; if (gcap < 32) gcap = 2048; }
@@ -2234,7 +2233,7 @@ static int bwd_rank1_impl(const float* act, const uint32_t* gate_bits, const flo
         return 0;
     }
     if (!act || !dh2 || !w2 || !rowptr_s || !dinv || !dh || !workspace) return GRAPES_EINVAL;
-    if (!aligned16(act) || !aligned16(dh)) return GRAPES_EALIGN;
+    if (!grapes_aligned16(act) || !grapes_aligned16(dh)) return GRAPES_EALIGN;
     float* pa = (float*)workspace;
     float* pb = pa + (size_t)CS_BLOCKS * f;
     float* partials = pb + (size_t)CS_BLOCKS * f;
@@ -2248,7 +2247,7 @@ static int bwd_rank1_impl(const float* act, const uint32_t* gate_bits, const flo
     const R1 r1{dh2, w2};
     int grid = grapes_div_up(n, 4); if (grid > 16384) grid = 16384;
     const int skip = (long_items && d_n_items && item_cap > 0) ? 1 : 0;
-    if (skip && !aligned16(partials)) return GRAPES_EALIGN;
+    if (skip && !grapes_aligned16(partials)) return GRAPES_EALIGN;
     if (gate_bits) {     // the gates from 32 bytes of bits per row (MODE 4) instead of the activation rows
         static int cap = 0;
         if (!cap) { const char* e = grapes_tune_env("GRAPES_R1BITS_GRID"); cap = e ? atoi(e) : 2048; if (cap < 1) cap = 2048; }
@@ -2420,7 +2419,7 @@ extern "C" int grapes_gcn_aggregate_bwd_rank1_bits_multi(int32_t count, const fl
         const int p = q < count ? q : 0;
         if (q < count) {
             if (n[p] <= 0 || !act[p] || !gate_bits[p] || !dh2[p] || !w2[p] || !rowptr_s[p] || !dinv[p] || !dh[p] || !workspace[p]) return GRAPES_EINVAL;
-            if (!aligned16(act[p]) || !aligned16(dh[p]) || !aligned16(workspace[p])) return GRAPES_EALIGN;
+            if (!grapes_aligned16(act[p]) || !grapes_aligned16(dh[p]) || !grapes_aligned16(workspace[p])) return GRAPES_EALIGN;
             if ((dw2[p] == nullptr) != (db1[p] == nullptr)) return GRAPES_EINVAL;
         }
         m.act[q] = act[p]; m.bits[q] = gate_bits[p]; m.dh2[q] = dh2[p]; m.w2[q] = w2[p]; m.rowptr[q] = rowptr_s[p]; m.csr[q] = csr_dst[p];
@@ -2481,7 +2480,7 @@ extern "C" int grapes_gcn_aggregate_bwd(const float* dout, const float* relu_out
     const bool need_pass = (relu_out != nullptr) || (dbias != nullptr) || (dpre_buf != dout);
     if ((need_pass || long_items) && !workspace) return GRAPES_EINVAL;
     {   // few rows: mask, bias gradient and aggregation in ONE launch (dpre_buf is then not written)
-        const bool vec = (f % 4 == 0) && aligned16(dout) && aligned16(dh) && (!relu_out || aligned16(relu_out));
+        const bool vec = (f % 4 == 0) && grapes_aligned16(dout) && grapes_aligned16(dh) && (!relu_out || grapes_aligned16(relu_out));
         const int VECW = vec ? 4 : 1;
         if (d_ticket && !long_items && n <= CS_SMALL_ROWS && f > 16 && f <= 64 * VECW && grapes_div_up(f, 64) <= 16 && (relu_out || dbias)) {
             const int ncb = grapes_div_up(f, 64);

@@ -271,11 +271,23 @@ class _GATConvFn(torch.autograd.Function):
         return dx, dw, da_src.view_as(att_src), da_dst.view_as(att_dst), dbias, None, None
 
 
+def _cuda_f32(x, who: str):
+    """A layer's input as the kernels take it: on the device (there is no CPU path), contiguous, fp32."""
+    if not x.is_cuda:
+        raise ops._lib.GrapesHipError(f"{who} input must be a cuda tensor (grapes_amd has no CPU path)")
+    x = x.contiguous()
+    return x if x.dtype == torch.float32 else x.float()
+
+
+def _refuse_large(edge_index, who: str):
+    if hasattr(edge_index, "full_graph_plan") and full_graph.use_large_path(edge_index, None):
+        raise ValueError(f"{who} over a graph with 2^31 or more entries is not built: the row-blocked 64-bit path of "
+                         "full_graph.py is GCN only")
+
+
 def _gat_graph(edge_index, n: int) -> ops.PreparedGraph:
     """The layer's graph: a PreparedGraph, an edge-index tensor, or a DeviceGraph below 2^31 entries."""
-    if hasattr(edge_index, "full_graph_plan") and full_graph.use_large_path(edge_index, None):
-        raise ValueError("GAT over a graph with 2^31 or more entries is not built: the row-blocked 64-bit path of "
-                         "full_graph.py is GCN only")
+    _refuse_large(edge_index, "GAT")
     return prepare_edges(edge_index, n)
 
 
@@ -308,11 +320,7 @@ class GATConv(nn.Module):
             self.bias.zero_()
 
     def forward(self, x, edge_index, relu: bool = False):
-        if not x.is_cuda:
-            raise ops._lib.GrapesHipError("GATConv input must be a cuda tensor (grapes_amd has no CPU path)")
-        x = x.contiguous()
-        if x.dtype != torch.float32:
-            x = x.float()
+        x = _cuda_f32(x, "GATConv")
         prep = _gat_graph(edge_index, x.shape[0])
         return _GATConvFn.apply(x, self.lin.weight, self.att_src, self.att_dst, self.bias, prep, relu)
 
@@ -383,12 +391,7 @@ class Linear(nn.Module):
         nn.init.uniform_(self.bias, -bound, bound)
 
     def forward(self, x, relu: bool = False):
-        if not x.is_cuda:
-            raise ops._lib.GrapesHipError("Linear input must be a cuda tensor (grapes_amd has no CPU path)")
-        x = x.contiguous()
-        if x.dtype != torch.float32:
-            x = x.float()
-        return _LinearFn.apply(x, self.weight, self.bias, relu)
+        return _LinearFn.apply(_cuda_f32(x, "Linear"), self.weight, self.bias, relu)
 
 
 class _GCN2ConvFn(torch.autograd.Function):
@@ -437,9 +440,7 @@ def _gcn2_graph(edge_index, n: int) -> ops.PreparedGraph:
     """The layer's graph WITH its stored-self-loop counts: a PreparedGraph that carries them (ops.gcn2_attach_loops), an
     edge-index tensor (counted once, cached beside the prepared graph) or a DeviceGraph below 2^31 entries (counted from its CSR)."""
     if hasattr(edge_index, "full_graph_plan"):                 # graph.DeviceGraph
-        if full_graph.use_large_path(edge_index, None):
-            raise ValueError("GCN2 over a graph with 2^31 or more entries is not built: the row-blocked 64-bit path of "
-                             "full_graph.py is GCN only")
+        _refuse_large(edge_index, "GCN2")
         prep = edge_index.gcn_prepared()
         if getattr(prep, "loops", None) is None:
             prep.loops = ops.gcn2_loop_counts_csr(edge_index.rowptr, edge_index.col, edge_index.num_nodes)
@@ -490,11 +491,7 @@ class GCN2Conv(nn.Module):
                              "(the only case modules/gcn.py:104-113 produces)")
         if x.shape[1] != self.channels:
             raise ValueError(f"GCN2Conv: width {x.shape[1]} != channels {self.channels}")
-        x, x_0 = x.contiguous(), x_0.contiguous()
-        if x.dtype != torch.float32:
-            x = x.float()
-        if x_0.dtype != torch.float32:
-            x_0 = x_0.float()
+        x, x_0 = _cuda_f32(x, "GCN2Conv"), _cuda_f32(x_0, "GCN2Conv")
         prep = _gcn2_graph(edge_index, x.shape[0])
         return _GCN2ConvFn.apply(x, x_0, self.weight1, self.weight2, prep, self.alpha, self.beta, relu)
 
@@ -596,9 +593,7 @@ class _PNAConvFn(torch.autograd.Function):
 
 def _pna_graph(edge_index, n: int) -> ops.PreparedGraph:
     """The layer's graph with its stored-self-loop counts (PNAConv aggregates the adjacency as stored, like GCN2Conv)."""
-    if hasattr(edge_index, "full_graph_plan") and full_graph.use_large_path(edge_index, None):
-        raise ValueError("PNA over a graph with 2^31 or more entries is not built: the row-blocked 64-bit path of "
-                         "full_graph.py is GCN only")
+    _refuse_large(edge_index, "PNA")
     return _gcn2_graph(edge_index, n)
 
 
@@ -635,13 +630,9 @@ class PNAConv(nn.Module):
             m.reset_parameters()
 
     def forward(self, x, edge_index, relu: bool = False):
-        if not x.is_cuda:
-            raise ops._lib.GrapesHipError("PNAConv input must be a cuda tensor (grapes_amd has no CPU path)")
+        x = _cuda_f32(x, "PNAConv")
         if x.shape[1] != self.in_channels:
             raise ValueError(f"PNAConv: width {x.shape[1]} != in_channels {self.in_channels}")
-        x = x.contiguous()
-        if x.dtype != torch.float32:
-            x = x.float()
         prep = _pna_graph(edge_index, x.shape[0])
         return _PNAConvFn.apply(x, self.pre_nn.weight, self.pre_nn.bias, self.post_nn.weight, self.post_nn.bias, self.lin.weight,
                                 self.lin.bias, prep, self.cfg, relu)

@@ -1498,6 +1498,15 @@ def _gat_width(f: int):
         raise ValueError(f"GAT aggregation: width {f} is not built (any width up to 256, multiples of 4 up to 1024)")
 
 
+def _long_items(prep, by_target: bool, forward: bool):
+    """(items, n_items, cap) as the row-gather entry points take them: prep's long-row work items by target or by source, or
+    (None, None, 0) where every row runs in the rows kernel — a small graph, or a forward over a graph prepared without them."""
+    if prep.n <= _SMALL_GRAPH or (forward and not prep.items_fwd):
+        return None, None, 0
+    items, n_items = (prep.items_t, prep.n_items_t) if by_target else (prep.items_s, prep.n_items_s)
+    return _p(items), _p(n_items), prep.item_cap
+
+
 def gat_scores(h, a_src, a_dst, d_n=None):
     """(s_src, s_dst) = (H a_src, H a_dst): the per-node halves of GATConv's attention logits, one read of H."""
     _chk(h, _f32, "h"); _chk(a_src, _f32, "a_src"); _chk(a_dst, _f32, "a_dst")
@@ -1523,14 +1532,11 @@ def gat_aggregate_fwd(h, s_src, s_dst, prep: PreparedGraph, bias=None, relu=Fals
     if out is None:
         out = torch.empty_like(h)
     row_ms = torch.empty((max(n, 1), 2), dtype=_f32, device=h.device)
-    use_items = prep.items_fwd and prep.n > _SMALL_GRAPH
-    ws = _ws(lib().grapes_gat_aggregate_workspace_bytes(prep.item_cap, f), h.device) if use_items else None
+    items, n_items, cap = _long_items(prep, by_target=True, forward=True)
+    ws = _ws(lib().grapes_gat_aggregate_workspace_bytes(cap, f), h.device) if cap else None
     _lib.check(lib().grapes_gat_aggregate_fwd(_p(h), _p(s_src), _p(s_dst), _p(prep.rowptr_t), _p(prep.csr_src), _p(bias), _p(out),
-                                              _p(row_ms), n, _p(prep.d_n), f, 1 if relu else 0,
-                                              _p(prep.items_t) if use_items else None,
-                                              _p(prep.n_items_t) if use_items else None,
-                                              prep.item_cap if use_items else 0, _p(ws), _p(prep.status), _stream()),
-               "gat_aggregate_fwd")
+                                              _p(row_ms), n, _p(prep.d_n), f, 1 if relu else 0, items, n_items, cap, _p(ws),
+                                              _p(prep.status), _stream()), "gat_aggregate_fwd")
     return out, row_ms
 
 
@@ -1549,15 +1555,14 @@ def gat_aggregate_bwd(dout, out, h, s_src, s_dst, row_ms, a_src, a_dst, prep: Pr
     dh = torch.empty_like(dout)
     da_src = torch.empty(f, dtype=_f32, device=dev); da_dst = torch.empty(f, dtype=_f32, device=dev)
     dbias = torch.empty(f, dtype=_f32, device=dev)
-    use_items = prep.n > _SMALL_GRAPH
-    cap = prep.item_cap if use_items else 0
+    items_t, n_items_t, cap = _long_items(prep, by_target=True, forward=False)
+    items_s, n_items_s, _ = _long_items(prep, by_target=False, forward=False)
     ws = _ws(lib().grapes_gat_aggregate_bwd_workspace_bytes(n, cap, f), dev)
     _lib.check(lib().grapes_gat_aggregate_bwd(_p(dout), _p(out), _p(bias), 1 if relu else 0, _p(h), _p(s_src), _p(s_dst), _p(row_ms),
                                               _p(a_src), _p(a_dst), _p(prep.rowptr_t), _p(prep.csr_src), _p(prep.rowptr_s),
                                               _p(prep.csr_dst), _p(dh), _p(da_src), _p(da_dst), _p(dbias), n, _p(prep.d_n), f,
-                                              _p(prep.items_t) if use_items else None, _p(prep.n_items_t) if use_items else None,
-                                              _p(prep.items_s) if use_items else None, _p(prep.n_items_s) if use_items else None,
-                                              cap, _p(ws), _p(prep.status), _stream()), "gat_aggregate_bwd")
+                                              items_t, n_items_t, items_s, n_items_s, cap, _p(ws), _p(prep.status), _stream()),
+               "gat_aggregate_bwd")
     return dh, da_src, da_dst, dbias
 
 
@@ -1609,12 +1614,10 @@ def gcn2_propagate_fwd(x, x0, prep: PreparedGraph, alpha: float, want_p: bool = 
     loops = gcn2_loops(prep)
     s_out = torch.empty_like(x)
     p_out = torch.empty_like(x) if want_p else None
-    use_items = prep.items_fwd and prep.n > _SMALL_GRAPH
-    cap = prep.item_cap if use_items else 0
-    ws = _ws(lib().grapes_gcn2_propagate_workspace_bytes(0, cap, f), x.device) if use_items else None
+    items, n_items, cap = _long_items(prep, by_target=True, forward=True)
+    ws = _ws(lib().grapes_gcn2_propagate_workspace_bytes(0, cap, f), x.device) if cap else None
     _lib.check(lib().grapes_gcn2_propagate_fwd(_p(x), _p(x0), _p(loops), _p(prep.rowptr_t), _p(prep.csr_src), float(alpha), _p(s_out),
-                                               _p(p_out), n, _p(prep.d_n), f, _p(prep.items_t) if use_items else None,
-                                               _p(prep.n_items_t) if use_items else None, cap, _p(ws), _p(prep.status),
+                                               _p(p_out), n, _p(prep.d_n), f, items, n_items, cap, _p(ws), _p(prep.status),
                                                _stream()), "gcn2_propagate_fwd")
     return s_out, p_out
 
@@ -1633,15 +1636,13 @@ def gcn2_propagate_bwd(ds, prep: PreparedGraph, alpha: float, ds_add=None, add_i
     accumulate = dx0 is not None
     if dx0 is None and want_x0:
         dx0 = torch.empty_like(ds)
-    use_items = prep.n > _SMALL_GRAPH
-    cap = prep.item_cap if use_items else 0
+    items, n_items, cap = _long_items(prep, by_target=False, forward=False)
     two = ds_add is not None or dx0_add is not None
-    ws = _ws(lib().grapes_gcn2_propagate_workspace_bytes(n if two else 0, cap, f), ds.device) if (two or use_items) else None
+    ws = _ws(lib().grapes_gcn2_propagate_workspace_bytes(n if two else 0, cap, f), ds.device) if (two or cap) else None
     _lib.check(lib().grapes_gcn2_propagate_bwd(_p(ds), _p(ds_add), 1 if add_is_p else 0, _p(dx0_add), _p(loops), _p(prep.rowptr_s),
                                                _p(prep.csr_dst), float(alpha), _p(dx), _p(dx0), 1 if accumulate else 0, n,
-                                               _p(prep.d_n), f, _p(prep.items_s) if use_items else None,
-                                               _p(prep.n_items_s) if use_items else None, cap, _p(ws), _p(prep.status),
-                                               _stream()), "gcn2_propagate_bwd")
+                                               _p(prep.d_n), f, items, n_items, cap, _p(ws), _p(prep.status), _stream()),
+               "gcn2_propagate_bwd")
     return dx, dx0
 
 
@@ -1711,14 +1712,12 @@ def pna_aggregate_fwd(x, ab, prep: PreparedGraph, cfg: PNAConfig):
     loops = gcn2_loops(prep)
     z = torch.empty((n, cfg.blocks * f), dtype=_f32, device=x.device)
     stats = torch.empty((n, PNA_NSTAT, f), dtype=_f32, device=x.device)
-    use_items = prep.items_fwd and prep.n > _SMALL_GRAPH
-    cap = prep.item_cap if use_items else 0
-    ws = _ws(lib().grapes_pna_aggregate_fwd_workspace_bytes(cap, f), x.device) if use_items else None
+    items, n_items, cap = _long_items(prep, by_target=True, forward=True)
+    ws = _ws(lib().grapes_pna_aggregate_fwd_workspace_bytes(cap, f), x.device) if cap else None
     _lib.check(lib().grapes_pna_aggregate_fwd(_p(x), _p(ab), ab.data_ptr() + 4 * f, 2 * f, _p(loops), _p(prep.rowptr_t),
                                               _p(prep.csr_src), cfg.n_agg, cfg.agg_code, cfg.n_scal, cfg.scal_code, cfg.avg_log,
-                                              cfg.avg_lin, _p(z), _p(stats), n, _p(prep.d_n), f,
-                                              _p(prep.items_t) if use_items else None, _p(prep.n_items_t) if use_items else None,
-                                              cap, _p(ws), _p(prep.status), _stream()), "pna_aggregate_fwd")
+                                              cfg.avg_lin, _p(z), _p(stats), n, _p(prep.d_n), f, items, n_items, cap, _p(ws),
+                                              _p(prep.status), _stream()), "pna_aggregate_fwd")
     return z, stats
 
 
@@ -1732,14 +1731,12 @@ def pna_aggregate_bwd(dz, ab, stats, prep: PreparedGraph, cfg: PNAConfig):
         raise ValueError("dz must be [n, blocks * f] and stats [n, 6, f] over the prepared graph's nodes")
     loops = gcn2_loops(prep)
     dab = torch.empty_like(ab)
-    use_items = prep.n > _SMALL_GRAPH
-    cap = prep.item_cap if use_items else 0
+    items, n_items, cap = _long_items(prep, by_target=False, forward=False)
     ws = _ws(lib().grapes_pna_aggregate_bwd_workspace_bytes(n, cap, f), dz.device)
     _lib.check(lib().grapes_pna_aggregate_bwd(_p(dz), ab.data_ptr() + 4 * f, 2 * f, _p(stats), _p(loops), _p(prep.rowptr_t),
                                               _p(prep.rowptr_s), _p(prep.csr_dst), cfg.n_agg, cfg.agg_code, cfg.n_scal,
                                               cfg.scal_code, cfg.avg_log, cfg.avg_lin, _p(dab), dab.data_ptr() + 4 * f, 2 * f, n,
-                                              _p(prep.d_n), f, _p(prep.items_s) if use_items else None,
-                                              _p(prep.n_items_s) if use_items else None, cap, _p(ws), _p(prep.status), _stream()),
+                                              _p(prep.d_n), f, items, n_items, cap, _p(ws), _p(prep.status), _stream()),
                "pna_aggregate_bwd")
     return dab
 

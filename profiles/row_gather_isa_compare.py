@@ -1,0 +1,92 @@
+#!/usr/bin/env python3
+"""Same machine code?  Compiles gat_kernels.hip, gcn2_kernels.hip and pna_kernels.hip of two source trees for the device only
+(the Makefile's flags + --cuda-device-only -S, no GPU needed) and compares the gfx950 assembly kernel by kernel.
+
+    python profiles/row_gather_isa_compare.py PARENT_CSRC [RESULT_CSRC] > profiles/row_gather_isa_compare.txt
+
+  - every kernel symbol of the parent must exist in the result, and no new one may appear;
+  - a kernel's instruction stream is compared after comments are dropped and basic-block labels renumbered in order of appearance;
+  - the three GAT *_chunks_k families took the strict item decode on purpose: for them the register, scratch and LDS counts of
+    the code object's metadata must not rise;
+  - every other kernel that differs is listed with its counts; the diff itself is printed for the first instantiation of each
+    kernel template (the others of a template differ the same way; --all-diffs prints them all).
+Exit status 1 when a symbol is missing or new or a count of a GAT *_chunks_k kernel rises."""
+import difflib
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "--cuda-device-only", "-S"]
+FILES = ["gat_kernels.hip", "gcn2_kernels.hip", "pna_kernels.hip"]
+EXPECTED = ("gat_fwd_chunks_k", "gat_bwd_dst_chunks_k", "gat_bwd_src_chunks_k")
+COUNTS = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size")
+
+
+def assembly(csrc, name, tmp):
+    out = os.path.join(tmp, name + ".s")
+    subprocess.run([HIPCC] + FLAGS + [os.path.join(csrc, name), "-o", out], check=True)
+    return open(out).read()
+
+
+def kernels(text):
+    """{symbol: (normalised instruction lines, {count: value})}"""
+    meta = {}
+    for blk in text.split("- .agpr_count:")[1:]:
+        nm = re.search(r"\.name:\s+(\S+)", blk).group(1)
+        meta[nm] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1)) for k in COUNTS}
+    body = {}
+    for nm in meta:
+        m = re.search(r"^%s:[^\n]*\n(.*?)^\s*\.section\s" % re.escape(nm), text, re.S | re.M)
+        labels, lines = {}, []
+        for ln in m.group(1).split("\n"):
+            ln = ln.split(";")[0].rstrip()
+            if ln.strip():
+                lines.append(re.sub(r"\.LBB\d+_\d+", lambda t: labels.setdefault(t.group(0), ".L%d" % len(labels)), ln))
+        body[nm] = lines
+    return {nm: (body[nm], meta[nm]) for nm in meta}
+
+
+def main(parent, result, all_diffs=False):
+    bad, other, shown = 0, 0, set()
+    with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
+        for name in FILES:
+            a, b = kernels(assembly(parent, name, ta)), kernels(assembly(result, name, tb))
+            missing, new = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+            same = [k for k in a if k in b and a[k][0] == b[k][0]]
+            print(f"== {name}: {len(a)} kernels in the parent, {len(b)} in the result, {len(same)} with identical instruction streams")
+            for k in missing:
+                print("  MISSING in the result:", k)
+            for k in new:
+                print("  NEW in the result:", k)
+            bad += len(missing) + len(new)
+            for k in sorted(set(a) & set(b)):
+                if a[k][0] == b[k][0] and a[k][1] == b[k][1]:
+                    continue
+                expected = any(e in k for e in EXPECTED)
+                rises = [c for c in COUNTS if b[k][1][c] > a[k][1][c]]
+                print(f"  {'differs (strict item decode)' if expected else 'DIFFERS'}: {k}")
+                print(f"      instructions {len(a[k][0])} -> {len(b[k][0])}; " +
+                      ", ".join(f"{c} {a[k][1][c]} -> {b[k][1][c]}" for c in COUNTS) + ("; RISES: " + ", ".join(rises) if rises else ""))
+                if expected:
+                    bad += 1 if rises else 0
+                    continue
+                other += 1
+                diff = list(difflib.unified_diff(a[k][0], b[k][0], "parent", "result", lineterm="", n=1))
+                template = k.split("ILi")[0]
+                if all_diffs or template not in shown:
+                    print("\n".join("      " + d for d in diff))
+                else:
+                    print(f"      ({sum(d[0] == '-' for d in diff[2:])} lines removed, {sum(d[0] == '+' for d in diff[2:])} added: like the template's first instantiation above)")
+                shown.add(template)
+    print(f"result: {'FAIL' if bad else 'ok'} (symbols equal and no count of a GAT *_chunks_k kernel rises); "
+          f"{other} other kernels differ, listed above")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    here = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "grapes_amd", "csrc")
+    args = [a for a in sys.argv[1:] if a != "--all-diffs"]
+    sys.exit(main(args[0], args[1] if len(args) > 1 else here, all_diffs="--all-diffs" in sys.argv))

@@ -149,6 +149,84 @@ def test_captured_forward_backward_replays_bit_identically():
     assert int(prep.status.item()) == 0 if prep.status is not None else True
 
 
+@pytest.mark.parametrize("c", [64, 47])
+def test_long_rows_on_both_csrs_and_device_row_count(c):
+    """A hub as target AND as source on a graph large enough for the work-item path (n > 2048): rows longer than GRAPES_LONG_ROW on
+    both CSRs, so the by-source chunk and combine kernels run as well; the hub row is measured on its own and with all rows.  Then
+    the same launches with d_n below the allocated rows leave the rows past it untouched."""
+    _need_gpu()
+    from grapes_amd import ops
+    n, hub = 2600, 5
+    rng = np.random.default_rng(71)
+    base = O.random_graph(n, seed=72, mean_deg=4, hub=hub, hub_deg=900, n_dup=20, n_loops=30, n_isolated=10)
+    out_edges = np.stack([np.full(700, hub), rng.integers(0, n - 10, 700)])          # the hub as source
+    ei = np.concatenate([base, out_edges, np.array([[hub, hub], [hub, hub]]).T.reshape(2, -1)], axis=1).astype(np.int64)
+    indeg, outdeg = np.bincount(ei[1][ei[0] != ei[1]], minlength=n), np.bincount(ei[0][ei[0] != ei[1]], minlength=n)
+    assert indeg[hub] > 64 * 8 and outdeg[hub] > 64 * 8
+    g = torch.Generator().manual_seed(73)
+    h, G = torch.randn(n, c, generator=g), torch.randn(n, c, generator=g)
+    a_s, a_d = (torch.rand(c, generator=g) * 2 - 1) * 0.3, (torch.rand(c, generator=g) * 2 - 1) * 0.3
+    b = (torch.rand(c, generator=g) * 2 - 1) * 0.1
+    eye = torch.eye(c, dtype=O.F64)                                                    # (W = I: the oracle's H is h itself)
+
+    def oracle(m, edges):
+        args = (h[:m].double(), eye, a_s.double(), a_d.double(), b.double(), edges)
+        r = O.gat_conv(*args, full=True)
+        raw = float(r["raw"].abs().min())
+        print(f"c {c} rows {m}: edges {r['src'].numel()}, min|raw| {raw:.2e}")
+        assert raw > 1e-5                                                             # no edge sits on LeakyReLU's kink in the oracle
+        return r["out"], O.gat_conv_grads(*args, G[:m].double())
+
+    def check(name, rows, got, ref, gr):
+        out, dh, da_src, da_dst, db = (t.cpu() for t in got)
+        errs = {"out": O.rel_err(out[rows], ref[rows]), "dh": O.rel_err(dh[rows], gr["dH"][rows])}
+        if name[:3] != "hub":                                                         # (the parameter gradients are sums over all rows)
+            errs.update(da_src=O.rel_err(da_src, gr["da_src"]), da_dst=O.rel_err(da_dst, gr["da_dst"]), db=O.rel_err(db, gr["db"]))
+        print(f"c {c} rows {name}:", {k: f"{v:.2e}" for k, v in errs.items()})
+        assert errs.pop("out") <= ACT_TOL
+        assert all(v <= GRAD_TOL for v in errs.values()), errs
+
+    ref, gr = oracle(n, ei)
+    src, dst = (torch.from_numpy(ei[k]).int().cuda().contiguous() for k in (0, 1))
+    prep = ops.PreparedGraph(src, dst, n)
+    assert int(prep.n_items_t.item()) > 8 and int(prep.n_items_s.item()) > 8
+    hd, Gd, asd, add, bd = h.cuda(), G.cuda(), a_s.cuda(), a_d.cuda(), b.cuda()
+    s_src, s_dst = ops.gat_scores(hd, asd, add)
+    out, row_ms = ops.gat_aggregate_fwd(hd, s_src, s_dst, prep, bd)
+    got = (out,) + tuple(ops.gat_aggregate_bwd(Gd, out, hd, s_src, s_dst, row_ms, asd, add, prep, bd))
+    for rows, name in ((torch.arange(n) == hub, "hub"), (torch.ones(n, dtype=torch.bool), "all")):
+        check(name, rows, got, ref, gr)
+    # d_n < allocated rows: a graph over the first m nodes, buffers of n rows pre-filled with a mark
+    m = 2100
+    em = ei[:, (ei[0] < m) & (ei[1] < m)]
+    refm, grm = oracle(m, em)
+    d_n = torch.tensor([m], dtype=torch.int32, device="cuda")
+    srcm, dstm = (torch.from_numpy(em[k]).int().cuda().contiguous() for k in (0, 1))
+    prepm = ops.PreparedGraph(srcm, dstm, n, d_n=d_n)
+    assert int(prepm.n_items_t.item()) > 8 and int(prepm.n_items_s.item()) > 8
+    L, P_, mark = ops.lib(), ops._p, 12345.0
+    oo, dho = torch.full((n, c), mark, device="cuda"), torch.full((n, c), mark, device="cuda")
+    sso, sdo = torch.full((n,), mark, device="cuda"), torch.full((n,), mark, device="cuda")
+    rmo = torch.full((n, 2), mark, device="cuda")
+    dpar = [torch.empty(c, device="cuda") for _ in range(3)]
+    ws = ops._ws(max(L.grapes_gat_aggregate_workspace_bytes(prepm.item_cap, c),
+                     L.grapes_gat_aggregate_bwd_workspace_bytes(n, prepm.item_cap, c)), "cuda")
+    assert L.grapes_gat_scores(P_(hd), P_(asd), P_(add), P_(sso), P_(sdo), n, P_(d_n), c, ops._stream()) == 0
+    assert L.grapes_gat_aggregate_fwd(P_(hd), P_(sso), P_(sdo), P_(prepm.rowptr_t), P_(prepm.csr_src), P_(bd), P_(oo), P_(rmo), n,
+                                      P_(d_n), c, 0, P_(prepm.items_t), P_(prepm.n_items_t), prepm.item_cap, P_(ws), None,
+                                      ops._stream()) == 0
+    assert L.grapes_gat_aggregate_bwd(P_(Gd), P_(oo), P_(bd), 0, P_(hd), P_(sso), P_(sdo), P_(rmo), P_(asd), P_(add),
+                                      P_(prepm.rowptr_t), P_(prepm.csr_src), P_(prepm.rowptr_s), P_(prepm.csr_dst), P_(dho),
+                                      P_(dpar[0]), P_(dpar[1]), P_(dpar[2]), n, P_(d_n), c, P_(prepm.items_t), P_(prepm.n_items_t),
+                                      P_(prepm.items_s), P_(prepm.n_items_s), prepm.item_cap, P_(ws), None, ops._stream()) == 0
+    torch.cuda.synchronize()
+    gotm = (oo[:m], dho[:m], dpar[0], dpar[1], dpar[2])
+    for rows, name in ((torch.arange(m) == hub, "hub"), (torch.ones(m, dtype=torch.bool), "all")):
+        check(name + " (d_n)", rows, gotm, refm, grm)
+    for t in (oo, dho, sso, sdo, rmo):
+        assert bool((t[m:] == mark).all())                               # rows past d_n are untouched
+
+
 def test_two_layer_gat_on_prepared_graphs_matches_oracle():
     _need_gpu()
     from grapes_amd import ops
