@@ -77,6 +77,9 @@ SIGNATURES = {
     "grapes_saint_subgraph_workspace_bytes": (SZ, [I32]),
     "grapes_saint_subgraph": (I32, [P, P, P, P, P, I32, I32, P, P, P, P, P, P, P]),
     "grapes_saint_masked_loss": (I32, [P, I64, I32, P, P, I32, P, P, P, P, I64, P, P, P, P]),
+    # GraphSAINT's node and edge samplers (graphsaint.py:8)
+    "grapes_saint_edge_weights": (I32, [P, P, I32, I64, P, P, P, P, P]),
+    "grapes_saint_draw_nodes": (I32, [P, P, I32, I32, P, P, P, P, U64, U64, P, P, P, P, P, P, P, P]),
     # GATConv aggregation (modules/gcn.py:45-72)
     "grapes_gat_scores": (I32, [P, P, P, P, P, I32, P, I32, P]),
     "grapes_gat_aggregate_workspace_bytes": (SZ, [I32, I32]),

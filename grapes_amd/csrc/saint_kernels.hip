@@ -4,6 +4,14 @@
 //   saint_walk_nodes_k   ONE workgroup: B walks of L steps (torch_cluster random_walk, p = q = 1), then the ascending
 //                        duplicate-free node set of the B (L + 1) visited ids (walks.view(-1).unique()), sorted in LDS, its
 //                        count and node_map[node_idx[i]] = i; advances the device Philox offset last.
+//   saint_colcount_k / saint_blockw_k / saint_roww_scan_k   the edge sampler's one-time weight table (PyG GraphSAINTEdgeSampler:
+//                        entry (r, c) weighs colcount[r] + rowcount[c]): entries per column (int32 atomics), per row the inclusive
+//                        weight prefix of its 64-entry blocks, and (ONE workgroup) the exclusive prefix of the row weights
+//   saint_draw_k         one wavefront per draw of the node sampler (PyG GraphSAINTNodeSampler: the row of a uniform entry) or
+//                        the edge sampler: a 64-ary search of rowptr / roww, then of the row's block prefixes, then one scan of
+//                        the block's 64 recomputed weights — a draw never walks a hub row
+//   saint_unique_ids_k   ONE workgroup: the drawn ids' node set, count and node_map (the walk's tail, saint_sort_unique), then
+//                        advances the device Philox offset
 //   saint_edge_count_k   one wavefront per local row: entries of the row whose column is in the node set
 //   saint_edge_scan_k    ONE workgroup: exclusive scan of those counts -> local row pointers, edge count (clamped to e_cap)
 //   saint_edge_write_k   one wavefront per local row: the induced edges (local row, local column) in CSR order
@@ -15,6 +23,13 @@
 // philox4x32_10(off + i / 4, seed).  Root b (b < B) is (uint64(word b) * N) >> 32 — all 32 bits, so every node of a graph with
 // up to 2^32 nodes can be drawn.  The uniform of walk b's step t (t < L) is philox_uniform_at(seed, off, B + b L + t): 24 bits,
 // like torch.rand.  The launch advances *d_offset by ceil(B (L + 1) / 4) counters.
+//
+// RNG contract of the node and edge samplers (same stream): draw b (b < B) takes the 64-bit word (stream word 2b) << 32 | (stream
+// word 2b + 1) — both are words of philox4x32_10(off + b / 2, seed) — and t = mulhi64(word, total), an integer in [0, total):
+// total = nnz = rowptr[N] (node sampler) or the total weight roww[N] (edge sampler).  t selects the stored entry e whose weight
+// interval [cum(e - 1), cum(e)) holds it (cum: inclusive prefix of the entry weights in CSR order; all 1 for the node sampler), so an
+// entry of weight 0 is never drawn.  Integer arithmetic throughout: no float enters the choice.  saint_unique_ids_k advances
+// *d_offset by ceil(2 B / 4) counters after every workgroup of saint_draw_k has read it (the next launch on the stream).
 //
 // Membership of the node set is tested as a sparse set: v is in the set iff m = node_map[v] < count and node_idx[m] == v, so
 // node_map needs no clearing (stale entries of other nodes are never trusted).
@@ -41,6 +56,46 @@ __device__ __forceinline__ int saint_block_scan(int v, int* wsum, int* total) {
     *total = wsum[SAINT_THREADS / 64];
     __syncthreads();
     return inc;
+}
+
+// The tail the walk and the draw share (one workgroup of SAINT_THREADS): ids[0 .. M) in LDS, written by this workgroup and not yet
+// fenced; P = M rounded up to a power of two (<= SAINT_MAX_IDS).  Sorts them, writes their ascending duplicate-free set to node_idx
+// and node_map[node_idx[i]] = i, and returns the set's size to every thread.
+__device__ __forceinline__ int saint_sort_unique(int32_t* ids, int* wsum, int M, int P, int32_t* __restrict__ node_idx,
+                                                 int32_t* __restrict__ node_map) {
+    const int tid = threadIdx.x;
+    for (int i = M + tid; i < P; i += blockDim.x) ids[i] = 0x7fffffff;       // padding sorts last
+    __syncthreads();
+    // bitonic sort of the P (a power of two) ids
+    for (int k = 2; k <= P; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += blockDim.x) {
+                const int p = i ^ j;
+                if (p > i) {
+                    const int a = ids[i], c = ids[p];
+                    const bool up = (i & k) == 0;
+                    if ((a > c) == up) { ids[i] = c; ids[p] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // unique: thread t owns the contiguous chunk [t * per, (t + 1) * per)
+    const int per = (P + SAINT_THREADS - 1) / SAINT_THREADS;
+    const int lo = tid * per, hi = min(lo + per, M);
+    int heads = 0;
+    for (int i = lo; i < hi; ++i) heads += (i == 0 || ids[i] != ids[i - 1]) ? 1 : 0;
+    int total;
+    int pos = saint_block_scan(heads, wsum, &total) - heads;
+    for (int i = lo; i < hi; ++i) {
+        if (i == 0 || ids[i] != ids[i - 1]) {
+            const int v = ids[i];
+            node_idx[pos] = v;
+            node_map[v] = pos;
+            ++pos;
+        }
+    }
+    return total;
 }
 
 // torch_cluster random_walk step (CPU, p = q = 1): a node without neighbours stays; otherwise
@@ -83,40 +138,177 @@ __global__ __launch_bounds__(SAINT_THREADS) void saint_walk_nodes_k(
             ids[b * W + t + 1] = v;
         }
     }
-    for (int i = M + tid; i < P; i += blockDim.x) ids[i] = 0x7fffffff;       // padding sorts last
-    __syncthreads();
-    // bitonic sort of the P (a power of two) ids
-    for (int k = 2; k <= P; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P; i += blockDim.x) {
-                const int p = i ^ j;
-                if (p > i) {
-                    const int a = ids[i], c = ids[p];
-                    const bool up = (i & k) == 0;
-                    if ((a > c) == up) { ids[i] = c; ids[p] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    // unique: thread t owns the contiguous chunk [t * per, (t + 1) * per)
-    const int per = (P + SAINT_THREADS - 1) / SAINT_THREADS;
-    const int lo = tid * per, hi = min(lo + per, M);
-    int heads = 0;
-    for (int i = lo; i < hi; ++i) heads += (i == 0 || ids[i] != ids[i - 1]) ? 1 : 0;
-    int total;
-    int pos = saint_block_scan(heads, wsum, &total) - heads;
-    for (int i = lo; i < hi; ++i) {
-        if (i == 0 || ids[i] != ids[i - 1]) {
-            const int v = ids[i];
-            node_idx[pos] = v;
-            node_map[v] = pos;
-            ++pos;
-        }
-    }
+    const int total = saint_sort_unique(ids, wsum, M, P, node_idx, node_map);
     if (tid == 0) {
         *d_count = total;
         if (d_offset) *d_offset = off + (uint64_t)((M + 3) >> 2);
+    }
+}
+
+// ---------------------------------------------------------------------------------------- node and edge samplers
+// Weight of the stored entry (r, c): colcount[r] + rowcount[c] in uint32 (the launcher refuses 2^31 entries or more); a column
+// outside [0, N) weighs 0, so such an entry is never drawn.  The table kernel and the draw compute it with this one function.
+__device__ __forceinline__ uint32_t saint_entry_weight(const int64_t* __restrict__ rowptr, uint32_t colcount_r, int c, int N) {
+    if ((unsigned)c >= (unsigned)N) return 0u;
+    return colcount_r + (uint32_t)(rowptr[c + 1] - rowptr[c]);
+}
+
+__device__ __forceinline__ int64_t saint_wave_incl_scan64(int64_t v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int64_t o = __shfl_up(v, d, 64);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+// colcount[c] += 1 for every stored entry with column c (colcount zeroed by the launcher): int32 atomics, any order, one result
+__global__ __launch_bounds__(256) void saint_colcount_k(const int32_t* __restrict__ col, int64_t nnz, int N,
+                                                        int32_t* __restrict__ colcount, int32_t* status) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < nnz; j += stride) {
+        const int c = col[j];
+        if ((unsigned)c < (unsigned)N) atomicAdd(&colcount[c], 1);
+        else if (status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+    }
+}
+
+// one wavefront per row r: blockw[(rowptr[r] >> 6) + r + k] = weight of the row's entries [0, 64 (k + 1)) (inclusive prefix over its
+// 64-entry blocks); roww[r + 1] = the row's weight (saint_roww_scan_k turns these into the prefix over rows)
+__global__ __launch_bounds__(256) void saint_blockw_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N,
+                                                      const int32_t* __restrict__ colcount, int64_t* __restrict__ blockw,
+                                                      int64_t* __restrict__ roww) {
+    const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    if (r >= N) return;
+    const int64_t a = rowptr[r], e = rowptr[r + 1];
+    const uint32_t cr = (uint32_t)colcount[r];
+    int64_t* bw = blockw + (a >> 6) + r;
+    unsigned long long run = 0ull;
+    for (int64_t j0 = a; j0 < e; j0 += 64) {
+        const int64_t j = j0 + lane;
+        const unsigned long long w = j < e ? (unsigned long long)saint_entry_weight(rowptr, cr, col[j], N) : 0ull;
+        run += wave_sum_u64(w);
+        if (lane == 0) bw[(j0 - a) >> 6] = (int64_t)run;
+    }
+    if (lane == 0) {
+        roww[r + 1] = (int64_t)run;
+        if (r == 0) roww[0] = 0;
+    }
+}
+
+// ONE workgroup: roww[1 .. N] (the rows' weights) -> their inclusive prefix in place, 8 consecutive rows per thread and round
+__global__ __launch_bounds__(SAINT_THREADS) void saint_roww_scan_k(int64_t* __restrict__ roww, int N) {
+    __shared__ int64_t ws[SAINT_THREADS / 64 + 1];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int64_t carry = 0;
+    for (int64_t t0 = 0; t0 < N; t0 += 8 * SAINT_THREADS) {
+        const int64_t i0 = t0 + 8 * (int64_t)tid;
+        int64_t v[8], s = 0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { v[q] = i0 + q < N ? roww[1 + i0 + q] : 0; s += v[q]; }
+        const int64_t inc = saint_wave_incl_scan64(s);
+        if (lane == 63) ws[w] = inc;
+        __syncthreads();
+        if (w == 0) {
+            const int64_t x = lane < SAINT_THREADS / 64 ? ws[lane] : 0;
+            const int64_t xi = saint_wave_incl_scan64(x);
+            if (lane < SAINT_THREADS / 64) ws[lane] = xi - x;
+            if (lane == SAINT_THREADS / 64 - 1) ws[SAINT_THREADS / 64] = xi;
+        }
+        __syncthreads();
+        int64_t run = carry + ws[w] + inc - s;
+        carry += ws[SAINT_THREADS / 64];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { run += v[q]; if (i0 + q < N) roww[1 + i0 + q] = run; }
+        __syncthreads();
+    }
+}
+
+// The largest i in [0, n) with cdf(i) <= t, where cdf(0) = 0 (never read), cdf(i) = arr[i + shift] for i >= 1, non-decreasing, and
+// 0 <= t < cdf(n).  64-ary: every lane probes one position per round, so a search of n entries is ceil(log64 n) dependent loads.
+// All 64 lanes call it with the same arguments.
+__device__ __forceinline__ int64_t saint_search64(const int64_t* __restrict__ arr, int shift, int64_t n, int64_t t) {
+    const int lane = threadIdx.x & 63;
+    int64_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int64_t step = (hi - lo + 63) >> 6;
+        const int64_t p = lo + (int64_t)(lane + 1) * step;
+        const bool le = p < hi && arr[p + shift] <= t;
+        lo += (int64_t)__popcll(__ballot(le)) * step;         // cdf is monotone: the lanes with cdf(p) <= t are the first ones
+        hi = min(hi, lo + step);
+    }
+    return lo;
+}
+
+// One wavefront per draw b < B.  t = draws[b], or mulhi64(word, total) of the 64-bit word (stream word 2b) << 32 | (stream word
+// 2b + 1); total = cdf[N] with cdf = rowptr (node sampler) or roww (edge sampler).  Node sampler: the row that holds entry t.
+// Edge sampler: the row by roww, the row's block by blockw, the entry by a scan of the block's recomputed weights; both endpoints.
+__global__ __launch_bounds__(256) void saint_draw_k(
+        const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N, int B, const int32_t* __restrict__ colcount,
+        const int64_t* __restrict__ blockw, const int64_t* __restrict__ roww, const int64_t* __restrict__ draws, uint64_t seed,
+        uint64_t offset, const uint64_t* d_offset, int32_t* __restrict__ ids, int64_t* __restrict__ entries, int32_t* status) {
+    const int b = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (b >= B) return;                                                   // (whole wavefronts leave: the scans below need all 64 lanes)
+    const bool edge = roww != nullptr;
+    const int64_t* cdf = edge ? roww : rowptr;
+    const int64_t total = cdf[N];
+    int64_t t;
+    if (draws) {
+        t = draws[b];
+    } else {
+        const uint64_t off = d_offset ? *d_offset : offset;
+        const Philox4 p = philox4x32_10(off + (uint64_t)(b >> 1), seed);
+        const uint64_t word = ((uint64_t)p.v[(2 * b) & 3] << 32) | (uint64_t)p.v[(2 * b + 1) & 3];
+        t = (int64_t)__umul64hi(word, (uint64_t)(total > 0 ? total : 0));
+    }
+    bool bad = t < 0 || t >= total;
+    int r = 0, c = 0;
+    int64_t ent = 0;
+    if (!bad) {                                                           // (wavefront-uniform)
+        r = (int)saint_search64(cdf, 0, N, t);
+        if (!edge) {
+            ent = t;
+        } else {
+            const int64_t a = rowptr[r], e = rowptr[r + 1], base = (a >> 6) + r;
+            int64_t u = t - roww[r];
+            const int64_t k = saint_search64(blockw + base, -1, (e - a + 63) >> 6, u);
+            if (k > 0) u -= blockw[base + k - 1];
+            const int64_t j = a + 64 * k + lane;
+            const int cj = j < e ? col[j] : -1;
+            const uint32_t w = saint_entry_weight(rowptr, (uint32_t)colcount[r], cj, N);
+            // 64 weights below 2^32: their prefix as two int scans of 16-bit halves
+            const int64_t inc = ((int64_t)wave_incl_scan((int)(w >> 16)) << 16) + (int64_t)wave_incl_scan((int)(w & 0xffffu));
+            const uint64_t hit = __ballot(inc > u);
+            if (hit == 0ull) {
+                bad = true;                                               // a table that is not this graph's
+            } else {
+                const int l = __ffsll((unsigned long long)hit) - 1;
+                c = __shfl(cj, l, 64);
+                ent = a + 64 * k + l;
+            }
+        }
+    }
+    if (lane == 0) {
+        if (bad) { r = 0; c = 0; ent = 0; if (status) atomicOr(status, GRAPES_STATUS_BAD_INDEX); }
+        if (edge) { ids[2 * b] = r; ids[2 * b + 1] = c; } else { ids[b] = r; }
+        entries[b] = ent;
+    }
+}
+
+// ONE workgroup, after saint_draw_k: the ascending duplicate-free set of the M drawn ids, its count and node_map, as the walk's tail;
+// advances the device Philox offset (the draw's workgroups have all read it by now)
+__global__ __launch_bounds__(SAINT_THREADS) void saint_unique_ids_k(const int32_t* __restrict__ drawn, int M, int P, uint64_t advance,
+                                                                    uint64_t* d_offset, int32_t* __restrict__ node_idx,
+                                                                    int32_t* __restrict__ d_count, int32_t* __restrict__ node_map) {
+    __shared__ int32_t ids[SAINT_MAX_IDS];
+    __shared__ int wsum[SAINT_THREADS / 64 + 1];
+    for (int i = threadIdx.x; i < M; i += blockDim.x) ids[i] = drawn[i];
+    const int total = saint_sort_unique(ids, wsum, M, P, node_idx, node_map);
+    if (threadIdx.x == 0) {
+        *d_count = total;
+        if (d_offset) *d_offset += advance;
     }
 }
 
@@ -307,6 +499,46 @@ extern "C" int grapes_saint_masked_loss(const float* z, int64_t ldz, int32_t C, 
     if (!z || !node_idx || !train_mask || !g || !loss_out || ((labels == nullptr) == (labels_f == nullptr))) return GRAPES_EINVAL;
     hipLaunchKernelGGL(saint_masked_loss_k, dim3(1), dim3(SAINT_THREADS), 0, (hipStream_t)stream, z, ldz, C, node_idx, d_count, n_cap,
                        train_mask, labels, labels_f, g, ldg, loss_out, d_train, status);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int grapes_saint_edge_weights(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, int64_t nnz, int32_t* colcount,
+                                         int64_t* blockw, int64_t* roww, int32_t* status, grapes_stream_t stream) {
+    if (num_nodes <= 0 || nnz < 0 || nnz >= ((int64_t)1 << 31)) return GRAPES_EINVAL;
+    if (!rowptr || !col || !colcount || !blockw || !roww) return GRAPES_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = grapes_zero_async(colcount, (size_t)num_nodes * 4, s);
+    if (e != hipSuccess) return (int)e;
+    if (nnz > 0) {
+        int grid = grapes_div_up(nnz, 256 * 8);
+        if (grid > 2048) grid = 2048;
+        hipLaunchKernelGGL(saint_colcount_k, dim3(grid), dim3(256), 0, s, col, nnz, num_nodes, colcount, status);
+        GRAPES_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(saint_blockw_k, dim3(grapes_div_up((int64_t)num_nodes * 64, 256)), dim3(256), 0, s, rowptr, col, num_nodes,
+                       (const int32_t*)colcount, blockw, roww);
+    GRAPES_LAUNCH_CHECK();
+    hipLaunchKernelGGL(saint_roww_scan_k, dim3(1), dim3(SAINT_THREADS), 0, s, roww, num_nodes);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int grapes_saint_draw_nodes(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, int32_t B, const int32_t* colcount,
+                                       const int64_t* blockw, const int64_t* roww, const int64_t* draws, uint64_t philox_seed,
+                                       uint64_t philox_offset, uint64_t* d_philox_offset, int32_t* ids, int64_t* entries,
+                                       int32_t* node_idx, int32_t* d_count, int32_t* node_map, int32_t* status, grapes_stream_t stream) {
+    const bool edge = roww != nullptr;
+    if (num_nodes <= 0 || B <= 0 || (int64_t)B * (edge ? 2 : 1) > SAINT_MAX_IDS) return GRAPES_EINVAL;
+    if (!rowptr || !col || !ids || !entries || !node_idx || !d_count || !node_map || (draws && !status)) return GRAPES_EINVAL;
+    if (edge != (colcount != nullptr) || edge != (blockw != nullptr)) return GRAPES_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int M = edge ? 2 * B : B;
+    hipLaunchKernelGGL(saint_draw_k, dim3(grapes_div_up((int64_t)B * 64, 256)), dim3(256), 0, s, rowptr, col, num_nodes, B, colcount,
+                       blockw, roww, draws, philox_seed, philox_offset, (const uint64_t*)d_philox_offset, ids, entries, status);
+    GRAPES_LAUNCH_CHECK();
+    hipLaunchKernelGGL(saint_unique_ids_k, dim3(1), dim3(SAINT_THREADS), 0, s, (const int32_t*)ids, M, saint_pow2(M),
+                       (uint64_t)((2 * (int64_t)B + 3) >> 2), d_philox_offset, node_idx, d_count, node_map);
     GRAPES_LAUNCH_CHECK();
     return 0;
 }

@@ -1,12 +1,13 @@
-"""GraphSAINT random-walk baseline driver (reference graphsaint.py).
+"""GraphSAINT baseline driver (reference graphsaint.py).
 
     python -m grapes_amd.graphsaint --dataset cora --max_epoch 50 --runs 1
 
 * Flags and defaults of graphsaint.py:13-20: --use_normalization (accepted, unused as in the reference), --hidden_dim 256,
   --dataset, --runs 1, --lr 0.01, --max_epoch 50, --embed_nodes, --node_emb_dim 64.  Added: --batch_size 256 and --walk_length 2
   (graphsaint.py:104 hard-codes them), --num_steps 1, --seed, --engine graph|eager (saint.GraphedSaintTrainer /
-  saint.EagerSaintTrainer), --e_cap (edge capacity of a batch) and --large_graph auto|true|false (the row-blocked 64-bit
-  evaluation of full_graph.py; automatic from 2^31 CSR entries on).
+  saint.EagerSaintTrainer), --e_cap (edge capacity of a batch), --large_graph auto|true|false (the row-blocked 64-bit
+  evaluation of full_graph.py; automatic from 2^31 CSR entries on) and --sampler rw|node|edge (GraphSAINT's three samplers:
+  the reference's random walks, or PyG's GraphSAINTNodeSampler / GraphSAINTEdgeSampler, which ignore --walk_length).
 * Per run: GCN(F, [hidden_dim, C]) without dropout, Adam(params + embeddings, lr) (graphsaint.py:115-116); per epoch one step per
   batch, then one full-graph forward that yields val and test: accuracy for 1-D labels, TP / FP / FN micro-F1 for multi-label
   (graphsaint.py:46-88).  It prints `Epoch: .., Loss: .., Val: .., Test: ..`; a run's result is its last epoch's val metric, and
@@ -47,6 +48,7 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument("--engine", default="graph", choices=["graph", "eager"])
     ap.add_argument("--e_cap", default=None, type=int)
     ap.add_argument("--large_graph", default="auto", choices=["auto", "true", "false"])
+    ap.add_argument("--sampler", default="rw", choices=["rw", "node", "edge"])
     return ap
 
 
@@ -116,7 +118,8 @@ def run(args, device=None, log=print) -> float:
     train_mask, val_mask, test_mask = (m.to(device) for m in (data.train_mask, data.val_mask, data.test_mask))
     model = saint.build_model(x.shape[1], args.hidden_dim, data.num_classes, device)
     tr = saint.make_trainer(args.engine, g, x, y, train_mask, model, args.lr, emb, batch_size=args.batch_size,
-                            walk_length=args.walk_length, num_steps=args.num_steps, seed=args.seed, e_cap=args.e_cap)
+                            walk_length=args.walk_length, num_steps=args.num_steps, seed=args.seed, e_cap=args.e_cap,
+                            sampler=args.sampler)
     large = _large_flag(args.large_graph)
     val = 0.0
     for epoch in range(1, args.max_epoch + 1):                                               # graphsaint.py:118-121

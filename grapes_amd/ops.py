@@ -2271,6 +2271,54 @@ def saint_walk_nodes(rowptr, col, num_nodes: int, batch_size: int, walk_length: 
     return walks, node_idx, count
 
 
+def saint_edge_weights(rowptr, col, num_nodes: int, status=None):
+    """(colcount int32 [N], blockw int64 [(nnz >> 6) + N], roww int64 [N + 1]) of grapes_saint_edge_weights: the one-time weight
+    table of GraphSAINTEdgeSampler.  Entry (r, c) weighs colcount[r] + rowcount[c]; row r's 64-entry blocks keep their inclusive
+    weight prefix in blockw from slot (rowptr[r] >> 6) + r on (slots no row owns stay 0); roww is the exclusive prefix over rows,
+    roww[N] the total weight.  No host read."""
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(status, _i32, "status", True)
+    N, nnz, dev = int(num_nodes), col.numel(), rowptr.device
+    if nnz >= 2 ** 31:
+        raise ValueError("saint_edge_weights: the edge sampler's weights are 32-bit: fewer than 2^31 stored entries")
+    colcount = torch.empty(N, dtype=_i32, device=dev)
+    blockw = torch.zeros((nnz >> 6) + N, dtype=_i64, device=dev)
+    roww = torch.empty(N + 1, dtype=_i64, device=dev)
+    _lib.check(lib().grapes_saint_edge_weights(_p(rowptr), _p(col), N, nnz, _p(colcount), _p(blockw), _p(roww), _p(status),
+                                               _stream()), "saint_edge_weights")
+    return colcount, blockw, roww
+
+
+def saint_draw_nodes(rowptr, col, num_nodes: int, batch_size: int, weights=None, draws=None, philox_seed: int = 0,
+                     philox_offset: int = 0, d_philox_offset=None, node_map=None, status=None, out=None):
+    """(ids int32 [B or 2 B], node_idx int32 [the same size], count int32 [1], entries int64 [B]) of grapes_saint_draw_nodes: B
+    draws of a stored entry — uniform (weights None: the node sampler; ids = the entries' rows) or by the table of
+    saint_edge_weights (the edge sampler; ids = row and column of every entry) — and the ascending duplicate-free set of the ids
+    as saint_walk_nodes returns it.  draws int64 [B] replace the Philox draws (values t in [0, total)).  out: the four tensors
+    to write (captured steps)."""
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(draws, _i64, "draws", True)
+    _chk(d_philox_offset, _i64, "d_philox_offset", True); _chk(node_map, _i32, "node_map"); _chk(status, _i32, "status", True)
+    B = int(batch_size)
+    M = B if weights is None else 2 * B
+    if B <= 0 or M > SAINT_MAX_IDS:
+        raise ValueError(f"saint_draw_nodes: {'2 * ' if weights is not None else ''}batch_size must be in 1 .. {SAINT_MAX_IDS}")
+    if draws is not None and draws.numel() < B:
+        raise ValueError("draws shorter than batch_size")
+    colcount, blockw, roww = weights if weights is not None else (None, None, None)
+    _chk(colcount, _i32, "colcount", True); _chk(blockw, _i64, "blockw", True); _chk(roww, _i64, "roww", True)
+    dev = rowptr.device
+    if draws is not None and status is None:
+        status = torch.zeros(1, dtype=_i32, device=dev)
+    if out is None:
+        out = (torch.empty(M, dtype=_i32, device=dev), torch.empty(M, dtype=_i32, device=dev), torch.empty(1, dtype=_i32, device=dev),
+               torch.empty(B, dtype=_i64, device=dev))
+    ids, node_idx, count, entries = out
+    _lib.check(lib().grapes_saint_draw_nodes(_p(rowptr), _p(col), int(num_nodes), B, _p(colcount), _p(blockw), _p(roww), _p(draws),
+                                             int(philox_seed) & (2 ** 64 - 1), int(philox_offset), _p(d_philox_offset), _p(ids),
+                                             _p(entries), _p(node_idx), _p(count), _p(node_map), _p(status), _stream()),
+               "saint_draw_nodes")
+    return ids, node_idx, count, entries
+
+
 def saint_subgraph(rowptr, col, node_idx, count, node_map, e_cap: int, status=None, out=None):
     """(edge_src, edge_dst int32 [e_cap], e_count int32 [1], rowptr_l int32 [n_cap + 1]) of grapes_saint_subgraph: the subgraph
     induced by the first *count ids of node_idx, relabelled to local ids, in CSR order.  Overflow of e_cap sets a status bit."""

@@ -1,11 +1,14 @@
-"""GraphSAINT random-walk training of a two-layer GCN (reference graphsaint.py:22-43, 104-121), in two forms.
+"""GraphSAINT training of a two-layer GCN (reference graphsaint.py:22-43, 104-121), in two forms.
 
-* EagerSaintTrainer — the readable form: modules.saint.GraphSAINTRandomWalkSampler batches, the GCN module with autograd and
+* EagerSaintTrainer — the readable form: batches of a modules.saint sampler, the GCN module with autograd and
   torch.optim.Adam, exactly the reference's loop body.  Two host reads per step (the batch's node and edge counts).
-* GraphedSaintTrainer — the whole step as one captured hipGraph: walk + node set (one launch), induced subgraph, feature-row
+* GraphedSaintTrainer — the whole step as one captured hipGraph: the draw + node set, induced subgraph, feature-row
   gather, both GCN layers forward and backward, the masked loss, the embedding-row gradient (--embed_nodes) and FusedAdam.
-  Buffers are sized for n_cap = B (L + 1) nodes and e_cap edges; every kernel reads the live counts on the device, so a step
+  Buffers are sized for the sampler's n_cap nodes and e_cap edges; every kernel reads the live counts on the device, so a step
   reads nothing back.  The status word (edge overflow, bad ids) is read once per epoch by check().
+
+sampler = "rw" (the reference's GraphSAINTRandomWalkSampler: n_cap = B (L + 1)), "node" (GraphSAINTNodeSampler: n_cap = B) or
+"edge" (GraphSAINTEdgeSampler: n_cap = 2 B); walk_length is read by "rw" alone.
 
 Both draw from the same Philox stream (seed, device offset), so from one seed they sample the same batches.
 
@@ -20,7 +23,7 @@ import torch
 
 from . import ops
 from .modules.gcn import GCN
-from .modules.saint import GraphSAINTRandomWalkSampler
+from .modules.saint import make_sampler
 
 
 class _GatherX(torch.autograd.Function):
@@ -67,13 +70,14 @@ def masked_loss(logits, node_idx, count, train_mask, y, g=None, loss=None):
 
 class EagerSaintTrainer:
     def __init__(self, graph, x, y, train_mask, model: GCN, optimizer, batch_size=256, walk_length=2, num_steps=1, seed=None,
-                 e_cap=None):
-        self.loader = GraphSAINTRandomWalkSampler(graph, batch_size, walk_length, num_steps, seed=seed, e_cap=e_cap)
+                 e_cap=None, sampler="rw"):
+        self.loader = make_sampler(sampler, graph, batch_size, walk_length, num_steps=num_steps, seed=seed, e_cap=e_cap)
         self.x, self.y, self.train_mask, self.model, self.optimizer = x, y, train_mask, model, optimizer
 
-    def step(self, roots=None, uniforms=None):
-        """One step (graphsaint.py:26-36); returns (loss tensor, batch)."""
-        b = self.loader.batch(roots, uniforms)
+    def step(self, *inject, **kw):
+        """One step (graphsaint.py:26-36); returns (loss tensor, batch).  inject: the sampler's injected draws (roots, uniforms
+        for "rw"; draws for "node" / "edge")."""
+        b = self.loader.batch(*inject, **kw)
         ids = b.node_idx.to(torch.int32)
         self.optimizer.zero_grad()                                                          # graphsaint.py:29
         x = _GatherX.apply(self.x, ids, None, None, False)                                  # batch.x (data.x gathered)
@@ -100,8 +104,8 @@ class GraphedSaintTrainer:
     is stepped by ops.FusedAdam."""
 
     def __init__(self, graph, x, y, train_mask, model: GCN, optimizer, batch_size=256, walk_length=2, num_steps=1, seed=None,
-                 e_cap=None):
-        self.loader = GraphSAINTRandomWalkSampler(graph, batch_size, walk_length, num_steps, seed=seed, e_cap=e_cap)
+                 e_cap=None, sampler="rw"):
+        self.loader = make_sampler(sampler, graph, batch_size, walk_length, num_steps=num_steps, seed=seed, e_cap=e_cap)
         L = self.loader
         g = L.graph
         dev = g.device
@@ -109,7 +113,10 @@ class GraphedSaintTrainer:
         self.n_cap, self.e_cap = L.n_cap, L.e_cap
         C = model.gcn_layers[-1].out_channels
         i32 = dict(dtype=torch.int32, device=dev)
-        self.walk_out = (torch.zeros((L.batch_size, L.walk_length + 1), **i32), torch.zeros(self.n_cap, **i32), torch.zeros(1, **i32))
+        self.draw_out = L.draw_buffers()                 # "rw": (walks, node_idx, count); else (ids, node_idx, count, entries)
+        self.walk_out = self.draw_out
+        if sampler == "edge":
+            L.weights()                                  # the one-time table (one host read) is built before the capture
         self.sub_out = (torch.zeros(self.e_cap, **i32), torch.zeros(self.e_cap, **i32), torch.zeros(1, **i32),
                         torch.zeros(self.n_cap + 1, **i32))
         self.xbuf = torch.zeros((self.n_cap, x.shape[1]), dtype=torch.float32, device=dev)
@@ -124,9 +131,8 @@ class GraphedSaintTrainer:
     def _body(self):
         L = self.loader
         g = L.graph
-        walks, node_idx, count = ops.saint_walk_nodes(g.rowptr, g.col, g.num_nodes, L.batch_size, L.walk_length,
-                                                      philox_seed=L.seed, d_philox_offset=L.philox_offset, node_map=g.node_map,
-                                                      status=L.status, out=self.walk_out)
+        d = L.draw(out=self.draw_out)
+        node_idx, count = d["node_idx"], d["count"]
         src, dst, d_e, _ = ops.saint_subgraph(g.rowptr, g.col, node_idx, count, g.node_map, self.e_cap, status=L.status,
                                               out=self.sub_out)
         if self.n_cap <= ops._SMALL_GRAPH:

@@ -53,7 +53,8 @@ extern "C" {
  * grapes_saint_subgraph(_workspace_bytes), grapes_saint_masked_loss; the GAT classifier (modules/gcn.py:45-72) — grapes_gat_scores,
  * grapes_gat_aggregate_fwd / _bwd (+ _workspace_bytes each); the GCN2 classifier (modules/gcn.py:76-117) —
  * grapes_gcn2_loop_counts(_csr), grapes_gcn2_propagate_fwd / _bwd (+ _workspace_bytes), grapes_gcn2_mix_fwd / _bwd; the PNA
- * classifier (modules/gcn.py:120-149) — grapes_pna_aggregate_fwd / _bwd (+ _workspace_bytes each), grapes_pna_add_input_grad. */
+ * classifier (modules/gcn.py:120-149) — grapes_pna_aggregate_fwd / _bwd (+ _workspace_bytes each), grapes_pna_add_input_grad; GraphSAINT's node and edge
+ * samplers — grapes_saint_edge_weights, grapes_saint_draw_nodes. */
 #define GRAPES_ABI_VERSION 302
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1254,6 +1255,23 @@ int grapes_saint_subgraph(const int64_t* rowptr, const int32_t* col, const int32
  * fp32[N, C]).  g [n_cap, ldg] = d loss / d z (0 on other rows).  T = 0: *loss_out = NaN and g = 0 (torch's mean over an empty
  * selection).  ONE workgroup, fixed summation order. */
 int grapes_saint_masked_loss(const float* z, int64_t ldz, int32_t C, const int32_t* node_idx, const int32_t* d_count, int32_t n_cap, const uint8_t* train_mask, const int64_t* labels, const float* labels_f, float* g, int64_t ldg, float* loss_out, int32_t* d_train, int32_t* status, grapes_stream_t stream);
+/* GraphSAINT's other two samplers (the reference imports GraphSAINTNodeSampler at graphsaint.py:8; PyG 2.5 loader/graph_saint.py).
+ * The one-time weight table of GraphSAINTEdgeSampler: the weight of the stored entry (r, c) is colcount[r] + rowcount[c] (PyG:
+ * prob = 1 / deg_in[row] + 1 / deg_out[col] with deg_in = 1 / colcount, deg_out = 1 / rowcount), an integer below 2^32.
+ * colcount int32[N]: entries per column (zeroed here, then int32 atomic adds).  blockw int64[(nnz >> 6) + N]: row r owns the slots
+ * from (rowptr[r] >> 6) + r on, one per 64-entry block of the row, holding the inclusive prefix of the block weights inside the row
+ * (slots no row owns are left as they are).  roww int64[N + 1]: exclusive prefix of the row weights; roww[N] = the total weight.
+ * A column outside [0, N) weighs 0 and ORs GRAPES_STATUS_BAD_INDEX into status.  nnz < 2^31.  Four launches, stream-ordered. */
+int grapes_saint_edge_weights(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, int64_t nnz, int32_t* colcount, int64_t* blockw, int64_t* roww, int32_t* status, grapes_stream_t stream);
+/* One batch of GraphSAINTNodeSampler (roww == NULL: PyG adj.storage.row()[randint(0, E, (B,))]) or GraphSAINTEdgeSampler (colcount /
+ * blockw / roww of grapes_saint_edge_weights: PyG's top-1 of rand(B, E).log() / prob per row, i.e. one weighted draw per row).
+ * Draw b: t = draws[b] when draws != NULL (a value outside [0, total) ORs GRAPES_STATUS_BAD_INDEX and draws entry 0's row), else
+ * t = mulhi64(word, total), word = (stream word 2b) << 32 | (stream word 2b + 1) of the stream (seed, off), off = *d_philox_offset
+ * when non-NULL; total = rowptr[N] (node) or roww[N] (edge), read on the device.  Node: ids[b] = the row holding entry t,
+ * entries[b] = t.  Edge: entries[b] = the entry e whose weight interval holds t, ids[2b] = its row, ids[2b + 1] = its column.
+ * Then node_idx / *d_count / node_map as grapes_saint_walk_nodes writes them, over the B (node) or 2 B (edge) ids (<= 16384).
+ * *d_philox_offset advances by ceil(2 B / 4).  Two launches: one wavefront per draw, then one workgroup. */
+int grapes_saint_draw_nodes(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, int32_t B, const int32_t* colcount, const int64_t* blockw, const int64_t* roww, const int64_t* draws, uint64_t philox_seed, uint64_t philox_offset, uint64_t* d_philox_offset, int32_t* ids, int64_t* entries, int32_t* node_idx, int32_t* d_count, int32_t* node_map, int32_t* status, grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:
