@@ -60,19 +60,6 @@ __device__ __forceinline__ void eff_counts(const int32_t* const (&d)[N], const i
 
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
-// Inclusive scan over the wavefront on the DPP network (no LDS crossbar round trips: the ds_bpermute form of the same scan
-// cost six dependent ~100-cycle hops).  Rows of 16 lanes scan with row_shr 1/2/4/8 (lanes without a source add 0), then
-// lane 15 of row 0 / 2 is added to row 1 / 3 (row_bcast:15) and lane 31 to rows 2 and 3 (row_bcast:31).
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);   // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1, 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2, 3
-    return v;
-}
-
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
@@ -99,49 +86,7 @@ __device__ __forceinline__ float wave_max(float v) {
 // a loop that keeps prefetches or stores in flight across iterations that wait is a full memory round trip per barrier.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// Exclusive scan over the block (blockDim.x a multiple of 64, <= 1024).  `lds` needs 17 ints.
-// Returns the exclusive prefix of v for this thread; *total = block sum.  Contains barriers:
-// every thread of the block must call it.
-__device__ __forceinline__ int block_excl_scan(int v, int* lds, int* total) {
-    const int lane = lane_id();
-    const int wid = threadIdx.x >> 6;
-    const int nw = (blockDim.x + 63) >> 6;
-    int incl = wave_incl_scan(v);
-    __syncthreads();  // protect lds reuse across consecutive calls
-    if (lane == 63) lds[wid] = incl;
-    __syncthreads();
-    if (wid == 0) {
-        int x = (lane < nw) ? lds[lane] : 0;
-        int xs = wave_incl_scan(x);
-        if (lane < nw) lds[lane] = xs - x;
-        if (lane == nw - 1) lds[16] = xs;
-    }
-    __syncthreads();
-    int base = lds[wid];
-    *total = lds[16];
-    return base + incl - v;
-}
-
-// Three exclusive scans at once (the same three barriers as one): a, b, c -> their exclusive prefixes; *ta / *tb / *tc the block sums.
-// `lds` needs 51 ints.
-__device__ __forceinline__ void block_excl_scan3(int& a, int& b, int& c, int* lds, int* ta, int* tb, int* tc) {
-    const int lane = lane_id();
-    const int wid = threadIdx.x >> 6;
-    const int nw = (blockDim.x + 63) >> 6;
-    const int ia = wave_incl_scan(a), ib = wave_incl_scan(b), ic = wave_incl_scan(c);
-    __syncthreads();  // protect lds reuse across consecutive calls
-    if (lane == 63) { lds[wid] = ia; lds[17 + wid] = ib; lds[34 + wid] = ic; }
-    __syncthreads();
-    if (wid == 0) {
-        const int xa = (lane < nw) ? lds[lane] : 0, xb = (lane < nw) ? lds[17 + lane] : 0, xc = (lane < nw) ? lds[34 + lane] : 0;
-        const int sa = wave_incl_scan(xa), sb = wave_incl_scan(xb), sc = wave_incl_scan(xc);
-        if (lane < nw) { lds[lane] = sa - xa; lds[17 + lane] = sb - xb; lds[34 + lane] = sc - xc; }
-        if (lane == nw - 1) { lds[16] = sa; lds[33] = sb; lds[50] = sc; }
-    }
-    __syncthreads();
-    *ta = lds[16]; *tb = lds[33]; *tc = lds[50];
-    a = lds[wid] + ia - a; b = lds[17 + wid] + ib - b; c = lds[34 + wid] + ic - c;
-}
+#include "block_prims.h"     // the scans, the sum of workgroup totals and the searches
 
 // Zero fill as a KERNEL node (hipMemsetAsync becomes a memset node under stream capture; the large scratch
 // clears of the hop pipeline stay ordinary kernel nodes).  bytes and ptr must be multiples of 4.

@@ -135,15 +135,6 @@ __global__ __launch_bounds__(256) void recv_expand_k(const int32_t* __restrict__
 }
 
 // ---------------------------------------------------------------------------- halo feature rows
-__device__ __forceinline__ int lower_bound_i32(const int32_t* __restrict__ v, int n, int key) {
-    int a = 0, b = n;                // first index with v[idx] >= key
-    while (a < b) {
-        const int mid = (a + b) >> 1;
-        if (v[mid] < key) a = mid + 1; else b = mid;
-    }
-    return a;
-}
-
 // grid (x, n_peers): the run of peer blockIdx.y's ascending list that this rank owns, gathered into its slot.
 template <bool VEC>
 __global__ __launch_bounds__(256) void serve_rows_k(const float* __restrict__ X, int F,
@@ -154,7 +145,7 @@ __global__ __launch_bounds__(256) void serve_rows_k(const float* __restrict__ X,
     const int32_t* q = req + (long long)p * (cap + 1);
     if (threadIdx.x == 0) {
         int m = q[cap]; m = m < 0 ? 0 : (m > cap ? cap : m);
-        const int a = lower_bound_i32(q, m, lo), b = lower_bound_i32(q, m, hi);
+        const int a = lower_bound(q, m, lo), b = lower_bound(q, m, hi);
         int cnt = b - a;
         if (cnt > n_slot) {
             if (status && blockIdx.x == 0) atomicOr(status, GRAPES_STATUS_NODE_OVERFLOW);
@@ -194,7 +185,7 @@ __global__ __launch_bounds__(256) void halo_assemble_k(const float* __restrict__
     const int n = eff_count(d_n, n_host);
     if ((int)threadIdx.x <= n_peers) {
         s_bnd[threadIdx.x] = bounds[threadIdx.x];
-        s_cut[threadIdx.x] = lower_bound_i32(ids, n, bounds[threadIdx.x]);
+        s_cut[threadIdx.x] = lower_bound(ids, n, bounds[threadIdx.x]);
     }
     __syncthreads();
     const uint32_t epoch = d_epoch ? (*d_epoch & 0xffffffu) : epoch_host;
@@ -320,7 +311,7 @@ __global__ __launch_bounds__(256) void halo_positions_k(const int32_t* __restric
                                                         uint32_t* __restrict__ code_pos) {
     __shared__ int s_cut[XCH_MAX_PEERS + 1];
     const int n = eff_count(d_n, n_host);
-    if ((int)threadIdx.x <= n_peers) s_cut[threadIdx.x] = lower_bound_i32(ids, n, bounds[threadIdx.x]);
+    if ((int)threadIdx.x <= n_peers) s_cut[threadIdx.x] = lower_bound(ids, n, bounds[threadIdx.x]);
     __syncthreads();
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n_host; i += gridDim.x * blockDim.x) {
         int q = 0;

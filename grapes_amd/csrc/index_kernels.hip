@@ -131,12 +131,23 @@ extern "C" int grapes_frontier_expand(const int64_t* rowptr, const int32_t* col,
     return 0;
 }
 
+// bit `id` of a bitmap (and, where the word was empty, the word's bit of the summary level bits1)
+__device__ __forceinline__ void mark_bit(unsigned long long* __restrict__ bits, unsigned long long* __restrict__ bits1,
+                                         int id, int num_nodes, int32_t* status) {
+    if (id < 0 || id >= num_nodes) {
+        if (status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+        return;
+    }
+    const int w = id >> 6;
+    const unsigned long long b = 1ull << (id & 63);
+    if (bits[w] & b) return;               // already visible: skip the atomic (hub neighbours repeat a lot)
+    const unsigned long long old = atomicOr(&bits[w], b);
+    if (bits1 && old == 0ull) atomicOr(&bits1[w >> 6], 1ull << (w & 63));
+}
+
 // get_neighborhoods in ONE launch for query lists of up to EXPAND_LDS_OFFS nodes (the step's <= B + K previous nodes):
 // every workgroup rebuilds the (short) row-length scan in LDS itself instead of waiting for a separate offsets launch;
 // workgroup 0 also publishes eoff / the edge count for the later consumers.
-__device__ __forceinline__ void mark_bit(unsigned long long* __restrict__ bits, unsigned long long* __restrict__ bits1,
-                                         int id, int num_nodes, int32_t* status);
-
 __device__ __forceinline__ void frontier_expand_fused_body(const int64_t* __restrict__ rowptr,
                                                                const int32_t* __restrict__ col,
                                                                const int32_t* __restrict__ nodes, int m_host,
@@ -586,19 +597,6 @@ extern "C" int grapes_bitmap_mark_rows(uint64_t* bits, uint64_t* bits1, const in
 
 // One launch for the three marks of a hop (main.py:183-187): `previous` -> prev_bits; queried nodes with >= 1 edge and
 // every neighbour -> bits (+ summary).  Same effect as bitmap_mark(prev_bits) + bitmap_mark_rows + bitmap_mark(dst).
-__device__ __forceinline__ void mark_bit(unsigned long long* __restrict__ bits, unsigned long long* __restrict__ bits1,
-                                         int id, int num_nodes, int32_t* status) {
-    if (id < 0 || id >= num_nodes) {
-        if (status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
-        return;
-    }
-    const int w = id >> 6;
-    const unsigned long long b = 1ull << (id & 63);
-    if (bits[w] & b) return;               // already visible: skip the atomic (hub neighbours repeat a lot)
-    const unsigned long long old = atomicOr(&bits[w], b);
-    if (bits1 && old == 0ull) atomicOr(&bits1[w >> 6], 1ull << (w & 63));
-}
-
 __global__ void bitmap_mark_hop_k(unsigned long long* __restrict__ prev_bits, unsigned long long* __restrict__ bits,
                                   unsigned long long* __restrict__ bits1, const int32_t* __restrict__ previous,
                                   int m_host, const int32_t* d_m, const int32_t* __restrict__ eoff,
@@ -838,15 +836,6 @@ extern "C" int grapes_bitmap_clear(uint64_t* bits, const int32_t* ids, int64_t n
 }
 
 // ---------------------------------------------------------------------------- frontier compaction
-// Sum of bsum[0..b) by the whole workgroup (integer => order-free, deterministic).
-__device__ __forceinline__ int block_prefix_of_sums(const int32_t* __restrict__ bsum, int b, int* lds) {
-    int acc = 0;
-    for (int i = threadIdx.x; i < b; i += blockDim.x) acc += bsum[i];
-    int tot;
-    block_excl_scan(acc, lds, &tot);
-    return tot;
-}
-
 // Two launches over ALL level-0 words of the bitmap (N/64 words: 38 K for ogbn-products, 1.7 M = 14 MB for
 // papers100M — a few microseconds of streaming either way, cheaper than first listing the non-empty words through a
 // summary level): (A) per-workgroup totals, (B) base offset from the totals + workgroup scan, ids emitted in ascending
@@ -1029,8 +1018,8 @@ __device__ __forceinline__ void compact_emit_body(unsigned long long* __restrict
         lookback_finish(sync, gc);
         base_b = (int)(pre & 0x7fffffffull); base_n = (int)(pre >> 31);
     } else {
-        base_b = block_prefix_of_sums(bsum_b, BID, lds);
-        base_n = block_prefix_of_sums(bsum_n, BID, lds);
+        base_b = block_sum_of(bsum_b, BID, lds);
+        base_n = block_sum_of(bsum_n, BID, lds);
     }
     GRAPES_STAMP_NW(4);                         // the predecessors' totals are here
     posb += base_b; posn += base_n;
@@ -1365,33 +1354,6 @@ __global__ __launch_bounds__(1024) void compact_emit_wide_k(unsigned long long* 
 // list (their ids are consecutive), their counters come by one load, the row starts of the counted build by a wavefront scan.
 // Same outputs, same side jobs, the bitmap consumed.
 #define COMPACT_SMALL_W 4096
-// exclusive scan of a 64-bit value over the workgroup (two counts packed 32 + 32: both grid-wide sums stay below 2^31)
-__device__ __forceinline__ unsigned long long block_excl_scan_u64(unsigned long long v, unsigned long long* lds /* 17 words */,
-                                                                  unsigned long long* total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    unsigned long long incl = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    __syncthreads();
-    if (lane == 63) lds[wid] = incl;
-    __syncthreads();
-    if (wid == 0) {
-        unsigned long long x = lane < nw ? lds[lane] : 0ull, xs = x;
-#pragma unroll
-        for (int d = 1; d < 16; d <<= 1) {
-            const unsigned long long t = __shfl_up(xs, d, 64);
-            if (lane >= d) xs += t;
-        }
-        if (lane < nw) lds[lane] = xs - x;
-        if (lane == nw - 1) lds[16] = xs;
-    }
-    __syncthreads();
-    *total = lds[16];
-    return lds[wid] + incl - v;
-}
 __global__ __launch_bounds__(1024) void compact_small_scan_k(const unsigned long long* __restrict__ bits,
                                                              const unsigned long long* __restrict__ prev_bits, int W, int n_cap,
                                                              int32_t* __restrict__ pre /* [4][W] */, int32_t* __restrict__ counts,
@@ -1740,7 +1702,7 @@ __global__ __launch_bounds__(1024) void slice_emit_k(const int32_t* __restrict__
         return;
     }
     if (blockIdx.x * blockDim.x >= e) return;
-    const int base = block_prefix_of_sums(bsum, blockIdx.x, lds);
+    const int base = block_sum_of(bsum, blockIdx.x, lds);
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     int c = 0, s = 0, d = 0;
     if (t < e) { d = dst[t]; s = src[t]; c = mult[d]; }

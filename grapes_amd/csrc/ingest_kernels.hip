@@ -126,12 +126,6 @@ static int scan_u32_to_i64(const unsigned* v, long long n, int64_t* out /* [n] e
 }
 
 // ---------------------------------------------------------------------------------------------- short rows: windows in LDS
-// first index r in [0, n] with a[r] >= key (a ascending, a[n] = total)
-__device__ __forceinline__ long long lower_bound_i64(const int64_t* __restrict__ a, long long n, long long key) {
-    long long lo = 0, hi = n + 1;
-    while (lo < hi) { const long long mid = (lo + hi) >> 1; if (a[mid] < key) lo = mid + 1; else hi = mid; }
-    return lo;
-}
 __global__ __launch_bounds__(512) void csr_window_sort_k(const int64_t* __restrict__ rowptr_raw /* [N+1] */, int N,
                                                          int32_t* __restrict__ col_raw, unsigned* __restrict__ udeg,
                                                          int32_t* __restrict__ long_rows, int32_t* __restrict__ n_long, int long_cap,
@@ -144,8 +138,8 @@ __global__ __launch_bounds__(512) void csr_window_sort_k(const int64_t* __restri
     const long long total = rowptr_raw[N];
     for (long long b = blockIdx.x; b * CSR_WIN < total; b += gridDim.x) {
         if (threadIdx.x == 0) {
-            s_r0 = lower_bound_i64(rowptr_raw, N, b * (long long)CSR_WIN);
-            s_r1 = lower_bound_i64(rowptr_raw, N, (b + 1) * (long long)CSR_WIN);
+            s_r0 = lower_bound(rowptr_raw, (long long)N + 1, b * (long long)CSR_WIN);
+            s_r1 = lower_bound(rowptr_raw, (long long)N + 1, (b + 1) * (long long)CSR_WIN);
         }
         __syncthreads();
         long long r0 = s_r0, r1 = s_r1;             // rows [r0, r1) start inside this window (r1 <= N)

@@ -6,6 +6,7 @@
 //   main.py:268,289 Adam updates of both optimisers (torch.optim.Adam semantics, one launch for all tensors)
 // One workgroup each for the two loss kernels (a few hundred rows); everything is fp32 like the reference.
 #include "common.h"
+#include "row_loss.h"
 
 #define LOSS_THREADS 1024
 #define LOSS_MAX_B 4096
@@ -57,32 +58,9 @@ __device__ __forceinline__ float loss_row(const float* __restrict__ logits, floa
                                           const float* __restrict__ labels_f, int multilabel, float inv, int lane) {
     float loss = 0.f;
     if ((unsigned)row < (unsigned)n_rows) {
-        const float* x = logits + (long long)row * C;
-        float* dx = dlogits + (long long)row * C;
-        if (!multilabel) {
-            const int y = (int)labels[gid];
-            float m = -INFINITY;
-            for (int c = lane; c < C; c += 64) m = fmaxf(m, x[c]);
-            m = wave_max(m);
-            float se = 0.f;
-            for (int c = lane; c < C; c += 64) se += expf(x[c] - m);
-            se = wave_sum(se);
-            const float lse = logf(se);
-            for (int c = lane; c < C; c += 64) {
-                const float lsm = (x[c] - m) - lse;                            // log_softmax
-                if (c == y) loss = -lsm;
-                dx[c] = (expf(lsm) - (c == y ? 1.0f : 0.0f)) * inv;
-            }
-            loss = wave_sum(loss);
-        } else {
-            const float* yv = labels_f + gid * C;
-            for (int c = lane; c < C; c += 64) {
-                const float v = x[c], t = yv[c];
-                loss += fmaxf(v, 0.f) - v * t + log1pf(expf(-fabsf(v)));       // stable BCE-with-logits
-                dx[c] = (1.0f / (1.0f + expf(-v)) - t) * inv;
-            }
-            loss = wave_sum(loss);
-        }
+        const RowStrided r{logits + (long long)row * C, dlogits + (long long)row * C, C, lane};
+        loss = multilabel ? row_loss_bce(r, labels_f + gid * C, inv)
+                          : row_loss_ce<CE_LOG_SOFTMAX>(r, (int)labels[gid], inv);
     }
     return loss;
 }
@@ -139,6 +117,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void classifier_loss_k(
             for (int u = 0; u < RIF; ++u) {
                 if (b0 + u >= B) continue;                              // uniform per wavefront
                 const bool ok = (unsigned)row[u] < (unsigned)n_rows;
+                // (row_loss.h's routine costs this pass two scalar registers and 0.2 % of the launch: it keeps its own form)
                 const float x = lane < C ? xv[u] : -INFINITY;
                 const float m = wave_max(x);
                 const float se = wave_sum(lane < C ? expf(x - m) : 0.f);
@@ -677,55 +656,25 @@ __global__ __launch_bounds__(256) void rl_loss_rows_k(const float* z, long long 
     for (long long i = (long long)blockIdx.x * RL_ROWS + wid; i < i_end; i += 4) {
         const long long r = rows[i];
         const float* zr = z + i * ldz;
-        float zd[RL_MAX_KC]; bool kp[RL_MAX_KC];
-        float mx = -INFINITY;
+        float zd[RL_MAX_KC], dz[RL_MAX_KC]; bool kp[RL_MAX_KC];
 #pragma unroll
         for (int k = 0; k < RL_MAX_KC; ++k) {
             const int c = lane + 64 * k;
-            zd[k] = 0.f; kp[k] = false;
+            zd[k] = 0.f; dz[k] = 0.f; kp[k] = false;
             if (k < KC && c < C) {
                 kp[k] = p > 0.f ? philox_uniform_at(seed, offset, r * C + c) >= p : true;
                 const float v = zr[c];
                 zd[k] = p > 0.f ? (kp[k] ? v * sc : 0.f) : v;
-                mx = fmaxf(mx, zd[k]);
             }
         }
-        float dz[RL_MAX_KC];
+        const RowSlots<RL_MAX_KC> rs{zd, dz, KC, C, lane};
         float lrow;
         if (!multi) {
             const long long y = labels[r];
             if ((y < 0 || y >= C) && lane == 0 && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
-            mx = wave_max(mx);
-            float se = 0.f;
-#pragma unroll
-            for (int k = 0; k < RL_MAX_KC; ++k) { const int c = lane + 64 * k; if (k < KC && c < C) se += expf(zd[k] - mx); }
-            se = wave_sum(se);
-            const float lse = mx + logf(se);
-            float ly = 0.f;
-#pragma unroll
-            for (int k = 0; k < RL_MAX_KC; ++k) {
-                const int c = lane + 64 * k;
-                dz[k] = 0.f;
-                if (k < KC && c < C) {
-                    const float t = c == y ? 1.0f : 0.f;
-                    if (c == y) ly = lse - zd[k];
-                    dz[k] = (expf(zd[k] - lse) - t) * inv;
-                }
-            }
-            lrow = wave_sum(ly);
+            lrow = row_loss_ce<CE_LOG_SUM_EXP>(rs, y, inv);
         } else {
-            float l = 0.f;
-#pragma unroll
-            for (int k = 0; k < RL_MAX_KC; ++k) {
-                const int c = lane + 64 * k;
-                dz[k] = 0.f;
-                if (k < KC && c < C) {
-                    const float x = zd[k], t = labels_f[r * C + c];
-                    l += fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
-                    dz[k] = (1.0f / (1.0f + expf(-x)) - t) * inv;
-                }
-            }
-            lrow = wave_sum(l);
+            lrow = row_loss_bce(rs, labels_f + r * C, inv);
         }
         const float ds = dinv[r];
 #pragma unroll

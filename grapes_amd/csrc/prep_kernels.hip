@@ -112,14 +112,6 @@ __global__ __launch_bounds__(1024) void prep_scan_count_k(int n_host, const int3
     if (threadIdx.x == 0) { bsum_t[blockIdx.x] = tt; bsum_s[blockIdx.x] = ts; }
 }
 
-__device__ __forceinline__ int prefix_of_sums(const int32_t* __restrict__ bsum, int b, int* lds) {
-    int acc = 0;
-    for (int i = threadIdx.x; i < b; i += blockDim.x) acc += bsum[i];
-    int tot;
-    block_excl_scan(acc, lds, &tot);
-    return tot;
-}
-
 // stage 2: row pointers, fill cursors, dinv, long-row work items
 __global__ __launch_bounds__(1024) void prep_scan_emit_k(int n_host, const int32_t* d_n, int grouped,
                                                          int32_t* __restrict__ cnt_t, int32_t* __restrict__ cnt_s,
@@ -158,8 +150,8 @@ __global__ __launch_bounds__(1024) void prep_scan_emit_k(int n_host, const int32
         lookback_finish(sync, live);
         base_t = (int)(pre & 0x7fffffffull); base_s = (int)(pre >> 31);
     } else {
-        base_t = prefix_of_sums(bsum_t, blockIdx.x, lds);
-        base_s = prefix_of_sums(bsum_s, blockIdx.x, lds);
+        base_t = block_sum_of(bsum_t, blockIdx.x, lds);
+        base_s = block_sum_of(bsum_s, blockIdx.x, lds);
     }
     pt += base_t; ps += base_s;
     if (i < n) {

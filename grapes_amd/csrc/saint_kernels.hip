@@ -39,25 +39,6 @@
 #define SAINT_THREADS 1024
 #define SAINT_MAX_IDS 16384          // B (L + 1) <= this: the node set is sorted in 64 KiB of LDS
 
-// inclusive scan of one value per thread over the whole workgroup (blockDim.x == SAINT_THREADS); *total = the sum
-__device__ __forceinline__ int saint_block_scan(int v, int* wsum, int* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    int inc = wave_incl_scan(v);
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    if (w == 0) {
-        int s = lane < nw ? wsum[lane] : 0;
-        int si = wave_incl_scan(s);
-        if (lane < nw) wsum[lane] = si - s;          // exclusive prefix of the wavefront totals
-        if (lane == nw - 1) wsum[SAINT_THREADS / 64] = si;
-    }
-    __syncthreads();
-    inc += wsum[w];
-    *total = wsum[SAINT_THREADS / 64];
-    __syncthreads();
-    return inc;
-}
-
 // The tail the walk and the draw share (one workgroup of SAINT_THREADS): ids[0 .. M) in LDS, written by this workgroup and not yet
 // fenced; P = M rounded up to a power of two (<= SAINT_MAX_IDS).  Sorts them, writes their ascending duplicate-free set to node_idx
 // and node_map[node_idx[i]] = i, and returns the set's size to every thread.
@@ -86,7 +67,7 @@ __device__ __forceinline__ int saint_sort_unique(int32_t* ids, int* wsum, int M,
     int heads = 0;
     for (int i = lo; i < hi; ++i) heads += (i == 0 || ids[i] != ids[i - 1]) ? 1 : 0;
     int total;
-    int pos = saint_block_scan(heads, wsum, &total) - heads;
+    int pos = block_excl_scan(heads, wsum, &total);
     for (int i = lo; i < hi; ++i) {
         if (i == 0 || ids[i] != ids[i - 1]) {
             const int v = ids[i];
@@ -153,16 +134,6 @@ __device__ __forceinline__ uint32_t saint_entry_weight(const int64_t* __restrict
     return colcount_r + (uint32_t)(rowptr[c + 1] - rowptr[c]);
 }
 
-__device__ __forceinline__ int64_t saint_wave_incl_scan64(int64_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int64_t o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
 // colcount[c] += 1 for every stored entry with column c (colcount zeroed by the launcher): int32 atomics, any order, one result
 __global__ __launch_bounds__(256) void saint_colcount_k(const int32_t* __restrict__ col, int64_t nnz, int N,
                                                         int32_t* __restrict__ colcount, int32_t* status) {
@@ -208,12 +179,13 @@ __global__ __launch_bounds__(SAINT_THREADS) void saint_roww_scan_k(int64_t* __re
         int64_t v[8], s = 0;
 #pragma unroll
         for (int q = 0; q < 8; ++q) { v[q] = i0 + q < N ? roww[1 + i0 + q] : 0; s += v[q]; }
-        const int64_t inc = saint_wave_incl_scan64(s);
+        // (block_excl_scan_u64 in its private form: the shared one is 8 % slower here — profiles/block_prims_ab.txt)
+        const int64_t inc = (int64_t)wave_incl_scan64((unsigned long long)s);
         if (lane == 63) ws[w] = inc;
         __syncthreads();
         if (w == 0) {
             const int64_t x = lane < SAINT_THREADS / 64 ? ws[lane] : 0;
-            const int64_t xi = saint_wave_incl_scan64(x);
+            const int64_t xi = (int64_t)wave_incl_scan64((unsigned long long)x);
             if (lane < SAINT_THREADS / 64) ws[lane] = xi - x;
             if (lane == SAINT_THREADS / 64 - 1) ws[SAINT_THREADS / 64] = xi;
         }
@@ -224,22 +196,6 @@ __global__ __launch_bounds__(SAINT_THREADS) void saint_roww_scan_k(int64_t* __re
         for (int q = 0; q < 8; ++q) { run += v[q]; if (i0 + q < N) roww[1 + i0 + q] = run; }
         __syncthreads();
     }
-}
-
-// The largest i in [0, n) with cdf(i) <= t, where cdf(0) = 0 (never read), cdf(i) = arr[i + shift] for i >= 1, non-decreasing, and
-// 0 <= t < cdf(n).  64-ary: every lane probes one position per round, so a search of n entries is ceil(log64 n) dependent loads.
-// All 64 lanes call it with the same arguments.
-__device__ __forceinline__ int64_t saint_search64(const int64_t* __restrict__ arr, int shift, int64_t n, int64_t t) {
-    const int lane = threadIdx.x & 63;
-    int64_t lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int64_t step = (hi - lo + 63) >> 6;
-        const int64_t p = lo + (int64_t)(lane + 1) * step;
-        const bool le = p < hi && arr[p + shift] <= t;
-        lo += (int64_t)__popcll(__ballot(le)) * step;         // cdf is monotone: the lanes with cdf(p) <= t are the first ones
-        hi = min(hi, lo + step);
-    }
-    return lo;
 }
 
 // One wavefront per draw b < B.  t = draws[b], or mulhi64(word, total) of the 64-bit word (stream word 2b) << 32 | (stream word
@@ -267,13 +223,13 @@ __global__ __launch_bounds__(256) void saint_draw_k(
     int r = 0, c = 0;
     int64_t ent = 0;
     if (!bad) {                                                           // (wavefront-uniform)
-        r = (int)saint_search64(cdf, 0, N, t);
+        r = (int)wave_search64(cdf, 0, N, t);
         if (!edge) {
             ent = t;
         } else {
             const int64_t a = rowptr[r], e = rowptr[r + 1], base = (a >> 6) + r;
             int64_t u = t - roww[r];
-            const int64_t k = saint_search64(blockw + base, -1, (e - a + 63) >> 6, u);
+            const int64_t k = wave_search64(blockw + base, -1, (e - a + 63) >> 6, u);
             if (k > 0) u -= blockw[base + k - 1];
             const int64_t j = a + 64 * k + lane;
             const int cj = j < e ? col[j] : -1;
@@ -343,7 +299,7 @@ __global__ __launch_bounds__(SAINT_THREADS) void saint_edge_scan_k(const int32_t
     int s = 0;
     for (int i = lo; i < hi; ++i) s += cnt[i];
     int total;
-    int run = saint_block_scan(s, wsum, &total) - s;
+    int run = block_excl_scan(s, wsum, &total);
     for (int i = lo; i < min(lo + per, n_cap); ++i) {
         rowptr_l[i] = i < n ? run : total;
         if (i < n) run += cnt[i];
@@ -383,6 +339,27 @@ __global__ __launch_bounds__(256) void saint_edge_write_k(const int64_t* __restr
         base += __popcll(bal);
         if (base >= e_cap) break;
     }
+}
+
+// saint_masked_loss_k stays out of block_prims.h and row_loss.h: on block_excl_scan and the shared row routines the launch measured
+// 1 % slower in every arrangement tried (profiles/block_prims_ab.txt), so it keeps its own scan (inclusive, one value per thread,
+// blockDim.x == SAINT_THREADS; *total = the sum) and its own rows, in the CE_LOG_SUM_EXP order of row_loss.h
+__device__ __forceinline__ int saint_block_scan(int v, int* wsum, int* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int inc = wave_incl_scan(v);
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    if (w == 0) {
+        int s = lane < nw ? wsum[lane] : 0;
+        int si = wave_incl_scan(s);
+        if (lane < nw) wsum[lane] = si - s;          // exclusive prefix of the wavefront totals
+        if (lane == nw - 1) wsum[SAINT_THREADS / 64] = si;
+    }
+    __syncthreads();
+    inc += wsum[w];
+    *total = wsum[SAINT_THREADS / 64];
+    __syncthreads();
+    return inc;
 }
 
 // ONE workgroup.  Rows i < count of z [n_cap, ldz] are the batch's logits (row i = node node_idx[i]); the training rows are those

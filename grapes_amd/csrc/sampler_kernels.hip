@@ -964,19 +964,6 @@ __device__ __forceinline__ uint4 ld_agent_x4(const uint32_t* p) {
     asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(r) : "v"(p) : "memory");
     return make_uint4(r.x, r.y, r.z, r.w);
 }
-// exclusive scan over the workgroup on ONE barrier: `buf` (NW ints) must not be in use by a scan that some wavefront may still read
-template <int NW>
-__device__ __forceinline__ int block_scan_1b(int v, int* buf, int* total) {
-    const int lane = lane_id(), wid = threadIdx.x >> 6;
-    const int incl = wave_incl_scan(v);
-    if (lane == 63) buf[wid] = incl;
-    lds_barrier();                                           // (LDS only: __syncthreads would wait for every store / atomic in flight)
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) { const int x = buf[w]; tot += x; base += w < wid ? x : 0; }
-    *total = tot;
-    return base + incl - v;
-}
 
 // A draw of more than DRAW_MAX_LIVE blocks of candidates (n > 196,608): the first DRAW_MAX_LIVE workgroups take the blocks
 // b = bid, bid + DRAW_MAX_LIVE, ... — keys, log-sigmoids to memory (agent-scope stores), statistics partials per BLOCK — meet at the

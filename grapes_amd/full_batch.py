@@ -32,7 +32,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from .main import _EAGER_CLASSIFIERS, _bool, build_gcn2, build_pna, check_classifier, load_data, read_config_file
+from .main import _EAGER_CLASSIFIERS, _bool, _large_flag, build_gcn2, build_pna, check_classifier, load_data, read_config_file
 
 # (name, type, default) — full-batch.py:26-50
 _FLAGS = [
@@ -77,10 +77,6 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     if getattr(args, "classifier", "gcn") in _EAGER_CLASSIFIERS:
         check_classifier(args)
     return args
-
-
-def _large_flag(v: str) -> Optional[bool]:
-    return {"auto": None, "true": True, "false": False}[v]
 
 
 def train(args, device=None, log=print) -> float:

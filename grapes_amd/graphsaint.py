@@ -27,7 +27,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from .main import _bool, load_data
+from .main import _bool, _large_flag, load_data
 
 
 def _parser() -> argparse.ArgumentParser:
@@ -88,10 +88,6 @@ def _f1(y_pred, y_true) -> float:
         return 2 * (precision * recall) / (precision + recall)
     except ZeroDivisionError:
         return 0.0
-
-
-def _large_flag(v: str) -> Optional[bool]:
-    return {"auto": None, "true": True, "false": False}[v]
 
 
 def run(args, device=None, log=print) -> float:

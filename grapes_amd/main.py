@@ -113,6 +113,11 @@ def _bool(v: str) -> bool:
     raise argparse.ArgumentTypeError(f"expected true/false, got {v!r}")
 
 
+def _large_flag(v: str) -> Optional[bool]:
+    """--large-graph auto / true / false of the full-batch and GraphSAINT drivers"""
+    return {"auto": None, "true": True, "false": False}[v]
+
+
 def _parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="grapes_amd.main", description=__doc__.split("\n\n")[0])
     for name, typ, default in _FLAGS + _EXTRA:

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 from typing import List, Optional
 
+import ctypes as _C
 import os
 
 import torch
@@ -178,9 +179,8 @@ def frontier_expand(rowptr, col, nodes, eoff, e_cap, d_m=None, want_pos=False, s
     return src, dst, pos
 
 
-class _SliceRemarkArgs(__import__("ctypes").Structure):
+class _SliceRemarkArgs(_C.Structure):
     """include/grapes_hip.h: grapes_slice_remark_args"""
-    _C = __import__("ctypes")
     _fields_ = [("mult", _C.c_void_p), ("unmark_ids", _C.c_void_p), ("n_unmark", _C.c_int32), ("d_n_unmark", _C.c_void_p),
                 ("mark_ids", _C.c_void_p), ("n_mark", _C.c_int32), ("d_n_mark", _C.c_void_p), ("clear_bits", _C.c_void_p),
                 ("clear_ids", _C.c_void_p), ("n_clear", _C.c_int32), ("d_n_clear", _C.c_void_p)]
@@ -203,24 +203,21 @@ def _remark_args(remark):
     return a, C.byref(a)
 
 
-class _DrawFinishArgs(__import__("ctypes").Structure):
+class _DrawFinishArgs(_C.Structure):
     """include/grapes_hip.h: grapes_draw_finish_args (filled by grapes_gumbel_topk_deferred)"""
-    _C = __import__("ctypes")
     _fields_ = [("parts_keys", _C.c_void_p), ("parts_emit", _C.c_void_p), ("sel", _C.c_void_p), ("keys_blocks", _C.c_int32),
                 ("emit_block", _C.c_int32), ("n_host", _C.c_int32), ("d_n", _C.c_void_p), ("stats", _C.c_void_p),
                 ("hist", _C.c_void_p), ("hist_words", _C.c_int32), ("stats_blocks", _C.c_int32)]
 
 
-class _HopCountArgs(__import__("ctypes").Structure):
+class _HopCountArgs(_C.Structure):
     """include/grapes_hip.h: grapes_hop_count_args"""
-    _C = __import__("ctypes")
     _fields_ = [("indeg", _C.c_void_p), ("loops", _C.c_void_p), ("seginfo", _C.c_void_p), ("wsum", _C.c_void_p),
                 ("slot", _C.c_void_p), ("n_long", _C.c_void_p)]
 
 
-class _HopDegreeArgs(__import__("ctypes").Structure):
+class _HopDegreeArgs(_C.Structure):
     """include/grapes_hip.h: grapes_hop_degree_args"""
-    _C = __import__("ctypes")
     _fields_ = [("indeg", _C.c_void_p), ("loops", _C.c_void_p), ("seginfo", _C.c_void_p), ("wsum", _C.c_void_p),
                 ("rowptr_t", _C.c_void_p), ("rowptr_s", _C.c_void_p), ("dinv", _C.c_void_p), ("seg_first", _C.c_void_p),
                 ("row_loops", _C.c_void_p), ("long_items", _C.c_void_p), ("n_long", _C.c_void_p), ("item_cap", _C.c_int32),

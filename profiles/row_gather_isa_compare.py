@@ -1,16 +1,23 @@
 #!/usr/bin/env python3
-"""Same machine code?  Compiles gat_kernels.hip, gcn2_kernels.hip and pna_kernels.hip of two source trees for the device only
-(the Makefile's flags + --cuda-device-only -S, no GPU needed) and compares the gfx950 assembly kernel by kernel.
+"""Same machine code?  Compiles translation units of two source trees for the device only (the Makefile's flags +
+--cuda-device-only -S, no GPU needed) and compares the gfx950 assembly kernel by kernel.  Without --files: gat_kernels.hip,
+gcn2_kernels.hip and pna_kernels.hip, as for the row-gather scaffold.
 
     python profiles/row_gather_isa_compare.py PARENT_CSRC [RESULT_CSRC] > profiles/row_gather_isa_compare.txt
+    python profiles/row_gather_isa_compare.py --files hop_unity.hip,loss_kernels.hip --no-diffs PARENT_CSRC > report.txt
+
+  --files A,B,...  the translation units to compare; then a rise of ANY kernel's count fails, not only a GAT *_chunks_k kernel's
+  --no-diffs       list the kernels that differ with their counts, without the instruction diffs
 
   - every kernel symbol of the parent must exist in the result, and no new one may appear;
   - a kernel's instruction stream is compared after comments are dropped and basic-block labels renumbered in order of appearance;
   - the three GAT *_chunks_k families took the strict item decode on purpose: for them the register, scratch and LDS counts of
     the code object's metadata must not rise;
-  - every other kernel that differs is listed with its counts; the diff itself is printed for the first instantiation of each
-    kernel template (the others of a template differ the same way; --all-diffs prints them all).
-Exit status 1 when a symbol is missing or new or a count of a GAT *_chunks_k kernel rises."""
+  - every other kernel that differs — in its instructions, or in its counts alone — is listed with its counts; the diff itself
+    is printed for the first instantiation of each kernel template (the others of a template differ the same way; --all-diffs
+    prints them all).
+Exit status 1 when a symbol is missing or new, a count of a GAT *_chunks_k kernel rises or, with --files, any kernel's."""
+import argparse
 import difflib
 import os
 import re
@@ -21,13 +28,14 @@ import tempfile
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "--cuda-device-only", "-S"]
 FILES = ["gat_kernels.hip", "gcn2_kernels.hip", "pna_kernels.hip"]
+EXTRA = {"sampler_kernels.hip": ["-ffp-contract=off"]}                      # (the Makefile's EXTRA_<unit>)
 EXPECTED = ("gat_fwd_chunks_k", "gat_bwd_dst_chunks_k", "gat_bwd_src_chunks_k")
 COUNTS = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size")
 
 
 def assembly(csrc, name, tmp):
     out = os.path.join(tmp, name + ".s")
-    subprocess.run([HIPCC] + FLAGS + [os.path.join(csrc, name), "-o", out], check=True)
+    subprocess.run([HIPCC] + FLAGS + EXTRA.get(name, []) + [os.path.join(csrc, name), "-o", out], check=True)
     return open(out).read()
 
 
@@ -49,10 +57,10 @@ def kernels(text):
     return {nm: (body[nm], meta[nm]) for nm in meta}
 
 
-def main(parent, result, all_diffs=False):
+def main(parent, result, all_diffs=False, files=None, no_diffs=False):
     bad, other, shown = 0, 0, set()
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
-        for name in FILES:
+        for name in files or FILES:
             a, b = kernels(assembly(parent, name, ta)), kernels(assembly(result, name, tb))
             missing, new = sorted(set(a) - set(b)), sorted(set(b) - set(a))
             same = [k for k in a if k in b and a[k][0] == b[k][0]]
@@ -67,13 +75,19 @@ def main(parent, result, all_diffs=False):
                     continue
                 expected = any(e in k for e in EXPECTED)
                 rises = [c for c in COUNTS if b[k][1][c] > a[k][1][c]]
-                print(f"  {'differs (strict item decode)' if expected else 'DIFFERS'}: {k}")
+                if a[k][0] == b[k][0]:
+                    print(f"  same instructions, other counts: {k}")
+                else:
+                    print(f"  {'differs (strict item decode)' if expected else 'DIFFERS'}: {k}")
                 print(f"      instructions {len(a[k][0])} -> {len(b[k][0])}; " +
                       ", ".join(f"{c} {a[k][1][c]} -> {b[k][1][c]}" for c in COUNTS) + ("; RISES: " + ", ".join(rises) if rises else ""))
                 if expected:
                     bad += 1 if rises else 0
                     continue
                 other += 1
+                bad += 1 if files and rises else 0
+                if no_diffs:
+                    continue
                 diff = list(difflib.unified_diff(a[k][0], b[k][0], "parent", "result", lineterm="", n=1))
                 template = k.split("ILi")[0]
                 if all_diffs or template not in shown:
@@ -81,12 +95,16 @@ def main(parent, result, all_diffs=False):
                 else:
                     print(f"      ({sum(d[0] == '-' for d in diff[2:])} lines removed, {sum(d[0] == '+' for d in diff[2:])} added: like the template's first instantiation above)")
                 shown.add(template)
-    print(f"result: {'FAIL' if bad else 'ok'} (symbols equal and no count of a GAT *_chunks_k kernel rises); "
+    print(f"result: {'FAIL' if bad else 'ok'} (symbols equal and no count of {'any' if files else 'a GAT *_chunks_k'} kernel rises); "
           f"{other} other kernels differ, listed above")
     return 1 if bad else 0
 
 
 if __name__ == "__main__":
     here = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "grapes_amd", "csrc")
-    args = [a for a in sys.argv[1:] if a != "--all-diffs"]
-    sys.exit(main(args[0], args[1] if len(args) > 1 else here, all_diffs="--all-diffs" in sys.argv))
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("parent"); ap.add_argument("result", nargs="?", default=here)
+    ap.add_argument("--files", type=lambda v: v.split(","))
+    ap.add_argument("--all-diffs", action="store_true"); ap.add_argument("--no-diffs", action="store_true")
+    a = ap.parse_args()
+    sys.exit(main(a.parent, a.result, all_diffs=a.all_diffs, files=a.files, no_diffs=a.no_diffs))
