@@ -94,6 +94,14 @@ SIGNATURES = {
     "grapes_gcn2_propagate_bwd": (I32, [P, P, I32, P, P, P, P, F32, P, P, I32, I32, P, I32, P, P, I32, P, P, P]),
     "grapes_gcn2_mix_fwd": (I32, [P, P, P, F32, F32, F32, I32, P, I32, P, I32, P]),
     "grapes_gcn2_mix_bwd": (I32, [P, P, I32, F32, F32, F32, P, P, P, I32, P, I32, P]),
+    # GCNConv with edge weights (PyG GCNConv.forward(x, edge_index, edge_weight))
+    "grapes_wgcn_structure_workspace_bytes": (SZ, [I32]),
+    "grapes_wgcn_structure": (I32, [P, P, I32, P, I32, P] + [P] * 12),
+    "grapes_wgcn_weights": (I32, [P, I32, P, P, P, P, P, I32, P, P, P, P, P, P]),
+    "grapes_wgcn_aggregate_workspace_bytes": (SZ, [I32, I32]),
+    "grapes_wgcn_aggregate_fwd": (I32, [P] * 8 + [I32, P, I32, I32, P, P, I32, P, P, P]),
+    "grapes_wgcn_aggregate_bwd_workspace_bytes": (SZ, [I32, I32, I32, I32]),
+    "grapes_wgcn_aggregate_bwd": (I32, [P] * 5 + [I32] + [P] * 14 + [I32, P, I32, P, P, P, P, I32, P, P, P]),
     "grapes_pna_aggregate_fwd_workspace_bytes": (SZ, [I32, I32]),
     "grapes_pna_aggregate_fwd": (I32, [P, P, P, I32, P, P, P, I32, I32, I32, I32, F32, F32, P, P, I32, P, I32, P, P, I32, P, P, P]),
     "grapes_pna_aggregate_bwd_workspace_bytes": (SZ, [I32, I32, I32]),

@@ -67,6 +67,38 @@ def clear_prepare_cache():
     _PREP_CACHE.clear()
 
 
+def weighted_structure(edge_index, n: int) -> ops.WeightedStructure:
+    """The slots of every entry of an edge-index tensor in its PreparedGraph (ops.WeightedStructure), built once and cached
+    beside the PreparedGraph, keyed on the tensor like it.  The weights are never cached."""
+    prep = prepare_edges(edge_index, n)
+    key = id(edge_index)
+    hit = _PREP_CACHE.get(key)
+    if hit is not None and hit[3] is prep and len(hit) > 4:
+        return hit[4]
+    ei = edge_index.to(torch.int32)
+    ws = ops.WeightedStructure(prep, ei[0].contiguous(), ei[1].contiguous())
+    if hit is not None and hit[3] is prep:
+        _PREP_CACHE[key] = hit[:4] + (ws,)
+    return ws
+
+
+def _check_edge_weight(edge_index, edge_weight, large_graph, who: str):
+    """ValueError unless edge_weight is one fp32 value per column of an edge-index TENSOR on the same device."""
+    if not torch.is_tensor(edge_index) or large_graph:
+        raise ValueError(f"{who}: edge_weight goes with an edge-index tensor [2, e]; the DeviceGraph / PreparedGraph / large-graph "
+                         "paths are unweighted")
+    if not torch.is_tensor(edge_weight):
+        raise ValueError(f"{who}: edge_weight must be a tensor")
+    if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError(f"{who}: edge_index must be [2, e]")
+    if edge_weight.dim() != 1 or edge_weight.numel() != edge_index.shape[1]:
+        raise ValueError(f"{who}: edge_weight {tuple(edge_weight.shape)} must hold one value per entry ({edge_index.shape[1]})")
+    if edge_weight.dtype != torch.float32:
+        raise ValueError(f"{who}: edge_weight must be float32, got {edge_weight.dtype}")
+    if edge_weight.device != edge_index.device:
+        raise ValueError(f"{who}: edge_weight is on {edge_weight.device}, edge_index on {edge_index.device}")
+
+
 class _GCNConvFn(torch.autograd.Function):
     """out = Â (X Wᵀ) + b (PyG order).  When the input needs no gradient and F_in < F_out the same value is
     computed aggregate-first, act((Â X) Wᵀ + b): the SpMM runs on the narrow side, bias/ReLU ride in the GEMM
@@ -100,8 +132,57 @@ class _GCNConvFn(torch.autograd.Function):
         return dx, dw, dbias, None, None
 
 
+class _WeightedGCNConvFn(torch.autograd.Function):
+    """_GCNConvFn with edge weights (PyG gcn_norm with edge_weight, ops.wgcn_*): the same transform-first / aggregate-first rule
+    and the same GEMMs.  The edge-weight gradient (formed only when edge_weight needs one) is that of the aggregation
+    out' = Â_w H with G = d out': transform-first H = X Wᵀ and G = the gated dout; aggregate-first H = X and
+    G = linear_bwd_input(gated dout, W)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, edge_weight, ws, relu):
+        f_out, f_in = weight.shape
+        d_n = ws.prep.d_n
+        vals = ops.wgcn_weights(ws, edge_weight.detach().contiguous())
+        ctx.ws, ctx.vals, ctx.relu = ws, vals, relu
+        ctx.want_dw = ctx.needs_input_grad[3]
+        ctx.agg_first = (not ctx.needs_input_grad[0]) and f_in < f_out and f_out > 1
+        if ctx.agg_first:
+            ax = ops.wgcn_aggregate_fwd(x, ws, vals)                             # Â_w X      (gather, narrow rows)
+            out = ops.linear_bias_act_fwd(ax, weight, bias, relu, d_n=d_n)       # (Â_w X) Wᵀ + b, ReLU  (MFMA)
+            ctx.save_for_backward(ax, weight, out if relu else None, x if ctx.want_dw else None)
+            return out
+        h = ops.linear_fwd(x, weight, d_n=d_n)                                   # H = X W^T   (MFMA fp32)
+        out = ops.wgcn_aggregate_fwd(h, ws, vals, bias, relu)                    # weighted gather + bias (+ReLU)
+        ctx.save_for_backward(x, weight, out if relu else None, h if ctx.want_dw else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        first, weight, out, h = ctx.saved_tensors
+        ws, vals, d_n = ctx.ws, ctx.vals, ctx.ws.prep.d_n
+        dout = dout.contiguous()
+        if ctx.agg_first:
+            dw = dbias = dew = None
+            if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+                dw, dbias = ops.linear_bwd_weight_gated(dout, first, gate=out if ctx.relu else None, d_n=d_n)
+            if ctx.want_dw:
+                g = ops.gcn2_mix_bwd(dout, out, True, 1.0, d_n=d_n)[0] if ctx.relu else dout
+                dax = ops.linear_bwd_input(g, weight, d_n=d_n)
+                dew = ops.wgcn_aggregate_bwd(dax, ws, vals, h=h, want_dh=False, want_dw=True, want_bias=False)[2]
+            return None, dw, dbias, dew, None, None
+        dh, dbias, dew = ops.wgcn_aggregate_bwd(dout, ws, vals, h=h, relu_out=out if ctx.relu else None,
+                                                want_dh=ctx.needs_input_grad[0] or ctx.needs_input_grad[1], want_dw=ctx.want_dw,
+                                                want_bias=ctx.needs_input_grad[2])
+        dw = ops.linear_bwd_weight(dh, first, d_n=d_n) if ctx.needs_input_grad[1] else None
+        dx = ops.linear_bwd_input(dh, weight, d_n=d_n) if ctx.needs_input_grad[0] else None
+        return dx, dw, dbias, dew, None, None
+
+
 class GCNConv(nn.Module):
-    """out = D^-1/2 (A + I) D^-1/2 · X Wᵀ + b with PyG's conventions."""
+    """out = D^-1/2 (A + I) D^-1/2 · X Wᵀ + b with PyG's conventions.  With edge_weight [e] (PyG's third
+    argument): out = D^-1/2 (A_w + diag(lw)) D^-1/2 · X Wᵀ + b, where A_w sums the weights of the non-loop entries (duplicates each
+    count), lw[i] = 1 or the weight of the LAST stored entry (i, i), and D = the weighted in-degree + lw.  A negative degree gives
+    NaN, as in PyG; it is not checked."""
 
     def __init__(self, in_channels: int, out_channels: int):
         super().__init__()
@@ -116,9 +197,17 @@ class GCNConv(nn.Module):
             self.lin.weight.uniform_(-a, a)
             self.bias.zero_()
 
-    def forward(self, x, edge_index, relu: bool = False, large_graph: Optional[bool] = None):
+    def forward(self, x, edge_index, relu: bool = False, large_graph: Optional[bool] = None, edge_weight=None):
+        if edge_weight is not None:
+            _check_edge_weight(edge_index, edge_weight, large_graph, "GCNConv")
         if not x.is_cuda:
             raise ops._lib.GrapesHipError("GCNConv input must be a cuda tensor (grapes_amd has no CPU path)")
+        if edge_weight is not None:
+            x = x.contiguous()
+            if x.dtype != torch.float32:
+                x = x.float()
+            ws = weighted_structure(edge_index, x.shape[0])
+            return _WeightedGCNConvFn.apply(x, self.lin.weight, self.bias, edge_weight, ws, relu)
         if _large(edge_index, large_graph):                    # a DeviceGraph with 2^31+ entries (or forced): full_graph.py
             return full_graph.conv_forward(self, x, edge_index, relu)
         x = x.contiguous()
@@ -224,9 +313,23 @@ class GCN(nn.Module):
             return _PhiloxDropoutFn.apply(x, float(self.dropout), seed, offset)
         return F.dropout(x, p=self.dropout, training=self.training)
 
-    def forward(self, x: torch.Tensor, edge_index: Union[torch.Tensor, "list[torch.Tensor]"], large_graph: Optional[bool] = None):
+    def forward(self, x: torch.Tensor, edge_index: Union[torch.Tensor, "list[torch.Tensor]"], large_graph: Optional[bool] = None,
+                edge_weight=None):
         """large_graph: None = automatic — a DeviceGraph with 2^31 or more entries runs the row-blocked 64-bit pass of
-        full_graph.py (inference only); True forces that pass on any DeviceGraph."""
+        full_graph.py (inference only); True forces that pass on any DeviceGraph.
+        edge_weight: one fp32 vector for an edge-index tensor, or for a list of edge lists a list of equal length (entries may be
+        None), indexed exactly as the edges are: [-i] for hidden layer i, [0] for the last."""
+        if edge_weight is not None:
+            if type(edge_index) == list:
+                if type(edge_weight) != list or len(edge_weight) != len(edge_index):
+                    raise ValueError("GCN: a list of edge lists takes a list of edge weights of equal length (entries may be None)")
+                for ei, ew in zip(edge_index, edge_weight):
+                    if ew is not None:
+                        _check_edge_weight(ei, ew, large_graph, "GCN")
+            elif type(edge_weight) == list:
+                raise ValueError("GCN: a list of edge weights goes with a list of edge lists")
+            else:
+                _check_edge_weight(edge_index, edge_weight, large_graph, "GCN")
         if _large(edge_index, large_graph):                                   # eval.py:50 on papers100M-sized graphs
             return full_graph.gcn_forward(self, x, edge_index), _memory_allocated_mb()
         layerwise_adjacency = type(edge_index) == list
@@ -236,10 +339,12 @@ class GCN(nn.Module):
         for i in range(1, n_layers):
             layer = self.gcn_layers[i - 1]
             edges = edge_index[-i] if layerwise_adjacency else edge_index      # gcn.py:31
-            x = layer(x, edges, relu=True)                                     # gcn.py:32 (ReLU fused)
+            w = edge_weight[-i] if (layerwise_adjacency and edge_weight is not None) else edge_weight
+            x = layer(x, edges, relu=True, edge_weight=w)                      # gcn.py:32 (ReLU fused)
             x = self._drop(x)                                                  # gcn.py:33
         edges = edge_index[0] if layerwise_adjacency else edge_index           # gcn.py:35
-        logits = self.gcn_layers[n_layers - 1](x, edges)
+        w = edge_weight[0] if (layerwise_adjacency and edge_weight is not None) else edge_weight
+        logits = self.gcn_layers[n_layers - 1](x, edges, edge_weight=w)
         logits = self._drop(logits)                                            # gcn.py:37
         memory_alloc = _memory_allocated_mb()                                  # gcn.py:40
         return logits, memory_alloc

@@ -16,7 +16,8 @@ every node-sized tensor gathered at node_idx.  The three samplers differ in the 
   rand(B, E).log() / (prob + 1e-10) per row, which is one weighted draw per row: the distribution is built here, not the key
   arithmetic, and the 1e-10 is dropped — an entry of weight 0 is never drawn.
 
-sample_coverage > 0 (GraphSAINT's node / edge normalisation) is not built: the reference runs with sample_coverage 0.
+sample_coverage > 0 (GraphSAINT's node / edge normalisation) is not built: the reference runs with sample_coverage 0.  The weighted
+layer its edge_norm needs now exists (modules.gcn.GCNConv.forward(..., edge_weight=)); the coverage counts themselves do not.
 
 The draws come from the project's Philox stream (seed, device offset): see ops.saint_walk_nodes, ops.saint_draw_nodes and DESIGN.md.
 """

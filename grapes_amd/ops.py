@@ -1748,6 +1748,103 @@ def pna_add_input_grad(dx, dz, d_n=None):
     return dx
 
 
+# ------------------------------------------------------------------------------- GCNConv with edge weights (PyG GCNConv.forward)
+def _wgcn_width(f: int):
+    if f < 1 or f > 1024 or (f > 256 and f % 4):
+        raise ValueError(f"weighted GCN aggregation: width {f} is not built (any width up to 256, multiples of 4 up to 1024)")
+
+
+class WeightedStructure:
+    """Where every entry of an edge list sits in the two CSRs of the PreparedGraph built from it: pos_t / pos_s [e] (slot by target
+    / by source, -1 for a stored loop or a dropped entry), their inverses inv_t / inv_s, and loop_src [n] (the input index of the
+    stored loop that sets a node's loop weight — the last one in input order — or -1).  Built once per edge list; the weights
+    themselves go through wgcn_weights on every call.  Duplicates of one (r, c) take adjacent slots in input order."""
+
+    __slots__ = ("prep", "edge_src", "edge_dst", "n", "e", "pos_t", "pos_s", "inv_t", "inv_s", "loop_src")
+
+    def __init__(self, prep: PreparedGraph, edge_src, edge_dst):
+        _chk(edge_src, _i32, "edge_src"); _chk(edge_dst, _i32, "edge_dst")
+        e = edge_src.numel()
+        if edge_dst.numel() != e or e != prep.e:
+            raise ValueError("WeightedStructure: edge_src / edge_dst must be the list the PreparedGraph was built from")
+        dev = edge_src.device
+        self.prep, self.edge_src, self.edge_dst, self.n, self.e = prep, edge_src, edge_dst, prep.n, e
+        self.pos_t = torch.empty(max(e, 1), dtype=_i32, device=dev); self.pos_s = torch.empty(max(e, 1), dtype=_i32, device=dev)
+        self.inv_t = torch.empty(max(e, 1), dtype=_i32, device=dev); self.inv_s = torch.empty(max(e, 1), dtype=_i32, device=dev)
+        self.loop_src = torch.empty(max(prep.n, 1), dtype=_i32, device=dev)
+        ws = _ws(lib().grapes_wgcn_structure_workspace_bytes(e), dev)
+        _lib.check(lib().grapes_wgcn_structure(_p(edge_src), _p(edge_dst), e, _p(prep.d_e), prep.n, _p(prep.d_n), _p(prep.rowptr_t),
+                                               _p(prep.csr_src), _p(prep.rowptr_s), _p(prep.csr_dst), _p(self.pos_t), _p(self.pos_s),
+                                               _p(self.inv_t), _p(self.inv_s), _p(self.loop_src), _p(ws), _p(prep.status), _stream()),
+                   "wgcn_structure")
+
+
+class WeightedValues:
+    """What wgcn_weights makes of one weight vector: val_t / val_s (the weights in both CSR orders), lw (the loop weights) and
+    dinv = (lw + the weighted in-degree)^-1/2 (inf -> 0; a negative degree gives NaN, as in PyG)."""
+
+    __slots__ = ("val_t", "val_s", "lw", "dinv")
+
+
+def wgcn_weights(ws: WeightedStructure, edge_weight) -> WeightedValues:
+    _chk(edge_weight, _f32, "edge_weight")
+    if edge_weight.numel() != ws.e:
+        raise ValueError(f"edge_weight holds {edge_weight.numel()} values for {ws.e} entries")
+    dev, prep = edge_weight.device, ws.prep
+    v = WeightedValues()
+    v.val_t = torch.empty(max(ws.e, 1), dtype=_f32, device=dev); v.val_s = torch.empty(max(ws.e, 1), dtype=_f32, device=dev)
+    v.lw = torch.empty(max(ws.n, 1), dtype=_f32, device=dev); v.dinv = torch.empty(max(ws.n, 1), dtype=_f32, device=dev)
+    _lib.check(lib().grapes_wgcn_weights(_p(edge_weight), ws.e, _p(ws.inv_t), _p(ws.inv_s), _p(ws.loop_src), _p(prep.rowptr_t),
+                                         _p(prep.rowptr_s), ws.n, _p(prep.d_n), _p(v.val_t), _p(v.val_s), _p(v.lw), _p(v.dinv),
+                                         _stream()), "wgcn_weights")
+    return v
+
+
+def wgcn_aggregate_fwd(h, ws: WeightedStructure, vals: WeightedValues, bias=None, relu=False, out=None):
+    """out[c] = dinv[c] sum_{e: r -> c} w_e dinv[r] h[r] + dinv[c]^2 lw[c] h[c] + bias (+ReLU) over the first ws.n rows of h (h and
+    out may hold more rows, which are left alone)."""
+    _chk(h, _f32, "h"); _chk(bias, _f32, "bias", True); _chk(out, _f32, "out", True)
+    prep, (rows, f) = ws.prep, h.shape
+    _wgcn_width(f)
+    if out is None:
+        out = torch.empty_like(h)
+    if rows < ws.n or out.shape[0] < ws.n or out.shape[1] != f or (bias is not None and bias.numel() != f):
+        raise ValueError("h and out need one row of the same width per node of the structure's graph, bias one value per column")
+    items, n_items, cap = _long_items(prep, by_target=True, forward=True)
+    wsp = _ws(lib().grapes_wgcn_aggregate_workspace_bytes(cap, f), h.device) if cap else None
+    _lib.check(lib().grapes_wgcn_aggregate_fwd(_p(h), _p(prep.rowptr_t), _p(prep.csr_src), _p(vals.val_t), _p(vals.dinv), _p(vals.lw),
+                                               _p(bias), _p(out), ws.n, _p(prep.d_n), f, 1 if relu else 0, items, n_items, cap,
+                                               _p(wsp), _p(prep.status), _stream()), "wgcn_aggregate_fwd")
+    return out
+
+
+def wgcn_aggregate_bwd(dout, ws: WeightedStructure, vals: WeightedValues, h=None, relu_out=None, want_dh=True, want_dw=False,
+                       want_bias=True):
+    """(dh, dbias, dw) of wgcn_aggregate_fwd + wgcn_weights: dout gated by relu_out > 0 when given; dw (the gradient of the edge
+    weights, in input order, through the normalisation too) needs h, the forward's input.  dout is not modified."""
+    _chk(dout, _f32, "dout"); _chk(relu_out, _f32, "relu_out", True); _chk(h, _f32, "h", True)
+    prep, (rows, f) = ws.prep, dout.shape
+    _wgcn_width(f)
+    if rows < ws.n or (relu_out is not None and relu_out.shape != dout.shape) or (h is not None and h.shape != dout.shape):
+        raise ValueError("dout, relu_out and h must be [>= n, f] over the structure's nodes")
+    if want_dw and h is None:
+        raise ValueError("the edge-weight gradient needs h, the aggregation's input")
+    if not (want_dh or want_dw or want_bias):
+        return None, None, None
+    dev = dout.device
+    dh = torch.empty_like(dout) if want_dh else None
+    dbias = torch.empty(f, dtype=_f32, device=dev) if want_bias else None
+    dw = torch.empty(max(ws.e, 1), dtype=_f32, device=dev)[: ws.e] if want_dw else None
+    items_t, n_items_t, cap = _long_items(prep, by_target=True, forward=False)
+    items_s, n_items_s, _ = _long_items(prep, by_target=False, forward=False)
+    wsp = _ws(lib().grapes_wgcn_aggregate_bwd_workspace_bytes(ws.n, ws.e, cap, f), dev)
+    _lib.check(lib().grapes_wgcn_aggregate_bwd(_p(dout), _p(relu_out), _p(h) if want_dw else None, _p(ws.edge_src), _p(ws.edge_dst),
+                                               ws.e, _p(prep.d_e), _p(ws.pos_t), _p(ws.loop_src), _p(prep.rowptr_t), _p(prep.csr_src),
+                                               _p(vals.val_t), _p(prep.rowptr_s), _p(prep.csr_dst), _p(vals.val_s), _p(vals.dinv),
+                                               _p(vals.lw), _p(dh), _p(dbias), _p(dw), ws.n, _p(prep.d_n), f, items_t, n_items_t,
+                                               items_s, n_items_s, cap, _p(wsp), _p(prep.status), _stream()), "wgcn_aggregate_bwd")
+    return dh, dbias, dw
+
 
 # ------------------------------------------------------------------------------- sampler
 def gumbel_topk(logits, k, uniforms=None, logit_index=None, candidate_ids=None, n=None, d_n=None, mode=0,

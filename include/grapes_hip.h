@@ -54,7 +54,8 @@ extern "C" {
  * grapes_gat_aggregate_fwd / _bwd (+ _workspace_bytes each); the GCN2 classifier (modules/gcn.py:76-117) —
  * grapes_gcn2_loop_counts(_csr), grapes_gcn2_propagate_fwd / _bwd (+ _workspace_bytes), grapes_gcn2_mix_fwd / _bwd; the PNA
  * classifier (modules/gcn.py:120-149) — grapes_pna_aggregate_fwd / _bwd (+ _workspace_bytes each), grapes_pna_add_input_grad; GraphSAINT's node and edge
- * samplers — grapes_saint_edge_weights, grapes_saint_draw_nodes. */
+ * samplers — grapes_saint_edge_weights, grapes_saint_draw_nodes; GCNConv with edge weights — grapes_wgcn_structure(_workspace_bytes),
+ * grapes_wgcn_weights, grapes_wgcn_aggregate_fwd / _bwd (+ _workspace_bytes each). */
 #define GRAPES_ABI_VERSION 302
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -732,6 +733,68 @@ int grapes_gcn2_mix_fwd(const float* s, const float* t1, const float* t2, float 
  * (g1, g2 optional; out may be NULL when relu == 0). */
 int grapes_gcn2_mix_bwd(const float* dout, const float* out, int32_t relu, float c0, float c1, float c2, float* g0, float* g1,
                         float* g2, int32_t n, const int32_t* d_n, int32_t f, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ GCNConv with edge weights (csrc/wgcn_kernels.hip)
+ * modules/gcn.py:9-42 builds its layers from PyG's GCNConv, whose forward is forward(x, edge_index, edge_weight=None)
+ * (torch_geometric 2.5.2, not in the reference tree).  With weights, gcn_norm(edge_index, edge_weight, add_self_loops=True,
+ * improved=False, flow='source_to_target') is
+ *   add_remaining_self_loops(fill_value=1): non-loop entries keep their weights; every node gets ONE loop of weight lw[i] = 1,
+ *     or the weight of its stored entry (i, i) — of the LAST one in input order when there are several (PyG assigns them by
+ *     index-put; the rule is fixed here so that the result is a function of the input);
+ *   deg[c] = lw[c] + sum of w_e over the non-loop entries into c;  dinv = deg^-1/2, inf -> 0.  A negative degree gives NaN, as in
+ *     PyG; it is not checked;
+ *   out[c] = dinv[c] sum_{e: r -> c} w_e dinv[r] H[r] + dinv[c]^2 lw[c] H[c] + bias   (duplicates each count; a weight 0 is legal)
+ * over the CSRs of grapes_gcn_prepare (ascending neighbour ids per row, stored loops and out-of-range entries dropped).  Widths:
+ * any f <= 256; f % 4 == 0 with 16-byte aligned rows up to 1024.  No floating-point atomics: every sum has a fixed order (slot
+ * order inside a row, chunk order across work items, a fixed tree across partials) and duplicates sit in input order, so results
+ * are bit-identical from run to run.  status: GRAPES_STATUS_BAD_INDEX when an entry finds no slot or a CSR entry is outside [0, n).
+ * Operands are taken to be finite: a lane without an entry adds 0 * (the row's own operand), so an inf / NaN in H[c] (forward) or
+ * G[r] (backward) reaches that row's sums even where its coefficient is 0. */
+/* The structure pass, once per edge list (replaces the bookkeeping of add_remaining_self_loops, gcn_norm's first call): for input
+ * entry i, pos_t[i] / pos_s[i] [e] = its slot in the by-target / by-source CSR (-1: a stored loop or a dropped entry), inv_t / inv_s
+ * [e] the inverse maps (slot -> input entry), loop_src [n] = the input index of the stored loop that sets lw, or -1.  edge_src /
+ * edge_dst / e / d_e / n / d_n: the list grapes_gcn_prepare was given (without a node_map).  Duplicates of one (r, c) take adjacent
+ * slots in input order.  Cost: one binary search per entry, plus L reads per member of a run of L duplicates of one (r, c) — L^2 per
+ * run, and the L claims of a run share one atomic counter: meant for multigraphs whose runs are short (a pair repeated 10^4 times
+ * costs 10^8 reads, once per edge list).  workspace: grapes_wgcn_structure_workspace_bytes(e), 16-byte aligned. */
+size_t grapes_wgcn_structure_workspace_bytes(int32_t e);
+int grapes_wgcn_structure(const int32_t* edge_src, const int32_t* edge_dst, int32_t e, const int32_t* d_e, int32_t n,
+                          const int32_t* d_n, const int32_t* rowptr_t, const int32_t* csr_src, const int32_t* rowptr_s,
+                          const int32_t* csr_dst, int32_t* pos_t, int32_t* pos_s, int32_t* inv_t, int32_t* inv_s,
+                          int32_t* loop_src, void* workspace, int32_t* status, grapes_stream_t stream);
+/* The weight pass, per call (replaces gcn_norm's scatter of edge_weight into deg, its pow(-0.5) and its masked_fill): val_t / val_s
+ * [e] = the weights in both CSR orders, lw [n], dinv [n] with deg summed in by-target slot order.  One launch. */
+int grapes_wgcn_weights(const float* edge_weight, int32_t e, const int32_t* inv_t, const int32_t* inv_s, const int32_t* loop_src,
+                        const int32_t* rowptr_t, const int32_t* rowptr_s, int32_t n, const int32_t* d_n, float* val_t, float* val_s,
+                        float* lw, float* dinv, grapes_stream_t stream);
+/* GCNConv.propagate with the normalised weights (+ bias, + ReLU when relu != 0) in ONE pass over the by-target CSR: a group of
+ * lanes per row, each lane reads one column index and one val_t per batch, val * dinv[col] is broadcast with the index.
+ * long_items / d_n_items / item_cap / workspace as grapes_gcn_aggregate_fwd (NULL: every row by one group): rows longer than
+ * GRAPES_LONG_ROW are cut into items whose partial sums are merged in chunk order.  workspace:
+ * grapes_wgcn_aggregate_workspace_bytes(item_cap, f), 16-byte aligned.  bias may be NULL; out must not alias h. */
+size_t grapes_wgcn_aggregate_workspace_bytes(int32_t item_cap, int32_t f);
+int grapes_wgcn_aggregate_fwd(const float* h, const int32_t* rowptr_t, const int32_t* csr_src, const float* val_t, const float* dinv,
+                              const float* lw, const float* bias, float* out, int32_t n, const int32_t* d_n, int32_t f,
+                              int32_t relu, const int32_t* long_items, const int32_t* d_n_items, int32_t item_cap, void* workspace,
+                              int32_t* status, grapes_stream_t stream);
+/* Backward of the above and of gcn_norm (autograd through GCNConv.forward with edge weights).  With G = dout gated by
+ * relu_out > 0 (relu_out NULL: G = dout), s = dinv, p_e = G[c] . H[r]:
+ *   dh[r] = s_r sum_{e: r -> c} w_e s_c G[c] + s_r^2 lw_r G[r]                       (by-source CSR)
+ *   dbias = column sums of G (the gated column-sum pass of grapes_gcn_aggregate_bwd: partials added in a fixed order)
+ *   t_i = sum_{e -> i} w_e s_r p_e + sum_{e: i -> c} w_e s_c p_e + 2 s_i lw_i (G[i] . H[i]),   q_i = -1/2 s_i^3 t_i (0 where s_i = 0)
+ *   dw[i] = s_r s_c p_e + q_c for a stored entry; s_i^2 (G[i] . H[i]) + q_i for the loop that set lw[i]; 0 for an overridden loop
+ *           and for a dropped entry                                                    (input order, through pos_t and loop_src)
+ * dh, dbias and dw may each be NULL (not all three); h, edge_src / edge_dst / pos_t / loop_src, rowptr_t / csr_src / val_t and
+ * items_t are needed for dw only.  items_t / items_s: the two halves of gcn_prepare's item table with their counts (NULL: no row
+ * splitting).  workspace: grapes_wgcn_aggregate_bwd_workspace_bytes(n, e, item_cap, f), 16-byte aligned. */
+size_t grapes_wgcn_aggregate_bwd_workspace_bytes(int32_t n, int32_t e, int32_t item_cap, int32_t f);
+int grapes_wgcn_aggregate_bwd(const float* dout, const float* relu_out, const float* h, const int32_t* edge_src,
+                              const int32_t* edge_dst, int32_t e, const int32_t* d_e, const int32_t* pos_t, const int32_t* loop_src,
+                              const int32_t* rowptr_t, const int32_t* csr_src, const float* val_t, const int32_t* rowptr_s,
+                              const int32_t* csr_dst, const float* val_s, const float* dinv, const float* lw, float* dh,
+                              float* dbias, float* dw, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_t,
+                              const int32_t* d_n_items_t, const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap,
+                              void* workspace, int32_t* status, grapes_stream_t stream);
 
 /* ------------------------------------------------------------------ PNAConv (csrc/pna_kernels.hip)
  * modules/gcn.py:120-149: PNA stacks PNAConv(in_channels, out_channels, aggregators, scalers, deg) layers, every other argument
