@@ -102,6 +102,11 @@ SIGNATURES = {
     "grapes_wgcn_aggregate_fwd": (I32, [P] * 8 + [I32, P, I32, I32, P, P, I32, P, P, P]),
     "grapes_wgcn_aggregate_bwd_workspace_bytes": (SZ, [I32, I32, I32, I32]),
     "grapes_wgcn_aggregate_bwd": (I32, [P] * 5 + [I32] + [P] * 14 + [I32, P, I32, P, P, P, P, I32, P, P, P]),
+    "grapes_wgcn_loops_workspace_bytes": (SZ, [I32, I32]),
+    "grapes_wgcn_loops": (I32, [P, P, I32, P, I32, P, P, P, P, P]),
+    "grapes_wgcn_weights_mode": (I32, [P, I32] + [P] * 7 + [I32, P, I32, F32] + [P] * 5),
+    "grapes_wgcn_aggregate_fwd_mode": (I32, [P] * 8 + [I32, P, I32, I32, I32, P, P, I32, P, P, P]),
+    "grapes_wgcn_aggregate_bwd_mode": (I32, [P] * 5 + [I32] + [P] * 14 + [I32, P, I32, I32, P, P, P, P, I32, P, P, P]),
     "grapes_pna_aggregate_fwd_workspace_bytes": (SZ, [I32, I32]),
     "grapes_pna_aggregate_fwd": (I32, [P, P, P, I32, P, P, P, I32, I32, I32, I32, F32, F32, P, P, I32, P, I32, P, P, I32, P, P, P]),
     "grapes_pna_aggregate_bwd_workspace_bytes": (SZ, [I32, I32, I32]),

@@ -125,24 +125,26 @@ class _GCNConvFn(torch.autograd.Function):
         prep = ctx.prep
         if ctx.agg_first:
             dw, dbias = ops.linear_bwd_weight_gated(dout.contiguous(), x, gate=out if ctx.relu else None, d_n=prep.d_n)
-            return None, dw, dbias, None, None
+            return None, dw, dbias if ctx.needs_input_grad[2] else None, None, None
         dh, dbias = ops.gcn_aggregate_bwd(dout.contiguous(), prep, relu_out=out if ctx.relu else None)
         dw = ops.linear_bwd_weight(dh, x, d_n=prep.d_n)
         dx = ops.linear_bwd_input(dh, weight, d_n=prep.d_n) if ctx.needs_input_grad[0] else None
-        return dx, dw, dbias, None, None
+        return dx, dw, dbias if ctx.needs_input_grad[2] else None, None, None
 
 
 class _WeightedGCNConvFn(torch.autograd.Function):
     """_GCNConvFn with edge weights (PyG gcn_norm with edge_weight, ops.wgcn_*): the same transform-first / aggregate-first rule
     and the same GEMMs.  The edge-weight gradient (formed only when edge_weight needs one) is that of the aggregation
     out' = Â_w H with G = d out': transform-first H = X Wᵀ and G = the gated dout; aggregate-first H = X and
-    G = linear_bwd_input(gated dout, W)."""
+    G = linear_bwd_input(gated dout, W).
+    mode / fill: the layer's rule for the loop weights and the normalisation (ops.WGCN_*: improved, add_self_loops=False,
+    normalize=False); there edge_weight may be None (every weight 1, no weight gradient) and bias may be None."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, edge_weight, ws, relu):
+    def forward(ctx, x, weight, bias, edge_weight, ws, relu, mode, fill):
         f_out, f_in = weight.shape
         d_n = ws.prep.d_n
-        vals = ops.wgcn_weights(ws, edge_weight.detach().contiguous())
+        vals = ops.wgcn_weights(ws, None if edge_weight is None else edge_weight.detach().contiguous(), mode, fill)
         ctx.ws, ctx.vals, ctx.relu = ws, vals, relu
         ctx.want_dw = ctx.needs_input_grad[3]
         ctx.agg_first = (not ctx.needs_input_grad[0]) and f_in < f_out and f_out > 1
@@ -164,50 +166,88 @@ class _WeightedGCNConvFn(torch.autograd.Function):
         if ctx.agg_first:
             dw = dbias = dew = None
             if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-                dw, dbias = ops.linear_bwd_weight_gated(dout, first, gate=out if ctx.relu else None, d_n=d_n)
+                dw, dbias = ops.linear_bwd_weight_gated(dout, first, gate=out if ctx.relu else None, d_n=d_n,
+                                                        want_bias=ctx.needs_input_grad[2])
             if ctx.want_dw:
                 g = ops.gcn2_mix_bwd(dout, out, True, 1.0, d_n=d_n)[0] if ctx.relu else dout
                 dax = ops.linear_bwd_input(g, weight, d_n=d_n)
                 dew = ops.wgcn_aggregate_bwd(dax, ws, vals, h=h, want_dh=False, want_dw=True, want_bias=False)[2]
-            return None, dw, dbias, dew, None, None
+            return None, dw, dbias, dew, None, None, None, None
         dh, dbias, dew = ops.wgcn_aggregate_bwd(dout, ws, vals, h=h, relu_out=out if ctx.relu else None,
                                                 want_dh=ctx.needs_input_grad[0] or ctx.needs_input_grad[1], want_dw=ctx.want_dw,
                                                 want_bias=ctx.needs_input_grad[2])
         dw = ops.linear_bwd_weight(dh, first, d_n=d_n) if ctx.needs_input_grad[1] else None
         dx = ops.linear_bwd_input(dh, weight, d_n=d_n) if ctx.needs_input_grad[0] else None
-        return dx, dw, dbias, dew, None, None
+        return dx, dw, dbias, dew, None, None, None, None
 
 
 class GCNConv(nn.Module):
     """out = D^-1/2 (A + I) D^-1/2 · X Wᵀ + b with PyG's conventions.  With edge_weight [e] (PyG's third
     argument): out = D^-1/2 (A_w + diag(lw)) D^-1/2 · X Wᵀ + b, where A_w sums the weights of the non-loop entries (duplicates each
     count), lw[i] = 1 or the weight of the LAST stored entry (i, i), and D = the weighted in-degree + lw.  A negative degree gives
-    NaN, as in PyG; it is not checked."""
+    NaN, as in PyG; it is not checked.
 
-    def __init__(self, in_channels: int, out_channels: int):
+    The constructor is PyG 2.5's [PyG-recall]: GCNConv(in_channels, out_channels, improved=False, cached=False, add_self_loops=None,
+    normalize=True, bias=True); add_self_loops=None means "as normalize".
+      improved=True           lw[i] = 2 where node i stores no loop (A + 2I);
+      add_self_loops=False    nothing is added and a stored loop is an ordinary entry: out = D^-1/2 A_w D^-1/2 · X Wᵀ + b with every
+                              occurrence counted in A_w and D (a node without an incoming entry outputs b); improved has no effect;
+      normalize=False         out[c] = Σ_{e: r -> c} w_e (X Wᵀ)[r] + b, the weights (1 without edge_weight) as given;
+      bias=False              no bias parameter.
+    Anything but (improved=False, add_self_loops=True, normalize=True) takes an edge-index tensor [2, e] (ops.wgcn_* with a mode);
+    cached=True is not built."""
+
+    def __init__(self, in_channels: int, out_channels: int, improved: bool = False, cached: bool = False,
+                 add_self_loops: Optional[bool] = None, normalize: bool = True, bias: bool = True):
         super().__init__()
+        if cached:
+            raise NotImplementedError("GCNConv: cached=True is not built (the normalisation is recomputed on every call)")
+        if add_self_loops is None:
+            add_self_loops = normalize
+        if add_self_loops and not normalize:
+            raise ValueError("GCNConv: add_self_loops=True goes with normalize=True only (PyG refuses the pair too)")
         self.in_channels, self.out_channels = in_channels, out_channels
+        self.improved, self.cached, self.add_self_loops, self.normalize = bool(improved), False, bool(add_self_loops), bool(normalize)
+        if not self.normalize:
+            self._mode, self._fill = ops.WGCN_UNNORMALIZED, 1.0
+        elif not self.add_self_loops:
+            self._mode, self._fill = ops.WGCN_LOOP_SUM, 1.0
+        else:
+            self._mode, self._fill = ops.WGCN_LOOP_FILL, (2.0 if self.improved else 1.0)
         self.lin = nn.Linear(in_channels, out_channels, bias=False)
-        self.bias = nn.Parameter(torch.zeros(out_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(out_channels))
+        else:
+            self.register_parameter("bias", None)
         self.reset_parameters()
 
     def reset_parameters(self):
         a = math.sqrt(6.0 / (self.in_channels + self.out_channels))    # PyG glorot
         with torch.no_grad():
             self.lin.weight.uniform_(-a, a)
-            self.bias.zero_()
+            if self.bias is not None:
+                self.bias.zero_()
+
+    def _default_mode(self) -> bool:
+        return self._mode == ops.WGCN_LOOP_FILL and self._fill == 1.0
 
     def forward(self, x, edge_index, relu: bool = False, large_graph: Optional[bool] = None, edge_weight=None):
         if edge_weight is not None:
             _check_edge_weight(edge_index, edge_weight, large_graph, "GCNConv")
+        elif not self._default_mode():
+            if not torch.is_tensor(edge_index) or large_graph:
+                raise ValueError("GCNConv: improved=True, add_self_loops=False and normalize=False go with an edge-index tensor "
+                                 "[2, e]; the DeviceGraph / PreparedGraph / large-graph paths are the default layer's")
+            if edge_index.dim() != 2 or edge_index.shape[0] != 2:
+                raise ValueError("GCNConv: edge_index must be [2, e]")
         if not x.is_cuda:
             raise ops._lib.GrapesHipError("GCNConv input must be a cuda tensor (grapes_amd has no CPU path)")
-        if edge_weight is not None:
+        if edge_weight is not None or not self._default_mode():
             x = x.contiguous()
             if x.dtype != torch.float32:
                 x = x.float()
             ws = weighted_structure(edge_index, x.shape[0])
-            return _WeightedGCNConvFn.apply(x, self.lin.weight, self.bias, edge_weight, ws, relu)
+            return _WeightedGCNConvFn.apply(x, self.lin.weight, self.bias, edge_weight, ws, relu, self._mode, self._fill)
         if _large(edge_index, large_graph):                    # a DeviceGraph with 2^31+ entries (or forced): full_graph.py
             return full_graph.conv_forward(self, x, edge_index, relu)
         x = x.contiguous()
@@ -215,6 +255,8 @@ class GCNConv(nn.Module):
             x = x.float()
         prep = prepare_edges(edge_index, x.shape[0])
         fo, fi = self.lin.weight.shape
+        if self.bias is None:                                  # (the inference forms below pad the bias: the training form serves)
+            return _GCNConvFn.apply(x, self.lin.weight, None, prep, relu)
         if (not torch.is_grad_enabled()) and _EVAL_PRESCALED and prep.n > ops._SMALL_GRAPH and prep.items_fwd and fo > 1:
             return self._forward_full_batch_inference(x, prep, relu)
         if ((not torch.is_grad_enabled()) and not _EVAL_PRESCALED and fo % _EVAL_ROW_PAD and fo > 16 and fi >= fo and

@@ -1754,13 +1754,18 @@ def _wgcn_width(f: int):
         raise ValueError(f"weighted GCN aggregation: width {f} is not built (any width up to 256, multiples of 4 up to 1024)")
 
 
+WGCN_LOOP_FILL, WGCN_LOOP_SUM, WGCN_UNNORMALIZED = 0, 1, 2      # GRAPES_WGCN_* of grapes_hip.h: the rule for lw, and whether dinv exists
+
+
 class WeightedStructure:
     """Where every entry of an edge list sits in the two CSRs of the PreparedGraph built from it: pos_t / pos_s [e] (slot by target
     / by source, -1 for a stored loop or a dropped entry), their inverses inv_t / inv_s, and loop_src [n] (the input index of the
     stored loop that sets a node's loop weight — the last one in input order — or -1).  Built once per edge list; the weights
-    themselves go through wgcn_weights on every call.  Duplicates of one (r, c) take adjacent slots in input order."""
+    themselves go through wgcn_weights on every call.  Duplicates of one (r, c) take adjacent slots in input order.
+    loops(): (loop_ptr [n + 1], loop_idx) — every node's stored loops as a list in input order, for the modes that sum them; built
+    on first use."""
 
-    __slots__ = ("prep", "edge_src", "edge_dst", "n", "e", "pos_t", "pos_s", "inv_t", "inv_s", "loop_src")
+    __slots__ = ("prep", "edge_src", "edge_dst", "n", "e", "pos_t", "pos_s", "inv_t", "inv_s", "loop_src", "_loops")
 
     def __init__(self, prep: PreparedGraph, edge_src, edge_dst):
         _chk(edge_src, _i32, "edge_src"); _chk(edge_dst, _i32, "edge_dst")
@@ -1769,6 +1774,7 @@ class WeightedStructure:
             raise ValueError("WeightedStructure: edge_src / edge_dst must be the list the PreparedGraph was built from")
         dev = edge_src.device
         self.prep, self.edge_src, self.edge_dst, self.n, self.e = prep, edge_src, edge_dst, prep.n, e
+        self._loops = None
         self.pos_t = torch.empty(max(e, 1), dtype=_i32, device=dev); self.pos_s = torch.empty(max(e, 1), dtype=_i32, device=dev)
         self.inv_t = torch.empty(max(e, 1), dtype=_i32, device=dev); self.inv_s = torch.empty(max(e, 1), dtype=_i32, device=dev)
         self.loop_src = torch.empty(max(prep.n, 1), dtype=_i32, device=dev)
@@ -1778,31 +1784,55 @@ class WeightedStructure:
                                                _p(self.inv_t), _p(self.inv_s), _p(self.loop_src), _p(ws), _p(prep.status), _stream()),
                    "wgcn_structure")
 
+    def loops(self):
+        if self._loops is None:
+            dev, prep = self.edge_src.device, self.prep
+            loop_ptr = torch.empty(self.n + 1, dtype=_i32, device=dev)
+            loop_idx = torch.empty(max(self.e, 1), dtype=_i32, device=dev)
+            ws = _ws(lib().grapes_wgcn_loops_workspace_bytes(self.n, self.e), dev)
+            _lib.check(lib().grapes_wgcn_loops(_p(self.edge_src), _p(self.edge_dst), self.e, _p(prep.d_e), self.n, _p(prep.d_n),
+                                               _p(loop_ptr), _p(loop_idx), _p(ws), _stream()), "wgcn_loops")
+            self._loops = (loop_ptr, loop_idx)
+        return self._loops
+
 
 class WeightedValues:
     """What wgcn_weights makes of one weight vector: val_t / val_s (the weights in both CSR orders), lw (the loop weights) and
-    dinv = (lw + the weighted in-degree)^-1/2 (inf -> 0; a negative degree gives NaN, as in PyG)."""
+    dinv = (lw + the weighted in-degree)^-1/2 (inf -> 0; a negative degree gives NaN, as in PyG); mode: the rule they were made
+    by (WGCN_UNNORMALIZED: dinv is None)."""
 
-    __slots__ = ("val_t", "val_s", "lw", "dinv")
+    __slots__ = ("val_t", "val_s", "lw", "dinv", "mode")
 
 
-def wgcn_weights(ws: WeightedStructure, edge_weight) -> WeightedValues:
-    _chk(edge_weight, _f32, "edge_weight")
-    if edge_weight.numel() != ws.e:
+def wgcn_weights(ws: WeightedStructure, edge_weight, mode: int = WGCN_LOOP_FILL, fill: float = 1.0) -> WeightedValues:
+    """mode / fill: the rule for lw (grapes_hip.h: GRAPES_WGCN_*).  edge_weight None (any mode but the default one): every weight
+    is 1 — no ones vector is formed."""
+    _chk(edge_weight, _f32, "edge_weight", mode != WGCN_LOOP_FILL or fill != 1.0)
+    if mode not in (WGCN_LOOP_FILL, WGCN_LOOP_SUM, WGCN_UNNORMALIZED):
+        raise ValueError(f"wgcn_weights: mode {mode}")
+    if edge_weight is not None and edge_weight.numel() != ws.e:
         raise ValueError(f"edge_weight holds {edge_weight.numel()} values for {ws.e} entries")
-    dev, prep = edge_weight.device, ws.prep
+    dev, prep = ws.edge_src.device, ws.prep
     v = WeightedValues()
+    v.mode = mode
     v.val_t = torch.empty(max(ws.e, 1), dtype=_f32, device=dev); v.val_s = torch.empty(max(ws.e, 1), dtype=_f32, device=dev)
-    v.lw = torch.empty(max(ws.n, 1), dtype=_f32, device=dev); v.dinv = torch.empty(max(ws.n, 1), dtype=_f32, device=dev)
-    _lib.check(lib().grapes_wgcn_weights(_p(edge_weight), ws.e, _p(ws.inv_t), _p(ws.inv_s), _p(ws.loop_src), _p(prep.rowptr_t),
-                                         _p(prep.rowptr_s), ws.n, _p(prep.d_n), _p(v.val_t), _p(v.val_s), _p(v.lw), _p(v.dinv),
-                                         _stream()), "wgcn_weights")
+    v.lw = torch.empty(max(ws.n, 1), dtype=_f32, device=dev)
+    v.dinv = torch.empty(max(ws.n, 1), dtype=_f32, device=dev) if mode != WGCN_UNNORMALIZED else None
+    if mode == WGCN_LOOP_FILL and fill == 1.0:
+        _lib.check(lib().grapes_wgcn_weights(_p(edge_weight), ws.e, _p(ws.inv_t), _p(ws.inv_s), _p(ws.loop_src), _p(prep.rowptr_t),
+                                             _p(prep.rowptr_s), ws.n, _p(prep.d_n), _p(v.val_t), _p(v.val_s), _p(v.lw), _p(v.dinv),
+                                             _stream()), "wgcn_weights")
+        return v
+    loop_ptr, loop_idx = (None, None) if mode == WGCN_LOOP_FILL else ws.loops()
+    _lib.check(lib().grapes_wgcn_weights_mode(_p(edge_weight), ws.e, _p(ws.inv_t), _p(ws.inv_s), _p(ws.loop_src), _p(loop_ptr),
+                                              _p(loop_idx), _p(prep.rowptr_t), _p(prep.rowptr_s), ws.n, _p(prep.d_n), mode, float(fill),
+                                              _p(v.val_t), _p(v.val_s), _p(v.lw), _p(v.dinv), _stream()), "wgcn_weights_mode")
     return v
 
 
 def wgcn_aggregate_fwd(h, ws: WeightedStructure, vals: WeightedValues, bias=None, relu=False, out=None):
     """out[c] = dinv[c] sum_{e: r -> c} w_e dinv[r] h[r] + dinv[c]^2 lw[c] h[c] + bias (+ReLU) over the first ws.n rows of h (h and
-    out may hold more rows, which are left alone)."""
+    out may hold more rows, which are left alone); with vals of WGCN_UNNORMALIZED out[c] = sum_e w_e h[r] + lw[c] h[c] + bias."""
     _chk(h, _f32, "h"); _chk(bias, _f32, "bias", True); _chk(out, _f32, "out", True)
     prep, (rows, f) = ws.prep, h.shape
     _wgcn_width(f)
@@ -1812,16 +1842,21 @@ def wgcn_aggregate_fwd(h, ws: WeightedStructure, vals: WeightedValues, bias=None
         raise ValueError("h and out need one row of the same width per node of the structure's graph, bias one value per column")
     items, n_items, cap = _long_items(prep, by_target=True, forward=True)
     wsp = _ws(lib().grapes_wgcn_aggregate_workspace_bytes(cap, f), h.device) if cap else None
-    _lib.check(lib().grapes_wgcn_aggregate_fwd(_p(h), _p(prep.rowptr_t), _p(prep.csr_src), _p(vals.val_t), _p(vals.dinv), _p(vals.lw),
-                                               _p(bias), _p(out), ws.n, _p(prep.d_n), f, 1 if relu else 0, items, n_items, cap,
-                                               _p(wsp), _p(prep.status), _stream()), "wgcn_aggregate_fwd")
+    head = (_p(h), _p(prep.rowptr_t), _p(prep.csr_src), _p(vals.val_t), _p(vals.dinv), _p(vals.lw), _p(bias), _p(out), ws.n,
+            _p(prep.d_n), f, 1 if relu else 0)
+    tail = (items, n_items, cap, _p(wsp), _p(prep.status), _stream())
+    if vals.mode == WGCN_LOOP_FILL:
+        _lib.check(lib().grapes_wgcn_aggregate_fwd(*head, *tail), "wgcn_aggregate_fwd")
+    else:
+        _lib.check(lib().grapes_wgcn_aggregate_fwd_mode(*head, vals.mode, *tail), "wgcn_aggregate_fwd_mode")
     return out
 
 
 def wgcn_aggregate_bwd(dout, ws: WeightedStructure, vals: WeightedValues, h=None, relu_out=None, want_dh=True, want_dw=False,
                        want_bias=True):
     """(dh, dbias, dw) of wgcn_aggregate_fwd + wgcn_weights: dout gated by relu_out > 0 when given; dw (the gradient of the edge
-    weights, in input order, through the normalisation too) needs h, the forward's input.  dout is not modified."""
+    weights, in input order, through the normalisation too — by the rule of vals.mode) needs h, the forward's input.  dout is not
+    modified."""
     _chk(dout, _f32, "dout"); _chk(relu_out, _f32, "relu_out", True); _chk(h, _f32, "h", True)
     prep, (rows, f) = ws.prep, dout.shape
     _wgcn_width(f)
@@ -1838,11 +1873,14 @@ def wgcn_aggregate_bwd(dout, ws: WeightedStructure, vals: WeightedValues, h=None
     items_t, n_items_t, cap = _long_items(prep, by_target=True, forward=False)
     items_s, n_items_s, _ = _long_items(prep, by_target=False, forward=False)
     wsp = _ws(lib().grapes_wgcn_aggregate_bwd_workspace_bytes(ws.n, ws.e, cap, f), dev)
-    _lib.check(lib().grapes_wgcn_aggregate_bwd(_p(dout), _p(relu_out), _p(h) if want_dw else None, _p(ws.edge_src), _p(ws.edge_dst),
-                                               ws.e, _p(prep.d_e), _p(ws.pos_t), _p(ws.loop_src), _p(prep.rowptr_t), _p(prep.csr_src),
-                                               _p(vals.val_t), _p(prep.rowptr_s), _p(prep.csr_dst), _p(vals.val_s), _p(vals.dinv),
-                                               _p(vals.lw), _p(dh), _p(dbias), _p(dw), ws.n, _p(prep.d_n), f, items_t, n_items_t,
-                                               items_s, n_items_s, cap, _p(wsp), _p(prep.status), _stream()), "wgcn_aggregate_bwd")
+    head = (_p(dout), _p(relu_out), _p(h) if want_dw else None, _p(ws.edge_src), _p(ws.edge_dst), ws.e, _p(prep.d_e), _p(ws.pos_t),
+            _p(ws.loop_src), _p(prep.rowptr_t), _p(prep.csr_src), _p(vals.val_t), _p(prep.rowptr_s), _p(prep.csr_dst), _p(vals.val_s),
+            _p(vals.dinv), _p(vals.lw), _p(dh), _p(dbias), _p(dw), ws.n, _p(prep.d_n), f)
+    tail = (items_t, n_items_t, items_s, n_items_s, cap, _p(wsp), _p(prep.status), _stream())
+    if vals.mode == WGCN_LOOP_FILL:
+        _lib.check(lib().grapes_wgcn_aggregate_bwd(*head, *tail), "wgcn_aggregate_bwd")
+    else:
+        _lib.check(lib().grapes_wgcn_aggregate_bwd_mode(*head, vals.mode, *tail), "wgcn_aggregate_bwd_mode")
     return dh, dbias, dw
 
 

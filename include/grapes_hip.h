@@ -55,7 +55,8 @@ extern "C" {
  * grapes_gcn2_loop_counts(_csr), grapes_gcn2_propagate_fwd / _bwd (+ _workspace_bytes), grapes_gcn2_mix_fwd / _bwd; the PNA
  * classifier (modules/gcn.py:120-149) — grapes_pna_aggregate_fwd / _bwd (+ _workspace_bytes each), grapes_pna_add_input_grad; GraphSAINT's node and edge
  * samplers — grapes_saint_edge_weights, grapes_saint_draw_nodes; GCNConv with edge weights — grapes_wgcn_structure(_workspace_bytes),
- * grapes_wgcn_weights, grapes_wgcn_aggregate_fwd / _bwd (+ _workspace_bytes each). */
+ * grapes_wgcn_weights, grapes_wgcn_aggregate_fwd / _bwd (+ _workspace_bytes each); GCNConv's improved / add_self_loops / normalize —
+ * grapes_wgcn_loops(_workspace_bytes), grapes_wgcn_weights_mode, grapes_wgcn_aggregate_fwd_mode / _bwd_mode. */
 #define GRAPES_ABI_VERSION 302
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -795,6 +796,48 @@ int grapes_wgcn_aggregate_bwd(const float* dout, const float* relu_out, const fl
                               float* dbias, float* dw, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_t,
                               const int32_t* d_n_items_t, const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap,
                               void* workspace, int32_t* status, grapes_stream_t stream);
+/* GCNConv's other constructor arguments (PyG 2.5 GCNConv(improved, add_self_loops, normalize), as recalled): the CSRs never hold a
+ * loop, so every mode is a rule for lw, and one of them drops the normalisation.
+ *   GRAPES_WGCN_LOOP_FILL     add_self_loops=True: lw[i] = the weight of the last stored (i, i), or fill (1; improved=True: 2).
+ *                             fill = 1 is the rule of the entry points above.
+ *   GRAPES_WGCN_LOOP_SUM      add_self_loops=False, normalize=True: nothing is added and a stored loop is an ordinary entry —
+ *                             lw[i] = the weights of ALL stored (i, i), added in input order (0 without one), deg, dinv and the
+ *                             formulas as above; a node without an incoming entry has dinv = 0 and outputs the bias.  dw: every
+ *                             stored loop of i gets s_i^2 (G[i] . H[i]) + q_i.
+ *   GRAPES_WGCN_UNNORMALIZED  normalize=False: lw as LOOP_SUM; no deg and no dinv (dinv may be NULL and is never read):
+ *                             out[c] = sum_{e: r -> c} w_e H[r] + lw_c H[c] + bias,  dh[r] = sum_{e: r -> c} w_e G[c] + lw_r G[r],
+ *                             dw[i] = p_e for a stored entry, G[i] . H[i] for a stored loop. */
+#define GRAPES_WGCN_LOOP_FILL 0
+#define GRAPES_WGCN_LOOP_SUM 1
+#define GRAPES_WGCN_UNNORMALIZED 2
+/* The structure pass of LOOP_SUM / UNNORMALIZED, once per edge list: the stored loops of every node as a list in input order —
+ * loop_ptr [n + 1], loop_idx [e] (the first loop_ptr[n] places are written) = input indices.  Integer atomics count and claim, a
+ * rank puts each node's claims in input order (L reads per member of a node with L stored loops).  workspace:
+ * grapes_wgcn_loops_workspace_bytes(n, e), 16-byte aligned. */
+size_t grapes_wgcn_loops_workspace_bytes(int32_t n, int32_t e);
+int grapes_wgcn_loops(const int32_t* edge_src, const int32_t* edge_dst, int32_t e, const int32_t* d_e, int32_t n, const int32_t* d_n,
+                      int32_t* loop_ptr, int32_t* loop_idx, void* workspace, grapes_stream_t stream);
+/* grapes_wgcn_weights with a mode.  edge_weight NULL: every weight is 1 (an unweighted call; no ones vector is formed).  loop_src is
+ * read by LOOP_FILL only, loop_ptr / loop_idx by the other two; UNNORMALIZED writes no dinv. */
+int grapes_wgcn_weights_mode(const float* edge_weight, int32_t e, const int32_t* inv_t, const int32_t* inv_s, const int32_t* loop_src,
+                             const int32_t* loop_ptr, const int32_t* loop_idx, const int32_t* rowptr_t, const int32_t* rowptr_s,
+                             int32_t n, const int32_t* d_n, int32_t mode, float fill, float* val_t, float* val_s, float* lw,
+                             float* dinv, grapes_stream_t stream);
+/* grapes_wgcn_aggregate_fwd / _bwd with a mode (the workspaces are theirs).  LOOP_FILL and LOOP_SUM run the same kernels over
+ * their own lw and dinv and differ in dw's loop rule; UNNORMALIZED runs specialisations that never load dinv: one memory request
+ * per gathered entry less, no by-source / by-target sums and no q in the backward. */
+int grapes_wgcn_aggregate_fwd_mode(const float* h, const int32_t* rowptr_t, const int32_t* csr_src, const float* val_t,
+                                   const float* dinv, const float* lw, const float* bias, float* out, int32_t n, const int32_t* d_n,
+                                   int32_t f, int32_t relu, int32_t mode, const int32_t* long_items, const int32_t* d_n_items,
+                                   int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
+int grapes_wgcn_aggregate_bwd_mode(const float* dout, const float* relu_out, const float* h, const int32_t* edge_src,
+                                   const int32_t* edge_dst, int32_t e, const int32_t* d_e, const int32_t* pos_t,
+                                   const int32_t* loop_src, const int32_t* rowptr_t, const int32_t* csr_src, const float* val_t,
+                                   const int32_t* rowptr_s, const int32_t* csr_dst, const float* val_s, const float* dinv,
+                                   const float* lw, float* dh, float* dbias, float* dw, int32_t n, const int32_t* d_n, int32_t f,
+                                   int32_t mode, const int32_t* items_t, const int32_t* d_n_items_t, const int32_t* items_s,
+                                   const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status,
+                                   grapes_stream_t stream);
 
 /* ------------------------------------------------------------------ PNAConv (csrc/pna_kernels.hip)
  * modules/gcn.py:120-149: PNA stacks PNAConv(in_channels, out_channels, aggregators, scalers, deg) layers, every other argument
