@@ -80,6 +80,11 @@ SIGNATURES = {
     # GraphSAINT's node and edge samplers (graphsaint.py:8)
     "grapes_saint_edge_weights": (I32, [P, P, I32, I64, P, P, P, P, P]),
     "grapes_saint_draw_nodes": (I32, [P, P, I32, I32, P, P, P, P, U64, U64, P, P, P, P, P, P, P, P]),
+    # GraphSAINT's normalisation (sample_coverage > 0)
+    "grapes_saint_coverage_count": (I32, [P, P, I32, P, P, P, I32, P, P, P, P]),
+    "grapes_saint_norms": (I32, [P, I32, P, P, I64, P, P, P]),
+    "grapes_saint_subgraph_ids": (I32, [P, P, P, P, P, I32, I32, P, P, P, P, P, P, P, P, P, P]),
+    "grapes_saint_masked_loss_weighted": (I32, [P, I64, I32, P, P, I32, P, P, P, P, P, I64, P, P, P, P]),
     # GATConv aggregation (modules/gcn.py:45-72)
     "grapes_gat_scores": (I32, [P, P, P, P, P, I32, P, I32, P]),
     "grapes_gat_aggregate_workspace_bytes": (SZ, [I32, I32]),

@@ -16,6 +16,11 @@
 //   saint_edge_scan_k    ONE workgroup: exclusive scan of those counts -> local row pointers, edge count (clamped to e_cap)
 //   saint_edge_write_k   one wavefront per local row: the induced edges (local row, local column) in CSR order
 //   saint_masked_loss_k  ONE workgroup: mean CE / BCE over the batch rows that are training rows, and d loss / d logits
+//   saint_coverage_count_k   GraphSAINT's normalisation [PyG-recall: GraphSAINTSampler._compute_norm]: one wavefront per local row
+//                        bumps node_count[v] and edge_count[j] of the row's member entries; one thread adds the set's size to a total
+//   saint_norms_k        one wavefront per CSR row (grid-stride): edge_norm and node_norm from the counts
+//   saint_edge_write_k<true>   the write kernel that also stores every edge's global entry position and its edge_norm
+//   saint_masked_loss_weighted_k   ONE workgroup: sum over the training rows of node_norm[v] * row loss, and d loss / d logits
 //
 // No kernel waits on another workgroup of its own launch.
 //
@@ -312,11 +317,15 @@ __global__ __launch_bounds__(SAINT_THREADS) void saint_edge_scan_k(const int32_t
 }
 
 // one wavefront per local row: the row's member entries, in CSR order, at rowptr_l[i] ..; nothing at or past e_cap is written
+// IDS: also edge_id[p] = j (the entry's position in col) and edge_norm_b[p] = edge_norm[j], each when its pointer is given
+template <bool IDS>
 __global__ __launch_bounds__(256) void saint_edge_write_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                           const int32_t* __restrict__ node_idx, const int32_t* __restrict__ d_count,
                                                           const int32_t* __restrict__ node_map, int n_cap,
                                                           const int32_t* __restrict__ rowptr_l, int e_cap,
-                                                          int32_t* __restrict__ src, int32_t* __restrict__ dst) {
+                                                          int32_t* __restrict__ src, int32_t* __restrict__ dst,
+                                                          int64_t* __restrict__ edge_id, const float* __restrict__ edge_norm,
+                                                          float* __restrict__ edge_norm_b) {
     const int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
     if (i >= n_cap) return;
     const int n = eff_count(d_count, n_cap);
@@ -335,7 +344,13 @@ __global__ __launch_bounds__(256) void saint_edge_write_k(const int64_t* __restr
         const uint64_t bal = __ballot(m >= 0);
         const int rank = __popcll(bal & ((1ull << lane) - 1ull));
         const int p = base + rank;
-        if (m >= 0 && p < e_cap) { src[p] = i; dst[p] = m; }
+        if (m >= 0 && p < e_cap) {
+            src[p] = i; dst[p] = m;
+            if (IDS) {
+                if (edge_id) edge_id[p] = j;
+                if (edge_norm_b) edge_norm_b[p] = edge_norm[j];
+            }
+        }
         base += __popcll(bal);
         if (base >= e_cap) break;
     }
@@ -428,6 +443,129 @@ __global__ __launch_bounds__(SAINT_THREADS) void saint_masked_loss_k(
     }
 }
 
+// ------------------------------------------------------------------------ GraphSAINT normalisation (sample_coverage > 0)
+// [PyG-recall: GraphSAINTSampler._compute_norm]  One wavefront per local row i < count of ONE drawn batch: lane 0 bumps
+// node_count[v], v = node_idx[i]; the lanes walk v's CSR row in strides of 64 and bump edge_count[j] of every entry whose column is
+// in the node set (the sparse-set test of the subgraph kernels).  Within a batch every v and every j is touched by one thread, and
+// batches are serial on the stream: plain read-add-writes, no atomics, one result.  Thread 0 of row 0 adds the set's size to *d_total.
+__global__ __launch_bounds__(256) void saint_coverage_count_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                              int N, const int32_t* __restrict__ node_idx,
+                                                              const int32_t* __restrict__ d_count, const int32_t* __restrict__ node_map,
+                                                              int n_cap, uint32_t* __restrict__ node_count,
+                                                              uint32_t* __restrict__ edge_count, int64_t* __restrict__ d_total) {
+    const int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (i >= n_cap) return;
+    const int n = eff_count(d_count, n_cap);
+    if (i >= n) return;
+    const int v = node_idx[i];
+    if ((unsigned)v >= (unsigned)N) return;
+    if (lane == 0) {
+        node_count[v] += 1u;
+        if (i == 0) *d_total += (int64_t)n;
+    }
+    const int64_t a = rowptr[v], e = rowptr[v + 1];
+    for (int64_t j = a + lane; j < e; j += 64) {
+        const int u = col[j];
+        if ((unsigned)u >= (unsigned)N) continue;
+        const int m = node_map[u];
+        if ((unsigned)m < (unsigned)n && node_idx[m] == u) edge_count[j] += 1u;
+    }
+}
+
+// One wavefront per CSR row r (grid-stride over the rows), so row(j) is free; the lanes walk the row in strides of 64 (a row
+// shorter than a wavefront leaves lanes idle, a longer one takes several strides).
+//   edge_norm[j] = fp32(node_count[r]) / fp32(edge_count[j]) clamped to [0, 1e4], a NaN (0 / 0) -> 0.1 (so x / 0 -> 1e4);
+//   node_norm[r] = (fp32(num_samples) / c) / fp32(N), c = fp32(node_count[r]) or 0.1 where the count is 0.
+// The fp32 divisions are the compiler's correctly rounded ones (the default of this build: no fast-math flag).
+__global__ __launch_bounds__(256) void saint_norms_k(const int64_t* __restrict__ rowptr, int N, const uint32_t* __restrict__ node_count,
+                                                     const uint32_t* __restrict__ edge_count, float num_samples,
+                                                     float* __restrict__ edge_norm, float* __restrict__ node_norm) {
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    for (int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; r < N; r += waves) {
+        const uint32_t nc = node_count[r];
+        const float ncf = (float)nc;
+        if (lane == 0) node_norm[r] = (num_samples / (nc ? ncf : 0.1f)) / (float)N;
+        const int64_t a = rowptr[r], e = rowptr[r + 1];
+        for (int64_t j = a + lane; j < e; j += 64) {
+            float q = ncf / (float)edge_count[j];
+            if (q != q) q = 0.1f;
+            else if (q > 1e4f) q = 1e4f;
+            else if (q < 0.f) q = 0.f;
+            edge_norm[j] = q;
+        }
+    }
+}
+
+// ONE workgroup; saint_masked_loss_k with a per-node weight table w = node_norm[N], read through node_idx like train_mask
+// [PyG-recall: examples/graph_saint.py, (loss * node_norm)[train_mask].sum()].  loss = sum over the training rows i of
+// w_i * rowloss_i, NOT divided by T.  CE: rowloss = lse - z[y], g = w_i (softmax - onehot).  BCE: rowloss = the mean over the C
+// columns of max(z, 0) - z y + log1p(exp(-|z|)), g = w_i (sigmoid(z) - y) / C.  Other rows (and rows >= count) get g = 0.  T = 0:
+// loss = 0 and g = 0.  Same fixed summation order: wavefront w sums rows w, w + 16, ... in double, the 16 sums are added in
+// wavefront order; no float atomics.  With w = 1 / T everywhere this is saint_masked_loss_k's loss.
+__global__ __launch_bounds__(SAINT_THREADS) void saint_masked_loss_weighted_k(
+        const float* __restrict__ z, int64_t ldz, int C, const int32_t* __restrict__ node_idx, const int32_t* __restrict__ d_count,
+        int n_cap, const uint8_t* __restrict__ train_mask, const float* __restrict__ node_norm, const int64_t* __restrict__ labels,
+        const float* __restrict__ labels_f, float* __restrict__ g, int64_t ldg, float* __restrict__ loss_out,
+        int32_t* __restrict__ d_train, int32_t* status) {
+    __shared__ int wsum[SAINT_THREADS / 64 + 1];
+    __shared__ double lsum[SAINT_THREADS / 64];
+    const int n = eff_count(d_count, n_cap);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6;
+    if (d_train) {                                                        // (workgroup-uniform)
+        int t = 0;
+        for (int i = tid; i < n; i += blockDim.x) t += train_mask[node_idx[i]] ? 1 : 0;
+        int T;
+        (void)saint_block_scan(t, wsum, &T);
+        if (tid == 0) *d_train = T;
+    }
+    double acc = 0.0;
+    for (int i = w; i < n_cap; i += nw) {
+        float* gr = g + (int64_t)i * ldg;
+        const int v = i < n ? node_idx[i] : -1;
+        if (v < 0 || !train_mask[v]) {
+            for (int c = lane; c < C; c += 64) gr[c] = 0.f;
+            continue;
+        }
+        const float* zr = z + (int64_t)i * ldz;
+        const float wi = node_norm[v];
+        if (labels_f) {
+            const float* yr = labels_f + (int64_t)v * C;
+            const float wc = wi / (float)C;
+            float rl = 0.f;
+            for (int c = lane; c < C; c += 64) {
+                const float x = zr[c], y = yr[c];
+                rl += fmaxf(x, 0.f) - x * y + log1pf(expf(-fabsf(x)));
+                gr[c] = (1.f / (1.f + expf(-x)) - y) * wc;
+            }
+            acc += (double)wi * ((double)wave_sum(rl) / (double)C);
+        } else {
+            const int64_t y = labels[v];
+            if (y < 0 || y >= C) {
+                if (lane == 0 && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+                for (int c = lane; c < C; c += 64) gr[c] = 0.f;
+                continue;
+            }
+            float mx = -INFINITY;
+            for (int c = lane; c < C; c += 64) mx = fmaxf(mx, zr[c]);
+            for (int d = 32; d > 0; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d, 64));
+            float se = 0.f;
+            for (int c = lane; c < C; c += 64) se += expf(zr[c] - mx);
+            se = wave_sum(se);
+            const float lse = mx + logf(se);
+            for (int c = lane; c < C; c += 64) gr[c] = (expf(zr[c] - lse) - (c == y ? 1.f : 0.f)) * wi;
+            acc += (double)wi * (double)(lse - zr[y]);
+        }
+    }
+    if (lane == 0) lsum[w] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int q = 0; q < nw; ++q) s += lsum[q];
+        *loss_out = (float)s;                         // no training row: 0
+    }
+}
+
 static int saint_pow2(int m) { int p = 64; while (p < m) p <<= 1; return p; }
 
 extern "C" int grapes_saint_walk_nodes(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, int32_t B, int32_t L,
@@ -462,8 +600,32 @@ extern "C" int grapes_saint_subgraph(const int64_t* rowptr, const int32_t* col, 
     hipLaunchKernelGGL(saint_edge_scan_k, dim3(1), dim3(SAINT_THREADS), 0, s, (const int32_t*)cnt, d_count, n_cap, e_cap, rowptr_l,
                        d_e, status);
     GRAPES_LAUNCH_CHECK();
-    hipLaunchKernelGGL(saint_edge_write_k, dim3(grid), dim3(256), 0, s, rowptr, col, node_idx, d_count, node_map, n_cap,
-                       (const int32_t*)rowptr_l, e_cap, edge_src, edge_dst);
+    hipLaunchKernelGGL(saint_edge_write_k<false>, dim3(grid), dim3(256), 0, s, rowptr, col, node_idx, d_count, node_map, n_cap,
+                       (const int32_t*)rowptr_l, e_cap, edge_src, edge_dst, (int64_t*)nullptr, (const float*)nullptr,
+                       (float*)nullptr);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int grapes_saint_subgraph_ids(const int64_t* rowptr, const int32_t* col, const int32_t* node_idx, const int32_t* d_count,
+                                         const int32_t* node_map, int32_t n_cap, int32_t e_cap, int32_t* rowptr_l, int32_t* edge_src,
+                                         int32_t* edge_dst, int32_t* d_e, int64_t* edge_id, const float* edge_norm,
+                                         float* edge_norm_b, void* workspace, int32_t* status, grapes_stream_t stream) {
+    if (n_cap <= 0 || n_cap > SAINT_MAX_IDS || e_cap <= 0) return GRAPES_EINVAL;
+    if (!rowptr || !col || !node_idx || !d_count || !node_map || !rowptr_l || !edge_src || !edge_dst || !d_e || !workspace)
+        return GRAPES_EINVAL;
+    if ((edge_norm == nullptr) != (edge_norm_b == nullptr)) return GRAPES_EINVAL;
+    if ((uintptr_t)workspace & 3) return GRAPES_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    int32_t* cnt = (int32_t*)workspace;
+    const int grid = grapes_div_up((int64_t)n_cap * 64, 256);
+    hipLaunchKernelGGL(saint_edge_count_k, dim3(grid), dim3(256), 0, s, rowptr, col, node_idx, d_count, node_map, n_cap, cnt);
+    GRAPES_LAUNCH_CHECK();
+    hipLaunchKernelGGL(saint_edge_scan_k, dim3(1), dim3(SAINT_THREADS), 0, s, (const int32_t*)cnt, d_count, n_cap, e_cap, rowptr_l,
+                       d_e, status);
+    GRAPES_LAUNCH_CHECK();
+    hipLaunchKernelGGL(saint_edge_write_k<true>, dim3(grid), dim3(256), 0, s, rowptr, col, node_idx, d_count, node_map, n_cap,
+                       (const int32_t*)rowptr_l, e_cap, edge_src, edge_dst, edge_id, edge_norm, edge_norm_b);
     GRAPES_LAUNCH_CHECK();
     return 0;
 }
@@ -516,6 +678,43 @@ extern "C" int grapes_saint_draw_nodes(const int64_t* rowptr, const int32_t* col
     GRAPES_LAUNCH_CHECK();
     hipLaunchKernelGGL(saint_unique_ids_k, dim3(1), dim3(SAINT_THREADS), 0, s, (const int32_t*)ids, M, saint_pow2(M),
                        (uint64_t)((2 * (int64_t)B + 3) >> 2), d_philox_offset, node_idx, d_count, node_map);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int grapes_saint_coverage_count(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* node_idx,
+                                           const int32_t* d_count, const int32_t* node_map, int32_t n_cap, uint32_t* node_count,
+                                           uint32_t* edge_count, int64_t* d_total, grapes_stream_t stream) {
+    if (num_nodes <= 0 || n_cap <= 0 || n_cap > SAINT_MAX_IDS) return GRAPES_EINVAL;
+    if (!rowptr || !col || !node_idx || !d_count || !node_map || !node_count || !edge_count || !d_total) return GRAPES_EINVAL;
+    hipLaunchKernelGGL(saint_coverage_count_k, dim3(grapes_div_up((int64_t)n_cap * 64, 256)), dim3(256), 0, (hipStream_t)stream,
+                       rowptr, col, num_nodes, node_idx, d_count, node_map, n_cap, node_count, edge_count, d_total);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int grapes_saint_norms(const int64_t* rowptr, int32_t num_nodes, const uint32_t* node_count, const uint32_t* edge_count,
+                                  int64_t num_samples, float* edge_norm, float* node_norm, grapes_stream_t stream) {
+    if (num_nodes <= 0 || num_samples < 0) return GRAPES_EINVAL;
+    if (!rowptr || !node_count || !edge_count || !edge_norm || !node_norm) return GRAPES_EINVAL;
+    int grid = grapes_div_up((int64_t)num_nodes * 64, 256);
+    if (grid > 65536) grid = 65536;
+    hipLaunchKernelGGL(saint_norms_k, dim3(grid), dim3(256), 0, (hipStream_t)stream, rowptr, num_nodes, node_count, edge_count,
+                       (float)num_samples, edge_norm, node_norm);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int grapes_saint_masked_loss_weighted(const float* z, int64_t ldz, int32_t C, const int32_t* node_idx,
+                                                 const int32_t* d_count, int32_t n_cap, const uint8_t* train_mask,
+                                                 const float* node_norm, const int64_t* labels, const float* labels_f, float* g,
+                                                 int64_t ldg, float* loss_out, int32_t* d_train, int32_t* status,
+                                                 grapes_stream_t stream) {
+    if (C <= 0 || n_cap <= 0 || ldz < C || ldg < C) return GRAPES_EINVAL;
+    if (!z || !node_idx || !train_mask || !node_norm || !g || !loss_out || ((labels == nullptr) == (labels_f == nullptr)))
+        return GRAPES_EINVAL;
+    hipLaunchKernelGGL(saint_masked_loss_weighted_k, dim3(1), dim3(SAINT_THREADS), 0, (hipStream_t)stream, z, ldz, C, node_idx, d_count,
+                       n_cap, train_mask, node_norm, labels, labels_f, g, ldg, loss_out, d_train, status);
     GRAPES_LAUNCH_CHECK();
     return 0;
 }

@@ -2,12 +2,15 @@
 
     python -m grapes_amd.graphsaint --dataset cora --max_epoch 50 --runs 1
 
-* Flags and defaults of graphsaint.py:13-20: --use_normalization (accepted, unused as in the reference), --hidden_dim 256,
+* Flags and defaults of graphsaint.py:13-20: --use_normalization (alone: accepted, unused as in the reference, which passes
+  sample_coverage 0; with --sample_coverage K > 0: GraphSAINT's normalised training — saint.py), --hidden_dim 256,
   --dataset, --runs 1, --lr 0.01, --max_epoch 50, --embed_nodes, --node_emb_dim 64.  Added: --batch_size 256 and --walk_length 2
   (graphsaint.py:104 hard-codes them), --num_steps 1, --seed, --engine graph|eager (saint.GraphedSaintTrainer /
   saint.EagerSaintTrainer), --e_cap (edge capacity of a batch), --large_graph auto|true|false (the row-blocked 64-bit
   evaluation of full_graph.py; automatic from 2^31 CSR entries on) and --sampler rw|node|edge (GraphSAINT's three samplers:
-  the reference's random walks, or PyG's GraphSAINTNodeSampler / GraphSAINTEdgeSampler, which ignore --walk_length).
+  the reference's random walks, or PyG's GraphSAINTNodeSampler / GraphSAINTEdgeSampler, which ignore --walk_length) and
+  --sample_coverage 0 (PyG's sample_coverage: with --use_normalization the coverage estimate runs until N * K nodes were sampled;
+  without that flag a value above 0 is a ValueError).
 * Per run: GCN(F, [hidden_dim, C]) without dropout, Adam(params + embeddings, lr) (graphsaint.py:115-116); per epoch one step per
   batch, then one full-graph forward that yields val and test: accuracy for 1-D labels, TP / FP / FN micro-F1 for multi-label
   (graphsaint.py:46-88).  It prints `Epoch: .., Loss: .., Val: .., Test: ..`; a run's result is its last epoch's val metric, and
@@ -32,7 +35,7 @@ from .main import _bool, _large_flag, load_data
 
 def _parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="grapes_amd.graphsaint", description=__doc__.split("\n\n")[0])
-    ap.add_argument("--use_normalization", action="store_true")                     # graphsaint.py:13 (unused)
+    ap.add_argument("--use_normalization", action="store_true")                     # graphsaint.py:13 (read with --sample_coverage)
     ap.add_argument("--hidden_dim", default=256, type=int)
     ap.add_argument("--dataset", type=str)
     ap.add_argument("--runs", default=1, type=int)
@@ -49,6 +52,7 @@ def _parser() -> argparse.ArgumentParser:
     ap.add_argument("--e_cap", default=None, type=int)
     ap.add_argument("--large_graph", default="auto", choices=["auto", "true", "false"])
     ap.add_argument("--sampler", default="rw", choices=["rw", "node", "edge"])
+    ap.add_argument("--sample_coverage", default=0, type=int)
     return ap
 
 
@@ -56,6 +60,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     args = _parser().parse_args(list(sys.argv[1:] if argv is None else argv))
     if args.dataset is None:
         raise SystemExit("--dataset is required")
+    if args.sample_coverage < 0 or (args.sample_coverage and not args.use_normalization):
+        raise ValueError("--sample_coverage K (K > 0) goes with --use_normalization: the estimate is read by the normalised step alone")
     return args
 
 
@@ -113,9 +119,12 @@ def run(args, device=None, log=print) -> float:
     y = data.y.to(device)
     train_mask, val_mask, test_mask = (m.to(device) for m in (data.train_mask, data.val_mask, data.test_mask))
     model = saint.build_model(x.shape[1], args.hidden_dim, data.num_classes, device)
+    # (--use_normalization alone stays unused: the trainers are called as before)
+    cov = getattr(args, "sample_coverage", 0)
+    norm = dict(sample_coverage=cov, use_normalization=True) if cov else {}
     tr = saint.make_trainer(args.engine, g, x, y, train_mask, model, args.lr, emb, batch_size=args.batch_size,
                             walk_length=args.walk_length, num_steps=args.num_steps, seed=args.seed, e_cap=args.e_cap,
-                            sampler=args.sampler)
+                            sampler=args.sampler, **norm)
     large = _large_flag(args.large_graph)
     val = 0.0
     for epoch in range(1, args.max_epoch + 1):                                               # graphsaint.py:118-121

@@ -16,8 +16,17 @@ every node-sized tensor gathered at node_idx.  The three samplers differ in the 
   rand(B, E).log() / (prob + 1e-10) per row, which is one weighted draw per row: the distribution is built here, not the key
   arithmetic, and the 1e-10 is dropped — an entry of weight 0 is never drawn.
 
-sample_coverage > 0 (GraphSAINT's node / edge normalisation) is not built: the reference runs with sample_coverage 0.  The weighted
-layer its edge_norm needs now exists (modules.gcn.GCNConv.forward(..., edge_weight=)); the coverage counts themselves do not.
+GraphSAINT's node / edge normalisation [PyG-recall: PyG 2.5 GraphSAINTSampler._compute_norm / __collate__] comes through
+estimate_norm(sample_coverage), not through the constructors: they keep refusing sample_coverage > 0 (the reference runs with 0)
+and name that method.  estimate_norm draws passes of num_steps batches with the sampler's own draw on its Philox stream while
+total_sampled_nodes < N * sample_coverage (tested before each pass, so at least one runs), counting per batch node_count[v] += 1
+over the node set and edge_count[j] += 1 over the stored entries j with both ends in it (ops.saint_coverage_count: integers,
+exact), then forms
+    edge_norm[j] = fp32(node_count[row(j)]) / fp32(edge_count[j]) clamped to [0, 1e4], 0 / 0 -> 0.1 (so x / 0 -> 1e4),
+    node_norm[v] = (fp32(num_samples) / fp32(node_count[v])) / fp32(N), a count of 0 taken as 0.1
+(ops.saint_norms).  Afterwards every batch also carries node_norm = node_norm[node_idx] ([n]), edge_id (int64 [E], the position in
+col of every edge, in the batch's edge order) and edge_norm = edge_norm[edge_id] ([E]) — what modules.gcn.GCNConv.forward(...,
+edge_weight=) and ops.saint_masked_loss_weighted take.  Without the call batches are what they were.
 
 The draws come from the project's Philox stream (seed, device offset): see ops.saint_walk_nodes, ops.saint_draw_nodes and DESIGN.md.
 """
@@ -59,8 +68,9 @@ class _SaintSampler:
     def __init__(self, data_or_graph, batch_size: int, num_steps: int, sample_coverage: int, seed: Optional[int],
                  e_cap: Optional[int], n_cap: int, limit: str):
         if sample_coverage:
-            raise NotImplementedError("GraphSAINT normalisation (sample_coverage > 0) is not built; the reference "
-                                      "(graphsaint.py:104) uses sample_coverage=0")
+            raise NotImplementedError("GraphSAINT normalisation does not come through the constructor's sample_coverage (the "
+                                      "reference, graphsaint.py:104, passes 0): build the sampler without it and call "
+                                      "estimate_norm(sample_coverage)")
         self.batch_size, self.num_steps, self.n_cap = int(batch_size), int(num_steps), int(n_cap)
         if self.n_cap > ops.SAINT_MAX_IDS:
             raise ValueError(f"{limit} must be at most {ops.SAINT_MAX_IDS}")
@@ -72,6 +82,36 @@ class _SaintSampler:
         self.seed = int(seed)
         self.philox_offset = torch.zeros(1, dtype=torch.int64, device=dev)
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+        # set by estimate_norm
+        self.sample_coverage, self.num_samples, self.total_sampled_nodes = 0, 0, 0
+        self.node_count = self.edge_count = self.node_norm = self.edge_norm = None
+
+    def weights(self):
+        """The draw's one-time table (the edge sampler's alone)."""
+        return None
+
+    def estimate_norm(self, sample_coverage: int):
+        """GraphSAINT's coverage estimate and the two norm vectors (the module docstring has the rules).  Each batch is a draw and
+        one counting launch; nothing is read back but the running total, once per pass.  Keeps node_count / edge_count (int32
+        tensors holding the uint32 counts), num_samples, total_sampled_nodes, node_norm [N], edge_norm [nnz] and sample_coverage;
+        from then on batches carry their norms.  Returns self."""
+        cov = int(sample_coverage)
+        if cov <= 0:
+            raise ValueError(f"estimate_norm: sample_coverage must be positive, not {sample_coverage!r}")
+        g = self.graph
+        self.weights()                                   # the edge sampler's table is built first, as before a first draw
+        counts = None
+        num_samples = total = 0
+        while total < g.num_nodes * cov:
+            for _ in range(self.num_steps):
+                d = self.draw()
+                counts = ops.saint_coverage_count(g.rowptr, g.col, g.num_nodes, d["node_idx"], d["count"], g.node_map, out=counts)
+            num_samples += self.num_steps
+            total = int(counts[2].item())
+        self.node_count, self.edge_count = counts[0], counts[1]
+        self.num_samples, self.total_sampled_nodes, self.sample_coverage = num_samples, total, cov
+        self.edge_norm, self.node_norm = ops.saint_norms(g.rowptr, g.num_nodes, self.node_count, self.edge_count, num_samples)
+        return self
 
     def __len__(self):
         return self.num_steps
@@ -87,9 +127,16 @@ class _SaintSampler:
 
     def sample(self, *inject, **kw):
         """One batch's device arrays (no host read): the dict of draw() plus edge_src / edge_dst (int32 [e_cap]), e_count,
-        rowptr_l."""
+        rowptr_l; after estimate_norm also edge_id (int64 [e_cap]), edge_norm (fp32 [e_cap], the edges' norms) and node_norm
+        (fp32 [N], the whole table: a kernel reads it through node_idx)."""
         g = self.graph
         d = self.draw(*inject, **kw)
+        if self.edge_norm is not None:
+            src, dst, d_e, rowptr_l, edge_id, enb = ops.saint_subgraph_ids(g.rowptr, g.col, d["node_idx"], d["count"], g.node_map,
+                                                                           self.e_cap, edge_norm=self.edge_norm, status=self.status)
+            d.update(edge_src=src, edge_dst=dst, e_count=d_e, rowptr_l=rowptr_l, edge_id=edge_id, edge_norm=enb,
+                     node_norm=self.node_norm)
+            return d
         src, dst, d_e, rowptr_l = ops.saint_subgraph(g.rowptr, g.col, d["node_idx"], d["count"], g.node_map, self.e_cap,
                                                      status=self.status)
         d.update(edge_src=src, edge_dst=dst, e_count=d_e, rowptr_l=rowptr_l)
@@ -111,6 +158,8 @@ class _SaintSampler:
         node_idx = s["node_idx"][:n].long()
         out = SimpleNamespace(node_idx=node_idx, num_nodes=n, edge_index=torch.stack([s["edge_src"][:e], s["edge_dst"][:e]]).long(),
                               **{k: s[k] for k in self._extras})
+        if "edge_id" in s:
+            out.node_norm, out.edge_norm, out.edge_id = s["node_norm"][node_idx], s["edge_norm"][:e], s["edge_id"][:e]
         if self.data is not None:
             for k in ("x", "y", "train_mask", "val_mask", "test_mask"):
                 t = getattr(self.data, k, None)
@@ -165,9 +214,6 @@ class _SaintEntrySampler(_SaintSampler):
                          "batch_size" if k == 1 else f"{k} * batch_size")
         if self.graph.nnz <= 0:
             raise ValueError(f"{type(self).__name__}: the graph has no stored entry to draw")
-
-    def weights(self):
-        return None
 
     def draw_buffers(self):
         dev = self.graph.device

@@ -2490,6 +2490,101 @@ def saint_masked_loss(z, C: int, node_idx, count, train_mask, labels, g=None, lo
     return loss, g
 
 
+# ------------------------------------------------------------------------------- GraphSAINT normalisation (sample_coverage > 0)
+# [PyG-recall: GraphSAINTSampler._compute_norm / __collate__].  node_count / edge_count are int32 tensors that hold the kernels'
+# uint32 counts (torch's uint32 supports too few operations); a count reaches 2^31 only after 2^31 batches.
+def saint_coverage_count(rowptr, col, num_nodes: int, node_idx, count, node_map, out=None):
+    """(node_count int32 [N], edge_count int32 [nnz], total int64 [1]) of grapes_saint_coverage_count: one drawn batch's share of
+    the coverage counts — node_count[v] += 1 over the node set, edge_count[j] += 1 over the stored entries with both ends in it,
+    total += the set's size.  out: the three tensors to add into (None: fresh zeros).  No host read."""
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(node_idx, _i32, "node_idx"); _chk(count, _i32, "count")
+    _chk(node_map, _i32, "node_map")
+    N, dev = int(num_nodes), rowptr.device
+    if out is None:
+        out = (torch.zeros(N, dtype=_i32, device=dev), torch.zeros(max(col.numel(), 1), dtype=_i32, device=dev),
+               torch.zeros(1, dtype=_i64, device=dev))
+    node_count, edge_count, total = out
+    _chk(node_count, _i32, "node_count"); _chk(edge_count, _i32, "edge_count"); _chk(total, _i64, "total")
+    if node_count.numel() < N or edge_count.numel() < col.numel() or rowptr.numel() != N + 1 or node_map.numel() < N:
+        raise ValueError("saint_coverage_count: node_count / node_map hold one value per node, edge_count one per stored entry")
+    _lib.check(lib().grapes_saint_coverage_count(_p(rowptr), _p(col), N, _p(node_idx), _p(count), _p(node_map), node_idx.numel(),
+                                                 _p(node_count), _p(edge_count), _p(total), _stream()), "saint_coverage_count")
+    return node_count, edge_count, total
+
+
+def saint_norms(rowptr, num_nodes: int, node_count, edge_count, num_samples: int, out=None):
+    """(edge_norm fp32 [nnz], node_norm fp32 [N]) of grapes_saint_norms from the counts of num_samples batches:
+    edge_norm[j] = node_count[row(j)] / edge_count[j] clamped to [0, 1e4] (0 / 0 -> 0.1), node_norm[v] = num_samples /
+    node_count[v] / N (a count of 0 taken as 0.1), all in fp32.  out: the two tensors to write."""
+    _chk(rowptr, _i64, "rowptr"); _chk(node_count, _i32, "node_count"); _chk(edge_count, _i32, "edge_count")
+    N, dev = int(num_nodes), rowptr.device
+    if rowptr.numel() != N + 1 or node_count.numel() < N:
+        raise ValueError("saint_norms: rowptr holds N + 1 values, node_count one per node")
+    if out is None:
+        out = (torch.empty(edge_count.numel(), dtype=_f32, device=dev), torch.empty(N, dtype=_f32, device=dev))
+    edge_norm, node_norm = out
+    _chk(edge_norm, _f32, "edge_norm"); _chk(node_norm, _f32, "node_norm")
+    if edge_norm.numel() < edge_count.numel() or node_norm.numel() < N:
+        raise ValueError("saint_norms: edge_norm holds one value per stored entry, node_norm one per node")
+    _lib.check(lib().grapes_saint_norms(_p(rowptr), N, _p(node_count), _p(edge_count), int(num_samples), _p(edge_norm),
+                                        _p(node_norm), _stream()), "saint_norms")
+    return edge_norm, node_norm
+
+
+def saint_subgraph_ids(rowptr, col, node_idx, count, node_map, e_cap: int, edge_norm=None, status=None, out=None):
+    """saint_subgraph that also tells which stored entry every edge is: (edge_src, edge_dst int32 [e_cap], e_count int32 [1],
+    rowptr_l int32 [n_cap + 1], edge_id int64 [e_cap], edge_norm_b fp32 [e_cap] or None) of grapes_saint_subgraph_ids.
+    edge_id[p] = the position in col of edge p; with the table edge_norm (fp32 [nnz]) edge_norm_b[p] = edge_norm[edge_id[p]].
+    out: the six tensors to write (the last None without a table)."""
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(node_idx, _i32, "node_idx"); _chk(count, _i32, "count")
+    _chk(node_map, _i32, "node_map"); _chk(status, _i32, "status", True); _chk(edge_norm, _f32, "edge_norm", True)
+    if edge_norm is not None and edge_norm.numel() < col.numel():
+        raise ValueError("saint_subgraph_ids: edge_norm holds one value per stored entry")
+    n_cap, dev, ec = node_idx.numel(), node_idx.device, max(int(e_cap), 1)
+    if out is None:
+        out = (torch.empty(ec, dtype=_i32, device=dev), torch.empty(ec, dtype=_i32, device=dev),
+               torch.empty(1, dtype=_i32, device=dev), torch.empty(n_cap + 1, dtype=_i32, device=dev),
+               torch.empty(ec, dtype=_i64, device=dev), torch.empty(ec, dtype=_f32, device=dev) if edge_norm is not None else None)
+    src, dst, d_e, rowptr_l, edge_id, edge_norm_b = out
+    _chk(edge_id, _i64, "edge_id"); _chk(edge_norm_b, _f32, "edge_norm_b", edge_norm is None)
+    if min(src.numel(), dst.numel(), edge_id.numel()) < int(e_cap) or (edge_norm_b is not None and edge_norm_b.numel() < int(e_cap)):
+        raise ValueError("saint_subgraph_ids: the edge buffers hold e_cap values each")
+    if edge_norm is None:
+        edge_norm_b = None
+    ws = _ws(lib().grapes_saint_subgraph_workspace_bytes(n_cap), dev)
+    _lib.check(lib().grapes_saint_subgraph_ids(_p(rowptr), _p(col), _p(node_idx), _p(count), _p(node_map), n_cap, int(e_cap),
+                                               _p(rowptr_l), _p(src), _p(dst), _p(d_e), _p(edge_id), _p(edge_norm), _p(edge_norm_b),
+                                               _p(ws), _p(status), _stream()), "saint_subgraph_ids")
+    return src, dst, d_e, rowptr_l, edge_id, edge_norm_b
+
+
+def saint_masked_loss_weighted(z, C: int, node_idx, count, train_mask, node_norm, labels, g=None, loss=None, d_train=None,
+                               status=None):
+    """(loss [1], g = d loss / d z [n_cap, C]) of grapes_saint_masked_loss_weighted: the SUM over the batch rows whose node is a
+    training node of node_norm[node] * row loss (CrossEntropy for labels int64 [N]; the mean over the columns of BCEWithLogits for
+    fp32 [N, C]); no training row: loss 0, g = 0.  node_norm: fp32 [N], read through node_idx."""
+    _chk(node_idx, _i32, "node_idx"); _chk(count, _i32, "count", True); _chk(d_train, _i32, "d_train", True)
+    _chk(status, _i32, "status", True); _chk(node_norm, _f32, "node_norm")
+    if z.dtype != _f32 or not z.is_cuda or z.dim() != 2 or z.stride(1) != 1:
+        raise _lib.GrapesHipError("saint_masked_loss_weighted: expected a CUDA fp32 matrix with unit column stride")
+    if not train_mask.is_cuda or train_mask.dtype not in (torch.bool, torch.uint8):
+        raise _lib.GrapesHipError("saint_masked_loss_weighted: train_mask must be a cuda bool / uint8 vector")
+    multi = labels.dim() == 2
+    _chk(labels, _f32 if multi else _i64, "labels")
+    if node_norm.numel() != train_mask.numel():
+        raise ValueError("saint_masked_loss_weighted: node_norm holds one value per node, like train_mask")
+    n_cap = z.shape[0]
+    if g is None:
+        g = torch.empty((n_cap, int(C)), dtype=_f32, device=z.device)
+    if loss is None:
+        loss = torch.empty(1, dtype=_f32, device=z.device)
+    _lib.check(lib().grapes_saint_masked_loss_weighted(_p(z), z.stride(0), int(C), _p(node_idx), _p(count), n_cap, _p(train_mask),
+                                                       _p(node_norm), None if multi else _p(labels), _p(labels) if multi else None,
+                                                       _p(g), g.stride(0), _p(loss), _p(d_train), _p(status), _stream()),
+               "saint_masked_loss_weighted")
+    return loss, g
+
+
 def classifier_loss(logits, local_rows, target_ids, labels, out_grad=None):
     """(loss_c [1], d loss_c / d logits [n_rows, C]) — main.py:260,267.  labels: int64 [N] or fp32 [N, C]."""
     _chk(logits, _f32, "logits"); _chk(local_rows, _i32, "local_rows"); _chk(target_ids, _i32, "target_ids")

@@ -14,6 +14,12 @@ Both draw from the same Philox stream (seed, device offset), so from one seed th
 
 The loss of a batch without a training row is NaN with gradients exactly zero (torch's mean over an empty selection), and the
 optimiser still steps — as in the reference.
+
+use_normalization=True with sample_coverage=K > 0 (both trainers, any sampler) trains with GraphSAINT's bias correction [PyG-recall:
+PyG 2.5 examples/graph_saint.py, whose flag the reference copied]: the loader's estimate_norm(K) runs at construction (it reads the
+host once per pass, so before any capture), the model runs with edge_weight = the batch's edge_norm, and the loss is
+sum over the training rows of node_norm * row loss — a sum, not a mean; a batch without a training row gives 0.  The defaults
+(0, False) give the step described above, launch for launch.
 """
 from __future__ import annotations
 
@@ -22,7 +28,7 @@ from typing import Optional
 import torch
 
 from . import ops
-from .modules.gcn import GCN
+from .modules.gcn import GCN, _WeightedGCNConvFn
 from .modules.saint import make_sampler
 
 
@@ -68,11 +74,59 @@ def masked_loss(logits, node_idx, count, train_mask, y, g=None, loss=None):
     return _MaskedLoss.apply(logits, node_idx, count, train_mask, y, g, loss)
 
 
+class _WeightedLoss(torch.autograd.Function):
+    """The normalised step's loss on the device count of training rows (ops.saint_masked_loss_weighted)."""
+
+    @staticmethod
+    def forward(ctx, z, node_idx, count, train_mask, node_norm, y, g, loss):
+        loss, g = ops.saint_masked_loss_weighted(z.contiguous(), z.shape[1], node_idx, count, train_mask, node_norm, y, g=g,
+                                                 loss=loss)
+        ctx.g = g
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, gl):
+        return ctx.g * gl, None, None, None, None, None, None, None
+
+
+def weighted_loss(logits, node_idx, count, train_mask, node_norm, y, g=None, loss=None):
+    """Sum over the rows of `logits` whose node (node_idx) is a training node of node_norm[node] * (CE for 1-D y, the mean over the
+    columns of BCEWithLogits for 2-D y)."""
+    return _WeightedLoss.apply(logits, node_idx, count, train_mask, node_norm, y, g, loss)
+
+
+def _normalised(loader, sample_coverage, use_normalization) -> bool:
+    """Validates the two arguments; with both on runs the loader's estimate and returns True."""
+    cov = int(sample_coverage)
+    if cov < 0:
+        raise ValueError(f"sample_coverage must not be negative, not {sample_coverage!r}")
+    if use_normalization and cov == 0:
+        raise ValueError("use_normalization needs the coverage estimate: pass sample_coverage > 0")
+    if cov and not use_normalization:
+        raise ValueError("sample_coverage > 0 estimates norms that only the normalised step reads: pass use_normalization=True")
+    if not use_normalization:
+        return False
+    loader.estimate_norm(cov)
+    return True
+
+
+def _weighted_gcn(model: GCN, x, ws: "ops.WeightedStructure", edge_weight):
+    """GCN.forward over a prepared weighted structure (GCNConv.forward refuses edge weights with a PreparedGraph, whose edge list
+    it does not have): _WeightedGCNConvFn per layer, the ReLU fused on the hidden layers, dropout as GCN.forward."""
+    n_layers = len(model.gcn_layers)
+    for i, layer in enumerate(model.gcn_layers):
+        last = i == n_layers - 1
+        x = _WeightedGCNConvFn.apply(x, layer.lin.weight, layer.bias, edge_weight, ws, not last, layer._mode, layer._fill)
+        x = model._drop(x)
+    return x
+
+
 class EagerSaintTrainer:
     def __init__(self, graph, x, y, train_mask, model: GCN, optimizer, batch_size=256, walk_length=2, num_steps=1, seed=None,
-                 e_cap=None, sampler="rw"):
+                 e_cap=None, sampler="rw", sample_coverage=0, use_normalization=False):
         self.loader = make_sampler(sampler, graph, batch_size, walk_length, num_steps=num_steps, seed=seed, e_cap=e_cap)
         self.x, self.y, self.train_mask, self.model, self.optimizer = x, y, train_mask, model, optimizer
+        self.normalised = _normalised(self.loader, sample_coverage, use_normalization)
 
     def step(self, *inject, **kw):
         """One step (graphsaint.py:26-36); returns (loss tensor, batch).  inject: the sampler's injected draws (roots, uniforms
@@ -81,8 +135,12 @@ class EagerSaintTrainer:
         ids = b.node_idx.to(torch.int32)
         self.optimizer.zero_grad()                                                          # graphsaint.py:29
         x = _GatherX.apply(self.x, ids, None, None, False)                                  # batch.x (data.x gathered)
-        out = self.model(x, b.edge_index)                                                   # graphsaint.py:31
-        loss = masked_loss(out[0], ids, None, self.train_mask, self.y)                      # graphsaint.py:32-34
+        if self.normalised:
+            out = self.model(x, b.edge_index, edge_weight=b.edge_norm)
+            loss = weighted_loss(out[0], ids, None, self.train_mask, self.loader.node_norm, self.y)
+        else:
+            out = self.model(x, b.edge_index)                                               # graphsaint.py:31
+            loss = masked_loss(out[0], ids, None, self.train_mask, self.y)                  # graphsaint.py:32-34
         loss.backward()                                                                     # graphsaint.py:36
         self.optimizer.step()                                                               # graphsaint.py:37
         return loss.detach(), b
@@ -104,9 +162,10 @@ class GraphedSaintTrainer:
     is stepped by ops.FusedAdam."""
 
     def __init__(self, graph, x, y, train_mask, model: GCN, optimizer, batch_size=256, walk_length=2, num_steps=1, seed=None,
-                 e_cap=None, sampler="rw"):
+                 e_cap=None, sampler="rw", sample_coverage=0, use_normalization=False):
         self.loader = make_sampler(sampler, graph, batch_size, walk_length, num_steps=num_steps, seed=seed, e_cap=e_cap)
         L = self.loader
+        self.normalised = _normalised(L, sample_coverage, use_normalization)     # (reads the host: before the capture)
         g = L.graph
         dev = g.device
         self.x, self.y, self.train_mask, self.model, self.optimizer = x, y, train_mask, model, optimizer
@@ -119,6 +178,9 @@ class GraphedSaintTrainer:
             L.weights()                                  # the one-time table (one host read) is built before the capture
         self.sub_out = (torch.zeros(self.e_cap, **i32), torch.zeros(self.e_cap, **i32), torch.zeros(1, **i32),
                         torch.zeros(self.n_cap + 1, **i32))
+        if self.normalised:                              # the edges' entry positions and norms, beside src / dst
+            self.sub_out = self.sub_out + (torch.zeros(self.e_cap, dtype=torch.int64, device=dev),
+                                           torch.zeros(self.e_cap, dtype=torch.float32, device=dev))
         self.xbuf = torch.zeros((self.n_cap, x.shape[1]), dtype=torch.float32, device=dev)
         self.gbuf = torch.zeros((self.n_cap, C), dtype=torch.float32, device=dev)
         self.lossbuf = torch.zeros(1, dtype=torch.float32, device=dev)
@@ -133,6 +195,8 @@ class GraphedSaintTrainer:
         g = L.graph
         d = L.draw(out=self.draw_out)
         node_idx, count = d["node_idx"], d["count"]
+        if self.normalised:
+            return self._body_normalised(node_idx, count)
         src, dst, d_e, _ = ops.saint_subgraph(g.rowptr, g.col, node_idx, count, g.node_map, self.e_cap, status=L.status,
                                               out=self.sub_out)
         if self.n_cap <= ops._SMALL_GRAPH:
@@ -144,6 +208,25 @@ class GraphedSaintTrainer:
         xb = _GatherX.apply(self.x, node_idx, count, self.xbuf, True)
         out = self.model(xb, prep)
         loss = masked_loss(out[0], node_idx, count, self.train_mask, self.y, g=self.gbuf, loss=self.lossbuf)
+        loss.backward()
+        self.fused.step()
+        self.loss_sum.add_(self.lossbuf)
+
+    def _body_normalised(self, node_idx, count):
+        """The rest of the step with GraphSAINT's norms.  The graph is the general PreparedGraph at every n_cap:
+        ops.WeightedStructure looks every entry up by binary search in the CSRs of that preparation (ascending neighbour ids per
+        row), which the small_batch form is not specified to produce."""
+        L = self.loader
+        g = L.graph
+        src, dst, d_e, _, _, enb = ops.saint_subgraph_ids(g.rowptr, g.col, node_idx, count, g.node_map, self.e_cap,
+                                                          edge_norm=L.edge_norm, status=L.status, out=self.sub_out)
+        prep = ops.PreparedGraph(src, dst, self.n_cap, d_n=count, d_e=d_e, status=L.status, src_grouped=True)
+        ws = ops.WeightedStructure(prep, src, dst)
+        for p in self.params:
+            p.grad.zero_()
+        xb = _GatherX.apply(self.x, node_idx, count, self.xbuf, True)
+        out = _weighted_gcn(self.model, xb, ws, enb)
+        loss = weighted_loss(out, node_idx, count, self.train_mask, L.node_norm, self.y, g=self.gbuf, loss=self.lossbuf)
         loss.backward()
         self.fused.step()
         self.loss_sum.add_(self.lossbuf)

@@ -54,7 +54,8 @@ extern "C" {
  * grapes_gat_aggregate_fwd / _bwd (+ _workspace_bytes each); the GCN2 classifier (modules/gcn.py:76-117) —
  * grapes_gcn2_loop_counts(_csr), grapes_gcn2_propagate_fwd / _bwd (+ _workspace_bytes), grapes_gcn2_mix_fwd / _bwd; the PNA
  * classifier (modules/gcn.py:120-149) — grapes_pna_aggregate_fwd / _bwd (+ _workspace_bytes each), grapes_pna_add_input_grad; GraphSAINT's node and edge
- * samplers — grapes_saint_edge_weights, grapes_saint_draw_nodes; GCNConv with edge weights — grapes_wgcn_structure(_workspace_bytes),
+ * samplers — grapes_saint_edge_weights, grapes_saint_draw_nodes; GraphSAINT's normalisation — grapes_saint_coverage_count,
+ * grapes_saint_norms, grapes_saint_subgraph_ids, grapes_saint_masked_loss_weighted; GCNConv with edge weights — grapes_wgcn_structure(_workspace_bytes),
  * grapes_wgcn_weights, grapes_wgcn_aggregate_fwd / _bwd (+ _workspace_bytes each); GCNConv's improved / add_self_loops / normalize —
  * grapes_wgcn_loops(_workspace_bytes), grapes_wgcn_weights_mode, grapes_wgcn_aggregate_fwd_mode / _bwd_mode. */
 #define GRAPES_ABI_VERSION 302
@@ -1378,6 +1379,33 @@ int grapes_saint_edge_weights(const int64_t* rowptr, const int32_t* col, int32_t
  * Then node_idx / *d_count / node_map as grapes_saint_walk_nodes writes them, over the B (node) or 2 B (edge) ids (<= 16384).
  * *d_philox_offset advances by ceil(2 B / 4).  Two launches: one wavefront per draw, then one workgroup. */
 int grapes_saint_draw_nodes(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, int32_t B, const int32_t* colcount, const int64_t* blockw, const int64_t* roww, const int64_t* draws, uint64_t philox_seed, uint64_t philox_offset, uint64_t* d_philox_offset, int32_t* ids, int64_t* entries, int32_t* node_idx, int32_t* d_count, int32_t* node_map, int32_t* status, grapes_stream_t stream);
+/* GraphSAINT's normalisation (sample_coverage > 0) [PyG-recall: PyG 2.5 GraphSAINTSampler._compute_norm / __collate__ and
+ * examples/graph_saint.py].  Stored entry j is position j of col; row(j) is the CSR row (the source) that holds it.
+ * One drawn batch's share of the coverage counts: node_count[v] += 1 (uint32[N]) for every v of the node set (node_idx / *d_count /
+ * node_map as the draw wrote them), edge_count[j] += 1 (uint32[nnz]) for every stored entry j whose row and column are both in the
+ * set (stored loops and duplicate entries are each their own j), *d_total += the set's size (int64, on the device).  The caller
+ * zeroes the three before the first batch.  One wavefront per local row; every v and every j is touched by one thread and batches
+ * are serial on the stream, so there are no atomics and the counts are exact and deterministic.  The subgraph is not formed and
+ * nothing is read back.  One launch. */
+int grapes_saint_coverage_count(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* node_idx, const int32_t* d_count, const int32_t* node_map, int32_t n_cap, uint32_t* node_count, uint32_t* edge_count, int64_t* d_total, grapes_stream_t stream);
+/* The two norm vectors from the counts of num_samples batches:
+ *   edge_norm[j] = fp32(node_count[row(j)]) / fp32(edge_count[j]) clamped to [0, 1e4]; a NaN (0 / 0) becomes 0.1, so x / 0 with
+ *     x > 0 gives 1e4;
+ *   node_norm[v] = (fp32(num_samples) / c) / fp32(N), c = fp32(node_count[v]), or 0.1 where the count is 0.
+ * One wavefront per CSR row, rows shorter and longer than a wavefront alike.  One launch. */
+int grapes_saint_norms(const int64_t* rowptr, int32_t num_nodes, const uint32_t* node_count, const uint32_t* edge_count, int64_t num_samples, float* edge_norm, float* node_norm, grapes_stream_t stream);
+/* grapes_saint_subgraph with every edge's origin: edge_id[p] = j (int64[e_cap], NULL: not wanted), the position in col of the entry
+ * that became edge p, and, when the table edge_norm (fp32[nnz]) is given, edge_norm_b[p] = edge_norm[j] (fp32[e_cap]; both NULL or
+ * both given) — written at the same slot p as edge_src / edge_dst, nothing at or past e_cap.  Everything else (outputs, order,
+ * overflow bit, workspace, three launches) as grapes_saint_subgraph. */
+int grapes_saint_subgraph_ids(const int64_t* rowptr, const int32_t* col, const int32_t* node_idx, const int32_t* d_count, const int32_t* node_map, int32_t n_cap, int32_t e_cap, int32_t* rowptr_l, int32_t* edge_src, int32_t* edge_dst, int32_t* d_e, int64_t* edge_id, const float* edge_norm, float* edge_norm_b, void* workspace, int32_t* status, grapes_stream_t stream);
+/* The normalised step's loss: grapes_saint_masked_loss with a per-node weight table node_norm (fp32[N]), read through node_idx like
+ * train_mask.  *loss_out = sum over the training rows i of node_norm[node_idx[i]] * rowloss_i — a sum, not divided by T; rowloss
+ * is CrossEntropy (labels int64[N]) or the mean over the C columns of the BCEWithLogits elements (labels_f fp32[N, C]).
+ * g row i = w_i (softmax - onehot) or w_i (sigmoid(z) - y) / C; 0 on other rows.  T = 0: *loss_out = 0 and g = 0.  A label outside
+ * [0, C) ORs GRAPES_STATUS_BAD_INDEX into status and the row counts nothing.  ONE workgroup, fixed summation order, no float
+ * atomics. */
+int grapes_saint_masked_loss_weighted(const float* z, int64_t ldz, int32_t C, const int32_t* node_idx, const int32_t* d_count, int32_t n_cap, const uint8_t* train_mask, const float* node_norm, const int64_t* labels, const float* labels_f, float* g, int64_t ldg, float* loss_out, int32_t* d_train, int32_t* status, grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:
