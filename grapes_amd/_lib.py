@@ -16,7 +16,7 @@ DIAG_LIB_PATH = os.path.join(_HERE, "libgrapes_hip_diag.so")
 # switches on (diag_switch below).  GRAPES_LIB_PATH overrides the path (other diagnostic builds: stamps, lb768).
 DIAG = os.environ.get("GRAPES_DIAG", "0") == "1"
 LIB_PATH = os.environ.get("GRAPES_LIB_PATH") or (DIAG_LIB_PATH if DIAG else os.path.join(_HERE, "libgrapes_hip.so"))
-ABI_MAJOR, ABI_MINOR = 3, 2          # include/grapes_hip.h: GRAPES_ABI_VERSION = 100 * MAJOR + MINOR
+ABI_MAJOR, ABI_MINOR = 3, 3          # include/grapes_hip.h: GRAPES_ABI_VERSION = 100 * MAJOR + MINOR
 
 
 def diag_switch(name: str, default: str) -> str:
@@ -75,16 +75,14 @@ SIGNATURES = {
     "grapes_rowlist_loss": (I32, [P, I64, I32, P, I32, P, P, P, F32, U64, U64, P, I64, I32, P, P, P, P, P]),
     "grapes_saint_walk_nodes": (I32, [P, P, I32, I32, I32, P, P, U64, U64, P, P, P, P, P, P, P]),
     "grapes_saint_subgraph_workspace_bytes": (SZ, [I32]),
-    "grapes_saint_subgraph": (I32, [P, P, P, P, P, I32, I32, P, P, P, P, P, P, P]),
-    "grapes_saint_masked_loss": (I32, [P, I64, I32, P, P, I32, P, P, P, P, I64, P, P, P, P]),
+    "grapes_saint_subgraph": (I32, [P, P, P, P, P, I32, I32, P, P, P, P, P, P, P, P, P, P]),
+    "grapes_saint_masked_loss": (I32, [P, I64, I32, P, P, I32, P, P, P, P, P, I64, P, P, P, P]),
     # GraphSAINT's node and edge samplers (graphsaint.py:8)
     "grapes_saint_edge_weights": (I32, [P, P, I32, I64, P, P, P, P, P]),
     "grapes_saint_draw_nodes": (I32, [P, P, I32, I32, P, P, P, P, U64, U64, P, P, P, P, P, P, P, P]),
     # GraphSAINT's normalisation (sample_coverage > 0)
     "grapes_saint_coverage_count": (I32, [P, P, I32, P, P, P, I32, P, P, P, P]),
     "grapes_saint_norms": (I32, [P, I32, P, P, I64, P, P, P]),
-    "grapes_saint_subgraph_ids": (I32, [P, P, P, P, P, I32, I32, P, P, P, P, P, P, P, P, P, P]),
-    "grapes_saint_masked_loss_weighted": (I32, [P, I64, I32, P, P, I32, P, P, P, P, P, I64, P, P, P, P]),
     # GATConv aggregation (modules/gcn.py:45-72)
     "grapes_gat_scores": (I32, [P, P, P, P, P, I32, P, I32, P]),
     "grapes_gat_aggregate_workspace_bytes": (SZ, [I32, I32]),
@@ -102,16 +100,13 @@ SIGNATURES = {
     # GCNConv with edge weights (PyG GCNConv.forward(x, edge_index, edge_weight))
     "grapes_wgcn_structure_workspace_bytes": (SZ, [I32]),
     "grapes_wgcn_structure": (I32, [P, P, I32, P, I32, P] + [P] * 12),
-    "grapes_wgcn_weights": (I32, [P, I32, P, P, P, P, P, I32, P, P, P, P, P, P]),
+    "grapes_wgcn_weights": (I32, [P, I32] + [P] * 7 + [I32, P, I32, F32] + [P] * 5),
     "grapes_wgcn_aggregate_workspace_bytes": (SZ, [I32, I32]),
-    "grapes_wgcn_aggregate_fwd": (I32, [P] * 8 + [I32, P, I32, I32, P, P, I32, P, P, P]),
+    "grapes_wgcn_aggregate_fwd": (I32, [P] * 8 + [I32, P, I32, I32, I32, P, P, I32, P, P, P]),
     "grapes_wgcn_aggregate_bwd_workspace_bytes": (SZ, [I32, I32, I32, I32]),
-    "grapes_wgcn_aggregate_bwd": (I32, [P] * 5 + [I32] + [P] * 14 + [I32, P, I32, P, P, P, P, I32, P, P, P]),
+    "grapes_wgcn_aggregate_bwd": (I32, [P] * 5 + [I32] + [P] * 14 + [I32, P, I32, I32, P, P, P, P, I32, P, P, P]),
     "grapes_wgcn_loops_workspace_bytes": (SZ, [I32, I32]),
     "grapes_wgcn_loops": (I32, [P, P, I32, P, I32, P, P, P, P, P]),
-    "grapes_wgcn_weights_mode": (I32, [P, I32] + [P] * 7 + [I32, P, I32, F32] + [P] * 5),
-    "grapes_wgcn_aggregate_fwd_mode": (I32, [P] * 8 + [I32, P, I32, I32, I32, P, P, I32, P, P, P]),
-    "grapes_wgcn_aggregate_bwd_mode": (I32, [P] * 5 + [I32] + [P] * 14 + [I32, P, I32, I32, P, P, P, P, I32, P, P, P]),
     "grapes_pna_aggregate_fwd_workspace_bytes": (SZ, [I32, I32]),
     "grapes_pna_aggregate_fwd": (I32, [P, P, P, I32, P, P, P, I32, I32, I32, I32, F32, F32, P, P, I32, P, I32, P, P, I32, P, P, P]),
     "grapes_pna_aggregate_bwd_workspace_bytes": (SZ, [I32, I32, I32]),

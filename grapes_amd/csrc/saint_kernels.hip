@@ -587,30 +587,8 @@ extern "C" size_t grapes_saint_subgraph_workspace_bytes(int32_t n_cap) {
 
 extern "C" int grapes_saint_subgraph(const int64_t* rowptr, const int32_t* col, const int32_t* node_idx, const int32_t* d_count,
                                      const int32_t* node_map, int32_t n_cap, int32_t e_cap, int32_t* rowptr_l, int32_t* edge_src,
-                                     int32_t* edge_dst, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream) {
-    if (n_cap <= 0 || n_cap > SAINT_MAX_IDS || e_cap <= 0) return GRAPES_EINVAL;
-    if (!rowptr || !col || !node_idx || !d_count || !node_map || !rowptr_l || !edge_src || !edge_dst || !d_e || !workspace)
-        return GRAPES_EINVAL;
-    if ((uintptr_t)workspace & 3) return GRAPES_EALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    int32_t* cnt = (int32_t*)workspace;
-    const int grid = grapes_div_up((int64_t)n_cap * 64, 256);
-    hipLaunchKernelGGL(saint_edge_count_k, dim3(grid), dim3(256), 0, s, rowptr, col, node_idx, d_count, node_map, n_cap, cnt);
-    GRAPES_LAUNCH_CHECK();
-    hipLaunchKernelGGL(saint_edge_scan_k, dim3(1), dim3(SAINT_THREADS), 0, s, (const int32_t*)cnt, d_count, n_cap, e_cap, rowptr_l,
-                       d_e, status);
-    GRAPES_LAUNCH_CHECK();
-    hipLaunchKernelGGL(saint_edge_write_k<false>, dim3(grid), dim3(256), 0, s, rowptr, col, node_idx, d_count, node_map, n_cap,
-                       (const int32_t*)rowptr_l, e_cap, edge_src, edge_dst, (int64_t*)nullptr, (const float*)nullptr,
-                       (float*)nullptr);
-    GRAPES_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int grapes_saint_subgraph_ids(const int64_t* rowptr, const int32_t* col, const int32_t* node_idx, const int32_t* d_count,
-                                         const int32_t* node_map, int32_t n_cap, int32_t e_cap, int32_t* rowptr_l, int32_t* edge_src,
-                                         int32_t* edge_dst, int32_t* d_e, int64_t* edge_id, const float* edge_norm,
-                                         float* edge_norm_b, void* workspace, int32_t* status, grapes_stream_t stream) {
+                                     int32_t* edge_dst, int32_t* d_e, int64_t* edge_id, const float* edge_norm, float* edge_norm_b,
+                                     void* workspace, int32_t* status, grapes_stream_t stream) {
     if (n_cap <= 0 || n_cap > SAINT_MAX_IDS || e_cap <= 0) return GRAPES_EINVAL;
     if (!rowptr || !col || !node_idx || !d_count || !node_map || !rowptr_l || !edge_src || !edge_dst || !d_e || !workspace)
         return GRAPES_EINVAL;
@@ -624,20 +602,13 @@ extern "C" int grapes_saint_subgraph_ids(const int64_t* rowptr, const int32_t* c
     hipLaunchKernelGGL(saint_edge_scan_k, dim3(1), dim3(SAINT_THREADS), 0, s, (const int32_t*)cnt, d_count, n_cap, e_cap, rowptr_l,
                        d_e, status);
     GRAPES_LAUNCH_CHECK();
-    hipLaunchKernelGGL(saint_edge_write_k<true>, dim3(grid), dim3(256), 0, s, rowptr, col, node_idx, d_count, node_map, n_cap,
-                       (const int32_t*)rowptr_l, e_cap, edge_src, edge_dst, edge_id, edge_norm, edge_norm_b);
-    GRAPES_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int grapes_saint_masked_loss(const float* z, int64_t ldz, int32_t C, const int32_t* node_idx, const int32_t* d_count,
-                                        int32_t n_cap, const uint8_t* train_mask, const int64_t* labels, const float* labels_f,
-                                        float* g, int64_t ldg, float* loss_out, int32_t* d_train, int32_t* status,
-                                        grapes_stream_t stream) {
-    if (C <= 0 || n_cap <= 0 || ldz < C || ldg < C) return GRAPES_EINVAL;
-    if (!z || !node_idx || !train_mask || !g || !loss_out || ((labels == nullptr) == (labels_f == nullptr))) return GRAPES_EINVAL;
-    hipLaunchKernelGGL(saint_masked_loss_k, dim3(1), dim3(SAINT_THREADS), 0, (hipStream_t)stream, z, ldz, C, node_idx, d_count, n_cap,
-                       train_mask, labels, labels_f, g, ldg, loss_out, d_train, status);
+    if (edge_id || edge_norm)
+        hipLaunchKernelGGL(saint_edge_write_k<true>, dim3(grid), dim3(256), 0, s, rowptr, col, node_idx, d_count, node_map, n_cap,
+                           (const int32_t*)rowptr_l, e_cap, edge_src, edge_dst, edge_id, edge_norm, edge_norm_b);
+    else
+        hipLaunchKernelGGL(saint_edge_write_k<false>, dim3(grid), dim3(256), 0, s, rowptr, col, node_idx, d_count, node_map, n_cap,
+                           (const int32_t*)rowptr_l, e_cap, edge_src, edge_dst, (int64_t*)nullptr, (const float*)nullptr,
+                           (float*)nullptr);
     GRAPES_LAUNCH_CHECK();
     return 0;
 }
@@ -705,16 +676,18 @@ extern "C" int grapes_saint_norms(const int64_t* rowptr, int32_t num_nodes, cons
     return 0;
 }
 
-extern "C" int grapes_saint_masked_loss_weighted(const float* z, int64_t ldz, int32_t C, const int32_t* node_idx,
-                                                 const int32_t* d_count, int32_t n_cap, const uint8_t* train_mask,
-                                                 const float* node_norm, const int64_t* labels, const float* labels_f, float* g,
-                                                 int64_t ldg, float* loss_out, int32_t* d_train, int32_t* status,
-                                                 grapes_stream_t stream) {
+extern "C" int grapes_saint_masked_loss(const float* z, int64_t ldz, int32_t C, const int32_t* node_idx, const int32_t* d_count,
+                                        int32_t n_cap, const uint8_t* train_mask, const float* node_norm, const int64_t* labels,
+                                        const float* labels_f, float* g, int64_t ldg, float* loss_out, int32_t* d_train,
+                                        int32_t* status, grapes_stream_t stream) {
     if (C <= 0 || n_cap <= 0 || ldz < C || ldg < C) return GRAPES_EINVAL;
-    if (!z || !node_idx || !train_mask || !node_norm || !g || !loss_out || ((labels == nullptr) == (labels_f == nullptr)))
-        return GRAPES_EINVAL;
-    hipLaunchKernelGGL(saint_masked_loss_weighted_k, dim3(1), dim3(SAINT_THREADS), 0, (hipStream_t)stream, z, ldz, C, node_idx, d_count,
-                       n_cap, train_mask, node_norm, labels, labels_f, g, ldg, loss_out, d_train, status);
+    if (!z || !node_idx || !train_mask || !g || !loss_out || ((labels == nullptr) == (labels_f == nullptr))) return GRAPES_EINVAL;
+    if (node_norm)
+        hipLaunchKernelGGL(saint_masked_loss_weighted_k, dim3(1), dim3(SAINT_THREADS), 0, (hipStream_t)stream, z, ldz, C, node_idx,
+                           d_count, n_cap, train_mask, node_norm, labels, labels_f, g, ldg, loss_out, d_train, status);
+    else
+        hipLaunchKernelGGL(saint_masked_loss_k, dim3(1), dim3(SAINT_THREADS), 0, (hipStream_t)stream, z, ldz, C, node_idx, d_count,
+                           n_cap, train_mask, labels, labels_f, g, ldg, loss_out, d_train, status);
     GRAPES_LAUNCH_CHECK();
     return 0;
 }

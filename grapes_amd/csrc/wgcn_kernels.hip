@@ -740,18 +740,9 @@ static int wg_weights(const float* edge_weight, int32_t e, const int32_t* inv_t,
 }
 
 extern "C" int grapes_wgcn_weights(const float* edge_weight, int32_t e, const int32_t* inv_t, const int32_t* inv_s,
-                                   const int32_t* loop_src, const int32_t* rowptr_t, const int32_t* rowptr_s, int32_t n,
-                                   const int32_t* d_n, float* val_t, float* val_s, float* lw, float* dinv, grapes_stream_t stream) {
-    if (n < 0 || e < 0 || !loop_src || !rowptr_t || !rowptr_s || !lw || !dinv) return GRAPES_EINVAL;
-    if (e > 0 && (!edge_weight || !inv_t || !inv_s || !val_t || !val_s)) return GRAPES_EINVAL;
-    return wg_weights(edge_weight, e, inv_t, inv_s, loop_src, nullptr, nullptr, rowptr_t, rowptr_s, n, d_n, WG_LOOP_FILL, 1.f, val_t, val_s,
-                      lw, dinv, (hipStream_t)stream);
-}
-
-extern "C" int grapes_wgcn_weights_mode(const float* edge_weight, int32_t e, const int32_t* inv_t, const int32_t* inv_s,
-                                        const int32_t* loop_src, const int32_t* loop_ptr, const int32_t* loop_idx,
-                                        const int32_t* rowptr_t, const int32_t* rowptr_s, int32_t n, const int32_t* d_n, int32_t mode,
-                                        float fill, float* val_t, float* val_s, float* lw, float* dinv, grapes_stream_t stream) {
+                                   const int32_t* loop_src, const int32_t* loop_ptr, const int32_t* loop_idx, const int32_t* rowptr_t,
+                                   const int32_t* rowptr_s, int32_t n, const int32_t* d_n, int32_t mode, float fill, float* val_t,
+                                   float* val_s, float* lw, float* dinv, grapes_stream_t stream) {
     if (n < 0 || e < 0 || !rowptr_t || !rowptr_s || !lw || mode < WG_LOOP_FILL || mode > WG_UNNORM) return GRAPES_EINVAL;
     if (mode == WG_LOOP_FILL ? !loop_src : (!loop_ptr || (e > 0 && !loop_idx))) return GRAPES_EINVAL;
     if (mode != WG_UNNORM && !dinv) return GRAPES_EINVAL;
@@ -817,17 +808,9 @@ static int wg_forward(const float* h, const int32_t* rowptr_t, const int32_t* cs
 }
 extern "C" int grapes_wgcn_aggregate_fwd(const float* h, const int32_t* rowptr_t, const int32_t* csr_src, const float* val_t,
                                          const float* dinv, const float* lw, const float* bias, float* out, int32_t n,
-                                         const int32_t* d_n, int32_t f, int32_t relu, const int32_t* long_items,
+                                         const int32_t* d_n, int32_t f, int32_t relu, int32_t mode, const int32_t* long_items,
                                          const int32_t* d_n_items, int32_t item_cap, void* workspace, int32_t* status,
                                          grapes_stream_t stream) {
-    return wg_forward(h, rowptr_t, csr_src, val_t, dinv, lw, bias, out, n, d_n, f, relu, true, long_items, d_n_items, item_cap, workspace,
-                      status, stream);
-}
-extern "C" int grapes_wgcn_aggregate_fwd_mode(const float* h, const int32_t* rowptr_t, const int32_t* csr_src, const float* val_t,
-                                              const float* dinv, const float* lw, const float* bias, float* out, int32_t n,
-                                              const int32_t* d_n, int32_t f, int32_t relu, int32_t mode, const int32_t* long_items,
-                                              const int32_t* d_n_items, int32_t item_cap, void* workspace, int32_t* status,
-                                              grapes_stream_t stream) {
     if (mode < WG_LOOP_FILL || mode > WG_UNNORM) return GRAPES_EINVAL;
     return wg_forward(h, rowptr_t, csr_src, val_t, dinv, lw, bias, out, n, d_n, f, relu, mode != WG_UNNORM, long_items, d_n_items, item_cap,
                       workspace, status, stream);
@@ -933,21 +916,9 @@ extern "C" int grapes_wgcn_aggregate_bwd(const float* dout, const float* relu_ou
                                          const int32_t* loop_src, const int32_t* rowptr_t, const int32_t* csr_src, const float* val_t,
                                          const int32_t* rowptr_s, const int32_t* csr_dst, const float* val_s, const float* dinv,
                                          const float* lw, float* dh, float* dbias, float* dw, int32_t n, const int32_t* d_n,
-                                         int32_t f, const int32_t* items_t, const int32_t* d_n_items_t, const int32_t* items_s,
-                                         const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status,
-                                         grapes_stream_t stream) {
-    return wg_backward(dout, relu_out, h, edge_src, edge_dst, e, d_e, pos_t, loop_src, rowptr_t, csr_src, val_t, rowptr_s, csr_dst, val_s,
-                       dinv, lw, dh, dbias, dw, n, d_n, f, WG_LOOP_FILL, items_t, d_n_items_t, items_s, d_n_items_s, item_cap, workspace,
-                       status, stream);
-}
-extern "C" int grapes_wgcn_aggregate_bwd_mode(const float* dout, const float* relu_out, const float* h, const int32_t* edge_src,
-                                              const int32_t* edge_dst, int32_t e, const int32_t* d_e, const int32_t* pos_t,
-                                              const int32_t* loop_src, const int32_t* rowptr_t, const int32_t* csr_src,
-                                              const float* val_t, const int32_t* rowptr_s, const int32_t* csr_dst, const float* val_s,
-                                              const float* dinv, const float* lw, float* dh, float* dbias, float* dw, int32_t n,
-                                              const int32_t* d_n, int32_t f, int32_t mode, const int32_t* items_t,
-                                              const int32_t* d_n_items_t, const int32_t* items_s, const int32_t* d_n_items_s,
-                                              int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream) {
+                                         int32_t f, int32_t mode, const int32_t* items_t, const int32_t* d_n_items_t,
+                                         const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap, void* workspace,
+                                         int32_t* status, grapes_stream_t stream) {
     if (mode < WG_LOOP_FILL || mode > WG_UNNORM) return GRAPES_EINVAL;
     return wg_backward(dout, relu_out, h, edge_src, edge_dst, e, d_e, pos_t, loop_src, rowptr_t, csr_src, val_t, rowptr_s, csr_dst, val_s,
                        dinv, lw, dh, dbias, dw, n, d_n, f, mode, items_t, d_n_items_t, items_s, d_n_items_s, item_cap, workspace, status,

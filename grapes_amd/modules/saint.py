@@ -26,7 +26,7 @@ exact), then forms
     node_norm[v] = (fp32(num_samples) / fp32(node_count[v])) / fp32(N), a count of 0 taken as 0.1
 (ops.saint_norms).  Afterwards every batch also carries node_norm = node_norm[node_idx] ([n]), edge_id (int64 [E], the position in
 col of every edge, in the batch's edge order) and edge_norm = edge_norm[edge_id] ([E]) — what modules.gcn.GCNConv.forward(...,
-edge_weight=) and ops.saint_masked_loss_weighted take.  Without the call batches are what they were.
+edge_weight=) and ops.saint_masked_loss(..., node_norm=) take.  Without the call batches are what they were.
 
 The draws come from the project's Philox stream (seed, device offset): see ops.saint_walk_nodes, ops.saint_draw_nodes and DESIGN.md.
 """
@@ -131,15 +131,11 @@ class _SaintSampler:
         (fp32 [N], the whole table: a kernel reads it through node_idx)."""
         g = self.graph
         d = self.draw(*inject, **kw)
-        if self.edge_norm is not None:
-            src, dst, d_e, rowptr_l, edge_id, enb = ops.saint_subgraph_ids(g.rowptr, g.col, d["node_idx"], d["count"], g.node_map,
-                                                                           self.e_cap, edge_norm=self.edge_norm, status=self.status)
-            d.update(edge_src=src, edge_dst=dst, e_count=d_e, rowptr_l=rowptr_l, edge_id=edge_id, edge_norm=enb,
-                     node_norm=self.node_norm)
-            return d
-        src, dst, d_e, rowptr_l = ops.saint_subgraph(g.rowptr, g.col, d["node_idx"], d["count"], g.node_map, self.e_cap,
-                                                     status=self.status)
+        src, dst, d_e, rowptr_l, *ids = ops.saint_subgraph(g.rowptr, g.col, d["node_idx"], d["count"], g.node_map, self.e_cap,
+                                                           edge_norm=self.edge_norm, status=self.status)
         d.update(edge_src=src, edge_dst=dst, e_count=d_e, rowptr_l=rowptr_l)
+        if ids:
+            d.update(edge_id=ids[0], edge_norm=ids[1], node_norm=self.node_norm)
         return d
 
     def check(self):

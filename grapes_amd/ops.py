@@ -1818,15 +1818,10 @@ def wgcn_weights(ws: WeightedStructure, edge_weight, mode: int = WGCN_LOOP_FILL,
     v.val_t = torch.empty(max(ws.e, 1), dtype=_f32, device=dev); v.val_s = torch.empty(max(ws.e, 1), dtype=_f32, device=dev)
     v.lw = torch.empty(max(ws.n, 1), dtype=_f32, device=dev)
     v.dinv = torch.empty(max(ws.n, 1), dtype=_f32, device=dev) if mode != WGCN_UNNORMALIZED else None
-    if mode == WGCN_LOOP_FILL and fill == 1.0:
-        _lib.check(lib().grapes_wgcn_weights(_p(edge_weight), ws.e, _p(ws.inv_t), _p(ws.inv_s), _p(ws.loop_src), _p(prep.rowptr_t),
-                                             _p(prep.rowptr_s), ws.n, _p(prep.d_n), _p(v.val_t), _p(v.val_s), _p(v.lw), _p(v.dinv),
-                                             _stream()), "wgcn_weights")
-        return v
     loop_ptr, loop_idx = (None, None) if mode == WGCN_LOOP_FILL else ws.loops()
-    _lib.check(lib().grapes_wgcn_weights_mode(_p(edge_weight), ws.e, _p(ws.inv_t), _p(ws.inv_s), _p(ws.loop_src), _p(loop_ptr),
-                                              _p(loop_idx), _p(prep.rowptr_t), _p(prep.rowptr_s), ws.n, _p(prep.d_n), mode, float(fill),
-                                              _p(v.val_t), _p(v.val_s), _p(v.lw), _p(v.dinv), _stream()), "wgcn_weights_mode")
+    _lib.check(lib().grapes_wgcn_weights(_p(edge_weight), ws.e, _p(ws.inv_t), _p(ws.inv_s), _p(ws.loop_src), _p(loop_ptr), _p(loop_idx),
+                                         _p(prep.rowptr_t), _p(prep.rowptr_s), ws.n, _p(prep.d_n), mode, float(fill), _p(v.val_t),
+                                         _p(v.val_s), _p(v.lw), _p(v.dinv), _stream()), "wgcn_weights")
     return v
 
 
@@ -1842,13 +1837,9 @@ def wgcn_aggregate_fwd(h, ws: WeightedStructure, vals: WeightedValues, bias=None
         raise ValueError("h and out need one row of the same width per node of the structure's graph, bias one value per column")
     items, n_items, cap = _long_items(prep, by_target=True, forward=True)
     wsp = _ws(lib().grapes_wgcn_aggregate_workspace_bytes(cap, f), h.device) if cap else None
-    head = (_p(h), _p(prep.rowptr_t), _p(prep.csr_src), _p(vals.val_t), _p(vals.dinv), _p(vals.lw), _p(bias), _p(out), ws.n,
-            _p(prep.d_n), f, 1 if relu else 0)
-    tail = (items, n_items, cap, _p(wsp), _p(prep.status), _stream())
-    if vals.mode == WGCN_LOOP_FILL:
-        _lib.check(lib().grapes_wgcn_aggregate_fwd(*head, *tail), "wgcn_aggregate_fwd")
-    else:
-        _lib.check(lib().grapes_wgcn_aggregate_fwd_mode(*head, vals.mode, *tail), "wgcn_aggregate_fwd_mode")
+    _lib.check(lib().grapes_wgcn_aggregate_fwd(_p(h), _p(prep.rowptr_t), _p(prep.csr_src), _p(vals.val_t), _p(vals.dinv), _p(vals.lw),
+                                               _p(bias), _p(out), ws.n, _p(prep.d_n), f, 1 if relu else 0, vals.mode, items, n_items,
+                                               cap, _p(wsp), _p(prep.status), _stream()), "wgcn_aggregate_fwd")
     return out
 
 
@@ -1873,14 +1864,12 @@ def wgcn_aggregate_bwd(dout, ws: WeightedStructure, vals: WeightedValues, h=None
     items_t, n_items_t, cap = _long_items(prep, by_target=True, forward=False)
     items_s, n_items_s, _ = _long_items(prep, by_target=False, forward=False)
     wsp = _ws(lib().grapes_wgcn_aggregate_bwd_workspace_bytes(ws.n, ws.e, cap, f), dev)
-    head = (_p(dout), _p(relu_out), _p(h) if want_dw else None, _p(ws.edge_src), _p(ws.edge_dst), ws.e, _p(prep.d_e), _p(ws.pos_t),
-            _p(ws.loop_src), _p(prep.rowptr_t), _p(prep.csr_src), _p(vals.val_t), _p(prep.rowptr_s), _p(prep.csr_dst), _p(vals.val_s),
-            _p(vals.dinv), _p(vals.lw), _p(dh), _p(dbias), _p(dw), ws.n, _p(prep.d_n), f)
-    tail = (items_t, n_items_t, items_s, n_items_s, cap, _p(wsp), _p(prep.status), _stream())
-    if vals.mode == WGCN_LOOP_FILL:
-        _lib.check(lib().grapes_wgcn_aggregate_bwd(*head, *tail), "wgcn_aggregate_bwd")
-    else:
-        _lib.check(lib().grapes_wgcn_aggregate_bwd_mode(*head, vals.mode, *tail), "wgcn_aggregate_bwd_mode")
+    _lib.check(lib().grapes_wgcn_aggregate_bwd(_p(dout), _p(relu_out), _p(h) if want_dw else None, _p(ws.edge_src), _p(ws.edge_dst),
+                                               ws.e, _p(prep.d_e), _p(ws.pos_t), _p(ws.loop_src), _p(prep.rowptr_t), _p(prep.csr_src),
+                                               _p(vals.val_t), _p(prep.rowptr_s), _p(prep.csr_dst), _p(vals.val_s), _p(vals.dinv),
+                                               _p(vals.lw), _p(dh), _p(dbias), _p(dw), ws.n, _p(prep.d_n), f, vals.mode, items_t,
+                                               n_items_t, items_s, n_items_s, cap, _p(wsp), _p(prep.status), _stream()),
+               "wgcn_aggregate_bwd")
     return dh, dbias, dw
 
 
@@ -2451,42 +2440,60 @@ def saint_draw_nodes(rowptr, col, num_nodes: int, batch_size: int, weights=None,
     return ids, node_idx, count, entries
 
 
-def saint_subgraph(rowptr, col, node_idx, count, node_map, e_cap: int, status=None, out=None):
+def saint_subgraph(rowptr, col, node_idx, count, node_map, e_cap: int, edge_norm=None, ids=False, status=None, out=None):
     """(edge_src, edge_dst int32 [e_cap], e_count int32 [1], rowptr_l int32 [n_cap + 1]) of grapes_saint_subgraph: the subgraph
-    induced by the first *count ids of node_idx, relabelled to local ids, in CSR order.  Overflow of e_cap sets a status bit."""
+    induced by the first *count ids of node_idx, relabelled to local ids, in CSR order.  Overflow of e_cap sets a status bit.
+    ids=True or a table edge_norm (fp32 [nnz]) also tells which stored entry every edge is — two more results: edge_id int64
+    [e_cap], the position in col of edge p, and edge_norm_b fp32 [e_cap] = edge_norm[edge_id[p]] (None without a table).
+    out: the four (or six) tensors to write."""
     _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(node_idx, _i32, "node_idx"); _chk(count, _i32, "count")
-    _chk(node_map, _i32, "node_map"); _chk(status, _i32, "status", True)
-    n_cap, dev = node_idx.numel(), node_idx.device
+    _chk(node_map, _i32, "node_map"); _chk(status, _i32, "status", True); _chk(edge_norm, _f32, "edge_norm", True)
+    if edge_norm is not None and edge_norm.numel() < col.numel():
+        raise ValueError("saint_subgraph: edge_norm holds one value per stored entry")
+    ids = ids or edge_norm is not None
+    n_cap, dev, ec = node_idx.numel(), node_idx.device, max(int(e_cap), 1)
     if out is None:
-        out = (torch.empty(max(int(e_cap), 1), dtype=_i32, device=dev), torch.empty(max(int(e_cap), 1), dtype=_i32, device=dev),
+        out = (torch.empty(ec, dtype=_i32, device=dev), torch.empty(ec, dtype=_i32, device=dev),
                torch.empty(1, dtype=_i32, device=dev), torch.empty(n_cap + 1, dtype=_i32, device=dev))
-    src, dst, d_e, rowptr_l = out
+        if ids:
+            out += (torch.empty(ec, dtype=_i64, device=dev), torch.empty(ec, dtype=_f32, device=dev) if edge_norm is not None else None)
+    src, dst, d_e, rowptr_l, edge_id, edge_norm_b = out if ids else (*out, None, None)
+    if ids:
+        _chk(edge_id, _i64, "edge_id"); _chk(edge_norm_b, _f32, "edge_norm_b", edge_norm is None)
+        if min(src.numel(), dst.numel(), edge_id.numel()) < int(e_cap) or (edge_norm_b is not None and edge_norm_b.numel() < int(e_cap)):
+            raise ValueError("saint_subgraph: the edge buffers hold e_cap values each")
+        if edge_norm is None:
+            edge_norm_b = None
     ws = _ws(lib().grapes_saint_subgraph_workspace_bytes(n_cap), dev)
     _lib.check(lib().grapes_saint_subgraph(_p(rowptr), _p(col), _p(node_idx), _p(count), _p(node_map), n_cap, int(e_cap),
-                                           _p(rowptr_l), _p(src), _p(dst), _p(d_e), _p(ws), _p(status), _stream()),
-               "saint_subgraph")
-    return src, dst, d_e, rowptr_l
+                                           _p(rowptr_l), _p(src), _p(dst), _p(d_e), _p(edge_id), _p(edge_norm), _p(edge_norm_b),
+                                           _p(ws), _p(status), _stream()), "saint_subgraph")
+    return (src, dst, d_e, rowptr_l, edge_id, edge_norm_b) if ids else (src, dst, d_e, rowptr_l)
 
 
-def saint_masked_loss(z, C: int, node_idx, count, train_mask, labels, g=None, loss=None, d_train=None, status=None):
-    """(loss [1], g = d loss / d z [n_cap, C]) of grapes_saint_masked_loss: mean CrossEntropy (labels int64 [N]) or BCEWithLogits
-    (fp32 [N, C]) over the batch rows whose node is a training node; no training row: loss NaN, g = 0."""
+def saint_masked_loss(z, C: int, node_idx, count, train_mask, labels, node_norm=None, g=None, loss=None, d_train=None, status=None):
+    """(loss [1], g = d loss / d z [n_cap, C]) of grapes_saint_masked_loss over the batch rows whose node is a training node: mean
+    CrossEntropy (labels int64 [N]) or BCEWithLogits (fp32 [N, C]); no training row: loss NaN, g = 0.  With node_norm (fp32 [N],
+    read through node_idx) the SUM of node_norm[node] * row loss (CrossEntropy, or the mean over the columns of BCEWithLogits); no
+    training row: loss 0, g = 0."""
     _chk(node_idx, _i32, "node_idx"); _chk(count, _i32, "count", True); _chk(d_train, _i32, "d_train", True)
-    _chk(status, _i32, "status", True)
+    _chk(status, _i32, "status", True); _chk(node_norm, _f32, "node_norm", True)
     if z.dtype != _f32 or not z.is_cuda or z.dim() != 2 or z.stride(1) != 1:
         raise _lib.GrapesHipError("saint_masked_loss: expected a CUDA fp32 matrix with unit column stride")
     if not train_mask.is_cuda or train_mask.dtype not in (torch.bool, torch.uint8):
         raise _lib.GrapesHipError("saint_masked_loss: train_mask must be a cuda bool / uint8 vector")
     multi = labels.dim() == 2
     _chk(labels, _f32 if multi else _i64, "labels")
+    if node_norm is not None and node_norm.numel() != train_mask.numel():
+        raise ValueError("saint_masked_loss: node_norm holds one value per node, like train_mask")
     n_cap = z.shape[0]
     if g is None:
         g = torch.empty((n_cap, int(C)), dtype=_f32, device=z.device)
     if loss is None:
         loss = torch.empty(1, dtype=_f32, device=z.device)
     _lib.check(lib().grapes_saint_masked_loss(_p(z), z.stride(0), int(C), _p(node_idx), _p(count), n_cap, _p(train_mask),
-                                              None if multi else _p(labels), _p(labels) if multi else None, _p(g), g.stride(0),
-                                              _p(loss), _p(d_train), _p(status), _stream()), "saint_masked_loss")
+                                              _p(node_norm), None if multi else _p(labels), _p(labels) if multi else None, _p(g),
+                                              g.stride(0), _p(loss), _p(d_train), _p(status), _stream()), "saint_masked_loss")
     return loss, g
 
 
@@ -2529,60 +2536,6 @@ def saint_norms(rowptr, num_nodes: int, node_count, edge_count, num_samples: int
     _lib.check(lib().grapes_saint_norms(_p(rowptr), N, _p(node_count), _p(edge_count), int(num_samples), _p(edge_norm),
                                         _p(node_norm), _stream()), "saint_norms")
     return edge_norm, node_norm
-
-
-def saint_subgraph_ids(rowptr, col, node_idx, count, node_map, e_cap: int, edge_norm=None, status=None, out=None):
-    """saint_subgraph that also tells which stored entry every edge is: (edge_src, edge_dst int32 [e_cap], e_count int32 [1],
-    rowptr_l int32 [n_cap + 1], edge_id int64 [e_cap], edge_norm_b fp32 [e_cap] or None) of grapes_saint_subgraph_ids.
-    edge_id[p] = the position in col of edge p; with the table edge_norm (fp32 [nnz]) edge_norm_b[p] = edge_norm[edge_id[p]].
-    out: the six tensors to write (the last None without a table)."""
-    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(node_idx, _i32, "node_idx"); _chk(count, _i32, "count")
-    _chk(node_map, _i32, "node_map"); _chk(status, _i32, "status", True); _chk(edge_norm, _f32, "edge_norm", True)
-    if edge_norm is not None and edge_norm.numel() < col.numel():
-        raise ValueError("saint_subgraph_ids: edge_norm holds one value per stored entry")
-    n_cap, dev, ec = node_idx.numel(), node_idx.device, max(int(e_cap), 1)
-    if out is None:
-        out = (torch.empty(ec, dtype=_i32, device=dev), torch.empty(ec, dtype=_i32, device=dev),
-               torch.empty(1, dtype=_i32, device=dev), torch.empty(n_cap + 1, dtype=_i32, device=dev),
-               torch.empty(ec, dtype=_i64, device=dev), torch.empty(ec, dtype=_f32, device=dev) if edge_norm is not None else None)
-    src, dst, d_e, rowptr_l, edge_id, edge_norm_b = out
-    _chk(edge_id, _i64, "edge_id"); _chk(edge_norm_b, _f32, "edge_norm_b", edge_norm is None)
-    if min(src.numel(), dst.numel(), edge_id.numel()) < int(e_cap) or (edge_norm_b is not None and edge_norm_b.numel() < int(e_cap)):
-        raise ValueError("saint_subgraph_ids: the edge buffers hold e_cap values each")
-    if edge_norm is None:
-        edge_norm_b = None
-    ws = _ws(lib().grapes_saint_subgraph_workspace_bytes(n_cap), dev)
-    _lib.check(lib().grapes_saint_subgraph_ids(_p(rowptr), _p(col), _p(node_idx), _p(count), _p(node_map), n_cap, int(e_cap),
-                                               _p(rowptr_l), _p(src), _p(dst), _p(d_e), _p(edge_id), _p(edge_norm), _p(edge_norm_b),
-                                               _p(ws), _p(status), _stream()), "saint_subgraph_ids")
-    return src, dst, d_e, rowptr_l, edge_id, edge_norm_b
-
-
-def saint_masked_loss_weighted(z, C: int, node_idx, count, train_mask, node_norm, labels, g=None, loss=None, d_train=None,
-                               status=None):
-    """(loss [1], g = d loss / d z [n_cap, C]) of grapes_saint_masked_loss_weighted: the SUM over the batch rows whose node is a
-    training node of node_norm[node] * row loss (CrossEntropy for labels int64 [N]; the mean over the columns of BCEWithLogits for
-    fp32 [N, C]); no training row: loss 0, g = 0.  node_norm: fp32 [N], read through node_idx."""
-    _chk(node_idx, _i32, "node_idx"); _chk(count, _i32, "count", True); _chk(d_train, _i32, "d_train", True)
-    _chk(status, _i32, "status", True); _chk(node_norm, _f32, "node_norm")
-    if z.dtype != _f32 or not z.is_cuda or z.dim() != 2 or z.stride(1) != 1:
-        raise _lib.GrapesHipError("saint_masked_loss_weighted: expected a CUDA fp32 matrix with unit column stride")
-    if not train_mask.is_cuda or train_mask.dtype not in (torch.bool, torch.uint8):
-        raise _lib.GrapesHipError("saint_masked_loss_weighted: train_mask must be a cuda bool / uint8 vector")
-    multi = labels.dim() == 2
-    _chk(labels, _f32 if multi else _i64, "labels")
-    if node_norm.numel() != train_mask.numel():
-        raise ValueError("saint_masked_loss_weighted: node_norm holds one value per node, like train_mask")
-    n_cap = z.shape[0]
-    if g is None:
-        g = torch.empty((n_cap, int(C)), dtype=_f32, device=z.device)
-    if loss is None:
-        loss = torch.empty(1, dtype=_f32, device=z.device)
-    _lib.check(lib().grapes_saint_masked_loss_weighted(_p(z), z.stride(0), int(C), _p(node_idx), _p(count), n_cap, _p(train_mask),
-                                                       _p(node_norm), None if multi else _p(labels), _p(labels) if multi else None,
-                                                       _p(g), g.stride(0), _p(loss), _p(d_train), _p(status), _stream()),
-               "saint_masked_loss_weighted")
-    return loss, g
 
 
 def classifier_loss(logits, local_rows, target_ids, labels, out_grad=None):

@@ -56,31 +56,11 @@ class _GatherX(torch.autograd.Function):
 
 
 class _MaskedLoss(torch.autograd.Function):
-    """graphsaint.py:31-34 on the device count of training rows (ops.saint_masked_loss)."""
+    """graphsaint.py:31-34 on the device count of training rows; with node_norm the normalised step's loss (ops.saint_masked_loss)."""
 
     @staticmethod
-    def forward(ctx, z, node_idx, count, train_mask, y, g, loss):
-        loss, g = ops.saint_masked_loss(z.contiguous(), z.shape[1], node_idx, count, train_mask, y, g=g, loss=loss)
-        ctx.g = g
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, gl):
-        return ctx.g * gl, None, None, None, None, None, None
-
-
-def masked_loss(logits, node_idx, count, train_mask, y, g=None, loss=None):
-    """Mean CE (1-D y) / BCEWithLogits (2-D y) over the rows of `logits` whose node (node_idx) is a training node."""
-    return _MaskedLoss.apply(logits, node_idx, count, train_mask, y, g, loss)
-
-
-class _WeightedLoss(torch.autograd.Function):
-    """The normalised step's loss on the device count of training rows (ops.saint_masked_loss_weighted)."""
-
-    @staticmethod
-    def forward(ctx, z, node_idx, count, train_mask, node_norm, y, g, loss):
-        loss, g = ops.saint_masked_loss_weighted(z.contiguous(), z.shape[1], node_idx, count, train_mask, node_norm, y, g=g,
-                                                 loss=loss)
+    def forward(ctx, z, node_idx, count, train_mask, y, node_norm, g, loss):
+        loss, g = ops.saint_masked_loss(z.contiguous(), z.shape[1], node_idx, count, train_mask, y, node_norm=node_norm, g=g, loss=loss)
         ctx.g = g
         return loss.view(())
 
@@ -89,10 +69,10 @@ class _WeightedLoss(torch.autograd.Function):
         return ctx.g * gl, None, None, None, None, None, None, None
 
 
-def weighted_loss(logits, node_idx, count, train_mask, node_norm, y, g=None, loss=None):
-    """Sum over the rows of `logits` whose node (node_idx) is a training node of node_norm[node] * (CE for 1-D y, the mean over the
-    columns of BCEWithLogits for 2-D y)."""
-    return _WeightedLoss.apply(logits, node_idx, count, train_mask, node_norm, y, g, loss)
+def masked_loss(logits, node_idx, count, train_mask, y, node_norm=None, g=None, loss=None):
+    """Over the rows of `logits` whose node (node_idx) is a training node: mean CE (1-D y) / BCEWithLogits (2-D y); with node_norm
+    the sum of node_norm[node] * (CE, or the mean over the columns of BCEWithLogits)."""
+    return _MaskedLoss.apply(logits, node_idx, count, train_mask, y, node_norm, g, loss)
 
 
 def _normalised(loader, sample_coverage, use_normalization) -> bool:
@@ -135,12 +115,8 @@ class EagerSaintTrainer:
         ids = b.node_idx.to(torch.int32)
         self.optimizer.zero_grad()                                                          # graphsaint.py:29
         x = _GatherX.apply(self.x, ids, None, None, False)                                  # batch.x (data.x gathered)
-        if self.normalised:
-            out = self.model(x, b.edge_index, edge_weight=b.edge_norm)
-            loss = weighted_loss(out[0], ids, None, self.train_mask, self.loader.node_norm, self.y)
-        else:
-            out = self.model(x, b.edge_index)                                               # graphsaint.py:31
-            loss = masked_loss(out[0], ids, None, self.train_mask, self.y)                  # graphsaint.py:32-34
+        out = self.model(x, b.edge_index, edge_weight=b.edge_norm if self.normalised else None)        # graphsaint.py:31
+        loss = masked_loss(out[0], ids, None, self.train_mask, self.y, self.loader.node_norm)           # graphsaint.py:32-34
         loss.backward()                                                                     # graphsaint.py:36
         self.optimizer.step()                                                               # graphsaint.py:37
         return loss.detach(), b
@@ -195,38 +171,24 @@ class GraphedSaintTrainer:
         g = L.graph
         d = L.draw(out=self.draw_out)
         node_idx, count = d["node_idx"], d["count"]
+        sub = ops.saint_subgraph(g.rowptr, g.col, node_idx, count, g.node_map, self.e_cap, edge_norm=L.edge_norm, status=L.status,
+                                 out=self.sub_out)
+        src, dst, d_e = sub[:3]
         if self.normalised:
-            return self._body_normalised(node_idx, count)
-        src, dst, d_e, _ = ops.saint_subgraph(g.rowptr, g.col, node_idx, count, g.node_map, self.e_cap, status=L.status,
-                                              out=self.sub_out)
-        if self.n_cap <= ops._SMALL_GRAPH:
+            # The graph is the general PreparedGraph at every n_cap: ops.WeightedStructure looks every entry up by binary search
+            # in the CSRs of that preparation (ascending neighbour ids per row), which the small_batch form is not specified to
+            # produce.
+            prep = ops.WeightedStructure(ops.PreparedGraph(src, dst, self.n_cap, d_n=count, d_e=d_e, status=L.status,
+                                                           src_grouped=True), src, dst)
+        elif self.n_cap <= ops._SMALL_GRAPH:
             prep = ops.PreparedGraph.small_batch([(src, dst, d_e)], self.n_cap, d_n=count, status=L.status)[0]
         else:
             prep = ops.PreparedGraph(src, dst, self.n_cap, d_n=count, d_e=d_e, status=L.status, src_grouped=True)
         for p in self.params:
             p.grad.zero_()
         xb = _GatherX.apply(self.x, node_idx, count, self.xbuf, True)
-        out = self.model(xb, prep)
-        loss = masked_loss(out[0], node_idx, count, self.train_mask, self.y, g=self.gbuf, loss=self.lossbuf)
-        loss.backward()
-        self.fused.step()
-        self.loss_sum.add_(self.lossbuf)
-
-    def _body_normalised(self, node_idx, count):
-        """The rest of the step with GraphSAINT's norms.  The graph is the general PreparedGraph at every n_cap:
-        ops.WeightedStructure looks every entry up by binary search in the CSRs of that preparation (ascending neighbour ids per
-        row), which the small_batch form is not specified to produce."""
-        L = self.loader
-        g = L.graph
-        src, dst, d_e, _, _, enb = ops.saint_subgraph_ids(g.rowptr, g.col, node_idx, count, g.node_map, self.e_cap,
-                                                          edge_norm=L.edge_norm, status=L.status, out=self.sub_out)
-        prep = ops.PreparedGraph(src, dst, self.n_cap, d_n=count, d_e=d_e, status=L.status, src_grouped=True)
-        ws = ops.WeightedStructure(prep, src, dst)
-        for p in self.params:
-            p.grad.zero_()
-        xb = _GatherX.apply(self.x, node_idx, count, self.xbuf, True)
-        out = _weighted_gcn(self.model, xb, ws, enb)
-        loss = weighted_loss(out, node_idx, count, self.train_mask, L.node_norm, self.y, g=self.gbuf, loss=self.lossbuf)
+        out = _weighted_gcn(self.model, xb, prep, sub[5]) if self.normalised else self.model(xb, prep)[0]    # sub[5]: the edges' norms
+        loss = masked_loss(out, node_idx, count, self.train_mask, self.y, L.node_norm, g=self.gbuf, loss=self.lossbuf)
         loss.backward()
         self.fused.step()
         self.loss_sum.add_(self.lossbuf)

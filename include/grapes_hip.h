@@ -55,10 +55,13 @@ extern "C" {
  * grapes_gcn2_loop_counts(_csr), grapes_gcn2_propagate_fwd / _bwd (+ _workspace_bytes), grapes_gcn2_mix_fwd / _bwd; the PNA
  * classifier (modules/gcn.py:120-149) — grapes_pna_aggregate_fwd / _bwd (+ _workspace_bytes each), grapes_pna_add_input_grad; GraphSAINT's node and edge
  * samplers — grapes_saint_edge_weights, grapes_saint_draw_nodes; GraphSAINT's normalisation — grapes_saint_coverage_count,
- * grapes_saint_norms, grapes_saint_subgraph_ids, grapes_saint_masked_loss_weighted; GCNConv with edge weights — grapes_wgcn_structure(_workspace_bytes),
- * grapes_wgcn_weights, grapes_wgcn_aggregate_fwd / _bwd (+ _workspace_bytes each); GCNConv's improved / add_self_loops / normalize —
- * grapes_wgcn_loops(_workspace_bytes), grapes_wgcn_weights_mode, grapes_wgcn_aggregate_fwd_mode / _bwd_mode. */
-#define GRAPES_ABI_VERSION 302
+ * grapes_saint_norms; GCNConv with edge weights and with its improved / add_self_loops / normalize arguments —
+ * grapes_wgcn_structure(_workspace_bytes), grapes_wgcn_loops(_workspace_bytes), grapes_wgcn_weights, grapes_wgcn_aggregate_fwd / _bwd
+ * (+ _workspace_bytes each);
+ * 303: five signatures grew the arguments of a twin that 302 had added beside them, and the twins left: grapes_wgcn_weights (loop_ptr,
+ * loop_idx, mode, fill), grapes_wgcn_aggregate_fwd / _bwd (mode) <- their _mode forms; grapes_saint_subgraph (edge_id, edge_norm,
+ * edge_norm_b) <- its _ids form; grapes_saint_masked_loss (node_norm) <- its _weighted form. */
+#define GRAPES_ABI_VERSION 303
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
 #define GRAPES_EALIGN (-2)   /* pointer not aligned as required */
@@ -764,43 +767,10 @@ int grapes_wgcn_structure(const int32_t* edge_src, const int32_t* edge_dst, int3
                           const int32_t* d_n, const int32_t* rowptr_t, const int32_t* csr_src, const int32_t* rowptr_s,
                           const int32_t* csr_dst, int32_t* pos_t, int32_t* pos_s, int32_t* inv_t, int32_t* inv_s,
                           int32_t* loop_src, void* workspace, int32_t* status, grapes_stream_t stream);
-/* The weight pass, per call (replaces gcn_norm's scatter of edge_weight into deg, its pow(-0.5) and its masked_fill): val_t / val_s
- * [e] = the weights in both CSR orders, lw [n], dinv [n] with deg summed in by-target slot order.  One launch. */
-int grapes_wgcn_weights(const float* edge_weight, int32_t e, const int32_t* inv_t, const int32_t* inv_s, const int32_t* loop_src,
-                        const int32_t* rowptr_t, const int32_t* rowptr_s, int32_t n, const int32_t* d_n, float* val_t, float* val_s,
-                        float* lw, float* dinv, grapes_stream_t stream);
-/* GCNConv.propagate with the normalised weights (+ bias, + ReLU when relu != 0) in ONE pass over the by-target CSR: a group of
- * lanes per row, each lane reads one column index and one val_t per batch, val * dinv[col] is broadcast with the index.
- * long_items / d_n_items / item_cap / workspace as grapes_gcn_aggregate_fwd (NULL: every row by one group): rows longer than
- * GRAPES_LONG_ROW are cut into items whose partial sums are merged in chunk order.  workspace:
- * grapes_wgcn_aggregate_workspace_bytes(item_cap, f), 16-byte aligned.  bias may be NULL; out must not alias h. */
-size_t grapes_wgcn_aggregate_workspace_bytes(int32_t item_cap, int32_t f);
-int grapes_wgcn_aggregate_fwd(const float* h, const int32_t* rowptr_t, const int32_t* csr_src, const float* val_t, const float* dinv,
-                              const float* lw, const float* bias, float* out, int32_t n, const int32_t* d_n, int32_t f,
-                              int32_t relu, const int32_t* long_items, const int32_t* d_n_items, int32_t item_cap, void* workspace,
-                              int32_t* status, grapes_stream_t stream);
-/* Backward of the above and of gcn_norm (autograd through GCNConv.forward with edge weights).  With G = dout gated by
- * relu_out > 0 (relu_out NULL: G = dout), s = dinv, p_e = G[c] . H[r]:
- *   dh[r] = s_r sum_{e: r -> c} w_e s_c G[c] + s_r^2 lw_r G[r]                       (by-source CSR)
- *   dbias = column sums of G (the gated column-sum pass of grapes_gcn_aggregate_bwd: partials added in a fixed order)
- *   t_i = sum_{e -> i} w_e s_r p_e + sum_{e: i -> c} w_e s_c p_e + 2 s_i lw_i (G[i] . H[i]),   q_i = -1/2 s_i^3 t_i (0 where s_i = 0)
- *   dw[i] = s_r s_c p_e + q_c for a stored entry; s_i^2 (G[i] . H[i]) + q_i for the loop that set lw[i]; 0 for an overridden loop
- *           and for a dropped entry                                                    (input order, through pos_t and loop_src)
- * dh, dbias and dw may each be NULL (not all three); h, edge_src / edge_dst / pos_t / loop_src, rowptr_t / csr_src / val_t and
- * items_t are needed for dw only.  items_t / items_s: the two halves of gcn_prepare's item table with their counts (NULL: no row
- * splitting).  workspace: grapes_wgcn_aggregate_bwd_workspace_bytes(n, e, item_cap, f), 16-byte aligned. */
-size_t grapes_wgcn_aggregate_bwd_workspace_bytes(int32_t n, int32_t e, int32_t item_cap, int32_t f);
-int grapes_wgcn_aggregate_bwd(const float* dout, const float* relu_out, const float* h, const int32_t* edge_src,
-                              const int32_t* edge_dst, int32_t e, const int32_t* d_e, const int32_t* pos_t, const int32_t* loop_src,
-                              const int32_t* rowptr_t, const int32_t* csr_src, const float* val_t, const int32_t* rowptr_s,
-                              const int32_t* csr_dst, const float* val_s, const float* dinv, const float* lw, float* dh,
-                              float* dbias, float* dw, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_t,
-                              const int32_t* d_n_items_t, const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap,
-                              void* workspace, int32_t* status, grapes_stream_t stream);
 /* GCNConv's other constructor arguments (PyG 2.5 GCNConv(improved, add_self_loops, normalize), as recalled): the CSRs never hold a
  * loop, so every mode is a rule for lw, and one of them drops the normalisation.
  *   GRAPES_WGCN_LOOP_FILL     add_self_loops=True: lw[i] = the weight of the last stored (i, i), or fill (1; improved=True: 2).
- *                             fill = 1 is the rule of the entry points above.
+ *                             fill = 1 is the rule written out above.
  *   GRAPES_WGCN_LOOP_SUM      add_self_loops=False, normalize=True: nothing is added and a stored loop is an ordinary entry —
  *                             lw[i] = the weights of ALL stored (i, i), added in input order (0 without one), deg, dinv and the
  *                             formulas as above; a node without an incoming entry has dinv = 0 and outputs the bias.  dw: every
@@ -818,27 +788,46 @@ int grapes_wgcn_aggregate_bwd(const float* dout, const float* relu_out, const fl
 size_t grapes_wgcn_loops_workspace_bytes(int32_t n, int32_t e);
 int grapes_wgcn_loops(const int32_t* edge_src, const int32_t* edge_dst, int32_t e, const int32_t* d_e, int32_t n, const int32_t* d_n,
                       int32_t* loop_ptr, int32_t* loop_idx, void* workspace, grapes_stream_t stream);
-/* grapes_wgcn_weights with a mode.  edge_weight NULL: every weight is 1 (an unweighted call; no ones vector is formed).  loop_src is
- * read by LOOP_FILL only, loop_ptr / loop_idx by the other two; UNNORMALIZED writes no dinv. */
-int grapes_wgcn_weights_mode(const float* edge_weight, int32_t e, const int32_t* inv_t, const int32_t* inv_s, const int32_t* loop_src,
-                             const int32_t* loop_ptr, const int32_t* loop_idx, const int32_t* rowptr_t, const int32_t* rowptr_s,
-                             int32_t n, const int32_t* d_n, int32_t mode, float fill, float* val_t, float* val_s, float* lw,
-                             float* dinv, grapes_stream_t stream);
-/* grapes_wgcn_aggregate_fwd / _bwd with a mode (the workspaces are theirs).  LOOP_FILL and LOOP_SUM run the same kernels over
- * their own lw and dinv and differ in dw's loop rule; UNNORMALIZED runs specialisations that never load dinv: one memory request
- * per gathered entry less, no by-source / by-target sums and no q in the backward. */
-int grapes_wgcn_aggregate_fwd_mode(const float* h, const int32_t* rowptr_t, const int32_t* csr_src, const float* val_t,
-                                   const float* dinv, const float* lw, const float* bias, float* out, int32_t n, const int32_t* d_n,
-                                   int32_t f, int32_t relu, int32_t mode, const int32_t* long_items, const int32_t* d_n_items,
-                                   int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
-int grapes_wgcn_aggregate_bwd_mode(const float* dout, const float* relu_out, const float* h, const int32_t* edge_src,
-                                   const int32_t* edge_dst, int32_t e, const int32_t* d_e, const int32_t* pos_t,
-                                   const int32_t* loop_src, const int32_t* rowptr_t, const int32_t* csr_src, const float* val_t,
-                                   const int32_t* rowptr_s, const int32_t* csr_dst, const float* val_s, const float* dinv,
-                                   const float* lw, float* dh, float* dbias, float* dw, int32_t n, const int32_t* d_n, int32_t f,
-                                   int32_t mode, const int32_t* items_t, const int32_t* d_n_items_t, const int32_t* items_s,
-                                   const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status,
-                                   grapes_stream_t stream);
+/* The weight pass, per call (replaces gcn_norm's scatter of edge_weight into deg, its pow(-0.5) and its masked_fill): val_t / val_s
+ * [e] = the weights in both CSR orders, lw [n] by the rule of `mode` (fill is read by LOOP_FILL alone), dinv [n] with deg summed in
+ * by-target slot order.  edge_weight NULL: every weight is 1 (an unweighted call; no ones vector is formed) — in every mode,
+ * LOOP_FILL with fill 1 included, which up to ABI 302 refused it.  loop_src is read by LOOP_FILL only, loop_ptr / loop_idx by the
+ * other two (NULL where not read); UNNORMALIZED writes no dinv (NULL).  One launch. */
+int grapes_wgcn_weights(const float* edge_weight, int32_t e, const int32_t* inv_t, const int32_t* inv_s, const int32_t* loop_src,
+                        const int32_t* loop_ptr, const int32_t* loop_idx, const int32_t* rowptr_t, const int32_t* rowptr_s, int32_t n,
+                        const int32_t* d_n, int32_t mode, float fill, float* val_t, float* val_s, float* lw, float* dinv,
+                        grapes_stream_t stream);
+/* GCNConv.propagate with the weights of that pass (+ bias, + ReLU when relu != 0) in ONE pass over the by-target CSR: a group of
+ * lanes per row, each lane reads one column index and one val_t per batch, val * dinv[col] is broadcast with the index.  mode: the
+ * one the weights were made by — LOOP_FILL and LOOP_SUM run the same kernels over their own lw and dinv; UNNORMALIZED runs
+ * specialisations that never load dinv (one memory request per gathered entry less).
+ * long_items / d_n_items / item_cap / workspace as grapes_gcn_aggregate_fwd (NULL: every row by one group): rows longer than
+ * GRAPES_LONG_ROW are cut into items whose partial sums are merged in chunk order.  workspace:
+ * grapes_wgcn_aggregate_workspace_bytes(item_cap, f), 16-byte aligned.  bias may be NULL; out must not alias h. */
+size_t grapes_wgcn_aggregate_workspace_bytes(int32_t item_cap, int32_t f);
+int grapes_wgcn_aggregate_fwd(const float* h, const int32_t* rowptr_t, const int32_t* csr_src, const float* val_t, const float* dinv,
+                              const float* lw, const float* bias, float* out, int32_t n, const int32_t* d_n, int32_t f,
+                              int32_t relu, int32_t mode, const int32_t* long_items, const int32_t* d_n_items, int32_t item_cap,
+                              void* workspace, int32_t* status, grapes_stream_t stream);
+/* Backward of the above and of gcn_norm (autograd through GCNConv.forward with edge weights).  With G = dout gated by
+ * relu_out > 0 (relu_out NULL: G = dout), s = dinv, p_e = G[c] . H[r], for LOOP_FILL (the modes above say where the others differ:
+ * dw's loop rule; UNNORMALIZED forms no by-source / by-target sums and no q):
+ *   dh[r] = s_r sum_{e: r -> c} w_e s_c G[c] + s_r^2 lw_r G[r]                       (by-source CSR)
+ *   dbias = column sums of G (the gated column-sum pass of grapes_gcn_aggregate_bwd: partials added in a fixed order)
+ *   t_i = sum_{e -> i} w_e s_r p_e + sum_{e: i -> c} w_e s_c p_e + 2 s_i lw_i (G[i] . H[i]),   q_i = -1/2 s_i^3 t_i (0 where s_i = 0)
+ *   dw[i] = s_r s_c p_e + q_c for a stored entry; s_i^2 (G[i] . H[i]) + q_i for the loop that set lw[i]; 0 for an overridden loop
+ *           and for a dropped entry                                                    (input order, through pos_t and loop_src)
+ * dh, dbias and dw may each be NULL (not all three); h, edge_src / edge_dst / pos_t / loop_src, rowptr_t / csr_src / val_t and
+ * items_t are needed for dw only.  items_t / items_s: the two halves of gcn_prepare's item table with their counts (NULL: no row
+ * splitting).  workspace: grapes_wgcn_aggregate_bwd_workspace_bytes(n, e, item_cap, f), 16-byte aligned. */
+size_t grapes_wgcn_aggregate_bwd_workspace_bytes(int32_t n, int32_t e, int32_t item_cap, int32_t f);
+int grapes_wgcn_aggregate_bwd(const float* dout, const float* relu_out, const float* h, const int32_t* edge_src,
+                              const int32_t* edge_dst, int32_t e, const int32_t* d_e, const int32_t* pos_t, const int32_t* loop_src,
+                              const int32_t* rowptr_t, const int32_t* csr_src, const float* val_t, const int32_t* rowptr_s,
+                              const int32_t* csr_dst, const float* val_s, const float* dinv, const float* lw, float* dh,
+                              float* dbias, float* dw, int32_t n, const int32_t* d_n, int32_t f, int32_t mode,
+                              const int32_t* items_t, const int32_t* d_n_items_t, const int32_t* items_s,
+                              const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
 
 /* ------------------------------------------------------------------ PNAConv (csrc/pna_kernels.hip)
  * modules/gcn.py:120-149: PNA stacks PNAConv(in_channels, out_channels, aggregators, scalers, deg) layers, every other argument
@@ -1352,16 +1341,25 @@ int grapes_saint_walk_nodes(const int64_t* rowptr, const int32_t* col, int32_t n
  * node_map as written by grapes_saint_walk_nodes.  Edges (edge_src[k], edge_dst[k]) = (local row, local column) in CSR order —
  * local row ascending, then the graph's column order (ascending for a sorted CSR); stored self-loops stay.  rowptr_l
  * int32[n_cap + 1]: the local row pointers (rows at or past the count are empty).  *d_e = min(edges, e_cap); more than e_cap
- * edges ORs GRAPES_STATUS_EDGE_OVERFLOW into status and only the first e_cap are written.  Three launches (per-row counts,
+ * edges ORs GRAPES_STATUS_EDGE_OVERFLOW into status and only the first e_cap are written.  Every edge's origin, when wanted (all
+ * three NULL: not formed): edge_id[p] = j (int64[e_cap], may be NULL on its own), the position in col of the entry that became edge
+ * p, and, with GraphSAINT's table edge_norm (fp32[nnz], grapes_saint_norms), edge_norm_b[p] = edge_norm[j] (fp32[e_cap]; both NULL or
+ * both given) — written at the same slot p as edge_src / edge_dst, nothing at or past e_cap.  Three launches (per-row counts,
  * one-workgroup scan, per-row writes).  workspace: grapes_saint_subgraph_workspace_bytes(n_cap), 4-byte aligned. */
 size_t grapes_saint_subgraph_workspace_bytes(int32_t n_cap);
-int grapes_saint_subgraph(const int64_t* rowptr, const int32_t* col, const int32_t* node_idx, const int32_t* d_count, const int32_t* node_map, int32_t n_cap, int32_t e_cap, int32_t* rowptr_l, int32_t* edge_src, int32_t* edge_dst, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream);
+int grapes_saint_subgraph(const int64_t* rowptr, const int32_t* col, const int32_t* node_idx, const int32_t* d_count, const int32_t* node_map, int32_t n_cap, int32_t e_cap, int32_t* rowptr_l, int32_t* edge_src, int32_t* edge_dst, int32_t* d_e, int64_t* edge_id, const float* edge_norm, float* edge_norm_b, void* workspace, int32_t* status, grapes_stream_t stream);
 /* graphsaint.py:31-34 loss_fn(out[0][train_idx], y[train_idx]), train_idx = batch.train_mask.nonzero(): over rows i < *d_count of
  * the batch logits z [n_cap, ldz] (row i = node node_idx[i]) with train_mask[node_idx[i]] != 0 (uint8 / bool [N]), T of them
- * (counted on the device; *d_train = T when non-NULL).  Mean CrossEntropy (labels int64[N]) or mean BCEWithLogits (labels_f
- * fp32[N, C]).  g [n_cap, ldg] = d loss / d z (0 on other rows).  T = 0: *loss_out = NaN and g = 0 (torch's mean over an empty
- * selection).  ONE workgroup, fixed summation order. */
-int grapes_saint_masked_loss(const float* z, int64_t ldz, int32_t C, const int32_t* node_idx, const int32_t* d_count, int32_t n_cap, const uint8_t* train_mask, const int64_t* labels, const float* labels_f, float* g, int64_t ldg, float* loss_out, int32_t* d_train, int32_t* status, grapes_stream_t stream);
+ * (counted on the device; *d_train = T when non-NULL).  rowloss is CrossEntropy (labels int64[N]) or the mean over the C columns
+ * of the BCEWithLogits elements (labels_f fp32[N, C]); exactly one of the two is given.
+ *   node_norm NULL: the mean — *loss_out = sum of rowloss / T, g [n_cap, ldg] = d loss / d z (0 on other rows).  T = 0:
+ *     *loss_out = NaN and g = 0 (torch's mean over an empty selection).
+ *   node_norm (fp32[N], read through node_idx like train_mask; grapes_saint_norms): the normalised step's loss — *loss_out = sum
+ *     over the training rows i of node_norm[node_idx[i]] * rowloss_i, a sum, not divided by T; g row i = w_i (softmax - onehot) or
+ *     w_i (sigmoid(z) - y) / C.  T = 0: *loss_out = 0 and g = 0.
+ * A label outside [0, C) ORs GRAPES_STATUS_BAD_INDEX into status and the row counts nothing.  ONE workgroup, fixed summation
+ * order, no float atomics. */
+int grapes_saint_masked_loss(const float* z, int64_t ldz, int32_t C, const int32_t* node_idx, const int32_t* d_count, int32_t n_cap, const uint8_t* train_mask, const float* node_norm, const int64_t* labels, const float* labels_f, float* g, int64_t ldg, float* loss_out, int32_t* d_train, int32_t* status, grapes_stream_t stream);
 /* GraphSAINT's other two samplers (the reference imports GraphSAINTNodeSampler at graphsaint.py:8; PyG 2.5 loader/graph_saint.py).
  * The one-time weight table of GraphSAINTEdgeSampler: the weight of the stored entry (r, c) is colcount[r] + rowcount[c] (PyG:
  * prob = 1 / deg_in[row] + 1 / deg_out[col] with deg_in = 1 / colcount, deg_out = 1 / rowcount), an integer below 2^32.
@@ -1394,18 +1392,6 @@ int grapes_saint_coverage_count(const int64_t* rowptr, const int32_t* col, int32
  *   node_norm[v] = (fp32(num_samples) / c) / fp32(N), c = fp32(node_count[v]), or 0.1 where the count is 0.
  * One wavefront per CSR row, rows shorter and longer than a wavefront alike.  One launch. */
 int grapes_saint_norms(const int64_t* rowptr, int32_t num_nodes, const uint32_t* node_count, const uint32_t* edge_count, int64_t num_samples, float* edge_norm, float* node_norm, grapes_stream_t stream);
-/* grapes_saint_subgraph with every edge's origin: edge_id[p] = j (int64[e_cap], NULL: not wanted), the position in col of the entry
- * that became edge p, and, when the table edge_norm (fp32[nnz]) is given, edge_norm_b[p] = edge_norm[j] (fp32[e_cap]; both NULL or
- * both given) — written at the same slot p as edge_src / edge_dst, nothing at or past e_cap.  Everything else (outputs, order,
- * overflow bit, workspace, three launches) as grapes_saint_subgraph. */
-int grapes_saint_subgraph_ids(const int64_t* rowptr, const int32_t* col, const int32_t* node_idx, const int32_t* d_count, const int32_t* node_map, int32_t n_cap, int32_t e_cap, int32_t* rowptr_l, int32_t* edge_src, int32_t* edge_dst, int32_t* d_e, int64_t* edge_id, const float* edge_norm, float* edge_norm_b, void* workspace, int32_t* status, grapes_stream_t stream);
-/* The normalised step's loss: grapes_saint_masked_loss with a per-node weight table node_norm (fp32[N]), read through node_idx like
- * train_mask.  *loss_out = sum over the training rows i of node_norm[node_idx[i]] * rowloss_i — a sum, not divided by T; rowloss
- * is CrossEntropy (labels int64[N]) or the mean over the C columns of the BCEWithLogits elements (labels_f fp32[N, C]).
- * g row i = w_i (softmax - onehot) or w_i (sigmoid(z) - y) / C; 0 on other rows.  T = 0: *loss_out = 0 and g = 0.  A label outside
- * [0, C) ORs GRAPES_STATUS_BAD_INDEX into status and the row counts nothing.  ONE workgroup, fixed summation order, no float
- * atomics. */
-int grapes_saint_masked_loss_weighted(const float* z, int64_t ldz, int32_t C, const int32_t* node_idx, const int32_t* d_count, int32_t n_cap, const uint8_t* train_mask, const float* node_norm, const int64_t* labels, const float* labels_f, float* g, int64_t ldg, float* loss_out, int32_t* d_train, int32_t* status, grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:

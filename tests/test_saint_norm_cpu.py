@@ -124,7 +124,7 @@ def test_ops_wrappers_refuse_cpu_tensors():
     with pytest.raises(_lib.GrapesHipError):
         ops.saint_norms(rowptr, 6, torch.zeros(6, dtype=torch.int32), torch.zeros(7, dtype=torch.int32), 3)
     with pytest.raises(_lib.GrapesHipError):
-        ops.saint_subgraph_ids(rowptr, col, idx, cnt, nmap, 8)
+        ops.saint_subgraph(rowptr, col, idx, cnt, nmap, 8, ids=True)
     with pytest.raises(_lib.GrapesHipError):
-        ops.saint_masked_loss_weighted(torch.zeros(4, 3), 3, idx, cnt, torch.zeros(6, dtype=torch.bool), torch.ones(6),
-                                       torch.zeros(6, dtype=torch.int64))
+        ops.saint_masked_loss(torch.zeros(4, 3), 3, idx, cnt, torch.zeros(6, dtype=torch.bool), torch.zeros(6, dtype=torch.int64),
+                              node_norm=torch.ones(6))

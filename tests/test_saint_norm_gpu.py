@@ -187,7 +187,7 @@ def test_subgraph_ids():
     table = torch.from_numpy(rng.random(len(indices), dtype=np.float32)).cuda()
     e_cap = ld.e_cap
     a = ops.saint_subgraph(g.rowptr, g.col, d["node_idx"], d["count"], g.node_map, e_cap, status=ld.status)
-    b = ops.saint_subgraph_ids(g.rowptr, g.col, d["node_idx"], d["count"], g.node_map, e_cap, edge_norm=table, status=ld.status)
+    b = ops.saint_subgraph(g.rowptr, g.col, d["node_idx"], d["count"], g.node_map, e_cap, edge_norm=table, status=ld.status)
     ld.check()
     e = int(a[2].item())
     assert e > 40 and int(b[2].item()) == e and torch.equal(a[3], b[3])
@@ -198,7 +198,7 @@ def test_subgraph_ids():
     assert np.array_equal(indices[eid], ns[dst]) and np.array_equal(NO.entry_rows(indptr)[eid], ns[src])
     assert len(np.unique(eid)) == e                                       # duplicate entries keep their own ids
     assert torch.equal(b[5][:e], table[b[4][:e]])
-    c = ops.saint_subgraph_ids(g.rowptr, g.col, d["node_idx"], d["count"], g.node_map, e_cap, status=ld.status)       # no table
+    c = ops.saint_subgraph(g.rowptr, g.col, d["node_idx"], d["count"], g.node_map, e_cap, ids=True, status=ld.status)   # no table
     assert c[5] is None and torch.equal(c[4][:e], b[4][:e])
     # e_cap below the edge count: the overflow bit, and nothing at or past e_cap (a guard region behind every buffer)
     small, guard = e - 37, 64
@@ -207,7 +207,7 @@ def test_subgraph_ids():
             torch.zeros(ld.n_cap + 1, **i32), torch.full((small + guard,), -7, dtype=torch.int64, device="cuda"),
             torch.full((small + guard,), -7.0, dtype=torch.float32, device="cuda"))
     status = torch.zeros(1, **i32)
-    ops.saint_subgraph_ids(g.rowptr, g.col, d["node_idx"], d["count"], g.node_map, small, edge_norm=table, status=status, out=bufs)
+    ops.saint_subgraph(g.rowptr, g.col, d["node_idx"], d["count"], g.node_map, small, edge_norm=table, status=status, out=bufs)
     assert int(status.item()) & 1 and int(bufs[2].item()) == small
     for k in (0, 1, 4, 5):
         assert torch.all(bufs[k][small:] == -7), k
@@ -284,7 +284,7 @@ def test_weighted_loss_against_fp64(C, multi):
     got_l, ref_l, mag_l, base_l = [], [], [], []
     for k, w in enumerate(ws):
         d_train, status = torch.zeros(1, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
-        loss, g = ops.saint_masked_loss_weighted(zd, C, idx, cnt, md, torch.from_numpy(w).cuda(), yd, d_train=d_train, status=status)
+        loss, g = ops.saint_masked_loss(zd, C, idx, cnt, md, yd, node_norm=torch.from_numpy(w).cuda(), d_train=d_train, status=status)
         wl = w[pad]
         rl, rg, ml, mg = NO.weighted_loss(z, yl, wl, train)
         bl, bg, _, _ = NO.weighted_loss(z, yl, wl, train, dtype=np.float32)
@@ -312,7 +312,7 @@ def test_weighted_loss_with_uniform_weights_is_the_masked_loss(multi):
     train = np.concatenate([mask[pad[:n]], np.zeros(n_cap - n, bool)])
     T = int(train.sum())
     w = np.full(N, F32(1) / F32(T), np.float32)
-    lw, gw = ops.saint_masked_loss_weighted(zd, C, idx, cnt, md, torch.from_numpy(w).cuda(), yd)
+    lw, gw = ops.saint_masked_loss(zd, C, idx, cnt, md, yd, node_norm=torch.from_numpy(w).cuda())
     lm, gm = ops.saint_masked_loss(zd, C, idx, cnt, md, yd)
     yl = np.concatenate([y[pad[:n]], y[pad[n:]]])
     rl, rg, ml, mg = NO.weighted_loss(z, yl, w[pad], train)
@@ -327,9 +327,9 @@ def test_weighted_loss_without_a_training_row_is_zero(multi):
     _cuda()
     from grapes_amd import ops
     N, n_cap, n, pad, z, y, mask, ws = _loss_case(7, multi, 6, T0=True)
-    loss, g = ops.saint_masked_loss_weighted(torch.from_numpy(z).cuda(), 7, torch.from_numpy(pad).cuda(),
-                                             torch.tensor([n], dtype=torch.int32, device="cuda"), torch.from_numpy(mask).cuda(),
-                                             torch.from_numpy(ws[0]).cuda(), torch.from_numpy(y).cuda())
+    loss, g = ops.saint_masked_loss(torch.from_numpy(z).cuda(), 7, torch.from_numpy(pad).cuda(),
+                                    torch.tensor([n], dtype=torch.int32, device="cuda"), torch.from_numpy(mask).cuda(),
+                                    torch.from_numpy(y).cuda(), node_norm=torch.from_numpy(ws[0]).cuda())
     assert float(loss.item()) == 0.0 and not g.any()
 
 
@@ -340,10 +340,28 @@ def test_weighted_loss_flags_a_label_out_of_range():
     mask[pad[3]] = True
     y = y.copy(); y[pad[3]] = 7
     status = torch.zeros(1, dtype=torch.int32, device="cuda")
-    loss, g = ops.saint_masked_loss_weighted(torch.from_numpy(z).cuda(), 7, torch.from_numpy(pad).cuda(),
-                                             torch.tensor([n], dtype=torch.int32, device="cuda"), torch.from_numpy(mask).cuda(),
-                                             torch.from_numpy(ws[0]).cuda(), torch.from_numpy(y).cuda(), status=status)
+    loss, g = ops.saint_masked_loss(torch.from_numpy(z).cuda(), 7, torch.from_numpy(pad).cuda(),
+                                    torch.tensor([n], dtype=torch.int32, device="cuda"), torch.from_numpy(mask).cuda(),
+                                    torch.from_numpy(y).cuda(), node_norm=torch.from_numpy(ws[0]).cuda(), status=status)
     assert int(status.item()) & 4 and not g[3].any() and np.isfinite(float(loss.item()))
+
+
+def test_c_entry_points_refuse_half_given_pairs():
+    """Refused on the host before any launch: a table without edge_norm_b (grapes_saint_subgraph), both label pointers
+    (grapes_saint_masked_loss)."""
+    _cuda()
+    from grapes_amd import _lib
+    L = _lib.load()
+    i32 = torch.zeros(8, dtype=torch.int32, device="cuda")
+    i64, f32, u8 = i32.long(), i32.float(), i32.to(torch.uint8)
+    p = lambda t: t.data_ptr()
+    EINVAL = -1
+    assert L.grapes_saint_subgraph(p(i64), p(i32), p(i32), p(i32), p(i32), 4, 4, p(i32), p(i32), p(i32), p(i32), p(i64), p(f32), None,
+                                   p(i32), p(i32), None) == EINVAL
+    assert L.grapes_saint_masked_loss(p(f32), 2, 2, p(i32), p(i32), 4, p(u8), None, p(i64), p(f32), p(f32), 2, p(f32), p(i32), p(i32),
+                                      None) == EINVAL
+    torch.cuda.synchronize()
+    assert not i32.any() and not f32.any()                                # nothing was launched
 
 
 # ------------------------------------------------------------------------------------------------------------ trainers
@@ -418,8 +436,9 @@ def test_captured_normalised_steps_match_eager(kind):
 
 @pytest.mark.parametrize("engine", ["eager", "graph"])
 def test_default_trainer_never_enters_the_normalised_path(engine, monkeypatch):
-    """A trainer built with the defaults launches what it launched before: none of the new entry points is called over three
-    steps, the old subgraph and loss are, and the Philox offset is three draws' worth.  (The driver's output with the defaults is
+    """A trainer built with the defaults launches what it launched before: none of the normalisation's entry points is called over
+    three steps, the subgraph and the loss are — each time without a table, without ids and without node_norm — and the Philox
+    offset is three draws' worth.  (The driver's output with the defaults is
     pinned to the parent's by tests/test_saint_samplers_gpu.py::test_cli_rw_output_is_the_parents and by test_cli below.)"""
     _cuda()
     from grapes_amd import ops
@@ -430,11 +449,21 @@ def test_default_trainer_never_enters_the_normalised_path(engine, monkeypatch):
         def f(*a, **k):
             raise AssertionError(f"{name} was called by a default trainer")
         return f
-    for name in ("saint_coverage_count", "saint_norms", "saint_subgraph_ids", "saint_masked_loss_weighted", "WeightedStructure"):
+    for name in ("saint_coverage_count", "saint_norms", "WeightedStructure"):
         monkeypatch.setattr(ops, name, refuse(name))
     old_sub, old_loss = ops.saint_subgraph, ops.saint_masked_loss
-    monkeypatch.setattr(ops, "saint_subgraph", lambda *a, **k: (calls.__setitem__("subgraph", calls["subgraph"] + 1), old_sub(*a, **k))[1])
-    monkeypatch.setattr(ops, "saint_masked_loss", lambda *a, **k: (calls.__setitem__("loss", calls["loss"] + 1), old_loss(*a, **k))[1])
+
+    def plain_sub(*a, **k):                                   # (rowptr, col, node_idx, count, node_map, e_cap) and keywords only
+        assert len(a) <= 6 and k.get("edge_norm") is None and not k.get("ids", False), (len(a), sorted(k))
+        calls["subgraph"] += 1
+        return old_sub(*a, **k)
+
+    def plain_loss(*a, **k):                                  # (z, C, node_idx, count, train_mask, labels) and keywords only
+        assert len(a) <= 6 and k.get("node_norm") is None, (len(a), sorted(k))
+        calls["loss"] += 1
+        return old_loss(*a, **k)
+    monkeypatch.setattr(ops, "saint_subgraph", plain_sub)
+    monkeypatch.setattr(ops, "saint_masked_loss", plain_loss)
     indptr, indices, g, x, y, tm, model = _setup(n=3000, seed=2)
     tr = make_trainer(engine, g, x, y, tm, model, 0.01, batch_size=128, walk_length=2, seed=77)
     assert tr.normalised is False and tr.loader.edge_norm is None and len(tr.sub_out if engine == "graph" else (0,) * 4) == 4
