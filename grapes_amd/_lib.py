@@ -89,6 +89,11 @@ SIGNATURES = {
     "grapes_gat_aggregate_fwd": (I32, [P, P, P, P, P, P, P, P, I32, P, I32, I32, P, P, I32, P, P, P]),
     "grapes_gat_aggregate_bwd_workspace_bytes": (SZ, [I32, I32, I32]),
     "grapes_gat_aggregate_bwd": (I32, [P] * 18 + [I32, P, I32, P, P, P, P, I32, P, P, P]),
+    # GATv2Conv aggregation (PyG GATv2Conv: multi-head dynamic attention)
+    "grapes_gatv2_aggregate_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_gatv2_aggregate_fwd": (I32, [P] * 9 + [I32, P, I32, I32, I32, F32, I32, P, P, I32, P, P, P]),
+    "grapes_gatv2_aggregate_bwd_workspace_bytes": (SZ, [I32, I32, I32, I32]),
+    "grapes_gatv2_aggregate_bwd": (I32, [P, P, P, P, I32] + [P] * 12 + [I32, P, I32, I32, I32, F32, P, P, P, P, I32, P, P, P]),
     # GCN2Conv propagation and blend (modules/gcn.py:76-117)
     "grapes_gcn2_loop_counts": (I32, [P, P, I32, P, P, I32, P, P, P]),
     "grapes_gcn2_loop_counts_csr": (I32, [P, P, I32, P, P]),

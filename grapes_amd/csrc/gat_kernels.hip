@@ -37,21 +37,6 @@ __device__ __forceinline__ float gat_dot(const float (&a)[NS][VEC], const float 
     return d;
 }
 
-// entry t of a walk over [beg - with_self, end): the row itself for t < beg (the implied unit self-loop), else csr[t].
-// An index outside [0, n) raises GRAPES_STATUS_BAD_INDEX and the entry is dropped.
-__device__ __forceinline__ bool gat_entry(const int32_t* __restrict__ csr, int t, int beg, int end, int row, int n, int& idx,
-                                          int32_t* status) {
-    idx = row;
-    if (t >= end) return false;
-    if (t < beg) return true;
-    const int c = batch_entry(csr, t, end, n, status);
-    if (c < 0) return false;
-    idx = c;
-    return true;
-}
-
-template <int NS> struct GatUnroll { static constexpr int U = NS == 1 ? 4 : 2; };
-
 // online softmax + weighted gather over entries [beg - with_self, end) of row `row`: (m, sum, acc) are updated in place
 template <int VEC, int LPR, int NS>
 __device__ __forceinline__ void gat_fwd_range(const float* __restrict__ h, const float* __restrict__ s_src,

@@ -1,4 +1,4 @@
-// The scaffold the row-gather aggregations share (gat_kernels.hip, gcn2_kernels.hip, pna_kernels.hip): a new aggregation starts
+// The scaffold the row-gather aggregations share (gat_kernels.hip, gatv2_kernels.hip, gcn2_kernels.hip, pna_kernels.hip): a new aggregation starts
 // here and adds only its own arithmetic.  Every one of them walks the CSRs grapes_gcn_prepare builds with the same three kernels:
 //
 //   *_rows_k      a group of LPR lanes (half a wavefront or a whole one) owns a row; per batch of LPR entries every lane reads ONE
@@ -121,6 +121,22 @@ __device__ __forceinline__ int batch_entry(const int32_t* __restrict__ csr, int 
     }
     return idx;
 }
+
+// entry t of a walk over [beg - with_self, end): the row itself for t < beg (the implied unit self-loop), else csr[t].
+// An index outside [0, n) raises GRAPES_STATUS_BAD_INDEX and the entry is dropped.
+__device__ __forceinline__ bool gat_entry(const int32_t* __restrict__ csr, int t, int beg, int end, int row, int n, int& idx,
+                                          int32_t* status) {
+    idx = row;
+    if (t >= end) return false;
+    if (t < beg) return true;
+    const int c = batch_entry(csr, t, end, n, status);
+    if (c < 0) return false;
+    idx = c;
+    return true;
+}
+
+// gathered rows a group keeps in flight per step of an attention kernel (gat_kernels.hip, gatv2_kernels.hip)
+template <int NS> struct GatUnroll { static constexpr int U = NS == 1 ? 4 : 2; };
 
 // ------------------------------------------------------------------------------------------------------------ host side
 

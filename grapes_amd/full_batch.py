@@ -6,10 +6,10 @@
   `eval_full_batch` false, `log_wandb` true).  `--config_file` is read first and the command line wins (full-batch.py:146-150).
   Flags that change nothing here are accepted and ignored: `log_wandb`, `notes`, `eval_on_cpu`, `eval_full_batch` and the
   sampler's (`sampling_hops`, `num_samples`, `use_indicators`, `lr_gf`, `loss_coef`, `log_z_init`, `reg_param`, `batch_size`).
-  Added: `--classifier gcn|gat|gcn2|pna` (gat: the reference's GAT, modules/gcn.py:45-72, trained by autograd over the whole graph;
+  Added: `--classifier gcn|gat|gcn2|pna|gatv2` (gat: the reference's GAT, modules/gcn.py:45-72, trained by autograd over the whole graph;
   below 2^31 entries, no dropout; gcn2: modules/gcn.py:76-117's GCN2 with `--gcn2_alpha`, `--gcn2_theta`, `--gcn2_shared_weights` and
   `--dropout`, trained the same way; pna: modules/gcn.py:120-149's PNA with `--pna_aggregators`, `--pna_scalers`, `--dropout` and the
-  graph's in-degree histogram, trained the same way), `--seed` (the synthetic data and the weights) and `--large_graph auto|true|false` (the row-blocked 64-bit path of
+  graph's in-degree histogram, trained the same way; gatv2: GATv2 with `--gat_heads` heads, trained the same way, no dropout), `--seed` (the synthetic data and the weights) and `--large_graph auto|true|false` (the row-blocked 64-bit path of
   full_graph.train_step: automatic from 2^31 CSR entries on).
 * Model `GCN(F, [hidden_dim, C], dropout)` and `Adam(lr=lr_gc)` (full-batch.py:72-76).  Each epoch is one full_graph.train_step
   over the whole graph — mean CrossEntropy, or mean BCEWithLogits for 2-D labels, on the train rows — then `step()`
@@ -32,7 +32,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from .main import _EAGER_CLASSIFIERS, _bool, _large_flag, build_gcn2, build_pna, check_classifier, load_data, read_config_file
+from .main import _EAGER_CLASSIFIERS, _bool, _large_flag, build_gatv2, build_gcn2, build_pna, check_classifier, load_data, read_config_file
 
 # (name, type, default) — full-batch.py:26-50
 _FLAGS = [
@@ -46,7 +46,8 @@ _FLAGS = [
 # additions of this driver (not in the reference)
 _EXTRA = [("seed", int, None), ("large_graph", str, "auto"), ("classifier", str, "gcn"),
           ("gcn2_alpha", float, 0.1), ("gcn2_theta", float, 0.5), ("gcn2_shared_weights", bool, True),
-          ("pna_aggregators", str, "mean,min,max,std"), ("pna_scalers", str, "identity,amplification,attenuation")]
+          ("pna_aggregators", str, "mean,min,max,std"), ("pna_scalers", str, "identity,amplification,attenuation"),
+          ("gat_heads", int, 1)]
 
 
 def _parser() -> argparse.ArgumentParser:
@@ -56,9 +57,10 @@ def _parser() -> argparse.ArgumentParser:
             ap.add_argument("--large_graph", choices=["auto", "true", "false"], default=default)
         elif name == "classifier":
             # (absent from the namespace unless given: a plain run's arguments stay the reference's + seed, large_graph)
-            ap.add_argument("--classifier", choices=["gcn", "gat", "gcn2", "pna"], default=argparse.SUPPRESS)
-        elif name.startswith("gcn2_") or name.startswith("pna_"):
-            # (--classifier gcn2's / pna's hyper-parameters: absent unless given, defaults in main.build_gcn2 / build_pna)
+            ap.add_argument("--classifier", choices=["gcn", "gat", "gcn2", "pna", "gatv2"], default=argparse.SUPPRESS)
+        elif name.startswith("gcn2_") or name.startswith("pna_") or name == "gat_heads":
+            # (--classifier gcn2's / pna's / gatv2's hyper-parameters: absent unless given, defaults in main.build_gcn2 / build_pna /
+            # build_gatv2)
             ap.add_argument(f"--{name}", type=_bool if typ is bool else typ, default=argparse.SUPPRESS)
         else:
             ap.add_argument(f"--{name}", type=_bool if typ is bool else typ, default=default)
@@ -104,6 +106,8 @@ def train(args, device=None, log=print) -> float:
             gcn_c = build_gcn2(args, x.shape[1], data.num_classes, args.sampling_hops).to(device)            # modules/gcn.py:76-117
         elif kind == "pna":
             gcn_c = build_pna(args, x.shape[1], data.num_classes, args.sampling_hops, g).to(device)          # modules/gcn.py:120-149
+        elif kind == "gatv2":
+            gcn_c = build_gatv2(args, x.shape[1], data.num_classes).to(device)
         else:
             gcn_c = GAT(x.shape[1], hidden_dims=[args.hidden_dim, data.num_classes]).to(device)              # modules/gcn.py:45-72
     else:

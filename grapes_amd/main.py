@@ -18,6 +18,8 @@
   `--classifier pna` makes it modules/gcn.py:120-149's PNA, PNAConv(F -> hidden_dim -> C) with `--pna_aggregators`
   (mean,min,max,std), `--pna_scalers` (identity,amplification,attenuation), `--dropout` and the in-degree histogram of the loaded
   graph as `deg`: eager engine as well.
+  `--classifier gatv2` makes it GATv2 (PyG's GATv2Conv: multi-head dynamic attention) with `--gat_heads` heads (1): hidden layer
+  GATv2Conv(F -> hidden_dim x heads, concatenated), last layer GATv2Conv(-> C, heads averaged); eager engine, no dropout.
 
 Datasets are outside this repository's scope (no dataset files and no network on the build machines): `--dataset`
 names a SYNTHETIC graph with the statistics of the corresponding benchmark (grapes_amd.synth.CONFIGS — cora,
@@ -54,10 +56,13 @@ _EXTRA = [("e_cap", int, 1 << 17), ("max_steps", int, None), ("engine", str, "au
           # --classifier gcn2 (modules/gcn.py:76-117; the reference never constructs the model: the defaults of PyG's GCNII example [PyG-recall])
           ("gcn2_alpha", float, 0.1), ("gcn2_theta", float, 0.5), ("gcn2_shared_weights", bool, True),
           # --classifier pna (modules/gcn.py:120-149; never constructed by the reference: the PNA paper's / PyG example's sets [PyG-recall])
-          ("pna_aggregators", str, "mean,min,max,std"), ("pna_scalers", str, "identity,amplification,attenuation")]
-# gat / gcn2 / pna: the classifier is modules/gcn.py:45-72's GAT / :76-117's GCN2 / :120-149's PNA (the sampler nets stay GCN)
-_CLASSIFIERS = ("gcn", "gat", "gcn2", "pna")
-_EAGER_CLASSIFIERS = ("gat", "gcn2", "pna")
+          ("pna_aggregators", str, "mean,min,max,std"), ("pna_scalers", str, "identity,amplification,attenuation"),
+          # --classifier gatv2 (PyG's GATv2Conv; not in the reference)
+          ("gat_heads", int, 1)]
+# gat / gcn2 / pna: the classifier is modules/gcn.py:45-72's GAT / :76-117's GCN2 / :120-149's PNA (the sampler nets stay GCN);
+# gatv2: GATv2, the multi-head dynamic-attention layer of PyG (not in the reference)
+_CLASSIFIERS = ("gcn", "gat", "gcn2", "pna", "gatv2")
+_EAGER_CLASSIFIERS = ("gat", "gcn2", "pna", "gatv2")
 
 
 def check_classifier(args) -> None:
@@ -70,6 +75,14 @@ def check_classifier(args) -> None:
             raise ValueError("--classifier gat runs on the eager engine: the captured step (--engine graph) is GCN only")
         if args.dropout:
             raise ValueError("--classifier gat takes no --dropout: the reference's GAT has none (modules/gcn.py:45-72)")
+    if classifier == "gatv2":
+        if getattr(args, "engine", "auto") == "graph":
+            raise ValueError("--classifier gatv2 runs on the eager engine: the captured step (--engine graph) is GCN only")
+        if args.dropout:
+            raise ValueError("--classifier gatv2 takes no --dropout: GATv2 follows the reference's GAT, which has none "
+                             "(modules/gcn.py:45-72)")
+        from . import ops
+        ops._gatv2_shape(int(getattr(args, "gat_heads", 1)), 1)                                      # (the head count is refused here)
     if classifier == "gcn2" and getattr(args, "engine", "auto") == "graph":
         raise ValueError("--classifier gcn2 runs on the eager engine: the captured step (--engine graph) is GCN only")
     if classifier == "pna":
@@ -91,6 +104,12 @@ def build_pna(args, F: int, C: int, hops: int, g):
                aggregators=_name_list(getattr(args, "pna_aggregators", "mean,min,max,std")),
                scalers=_name_list(getattr(args, "pna_scalers", "identity,amplification,attenuation")),
                deg=pna_degree_histogram(g), dropout=args.dropout)
+
+
+def build_gatv2(args, F: int, C: int):
+    """GATv2(F, [hidden_dim, C], heads=gat_heads): GAT's two layers (modules/gcn.py:45-72) as GATv2Conv with --gat_heads heads."""
+    from .modules.gcn import GATv2
+    return GATv2(F, [args.hidden_dim, C], heads=int(getattr(args, "gat_heads", 1)))
 
 
 def build_gcn2(args, F: int, C: int, hops: int):
@@ -227,6 +246,8 @@ def train(args, device=None, log=print):
     num_ind = args.sampling_hops + 1 if args.use_indicators else 0                                 # main.py:104-107
     if getattr(args, "classifier", "gcn") == "gat":
         gcn_c = GAT(F, hidden_dims=[args.hidden_dim, C]).to(device)                                # modules/gcn.py:45-72
+    elif getattr(args, "classifier", "gcn") == "gatv2":
+        gcn_c = build_gatv2(args, F, C).to(device)
     elif getattr(args, "classifier", "gcn") == "gcn2":
         gcn_c = build_gcn2(args, F, C, args.sampling_hops).to(device)                              # modules/gcn.py:76-117
     elif getattr(args, "classifier", "gcn") == "pna":

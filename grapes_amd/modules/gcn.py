@@ -1,11 +1,12 @@
 """Drop-in ``GCN`` (reference modules/gcn.py:9-42), ``GAT`` (modules/gcn.py:45-72), ``GCN2`` (modules/gcn.py:76-117) and ``PNA``
-(modules/gcn.py:120-149) whose layers run the gfx950 kernels.
+(modules/gcn.py:120-149) whose layers run the gfx950 kernels, and ``GATv2`` (PyG's GATv2Conv under GAT's routing; not in the reference).
 
 state_dict keys match PyG's GCNConv inside the reference module: ``gcn_layers.{i}.lin.weight``
 ([out,in]) and ``gcn_layers.{i}.bias``; for GAT [PyG-recall: torch_geometric 2.5.2 GATConv] ``gat_layers.{i}.lin.weight``,
 ``.att_src`` / ``.att_dst`` ([1, 1, out]) and ``.bias``; for GCN2 [PyG-recall: GCN2Conv, Linear] ``lins.{0,1}.weight`` / ``.bias``
 and ``conv.{i}.weight1`` (``.weight2`` with ``shared_weights=False``); for PNA [PyG-recall: PNAConv] ``conv.{i}.pre_nn`` / ``.post_nn`` /
-``.lin`` ``.weight`` / ``.bias`` and ``lins.weight`` / ``.bias``.
+``.lin`` ``.weight`` / ``.bias`` and ``lins.weight`` / ``.bias``; for GATv2 [PyG-recall: GATv2Conv] ``gat_layers.{i}.att`` ([1, heads, out]),
+``.lin_l.weight`` / ``.bias``, ``.lin_r.weight`` / ``.bias`` (absent with ``share_weights``) and ``.bias``.
 """
 from __future__ import annotations
 
@@ -496,6 +497,126 @@ class GAT(nn.Module):
         return self.gat_layers[n_layers - 1](x, edges)                         # gcn.py:70,72
 
 
+# ------------------------------------------------------------------------------------------------ GATv2 (PyG GATv2Conv)
+class _GATv2ConvFn(torch.autograd.Function):
+    """out = per-head softmax-weighted gather of x_l = lin_l(x) with the scores att . LeakyReLU(x_l[j] + x_r[i]), x_r = lin_r(x):
+    grapes_linear_bias_act_fwd (one GEMM when the weights are shared, else two), grapes_gatv2_aggregate_fwd.  The backward
+    recomputes scores and attention weights from x_l, x_r and the per-head (row max, log sum): nothing is stored per edge."""
+
+    @staticmethod
+    def forward(ctx, x, w_l, b_l, w_r, b_r, att, bias, prep, heads, concat, slope, relu):
+        shared = w_r is None
+        x_l = ops.linear_bias_act_fwd(x, w_l, b_l, d_n=prep.d_n)              # x Wᵀ + b in the GEMM's epilogue (MFMA fp32)
+        x_r = x_l if shared else ops.linear_bias_act_fwd(x, w_r, b_r, d_n=prep.d_n)
+        out, agg, row_ms = ops.gatv2_aggregate_fwd(x_l, x_r, att.reshape(-1), prep, heads, concat, slope, bias, relu)
+        ctx.prep, ctx.cfg = prep, (heads, concat, slope, relu, shared)
+        ctx.save_for_backward(x, w_l, w_r, att, bias, x_l, x_r, row_ms, out, agg)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w_l, w_r, att, bias, x_l, x_r, row_ms, out, agg = ctx.saved_tensors
+        prep, (heads, concat, slope, relu, shared) = ctx.prep, ctx.cfg
+        d_n = prep.d_n
+        dx_l, dx_r, datt, dbias = ops.gatv2_aggregate_bwd(dout.contiguous(), out, agg, x_l, x_r, att.reshape(-1), row_ms, prep, heads,
+                                                          concat, slope, bias, relu)
+        if bias is None:
+            dbias = None
+        need_dx = ctx.needs_input_grad[0]
+        if shared:                                                             # one weight: the two contributions add
+            d = ops.pna_add_input_grad(dx_l, dx_r, d_n=d_n)                    # (dx_l += dx_r, in place)
+            dw_l, db_l = ops.linear_bwd_weight_gated(d, x, d_n=d_n)            # dW and the bias gradient from one GEMM
+            dx = ops.linear_bwd_input(d, w_l, d_n=d_n) if need_dx else None
+            return dx, dw_l, db_l, None, None, datt.view_as(att), dbias, None, None, None, None, None
+        dw_l, db_l = ops.linear_bwd_weight_gated(dx_l, x, d_n=d_n)
+        dw_r, db_r = ops.linear_bwd_weight_gated(dx_r, x, d_n=d_n)
+        dx = None
+        if need_dx:
+            dx = ops.pna_add_input_grad(ops.linear_bwd_input(dx_l, w_l, d_n=d_n), ops.linear_bwd_input(dx_r, w_r, d_n=d_n), d_n=d_n)
+        return dx, dw_l, db_l, dw_r, db_r, datt.view_as(att), dbias, None, None, None, None, None
+
+
+class GATv2Conv(nn.Module):
+    """PyG GATv2Conv [PyG-recall: torch_geometric 2.5.2]: `heads` heads of dynamic attention,
+    e_ij = att . LeakyReLU(lin_l(x_j) + lin_r(x_i)), softmax per head over the incoming edges and one re-added self-loop, the heads
+    side by side (concat) or averaged, + bias.  State dict: att [1, H, C], lin_l.{weight,bias}, lin_r.{weight,bias} (absent with
+    share_weights), bias.  Not built (NotImplementedError): attention dropout, edge features, add_self_loops=False, another
+    fill_value."""
+
+    def __init__(self, in_channels: int, out_channels: int, heads: int = 1, concat: bool = True, negative_slope: float = 0.2,
+                 dropout: float = 0.0, add_self_loops: bool = True, edge_dim=None, fill_value="mean", bias: bool = True,
+                 share_weights: bool = False):
+        super().__init__()
+        if dropout:
+            raise NotImplementedError("GATv2Conv: attention dropout is not built (the two backward passes walk different CSRs and "
+                                      "share no edge id to key a mask on)")
+        if edge_dim is not None:
+            raise NotImplementedError("GATv2Conv: edge features (edge_dim) are not built")
+        if not add_self_loops:
+            raise NotImplementedError("GATv2Conv: add_self_loops=False is not built (the kernels imply one unit self-loop per node)")
+        if not (isinstance(fill_value, str) and fill_value == "mean"):
+            raise NotImplementedError("GATv2Conv: fill_value other than the default is not built (it fills edge features only)")
+        ops._gatv2_shape(heads, out_channels)
+        ops._gatv2_slope(negative_slope)
+        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, bool(concat)
+        self.negative_slope, self.share_weights = float(negative_slope), bool(share_weights)
+        self.lin_l = nn.Linear(in_channels, heads * out_channels, bias=True)
+        if share_weights:                       # (the same module, not registered twice: the state dict has no lin_r.* keys)
+            object.__setattr__(self, "lin_r", self.lin_l)
+        else:
+            self.lin_r = nn.Linear(in_channels, heads * out_channels, bias=True)
+        self.att = nn.Parameter(torch.empty(1, heads, out_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(heads * out_channels if concat else out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        a = math.sqrt(6.0 / (self.in_channels + self.heads * self.out_channels))    # PyG glorot
+        b = math.sqrt(6.0 / (self.heads + self.out_channels))                       # glorot on [1, H, C]: fan = size(-2) + size(-1)
+        with torch.no_grad():
+            for lin in ((self.lin_l,) if self.share_weights else (self.lin_l, self.lin_r)):
+                lin.weight.uniform_(-a, a)
+                lin.bias.zero_()
+            self.att.uniform_(-b, b)
+            if self.bias is not None:
+                self.bias.zero_()
+
+    def forward(self, x, edge_index, relu: bool = False):
+        x = _cuda_f32(x, "GATv2Conv")
+        prep = _gat_graph(edge_index, x.shape[0])
+        shared = self.share_weights
+        return _GATv2ConvFn.apply(x, self.lin_l.weight, self.lin_l.bias, None if shared else self.lin_r.weight,
+                                  None if shared else self.lin_r.bias, self.att, self.bias, prep, self.heads, self.concat,
+                                  self.negative_slope, relu)
+
+
+class GATv2(nn.Module):
+    """GAT's routing (modules/gcn.py:45-72) over GATv2Conv layers with `heads` heads: hidden layers concatenate their heads (the
+    next layer's input is hidden x heads wide) with the ReLU fused, the last layer averages them; logits ONLY."""
+
+    def __init__(self, in_features: int, hidden_dims: "list[int]", heads: int = 1):
+        super(GATv2, self).__init__()
+        gat_layers, d_in = [], in_features
+        for hidden in hidden_dims[:-1]:
+            gat_layers.append(GATv2Conv(d_in, hidden, heads=heads))
+            d_in = hidden * heads
+        gat_layers.append(GATv2Conv(d_in, hidden_dims[-1], heads=heads, concat=False))
+        self.gat_layers = nn.ModuleList(gat_layers)
+
+    def forward(self, x: torch.Tensor, edge_index: Union[torch.Tensor, "list[torch.Tensor]"]) -> torch.Tensor:
+        if not x.is_cuda:
+            raise ops._lib.GrapesHipError("GATv2 input must be a cuda tensor (grapes_amd has no CPU path)")
+        layerwise_adjacency = type(edge_index) == list
+        n_layers = len(self.gat_layers)
+        for i in range(1, n_layers):
+            edges = edge_index[-i] if layerwise_adjacency else edge_index
+            x = self.gat_layers[i - 1](x, edges, relu=True)
+        edges = edge_index[0] if layerwise_adjacency else edge_index
+        return self.gat_layers[n_layers - 1](x, edges)
+
+
 # ------------------------------------------------------------------------------------------------ GCN2 (modules/gcn.py:76-117)
 class _LinearFn(torch.autograd.Function):
     """act(x Wᵀ + b): one GEMM with the bias and the ReLU in its epilogue; the backward gates by the saved output."""
@@ -831,10 +952,10 @@ class PNA(nn.Module):
 
 
 def classifier_layers(model) -> nn.ModuleList:
-    """The conv layers of a classifier: GCN (gcn_layers), GAT (gat_layers), GCN2 or PNA (conv)."""
+    """The conv layers of a classifier: GCN (gcn_layers), GAT or GATv2 (gat_layers), GCN2 or PNA (conv)."""
     if isinstance(model, (GCN2, PNA)):
         return model.conv
-    return model.gat_layers if isinstance(model, GAT) else model.gcn_layers
+    return model.gat_layers if isinstance(model, (GAT, GATv2)) else model.gcn_layers
 
 
 def classifier_needs_loops(model) -> bool:
@@ -845,7 +966,7 @@ def classifier_needs_loops(model) -> bool:
 
 def classifier_logits(model, x, edge_index):
     """(logits, allocated MiB): GCN.forward returns the pair (gcn.py:42), GAT.forward, GCN2.forward and PNA.forward the logits alone
-    (gcn.py:72,117,149)."""
-    if isinstance(model, (GAT, GCN2, PNA)):
+    (gcn.py:72,117,149), and so does GATv2.forward."""
+    if isinstance(model, (GAT, GATv2, GCN2, PNA)):
         return model(x, edge_index), _memory_allocated_mb()
     return model(x, edge_index)

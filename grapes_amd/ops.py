@@ -1563,6 +1563,99 @@ def gat_aggregate_bwd(dout, out, h, s_src, s_dst, row_ms, a_src, a_dst, prep: Pr
     return dh, da_src, da_dst, dbias
 
 
+# ------------------------------------------------------------------------------- GATv2Conv aggregation (PyG GATv2Conv)
+def _gatv2_shape(heads: int, c: int):
+    """The shapes csrc/gatv2_kernels.hip is built for: 1..16 heads of c channels, f = heads c up to 256, or up to 1024 with c % 4 == 0."""
+    if not 1 <= heads <= 16:
+        raise ValueError(f"GATv2 aggregation: heads = {heads} is not built (1 <= heads <= 16)")
+    f = heads * c
+    if c < 1 or f > 1024 or (f > 256 and c % 4):
+        raise ValueError(f"GATv2 aggregation: heads x out_channels = {heads} x {c} is not built (heads * out_channels up to 256, "
+                         "or up to 1024 with out_channels % 4 == 0)")
+
+
+def _gatv2_slope(negative_slope: float) -> float:
+    if not 0.0 <= negative_slope < 1.0:
+        raise ValueError(f"GATv2 aggregation: negative_slope = {negative_slope} is outside [0, 1)")
+    return float(negative_slope)
+
+
+def _gatv2_items(prep, by_target: bool, forward: bool):
+    """(items, n_items, cap): prep's long-row work items by target or by source, whatever the graph's size — one head's score
+    costs a whole row of arithmetic per edge, so a hub row is worth its own workgroups on a small graph too; (None, None, 0) for a
+    forward over a graph prepared without them."""
+    if forward and not prep.items_fwd:
+        return None, None, 0
+    items, n_items = (prep.items_t, prep.n_items_t) if by_target else (prep.items_s, prep.n_items_s)
+    return _p(items), _p(n_items), prep.item_cap
+
+
+def gatv2_aggregate_fwd(x_l, x_r, att, prep: PreparedGraph, heads: int, concat=True, negative_slope=0.2, bias=None, relu=False):
+    """(out, agg, row_ms) of GATv2Conv's propagate over prep's by-target CSR plus one unit self-loop per node: per head h,
+    e_ij = att[h] . LeakyReLU(x_l[j, h] + x_r[i, h]), alpha = softmax_j e_ij, agg_i[h] = sum_j alpha_ij x_l[j, h]; out = the heads
+    side by side [n, f] (concat) or their mean [n, c], + bias (+ReLU).  agg [n, f] is the per-head aggregate when concat is false
+    (else None: it is out - bias); row_ms [n, heads, 2] = (maximum, log of the softmax sum), what gatv2_aggregate_bwd recomputes
+    the attention weights from."""
+    _chk(x_l, _f32, "x_l"); _chk(x_r, _f32, "x_r"); _chk(att, _f32, "att"); _chk(bias, _f32, "bias", True)
+    n, f = x_l.shape
+    if heads < 1 or f % heads:
+        raise ValueError(f"GATv2 aggregation: width {f} is not a multiple of heads = {heads}")
+    c = f // heads
+    _gatv2_shape(heads, c)
+    slope = _gatv2_slope(negative_slope)
+    if n != prep.n or x_r.shape != x_l.shape or att.numel() != f:
+        raise ValueError("x_l and x_r must be [n, heads * c] over the prepared graph's nodes and att must hold heads * c values")
+    if bias is not None and bias.numel() != (f if concat else c):
+        raise ValueError("bias must hold heads * c values (concat) or c values (head mean)")
+    dev = x_l.device
+    out = torch.empty((n, f if concat else c), dtype=_f32, device=dev)
+    agg = None if concat else torch.empty((n, f), dtype=_f32, device=dev)
+    row_ms = torch.empty((max(n, 1), heads, 2), dtype=_f32, device=dev)
+    items, n_items, cap = _gatv2_items(prep, by_target=True, forward=True)
+    ws = _ws(lib().grapes_gatv2_aggregate_workspace_bytes(cap, f, heads), dev) if cap else None
+    _lib.check(lib().grapes_gatv2_aggregate_fwd(_p(x_l), _p(x_r), _p(att), _p(prep.rowptr_t), _p(prep.csr_src), _p(bias), _p(out),
+                                                _p(agg), _p(row_ms), n, _p(prep.d_n), heads, c, 1 if concat else 0, slope,
+                                                1 if relu else 0, items, n_items, cap, _p(ws), _p(prep.status), _stream()),
+               "gatv2_aggregate_fwd")
+    return out, agg, row_ms
+
+
+def gatv2_aggregate_bwd(dout, out, agg, x_l, x_r, att, row_ms, prep: PreparedGraph, heads: int, concat=True, negative_slope=0.2,
+                        bias=None, relu=False):
+    """Returns (dx_l, dx_r, datt, dbias) for gatv2_aggregate_fwd.  `out`, `agg` and `row_ms` are the forward's; dout is not
+    modified."""
+    for t, name in ((dout, "dout"), (out, "out"), (x_l, "x_l"), (x_r, "x_r"), (att, "att"), (row_ms, "row_ms")):
+        _chk(t, _f32, name)
+    _chk(bias, _f32, "bias", True); _chk(agg, _f32, "agg", concat)
+    n, f = x_l.shape
+    if heads < 1 or f % heads:
+        raise ValueError(f"GATv2 aggregation: width {f} is not a multiple of heads = {heads}")
+    c = f // heads
+    _gatv2_shape(heads, c)
+    slope = _gatv2_slope(negative_slope)
+    w = f if concat else c
+    if n != prep.n or x_r.shape != x_l.shape or tuple(dout.shape) != (n, w) or out.shape != dout.shape or att.numel() != f:
+        raise ValueError("x_l and x_r must be [n, heads * c] over the prepared graph's nodes, dout and out [n, heads * c] (concat) "
+                         "or [n, c]")
+    if not concat and tuple(agg.shape) != (n, f):
+        raise ValueError("agg must be the forward's [n, heads * c] per-head aggregate")
+    if row_ms.numel() < n * heads * 2:
+        raise ValueError("row_ms must be the forward's [n, heads, 2]")
+    dev = dout.device
+    dx_l, dx_r = torch.empty_like(x_l), torch.empty_like(x_l)
+    datt = torch.empty(f, dtype=_f32, device=dev)
+    dbias = torch.empty(w, dtype=_f32, device=dev)
+    items_t, n_items_t, cap = _gatv2_items(prep, by_target=True, forward=False)
+    items_s, n_items_s, _ = _gatv2_items(prep, by_target=False, forward=False)
+    ws = _ws(lib().grapes_gatv2_aggregate_bwd_workspace_bytes(n, cap, f, heads), dev)
+    _lib.check(lib().grapes_gatv2_aggregate_bwd(_p(dout), _p(out), _p(agg), _p(bias), 1 if relu else 0, _p(x_l), _p(x_r), _p(att),
+                                                _p(row_ms), _p(prep.rowptr_t), _p(prep.csr_src), _p(prep.rowptr_s), _p(prep.csr_dst),
+                                                _p(dx_l), _p(dx_r), _p(datt), _p(dbias), n, _p(prep.d_n), heads, c,
+                                                1 if concat else 0, slope, items_t, n_items_t, items_s, n_items_s, cap, _p(ws),
+                                                _p(prep.status), _stream()), "gatv2_aggregate_bwd")
+    return dx_l, dx_r, datt, dbias
+
+
 # ------------------------------------------------------------------------------- GCN2Conv propagation (modules/gcn.py:76-117)
 def _gcn2_width(f: int):
     if f < 1 or f > 1024:

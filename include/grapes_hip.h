@@ -689,6 +689,47 @@ int grapes_gat_aggregate_bwd(const float* dout, const float* out, const float* b
                              const int32_t* d_n_items_t, const int32_t* items_s, const int32_t* d_n_items_s,
                              int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
 
+/* ------------------------------------------------------------------ GATv2Conv aggregation (csrc/gatv2_kernels.hip)
+ * PyG's GATv2Conv (torch_geometric 2.5.2, not in the reference tree) with `heads` heads of `c` channels, f = heads c, LeakyReLU slope
+ * negative_slope in [0, 1), add_self_loops, no attention dropout.  With x_l = lin_l(x), x_r = lin_r(x) (grapes_linear_fwd), [n, f]
+ * viewed as [n, heads, c], and att [heads, c]:
+ *   e_ij[h] = sum_c att[h, c] LeakyReLU(x_l[j, h, c] + x_r[i, h, c])   alpha_ij[h] = softmax over the edges j -> i, per head
+ *   agg_i[h] = sum_j alpha_ij[h] x_l[j, h]   out_i = concat_h agg_i[h] + bias (concat != 0, [n, f]) or mean_h agg_i[h] + bias ([n, c])
+ * over the edge set of grapes_gcn_prepare: stored self-loops dropped, one unit self-loop per node implied, duplicates kept.
+ * Shapes: 1 <= heads <= 16; c % 4 == 0 with 16-byte aligned rows up to f = 1024, any c up to f = 256; GRAPES_EINVAL / GRAPES_EALIGN
+ * otherwise.  Every sum has a fixed order (no floating-point atomics): results are bit-identical from run to run.  status:
+ * GRAPES_STATUS_BAD_INDEX when a CSR entry is outside [0, n) (the entry is dropped). */
+/* GATv2Conv.propagate (+ a ReLU on the result when relu != 0): the per-edge score, one online softmax per head and the weighted
+ * gather in ONE pass over the by-target CSR, every row x_l[j] loaded once per edge; 1 / sum, head concat or mean, bias and ReLU
+ * follow.  row_ms [n][heads][2] receives (maximum, log of the softmax sum) per head for the backward; agg [n][f] receives the
+ * per-head aggregate before the mean and the bias when concat == 0 (NULL otherwise: it is out - bias).  long_items / d_n_items /
+ * item_cap / workspace as grapes_gat_aggregate_fwd: rows longer than GRAPES_LONG_ROW are cut into items whose per-head (max, sum)
+ * and accumulators are merged in chunk order.  workspace: grapes_gatv2_aggregate_workspace_bytes(item_cap, f, heads), 16-byte
+ * aligned.  bias may be NULL. */
+size_t grapes_gatv2_aggregate_workspace_bytes(int32_t item_cap, int32_t f, int32_t heads);
+int grapes_gatv2_aggregate_fwd(const float* x_l, const float* x_r, const float* att, const int32_t* rowptr_t,
+                               const int32_t* csr_src, const float* bias, float* out, float* agg, float* row_ms, int32_t n,
+                               const int32_t* d_n, int32_t heads, int32_t c, int32_t concat, float negative_slope, int32_t relu,
+                               const int32_t* long_items, const int32_t* d_n_items, int32_t item_cap, void* workspace,
+                               int32_t* status, grapes_stream_t stream);
+/* Backward of the above (autograd through GATv2Conv.propagate).  With G = dout gated by out > 0 when relu != 0, viewed per head
+ * (G / heads for every head when concat == 0), z_ij = x_l[j] + x_r[i], c[i, h] = G[i, h] . agg_i[h],
+ * de_ij[h] = alpha_ij[h] (G[i, h] . x_l[j, h] - c[i, h]) and dz_ij[h, c] = de_ij[h] att[h, c] (z_ij > 0 ? 1 : negative_slope):
+ *   dx_l[j] = sum_i alpha_ij G[i] + dz_ij   dx_r[i] = sum_j dz_ij   datt[h, c] = sum_ij de_ij[h] LeakyReLU(z_ij[h, c])
+ *   dbias = sum_i dout_i (gated; [f] or [c])                                               (datt and dbias may be NULL)
+ * Nothing is kept per edge: a pass over the by-target CSR (dx_r, datt) and one over the by-source CSR (dx_l) each recompute z, e
+ * and alpha from x_l, x_r and row_ms; datt and dbias are per-workgroup partials added in a fixed tree.  out / agg: the forward's.
+ * items_t / items_s: the two halves of gcn_prepare's item table with their counts (NULL: no row splitting).
+ * workspace: grapes_gatv2_aggregate_bwd_workspace_bytes(n, item_cap, f, heads), 16-byte aligned. */
+size_t grapes_gatv2_aggregate_bwd_workspace_bytes(int32_t n, int32_t item_cap, int32_t f, int32_t heads);
+int grapes_gatv2_aggregate_bwd(const float* dout, const float* out, const float* agg, const float* bias, int32_t relu,
+                               const float* x_l, const float* x_r, const float* att, const float* row_ms,
+                               const int32_t* rowptr_t, const int32_t* csr_src, const int32_t* rowptr_s, const int32_t* csr_dst,
+                               float* dx_l, float* dx_r, float* datt, float* dbias, int32_t n, const int32_t* d_n, int32_t heads,
+                               int32_t c, int32_t concat, float negative_slope, const int32_t* items_t,
+                               const int32_t* d_n_items_t, const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap,
+                               void* workspace, int32_t* status, grapes_stream_t stream);
+
 /* ------------------------------------------------------------------ GCN2Conv / GCNII (csrc/gcn2_kernels.hip)
  * modules/gcn.py:76-117: GCN2 stacks GCN2Conv(channels, alpha, theta, layer, shared_weights, normalize=False) layers
  * (torch_geometric 2.5.2, not in the reference tree).  normalize=False: no gcn_norm and no added loop; with
