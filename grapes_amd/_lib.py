@@ -83,6 +83,10 @@ SIGNATURES = {
     # GraphSAINT's normalisation (sample_coverage > 0)
     "grapes_saint_coverage_count": (I32, [P, P, I32, P, P, P, I32, P, P, P, P]),
     "grapes_saint_norms": (I32, [P, I32, P, P, I64, P, P, P]),
+    # LADIES / FastGCN layer-wise samplers
+    "grapes_ladies_importance": (I32, [P, P, P, I32, P, I32, P, P, I32, P, P, P, P, P, P]),
+    "grapes_ladies_layer_workspace_bytes": (SZ, [I32]),
+    "grapes_ladies_layer": (I32, [P, P, I32, P, I32, P, P, P, I32, P, P, P, P, P, P, P]),
     # GATConv aggregation (modules/gcn.py:45-72)
     "grapes_gat_scores": (I32, [P, P, P, P, P, I32, P, I32, P]),
     "grapes_gat_aggregate_workspace_bytes": (SZ, [I32, I32]),

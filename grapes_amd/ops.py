@@ -2631,6 +2631,64 @@ def saint_norms(rowptr, num_nodes: int, node_count, edge_count, num_samples: int
     return edge_norm, node_norm
 
 
+# ------------------------------------------------------------------------------- LADIES / FastGCN layer-wise samplers
+# [LADIES-recall: acbull/LADIES pytorch_ladies.py, ladies_sampler / fastgcn_sampler]  V = A + I, P = D^-1 V (grapes_hip.h).
+def ladies_importance(rowptr, rowptr_t, col_t, num_nodes: int, ids=None, n=None, d_n=None, prev_bits=None, m=None, d_m=None,
+                      pi_table=None, status=None, out=None):
+    """(pi fp32 [n], logit fp32 [n]) of grapes_ladies_importance: pi[k] = sum over the rows i of the set of P_ij^2 for j = ids[k]
+    (ids None: j = k, n defaults to N), logit = logf(pi) - (20 + logf(float(m))).  The set: the bitmap prev_bits of m rows, or every
+    row (prev_bits None: m defaults to N).  rowptr_t / col_t: the CSR of the transpose (the graph's own arrays when symmetric).
+    pi_table (fp32 [N]): also pi_table[ids[k]] = pi[k].  out: the two tensors to write; entries past *d_n stay as they are."""
+    _chk(rowptr, _i64, "rowptr"); _chk(rowptr_t, _i64, "rowptr_t"); _chk(col_t, _i32, "col_t"); _chk(ids, _i32, "ids", True)
+    _chk(d_n, _i32, "d_n", True); _chk(prev_bits, _i64, "prev_bits", True); _chk(d_m, _i32, "d_m", True)
+    _chk(pi_table, _f32, "pi_table", True); _chk(status, _i32, "status", True)
+    N, dev = int(num_nodes), rowptr.device
+    if n is None:
+        n = ids.numel() if ids is not None else N
+    if m is None:
+        if prev_bits is not None:
+            raise ValueError("ladies_importance: a bitmap comes with m, the number of rows it holds")
+        m = N
+    n, m = int(n), int(m)
+    if rowptr.numel() != N + 1 or rowptr_t.numel() != N + 1 or n < 1 or m < 1 or (ids is not None and ids.numel() < n):
+        raise ValueError("ladies_importance: rowptr / rowptr_t hold N + 1 values, ids at least n >= 1 ids, and m >= 1")
+    if (prev_bits is not None and prev_bits.numel() < (N + 63) // 64) or (pi_table is not None and pi_table.numel() < N):
+        raise ValueError("ladies_importance: prev_bits holds ceil(N / 64) words, pi_table one value per node")
+    if out is None:
+        out = (torch.empty(n, dtype=_f32, device=dev), torch.empty(n, dtype=_f32, device=dev))
+    pi, logit = out
+    _chk(pi, _f32, "pi"); _chk(logit, _f32, "logit")
+    if pi.numel() < n or logit.numel() < n:
+        raise ValueError("ladies_importance: pi and logit hold n values each")
+    _lib.check(lib().grapes_ladies_importance(_p(rowptr), _p(rowptr_t), _p(col_t), N, _p(ids), n, _p(d_n), _p(prev_bits), m, _p(d_m),
+                                              _p(pi), _p(logit), _p(pi_table), _p(status), _stream()), "ladies_importance")
+    return pi, logit
+
+
+def ladies_layer(rowptr, col, num_nodes: int, rows, keep_bits, pi_table, e_cap: int, d_m=None, status=None, out=None):
+    """(edge_src, edge_dst int32 [e_cap], weight fp32 [e_cap], e_count int32 [1]) of grapes_ladies_layer: for the rows i = rows[r]
+    in order and ascending j, every (i, j) of V = A + I with j in the bitmap keep_bits — source j, target i, global ids — with
+    weight (v_ij / pi_table[j]) / the row's sum of them.  More than e_cap entries set the overflow status bit.
+    out: the four tensors to write."""
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(rows, _i32, "rows"); _chk(keep_bits, _i64, "keep_bits")
+    _chk(pi_table, _f32, "pi_table"); _chk(d_m, _i32, "d_m", True); _chk(status, _i32, "status", True)
+    N, dev, m, ec = int(num_nodes), rows.device, rows.numel(), int(e_cap)
+    if rowptr.numel() != N + 1 or keep_bits.numel() < (N + 63) // 64 or pi_table.numel() < N or m < 1 or ec < 1:
+        raise ValueError("ladies_layer: rowptr holds N + 1 values, keep_bits ceil(N / 64) words, pi_table N values; rows and e_cap "
+                         "are not empty")
+    if out is None:
+        out = (torch.empty(ec, dtype=_i32, device=dev), torch.empty(ec, dtype=_i32, device=dev),
+               torch.empty(ec, dtype=_f32, device=dev), torch.empty(1, dtype=_i32, device=dev))
+    src, dst, w, d_e = out
+    _chk(src, _i32, "edge_src"); _chk(dst, _i32, "edge_dst"); _chk(w, _f32, "weight"); _chk(d_e, _i32, "e_count")
+    if min(src.numel(), dst.numel(), w.numel()) < ec:
+        raise ValueError("ladies_layer: the edge buffers hold e_cap values each")
+    ws = _ws(lib().grapes_ladies_layer_workspace_bytes(m), dev)
+    _lib.check(lib().grapes_ladies_layer(_p(rowptr), _p(col), N, _p(rows), m, _p(d_m), _p(keep_bits), _p(pi_table), ec, _p(src),
+                                         _p(dst), _p(w), _p(d_e), _p(ws), _p(status), _stream()), "ladies_layer")
+    return src, dst, w, d_e
+
+
 def classifier_loss(logits, local_rows, target_ids, labels, out_grad=None):
     """(loss_c [1], d loss_c / d logits [n_rows, C]) — main.py:260,267.  labels: int64 [N] or fp32 [N, C]."""
     _chk(logits, _f32, "logits"); _chk(local_rows, _i32, "local_rows"); _chk(target_ids, _i32, "target_ids")

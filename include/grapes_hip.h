@@ -60,7 +60,9 @@ extern "C" {
  * (+ _workspace_bytes each);
  * 303: five signatures grew the arguments of a twin that 302 had added beside them, and the twins left: grapes_wgcn_weights (loop_ptr,
  * loop_idx, mode, fill), grapes_wgcn_aggregate_fwd / _bwd (mode) <- their _mode forms; grapes_saint_subgraph (edge_id, edge_norm,
- * edge_norm_b) <- its _ids form; grapes_saint_masked_loss (node_norm) <- its _weighted form. */
+ * edge_norm_b) <- its _ids form; grapes_saint_masked_loss (node_norm) <- its _weighted form; added within 303 (no signature of an
+ * earlier entry point changed): the LADIES / FastGCN layer-wise samplers — grapes_ladies_importance,
+ * grapes_ladies_layer(_workspace_bytes). */
 #define GRAPES_ABI_VERSION 303
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1433,6 +1435,33 @@ int grapes_saint_coverage_count(const int64_t* rowptr, const int32_t* col, int32
  *   node_norm[v] = (fp32(num_samples) / c) / fp32(N), c = fp32(node_count[v]), or 0.1 where the count is 0.
  * One wavefront per CSR row, rows shorter and longer than a wavefront alike.  One launch. */
 int grapes_saint_norms(const int64_t* rowptr, int32_t num_nodes, const uint32_t* node_count, const uint32_t* edge_count, int64_t num_samples, float* edge_norm, float* node_norm, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ LADIES / FastGCN layer-wise importance sampling
+ * (csrc/ladies_kernels.hip) [LADIES-recall: acbull/LADIES pytorch_ladies.py].  V = A + I over the CSR (rowptr int64[N + 1], col
+ * int32, ascending, duplicate-free; a stored (i, i) makes v_ii = 2), P = D^-1 V, D_i = (rowptr[i + 1] - rowptr[i]) + 1.
+ * The importance of n candidates [LADIES-recall: ladies_sampler, `pi = np.array(np.sum(U.multiply(U), axis=0))[0]` with
+ * U = lap_matrix[previous_nodes, :]; fastgcn_sampler, the same over every row of lap_matrix]:
+ *   pi[k] = sum over the rows i of the set of P_ij^2, j = ids[k] (ids NULL: j = k); logit[k] = logf(pi[k]) - C with
+ *   C = 20 + logf(float(m)) — the shifted logits the existing draw (grapes_gumbel_topk*, mode 0) takes: there log sigmoid(l) = l in
+ *   fp32, so its exact-k Gumbel draw samples without replacement in proportion to pi; pi_table[j] = pi[k] when given (fp32[N]; only
+ *   candidates are written).
+ * The set is the bitmap prev_bits (uint64[ceil(N / 64)], bit v & 63 of word v >> 6) of m (*d_m) rows, or every row (prev_bits NULL;
+ * pass m = N).  rowptr_t / col_t: the CSR of the transpose (the graph's own arrays when it is symmetric); rowptr gives D_i.
+ * n / d_n, m / d_m: capacity and optional device count, as everywhere; entries at or past *d_n are not written.  One wavefront per
+ * candidate walks row j of the transpose 64 entries per trip (long rows by the same loop), lane-strided partial sums, a butterfly,
+ * then the diagonal term (v_jj / D_j)^2 when j is in the set: a fixed order, no atomics.  An id outside [0, N) raises
+ * GRAPES_STATUS_BAD_INDEX (its pi is 0, its logit -inf).  One launch. */
+int grapes_ladies_importance(const int64_t* rowptr, const int64_t* rowptr_t, const int32_t* col_t, int32_t num_nodes, const int32_t* ids, int32_t n, const int32_t* d_n, const uint64_t* prev_bits, int32_t m, const int32_t* d_m, float* pi, float* logit, float* pi_table, int32_t* status, grapes_stream_t stream);
+/* One layer's reweighted, row-normalised slice [LADIES-recall: ladies_sampler, `adj = U[:, after_nodes].multiply(1 / p[after_nodes])`
+ * then `row_normalize(adj)`]: for the rows i = rows[r], r < m (*d_m), in that order, and within a row for ascending j, every
+ * (i, j) with v_ij > 0 and j in keep_bits (the bitmap of the kept columns): edge_src[e] = j, edge_dst[e] = i (global ids),
+ * weight[e] = (v_ij / pi_table[j]) / sum over the row's kept j' of v_ij' / pi_table[j'].  The diagonal entry sits at its sorted
+ * place, a stored loop folded into it (v = 2).  A row without a kept column has no entries.  *d_e = the entry count; more than e_cap
+ * raise GRAPES_STATUS_EDGE_OVERFLOW, *d_e = e_cap and nothing past e_cap is written.  An id outside [0, N) raises
+ * GRAPES_STATUS_BAD_INDEX and is dropped.  Count, one-workgroup scan, write: three launches; the row sums in the importance's fixed
+ * order.  workspace: grapes_ladies_layer_workspace_bytes(m), 4-byte aligned. */
+size_t grapes_ladies_layer_workspace_bytes(int32_t m);
+int grapes_ladies_layer(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* rows, int32_t m, const int32_t* d_m, const uint64_t* keep_bits, const float* pi_table, int32_t e_cap, int32_t* edge_src, int32_t* edge_dst, float* weight, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:
