@@ -60,7 +60,7 @@ __device__ __forceinline__ float loss_row(const float* __restrict__ logits, floa
     if ((unsigned)row < (unsigned)n_rows) {
         const RowStrided r{logits + (long long)row * C, dlogits + (long long)row * C, C, lane};
         loss = multilabel ? row_loss_bce(r, labels_f + gid * C, inv)
-                          : row_loss_ce<CE_LOG_SOFTMAX>(r, (int)labels[gid], inv);
+                          : row_loss_ce(r, (int)labels[gid], inv);
     }
     return loss;
 }
@@ -672,7 +672,7 @@ __global__ __launch_bounds__(256) void rl_loss_rows_k(const float* z, long long 
         if (!multi) {
             const long long y = labels[r];
             if ((y < 0 || y >= C) && lane == 0 && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
-            lrow = row_loss_ce<CE_LOG_SUM_EXP>(rs, y, inv);
+            lrow = row_loss_ce(rs, y, inv);
         } else {
             lrow = row_loss_bce(rs, labels_f + r * C, inv);
         }

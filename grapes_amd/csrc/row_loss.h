@@ -6,7 +6,7 @@
 //   RowSlots     lane l holds column l + 64 k in register slot k, already transformed (the dropout in front of rl_loss_rows_k); the
 //                gradient goes to register slots too
 // A Row has  each(f): f(k, c) for every (slot, column) the lane holds;  get(k, c);  put(k, c, gradient).  A call site reads
-//     const RowStrided r{z_row, g_row, C, lane};   loss = row_loss_ce<CE_LOG_SUM_EXP>(r, label, 1.f / rows);
+//     const RowStrided r{z_row, g_row, C, lane};   loss = row_loss_ce(r, label, 1.f / rows);
 // Label reading and checking, dropout, dinv and row masks, and the reduction over rows stay with the kernels.  All 64 lanes call;
 // the row's loss comes back to every lane.  `inv` scales the gradient (1 / rows, or 1 / (rows C)), not the returned loss.
 #pragma once                 // (after common.h: wave_max, wave_sum)
@@ -27,14 +27,12 @@ struct RowSlots {
     __device__ __forceinline__ float get(int k, int) const { return x[k]; }
     __device__ __forceinline__ void put(int k, int, float v) const { g[k] = v; }
 };
-// The two orders of operations the trainers' cross-entropy rows were written in.  They agree to the last bits but not in them, so
-// each site keeps its own until ONE is chosen for all (a change of results, hence not made here: it is this template argument).
-//   CE_LOG_SOFTMAX   lsm = (x - m) - log(se),  p = exp(lsm),      loss = -lsm[y]       the GRAPES step (classifier_loss_k, step_losses_mb_k)
-//   CE_LOG_SUM_EXP   lse = m + log(se),        p = exp(x - lse),  loss = lse - x[y]    full-batch (rl_loss_rows_k); GraphSAINT's own rows
-enum CeOrder { CE_LOG_SOFTMAX, CE_LOG_SUM_EXP };
+// Cross-entropy rows are formed shift first, as torch's log_softmax:  lsm = (x - m) - log(se),  p = exp(lsm),  loss = -lsm[y].  The
+// row maximum is never added back (lse = m + log(se), p = exp(x - lse)): that sum is rounded at the size of m, so a common offset of
+// the row would reach the softmax — 2^-24 |m| of error in every p.
 
 // y outside [0, C): no column matches — loss 0 and the plain softmax as the gradient (the callers that refuse such a label do so first).
-template <CeOrder ORD, class Row>
+template <class Row>
 __device__ __forceinline__ float row_loss_ce(const Row& r, long long y, float inv) {
     float m = -INFINITY;
     r.each([&](int k, int c) { m = fmaxf(m, r.get(k, c)); });
@@ -42,20 +40,12 @@ __device__ __forceinline__ float row_loss_ce(const Row& r, long long y, float in
     float se = 0.f;
     r.each([&](int k, int c) { se += expf(r.get(k, c) - m); });
     se = wave_sum(se);
-    const float lse = ORD == CE_LOG_SOFTMAX ? logf(se) : m + logf(se);
+    const float lse = logf(se);
     float loss = 0.f;
     r.each([&](int k, int c) {
-        const float x = r.get(k, c);
-        float p;
-        if (ORD == CE_LOG_SOFTMAX) {
-            const float lsm = (x - m) - lse;                                   // log_softmax
-            if (c == y) loss = -lsm;
-            p = expf(lsm);
-        } else {
-            if (c == y) loss = lse - x;
-            p = expf(x - lse);
-        }
-        r.put(k, c, (p - (c == y ? 1.0f : 0.0f)) * inv);
+        const float lsm = (r.get(k, c) - m) - lse;                             // log_softmax
+        if (c == y) loss = -lsm;
+        r.put(k, c, (expf(lsm) - (c == y ? 1.0f : 0.0f)) * inv);
     });
     return wave_sum(loss);                                                     // (one lane holds column y: the others add 0)
 }

@@ -358,7 +358,7 @@ __global__ __launch_bounds__(256) void saint_edge_write_k(const int64_t* __restr
 
 // saint_masked_loss_k stays out of block_prims.h and row_loss.h: on block_excl_scan and the shared row routines the launch measured
 // 1 % slower in every arrangement tried (profiles/block_prims_ab.txt), so it keeps its own scan (inclusive, one value per thread,
-// blockDim.x == SAINT_THREADS; *total = the sum) and its own rows, in the CE_LOG_SUM_EXP order of row_loss.h
+// blockDim.x == SAINT_THREADS; *total = the sum) and its own rows, shift first as row_loss.h's (lsm = (z - mx) - log(se))
 __device__ __forceinline__ int saint_block_scan(int v, int* wsum, int* total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
     int inc = wave_incl_scan(v);
@@ -378,7 +378,7 @@ __device__ __forceinline__ int saint_block_scan(int v, int* wsum, int* total) {
 }
 
 // ONE workgroup.  Rows i < count of z [n_cap, ldz] are the batch's logits (row i = node node_idx[i]); the training rows are those
-// with train_mask[node_idx[i]] != 0, T of them.  CE (labels int64[N]): loss = sum_train (lse - z[y]) / T,
+// with train_mask[node_idx[i]] != 0, T of them.  CE (labels int64[N]): loss = sum_train (log(se) - (z[y] - max)) / T,
 // g = (softmax - onehot) / T.  BCE (labels_f fp32[N, C]): loss = sum_train sum_c (max(z, 0) - z y + log1p(exp(-|z|))) / (T C),
 // g = (sigmoid(z) - y) / (T C).  Other rows (and rows >= count) get g = 0.  T = 0: loss = 0 / 0 = NaN and g = 0, as torch's
 // mean over an empty selection.  Wavefront w sums rows w, w + 16, ... in double in that order; the 16 sums are added in wavefront
@@ -428,9 +428,9 @@ __global__ __launch_bounds__(SAINT_THREADS) void saint_masked_loss_k(
             float se = 0.f;
             for (int c = lane; c < C; c += 64) se += expf(zr[c] - mx);
             se = wave_sum(se);
-            const float lse = mx + logf(se);
-            for (int c = lane; c < C; c += 64) gr[c] = (expf(zr[c] - lse) - (c == y ? 1.f : 0.f)) * inv;
-            acc += (double)(lse - zr[y]);
+            const float lse = logf(se);
+            for (int c = lane; c < C; c += 64) gr[c] = (expf((zr[c] - mx) - lse) - (c == y ? 1.f : 0.f)) * inv;
+            acc += (double)(lse - (zr[y] - mx));
         }
     }
     if (lane == 0) lsum[w] = acc;
@@ -499,7 +499,7 @@ __global__ __launch_bounds__(256) void saint_norms_k(const int64_t* __restrict__
 
 // ONE workgroup; saint_masked_loss_k with a per-node weight table w = node_norm[N], read through node_idx like train_mask
 // [PyG-recall: examples/graph_saint.py, (loss * node_norm)[train_mask].sum()].  loss = sum over the training rows i of
-// w_i * rowloss_i, NOT divided by T.  CE: rowloss = lse - z[y], g = w_i (softmax - onehot).  BCE: rowloss = the mean over the C
+// w_i * rowloss_i, NOT divided by T.  CE: rowloss = log(se) - (z[y] - max), g = w_i (softmax - onehot).  BCE: rowloss = the mean over the C
 // columns of max(z, 0) - z y + log1p(exp(-|z|)), g = w_i (sigmoid(z) - y) / C.  Other rows (and rows >= count) get g = 0.  T = 0:
 // loss = 0 and g = 0.  Same fixed summation order: wavefront w sums rows w, w + 16, ... in double, the 16 sums are added in
 // wavefront order; no float atomics.  With w = 1 / T everywhere this is saint_masked_loss_k's loss.
@@ -552,9 +552,9 @@ __global__ __launch_bounds__(SAINT_THREADS) void saint_masked_loss_weighted_k(
             float se = 0.f;
             for (int c = lane; c < C; c += 64) se += expf(zr[c] - mx);
             se = wave_sum(se);
-            const float lse = mx + logf(se);
-            for (int c = lane; c < C; c += 64) gr[c] = (expf(zr[c] - lse) - (c == y ? 1.f : 0.f)) * wi;
-            acc += (double)wi * (double)(lse - zr[y]);
+            const float lse = logf(se);
+            for (int c = lane; c < C; c += 64) gr[c] = (expf((zr[c] - mx) - lse) - (c == y ? 1.f : 0.f)) * wi;
+            acc += (double)wi * (double)(lse - (zr[y] - mx));
         }
     }
     if (lane == 0) lsum[w] = acc;

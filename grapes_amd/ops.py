@@ -2400,9 +2400,12 @@ def rowlist_gather_t_workspace_bytes(n_src: int, item_cap: int, f: int) -> int:
 
 
 def rowlist_gather_t(g, srcs, src_off, pos, dinv, chunk: int, out=None, status=None):
-    """out[j] = dinv[srcs[j]] * sum of g[pos[k]] over source j's entries (grapes_rowlist_gather_t).  g [M, f], f % 4 == 0."""
-    _chk(g, _f32, "g"); _chk(srcs, _i32, "srcs"); _chk(src_off, _i64, "src_off"); _chk(pos, _i32, "pos"); _chk(dinv, _f32, "dinv")
+    """out[j] = dinv[srcs[j]] * sum of g[pos[k]] over source j's entries (grapes_rowlist_gather_t).  g [M, f], f % 4 == 0; g may be
+    a column slice of a wider matrix (unit column stride, the row pitch a multiple of 4)."""
+    _chk(srcs, _i32, "srcs"); _chk(src_off, _i64, "src_off"); _chk(pos, _i32, "pos"); _chk(dinv, _f32, "dinv")
     _chk(status, _i32, "status", True)
+    if g.dtype != _f32 or not g.is_cuda or g.dim() != 2 or g.stride(1) != 1:
+        raise _lib.GrapesHipError("rowlist_gather_t: expected a CUDA fp32 matrix with unit column stride")
     n_src, f = srcs.numel(), g.shape[1]
     if out is None:
         out = torch.empty((n_src, f), dtype=_f32, device=g.device)

@@ -49,7 +49,8 @@ def weighted_loss(z, y, w, train, dtype=np.float64):
     """(loss, g, loss_mag, g_mag) of the normalised step's loss over the rows i with train[i]: loss = sum_i w_i rowloss_i.
     y 1-D: rowloss = lse - z[y], g = w (softmax - onehot).  y 2-D: rowloss = mean_c (max(z, 0) - z y + log1p(exp(-|z|))),
     g = w (sigmoid - y) / C.  Rows that do not train have g = 0.  dtype float32 evaluates the kernel's formulas in fp32 (the rows
-    added one after the other in fp32): the baseline of oracle/accuracy.py's criterion.  *_mag: the sums of the absolute values of
+    added one after the other in fp32; the cross-entropy rows shift first, lsm = (z - max) - log(se), so that a common offset of a
+    row costs the baseline nothing): the baseline of oracle/accuracy.py's criterion.  *_mag: the sums of the absolute values of
     the terms each output adds up (fp64 only meaningful)."""
     z = np.asarray(z).astype(dtype)
     w = np.asarray(w).astype(dtype)
@@ -65,11 +66,16 @@ def weighted_loss(z, y, w, train, dtype=np.float64):
         mx = zt.max(1)
         se = np.exp(zt - mx[:, None]).sum(1, dtype=dtype)
         lse = mx + np.log(se)
-        p = np.exp(zt - lse[:, None])
+        zy = zt[np.arange(len(rows)), yt]
+        if dtype == np.float64:
+            p = np.exp(zt - lse[:, None])
+            rl = lse - zy
+        else:       # the fp32 baseline shifts first, as the kernels and torch's log_softmax do: no rounding at the size of mx
+            lsm = (zt - mx[:, None]) - np.log(se)[:, None]
+            p = np.exp(lsm)
+            rl = -lsm[np.arange(len(rows)), yt]
         one = np.zeros_like(p)
         one[np.arange(len(rows)), yt] = 1
-        zy = zt[np.arange(len(rows)), yt]
-        rl = lse - zy
         rl_mag = np.abs(lse) + np.abs(zy)
         g[rows] = (p - one) * wt[:, None]
         gm[rows] = (p + one) * np.abs(wt)[:, None]

@@ -255,12 +255,14 @@ def test_estimate_norm_end_to_end(kind):
 
 
 # ------------------------------------------------------------------------------------------------------ the weighted loss
-def _loss_case(C, multi, seed, T0=False):
+def _loss_case(C, multi, seed, T0=False, shifted=False):
     rng = np.random.default_rng(seed)
     N, n_cap, n = 500, 96, 83
     node_idx = np.sort(rng.choice(N, n, replace=False)).astype(np.int32)
     pad = np.concatenate([node_idx, np.zeros(n_cap - n, np.int32)])
     z = (2 * rng.standard_normal((n_cap, C))).astype(np.float32)
+    if shifted:     # a common offset of -1000 or +1000 per row: softmax and row loss do not depend on it
+        z = (z + np.random.default_rng(seed + 1).choice([-1000.0, 1000.0], n_cap)[:, None]).astype(np.float32)
     y = (rng.random((N, C)) < 0.3).astype(np.float32) if multi else rng.integers(0, C, N)
     mask = np.zeros(N, bool) if T0 else rng.random(N) < 0.5
     ws = [(rng.random(N) * 3 + 0.01).astype(np.float32) for _ in range(8)]
@@ -271,11 +273,36 @@ def _loss_case(C, multi, seed, T0=False):
 @pytest.mark.parametrize("C", [7, 70])
 def test_weighted_loss_against_fp64(C, multi):
     """Loss and g against the fp64 oracle under oracle/accuracy.py's criterion, its factors unchanged.  The baseline is the
-    kernel's own formulas evaluated in numpy fp32 (NO.weighted_loss(dtype=float32)), the magnitude of an output the sum of the
+    loss's formulas evaluated in numpy fp32, shift first (NO.weighted_loss(dtype=float32)), the magnitude of an output the sum of the
     absolute values of the terms it adds up.  The loss is one number per launch, so eight weight tables are judged together."""
+    _weighted_loss_against_fp64(C, multi, False)
+
+
+@pytest.mark.parametrize("C", [7, 70])
+def test_weighted_loss_against_fp64_on_shifted_logits(C):
+    """The CE case of the test above with a common offset of +-1000 added to every row, and saint_masked_loss_k (no weights) on the
+    same logits.  A row written lse = max + log(se), p = exp(z - lse) rounds lse at the size of the offset and carries 2^-24 * 1000
+    into every p (grapes_rowlist_loss in that order: about 100 times the baseline's rms error of g); the kernels form
+    (z - max) - log(se), as the baseline does."""
+    _weighted_loss_against_fp64(C, False, True)
+    from grapes_amd import ops
+    N, n_cap, n, pad, z, y, mask, _ = _loss_case(C, False, 10 * C, shifted=True)
+    train = np.concatenate([mask[pad[:n]], np.zeros(n_cap - n, bool)])
+    w = np.full(n_cap, F32(1) / F32(train.sum()), np.float32)
+    lm, gm = ops.saint_masked_loss(torch.from_numpy(z).cuda(), C, torch.from_numpy(pad).cuda(),
+                                   torch.tensor([n], dtype=torch.int32, device="cuda"), torch.from_numpy(mask).cuda(),
+                                   torch.from_numpy(y).cuda())
+    yl = np.concatenate([y[pad[:n]], y[pad[n:]]])
+    rl, rg, ml, mg = NO.weighted_loss(z, yl, w, train)
+    _, bg, _, _ = NO.weighted_loss(z, yl, w, train, dtype=np.float32)
+    assert_fp32_accuracy(gm.cpu().numpy(), rg, mg, bg, f"masked loss g C={C} shifted")
+    assert abs(float(lm.item()) - rl) <= 4 * 2.0 ** -24 * ml, (float(lm.item()), rl)          # one number: 4 ulp of its magnitude
+
+
+def _weighted_loss_against_fp64(C, multi, shifted):
     _cuda()
     from grapes_amd import ops
-    N, n_cap, n, pad, z, y, mask, ws = _loss_case(C, multi, 10 * C + multi)
+    N, n_cap, n, pad, z, y, mask, ws = _loss_case(C, multi, 10 * C + multi, shifted=shifted)
     zd, yd, md = torch.from_numpy(z).cuda(), torch.from_numpy(y).cuda(), torch.from_numpy(mask).cuda()
     idx, cnt = torch.from_numpy(pad).cuda(), torch.tensor([n], dtype=torch.int32, device="cuda")
     train = np.concatenate([mask[pad[:n]], np.zeros(n_cap - n, bool)])
@@ -292,8 +319,9 @@ def test_weighted_loss_against_fp64(C, multi):
         got_l.append(float(loss.item())); ref_l.append(rl); mag_l.append(ml); base_l.append(float(bl))
         if k == 0:
             assert g.shape == (n_cap, C) and not g.cpu().numpy()[~train].any()
-            assert_fp32_accuracy(g.cpu().numpy(), rg, mg, bg, f"weighted loss g C={C} multi={multi}")
-    assert_fp32_accuracy(np.array(got_l), np.array(ref_l), np.array(mag_l), np.array(base_l), f"weighted loss C={C} multi={multi}")
+            assert_fp32_accuracy(g.cpu().numpy(), rg, mg, bg, f"weighted loss g C={C} multi={multi}" + " shifted" * shifted)
+    assert_fp32_accuracy(np.array(got_l), np.array(ref_l), np.array(mag_l), np.array(base_l),
+                         f"weighted loss C={C} multi={multi}" + " shifted" * shifted)
 
 
 @pytest.mark.parametrize("multi", [False, True])
