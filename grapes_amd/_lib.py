@@ -87,6 +87,11 @@ SIGNATURES = {
     "grapes_ladies_importance": (I32, [P, P, P, I32, P, I32, P, P, I32, P, P, P, P, P, P]),
     "grapes_ladies_layer_workspace_bytes": (SZ, [I32]),
     "grapes_ladies_layer": (I32, [P, P, I32, P, I32, P, P, P, I32, P, P, P, P, P, P, P]),
+    # AS-GCN adaptive layer-wise sampler
+    "grapes_asgcn_importance": (I32, [P, P, P, I32, P, I32, P, P, I32, P, P, I64, I32] + [P] * 10 + [P]),
+    "grapes_asgcn_rows_workspace_bytes": (SZ, [I32, I32]),
+    "grapes_asgcn_variance": (I32, [P, P, P, I32, P, I32, P, I32, I32, P, P, P, P, P, P]),
+    "grapes_asgcn_logq_bwd": (I32, [P, P, P, P, I32, P, I32, I32, P, P, P, P]),
     # GATConv aggregation (modules/gcn.py:45-72)
     "grapes_gat_scores": (I32, [P, P, P, P, P, I32, P, I32, P]),
     "grapes_gat_aggregate_workspace_bytes": (SZ, [I32, I32]),

@@ -14,8 +14,8 @@ the project's GCN, the two baselines of the reference's analysis/significance.py
   follow the LADIES script's defaults [LADIES-recall]; --num_layers 2 (theirs is 5: the project's GCN shape is two layers),
   --eval_frequency 1, --dropout 0, --runs 1, --seed, --e_cap (a layer's entry capacity; automatic by default).  An epoch is one pass
   over a permutation of the training nodes in batches of --batch_size (their script draws --batch_num batches per epoch instead).
-* Not built: LADIES' own SuGCN head (their extra linear classifier), a captured (hipGraph) step, partitioned / multi-GPU forms,
-  AS-GCN.
+* Not built: LADIES' own SuGCN head (their extra linear classifier), a captured (hipGraph) step, partitioned / multi-GPU forms.
+  AS-GCN, the adaptive layer-wise sampler, is grapes_amd.asgcn.
 
 Datasets as in grapes_amd.main: a synthetic stand-in by name, or `module:function`.
 """
@@ -62,10 +62,11 @@ def weighted_structures(edge_index, n: int):
     return out
 
 
-def layerwise_gcn(model: GCN, x, structures, edge_weight):
+def layerwise_gcn(model: GCN, x, structures, edge_weight, tap=None):
     """GCN.forward's routing (hidden layer i on [-i], the last layer on [0]) with every layer as _WeightedGCNConvFn in
     WGCN_UNNORMALIZED mode; structures / edge_weight hold one entry per layer.  A layer without an entry (FastGCN drew no
-    neighbour of its rows) outputs its bias."""
+    neighbour of its rows) outputs its bias.  tap: a list that receives the input of the last layer (grapes_amd.asgcn's variance
+    term transforms it)."""
     n_layers = len(model.gcn_layers)
     if len(structures) != n_layers or len(edge_weight) != n_layers:
         raise ValueError(f"layerwise_gcn: {n_layers} layers take {n_layers} structures and weight vectors")
@@ -73,6 +74,8 @@ def layerwise_gcn(model: GCN, x, structures, edge_weight):
         last = i == n_layers - 1
         k = 0 if last else -(i + 1)
         ws, w = structures[k], edge_weight[k]
+        if last and tap is not None:
+            tap.append(x)
         if ws is None:
             x = layer.bias.unsqueeze(0).expand(x.shape[0], -1).contiguous()
             x = x if last else torch.relu(x)

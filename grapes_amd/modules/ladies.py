@@ -119,6 +119,19 @@ class LayerWiseSampler:
             self._arange = torch.arange(self.graph.num_nodes, dtype=torch.int32, device=self.graph.device)
         return self._arange
 
+    # ------------------------------------------------------------------ what a subclass with another importance replaces
+    def _importance(self, cand, m: int):
+        """(pi, logit, further per-layer fields) over the candidates of a layer whose m rows are marked in prev_bits; pi is also
+        written to pi_table, which the layer's weights read."""
+        g = self.graph
+        pi, logit = ops.ladies_importance(g.rowptr, self.rowptr_t, self.col_t, g.num_nodes, ids=cand, prev_bits=g.prev_bits, m=m,
+                                          pi_table=self.pi_table, status=self.status)
+        return pi, logit, {}
+
+    def _batch_fields(self, node_idx, layers) -> dict:
+        """Further fields of the batch's namespace (node_map holds node_idx's ranks when this is called)."""
+        return {}
+
     # ------------------------------------------------------------------ one batch
     def sample(self, targets, uniforms=None) -> SimpleNamespace:
         """targets: node ids (any integer tensor; taken in the given order).  uniforms: per layer one fp32 tensor with at least as
@@ -149,13 +162,12 @@ class LayerWiseSampler:
                 n = int(counts[0].item())                                # the candidate count (host read)
                 cand = cand_buf[:n]
                 ops.bitmap_mark_lists(g.prev_bits, None, [(prev, None)], N, status=self.status)
-                pi, logit = ops.ladies_importance(g.rowptr, self.rowptr_t, self.col_t, N, ids=cand, prev_bits=g.prev_bits, m=m,
-                                                  pi_table=self.pi_table, status=self.status)
+                pi, logit, extra = self._importance(cand, m)
                 ops.bitmap_clear(g.prev_bits, prev)
                 sampled = self._draw(logit, cand, n, u)
                 after = self._union([sampled, targets])
             else:
-                cand, pi, logit = None, self.global_pi, self.global_logit
+                cand, pi, logit, extra = None, self.global_pi, self.global_logit, {}
                 sampled = self._draw(logit, None, N, u)
                 after = sampled
             e_cap = self.e_cap if self.e_cap is not None else max(1, min(deg_sum + m, m * after.numel()))
@@ -164,7 +176,7 @@ class LayerWiseSampler:
             ops.bitmap_clear(g.bits, after)
             e = int(d_l.item())                                          # the layer's entry count (host read)
             layers.append(SimpleNamespace(prev=prev, candidates=cand, pi=pi, logit=logit, sampled=sampled, after=after,
-                                          edge_src=src[:e], edge_dst=dst[:e], weight=w[:e]))
+                                          edge_src=src[:e], edge_dst=dst[:e], weight=w[:e], **extra))
             prev = after
         node_idx = self._union([targets] + [L.after for L in layers])     # (also node_map[id] = rank)
         edge_index = [torch.stack([ops.tensormap_map(g.node_map, L.edge_src.contiguous()),
@@ -172,7 +184,7 @@ class LayerWiseSampler:
                       else torch.zeros((2, 0), dtype=torch.int32, device=dev) for L in layers]
         return SimpleNamespace(node_idx=node_idx, num_nodes=node_idx.numel(), targets=targets,
                                local_targets=ops.tensormap_map(g.node_map, targets), edge_index=edge_index,
-                               edge_weight=[L.weight for L in layers], layers=layers)
+                               edge_weight=[L.weight for L in layers], layers=layers, **self._batch_fields(node_idx, layers))
 
     def check(self):
         """Reads the status word (synchronises); raises GrapesHipError on an edge overflow or a bad id, and clears it (and, as
@@ -183,4 +195,4 @@ class LayerWiseSampler:
             self.graph.bits.zero_(); self.graph.prev_bits.zero_()
             bits = [n for b, n in ((1, "edge buffer overflow (raise e_cap)"), (2, "node buffer overflow"), (4, "index out of range"))
                     if s & b]
-            raise ops._lib.GrapesHipError(f"{self.kind} sampler: " + ", ".join(bits))
+            raise ops._lib.GrapesHipError(f"{getattr(self, '_name', self.kind)} sampler: " + ", ".join(bits))

@@ -2692,6 +2692,93 @@ def ladies_layer(rowptr, col, num_nodes: int, rows, keep_bits, pi_table, e_cap: 
     return src, dst, w, d_e
 
 
+# ------------------------------------------------------------------------------- AS-GCN adaptive layer-wise sampler
+# [AS-GCN-recall: Huang et al., NeurIPS 2018, the layer-wise sampler with g(x(u_j))] on the LADIES conventions (grapes_hip.h).
+def asgcn_importance(rowptr, rowptr_t, col_t, num_nodes: int, x, w_g, b_g, ids=None, n=None, d_n=None, prev_bits=None, m=None,
+                     d_m=None, q_table=None, a_table=None, status=None, out=None):
+    """(c, a, q, logq, logit), fp32 [n] each, of grapes_asgcn_importance for j = ids[k] (ids None: j = k, n defaults to N):
+    c = sum over the rows i of the set of P_ij, a = <x[j], w_g> + b_g, q = c (max(a, 0) + 1), logq = logf(q),
+    logit = (logq - max logq) - 20.  x fp32 [N, F] (rows may be strided), w_g fp32 [F], b_g fp32 [1].  The set: the bitmap prev_bits
+    of m rows, or every row (prev_bits None).  q_table / a_table (fp32 [N]): also written at the candidates.  out: the five tensors
+    to write; entries past *d_n stay as they are."""
+    _chk(rowptr, _i64, "rowptr"); _chk(rowptr_t, _i64, "rowptr_t"); _chk(col_t, _i32, "col_t"); _chk(ids, _i32, "ids", True)
+    _chk(d_n, _i32, "d_n", True); _chk(prev_bits, _i64, "prev_bits", True); _chk(d_m, _i32, "d_m", True)
+    _chk(q_table, _f32, "q_table", True); _chk(a_table, _f32, "a_table", True); _chk(status, _i32, "status", True)
+    _chk(w_g, _f32, "w_g"); _chk(b_g, _f32, "b_g")
+    N, dev = int(num_nodes), rowptr.device
+    if x.dim() != 2:
+        raise ValueError("asgcn_importance: x is a matrix of one feature row per node")
+    F = int(x.shape[1])
+    ldx = _row_strided(x, F, "asgcn_importance: x")
+    if n is None:
+        n = ids.numel() if ids is not None else N
+    if m is None:
+        if prev_bits is not None:
+            raise ValueError("asgcn_importance: a bitmap comes with m, the number of rows it holds")
+        m = N
+    n, m = int(n), int(m)
+    if rowptr.numel() != N + 1 or rowptr_t.numel() != N + 1 or n < 1 or m < 1 or (ids is not None and ids.numel() < n):
+        raise ValueError("asgcn_importance: rowptr / rowptr_t hold N + 1 values, ids at least n >= 1 ids, and m >= 1")
+    if x.shape[0] < N or F < 1 or w_g.numel() != F or b_g.numel() != 1:
+        raise ValueError("asgcn_importance: x holds one row of F >= 1 features per node, w_g F values, b_g one")
+    if (prev_bits is not None and prev_bits.numel() < (N + 63) // 64) or any(t is not None and t.numel() < N for t in (q_table, a_table)):
+        raise ValueError("asgcn_importance: prev_bits holds ceil(N / 64) words, q_table and a_table one value per node")
+    if out is None:
+        out = tuple(torch.empty(n, dtype=_f32, device=dev) for _ in range(5))
+    for t, name in zip(out, ("c", "a", "q", "logq", "logit")):
+        _chk(t, _f32, name)
+        if t.numel() < n:
+            raise ValueError("asgcn_importance: c, a, q, logq and logit hold n values each")
+    c, a, q, logq, logit = out
+    _lib.check(lib().grapes_asgcn_importance(_p(rowptr), _p(rowptr_t), _p(col_t), N, _p(ids), n, _p(d_n), _p(prev_bits), m, _p(d_m),
+                                             _p(x), ldx, F, _p(w_g), _p(b_g), _p(c), _p(a), _p(q), _p(logq), _p(logit), _p(q_table),
+                                             _p(a_table), _p(status), _stream()), "asgcn_importance")
+    return c, a, q, logq, logit
+
+
+def _asgcn_entries(who, edge_src, edge_dst, weight, rows, n_local):
+    """The checks the two calls over a layer's entry list share -> (e, m, workspace)."""
+    _chk(edge_src, _i32, "edge_src"); _chk(edge_dst, _i32, "edge_dst"); _chk(weight, _f32, "weight"); _chk(rows, _i32, "rows")
+    e, m = edge_src.numel(), rows.numel()
+    if e < 1 or m < 1 or int(n_local) < 1 or edge_dst.numel() != e or weight.numel() != e:
+        raise ValueError(f"{who}: edge_src, edge_dst and weight hold the same e >= 1 entries, rows m >= 1 ids below n_local >= 1")
+    return e, m, _ws(lib().grapes_asgcn_rows_workspace_bytes(m, int(n_local)), edge_src.device)
+
+
+def asgcn_variance(edge_src, edge_dst, weight, rows, h, status=None):
+    """(V fp32 [m], L_var fp32 [1], dw fp32 [e]) of grapes_asgcn_variance over one layer's entry list in ladies_layer's order with
+    LOCAL ids (row-contiguous, rows in `rows` order): with mu_i = sum_j w_ij h[j] and s_i the row's entries,
+    V_i = s_i sum_j w_ij^2 |h_j|^2 - |mu_i|^2, L_var = mean V, dw = d L_var / d w = (2 / m)(s_i w_ij |h_j|^2 - <mu_i, h_j>).
+    h fp32 [n_local, C] is a constant of the term."""
+    _chk(h, _f32, "h"); _chk(status, _i32, "status", True)
+    n_local, C = h.shape
+    _wgcn_width(C)
+    e, m, ws = _asgcn_entries("asgcn_variance", edge_src, edge_dst, weight, rows, n_local)
+    dev = h.device
+    V, lvar, dw = torch.empty(m, dtype=_f32, device=dev), torch.empty(1, dtype=_f32, device=dev), torch.empty(e, dtype=_f32, device=dev)
+    _lib.check(lib().grapes_asgcn_variance(_p(edge_src), _p(edge_dst), _p(weight), e, _p(rows), m, _p(h), n_local, C, _p(V), _p(lvar),
+                                           _p(dw), _p(ws), _p(status), _stream()), "asgcn_variance")
+    return V, lvar, dw
+
+
+def asgcn_logq_bwd(edge_src, edge_dst, weight, grad_weight, rows, n_local: int, out=None, status=None):
+    """T fp32 [n_local] of grapes_asgcn_logq_bwd: T[j] += sum_i w_ij (G_ij - sum_j' G_ij' w_ij') over one layer's entry list (LOCAL
+    ids, ladies_layer's order, a row's sources ascending), G = grad_weight = d L / d w; d L / d logq_j = -T[j].  out: the array
+    to accumulate into (None: zeros)."""
+    _chk(grad_weight, _f32, "grad_weight"); _chk(status, _i32, "status", True)
+    e, m, ws = _asgcn_entries("asgcn_logq_bwd", edge_src, edge_dst, weight, rows, n_local)
+    if grad_weight.numel() != e:
+        raise ValueError("asgcn_logq_bwd: grad_weight holds one value per entry")
+    if out is None:
+        out = torch.zeros(int(n_local), dtype=_f32, device=edge_src.device)
+    _chk(out, _f32, "out")
+    if out.numel() < int(n_local):
+        raise ValueError("asgcn_logq_bwd: out holds one value per batch node")
+    _lib.check(lib().grapes_asgcn_logq_bwd(_p(edge_src), _p(edge_dst), _p(weight), _p(grad_weight), e, _p(rows), m, int(n_local),
+                                           _p(out), _p(ws), _p(status), _stream()), "asgcn_logq_bwd")
+    return out
+
+
 def classifier_loss(logits, local_rows, target_ids, labels, out_grad=None):
     """(loss_c [1], d loss_c / d logits [n_rows, C]) — main.py:260,267.  labels: int64 [N] or fp32 [N, C]."""
     _chk(logits, _f32, "logits"); _chk(local_rows, _i32, "local_rows"); _chk(target_ids, _i32, "target_ids")

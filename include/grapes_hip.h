@@ -62,7 +62,8 @@ extern "C" {
  * loop_idx, mode, fill), grapes_wgcn_aggregate_fwd / _bwd (mode) <- their _mode forms; grapes_saint_subgraph (edge_id, edge_norm,
  * edge_norm_b) <- its _ids form; grapes_saint_masked_loss (node_norm) <- its _weighted form; added within 303 (no signature of an
  * earlier entry point changed): the LADIES / FastGCN layer-wise samplers — grapes_ladies_importance,
- * grapes_ladies_layer(_workspace_bytes). */
+ * grapes_ladies_layer(_workspace_bytes); the AS-GCN adaptive sampler — grapes_asgcn_importance, grapes_asgcn_rows_workspace_bytes,
+ * grapes_asgcn_variance, grapes_asgcn_logq_bwd. */
 #define GRAPES_ABI_VERSION 303
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1462,6 +1463,41 @@ int grapes_ladies_importance(const int64_t* rowptr, const int64_t* rowptr_t, con
  * order.  workspace: grapes_ladies_layer_workspace_bytes(m), 4-byte aligned. */
 size_t grapes_ladies_layer_workspace_bytes(int32_t m);
 int grapes_ladies_layer(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* rows, int32_t m, const int32_t* d_m, const uint64_t* keep_bits, const float* pi_table, int32_t e_cap, int32_t* edge_src, int32_t* edge_dst, float* weight, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ AS-GCN: the adaptive layer-wise sampler and its variance loss
+ * (csrc/asgcn_kernels.hip) [AS-GCN-recall: Huang et al., "Adaptive Sampling Towards Fast Graph Representation Learning", NeurIPS
+ * 2018; the layer-wise sampler with the self-dependent function g(x(u_j))], on the LADIES conventions above (V, P, D, the set as a
+ * bitmap or every row, the transpose CSR, n / d_n, the status bits).  The sampler's parameters: w_g fp32[f], b_g fp32[1] (device).
+ * For the n candidates j = ids[k] (ids NULL: j = k), with x fp32[N, f] whose rows are ldx >= f floats apart:
+ *   c[k] = sum over the rows i of the set of P_ij (the column mass, > 0 for a candidate);  a[k] = <x_j, w_g> + b_g;
+ *   g = max(a, 0) + 1;  q[k] = c g;  logq[k] = logf(q);  logit[k] = (logq[k] - M) - 20 with M = max over the live k of logq, exactly
+ *   those two fp32 roundings: logit <= -20, where the existing draw (grapes_gumbel_topk*, mode 0) samples without replacement in
+ *   proportion to q.  q_table[j] = q[k], a_table[j] = a[k] when given (fp32[N]; only candidates are written).
+ * One wavefront per candidate: the transpose-row walk of grapes_ladies_importance (64 entries per trip, lane-strided partial sums, a
+ * butterfly, the diagonal term last) and in the same wavefront the lane-strided dot product over the feature row — 16-byte loads
+ * when f % 4 == 0, ldx % 4 == 0 and x and w_g are 16-byte aligned, scalar loads otherwise; any f >= 1.  Then one workgroup takes
+ * the maximum and writes logit: two launches, a fixed order, no atomics — two calls give the same bits.  m / d_m are accepted as
+ * grapes_ladies_importance takes them (m >= 1) and not read: the shift is the layer's maximum.  An id outside [0, N) raises
+ * GRAPES_STATUS_BAD_INDEX (c = a = q = 0, logq = logit = -inf); entries at or past *d_n are not written. */
+int grapes_asgcn_importance(const int64_t* rowptr, const int64_t* rowptr_t, const int32_t* col_t, int32_t num_nodes, const int32_t* ids, int32_t n, const int32_t* d_n, const uint64_t* prev_bits, int32_t m, const int32_t* d_m, const float* x, int64_t ldx, int32_t f, const float* w_g, const float* b_g, float* c, float* a, float* q, float* logq, float* logit, float* q_table, float* a_table, int32_t* status, grapes_stream_t stream);
+/* The two calls below run over ONE layer's entry list in grapes_ladies_layer's order with LOCAL ids (the batch's ranks, below
+ * n_local): e entries (edge_src[t] = j, edge_dst[t] = i, weight[t] = w_ij), row-contiguous, a row's sources ascending, and
+ * rows int32[m] = the layer's rows in the list's order (distinct; a row may have no entry).  A small launch of their own finds each
+ * row's offsets from the runs of edge_dst (not from a WeightedStructure's CSR, where the diagonal entry is no entry): the diagonal
+ * is an ordinary entry here.  An id outside [0, n_local), or a target that is none of the rows, raises GRAPES_STATUS_BAD_INDEX and
+ * is left out.  workspace: grapes_asgcn_rows_workspace_bytes(m, n_local), 4-byte aligned.
+ * The variance term over h fp32[n_local, c] (the layer's transformed input, a constant here), s_i = the entries of row i:
+ *   mu_i = sum_j w_ij h_j;  v[r] = s_i sum_j w_ij^2 |h_j|^2 - |mu_i|^2 (0 for a row without an entry);  l_var[0] = (sum_r v[r]) / m
+ *   in a fixed order;  dw[t] = (2 / m) (s_i w_ij |h_j|^2 - <mu_i, h_j>), the gradient of l_var by the weights.
+ * Widths: any c <= 256, multiples of 4 up to 1024.  One wavefront per row whatever its length, looping in batches: a first sweep
+ * for mu_i, a second for the entries; lanes are (entry slot, channel) so that a narrow h fills the wavefront.  Four launches. */
+size_t grapes_asgcn_rows_workspace_bytes(int32_t m, int32_t n_local);
+int grapes_asgcn_variance(const int32_t* edge_src, const int32_t* edge_dst, const float* weight, int32_t e, const int32_t* rows, int32_t m, const float* h, int32_t n_local, int32_t c, float* v, float* l_var, float* dw, void* workspace, int32_t* status, grapes_stream_t stream);
+/* d L / d logq from g[t] = d L / d w_ij: Gbar_i = sum_j g_ij w_ij per row, then t[j] += sum over the rows i, in the list's row order,
+ * of w_ij (g_ij - Gbar_i) for every j < n_local (t fp32[n_local] is accumulated into: one array serves every layer of a batch);
+ * d L / d logq_j = -t[j].  One wavefront per row for the means, one per column for the sums (lane l takes the rows l, l + 64, ...
+ * and finds j in each by a binary search): a fixed order, no float atomics.  Four launches. */
+int grapes_asgcn_logq_bwd(const int32_t* edge_src, const int32_t* edge_dst, const float* weight, const float* g, int32_t e, const int32_t* rows, int32_t m, int32_t n_local, float* t, void* workspace, int32_t* status, grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:
