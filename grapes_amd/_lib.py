@@ -92,6 +92,12 @@ SIGNATURES = {
     "grapes_asgcn_rows_workspace_bytes": (SZ, [I32, I32]),
     "grapes_asgcn_variance": (I32, [P, P, P, I32, P, I32, P, I32, I32, P, P, P, P, P, P]),
     "grapes_asgcn_logq_bwd": (I32, [P, P, P, P, I32, P, I32, I32, P, P, P, P]),
+    # GraphSAGE: node-wise neighbour sampler, SAGEConv aggregation
+    "grapes_sage_sample_layer_workspace_bytes": (SZ, [I32]),
+    "grapes_sage_sample_layer": (I32, [P, P, I32, P, I32, P, I32, P, I64, U64, U64, P, I32, P, P, P, P, P, P, P]),
+    "grapes_sage_aggregate_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_sage_aggregate_fwd": (I32, [P, I64, P, I64, P, P, P, P, I32, I32, P, I64, P, I64, I32, P, I32, P, P, I32, P, P, P]),
+    "grapes_sage_aggregate_bwd": (I32, [P, I64, P, I64, P, P, P, P, I32, P, I64, P, I64, P, I64, P, I32, P, I32, P, P, I32, P, P, P]),
     # GATConv aggregation (modules/gcn.py:45-72)
     "grapes_gat_scores": (I32, [P, P, P, P, P, I32, P, I32, P]),
     "grapes_gat_aggregate_workspace_bytes": (SZ, [I32, I32]),

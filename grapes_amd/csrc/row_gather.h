@@ -75,6 +75,31 @@ __device__ __forceinline__ void row_store(float* __restrict__ base, long long ro
     }
 }
 
+// the same slabs of a matrix whose rows are ld >= F floats apart (a column block of a wider matrix: sage_kernels.hip); with
+// VEC == 4 the base is 16-byte aligned and ld % 4 == 0
+template <int VEC, int LPR, int NS>
+__device__ __forceinline__ void row_load_ld(const float* __restrict__ base, long long row, long long ld, int F, int l,
+                                            float (&r)[NS][VEC]) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int f = (s * LPR + l) * VEC;
+        if (f < F) vec_load<VEC>(base + row * ld + f, r[s]);
+        else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) r[s][v] = 0.f;
+        }
+    }
+}
+template <int VEC, int LPR, int NS>
+__device__ __forceinline__ void row_store_ld(float* __restrict__ base, long long row, long long ld, int F, int l,
+                                             const float (&r)[NS][VEC]) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int f = (s * LPR + l) * VEC;
+        if (f < F) vec_store<VEC>(base + row * ld + f, r[s]);
+    }
+}
+
 // the live length of a long-row item list: the device count, at most the list's capacity
 __device__ __forceinline__ int item_count(const int32_t* __restrict__ d_n_items, int item_cap) {
     const int n_items = *d_n_items;

@@ -1,0 +1,619 @@
+// GraphSAGE [Hamilton et al., NeurIPS 2017; PyG-recall: torch_geometric 2.5.2 SAGEConv, NeighborLoader]: the node-wise uniform
+// neighbour sampler over the DeviceGraph CSR, and SAGEConv's mean / sum aggregation, forward and backward, over the CSRs
+// grapes_gcn_prepare builds.
+//
+// ---- the sampler (grapes_sage_sample_layer): for every list row r keep min(deg, fanout) of the entries of CSR row rows[r],
+// uniformly without replacement.  The rule, bit-reproducible on a CPU (tests/sage_oracle.py):
+//   off_r = the exclusive prefix over r, in list order, of deg(rows[r]);  entry t of list row r has stream position p = off_r + t;
+//   its key is keys[p] when keys are given, else raw 32-bit word p of the Philox stream (seed, off) — word p & 3 of
+//   philox4x32_10(off + p / 4, seed), as grapes_saint_draw_nodes indexes words;
+//   row r keeps the min(deg, fanout) entries with the smallest composite (key << 32) | t: unique, so a tie in the word goes to the
+//   lower position and nothing depends on scheduling;  kept entries are written for r ascending and within a row for t ascending.
+// A row with deg <= fanout keeps everything; its words are skipped all the same, so p is the same on every path.  A row listed
+// twice draws twice (its p differs).
+//
+//   sage_scan_k    ONE workgroup: the rows' degrees, both exclusive prefixes (block_excl_scan_u64), the edge count, the overflow
+//                  bit, the stream's base offset for the write kernel and its advance by ceil(sum deg / 4)
+//   sage_write_k   one wavefront per list row.  deg <= fanout: a copy.  deg <= 64: a key per lane, its rank by 64 broadcast
+//                  compares, the kept lanes compacted by a ballot.  Longer rows: a lane takes four stream positions (one Philox
+//                  call) per trip; an 8-bit radix select on the 32-bit word counts one digit per pass, of the entries that match the
+//                  prefix found so far, in a wavefront-private 256-bin LDS histogram; once the candidates (at or below the prefix)
+//                  fit 128 slots — after the first pass for a row of up to ~ 16 000 entries — one more pass lists them in order and
+//                  the row ends in registers like a short one; words that tie beyond that take four passes and a fifth that writes
+//                  word < T and the first positions with word == T.  Two to five generations of the keys: linear in deg, no sort,
+//                  nothing through global memory.  Integer arithmetic only.
+//
+// ---- the aggregation (grapes_sage_aggregate_fwd / _bwd), on the row-gather scaffold (row_gather.h):
+//   out[i] = act(s_i (sum_{j in row i} src[j] + loops[i] src[i]) + add[i] + bias),  s_i = 1 / deg_i (mean) or 1 (sum),
+//   deg_i = (rowptr[i + 1] - rowptr[i]) + loops[i]: the scale is applied ONCE per row, there is no per-edge weight; an empty row
+//   aggregates to 0.  src, add, out (and copy: copy[i] = src[i], the root operand of the aggregate-first form) have their own
+//   leading dimensions, so halves of one GEMM output are used in place.
+//   sage_rows_k / sage_chunks_k / sage_combine_k   the scaffold's three kernels
+//   sage_gate_k / sage_colsum_k    backward: g = dout gated by relu_out > 0, dadd = g, gs = s g, and the column sums of g as
+//                                  per-slab partials added in a fixed order
+// The backward propagation is the SAME gather over the by-source CSR on the pre-scaled rows gs.  No float atomics: every sum has a
+// fixed order (entry order inside a row, chunk order across work items, slab order for the bias), two runs are bit-identical.
+// No kernel waits on another workgroup.
+#include "row_gather.h"
+#include "philox.h"
+
+#define SAGE_SCAN_THREADS 1024
+#define SAGE_MAX_FANOUT 64
+#define SAGE_CAND 128                 // candidates a long row finishes in registers with (two per lane; half the histogram's LDS each for words and positions)
+#define SAGE_SLAB 128                 // rows per column-sum partial
+
+// ------------------------------------------------------------------------------------------------------------ the sampler
+
+// key of stream position p
+__device__ __forceinline__ uint32_t sage_key(const uint32_t* __restrict__ keys, long long n_keys, uint64_t seed, uint64_t off,
+                                             long long p, int32_t* status) {
+    if (keys) {
+        if (p < n_keys) return keys[p];
+        if (status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);                // (a key list shorter than the rows' entries)
+        return 0xffffffffu;
+    }
+    const Philox4 w = philox4x32_10(off + (uint64_t)(p >> 2), seed);
+    const int q = (int)(p & 3);
+    return q == 0 ? w.v[0] : (q == 1 ? w.v[1] : (q == 2 ? w.v[2] : w.v[3]));
+}
+
+// ONE workgroup.  off_p[r] = sum of deg over the list rows before r, off_e[r] = min(sum of min(deg, fanout) before r, e_cap);
+// *d_e = min(total, e_cap); *base_off = the stream offset of this call; *d_philox_offset += ceil(sum deg / 4).
+// A row id outside [0, N) counts as an empty row and raises GRAPES_STATUS_BAD_INDEX.
+__global__ __launch_bounds__(SAGE_SCAN_THREADS) void sage_scan_k(const int64_t* __restrict__ rowptr, int N,
+                                                                 const int32_t* __restrict__ rows, int m_host,
+                                                                 const int32_t* __restrict__ d_m, int fanout, int e_cap,
+                                                                 uint64_t philox_offset, uint64_t* d_philox_offset,
+                                                                 long long* __restrict__ off_p, uint64_t* __restrict__ base_off,
+                                                                 int32_t* __restrict__ off_e, int32_t* __restrict__ d_e,
+                                                                 int32_t* status) {
+    __shared__ unsigned long long lds[17];
+    const int live = eff_count(d_m, m_host);
+    const int per = (m_host + SAGE_SCAN_THREADS - 1) / SAGE_SCAN_THREADS;
+    const int lo = min((int)threadIdx.x * per, m_host), hi = min(lo + per, m_host);
+    unsigned long long sd = 0ull, sc = 0ull;
+    bool bad = false;
+    for (int r = lo; r < hi; ++r) {
+        long long deg = 0;
+        if (r < live) {
+            const int i = rows[r];
+            if ((unsigned)i < (unsigned)N) deg = (long long)(rowptr[i + 1] - rowptr[i]);
+            else bad = true;
+        }
+        if (deg < 0) deg = 0;
+        off_p[r] = deg;                                                       // (the degree, until the second loop)
+        sd += (unsigned long long)deg;
+        sc += (unsigned long long)(deg < fanout ? deg : fanout);
+    }
+    if (bad && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+    unsigned long long total_d, total_c;
+    unsigned long long run_d = block_excl_scan_u64(sd, lds, &total_d);
+    unsigned long long run_c = block_excl_scan_u64(sc, lds, &total_c);
+    for (int r = lo; r < hi; ++r) {
+        const long long deg = off_p[r];
+        off_p[r] = (long long)run_d;
+        off_e[r] = run_c < (unsigned long long)e_cap ? (int)run_c : e_cap;
+        run_d += (unsigned long long)deg;
+        run_c += (unsigned long long)(deg < fanout ? deg : fanout);
+    }
+    if (threadIdx.x == 0) {
+        *d_e = total_c < (unsigned long long)e_cap ? (int)total_c : e_cap;
+        if (total_c > (unsigned long long)e_cap && status) atomicOr(status, GRAPES_STATUS_EDGE_OVERFLOW);
+        const uint64_t base = d_philox_offset ? *d_philox_offset : philox_offset;
+        *base_off = base;
+        if (d_philox_offset) *d_philox_offset = base + (uint64_t)((total_d + 3ull) >> 2);
+    }
+}
+
+// One kept entry, t of row i, into slot p.  A column outside [0, N) raises GRAPES_STATUS_BAD_INDEX and is dropped: its slot holds -1 in
+// every array, so the list's layout does not depend on the data.
+__device__ __forceinline__ void sage_store(int p, long long t, const int32_t* __restrict__ col, int64_t a, int i, int N,
+                                           int32_t* __restrict__ edge_src, int32_t* __restrict__ edge_dst,
+                                           int64_t* __restrict__ edge_pos, int32_t* status) {
+    const int c = col[a + t];
+    const bool ok = (unsigned)c < (unsigned)N;
+    if (!ok && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+    edge_src[p] = ok ? c : -1;
+    edge_dst[p] = ok ? i : -1;
+    if (edge_pos) edge_pos[p] = ok ? (int64_t)(a + t) : (int64_t)-1;
+}
+
+// The kept lanes (one entry each), compacted behind `base` in lane order (= ascending t); nothing is written at or past e_cap.
+__device__ __forceinline__ void sage_emit(bool kept, long long t, int lane, const int32_t* __restrict__ col, int64_t a, int i, int N,
+                                          int& base, int e_cap, int32_t* __restrict__ edge_src, int32_t* __restrict__ edge_dst,
+                                          int64_t* __restrict__ edge_pos, int32_t* status) {
+    const unsigned long long bal = __ballot(kept);
+    const int p = base + __popcll(bal & ((1ull << lane) - 1ull));
+    if (kept && p < e_cap) sage_store(p, t, col, a, i, N, edge_src, edge_dst, edge_pos, status);
+    base += __popcll(bal);
+}
+
+// A lane's share of one trip over a long row: the four stream positions 4 c .. 4 c + 3 of Philox counter c = c0 + rel (one Philox
+// call), t0 + j = their positions in the row, in[j] = inside the row, kw[j] = their keys (0xffffffff outside the row).
+struct SageTrip { uint32_t kw[4]; bool in[4]; long long t0; };
+__device__ __forceinline__ void sage_trip(SageTrip& T, const uint32_t* __restrict__ keys, long long n_keys, uint64_t seed, uint64_t off,
+                                          long long P, long long deg, long long c0, long long nctr, long long rel, int32_t* status) {
+    const long long c = c0 + rel;
+    T.t0 = 4 * c - P;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) T.in[j] = rel < nctr && T.t0 + j >= 0 && T.t0 + j < deg;
+    if (keys) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) T.kw[j] = T.in[j] ? sage_key(keys, n_keys, seed, off, 4 * c + j, status) : 0xffffffffu;
+    } else {
+        const Philox4 w = philox4x32_10(off + (uint64_t)c, seed);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) T.kw[j] = T.in[j] ? w.v[j] : 0xffffffffu;
+    }
+}
+
+__global__ __launch_bounds__(256) void sage_write_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N,
+                                                    const int32_t* __restrict__ rows, int m_host, const int32_t* __restrict__ d_m,
+                                                    int fanout, const uint32_t* __restrict__ keys, long long n_keys, uint64_t seed,
+                                                    const long long* __restrict__ off_p, const uint64_t* __restrict__ base_off,
+                                                    const int32_t* __restrict__ off_e, int e_cap, int32_t* __restrict__ edge_src,
+                                                    int32_t* __restrict__ edge_dst, int64_t* __restrict__ edge_pos, int32_t* status) {
+    __shared__ int hist[4][256];
+    const int r = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+    if (r >= m_host) return;                                                  // (whole wavefronts leave)
+    if (r >= eff_count(d_m, m_host)) return;
+    const int i = rows[r];
+    if ((unsigned)i >= (unsigned)N) return;                                   // (counted as empty, the bit raised by sage_scan_k)
+    const int64_t a = rowptr[i];
+    const long long deg = (long long)(rowptr[i + 1] - a);
+    int base = off_e[r];
+    if (deg <= 0 || base >= e_cap) return;
+    const long long P = off_p[r];
+    const uint64_t off = *base_off;
+
+    if (deg <= fanout) {                                                      // keeps everything: no key is looked at
+        for (long long t0 = 0; t0 < deg && base < e_cap; t0 += 64)
+            sage_emit(t0 + lane < deg, t0 + lane, lane, col, a, i, N, base, e_cap, edge_src, edge_dst, edge_pos, status);
+        return;
+    }
+    if (deg <= 64) {                                                          // in registers: lane t holds key t
+        const int d = (int)deg;
+        const uint32_t key = lane < d ? sage_key(keys, n_keys, seed, off, P + lane, status) : 0xffffffffu;
+        int rank = 0;                                                         // entries with a smaller composite (key, t)
+        for (int s = 0; s < d; ++s) {
+            const uint32_t ks = (uint32_t)__shfl((int)key, s, 64);
+            rank += (ks < key || (ks == key && s < lane)) ? 1 : 0;
+        }
+        sage_emit(lane < d && rank < fanout, lane, lane, col, a, i, N, base, e_cap, edge_src, edge_dst, edge_pos, status);
+        return;
+    }
+    // Longer rows.  A lane takes one Philox counter per trip — four consecutive stream positions, 256 per trip — so a generation of
+    // the row's keys costs deg / 4 Philox calls.  Radix select: after pass q the top 8 (q + 1) bits of the threshold word are known
+    // (prefix), `need` = how many entries are still to be taken among those whose word matches them, and the candidates — the
+    // entries at or below the prefix on those bits — number (fanout - need) + the matching bin.  As soon as they fit SAGE_CAND slots
+    // (after ONE pass unless deg is beyond ~ 256 (SAGE_CAND - fanout) or the words tie) a collect pass lists them in t order in the
+    // histogram's LDS and the row ends in registers like a short one: two or three generations of the keys.  Words that tie beyond
+    // that take all four passes and a fifth that writes word < T and the first `need` positions with word == T.
+    int* h = hist[threadIdx.x >> 6];
+    const long long c0 = P >> 2, nctr = ((P + deg + 3) >> 2) - c0;           // the counters that cover the row's positions
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    uint32_t prefix = 0u;
+    int need = fanout;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        for (int b = lane; b < 256; b += 64) h[b] = 0;
+        __builtin_amdgcn_wave_barrier();
+        for (long long cb = 0; cb < nctr; cb += 64) {
+            SageTrip T;
+            sage_trip(T, keys, n_keys, seed, off, P, deg, c0, nctr, cb + lane, status);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (T.in[j] && ((uint64_t)T.kw[j] >> (shift + 8)) == ((uint64_t)prefix >> (shift + 8)))
+                    atomicAdd(&h[(T.kw[j] >> shift) & 255u], 1);
+        }
+        __builtin_amdgcn_wave_barrier();
+        const int b0 = h[4 * lane], b1 = h[4 * lane + 1], b2 = h[4 * lane + 2], b3 = h[4 * lane + 3];   // lane l: bins 4 l .. 4 l + 3
+        const int s4 = b0 + b1 + b2 + b3;
+        const int incl = wave_incl_scan(s4), excl = incl - s4;
+        const bool here = excl < need && need <= incl;                        // exactly one lane: 1 <= need <= the matching entries
+        int bin = 0, below = excl, cbin = b0;
+        if (need > below + b0) { below += b0; bin = 1; cbin = b1;
+            if (need > below + b1) { below += b1; bin = 2; cbin = b2;
+                if (need > below + b2) { below += b2; bin = 3; cbin = b3; } } }
+        bin += 4 * lane;
+        const unsigned long long hb = __ballot(here);
+        const int from = hb ? __ffsll((long long)hb) - 1 : 0;
+        bin = __shfl(bin, from, 64);
+        below = __shfl(below, from, 64);
+        cbin = __shfl(cbin, from, 64);
+        prefix |= (uint32_t)bin << shift;
+        need -= below;
+        __builtin_amdgcn_wave_barrier();
+        const int C = (fanout - need) + cbin;                                 // the candidates: at or below the prefix on the known bits
+        if (C > SAGE_CAND || deg >= (1ll << 31)) continue;
+        uint32_t* ckey = reinterpret_cast<uint32_t*>(h);                      // (the histogram is read: its LDS holds the candidates)
+        int* ct = h + SAGE_CAND;
+        int cn = 0;
+        for (long long cb = 0; cb < nctr; cb += 64) {
+            SageTrip T;
+            sage_trip(T, keys, n_keys, seed, off, P, deg, c0, nctr, cb + lane, status);
+            bool cand[4];
+            int before = 0, total = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                cand[j] = T.in[j] && ((uint64_t)T.kw[j] >> shift) <= ((uint64_t)prefix >> shift);
+                const unsigned long long bj = __ballot(cand[j]);
+                before += __popcll(bj & lt); total += __popcll(bj);
+            }
+            int slot = cn + before;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (cand[j]) {
+                    if (slot < SAGE_CAND) { ckey[slot] = T.kw[j]; ct[slot] = (int)(T.t0 + j); }
+                    ++slot;
+                }
+            cn += total;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (cn > SAGE_CAND) cn = SAGE_CAND;                                   // (cn == C)
+        // candidate q < cn sits in slot q, in t order: lane l ranks the candidates l and l + 64 by (word, slot)
+        const int q0 = lane, q1 = lane + 64;
+        const uint32_t k0 = q0 < cn ? ckey[q0] : 0xffffffffu, k1 = q1 < cn ? ckey[q1] : 0xffffffffu;
+        const int t0 = q0 < cn ? ct[q0] : 0, t1 = q1 < cn ? ct[q1] : 0;
+        int r0 = 0, r1 = 0;
+        for (int q = 0; q < cn; ++q) {
+            const uint32_t kq = ckey[q];                                      // (one address for the wavefront: a broadcast read)
+            r0 += (kq < k0 || (kq == k0 && q < q0)) ? 1 : 0;
+            r1 += (kq < k1 || (kq == k1 && q < q1)) ? 1 : 0;
+        }
+        sage_emit(q0 < cn && r0 < fanout, t0, lane, col, a, i, N, base, e_cap, edge_src, edge_dst, edge_pos, status);
+        sage_emit(q1 < cn && r1 < fanout, t1, lane, col, a, i, N, base, e_cap, edge_src, edge_dst, edge_pos, status);
+        return;
+    }
+    // prefix = the threshold word T; every word < T is kept (fanout - need of them) and the first `need` positions with word == T
+    int eq_seen = 0;
+    for (long long cb = 0; cb < nctr && base < e_cap; cb += 64) {
+        SageTrip T;
+        sage_trip(T, keys, n_keys, seed, off, P, deg, c0, nctr, cb + lane, status);
+        bool eq[4], kept[4];
+        int eq_before = 0, eq_total = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            eq[j] = T.in[j] && T.kw[j] == prefix;
+            const unsigned long long bj = __ballot(eq[j]);
+            eq_before += __popcll(bj & lt); eq_total += __popcll(bj);
+        }
+        int run = eq_seen + eq_before;                                        // the equal words at lower positions
+        int before = 0, total = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            kept[j] = T.in[j] && (T.kw[j] < prefix || (eq[j] && run < need));
+            run += eq[j] ? 1 : 0;
+            const unsigned long long bj = __ballot(kept[j]);
+            before += __popcll(bj & lt); total += __popcll(bj);
+        }
+        int slot = base + before;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (kept[j]) {
+                if (slot < e_cap) sage_store(slot, T.t0 + j, col, a, i, N, edge_src, edge_dst, edge_pos, status);
+                ++slot;
+            }
+        base += total;
+        eq_seen += eq_total;
+    }
+}
+
+// off_p int64[m] | base_off uint64[1] (+ 8 bytes of padding) | off_e int32[m]
+extern "C" size_t grapes_sage_sample_layer_workspace_bytes(int32_t m) {
+    return (size_t)(m > 0 ? m : 1) * 12 + 16;
+}
+
+extern "C" int grapes_sage_sample_layer(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* rows, int32_t m,
+                                        const int32_t* d_m, int32_t fanout, const uint32_t* keys, int64_t n_keys,
+                                        uint64_t philox_seed, uint64_t philox_offset, uint64_t* d_philox_offset, int32_t e_cap,
+                                        int32_t* edge_src, int32_t* edge_dst, int64_t* edge_pos, int32_t* d_e, void* workspace,
+                                        int32_t* status, grapes_stream_t stream) {
+    if (num_nodes <= 0 || m <= 0 || e_cap <= 0 || fanout < 1 || fanout > SAGE_MAX_FANOUT) return GRAPES_EINVAL;
+    if (!rowptr || !col || !rows || !edge_src || !edge_dst || !d_e || !workspace || (keys && n_keys < 0)) return GRAPES_EINVAL;
+    if ((uintptr_t)workspace & 7) return GRAPES_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    long long* off_p = (long long*)workspace;
+    uint64_t* base_off = (uint64_t*)(off_p + m);
+    int32_t* off_e = (int32_t*)(base_off + 2);
+    hipLaunchKernelGGL(sage_scan_k, dim3(1), dim3(SAGE_SCAN_THREADS), 0, s, rowptr, num_nodes, rows, m, d_m, fanout, e_cap,
+                       philox_offset, d_philox_offset, off_p, base_off, off_e, d_e, status);
+    GRAPES_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sage_write_k, dim3(grapes_div_up((int64_t)m * 64, 256)), dim3(256), 0, s, rowptr, col, num_nodes, rows, m, d_m,
+                       fanout, keys, (long long)n_keys, philox_seed, (const long long*)off_p, (const uint64_t*)base_off,
+                       (const int32_t*)off_e, e_cap, edge_src, edge_dst, edge_pos, status);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------ the aggregation
+
+template <int NS> struct SageUnroll { static constexpr int U = NS == 1 ? 4 : 2; };
+
+// acc += sum of the rows m[csr[t]], t in [beg, end), rows ld floats apart.  An index outside [0, n) raises
+// GRAPES_STATUS_BAD_INDEX and the entry is dropped (its lane loads the row itself and adds nothing, so the loads need no predicate).
+template <int VEC, int LPR, int NS>
+__device__ __forceinline__ void sage_gather(const float* __restrict__ m, long long ld, const int32_t* __restrict__ csr, int row, int n,
+                                            int beg, int end, int F, int l, float (&acc)[NS][VEC], int32_t* status) {
+    constexpr int U = SageUnroll<NS>::U;
+    for (int b = beg; b < end; b += LPR) {
+        const int c = batch_entry(csr, b + l, end, n, status);
+        const int idx = c < 0 ? row : c;
+        const int live = c < 0 ? 0 : 1;
+        const int cnt = end - b < LPR ? end - b : LPR;
+        for (int k = 0; k < cnt; k += U) {
+            float hv[U][NS][VEC];
+            int lk[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int ik = __shfl(idx, k + u, LPR);
+                lk[u] = k + u < cnt ? __shfl(live, k + u, LPR) : 0;
+                row_load_ld<VEC, LPR, NS>(m, ik, ld, F, l, hv[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+#pragma unroll
+                for (int s = 0; s < NS; ++s)
+#pragma unroll
+                    for (int v = 0; v < VEC; ++v) acc[s][v] += lk[u] ? hv[u][s][v] : 0.f;
+        }
+    }
+}
+
+// What a row's sum becomes:  out[row] = act(s (sum + loops[row] src[row]) + add[row] + bias),  s = 1 / ((end - beg) + loops[row]) when
+// mean (0 for an empty row) else 1.  add, bias and loops are optional.
+struct SageEpi {
+    const float* src; long long ld_src;
+    const float* add; long long ld_add;
+    const float* bias;
+    const int32_t* loops;
+    float* out; long long ld_out;
+    float* copy; long long ld_copy;
+    int mean, relu;
+};
+
+__device__ __forceinline__ float sage_scale(int mean, int deg) {
+    return mean ? (deg > 0 ? 1.0f / (float)deg : 0.f) : 1.f;
+}
+
+template <int VEC, int LPR, int NS>
+__device__ __forceinline__ void sage_finish(const SageEpi& e, float (&acc)[NS][VEC], int row, int cnt, int F, int l) {
+    const int lp = e.loops ? e.loops[row] : 0;
+    if (lp != 0) {
+        float xr[NS][VEC];
+        row_load_ld<VEC, LPR, NS>(e.src, row, e.ld_src, F, l, xr);
+        const float lf = (float)lp;
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(lf, xr[s][v], acc[s][v]);
+    }
+    const float sc = sage_scale(e.mean, cnt + lp);
+    float ad[NS][VEC];
+    if (e.add) row_load_ld<VEC, LPR, NS>(e.add, row, e.ld_add, F, l, ad);
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            float o = acc[s][v] * sc;
+            if (e.add) o += ad[s][v];
+            const int f = (s * LPR + l) * VEC + v;
+            if (e.bias && f < F) o += e.bias[f];
+            acc[s][v] = e.relu ? fmaxf(o, 0.f) : o;
+        }
+    row_store_ld<VEC, LPR, NS>(e.out, row, e.ld_out, F, l, acc);
+}
+
+// rows longer than GRAPES_LONG_ROW (skip_long): only the row-local copy here, the sum by sage_chunks_k / sage_combine_k
+template <int VEC, int LPR, int NS>
+__global__ __launch_bounds__(256) void sage_rows_k(SageEpi e, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ csr,
+                                                   int n_host, const int32_t* d_n, int F, int skip_long, int32_t* status) {
+    const int n = eff_count(d_n, n_host);
+    const int l = threadIdx.x % LPR, G = 256 / LPR;
+    for (int row = blockIdx.x * G + threadIdx.x / LPR; row < n; row += gridDim.x * G) {
+        const int beg = rowptr[row], end = rowptr[row + 1];
+        if (e.copy) {
+            float xr[NS][VEC];
+            row_load_ld<VEC, LPR, NS>(e.src, row, e.ld_src, F, l, xr);
+            row_store_ld<VEC, LPR, NS>(e.copy, row, e.ld_copy, F, l, xr);
+        }
+        if (skip_long && end - beg > GRAPES_LONG_ROW) continue;
+        float acc[NS][VEC];
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
+        sage_gather<VEC, LPR, NS>(e.src, e.ld_src, csr, row, n, beg, end, F, l, acc, status);
+        sage_finish<VEC, LPR, NS>(e, acc, row, end - beg, F, l);
+    }
+}
+
+// one group per work item (row, chunk): the chunk's sum -> pacc[it F]
+template <int VEC, int LPR, int NS>
+__global__ __launch_bounds__(256) void sage_chunks_k(const float* __restrict__ m, long long ld, const int32_t* __restrict__ rowptr,
+                                                     const int32_t* __restrict__ csr, int n_host, const int32_t* d_n, int F,
+                                                     const int32_t* __restrict__ items, const int32_t* __restrict__ d_n_items,
+                                                     int item_cap, float* __restrict__ pacc, int32_t* status) {
+    const int n = eff_count(d_n, n_host);
+    const int n_items = item_count(d_n_items, item_cap);
+    const int l = threadIdx.x % LPR, G = 256 / LPR;
+    for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
+        int row, beg, end;
+        float acc[NS][VEC];
+#pragma unroll
+        for (int s = 0; s < NS; ++s)
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
+        item_range(items, it, rowptr, n, row, beg, end);
+        if (beg < end) sage_gather<VEC, LPR, NS>(m, ld, csr, row, n, beg, end, F, l, acc, status);
+        row_store<VEC, LPR, NS>(pacc, it, F, l, acc);
+    }
+}
+
+// one workgroup per long row (led by its chunk-0 item), a thread per column: the items added in chunk order, then sage_finish's epilogue
+__global__ __launch_bounds__(256) void sage_combine_k(SageEpi e, const int32_t* __restrict__ rowptr, int n_host, const int32_t* d_n,
+                                                      int F, const int32_t* __restrict__ items,
+                                                      const int32_t* __restrict__ d_n_items, int item_cap,
+                                                      const float* __restrict__ pacc) {
+    const int n = eff_count(d_n, n_host);
+    const int n_items = item_count(d_n_items, item_cap);
+    for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
+        int row, nc;
+        if (!item_leads(items, it, n_items, rowptr, n, row, nc)) continue;
+        const int lp = e.loops ? e.loops[row] : 0;
+        const float sc = sage_scale(e.mean, (rowptr[row + 1] - rowptr[row]) + lp);
+        for (int f = threadIdx.x; f < F; f += 256) {
+            float a = 0.f;
+            for (int c = 0; c < nc; ++c) a += pacc[(long long)(it + c) * F + f];
+            if (lp != 0) a = fmaf((float)lp, e.src[(long long)row * e.ld_src + f], a);
+            float o = a * sc;
+            if (e.add) o += e.add[(long long)row * e.ld_add + f];
+            if (e.bias) o += e.bias[f];
+            e.out[(long long)row * e.ld_out + f] = e.relu ? fmaxf(o, 0.f) : o;
+        }
+    }
+}
+
+// Backward, row-local: g = dout gated by relu_out > 0;  dadd = g;  gs = s g (rows F floats apart);  part[slab] = the column sums of g
+// over the slab's SAGE_SLAB rows: thread (rg, column) adds the rows rg, rg + 4, ... of the slab, the four sums meet in rg order.
+// gs, dadd and part are optional.  Workgroup (x, y): 64 columns at 64 x, the slabs y, y + gridDim.y, ...
+__global__ __launch_bounds__(256) void sage_gate_k(const float* __restrict__ dout, long long ld_dout, const float* __restrict__ relu_out,
+                                                   long long ld_relu, const int32_t* __restrict__ loops,
+                                                   const int32_t* __restrict__ rowptr_t, int mean, float* __restrict__ gs,
+                                                   float* __restrict__ dadd, long long ld_dadd, float* __restrict__ part, int n_host,
+                                                   const int32_t* d_n, int F) {
+    __shared__ float red[4][64];
+    const int n = eff_count(d_n, n_host);
+    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6, f = blockIdx.x * 64 + cl;
+    const int slabs = (n_host + SAGE_SLAB - 1) / SAGE_SLAB;
+    for (int slab = blockIdx.y; slab < slabs; slab += gridDim.y) {
+        const int r0 = slab * SAGE_SLAB, r1 = min(r0 + SAGE_SLAB, n);
+        float acc = 0.f;
+        for (int row = r0 + rg; row < r1; row += 4) {
+            float sc = 1.f;
+            if (mean) sc = sage_scale(1, (rowptr_t[row + 1] - rowptr_t[row]) + (loops ? loops[row] : 0));
+            if (f < F) {
+                float g = dout[(long long)row * ld_dout + f];
+                if (relu_out && !(relu_out[(long long)row * ld_relu + f] > 0.f)) g = 0.f;
+                if (dadd) dadd[(long long)row * ld_dadd + f] = g;
+                if (gs) gs[(long long)row * F + f] = sc * g;
+                acc += g;
+            }
+        }
+        if (part) {                                                           // (workgroup-uniform)
+            red[rg][cl] = acc;
+            __syncthreads();
+            if (rg == 0 && f < F) part[(long long)slab * F + f] = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
+            __syncthreads();
+        }
+    }
+}
+// one wavefront per column: lane l adds the partials l, l + 64, ... in that order, then a butterfly over the lanes
+__global__ __launch_bounds__(256) void sage_colsum_k(const float* __restrict__ part, int slabs, int F, float* __restrict__ dbias) {
+    const int f = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
+    if (f >= F) return;
+    float a = 0.f;
+    for (int b = l; b < slabs; b += 64) a += part[(long long)b * F + f];
+    a = wave_sum(a);
+    if (l == 0) dbias[f] = a;
+}
+
+// ------------------------------------------------------------------------------------------------------------ host side
+
+// 0: float4 columns, 1: scalar columns, negative: not covered
+static inline int sage_shape(int f, bool aligned) {
+    if (f < 1) return GRAPES_EINVAL;
+    if (f % 4 == 0 && aligned) return f <= 1024 ? 0 : GRAPES_EINVAL;
+    if (f <= 256) return 1;
+    return f % 4 == 0 && f <= 1024 ? GRAPES_EALIGN : GRAPES_EINVAL;
+}
+static inline bool sage_vec_ok(const void* p, int64_t ld) { return !p || (grapes_aligned16(p) && ld % 4 == 0); }
+
+// the launches of a gather over (rowptr, csr): rows, and for long rows chunks + combine
+static int sage_propagate(const SageEpi& epi, const int32_t* rowptr, const int32_t* csr, int32_t n, const int32_t* d_n, int32_t f,
+                          bool vec, const int32_t* items, const int32_t* d_n_items, int32_t item_cap, float* pacc, int32_t* status,
+                          hipStream_t s) {
+    const int skip = (items && d_n_items && pacc && item_cap > 0) ? 1 : 0;
+    ROW_LAUNCH(sage_rows_k, 4, vec, f, n, s, epi, rowptr, csr, n, d_n, f, skip, status);
+    if (skip) {
+        ROW_LAUNCH(sage_chunks_k, 4, vec, f, item_cap, s, epi.src, epi.ld_src, rowptr, csr, n, d_n, f, items, d_n_items, item_cap, pacc,
+                   status);
+        const int g2 = item_cap < 2048 ? item_cap : 2048;
+        hipLaunchKernelGGL(sage_combine_k, dim3(g2), dim3(256), 0, s, epi, rowptr, n, d_n, f, items, d_n_items, item_cap,
+                           (const float*)pacc);
+        GRAPES_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+static inline size_t sage_slabs(int32_t n) { return n > 0 ? ((size_t)n + SAGE_SLAB - 1) / SAGE_SLAB : 0; }
+
+// workspace: [pacc item_cap f] [gs n f] [part slabs f]
+extern "C" size_t grapes_sage_aggregate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f) {
+    const size_t N = n > 0 ? (size_t)n : 0, I = item_cap > 0 ? (size_t)item_cap : 0, F = f > 0 ? (size_t)f : 1;
+    return grapes_round16(I * F * sizeof(float)) + grapes_round16(N * F * sizeof(float)) +
+           grapes_round16(sage_slabs(n) * F * sizeof(float)) + 16;
+}
+
+extern "C" int grapes_sage_aggregate_fwd(const float* src, int64_t ld_src, const float* add, int64_t ld_add, const float* bias,
+                                         const int32_t* loops, const int32_t* rowptr_t, const int32_t* csr_src, int32_t mean,
+                                         int32_t relu, float* out, int64_t ld_out, float* copy_out, int64_t ld_copy, int32_t n,
+                                         const int32_t* d_n, int32_t f, const int32_t* long_items, const int32_t* d_n_items,
+                                         int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream) {
+    if (!src || !rowptr_t || !csr_src || !out || n < 0 || f < 1) return GRAPES_EINVAL;
+    if (ld_src < f || ld_out < f || (add && ld_add < f) || (copy_out && ld_copy < f)) return GRAPES_EINVAL;
+    if (out == src || copy_out == src || (copy_out && copy_out == out)) return GRAPES_EINVAL;
+    const bool use_items = long_items && d_n_items && workspace && item_cap > 0;
+    if (use_items && !grapes_aligned16(workspace)) return GRAPES_EALIGN;
+    const int shape = sage_shape(f, sage_vec_ok(src, ld_src) && sage_vec_ok(add, ld_add) && sage_vec_ok(out, ld_out) &&
+                                    sage_vec_ok(copy_out, ld_copy) && (!bias || grapes_aligned16(bias)));
+    if (shape < 0) return shape;
+    if (n == 0) return 0;
+    SageEpi epi;
+    epi.src = src; epi.ld_src = ld_src; epi.add = add; epi.ld_add = ld_add; epi.bias = bias; epi.loops = loops;
+    epi.out = out; epi.ld_out = ld_out; epi.copy = copy_out; epi.ld_copy = ld_copy; epi.mean = mean ? 1 : 0; epi.relu = relu ? 1 : 0;
+    return sage_propagate(epi, rowptr_t, csr_src, n, d_n, f, shape == 0, use_items ? long_items : nullptr, d_n_items, item_cap,
+                          (float*)workspace, status, (hipStream_t)stream);
+}
+
+extern "C" int grapes_sage_aggregate_bwd(const float* dout, int64_t ld_dout, const float* relu_out, int64_t ld_relu,
+                                         const int32_t* loops, const int32_t* rowptr_t, const int32_t* rowptr_s,
+                                         const int32_t* csr_dst, int32_t mean, const float* add, int64_t ld_add, float* dsrc,
+                                         int64_t ld_dsrc, float* dadd, int64_t ld_dadd, float* dbias, int32_t n, const int32_t* d_n,
+                                         int32_t f, const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap,
+                                         void* workspace, int32_t* status, grapes_stream_t stream) {
+    if (!dout || !rowptr_t || n < 0 || f < 1 || ld_dout < f) return GRAPES_EINVAL;
+    if (dsrc && (!rowptr_s || !csr_dst || ld_dsrc < f || dsrc == dout || dsrc == dadd)) return GRAPES_EINVAL;
+    if ((relu_out && ld_relu < f) || (add && ld_add < f) || (dadd && (ld_dadd < f || dadd == dout))) return GRAPES_EINVAL;
+    const bool pass = mean || relu_out || dadd || dbias;                      // the row-local pass; without it dsrc gathers dout itself
+    const bool use_items = dsrc && items_s && d_n_items_s && item_cap > 0;
+    if ((pass || use_items) && !workspace) return GRAPES_EINVAL;
+    if (workspace && !grapes_aligned16(workspace)) return GRAPES_EALIGN;
+    const bool src_ok = pass ? true : sage_vec_ok(dout, ld_dout);
+    const int shape = sage_shape(f, src_ok && sage_vec_ok(add, ld_add) && sage_vec_ok(dsrc, ld_dsrc));
+    if (shape < 0) return shape;
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t I = item_cap > 0 ? (size_t)item_cap : 0;
+    float* pacc = (float*)workspace;
+    float* gs = workspace ? (float*)((char*)workspace + grapes_round16(I * f * sizeof(float))) : nullptr;
+    float* part = workspace ? (float*)((char*)gs + grapes_round16((size_t)n * f * sizeof(float))) : nullptr;
+    if (pass) {
+        const int slabs = (int)sage_slabs(n);
+        const dim3 grid(grapes_div_up(f, 64), slabs < 4096 ? slabs : 4096);
+        hipLaunchKernelGGL(sage_gate_k, grid, dim3(256), 0, s, dout, (long long)ld_dout, relu_out, (long long)ld_relu, loops, rowptr_t,
+                           mean ? 1 : 0, dsrc ? gs : (float*)nullptr, dadd, (long long)ld_dadd, dbias ? part : (float*)nullptr, n, d_n,
+                           f);
+        GRAPES_LAUNCH_CHECK();
+        if (dbias) {
+            hipLaunchKernelGGL(sage_colsum_k, dim3(grapes_div_up(f, 4)), dim3(256), 0, s, (const float*)part, slabs, f, dbias);
+            GRAPES_LAUNCH_CHECK();
+        }
+    }
+    if (!dsrc) return 0;
+    SageEpi epi;
+    epi.src = pass ? gs : dout; epi.ld_src = pass ? f : ld_dout; epi.add = add; epi.ld_add = ld_add; epi.bias = nullptr;
+    epi.loops = loops; epi.out = dsrc; epi.ld_out = ld_dsrc; epi.copy = nullptr; epi.ld_copy = 0; epi.mean = 0; epi.relu = 0;
+    return sage_propagate(epi, rowptr_s, csr_dst, n, d_n, f, shape == 0, use_items ? items_s : nullptr, d_n_items_s, item_cap, pacc,
+                          status, s);
+}

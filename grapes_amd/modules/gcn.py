@@ -951,8 +951,181 @@ class PNA(nn.Module):
         return self.conv[n_conv - 1](x, edges)
 
 
+# ------------------------------------------------------------------------------------------------ GraphSAGE (PyG SAGEConv)
+class _SAGEConvFn(torch.autograd.Function):
+    """out = act(W_l aggr_{j -> i} x_j + W_r x_i + b), aggr = mean or sum — both linear, so either operand form computes it:
+      transform-first   H = x [W_l ; W_r]ᵀ in ONE GEMM ([n, 2 out]), then grapes_sage_aggregate_fwd gathers the left half with the
+                        right half, the bias and the ReLU in its epilogue; backward: the gated gather of dout over the by-source
+                        CSR into the left half of dH with g in its right half, then dW = dHᵀ x and dx = dH W, one GEMM each.
+      aggregate-first   Z = [aggr x | x] from one gather of x itself ([n, 2 in]), then ONE GEMM act(Z [W_l | W_r]ᵀ + b);
+                        backward: dW and db from one gated GEMM, dZ = g W, dx = the gather of dZ's left half plus its right half.
+    Saved: x or Z, the stacked weight and, with ReLU, the output; nothing of size e."""
+
+    @staticmethod
+    def forward(ctx, x, w_l, w_r, bias, prep, aggr, relu, agg_first, long_rows):
+        d_n, n = prep.d_n, x.shape[0]
+        f_out, f_in = w_l.shape
+        ctx.prep, ctx.aggr, ctx.relu, ctx.agg_first, ctx.root, ctx.long_rows = prep, aggr, relu, agg_first, w_r is not None, long_rows
+        ctx.f_in, ctx.f_out = f_in, f_out
+        if agg_first:
+            if w_r is not None:
+                z = torch.empty((n, 2 * f_in), dtype=torch.float32, device=x.device)
+                ops.sage_aggregate_fwd(x, prep, aggr, out=z[:, :f_in], copy_out=z[:, f_in:], long_rows=long_rows)
+                w = torch.cat([w_l, w_r], 1)                                   # [W_l | W_r]: [out, 2 in]
+            else:
+                z, w = ops.sage_aggregate_fwd(x, prep, aggr, long_rows=long_rows), w_l
+            out = ops.linear_bias_act_fwd(z, w, bias, relu, d_n=d_n)
+            ctx.save_for_backward(z, w, out if relu else None)
+            return out
+        w = torch.cat([w_l, w_r], 0) if w_r is not None else w_l               # [W_l ; W_r]: [2 out, in]
+        h = ops.linear_fwd(x, w, d_n=d_n)
+        out = ops.sage_aggregate_fwd(h[:, :f_out], prep, aggr, add=h[:, f_out:] if w_r is not None else None, bias=bias, relu=relu,
+                                     long_rows=long_rows)
+        ctx.save_for_backward(x, w, out if relu else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        a, w, out = ctx.saved_tensors
+        prep, d_n, f_in, f_out = ctx.prep, ctx.prep.d_n, ctx.f_in, ctx.f_out
+        dout = dout.contiguous()
+        want_b = ctx.needs_input_grad[3]
+        if ctx.agg_first:
+            dw, dbias = ops.linear_bwd_weight_gated(dout, a, gate=out if ctx.relu else None, d_n=d_n, want_bias=want_b)
+            dx = None
+            if ctx.needs_input_grad[0]:
+                g = ops.gcn2_mix_bwd(dout, out, True, 1.0, d_n=d_n)[0] if ctx.relu else dout
+                dz = ops.linear_bwd_input(g, w, d_n=d_n)
+                dx = ops.sage_aggregate_bwd(dz[:, :f_in], prep, ctx.aggr, add=dz[:, f_in:] if ctx.root else None,
+                                            long_rows=ctx.long_rows)[0]
+            dw_l, dw_r = (dw[:, :f_in].contiguous(), dw[:, f_in:].contiguous()) if ctx.root else (dw, None)
+            return dx, dw_l, dw_r, dbias if want_b else None, None, None, None, None, None
+        dh = torch.empty((dout.shape[0], w.shape[0]), dtype=torch.float32, device=dout.device)
+        _, _, dbias = ops.sage_aggregate_bwd(dout, prep, ctx.aggr, relu_out=out if ctx.relu else None, dsrc=dh[:, :f_out],
+                                             dadd=dh[:, f_out:] if ctx.root else None, want_bias=want_b, long_rows=ctx.long_rows)
+        dw = ops.linear_bwd_weight(dh, a, d_n=d_n)
+        dx = ops.linear_bwd_input(dh, w, d_n=d_n) if ctx.needs_input_grad[0] else None
+        dw_l, dw_r = (dw[:f_out], dw[f_out:]) if ctx.root else (dw, None)
+        return dx, dw_l, dw_r, dbias, None, None, None, None, None
+
+
+def _sage_graph(edge_index, n: int) -> ops.PreparedGraph:
+    """The layer's graph with its stored-self-loop counts (SAGEConv aggregates the adjacency as stored, like GCN2Conv and PNAConv)."""
+    _refuse_large(edge_index, "SAGE")
+    return _gcn2_graph(edge_index, n)
+
+
+class _SAGELin(nn.Module):
+    """The parameters of one of SAGEConv's two linear maps under PyG's names: `weight` [out, in] and, for lin_l, `bias`."""
+
+    def __init__(self, in_channels: int, out_channels: int, bias: bool):
+        super().__init__()
+        self.in_channels = in_channels
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels))
+        if bias:
+            self.bias = nn.Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))                 # [PyG-recall: Linear's default, as nn.Linear]
+        if self.bias is not None:
+            bound = 1.0 / math.sqrt(self.in_channels) if self.in_channels > 0 else 0.0
+            nn.init.uniform_(self.bias, -bound, bound)
+
+
+class SAGEConv(nn.Module):
+    """PyG SAGEConv(in_channels, out_channels, aggr="mean" | "sum", root_weight=True, bias=True) [PyG-recall: torch_geometric 2.5.2]:
+    out_i = W_l aggr_{j -> i} x_j + W_r x_i + b, keys `lin_l.weight`, `lin_l.bias`, `lin_r.weight` (absent with root_weight=False).
+    The adjacency is used as stored: duplicates by multiplicity, stored loops are ordinary neighbours, none added; a node without a
+    neighbour aggregates 0.  Not built: aggr="max" / "lstm", project=True, normalize=True, the bipartite (x_src, x_dst) call.
+
+    The operand form is chosen by width (both compute the same map, see _SAGEConvFn): aggregate-first when in_channels <
+    out_channels and in_channels is a width the gather is built for (any up to 256, multiples of 4 up to 1024) — the gather then
+    moves the narrower rows; transform-first otherwise, which needs out_channels to be such a width.  forward's private `_form`
+    ("transform" / "aggregate") forces one; `_long_rows` is ops.sage_aggregate_fwd's long_rows."""
+
+    def __init__(self, in_channels: int, out_channels: int, aggr: str = "mean", normalize: bool = False, root_weight: bool = True,
+                 project: bool = False, bias: bool = True):
+        super().__init__()
+        if aggr not in ops.SAGE_AGGRS:
+            raise NotImplementedError(f"SAGEConv: aggr={aggr!r} is not built (built: {', '.join(ops.SAGE_AGGRS)}; max is not linear "
+                                      "and needs its own gather)")
+        if normalize or project:
+            raise NotImplementedError("SAGEConv: normalize=True and project=True are not built")
+        if int(in_channels) < 1 or int(out_channels) < 1:
+            raise ValueError("SAGEConv: in_channels and out_channels are at least 1")
+        self.in_channels, self.out_channels, self.aggr, self.root_weight = int(in_channels), int(out_channels), aggr, bool(root_weight)
+        if not self.form_ok("transform") and not self.form_ok("aggregate"):
+            raise ValueError(f"SAGEConv: {in_channels} -> {out_channels} is not built: the gather takes any width up to 256 and "
+                             "multiples of 4 up to 1024 (out_channels, or in_channels when it is the smaller)")
+        self.lin_l = _SAGELin(self.in_channels, self.out_channels, bias)
+        if root_weight:
+            self.lin_r = _SAGELin(self.in_channels, self.out_channels, False)
+        else:
+            self.register_module("lin_r", None)
+
+    def reset_parameters(self):
+        self.lin_l.reset_parameters()
+        if self.lin_r is not None:
+            self.lin_r.reset_parameters()
+
+    def form_ok(self, form: str) -> bool:
+        """Whether an operand form can run these widths (aggregate-first also needs two output columns for its fused GEMM)."""
+        if form == "aggregate":
+            return ops.sage_width_ok(self.in_channels) and self.out_channels >= 2
+        return ops.sage_width_ok(self.out_channels)
+
+    def default_form(self) -> str:
+        if self.in_channels < self.out_channels and self.form_ok("aggregate"):
+            return "aggregate"
+        return "transform" if self.form_ok("transform") else "aggregate"
+
+    def forward(self, x, edge_index, relu: bool = False, _form: Optional[str] = None, _long_rows: Optional[bool] = None):
+        x = _cuda_f32(x, "SAGEConv")
+        if x.dim() != 2 or x.shape[1] != self.in_channels:
+            raise ValueError(f"SAGEConv: width {tuple(x.shape)[-1]} != in_channels {self.in_channels}")
+        form = self.default_form() if _form is None else _form
+        if form not in ("transform", "aggregate") or not self.form_ok(form):
+            raise ValueError(f"SAGEConv: the {form!r} form is not built for {self.in_channels} -> {self.out_channels}")
+        prep = _sage_graph(edge_index, x.shape[0])
+        return _SAGEConvFn.apply(x, self.lin_l.weight, self.lin_r.weight if self.lin_r is not None else None, self.lin_l.bias, prep,
+                                 self.aggr, relu, form == "aggregate", _long_rows)
+
+
+class SAGE(nn.Module):
+    """GraphSAGE(in_features, hidden_dims, dropout=0., aggr="mean") with GCN's routing: SAGEConv(dims[i], dims[i + 1]) layers in
+    `convs` [PyG-recall: GraphSAGE's name], ReLU (fused into the layer) and dropout between them, edge_index[-i] for hidden layer i
+    and [0] for the last when a list is given, a single tensor / DeviceGraph for every layer otherwise; logits ONLY.  Every layer
+    runs over the batch's node_idx rows (no bipartite trimming)."""
+
+    def __init__(self, in_features: int, hidden_dims: "list[int]", dropout: float = 0., aggr: str = "mean"):
+        super(SAGE, self).__init__()
+        dims = [in_features] + list(hidden_dims)
+        self.convs = nn.ModuleList([SAGEConv(dims[i], dims[i + 1], aggr=aggr) for i in range(len(hidden_dims))])
+        self.dropout, self.aggr = dropout, aggr
+        self.philox_dropout = None          # as GCN: a callable n_elements -> (seed, offset)
+
+    _drop = GCN._drop
+
+    def forward(self, x: torch.Tensor, edge_index: Union[torch.Tensor, "list[torch.Tensor]"]) -> torch.Tensor:
+        if not x.is_cuda:
+            raise ops._lib.GrapesHipError("SAGE input must be a cuda tensor (grapes_amd has no CPU path)")
+        layerwise_adjacency = type(edge_index) == list
+        n_conv = len(self.convs)
+        for i in range(1, n_conv):
+            edges = edge_index[-i] if layerwise_adjacency else edge_index
+            x = self.convs[i - 1](x, edges, relu=True)
+            x = self._drop(x)
+        edges = edge_index[0] if layerwise_adjacency else edge_index
+        return self.convs[n_conv - 1](x, edges)
+
+
 def classifier_layers(model) -> nn.ModuleList:
-    """The conv layers of a classifier: GCN (gcn_layers), GAT or GATv2 (gat_layers), GCN2 or PNA (conv)."""
+    """The conv layers of a classifier: GCN (gcn_layers), GAT or GATv2 (gat_layers), GCN2 or PNA (conv), SAGE (convs)."""
+    if isinstance(model, SAGE):
+        return model.convs
     if isinstance(model, (GCN2, PNA)):
         return model.conv
     return model.gat_layers if isinstance(model, (GAT, GATv2)) else model.gcn_layers
@@ -960,13 +1133,13 @@ def classifier_layers(model) -> nn.ModuleList:
 
 def classifier_needs_loops(model) -> bool:
     """True when the classifier counts stored self-loops (GCN2Conv with normalize=False, PNAConv): its PreparedGraphs then need
-    ops.gcn2_attach_loops (the graph build drops the loops)."""
-    return isinstance(model, (GCN2, PNA))
+    ops.gcn2_attach_loops (the graph build drops the loops).  SAGEConv counts them too."""
+    return isinstance(model, (GCN2, PNA, SAGE))
 
 
 def classifier_logits(model, x, edge_index):
     """(logits, allocated MiB): GCN.forward returns the pair (gcn.py:42), GAT.forward, GCN2.forward and PNA.forward the logits alone
-    (gcn.py:72,117,149), and so does GATv2.forward."""
-    if isinstance(model, (GAT, GATv2, GCN2, PNA)):
+    (gcn.py:72,117,149), and so do GATv2.forward and SAGE.forward."""
+    if isinstance(model, (GAT, GATv2, GCN2, PNA, SAGE)):
         return model(x, edge_index), _memory_allocated_mb()
     return model(x, edge_index)

@@ -41,6 +41,28 @@ KINDS = ("ladies", "fastgcn")
 _UNION_MAX = 4096                   # ops.union_sorted's limit (ids in all its lists)
 
 
+def union_of_lists(g, lists, status):
+    """The ascending duplicate-free union of id lists (int32 tensors, exact lengths) over the DeviceGraph g: one union_sorted launch
+    per four lists while they are small, else marks into the frontier bitmap and a compaction (which zeroes it again).
+    node_map[id] = rank.  Shared by the layer-wise samplers here and modules.sage.NeighborSampler."""
+    N = g.num_nodes
+    lists = [t for t in lists if t.numel()]
+    total = sum(t.numel() for t in lists)
+    if total <= _UNION_MAX:
+        acc = []
+        while True:
+            part, lists = acc + lists[:4 - len(acc)], lists[4 - len(acc):]
+            cap = sum(t.numel() for t in part)
+            out, counts = ops.union_sorted([(t, None) for t in part], N, cap, node_map=g.node_map, status=status)
+            acc = [out[:int(counts[0].item())]]
+            if not lists:
+                return acc[0]
+    for i in range(0, len(lists), 4):
+        ops.bitmap_mark_lists(g.bits, None, [(t, None) for t in lists[i:i + 4]], N, status=status)
+    out, _, _, counts = ops.frontier_compact(g.bits, None, None, N, min(total, N), node_map=g.node_map, status=status)
+    return out[:int(counts[0].item())]
+
+
 class LayerWiseSampler:
     """LayerWiseSampler(data_or_graph, samp_num, num_layers, kind="ladies" | "fastgcn", seed=None, e_cap=None).
     data_or_graph: a DeviceGraph, or a data object as the GraphSAINT samplers take.  samp_num: nodes drawn per layer.  seed: the
@@ -79,25 +101,7 @@ class LayerWiseSampler:
 
     # ------------------------------------------------------------------ set work
     def _union(self, lists):
-        """The ascending duplicate-free union of id lists (int32 tensors, exact lengths): one union_sorted launch per four lists
-        while they are small, else marks into the frontier bitmap and a compaction (which zeroes it again).  node_map[id] = rank."""
-        g = self.graph
-        N = g.num_nodes
-        lists = [t for t in lists if t.numel()]
-        total = sum(t.numel() for t in lists)
-        if total <= _UNION_MAX:
-            acc = []
-            while True:
-                part, lists = acc + lists[:4 - len(acc)], lists[4 - len(acc):]
-                cap = sum(t.numel() for t in part)
-                out, counts = ops.union_sorted([(t, None) for t in part], N, cap, node_map=g.node_map, status=self.status)
-                acc = [out[:int(counts[0].item())]]
-                if not lists:
-                    return acc[0]
-        for i in range(0, len(lists), 4):
-            ops.bitmap_mark_lists(g.bits, None, [(t, None) for t in lists[i:i + 4]], N, status=self.status)
-        out, _, _, counts = ops.frontier_compact(g.bits, None, None, N, min(total, N), node_map=g.node_map, status=self.status)
-        return out[:int(counts[0].item())]
+        return union_of_lists(self.graph, lists, self.status)
 
     def _uniforms(self, n: int):
         u = ops.philox_uniform(n, self.seed, self.philox_offset, self.graph.device)

@@ -2779,6 +2779,157 @@ def asgcn_logq_bwd(edge_src, edge_dst, weight, grad_weight, rows, n_local: int, 
     return out
 
 
+# ------------------------------------------------------------------------------- GraphSAGE: node-wise sampler, SAGEConv aggregation
+# [Hamilton et al., NeurIPS 2017; PyG-recall: torch_geometric 2.5.2 SAGEConv, NeighborLoader] (grapes_hip.h, csrc/sage_kernels.hip)
+SAGE_MAX_FANOUT = 64
+SAGE_AGGRS = ("mean", "sum")
+
+
+def sage_sample_layer(rowptr, col, num_nodes: int, rows, fanout: int, e_cap: Optional[int] = None, keys=None, philox_seed: int = 0,
+                      philox_offset: int = 0, d_philox_offset=None, d_m=None, deg_sum: Optional[int] = None, want_pos: bool = True,
+                      status=None, out=None):
+    """(edge_src, edge_dst int32 [e_cap], edge_pos int64 [e_cap] or None, e_count int32 [1]) of grapes_sage_sample_layer: for the rows
+    i = rows[r] in order keep min(deg_i, fanout) entries of CSR row i, uniformly without replacement — those with the smallest
+    (key << 32) | t, key = keys[p] or raw word p of the Philox stream (philox_seed, offset) at the stream position p = (entries of
+    the list rows before r) + t — written for r ascending and within a row for t ascending: source = the neighbour, target = the row,
+    global ids; edge_pos = the entry's position in col.  1 <= fanout <= 64.  e_cap defaults to rows.numel() * fanout, which cannot
+    overflow; more entries than e_cap set the overflow status bit.  keys: int32 (or uint32) bit patterns, one per stream position.
+    deg_sum: the rows' entry count when the caller knows it — 2^31 or more is refused here, and keys must hold that many.
+    d_philox_offset: int64 [1] device stream offset, used instead of philox_offset and advanced by ceil(deg_sum / 4).
+    out: the four tensors to write (edge_pos may be None)."""
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(rows, _i32, "rows"); _chk(d_m, _i32, "d_m", True)
+    _chk(status, _i32, "status", True); _chk(d_philox_offset, _i64, "d_philox_offset", True)
+    N, dev, m, k = int(num_nodes), rows.device, rows.numel(), int(fanout)
+    if not 1 <= k <= SAGE_MAX_FANOUT:
+        raise ValueError(f"sage_sample_layer: fanout = {fanout} is not built (1 <= fanout <= {SAGE_MAX_FANOUT})")
+    ec = m * k if e_cap is None else int(e_cap)
+    if rowptr.numel() != N + 1 or m < 1 or ec < 1:
+        raise ValueError("sage_sample_layer: rowptr holds N + 1 values; rows and e_cap are not empty")
+    if deg_sum is not None and int(deg_sum) >= 2 ** 31:
+        raise ValueError("sage_sample_layer: rows with 2^31 or more entries in all are not built")
+    n_keys = 0
+    if keys is not None:
+        if not keys.is_cuda or keys.dtype not in (_i32, getattr(torch, "uint32", _i32)) or not keys.is_contiguous():
+            raise TypeError("sage_sample_layer: keys must be a contiguous cuda tensor of 32-bit words (int32 bit patterns or uint32)")
+        n_keys = keys.numel()
+        if deg_sum is not None and n_keys < int(deg_sum):
+            raise ValueError("sage_sample_layer: keys holds one word per entry of the listed rows")
+    if out is None:
+        out = (torch.empty(ec, dtype=_i32, device=dev), torch.empty(ec, dtype=_i32, device=dev),
+               torch.empty(ec, dtype=_i64, device=dev) if want_pos else None, torch.empty(1, dtype=_i32, device=dev))
+    src, dst, pos, d_e = out
+    _chk(src, _i32, "edge_src"); _chk(dst, _i32, "edge_dst"); _chk(pos, _i64, "edge_pos", True); _chk(d_e, _i32, "e_count")
+    if min(src.numel(), dst.numel()) < ec or (pos is not None and pos.numel() < ec):
+        raise ValueError("sage_sample_layer: the edge buffers hold e_cap values each")
+    ws = _ws(lib().grapes_sage_sample_layer_workspace_bytes(m), dev)
+    _lib.check(lib().grapes_sage_sample_layer(_p(rowptr), _p(col), N, _p(rows), m, _p(d_m), k, _p(keys), n_keys,
+                                              int(philox_seed) & (2 ** 64 - 1), int(philox_offset) & (2 ** 64 - 1),
+                                              _p(d_philox_offset), ec, _p(src), _p(dst), _p(pos), _p(d_e), _p(ws), _p(status),
+                                              _stream()), "sage_sample_layer")
+    return src, dst, pos, d_e
+
+
+def _sage_width(f: int):
+    if f < 1 or f > 1024 or (f > 256 and f % 4):
+        raise ValueError(f"SAGE aggregation: width {f} is not built (any width up to 256, multiples of 4 up to 1024)")
+
+
+def sage_width_ok(f: int) -> bool:
+    return 1 <= f <= 1024 and not (f > 256 and f % 4)
+
+
+def _sage_rows(t, name: str, n: int, f: int, allow_none: bool = False):
+    """The leading dimension of a row-major [n, f] matrix that may be a column block of a wider one."""
+    if t is None:
+        if allow_none:
+            return 0
+        raise TypeError(f"{name} is required")
+    if not t.is_cuda:
+        raise _lib.GrapesHipError(f"{name} must live in HBM (cuda tensor); grapes_amd has no CPU path")
+    if t.dtype != _f32:
+        raise TypeError(f"{name}: expected {_f32}, got {t.dtype}")
+    if t.dim() != 2 or tuple(t.shape) != (n, f):
+        raise ValueError(f"{name} must be [{n}, {f}], got {tuple(t.shape)}")
+    if f > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name} must have contiguous rows")
+    ld = t.stride(0) if n > 1 else max(f, t.stride(0))
+    if ld < f:
+        raise ValueError(f"{name}: rows overlap")
+    return ld
+
+
+def _sage_items(prep, by_target: bool, forward: bool, long_rows: Optional[bool]):
+    """_long_items' rule (long_rows None), prep's work items whatever the graph's size (True) or every row by one group (False)."""
+    if long_rows is None:
+        return _long_items(prep, by_target, forward)
+    if not long_rows or (forward and not prep.items_fwd):
+        return None, None, 0
+    items, n_items = (prep.items_t, prep.n_items_t) if by_target else (prep.items_s, prep.n_items_s)
+    return _p(items), _p(n_items), prep.item_cap
+
+
+def _sage_aggr(aggr: str) -> int:
+    if aggr not in SAGE_AGGRS:
+        raise NotImplementedError(f"SAGE aggregation {aggr!r} is not built (built: {', '.join(SAGE_AGGRS)})")
+    return 1 if aggr == "mean" else 0
+
+
+def sage_aggregate_fwd(src, prep: PreparedGraph, aggr: str = "mean", add=None, bias=None, relu: bool = False, out=None, copy_out=None,
+                       long_rows: Optional[bool] = None):
+    """out[i] = act(s_i (sum_{j -> i} src[j] + loops[i] src[i]) + add[i] + bias) over prep's by-target CSR and its stored loops,
+    s_i = 1 / deg_i (mean; an empty row gives 0) or 1 (sum).  src, add, out and copy_out ([n, f]) may be column blocks of wider
+    matrices (rows contiguous); copy_out[i] = src[i].  long_rows: see _sage_items (tests force either form)."""
+    n, f = src.shape
+    _sage_width(f)
+    mean = _sage_aggr(aggr)
+    if n != prep.n:
+        raise ValueError("src must be [n, f] over the prepared graph's nodes")
+    _chk(bias, _f32, "bias", True)
+    if bias is not None and bias.numel() != f:
+        raise ValueError("bias must hold f values")
+    loops = gcn2_loops(prep)
+    if out is None:
+        out = torch.empty((n, f), dtype=_f32, device=src.device)
+    ld_src, ld_add = _sage_rows(src, "src", n, f), _sage_rows(add, "add", n, f, True)
+    ld_out, ld_copy = _sage_rows(out, "out", n, f), _sage_rows(copy_out, "copy_out", n, f, True)
+    items, n_items, cap = _sage_items(prep, True, True, long_rows)
+    ws = _ws(lib().grapes_sage_aggregate_workspace_bytes(0, cap, f), src.device) if cap else None
+    _lib.check(lib().grapes_sage_aggregate_fwd(_p(src), ld_src, _p(add), ld_add, _p(bias), _p(loops), _p(prep.rowptr_t),
+                                               _p(prep.csr_src), mean, 1 if relu else 0, _p(out), ld_out, _p(copy_out), ld_copy, n,
+                                               _p(prep.d_n), f, items, n_items, cap, _p(ws), _p(prep.status), _stream()),
+               "sage_aggregate_fwd")
+    return out
+
+
+def sage_aggregate_bwd(dout, prep: PreparedGraph, aggr: str = "mean", relu_out=None, add=None, want_src: bool = True,
+                       want_add: bool = False, want_bias: bool = False, dsrc=None, dadd=None, long_rows: Optional[bool] = None):
+    """(dsrc, dadd, dbias) of sage_aggregate_fwd from dout = d out: g = dout gated by relu_out > 0 (the forward's output, when the
+    ReLU was fused); dsrc[j] = sum_{i <- j} s_i g_i + loops[j] s_j g_j (+ add[j]) over the by-source CSR; dadd = g; dbias = the
+    column sums of g.  dsrc / dadd: tensors (column blocks allowed) to write; want_*: allocate them.  Fixed order, no atomics."""
+    n, f = dout.shape
+    _sage_width(f)
+    mean = _sage_aggr(aggr)
+    if n != prep.n:
+        raise ValueError("dout must be [n, f] over the prepared graph's nodes")
+    loops = gcn2_loops(prep)
+    dev = dout.device
+    if dsrc is None and want_src:
+        dsrc = torch.empty((n, f), dtype=_f32, device=dev)
+    if dadd is None and want_add:
+        dadd = torch.empty((n, f), dtype=_f32, device=dev)
+    dbias = torch.empty(f, dtype=_f32, device=dev) if want_bias else None
+    ld_dout, ld_relu = _sage_rows(dout, "dout", n, f), _sage_rows(relu_out, "relu_out", n, f, True)
+    ld_add, ld_dsrc = _sage_rows(add, "add", n, f, True), _sage_rows(dsrc, "dsrc", n, f, True)
+    ld_dadd = _sage_rows(dadd, "dadd", n, f, True)
+    items, n_items, cap = _sage_items(prep, False, False, long_rows) if dsrc is not None else (None, None, 0)
+    ws = _ws(lib().grapes_sage_aggregate_workspace_bytes(n, cap, f), dev)
+    _lib.check(lib().grapes_sage_aggregate_bwd(_p(dout), ld_dout, _p(relu_out), ld_relu, _p(loops), _p(prep.rowptr_t),
+                                               _p(prep.rowptr_s), _p(prep.csr_dst), mean, _p(add), ld_add, _p(dsrc), ld_dsrc,
+                                               _p(dadd), ld_dadd, _p(dbias), n, _p(prep.d_n), f, items, n_items, cap, _p(ws),
+                                               _p(prep.status), _stream()), "sage_aggregate_bwd")
+    return dsrc, dadd, dbias
+
+
 def classifier_loss(logits, local_rows, target_ids, labels, out_grad=None):
     """(loss_c [1], d loss_c / d logits [n_rows, C]) — main.py:260,267.  labels: int64 [N] or fp32 [N, C]."""
     _chk(logits, _f32, "logits"); _chk(local_rows, _i32, "local_rows"); _chk(target_ids, _i32, "target_ids")

@@ -63,7 +63,8 @@ extern "C" {
  * edge_norm_b) <- its _ids form; grapes_saint_masked_loss (node_norm) <- its _weighted form; added within 303 (no signature of an
  * earlier entry point changed): the LADIES / FastGCN layer-wise samplers — grapes_ladies_importance,
  * grapes_ladies_layer(_workspace_bytes); the AS-GCN adaptive sampler — grapes_asgcn_importance, grapes_asgcn_rows_workspace_bytes,
- * grapes_asgcn_variance, grapes_asgcn_logq_bwd. */
+ * grapes_asgcn_variance, grapes_asgcn_logq_bwd; GraphSAGE — grapes_sage_sample_layer(_workspace_bytes),
+ * grapes_sage_aggregate_fwd / _bwd, grapes_sage_aggregate_workspace_bytes. */
 #define GRAPES_ABI_VERSION 303
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1498,6 +1499,62 @@ int grapes_asgcn_variance(const int32_t* edge_src, const int32_t* edge_dst, cons
  * d L / d logq_j = -t[j].  One wavefront per row for the means, one per column for the sums (lane l takes the rows l, l + 64, ...
  * and finds j in each by a binary search): a fixed order, no float atomics.  Four launches. */
 int grapes_asgcn_logq_bwd(const int32_t* edge_src, const int32_t* edge_dst, const float* weight, const float* g, int32_t e, const int32_t* rows, int32_t m, int32_t n_local, float* t, void* workspace, int32_t* status, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ GraphSAGE: the node-wise neighbour sampler and SAGEConv's
+ * aggregation (csrc/sage_kernels.hip) [Hamilton et al., NeurIPS 2017; PyG-recall: torch_geometric 2.5.2 SAGEConv, NeighborLoader].
+ * The sampler: for the rows i = rows[r], r < m (*d_m), of the CSR (rowptr int64[N + 1], col int32) keep min(deg_i, fanout) entries of
+ * row i, uniformly without replacement, 1 <= fanout <= 64.  The rule (bit-reproducible on a CPU):
+ *   off_r = the exclusive prefix over r, in list order, of deg(rows[r]); entry t of list row r has stream position p = off_r + t;
+ *   its key is keys[p] when keys (uint32[n_keys]) is given, else raw 32-bit word p of the Philox stream (seed, off), off =
+ *   *d_philox_offset when given else philox_offset: word p & 3 of philox4x32_10(off + p / 4, seed), as grapes_saint_draw_nodes
+ *   indexes words;
+ *   list row r keeps its min(deg, fanout) entries with the smallest composite (key << 32) | t — unique, so a tie in the word goes to
+ *   the lower position and nothing depends on scheduling;
+ *   kept entries are written for r ascending and within a row for t ascending: edge_src[e] = col entry (the neighbour), edge_dst[e] =
+ *   the row (global ids: the direction of slice_adjacency and grapes_ladies_layer), edge_pos[e] = the entry's position in col
+ *   (int64; edge_pos may be NULL);  *d_e = sum of min(deg, fanout).
+ * A row listed twice draws twice, independently (its p differs).  A row with deg <= fanout keeps everything; its words are skipped
+ * all the same, so p is the same on every path.  *d_philox_offset advances by ceil(sum deg / 4) (with keys too).  A row id outside
+ * [0, N) raises GRAPES_STATUS_BAD_INDEX and is dropped (an empty row).  A column outside [0, N) raises it too and is dropped: its
+ * slot holds -1 in edge_src, edge_dst and edge_pos, so that the list's layout never depends on the data.  A stream position at or
+ * past n_keys raises it as well (key 0xffffffff).  More than e_cap entries raise GRAPES_STATUS_EDGE_OVERFLOW, *d_e = e_cap and
+ * nothing is written past e_cap.  Positions are 64-bit on the device; a caller that knows sum deg refuses 2^31 or more
+ * (ops.sage_sample_layer does).  Rows at or past *d_m write nothing.
+ * Two launches.  One workgroup: the degrees, both prefixes, the count, the offset's advance.  Then one wavefront per list row:
+ * deg <= fanout is a copy; deg <= 64 ranks one key per lane by broadcast compares in registers; a longer row is walked 256 stream
+ * positions per trip (a lane takes the four words of one Philox call) by an 8-bit radix select on the word — a pass counts one digit
+ * of the entries that match the prefix found so far in a wavefront-private 256-bin LDS histogram; once the entries at or below the
+ * prefix fit 128 slots (after one pass for rows of up to about 16 000 entries) one more pass lists them in order and the row ends in
+ * registers; words that tie beyond that take four passes and a fifth that writes every word below the threshold and the first
+ * positions that equal it.  Two to five generations of a row's keys: linear in deg, no sort, nothing through global memory, no float
+ * arithmetic.  workspace: grapes_sage_sample_layer_workspace_bytes(m), 8-byte aligned. */
+size_t grapes_sage_sample_layer_workspace_bytes(int32_t m);
+int grapes_sage_sample_layer(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* rows, int32_t m, const int32_t* d_m, int32_t fanout, const uint32_t* keys, int64_t n_keys, uint64_t philox_seed, uint64_t philox_offset, uint64_t* d_philox_offset, int32_t e_cap, int32_t* edge_src, int32_t* edge_dst, int64_t* edge_pos, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream);
+/* SAGEConv's aggregation over the CSRs grapes_gcn_prepare builds, used as stored: no self-loop is added, duplicate entries count
+ * by multiplicity, and the stored self-loops the build drops come back through loops[i] (grapes_gcn2_loop_counts; NULL: none):
+ *   out[i, :f] = act(s_i (sum_{j in row i of the by-target CSR} src[j, :f] + loops[i] src[i, :f]) + add[i, :f] + bias)
+ *   s_i = 1 / deg_i (mean != 0) or 1 (sum), deg_i = (rowptr_t[i + 1] - rowptr_t[i]) + loops[i]; an empty row aggregates to 0.
+ * The scale is applied once per row: there is no per-edge weight.  add, bias and the ReLU (relu != 0) are optional.  copy_out
+ * (optional): copy_out[i, :f] = src[i, :f], the root operand beside the aggregate in the aggregate-first form.  src, add, out and
+ * copy_out are row-major with their own leading dimensions (ld_* >= f floats), so column blocks of one GEMM output are used in
+ * place; out and copy_out must not alias src.  Widths: any f <= 256; up to 1024 when f % 4 == 0 and every matrix is 16-byte
+ * aligned with ld % 4 == 0 (float4 columns), else GRAPES_EALIGN / GRAPES_EINVAL.  long_items / d_n_items / item_cap / workspace as
+ * grapes_gcn2_propagate_fwd (NULL: every row by one group of lanes): rows longer than GRAPES_LONG_ROW are cut into items whose
+ * partial sums are merged in chunk order.  Every sum has a fixed order, no floating-point atomics: two runs give the same bits.
+ * status: GRAPES_STATUS_BAD_INDEX when a CSR entry is outside [0, n) (the entry is dropped).
+ * workspace: grapes_sage_aggregate_workspace_bytes(0, item_cap, f) for the forward, (n, item_cap, f) for the backward; 16-byte
+ * aligned. */
+size_t grapes_sage_aggregate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f);
+int grapes_sage_aggregate_fwd(const float* src, int64_t ld_src, const float* add, int64_t ld_add, const float* bias, const int32_t* loops, const int32_t* rowptr_t, const int32_t* csr_src, int32_t mean, int32_t relu, float* out, int64_t ld_out, float* copy_out, int64_t ld_copy, int32_t n, const int32_t* d_n, int32_t f, const int32_t* long_items, const int32_t* d_n_items, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
+/* Backward of the above.  g = dout, gated by relu_out > 0 when relu_out (the forward's output) is given:
+ *   dsrc[j] = sum_{i in row j of the by-source CSR} s_i g_i + loops[j] s_j g_j (+ add[j]);   dadd = g;   dbias = column sums of g.
+ * One row-local pass writes dadd, the pre-scaled rows s g and per-128-row partial column sums (added in a fixed order by a second
+ * launch); dsrc is then the forward's gather over rowptr_s / csr_dst on the pre-scaled rows, with the by-source items.  The pass is
+ * left out when nothing needs it (sum, no gate, no dadd, no dbias): dsrc gathers dout itself.  add (optional) is a gradient that
+ * reaches the source rows directly (the root half of the aggregate-first form).  dsrc, dadd and dbias may each be NULL; dsrc and
+ * dadd must not alias dout.  s_i always comes from the by-target row pointers rowptr_t.  workspace: required unless the pass is
+ * left out and there are no items. */
+int grapes_sage_aggregate_bwd(const float* dout, int64_t ld_dout, const float* relu_out, int64_t ld_relu, const int32_t* loops, const int32_t* rowptr_t, const int32_t* rowptr_s, const int32_t* csr_dst, int32_t mean, const float* add, int64_t ld_add, float* dsrc, int64_t ld_dsrc, float* dadd, int64_t ld_dadd, float* dbias, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:
