@@ -23,18 +23,16 @@ Datasets as in grapes_amd.main: a synthetic stand-in by name, or `module:functio
 """
 from __future__ import annotations
 
-import argparse
-import sys
 from typing import Optional, Sequence
 
 import torch
 
 from . import ops
-from .ladies import MAX_TARGETS, _TargetLoss, build_model, evaluate, full_graph_structure, layerwise_gcn, weighted_structures
-from .main import load_data
+from .driver import check_ranges, parse_with_dataset, repeat_runs, target_batch_parser, train_target_batches
+from .ladies import LadiesTrainer, build_model, layerwise_gcn, weighted_structures
 from .modules.asgcn import AdaptiveSampler
 from .modules.gcn import GCN
-from .saint import _GatherX
+from .target_batch import TargetBatchTrainer, _TargetLoss
 
 
 class _SamplerLogit(torch.autograd.Function):
@@ -86,28 +84,26 @@ class _VarianceTerm(torch.autograd.Function):
         return ctx.dw * gl, None, None, None, None, None
 
 
-class AsgcnTrainer:
-    """The eager step.  graph: LadiesTrainer's first argument, accepted so that the two are built alike and not read — the sampler
-    holds the DeviceGraph it was made over; x fp32 [N, F]; y int64 [N] or fp32 [N, C]; model: GCN with sampler.num_layers layers;
-    optimizer: any torch optimiser over the model's AND the sampler's parameters; var_coef: the weight of L_var."""
+class AsgcnTrainer(LadiesTrainer):
+    """The eager step; epoch(), evaluate() and check() are LadiesTrainer's.  graph: LadiesTrainer's first argument, accepted so
+    that the two are built alike and not read — the sampler holds the DeviceGraph it was made over; x fp32 [N, F]; y int64 [N] or
+    fp32 [N, C]; model: GCN with sampler.num_layers layers; optimizer: any torch optimiser over the model's AND the sampler's
+    parameters; var_coef: the weight of L_var."""
 
     def __init__(self, graph, x, y, model: GCN, sampler: AdaptiveSampler, optimizer, var_coef: float = 0.5):
         if len(model.gcn_layers) != sampler.num_layers:
             raise ValueError("AsgcnTrainer: the sampler draws one layer per GCN layer")
-        self.x, self.y, self.model, self.sampler, self.optimizer = x, y, model, sampler, optimizer
+        TargetBatchTrainer.__init__(self, x, y, model, optimizer, sampler)
         self.var_coef = float(var_coef)
-        self._full = None
+
+    def _sample(self, targets, uniforms):
+        return self.sampler.sample(targets, self.x, uniforms)
 
     def step(self, targets, uniforms=None):
         """One step on a batch of distinct target nodes (at most 4096); returns (loss tensor, batch); the batch also carries
         loss_c and loss_var (0-d tensors)."""
-        if targets.numel() > MAX_TARGETS:
-            raise ValueError(f"AsgcnTrainer.step: at most {MAX_TARGETS} targets per batch")
         sm = self.sampler
-        b = sm.sample(targets, self.x, uniforms)
-        sm.check()
-        self.optimizer.zero_grad()
-        xb = _GatherX.apply(self.x, b.node_idx, None, None, False)
+        b, xb = self._batch(targets, uniforms)
         weights = b.edge_weight
         if sm.w_g.requires_grad or sm.b_g.requires_grad:
             a_b = _SamplerLogit.apply(xb, sm.w_g, sm.b_g)
@@ -126,89 +122,30 @@ class AsgcnTrainer:
         b.loss_c, b.loss_var = loss_c.detach(), loss_var.detach()
         return (loss_c + self.var_coef * loss_var).detach(), b
 
-    def epoch(self, train_nodes, batch_size: int):
-        """One pass over a permutation of train_nodes in batches of batch_size; the mean of the step losses."""
-        perm = train_nodes[torch.randperm(train_nodes.numel(), device=train_nodes.device)]
-        tot, k = 0.0, 0
-        for i in range(0, perm.numel(), batch_size):
-            loss, _ = self.step(perm[i:i + batch_size])
-            tot, k = tot + float(loss), k + 1
-        return tot / max(k, 1)
 
-    def evaluate(self, masks):
-        if self._full is None:
-            self._full = full_graph_structure(self.sampler.graph)
-        return evaluate(self.model, self.x.detach(), self.sampler.graph, self.y, masks, self._full)
-
-    def check(self):
-        self.sampler.check()
-
-
-def _parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(prog="grapes_amd.asgcn", description=__doc__.split("\n\n")[0])
-    ap.add_argument("--dataset", type=str)
+def parse_args(argv: Optional[Sequence[str]] = None):
+    ap = target_batch_parser("grapes_amd.asgcn", __doc__.split("\n\n")[0])
     ap.add_argument("--samp_num", default=64, type=int)
-    ap.add_argument("--batch_size", default=512, type=int)
-    ap.add_argument("--hidden_dim", default=256, type=int)
-    ap.add_argument("--num_layers", default=2, type=int)
-    ap.add_argument("--lr", default=1e-3, type=float)
-    ap.add_argument("--max_epoch", default=100, type=int)
-    ap.add_argument("--eval_frequency", default=1, type=int)
-    ap.add_argument("--dropout", default=0.0, type=float)
-    ap.add_argument("--runs", default=1, type=int)
-    ap.add_argument("--seed", default=None, type=int)
     ap.add_argument("--e_cap", default=None, type=int)
     ap.add_argument("--var_coef", default=0.5, type=float)
-    return ap
-
-
-def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
-    args = _parser().parse_args(list(sys.argv[1:] if argv is None else argv))
-    if args.dataset is None:
-        raise SystemExit("--dataset is required")
-    if args.num_layers < 1 or args.samp_num < 1 or not 1 <= args.batch_size <= MAX_TARGETS or args.eval_frequency < 1:
-        raise ValueError(f"--num_layers, --samp_num and --eval_frequency are at least 1, --batch_size is 1 .. {MAX_TARGETS}")
+    args = parse_with_dataset(ap, argv)
+    check_ranges(args, "num_layers", "samp_num", "eval_frequency")
     if args.var_coef < 0:
         raise ValueError("--var_coef is not negative")
     return args
 
 
 def run(args, device=None, log=print) -> float:
-    from .graph import DeviceGraph
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    data = load_data(args, device)
-    if getattr(data, "rowptr", None) is not None:
-        g = DeviceGraph(data.rowptr, data.col, data.num_nodes)
-    else:
-        g = DeviceGraph.from_edge_index(data.edge_index.to(device), data.num_nodes)
-    if args.seed is not None:
-        torch.manual_seed(args.seed)
-    x, y = data.x.to(device).contiguous(), data.y.to(device)
-    train_mask, val_mask, test_mask = (m.to(device) for m in (data.train_mask, data.val_mask, data.test_mask))
-    model = build_model(x.shape[1], args.hidden_dim, data.num_classes, args.num_layers, args.dropout, device)
-    sampler = AdaptiveSampler(g, args.samp_num, args.num_layers, x.shape[1], seed=args.seed, e_cap=args.e_cap)
-    opt = torch.optim.Adam(list(model.parameters()) + list(sampler.parameters()), lr=args.lr)
-    tr = AsgcnTrainer(g, x, y, model, sampler, opt, var_coef=args.var_coef)
-    train_nodes = torch.nonzero(train_mask, as_tuple=False).reshape(-1)
-    val = 0.0
-    for epoch in range(1, args.max_epoch + 1):
-        loss = tr.epoch(train_nodes, args.batch_size)
-        if epoch % args.eval_frequency == 0 or epoch == args.max_epoch:
-            val, test = tr.evaluate((val_mask, test_mask))
-            log(f"Epoch: {epoch:02d}, Loss: {loss:.4f}, Val: {val:.4f}, Test: {test:.4f}")
-        else:
-            log(f"Epoch: {epoch:02d}, Loss: {loss:.4f}")
-    return val
+    def make(g, x, y, data, device):
+        model = build_model(x.shape[1], args.hidden_dim, data.num_classes, args.num_layers, args.dropout, device)
+        sampler = AdaptiveSampler(g, args.samp_num, args.num_layers, x.shape[1], seed=args.seed, e_cap=args.e_cap)
+        opt = torch.optim.Adam(list(model.parameters()) + list(sampler.parameters()), lr=args.lr)
+        return AsgcnTrainer(g, x, y, model, sampler, opt, var_coef=args.var_coef)
+    return train_target_batches(args, make, device, log)
 
 
 def main(argv: Optional[Sequence[str]] = None) -> float:
-    args = parse_args(argv)
-    results = torch.empty(args.runs)
-    for r in range(args.runs):
-        results[r] = run(args)
-    std = float(results.std()) if args.runs > 1 else 0.0
-    print(f"Acc: {100 * float(results.mean()):.2f} ± {100 * std:.2f}")
-    return float(results.mean())
+    return repeat_runs(run, parse_args(argv))
 
 
 if __name__ == "__main__":

@@ -32,7 +32,8 @@ from typing import Optional, Sequence
 
 import torch
 
-from .main import _EAGER_CLASSIFIERS, _bool, _large_flag, build_gatv2, build_gcn2, build_pna, check_classifier, load_data, read_config_file
+from .driver import open_graph, repeat_runs
+from .main import _EAGER_CLASSIFIERS, _bool, _large_flag, build_classifier, check_classifier, load_data, read_config_file
 
 # (name, type, default) — full-batch.py:26-50
 _FLAGS = [
@@ -84,14 +85,9 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
 def train(args, device=None, log=print) -> float:
     from . import full_graph
     from .eval import _metrics
-    from .graph import DeviceGraph
-    from .modules.gcn import GAT, GCN
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     data = load_data(args, device)
-    if getattr(data, "rowptr", None) is not None:
-        g = DeviceGraph(data.rowptr, data.col, data.num_nodes)
-    else:
-        g = DeviceGraph.from_edge_index(data.edge_index.to(device), data.num_nodes)
+    g = open_graph(data, device)
     if args.seed is not None:
         torch.manual_seed(args.seed)
     x = data.x.to(device).contiguous()
@@ -99,19 +95,9 @@ def train(args, device=None, log=print) -> float:
     large = _large_flag(args.large_graph)
     kind = getattr(args, "classifier", "gcn")
     gat = kind in _EAGER_CLASSIFIERS                   # (all train by autograd over the whole graph and return the logits alone)
-    if gat:
-        if full_graph.use_large_path(g, large):
-            raise ValueError(f"--classifier {kind}: graphs with 2^31 or more entries (the row-blocked path) take a GCN classifier")
-        if kind == "gcn2":
-            gcn_c = build_gcn2(args, x.shape[1], data.num_classes, args.sampling_hops).to(device)            # modules/gcn.py:76-117
-        elif kind == "pna":
-            gcn_c = build_pna(args, x.shape[1], data.num_classes, args.sampling_hops, g).to(device)          # modules/gcn.py:120-149
-        elif kind == "gatv2":
-            gcn_c = build_gatv2(args, x.shape[1], data.num_classes).to(device)
-        else:
-            gcn_c = GAT(x.shape[1], hidden_dims=[args.hidden_dim, data.num_classes]).to(device)              # modules/gcn.py:45-72
-    else:
-        gcn_c = GCN(x.shape[1], hidden_dims=[args.hidden_dim, data.num_classes], dropout=args.dropout).to(device)  # full-batch.py:73
+    if gat and full_graph.use_large_path(g, large):
+        raise ValueError(f"--classifier {kind}: graphs with 2^31 or more entries (the row-blocked path) take a GCN classifier")
+    gcn_c = build_classifier(args, x.shape[1], data.num_classes, g).to(device)                               # full-batch.py:73
     optimizer_c = torch.optim.Adam(gcn_c.parameters(), lr=args.lr_gc)                                        # full-batch.py:76
     train_mask, val_mask, test_mask = (m.to(device) for m in (data.train_mask, data.val_mask, data.test_mask))
     val_idx = val_mask.nonzero().squeeze(1)
@@ -147,13 +133,7 @@ def train(args, device=None, log=print) -> float:
 
 
 def main(argv: Optional[Sequence[str]] = None) -> float:
-    args = parse_args(argv)
-    results = torch.empty(args.runs)
-    for r in range(args.runs):                                                                                # full-batch.py:152-155
-        results[r] = train(args)
-    std = float(results.std()) if args.runs > 1 else 0.0
-    print(f"Acc: {100 * float(results.mean()):.2f} ± {100 * std:.2f}")                                       # full-batch.py:157
-    return float(results.mean())
+    return repeat_runs(train, parse_args(argv))                                                               # full-batch.py:152-157
 
 
 if __name__ == "__main__":

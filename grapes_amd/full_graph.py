@@ -25,6 +25,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
+from .modules.sampling import draw_seed
 
 LARGE_NNZ = 2 ** 31 - 1          # entry counts from here on need the 64-bit path (DeviceGraph.gcn_prepared refuses them)
 DEFAULT_BLOCK_ROWS = 1 << 20
@@ -285,7 +286,7 @@ def _dropout_streams(gcn, n: int, h: int, c: int):
         return 0.0, (0, 0), (0, 0)
     if gcn.philox_dropout is not None:
         return p, gcn.philox_dropout(n * h), gcn.philox_dropout(n * c)
-    seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    seed = draw_seed(None)
     return p, (seed, 0), (seed, (n * h + 3) // 4)
 
 

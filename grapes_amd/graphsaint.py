@@ -25,11 +25,11 @@ Datasets as in grapes_amd.main: a synthetic stand-in by name, or `module:functio
 from __future__ import annotations
 
 import argparse
-import sys
 from typing import Optional, Sequence
 
 import torch
 
+from .driver import open_graph, parse_with_dataset, repeat_runs
 from .main import _bool, _large_flag, load_data
 
 
@@ -57,9 +57,7 @@ def _parser() -> argparse.ArgumentParser:
 
 
 def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
-    args = _parser().parse_args(list(sys.argv[1:] if argv is None else argv))
-    if args.dataset is None:
-        raise SystemExit("--dataset is required")
+    args = parse_with_dataset(_parser(), argv)
     if args.sample_coverage < 0 or (args.sample_coverage and not args.use_normalization):
         raise ValueError("--sample_coverage K (K > 0) goes with --use_normalization: the estimate is read by the normalised step alone")
     return args
@@ -88,23 +86,16 @@ def evaluate(model, x, g, y, val_mask, test_mask, large_graph: Optional[bool]):
 
 
 def _f1(y_pred, y_true) -> float:
-    tp = int((y_true & y_pred).sum()); fp = int((~y_true & y_pred).sum()); fn = int((y_true & ~y_pred).sum())
-    try:
-        precision, recall = tp / (tp + fp), tp / (tp + fn)
-        return 2 * (precision * recall) / (precision + recall)
-    except ZeroDivisionError:
-        return 0.0
+    """TP / FP / FN micro-F1 of boolean [n, C] predictions: eval._metrics thresholds them (> 0, > 0.5) to themselves."""
+    from .eval import _metrics
+    return _metrics(y_pred, y_true)[0]
 
 
 def run(args, device=None, log=print) -> float:
     from . import saint
-    from .graph import DeviceGraph
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     data = load_data(args, device)
-    if getattr(data, "rowptr", None) is not None:
-        g = DeviceGraph(data.rowptr, data.col, data.num_nodes)
-    else:
-        g = DeviceGraph.from_edge_index(data.edge_index.to(device), data.num_nodes)
+    g = open_graph(data, device)
     if args.seed is not None:
         torch.manual_seed(args.seed)
     emb = []
@@ -135,13 +126,7 @@ def run(args, device=None, log=print) -> float:
 
 
 def main(argv: Optional[Sequence[str]] = None) -> float:
-    args = parse_args(argv)
-    results = torch.empty(args.runs)
-    for r in range(args.runs):
-        results[r] = run(args)
-    std = float(results.std()) if args.runs > 1 else 0.0
-    print(f"Acc: {100 * float(results.mean()):.2f} ± {100 * std:.2f}")                    # graphsaint.py:124
-    return float(results.mean())
+    return repeat_runs(run, parse_args(argv))                                                # graphsaint.py:119-127
 
 
 if __name__ == "__main__":

@@ -21,33 +21,15 @@ Datasets as in grapes_amd.main: a synthetic stand-in by name, or `module:functio
 """
 from __future__ import annotations
 
-import argparse
-import sys
 from typing import Optional, Sequence
 
 import torch
 
 from . import ops
-from .main import load_data
+from .driver import check_ranges, parse_with_dataset, repeat_runs, target_batch_parser, train_target_batches
 from .modules.gcn import GCN, _WeightedGCNConvFn
 from .modules.ladies import KINDS, LayerWiseSampler
-from .saint import _GatherX
-
-MAX_TARGETS = 4096                  # ops.classifier_loss: one workgroup's rows
-
-
-class _TargetLoss(torch.autograd.Function):
-    """ops.classifier_loss over the targets' rows of the logits; d loss / d logits is zero on every other row."""
-
-    @staticmethod
-    def forward(ctx, z, local_rows, target_ids, y):
-        loss, g = ops.classifier_loss(z.contiguous(), local_rows, target_ids, y)
-        ctx.g = g
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, gl):
-        return ctx.g * gl, None, None, None
+from .target_batch import TargetBatchTrainer, full_graph_metrics
 
 
 def weighted_structures(edge_index, n: int):
@@ -103,84 +85,45 @@ def full_graph_structure(g):
 
 def evaluate(model, x, g, y, masks, structure=None):
     """The metric (accuracy, or micro-F1 for 2-D labels) of every mask from ONE full-graph forward with P."""
-    from .eval import _metrics
     ws, w = structure if structure is not None else full_graph_structure(g)
-    L, was = len(model.gcn_layers), model.training
-    model.eval()                                                          # (no dropout at inference)
-    try:
-        with torch.no_grad():
-            logits = layerwise_gcn(model, x, [ws] * L, [w] * L)
-            return tuple(_metrics(logits[m], y[m])[0] for m in masks)
-    finally:
-        model.train(was)
+    L = len(model.gcn_layers)
+    return full_graph_metrics(model, lambda: layerwise_gcn(model, x, [ws] * L, [w] * L), y, masks)
 
 
-class LadiesTrainer:
+class LadiesTrainer(TargetBatchTrainer):
     """The eager step.  graph: a DeviceGraph (or what LayerWiseSampler takes); x fp32 [N, F]; y int64 [N] or fp32 [N, C];
     model: GCN with num_layers layers; optimizer: any torch optimiser over its parameters."""
 
+    _full = None                        # full_graph_structure of the sampler's graph, built by the first evaluate()
+
     def __init__(self, graph, x, y, model: GCN, optimizer, samp_num: int = 64, kind: str = "ladies", seed: Optional[int] = None,
                  e_cap: Optional[int] = None):
-        self.sampler = LayerWiseSampler(graph, samp_num, len(model.gcn_layers), kind=kind, seed=seed, e_cap=e_cap)
-        self.x, self.y, self.model, self.optimizer = x, y, model, optimizer
-        self._full = None
+        sampler = LayerWiseSampler(graph, samp_num, len(model.gcn_layers), kind=kind, seed=seed, e_cap=e_cap)
+        super().__init__(x, y, model, optimizer, sampler)
 
     def step(self, targets, uniforms=None):
-        """One step on a batch of distinct target nodes (at most 4096); returns (loss tensor, batch)."""
-        if targets.numel() > MAX_TARGETS:
-            raise ValueError(f"LadiesTrainer.step: at most {MAX_TARGETS} targets per batch")
-        b = self.sampler.sample(targets, uniforms)
-        self.sampler.check()
-        self.optimizer.zero_grad()
-        xb = _GatherX.apply(self.x, b.node_idx, None, None, False)
-        out = layerwise_gcn(self.model, xb, weighted_structures(b.edge_index, b.num_nodes), b.edge_weight)
-        loss = _TargetLoss.apply(out, b.local_targets, b.targets, self.y)
-        loss.backward()
-        self.optimizer.step()
-        return loss.detach(), b
+        """TargetBatchTrainer.step; uniforms: LayerWiseSampler.sample's."""
+        return super().step(targets, uniforms)
 
-    def epoch(self, train_nodes, batch_size: int):
-        """One pass over a permutation of train_nodes in batches of batch_size; the mean of the step losses."""
-        perm = train_nodes[torch.randperm(train_nodes.numel(), device=train_nodes.device)]
-        tot, k = 0.0, 0
-        for i in range(0, perm.numel(), batch_size):
-            loss, _ = self.step(perm[i:i + batch_size])
-            tot, k = tot + float(loss), k + 1
-        return tot / max(k, 1)
+    def _sample(self, targets, uniforms):
+        return self.sampler.sample(targets, uniforms)
+
+    def _forward(self, xb, b):
+        return layerwise_gcn(self.model, xb, weighted_structures(b.edge_index, b.num_nodes), b.edge_weight)
 
     def evaluate(self, masks):
         if self._full is None:
             self._full = full_graph_structure(self.sampler.graph)
         return evaluate(self.model, self.x.detach(), self.sampler.graph, self.y, masks, self._full)
 
-    def check(self):
-        self.sampler.check()
 
-
-def _parser() -> argparse.ArgumentParser:
-    ap = argparse.ArgumentParser(prog="grapes_amd.ladies", description=__doc__.split("\n\n")[0])
-    ap.add_argument("--dataset", type=str)
+def parse_args(argv: Optional[Sequence[str]] = None):
+    ap = target_batch_parser("grapes_amd.ladies", __doc__.split("\n\n")[0])
     ap.add_argument("--sampler", default="ladies", choices=list(KINDS))
     ap.add_argument("--samp_num", default=64, type=int)
-    ap.add_argument("--batch_size", default=512, type=int)
-    ap.add_argument("--hidden_dim", default=256, type=int)
-    ap.add_argument("--num_layers", default=2, type=int)
-    ap.add_argument("--lr", default=1e-3, type=float)
-    ap.add_argument("--max_epoch", default=100, type=int)
-    ap.add_argument("--eval_frequency", default=1, type=int)
-    ap.add_argument("--dropout", default=0.0, type=float)
-    ap.add_argument("--runs", default=1, type=int)
-    ap.add_argument("--seed", default=None, type=int)
     ap.add_argument("--e_cap", default=None, type=int)
-    return ap
-
-
-def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
-    args = _parser().parse_args(list(sys.argv[1:] if argv is None else argv))
-    if args.dataset is None:
-        raise SystemExit("--dataset is required")
-    if args.num_layers < 1 or args.samp_num < 1 or not 1 <= args.batch_size <= MAX_TARGETS or args.eval_frequency < 1:
-        raise ValueError(f"--num_layers, --samp_num and --eval_frequency are at least 1, --batch_size is 1 .. {MAX_TARGETS}")
+    args = parse_with_dataset(ap, argv)
+    check_ranges(args, "num_layers", "samp_num", "eval_frequency")
     return args
 
 
@@ -189,40 +132,15 @@ def build_model(F: int, hidden_dim: int, C: int, num_layers: int, dropout: float
 
 
 def run(args, device=None, log=print) -> float:
-    from .graph import DeviceGraph
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-    data = load_data(args, device)
-    if getattr(data, "rowptr", None) is not None:
-        g = DeviceGraph(data.rowptr, data.col, data.num_nodes)
-    else:
-        g = DeviceGraph.from_edge_index(data.edge_index.to(device), data.num_nodes)
-    if args.seed is not None:
-        torch.manual_seed(args.seed)
-    x, y = data.x.to(device).contiguous(), data.y.to(device)
-    train_mask, val_mask, test_mask = (m.to(device) for m in (data.train_mask, data.val_mask, data.test_mask))
-    model = build_model(x.shape[1], args.hidden_dim, data.num_classes, args.num_layers, args.dropout, device)
-    tr = LadiesTrainer(g, x, y, model, torch.optim.Adam(model.parameters(), lr=args.lr), samp_num=args.samp_num, kind=args.sampler,
-                       seed=args.seed, e_cap=args.e_cap)
-    train_nodes = torch.nonzero(train_mask, as_tuple=False).reshape(-1)
-    val = 0.0
-    for epoch in range(1, args.max_epoch + 1):
-        loss = tr.epoch(train_nodes, args.batch_size)
-        if epoch % args.eval_frequency == 0 or epoch == args.max_epoch:
-            val, test = tr.evaluate((val_mask, test_mask))
-            log(f"Epoch: {epoch:02d}, Loss: {loss:.4f}, Val: {val:.4f}, Test: {test:.4f}")
-        else:
-            log(f"Epoch: {epoch:02d}, Loss: {loss:.4f}")
-    return val
+    def make(g, x, y, data, device):
+        model = build_model(x.shape[1], args.hidden_dim, data.num_classes, args.num_layers, args.dropout, device)
+        return LadiesTrainer(g, x, y, model, torch.optim.Adam(model.parameters(), lr=args.lr), samp_num=args.samp_num,
+                             kind=args.sampler, seed=args.seed, e_cap=args.e_cap)
+    return train_target_batches(args, make, device, log)
 
 
 def main(argv: Optional[Sequence[str]] = None) -> float:
-    args = parse_args(argv)
-    results = torch.empty(args.runs)
-    for r in range(args.runs):
-        results[r] = run(args)
-    std = float(results.std()) if args.runs > 1 else 0.0
-    print(f"Acc: {100 * float(results.mean()):.2f} ± {100 * std:.2f}")
-    return float(results.mean())
+    return repeat_runs(run, parse_args(argv))
 
 
 if __name__ == "__main__":

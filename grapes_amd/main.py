@@ -120,6 +120,22 @@ def build_gcn2(args, F: int, C: int, hops: int):
                 theta=getattr(args, "gcn2_theta", 0.5), shared_weights=getattr(args, "gcn2_shared_weights", True),
                 dropout=args.dropout)
 
+
+def build_classifier(args, F: int, C: int, graph):
+    """The classifier --classifier names (absent from args: gcn), on the host.  The sampler nets stay GCN."""
+    from .modules.gcn import GAT, GCN
+    kind = getattr(args, "classifier", "gcn")
+    if kind == "gat":
+        return GAT(F, hidden_dims=[args.hidden_dim, C])                                            # modules/gcn.py:45-72
+    if kind == "gatv2":
+        return build_gatv2(args, F, C)
+    if kind == "gcn2":
+        return build_gcn2(args, F, C, args.sampling_hops)                                          # modules/gcn.py:76-117
+    if kind == "pna":
+        return build_pna(args, F, C, args.sampling_hops, graph)                                    # modules/gcn.py:120-149
+    return GCN(F, hidden_dims=[args.hidden_dim, C], dropout=args.dropout)                          # main.py:110
+
+
 _DATASET_ALIASES = {"ogbn-arxiv": "arxiv", "ogbn-products": "products", "reddit2": "reddit"}
 
 
@@ -216,17 +232,15 @@ def _batches(idx: torch.Tensor, batch_size: int):
 
 # ------------------------------------------------------------------------------------------------ one run
 def train(args, device=None, log=print):
+    from .driver import open_graph
     from .eval import evaluate
     from .graph import DeviceGraph
-    from .modules.gcn import GAT, GCN
+    from .modules.gcn import GCN
     from .step import GrapesTrainer
     from .step_graph import GraphedTrainer
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
     data = load_data(args, device)
-    if getattr(data, "rowptr", None) is not None:
-        g = DeviceGraph(data.rowptr, data.col, data.num_nodes)
-    else:
-        g = DeviceGraph.from_edge_index(data.edge_index.to(device), data.num_nodes)              # main.py:134-136
+    g = open_graph(data, device)                                                                   # main.py:134-136
     y = data.y.to(device)
     if args.seed is not None:
         torch.manual_seed(args.seed)
@@ -244,16 +258,7 @@ def train(args, device=None, log=print):
         x = data.x.to(device).contiguous()
     F, C = x.shape[1], data.num_classes
     num_ind = args.sampling_hops + 1 if args.use_indicators else 0                                 # main.py:104-107
-    if getattr(args, "classifier", "gcn") == "gat":
-        gcn_c = GAT(F, hidden_dims=[args.hidden_dim, C]).to(device)                                # modules/gcn.py:45-72
-    elif getattr(args, "classifier", "gcn") == "gatv2":
-        gcn_c = build_gatv2(args, F, C).to(device)
-    elif getattr(args, "classifier", "gcn") == "gcn2":
-        gcn_c = build_gcn2(args, F, C, args.sampling_hops).to(device)                              # modules/gcn.py:76-117
-    elif getattr(args, "classifier", "gcn") == "pna":
-        gcn_c = build_pna(args, F, C, args.sampling_hops, g).to(device)                            # modules/gcn.py:120-149
-    else:
-        gcn_c = GCN(F, hidden_dims=[args.hidden_dim, C], dropout=args.dropout).to(device)          # main.py:110
+    gcn_c = build_classifier(args, F, C, g).to(device)
     gcn_gf = GCN(F + num_ind, hidden_dims=[args.hidden_dim, 1]).to(device)                          # main.py:112-113
     gcn_z = GCN(F, hidden_dims=[args.hidden_dim, 1]).to(device)                                     # main.py:114
     opt_c = torch.optim.Adam(list(gcn_c.parameters()) + embedding_params, lr=args.lr_gc, capturable=True)   # main.py:116
@@ -337,13 +342,8 @@ def train(args, device=None, log=print):
 
 
 def main(argv: Optional[Sequence[str]] = None) -> float:
-    args = parse_args(argv)
-    results = torch.empty(args.runs)
-    for r in range(args.runs):                                                                       # main.py:376-385
-        results[r] = train(args)
-    std = float(results.std()) if args.runs > 1 else 0.0
-    print(f"Acc: {100 * float(results.mean()):.2f} ± {100 * std:.2f}")                              # main.py:390
-    return float(results.mean())
+    from .driver import repeat_runs
+    return repeat_runs(train, parse_args(argv))                                                      # main.py:376-390
 
 
 if __name__ == "__main__":

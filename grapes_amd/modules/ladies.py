@@ -35,32 +35,9 @@ from typing import Optional
 import torch
 
 from .. import ops
-from .saint import _graph_of
+from .sampling import _graph_of, as_targets, draw_seed, local_edge_lists, raise_on_status, union_of_lists
 
 KINDS = ("ladies", "fastgcn")
-_UNION_MAX = 4096                   # ops.union_sorted's limit (ids in all its lists)
-
-
-def union_of_lists(g, lists, status):
-    """The ascending duplicate-free union of id lists (int32 tensors, exact lengths) over the DeviceGraph g: one union_sorted launch
-    per four lists while they are small, else marks into the frontier bitmap and a compaction (which zeroes it again).
-    node_map[id] = rank.  Shared by the layer-wise samplers here and modules.sage.NeighborSampler."""
-    N = g.num_nodes
-    lists = [t for t in lists if t.numel()]
-    total = sum(t.numel() for t in lists)
-    if total <= _UNION_MAX:
-        acc = []
-        while True:
-            part, lists = acc + lists[:4 - len(acc)], lists[4 - len(acc):]
-            cap = sum(t.numel() for t in part)
-            out, counts = ops.union_sorted([(t, None) for t in part], N, cap, node_map=g.node_map, status=status)
-            acc = [out[:int(counts[0].item())]]
-            if not lists:
-                return acc[0]
-    for i in range(0, len(lists), 4):
-        ops.bitmap_mark_lists(g.bits, None, [(t, None) for t in lists[i:i + 4]], N, status=status)
-    out, _, _, counts = ops.frontier_compact(g.bits, None, None, N, min(total, N), node_map=g.node_map, status=status)
-    return out[:int(counts[0].item())]
 
 
 class LayerWiseSampler:
@@ -84,9 +61,7 @@ class LayerWiseSampler:
                              "layer's entry offsets are 32-bit")
         dev, N = g.device, g.num_nodes
         self.e_cap = None if e_cap is None else int(e_cap)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self.seed, self.philox_offset = int(seed), 0
+        self.seed, self.philox_offset = draw_seed(seed), 0
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         flag = ops.csr_symmetric_check(g.rowptr, g.col, N)
         if flag & 2:
@@ -146,9 +121,7 @@ class LayerWiseSampler:
         edge_src, edge_dst (global ids) and weight."""
         g = self.graph
         dev, N = g.device, g.num_nodes
-        targets = targets.to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
-        if targets.numel() < 1:
-            raise ValueError("LayerWiseSampler.sample: no target")
+        targets = as_targets(targets, dev, "LayerWiseSampler")
         uniforms = list(uniforms) if uniforms is not None else []
         prev, layers = targets, []
         for d in range(self.num_layers):
@@ -183,9 +156,7 @@ class LayerWiseSampler:
                                           edge_src=src[:e], edge_dst=dst[:e], weight=w[:e], **extra))
             prev = after
         node_idx = self._union([targets] + [L.after for L in layers])     # (also node_map[id] = rank)
-        edge_index = [torch.stack([ops.tensormap_map(g.node_map, L.edge_src.contiguous()),
-                                   ops.tensormap_map(g.node_map, L.edge_dst.contiguous())]) if L.edge_src.numel()
-                      else torch.zeros((2, 0), dtype=torch.int32, device=dev) for L in layers]
+        edge_index = local_edge_lists(g, layers, dev)
         return SimpleNamespace(node_idx=node_idx, num_nodes=node_idx.numel(), targets=targets,
                                local_targets=ops.tensormap_map(g.node_map, targets), edge_index=edge_index,
                                edge_weight=[L.weight for L in layers], layers=layers, **self._batch_fields(node_idx, layers))
@@ -193,10 +164,5 @@ class LayerWiseSampler:
     def check(self):
         """Reads the status word (synchronises); raises GrapesHipError on an edge overflow or a bad id, and clears it (and, as
         DeviceGraph.check_status does, the bitmaps a truncated batch may have left marked)."""
-        s = int(self.status.item())
-        if s:
-            self.status.zero_()
-            self.graph.bits.zero_(); self.graph.prev_bits.zero_()
-            bits = [n for b, n in ((1, "edge buffer overflow (raise e_cap)"), (2, "node buffer overflow"), (4, "index out of range"))
-                    if s & b]
-            raise ops._lib.GrapesHipError(f"{getattr(self, '_name', self.kind)} sampler: " + ", ".join(bits))
+        raise_on_status(self.status, f"{getattr(self, '_name', self.kind)} sampler", graph=self.graph,
+                        hints={1: " (raise e_cap)"})

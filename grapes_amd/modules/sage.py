@@ -25,8 +25,7 @@ from typing import Optional, Sequence
 import torch
 
 from .. import ops
-from .ladies import union_of_lists
-from .saint import _graph_of
+from .sampling import _graph_of, as_targets, draw_seed, local_edge_lists, raise_on_status, union_of_lists
 
 
 def check_fanouts(fanouts: Sequence[int]) -> "list[int]":
@@ -53,9 +52,7 @@ class NeighborSampler:
         if g.nnz >= 2 ** 31:
             raise ValueError("neighbour sampling over a graph with 2^31 or more entries is not built: the layer's entry offsets are "
                              "32-bit")
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self.seed, self.philox_offset = int(seed), 0
+        self.seed, self.philox_offset = draw_seed(seed), 0
         self.status = torch.zeros(1, dtype=torch.int32, device=g.device)
         if ops.csr_symmetric_check(g.rowptr, g.col, g.num_nodes) & 2:
             raise ops._lib.GrapesHipError("NeighborSampler: a column id is outside [0, num_nodes)")
@@ -66,9 +63,7 @@ class NeighborSampler:
         list draw from the stream.  Returns the batch namespace described in the module docstring."""
         g = self.graph
         dev, N = g.device, g.num_nodes
-        targets = targets.to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
-        if targets.numel() < 1:
-            raise ValueError("NeighborSampler.sample: no target")
+        targets = as_targets(targets, dev, "NeighborSampler")
         keys = list(keys) if keys is not None else []
         prev, layers = targets, []
         for d, k in enumerate(self.fanouts):
@@ -96,18 +91,11 @@ class NeighborSampler:
             layers.append(SimpleNamespace(prev=prev, after=after, edge_src=src, edge_dst=dst, edge_pos=pos, fanout=k))
             prev = after
         node_idx = prev                                  # the last union holds every earlier layer, and left node_map[id] = rank
-        edge_index = [torch.stack([ops.tensormap_map(g.node_map, L.edge_src.contiguous()),
-                                   ops.tensormap_map(g.node_map, L.edge_dst.contiguous())]) if L.edge_src.numel()
-                      else torch.zeros((2, 0), dtype=torch.int32, device=dev) for L in layers]
         return SimpleNamespace(node_idx=node_idx, num_nodes=node_idx.numel(), targets=targets,
-                               local_targets=ops.tensormap_map(g.node_map, targets), edge_index=edge_index, layers=layers)
+                               local_targets=ops.tensormap_map(g.node_map, targets), edge_index=local_edge_lists(g, layers, dev),
+                               layers=layers)
 
     def check(self):
         """Reads the status word (synchronises); raises GrapesHipError on an edge overflow or a bad id, and clears it (and, as
         DeviceGraph.check_status does, the bitmaps a truncated batch may have left marked)."""
-        s = int(self.status.item())
-        if s:
-            self.status.zero_()
-            self.graph.bits.zero_(); self.graph.prev_bits.zero_()
-            bits = [n for b, n in ((1, "edge buffer overflow"), (2, "node buffer overflow"), (4, "index out of range")) if s & b]
-            raise ops._lib.GrapesHipError("neighbour sampler: " + ", ".join(bits))
+        raise_on_status(self.status, "neighbour sampler", graph=self.graph)

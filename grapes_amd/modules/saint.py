@@ -38,21 +38,7 @@ from typing import Optional
 import torch
 
 from .. import ops
-
-
-def _graph_of(data_or_graph):
-    from ..graph import DeviceGraph
-    if isinstance(data_or_graph, DeviceGraph):
-        return data_or_graph, None
-    g = getattr(data_or_graph, "graph", None)
-    if isinstance(g, DeviceGraph):
-        return g, data_or_graph
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if getattr(data_or_graph, "rowptr", None) is not None:
-        g = DeviceGraph(data_or_graph.rowptr.to(dev), data_or_graph.col.to(dev), int(data_or_graph.num_nodes))
-    else:
-        g = DeviceGraph.from_edge_index(data_or_graph.edge_index.to(dev), int(data_or_graph.num_nodes), device=dev)
-    return g, data_or_graph
+from .sampling import _graph_of, draw_seed, raise_on_status
 
 
 class _SaintSampler:
@@ -77,9 +63,7 @@ class _SaintSampler:
         self.graph, self.data = _graph_of(data_or_graph)
         dev = self.graph.device
         self.e_cap = int(e_cap) if e_cap is not None else max(1, min(self.n_cap * self.n_cap, self.graph.nnz))
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        self.seed = int(seed)
+        self.seed = draw_seed(seed)
         self.philox_offset = torch.zeros(1, dtype=torch.int64, device=dev)
         self.status = torch.zeros(1, dtype=torch.int32, device=dev)
         # set by estimate_norm
@@ -140,11 +124,7 @@ class _SaintSampler:
 
     def check(self):
         """Reads the status word (synchronises); raises GrapesHipError on an edge overflow or a bad id, and clears it."""
-        s = int(self.status.item())
-        if s:
-            self.status.zero_()
-            bits = [n for b, n in ((1, "edge buffer overflow (raise e_cap)"), (4, "index out of range")) if s & b]
-            raise ops._lib.GrapesHipError("GraphSAINT sampler: " + ", ".join(bits))
+        raise_on_status(self.status, "GraphSAINT sampler", hints={1: " (raise e_cap)", 2: None})
 
     def batch(self, *inject, **kw) -> SimpleNamespace:
         """One batch in PyG's form (two host reads: the node and edge counts)."""

@@ -30,29 +30,7 @@ import torch
 from . import ops
 from .modules.gcn import GCN, _WeightedGCNConvFn
 from .modules.saint import make_sampler
-
-
-class _GatherX(torch.autograd.Function):
-    """X[node_idx[:count]] (rows past the count are left as they are).  Backward: with into_grad the rows' gradients are added
-    into X.grad in place (node_idx is duplicate-free) and nothing is returned; otherwise a dense [N, F] gradient is returned."""
-
-    @staticmethod
-    def forward(ctx, X, node_idx, count, out, into_grad):
-        ctx.save_for_backward(node_idx)
-        ctx.count, ctx.X, ctx.into_grad = count, X, into_grad
-        return ops.gather_rows(X.detach(), node_idx, d_n=count, out=out)
-
-    @staticmethod
-    def backward(ctx, dx):
-        (node_idx,) = ctx.saved_tensors
-        X = ctx.X
-        dx = dx.contiguous()
-        if ctx.into_grad and X.grad is not None:
-            ops.scatter_rows(X.grad, node_idx, dx, d_n=ctx.count, accumulate=True)
-            return None, None, None, None, None
-        g = torch.zeros(X.shape, dtype=torch.float32, device=dx.device)
-        ops.scatter_rows(g, node_idx, dx, d_n=ctx.count)
-        return g, None, None, None, None
+from .target_batch import _GatherX
 
 
 class _MaskedLoss(torch.autograd.Function):

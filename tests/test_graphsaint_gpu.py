@@ -179,7 +179,8 @@ def _check(a, b, what):
 def test_one_step_against_fp64(multi, embed):
     _cuda()
     from grapes_amd.modules.saint import GraphSAINTRandomWalkSampler
-    from grapes_amd.saint import _GatherX, masked_loss
+    from grapes_amd.saint import masked_loss
+    from grapes_amd.target_batch import _GatherX
     indptr, indices, g, x, y, tm, model = _setup(multi, embed)
     B, L = 64, 2
     roots, u = _draws(B, L, g.num_nodes, 5)

@@ -346,7 +346,7 @@ def _params(model):
 @pytest.mark.parametrize("fanouts", [[3, 2], [-1, 2]])
 def test_neighbor_sampler_batch_and_model_against_the_oracle(fanouts):
     _ops()
-    from grapes_amd.ladies import _TargetLoss
+    from grapes_amd.target_batch import _TargetLoss
     from grapes_amd.modules.gcn import SAGE
     from grapes_amd.modules.sage import NeighborSampler
     ip, ix, g = _graph40()
