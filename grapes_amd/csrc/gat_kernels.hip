@@ -43,7 +43,7 @@ __device__ __forceinline__ void gat_fwd_range(const float* __restrict__ h, const
                                               const int32_t* __restrict__ csr, int row, int n, float sd, int beg, int end,
                                               bool with_self, int F, int l, float& m, float& sum, float (&acc)[NS][VEC],
                                               int32_t* status) {
-    constexpr int U = GatUnroll<NS>::U;
+    constexpr int U = RowUnroll<NS>::U;
     for (int b = with_self ? beg - 1 : beg; b < end; b += LPR) {
         int idx;
         const bool ok = gat_entry(csr, b + l, beg, end, row, n, idx, status);
@@ -251,7 +251,7 @@ __device__ __forceinline__ float gat_bwd_dst_range(const float* __restrict__ h, 
                                                    const int32_t* __restrict__ csr, int row, int n, float4 q,
                                                    const float (&g)[NS][VEC], int beg, int end, bool with_self, int F, int l,
                                                    int32_t* status) {
-    constexpr int U = GatUnroll<NS>::U;
+    constexpr int U = RowUnroll<NS>::U;
     float part = 0.f;
     for (int b = with_self ? beg - 1 : beg; b < end; b += LPR) {
         int idx;
@@ -340,7 +340,7 @@ __device__ __forceinline__ float gat_bwd_src_range(const float* __restrict__ gma
                                                    const int32_t* __restrict__ csr, int row, int n, float ss,
                                                    const float (&hreg)[NS][VEC], int beg, int end, bool with_self, int F, int l,
                                                    float (&acc)[NS][VEC], int32_t* status) {
-    constexpr int U = GatUnroll<NS>::U;
+    constexpr int U = RowUnroll<NS>::U;
     float part = 0.f;
     for (int b = with_self ? beg - 1 : beg; b < end; b += LPR) {
         int idx;

@@ -108,7 +108,7 @@ __device__ __forceinline__ void gv2_fwd_range(const float* __restrict__ xl, cons
                                               const float (&xr)[NS][VEC], const float (&at)[NS][VEC], const int (&hd)[NS], int H,
                                               int lh, float slope, int beg, int end, bool with_self, int F, int l, float (&m)[NS],
                                               float (&sum)[NS], float (&acc)[NS][VEC], int32_t* status) {
-    constexpr int U = GatUnroll<NS>::U;
+    constexpr int U = RowUnroll<NS>::U;
     for (int b = with_self ? beg - 1 : beg; b < end; b += LPR) {
         int idx;
         const int ok = gat_entry(csr, b + l, beg, end, row, n, idx, status) ? 1 : 0;
@@ -401,7 +401,7 @@ __device__ __forceinline__ void gv2_bwd_dst_range(const float* __restrict__ xl, 
                                                   const float4 (&q)[NS], const int (&hd)[NS], int H, int lh, float slope, int beg,
                                                   int end, bool with_self, int F, int l, float (&dxr)[NS][VEC],
                                                   float (&datt)[NS][VEC], int32_t* status) {
-    constexpr int U = GatUnroll<NS>::U;
+    constexpr int U = RowUnroll<NS>::U;
     for (int b = with_self ? beg - 1 : beg; b < end; b += LPR) {
         int idx;
         const int ok = gat_entry(csr, b + l, beg, end, row, n, idx, status) ? 1 : 0;
@@ -543,7 +543,7 @@ __device__ __forceinline__ void gv2_bwd_src_range(const float* __restrict__ xrm,
                                                   const float (&xlr)[NS][VEC], const float (&at)[NS][VEC], const int (&hd)[NS], int H,
                                                   int lh, float slope, int beg, int end, bool with_self, int F, int l,
                                                   float (&acc)[NS][VEC], int32_t* status) {
-    constexpr int U = GatUnroll<NS>::U;
+    constexpr int U = RowUnroll<NS>::U;
     for (int b = with_self ? beg - 1 : beg; b < end; b += LPR) {
         int idx;
         const int ok = gat_entry(csr, b + l, beg, end, row, n, idx, status) ? 1 : 0;

@@ -6,12 +6,9 @@
 //   S_i  = (1 - alpha) (sum_{j -> i} x_j + loops[i] x_i) + alpha x0_i                 P'_i = (1 - alpha) (sum ... ) (optional)
 //   out  = act(c0 S + c1 T1 [+ c2 T2])          T1 = S W1 (shared) or P' W1, T2 = x0 W2: the project's GEMM entry points
 //
-//   gcn2_rows_k       a group of LPR lanes (half a wavefront or a whole one) owns a row of the CSR: every lane reads ONE column
-//                     index of a batch of LPR entries, the batch's rows are gathered U at a time (U independent row loads in
-//                     flight per group) with the indices broadcast from the lanes that own them; the sum stays in registers and
-//                     the epilogue (loops, scale, x0 blend, the optional second output) writes each output row once.
-//   gcn2_chunks_k     rows longer than GRAPES_LONG_ROW: one group per work item (64 consecutive entries) -> pacc[item]
-//   gcn2_combine_k    ... one workgroup per long row adds its items in chunk order, then the same epilogue
+//   row_sum_rows_k / row_sum_chunks_k / row_sum_combine_k   the plain-sum gather shared with SAGEConv (row_sum.h): the sum stays
+//                     in registers and the epilogue below (G2Epi: scale, x0 blend, the optional second output) writes each output
+//                     row once; rows longer than GRAPES_LONG_ROW go through work items added in chunk order
 //   gcn2_bwd_sum_k    backward only, when the gradient of S arrives in two pieces: D = ds + ds_add and the x0 gradient, one pass
 //   gcn2_mix_fwd_k / gcn2_mix_bwd_k   the blend and its gated backward, one read of every operand
 //   gcn2_loops_k / gcn2_loops_csr_k   loops[i] = number of stored edges (i, i)
@@ -19,160 +16,57 @@
 // The backward propagation is the SAME gather over the by-source CSR (dx_j = (1 - alpha) (sum_{j -> i} D_i + loops[j] D_j)):
 // no floating-point atomics anywhere, every sum has a fixed order (entry order inside a row, chunk order across work items), so
 // two runs are bit-identical.  No kernel waits on another workgroup.
-#include "row_gather.h"
+#include "row_sum.h"
 
-template <int NS> struct G2Unroll { static constexpr int U = NS == 1 ? 4 : (NS <= 4 ? 2 : 1); };
-
-// acc += sum of the rows m[csr[t]], t in [beg, end).  An index outside [0, n) raises GRAPES_STATUS_BAD_INDEX and the entry is
-// dropped (its lane keeps the row itself with weight 0, so the loads below need no predicate).
-template <int VEC, int LPR, int NS>
-__device__ __forceinline__ void g2_gather(const float* __restrict__ m, const int32_t* __restrict__ csr, int row, int n, int beg,
-                                          int end, int F, int l, float (&acc)[NS][VEC], int32_t* status) {
-    constexpr int U = G2Unroll<NS>::U;
-    for (int b = beg; b < end; b += LPR) {
-        const int c = batch_entry(csr, b + l, end, n, status);
-        const int idx = c < 0 ? row : c;
-        const float w = c < 0 ? 0.f : 1.f;
-        const int cnt = end - b < LPR ? end - b : LPR;
-        for (int k = 0; k < cnt; k += U) {
-            float hv[U][NS][VEC], wk[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int ik = __shfl(idx, k + u, LPR);
-                wk[u] = __shfl(w, k + u, LPR);
-                row_load<VEC, LPR, NS>(m, ik, F, l, hv[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int s = 0; s < NS; ++s)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(wk[u], hv[u][s][v], acc[s][v]);
-        }
-    }
-}
-
-// What a row's sum becomes:  p = c_acc (sum + loops[row] src[row]);  out1[row] = p + c_self self_mat[row];  out2[row] = p;
-// aux[row] (+)= c_aux src[row].  self_mat, loops, out2 and aux are optional.
+// The epilogue of the shared row sum (row_sum.h), p = the row's sum + loops[row] src[row]:
+//   q = c_acc p;  out1[row] = q + c_self self_mat[row];  out2[row] = q;  aux[row] (+)= c_aux src[row] (every row, long or not).
+// self_mat, loops, out2 and aux are optional.  Every matrix has rows F = ld_src floats apart.
 struct G2Epi {
-    const float* src;
-    const float* self_mat;
+    const float* src; int ld_src;
     const int32_t* loops;
+    const float* self_mat;
     float* out1;
     float* out2;
     float* aux;
     float c_acc, c_self, c_aux;
     int aux_accumulate;
-};
 
-template <int VEC, int LPR, int NS>
-__device__ __forceinline__ void g2_finish(const G2Epi& e, float (&acc)[NS][VEC], int row, int F, int l) {
-    const int lp = e.loops ? e.loops[row] : 0;
-    if (lp != 0) {
-        float xr[NS][VEC];
-        row_load<VEC, LPR, NS>(e.src, row, F, l, xr);
-        const float lf = (float)lp;
+    template <int VEC, int LPR, int NS>
+    __device__ __forceinline__ void pre(int row, int F, int l) const {
+        if (!aux) return;
+        float d[NS][VEC], a[NS][VEC];
+        row_load<VEC, LPR, NS>(src, row, F, l, d);
+        if (aux_accumulate) row_load<VEC, LPR, NS>(aux, row, F, l, a);
 #pragma unroll
         for (int s = 0; s < NS; ++s)
 #pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(lf, xr[s][v], acc[s][v]);
+            for (int v = 0; v < VEC; ++v) d[s][v] = aux_accumulate ? fmaf(c_aux, d[s][v], a[s][v]) : c_aux * d[s][v];
+        row_store<VEC, LPR, NS>(aux, row, F, l, d);
     }
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[s][v] *= e.c_acc;
-    if (e.out2) row_store<VEC, LPR, NS>(e.out2, row, F, l, acc);
-    if (e.self_mat) {
-        float x0[NS][VEC];
-        row_load<VEC, LPR, NS>(e.self_mat, row, F, l, x0);
+    template <int VEC, int LPR, int NS>
+    __device__ __forceinline__ void finish(float (&acc)[NS][VEC], int row, int, int F, int l) const {
 #pragma unroll
         for (int s = 0; s < NS; ++s)
 #pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(e.c_self, x0[s][v], acc[s][v]);
-    }
-    row_store<VEC, LPR, NS>(e.out1, row, F, l, acc);
-}
-
-// rows longer than GRAPES_LONG_ROW (skip_long): only the row-local aux term here, the sum by gcn2_chunks_k / gcn2_combine_k
-template <int VEC, int LPR, int NS>
-__global__ __launch_bounds__(256) void gcn2_rows_k(G2Epi e, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ csr,
-                                                   int n_host, const int32_t* d_n, int F, int skip_long, int32_t* status) {
-    const int n = eff_count(d_n, n_host);
-    const int l = threadIdx.x % LPR, G = 256 / LPR;
-    for (int row = blockIdx.x * G + threadIdx.x / LPR; row < n; row += gridDim.x * G) {
-        const int beg = rowptr[row], end = rowptr[row + 1];
-        if (e.aux) {
-            float d[NS][VEC], a[NS][VEC];
-            row_load<VEC, LPR, NS>(e.src, row, F, l, d);
-            if (e.aux_accumulate) row_load<VEC, LPR, NS>(e.aux, row, F, l, a);
+            for (int v = 0; v < VEC; ++v) acc[s][v] *= c_acc;
+        if (out2) row_store<VEC, LPR, NS>(out2, row, F, l, acc);
+        if (self_mat) {
+            float x0[NS][VEC];
+            row_load<VEC, LPR, NS>(self_mat, row, F, l, x0);
 #pragma unroll
             for (int s = 0; s < NS; ++s)
 #pragma unroll
-                for (int v = 0; v < VEC; ++v) d[s][v] = e.aux_accumulate ? fmaf(e.c_aux, d[s][v], a[s][v]) : e.c_aux * d[s][v];
-            row_store<VEC, LPR, NS>(e.aux, row, F, l, d);
+                for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(c_self, x0[s][v], acc[s][v]);
         }
-        if (skip_long && end - beg > GRAPES_LONG_ROW) continue;
-        float acc[NS][VEC];
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
-        g2_gather<VEC, LPR, NS>(e.src, csr, row, n, beg, end, F, l, acc, status);
-        g2_finish<VEC, LPR, NS>(e, acc, row, F, l);
+        row_store<VEC, LPR, NS>(out1, row, F, l, acc);
     }
-}
-
-// one group per work item (row, chunk): the chunk's sum -> pacc[it F]
-template <int VEC, int LPR, int NS>
-__global__ __launch_bounds__(256) void gcn2_chunks_k(const float* __restrict__ m, const int32_t* __restrict__ rowptr,
-                                                     const int32_t* __restrict__ csr, int n_host, const int32_t* d_n, int F,
-                                                     const int32_t* __restrict__ items, const int32_t* __restrict__ d_n_items,
-                                                     int item_cap, float* __restrict__ pacc, int32_t* status) {
-    const int n = eff_count(d_n, n_host);
-    const int n_items = item_count(d_n_items, item_cap);
-    const int l = threadIdx.x % LPR, G = 256 / LPR;
-    for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
-        int row, beg, end;
-        float acc[NS][VEC];
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
-        item_range(items, it, rowptr, n, row, beg, end);
-        if (beg < end) g2_gather<VEC, LPR, NS>(m, csr, row, n, beg, end, F, l, acc, status);
-        row_store<VEC, LPR, NS>(pacc, it, F, l, acc);
+    __device__ __forceinline__ void finish_col(float a, int row, int, int F, int f) const {
+        const long long o = (long long)row * F + f;
+        a *= c_acc;
+        if (out2) out2[o] = a;
+        out1[o] = self_mat ? fmaf(c_self, self_mat[o], a) : a;
     }
-}
-
-// The item with chunk 0 leads its row: its nc items are contiguous and in chunk order.  One workgroup per long row, a thread per
-// column: the items added in chunk order, then the epilogue of g2_finish.
-__global__ __launch_bounds__(256) void gcn2_combine_k(G2Epi e, const int32_t* __restrict__ rowptr, int n_host, const int32_t* d_n,
-                                                      int F, const int32_t* __restrict__ items,
-                                                      const int32_t* __restrict__ d_n_items, int item_cap,
-                                                      const float* __restrict__ pacc) {
-    const int n = eff_count(d_n, n_host);
-    const int n_items = item_count(d_n_items, item_cap);
-    for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
-        int row, nc;
-        if (!item_leads(items, it, n_items, rowptr, n, row, nc)) continue;
-        const float lf = e.loops ? (float)e.loops[row] : 0.f;
-        for (int f = threadIdx.x; f < F; f += 256) {
-            float a = 0.f;
-            int c = 0;
-            for (; c + 4 <= nc; c += 4) {
-                const float p0 = pacc[(long long)(it + c) * F + f], p1 = pacc[(long long)(it + c + 1) * F + f];
-                const float p2 = pacc[(long long)(it + c + 2) * F + f], p3 = pacc[(long long)(it + c + 3) * F + f];
-                a += p0; a += p1; a += p2; a += p3;
-            }
-            for (; c < nc; ++c) a += pacc[(long long)(it + c) * F + f];
-            const long long o = (long long)row * F + f;
-            if (lf != 0.f) a = fmaf(lf, e.src[o], a);
-            a *= e.c_acc;
-            if (e.out2) e.out2[o] = a;
-            e.out1[o] = e.self_mat ? fmaf(e.c_self, e.self_mat[o], a) : a;
-        }
-    }
-}
+};
 
 // D = ds + ds_add;  dx0 (+)= alpha (add_is_p ? ds : D) + dx0_add   over the first n rows, flat (VEC elements per thread)
 template <int VEC>
@@ -316,23 +210,6 @@ extern "C" size_t grapes_gcn2_propagate_workspace_bytes(int32_t n, int32_t item_
     return grapes_round16(I * F * sizeof(float)) + grapes_round16(N * F * sizeof(float)) + 16;
 }
 
-// the launches of a propagation over (rowptr, csr): rows, and for long rows chunks + combine
-static int g2_propagate(const G2Epi& epi, const int32_t* rowptr, const int32_t* csr, int32_t n, const int32_t* d_n, int32_t f,
-                        bool vec, const int32_t* items, const int32_t* d_n_items, int32_t item_cap, float* pacc, int32_t* status,
-                        hipStream_t s) {
-    const int skip = (items && d_n_items && pacc && item_cap > 0) ? 1 : 0;
-    ROW_LAUNCH(gcn2_rows_k, 16, vec, f, n, s, epi, rowptr, csr, n, d_n, f, skip, status);
-    if (skip) {
-        ROW_LAUNCH(gcn2_chunks_k, 16, vec, f, item_cap, s, epi.src, rowptr, csr, n, d_n, f, items,
-                  d_n_items, item_cap, pacc, status);
-        const int g2 = item_cap < 2048 ? item_cap : 2048;
-        hipLaunchKernelGGL(gcn2_combine_k, dim3(g2), dim3(256), 0, s, epi, rowptr, n, d_n, f, items, d_n_items, item_cap,
-                           (const float*)pacc);
-        GRAPES_LAUNCH_CHECK();
-    }
-    return 0;
-}
-
 extern "C" int grapes_gcn2_propagate_fwd(const float* x, const float* x0, const int32_t* loops, const int32_t* rowptr_t,
                                          const int32_t* csr_src, float alpha, float* s_out, float* p_out, int32_t n,
                                          const int32_t* d_n, int32_t f, const int32_t* long_items, const int32_t* d_n_items,
@@ -344,9 +221,9 @@ extern "C" int grapes_gcn2_propagate_fwd(const float* x, const float* x0, const 
     if (n == 0) return 0;
     const bool vec = f % 4 == 0 && grapes_aligned16(x) && grapes_aligned16(x0) && grapes_aligned16(s_out) && (!p_out || grapes_aligned16(p_out));
     G2Epi epi;
-    epi.src = x; epi.self_mat = x0; epi.loops = loops; epi.out1 = s_out; epi.out2 = p_out; epi.aux = nullptr;
+    epi.src = x; epi.ld_src = f; epi.self_mat = x0; epi.loops = loops; epi.out1 = s_out; epi.out2 = p_out; epi.aux = nullptr;
     epi.c_acc = 1.f - alpha; epi.c_self = alpha; epi.c_aux = 0.f; epi.aux_accumulate = 0;
-    return g2_propagate(epi, rowptr_t, csr_src, n, d_n, f, vec, use_items ? long_items : nullptr, d_n_items, item_cap,
+    return row_sum_propagate<16>(epi, rowptr_t, csr_src, n, d_n, f, vec, use_items ? long_items : nullptr, d_n_items, item_cap,
                         (float*)workspace, status, (hipStream_t)stream);
 }
 
@@ -368,7 +245,7 @@ extern "C" int grapes_gcn2_propagate_bwd(const float* ds, const float* ds_add, i
     float* pacc = (float*)workspace;
     float* dsum = (float*)((char*)workspace + grapes_round16((size_t)(item_cap > 0 ? item_cap : 0) * f * sizeof(float)));
     G2Epi epi;
-    epi.src = ds; epi.self_mat = nullptr; epi.loops = loops; epi.out1 = dx; epi.out2 = nullptr;
+    epi.src = ds; epi.ld_src = f; epi.self_mat = nullptr; epi.loops = loops; epi.out1 = dx; epi.out2 = nullptr;
     epi.aux = dx0; epi.c_acc = 1.f - alpha; epi.c_self = 0.f; epi.c_aux = alpha; epi.aux_accumulate = accumulate_x0 ? 1 : 0;
     if (two) {
         if (vec) hipLaunchKernelGGL(gcn2_bwd_sum_k<4>, dim3(flat_grid(n, f, 4)), dim3(256), 0, s, ds, ds_add, add_is_p ? 1 : 0,
@@ -378,7 +255,7 @@ extern "C" int grapes_gcn2_propagate_bwd(const float* ds, const float* ds_add, i
         GRAPES_LAUNCH_CHECK();
         epi.src = dsum; epi.aux = nullptr;
     }
-    return g2_propagate(epi, rowptr_s, csr_dst, n, d_n, f, vec, use_items ? items_s : nullptr, d_n_items_s, item_cap, pacc, status, s);
+    return row_sum_propagate<16>(epi, rowptr_s, csr_dst, n, d_n, f, vec, use_items ? items_s : nullptr, d_n_items_s, item_cap, pacc, status, s);
 }
 
 extern "C" int grapes_gcn2_mix_fwd(const float* s_in, const float* t1, const float* t2, float c0, float c1, float c2, int32_t relu,

@@ -1,5 +1,6 @@
-// The scaffold the row-gather aggregations share (gat_kernels.hip, gatv2_kernels.hip, gcn2_kernels.hip, pna_kernels.hip): a new aggregation starts
-// here and adds only its own arithmetic.  Every one of them walks the CSRs grapes_gcn_prepare builds with the same three kernels:
+// The scaffold the row-gather aggregations share (gat_, gatv2_, gcn2_, pna_, sage_ and wgcn_kernels.hip): a new aggregation starts
+// here and adds only its own arithmetic; one that is a plain row sum with a row-local epilogue starts at row_sum.h.  Every one of
+// them walks the CSRs grapes_gcn_prepare builds with the same three kernels:
 //
 //   *_rows_k      a group of LPR lanes (half a wavefront or a whole one) owns a row; per batch of LPR entries every lane reads ONE
 //                 column index (batch_entry), then the batch's rows are gathered with the indices broadcast from their lanes
@@ -160,8 +161,8 @@ __device__ __forceinline__ bool gat_entry(const int32_t* __restrict__ csr, int t
     return true;
 }
 
-// gathered rows a group keeps in flight per step of an attention kernel (gat_kernels.hip, gatv2_kernels.hip)
-template <int NS> struct GatUnroll { static constexpr int U = NS == 1 ? 4 : 2; };
+// gathered rows a group keeps in flight per step of a gather loop: independent row loads, as many as the registers of NS slabs allow
+template <int NS> struct RowUnroll { static constexpr int U = NS == 1 ? 4 : (NS <= 4 ? 2 : 1); };
 
 // ------------------------------------------------------------------------------------------------------------ host side
 
@@ -172,6 +173,15 @@ static inline int row_grid(int rows, int lanes) {
 static inline int flat_grid(int64_t n, int64_t f, int vec) {
     int64_t g = (n * f / vec + 255) / 256;
     return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
+}
+
+// The column shape of a width-f gather whose wide scalar form is not built (ROW_LAUNCH with NS_WIDE = 4) — 0: float4 columns,
+// 1: scalar columns, negative: not covered (GRAPES_EALIGN where alignment alone stands in the way)
+static inline int gather_shape(int f, bool aligned) {
+    if (f < 1) return GRAPES_EINVAL;
+    if (f % 4 == 0 && aligned) return f <= 1024 ? 0 : GRAPES_EINVAL;
+    if (f <= 256) return 1;
+    return f % 4 == 0 && f <= 1024 ? GRAPES_EALIGN : GRAPES_EINVAL;
 }
 
 // KERNEL<VEC, LPR, NS> over `rows` rows or work items, a group of LPR lanes each: lanes per row and slabs per lane by width —

@@ -23,18 +23,18 @@
 //                  word < T and the first positions with word == T.  Two to five generations of the keys: linear in deg, no sort,
 //                  nothing through global memory.  Integer arithmetic only.
 //
-// ---- the aggregation (grapes_sage_aggregate_fwd / _bwd), on the row-gather scaffold (row_gather.h):
+// ---- the aggregation (grapes_sage_aggregate_fwd / _bwd), the plain-sum gather shared with GCN2Conv (row_sum.h):
 //   out[i] = act(s_i (sum_{j in row i} src[j] + loops[i] src[i]) + add[i] + bias),  s_i = 1 / deg_i (mean) or 1 (sum),
 //   deg_i = (rowptr[i + 1] - rowptr[i]) + loops[i]: the scale is applied ONCE per row, there is no per-edge weight; an empty row
 //   aggregates to 0.  src, add, out (and copy: copy[i] = src[i], the root operand of the aggregate-first form) have their own
 //   leading dimensions, so halves of one GEMM output are used in place.
-//   sage_rows_k / sage_chunks_k / sage_combine_k   the scaffold's three kernels
+//   row_sum_rows_k / row_sum_chunks_k / row_sum_combine_k   the shared kernels; SageEpi below is their epilogue
 //   sage_gate_k / sage_colsum_k    backward: g = dout gated by relu_out > 0, dadd = g, gs = s g, and the column sums of g as
 //                                  per-slab partials added in a fixed order
 // The backward propagation is the SAME gather over the by-source CSR on the pre-scaled rows gs.  No float atomics: every sum has a
 // fixed order (entry order inside a row, chunk order across work items, slab order for the bias), two runs are bit-identical.
 // No kernel waits on another workgroup.
-#include "row_gather.h"
+#include "row_sum.h"
 #include "philox.h"
 
 #define SAGE_SCAN_THREADS 1024
@@ -328,151 +328,53 @@ extern "C" int grapes_sage_sample_layer(const int64_t* rowptr, const int32_t* co
 
 // ------------------------------------------------------------------------------------------------------------ the aggregation
 
-template <int NS> struct SageUnroll { static constexpr int U = NS == 1 ? 4 : 2; };
-
-// acc += sum of the rows m[csr[t]], t in [beg, end), rows ld floats apart.  An index outside [0, n) raises
-// GRAPES_STATUS_BAD_INDEX and the entry is dropped (its lane loads the row itself and adds nothing, so the loads need no predicate).
-template <int VEC, int LPR, int NS>
-__device__ __forceinline__ void sage_gather(const float* __restrict__ m, long long ld, const int32_t* __restrict__ csr, int row, int n,
-                                            int beg, int end, int F, int l, float (&acc)[NS][VEC], int32_t* status) {
-    constexpr int U = SageUnroll<NS>::U;
-    for (int b = beg; b < end; b += LPR) {
-        const int c = batch_entry(csr, b + l, end, n, status);
-        const int idx = c < 0 ? row : c;
-        const int live = c < 0 ? 0 : 1;
-        const int cnt = end - b < LPR ? end - b : LPR;
-        for (int k = 0; k < cnt; k += U) {
-            float hv[U][NS][VEC];
-            int lk[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int ik = __shfl(idx, k + u, LPR);
-                lk[u] = k + u < cnt ? __shfl(live, k + u, LPR) : 0;
-                row_load_ld<VEC, LPR, NS>(m, ik, ld, F, l, hv[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int s = 0; s < NS; ++s)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[s][v] += lk[u] ? hv[u][s][v] : 0.f;
-        }
-    }
-}
-
-// What a row's sum becomes:  out[row] = act(s (sum + loops[row] src[row]) + add[row] + bias),  s = 1 / ((end - beg) + loops[row]) when
-// mean (0 for an empty row) else 1.  add, bias and loops are optional.
-struct SageEpi {
-    const float* src; long long ld_src;
-    const float* add; long long ld_add;
-    const float* bias;
-    const int32_t* loops;
-    float* out; long long ld_out;
-    float* copy; long long ld_copy;
-    int mean, relu;
-};
-
 __device__ __forceinline__ float sage_scale(int mean, int deg) {
     return mean ? (deg > 0 ? 1.0f / (float)deg : 0.f) : 1.f;
 }
 
-template <int VEC, int LPR, int NS>
-__device__ __forceinline__ void sage_finish(const SageEpi& e, float (&acc)[NS][VEC], int row, int cnt, int F, int l) {
-    const int lp = e.loops ? e.loops[row] : 0;
-    if (lp != 0) {
+// The epilogue of the shared row sum (row_sum.h), p = the row's sum + loops[row] src[row]:
+//   out[row] = act(s p + add[row] + bias),  s = 1 / deg when mean (0 for an empty row) else 1;  copy[row] = src[row] (every row, long or
+//   not).  add, bias, loops and copy are optional.
+struct SageEpi {
+    const float* src; long long ld_src;
+    const int32_t* loops;
+    const float* add; long long ld_add;
+    const float* bias;
+    float* out; long long ld_out;
+    float* copy; long long ld_copy;
+    int mean, relu;
+
+    template <int VEC, int LPR, int NS>
+    __device__ __forceinline__ void pre(int row, int F, int l) const {
+        if (!copy) return;
         float xr[NS][VEC];
-        row_load_ld<VEC, LPR, NS>(e.src, row, e.ld_src, F, l, xr);
-        const float lf = (float)lp;
+        row_load_ld<VEC, LPR, NS>(src, row, ld_src, F, l, xr);
+        row_store_ld<VEC, LPR, NS>(copy, row, ld_copy, F, l, xr);
+    }
+    template <int VEC, int LPR, int NS>
+    __device__ __forceinline__ void finish(float (&acc)[NS][VEC], int row, int deg, int F, int l) const {
+        const float sc = sage_scale(mean, deg);
+        float ad[NS][VEC];
+        if (add) row_load_ld<VEC, LPR, NS>(add, row, ld_add, F, l, ad);
 #pragma unroll
         for (int s = 0; s < NS; ++s)
 #pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(lf, xr[s][v], acc[s][v]);
+            for (int v = 0; v < VEC; ++v) {
+                float o = acc[s][v] * sc;
+                if (add) o += ad[s][v];
+                const int f = (s * LPR + l) * VEC + v;
+                if (bias && f < F) o += bias[f];
+                acc[s][v] = relu ? fmaxf(o, 0.f) : o;
+            }
+        row_store_ld<VEC, LPR, NS>(out, row, ld_out, F, l, acc);
     }
-    const float sc = sage_scale(e.mean, cnt + lp);
-    float ad[NS][VEC];
-    if (e.add) row_load_ld<VEC, LPR, NS>(e.add, row, e.ld_add, F, l, ad);
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) {
-            float o = acc[s][v] * sc;
-            if (e.add) o += ad[s][v];
-            const int f = (s * LPR + l) * VEC + v;
-            if (e.bias && f < F) o += e.bias[f];
-            acc[s][v] = e.relu ? fmaxf(o, 0.f) : o;
-        }
-    row_store_ld<VEC, LPR, NS>(e.out, row, e.ld_out, F, l, acc);
-}
-
-// rows longer than GRAPES_LONG_ROW (skip_long): only the row-local copy here, the sum by sage_chunks_k / sage_combine_k
-template <int VEC, int LPR, int NS>
-__global__ __launch_bounds__(256) void sage_rows_k(SageEpi e, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ csr,
-                                                   int n_host, const int32_t* d_n, int F, int skip_long, int32_t* status) {
-    const int n = eff_count(d_n, n_host);
-    const int l = threadIdx.x % LPR, G = 256 / LPR;
-    for (int row = blockIdx.x * G + threadIdx.x / LPR; row < n; row += gridDim.x * G) {
-        const int beg = rowptr[row], end = rowptr[row + 1];
-        if (e.copy) {
-            float xr[NS][VEC];
-            row_load_ld<VEC, LPR, NS>(e.src, row, e.ld_src, F, l, xr);
-            row_store_ld<VEC, LPR, NS>(e.copy, row, e.ld_copy, F, l, xr);
-        }
-        if (skip_long && end - beg > GRAPES_LONG_ROW) continue;
-        float acc[NS][VEC];
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
-        sage_gather<VEC, LPR, NS>(e.src, e.ld_src, csr, row, n, beg, end, F, l, acc, status);
-        sage_finish<VEC, LPR, NS>(e, acc, row, end - beg, F, l);
+    __device__ __forceinline__ void finish_col(float a, int row, int deg, int, int f) const {
+        float o = a * sage_scale(mean, deg);
+        if (add) o += add[(long long)row * ld_add + f];
+        if (bias) o += bias[f];
+        out[(long long)row * ld_out + f] = relu ? fmaxf(o, 0.f) : o;
     }
-}
-
-// one group per work item (row, chunk): the chunk's sum -> pacc[it F]
-template <int VEC, int LPR, int NS>
-__global__ __launch_bounds__(256) void sage_chunks_k(const float* __restrict__ m, long long ld, const int32_t* __restrict__ rowptr,
-                                                     const int32_t* __restrict__ csr, int n_host, const int32_t* d_n, int F,
-                                                     const int32_t* __restrict__ items, const int32_t* __restrict__ d_n_items,
-                                                     int item_cap, float* __restrict__ pacc, int32_t* status) {
-    const int n = eff_count(d_n, n_host);
-    const int n_items = item_count(d_n_items, item_cap);
-    const int l = threadIdx.x % LPR, G = 256 / LPR;
-    for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
-        int row, beg, end;
-        float acc[NS][VEC];
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
-        item_range(items, it, rowptr, n, row, beg, end);
-        if (beg < end) sage_gather<VEC, LPR, NS>(m, ld, csr, row, n, beg, end, F, l, acc, status);
-        row_store<VEC, LPR, NS>(pacc, it, F, l, acc);
-    }
-}
-
-// one workgroup per long row (led by its chunk-0 item), a thread per column: the items added in chunk order, then sage_finish's epilogue
-__global__ __launch_bounds__(256) void sage_combine_k(SageEpi e, const int32_t* __restrict__ rowptr, int n_host, const int32_t* d_n,
-                                                      int F, const int32_t* __restrict__ items,
-                                                      const int32_t* __restrict__ d_n_items, int item_cap,
-                                                      const float* __restrict__ pacc) {
-    const int n = eff_count(d_n, n_host);
-    const int n_items = item_count(d_n_items, item_cap);
-    for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
-        int row, nc;
-        if (!item_leads(items, it, n_items, rowptr, n, row, nc)) continue;
-        const int lp = e.loops ? e.loops[row] : 0;
-        const float sc = sage_scale(e.mean, (rowptr[row + 1] - rowptr[row]) + lp);
-        for (int f = threadIdx.x; f < F; f += 256) {
-            float a = 0.f;
-            for (int c = 0; c < nc; ++c) a += pacc[(long long)(it + c) * F + f];
-            if (lp != 0) a = fmaf((float)lp, e.src[(long long)row * e.ld_src + f], a);
-            float o = a * sc;
-            if (e.add) o += e.add[(long long)row * e.ld_add + f];
-            if (e.bias) o += e.bias[f];
-            e.out[(long long)row * e.ld_out + f] = e.relu ? fmaxf(o, 0.f) : o;
-        }
-    }
-}
+};
 
 // Backward, row-local: g = dout gated by relu_out > 0;  dadd = g;  gs = s g (rows F floats apart);  part[slab] = the column sums of g
 // over the slab's SAGE_SLAB rows: thread (rg, column) adds the rows rg, rg + 4, ... of the slab, the four sums meet in rg order.
@@ -520,31 +422,7 @@ __global__ __launch_bounds__(256) void sage_colsum_k(const float* __restrict__ p
 
 // ------------------------------------------------------------------------------------------------------------ host side
 
-// 0: float4 columns, 1: scalar columns, negative: not covered
-static inline int sage_shape(int f, bool aligned) {
-    if (f < 1) return GRAPES_EINVAL;
-    if (f % 4 == 0 && aligned) return f <= 1024 ? 0 : GRAPES_EINVAL;
-    if (f <= 256) return 1;
-    return f % 4 == 0 && f <= 1024 ? GRAPES_EALIGN : GRAPES_EINVAL;
-}
 static inline bool sage_vec_ok(const void* p, int64_t ld) { return !p || (grapes_aligned16(p) && ld % 4 == 0); }
-
-// the launches of a gather over (rowptr, csr): rows, and for long rows chunks + combine
-static int sage_propagate(const SageEpi& epi, const int32_t* rowptr, const int32_t* csr, int32_t n, const int32_t* d_n, int32_t f,
-                          bool vec, const int32_t* items, const int32_t* d_n_items, int32_t item_cap, float* pacc, int32_t* status,
-                          hipStream_t s) {
-    const int skip = (items && d_n_items && pacc && item_cap > 0) ? 1 : 0;
-    ROW_LAUNCH(sage_rows_k, 4, vec, f, n, s, epi, rowptr, csr, n, d_n, f, skip, status);
-    if (skip) {
-        ROW_LAUNCH(sage_chunks_k, 4, vec, f, item_cap, s, epi.src, epi.ld_src, rowptr, csr, n, d_n, f, items, d_n_items, item_cap, pacc,
-                   status);
-        const int g2 = item_cap < 2048 ? item_cap : 2048;
-        hipLaunchKernelGGL(sage_combine_k, dim3(g2), dim3(256), 0, s, epi, rowptr, n, d_n, f, items, d_n_items, item_cap,
-                           (const float*)pacc);
-        GRAPES_LAUNCH_CHECK();
-    }
-    return 0;
-}
 
 static inline size_t sage_slabs(int32_t n) { return n > 0 ? ((size_t)n + SAGE_SLAB - 1) / SAGE_SLAB : 0; }
 
@@ -565,14 +443,14 @@ extern "C" int grapes_sage_aggregate_fwd(const float* src, int64_t ld_src, const
     if (out == src || copy_out == src || (copy_out && copy_out == out)) return GRAPES_EINVAL;
     const bool use_items = long_items && d_n_items && workspace && item_cap > 0;
     if (use_items && !grapes_aligned16(workspace)) return GRAPES_EALIGN;
-    const int shape = sage_shape(f, sage_vec_ok(src, ld_src) && sage_vec_ok(add, ld_add) && sage_vec_ok(out, ld_out) &&
+    const int shape = gather_shape(f, sage_vec_ok(src, ld_src) && sage_vec_ok(add, ld_add) && sage_vec_ok(out, ld_out) &&
                                     sage_vec_ok(copy_out, ld_copy) && (!bias || grapes_aligned16(bias)));
     if (shape < 0) return shape;
     if (n == 0) return 0;
     SageEpi epi;
     epi.src = src; epi.ld_src = ld_src; epi.add = add; epi.ld_add = ld_add; epi.bias = bias; epi.loops = loops;
     epi.out = out; epi.ld_out = ld_out; epi.copy = copy_out; epi.ld_copy = ld_copy; epi.mean = mean ? 1 : 0; epi.relu = relu ? 1 : 0;
-    return sage_propagate(epi, rowptr_t, csr_src, n, d_n, f, shape == 0, use_items ? long_items : nullptr, d_n_items, item_cap,
+    return row_sum_propagate<4>(epi, rowptr_t, csr_src, n, d_n, f, shape == 0, use_items ? long_items : nullptr, d_n_items, item_cap,
                           (float*)workspace, status, (hipStream_t)stream);
 }
 
@@ -590,7 +468,7 @@ extern "C" int grapes_sage_aggregate_bwd(const float* dout, int64_t ld_dout, con
     if ((pass || use_items) && !workspace) return GRAPES_EINVAL;
     if (workspace && !grapes_aligned16(workspace)) return GRAPES_EALIGN;
     const bool src_ok = pass ? true : sage_vec_ok(dout, ld_dout);
-    const int shape = sage_shape(f, src_ok && sage_vec_ok(add, ld_add) && sage_vec_ok(dsrc, ld_dsrc));
+    const int shape = gather_shape(f, src_ok && sage_vec_ok(add, ld_add) && sage_vec_ok(dsrc, ld_dsrc));
     if (shape < 0) return shape;
     if (n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -614,6 +492,6 @@ extern "C" int grapes_sage_aggregate_bwd(const float* dout, int64_t ld_dout, con
     SageEpi epi;
     epi.src = pass ? gs : dout; epi.ld_src = pass ? f : ld_dout; epi.add = add; epi.ld_add = ld_add; epi.bias = nullptr;
     epi.loops = loops; epi.out = dsrc; epi.ld_out = ld_dsrc; epi.copy = nullptr; epi.ld_copy = 0; epi.mean = 0; epi.relu = 0;
-    return sage_propagate(epi, rowptr_s, csr_dst, n, d_n, f, shape == 0, use_items ? items_s : nullptr, d_n_items_s, item_cap, pacc,
+    return row_sum_propagate<4>(epi, rowptr_s, csr_dst, n, d_n, f, shape == 0, use_items ? items_s : nullptr, d_n_items_s, item_cap, pacc,
                           status, s);
 }

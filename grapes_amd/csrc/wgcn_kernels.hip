@@ -47,8 +47,6 @@ enum { WG_ACC = 0, WG_ACC_DOT = 1, WG_DOT = 2 };
 // the rule for lw and the normalisation: GRAPES_WGCN_LOOP_FILL / _LOOP_SUM / _UNNORMALIZED of the header
 enum { WG_LOOP_FILL = GRAPES_WGCN_LOOP_FILL, WG_LOOP_SUM = GRAPES_WGCN_LOOP_SUM, WG_UNNORM = GRAPES_WGCN_UNNORMALIZED };
 
-template <int NS> struct WgUnroll { static constexpr int U = NS == 1 ? 4 : 2; };
-
 template <int VEC, int NS>
 __device__ __forceinline__ float wg_dot(const float (&a)[NS][VEC], const float (&b)[NS][VEC]) {
     float d = 0.f;
@@ -77,7 +75,7 @@ __device__ __forceinline__ float wg_range(const float* __restrict__ m, const int
                                           const float* __restrict__ dinv, int row, int n, int beg, int end, int F, int l,
                                           float (&acc)[NS][VEC], const float (&oth)[NS][VEC], float* __restrict__ pslot,
                                           int32_t* status) {
-    constexpr int U = WgUnroll<NS>::U;
+    constexpr int U = RowUnroll<NS>::U;
     float part = 0.f;
     for (int b = beg; b < end; b += LPR) {
         const int c = batch_entry(csr, b + l, end, n, status);
@@ -624,13 +622,6 @@ __global__ __launch_bounds__(256) void wgcn_weights_k(const float* __restrict__ 
 
 // ------------------------------------------------------------------------------------------------------------ host side
 
-// 0: float4 columns, 1: scalar columns, negative: not covered
-static inline int wg_shape(int f, bool aligned) {
-    if (f < 1) return GRAPES_EINVAL;
-    if (f % 4 == 0 && aligned) return f <= 1024 ? 0 : GRAPES_EINVAL;
-    if (f <= 256) return 1;
-    return f % 4 == 0 && f <= 1024 ? GRAPES_EALIGN : GRAPES_EINVAL;
-}
 static inline int wg_flat_grid(int count) {
     int g = grapes_div_up(count > 0 ? count : 1, 256);
     return g > 4096 ? 4096 : g;
@@ -797,7 +788,7 @@ static int wg_forward(const float* h, const int32_t* rowptr_t, const int32_t* cs
     if (!h || !rowptr_t || !csr_src || !val_t || (norm && !dinv) || !lw || !out || out == h || n < 0) return GRAPES_EINVAL;
     const bool use_items = long_items && d_n_items && workspace && item_cap > 0;
     if (use_items && !grapes_aligned16(workspace)) return GRAPES_EALIGN;
-    const int shape = wg_shape(f, grapes_aligned16(h) && grapes_aligned16(out) && (!bias || grapes_aligned16(bias)));
+    const int shape = gather_shape(f, grapes_aligned16(h) && grapes_aligned16(out) && (!bias || grapes_aligned16(bias)));
     if (shape < 0) return shape;
     if (n == 0) return 0;
     WgEpi epi;
@@ -849,7 +840,7 @@ static int wg_backward(const float* dout, const float* relu_out, const float* h,
         return GRAPES_EINVAL;
     if (dh && (dh == dout || dh == h)) return GRAPES_EINVAL;
     if (!grapes_aligned16(workspace)) return GRAPES_EALIGN;
-    const int shape = wg_shape(f, grapes_aligned16(dout) && (!dh || grapes_aligned16(dh)) && (!relu_out || grapes_aligned16(relu_out)) &&
+    const int shape = gather_shape(f, grapes_aligned16(dout) && (!dh || grapes_aligned16(dh)) && (!relu_out || grapes_aligned16(relu_out)) &&
                                       (!dw || grapes_aligned16(h)));
     if (shape < 0) return shape;
     if (n == 0) return 0;

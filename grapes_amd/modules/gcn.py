@@ -433,10 +433,11 @@ def _refuse_large(edge_index, who: str):
                          "full_graph.py is GCN only")
 
 
-def _gat_graph(edge_index, n: int) -> ops.PreparedGraph:
-    """The layer's graph: a PreparedGraph, an edge-index tensor, or a DeviceGraph below 2^31 entries."""
-    _refuse_large(edge_index, "GAT")
-    return prepare_edges(edge_index, n)
+def _layer_graph(edge_index, n: int, who: str, loops: bool) -> ops.PreparedGraph:
+    """The graph of layer `who`: a PreparedGraph, an edge-index tensor, or a DeviceGraph below 2^31 entries — with its stored-self-loop
+    counts (_gcn2_graph) for the layers that aggregate the adjacency as stored (loops: PNAConv and SAGEConv, like GCN2Conv)."""
+    _refuse_large(edge_index, who)
+    return _gcn2_graph(edge_index, n) if loops else prepare_edges(edge_index, n)
 
 
 class GATConv(nn.Module):
@@ -469,7 +470,7 @@ class GATConv(nn.Module):
 
     def forward(self, x, edge_index, relu: bool = False):
         x = _cuda_f32(x, "GATConv")
-        prep = _gat_graph(edge_index, x.shape[0])
+        prep = _layer_graph(edge_index, x.shape[0], "GAT", loops=False)
         return _GATConvFn.apply(x, self.lin.weight, self.att_src, self.att_dst, self.bias, prep, relu)
 
 
@@ -585,7 +586,7 @@ class GATv2Conv(nn.Module):
 
     def forward(self, x, edge_index, relu: bool = False):
         x = _cuda_f32(x, "GATv2Conv")
-        prep = _gat_graph(edge_index, x.shape[0])
+        prep = _layer_graph(edge_index, x.shape[0], "GAT", loops=False)
         shared = self.share_weights
         return _GATv2ConvFn.apply(x, self.lin_l.weight, self.lin_l.bias, None if shared else self.lin_r.weight,
                                   None if shared else self.lin_r.bias, self.att, self.bias, prep, self.heads, self.concat,
@@ -859,12 +860,6 @@ class _PNAConvFn(torch.autograd.Function):
         return dx, dw_pre, db2[:f].contiguous(), dw_post, db_post, dw_lin, db_lin, None, None, None
 
 
-def _pna_graph(edge_index, n: int) -> ops.PreparedGraph:
-    """The layer's graph with its stored-self-loop counts (PNAConv aggregates the adjacency as stored, like GCN2Conv)."""
-    _refuse_large(edge_index, "PNA")
-    return _gcn2_graph(edge_index, n)
-
-
 class PNAConv(nn.Module):
     """PyG PNAConv(in_channels, out_channels, aggregators, scalers, deg) as modules/gcn.py:130-131 builds it, every other
     argument at its default [PyG-recall]: one tower, pre_nn = Linear(2 F, F) on [x_i | x_j] per stored edge (j -> i), the
@@ -901,7 +896,7 @@ class PNAConv(nn.Module):
         x = _cuda_f32(x, "PNAConv")
         if x.shape[1] != self.in_channels:
             raise ValueError(f"PNAConv: width {x.shape[1]} != in_channels {self.in_channels}")
-        prep = _pna_graph(edge_index, x.shape[0])
+        prep = _layer_graph(edge_index, x.shape[0], "PNA", loops=True)
         return _PNAConvFn.apply(x, self.pre_nn.weight, self.pre_nn.bias, self.post_nn.weight, self.post_nn.bias, self.lin.weight,
                                 self.lin.bias, prep, self.cfg, relu)
 
@@ -1009,12 +1004,6 @@ class _SAGEConvFn(torch.autograd.Function):
         return dx, dw_l, dw_r, dbias, None, None, None, None, None
 
 
-def _sage_graph(edge_index, n: int) -> ops.PreparedGraph:
-    """The layer's graph with its stored-self-loop counts (SAGEConv aggregates the adjacency as stored, like GCN2Conv and PNAConv)."""
-    _refuse_large(edge_index, "SAGE")
-    return _gcn2_graph(edge_index, n)
-
-
 class _SAGELin(nn.Module):
     """The parameters of one of SAGEConv's two linear maps under PyG's names: `weight` [out, in] and, for lin_l, `bias`."""
 
@@ -1074,8 +1063,8 @@ class SAGEConv(nn.Module):
     def form_ok(self, form: str) -> bool:
         """Whether an operand form can run these widths (aggregate-first also needs two output columns for its fused GEMM)."""
         if form == "aggregate":
-            return ops.sage_width_ok(self.in_channels) and self.out_channels >= 2
-        return ops.sage_width_ok(self.out_channels)
+            return ops.gather_width_ok(self.in_channels) and self.out_channels >= 2
+        return ops.gather_width_ok(self.out_channels)
 
     def default_form(self) -> str:
         if self.in_channels < self.out_channels and self.form_ok("aggregate"):
@@ -1089,7 +1078,7 @@ class SAGEConv(nn.Module):
         form = self.default_form() if _form is None else _form
         if form not in ("transform", "aggregate") or not self.form_ok(form):
             raise ValueError(f"SAGEConv: the {form!r} form is not built for {self.in_channels} -> {self.out_channels}")
-        prep = _sage_graph(edge_index, x.shape[0])
+        prep = _layer_graph(edge_index, x.shape[0], "SAGE", loops=True)
         return _SAGEConvFn.apply(x, self.lin_l.weight, self.lin_r.weight if self.lin_r is not None else None, self.lin_l.bias, prep,
                                  self.aggr, relu, form == "aggregate", _long_rows)
 

@@ -1490,15 +1490,26 @@ def gcn_aggregate_bwd(dout, prep: PreparedGraph, relu_out=None, want_bias=True, 
 
 
 # ------------------------------------------------------------------------------- GATConv aggregation (modules/gcn.py:45-72)
-def _gat_width(f: int):
-    if f < 1 or f > 1024 or (f > 256 and f % 4):
-        raise ValueError(f"GAT aggregation: width {f} is not built (any width up to 256, multiples of 4 up to 1024)")
+def gather_width_ok(f: int, wide_scalar: bool = False) -> bool:
+    """The widths the row-gather kernels are built for (csrc/row_gather.h, ROW_LAUNCH): float4 columns up to 1024, scalar columns up
+    to 256 — or, where the wide scalar form is built too (wide_scalar: GCN2), any width up to 1024."""
+    return 1 <= f <= 1024 and (wide_scalar or f <= 256 or f % 4 == 0)
 
 
-def _long_items(prep, by_target: bool, forward: bool):
+def _gather_width(f: int, who: str, wide_scalar: bool = False):
+    if not gather_width_ok(f, wide_scalar):
+        built = "any width up to 1024" if wide_scalar else "any width up to 256, multiples of 4 up to 1024"
+        raise ValueError(f"{who}: width {f} is not built ({built})")
+
+
+def _long_items(prep, by_target: bool, forward: bool, long_rows: Optional[bool] = None):
     """(items, n_items, cap) as the row-gather entry points take them: prep's long-row work items by target or by source, or
-    (None, None, 0) where every row runs in the rows kernel — a small graph, or a forward over a graph prepared without them."""
-    if prep.n <= _SMALL_GRAPH or (forward and not prep.items_fwd):
+    (None, None, 0) where every row runs in the rows kernel — a forward over a graph prepared without them, or a graph that counts
+    as small.  long_rows None: up to _SMALL_GRAPH nodes is small.  True: no graph is (GATv2: one head's score costs a whole row of
+    arithmetic per edge, so a hub row is worth its own workgroups on a small graph too).  False: every graph is.  Tests force
+    either form."""
+    small = prep.n <= _SMALL_GRAPH if long_rows is None else not long_rows
+    if small or (forward and not prep.items_fwd):
         return None, None, 0
     items, n_items = (prep.items_t, prep.n_items_t) if by_target else (prep.items_s, prep.n_items_s)
     return _p(items), _p(n_items), prep.item_cap
@@ -1508,7 +1519,7 @@ def gat_scores(h, a_src, a_dst, d_n=None):
     """(s_src, s_dst) = (H a_src, H a_dst): the per-node halves of GATConv's attention logits, one read of H."""
     _chk(h, _f32, "h"); _chk(a_src, _f32, "a_src"); _chk(a_dst, _f32, "a_dst")
     n, f = h.shape
-    _gat_width(f)
+    _gather_width(f, "GAT aggregation")
     if a_src.numel() != f or a_dst.numel() != f:
         raise ValueError("a_src / a_dst must hold one value per column of h")
     s_src = torch.empty(max(n, 1), dtype=_f32, device=h.device)
@@ -1523,7 +1534,7 @@ def gat_aggregate_fwd(h, s_src, s_dst, prep: PreparedGraph, bias=None, relu=Fals
     attention weights from."""
     _chk(h, _f32, "h"); _chk(s_src, _f32, "s_src"); _chk(s_dst, _f32, "s_dst"); _chk(bias, _f32, "bias", True)
     n, f = h.shape
-    _gat_width(f)
+    _gather_width(f, "GAT aggregation")
     if n != prep.n or s_src.numel() < n or s_dst.numel() < n:
         raise ValueError("h, s_src and s_dst need one row per node of the prepared graph")
     if out is None:
@@ -1545,7 +1556,7 @@ def gat_aggregate_bwd(dout, out, h, s_src, s_dst, row_ms, a_src, a_dst, prep: Pr
         _chk(t, _f32, name)
     _chk(bias, _f32, "bias", True)
     n, f = dout.shape
-    _gat_width(f)
+    _gather_width(f, "GAT aggregation")
     if n != prep.n or out.shape != dout.shape or h.shape != dout.shape:
         raise ValueError("dout, out and h must be [n, f] over the prepared graph's nodes")
     dev = dout.device
@@ -1580,16 +1591,6 @@ def _gatv2_slope(negative_slope: float) -> float:
     return float(negative_slope)
 
 
-def _gatv2_items(prep, by_target: bool, forward: bool):
-    """(items, n_items, cap): prep's long-row work items by target or by source, whatever the graph's size — one head's score
-    costs a whole row of arithmetic per edge, so a hub row is worth its own workgroups on a small graph too; (None, None, 0) for a
-    forward over a graph prepared without them."""
-    if forward and not prep.items_fwd:
-        return None, None, 0
-    items, n_items = (prep.items_t, prep.n_items_t) if by_target else (prep.items_s, prep.n_items_s)
-    return _p(items), _p(n_items), prep.item_cap
-
-
 def gatv2_aggregate_fwd(x_l, x_r, att, prep: PreparedGraph, heads: int, concat=True, negative_slope=0.2, bias=None, relu=False):
     """(out, agg, row_ms) of GATv2Conv's propagate over prep's by-target CSR plus one unit self-loop per node: per head h,
     e_ij = att[h] . LeakyReLU(x_l[j, h] + x_r[i, h]), alpha = softmax_j e_ij, agg_i[h] = sum_j alpha_ij x_l[j, h]; out = the heads
@@ -1611,7 +1612,7 @@ def gatv2_aggregate_fwd(x_l, x_r, att, prep: PreparedGraph, heads: int, concat=T
     out = torch.empty((n, f if concat else c), dtype=_f32, device=dev)
     agg = None if concat else torch.empty((n, f), dtype=_f32, device=dev)
     row_ms = torch.empty((max(n, 1), heads, 2), dtype=_f32, device=dev)
-    items, n_items, cap = _gatv2_items(prep, by_target=True, forward=True)
+    items, n_items, cap = _long_items(prep, by_target=True, forward=True, long_rows=True)
     ws = _ws(lib().grapes_gatv2_aggregate_workspace_bytes(cap, f, heads), dev) if cap else None
     _lib.check(lib().grapes_gatv2_aggregate_fwd(_p(x_l), _p(x_r), _p(att), _p(prep.rowptr_t), _p(prep.csr_src), _p(bias), _p(out),
                                                 _p(agg), _p(row_ms), n, _p(prep.d_n), heads, c, 1 if concat else 0, slope,
@@ -1645,8 +1646,8 @@ def gatv2_aggregate_bwd(dout, out, agg, x_l, x_r, att, row_ms, prep: PreparedGra
     dx_l, dx_r = torch.empty_like(x_l), torch.empty_like(x_l)
     datt = torch.empty(f, dtype=_f32, device=dev)
     dbias = torch.empty(w, dtype=_f32, device=dev)
-    items_t, n_items_t, cap = _gatv2_items(prep, by_target=True, forward=False)
-    items_s, n_items_s, _ = _gatv2_items(prep, by_target=False, forward=False)
+    items_t, n_items_t, cap = _long_items(prep, by_target=True, forward=False, long_rows=True)
+    items_s, n_items_s, _ = _long_items(prep, by_target=False, forward=False, long_rows=True)
     ws = _ws(lib().grapes_gatv2_aggregate_bwd_workspace_bytes(n, cap, f, heads), dev)
     _lib.check(lib().grapes_gatv2_aggregate_bwd(_p(dout), _p(out), _p(agg), _p(bias), 1 if relu else 0, _p(x_l), _p(x_r), _p(att),
                                                 _p(row_ms), _p(prep.rowptr_t), _p(prep.csr_src), _p(prep.rowptr_s), _p(prep.csr_dst),
@@ -1657,11 +1658,6 @@ def gatv2_aggregate_bwd(dout, out, agg, x_l, x_r, att, row_ms, prep: PreparedGra
 
 
 # ------------------------------------------------------------------------------- GCN2Conv propagation (modules/gcn.py:76-117)
-def _gcn2_width(f: int):
-    if f < 1 or f > 1024:
-        raise ValueError(f"GCN2 propagation: width {f} is not built (any width up to 1024)")
-
-
 def gcn2_loop_counts(edge_src, edge_dst, n, d_n=None, d_e=None, node_map=None):
     """int32[n]: loops[i] = number of stored edges (i, i) of the edge list a PreparedGraph is built from (the build drops them;
     GCN2Conv(normalize=False) counts them like any edge)."""
@@ -1698,7 +1694,7 @@ def gcn2_propagate_fwd(x, x0, prep: PreparedGraph, alpha: float, want_p: bool = 
     """(S, P'): S = (1 - alpha) (A x + loops * x) + alpha x0 over prep's by-target CSR, P' = S's first term (want_p)."""
     _chk(x, _f32, "x"); _chk(x0, _f32, "x0")
     n, f = x.shape
-    _gcn2_width(f)
+    _gather_width(f, "GCN2 propagation", wide_scalar=True)
     if n != prep.n or tuple(x0.shape) != (n, f):
         raise ValueError("x and x0 must be [n, f] over the prepared graph's nodes")
     loops = gcn2_loops(prep)
@@ -1718,7 +1714,7 @@ def gcn2_propagate_bwd(ds, prep: PreparedGraph, alpha: float, ds_add=None, add_i
     that reaches x0 directly).  A dx0 tensor passed in is accumulated into."""
     _chk(ds, _f32, "ds"); _chk(ds_add, _f32, "ds_add", True); _chk(dx0_add, _f32, "dx0_add", True); _chk(dx0, _f32, "dx0", True)
     n, f = ds.shape
-    _gcn2_width(f)
+    _gather_width(f, "GCN2 propagation", wide_scalar=True)
     if n != prep.n:
         raise ValueError("ds must be [n, f] over the prepared graph's nodes")
     loops = gcn2_loops(prep)
@@ -1842,11 +1838,6 @@ def pna_add_input_grad(dx, dz, d_n=None):
 
 
 # ------------------------------------------------------------------------------- GCNConv with edge weights (PyG GCNConv.forward)
-def _wgcn_width(f: int):
-    if f < 1 or f > 1024 or (f > 256 and f % 4):
-        raise ValueError(f"weighted GCN aggregation: width {f} is not built (any width up to 256, multiples of 4 up to 1024)")
-
-
 WGCN_LOOP_FILL, WGCN_LOOP_SUM, WGCN_UNNORMALIZED = 0, 1, 2      # GRAPES_WGCN_* of grapes_hip.h: the rule for lw, and whether dinv exists
 
 
@@ -1923,7 +1914,7 @@ def wgcn_aggregate_fwd(h, ws: WeightedStructure, vals: WeightedValues, bias=None
     out may hold more rows, which are left alone); with vals of WGCN_UNNORMALIZED out[c] = sum_e w_e h[r] + lw[c] h[c] + bias."""
     _chk(h, _f32, "h"); _chk(bias, _f32, "bias", True); _chk(out, _f32, "out", True)
     prep, (rows, f) = ws.prep, h.shape
-    _wgcn_width(f)
+    _gather_width(f, "weighted GCN aggregation")
     if out is None:
         out = torch.empty_like(h)
     if rows < ws.n or out.shape[0] < ws.n or out.shape[1] != f or (bias is not None and bias.numel() != f):
@@ -1943,7 +1934,7 @@ def wgcn_aggregate_bwd(dout, ws: WeightedStructure, vals: WeightedValues, h=None
     modified."""
     _chk(dout, _f32, "dout"); _chk(relu_out, _f32, "relu_out", True); _chk(h, _f32, "h", True)
     prep, (rows, f) = ws.prep, dout.shape
-    _wgcn_width(f)
+    _gather_width(f, "weighted GCN aggregation")
     if rows < ws.n or (relu_out is not None and relu_out.shape != dout.shape) or (h is not None and h.shape != dout.shape):
         raise ValueError("dout, relu_out and h must be [>= n, f] over the structure's nodes")
     if want_dw and h is None:
@@ -2752,7 +2743,7 @@ def asgcn_variance(edge_src, edge_dst, weight, rows, h, status=None):
     h fp32 [n_local, C] is a constant of the term."""
     _chk(h, _f32, "h"); _chk(status, _i32, "status", True)
     n_local, C = h.shape
-    _wgcn_width(C)
+    _gather_width(C, "weighted GCN aggregation")
     e, m, ws = _asgcn_entries("asgcn_variance", edge_src, edge_dst, weight, rows, n_local)
     dev = h.device
     V, lvar, dw = torch.empty(m, dtype=_f32, device=dev), torch.empty(1, dtype=_f32, device=dev), torch.empty(e, dtype=_f32, device=dev)
@@ -2829,15 +2820,6 @@ def sage_sample_layer(rowptr, col, num_nodes: int, rows, fanout: int, e_cap: Opt
     return src, dst, pos, d_e
 
 
-def _sage_width(f: int):
-    if f < 1 or f > 1024 or (f > 256 and f % 4):
-        raise ValueError(f"SAGE aggregation: width {f} is not built (any width up to 256, multiples of 4 up to 1024)")
-
-
-def sage_width_ok(f: int) -> bool:
-    return 1 <= f <= 1024 and not (f > 256 and f % 4)
-
-
 def _sage_rows(t, name: str, n: int, f: int, allow_none: bool = False):
     """The leading dimension of a row-major [n, f] matrix that may be a column block of a wider one."""
     if t is None:
@@ -2858,16 +2840,6 @@ def _sage_rows(t, name: str, n: int, f: int, allow_none: bool = False):
     return ld
 
 
-def _sage_items(prep, by_target: bool, forward: bool, long_rows: Optional[bool]):
-    """_long_items' rule (long_rows None), prep's work items whatever the graph's size (True) or every row by one group (False)."""
-    if long_rows is None:
-        return _long_items(prep, by_target, forward)
-    if not long_rows or (forward and not prep.items_fwd):
-        return None, None, 0
-    items, n_items = (prep.items_t, prep.n_items_t) if by_target else (prep.items_s, prep.n_items_s)
-    return _p(items), _p(n_items), prep.item_cap
-
-
 def _sage_aggr(aggr: str) -> int:
     if aggr not in SAGE_AGGRS:
         raise NotImplementedError(f"SAGE aggregation {aggr!r} is not built (built: {', '.join(SAGE_AGGRS)})")
@@ -2878,9 +2850,9 @@ def sage_aggregate_fwd(src, prep: PreparedGraph, aggr: str = "mean", add=None, b
                        long_rows: Optional[bool] = None):
     """out[i] = act(s_i (sum_{j -> i} src[j] + loops[i] src[i]) + add[i] + bias) over prep's by-target CSR and its stored loops,
     s_i = 1 / deg_i (mean; an empty row gives 0) or 1 (sum).  src, add, out and copy_out ([n, f]) may be column blocks of wider
-    matrices (rows contiguous); copy_out[i] = src[i].  long_rows: see _sage_items (tests force either form)."""
+    matrices (rows contiguous); copy_out[i] = src[i].  long_rows: see _long_items (tests force either form)."""
     n, f = src.shape
-    _sage_width(f)
+    _gather_width(f, "SAGE aggregation")
     mean = _sage_aggr(aggr)
     if n != prep.n:
         raise ValueError("src must be [n, f] over the prepared graph's nodes")
@@ -2892,7 +2864,7 @@ def sage_aggregate_fwd(src, prep: PreparedGraph, aggr: str = "mean", add=None, b
         out = torch.empty((n, f), dtype=_f32, device=src.device)
     ld_src, ld_add = _sage_rows(src, "src", n, f), _sage_rows(add, "add", n, f, True)
     ld_out, ld_copy = _sage_rows(out, "out", n, f), _sage_rows(copy_out, "copy_out", n, f, True)
-    items, n_items, cap = _sage_items(prep, True, True, long_rows)
+    items, n_items, cap = _long_items(prep, True, True, long_rows)
     ws = _ws(lib().grapes_sage_aggregate_workspace_bytes(0, cap, f), src.device) if cap else None
     _lib.check(lib().grapes_sage_aggregate_fwd(_p(src), ld_src, _p(add), ld_add, _p(bias), _p(loops), _p(prep.rowptr_t),
                                                _p(prep.csr_src), mean, 1 if relu else 0, _p(out), ld_out, _p(copy_out), ld_copy, n,
@@ -2907,7 +2879,7 @@ def sage_aggregate_bwd(dout, prep: PreparedGraph, aggr: str = "mean", relu_out=N
     ReLU was fused); dsrc[j] = sum_{i <- j} s_i g_i + loops[j] s_j g_j (+ add[j]) over the by-source CSR; dadd = g; dbias = the
     column sums of g.  dsrc / dadd: tensors (column blocks allowed) to write; want_*: allocate them.  Fixed order, no atomics."""
     n, f = dout.shape
-    _sage_width(f)
+    _gather_width(f, "SAGE aggregation")
     mean = _sage_aggr(aggr)
     if n != prep.n:
         raise ValueError("dout must be [n, f] over the prepared graph's nodes")
@@ -2921,7 +2893,7 @@ def sage_aggregate_bwd(dout, prep: PreparedGraph, aggr: str = "mean", relu_out=N
     ld_dout, ld_relu = _sage_rows(dout, "dout", n, f), _sage_rows(relu_out, "relu_out", n, f, True)
     ld_add, ld_dsrc = _sage_rows(add, "add", n, f, True), _sage_rows(dsrc, "dsrc", n, f, True)
     ld_dadd = _sage_rows(dadd, "dadd", n, f, True)
-    items, n_items, cap = _sage_items(prep, False, False, long_rows) if dsrc is not None else (None, None, 0)
+    items, n_items, cap = _long_items(prep, False, False, long_rows) if dsrc is not None else (None, None, 0)
     ws = _ws(lib().grapes_sage_aggregate_workspace_bytes(n, cap, f), dev)
     _lib.check(lib().grapes_sage_aggregate_bwd(_p(dout), ld_dout, _p(relu_out), ld_relu, _p(loops), _p(prep.rowptr_t),
                                                _p(prep.rowptr_s), _p(prep.csr_dst), mean, _p(add), ld_add, _p(dsrc), ld_dsrc,

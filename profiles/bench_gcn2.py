@@ -95,7 +95,7 @@ def _short(name):
 def summarize(dirs):
     print("# rocprofv3 --kernel-trace --stats, MI355X; one process per row; us per call = sum over the call's kernels of their mean time")
     print("# spread = max / min over the run's repeats of the GCN aggregation's main kernel (its own run-to-run variation)")
-    print("# prop = gcn2_rows_k + gcn2_chunks_k + gcn2_combine_k once; a bwd run's mean of those kernels is over the bare backward call")
+    print("# prop = row_sum_rows_k + row_sum_chunks_k + row_sum_combine_k once; a bwd run's mean of those kernels is over the bare backward call")
     print("# and the conv's forward and backward calls (the same kernels over the two CSRs)")
     print(f"{'shape':10s} {'width':>5s} {'phase':>5s} {'GCN us':>8s} {'prop us':>8s} {'prop/GCN':>8s} {'bytes':>6s} {'spread':>6s} {'bound':>6s} "
           f"{'met':>4s} {'conv us':>8s}   kernels (us per call x calls per iteration)")
@@ -114,7 +114,7 @@ def summarize(dirs):
                 continue                                          # (set-up kernels: the graph build, the generators)
             mean, per_it = sum(ts) / len(ts), len(ts) // iters
             names.append(f"{k} {mean / 1e3:.1f} x{per_it}")
-            if k.startswith("gcn2_rows") or k.startswith("gcn2_chunks") or k.startswith("gcn2_combine"):
+            if k.startswith("row_sum_"):
                 prop += mean                                     # (one call of the bare propagation; the conv's call is the second)
                 conv += mean * (per_it - 1)
             elif k.startswith("gcn2_"):

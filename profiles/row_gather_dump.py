@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""Bit-level record of the six row-gather aggregation entry points (GAT, GCN2 and PNA, forward and backward), to compare two
-builds of the library: every output array of one fixed-seed run is hashed (SHA-256 of its bytes) into a JSON file.
+"""Bit-level record of the eight row-gather aggregation entry points (GAT, GCN2, PNA and SAGE, forward and backward), to compare
+two builds of the library: every output array of one fixed-seed run is hashed (SHA-256 of its bytes) into a JSON file.
 
     python profiles/row_gather_dump.py --out A.json             (on each build, on the GPU)
     python profiles/row_gather_dump.py --compare A.json B.json  (anywhere)
 
 Graphs: n = 3000 with a hub row as target (in-degree > 2000), and n = 2600 with one hub as target AND source, so the long-row
 chunk and combine kernels run on both CSRs.  Widths: one per instantiated template shape <VEC, LPR, NS> — f = 24, 64, 100, 256,
-512 for GAT and GCN2, f = 32, 100, 256 for PNA — each with 16-byte-aligned operands (the float4 shapes) and, where the scalar
-shape covers the width, with operands one float off alignment (the scalar shapes)."""
+512 for GAT, GCN2 and SAGE, f = 32, 100, 256 for PNA — each with 16-byte-aligned operands (the float4 shapes) and, where the scalar
+shape covers the width, with operands one float off alignment (the scalar shapes).  SAGE: mean and sum, with the long-row work
+items and without them, plain (contiguous operands, nothing fused) and with add, bias and ReLU on column blocks of wider matrices.
+Every input is finite."""
 import argparse
 import hashlib
 import json
@@ -72,6 +74,23 @@ def dump(path):
                 put(key + "/gcn2_fwd", *ops.gcn2_propagate_fwd(x, x0, prep, 0.3, want_p=True))
                 put(key + "/gcn2_bwd", *ops.gcn2_propagate_bwd(ds, prep, 0.3))
                 put(key + "/gcn2_bwd_two", *ops.gcn2_propagate_bwd(ds, prep, 0.3, ds_add=ds2, add_is_p=True, dx0=x0.clone()))
+                if off and f > 256:                                          # SAGE: scalar columns up to 256
+                    continue
+                wide, dwide, bias = rand(gen, n, 3 * f, off=off), rand(gen, n, 3 * f, off=off), rand(gen, f, off=off)
+                for aggr in ("mean", "sum"):
+                    for long_rows in (True, False):
+                        k2 = key + f"/sage_{aggr}/long{int(long_rows)}"
+                        out = ops.sage_aggregate_fwd(x, prep, aggr, long_rows=long_rows)
+                        put(k2 + "/fwd_plain", out)
+                        put(k2 + "/bwd_plain", ops.sage_aggregate_bwd(ds, prep, aggr, long_rows=long_rows)[0])
+                        # column blocks of wider matrices: src and add in, out and the root copy out; add, bias and ReLU fused
+                        o2, d2 = torch.zeros(n, 2 * f, device=dev), torch.zeros(n, 2 * f, device=dev)
+                        ops.sage_aggregate_fwd(wide[:, f:2 * f], prep, aggr, add=wide[:, 2 * f:], bias=bias, relu=True, out=o2[:, f:],
+                                               copy_out=o2[:, :f], long_rows=long_rows)
+                        _, _, dbias = ops.sage_aggregate_bwd(dwide[:, :f], prep, aggr, relu_out=o2[:, f:], add=dwide[:, 2 * f:],
+                                                             dsrc=d2[:, :f], dadd=d2[:, f:], want_bias=True, long_rows=long_rows)
+                        put(k2 + "/fwd_blocks", o2)
+                        put(k2 + "/bwd_blocks", d2, dbias)
         for f in (32, 100, 256):
             for off in (0, 1):
                 key = f"{gname}/f{f}/off{off}"

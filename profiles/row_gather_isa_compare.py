@@ -9,15 +9,19 @@ gcn2_kernels.hip and pna_kernels.hip, as for the row-gather scaffold.
   --files A,B,...  the translation units to compare; then a rise of ANY kernel's count fails, not only a GAT *_chunks_k kernel's
   --no-diffs       list the kernels that differ with their counts, without the instruction diffs
 
-  - every kernel symbol of the parent must exist in the result, and no new one may appear;
+  - every kernel of the parent must exist in the result, and no new one may appear; kernels are named as the demangler prints
+    them, and RENAME maps the parent's names of the kernels that moved into row_sum.h to the result's;
   - a kernel's instruction stream is compared after comments are dropped and basic-block labels renumbered in order of appearance;
   - the three GAT *_chunks_k families took the strict item decode on purpose: for them the register, scratch and LDS counts of
     the code object's metadata must not rise;
   - every other kernel that differs — in its instructions, or in its counts alone — is listed with its counts; the diff itself
     is printed for the first instantiation of each kernel template (the others of a template differ the same way; --all-diffs
-    prints them all).
+    prints them all);
+  - a renamed kernel changed on purpose: its counts in the parent and in the result are listed side by side, with any rise marked,
+    and the opcodes whose number changed stand in for the diff.
 Exit status 1 when a symbol is missing or new, a count of a GAT *_chunks_k kernel rises or, with --files, any kernel's."""
 import argparse
+import collections
 import difflib
 import os
 import re
@@ -26,10 +30,14 @@ import sys
 import tempfile
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+CXXFILT = os.environ.get("CXXFILT", "c++filt")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "--cuda-device-only", "-S"]
 FILES = ["gat_kernels.hip", "gcn2_kernels.hip", "pna_kernels.hip"]
 EXTRA = {"sampler_kernels.hip": ["-ffp-contract=off"]}                      # (the Makefile's EXTRA_<unit>)
 EXPECTED = ("gat_fwd_chunks_k", "gat_bwd_dst_chunks_k", "gat_bwd_src_chunks_k")
+# parent kernel -> (result kernel, trailing template argument): the plain-sum gather GCN2Conv and SAGEConv share (row_sum.h)
+RENAME = {"gcn2_rows_k": ("row_sum_rows_k", "G2Epi"), "gcn2_chunks_k": ("row_sum_chunks_k", None), "gcn2_combine_k": ("row_sum_combine_k", "G2Epi"),
+          "sage_rows_k": ("row_sum_rows_k", "SageEpi"), "sage_chunks_k": ("row_sum_chunks_k", None), "sage_combine_k": ("row_sum_combine_k", "SageEpi")}
 COUNTS = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size")
 
 
@@ -39,8 +47,18 @@ def assembly(csrc, name, tmp):
     return open(out).read()
 
 
+def renamed(key):
+    """The result's name of the parent's kernel `key` ('name' or 'name<args>'), or None where it keeps its name."""
+    name, _, args = key.partition("<")
+    if name not in RENAME:
+        return None
+    new, last = RENAME[name]
+    targs = [t for t in (args[:-1], last) if t]
+    return new + ("<" + ", ".join(targs) + ">" if targs else "")
+
+
 def kernels(text):
-    """{symbol: (normalised instruction lines, {count: value})}"""
+    """{kernel as the demangler prints it, without return type and parameters: (normalised instruction lines, {count: value})}"""
     meta = {}
     for blk in text.split("- .agpr_count:")[1:]:
         nm = re.search(r"\.name:\s+(\S+)", blk).group(1)
@@ -54,7 +72,11 @@ def kernels(text):
             if ln.strip():
                 lines.append(re.sub(r"\.LBB\d+_\d+", lambda t: labels.setdefault(t.group(0), ".L%d" % len(labels)), ln))
         body[nm] = lines
-    return {nm: (body[nm], meta[nm]) for nm in meta}
+    names = list(meta)
+    plain = subprocess.run([CXXFILT], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+    keys = {nm: re.sub(r"^void ", "", d.split("(")[0]) for nm, d in zip(names, plain)}
+    assert len(set(keys.values())) == len(names), "two kernels demangle to one name"
+    return {keys[nm]: (body[nm], meta[nm]) for nm in meta}
 
 
 def main(parent, result, all_diffs=False, files=None, no_diffs=False):
@@ -62,9 +84,17 @@ def main(parent, result, all_diffs=False, files=None, no_diffs=False):
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
         for name in files or FILES:
             a, b = kernels(assembly(parent, name, ta)), kernels(assembly(result, name, tb))
-            missing, new = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+            moved = {k: renamed(k) for k in a if k not in b and renamed(k) in b}
+            missing, new = sorted(set(a) - set(b) - set(moved)), sorted(set(b) - set(a) - set(moved.values()))
             same = [k for k in a if k in b and a[k][0] == b[k][0]]
             print(f"== {name}: {len(a)} kernels in the parent, {len(b)} in the result, {len(same)} with identical instruction streams")
+            for k, to in sorted(moved.items()):
+                rises = [c for c in COUNTS if b[to][1][c] > a[k][1][c]]
+                print(f"  renamed (changed on purpose): {k} -> {to}")
+                print(f"      instructions {len(a[k][0])} -> {len(b[to][0])}; " +
+                      ", ".join(f"{c} {a[k][1][c]} -> {b[to][1][c]}" for c in COUNTS) + ("; RISES: " + ", ".join(rises) if rises else ""))
+                ha, hb = (collections.Counter(ln.split()[0] for ln in side if not ln.endswith(":")) for side in (a[k][0], b[to][0]))
+                print("      opcodes: " + ", ".join(f"{op} {ha[op]} -> {hb[op]}" for op in sorted(set(ha) | set(hb)) if ha[op] != hb[op]))
             for k in missing:
                 print("  MISSING in the result:", k)
             for k in new:
@@ -89,7 +119,7 @@ def main(parent, result, all_diffs=False, files=None, no_diffs=False):
                 if no_diffs:
                     continue
                 diff = list(difflib.unified_diff(a[k][0], b[k][0], "parent", "result", lineterm="", n=1))
-                template = k.split("ILi")[0]
+                template = k.split("<")[0]
                 if all_diffs or template not in shown:
                     print("\n".join("      " + d for d in diff))
                 else:

@@ -247,12 +247,12 @@ def test_two_runs_are_bit_identical():
 
 def test_captured_forward_backward_replays_bit_identically():
     _need_gpu()
-    from grapes_amd.modules.gcn import _pna_graph
+    from grapes_amd.modules.gcn import _layer_graph
     F, C, relu = O.CONV_CASES[4]                                           # 256 wide, ReLU
     ei, x, P, G, _, _ = O.conv_case(F, C, seed=41)
     conv = _conv(F, C, P, O.degree_histogram(ei, N))
     xd, Gd = x.cuda(), G.cuda()
-    prep = _pna_graph(torch.from_numpy(ei).cuda(), N)                      # (the graph build and the loop count are outside the capture)
+    prep = _layer_graph(torch.from_numpy(ei).cuda(), N, "PNA", loops=True)    # (the graph build and the loop count are outside the capture)
     eager = [t.clone() for t in _run(conv, xd, prep, Gd, True)]
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
