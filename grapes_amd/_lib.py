@@ -98,6 +98,11 @@ SIGNATURES = {
     "grapes_sage_aggregate_workspace_bytes": (SZ, [I32, I32, I32]),
     "grapes_sage_aggregate_fwd": (I32, [P, I64, P, I64, P, P, P, P, I32, I32, P, I64, P, I64, I32, P, I32, P, P, I32, P, P, P]),
     "grapes_sage_aggregate_bwd": (I32, [P, I64, P, I64, P, P, P, P, I32, P, I64, P, I64, P, I64, P, I32, P, I32, P, P, I32, P, P, P]),
+    # VR-GCN: the control-variate aggregation over historical activations
+    "grapes_vrgcn_long_row": (I32, []),
+    "grapes_vrgcn_aggregate_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_vrgcn_aggregate_fwd": (I32, [P, I64, P, I32, P, I64, P, P, P, I32, P, P, I32, P, P, P, I64, P, I32, I32, P, P, P]),
+    "grapes_vrgcn_aggregate_bwd": (I32, [P, I64, P, P, P, P, I32, P, P, P, I64, I32, I32, I32, P, P]),
     # GATConv aggregation (modules/gcn.py:45-72)
     "grapes_gat_scores": (I32, [P, P, P, P, P, I32, P, I32, P]),
     "grapes_gat_aggregate_workspace_bytes": (SZ, [I32, I32]),

@@ -2902,6 +2902,91 @@ def sage_aggregate_bwd(dout, prep: PreparedGraph, aggr: str = "mean", relu_out=N
     return dsrc, dadd, dbias
 
 
+# ------------------------------------------------------------------------------- VR-GCN: control variates on historical activations
+# [Chen, Zhu and Song, ICML 2018] (grapes_hip.h, csrc/vrgcn_kernels.hip)
+VRGCN_LONG_ROW = 64          # grapes_vrgcn_long_row(): rows with more entries are cut into chunks of this many (1 GRAPES_LONG_ROW)
+VRGCN_ITEM_CAP_MAX = 1 << 20
+
+
+def _vrgcn_ids(t, name: str, n: Optional[int] = None):
+    _chk(t, _i32, name)
+    if t.dim() != 1 or (n is not None and t.numel() != n):
+        raise ValueError(f"{name} must be a flat int32 tensor" + (f" of {n} values" if n is not None else ""))
+
+
+def vrgcn_item_cap(rowptr, rows_g) -> int:
+    """The chunks of the listed rows with more than VRGCN_LONG_ROW entries (one host read)."""
+    deg = rowptr[rows_g.long() + 1] - rowptr[rows_g.long()]
+    nc = torch.where(deg > VRGCN_LONG_ROW, (deg + (VRGCN_LONG_ROW - 1)) // VRGCN_LONG_ROW, torch.zeros_like(deg))
+    return int(nc.sum().item())
+
+
+def vrgcn_aggregate_fwd(h, node_idx, hbar, dinv, rowptr, col, rows_g, rows_l, prep: PreparedGraph, item_cap: Optional[int] = None,
+                        want_coef: bool = True, out=None, status=None):
+    """(A [m, f], coef [m] or None) of grapes_vrgcn_aggregate_fwd: for the listed rows u = rows_g[r] (local id rows_l[r])
+      A[r] = dinv_u (dinv_u h[loc u] + (d_u / k_u) sum_{kept v} dinv_v (h[loc v] - hbar[v]) + sum_{every entry v of row u} dinv_v hbar[v])
+    over the loop-free global CSR (rowptr int64 [N + 1], col int32; d_u = row u's entries, dinv fp32 [N] = (d + 1)^-1/2), the layer's
+    input h [n_local, f] on the batch's local rows (node_idx int32 [n_local] = their global ids), its history hbar [N, f] on global
+    rows, and the kept entries as prep's by-target CSR over local ids (prep.n = n_local).  coef[r] = (d_u / k_u) dinv_u is what
+    vrgcn_aggregate_bwd takes.  item_cap: the chunks of the listed rows longer than VRGCN_LONG_ROW (None: counted here, one host
+    read; 0: every row by one group of lanes).  status defaults to prep.status."""
+    for t, name in ((h, "h"), (hbar, "hbar"), (dinv, "dinv")):
+        _chk(t, _f32, name)
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(status, _i32, "status", True)
+    _vrgcn_ids(node_idx, "node_idx"); _vrgcn_ids(rows_g, "rows_g"); _vrgcn_ids(rows_l, "rows_l", rows_g.numel())
+    if h.dim() != 2 or hbar.dim() != 2 or h.shape[1] != hbar.shape[1]:
+        raise ValueError("h is [n_local, f] and hbar [N, f]")
+    n_local, f = h.shape
+    N, m = hbar.shape[0], rows_g.numel()
+    _gather_width(f, "VR-GCN aggregation")
+    if node_idx.numel() != n_local or prep.n != n_local or n_local < 1:
+        raise ValueError("node_idx and the prepared kept entries cover h's n_local rows")
+    if rowptr.numel() != N + 1 or dinv.numel() != N or N < 1:
+        raise ValueError("rowptr holds N + 1 values and dinv N, N = hbar's rows")
+    if col.numel() >= 2 ** 31:
+        raise ValueError("VR-GCN aggregation over a graph with 2^31 or more entries is not built")
+    if item_cap is None:
+        item_cap = vrgcn_item_cap(rowptr, rows_g) if m else 0
+    item_cap = int(item_cap)
+    if not 0 <= item_cap <= VRGCN_ITEM_CAP_MAX:
+        raise ValueError(f"item_cap is 0 .. {VRGCN_ITEM_CAP_MAX}")
+    dev = h.device
+    if out is None:
+        out = torch.empty((m, f), dtype=_f32, device=dev)
+    ld_out = _sage_rows(out, "out", m, f)
+    coef = torch.empty(max(m, 1), dtype=_f32, device=dev) if want_coef else None
+    ws = _ws(lib().grapes_vrgcn_aggregate_workspace_bytes(m, item_cap, f), dev) if item_cap else None
+    st = status if status is not None else prep.status
+    _lib.check(lib().grapes_vrgcn_aggregate_fwd(_p(h), f, _p(node_idx), n_local, _p(hbar), f, _p(dinv), _p(rowptr), _p(col), N,
+                                                _p(rows_g), _p(rows_l), m, _p(prep.rowptr_t), _p(prep.csr_src), _p(out), ld_out,
+                                                _p(coef), f, item_cap, _p(ws), _p(st), _stream()), "vrgcn_aggregate_fwd")
+    return out, (coef[:m] if coef is not None else None)
+
+
+def vrgcn_aggregate_bwd(da, coef, pos, node_idx, dinv, prep: PreparedGraph, out=None, status=None):
+    """dh [n_local, f] of grapes_vrgcn_aggregate_bwd from da = d A [m, f]:
+      dh[loc v] = dinv_v sum_{kept (u, v)} coef[pos[loc u]] da[pos[loc u]] + dinv_v^2 da[pos[loc v]]   (the self term for listed v)
+    over prep's by-source CSR; pos int32 [n_local] = a local node's position among the listed rows, or -1.  hbar is a constant and has
+    no gradient.  Fixed order, no atomics."""
+    _chk(da, _f32, "da"); _chk(coef, _f32, "coef"); _chk(dinv, _f32, "dinv"); _chk(status, _i32, "status", True)
+    _vrgcn_ids(node_idx, "node_idx"); _vrgcn_ids(pos, "pos", node_idx.numel())
+    if da.dim() != 2 or da.shape[0] < 1 or coef.numel() != da.shape[0]:
+        raise ValueError("da is [m, f] with m >= 1 and coef holds m values")
+    m, f = da.shape
+    n_local = node_idx.numel()
+    _gather_width(f, "VR-GCN aggregation")
+    if prep.n != n_local or n_local < 1:
+        raise ValueError("the prepared kept entries cover node_idx's n_local rows")
+    if out is None:
+        out = torch.empty((n_local, f), dtype=_f32, device=da.device)
+    ld_out = _sage_rows(out, "dh", n_local, f)
+    st = status if status is not None else prep.status
+    _lib.check(lib().grapes_vrgcn_aggregate_bwd(_p(da), f, _p(coef), _p(pos), _p(node_idx), _p(dinv), dinv.numel(), _p(prep.rowptr_s),
+                                                _p(prep.csr_dst), _p(out), ld_out, n_local, m, f, _p(st), _stream()),
+               "vrgcn_aggregate_bwd")
+    return out
+
+
 def classifier_loss(logits, local_rows, target_ids, labels, out_grad=None):
     """(loss_c [1], d loss_c / d logits [n_rows, C]) — main.py:260,267.  labels: int64 [N] or fp32 [N, C]."""
     _chk(logits, _f32, "logits"); _chk(local_rows, _i32, "local_rows"); _chk(target_ids, _i32, "target_ids")

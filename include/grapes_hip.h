@@ -64,7 +64,8 @@ extern "C" {
  * earlier entry point changed): the LADIES / FastGCN layer-wise samplers — grapes_ladies_importance,
  * grapes_ladies_layer(_workspace_bytes); the AS-GCN adaptive sampler — grapes_asgcn_importance, grapes_asgcn_rows_workspace_bytes,
  * grapes_asgcn_variance, grapes_asgcn_logq_bwd; GraphSAGE — grapes_sage_sample_layer(_workspace_bytes),
- * grapes_sage_aggregate_fwd / _bwd, grapes_sage_aggregate_workspace_bytes. */
+ * grapes_sage_aggregate_fwd / _bwd, grapes_sage_aggregate_workspace_bytes; VR-GCN — grapes_vrgcn_aggregate_fwd / _bwd,
+ * grapes_vrgcn_aggregate_workspace_bytes, grapes_vrgcn_long_row. */
 #define GRAPES_ABI_VERSION 303
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1555,6 +1556,33 @@ int grapes_sage_aggregate_fwd(const float* src, int64_t ld_src, const float* add
  * dadd must not alias dout.  s_i always comes from the by-target row pointers rowptr_t.  workspace: required unless the pass is
  * left out and there are no items. */
 int grapes_sage_aggregate_bwd(const float* dout, int64_t ld_dout, const float* relu_out, int64_t ld_relu, const int32_t* loops, const int32_t* rowptr_t, const int32_t* rowptr_s, const int32_t* csr_dst, int32_t mean, const float* add, int64_t ld_add, float* dsrc, int64_t ld_dsrc, float* dadd, int64_t ld_dadd, float* dbias, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ VR-GCN: the control-variate aggregation over historical
+ * activations (csrc/vrgcn_kernels.hip) [Chen, Zhu and Song, ICML 2018].  The graph is a loop-free CSR (rowptr int64[N + 1], col
+ * int32) with d_u stored entries in row u and dinv[u] = (d_u + 1)^-1/2 (float[N], the caller's table); a batch has n_local nodes,
+ * node_idx[local id] = global id.  h [n_local, f] is the layer's input on local rows, hbar [N, f] its history on GLOBAL rows, read in
+ * place.  For the m listed rows (u = rows_g[r], its local id rows_l[r]) and the layer's kept entries as the by-target CSR
+ * grapes_gcn_prepare builds over the batch's local ids (rowptr_k int32[n_local + 1], csr_k: row loc u holds the local ids of its
+ * k_u kept sources):
+ *   out[r] = dinv_u (dinv_u h[loc u] + (d_u / k_u) sum_{kept v} dinv_v (h[loc v] - hbar[v]) + sum_{every entry v of row u} dinv_v hbar[v])
+ * coef (optional, float[m]) receives (d_u / k_u) dinv_u (0 for k_u = 0), the backward's per-row factor.  A group of lanes owns a row
+ * and keeps one accumulator in registers across both walks; d_u / k_u and dinv_u are applied once per row.  item_cap > 0: rows
+ * with more than grapes_vrgcn_long_row() entries (a multiple of GRAPES_LONG_ROW) are cut into chunks of that many entries, one
+ * group each, whose partial sums are added in chunk order (four launches instead of one); item_cap bounds the chunks of the
+ * listed long rows (at most 2^20; more raise GRAPES_STATUS_EDGE_OVERFLOW and the result is invalid); item_cap = 0: every row by
+ * one group.  No float atomics: two runs give the same bits.  Widths as grapes_sage_aggregate_fwd: any f <= 256, up to 1024 when
+ * f % 4 == 0 and h, hbar, out are 16-byte aligned with ld % 4 == 0, else GRAPES_EALIGN / GRAPES_EINVAL.  An index outside its table
+ * (a listed row, a kept source, its node_idx, a column) raises GRAPES_STATUS_BAD_INDEX and is dropped (a bad listed row gives
+ * zeros).  workspace: grapes_vrgcn_aggregate_workspace_bytes(m, item_cap, f), 16-byte aligned; may be NULL with item_cap = 0. */
+int32_t grapes_vrgcn_long_row(void);
+size_t grapes_vrgcn_aggregate_workspace_bytes(int32_t m, int32_t item_cap, int32_t f);
+int grapes_vrgcn_aggregate_fwd(const float* h, int64_t ld_h, const int32_t* node_idx, int32_t n_local, const float* hbar, int64_t ld_hbar, const float* dinv, const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* rows_g, const int32_t* rows_l, int32_t m, const int32_t* rowptr_k, const int32_t* csr_k, float* out, int64_t ld_out, float* coef, int32_t f, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
+/* Backward of the above with hbar a constant, over the by-source CSR of the same preparation (rowptr_s int32[n_local + 1], csr_dst:
+ * row loc v holds the local ids of the rows that kept v); pos[local id] = the list position r of that node or -1:
+ *   dh[loc v] = dinv_v sum_{kept (u, v)} coef[pos[loc u]] da[pos[loc u]] + dinv_v^2 da[pos[loc v]]   (the self term for listed v only)
+ * for every local row (rows nothing reaches get zeros).  One launch, a group per local row, entries in the CSR's order: no float
+ * atomics, two runs give the same bits.  A target that is none of the listed rows raises GRAPES_STATUS_BAD_INDEX and is dropped. */
+int grapes_vrgcn_aggregate_bwd(const float* da, int64_t ld_da, const float* coef, const int32_t* pos, const int32_t* node_idx, const float* dinv, int32_t num_nodes, const int32_t* rowptr_s, const int32_t* csr_dst, float* dh, int64_t ld_dh, int32_t n_local, int32_t m, int32_t f, int32_t* status, grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:
