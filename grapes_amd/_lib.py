@@ -103,6 +103,11 @@ SIGNATURES = {
     "grapes_vrgcn_aggregate_workspace_bytes": (SZ, [I32, I32, I32]),
     "grapes_vrgcn_aggregate_fwd": (I32, [P, I64, P, I32, P, I64, P, P, P, I32, P, P, I32, P, P, P, I64, P, I32, I32, P, P, P]),
     "grapes_vrgcn_aggregate_bwd": (I32, [P, I64, P, P, P, P, I32, P, P, P, I64, I32, I32, I32, P, P]),
+    # LABOR: the layer-neighbour sampler with shared per-node variates
+    "grapes_labor_sample_layer_workspace_bytes": (SZ, [I32, I32]),
+    "grapes_labor_sample_layer": (I32, [P, P, I32, P, I32, P, I32, P, U64, U64, P, P, I32, I32, P, P, P, P, P, P, P, P]),
+    "grapes_labor_importance_workspace_bytes": (SZ, [I32]),
+    "grapes_labor_importance": (I32, [P, P, I32, P, I32, P, I32, I32, P, P, P, P, P]),
     # GATConv aggregation (modules/gcn.py:45-72)
     "grapes_gat_scores": (I32, [P, P, P, P, P, I32, P, I32, P]),
     "grapes_gat_aggregate_workspace_bytes": (SZ, [I32, I32]),

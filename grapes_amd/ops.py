@@ -2987,6 +2987,105 @@ def vrgcn_aggregate_bwd(da, coef, pos, node_idx, dinv, prep: PreparedGraph, out=
     return out
 
 
+# ------------------------------------------------------------------------------- LABOR: the layer-neighbour sampler
+# [Balin and Catalyurek, NeurIPS 2023; LABOR-recall: DGL's LaborSampler] (grapes_hip.h, csrc/labor_kernels.hip)
+LABOR_CHUNK = 64             # GRAPES_LONG_ROW: the entries of one work item; a longer row is cut over several wavefronts
+LABOR_MAX_ITERS = 8
+LABOR_ITEM_CAP_MAX = 1 << 24
+
+
+def _labor_rows(who, rowptr, col, num_nodes, rows, d_m, status):
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(rows, _i32, "rows"); _chk(d_m, _i32, "d_m", True)
+    _chk(status, _i32, "status", True)
+    N, m = int(num_nodes), rows.numel()
+    if N < 1 or rowptr.numel() != N + 1 or m < 1:
+        raise ValueError(f"{who}: rowptr holds N + 1 values and rows is not empty")
+    return N, m
+
+
+def labor_item_cap(m: int, deg_sum: int) -> int:
+    """An upper bound of the work items of m rows with deg_sum entries in all: sum of ceil(deg / LABOR_CHUNK) <= m + deg_sum // 64,
+    and no item is empty."""
+    return max(1, min(int(m) + int(deg_sum) // LABOR_CHUNK, int(deg_sum)))
+
+
+def labor_sample_layer(rowptr, col, num_nodes: int, rows, fanout: int, e_cap: Optional[int] = None, keys=None, philox_seed: int = 0,
+                       philox_base: int = 0, c=None, pi=None, d_m=None, deg_sum: Optional[int] = None, item_cap: Optional[int] = None,
+                       want_pos: bool = True, want_weight: bool = True, status=None, out=None):
+    """(edge_src, edge_dst int32 [e_cap], edge_pos int64 [e_cap] or None, edge_weight fp32 [e_cap] or None, e_count int32 [1]) of
+    grapes_labor_sample_layer [LABOR-recall]: for the rows s = rows[r] in order, d_s = deg(s), every stored entry t (a global id) of
+    row s is kept with the variate r_t of NODE t — keys[t], or word t & 3 of philox4x32_10(philox_base + (t >> 2), philox_seed) —
+    shared by every row that sees t:  d_s <= fanout keeps everything;  c, pi None (LABOR-0): kept iff r_t d_s < fanout << 32 in 64-bit
+    integers;  c fp32 [m], pi fp32 [N] (ops.labor_importance): kept iff (r_t >> 8) 2^-24 < fminf(1, c[r] pi[t]).  edge_weight: the
+    Hajek weights (1 / p) / (the row's sum of 1 / p over its kept entries).  Entries come for r ascending and within a row in CSR
+    order: source = the neighbour, target = the row.  fanout >= 1 (no upper limit: a fanout past every degree is the expansion with
+    weights 1 / d_s).  keys: int32 (or uint32) bit patterns, one per NODE.  deg_sum: the rows' entry count when the caller knows it
+    (2^31 or more is refused); it sets the defaults e_cap = deg_sum — which cannot overflow — and item_cap
+    (ops.labor_item_cap); without it both e_cap and item_cap are required.  More kept entries than e_cap, or more work items than
+    item_cap, set the overflow status bit.  out: the five tensors to write (edge_pos and edge_weight may be None)."""
+    N, m = _labor_rows("labor_sample_layer", rowptr, col, num_nodes, rows, d_m, status)
+    _chk(c, _f32, "c", True); _chk(pi, _f32, "pi", True)
+    k, dev = int(fanout), rows.device
+    if not 1 <= k < 2 ** 31:
+        raise ValueError(f"labor_sample_layer: fanout = {fanout} is not built (1 <= fanout < 2^31)")
+    if (c is None) != (pi is None) or (c is not None and (c.numel() != m or pi.numel() != N)):
+        raise ValueError("labor_sample_layer: c holds one value per listed row and pi one per node; both or neither")
+    if deg_sum is None and (e_cap is None or item_cap is None):
+        raise ValueError("labor_sample_layer: give deg_sum, the rows' entry count, or both e_cap and item_cap")
+    if deg_sum is not None and int(deg_sum) >= 2 ** 31:
+        raise ValueError("labor_sample_layer: rows with 2^31 or more entries in all are not built")
+    ec = max(int(deg_sum), 1) if e_cap is None else int(e_cap)
+    ic = labor_item_cap(m, deg_sum) if item_cap is None else int(item_cap)
+    if ec < 1 or not 1 <= ic <= LABOR_ITEM_CAP_MAX:
+        raise ValueError(f"labor_sample_layer: e_cap is at least 1 and item_cap is 1 .. {LABOR_ITEM_CAP_MAX}")
+    if keys is not None:
+        if not keys.is_cuda or keys.dtype not in (_i32, getattr(torch, "uint32", _i32)) or not keys.is_contiguous():
+            raise TypeError("labor_sample_layer: keys must be a contiguous cuda tensor of 32-bit words (int32 bit patterns or uint32)")
+        if keys.numel() != N:
+            raise ValueError("labor_sample_layer: keys holds one word per node")
+    if out is None:
+        out = (torch.empty(ec, dtype=_i32, device=dev), torch.empty(ec, dtype=_i32, device=dev),
+               torch.empty(ec, dtype=_i64, device=dev) if want_pos else None,
+               torch.empty(ec, dtype=_f32, device=dev) if want_weight else None, torch.empty(1, dtype=_i32, device=dev))
+    src, dst, pos, w, d_e = out
+    _chk(src, _i32, "edge_src"); _chk(dst, _i32, "edge_dst"); _chk(pos, _i64, "edge_pos", True); _chk(w, _f32, "edge_weight", True)
+    _chk(d_e, _i32, "e_count")
+    if min(src.numel(), dst.numel()) < ec or (pos is not None and pos.numel() < ec) or (w is not None and w.numel() < ec):
+        raise ValueError("labor_sample_layer: the edge buffers hold e_cap values each")
+    ws = _ws(lib().grapes_labor_sample_layer_workspace_bytes(m, ic), dev)
+    _lib.check(lib().grapes_labor_sample_layer(_p(rowptr), _p(col), N, _p(rows), m, _p(d_m), k, _p(keys),
+                                               int(philox_seed) & (2 ** 64 - 1), int(philox_base) & (2 ** 64 - 1), _p(c), _p(pi), ic, ec,
+                                               _p(src), _p(dst), _p(pos), _p(w), _p(d_e), _p(ws), _p(status), _stream()),
+               "labor_sample_layer")
+    return src, dst, pos, w, d_e
+
+
+def labor_scratch(num_nodes: int, device) -> torch.Tensor:
+    """The N-sized table of grapes_labor_importance: zero at rest, left zero by every call."""
+    return torch.zeros(lib().grapes_labor_importance_workspace_bytes(int(num_nodes)) // 4, dtype=_i32, device=device)
+
+
+def labor_importance(rowptr, col, num_nodes: int, rows, fanout: int, iters: int, scratch, pi=None, d_m=None, status=None):
+    """(c fp32 [m], pi fp32 [N]) of grapes_labor_importance [LABOR-recall]: `iters` (0 .. 8) iterations pi_t <- pi_t max_s c_s(pi) from
+    pi = 1, over the listed rows with more than `fanout` entries, then c_s(pi) once more; c_s solves sum_t 1 / min(1, c pi_t) =
+    d_s^2 / fanout (0 is written for a row with d_s <= fanout, whose p is 1).  pi: the table to write (only the columns the rows touch
+    are written, and only they mean anything).  scratch: ops.labor_scratch(N, device) — zero on entry, zero again on return."""
+    N, m = _labor_rows("labor_importance", rowptr, col, num_nodes, rows, d_m, status)
+    _chk(scratch, _i32, "scratch"); _chk(pi, _f32, "pi", True)
+    k, it = int(fanout), int(iters)
+    if not 1 <= k < 2 ** 31 or not 0 <= it <= LABOR_MAX_ITERS:
+        raise ValueError(f"labor_importance: fanout >= 1 and 0 <= iters <= {LABOR_MAX_ITERS}, not {fanout} and {iters}")
+    if scratch.numel() * 4 < lib().grapes_labor_importance_workspace_bytes(N) or (pi is not None and pi.numel() != N):
+        raise ValueError("labor_importance: scratch is ops.labor_scratch(num_nodes, device) and pi holds one value per node")
+    dev = rows.device
+    if pi is None:
+        pi = torch.empty(N, dtype=_f32, device=dev)
+    c = torch.empty(m, dtype=_f32, device=dev)
+    _lib.check(lib().grapes_labor_importance(_p(rowptr), _p(col), N, _p(rows), m, _p(d_m), k, it, _p(c), _p(pi), _p(scratch),
+                                             _p(status), _stream()), "labor_importance")
+    return c, pi
+
+
 def classifier_loss(logits, local_rows, target_ids, labels, out_grad=None):
     """(loss_c [1], d loss_c / d logits [n_rows, C]) — main.py:260,267.  labels: int64 [N] or fp32 [N, C]."""
     _chk(logits, _f32, "logits"); _chk(local_rows, _i32, "local_rows"); _chk(target_ids, _i32, "target_ids")

@@ -65,7 +65,8 @@ extern "C" {
  * grapes_ladies_layer(_workspace_bytes); the AS-GCN adaptive sampler — grapes_asgcn_importance, grapes_asgcn_rows_workspace_bytes,
  * grapes_asgcn_variance, grapes_asgcn_logq_bwd; GraphSAGE — grapes_sage_sample_layer(_workspace_bytes),
  * grapes_sage_aggregate_fwd / _bwd, grapes_sage_aggregate_workspace_bytes; VR-GCN — grapes_vrgcn_aggregate_fwd / _bwd,
- * grapes_vrgcn_aggregate_workspace_bytes, grapes_vrgcn_long_row. */
+ * grapes_vrgcn_aggregate_workspace_bytes, grapes_vrgcn_long_row; LABOR — grapes_labor_sample_layer(_workspace_bytes),
+ * grapes_labor_importance(_workspace_bytes). */
 #define GRAPES_ABI_VERSION 303
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1583,6 +1584,46 @@ int grapes_vrgcn_aggregate_fwd(const float* h, int64_t ld_h, const int32_t* node
  * for every local row (rows nothing reaches get zeros).  One launch, a group per local row, entries in the CSR's order: no float
  * atomics, two runs give the same bits.  A target that is none of the listed rows raises GRAPES_STATUS_BAD_INDEX and is dropped. */
 int grapes_vrgcn_aggregate_bwd(const float* da, int64_t ld_da, const float* coef, const int32_t* pos, const int32_t* node_idx, const float* dinv, int32_t num_nodes, const int32_t* rowptr_s, const int32_t* csr_dst, float* dh, int64_t ld_dh, int32_t n_local, int32_t m, int32_t f, int32_t* status, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ LABOR: the layer-neighbour sampler (csrc/labor_kernels.hip)
+ * [Balin and Catalyurek, NeurIPS 2023; LABOR-recall: DGL's LaborSampler].  Neighbour sampling's per-row estimator with ONE variate
+ * per candidate vertex, shared by every row that sees it.  For the rows s = rows[r], r < m (*d_m), of the CSR (rowptr int64[N + 1],
+ * col int32), d_s = deg(s), fanout k >= 1, and every stored entry t of row s (duplicates are separate entries, a stored loop is an
+ * ordinary entry; t is a GLOBAL node id):
+ *   r_t = keys[t] when keys (uint32[N], one word per NODE) is given, else 32-bit word t & 3 of philox4x32_10(philox_base + (t >> 2),
+ *   philox_seed): every row sees the same r_t for the same t;
+ *   d_s <= k: every entry is kept, p_st = 1;
+ *   c == pi == NULL (LABOR-0): entry t is kept iff (uint64) r_t * d_s < (uint64) k << 32 — probability k / d_s, integers only;
+ *   c (float[m], per list row) and pi (float[N], per node) given: kept iff u_t < p_st with u_t = (r_t >> 8) * 2^-24 and
+ *   p_st = fminf(1, c[r] * pi[t]), ONE fp32 multiply contracted with nothing: a CPU given the same c and pi keeps the same entries;
+ *   edge_weight (optional): the Hajek weights w_st = (1 / p_st) / sum_{t' kept in row s} (1 / p_st') — LABOR-0: 1 / kept_s; a row's sum
+ *   is formed per 64-entry chunk (a butterfly over the lanes) and over its chunks in chunk order, in fp32: two runs give the same bits;
+ *   kept entries are written for r ascending and within a row in CSR order: edge_src[e] = t, edge_dst[e] = s, edge_pos[e] = the
+ *   entry's position in col (int64; may be NULL); *d_e = their number.  A row that keeps nothing has no entry.
+ * A work item is GRAPES_LONG_ROW = 64 consecutive entries of one list row, one per lane: a longer row is cut over several wavefronts
+ * and its chunks' counts feed the same prefix as every other row's.  item_cap bounds the items, sum over the rows of ceil(d_s / 64)
+ * (at most m + (sum d_s) / 64; up to 2^24): more raise GRAPES_STATUS_EDGE_OVERFLOW and the list is incomplete.  More than e_cap kept
+ * entries raise it too, *d_e = e_cap and nothing is written past e_cap.  A row id outside [0, N) raises GRAPES_STATUS_BAD_INDEX and
+ * counts as an empty row; a column outside [0, N) raises it and is never kept.  Rows at or past *d_m write nothing.
+ * Four launches: one workgroup (the rows' chunk counts and their prefix), a wavefront per item (its kept lanes as a 64-bit mask — a
+ * lane computes a Philox call only for the entry it tests), one workgroup (the prefix of the masks' popcounts, the count, the
+ * overflow bit), a wavefront per item (the write).  workspace: grapes_labor_sample_layer_workspace_bytes(m, item_cap), 8-byte
+ * aligned. */
+size_t grapes_labor_sample_layer_workspace_bytes(int32_t m, int32_t item_cap);
+int grapes_labor_sample_layer(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* rows, int32_t m, const int32_t* d_m, int32_t fanout, const uint32_t* keys, uint64_t philox_seed, uint64_t philox_base, const float* c, const float* pi, int32_t item_cap, int32_t e_cap, int32_t* edge_src, int32_t* edge_dst, int64_t* edge_pos, float* edge_weight, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream);
+/* LABOR's importance iterations for one layer (0 <= iters <= 8), from pi = 1 on every column the rows touch:
+ *   c_s(pi), for a row with d_s > k, solves sum_{t in N(s)} 1 / min(1, c pi_t) = d_s^2 / k (pi = 1: c_s = k / d_s);
+ *   one iteration: pi_t <- pi_t * max_{s listed, d_s > k, t in N(s)} c_s(pi); rows with d_s <= k take no part, and a column that only
+ *   they see keeps its pi;  after `iters` iterations c_s is solved once more for the final pi.
+ * Writes c[r] (float[m]; 0 for a row with d_s <= k, whose p is 1) and pi[t] (float[N]) for every column t the rows touch; other
+ * entries of pi are left alone.  c_s is solved without a sort by the monotone fixed point J = {}, c = (sum_{t not in J} 1 / pi_t) /
+ * (d_s^2 / k - |J|), J <- {t : c pi_t >= 1}, until J stops growing (c never decreases; at most d_s rounds).  fp32; one wavefront per
+ * row, every row sum in a fixed order; the maximum is an integer atomic max on the bit patterns of the positive floats: no float
+ * atomics, two runs give the same bits.  workspace: grapes_labor_importance_workspace_bytes(N) bytes, a table of one word per node
+ * that must be ZERO on entry and is zero again on return (as the DeviceGraph's bitmaps are).  1 + 2 iters + 1 launches.  Bad ids as
+ * above (dropped, GRAPES_STATUS_BAD_INDEX). */
+size_t grapes_labor_importance_workspace_bytes(int32_t num_nodes);
+int grapes_labor_importance(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* rows, int32_t m, const int32_t* d_m, int32_t fanout, int32_t iters, float* c, float* pi, void* workspace, int32_t* status, grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:
