@@ -12,8 +12,7 @@
 //   Hajek weights w_st = (1 / p_st) / sum over the kept entries of the row of 1 / p_st (LABOR-0: 1 / kept_s).
 // The test on an entry depends on that entry alone: there is no selection pass, and a long row is simply cut.  A work item is
 // LABOR_CHUNK = GRAPES_LONG_ROW = 64 consecutive entries of one list row, one per lane:
-//   labor_items_k  ONE workgroup: every row's chunk count and its exclusive prefix -> item_off (labor_scan_tiles: block_excl_scan_u64
-//                  over tiles of 4096 rows, a thread's four rows requested together)
+//   labor_items_k  ONE workgroup: every row's chunk count and its exclusive prefix -> item_off (list_scan_tiles of row_list.h)
 //   labor_count_k  a wavefront per item: finds its row (lower_bound over item_off), tests its 64 entries — a lane computes a Philox
 //                  call only for the entry it tests — and stores the kept lanes as one 64-bit mask (+ the chunk's sum of 1 / p)
 //   labor_scan_k   ONE workgroup: the exclusive prefix of the masks' popcounts over ALL items — the chunks of a long row feed the same
@@ -31,111 +30,52 @@
 //   labor_c_k        the final c
 // No kernel waits on another workgroup.
 #include "philox.h"
+#include "row_list.h"
 
-#define LABOR_SCAN_THREADS 1024
 #define LABOR_CHUNK GRAPES_LONG_ROW
 #define LABOR_MAX_ITERS 8
-#define LABOR_PER 4                   // consecutive values a thread takes from one tile of a single-workgroup scan
 static_assert(LABOR_CHUNK == 64, "a work item is one entry per lane and its kept set one 64-bit mask");
-
-// The row of list position r: its id, the start of its entries and their number (0 for a row at or past the live count or outside [0, N)).
-struct LaborRow { int i; int64_t a; long long deg; };
-__device__ __forceinline__ LaborRow labor_row(const int64_t* __restrict__ rowptr, int N, const int32_t* __restrict__ rows, int r,
-                                              int live, bool* bad) {
-    LaborRow R; R.i = -1; R.a = 0; R.deg = 0;
-    if (r >= live) return R;
-    const int i = rows[r];
-    if ((unsigned)i >= (unsigned)N) { if (bad) *bad = true; return R; }
-    R.i = i; R.a = rowptr[i];
-    const long long deg = (long long)(rowptr[i + 1] - R.a);
-    R.deg = deg > 0 ? deg : 0;
-    return R;
-}
 
 // r_t: the word of node t (t inside [0, N))
 __device__ __forceinline__ uint32_t labor_word(const uint32_t* __restrict__ keys, uint64_t seed, uint64_t base, int t) {
-    if (keys) return keys[t];
-    const Philox4 w = philox4x32_10(base + (uint64_t)((uint32_t)t >> 2), seed);
-    const int q = t & 3;
-    return q == 0 ? w.v[0] : (q == 1 ? w.v[1] : (q == 2 ? w.v[2] : w.v[3]));
+    return keys ? keys[t] : philox_word_at(seed, base, (long long)t);
 }
 
 // p_st of an entry of a row with d_s > k under the importance rule: ONE multiply, then the clamp
 __device__ __forceinline__ float labor_p(float c_s, float pi_t) { return fminf(1.f, c_s * pi_t); }
 
-// The exclusive prefix of n values by ONE workgroup, in tiles of LABOR_SCAN_THREADS * LABOR_PER values: a thread takes LABOR_PER
-// consecutive values per tile — value(i0, v) fills v[q] with the value of index i0 + q (0 at or past n) and requests its loads together,
-// so a tile costs one memory round trip per level of indirection instead of one per value, and a wavefront's loads cover whole cache
-// lines — then one block_excl_scan_u64 per tile with the carry of the tiles before.  out[i] = min(prefix, cap) for i < n; returns the
-// total.  n is workgroup-uniform; every thread must call it.
-template <class F>
-__device__ __forceinline__ unsigned long long labor_scan_tiles(F value, int n, int cap, int32_t* __restrict__ out,
-                                                               unsigned long long* lds) {
-    unsigned long long carry = 0ull;
-    for (int tile = 0; tile < n; tile += LABOR_SCAN_THREADS * LABOR_PER) {
-        const int i0 = tile + (int)threadIdx.x * LABOR_PER;
-        int v[LABOR_PER];
-        value(i0, v);
-        unsigned long long s = 0ull;
-#pragma unroll
-        for (int q = 0; q < LABOR_PER; ++q) s += (unsigned long long)v[q];
-        unsigned long long tot;
-        unsigned long long run = carry + block_excl_scan_u64(s, lds, &tot);
-#pragma unroll
-        for (int q = 0; q < LABOR_PER; ++q) {
-            if (i0 + q < n) out[i0 + q] = run < (unsigned long long)cap ? (int)run : cap;
-            run += (unsigned long long)v[q];
-        }
-        carry += tot;
-    }
-    return carry;
-}
-
 // ONE workgroup.  item_off[r] = the chunks of the list rows before r, item_off[m] = their total, both clamped to item_cap (more raise
 // GRAPES_STATUS_EDGE_OVERFLOW).  A row id outside [0, N) counts as an empty row and raises GRAPES_STATUS_BAD_INDEX.
-__global__ __launch_bounds__(LABOR_SCAN_THREADS) void labor_items_k(const int64_t* __restrict__ rowptr, int N,
-                                                                    const int32_t* __restrict__ rows, int m_host,
-                                                                    const int32_t* __restrict__ d_m, int item_cap,
-                                                                    int32_t* __restrict__ item_off, int32_t* status) {
+__global__ __launch_bounds__(LIST_SCAN_THREADS) void labor_items_k(const int64_t* __restrict__ rowptr, int N,
+                                                                   const int32_t* __restrict__ rows, int m_host,
+                                                                   const int32_t* __restrict__ d_m, int item_cap,
+                                                                   int32_t* __restrict__ item_off, int32_t* status) {
     __shared__ unsigned long long lds[17];
     const int live = eff_count(d_m, m_host);
     bool bad = false;
-    auto chunks = [&](int i0, int (&v)[LABOR_PER]) {
-        int id[LABOR_PER];
-        int64_t a[LABOR_PER], b[LABOR_PER];
+    auto chunks = [&](int i0, int (&v)[LIST_SCAN_PER]) {
+        long long deg[LIST_SCAN_PER];
+        list_row_degrees(rowptr, N, rows, i0, live, deg, bad);                // (live <= m_host)
 #pragma unroll
-        for (int q = 0; q < LABOR_PER; ++q) id[q] = i0 + q < live ? rows[i0 + q] : 0;               // (live <= m_host)
-#pragma unroll
-        for (int q = 0; q < LABOR_PER; ++q) {
-            const bool ok = i0 + q < live && (unsigned)id[q] < (unsigned)N;
-            bad = bad || (i0 + q < live && !ok);
-            a[q] = ok ? rowptr[id[q]] : 0;
-            b[q] = ok ? rowptr[id[q] + 1] : 0;
-        }
-#pragma unroll
-        for (int q = 0; q < LABOR_PER; ++q) {
-            const long long deg = b[q] > a[q] ? (long long)(b[q] - a[q]) : 0ll;
-            const long long nch = (deg + LABOR_CHUNK - 1) / LABOR_CHUNK;
+        for (int q = 0; q < LIST_SCAN_PER; ++q) {
+            const long long nch = (deg[q] + LABOR_CHUNK - 1) / LABOR_CHUNK;
             v[q] = (int)(nch < 0x7fffffffll ? nch : 0x7fffffffll);
         }
     };
-    const unsigned long long total = labor_scan_tiles(chunks, m_host, item_cap, item_off, lds);
+    const unsigned long long total = list_scan_tiles<int>(chunks, m_host, (unsigned long long)item_cap, item_off, lds);
     if (bad && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
-    if (threadIdx.x == 0) {
-        item_off[m_host] = total < (unsigned long long)item_cap ? (int)total : item_cap;
-        if (total > (unsigned long long)item_cap && status) atomicOr(status, GRAPES_STATUS_EDGE_OVERFLOW);
-    }
+    list_scan_finish(total, item_cap, item_off + m_host, nullptr, status);
 }
 
 // The item of this wavefront: its list row and the entry of this lane.  false: no such item (whole wavefronts leave).
-struct LaborItem { int r; LaborRow R; long long t; };
+struct LaborItem { int r; ListRow R; long long t; };
 __device__ __forceinline__ bool labor_item(LaborItem& I, int it, const int64_t* __restrict__ rowptr, int N,
                                            const int32_t* __restrict__ rows, int m_host, const int32_t* __restrict__ d_m,
                                            const int32_t* __restrict__ item_off, int lane) {
     if (it >= item_off[m_host]) return false;
     // the last row with item_off[r] <= it: rows without an entry own no item and are stepped over
     I.r = lower_bound<int32_t, int, int>(item_off, m_host, it + 1) - 1;
-    I.R = labor_row(rowptr, N, rows, I.r, eff_count(d_m, m_host), nullptr);
+    I.R = list_row(rowptr, N, rows, I.r, eff_count(d_m, m_host), nullptr);
     I.t = (long long)(it - item_off[I.r]) * LABOR_CHUNK + lane;
     return true;
 }
@@ -178,24 +118,20 @@ __global__ __launch_bounds__(256) void labor_count_k(const int64_t* __restrict__
 }
 
 // ONE workgroup.  off[it] = min(the kept entries of the items before it, e_cap), off[n_items] = *d_e = min(their total, e_cap).
-__global__ __launch_bounds__(LABOR_SCAN_THREADS) void labor_scan_k(const unsigned long long* __restrict__ mask,
-                                                                   const int32_t* __restrict__ item_off, int m_host, int e_cap,
-                                                                   int32_t* __restrict__ off, int32_t* __restrict__ d_e, int32_t* status) {
+__global__ __launch_bounds__(LIST_SCAN_THREADS) void labor_scan_k(const unsigned long long* __restrict__ mask,
+                                                                  const int32_t* __restrict__ item_off, int m_host, int e_cap,
+                                                                  int32_t* __restrict__ off, int32_t* __restrict__ d_e, int32_t* status) {
     __shared__ unsigned long long lds[17];
     const int n_items = item_off[m_host];
-    auto kept = [&](int i0, int (&v)[LABOR_PER]) {
-        unsigned long long w[LABOR_PER];
+    auto kept = [&](int i0, int (&v)[LIST_SCAN_PER]) {
+        unsigned long long w[LIST_SCAN_PER];
 #pragma unroll
-        for (int q = 0; q < LABOR_PER; ++q) w[q] = i0 + q < n_items ? mask[i0 + q] : 0ull;
+        for (int q = 0; q < LIST_SCAN_PER; ++q) w[q] = i0 + q < n_items ? mask[i0 + q] : 0ull;
 #pragma unroll
-        for (int q = 0; q < LABOR_PER; ++q) v[q] = __popcll(w[q]);
+        for (int q = 0; q < LIST_SCAN_PER; ++q) v[q] = __popcll(w[q]);
     };
-    const unsigned long long total = labor_scan_tiles(kept, n_items, e_cap, off, lds);
-    if (threadIdx.x == 0) {
-        off[n_items] = total < (unsigned long long)e_cap ? (int)total : e_cap;
-        *d_e = total < (unsigned long long)e_cap ? (int)total : e_cap;
-        if (total > (unsigned long long)e_cap && status) atomicOr(status, GRAPES_STATUS_EDGE_OVERFLOW);
-    }
+    const unsigned long long total = list_scan_tiles<int>(kept, n_items, (unsigned long long)e_cap, off, lds);
+    list_scan_finish(total, e_cap, off + n_items, d_e, status);
 }
 
 // A wavefront per item: its kept lanes behind off[it], in lane order; nothing is written at or past e_cap.
@@ -212,10 +148,10 @@ __global__ __launch_bounds__(256) void labor_write_k(const int64_t* __restrict__
     LaborItem I;
     if (!labor_item(I, it, rowptr, N, rows, m_host, d_m, item_off, lane)) return;
     const unsigned long long bal = mask[it];
-    const int base = off[it];
+    int base = off[it];
     if (bal == 0ull || base >= e_cap) return;
     const bool keep = (bal >> lane) & 1ull;
-    const int p = base + __popcll(bal & ((1ull << lane) - 1ull));
+    const int p = wave_compact_slot(keep, lane, base);
     const int i0 = item_off[I.r], i1 = item_off[I.r + 1];
     float w = 0.f;
     if (edge_weight) {
@@ -260,13 +196,13 @@ extern "C" int grapes_labor_sample_layer(const int64_t* rowptr, const int32_t* c
     int32_t* off = item_off + (m + 1);
     float* rsum = (float*)(off + (item_cap + 1));
     const dim3 grid(grapes_div_up((int64_t)item_cap * 64, 256));
-    hipLaunchKernelGGL(labor_items_k, dim3(1), dim3(LABOR_SCAN_THREADS), 0, s, rowptr, num_nodes, rows, m, d_m, item_cap, item_off,
+    hipLaunchKernelGGL(labor_items_k, dim3(1), dim3(LIST_SCAN_THREADS), 0, s, rowptr, num_nodes, rows, m, d_m, item_cap, item_off,
                        status);
     GRAPES_LAUNCH_CHECK();
     hipLaunchKernelGGL(labor_count_k, grid, dim3(256), 0, s, rowptr, col, num_nodes, rows, m, d_m, fanout, keys, philox_seed,
                        philox_base, c, pi, (const int32_t*)item_off, item_cap, mask, rsum, status);
     GRAPES_LAUNCH_CHECK();
-    hipLaunchKernelGGL(labor_scan_k, dim3(1), dim3(LABOR_SCAN_THREADS), 0, s, (const unsigned long long*)mask,
+    hipLaunchKernelGGL(labor_scan_k, dim3(1), dim3(LIST_SCAN_THREADS), 0, s, (const unsigned long long*)mask,
                        (const int32_t*)item_off, m, e_cap, off, d_e, status);
     GRAPES_LAUNCH_CHECK();
     hipLaunchKernelGGL(labor_write_k, grid, dim3(256), 0, s, rowptr, col, num_nodes, rows, m, d_m, fanout, c, pi,
@@ -323,7 +259,7 @@ __device__ __forceinline__ float labor_solve_c(const int32_t* __restrict__ col, 
     const int r = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;                    \
     if (r >= m_host) return;                                                                                               \
     bool bad = false;                                                                                                      \
-    const LaborRow R = labor_row(rowptr, N, rows, r, eff_count(d_m, m_host), &bad)
+    const ListRow R = list_row(rowptr, N, rows, r, eff_count(d_m, m_host), &bad)
 
 __global__ __launch_bounds__(256) void labor_pi_init_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N,
                                                        const int32_t* __restrict__ rows, int m_host, const int32_t* __restrict__ d_m,

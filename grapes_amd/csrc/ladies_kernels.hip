@@ -14,7 +14,7 @@
 // lane busy; there is no item list, since a layer has a few thousand rows at the most and a walk reads 4 bytes per entry.
 //
 // No kernel waits on another workgroup of its own launch.
-#include "common.h"
+#include "row_list.h"
 
 #define LADIES_SCAN_THREADS 1024
 
@@ -75,15 +75,16 @@ __device__ __forceinline__ int ladies_entry(const int32_t* __restrict__ crow, in
     return j;
 }
 
+// list_row plus the diagonal's place; false: no row (bad = an id outside [0, N))
 struct LadiesRow { int i; int deg; int pos; int ins; const int32_t* crow; };
 
 __device__ __forceinline__ bool ladies_row(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N,
-                                           const int32_t* __restrict__ rows, int r, LadiesRow& R) {
-    R.i = rows[r];
-    if ((unsigned)R.i >= (unsigned)N) return false;
-    const int64_t a = rowptr[R.i];
-    R.deg = (int)(rowptr[R.i + 1] - a);
-    R.crow = col + a;
+                                           const int32_t* __restrict__ rows, int r, int live, LadiesRow& R, bool* bad) {
+    const ListRow L = list_row(rowptr, N, rows, r, live, bad);
+    if (L.i < 0) return false;
+    R.i = L.i;
+    R.deg = (int)L.deg;
+    R.crow = col + L.a;
     R.pos = lower_bound(R.crow, R.deg, R.i);
     R.ins = (R.pos < R.deg && R.crow[R.pos] == R.i) ? 0 : 1;
     return true;
@@ -96,10 +97,11 @@ __global__ __launch_bounds__(256) void ladies_count_k(const int64_t* __restrict_
     const int r = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
     if (r >= m_host) return;
     LadiesRow R;
-    if (r >= eff_count(d_m, m_host) || !ladies_row(rowptr, col, N, rows, r, R)) {
+    bool bad = false;
+    if (!ladies_row(rowptr, col, N, rows, r, eff_count(d_m, m_host), R, &bad)) {
         if (lane == 0) {
             cnt[r] = 0; rsum[r] = 0.f;
-            if (r < eff_count(d_m, m_host) && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+            if (bad && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
         }
         return;
     }
@@ -119,6 +121,8 @@ __global__ __launch_bounds__(256) void ladies_count_k(const int64_t* __restrict_
 }
 
 // ONE workgroup: off[r] = min(sum of cnt[0 .. r), e_cap) for r < m_host; *d_e = min(total, e_cap); the overflow bit
+// (Its own prefix, a thread walking its span, not row_list.h's tiled one: on that the layer call measured 0.6 - 2 % slower at 512 and
+// 574 rows, above the spread between runs of the parent — profiles/row_list_ab.json.)
 __global__ __launch_bounds__(LADIES_SCAN_THREADS) void ladies_scan_k(const int32_t* __restrict__ cnt, int m_host, int e_cap,
                                                                      int32_t* __restrict__ off, int32_t* __restrict__ d_e,
                                                                      int32_t* status) {
@@ -133,10 +137,7 @@ __global__ __launch_bounds__(LADIES_SCAN_THREADS) void ladies_scan_k(const int32
         off[r] = run < (unsigned long long)e_cap ? (int)run : e_cap;
         run += (unsigned long long)cnt[r];
     }
-    if (threadIdx.x == 0) {
-        *d_e = total < (unsigned long long)e_cap ? (int)total : e_cap;
-        if (total > (unsigned long long)e_cap && status) atomicOr(status, GRAPES_STATUS_EDGE_OVERFLOW);
-    }
+    list_scan_finish(total, e_cap, nullptr, d_e, status);
 }
 
 __global__ __launch_bounds__(256) void ladies_write_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N,
@@ -147,9 +148,9 @@ __global__ __launch_bounds__(256) void ladies_write_k(const int64_t* __restrict_
                                                       int32_t* __restrict__ edge_dst, float* __restrict__ weight) {
     const int r = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
     if (r >= m_host) return;
-    if (r >= eff_count(d_m, m_host) || cnt[r] == 0) return;               // (a bad row id counted 0)
+    if (cnt[r] == 0) return;                                              // (a row past the live count or with a bad id counted 0)
     LadiesRow R;
-    if (!ladies_row(rowptr, col, N, rows, r, R)) return;
+    if (!ladies_row(rowptr, col, N, rows, r, eff_count(d_m, m_host), R, nullptr)) return;
     const float s = rsum[r];
     int base = off[r];
     for (int q0 = 0; q0 < R.deg + R.ins; q0 += 64) {
@@ -157,13 +158,11 @@ __global__ __launch_bounds__(256) void ladies_write_k(const int64_t* __restrict_
         float v;
         const int j = ladies_entry(R.crow, R.deg, R.i, R.pos, R.ins, q0 + lane, v);
         const bool kept = (unsigned)j < (unsigned)N && ladies_bit(keep, j);
-        const unsigned long long bal = __ballot(kept);
-        const int p = base + __popcll(bal & ((1ull << lane) - 1ull));
+        const int p = wave_compact_slot(kept, lane, base);
         if (kept && p < e_cap) {
             edge_src[p] = j; edge_dst[p] = R.i;
             weight[p] = (v / pi_table[j]) / s;
         }
-        base += __popcll(bal);
     }
 }
 

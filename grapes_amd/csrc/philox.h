@@ -22,6 +22,14 @@ __device__ __forceinline__ Philox4 philox4x32_10(uint64_t ctr, uint64_t seed) {
     Philox4 r; r.v[0] = c0; r.v[1] = c1; r.v[2] = c2; r.v[3] = c3;
     return r;
 }
+// raw 32-bit word i of the stream (seed, offset)
+__device__ __forceinline__ uint32_t philox_word_at(uint64_t seed, uint64_t offset, long long i) {
+    const Philox4 p = philox4x32_10(offset + (uint64_t)(i >> 2), seed);
+    const int q = (int)(i & 3);                                  // (selects: a dynamic index would put the four words in LDS)
+    return q == 0 ? p.v[0] : (q == 1 ? p.v[1] : (q == 2 ? p.v[2] : p.v[3]));
+}
+// (the same word by a dynamic index, kept: on philox_word_at's selects the kernels of the captured step that call this change their
+// registers, LDS and scratch — profiles/row_list_resources.txt)
 __device__ __forceinline__ float philox_uniform_at(uint64_t seed, uint64_t offset, long long i) {
     const Philox4 p = philox4x32_10(offset + (uint64_t)(i >> 2), seed);
     return (float)(p.v[i & 3] >> 8) * 5.9604644775390625e-08f;   // 2^-24

@@ -12,7 +12,7 @@
 // A row with deg <= fanout keeps everything; its words are skipped all the same, so p is the same on every path.  A row listed
 // twice draws twice (its p differs).
 //
-//   sage_scan_k    ONE workgroup: the rows' degrees, both exclusive prefixes (block_excl_scan_u64), the edge count, the overflow
+//   sage_scan_k    ONE workgroup: the rows' degrees, both exclusive prefixes (list_scan_tiles of row_list.h), the edge count, the overflow
 //                  bit, the stream's base offset for the write kernel and its advance by ceil(sum deg / 4)
 //   sage_write_k   one wavefront per list row.  deg <= fanout: a copy.  deg <= 64: a key per lane, its rank by 64 broadcast
 //                  compares, the kept lanes compacted by a ballot.  Longer rows: a lane takes four stream positions (one Philox
@@ -36,8 +36,8 @@
 // No kernel waits on another workgroup.
 #include "row_sum.h"
 #include "philox.h"
+#include "row_list.h"
 
-#define SAGE_SCAN_THREADS 1024
 #define SAGE_MAX_FANOUT 64
 #define SAGE_CAND 128                 // candidates a long row finishes in registers with (two per lane; half the histogram's LDS each for words and positions)
 #define SAGE_SLAB 128                 // rows per column-sum partial
@@ -52,15 +52,13 @@ __device__ __forceinline__ uint32_t sage_key(const uint32_t* __restrict__ keys, 
         if (status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);                // (a key list shorter than the rows' entries)
         return 0xffffffffu;
     }
-    const Philox4 w = philox4x32_10(off + (uint64_t)(p >> 2), seed);
-    const int q = (int)(p & 3);
-    return q == 0 ? w.v[0] : (q == 1 ? w.v[1] : (q == 2 ? w.v[2] : w.v[3]));
+    return philox_word_at(seed, off, p);
 }
 
 // ONE workgroup.  off_p[r] = sum of deg over the list rows before r, off_e[r] = min(sum of min(deg, fanout) before r, e_cap);
 // *d_e = min(total, e_cap); *base_off = the stream offset of this call; *d_philox_offset += ceil(sum deg / 4).
 // A row id outside [0, N) counts as an empty row and raises GRAPES_STATUS_BAD_INDEX.
-__global__ __launch_bounds__(SAGE_SCAN_THREADS) void sage_scan_k(const int64_t* __restrict__ rowptr, int N,
+__global__ __launch_bounds__(LIST_SCAN_THREADS) void sage_scan_k(const int64_t* __restrict__ rowptr, int N,
                                                                  const int32_t* __restrict__ rows, int m_host,
                                                                  const int32_t* __restrict__ d_m, int fanout, int e_cap,
                                                                  uint64_t philox_offset, uint64_t* d_philox_offset,
@@ -69,36 +67,22 @@ __global__ __launch_bounds__(SAGE_SCAN_THREADS) void sage_scan_k(const int64_t* 
                                                                  int32_t* status) {
     __shared__ unsigned long long lds[17];
     const int live = eff_count(d_m, m_host);
-    const int per = (m_host + SAGE_SCAN_THREADS - 1) / SAGE_SCAN_THREADS;
-    const int lo = min((int)threadIdx.x * per, m_host), hi = min(lo + per, m_host);
-    unsigned long long sd = 0ull, sc = 0ull;
     bool bad = false;
-    for (int r = lo; r < hi; ++r) {
-        long long deg = 0;
-        if (r < live) {
-            const int i = rows[r];
-            if ((unsigned)i < (unsigned)N) deg = (long long)(rowptr[i + 1] - rowptr[i]);
-            else bad = true;
-        }
-        if (deg < 0) deg = 0;
-        off_p[r] = deg;                                                       // (the degree, until the second loop)
-        sd += (unsigned long long)deg;
-        sc += (unsigned long long)(deg < fanout ? deg : fanout);
-    }
+    auto degrees = [&](int i0, long long (&v)[LIST_SCAN_PER]) {
+        list_row_degrees(rowptr, N, rows, i0, live, v, bad);
+#pragma unroll
+        for (int q = 0; q < LIST_SCAN_PER; ++q)                               // (the kept count, until the second prefix)
+            if (i0 + q < m_host) off_e[i0 + q] = (int)(v[q] < fanout ? v[q] : fanout);
+    };
+    auto kept = [&](int i0, int (&v)[LIST_SCAN_PER]) {
+#pragma unroll
+        for (int q = 0; q < LIST_SCAN_PER; ++q) v[q] = i0 + q < m_host ? off_e[i0 + q] : 0;
+    };
+    const unsigned long long total_d = list_scan_tiles<long long>(degrees, m_host, LIST_NO_CAP, off_p, lds);
     if (bad && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
-    unsigned long long total_d, total_c;
-    unsigned long long run_d = block_excl_scan_u64(sd, lds, &total_d);
-    unsigned long long run_c = block_excl_scan_u64(sc, lds, &total_c);
-    for (int r = lo; r < hi; ++r) {
-        const long long deg = off_p[r];
-        off_p[r] = (long long)run_d;
-        off_e[r] = run_c < (unsigned long long)e_cap ? (int)run_c : e_cap;
-        run_d += (unsigned long long)deg;
-        run_c += (unsigned long long)(deg < fanout ? deg : fanout);
-    }
+    const unsigned long long total_c = list_scan_tiles<int>(kept, m_host, (unsigned long long)e_cap, off_e, lds);
+    list_scan_finish(total_c, e_cap, nullptr, d_e, status);
     if (threadIdx.x == 0) {
-        *d_e = total_c < (unsigned long long)e_cap ? (int)total_c : e_cap;
-        if (total_c > (unsigned long long)e_cap && status) atomicOr(status, GRAPES_STATUS_EDGE_OVERFLOW);
         const uint64_t base = d_philox_offset ? *d_philox_offset : philox_offset;
         *base_off = base;
         if (d_philox_offset) *d_philox_offset = base + (uint64_t)((total_d + 3ull) >> 2);
@@ -122,10 +106,8 @@ __device__ __forceinline__ void sage_store(int p, long long t, const int32_t* __
 __device__ __forceinline__ void sage_emit(bool kept, long long t, int lane, const int32_t* __restrict__ col, int64_t a, int i, int N,
                                           int& base, int e_cap, int32_t* __restrict__ edge_src, int32_t* __restrict__ edge_dst,
                                           int64_t* __restrict__ edge_pos, int32_t* status) {
-    const unsigned long long bal = __ballot(kept);
-    const int p = base + __popcll(bal & ((1ull << lane) - 1ull));
+    const int p = wave_compact_slot(kept, lane, base);
     if (kept && p < e_cap) sage_store(p, t, col, a, i, N, edge_src, edge_dst, edge_pos, status);
-    base += __popcll(bal);
 }
 
 // A lane's share of one trip over a long row: the four stream positions 4 c .. 4 c + 3 of Philox counter c = c0 + rel (one Philox
@@ -156,11 +138,10 @@ __global__ __launch_bounds__(256) void sage_write_k(const int64_t* __restrict__ 
     __shared__ int hist[4][256];
     const int r = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
     if (r >= m_host) return;                                                  // (whole wavefronts leave)
-    if (r >= eff_count(d_m, m_host)) return;
-    const int i = rows[r];
-    if ((unsigned)i >= (unsigned)N) return;                                   // (counted as empty, the bit raised by sage_scan_k)
-    const int64_t a = rowptr[i];
-    const long long deg = (long long)(rowptr[i + 1] - a);
+    const ListRow R = list_row(rowptr, N, rows, r, eff_count(d_m, m_host), nullptr);   // (a bad id: empty, the bit raised by sage_scan_k)
+    const int i = R.i;
+    const int64_t a = R.a;
+    const long long deg = R.deg;
     int base = off_e[r];
     if (deg <= 0 || base >= e_cap) return;
     const long long P = off_p[r];
@@ -316,7 +297,7 @@ extern "C" int grapes_sage_sample_layer(const int64_t* rowptr, const int32_t* co
     long long* off_p = (long long*)workspace;
     uint64_t* base_off = (uint64_t*)(off_p + m);
     int32_t* off_e = (int32_t*)(base_off + 2);
-    hipLaunchKernelGGL(sage_scan_k, dim3(1), dim3(SAGE_SCAN_THREADS), 0, s, rowptr, num_nodes, rows, m, d_m, fanout, e_cap,
+    hipLaunchKernelGGL(sage_scan_k, dim3(1), dim3(LIST_SCAN_THREADS), 0, s, rowptr, num_nodes, rows, m, d_m, fanout, e_cap,
                        philox_offset, d_philox_offset, off_p, base_off, off_e, d_e, status);
     GRAPES_LAUNCH_CHECK();
     hipLaunchKernelGGL(sage_write_k, dim3(grapes_div_up((int64_t)m * 64, 256)), dim3(256), 0, s, rowptr, col, num_nodes, rows, m, d_m,

@@ -38,11 +38,12 @@
 //
 // Membership of the node set is tested as a sparse set: v is in the set iff m = node_map[v] < count and node_idx[m] == v, so
 // node_map needs no clearing (stale entries of other nodes are never trusted).
-#include "common.h"
 #include "philox.h"
+#include "row_list.h"
 
 #define SAINT_THREADS 1024
 #define SAINT_MAX_IDS 16384          // B (L + 1) <= this: the node set is sorted in 64 KiB of LDS
+#define SAINT_ANY_ID 0x7fffffff      // list_row's N for the edge kernels: node_idx is this library's own output and is not validated
 
 // The tail the walk and the draw share (one workgroup of SAINT_THREADS): ids[0 .. M) in LDS, written by this workgroup and not yet
 // fenced; P = M rounded up to a power of two (<= SAINT_MAX_IDS).  Sorts them, writes their ascending duplicate-free set to node_idx
@@ -281,8 +282,8 @@ __global__ __launch_bounds__(256) void saint_edge_count_k(const int64_t* __restr
     if (i >= n_cap) return;
     const int n = eff_count(d_count, n_cap);
     if (i >= n) { if (lane == 0) cnt[i] = 0; return; }
-    const int v = node_idx[i];
-    const int64_t a = rowptr[v], e = rowptr[v + 1];
+    const ListRow R = list_row(rowptr, SAINT_ANY_ID, node_idx, i, n, nullptr);
+    const int64_t a = R.a, e = R.a + R.deg;
     int c = 0;
     for (int64_t j = a + lane; j < e; j += 64) {
         const int u = col[j];
@@ -294,6 +295,8 @@ __global__ __launch_bounds__(256) void saint_edge_count_k(const int64_t* __restr
 }
 
 // ONE workgroup: rowptr_l[i] = sum of cnt[0 .. i) for i <= n_cap (rows at or past the count are empty); *d_e = min(total, e_cap)
+// (Its own 32-bit prefix, a thread walking its span, not row_list.h's tiled 64-bit one: on that saint_subgraph measured 1 - 2 % slower at
+// 256 and 768 ids, above the spread between runs of the parent — profiles/row_list_ab.json.)
 __global__ __launch_bounds__(SAINT_THREADS) void saint_edge_scan_k(const int32_t* __restrict__ cnt, const int32_t* __restrict__ d_count,
                                                                    int n_cap, int e_cap, int32_t* __restrict__ rowptr_l,
                                                                    int32_t* __restrict__ d_e, int32_t* status) {
@@ -309,11 +312,8 @@ __global__ __launch_bounds__(SAINT_THREADS) void saint_edge_scan_k(const int32_t
         rowptr_l[i] = i < n ? run : total;
         if (i < n) run += cnt[i];
     }
-    if (threadIdx.x == 0) {
-        rowptr_l[n_cap] = total;
-        *d_e = total < e_cap ? total : e_cap;
-        if (total > e_cap && status) atomicOr(status, GRAPES_STATUS_EDGE_OVERFLOW);
-    }
+    if (threadIdx.x == 0) rowptr_l[n_cap] = total;                        // (row pointers: not clamped)
+    list_scan_finish((unsigned long long)total, e_cap, nullptr, d_e, status);
 }
 
 // one wavefront per local row: the row's member entries, in CSR order, at rowptr_l[i] ..; nothing at or past e_cap is written
@@ -329,9 +329,8 @@ __global__ __launch_bounds__(256) void saint_edge_write_k(const int64_t* __restr
     const int i = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
     if (i >= n_cap) return;
     const int n = eff_count(d_count, n_cap);
-    if (i >= n) return;
-    const int v = node_idx[i];
-    const int64_t a = rowptr[v], e = rowptr[v + 1];
+    const ListRow R = list_row(rowptr, SAINT_ANY_ID, node_idx, i, n, nullptr);
+    const int64_t a = R.a, e = R.a + R.deg;
     int base = rowptr_l[i];
     for (int64_t j0 = a; j0 < e; j0 += 64) {
         const int64_t j = j0 + lane;
@@ -341,9 +340,7 @@ __global__ __launch_bounds__(256) void saint_edge_write_k(const int64_t* __restr
             const int mm = node_map[u];
             if ((unsigned)mm < (unsigned)n && node_idx[mm] == u) m = mm;
         }
-        const uint64_t bal = __ballot(m >= 0);
-        const int rank = __popcll(bal & ((1ull << lane) - 1ull));
-        const int p = base + rank;
+        const int p = wave_compact_slot(m >= 0, lane, base);
         if (m >= 0 && p < e_cap) {
             src[p] = i; dst[p] = m;
             if (IDS) {
@@ -351,7 +348,6 @@ __global__ __launch_bounds__(256) void saint_edge_write_k(const int64_t* __restr
                 if (edge_norm_b) edge_norm_b[p] = edge_norm[j];
             }
         }
-        base += __popcll(bal);
         if (base >= e_cap) break;
     }
 }

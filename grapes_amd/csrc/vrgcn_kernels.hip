@@ -29,7 +29,7 @@
 // entry is dropped; it then contributes 0 times row 0 of the table, so a non-finite value there would reach the sum (as in
 // row_sum.h, where the stand-in is the row itself).
 #include "row_gather.h"
-#include "block_prims.h"
+#include "row_list.h"
 
 // The long-row threshold (= the chunk length) and the history rows in flight were chosen by measurement on the products-shaped
 // synthetic graph (batch 512, width 256; DESIGN.md has the table): chunks of 512 entries walked four rows at a time leave one group
@@ -182,7 +182,10 @@ __global__ __launch_bounds__(256) void vrgcn_rows_k(VrArgs a, int skip_long) {
 }
 
 // ONE workgroup.  item_off[r] = min(the chunks of the long rows listed before r, item_cap), item_off[m] = the live items; more
-// than item_cap raise GRAPES_STATUS_EDGE_OVERFLOW (the rows past the capacity then lack chunks: the result is invalid).
+// than item_cap raise GRAPES_STATUS_EDGE_OVERFLOW (the rows past the capacity then lack chunks: the result is invalid).  A row that
+// names no node has no chunks; vrgcn_rows_k raises its bit.
+// (Its own 32-bit prefix, not row_list.h's tiled 64-bit one: on that the call measured 5 % slower at 512 rows, above the spread
+// between two runs of the parent — profiles/row_list_ab.json.)
 __global__ __launch_bounds__(VRGCN_SCAN_THREADS) void vrgcn_items_k(const int64_t* __restrict__ rowptr, int N,
                                                                     const int32_t* __restrict__ rows_g, int m, int item_cap,
                                                                     int32_t* __restrict__ item_off, int32_t* status) {
@@ -191,9 +194,7 @@ __global__ __launch_bounds__(VRGCN_SCAN_THREADS) void vrgcn_items_k(const int64_
     const int lo = min((int)threadIdx.x * per, m), hi = min(lo + per, m);
     int mine = 0;
     for (int r = lo; r < hi; ++r) {
-        const int u = rows_g[r];
-        long long d = 0;
-        if ((unsigned)u < (unsigned)N) d = rowptr[u + 1] - rowptr[u];
+        const long long d = list_row(rowptr, N, rows_g, r, m, nullptr).deg;
         const long long nc = d > VRGCN_LONG_ROW ? (d + VRGCN_LONG_ROW - 1) / VRGCN_LONG_ROW : 0;
         const int c = nc > item_cap ? item_cap + 1 : (int)nc;                // (clamped: the prefix stays inside 32 bits)
         item_off[r + 1] = c;                                                  // (the count, until the second loop)
@@ -205,20 +206,8 @@ __global__ __launch_bounds__(VRGCN_SCAN_THREADS) void vrgcn_items_k(const int64_
         run += item_off[r + 1];
         item_off[r + 1] = run < item_cap ? (int)run : item_cap;
     }
-    if (threadIdx.x == 0) {
-        item_off[0] = 0;
-        if (total > item_cap && status) atomicOr(status, GRAPES_STATUS_EDGE_OVERFLOW);
-    }
-}
-
-// the listed row of work item `it`: the last r with item_off[r] <= it (rows without items share their successor's offset)
-__device__ __forceinline__ int vr_item_row(const int32_t* __restrict__ item_off, int m, int it) {
-    int lo = 0, hi = m;                                                       // the first r in [0, m] with item_off[r] > it, minus 1
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (item_off[mid + 1] > it) hi = mid; else lo = mid + 1;
-    }
-    return lo;
+    if (threadIdx.x == 0) item_off[0] = 0;
+    list_scan_finish((unsigned long long)total, item_cap, nullptr, nullptr, status);
 }
 
 template <int VEC, int LPR, int NS>
@@ -226,16 +215,15 @@ __global__ __launch_bounds__(256) void vrgcn_chunks_k(VrArgs a) {
     const int l = threadIdx.x % LPR, G = 256 / LPR;
     const int n_items = a.item_off[a.m];
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
-        const int r = vr_item_row(a.item_off, a.m, it);
+        // the last row with item_off[r] <= it: rows without items share their successor's offset and are stepped over
+        const int r = lower_bound<int32_t, int, int>(a.item_off, a.m, it + 1) - 1;
+        const ListRow R = list_row(a.rowptr, a.N, a.rows_g, r, a.m, nullptr);
         float acc[NS][VEC];
         vr_zero<VEC, NS>(acc);
-        if (r < a.m) {
-            const int u = a.rows_g[r];
-            if ((unsigned)u < (unsigned)a.N) {
-                const long long beg = a.rowptr[u] + (long long)(it - a.item_off[r]) * VRGCN_LONG_ROW, re = a.rowptr[u + 1];
-                const long long end = beg + VRGCN_LONG_ROW < re ? beg + VRGCN_LONG_ROW : re;
-                vr_full_walk<VEC, LPR, NS>(a, beg, end, l, acc);
-            }
+        if (R.i >= 0) {
+            const long long beg = R.a + (long long)(it - a.item_off[r]) * VRGCN_LONG_ROW, re = R.a + R.deg;
+            const long long end = beg + VRGCN_LONG_ROW < re ? beg + VRGCN_LONG_ROW : re;
+            vr_full_walk<VEC, LPR, NS>(a, beg, end, l, acc);
         }
         row_store<VEC, LPR, NS>(a.pacc, it, a.F, l, acc);
     }

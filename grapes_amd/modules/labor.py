@@ -39,82 +39,51 @@ from typing import Optional, Sequence
 import torch
 
 from .. import ops
-from .sage import check_fanouts
-from .sampling import _graph_of, as_targets, draw_seed, local_edge_lists, raise_on_status, union_of_lists
+from .sampling import InwardSampler
 
 _EVERY = 2 ** 31 - 1                # the fanout of a -1 layer: past every degree
 
 
-class LaborSampler:
+class LaborSampler(InwardSampler):
     """LaborSampler(data_or_graph, fanouts, importance_iters=0, layer_dependency=False, seed=None).  data_or_graph: a DeviceGraph, or
     a data object as the GraphSAINT samplers take.  fanouts: one entry per layer, fanouts[0] next to the output; -1 keeps every
     neighbour, else 1 .. ops.SAGE_MAX_FANOUT.  importance_iters: 0 .. ops.LABOR_MAX_ITERS.  seed: the Philox key of the draws (None:
     from torch's generator)."""
 
+    _KIND = "layer-neighbour"
+
     def __init__(self, data_or_graph, fanouts: Sequence[int], importance_iters: int = 0, layer_dependency: bool = False,
                  seed: Optional[int] = None):
-        self.fanouts = check_fanouts(fanouts)
-        self.num_layers = len(self.fanouts)
         self.importance_iters = int(importance_iters)
         if not 0 <= self.importance_iters <= ops.LABOR_MAX_ITERS:
             raise ValueError(f"LaborSampler: importance_iters {importance_iters} is not built (0 .. {ops.LABOR_MAX_ITERS})")
         self.layer_dependency = bool(layer_dependency)
-        self.graph, self.data = _graph_of(data_or_graph)
-        g = self.graph
-        if g.nnz >= 2 ** 31:
-            raise ValueError("layer-neighbour sampling over a graph with 2^31 or more entries is not built: the layer's entry offsets "
-                             "are 32-bit")
-        self.seed, self.philox_offset = draw_seed(seed), 0
-        self.status = torch.zeros(1, dtype=torch.int32, device=g.device)
-        self.scratch = ops.labor_scratch(g.num_nodes, g.device) if self.importance_iters else None
-        if ops.csr_symmetric_check(g.rowptr, g.col, g.num_nodes) & 2:
-            raise ops._lib.GrapesHipError("LaborSampler: a column id is outside [0, num_nodes)")
+        super().__init__(data_or_graph, fanouts, seed)
+        self.scratch = ops.labor_scratch(self.graph.num_nodes, self.graph.device) if self.importance_iters else None
 
     def layer_base(self, d: int) -> int:
         """The Philox counter of node 0's variates in layer d of the NEXT sample() call."""
         return self.philox_offset + (0 if self.layer_dependency else d * ((self.graph.num_nodes + 3) // 4))
 
+    def _layer(self, d, k, prev, eoff, deg_sum, keys):
+        g = self.graph
+        c = pi = None
+        if self.importance_iters and k != -1:
+            c, pi = ops.labor_importance(g.rowptr, g.col, g.num_nodes, prev, k, self.importance_iters, self.scratch, status=self.status)
+        src, dst, pos, w, d_l = ops.labor_sample_layer(g.rowptr, g.col, g.num_nodes, prev, _EVERY if k == -1 else k, keys=keys,
+                                                       philox_seed=self.seed, philox_base=self.layer_base(d), c=c, pi=pi,
+                                                       deg_sum=deg_sum, want_pos=k != -1, status=self.status)
+        return dict(edge_src=src, edge_dst=dst, edge_pos=pos, edge_weight=w, c=c, pi=pi), d_l   # (a -1 layer: no edge_pos, rows whole)
+
+    def _empty_layer(self, dev):
+        return dict(super()._empty_layer(dev), edge_weight=torch.zeros(0, dtype=torch.float32, device=dev), c=None, pi=None)
+
     def sample(self, targets, keys=None) -> SimpleNamespace:
         """targets: node ids (any integer tensor; taken in the given order).  keys: per layer one int32 table of N words indexed by
         GLOBAL node id — one word per node, not per entry — replacing the layer's variates (tests); None entries and layers past the
         list draw from the stream.  Returns the batch namespace described in the module docstring."""
-        g = self.graph
-        dev, N = g.device, g.num_nodes
-        targets = as_targets(targets, dev, "LaborSampler")
-        keys = list(keys) if keys is not None else []
-        prev, layers = targets, []
-        for d, k in enumerate(self.fanouts):
-            _, d_e = ops.frontier_offsets(g.rowptr, prev)
-            deg_sum = int(d_e.item())                                    # the rows' entry count (host read)
-            if deg_sum >= 2 ** 31:
-                raise ValueError("LaborSampler.sample: a layer's rows hold 2^31 or more entries")
-            c = pi = None
-            if deg_sum == 0:
-                empty = torch.zeros(0, dtype=torch.int32, device=dev)
-                src, dst, pos = empty, empty, torch.zeros(0, dtype=torch.int64, device=dev)
-                w = torch.zeros(0, dtype=torch.float32, device=dev)
-            else:
-                if self.importance_iters and k != -1:
-                    c, pi = ops.labor_importance(g.rowptr, g.col, N, prev, k, self.importance_iters, self.scratch,
-                                                 status=self.status)
-                src, dst, pos, w, d_l = ops.labor_sample_layer(g.rowptr, g.col, N, prev, _EVERY if k == -1 else k,
-                                                               keys=keys[d] if d < len(keys) else None, philox_seed=self.seed,
-                                                               philox_base=self.layer_base(d), c=c, pi=pi, deg_sum=deg_sum,
-                                                               want_pos=k != -1, status=self.status)
-                e = int(d_l.item())                                      # the layer's entry count (host read)
-                src, dst, w = src[:e], dst[:e], w[:e]
-                pos = pos[:e] if pos is not None else None               # (a -1 layer keeps its rows whole, in order)
-            after = union_of_lists(g, [prev, src], self.status) if src.numel() else union_of_lists(g, [prev], self.status)
-            layers.append(SimpleNamespace(prev=prev, after=after, edge_src=src, edge_dst=dst, edge_pos=pos, edge_weight=w, fanout=k,
-                                          c=c, pi=pi))
-            prev = after
-        self.philox_offset += self.num_layers * ((N + 3) // 4)
-        node_idx = prev                                  # the last union holds every earlier layer, and left node_map[id] = rank
-        return SimpleNamespace(node_idx=node_idx, num_nodes=node_idx.numel(), targets=targets,
-                               local_targets=ops.tensormap_map(g.node_map, targets), edge_index=local_edge_lists(g, layers, dev),
-                               edge_weight=[L.edge_weight for L in layers], uniform=self.importance_iters == 0, layers=layers)
-
-    def check(self):
-        """Reads the status word (synchronises); raises GrapesHipError on an edge overflow or a bad id, and clears it (and, as
-        DeviceGraph.check_status does, the bitmaps a truncated batch may have left marked)."""
-        raise_on_status(self.status, "layer-neighbour sampler", graph=self.graph)
+        batch = super().sample(targets, keys)
+        self.philox_offset += self.num_layers * ((self.graph.num_nodes + 3) // 4)
+        batch.edge_weight = [L.edge_weight for L in batch.layers]
+        batch.uniform = self.importance_iters == 0
+        return batch

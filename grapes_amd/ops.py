@@ -2625,6 +2625,64 @@ def saint_norms(rowptr, num_nodes: int, node_count, edge_count, num_samples: int
     return edge_norm, node_norm
 
 
+# ------------------------------------------------------------------------------- what the samplers' layer calls share
+def _list_rows(who, rowptr, col, num_nodes, rows, d_m, status, bad=False, says="rowptr holds N + 1 values and rows is not empty"):
+    """The checks of every call over a list of rows of the CSR -> (N, m).  bad: the caller's further conditions under the same
+    message `says`."""
+    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(rows, _i32, "rows"); _chk(d_m, _i32, "d_m", True)
+    _chk(status, _i32, "status", True)
+    N, m = int(num_nodes), rows.numel()
+    if rowptr.numel() != N + 1 or m < 1 or bad:
+        raise ValueError(f"{who}: {says}")
+    return N, m
+
+
+def _edge_buffers(who, ec, dev, out, pos=None, weight=None, weight_name="edge_weight"):
+    """A layer's edge buffers (edge_src, edge_dst[, edge_pos][, the weights], e_count): allocated for e_cap = ec entries, or out's,
+    checked.  pos / weight: None — the call has no such buffer; else whether to allocate it (a buffer not wanted is None)."""
+    opt = [(want, dt, name) for want, dt, name in ((pos, _i64, "edge_pos"), (weight, _f32, weight_name)) if want is not None]
+    if out is None:
+        out = (torch.empty(ec, dtype=_i32, device=dev), torch.empty(ec, dtype=_i32, device=dev),
+               *(torch.empty(ec, dtype=dt, device=dev) if want else None for want, dt, _ in opt),
+               torch.empty(1, dtype=_i32, device=dev))
+    src, dst, *rest, d_e = out
+    _chk(src, _i32, "edge_src"); _chk(dst, _i32, "edge_dst")
+    for t, (_, dt, name) in zip(rest, opt):
+        _chk(t, dt, name, True)
+    _chk(d_e, _i32, "e_count")
+    if any(t is not None and t.numel() < ec for t in (src, dst, *rest)):
+        raise ValueError(f"{who}: the edge buffers hold e_cap values each")
+    return out
+
+
+def _key_words(who, keys) -> int:
+    """The number of 32-bit words in a caller's key tensor (0 for None), after its type check."""
+    if keys is None:
+        return 0
+    if not keys.is_cuda or keys.dtype not in (_i32, getattr(torch, "uint32", _i32)) or not keys.is_contiguous():
+        raise TypeError(f"{who}: keys must be a contiguous cuda tensor of 32-bit words (int32 bit patterns or uint32)")
+    return keys.numel()
+
+
+def _candidate_set(who, rowptr, rowptr_t, col_t, num_nodes, ids, n, d_n, prev_bits, m, d_m, status):
+    """The candidate-set arguments of the layer-wise importances -> (N, n, m): n defaults to ids' length or N, m to N — a bitmap comes
+    with its m."""
+    _chk(rowptr, _i64, "rowptr"); _chk(rowptr_t, _i64, "rowptr_t"); _chk(col_t, _i32, "col_t"); _chk(ids, _i32, "ids", True)
+    _chk(d_n, _i32, "d_n", True); _chk(prev_bits, _i64, "prev_bits", True); _chk(d_m, _i32, "d_m", True)
+    _chk(status, _i32, "status", True)
+    N = int(num_nodes)
+    if n is None:
+        n = ids.numel() if ids is not None else N
+    if m is None:
+        if prev_bits is not None:
+            raise ValueError(f"{who}: a bitmap comes with m, the number of rows it holds")
+        m = N
+    n, m = int(n), int(m)
+    if rowptr.numel() != N + 1 or rowptr_t.numel() != N + 1 or n < 1 or m < 1 or (ids is not None and ids.numel() < n):
+        raise ValueError(f"{who}: rowptr / rowptr_t hold N + 1 values, ids at least n >= 1 ids, and m >= 1")
+    return N, n, m
+
+
 # ------------------------------------------------------------------------------- LADIES / FastGCN layer-wise samplers
 # [LADIES-recall: acbull/LADIES pytorch_ladies.py, ladies_sampler / fastgcn_sampler]  V = A + I, P = D^-1 V (grapes_hip.h).
 def ladies_importance(rowptr, rowptr_t, col_t, num_nodes: int, ids=None, n=None, d_n=None, prev_bits=None, m=None, d_m=None,
@@ -2633,19 +2691,9 @@ def ladies_importance(rowptr, rowptr_t, col_t, num_nodes: int, ids=None, n=None,
     (ids None: j = k, n defaults to N), logit = logf(pi) - (20 + logf(float(m))).  The set: the bitmap prev_bits of m rows, or every
     row (prev_bits None: m defaults to N).  rowptr_t / col_t: the CSR of the transpose (the graph's own arrays when symmetric).
     pi_table (fp32 [N]): also pi_table[ids[k]] = pi[k].  out: the two tensors to write; entries past *d_n stay as they are."""
-    _chk(rowptr, _i64, "rowptr"); _chk(rowptr_t, _i64, "rowptr_t"); _chk(col_t, _i32, "col_t"); _chk(ids, _i32, "ids", True)
-    _chk(d_n, _i32, "d_n", True); _chk(prev_bits, _i64, "prev_bits", True); _chk(d_m, _i32, "d_m", True)
-    _chk(pi_table, _f32, "pi_table", True); _chk(status, _i32, "status", True)
-    N, dev = int(num_nodes), rowptr.device
-    if n is None:
-        n = ids.numel() if ids is not None else N
-    if m is None:
-        if prev_bits is not None:
-            raise ValueError("ladies_importance: a bitmap comes with m, the number of rows it holds")
-        m = N
-    n, m = int(n), int(m)
-    if rowptr.numel() != N + 1 or rowptr_t.numel() != N + 1 or n < 1 or m < 1 or (ids is not None and ids.numel() < n):
-        raise ValueError("ladies_importance: rowptr / rowptr_t hold N + 1 values, ids at least n >= 1 ids, and m >= 1")
+    _chk(pi_table, _f32, "pi_table", True)
+    N, n, m = _candidate_set("ladies_importance", rowptr, rowptr_t, col_t, num_nodes, ids, n, d_n, prev_bits, m, d_m, status)
+    dev = rowptr.device
     if (prev_bits is not None and prev_bits.numel() < (N + 63) // 64) or (pi_table is not None and pi_table.numel() < N):
         raise ValueError("ladies_importance: prev_bits holds ceil(N / 64) words, pi_table one value per node")
     if out is None:
@@ -2664,19 +2712,13 @@ def ladies_layer(rowptr, col, num_nodes: int, rows, keep_bits, pi_table, e_cap: 
     in order and ascending j, every (i, j) of V = A + I with j in the bitmap keep_bits — source j, target i, global ids — with
     weight (v_ij / pi_table[j]) / the row's sum of them.  More than e_cap entries set the overflow status bit.
     out: the four tensors to write."""
-    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(rows, _i32, "rows"); _chk(keep_bits, _i64, "keep_bits")
-    _chk(pi_table, _f32, "pi_table"); _chk(d_m, _i32, "d_m", True); _chk(status, _i32, "status", True)
-    N, dev, m, ec = int(num_nodes), rows.device, rows.numel(), int(e_cap)
-    if rowptr.numel() != N + 1 or keep_bits.numel() < (N + 63) // 64 or pi_table.numel() < N or m < 1 or ec < 1:
-        raise ValueError("ladies_layer: rowptr holds N + 1 values, keep_bits ceil(N / 64) words, pi_table N values; rows and e_cap "
-                         "are not empty")
-    if out is None:
-        out = (torch.empty(ec, dtype=_i32, device=dev), torch.empty(ec, dtype=_i32, device=dev),
-               torch.empty(ec, dtype=_f32, device=dev), torch.empty(1, dtype=_i32, device=dev))
-    src, dst, w, d_e = out
-    _chk(src, _i32, "edge_src"); _chk(dst, _i32, "edge_dst"); _chk(w, _f32, "weight"); _chk(d_e, _i32, "e_count")
-    if min(src.numel(), dst.numel(), w.numel()) < ec:
-        raise ValueError("ladies_layer: the edge buffers hold e_cap values each")
+    _chk(keep_bits, _i64, "keep_bits"); _chk(pi_table, _f32, "pi_table")
+    dev, ec = rows.device, int(e_cap)
+    N, m = _list_rows("ladies_layer", rowptr, col, num_nodes, rows, d_m, status,
+                      keep_bits.numel() < (int(num_nodes) + 63) // 64 or pi_table.numel() < int(num_nodes) or ec < 1,
+                      "rowptr holds N + 1 values, keep_bits ceil(N / 64) words, pi_table N values; rows and e_cap are not empty")
+    src, dst, w, d_e = _edge_buffers("ladies_layer", ec, dev, out, weight=True, weight_name="weight")
+    _chk(w, _f32, "weight")
     ws = _ws(lib().grapes_ladies_layer_workspace_bytes(m), dev)
     _lib.check(lib().grapes_ladies_layer(_p(rowptr), _p(col), N, _p(rows), m, _p(d_m), _p(keep_bits), _p(pi_table), ec, _p(src),
                                          _p(dst), _p(w), _p(d_e), _p(ws), _p(status), _stream()), "ladies_layer")
@@ -2692,24 +2734,13 @@ def asgcn_importance(rowptr, rowptr_t, col_t, num_nodes: int, x, w_g, b_g, ids=N
     logit = (logq - max logq) - 20.  x fp32 [N, F] (rows may be strided), w_g fp32 [F], b_g fp32 [1].  The set: the bitmap prev_bits
     of m rows, or every row (prev_bits None).  q_table / a_table (fp32 [N]): also written at the candidates.  out: the five tensors
     to write; entries past *d_n stay as they are."""
-    _chk(rowptr, _i64, "rowptr"); _chk(rowptr_t, _i64, "rowptr_t"); _chk(col_t, _i32, "col_t"); _chk(ids, _i32, "ids", True)
-    _chk(d_n, _i32, "d_n", True); _chk(prev_bits, _i64, "prev_bits", True); _chk(d_m, _i32, "d_m", True)
-    _chk(q_table, _f32, "q_table", True); _chk(a_table, _f32, "a_table", True); _chk(status, _i32, "status", True)
-    _chk(w_g, _f32, "w_g"); _chk(b_g, _f32, "b_g")
-    N, dev = int(num_nodes), rowptr.device
+    _chk(q_table, _f32, "q_table", True); _chk(a_table, _f32, "a_table", True); _chk(w_g, _f32, "w_g"); _chk(b_g, _f32, "b_g")
     if x.dim() != 2:
         raise ValueError("asgcn_importance: x is a matrix of one feature row per node")
     F = int(x.shape[1])
     ldx = _row_strided(x, F, "asgcn_importance: x")
-    if n is None:
-        n = ids.numel() if ids is not None else N
-    if m is None:
-        if prev_bits is not None:
-            raise ValueError("asgcn_importance: a bitmap comes with m, the number of rows it holds")
-        m = N
-    n, m = int(n), int(m)
-    if rowptr.numel() != N + 1 or rowptr_t.numel() != N + 1 or n < 1 or m < 1 or (ids is not None and ids.numel() < n):
-        raise ValueError("asgcn_importance: rowptr / rowptr_t hold N + 1 values, ids at least n >= 1 ids, and m >= 1")
+    N, n, m = _candidate_set("asgcn_importance", rowptr, rowptr_t, col_t, num_nodes, ids, n, d_n, prev_bits, m, d_m, status)
+    dev = rowptr.device
     if x.shape[0] < N or F < 1 or w_g.numel() != F or b_g.numel() != 1:
         raise ValueError("asgcn_importance: x holds one row of F >= 1 features per node, w_g F values, b_g one")
     if (prev_bits is not None and prev_bits.numel() < (N + 63) // 64) or any(t is not None and t.numel() < N for t in (q_table, a_table)):
@@ -2788,30 +2819,19 @@ def sage_sample_layer(rowptr, col, num_nodes: int, rows, fanout: int, e_cap: Opt
     deg_sum: the rows' entry count when the caller knows it — 2^31 or more is refused here, and keys must hold that many.
     d_philox_offset: int64 [1] device stream offset, used instead of philox_offset and advanced by ceil(deg_sum / 4).
     out: the four tensors to write (edge_pos may be None)."""
-    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(rows, _i32, "rows"); _chk(d_m, _i32, "d_m", True)
-    _chk(status, _i32, "status", True); _chk(d_philox_offset, _i64, "d_philox_offset", True)
-    N, dev, m, k = int(num_nodes), rows.device, rows.numel(), int(fanout)
+    _chk(d_philox_offset, _i64, "d_philox_offset", True)
+    dev, k = rows.device, int(fanout)
     if not 1 <= k <= SAGE_MAX_FANOUT:
         raise ValueError(f"sage_sample_layer: fanout = {fanout} is not built (1 <= fanout <= {SAGE_MAX_FANOUT})")
-    ec = m * k if e_cap is None else int(e_cap)
-    if rowptr.numel() != N + 1 or m < 1 or ec < 1:
-        raise ValueError("sage_sample_layer: rowptr holds N + 1 values; rows and e_cap are not empty")
+    ec = rows.numel() * k if e_cap is None else int(e_cap)
+    N, m = _list_rows("sage_sample_layer", rowptr, col, num_nodes, rows, d_m, status, ec < 1,
+                      "rowptr holds N + 1 values; rows and e_cap are not empty")
     if deg_sum is not None and int(deg_sum) >= 2 ** 31:
         raise ValueError("sage_sample_layer: rows with 2^31 or more entries in all are not built")
-    n_keys = 0
-    if keys is not None:
-        if not keys.is_cuda or keys.dtype not in (_i32, getattr(torch, "uint32", _i32)) or not keys.is_contiguous():
-            raise TypeError("sage_sample_layer: keys must be a contiguous cuda tensor of 32-bit words (int32 bit patterns or uint32)")
-        n_keys = keys.numel()
-        if deg_sum is not None and n_keys < int(deg_sum):
-            raise ValueError("sage_sample_layer: keys holds one word per entry of the listed rows")
-    if out is None:
-        out = (torch.empty(ec, dtype=_i32, device=dev), torch.empty(ec, dtype=_i32, device=dev),
-               torch.empty(ec, dtype=_i64, device=dev) if want_pos else None, torch.empty(1, dtype=_i32, device=dev))
-    src, dst, pos, d_e = out
-    _chk(src, _i32, "edge_src"); _chk(dst, _i32, "edge_dst"); _chk(pos, _i64, "edge_pos", True); _chk(d_e, _i32, "e_count")
-    if min(src.numel(), dst.numel()) < ec or (pos is not None and pos.numel() < ec):
-        raise ValueError("sage_sample_layer: the edge buffers hold e_cap values each")
+    n_keys = _key_words("sage_sample_layer", keys)
+    if keys is not None and deg_sum is not None and n_keys < int(deg_sum):
+        raise ValueError("sage_sample_layer: keys holds one word per entry of the listed rows")
+    src, dst, pos, d_e = _edge_buffers("sage_sample_layer", ec, dev, out, pos=bool(want_pos))
     ws = _ws(lib().grapes_sage_sample_layer_workspace_bytes(m), dev)
     _lib.check(lib().grapes_sage_sample_layer(_p(rowptr), _p(col), N, _p(rows), m, _p(d_m), k, _p(keys), n_keys,
                                               int(philox_seed) & (2 ** 64 - 1), int(philox_offset) & (2 ** 64 - 1),
@@ -2820,7 +2840,7 @@ def sage_sample_layer(rowptr, col, num_nodes: int, rows, fanout: int, e_cap: Opt
     return src, dst, pos, d_e
 
 
-def _sage_rows(t, name: str, n: int, f: int, allow_none: bool = False):
+def _strided_rows(t, name: str, n: int, f: int, allow_none: bool = False):
     """The leading dimension of a row-major [n, f] matrix that may be a column block of a wider one."""
     if t is None:
         if allow_none:
@@ -2862,8 +2882,8 @@ def sage_aggregate_fwd(src, prep: PreparedGraph, aggr: str = "mean", add=None, b
     loops = gcn2_loops(prep)
     if out is None:
         out = torch.empty((n, f), dtype=_f32, device=src.device)
-    ld_src, ld_add = _sage_rows(src, "src", n, f), _sage_rows(add, "add", n, f, True)
-    ld_out, ld_copy = _sage_rows(out, "out", n, f), _sage_rows(copy_out, "copy_out", n, f, True)
+    ld_src, ld_add = _strided_rows(src, "src", n, f), _strided_rows(add, "add", n, f, True)
+    ld_out, ld_copy = _strided_rows(out, "out", n, f), _strided_rows(copy_out, "copy_out", n, f, True)
     items, n_items, cap = _long_items(prep, True, True, long_rows)
     ws = _ws(lib().grapes_sage_aggregate_workspace_bytes(0, cap, f), src.device) if cap else None
     _lib.check(lib().grapes_sage_aggregate_fwd(_p(src), ld_src, _p(add), ld_add, _p(bias), _p(loops), _p(prep.rowptr_t),
@@ -2890,9 +2910,9 @@ def sage_aggregate_bwd(dout, prep: PreparedGraph, aggr: str = "mean", relu_out=N
     if dadd is None and want_add:
         dadd = torch.empty((n, f), dtype=_f32, device=dev)
     dbias = torch.empty(f, dtype=_f32, device=dev) if want_bias else None
-    ld_dout, ld_relu = _sage_rows(dout, "dout", n, f), _sage_rows(relu_out, "relu_out", n, f, True)
-    ld_add, ld_dsrc = _sage_rows(add, "add", n, f, True), _sage_rows(dsrc, "dsrc", n, f, True)
-    ld_dadd = _sage_rows(dadd, "dadd", n, f, True)
+    ld_dout, ld_relu = _strided_rows(dout, "dout", n, f), _strided_rows(relu_out, "relu_out", n, f, True)
+    ld_add, ld_dsrc = _strided_rows(add, "add", n, f, True), _strided_rows(dsrc, "dsrc", n, f, True)
+    ld_dadd = _strided_rows(dadd, "dadd", n, f, True)
     items, n_items, cap = _long_items(prep, False, False, long_rows) if dsrc is not None else (None, None, 0)
     ws = _ws(lib().grapes_sage_aggregate_workspace_bytes(n, cap, f), dev)
     _lib.check(lib().grapes_sage_aggregate_bwd(_p(dout), ld_dout, _p(relu_out), ld_relu, _p(loops), _p(prep.rowptr_t),
@@ -2953,7 +2973,7 @@ def vrgcn_aggregate_fwd(h, node_idx, hbar, dinv, rowptr, col, rows_g, rows_l, pr
     dev = h.device
     if out is None:
         out = torch.empty((m, f), dtype=_f32, device=dev)
-    ld_out = _sage_rows(out, "out", m, f)
+    ld_out = _strided_rows(out, "out", m, f)
     coef = torch.empty(max(m, 1), dtype=_f32, device=dev) if want_coef else None
     ws = _ws(lib().grapes_vrgcn_aggregate_workspace_bytes(m, item_cap, f), dev) if item_cap else None
     st = status if status is not None else prep.status
@@ -2979,7 +2999,7 @@ def vrgcn_aggregate_bwd(da, coef, pos, node_idx, dinv, prep: PreparedGraph, out=
         raise ValueError("the prepared kept entries cover node_idx's n_local rows")
     if out is None:
         out = torch.empty((n_local, f), dtype=_f32, device=da.device)
-    ld_out = _sage_rows(out, "dh", n_local, f)
+    ld_out = _strided_rows(out, "dh", n_local, f)
     st = status if status is not None else prep.status
     _lib.check(lib().grapes_vrgcn_aggregate_bwd(_p(da), f, _p(coef), _p(pos), _p(node_idx), _p(dinv), dinv.numel(), _p(prep.rowptr_s),
                                                 _p(prep.csr_dst), _p(out), ld_out, n_local, m, f, _p(st), _stream()),
@@ -2992,15 +3012,6 @@ def vrgcn_aggregate_bwd(da, coef, pos, node_idx, dinv, prep: PreparedGraph, out=
 LABOR_CHUNK = 64             # GRAPES_LONG_ROW: the entries of one work item; a longer row is cut over several wavefronts
 LABOR_MAX_ITERS = 8
 LABOR_ITEM_CAP_MAX = 1 << 24
-
-
-def _labor_rows(who, rowptr, col, num_nodes, rows, d_m, status):
-    _chk(rowptr, _i64, "rowptr"); _chk(col, _i32, "col"); _chk(rows, _i32, "rows"); _chk(d_m, _i32, "d_m", True)
-    _chk(status, _i32, "status", True)
-    N, m = int(num_nodes), rows.numel()
-    if N < 1 or rowptr.numel() != N + 1 or m < 1:
-        raise ValueError(f"{who}: rowptr holds N + 1 values and rows is not empty")
-    return N, m
 
 
 def labor_item_cap(m: int, deg_sum: int) -> int:
@@ -3023,7 +3034,7 @@ def labor_sample_layer(rowptr, col, num_nodes: int, rows, fanout: int, e_cap: Op
     (2^31 or more is refused); it sets the defaults e_cap = deg_sum — which cannot overflow — and item_cap
     (ops.labor_item_cap); without it both e_cap and item_cap are required.  More kept entries than e_cap, or more work items than
     item_cap, set the overflow status bit.  out: the five tensors to write (edge_pos and edge_weight may be None)."""
-    N, m = _labor_rows("labor_sample_layer", rowptr, col, num_nodes, rows, d_m, status)
+    N, m = _list_rows("labor_sample_layer", rowptr, col, num_nodes, rows, d_m, status, int(num_nodes) < 1)
     _chk(c, _f32, "c", True); _chk(pi, _f32, "pi", True)
     k, dev = int(fanout), rows.device
     if not 1 <= k < 2 ** 31:
@@ -3038,20 +3049,9 @@ def labor_sample_layer(rowptr, col, num_nodes: int, rows, fanout: int, e_cap: Op
     ic = labor_item_cap(m, deg_sum) if item_cap is None else int(item_cap)
     if ec < 1 or not 1 <= ic <= LABOR_ITEM_CAP_MAX:
         raise ValueError(f"labor_sample_layer: e_cap is at least 1 and item_cap is 1 .. {LABOR_ITEM_CAP_MAX}")
-    if keys is not None:
-        if not keys.is_cuda or keys.dtype not in (_i32, getattr(torch, "uint32", _i32)) or not keys.is_contiguous():
-            raise TypeError("labor_sample_layer: keys must be a contiguous cuda tensor of 32-bit words (int32 bit patterns or uint32)")
-        if keys.numel() != N:
-            raise ValueError("labor_sample_layer: keys holds one word per node")
-    if out is None:
-        out = (torch.empty(ec, dtype=_i32, device=dev), torch.empty(ec, dtype=_i32, device=dev),
-               torch.empty(ec, dtype=_i64, device=dev) if want_pos else None,
-               torch.empty(ec, dtype=_f32, device=dev) if want_weight else None, torch.empty(1, dtype=_i32, device=dev))
-    src, dst, pos, w, d_e = out
-    _chk(src, _i32, "edge_src"); _chk(dst, _i32, "edge_dst"); _chk(pos, _i64, "edge_pos", True); _chk(w, _f32, "edge_weight", True)
-    _chk(d_e, _i32, "e_count")
-    if min(src.numel(), dst.numel()) < ec or (pos is not None and pos.numel() < ec) or (w is not None and w.numel() < ec):
-        raise ValueError("labor_sample_layer: the edge buffers hold e_cap values each")
+    if keys is not None and _key_words("labor_sample_layer", keys) != N:
+        raise ValueError("labor_sample_layer: keys holds one word per node")
+    src, dst, pos, w, d_e = _edge_buffers("labor_sample_layer", ec, dev, out, pos=bool(want_pos), weight=bool(want_weight))
     ws = _ws(lib().grapes_labor_sample_layer_workspace_bytes(m, ic), dev)
     _lib.check(lib().grapes_labor_sample_layer(_p(rowptr), _p(col), N, _p(rows), m, _p(d_m), k, _p(keys),
                                                int(philox_seed) & (2 ** 64 - 1), int(philox_base) & (2 ** 64 - 1), _p(c), _p(pi), ic, ec,
@@ -3070,7 +3070,7 @@ def labor_importance(rowptr, col, num_nodes: int, rows, fanout: int, iters: int,
     pi = 1, over the listed rows with more than `fanout` entries, then c_s(pi) once more; c_s solves sum_t 1 / min(1, c pi_t) =
     d_s^2 / fanout (0 is written for a row with d_s <= fanout, whose p is 1).  pi: the table to write (only the columns the rows touch
     are written, and only they mean anything).  scratch: ops.labor_scratch(N, device) — zero on entry, zero again on return."""
-    N, m = _labor_rows("labor_importance", rowptr, col, num_nodes, rows, d_m, status)
+    N, m = _list_rows("labor_importance", rowptr, col, num_nodes, rows, d_m, status, int(num_nodes) < 1)
     _chk(scratch, _i32, "scratch"); _chk(pi, _f32, "pi", True)
     k, it = int(fanout), int(iters)
     if not 1 <= k < 2 ** 31 or not 0 <= it <= LABOR_MAX_ITERS:

@@ -7,7 +7,8 @@ Tolerances.  An importance pi_j is a sum of t_j positive fp32 terms, each with a
 <= (t_i + 8) 2^-24.  The trainer's logits and gradients are judged by the project's element-wise criterion (oracle/accuracy.py) as
 tests/test_wgcn_gpu.py judges its WGCN_UNNORMALIZED layers, the reference chained through both layers; the scalar loss — a mean of B
 row losses, each a few fp32 operations on logits that the criterion holds to fp32 accuracy — by
-|d| <= (B + 8) 2^-24 (mean |row loss| + max |logit magnitude|).  Every graph has at most 4 096 nodes."""
+|d| <= (B + 8) 2^-24 (mean |row loss| + max |logit magnitude|).  Every graph has at most 4 096 nodes, but the one of the row list
+past one scan tile (5 000)."""
 import numpy as np
 import pytest
 import torch
@@ -97,6 +98,8 @@ def _cases():
     out["e_directed"] = _Case(ip, ix, 80, rng.permutation(80)[:20], symmetric=False)
     ip, ix = LO.random_symmetric(300, 8, 15)
     out["g_prev1"] = _Case(ip, ix, 300, [int(np.argmax(np.diff(ip)))])
+    ip, ix = LO.random_symmetric(5000, 6, 16)                            # 4 500 rows: past one tile (4 096) of a row-list prefix
+    out["h_two_tiles"] = _Case(ip, ix, 5000, np.random.default_rng(3).permutation(5000)[:4500])
     return out
 
 
@@ -230,7 +233,7 @@ def _check_layer(got, c, rows, after, table, what):
     return e
 
 
-@pytest.mark.parametrize("name", PREV_CASES)
+@pytest.mark.parametrize("name", PREV_CASES + ["h_two_tiles"])
 def test_layer_entries_and_weights(name):
     ops, c = _ops(), _case(name)
     cand = LO.candidates(c.indptr, c.indices, c.prev)
@@ -240,9 +243,10 @@ def test_layer_entries_and_weights(name):
     status = torch.zeros(1, dtype=torch.int32, device="cuda")
     rows = _dev(c.prev.astype(np.int32))
     need = len(LO.layer_entries(c.indptr, c.indices, c.n, c.prev, after, _np(table).astype(F64))[0])
-    got = ops.ladies_layer(c.rowptr, c.col, c.n, rows, _bitmap(after, c.n), table, need + 5, status=status)
+    e_cap = need if name == "h_two_tiles" else need + 5                  # (the two-tile case: the capacity exact)
+    got = ops.ladies_layer(c.rowptr, c.col, c.n, rows, _bitmap(after, c.n), table, e_cap, status=status)
     assert _check_layer(got, c, c.prev, after, table, name) == need and int(status.item()) == 0
-    again = ops.ladies_layer(c.rowptr, c.col, c.n, rows, _bitmap(after, c.n), table, need + 5)
+    again = ops.ladies_layer(c.rowptr, c.col, c.n, rows, _bitmap(after, c.n), table, e_cap)
     assert all(torch.equal(a[:need], b[:need]) for a, b in zip(got[:3], again[:3]))
 
 
@@ -261,20 +265,22 @@ def test_fastgcn_layer_with_empty_rows():
 
 
 def test_layer_overflow_writes_nothing_past_e_cap():
-    ops, c = _ops(), _case("d_loops")
-    cand = LO.candidates(c.indptr, c.indices, c.prev)
-    table = _device_table(ops, c, cand)
-    rs, rd, rw, _ = LO.layer_entries(c.indptr, c.indices, c.n, c.prev, cand, _np(table).astype(F64))
-    e_cap, guard = len(rs) - 1, 64
-    bufs = (torch.full((e_cap + guard,), -7, dtype=torch.int32, device="cuda"), torch.full((e_cap + guard,), -7, dtype=torch.int32, device="cuda"),
-            torch.full((e_cap + guard,), SENTINEL, device="cuda"))
-    status = torch.zeros(1, dtype=torch.int32, device="cuda")
-    out = (bufs[0][:e_cap], bufs[1][:e_cap], bufs[2][:e_cap], torch.zeros(1, dtype=torch.int32, device="cuda"))
-    src, dst, w, d_e = ops.ladies_layer(c.rowptr, c.col, c.n, _dev(c.prev.astype(np.int32)), _bitmap(cand, c.n), table, e_cap,
-                                        status=status, out=out)
-    assert int(status.item()) & 1 and int(d_e.item()) == e_cap
-    assert bool((bufs[0][e_cap:] == -7).all()) and bool((bufs[1][e_cap:] == -7).all()) and bool((bufs[2][e_cap:] == SENTINEL).all())
-    assert np.array_equal(_np(src), rs[:e_cap]) and np.array_equal(_np(dst), rd[:e_cap])
+    ops = _ops()
+    for name in ("d_loops", "h_two_tiles"):                              # (the second: the count one above e_cap behind a tile boundary)
+        c = _case(name)
+        cand = LO.candidates(c.indptr, c.indices, c.prev)
+        table = _device_table(ops, c, cand)
+        rs, rd, rw, _ = LO.layer_entries(c.indptr, c.indices, c.n, c.prev, cand, _np(table).astype(F64))
+        e_cap, guard = len(rs) - 1, 64
+        bufs = (torch.full((e_cap + guard,), -7, dtype=torch.int32, device="cuda"),
+                torch.full((e_cap + guard,), -7, dtype=torch.int32, device="cuda"), torch.full((e_cap + guard,), SENTINEL, device="cuda"))
+        status = torch.zeros(1, dtype=torch.int32, device="cuda")
+        out = (bufs[0][:e_cap], bufs[1][:e_cap], bufs[2][:e_cap], torch.zeros(1, dtype=torch.int32, device="cuda"))
+        src, dst, w, d_e = ops.ladies_layer(c.rowptr, c.col, c.n, _dev(c.prev.astype(np.int32)), _bitmap(cand, c.n), table, e_cap,
+                                            status=status, out=out)
+        assert int(status.item()) & 1 and int(d_e.item()) == e_cap, name
+        assert bool((bufs[0][e_cap:] == -7).all()) and bool((bufs[1][e_cap:] == -7).all()) and bool((bufs[2][e_cap:] == SENTINEL).all())
+        assert np.array_equal(_np(src), rs[:e_cap]) and np.array_equal(_np(dst), rd[:e_cap]), name
 
 
 # ------------------------------------------------------------------------------------------------------------ whole sampler

@@ -4,7 +4,8 @@ the host oracle of tests/sage_oracle.py.
 Sampled sets and edge lists are bit-exact: the selection is integer arithmetic on Philox words (or given keys).  Activations and
 gradients are judged by the project's measure (gat_oracle.rel_err: max |a - ref| / max(1, max |ref|)) at its tolerances, 1e-5 and
 1e-4, against fp64; the backward of a fused ReLU is compared on the device's own gates (out > 0), so a pre-activation within fp32
-rounding of 0 cannot flip a whole gradient row.  Every graph has at most 1 200 nodes."""
+rounding of 0 cannot flip a whole gradient row.  Every graph has at most 1 200 nodes, but the one of the row list past one scan
+tile (5 000)."""
 import numpy as np
 import pytest
 import torch
@@ -156,6 +157,28 @@ def test_device_row_count_offset_advance_and_untouched_tails():
     ops.sage_sample_layer(rp, col, N_S, rows, 3, e_cap=cap, philox_seed=3, d_philox_offset=d_off, d_m=d_m, status=status, out=out)
     nxt = SO.sample_layer(ip, ix, ROWS[:5], 3, seed=3, offset=40 + SO.offset_advance(want[3]))
     _same([_np(t)[:e] for t in out[:3]], nxt, "the advanced offset")
+
+
+def test_a_row_list_past_one_scan_tile():
+    """4 500 list rows over a sparse graph of 5 000 nodes: sage_scan_k's two prefixes carry their totals from one tile of 4 096 rows
+    into the next.  The 1 000-entry hub is listed first, so every later stream position is large, and 300 rows are listed twice.  On
+    the Philox stream, then with a live count on the device below m (behind the tile boundary)."""
+    ops = _ops()
+    n, k, m = 5000, 3, 4500
+    rng = np.random.default_rng(31)
+    ip, ix = SO.degree_graph([1000] + rng.integers(0, 7, n - 1).tolist(), n, 32)
+    rows = np.concatenate([[0], rng.permutation(np.arange(1, n))[:m - 301], np.zeros(300, np.int64)])
+    rows[-300:] = rows[1:301]
+    assert len(rows) == m and (np.diff(ip)[rows[4096:]] > k).any()
+    rp, col, d_rows = _dev(ip), _dev(ix), _dev(rows.astype(np.int32))
+    status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    for live in (m, 4200):
+        want = SO.sample_layer(ip, ix, rows[:live], k, seed=21, offset=7)
+        d_m = None if live == m else torch.tensor([live], dtype=torch.int32, device="cuda")
+        src, dst, pos, d_e = ops.sage_sample_layer(rp, col, n, d_rows, k, philox_seed=21, philox_offset=7, d_m=d_m, status=status)
+        e = int(d_e.item())
+        assert e == len(want[0]) and int(status.item()) == 0
+        _same([_np(t)[:e] for t in (src, dst, pos)], want, f"4 500 rows, {live} live")
 
 
 def test_overflow_and_bad_row_id():

@@ -215,6 +215,51 @@ def test_subgraph_ids():
     assert torch.equal(bufs[5][:small], b[5][:small])
 
 
+def test_subgraph_of_a_node_set_past_one_scan_tile():
+    """4 500 of 5 000 nodes (more than one tile of 4 096 of a row-list prefix, below SAINT_MAX_IDS) in a buffer of 4 600, over a sparse
+    directed graph with one 300-entry row: edges, local row pointers and — ids=True — entry ids against the oracle; then e_cap one
+    below the count."""
+    _cuda()
+    from grapes_amd import ops
+    rng = np.random.default_rng(41)
+    n, n_set, n_cap = 5000, 4500, 4600
+    s = np.concatenate([rng.integers(0, n, 4 * n), np.full(300, 17)])
+    d = np.concatenate([rng.integers(0, n, 4 * n), rng.choice(n, 300, replace=False)])
+    order = np.lexsort((d, s))
+    s, d = s[order], d[order]
+    indptr = np.concatenate([[0], np.cumsum(np.bincount(s, minlength=n))]).astype(np.int64)
+    ns = np.sort(np.concatenate([[17], rng.permutation(np.setdiff1d(np.arange(n), [17]))[:n_set - 1]]))
+    node_idx = np.concatenate([ns, np.zeros(n_cap - n_set, np.int64)]).astype(np.int32)
+    node_map = rng.integers(0, n_cap, n).astype(np.int32)                # stale everywhere but at the set's nodes
+    node_map[ns] = np.arange(n_set)
+    i32 = dict(dtype=torch.int32, device="cuda")
+    rowptr, col = torch.from_numpy(indptr).cuda(), torch.from_numpy(d.astype(np.int32)).cuda()
+    d_idx, d_map, count = torch.from_numpy(node_idx).cuda(), torch.from_numpy(node_map).cuda(), torch.tensor([n_set], **i32)
+    rs, rd = O.induced_subgraph(indptr, d, ns)
+    e = len(rs)
+    want_ptr = np.concatenate([[0], np.cumsum(np.bincount(rs, minlength=n_cap))])
+    assert e > 4096 and want_ptr[4096] < e
+    status = torch.zeros(1, **i32)
+    a = ops.saint_subgraph(rowptr, col, d_idx, count, d_map, e, status=status)           # the capacity exact
+    c = ops.saint_subgraph(rowptr, col, d_idx, count, d_map, e, ids=True, status=status)
+    assert int(status.item()) == 0 and int(a[2].item()) == e and int(c[2].item()) == e
+    for got in (a, c):
+        assert np.array_equal(got[0].cpu().numpy(), rs) and np.array_equal(got[1].cpu().numpy(), rd)
+        assert np.array_equal(got[3].cpu().numpy(), want_ptr)
+    eid = c[4].cpu().numpy()
+    assert c[5] is None and np.array_equal(d[eid], ns[rd]) and np.array_equal(NO.entry_rows(indptr)[eid], ns[rs])
+    assert (np.diff(eid) > 0).all()
+    small, guard = e - 1, 64
+    bufs = (torch.full((small + guard,), -7, **i32), torch.full((small + guard,), -7, **i32), torch.zeros(1, **i32),
+            torch.zeros(n_cap + 1, **i32), torch.full((small + guard,), -7, dtype=torch.int64, device="cuda"), None)
+    ops.saint_subgraph(rowptr, col, d_idx, count, d_map, small, ids=True, status=status, out=bufs)
+    assert int(status.item()) & 1 and int(bufs[2].item()) == small
+    for k in (0, 1, 4):
+        assert torch.all(bufs[k][small:] == -7), k
+    assert torch.equal(bufs[0][:small], c[0][:small]) and torch.equal(bufs[4][:small], c[4][:small])
+    assert np.array_equal(bufs[3].cpu().numpy(), want_ptr)               # the row pointers are not clamped
+
+
 @pytest.mark.parametrize("kind", KINDS)
 def test_estimate_norm_end_to_end(kind):
     _cuda()

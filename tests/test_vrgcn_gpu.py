@@ -3,7 +3,7 @@ tests/vrgcn_oracle.py.
 
 Activations and gradients are judged by the project's measure (gat_oracle.rel_err: max |a - ref| / max(1, max |ref|)) at its
 tolerances, 1e-5 and 1e-4; the backward of a ReLU is compared on the device's own gates, so a pre-activation within fp32 rounding of
-0 cannot flip a whole gradient row.  Every graph has at most 1 100 nodes."""
+0 cannot flip a whole gradient row.  Every graph has at most 1 100 nodes, but the one of the row list past one scan tile (5 000)."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -21,6 +21,7 @@ ACT_TOL, GRAD_TOL = 1e-5, 1e-4
 F32, F64 = np.float32, np.float64
 K = 2                                                                    # the fanout of the kernel tests
 N_K = 1100
+N_BIG = 5000                                                             # the graph of the row list longer than one scan tile (4 096 rows)
 DEGREES = [0, K - 1, K, K + 1, 63, 64, 65, 129, 1000]                    # rows 0 .. 8; row 9 stores duplicate entries
 HUB, DUP = 8, 9
 
@@ -48,48 +49,48 @@ def _np(t):
 _KG = {}
 
 
-def _kernel_graph():
-    """(indptr, indices, kept): rows 0 .. 8 have DEGREES distinct columns among the nodes 16 .., row 9 stores (20, 20, 31, 40), every
-    later row 0 .. 5 random columns (so dinv varies); loop-free, not symmetric — the kernels read rows only.  kept[u] = K of row u's
-    entries (all of them for d <= K), row 9 keeps both copies of its duplicate."""
-    if not _KG:
+def _kernel_graph(n=N_K):
+    """(indptr, indices, kept) over n nodes: rows 0 .. 8 have DEGREES distinct columns among the nodes 16 .., row 9 stores
+    (20, 20, 31, 40), every later row 0 .. 5 random columns (so dinv varies); loop-free, not symmetric — the kernels read rows only.
+    kept[u] = K of row u's entries (all of them for d <= K), row 9 keeps both copies of its duplicate."""
+    if n not in _KG:
         rng = np.random.default_rng(7)
-        rows = [sorted(rng.choice(np.arange(16, N_K), d, replace=False).tolist()) for d in DEGREES] + [[20, 20, 31, 40]]
-        for u in range(10, N_K):
-            c = rng.choice(N_K, int(rng.integers(0, 6)), replace=False)
+        rows = [sorted(rng.choice(np.arange(16, n), d, replace=False).tolist()) for d in DEGREES] + [[20, 20, 31, 40]]
+        for u in range(10, n):
+            c = rng.choice(n, int(rng.integers(0, 6)), replace=False)
             rows.append(sorted(int(v) for v in c if v != u))
         ip, ix = SO.csr_from_rows(rows)
         kept = {}
-        for u in range(10):
+        for u in range(n):
             cols = np.asarray(rows[u], dtype=np.int64)
             kept[u] = cols if len(cols) <= K else cols[np.sort(rng.choice(len(cols), K, replace=False))]
         kept[DUP] = np.array([20, 20], dtype=np.int64)
-        _KG.update(ip=ip, ix=ix.astype(np.int64), kept=kept, d_rowptr=_dev(ip), d_col=_dev(ix.astype(np.int32)),
-                   d_dinv=_dev(VO.dinv(ip).astype(F32)))
-    return _KG
+        _KG[n] = dict(n=n, ip=ip, ix=ix.astype(np.int64), kept=kept, d_rowptr=_dev(ip), d_col=_dev(ix.astype(np.int32)),
+                      d_dinv=_dev(VO.dinv(ip).astype(F32)))
+    return _KG[n]
 
 
-def _batch(rows, kept, extra=(3, 500, 1099)):
+def _batch(rows, kept, n=N_K, extra=(3, 500, 1099)):
     """The batch of the listed rows: node_idx = the ascending union of the rows, their kept sources and a few bystanders; the kept
     entries as local lists in the rows' order."""
     node_idx = np.unique(np.concatenate([np.asarray(rows, dtype=np.int64)] + [np.asarray(k, dtype=np.int64) for k in kept] +
                                         [np.asarray(extra, dtype=np.int64)]))
-    loc = np.full(N_K, -1, np.int64)
+    loc = np.full(n, -1, np.int64)
     loc[node_idx] = np.arange(len(node_idx))
     src = np.concatenate([np.asarray(k, dtype=np.int64) for k in kept]) if len(kept) else np.zeros(0, np.int64)
     dst = np.concatenate([np.full(len(k), u, np.int64) for u, k in zip(rows, kept)]) if len(kept) else np.zeros(0, np.int64)
     return node_idx, loc, loc[src].astype(np.int32), loc[dst].astype(np.int32)
 
 
-def _run(ops, rows, kept, f, seed, item_cap=None, hbar_from_h=False, col=None, status=None):
+def _run(ops, rows, kept, f, seed, item_cap=None, hbar_from_h=False, col=None, status=None, n=N_K):
     """The forward and the backward of one case on the device and in the oracle."""
-    G = _kernel_graph()
+    G = _kernel_graph(n)
     rows = np.asarray(rows, dtype=np.int64)
-    node_idx, loc, ls, ld = _batch(rows, kept)
+    node_idx, loc, ls, ld = _batch(rows, kept, n)
     n_local, m = len(node_idx), len(rows)
     rng = np.random.default_rng(seed)
     H = rng.standard_normal((n_local, f)).astype(F32)
-    Hbar = rng.standard_normal((N_K, f)).astype(F32)
+    Hbar = rng.standard_normal((n, f)).astype(F32)
     if hbar_from_h:
         Hbar[node_idx] = H
     dA = rng.standard_normal((m, f)).astype(F32)
@@ -109,13 +110,13 @@ def _run(ops, rows, kept, f, seed, item_cap=None, hbar_from_h=False, col=None, s
     A, coef = fwd()
     bwd = lambda: ops.vrgcn_aggregate_bwd(_dev(dA), coef, _dev(pos), d_idx, G["d_dinv"], prep, status=st)
     dH = bwd()
-    Hg = np.zeros((N_K, f))
+    Hg = np.zeros((n, f))
     Hg[node_idx] = H
     out = dict(A=_np(A), dH=_np(dH), fwd=fwd, bwd=bwd, status=st, hbar_same=bool(torch.equal(d_Hbar, keep)), node_idx=node_idx,
                Hg=Hg, Hbar=Hbar.astype(F64), rows=rows)
     if col is None:
         out["A64"] = VO.aggregate(G["ip"], G["ix"], rows, kept, Hg, Hbar)
-        out["dH64"] = VO.aggregate_grad(G["ip"], rows, kept, dA, N_K)[node_idx]
+        out["dH64"] = VO.aggregate_grad(G["ip"], rows, kept, dA, n)[node_idx]
     return out
 
 
@@ -170,6 +171,23 @@ def test_every_row_by_one_group_is_the_same_sum_up_to_rounding():
     T = ops.VRGCN_LONG_ROW
     assert need == sum(-(-d // T) for d in np.diff(G["ip"])[ALL_ROWS] if d > T)
     _check(_run(ops, ALL_ROWS, kept, 64, seed=5, item_cap=need + 5), "a capacity above the rows' chunks")
+
+
+def test_a_row_list_past_one_scan_tile():
+    """4 303 distinct listed rows, more than one tile (4 096) of a one-workgroup row-list prefix and five rows to a thread of
+    vrgcn_items_k.  The 1 000-entry row is listed first, the rows of 129 and 65 entries behind position 4 096.  item_cap exact, then one too few (the
+    overflow bit; the result is then invalid and is not looked at)."""
+    ops = _ops()
+    G = _kernel_graph(N_BIG)
+    rows = [HUB] + list(range(10, 4310)) + [7, 6]
+    deg, T = np.diff(G["ip"])[rows], ops.VRGCN_LONG_ROW
+    assert len(rows) > 4096 + 2 and deg[0] > T and (deg[-2:] > T).all() and not (deg[1:-2] > T).any()
+    need = ops.vrgcn_item_cap(G["d_rowptr"], _dev(np.asarray(rows, dtype=np.int32)))
+    assert need == sum(-(-d // T) for d in deg if d > T)
+    kept = [G["kept"][u] for u in rows]
+    _check(_run(ops, rows, kept, 32, seed=12, item_cap=need, n=N_BIG), "4 303 rows, item_cap exact")
+    r = _run(ops, rows, kept, 32, seed=12, item_cap=need - 1, n=N_BIG)
+    assert int(r["status"].item()) == 1                                  # GRAPES_STATUS_EDGE_OVERFLOW
 
 
 def test_two_calls_are_bit_equal():
