@@ -108,6 +108,11 @@ SIGNATURES = {
     "grapes_labor_sample_layer": (I32, [P, P, I32, P, I32, P, I32, P, U64, U64, P, P, I32, I32, P, P, P, P, P, P, P, P]),
     "grapes_labor_importance_workspace_bytes": (SZ, [I32]),
     "grapes_labor_importance": (I32, [P, P, I32, P, I32, P, I32, I32, P, P, P, P, P]),
+    # ShaDow-GNN: the per-root ego-net sampler and the segment mean of its readout
+    "grapes_shadow_sample_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_shadow_sample": (I32, [P, P, I32, P, I32, P, I32, I32, P, U64, U64, P, I32, I32, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "grapes_segment_mean_fwd": (I32, [P, P, I32, I32, I32, P, P, P]),
+    "grapes_segment_mean_bwd": (I32, [P, P, I32, I32, I32, P, P, P]),
     # GATConv aggregation (modules/gcn.py:45-72)
     "grapes_gat_scores": (I32, [P, P, P, P, P, I32, P, I32, P]),
     "grapes_gat_aggregate_workspace_bytes": (SZ, [I32, I32]),

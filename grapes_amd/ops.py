@@ -3086,6 +3086,116 @@ def labor_importance(rowptr, col, num_nodes: int, rows, fanout: int, iters: int,
     return c, pi
 
 
+# ------------------------------------------------------------------------------- ShaDow-GNN: the per-root ego-net sampler
+# [Zeng et al., NeurIPS 2021; PyG-recall: ShaDowKHopSampler] (grapes_hip.h, csrc/shadow_kernels.hip)
+SHADOW_MAX_NODES = 1024      # the ego-net cap: 1 + k + ... + k^depth nodes of one root sit in one workgroup's LDS
+SHADOW_MAX_ROOTS = 4096
+SHADOW_MAX_FANOUT = 64
+SEGMENT_MEAN_MAX_WIDTH = 1024
+
+
+def shadow_cap(depth: int, fanout: int) -> int:
+    """C = 1 + k + k^2 + ... + k^depth, the most nodes one ego-net can hold.  ValueError unless depth >= 1, 1 <= k <=
+    SHADOW_MAX_FANOUT (-1, every neighbour, is refused: the ego-net would be unbounded) and C <= SHADOW_MAX_NODES."""
+    depth, k = int(depth), int(fanout)
+    if depth < 1:
+        raise ValueError(f"shadow_sample: depth = {depth} is not built (depth >= 1)")
+    if not 1 <= k <= SHADOW_MAX_FANOUT:
+        raise ValueError(f"shadow_sample: num_neighbors = {k} is not built (1 .. {SHADOW_MAX_FANOUT}; -1, every neighbour, would leave "
+                         "the ego-net unbounded)")
+    C = 1
+    for h in range(1, depth + 1):
+        C += k ** h
+        if C > SHADOW_MAX_NODES:
+            raise ValueError(f"shadow_sample: depth {depth} with num_neighbors {k} exceeds the ego-net cap: 1 + k + ... + k^depth "
+                             f"must be at most {SHADOW_MAX_NODES}")
+    return C
+
+
+def shadow_sample(rowptr, col, num_nodes: int, roots, depth: int, fanout: int, n_cap: Optional[int] = None, e_cap: Optional[int] = None,
+                  words=None, philox_seed: int = 0, philox_offset: int = 0, d_philox_offset=None, d_m=None, want_e_id: bool = True,
+                  status=None, out=None):
+    """(n_id int32 [n_cap], ptr int32 [B + 1], batch int32 [n_cap], root_n_id int32 [B], edge_index int32 [2, e_cap], e_id int64 [e_cap] or
+    None, n_count int32 [1], e_count int32 [1]) of grapes_shadow_sample: one sampled ego-net per root — depth hops, at most fanout
+    entries per expanded row chosen by Floyd's algorithm on Philox words, then the subgraph induced on the reached set — concatenated
+    in root order; the rule is in grapes_hip.h.  edge_index[0] holds the sources (the neighbours), edge_index[1] the targets (the
+    rows), batch-local ids.  n_cap defaults to B * C, which cannot overflow; e_cap is required (an ego-net's induced entries are not
+    bounded by its nodes where the graph stores duplicates).  words: int32 (or uint32) bit patterns [B, depth, fanout] replacing the
+    Philox words (tests).  d_philox_offset: int64 [1] device stream offset, used instead of philox_offset and advanced by B * depth.
+    out: the eight tensors to write (e_id may be None)."""
+    _chk(d_philox_offset, _i64, "d_philox_offset", True)
+    C = shadow_cap(depth, fanout)
+    N, B = _list_rows("shadow_sample", rowptr, col, num_nodes, roots, d_m, status, int(num_nodes) < 1 or e_cap is None,
+                      "rowptr holds N + 1 values, roots is not empty and e_cap is given")
+    if B > SHADOW_MAX_ROOTS:
+        raise ValueError(f"shadow_sample: at most {SHADOW_MAX_ROOTS} roots per call")
+    if col.numel() >= 2 ** 31:
+        raise ValueError("shadow_sample: a graph with 2^31 or more entries is not built")
+    nc, ec, dev = B * C if n_cap is None else int(n_cap), int(e_cap), roots.device
+    if nc < 1 or ec < 1:
+        raise ValueError("shadow_sample: n_cap and e_cap are at least 1")
+    if words is not None and _key_words("shadow_sample", words) != B * int(depth) * int(fanout):
+        raise ValueError("shadow_sample: words holds one word per (root, hop, step): [B, depth, fanout]")
+    if out is None:
+        out = (torch.empty(nc, dtype=_i32, device=dev), torch.empty(B + 1, dtype=_i32, device=dev), torch.empty(nc, dtype=_i32, device=dev),
+               torch.empty(B, dtype=_i32, device=dev), torch.empty((2, ec), dtype=_i32, device=dev),
+               torch.empty(ec, dtype=_i64, device=dev) if want_e_id else None, torch.empty(1, dtype=_i32, device=dev),
+               torch.empty(1, dtype=_i32, device=dev))
+    n_id, ptr, batch, root_n_id, ei, e_id, d_n, d_e = out
+    for t, name in ((n_id, "n_id"), (ptr, "ptr"), (batch, "batch"), (root_n_id, "root_n_id"), (ei, "edge_index"), (d_n, "n_count"),
+                    (d_e, "e_count")):
+        _chk(t, _i32, name)
+    _chk(e_id, _i64, "e_id", True)
+    if (n_id.numel() < nc or batch.numel() < nc or ptr.numel() < B + 1 or root_n_id.numel() < B or ei.dim() != 2 or ei.shape[0] != 2 or
+            ei.shape[1] < ec or (e_id is not None and e_id.numel() < ec)):
+        raise ValueError("shadow_sample: n_id and batch hold n_cap values, ptr B + 1, root_n_id B, edge_index [2, e_cap], e_id e_cap")
+    ws = _ws(lib().grapes_shadow_sample_workspace_bytes(B, int(depth), int(fanout)), dev)
+    if col.numel() == 0:
+        col = ws                                                     # (a graph without an entry: any address, never read)
+    _lib.check(lib().grapes_shadow_sample(_p(rowptr), _p(col), N, _p(roots), B, _p(d_m), int(depth), int(fanout), _p(words),
+                                          int(philox_seed) & (2 ** 64 - 1), int(philox_offset) & (2 ** 64 - 1), _p(d_philox_offset),
+                                          nc, ec, _p(n_id), _p(ptr), _p(batch), _p(root_n_id), ei[0].data_ptr(), ei[1].data_ptr(),
+                                          _p(e_id), _p(d_n), _p(d_e), _p(ws), _p(status), _stream()), "shadow_sample")
+    return n_id, ptr, batch, root_n_id, ei, e_id, d_n, d_e
+
+
+def _segments(who, x, ptr, status):
+    """The checks of the two segment-mean calls -> (num_segments, n_rows, f)."""
+    _chk(x, _f32, who + ": the matrix"); _chk(ptr, _i32, "ptr"); _chk(status, _i32, "status", True)
+    if x.dim() != 2 or ptr.dim() != 1 or ptr.numel() < 2 or not 1 <= x.shape[1] <= SEGMENT_MEAN_MAX_WIDTH:
+        raise ValueError(f"{who}: a matrix of 1 .. {SEGMENT_MEAN_MAX_WIDTH} columns and ptr with one more entry than there are segments")
+    return ptr.numel() - 1, int(x.shape[0]), int(x.shape[1])
+
+
+def segment_mean_fwd(h, ptr, status=None, out=None):
+    """out fp32 [B, f]: out[b] = the mean of the rows h[ptr[b] : ptr[b + 1]] (0 for an empty segment), ptr int32 [B + 1] ascending
+    inside [0, h's rows]; f <= 1024.  The rows are added in row order and divided once: a fixed order, no atomics."""
+    B, _, f = _segments("segment_mean_fwd", h, ptr, status)
+    if out is None:
+        out = torch.empty((B, f), dtype=_f32, device=h.device)
+    _chk(out, _f32, "out")
+    if tuple(out.shape) != (B, f):
+        raise ValueError("segment_mean_fwd: out is [B, f]")
+    _lib.check(lib().grapes_segment_mean_fwd(_p(h), _p(ptr), B, int(h.shape[0]), f, _p(out), _p(status), _stream()), "segment_mean_fwd")
+    return out
+
+
+def segment_mean_bwd(g, ptr, n_rows: int, status=None, out=None):
+    """dh fp32 [n_rows, f] of segment_mean_fwd from g = d out [B, f]: dh[r] = g[b] / n_b for the rows of segment b, 0 for a row of no
+    segment."""
+    _chk(g, _f32, "g"); _chk(ptr, _i32, "ptr"); _chk(status, _i32, "status", True)
+    if g.dim() != 2 or ptr.dim() != 1 or ptr.numel() != g.shape[0] + 1 or not 1 <= g.shape[1] <= SEGMENT_MEAN_MAX_WIDTH or int(n_rows) < 0:
+        raise ValueError(f"segment_mean_bwd: g is [B, f] with f in 1 .. {SEGMENT_MEAN_MAX_WIDTH}, ptr holds B + 1 entries")
+    B, f = g.shape
+    if out is None:
+        out = torch.empty((int(n_rows), f), dtype=_f32, device=g.device)
+    _chk(out, _f32, "dh")
+    if tuple(out.shape) != (int(n_rows), f):
+        raise ValueError("segment_mean_bwd: dh is [n_rows, f]")
+    _lib.check(lib().grapes_segment_mean_bwd(_p(g), _p(ptr), B, int(n_rows), f, _p(out), _p(status), _stream()), "segment_mean_bwd")
+    return out
+
+
 def classifier_loss(logits, local_rows, target_ids, labels, out_grad=None):
     """(loss_c [1], d loss_c / d logits [n_rows, C]) — main.py:260,267.  labels: int64 [N] or fp32 [N, C]."""
     _chk(logits, _f32, "logits"); _chk(local_rows, _i32, "local_rows"); _chk(target_ids, _i32, "target_ids")

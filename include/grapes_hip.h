@@ -66,7 +66,7 @@ extern "C" {
  * grapes_asgcn_variance, grapes_asgcn_logq_bwd; GraphSAGE — grapes_sage_sample_layer(_workspace_bytes),
  * grapes_sage_aggregate_fwd / _bwd, grapes_sage_aggregate_workspace_bytes; VR-GCN — grapes_vrgcn_aggregate_fwd / _bwd,
  * grapes_vrgcn_aggregate_workspace_bytes, grapes_vrgcn_long_row; LABOR — grapes_labor_sample_layer(_workspace_bytes),
- * grapes_labor_importance(_workspace_bytes). */
+ * grapes_labor_importance(_workspace_bytes); ShaDow-GNN — grapes_shadow_sample(_workspace_bytes), grapes_segment_mean_fwd / _bwd. */
 #define GRAPES_ABI_VERSION 303
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1624,6 +1624,50 @@ int grapes_labor_sample_layer(const int64_t* rowptr, const int32_t* col, int32_t
  * above (dropped, GRAPES_STATUS_BAD_INDEX). */
 size_t grapes_labor_importance_workspace_bytes(int32_t num_nodes);
 int grapes_labor_importance(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* rows, int32_t m, const int32_t* d_m, int32_t fanout, int32_t iters, float* c, float* pi, void* workspace, int32_t* status, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ ShaDow-GNN: the per-root ego-net sampler (csrc/shadow_kernels.hip)
+ * [Zeng et al., NeurIPS 2021; PyG-recall: ShaDowKHopSampler(data, depth, num_neighbors) over torch_sparse's ego_k_hop_sample_adj].
+ * Every root gets its OWN sampled ego-net; the batch is the disjoint union of the ego-nets, in root order.  The rule (integers only,
+ * bit-reproducible on a CPU):
+ *   inputs   the CSR (rowptr int64[N + 1], col int32, fewer than 2^31 entries); roots[b], b < m (*d_m), 1 <= m <= 4096; depth >= 1;
+ *            fanout k, 1 <= k <= 64, one value for every hop; C = 1 + k + k^2 + ... + k^depth <= 1024, the ego-net cap (more:
+ *            GRAPES_EINVAL).
+ *   hops     S_0 = F_0 = {root}.  Hop h = 1 .. depth expands every v in F_{h-1}, the nodes first reached at hop h - 1: deg(v) <= k
+ *            keeps every entry of v's row; deg(v) > k keeps the entries at the positions Cset chosen by Floyd's algorithm below;
+ *            S_h = S_{h-1} united with {col[rowptr[v] + t] : t in Cset} over the expanded v;  F_h = S_h \ S_{h-1}.
+ *   Floyd    for a row v with d = deg(v) > k: for s = 0 .. k - 1, j = d - k + s, t = ((uint64) w_s * (j + 1)) >> 32 — a 64-bit product
+ *            of the 32-bit word w_s, so 0 <= t <= j; t joins Cset when it is absent, else j does (j is always absent).  k steps
+ *            whatever the degree; every k-subset of the positions is equally likely [Floyd-recall: Bentley and Floyd, CACM 1987].
+ *   words    w_s = word s & 3 of Philox4x32-10 under key philox_seed at the 128-bit counter whose low 64 bits are
+ *            ((uint64) v << 4) | (s >> 2) and whose high 64 bits are off + b * depth + (h - 1); off = *d_philox_offset when given, else
+ *            philox_offset.  The call advances *d_philox_offset by (*d_m) * depth.  A draw depends on (b, h, v) alone, so the result
+ *            is a set that no scheduling order can change.
+ *   hook     (the argument `words`, uint32[m][depth][k], optional, for tests): words[b][h - 1][s] replaces w_s for every row that root b
+ *            expands at hop h; all zeros force the collision branch at every step and keep the positions {0, d - k + 1, ..., d - 1}.
+ *   edges    the ego-net of b is the subgraph induced on S_depth: every stored entry (u, c) with both ends in the set is kept;
+ *            stored self-loops and duplicate entries stay (as grapes_saint_subgraph keeps them).
+ * Outputs, the ego-nets concatenated in root order: n_id int32[n_total] the global ids, ascending within an ego-net; ptr int32[m + 1];
+ * batch int32[n_total] the ego-net of each row; root_n_id int32[m] the batch-local row of each root; edge_src / edge_dst
+ * int32[e_total] batch-local ids, source = the neighbour and target = the row, ordered by ego-net, then local row ascending, then the
+ * CSR's order within the row; e_id int64[e_total] (optional) each entry's position in col; *d_n = n_total, *d_e = e_total.
+ * More than n_cap nodes raise GRAPES_STATUS_NODE_OVERFLOW, more than e_cap entries GRAPES_STATUS_EDGE_OVERFLOW: the counts (and ptr)
+ * are clamped and nothing is written at or past a capacity.  A root outside [0, N) raises GRAPES_STATUS_BAD_INDEX and becomes an empty
+ * ego-net (ptr[b + 1] = ptr[b], root_n_id[b] = -1), as does a root at or past *d_m (without the bit); a column outside [0, N) raises
+ * it too and its entry is dropped.  A root listed twice gets two ego-nets with independent draws (its b differs).
+ * Three launches: a workgroup per root builds the sorted set in LDS and counts the induced entries per member (a wavefront strides over
+ * a member's row, the whole workgroup over a row of more than 256 entries); one workgroup turns the counts into ptr and the edge
+ * offsets; a workgroup per root writes.  No float, no global atomic beyond the status OR: two runs give the same bits.
+ * workspace: grapes_shadow_sample_workspace_bytes(m, depth, fanout) bytes (0 for arguments outside the rule), 4-byte aligned. */
+size_t grapes_shadow_sample_workspace_bytes(int32_t m, int32_t depth, int32_t fanout);
+int grapes_shadow_sample(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* roots, int32_t m, const int32_t* d_m, int32_t depth, int32_t fanout, const uint32_t* words, uint64_t philox_seed, uint64_t philox_offset, uint64_t* d_philox_offset, int32_t n_cap, int32_t e_cap, int32_t* n_id, int32_t* ptr, int32_t* batch, int32_t* root_n_id, int32_t* edge_src, int32_t* edge_dst, int64_t* e_id, int32_t* d_n, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream);
+/* The mean over contiguous row segments, ShaDow's pooled readout: out[b, :f] = the mean of h[ptr[b] .. ptr[b + 1], :f] for b <
+ * num_segments, 0 for an empty segment; h is [n_rows, f] row-major, 1 <= f <= 1024.  A thread owns a column and adds the segment's
+ * rows in row order, then divides once: n_b - 1 additions and one division in a fixed order, no atomics.  The backward writes
+ * dh[r, :f] = g[b, :f] / n_b for every row r of segment b — one division, so it is exact up to that rounding — and 0 for the rows in
+ * front of the first segment and behind the last.  A segment that is not a run inside [0, n_rows] raises GRAPES_STATUS_BAD_INDEX and
+ * counts as empty.  One launch each. */
+int grapes_segment_mean_fwd(const float* h, const int32_t* ptr, int32_t num_segments, int32_t n_rows, int32_t f, float* out, int32_t* status, grapes_stream_t stream);
+int grapes_segment_mean_bwd(const float* g, const int32_t* ptr, int32_t num_segments, int32_t n_rows, int32_t f, float* dh, int32_t* status, grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:
