@@ -113,6 +113,12 @@ SIGNATURES = {
     "grapes_shadow_sample": (I32, [P, P, I32, P, I32, P, I32, I32, P, U64, U64, P, I32, I32, P, P, P, P, P, P, P, P, P, P, P, P]),
     "grapes_segment_mean_fwd": (I32, [P, P, I32, I32, I32, P, P, P]),
     "grapes_segment_mean_bwd": (I32, [P, P, I32, I32, I32, P, P, P]),
+    # Cluster-GCN: the cluster-union batch and ClusterGCNConv's propagation
+    "grapes_cluster_batch_workspace_bytes": (SZ, [I32, I32]),
+    "grapes_cluster_batch": (I32, [P, P, I32, P, P, P, I32, P, I32, P, I32, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P]),
+    "grapes_cluster_aggregate_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_cluster_aggregate_fwd": (I32, [P, I64, P, I64, P, P, P, F32, I32, P, I64, P, I64, I32, P, I32, P, P, I32, P, P, P]),
+    "grapes_cluster_aggregate_bwd": (I32, [P, I64, P, I64, P, P, P, F32, P, I64, P, I64, P, I64, P, I32, P, I32, P, P, I32, P, P, P]),
     # GATConv aggregation (modules/gcn.py:45-72)
     "grapes_gat_scores": (I32, [P, P, P, P, P, I32, P, I32, P]),
     "grapes_gat_aggregate_workspace_bytes": (SZ, [I32, I32]),

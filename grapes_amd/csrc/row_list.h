@@ -11,7 +11,8 @@
 //
 // Which scan when: list_scan_tiles wherever ONE workgroup of LIST_SCAN_THREADS turns a list's counts into offsets and the counts sit
 // behind loads (a table, or rows -> rowptr): a thread's LIST_SCAN_PER values are requested together, so a tile costs one memory
-// round trip per level of indirection: measured on layers of thousands of rows (sage_scan_k, labor_items_k, labor_scan_k).  A list
+// round trip per level of indirection: measured on layers of thousands of rows (sage_scan_k, labor_items_k, labor_scan_k; the three
+// one-workgroup kernels of cluster_kernels.hip follow them).  A list
 // of a few hundred values whose counts another kernel left in one table gains nothing from the tiles and measured 1 - 2 % slower on
 // them: ladies_scan_k, saint_edge_scan_k and vrgcn_items_k keep a thread walking its own span, on block_excl_scan(_u64), and share
 // list_scan_finish alone (profiles/row_list_ab.json).

@@ -29,18 +29,18 @@
 //   aggregates to 0.  src, add, out (and copy: copy[i] = src[i], the root operand of the aggregate-first form) have their own
 //   leading dimensions, so halves of one GEMM output are used in place.
 //   row_sum_rows_k / row_sum_chunks_k / row_sum_combine_k   the shared kernels; SageEpi below is their epilogue
-//   sage_gate_k / sage_colsum_k    backward: g = dout gated by relu_out > 0, dadd = g, gs = s g, and the column sums of g as
+//   row_gate_k / row_colsum_k      backward (row_gate.h): g = dout gated by relu_out > 0, dadd = g, gs = s g, and the column sums of g as
 //                                  per-slab partials added in a fixed order
 // The backward propagation is the SAME gather over the by-source CSR on the pre-scaled rows gs.  No float atomics: every sum has a
 // fixed order (entry order inside a row, chunk order across work items, slab order for the bias), two runs are bit-identical.
 // No kernel waits on another workgroup.
 #include "row_sum.h"
+#include "row_gate.h"
 #include "philox.h"
 #include "row_list.h"
 
 #define SAGE_MAX_FANOUT 64
 #define SAGE_CAND 128                 // candidates a long row finishes in registers with (two per lane; half the histogram's LDS each for words and positions)
-#define SAGE_SLAB 128                 // rows per column-sum partial
 
 // ------------------------------------------------------------------------------------------------------------ the sampler
 
@@ -357,61 +357,25 @@ struct SageEpi {
     }
 };
 
-// Backward, row-local: g = dout gated by relu_out > 0;  dadd = g;  gs = s g (rows F floats apart);  part[slab] = the column sums of g
-// over the slab's SAGE_SLAB rows: thread (rg, column) adds the rows rg, rg + 4, ... of the slab, the four sums meet in rg order.
-// gs, dadd and part are optional.  Workgroup (x, y): 64 columns at 64 x, the slabs y, y + gridDim.y, ...
-__global__ __launch_bounds__(256) void sage_gate_k(const float* __restrict__ dout, long long ld_dout, const float* __restrict__ relu_out,
-                                                   long long ld_relu, const int32_t* __restrict__ loops,
-                                                   const int32_t* __restrict__ rowptr_t, int mean, float* __restrict__ gs,
-                                                   float* __restrict__ dadd, long long ld_dadd, float* __restrict__ part, int n_host,
-                                                   const int32_t* d_n, int F) {
-    __shared__ float red[4][64];
-    const int n = eff_count(d_n, n_host);
-    const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6, f = blockIdx.x * 64 + cl;
-    const int slabs = (n_host + SAGE_SLAB - 1) / SAGE_SLAB;
-    for (int slab = blockIdx.y; slab < slabs; slab += gridDim.y) {
-        const int r0 = slab * SAGE_SLAB, r1 = min(r0 + SAGE_SLAB, n);
-        float acc = 0.f;
-        for (int row = r0 + rg; row < r1; row += 4) {
-            float sc = 1.f;
-            if (mean) sc = sage_scale(1, (rowptr_t[row + 1] - rowptr_t[row]) + (loops ? loops[row] : 0));
-            if (f < F) {
-                float g = dout[(long long)row * ld_dout + f];
-                if (relu_out && !(relu_out[(long long)row * ld_relu + f] > 0.f)) g = 0.f;
-                if (dadd) dadd[(long long)row * ld_dadd + f] = g;
-                if (gs) gs[(long long)row * F + f] = sc * g;
-                acc += g;
-            }
-        }
-        if (part) {                                                           // (workgroup-uniform)
-            red[rg][cl] = acc;
-            __syncthreads();
-            if (rg == 0 && f < F) part[(long long)slab * F + f] = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
-            __syncthreads();
-        }
+// Backward, row-local (row_gate.h): g = dout gated by relu_out > 0;  dadd = g;  gs = s g;  the column sums of g.  s of a row:
+struct SageScale {
+    const int32_t* loops; const int32_t* rowptr_t; int mean;
+    __device__ __forceinline__ float operator()(int row) const {
+        float sc = 1.f;
+        if (mean) sc = sage_scale(1, (rowptr_t[row + 1] - rowptr_t[row]) + (loops ? loops[row] : 0));
+        return sc;
     }
-}
-// one wavefront per column: lane l adds the partials l, l + 64, ... in that order, then a butterfly over the lanes
-__global__ __launch_bounds__(256) void sage_colsum_k(const float* __restrict__ part, int slabs, int F, float* __restrict__ dbias) {
-    const int f = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
-    if (f >= F) return;
-    float a = 0.f;
-    for (int b = l; b < slabs; b += 64) a += part[(long long)b * F + f];
-    a = wave_sum(a);
-    if (l == 0) dbias[f] = a;
-}
+};
 
 // ------------------------------------------------------------------------------------------------------------ host side
 
 static inline bool sage_vec_ok(const void* p, int64_t ld) { return !p || (grapes_aligned16(p) && ld % 4 == 0); }
 
-static inline size_t sage_slabs(int32_t n) { return n > 0 ? ((size_t)n + SAGE_SLAB - 1) / SAGE_SLAB : 0; }
-
 // workspace: [pacc item_cap f] [gs n f] [part slabs f]
 extern "C" size_t grapes_sage_aggregate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f) {
     const size_t N = n > 0 ? (size_t)n : 0, I = item_cap > 0 ? (size_t)item_cap : 0, F = f > 0 ? (size_t)f : 1;
     return grapes_round16(I * F * sizeof(float)) + grapes_round16(N * F * sizeof(float)) +
-           grapes_round16(sage_slabs(n) * F * sizeof(float)) + 16;
+           grapes_round16(row_gate_slabs(n) * F * sizeof(float)) + 16;
 }
 
 extern "C" int grapes_sage_aggregate_fwd(const float* src, int64_t ld_src, const float* add, int64_t ld_add, const float* bias,
@@ -458,16 +422,10 @@ extern "C" int grapes_sage_aggregate_bwd(const float* dout, int64_t ld_dout, con
     float* gs = workspace ? (float*)((char*)workspace + grapes_round16(I * f * sizeof(float))) : nullptr;
     float* part = workspace ? (float*)((char*)gs + grapes_round16((size_t)n * f * sizeof(float))) : nullptr;
     if (pass) {
-        const int slabs = (int)sage_slabs(n);
-        const dim3 grid(grapes_div_up(f, 64), slabs < 4096 ? slabs : 4096);
-        hipLaunchKernelGGL(sage_gate_k, grid, dim3(256), 0, s, dout, (long long)ld_dout, relu_out, (long long)ld_relu, loops, rowptr_t,
-                           mean ? 1 : 0, dsrc ? gs : (float*)nullptr, dadd, (long long)ld_dadd, dbias ? part : (float*)nullptr, n, d_n,
-                           f);
-        GRAPES_LAUNCH_CHECK();
-        if (dbias) {
-            hipLaunchKernelGGL(sage_colsum_k, dim3(grapes_div_up(f, 4)), dim3(256), 0, s, (const float*)part, slabs, f, dbias);
-            GRAPES_LAUNCH_CHECK();
-        }
+        const SageScale scale{loops, rowptr_t, mean ? 1 : 0};
+        const int rc = row_gate_launch(dout, (long long)ld_dout, relu_out, (long long)ld_relu, scale, dsrc ? gs : (float*)nullptr, dadd,
+                                       (long long)ld_dadd, part, dbias, n, d_n, f, s);
+        if (rc) return rc;
     }
     if (!dsrc) return 0;
     SageEpi epi;

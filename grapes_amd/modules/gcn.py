@@ -1111,6 +1111,126 @@ class SAGE(nn.Module):
         return self.convs[n_conv - 1](x, edges)
 
 
+# ------------------------------------------------------------------------------------------------ Cluster-GCN (PyG ClusterGCNConv)
+class _ClusterGCNConvFn(torch.autograd.Function):
+    """out = act(W_out (A^ x)_i + b + W_root x_i), (A^ x)_i = s_i (sum_{j -> i} x_j + (1 + lambda) x_i), s_i = 1 / (1 + deg_i) over the
+    loop-free adjacency — linear in x, so either operand form computes it, as _SAGEConvFn:
+      transform-first   H = x [W_out ; W_root]ᵀ in ONE GEMM ([n, 2 out]), then grapes_cluster_aggregate_fwd propagates the left half
+                        with the right half, the bias and the ReLU in its epilogue; backward: the gated propagation of dout over the
+                        by-source CSR into the left half of dH with g in its right half, then dW = dHᵀ x and dx = dH W.
+      aggregate-first   Z = [A^ x | x] from one propagation of x itself ([n, 2 in]), then ONE GEMM act(Z [W_out | W_root]ᵀ + b);
+                        backward: dW and db from one gated GEMM, dZ = g W, dx = the propagation of dZ's left half plus its right half.
+    Saved: x or Z, the stacked weight and, with ReLU, the output; nothing of size e."""
+
+    @staticmethod
+    def forward(ctx, x, w_out, w_root, bias, prep, lam, relu, agg_first, long_rows):
+        d_n, n = prep.d_n, x.shape[0]
+        f_out, f_in = w_out.shape
+        ctx.prep, ctx.lam, ctx.relu, ctx.agg_first, ctx.long_rows, ctx.f_in, ctx.f_out = prep, lam, relu, agg_first, long_rows, f_in, f_out
+        if agg_first:
+            z = torch.empty((n, 2 * f_in), dtype=torch.float32, device=x.device)
+            ops.cluster_aggregate_fwd(x, prep, lam, out=z[:, :f_in], copy_out=z[:, f_in:], long_rows=long_rows)
+            w = torch.cat([w_out, w_root], 1)                                  # [W_out | W_root]: [out, 2 in]
+            out = ops.linear_bias_act_fwd(z, w, bias, relu, d_n=d_n)
+            ctx.save_for_backward(z, w, out if relu else None)
+            return out
+        w = torch.cat([w_out, w_root], 0)                                      # [W_out ; W_root]: [2 out, in]
+        h = ops.linear_fwd(x, w, d_n=d_n)
+        out = ops.cluster_aggregate_fwd(h[:, :f_out], prep, lam, add=h[:, f_out:], bias=bias, relu=relu, long_rows=long_rows)
+        ctx.save_for_backward(x, w, out if relu else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        a, w, out = ctx.saved_tensors
+        prep, d_n, f_in, f_out = ctx.prep, ctx.prep.d_n, ctx.f_in, ctx.f_out
+        dout = dout.contiguous()
+        want_b = ctx.needs_input_grad[3]
+        if ctx.agg_first:
+            dw, dbias = ops.linear_bwd_weight_gated(dout, a, gate=out if ctx.relu else None, d_n=d_n, want_bias=want_b)
+            dx = None
+            if ctx.needs_input_grad[0]:
+                g = ops.gcn2_mix_bwd(dout, out, True, 1.0, d_n=d_n)[0] if ctx.relu else dout
+                dz = ops.linear_bwd_input(g, w, d_n=d_n)
+                dx = ops.cluster_aggregate_bwd(dz[:, :f_in], prep, ctx.lam, add=dz[:, f_in:], long_rows=ctx.long_rows)[0]
+            return dx, dw[:, :f_in].contiguous(), dw[:, f_in:].contiguous(), dbias if want_b else None, None, None, None, None, None
+        dh = torch.empty((dout.shape[0], w.shape[0]), dtype=torch.float32, device=dout.device)
+        _, _, dbias = ops.cluster_aggregate_bwd(dout, prep, ctx.lam, relu_out=out if ctx.relu else None, dsrc=dh[:, :f_out],
+                                                dadd=dh[:, f_out:], want_bias=want_b, long_rows=ctx.long_rows)
+        dw = ops.linear_bwd_weight(dh, a, d_n=d_n)
+        dx = ops.linear_bwd_input(dh, w, d_n=d_n) if ctx.needs_input_grad[0] else None
+        return dx, dw[:f_out], dw[f_out:], dbias, None, None, None, None, None
+
+
+class ClusterGCNConv(nn.Module):
+    """PyG ClusterGCNConv(in_channels, out_channels, diag_lambda=0., add_self_loops=True, bias=True) [PyG-recall]:
+    out_i = W_out (A^ x)_i + b + W_root x_i with A^ = D⁻¹(A + I) + diag_lambda diag(D⁻¹), D the degrees of A + I; keys `lin_out.weight`,
+    `lin_out.bias`, `lin_root.weight`.  Stored self-loops are dropped before the one loop per node is added and duplicates count by
+    multiplicity (PyG's remove_self_loops, add_self_loops).  Not built: add_self_loops=False.
+
+    The operand form is chosen by width as SAGEConv's: aggregate-first when in_channels < out_channels and in_channels is a width
+    the gather is built for (any up to 256, multiples of 4 up to 1024), transform-first otherwise, which needs out_channels to be
+    such a width.  forward's private `_form` ("transform" / "aggregate") forces one; `_long_rows` is ops.cluster_aggregate_fwd's."""
+
+    def __init__(self, in_channels: int, out_channels: int, diag_lambda: float = 0., add_self_loops: bool = True, bias: bool = True):
+        super().__init__()
+        if not add_self_loops:
+            raise NotImplementedError("ClusterGCNConv: add_self_loops=False is not built (the kernels' scale is 1 / (1 + deg))")
+        if int(in_channels) < 1 or int(out_channels) < 1:
+            raise ValueError("ClusterGCNConv: in_channels and out_channels are at least 1")
+        self.in_channels, self.out_channels, self.diag_lambda = int(in_channels), int(out_channels), float(diag_lambda)
+        if not self.form_ok("transform") and not self.form_ok("aggregate"):
+            raise ValueError(f"ClusterGCNConv: {in_channels} -> {out_channels} is not built: the gather takes any width up to 256 and "
+                             "multiples of 4 up to 1024 (out_channels, or in_channels when it is the smaller)")
+        self.lin_out = _SAGELin(self.in_channels, self.out_channels, bias)
+        self.lin_root = _SAGELin(self.in_channels, self.out_channels, False)
+
+    def reset_parameters(self):
+        self.lin_out.reset_parameters()
+        self.lin_root.reset_parameters()
+
+    form_ok = SAGEConv.form_ok
+    default_form = SAGEConv.default_form
+
+    def forward(self, x, edge_index, relu: bool = False, _form: Optional[str] = None, _long_rows: Optional[bool] = None):
+        x = _cuda_f32(x, "ClusterGCNConv")
+        if x.dim() != 2 or x.shape[1] != self.in_channels:
+            raise ValueError(f"ClusterGCNConv: width {tuple(x.shape)[-1]} != in_channels {self.in_channels}")
+        form = self.default_form() if _form is None else _form
+        if form not in ("transform", "aggregate") or not self.form_ok(form):
+            raise ValueError(f"ClusterGCNConv: the {form!r} form is not built for {self.in_channels} -> {self.out_channels}")
+        prep = _layer_graph(edge_index, x.shape[0], "ClusterGCN", loops=False)
+        return _ClusterGCNConvFn.apply(x, self.lin_out.weight, self.lin_root.weight, self.lin_out.bias, prep, self.diag_lambda, relu,
+                                       form == "aggregate", _long_rows)
+
+
+class ClusterGCN(nn.Module):
+    """ClusterGCN(in_features, hidden_dims, dropout=0., diag_lambda=0.) with SAGE's routing: ClusterGCNConv(dims[i], dims[i + 1])
+    layers in `convs`, ReLU (fused into the layer) and dropout between them, edge_index[-i] for hidden layer i and [0] for the last
+    when a list is given, a single tensor / DeviceGraph for every layer otherwise; logits ONLY."""
+
+    def __init__(self, in_features: int, hidden_dims: "list[int]", dropout: float = 0., diag_lambda: float = 0.):
+        super(ClusterGCN, self).__init__()
+        dims = [in_features] + list(hidden_dims)
+        self.convs = nn.ModuleList([ClusterGCNConv(dims[i], dims[i + 1], diag_lambda=diag_lambda) for i in range(len(hidden_dims))])
+        self.dropout, self.diag_lambda = dropout, float(diag_lambda)
+        self.philox_dropout = None          # as GCN: a callable n_elements -> (seed, offset)
+
+    _drop = GCN._drop
+
+    def forward(self, x: torch.Tensor, edge_index: Union[torch.Tensor, "list[torch.Tensor]"]) -> torch.Tensor:
+        if not x.is_cuda:
+            raise ops._lib.GrapesHipError("ClusterGCN input must be a cuda tensor (grapes_amd has no CPU path)")
+        layerwise_adjacency = type(edge_index) == list
+        n_conv = len(self.convs)
+        for i in range(1, n_conv):
+            edges = edge_index[-i] if layerwise_adjacency else edge_index
+            x = self.convs[i - 1](x, edges, relu=True)
+            x = self._drop(x)
+        edges = edge_index[0] if layerwise_adjacency else edge_index
+        return self.convs[n_conv - 1](x, edges)
+
+
 def classifier_layers(model) -> nn.ModuleList:
     """The conv layers of a classifier: GCN (gcn_layers), GAT or GATv2 (gat_layers), GCN2 or PNA (conv), SAGE (convs)."""
     if isinstance(model, SAGE):

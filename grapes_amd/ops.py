@@ -3196,6 +3196,118 @@ def segment_mean_bwd(g, ptr, n_rows: int, status=None, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------- Cluster-GCN: cluster-union batches, ClusterGCNConv
+# [Chiang et al., KDD 2019; PyG-recall: ClusterData, ClusterLoader, ClusterGCNConv] (grapes_hip.h, csrc/cluster_kernels.hip)
+CLUSTER_MAX_BATCH_PARTS = 1 << 20        # clusters of one batch
+CLUSTER_CHUNK = 64                       # GRAPES_LONG_ROW: the entries of one work item; a longer row is cut over several wavefronts
+CLUSTER_ITEM_CAP_MAX = 1 << 24
+CLUSTER_MAX_SERIAL = 2 ** 31 - 1
+
+
+def cluster_batch(rowptr, col, num_nodes: int, perm, partptr, where, clusters, stamp, serial: int, n_cap: int, e_cap: int,
+                  item_cap: Optional[int] = None, want_e_id: bool = True, status=None, out=None):
+    """(cptr int32 [q + 1], node_idx int32 [n_cap], rowptr_l int32 [n_cap + 1], edge_index int32 [2, e_cap], e_id int64 [e_cap] or None,
+    n_count int32 [1], e_count int32 [1]) of grapes_cluster_batch: the subgraph induced on the union of the chosen clusters, taken in
+    the given order; the rule is in grapes_hip.h.  perm int32 [N], partptr int32 [P + 1] and where int32 [N, 2] are the partition
+    tables (modules.cluster.ClusterData builds them); stamp int32 [P, 2] is the caller's membership table, zeroed once, and serial
+    (1 .. 2^31 - 1) a value no call has passed since.  edge_index[0] holds the neighbours, edge_index[1] the target rows, batch-local
+    ids; rowptr_l[i] = the edge count for every slot from n to n_cap.  item_cap: the work items (64 entries of one row) the call has
+    room for — default n_cap + nnz / 64, which cannot overflow but launches 64 threads per item of room: pass the partition's bound, as
+    ClusterLoader does.  out: the seven tensors to write (e_id may be None)."""
+    _chk(rowptr, _i64, "rowptr")
+    for t, name in ((col, "col"), (perm, "perm"), (partptr, "partptr"), (where, "where"), (clusters, "clusters"), (stamp, "stamp")):
+        _chk(t, _i32, name)
+    _chk(status, _i32, "status", True)
+    N, P, q, dev = int(num_nodes), partptr.numel() - 1, clusters.numel(), clusters.device
+    if (rowptr.numel() != N + 1 or N < 1 or P < 1 or perm.numel() != N or tuple(where.shape) != (N, 2) or tuple(stamp.shape) != (P, 2)):
+        raise ValueError("cluster_batch: rowptr holds N + 1 values, perm N, partptr P + 1, where is [N, 2] and stamp [P, 2]")
+    if not 1 <= q <= CLUSTER_MAX_BATCH_PARTS:
+        raise ValueError(f"cluster_batch: 1 .. {CLUSTER_MAX_BATCH_PARTS} clusters per batch")
+    if col.numel() >= 2 ** 31:
+        raise ValueError("cluster_batch: a graph with 2^31 or more entries is not built")
+    if not 1 <= int(serial) <= CLUSTER_MAX_SERIAL:
+        raise ValueError(f"cluster_batch: serial is 1 .. {CLUSTER_MAX_SERIAL}")
+    nc, ec = int(n_cap), int(e_cap)
+    ic = min(nc + col.numel() // CLUSTER_CHUNK + 1, CLUSTER_ITEM_CAP_MAX) if item_cap is None else int(item_cap)
+    if not 1 <= nc <= 2 ** 31 - 2 or ec < 1 or not 1 <= ic <= CLUSTER_ITEM_CAP_MAX:
+        raise ValueError(f"cluster_batch: n_cap is 1 .. 2^31 - 2, e_cap at least 1, item_cap 1 .. {CLUSTER_ITEM_CAP_MAX}")
+    if out is None:
+        out = (torch.empty(q + 1, dtype=_i32, device=dev), torch.empty(nc, dtype=_i32, device=dev),
+               torch.empty(nc + 1, dtype=_i32, device=dev), torch.empty((2, ec), dtype=_i32, device=dev),
+               torch.empty(ec, dtype=_i64, device=dev) if want_e_id else None, torch.empty(1, dtype=_i32, device=dev),
+               torch.empty(1, dtype=_i32, device=dev))
+    cptr, node_idx, rowptr_l, ei, e_id, d_n, d_e = out
+    for t, name in ((cptr, "cptr"), (node_idx, "node_idx"), (rowptr_l, "rowptr_l"), (ei, "edge_index"), (d_n, "n_count"), (d_e, "e_count")):
+        _chk(t, _i32, name)
+    _chk(e_id, _i64, "e_id", True)
+    if (cptr.numel() < q + 1 or node_idx.numel() < nc or rowptr_l.numel() < nc + 1 or ei.dim() != 2 or ei.shape[0] != 2 or
+            ei.shape[1] < ec or (e_id is not None and e_id.numel() < ec)):
+        raise ValueError("cluster_batch: cptr holds q + 1 values, node_idx n_cap, rowptr_l n_cap + 1, edge_index [2, e_cap], e_id e_cap")
+    ws = _ws(lib().grapes_cluster_batch_workspace_bytes(nc, ic), dev)
+    if col.numel() == 0:
+        col = ws                                                     # (a graph without an entry: any address, never read)
+    _lib.check(lib().grapes_cluster_batch(_p(rowptr), _p(col), N, _p(perm), _p(partptr), _p(where), P, _p(clusters), q, _p(stamp),
+                                          int(serial), nc, ic, ec, _p(cptr), _p(node_idx), _p(rowptr_l), ei[0].data_ptr(),
+                                          ei[1].data_ptr(), _p(e_id), _p(d_n), _p(d_e), _p(ws), _p(status), _stream()), "cluster_batch")
+    return cptr, node_idx, rowptr_l, ei, e_id, d_n, d_e
+
+
+def cluster_aggregate_fwd(src, prep: PreparedGraph, diag_lambda: float = 0.0, add=None, bias=None, relu: bool = False, out=None,
+                          copy_out=None, long_rows: Optional[bool] = None):
+    """out[i] = act(s_i (sum_{j -> i} src[j] + (1 + diag_lambda) src[i]) + add[i] + bias) over prep's loop-free by-target CSR,
+    s_i = 1 / (1 + deg_i): ClusterGCNConv's propagation.  src, add, out and copy_out ([n, f]) may be column blocks of wider matrices
+    (rows contiguous); copy_out[i] = src[i].  long_rows: see _long_items (tests force either form)."""
+    if not src.is_cuda:
+        raise _lib.GrapesHipError("cluster_aggregate_fwd: src must live in HBM (cuda tensor); grapes_amd has no CPU path")
+    n, f = src.shape
+    _gather_width(f, "Cluster-GCN aggregation")
+    if n != prep.n:
+        raise ValueError("src must be [n, f] over the prepared graph's nodes")
+    _chk(bias, _f32, "bias", True)
+    if bias is not None and bias.numel() != f:
+        raise ValueError("bias must hold f values")
+    if out is None:
+        out = torch.empty((n, f), dtype=_f32, device=src.device)
+    ld_src, ld_add = _strided_rows(src, "src", n, f), _strided_rows(add, "add", n, f, True)
+    ld_out, ld_copy = _strided_rows(out, "out", n, f), _strided_rows(copy_out, "copy_out", n, f, True)
+    items, n_items, cap = _long_items(prep, True, True, long_rows)
+    ws = _ws(lib().grapes_cluster_aggregate_workspace_bytes(0, cap, f), src.device) if cap else None
+    _lib.check(lib().grapes_cluster_aggregate_fwd(_p(src), ld_src, _p(add), ld_add, _p(bias), _p(prep.rowptr_t), _p(prep.csr_src),
+                                                  float(diag_lambda), 1 if relu else 0, _p(out), ld_out, _p(copy_out), ld_copy, n,
+                                                  _p(prep.d_n), f, items, n_items, cap, _p(ws), _p(prep.status), _stream()),
+               "cluster_aggregate_fwd")
+    return out
+
+
+def cluster_aggregate_bwd(dout, prep: PreparedGraph, diag_lambda: float = 0.0, relu_out=None, add=None, want_src: bool = True,
+                          want_add: bool = False, want_bias: bool = False, dsrc=None, dadd=None, long_rows: Optional[bool] = None):
+    """(dsrc, dadd, dbias) of cluster_aggregate_fwd from dout = d out: g = dout gated by relu_out > 0 (the forward's output, when the
+    ReLU was fused); dsrc[j] = sum_{i <- j} s_i g_i + (1 + diag_lambda) s_j g_j (+ add[j]) over the by-source CSR; dadd = g; dbias =
+    the column sums of g.  dsrc / dadd: tensors (column blocks allowed) to write; want_*: allocate them.  Fixed order, no atomics."""
+    if not dout.is_cuda:
+        raise _lib.GrapesHipError("cluster_aggregate_bwd: dout must live in HBM (cuda tensor); grapes_amd has no CPU path")
+    n, f = dout.shape
+    _gather_width(f, "Cluster-GCN aggregation")
+    if n != prep.n:
+        raise ValueError("dout must be [n, f] over the prepared graph's nodes")
+    dev = dout.device
+    if dsrc is None and want_src:
+        dsrc = torch.empty((n, f), dtype=_f32, device=dev)
+    if dadd is None and want_add:
+        dadd = torch.empty((n, f), dtype=_f32, device=dev)
+    dbias = torch.empty(f, dtype=_f32, device=dev) if want_bias else None
+    ld_dout, ld_relu = _strided_rows(dout, "dout", n, f), _strided_rows(relu_out, "relu_out", n, f, True)
+    ld_add, ld_dsrc = _strided_rows(add, "add", n, f, True), _strided_rows(dsrc, "dsrc", n, f, True)
+    ld_dadd = _strided_rows(dadd, "dadd", n, f, True)
+    items, n_items, cap = _long_items(prep, False, False, long_rows) if dsrc is not None else (None, None, 0)
+    ws = _ws(lib().grapes_cluster_aggregate_workspace_bytes(n, cap, f), dev)
+    _lib.check(lib().grapes_cluster_aggregate_bwd(_p(dout), ld_dout, _p(relu_out), ld_relu, _p(prep.rowptr_t), _p(prep.rowptr_s),
+                                                  _p(prep.csr_dst), float(diag_lambda), _p(add), ld_add, _p(dsrc), ld_dsrc, _p(dadd),
+                                                  ld_dadd, _p(dbias), n, _p(prep.d_n), f, items, n_items, cap, _p(ws),
+                                                  _p(prep.status), _stream()), "cluster_aggregate_bwd")
+    return dsrc, dadd, dbias
+
+
 def classifier_loss(logits, local_rows, target_ids, labels, out_grad=None):
     """(loss_c [1], d loss_c / d logits [n_rows, C]) — main.py:260,267.  labels: int64 [N] or fp32 [N, C]."""
     _chk(logits, _f32, "logits"); _chk(local_rows, _i32, "local_rows"); _chk(target_ids, _i32, "target_ids")

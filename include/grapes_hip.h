@@ -66,7 +66,8 @@ extern "C" {
  * grapes_asgcn_variance, grapes_asgcn_logq_bwd; GraphSAGE — grapes_sage_sample_layer(_workspace_bytes),
  * grapes_sage_aggregate_fwd / _bwd, grapes_sage_aggregate_workspace_bytes; VR-GCN — grapes_vrgcn_aggregate_fwd / _bwd,
  * grapes_vrgcn_aggregate_workspace_bytes, grapes_vrgcn_long_row; LABOR — grapes_labor_sample_layer(_workspace_bytes),
- * grapes_labor_importance(_workspace_bytes); ShaDow-GNN — grapes_shadow_sample(_workspace_bytes), grapes_segment_mean_fwd / _bwd. */
+ * grapes_labor_importance(_workspace_bytes); ShaDow-GNN — grapes_shadow_sample(_workspace_bytes), grapes_segment_mean_fwd / _bwd;
+ * Cluster-GCN — grapes_cluster_batch(_workspace_bytes), grapes_cluster_aggregate_fwd / _bwd, grapes_cluster_aggregate_workspace_bytes. */
 #define GRAPES_ABI_VERSION 303
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1668,6 +1669,53 @@ int grapes_shadow_sample(const int64_t* rowptr, const int32_t* col, int32_t num_
  * counts as empty.  One launch each. */
 int grapes_segment_mean_fwd(const float* h, const int32_t* ptr, int32_t num_segments, int32_t n_rows, int32_t f, float* out, int32_t* status, grapes_stream_t stream);
 int grapes_segment_mean_bwd(const float* g, const int32_t* ptr, int32_t num_segments, int32_t n_rows, int32_t f, float* dh, int32_t* status, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ Cluster-GCN: cluster-union batches (csrc/cluster_kernels.hip)
+ * [Chiang et al., KDD 2019; PyG-recall: ClusterData, ClusterLoader, ClusterGCNConv].  The graph is cut into P clusters once; a batch is
+ * the subgraph induced on the union of q chosen clusters.  The rule (integers only, bit-reproducible on a CPU):
+ *   inputs   the CSR (rowptr int64[N + 1], col int32, fewer than 2^31 entries); the partition tables, built once: perm int32[N] the node
+ *            ids in cluster order, ascending id inside a cluster; partptr int32[P + 1]; where int32[N][2] = (cluster of v, position of
+ *            v inside its cluster), 8-byte aligned so that the pair is one load; clusters int32[q], 1 <= q <= 2^20, taken IN THE GIVEN
+ *            ORDER; stamp int32[P][2], 8-byte aligned, the caller's scratch membership table, and serial >= 1; the capacities n_cap
+ *            (<= 2^31 - 2), item_cap (<= 2^24) and e_cap.
+ *   nodes    *d_n = n = the sum of the chosen clusters' sizes; cptr int32[q + 1]: the rows of chosen cluster k are cptr[k] ..
+ *            cptr[k + 1] (an empty cluster has an empty range); node_idx[cptr[k] + t] = perm[partptr[clusters[k]] + t].
+ *   edges    for local row i ascending, then the entries j of row node_idx[i] in col's stored order: an entry whose u = col[j] lies in a
+ *            chosen cluster becomes edge p: edge_src[p] = the local row of u, the neighbour (cptr[slot of where[u].cluster] +
+ *            where[u].position); edge_dst[p] = i; edge_id[p] = j (edge_id may be NULL).  Stored self-loops and duplicates stay.
+ *            *d_e = min(e, e_cap).  rowptr_l int32[n_cap + 1]: the first edge of local row i for i < n, and min(e, e_cap) for
+ *            EVERY slot n <= i <= n_cap — written by the call, so a caller may hand rowptr_l on with n_cap rows.
+ *   status   more than e_cap edges OR GRAPES_STATUS_EDGE_OVERFLOW: exactly the first e_cap edges in that order are written, nothing at
+ *            or past e_cap.  n > n_cap ORs GRAPES_STATUS_NODE_OVERFLOW; a cluster id outside [0, P) or a cluster listed twice ORs
+ *            GRAPES_STATUS_BAD_INDEX (it takes precedence over the node overflow): either way the batch is empty — *d_n = *d_e = 0,
+ *            cptr and rowptr_l all zero, no row or edge written — whichever thread wins a race.  A col entry outside [0, N) ORs
+ *            GRAPES_STATUS_BAD_INDEX and is dropped.  A row is cut into work items of 64 entries; a batch of more than item_cap items
+ *            ORs GRAPES_STATUS_EDGE_OVERFLOW and keeps the edges of the first item_cap items alone (the sum over the batch's rows of
+ *            ceil(deg / 64) never exceeds a cap taken from the partition: ClusterLoader's default).
+ *   stamps   stamp[c] = (serial, first local row of c) for every chosen c; u is a member iff stamp[where[u].cluster].serial ==
+ *            serial.  The table is NOT cleared between calls: the caller zeroes it once and passes a serial no call has used since
+ *            (1, 2, ...; zero it again before a serial would repeat).  A refused call leaves its serial in the table like any other.
+ * Six launches: one workgroup turns the q sizes into cptr, the stamps and n; a thread per row finds node_idx and the row's items; one
+ * workgroup scans the items; a wavefront per item tests its 64 entries (col -> where -> stamp: an item's lookups are in flight
+ * together, and a hub row is cut over many wavefronts); one workgroup scans the kept counts; a wavefront per item writes.  No float,
+ * no host read, no global atomic beyond the status OR and the stamps: two runs give the same bits.
+ * workspace: grapes_cluster_batch_workspace_bytes(n_cap, item_cap) bytes, 8-byte aligned. */
+size_t grapes_cluster_batch_workspace_bytes(int32_t n_cap, int32_t item_cap);
+int grapes_cluster_batch(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* perm, const int32_t* partptr, const int32_t* where, int32_t num_parts, const int32_t* clusters, int32_t q, int32_t* stamp, int32_t serial, int32_t n_cap, int32_t item_cap, int32_t e_cap, int32_t* cptr, int32_t* node_idx, int32_t* rowptr_l, int32_t* edge_src, int32_t* edge_dst, int64_t* edge_id, int32_t* d_n, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream);
+/* ClusterGCNConv's propagation [PyG-recall: torch_geometric ClusterGCNConv] over the loop-free CSRs of grapes_gcn_prepare (duplicates
+ * count by multiplicity: PyG's remove_self_loops followed by add_self_loops):
+ *   d_i = 1 + (rowptr_t[i + 1] - rowptr_t[i]),  s_i = 1 / d_i,  self_weight = 1 + diag_lambda
+ *   out[i] = act(s_i (sum_{j in row i} src[j] + self_weight src[i]) + add[i] + bias)
+ * and its backward from dout: g = dout gated by relu_out > 0; dsrc[j] = sum_{i in row j of the by-source CSR} s_i g_i + self_weight
+ * s_j g_j (+ add[j]); dadd = g; dbias = the column sums of g.  Leading dimensions, copy_out (copy_out[i] = src[i]), the long-row items,
+ * the widths (any f <= 256, multiples of 4 up to 1024 with 16-byte aligned operands), the status word and the optional arguments are
+ * those of grapes_sage_aggregate_fwd / _bwd; with diag_lambda = 0 the forward equals grapes_sage_aggregate_fwd(mean, loops = ones).
+ * Fixed summation order, no float atomics.  The backward always needs its workspace (gs = s g).
+ * workspace: grapes_cluster_aggregate_workspace_bytes(0, item_cap, f) for the forward, (n, item_cap, f) for the backward; 16-byte
+ * aligned. */
+size_t grapes_cluster_aggregate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f);
+int grapes_cluster_aggregate_fwd(const float* src, int64_t ld_src, const float* add, int64_t ld_add, const float* bias, const int32_t* rowptr_t, const int32_t* csr_src, float diag_lambda, int32_t relu, float* out, int64_t ld_out, float* copy_out, int64_t ld_copy, int32_t n, const int32_t* d_n, int32_t f, const int32_t* long_items, const int32_t* d_n_items, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
+int grapes_cluster_aggregate_bwd(const float* dout, int64_t ld_dout, const float* relu_out, int64_t ld_relu, const int32_t* rowptr_t, const int32_t* rowptr_s, const int32_t* csr_dst, float diag_lambda, const float* add, int64_t ld_add, float* dsrc, int64_t ld_dsrc, float* dadd, int64_t ld_dadd, float* dbias, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:
