@@ -735,6 +735,603 @@ def assert_aggregate_accuracy(got, ref, mag, base, lens, what: str = "", extra: 
 AGG_GRAPHS = {"small": (1500, 37, (6000,)), "large": (2600, 41, (5000, 20000)), "rows9k": (9000, 23, (5000,))}
 
 
-def aggregate_case(size: str, kind: str, f: int, seed: int = 0, pad: bool = True) -> Dict[str, np.ndarray]:
+def aggregate_case(size: str, kind: str, f: int, seed: int = 0, pad: bool = True,
+                   row_lengths: Sequence[int] = AGG_ROW_LENGTHS) -> Dict[str, np.ndarray]:
     n, n_pad, hubs = AGG_GRAPHS[size]
-    return aggregate_problem(kind, n, tuple(AGG_ROW_LENGTHS) + tuple(hubs), f, seed, n_pad=n_pad if pad else 0)
+    return aggregate_problem(kind, n, tuple(row_lengths) + tuple(hubs), f, seed, n_pad=n_pad if pad else 0)
+
+
+# --------------------------------------------------------------------------------- attention aggregation (GAT, GATv2)
+# grapes_amd/csrc/gat_kernels.hip, gatv2_kernels.hip: out_i = sum_j alpha_ij H_j + b over a row's entries and the implied unit
+# self-loop, alpha = softmax_j e_ij, and the analytic backward.  The same criterion as the plain aggregation — each output relative
+# to the fp64 sum of |terms| of ITS OWN terms, against a host fp32 baseline in CSR order (self-loop first) — and beside it a hard
+# cap per output, |got - ref| <= K 2^-24 mag with K = L_r + c0 + c1 S_r (attention_cap_excess; the constants are derived at
+# gat_forward_sums and gat_backward_reference).  The graphs and [cap, f] operands are aggregate_problem's; the row lengths gain
+# the attention kernels' own boundaries: 3; 30-33 and 62-65 (one batch of LPR = 32 / 64 lanes with the self-loop at position -1,
+# one entry short of it, one and two past it); 95-97 and 127-129 (the second work item; three batches of 32); 191-193, 257, 321
+# (chunk counts 3, 4 (+1 entry), 5, 6: gat_fwd_combine_k's four quarters with per = 1 and 2, an empty last quarter at nc = 5).
+ATT_ROW_LENGTHS = (0, 1, 2, 3, 4, 5, 8, 9, 15, 16, 17, 24, 30, 31, 32, 33, 62, 63, 64, 65, 95, 96, 97, 127, 128, 129, 191, 192, 193,
+                   200, 257, 321, 1000)
+ATT_KINDS = AGG_KINDS
+ATT_REGIMES = ("narrow", "wide_asc", "wide_desc", "wide_rand", "ties")
+# the row groups a result is also judged on one by one, so that a failure names the boundary: (name, shortest, longest)
+ATT_GROUPS = (("L<=5", 0, 5), ("L30..33", 30, 33), ("L62..65", 62, 65), ("L95..129", 95, 129), ("L191..321", 191, 321),
+              ("hubs", 1000, 1 << 30))
+ATT_QUANTUM = 2.0 ** -7
+GAT_SLOPE32 = np.float32(0.2)       # GAT_SLOPE of gat_kernels.hip: the kernels' constant IS this fp32 value, and so is the reference's
+ATT_C0, ATT_C1 = 14, 2              # forward cap K = L + ATT_C0 + ATT_C1 S (gat_forward_sums)
+
+
+def attention_case(size: str, kind: str, f: int, seed: int = 0, pad: bool = True, transpose: bool = False,
+                   hub_cap: Optional[int] = None, compress: bool = True) -> Dict[str, np.ndarray]:
+    """aggregate_case over ATT_ROW_LENGTHS (+ the hubs of AGG_GRAPHS[size], each cut to hub_cap entries if given).
+    transpose: the same graph with src and dst swapped (re-sorted by (source, destination)), so that the named lengths are the
+    rows of the by-source CSR, the one the backward walks.  lens / lens_s: entries per by-target / by-source row as the build
+    leaves them (stored self-loops dropped).  kind `mixed`: the operand rows are spread over 10^[-4, 4] instead of
+    10^[-12, 12] (h, dout -> sign |.|^(1/3), formed in fp64 and rounded to fp32 once): the attention backward multiplies three
+    operand rows into one parameter gradient (ds H with ds ~ alpha G.H), which at 10^12 each leaves fp32's range, and a weight of
+    e^-56 beside a row at 10^-12 its normal range; nothing else of the operands changes.  compress=False keeps 10^[-12, 12], which
+    the forward alone can take (tests of the criterion)."""
+    n, n_pad, hubs = AGG_GRAPHS[size]
+    if hub_cap is not None:
+        hubs = tuple(min(h, hub_cap) for h in hubs)
+    p = aggregate_problem(kind, n, tuple(ATT_ROW_LENGTHS) + hubs, f, seed, n_pad=n_pad if pad else 0)
+    if transpose:
+        src, dst = p["dst"].astype(np.int64), p["src"].astype(np.int64)
+        o = np.lexsort((dst, src))
+        p["src"], p["dst"] = src[o].astype(np.int32), dst[o].astype(np.int32)
+    keep = p["src"] != p["dst"]
+    p["lens"] = np.bincount(p["dst"][keep], minlength=n).astype(np.int64)
+    p["lens_s"] = np.bincount(p["src"][keep], minlength=n).astype(np.int64)
+    if kind == "mixed" and compress:
+        for k in ("h", "dout"):
+            p[k] = np.ascontiguousarray(np.cbrt(p[k].astype(np.float64)), dtype=np.float32)
+    return p
+
+
+def attention_scores(n: int, cap: int, regime: str, seed: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """(s_src, s_dst) fp32 [cap], NaN past n.  s_src is an EVEN multiple of 2^-7 and s_dst an ODD one, both below 2^6: every
+    raw = s_src[j] + s_dst[i] is exact in fp32 (at most 14 significant bits) and never 0, LeakyReLU's kink.  A row's entries
+    ascend by source id, so the node order of s_src places a row's maximum:
+      narrow     |raw| <= 2, random;
+      wide_asc   s_src ascending in node id over [-40, 40] (the maximum in a row's LAST batch or chunk), s_dst random in [-8, 8]:
+                 e spans 50 and more, most weights of a long row fall below 2^-24 of the largest;
+      wide_desc  descending (the maximum at the first entry, or the self-loop);  wide_rand  a random permutation of the same;
+      ties       every raw the same negative value."""
+    rng = np.random.default_rng(7919 + seed)
+    q = ATT_QUANTUM
+    if regime == "narrow":
+        s_src, s_dst = 2 * q * rng.integers(-64, 65, n), q * (2 * rng.integers(-64, 64, n) + 1)
+    elif regime in ("wide_asc", "wide_desc", "wide_rand"):
+        s_src = 2 * q * np.round(np.linspace(-40.0, 40.0, n) / (2 * q))
+        if regime == "wide_desc":
+            s_src = s_src[::-1]
+        elif regime == "wide_rand":
+            s_src = rng.permutation(s_src)
+        s_dst = q * (2 * rng.integers(-512, 512, n) + 1)
+    elif regime == "ties":
+        s_src, s_dst = np.full(n, 32 * q), np.full(n, -81 * q)
+    else:
+        raise ValueError(regime)
+    out = []
+    for s in (s_src, s_dst):
+        v = np.full(cap, np.nan, np.float32)
+        v[:n] = s
+        assert np.array_equal(v[:n].astype(np.float64), s)
+        out.append(v)
+    return out[0], out[1]
+
+
+def _ext_csr(rowptr, csr, n):
+    """The walk of the attention kernels: every row's implied self-loop FIRST, then its entries -> (ptr [n + 1], row [E + n],
+    col [E + n]) int64."""
+    rowptr = np.asarray(rowptr, dtype=np.int64)[:n + 1]
+    csr = np.asarray(csr, dtype=np.int64)[:rowptr[-1]]
+    ptr = rowptr + np.arange(n + 1)
+    row = np.repeat(np.arange(n), np.diff(ptr))
+    col = np.empty(ptr[-1], np.int64)
+    stored = np.ones(len(col), bool)
+    stored[ptr[:-1]] = False
+    col[ptr[:-1]] = np.arange(n)
+    col[stored] = csr
+    return ptr, row, col
+
+
+def _seq_rows(ptr, f: int, terms) -> np.ndarray:
+    """[n, f] fp32: for every row of the walk `ptr` the sequential fp32 sum of terms(entry ids) ([k, f] fp32) in entry order — rows
+    of up to AGG_LOOP_ROWS + 1 entries all together by position-in-row, longer ones through _seq_sum_f32 (the same chain)."""
+    n = len(ptr) - 1
+    lens = np.diff(ptr)
+    acc = np.zeros((n, f), np.float32)
+    short = lens <= AGG_LOOP_ROWS + 1
+    for j in range(int(min(AGG_LOOP_ROWS + 1, lens.max())) if n else 0):
+        rows = np.nonzero(short & (lens > j))[0]
+        acc[rows] += np.asarray(terms(ptr[rows] + j), dtype=np.float32)
+    for r in np.nonzero(~short)[0]:
+        acc[r] = _seq_sum_f32(np.ascontiguousarray(terms(np.arange(ptr[r], ptr[r + 1])), dtype=np.float32))
+    return acc
+
+
+def _row_max(v, ptr):
+    return np.maximum.reduceat(v, ptr[:-1])         # (every row of an extended walk has its self-loop: no empty segment)
+
+
+class GatWeights:
+    """The attention weights of one graph and one pair of score vectors, which do not depend on the width: by-target walk
+    (ptr, row, col; L = stored entries per row), fp64 alpha per entry, and the fp32 two-pass softmax of the baseline:
+      e32 = raw > 0 ? raw : fl32(0.2f raw)  (as gat_leaky forms it; raw itself is exact),  m32 = the row's fp32 maximum,
+      p32 = fl32(exp(fl64(fl32(e32 - m32))))  (widened before exp: the same on every host),  sum32 = the p32 added sequentially
+      in walk order, lse32 = fl32(log(fl64(sum32))).
+    S [n] = max_j |e_ij| + max_j |e_ij - m_i| in fp64, the score term of the caps.  lse_ref = log sum_j exp(e64_ij - m32_i): what
+    row_ms[i, 1] must be beside a maximum of m32_i."""
+
+    def __init__(self, rowptr, csr, s_src, s_dst, n):
+        f32, f64 = np.float32, np.float64
+        self.n = n
+        self.s_src, self.s_dst = np.asarray(s_src, dtype=f32), np.asarray(s_dst, dtype=f32)
+        self.ptr, self.row, self.col = _ext_csr(rowptr, csr, n)
+        ptr, row, col = self.ptr, self.row, self.col
+        self.L = np.diff(ptr) - 1
+        e32, e64, _, _ = self.scores(row, col)
+        self.m32 = _row_max(e32, ptr)
+        self.p32 = np.exp((e32 - self.m32[row]).astype(f32).astype(f64)).astype(f32)
+        self.sum32 = _seq_rows(ptr, 1, lambda idx: self.p32[idx, None])[:, 0]
+        self.lse32 = np.log(self.sum32.astype(f64)).astype(f32)
+        self.m64 = _row_max(e64, ptr)
+        p64 = np.exp(e64 - self.m64[row])
+        self.den64 = np.add.reduceat(p64, ptr[:-1])
+        self.alpha64 = p64 / self.den64[row]
+        self.lse_ref = np.log(np.add.reduceat(np.exp(e64 - self.m32.astype(f64)[row]), ptr[:-1]))
+        self.S = _row_max(np.abs(e64), ptr) + _row_max(np.abs(e64 - self.m64[row]), ptr)
+
+    def scores(self, i, j):
+        """(e32, e64, slope32, slope64) of the entries j -> i."""
+        raw32 = self.s_src[j] + self.s_dst[i]
+        raw64 = self.s_src[j].astype(np.float64) + self.s_dst[i].astype(np.float64)
+        assert np.array_equal(raw32.astype(np.float64), raw64), "a score sum is not exact in fp32"
+        pos = raw32 > 0
+        e32 = np.where(pos, raw32, GAT_SLOPE32 * raw32).astype(np.float32)
+        e64 = np.where(pos, raw64, float(GAT_SLOPE32) * raw64)
+        return e32, e64, np.where(pos, np.float32(1), GAT_SLOPE32), np.where(pos, 1.0, float(GAT_SLOPE32))
+
+    def K(self):
+        """The forward cap's per-row factor L + ATT_C0 + ATT_C1 S."""
+        return self.L + ATT_C0 + ATT_C1 * self.S
+
+
+def _named_rows64(h32, n):
+    """[cap, f] fp64 with the capacity rows (NaN: no entry names them) zeroed."""
+    h64 = np.asarray(h32, dtype=np.float64).copy()
+    h64[n:] = 0.0
+    return torch.from_numpy(h64)
+
+
+def _sp64(row, col, val, n, cap):
+    return torch.sparse_coo_tensor(torch.from_numpy(np.stack([row, col])), torch.from_numpy(np.asarray(val, dtype=np.float64)),
+                                   (n, cap), dtype=torch.float64)
+
+
+def gat_forward_sums(w: GatWeights, h):
+    """out before bias and ReLU: (ref fp64, mag fp64, base fp32 numpy) with ref = sum_j alpha_ij H_j, mag = sum_j alpha_ij |H_j|
+    (aggregate_finish adds the bias and the ReLU).  The baseline adds the products fl32(p32 h) sequentially in walk order (self-loop
+    first) and divides once by sum32.
+
+    The cap K = L + ATT_C0 + ATT_C1 S, first-order roundings of out = (sum p h) / (sum p) in units of u = 2^-24 of mag:
+      a weight:  e = fl32(0.2f raw) errs by u |e| (exact where raw > 0), d = fl32(e - m) by u |d|, expf is documented to 1 ulp = 2 u:
+                 p = exp(e - m)(1 + t), |t| <= u (|e| + |d| + 2) <= u (S + 2).  A shift of every e of a row by the same amount — the
+                 error of the maximum itself, the common factor exp(m_old - m_new) of a rescale or exp(m_c - M) of the combine, which
+                 multiplies accumulator and sum alike — cancels in the quotient and costs nothing.
+      the quotient carries that error once in the numerator and once in the denominator:           2 S + 4
+      the accumulator: L + 1 fused multiply-adds in a chain (the product is not rounded):           L
+      the denominator: a butterfly of log2(64) adds, one rounding joining the running sum:          6 + 1
+      the reciprocal of the sum, its product with the accumulator, and the bias:                    2 + 1
+    so c1 = 2 and c0 = 4 + 7 + 3 = 14.  Not in the form: the roundings a row makes once per BATCH after the first (acc *= sc, and
+    the running sum's fused multiply-add): at most 2 ceil((L + 1) / 32) - 2, a sixteenth of L.  The L of the chain is itself a
+    worst case that only the row's first entries suffer and that rounding errors of alternating sign never reach; tests/
+    test_attention_accuracy_cpu.py shows a faithful emulation at a fifth of the cap on every row of the cases judged."""
+    n = w.n
+    h32 = np.ascontiguousarray(np.asarray(h, dtype=np.float32))
+    f = h32.shape[1]
+    h64 = _named_rows64(h32, n)
+    A = _sp64(w.row, w.col, w.alpha64, n, h32.shape[0])
+    ref, mag = torch.sparse.mm(A, h64), torch.sparse.mm(A, h64.abs())
+    acc = _seq_rows(w.ptr, f, lambda idx: w.p32[idx, None] * h32[w.col[idx]])
+    return ref, mag, (acc / w.sum32[:, None]).astype(np.float32)
+
+
+def attention_cap_excess(got, ref, capw) -> float:
+    """max over the outputs of |got - ref| / (2^-24 capw): capw is K mag for an output with one factor K, or the sum of its parts'
+    K |part| for one that adds up results with factors of their own (dh, da_src).  An output with capw == 0 must be 0."""
+    got, ref, capw = (torch.as_tensor(v).double().cpu() for v in (got, ref, capw))
+    if got.numel() == 0:
+        return 0.0
+    bound = U32 * capw.expand_as(ref)
+    err = (got - ref).abs()
+    err = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err)
+    q = torch.where(bound > 0, err / torch.where(bound > 0, bound, torch.ones_like(bound)),
+                    torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, float("inf"))))
+    return float(q.max())
+
+
+def row_groups(lens) -> Dict[str, np.ndarray]:
+    """{"all": every row, group name: the rows whose length falls in the group} over ATT_GROUPS (empty groups left out)."""
+    lens = np.asarray(lens)
+    out = {"all": np.arange(len(lens))}
+    for name, lo, hi in ATT_GROUPS:
+        rows = np.nonzero((lens >= lo) & (lens <= hi))[0]
+        if len(rows):
+            out[name] = rows
+    return out
+
+
+def assert_attention_accuracy(got, ref, mag, base, capw, lens=None, what: str = "") -> Dict[str, Tuple[Accuracy, float]]:
+    """The ratio criterion and the cap |got - ref| <= 2^-24 capw on all outputs together and, where lens [rows] is given, on every
+    row group of ATT_GROUPS by itself, one [accuracy] and one [cap] line each.  -> {group: (Accuracy, cap quotient)}; every group
+    is printed before the first failure is raised.
+    All rows together are judged by the project's criterion unchanged.  A GROUP may be one row of one column, a single draw of the
+    baseline's error, which lies anywhere between 0 and its typical size (measured: 0.05 u on the one output of a 1262-entry row at
+    f = 1, where the kernel's 0.3 u then stood at a ratio of 8).  So within a group the baseline's max and rms are not taken below
+    the baseline's rms over ALL outputs of the tensor, its typical error per output; the factors stay RMS_FACTOR and MAX_FACTOR, and
+    the cap, which knows each row's own length, is unchanged."""
+    got, ref, mag, base = (torch.as_tensor(np.asarray(v) if isinstance(v, np.ndarray) else v).cpu() for v in (got, ref, mag, base))
+    capw = torch.as_tensor(capw).double().expand_as(ref)
+    res, bad = {}, []
+    for name, rows in (row_groups(lens) if lens is not None else {"all": slice(None)}).items():
+        a = Accuracy(got[rows], ref[rows], mag[rows], base[rows])
+        if name == "all":
+            typical = a.base_rms
+        else:       # (see the docstring: a group's baseline is not taken below the baseline's typical error over the tensor)
+            a.base_max, a.base_rms = max(a.base_max, typical), max(a.base_rms, typical)
+        x = attention_cap_excess(got[rows], ref[rows], capw[rows])
+        print(f"[accuracy] {what} {name}: {a}")
+        print(f"[cap] {what} {name}: worst |err| / (K u mag) = {x:.3f}")
+        res[name] = (a, x)
+        if not (a.ok() and x <= 1.0):
+            bad.append(f"{what} {name}: {a}; cap x{x:.3f}")
+    assert not bad, "; ".join(bad)
+    return res
+
+
+def gat_row_ms_excess(w: GatWeights, row_ms) -> float:
+    """row_ms [n, 2] = (maximum, log of the softmax sum) of the forward.  The maximum must be the fp32 maximum of the fp32 e BIT
+    FOR BIT (asserted).  Returns the worst |row_ms[:, 1] - lse_ref| / bound with the absolute bound
+        (L + ATT_C0 + ATT_C1 S + 2 lse_ref) 2^-24:
+    the sum's relative error is that of the forward's denominator (weights S + 2, butterfly and running sum 7, under
+    L + ATT_C0 + ATT_C1 S), which is the absolute error of its logarithm, and logf adds 1 ulp = 2 u of its result."""
+    r = np.asarray(row_ms, dtype=np.float32)[:w.n]
+    assert np.array_equal(r[:, 0].view(np.int32), w.m32.view(np.int32)), "row_ms maximum is not the fp32 maximum of the fp32 scores"
+    bound = (w.K() + 2 * w.lse_ref) * U32
+    err = np.abs(r[:, 1].astype(np.float64) - w.lse_ref)
+    return float(np.max(np.where(np.isnan(err), np.inf, err) / bound))
+
+
+_DOT_BLOCK = 4096
+
+
+def _dots(a32, ia, b32, ib):
+    """Per pair k the dot product a[ia[k]] . b[ib[k]] over the columns: (fp64, fp64 of |a||b|, fp32 with the products rounded and
+    added in column order)."""
+    m = len(ia)
+    d64, dm, d32 = np.zeros(m), np.zeros(m), np.zeros(m, np.float32)
+    for k in range(0, m, _DOT_BLOCK):
+        x, y = a32[ia[k:k + _DOT_BLOCK]], b32[ib[k:k + _DOT_BLOCK]]
+        x64, y64 = x.astype(np.float64), y.astype(np.float64)
+        d64[k:k + _DOT_BLOCK] = (x64 * y64).sum(1)
+        dm[k:k + _DOT_BLOCK] = np.abs(x64 * y64).sum(1)
+        d32[k:k + _DOT_BLOCK] = np.add.accumulate(x * y, axis=1, dtype=np.float32)[:, -1]
+    return d64, dm, d32
+
+
+def gat_backward_reference(wt: GatWeights, rowptr_s, csr_dst, h, dout, out, a_src, a_dst, bias=None, relu=False):
+    """ops.gat_aggregate_bwd at aggregation level (tests/gat_oracle.gat_conv_grads restated over the entry point's own inputs):
+        G = dout (where out > 0 under ReLU; `out` is the DEVICE forward's fp32 output),  c_i = G_i . (out_i - b),
+        g_ij = alpha_ij (G_i . H_j - c_i) slope_ij,   ds_dst[i] = sum_j g_ij,   ds_src[j] = sum_i g_ij,
+        dh_j = sum_i alpha_ij G_i + ds_src[j] a_src + ds_dst[j] a_dst,   da_src = ds_srcᵀ H,  da_dst = ds_dstᵀ H,  dbias = colsum G
+    over the by-target walk of wt and the by-source walk of (rowptr_s, csr_dst), self-loop first in both.  alpha is recomputed in
+    fp64 from the scores: row_ms is not read, so a wrong row_ms shows in the gradients.
+    -> {"dh" | "da_src" | "da_dst" | "dbias" | "ds_src" | "ds_dst": (ref, mag, base, capw)}.
+    mag: the fp64 sum of |terms|, products taken apart — sum_f |G_if| |H_jf| + sum_f |G_if| |out_if - b_f| for (G_i . H_j - c_i), and
+    for dh the magnitudes of ds_src and ds_dst times |a_src|, |a_dst|.
+    base: the same formulas in fp32: alpha32 = fl32(exp(fl64(fl32(fl32(e32 - m32) - lse32)))) from the baseline forward's own
+    (m32, lse32), dot products with rounded products added in column order, every row sum sequential in walk order, the
+    parameter gradients in row order (colsum_reference's).
+    capw (first-order roundings in u = 2^-24; B_i = ceil((L_t(i) + 1) / 32) batches, lse <= log(L + 1) <= 10 here):
+      alpha as the backward forms it, expf((e - m) - lse) from the stored pair: e, d and d - lse round (S_i + S_i + 10), expf 2; the
+        stored lse carries the forward denominator's error (S_i + 2 + 6 + B_i) and logf's 2 lse (20):  K_a(i) = 3 S_i + B_i + 40
+      G_i . H_j and c_i: a chain of ceil(F / 32) fused multiply-adds per lane and a butterfly (D = ceil(F / 32) + 6), out - b,
+        the difference and two products:                                                            K_g(i) = K_a(i) + D + 4
+      ds_dst[i]: L_t(i) adds;  ds_src[j]: L_s(j) adds, each term with its own K_g(i)
+      dh_j: sum_i (L_s(j) + 2 + K_a(i)) alpha |G_i| + (cap of ds_src[j] + 2 its mag) |a_src| + the same for ds_dst[j]
+      da_src, da_dst: sum_r (cap of ds[r] + (n + 1) its mag) |H_r|;  dbias: n mag."""
+    f32, f64 = np.float32, np.float64
+    n = wt.n
+    h32, d32, o32 = (np.ascontiguousarray(np.asarray(v, dtype=f32)) for v in (h, dout, out))
+    cap, F = h32.shape
+    as32, ad32 = np.asarray(a_src, dtype=f32).reshape(-1), np.asarray(a_dst, dtype=f32).reshape(-1)
+    b32 = np.zeros(F, f32) if bias is None else np.asarray(bias, dtype=f32)
+    G32 = np.zeros((cap, F), f32)
+    G32[:n] = np.where(o32[:n] > 0, d32[:n], f32(0)) if relu else d32[:n]
+    H32 = h32.copy()
+    H32[n:] = 0
+    ob32 = np.zeros((cap, F), f32)
+    ob32[:n] = o32[:n] - b32
+    ob64 = np.zeros((cap, F))
+    ob64[:n] = o32[:n].astype(f64) - b32.astype(f64)
+    G64, H64 = G32.astype(f64), H32.astype(f64)
+    c64, magc = (G64 * ob64).sum(1), np.abs(G64 * ob64).sum(1)
+    c32 = np.add.accumulate(G32 * ob32, axis=1, dtype=f32)[:, -1]
+    ptr_s, row_s, col_s = _ext_csr(rowptr_s, csr_dst, n)
+    Lt, Ls = wt.L, np.diff(ptr_s) - 1
+    Ka = 3 * wt.S + np.ceil((Lt + 1) / 32.0) + 40
+    Kg = Ka + np.ceil(F / 32.0) + 6 + 4
+
+    def edges(i, j):
+        e32, e64, sl32, sl64 = wt.scores(i, j)
+        a64 = np.exp(e64 - wt.m64[i]) / wt.den64[i]
+        a32 = np.exp(((e32 - wt.m32[i]).astype(f32) - wt.lse32[i]).astype(f32).astype(f64)).astype(f32)
+        dot64, dotm, dot32 = _dots(G32, i, H32, j)
+        g64 = a64 * (dot64 - c64[i]) * sl64
+        tm = a64 * sl64 * (dotm + magc[i])
+        g32 = ((a32 * (dot32 - c32[i])).astype(f32) * sl32).astype(f32)
+        return a64, a32, g64, tm, g32
+
+    _, _, g64, tm, g32 = edges(wt.row, wt.col)
+    dsd64, dsdm = np.add.reduceat(g64, wt.ptr[:-1]), np.add.reduceat(tm, wt.ptr[:-1])
+    dsd32 = _seq_rows(wt.ptr, 1, lambda idx: g32[idx, None])[:, 0]
+    dsdc = (Lt + Kg) * dsdm
+    a64, a32, g64, tm, g32 = edges(col_s, row_s)
+    dss64, dssm = np.add.reduceat(g64, ptr_s[:-1]), np.add.reduceat(tm, ptr_s[:-1])
+    dss32 = _seq_rows(ptr_s, 1, lambda idx: g32[idx, None])[:, 0]
+    dssc = np.add.reduceat(tm * (Ls[row_s] + Kg[col_s]), ptr_s[:-1])
+
+    t = torch.from_numpy
+    Gt, Ht = t(G64), t(H64[:n])
+    as64, ad64 = t(as32.astype(f64)), t(ad32.astype(f64))
+    A = _sp64(row_s, col_s, a64, n, cap)
+    Ac = _sp64(row_s, col_s, a64 * (Ls[row_s] + 2 + Ka[col_s]), n, cap)
+    col = lambda v: t(np.asarray(v, dtype=f64))[:, None]
+    dh_ref = torch.sparse.mm(A, Gt) + col(dss64) * as64 + col(dsd64) * ad64
+    dh_mag = torch.sparse.mm(A, Gt.abs()) + col(dssm) * as64.abs() + col(dsdm) * ad64.abs()
+    dh_cap = torch.sparse.mm(Ac, Gt.abs()) + col(dssc + 2 * dssm) * as64.abs() + col(dsdc + 2 * dsdm) * ad64.abs()
+    acc = _seq_rows(ptr_s, F, lambda idx: a32[idx, None] * G32[col_s[idx]])
+    dh_base = ((acc + dss32[:, None] * as32).astype(f32) + dsd32[:, None] * ad32).astype(f32)
+    res = {"dh": (dh_ref, dh_mag, t(dh_base), dh_cap),
+           "ds_src": (t(dss64), t(dssm), t(dss32), t(dssc)), "ds_dst": (t(dsd64), t(dsdm), t(dsd32), t(dsdc))}
+    for name, s64, sm, sc, s32 in (("da_src", dss64, dssm, dssc, dss32), ("da_dst", dsd64, dsdm, dsdc, dsd32)):
+        res[name] = (t(s64) @ Ht, t(sm) @ Ht.abs(), t(_seq_sum_f32(np.ascontiguousarray(s32[:, None] * H32[:n]))),
+                     t(sc + (n + 1) * sm) @ Ht.abs())
+    db = colsum_reference(G32[:n])
+    res["dbias"] = (db[0], db[1], db[2], float(n) * db[1])
+    return res
+# ----------------------------------------------------------------------------------------------------------- GATv2
+GATV2_KINDS = ("normal", "zeros", "striped")
+# K = L + GATV2_C0 + GATV2_C1 S of the GATv2 forward (Gatv2Weights)
+GATV2_SCORE_ROUNDINGS = 15
+GATV2_C0, GATV2_C1 = ATT_C0, 2 * GATV2_SCORE_ROUNDINGS
+_V2_BLOCK = 2048
+
+
+def gatv2_inputs(p: Dict[str, np.ndarray], heads: int, c: int, seed: int = 0) -> Dict[str, np.ndarray]:
+    """The GATv2 operands over an attention_case p of width heads * c: x_l = p["h"] rounded to an EVEN multiple of 2^-7 (zeros and
+    stripes stay exact zeros), x_r = N(0,1) rounded to an ODD multiple, so that every z = x_l[j] + x_r[i] is exact in fp32 and never
+    on LeakyReLU's kink; att ~ N(0,1) 0.3 [heads * c]; dout = p["dout"]; bias [heads * c] (concat; the head mean takes its first c).
+    Kinds normal, zeros and striped only: there is no `mixed` kind here, because GATv2's score att . LeakyReLU(x_l + x_r) depends
+    on x_l itself — rows of x_l at 10^[-4, 4] would put every score beyond exp's range."""
+    q = ATT_QUANTUM
+    n, cap, f = p["n"], p["cap"], heads * c
+    assert p["h"].shape[1] == f
+    rng = np.random.default_rng(31337 + seed)
+    x_l = np.full((cap, f), np.nan, np.float32)
+    x_r = np.full((cap, f), np.nan, np.float32)
+    x_l[:n] = 2 * q * np.round(p["h"][:n].astype(np.float64) / (2 * q))
+    x_r[:n] = q * (2 * np.round(rng.standard_normal((n, f)) / (2 * q)) + 1)
+    att = (rng.standard_normal(f) * 0.3).astype(np.float32)
+    return {"x_l": x_l, "x_r": x_r, "att": att, "dout": p["dout"], "bias": p["bias"]}
+
+
+class Gatv2Weights:
+    """Per head the attention weights of gatv2_aggregate_fwd over the by-target walk (self-loop first), [entries, heads]:
+      e = sum_c att[h, c] LeakyReLU(z),  z = x_l[j] + x_r[i] (exact),  T = sum_c |att| |LeakyReLU z|
+    in fp64 (alpha64, m64, den64, lse64) and for the baseline in fp32: products fl32(att fl32(LeakyReLU z)) added in column order,
+    then the two-pass softmax of GatWeights (m32, p32, sum32, lse32).
+    S [n, heads] = max_j |e| + max_j |e - m| + max_j T.  The forward cap is K = L + GATV2_C0 + GATV2_C1 S: as in gat_forward_sums,
+    but a weight's exponent now carries the score's own rounding — the slope product, at most 4 fused multiply-adds per slab, up
+    to 4 slabs and a butterfly of 6 (head_sum): 15 roundings relative to T — besides that of e - m: |t| <= u (15 T + |d| + 2) <=
+    u (15 S + 2), once in the numerator and once in the denominator: GATV2_C1 = 30, GATV2_C0 = ATT_C0."""
+
+    def __init__(self, rowptr, csr, x_l, x_r, att, heads, slope, n):
+        f32, f64 = np.float32, np.float64
+        self.n, self.H = n, heads
+        self.x_l, self.x_r = (np.ascontiguousarray(np.asarray(v, dtype=f32)) for v in (x_l, x_r))
+        self.att = np.asarray(att, dtype=f32).reshape(-1)
+        self.F = self.att.size
+        self.C = self.F // heads
+        self.slope32 = f32(slope)
+        self.ptr, self.row, self.col = _ext_csr(rowptr, csr, n)
+        ptr, row = self.ptr, self.row
+        self.L = np.diff(ptr) - 1
+        e32, e64, T = self.scores(row, self.col)
+        self.m32 = _row_max(e32, ptr)
+        self.p32 = np.exp((e32 - self.m32[row]).astype(f32).astype(f64)).astype(f32)
+        self.sum32 = _seq_rows(ptr, heads, lambda idx: self.p32[idx])
+        self.lse32 = np.log(self.sum32.astype(f64)).astype(f32)
+        self.m64 = _row_max(e64, ptr)
+        p64 = np.exp(e64 - self.m64[row])
+        self.den64 = np.add.reduceat(p64, ptr[:-1])
+        self.alpha64 = p64 / self.den64[row]
+        self.lse64 = np.log(self.den64)
+        self.S = _row_max(np.abs(e64), ptr) + _row_max(np.abs(e64 - self.m64[row]), ptr) + _row_max(T, ptr)
+
+    def leaky(self, i, j):
+        """(z32, LeakyReLU z in fp32 as gv2_leaky forms it, in fp64, dLeaky/dz fp32) of the entries j -> i, [k, F]."""
+        z = self.x_l[j] + self.x_r[i]
+        pos = z > 0
+        return z, np.where(pos, z, self.slope32 * z).astype(np.float32), np.where(pos, z.astype(np.float64), float(self.slope32) * z.astype(np.float64)), \
+            np.where(pos, np.float32(1), self.slope32)
+
+    def scores(self, i, j):
+        """(e32, e64, T) [k, heads] of the entries j -> i."""
+        k, H, C = len(i), self.H, self.C
+        e32, e64, T = np.zeros((k, H), np.float32), np.zeros((k, H)), np.zeros((k, H))
+        a64 = self.att.astype(np.float64)
+        for b in range(0, k, _V2_BLOCK):
+            s = slice(b, b + _V2_BLOCK)
+            z, l32, l64, _ = self.leaky(i[s], j[s])
+            assert np.array_equal(z.astype(np.float64), self.x_l[j[s]].astype(np.float64) + self.x_r[i[s]]), "z is not exact in fp32"
+            e64[s] = (a64 * l64).reshape(-1, H, C).sum(2)
+            T[s] = np.abs(a64 * l64).reshape(-1, H, C).sum(2)
+            e32[s] = np.add.accumulate((self.att * l32).reshape(-1, H, C), axis=2, dtype=np.float32)[:, :, -1]
+        return e32, e64, T
+
+    def K(self):
+        return self.L[:, None] + GATV2_C0 + GATV2_C1 * self.S            # [n, heads]
+
+
+def _per_col(v, C):
+    """[k, heads] -> [k, heads * C]: every head's value over its C columns."""
+    return np.repeat(v, C, axis=1)
+
+
+def gatv2_forward_reference(w: Gatv2Weights, bias=None, relu=False, concat=True):
+    """ops.gatv2_aggregate_fwd -> {"out": (ref, mag, base, capw), "agg": the per-head aggregate before bias likewise}:
+    agg_i[h] = sum_j alpha_ij[h] x_l[j, h];  out = agg + b (ReLU), or mean_h agg[h] + b (ReLU) with the heads added in head order and
+    one division by H in the baseline (cap: the heads' own caps / H + (H + 2) mag)."""
+    n, H, C, F = w.n, w.H, w.C, w.F
+    cap_rows = w.x_l.shape[0]
+    xl64 = _named_rows64(w.x_l, n)
+    ref, mag = torch.zeros(n, F, dtype=torch.float64), torch.zeros(n, F, dtype=torch.float64)
+    for h in range(H):
+        A = _sp64(w.row, w.col, w.alpha64[:, h], n, cap_rows)
+        cols = slice(h * C, (h + 1) * C)
+        ref[:, cols], mag[:, cols] = torch.sparse.mm(A, xl64[:, cols].contiguous()), torch.sparse.mm(A, xl64[:, cols].abs().contiguous())
+    acc = _seq_rows(w.ptr, F, lambda idx: _per_col(w.p32[idx], C) * w.x_l[w.col[idx]])
+    base = (acc / _per_col(w.sum32, C)).astype(np.float32)
+    K = torch.from_numpy(_per_col(w.K(), C))
+    agg = (ref, mag, torch.from_numpy(base), K * mag)
+    b32 = None if bias is None else np.asarray(bias, dtype=np.float32)[:F if concat else C]
+    if concat:
+        r, m, b = aggregate_finish((ref, mag, base), b32, relu)
+        return {"agg": agg, "out": (r, m, b, K * m)}
+    r, m = ref.view(n, H, C).sum(1) / H, mag.view(n, H, C).sum(1) / H
+    capw = (K * mag).view(n, H, C).sum(1) / H + (H + 2) * m
+    b = np.add.accumulate(base.reshape(n, H, C), axis=1, dtype=np.float32)[:, -1] / np.float32(H)
+    r, m2, b = aggregate_finish((r, m, b.astype(np.float32)), b32, relu)
+    return {"agg": agg, "out": (r, m2, b, capw + (m2 - m))}
+
+
+def gatv2_row_ms_excess(w: Gatv2Weights, row_ms) -> float:
+    """row_ms [n, heads, 2] = (maximum, log sum).  The kernel's score is not the baseline's bit for bit (another order of the C
+    products), so the PAIR is judged: row_ms[.., 0] + row_ms[.., 1] against m64 + lse64, the logarithm of sum_j exp(e_ij), within
+    (K + 2 lse64) 2^-24 + 15 u max T (the maximum's own rounding, under GATV2_C1 S) -> worst error / bound; and the maximum alone
+    within 15 u max T <= 15 u S of m64."""
+    r = np.asarray(row_ms, dtype=np.float64).reshape(-1, w.H, 2)[:w.n]
+    bound = (w.K() + 2 * w.lse64 + GATV2_SCORE_ROUNDINGS * w.S) * U32
+    err = np.abs(r[:, :, 0] + r[:, :, 1] - (w.m64 + w.lse64))
+    bm = GATV2_SCORE_ROUNDINGS * w.S * U32
+    errm = np.abs(r[:, :, 0] - w.m64)
+    errm = np.where(bm > 0, errm / np.where(bm > 0, bm, 1.0), np.where(errm == 0, 0.0, np.inf))     # (S = 0: every score exactly 0)
+    q = np.maximum(err / bound, errm)
+    return float(np.max(np.where(np.isnan(q), np.inf, q)))
+
+
+def gatv2_backward_reference(w: Gatv2Weights, rowptr_s, csr_dst, dout, out, agg_dev, bias=None, relu=False, concat=True):
+    """ops.gatv2_aggregate_bwd (tests/gatv2_oracle.gatv2_conv_grads restated over the entry point's own inputs):
+        G[i, h] = dout (where out > 0 under ReLU; / H for the head mean),  c[i, h] = G[i, h] . A[i, h],  A = out - b (concat) or the
+        forward's saved per-head aggregate,  de_ij[h] = alpha_ij[h] (G[i, h] . x_l[j, h] - c[i, h]),  dz_ij = de att (z > 0 ? 1 : slope),
+        dx_r[i] = sum_j dz_ij,  dx_l[j] = sum_i alpha_ij G_i + dz_ij,  datt = sum_ij de_ij LeakyReLU(z_ij),  dbias = colsum of the gated dout
+    -> {"dx_l" | "dx_r" | "datt" | "dbias": (ref, mag, base, capw)}; `out` and `agg_dev` are the DEVICE forward's; alpha is recomputed
+    in fp64 from x_l, x_r, att (row_ms is not read).  mag: sums of |terms| with the products taken apart, as gat_backward_reference.
+    base: the same formulas in fp32 — alpha32 = fl32(exp(fl64(fl32(fl32(e32 - m32) - lse32)))), dot products in column order, row
+    sums in walk order, datt over all entries in by-target walk order, dbias in row order (head mean: every head's column sum of
+    fl32(g fl32(1 / H)), the heads added in head order, as gatv2_bwd_rows_k and gatv2_bwd_params_final_k form it).
+    capw, in u = 2^-24 (B_i = ceil((L_t(i) + 1) / 32), lse <= 10):
+      alpha from the stored pair: K_a = 3 * 15 S + B_i + 40 (gat_backward_reference's K_a with the score's 15 roundings in S);
+      de: + the two C-term dot products (at most 15 roundings each, as the score's), the difference, the product, G / H:  K_e = K_a + 20
+      dz = de att slope': + 2;  dx_r[i]: L_t(i) adds;  dx_l[j]: 2 L_s(j) adds (two terms per entry);  datt: E + n adds and
+      LeakyReLU's product;  dbias: n mag."""
+    f32, f64 = np.float32, np.float64
+    n, H, C, F = w.n, w.H, w.C, w.F
+    cap_rows = w.x_l.shape[0]
+    W = F if concat else C
+    d32, o32 = np.asarray(dout, dtype=f32)[:n, :W], np.asarray(out, dtype=f32)[:n]
+    g = np.where(o32 > 0, d32, f32(0)) if relu else d32
+    G32 = np.zeros((cap_rows, F), f32)
+    G32[:n] = g if concat else np.tile((g * (f32(1) / f32(H))).astype(f32), (1, H))
+    G64 = np.zeros((cap_rows, F))
+    G64[:n] = g.astype(f64) if concat else np.tile(g.astype(f64) / H, (1, H))
+    A32 = np.zeros((cap_rows, F), f32)
+    if concat:
+        b32 = np.zeros(F, f32) if bias is None else np.asarray(bias, dtype=f32)[:F]
+        A32[:n] = o32 - b32
+        A64 = np.zeros((cap_rows, F))
+        A64[:n] = o32.astype(f64) - b32.astype(f64)
+    else:
+        A32[:n] = np.asarray(agg_dev, dtype=f32)[:n]
+        A64 = A32.astype(f64)
+    hs = lambda v: v.reshape(-1, H, C)
+    c64, magc = hs(G64 * A64).sum(2), hs(np.abs(G64 * A64)).sum(2)
+    c32 = np.add.accumulate(hs(G32 * A32), axis=2, dtype=f32)[:, :, -1]
+    ptr_s, row_s, col_s = _ext_csr(rowptr_s, csr_dst, n)
+    Lt, Ls = w.L, np.diff(ptr_s) - 1
+    Ka = 3 * GATV2_SCORE_ROUNDINGS * w.S + np.ceil((Lt + 1) / 32.0)[:, None] + 40
+    Ke = Ka + 20
+    a64t, a32t = w.att.astype(f64), w.att
+    xl32 = w.x_l.copy(); xl32[n:] = 0
+    t = torch.from_numpy
+
+    def walk(i, j, ptr, out_rows, Lrow, with_alpha_g, want_datt):
+        """One walk over the entries j -> i: the row sums over `out_rows` of dz (+ alpha G) as (ref, mag, capw) fp64 [n, F], the
+        per-entry fp32 scalars (alpha32, de32) for the baseline, and datt's (ref, mag, capw, base)."""
+        k = len(i)
+        ref, mag, cw = (torch.zeros(n, F, dtype=torch.float64) for _ in range(3))
+        al32, de32 = np.zeros((k, H), f32), np.zeros((k, H), f32)
+        da = [np.zeros(F), np.zeros(F), np.zeros(F), np.zeros(F, f32)]
+        rows_t = t(out_rows)
+        e32, e64, _ = w.scores(i, j)
+        for b in range(0, k, _V2_BLOCK):
+            s = slice(b, b + _V2_BLOCK)
+            ii, jj = i[s], j[s]
+            a64 = np.exp(e64[s] - w.m64[ii]) / w.den64[ii]
+            a32 = np.exp(((e32[s] - w.m32[ii]).astype(f32) - w.lse32[ii]).astype(f32).astype(f64)).astype(f32)
+            gx = G64[ii] * xl32[jj].astype(f64)
+            dot64, dotm = hs(gx).sum(2), hs(np.abs(gx)).sum(2)
+            dot32 = np.add.accumulate(hs(G32[ii] * xl32[jj]), axis=2, dtype=f32)[:, :, -1]
+            de64 = a64 * (dot64 - c64[ii])
+            tm = a64 * (dotm + magc[ii])
+            d32_ = (a32 * (dot32 - c32[ii])).astype(f32)
+            al32[s], de32[s] = a32, d32_
+            z, l32, l64, sl32 = w.leaky(ii, jj)
+            sl64 = sl32.astype(f64)
+            dz = _per_col(de64, C) * a64t * sl64
+            dzm = _per_col(tm, C) * np.abs(a64t) * sl64
+            dzc = _per_col(tm * (Ke[ii] + 2 + Lrow[out_rows[s]][:, None] * (2 if with_alpha_g else 1)), C) * np.abs(a64t) * sl64
+            if with_alpha_g:
+                ag = _per_col(a64, C) * np.abs(G64[ii])
+                dz = dz + _per_col(a64, C) * G64[ii]
+                dzm = dzm + ag
+                dzc = dzc + _per_col(Ka[ii] + 1 + 2 * Lrow[out_rows[s]][:, None], C) * ag
+            ref.index_add_(0, rows_t[s], t(dz)); mag.index_add_(0, rows_t[s], t(dzm)); cw.index_add_(0, rows_t[s], t(dzc))
+            if want_datt:
+                da[0] += (_per_col(de64, C) * l64).sum(0)
+                da[1] += (_per_col(tm, C) * np.abs(l64)).sum(0)
+                da[2] += (_per_col(tm * (Ke[ii] + 2 + k), C) * np.abs(l64)).sum(0)
+                terms = np.concatenate([da[3][None], _per_col(d32_, C) * l32])
+                da[3] = _seq_sum_f32(np.ascontiguousarray(terms, dtype=f32))
+        return (ref, mag, cw), al32, de32, da
+
+    def dz32(i, j, de):
+        _, _, _, sl32 = w.leaky(i, j)
+        return ((_per_col(de, C) * a32t).astype(f32) * sl32).astype(f32)
+
+    (r_ref, r_mag, r_cw), _, de_t, da = walk(w.row, w.col, w.ptr, w.row, Lt, False, True)
+    r_base = _seq_rows(w.ptr, F, lambda idx: dz32(w.row[idx], w.col[idx], de_t[idx]))
+    (l_ref, l_mag, l_cw), al_s, de_s, _ = walk(col_s, row_s, ptr_s, row_s, Ls, True, False)
+    l_base = _seq_rows(ptr_s, F, lambda idx: (dz32(col_s[idx], row_s[idx], de_s[idx]) + _per_col(al_s[idx], C) * G32[col_s[idx]]).astype(f32))
+    res = {"dx_r": (r_ref, r_mag, t(r_base), r_cw), "dx_l": (l_ref, l_mag, t(l_base), l_cw),
+           "datt": (t(da[0]), t(da[1]), t(da[3]), t(da[2]))}
+    db = colsum_reference(g)
+    if not concat:      # the head mean hands every head fl32(g fl32(1 / H)) and adds the heads' column sums in head order
+        part = _seq_sum_f32(np.ascontiguousarray((g * (f32(1) / f32(H))).astype(f32)))
+        db = (db[0], db[1], t(np.add.accumulate(np.tile(part, (H, 1)), axis=0, dtype=f32)[-1].copy()))
+    res["dbias"] = (db[0], db[1], db[2], float(n + H + 2) * db[1])
+    return res
