@@ -119,6 +119,13 @@ SIGNATURES = {
     "grapes_cluster_aggregate_workspace_bytes": (SZ, [I32, I32, I32]),
     "grapes_cluster_aggregate_fwd": (I32, [P, I64, P, I64, P, P, P, F32, I32, P, I64, P, I64, I32, P, I32, P, P, I32, P, P, P]),
     "grapes_cluster_aggregate_bwd": (I32, [P, I64, P, I64, P, P, P, F32, P, I64, P, I64, P, I64, P, I32, P, I32, P, P, I32, P, P, P]),
+    # Cluster-GCN's graph partitioner: size-constrained synchronous label propagation
+    "grapes_partition_propose_workspace_bytes": (SZ, [I32, I32]),
+    "grapes_partition_propose": (I32, [P, P, I32, P, I32, P, P, P, P, P]),
+    "grapes_partition_admit_workspace_bytes": (SZ, [I32, I32]),
+    "grapes_partition_admit": (I32, [P, P, I32, I32, P, P, I32, P, P, P, P]),
+    "grapes_partition_cut_workspace_bytes": (SZ, [I32]),
+    "grapes_partition_cut": (I32, [P, P, I32, P, I32, P, P, P, P]),
     # GATConv aggregation (modules/gcn.py:45-72)
     "grapes_gat_scores": (I32, [P, P, P, P, P, I32, P, I32, P]),
     "grapes_gat_aggregate_workspace_bytes": (SZ, [I32, I32]),

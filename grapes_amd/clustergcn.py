@@ -11,10 +11,14 @@ the union of a few of them.
   the GraphSAINT step does.
 * epoch(): one pass over a permutation of the clusters.  evaluate(): ONE exact full-graph forward, the model in eval mode; accuracy
   for 1-D labels, micro-F1 for multi-label (eval._metrics).
-* Flags: --dataset, --num_parts 32, --batch_size 4 (clusters per step), --partition random|range|file, --partition_file x.npy (an
-  integer array [N] of cluster ids in [0, num_parts), e.g. METIS's output computed elsewhere), --diag_lambda 0, --hidden_dim 256,
-  --num_layers 2, --lr 1e-3, --max_epoch 100, --eval_frequency 1, --dropout 0, --runs 1, --seed.
-* Not built: a graph partitioner (METIS-class or label propagation; --partition file is the way in for one), a captured (hipGraph)
+* Flags: --dataset, --num_parts 32, --batch_size 4 (clusters per step), --partition random|range|file|lp[:ROUNDS[:IMBALANCE]],
+  --partition_file x.npy (an integer array [N] of cluster ids in [0, num_parts), e.g. METIS's output computed elsewhere, or what
+  `python -m grapes_amd.partition` wrote), --diag_lambda 0, --hidden_dim 256, --num_layers 2, --lr 1e-3, --max_epoch 100,
+  --eval_frequency 1, --dropout 0, --runs 1, --seed.  --partition lp (30 rounds, imbalance 0.1), lp:ROUNDS, lp:ROUNDS:IMBALANCE:
+  a random start seeded by --seed, refined by size-constrained label propagation (modules.cluster.refine_partition); the run
+  prints the starting cut, the final cut and the rounds used.
+* Not built: a METIS-class partitioner (multilevel coarsening, a swap or rebalancing phase: label propagation stalls once clusters
+  sit at their cap; --partition file is the way in for a better assignment), edge or node weights in the partitioner, a captured (hipGraph)
   step, multi-GPU forms, graphs with 2^31 or more entries, GraphSAINT-style normalisation of cluster batches, the paper's stochastic
   multiple-partition variant with a normalisation rebuilt per batch beyond what ClusterGCNConv computes on the union itself.
   `--classifier` / `--model_type` routes in grapes_amd.main and grapes_amd.full_batch do not take this loader.
@@ -74,12 +78,43 @@ class ClusterTrainer:
         self.loader.check()
 
 
+LP_ROUNDS, LP_IMBALANCE = 30, 0.1
+
+
+def parse_partition(value: str):
+    """(method, rounds, imbalance) of a --partition value: "random", "range", "file", or "lp", "lp:ROUNDS", "lp:ROUNDS:IMBALANCE"
+    (label propagation from a random start: ROUNDS a non-negative integer, IMBALANCE a non-negative number).  ValueError for
+    anything else."""
+    if value in ("random", "range", "file"):
+        return value, None, None
+    head, *rest = value.split(":")
+    if head != "lp" or len(rest) > 2:
+        raise ValueError(f"--partition is random, range, file, lp, lp:ROUNDS or lp:ROUNDS:IMBALANCE, not {value!r}")
+    try:
+        rounds = int(rest[0]) if rest else LP_ROUNDS
+        imbalance = float(rest[1]) if len(rest) > 1 else LP_IMBALANCE
+    except ValueError:
+        raise ValueError(f"--partition {value!r}: ROUNDS is an integer and IMBALANCE a number") from None
+    if rounds < 0 or not 0 <= imbalance < float("inf"):
+        raise ValueError(f"--partition {value!r}: ROUNDS and IMBALANCE are at least 0")
+    return "lp", rounds, imbalance
+
+
+def _partition_arg(value: str) -> str:
+    """argparse's check of --partition: the value itself, kept as given (it is parsed after parse_args)."""
+    try:
+        parse_partition(value)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+    return value
+
+
 def _parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="grapes_amd.clustergcn", description=__doc__.split("\n\n")[0])
     ap.add_argument("--dataset", type=str)
     ap.add_argument("--num_parts", default=32, type=int)
     ap.add_argument("--batch_size", default=4, type=int)
-    ap.add_argument("--partition", default="random", choices=["random", "range", "file"])
+    ap.add_argument("--partition", default="random", type=_partition_arg, metavar="random|range|file|lp[:ROUNDS[:IMBALANCE]]")
     ap.add_argument("--partition_file", default=None, type=str)
     ap.add_argument("--diag_lambda", default=0.0, type=float)
     ap.add_argument("--hidden_dim", default=256, type=int)
@@ -113,6 +148,12 @@ def load_partition(path: str) -> torch.Tensor:
     return torch.from_numpy(part.astype(np.int64))
 
 
+def partition_report(info) -> str:
+    """One line on a refinement (modules.cluster.refine_partition's info): the starting cut, the final cut, the rounds used."""
+    return (f"Partition: label propagation, cut {info['cuts'][0]} -> {info['cuts'][info['round']]} "
+            f"(round {info['round']} of {len(info['moved'])} run; largest cluster {info['max_size']}, cap {info['cap']})")
+
+
 def build_model(F: int, hidden_dim: int, C: int, num_layers: int, dropout: float, diag_lambda: float, device) -> ClusterGCN:
     return ClusterGCN(F, hidden_dims=[hidden_dim] * (num_layers - 1) + [C], dropout=dropout, diag_lambda=diag_lambda).to(device)
 
@@ -127,8 +168,13 @@ def run(args, device=None, log=print) -> float:
     x, y = data.x.to(device).contiguous(), data.y.to(device)
     train_mask, val_mask, test_mask = (m.to(device) for m in (data.train_mask, data.val_mask, data.test_mask))
     model = build_model(x.shape[1], args.hidden_dim, data.num_classes, args.num_layers, args.dropout, args.diag_lambda, device)
-    part = load_partition(args.partition_file) if args.partition == "file" else None
-    cd = ClusterData(g, args.num_parts, part=part, method=args.partition if part is None else "random", seed=args.seed)
+    method, lp_rounds, lp_imbalance = parse_partition(args.partition)
+    part = load_partition(args.partition_file) if method == "file" else None
+    if method == "lp":
+        cd = ClusterData(g, args.num_parts, method="lp", seed=args.seed, lp_start="random", lp_rounds=lp_rounds, lp_imbalance=lp_imbalance)
+        log(partition_report(cd.lp_info))
+    else:
+        cd = ClusterData(g, args.num_parts, part=part, method=method if part is None else "random", seed=args.seed)
     tr = ClusterTrainer(cd, x, y, train_mask, model, torch.optim.Adam(model.parameters(), lr=args.lr), batch_size=args.batch_size,
                         seed=args.seed)
     val = 0.0

@@ -16,8 +16,14 @@ A batch (ClusterLoader.batch) has
   e_id           int64 [e]: each entry's position in the graph's col.
 batch() reads two counts on the host (n and e): this is the eager form.
 
-A graph partitioner of METIS quality is not built: `part=` takes an assignment computed elsewhere; "random" and "range" are the two
-built-in cuts.
+The partition.  "random" and "range" are the two graph-free cuts (make_partition).  method="lp" follows the graph: it refines a
+balanced start — random or range, or a given `part=` — by size-constrained synchronous label propagation on the kernels of
+csrc/partition_kernels.hip (refine_partition; the rule is in include/grapes_hip.h, integers only, bit-reproducible).  Every node
+proposes the commonest label among its neighbours, a cluster admits the proposers with the largest gain up to `cap`, and the
+assignment of the round with the smallest cut is kept, so the result is never worse than the start.  Its limit: once clusters sit
+at `cap` the rule stalls — on a planted graph it stops at about twice the planted cut.  Not built: a partitioner of METIS quality
+(multilevel coarsening), a swap or rebalancing phase that would get past that stall, edge or node weights; `part=` still takes an
+assignment computed elsewhere.
 """
 from __future__ import annotations
 
@@ -42,6 +48,8 @@ def make_partition(num_nodes: int, num_parts: int, method: str = "random", seed:
     N, P = int(num_nodes), int(num_parts)
     if N < 1 or not 1 <= P <= N:
         raise ValueError(f"ClusterData: num_parts is 1 .. num_nodes ({N}), not {num_parts}")
+    if method == "lp":
+        raise ValueError("make_partition: method 'lp' refines an assignment over a graph: ClusterData(graph, num_parts, method='lp')")
     if method not in METHODS:
         raise ValueError(f"ClusterData: method {method!r} is not built (built: {', '.join(METHODS)}; part= takes any other assignment)")
     pos = torch.arange(N, dtype=torch.int64) * P // N
@@ -77,27 +85,94 @@ def partition_tables(part, num_parts: int):
     return perm.to(torch.int32).contiguous(), partptr.to(torch.int32).contiguous(), where.contiguous()
 
 
-class ClusterData:
-    """ClusterData(data_or_graph, num_parts, part=None, method="random" | "range", seed=None).  data_or_graph: a DeviceGraph, or a
-    data object as the GraphSAINT samplers take.  part: the cluster of every node computed elsewhere (METIS offline, say) — it wins
-    over method; seed: "random"'s (None: from torch's generator).  Built once with torch ops: perm, partptr, where
-    (partition_tables), the clusters' sizes and their work-item counts (the sum over a cluster's rows of ceil(deg / 64), which bounds
-    the items of any batch)."""
+def default_cap(num_nodes: int, num_parts: int, imbalance: float = 0.1) -> int:
+    """ceil(N / P) + floor(imbalance N / P), in integers: imbalance is taken as the nearest fraction with a denominator up to 10^6."""
+    from fractions import Fraction
+    N, P = int(num_nodes), int(num_parts)
+    if not imbalance >= 0:
+        raise ValueError("refine_partition: imbalance is at least 0")
+    f = Fraction(imbalance).limit_denominator(10 ** 6)
+    return -(-N // P) + (f.numerator * N) // (f.denominator * P)
 
-    def __init__(self, data_or_graph, num_parts: int, part=None, method: str = "random", seed: Optional[int] = None):
+
+def refine_partition(graph, part, num_parts: int, rounds: int = 30, imbalance: float = 0.1, cap: Optional[int] = None):
+    """(part int32 [N] on the device, info): `part` refined over the DeviceGraph `graph` by at most `rounds` rounds of the
+    size-constrained synchronous label propagation written in include/grapes_hip.h (ops.partition_propose / _admit / _cut).  cap: the
+    largest size a cluster may reach — default ceil(N / P) + floor(imbalance N / P); one below the start's largest cluster is a
+    ValueError.  The cut is evaluated for the start and after every round, and the assignment of the earliest round with the
+    smallest cut is returned; a round that moves nothing ends the run.  One host read per round: the eager form of a one-time
+    preprocessing step.  info: cuts (the start's first, then one per round that moved a node), moved (one per round run), round (the
+    chosen one; 0 = the start), max_size (the largest cluster of the returned assignment) and cap."""
+    g = graph
+    N, P, dev = g.num_nodes, int(num_parts), g.device
+    if not 1 <= P <= N:
+        raise ValueError(f"refine_partition: num_parts is 1 .. num_nodes ({N}), not {num_parts}")
+    if g.nnz >= 2 ** 31:
+        raise ValueError("refine_partition: a graph with 2^31 or more entries is not built")
+    if not torch.is_tensor(part) or part.numel() != N or part.is_floating_point() or part.dtype == torch.bool:
+        raise ValueError("refine_partition: part is an integer tensor with one cluster id per node")
+    if int(rounds) < 0:
+        raise ValueError("refine_partition: rounds is at least 0")
+    part64 = part.to(dev).reshape(-1).to(torch.int64)
+    if int(part64.min()) < 0 or int(part64.max()) >= P:
+        raise ValueError(f"refine_partition: part holds a cluster id outside [0, {P})")
+    size = torch.bincount(part64, minlength=P).to(torch.int32)
+    cap = default_cap(N, P, imbalance) if cap is None else int(cap)
+    if cap < int(size.max()) or cap >= 2 ** 31:
+        raise ValueError(f"refine_partition: cap {cap} is below the start's largest cluster ({int(size.max())}), or not below 2^31")
+    cur = part64.to(torch.int32).contiguous()
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    want, gain = torch.empty_like(cur), torch.empty_like(cur)
+    moved, cut = torch.empty(1, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int64, device=dev)
+
+    def cut_now() -> int:
+        ops.partition_cut(g.rowptr, g.col, N, cur, P, status=status, out=cut)
+        return int(cut.item())
+
+    cuts, moves, best, best_round = [cut_now()], [], cur.clone(), 0
+    raise_on_status(status, "refine_partition")
+    for r in range(1, int(rounds) + 1):
+        ops.partition_propose(g.rowptr, g.col, N, cur, P, status=status, out=(want, gain))
+        ops.partition_admit(want, gain, cur, size, cap, status=status, moved=moved)
+        moves.append(int(moved.item()))                              # (the round's host read)
+        if moves[-1] == 0:
+            break
+        cuts.append(cut_now())
+        if cuts[-1] < cuts[best_round]:
+            best, best_round = cur.clone(), r
+    raise_on_status(status, "refine_partition")
+    info = dict(cuts=cuts, moved=moves, round=best_round, max_size=int(torch.bincount(best.to(torch.int64), minlength=P).max()), cap=cap)
+    return best, info
+
+
+class ClusterData:
+    """ClusterData(data_or_graph, num_parts, part=None, method="random" | "range" | "lp", seed=None, lp_start="random", lp_rounds=30,
+    lp_imbalance=0.1).  data_or_graph: a DeviceGraph, or a data object as the GraphSAINT samplers take.  part: the cluster of every
+    node computed elsewhere (METIS offline, say) — it wins over method "random" / "range"; seed: "random"'s (None: from torch's
+    generator).  method="lp": the start — make_partition(lp_start), or the given part — is refined by refine_partition(rounds =
+    lp_rounds, imbalance = lp_imbalance) and its info kept as lp_info (None otherwise).  Built once with torch ops: perm, partptr,
+    where (partition_tables), the clusters' sizes and their work-item counts (the sum over a cluster's rows of ceil(deg / 64), which
+    bounds the items of any batch)."""
+
+    def __init__(self, data_or_graph, num_parts: int, part=None, method: str = "random", seed: Optional[int] = None,
+                 lp_start: str = "random", lp_rounds: int = 30, lp_imbalance: float = 0.1):
         self.graph, self.data = _graph_of(data_or_graph)
         g = self.graph
         if g.nnz >= 2 ** 31:
             raise ValueError("cluster batches over a graph with 2^31 or more entries are not built: the batch's edge offsets are 32-bit")
         N, self.num_parts = g.num_nodes, int(num_parts)
+        lp = method == "lp"
         if part is None:
-            part = make_partition(N, self.num_parts, method, seed)
+            part = make_partition(N, self.num_parts, lp_start if lp else method, seed)
         elif not torch.is_tensor(part) or part.numel() != N:
             raise ValueError("ClusterData: part holds one cluster id per node")
         if not 1 <= self.num_parts <= N:
             raise ValueError(f"ClusterData: num_parts is 1 .. num_nodes ({N}), not {num_parts}")
         if ops.csr_symmetric_check(g.rowptr, g.col, N) & 2:
             raise GrapesHipError("ClusterData: a column id is outside [0, num_nodes)")
+        self.lp_info = None
+        if lp:
+            part, self.lp_info = refine_partition(g, part, self.num_parts, rounds=lp_rounds, imbalance=lp_imbalance)
         self.perm, self.partptr, self.where = partition_tables(part.to(g.device).reshape(-1), self.num_parts)
         self.part = self.where[:, 0].contiguous()
         self.sizes = (self.partptr[1:] - self.partptr[:-1]).to(torch.int64)

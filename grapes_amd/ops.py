@@ -3252,6 +3252,71 @@ def cluster_batch(rowptr, col, num_nodes: int, perm, partptr, where, clusters, s
     return cptr, node_idx, rowptr_l, ei, e_id, d_n, d_e
 
 
+# the graph partitioner: size-constrained synchronous label propagation (grapes_hip.h, csrc/partition_kernels.hip)
+PARTITION_LDS_ROW = 2048                 # rows of 65 .. this many entries count in an LDS table; longer ones in slabs of the workspace
+
+
+def _partition_graph(rowptr, col, num_nodes: int, part, num_parts: int, status, who: str):
+    _chk(rowptr, _i64, "rowptr")
+    _chk(col, _i32, "col")
+    _chk(part, _i32, "part")
+    _chk(status, _i32, "status", True)
+    N, P = int(num_nodes), int(num_parts)
+    if N < 1 or not 1 <= P <= N or rowptr.numel() != N + 1 or part.numel() != N:
+        raise ValueError(f"{who}: rowptr holds N + 1 values, part N, and num_parts is 1 .. N")
+    if col.numel() >= 2 ** 31:
+        raise ValueError(f"{who}: a graph with 2^31 or more entries is not built")
+    return N, P
+
+
+def partition_propose(rowptr, col, num_nodes: int, part, num_parts: int, status=None, out=None):
+    """(want int32 [N], gain int32 [N]) of grapes_partition_propose: the proposal of every node under the label-propagation rule of
+    grapes_hip.h from part int32 [N] — want[v] = -1 and gain[v] = 0 for a node that stays.  out: the two tensors to write."""
+    N, P = _partition_graph(rowptr, col, num_nodes, part, num_parts, status, "partition_propose")
+    dev = part.device
+    want, gain = out if out is not None else (torch.empty(N, dtype=_i32, device=dev), torch.empty(N, dtype=_i32, device=dev))
+    _chk(want, _i32, "want")
+    _chk(gain, _i32, "gain")
+    if want.numel() != N or gain.numel() != N:
+        raise ValueError("partition_propose: want and gain hold N values")
+    ws = _ws(lib().grapes_partition_propose_workspace_bytes(N, P), dev)
+    if col.numel() == 0:
+        col = ws                                                     # (a graph without an entry: any address, never read)
+    _lib.check(lib().grapes_partition_propose(_p(rowptr), _p(col), N, _p(part), P, _p(want), _p(gain), _p(ws), _p(status), _stream()),
+               "partition_propose")
+    return want, gain
+
+
+def partition_admit(want, gain, part, size, cap: int, status=None, moved=None):
+    """grapes_partition_admit: admits, per destination, the cap - size proposers with the smallest keys and moves them — part int32 [N]
+    and size int32 [P] are updated in place.  Returns moved int32 [1]."""
+    for t, name in ((want, "want"), (gain, "gain"), (part, "part"), (size, "size")):
+        _chk(t, _i32, name)
+    _chk(status, _i32, "status", True)
+    N, P, dev = part.numel(), size.numel(), part.device
+    if N < 1 or not 1 <= P <= N or want.numel() != N or gain.numel() != N or not 0 <= int(cap) < 2 ** 31:
+        raise ValueError("partition_admit: want, gain and part hold N values, size 1 .. N, and cap is 0 .. 2^31 - 1")
+    moved = torch.empty(1, dtype=_i32, device=dev) if moved is None else moved
+    _chk(moved, _i32, "moved")
+    ws = _ws(lib().grapes_partition_admit_workspace_bytes(N, P), dev)
+    _lib.check(lib().grapes_partition_admit(_p(want), _p(gain), N, P, _p(part), _p(size), int(cap), _p(moved), _p(ws), _p(status),
+                                            _stream()), "partition_admit")
+    return moved
+
+
+def partition_cut(rowptr, col, num_nodes: int, part, num_parts: int, status=None, out=None):
+    """int64 [1]: the stored entries (v, u) with u != v and part[v] != part[u] (grapes_partition_cut)."""
+    N, P = _partition_graph(rowptr, col, num_nodes, part, num_parts, status, "partition_cut")
+    dev = part.device
+    cut = torch.empty(1, dtype=_i64, device=dev) if out is None else out
+    _chk(cut, _i64, "cut")
+    ws = _ws(lib().grapes_partition_cut_workspace_bytes(N), dev)
+    if col.numel() == 0:
+        col = ws
+    _lib.check(lib().grapes_partition_cut(_p(rowptr), _p(col), N, _p(part), P, _p(cut), _p(ws), _p(status), _stream()), "partition_cut")
+    return cut
+
+
 def cluster_aggregate_fwd(src, prep: PreparedGraph, diag_lambda: float = 0.0, add=None, bias=None, relu: bool = False, out=None,
                           copy_out=None, long_rows: Optional[bool] = None):
     """out[i] = act(s_i (sum_{j -> i} src[j] + (1 + diag_lambda) src[i]) + add[i] + bias) over prep's loop-free by-target CSR,

@@ -67,7 +67,8 @@ extern "C" {
  * grapes_sage_aggregate_fwd / _bwd, grapes_sage_aggregate_workspace_bytes; VR-GCN — grapes_vrgcn_aggregate_fwd / _bwd,
  * grapes_vrgcn_aggregate_workspace_bytes, grapes_vrgcn_long_row; LABOR — grapes_labor_sample_layer(_workspace_bytes),
  * grapes_labor_importance(_workspace_bytes); ShaDow-GNN — grapes_shadow_sample(_workspace_bytes), grapes_segment_mean_fwd / _bwd;
- * Cluster-GCN — grapes_cluster_batch(_workspace_bytes), grapes_cluster_aggregate_fwd / _bwd, grapes_cluster_aggregate_workspace_bytes. */
+ * Cluster-GCN — grapes_cluster_batch(_workspace_bytes), grapes_cluster_aggregate_fwd / _bwd, grapes_cluster_aggregate_workspace_bytes; its graph partitioner —
+ * grapes_partition_propose, grapes_partition_admit, grapes_partition_cut (+ _workspace_bytes each). */
 #define GRAPES_ABI_VERSION 303
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1716,6 +1717,38 @@ int grapes_cluster_batch(const int64_t* rowptr, const int32_t* col, int32_t num_
 size_t grapes_cluster_aggregate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f);
 int grapes_cluster_aggregate_fwd(const float* src, int64_t ld_src, const float* add, int64_t ld_add, const float* bias, const int32_t* rowptr_t, const int32_t* csr_src, float diag_lambda, int32_t relu, float* out, int64_t ld_out, float* copy_out, int64_t ld_copy, int32_t n, const int32_t* d_n, int32_t f, const int32_t* long_items, const int32_t* d_n_items, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
 int grapes_cluster_aggregate_bwd(const float* dout, int64_t ld_dout, const float* relu_out, int64_t ld_relu, const int32_t* rowptr_t, const int32_t* rowptr_s, const int32_t* csr_dst, float diag_lambda, const float* add, int64_t ld_add, float* dsrc, int64_t ld_dsrc, float* dadd, int64_t ld_dadd, float* dbias, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ the graph partitioner of Cluster-GCN (csrc/partition_kernels.hip)
+ * Size-constrained SYNCHRONOUS label propagation that refines a starting assignment.  Integers only, bit-reproducible on a CPU
+ * (tests/partition_oracle.py).  The rule, for the CSR (rowptr int64[N + 1], col int32, fewer than 2^31 entries), P clusters, part
+ * int32[N] in [0, P), cap = the largest size a cluster may reach; one round is a proposal and an admission:
+ *   propose  every node v, every round, from part as it stood at the start of the round: count the labels part[u] over the stored
+ *            entries u of row v with u != v (a duplicate entry counts once each).  cur = part[v], m = the largest count.  v stays when
+ *            the row has no such entry or count[cur] == m: want[v] = -1, gain[v] = 0.  Otherwise want[v] = the smallest label among
+ *            those with count m and gain[v] = m - count[cur] >= 1.
+ *   admit    size[c] = the size of c at the start of the round, free[c] = max(cap - size[c], 0): nodes that leave in this round are
+ *            not credited, so no cluster ever exceeds cap.  Among the proposers to c, the free[c] with the smallest 64-bit key
+ *            ((0x7fffffff - gain) << 32) | v are admitted — the larger gain first, then the smaller node id; keys are unique, so the
+ *            admitted set does not depend on the order in which the proposers were gathered.  An admitted v takes part[v] = want[v];
+ *            size is updated at both ends; *moved = the nodes admitted.
+ *   cut      the stored entries (v, u) with u != v and part[v] != part[u], an exact int64.
+ * The driver (modules/cluster.py: refine_partition) evaluates the cut of the start and after every round, returns the assignment of
+ * the earliest round with the smallest cut — synchronous propagation can oscillate; the result is never worse than the start — and
+ * stops when a round moves nothing.  Once clusters sit at cap the rule stalls: there is no swap or rebalancing phase.
+ *   status   a column outside [0, N) or a label outside [0, P) ORs GRAPES_STATUS_BAD_INDEX and the entry is dropped; a node whose own
+ *            label is outside [0, P) ORs it and stays (propose), counts nothing (cut).  grapes_partition_admit ORs it for a proposal
+ *            with want >= P, gain < 1 or such a label, and ignores the proposal.
+ * grapes_partition_propose: rows of at most 64 entries on one wavefront in registers; rows of 65 .. 2048 entries by a workgroup with an
+ * LDS table keyed by label; longer rows by 16 workgroups of 1024 threads over P-sized slabs of the workspace.  grapes_partition_admit:
+ * histogram, one-workgroup scan, scatter of the keys, the limit of every destination (a fuller bucket by an 8-bit radix select over its
+ * keys), apply; part and size are updated in place.  grapes_partition_cut: one pass, 64-bit integer sums.  No floating point; integer
+ * atomics only; two runs give the same bits.  Workspaces: the _workspace_bytes companions; 8-byte aligned. */
+size_t grapes_partition_propose_workspace_bytes(int32_t num_nodes, int32_t num_parts);
+int grapes_partition_propose(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* part, int32_t num_parts, int32_t* want, int32_t* gain, void* workspace, int32_t* status, grapes_stream_t stream);
+size_t grapes_partition_admit_workspace_bytes(int32_t num_nodes, int32_t num_parts);
+int grapes_partition_admit(const int32_t* want, const int32_t* gain, int32_t num_nodes, int32_t num_parts, int32_t* part, int32_t* size, int32_t cap, int32_t* moved, void* workspace, int32_t* status, grapes_stream_t stream);
+size_t grapes_partition_cut_workspace_bytes(int32_t num_nodes);
+int grapes_partition_cut(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* part, int32_t num_parts, int64_t* cut, void* workspace, int32_t* status, grapes_stream_t stream);
 
 #ifdef GRAPES_DIAG
 /* ------------------------------------------------------------------ pre-split feature planes (round 4; DIAGNOSTIC BUILD ONLY:
