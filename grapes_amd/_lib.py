@@ -111,6 +111,8 @@ SIGNATURES = {
     # ShaDow-GNN: the per-root ego-net sampler and the segment mean of its readout
     "grapes_shadow_sample_workspace_bytes": (SZ, [I32, I32, I32]),
     "grapes_shadow_sample": (I32, [P, P, I32, P, I32, P, I32, I32, P, U64, U64, P, I32, I32, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "grapes_shadow_ppr_sample_workspace_bytes": (SZ, [I32, I32]),
+    "grapes_shadow_ppr_sample": (I32, [P, P, I32, P, I32, P, I32, U32, U32, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "grapes_segment_mean_fwd": (I32, [P, P, I32, I32, I32, P, P, P]),
     "grapes_segment_mean_bwd": (I32, [P, P, I32, I32, I32, P, P, P]),
     # Cluster-GCN: the cluster-union batch and ClusterGCNConv's propagation

@@ -21,6 +21,9 @@
 // Integer code only, no float, no global atomic beyond the status OR, no kernel waits on another workgroup: the outputs do not
 // depend on scheduling and two runs give the same bits.
 //
+// The sort / count / staging half of shadow_build_k is shadow_stage, a __device__ function: the PPR scopes further down
+// (grapes_shadow_ppr_sample: shadow_ppr_build_k, then the same scan and write) build their member list another way and enter it too.
+//
 // The segment mean at the end of the file is the model's readout over an ego-net's rows (grapes_segment_mean_fwd / _bwd).
 #include "philox.h"
 #include "row_list.h"
@@ -79,6 +82,82 @@ __device__ __forceinline__ void shadow_rows(const int64_t* __restrict__ rowptr, 
 __device__ __forceinline__ int shadow_rank(const int* set, int n, int c) {
     const int i = lower_bound<int, int, int>(set, n, c);
     return (i < n && set[i] == c) ? i : -1;
+}
+
+// The second half of a build kernel, shared by shadow_build_k and shadow_ppr_build_k: the member list nodes[0 .. n) of root b (any order,
+// n <= C <= SHADOW_MAX_NODES, in LDS, complete and behind a barrier) -> the sorted set, the induced entries counted per member, and
+// both in the [B, C] staging area with nb[b] and eb[b].  The caller hands over its LDS: nodes and cnt of SHADOW_MAX_NODES ints, longs
+// (the list of long member rows; *n_long = 0 on entry) SHADOW_MAX_NODES ints, ra / rdeg of SHADOW_MAX_NODES entries, scan_lds of 17
+// ints.  `bad`: the thread met a column outside [0, N) before.  Every thread of the workgroup calls it; nodes stays sorted in LDS.
+__device__ __forceinline__ void shadow_stage(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N, int b, int C, int n,
+                                             int* nodes, int* cnt, int* longs, int64_t* ra, int* rdeg, int* scan_lds, int* n_long,
+                                             int32_t* __restrict__ set_out, int32_t* __restrict__ cnt_out, int32_t* __restrict__ nb,
+                                             int32_t* __restrict__ eb, int32_t* status, bool bad) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    // ---- the sorted set: one bitonic sort of the list, padded to a power of two
+    int P = 1;
+    while (P < n) P <<= 1;
+    for (int i = n + tid; i < P; i += SHADOW_THREADS) nodes[i] = 0x7fffffff;
+    for (int i = tid; i < n; i += SHADOW_THREADS) cnt[i] = 0;
+    __syncthreads();
+    for (int kk = 2; kk <= P; kk <<= 1) {
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += SHADOW_THREADS) {
+                const int x = i ^ j;
+                if (x > i) {
+                    const int u = nodes[i], w = nodes[x];
+                    if ((u > w) == ((i & kk) == 0)) { nodes[i] = w; nodes[x] = u; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < n; i += SHADOW_THREADS) set_out[(size_t)b * C + i] = nodes[i];
+
+    // ---- the induced entries of every member: a wavefront per short row
+    shadow_rows(rowptr, nodes, 0, n, ra, rdeg);
+    __syncthreads();
+    for (int i = wid; i < n; i += SHADOW_WAVES) {
+        const int64_t a = ra[i];
+        const long long deg = rdeg[i];
+        if (deg > SHADOW_LONG_ROW) {
+            if (lane == 0) longs[atomicAdd(n_long, 1)] = i;
+            continue;
+        }
+        int c = 0;
+        for (long long t0 = 0; t0 < deg; t0 += 64) {
+            const long long t = t0 + lane;
+            const int cj = t < deg ? col[a + t] : -1;
+            const bool valid = (unsigned)cj < (unsigned)N;
+            if (t < deg && !valid) bad = true;
+            c += __popcll(__ballot(valid && shadow_rank(nodes, n, cj) >= 0));
+        }
+        if (lane == 0) cnt[i] = c;
+    }
+    __syncthreads();
+    // the long rows, each by the whole workgroup (their order in the list changes nothing: a row's count is its own)
+    const int nl = *n_long;
+    for (int q = 0; q < nl; ++q) {
+        const int i = longs[q];
+        const int64_t a = ra[i];
+        const long long deg = rdeg[i];
+        int c = 0;
+        for (long long t0 = 0; t0 < deg; t0 += SHADOW_THREADS) {
+            const long long t = t0 + tid;
+            const int cj = t < deg ? col[a + t] : -1;
+            const bool valid = (unsigned)cj < (unsigned)N;
+            if (t < deg && !valid) bad = true;
+            c += __popcll(__ballot(valid && shadow_rank(nodes, n, cj) >= 0));
+        }
+        if (lane == 0) atomicAdd(&cnt[i], c);
+    }
+    __syncthreads();
+    int s = 0;
+    for (int i = tid; i < n; i += SHADOW_THREADS) { const int c = cnt[i]; cnt_out[(size_t)b * C + i] = c; s += c; }
+    int total;
+    block_excl_scan(s, scan_lds, &total);
+    if (tid == 0) { nb[b] = n; eb[b] = total; }
+    if (bad && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
 }
 
 __global__ __launch_bounds__(SHADOW_THREADS) void shadow_build_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N,
@@ -173,71 +252,7 @@ __global__ __launch_bounds__(SHADOW_THREADS) void shadow_build_k(const int64_t* 
     int n = n_nodes < SHADOW_MAX_NODES ? n_nodes : SHADOW_MAX_NODES;
     n = n < C ? n : C;
 
-    // ---- the sorted set: one bitonic sort of the list, padded to a power of two
-    int P = 1;
-    while (P < n) P <<= 1;
-    for (int i = n + tid; i < P; i += SHADOW_THREADS) nodes[i] = 0x7fffffff;
-    for (int i = tid; i < n; i += SHADOW_THREADS) cnt[i] = 0;
-    __syncthreads();
-    for (int kk = 2; kk <= P; kk <<= 1) {
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < P; i += SHADOW_THREADS) {
-                const int x = i ^ j;
-                if (x > i) {
-                    const int u = nodes[i], w = nodes[x];
-                    if ((u > w) == ((i & kk) == 0)) { nodes[i] = w; nodes[x] = u; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < n; i += SHADOW_THREADS) set_out[(size_t)b * C + i] = nodes[i];
-
-    // ---- the induced entries of every member: a wavefront per short row
-    int* longs = hash;
-    shadow_rows(rowptr, nodes, 0, n, ra, rdeg);
-    __syncthreads();
-    for (int i = wid; i < n; i += SHADOW_WAVES) {
-        const int64_t a = ra[i];
-        const long long deg = rdeg[i];
-        if (deg > SHADOW_LONG_ROW) {
-            if (lane == 0) longs[atomicAdd(&n_long, 1)] = i;
-            continue;
-        }
-        int c = 0;
-        for (long long t0 = 0; t0 < deg; t0 += 64) {
-            const long long t = t0 + lane;
-            const int cj = t < deg ? col[a + t] : -1;
-            const bool valid = (unsigned)cj < (unsigned)N;
-            if (t < deg && !valid) bad = true;
-            c += __popcll(__ballot(valid && shadow_rank(nodes, n, cj) >= 0));
-        }
-        if (lane == 0) cnt[i] = c;
-    }
-    __syncthreads();
-    // the long rows, each by the whole workgroup (their order in the list changes nothing: a row's count is its own)
-    const int nl = n_long;
-    for (int q = 0; q < nl; ++q) {
-        const int i = longs[q];
-        const int64_t a = ra[i];
-        const long long deg = rdeg[i];
-        int c = 0;
-        for (long long t0 = 0; t0 < deg; t0 += SHADOW_THREADS) {
-            const long long t = t0 + tid;
-            const int cj = t < deg ? col[a + t] : -1;
-            const bool valid = (unsigned)cj < (unsigned)N;
-            if (t < deg && !valid) bad = true;
-            c += __popcll(__ballot(valid && shadow_rank(nodes, n, cj) >= 0));
-        }
-        if (lane == 0) atomicAdd(&cnt[i], c);
-    }
-    __syncthreads();
-    int s = 0;
-    for (int i = tid; i < n; i += SHADOW_THREADS) { const int c = cnt[i]; cnt_out[(size_t)b * C + i] = c; s += c; }
-    int total;
-    block_excl_scan(s, scan_lds, &total);
-    if (tid == 0) { nb[b] = n; eb[b] = total; }
-    if (bad && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+    shadow_stage(rowptr, col, N, b, C, n, nodes, cnt, hash, ra, rdeg, scan_lds, &n_long, set_out, cnt_out, nb, eb, status, bad);
 }
 
 // ONE workgroup.  ptr[b] = min(nodes of the ego-nets before b, n_cap), eoff[b] the same for the entries and e_cap; ptr[m], eoff[m],
@@ -271,7 +286,11 @@ __global__ __launch_bounds__(LIST_SCAN_THREADS) void shadow_scan_k(const int32_t
 }
 
 // A workgroup per root: its rows of n_id / batch, root_n_id, and its edges behind eoff[b] — local row ascending, within a row in the
-// CSR's order.  Nothing is written at or past n_cap / e_cap.
+// CSR's order.  Nothing is written at or past n_cap / e_cap.  score_in (optional): the staged [B, C] scores of the members, copied
+// to score beside n_id; with NULL nothing more is read or written.  SCORES = false compiles the copy out for the k-hop
+// sampler's launch, which never has scores: a run-time NULL test there measured 0.8 - 1.2 us on its 175 us call
+// (profiles/shadow_ppr_bench.json, refactor_check).
+template <bool SCORES>
 __global__ __launch_bounds__(SHADOW_THREADS) void shadow_write_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N,
                                                                  const int32_t* __restrict__ roots, int C,
                                                                  const int32_t* __restrict__ set_in, const int32_t* __restrict__ cnt_in,
@@ -279,7 +298,8 @@ __global__ __launch_bounds__(SHADOW_THREADS) void shadow_write_k(const int64_t* 
                                                                  const int32_t* __restrict__ eoff, int n_cap, int e_cap,
                                                                  int32_t* __restrict__ n_id, int32_t* __restrict__ batch,
                                                                  int32_t* __restrict__ root_n_id, int32_t* __restrict__ edge_src,
-                                                                 int32_t* __restrict__ edge_dst, int64_t* __restrict__ e_id) {
+                                                                 int32_t* __restrict__ edge_dst, int64_t* __restrict__ e_id,
+                                                                 const uint32_t* __restrict__ score_in, uint32_t* __restrict__ score) {
     __shared__ int nodes[SHADOW_MAX_NODES];
     __shared__ int roff[SHADOW_MAX_NODES];
     __shared__ int longs[SHADOW_MAX_NODES];
@@ -315,6 +335,10 @@ __global__ __launch_bounds__(SHADOW_THREADS) void shadow_write_k(const int64_t* 
     __syncthreads();
     for (int i = tid; i < n; i += SHADOW_THREADS) {
         if (nbase + i < n_cap) { n_id[nbase + i] = nodes[i]; batch[nbase + i] = b; }
+    }
+    if (SCORES && score_in) {                                                   // (the PPR scopes: a member's staged score beside its id)
+        for (int i = tid; i < n; i += SHADOW_THREADS)
+            if (nbase + i < n_cap) score[nbase + i] = score_in[(size_t)b * C + i];
     }
     if (tid == 0) root_n_id[b] = nbase + shadow_rank(nodes, n, roots[b]);       // (the root is a member)
     if (ebase >= e_cap) return;                                                 // (workgroup-uniform) every slot is past the capacity
@@ -398,9 +422,294 @@ extern "C" int grapes_shadow_sample(const int64_t* rowptr, const int32_t* col, i
     hipLaunchKernelGGL(shadow_scan_k, dim3(1), dim3(LIST_SCAN_THREADS), 0, s, (const int32_t*)nb, (const int32_t*)eb, m, d_m, depth,
                        n_cap, e_cap, ptr, eoff, d_n, d_e, d_philox_offset, status);
     GRAPES_LAUNCH_CHECK();
-    hipLaunchKernelGGL(shadow_write_k, dim3(m), dim3(SHADOW_THREADS), 0, s, rowptr, col, num_nodes, roots, C, (const int32_t*)set,
+    hipLaunchKernelGGL(shadow_write_k<false>, dim3(m), dim3(SHADOW_THREADS), 0, s, rowptr, col, num_nodes, roots, C, (const int32_t*)set,
                        (const int32_t*)cnt, (const int32_t*)nb, (const int32_t*)ptr, (const int32_t*)eoff, n_cap, e_cap, n_id, batch,
-                       root_n_id, edge_src, edge_dst, e_id);
+                       root_n_id, edge_src, edge_dst, e_id, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------ the PPR scopes
+// grapes_shadow_ppr_sample: the scope of a root is the k best nodes of an approximate personalised PageRank from it, by synchronous
+// forward push in FIXED POINT (the rule in include/grapes_hip.h; tests/shadow_ppr_oracle.py reproduces it bit for bit).
+//   shadow_ppr_build_k   a workgroup per root, the touched table in LDS: an open-addressing hash of PPR_HASH = 8192 id slots with the
+//                    residual r beside it (the one array other nodes' pushes add into: integer LDS atomics), at most half full, so
+//                    a probe always ends; per TOUCHED INDEX (insertion order, at most PPR_T = 4096) the slot, the row start, the
+//                    degree and p — p is only ever written by its own node's push, so it needs no slot and no atomic.
+//                    A round is two dependent memory trips whatever the frontier's size: (1) every thread fetches the row pointers of
+//                    one newly touched node (degrees and row starts stay cached in LDS for the rest of the call); (2) after the
+//                    workgroup scan that counts the frontier and its entries — the three stops are workgroup-uniform decisions on
+//                    its totals — the frontier's entries are walked FLAT: the stop-2 rule bounds a round that runs to
+//                    sum deg <= PPR_T entries, so a thread takes at most PPR_PER = 4 of them, finds each one's frontier row by a
+//                    binary search of the rows' offsets in LDS, and requests its columns together.  A hub row is spread over the
+//                    workgroup like any other, so the push itself needs no long-row path (the induced-entry count in
+//                    shadow_stage keeps its own).  Then CAS to insert, add to r.
+//                    Selection: one 64-bit key per touched node, (2^32 - 1 - score) << 32 | id — ascending keys are score
+//                    descending, then id ascending; the root and zero scores get the largest key — over the dead row-start / degree
+//                    arrays, and ONE bitonic sort.  Bitonic and not a radix select: the sort is the network shadow_stage already
+//                    runs, has one path for every size, and is 78 LDS passes of 4 keys per thread at the most; a radix select over
+//                    64-bit keys is 8 histogram passes with LDS atomics plus a compaction that must still resolve the ties at the
+//                    k-th key by id.  (Neither has been timed against the other.)  The first k keys and the root enter
+//                    shadow_stage; each member's score is staged at its rank in the sorted set.
+//   shadow_scan_k / shadow_write_k as above (depth 0: there is no stream to advance); the write copies the staged scores.
+// Integer code only, no float, no global atomic beyond the status OR, no kernel waits on another workgroup.  Which lane wins a slot or
+// which touched index a node gets changes nothing: r and p are sums of integers, and the keys are distinct.
+#define PPR_T 4096                      // the touched-set capacity: part of the rule
+#define PPR_HASH 8192
+#define PPR_ONE (1u << 30)
+#define PPR_MAX_K (SHADOW_MAX_NODES - 1)
+#define PPR_MAX_ROUNDS 1024
+#define PPR_PER (PPR_T / SHADOW_THREADS)
+static_assert(PPR_T == PPR_PER * SHADOW_THREADS && PPR_HASH == 2 * PPR_T && PPR_T <= 65536, "a thread takes PPR_PER touched nodes; 16-bit lists");
+// one LDS block, carved by hand so that the selection's keys and the stage's arrays can lie over what is dead by then
+#define PPR_O_HKEY 0                               // int      [PPR_HASH]  ids; after the selection: shadow_stage's arrays
+#define PPR_O_HR (PPR_O_HKEY + 4 * PPR_HASH)       // uint32   [PPR_HASH]  r, by slot
+#define PPR_O_TRA (PPR_O_HR + 4 * PPR_HASH)        // uint32   [PPR_T]     row start (fewer than 2^31 entries)   } after the rounds: the
+#define PPR_O_TDEG (PPR_O_TRA + 4 * PPR_T)         // int      [PPR_T]     degree                                } PPR_T 64-bit keys
+#define PPR_O_TP (PPR_O_TDEG + 4 * PPR_T)          // uint32   [PPR_T]     p
+#define PPR_O_FR (PPR_O_TP + 4 * PPR_T)            // uint32   [PPR_T]     the frontier's snapshot of r
+#define PPR_O_TSLOT (PPR_O_FR + 4 * PPR_T)         // uint16   [PPR_T]     touched index -> slot
+#define PPR_O_FT (PPR_O_TSLOT + 2 * PPR_T)         // uint16   [PPR_T]     frontier position -> touched index
+#define PPR_O_FOFF (PPR_O_FT + 2 * PPR_T)          // uint16   [PPR_T]     frontier position -> its first entry in the flat walk
+#define PPR_LDS_BYTES (PPR_O_FOFF + 2 * PPR_T)     // 152 KiB of the CU's 160
+static_assert(PPR_O_TDEG == PPR_O_TRA + 4 * PPR_T && 8 * PPR_T == 2 * 4 * PPR_T, "the keys lie over tra and tdeg");
+static_assert(4 * PPR_HASH >= SHADOW_MAX_NODES * (4 + 4 + 4 + 8 + 4), "the stage's arrays lie over the id slots");
+
+// id -> its slot (-1: no free slot, which the rule's capacity check excludes); the lane that takes an empty slot appends the touched index
+__device__ __forceinline__ int ppr_insert(int* hkey, unsigned short* tslot, int* n_touched, int c) {
+    unsigned slot = ((unsigned)c * 0x9E3779B1u) >> 19;                          // 13 bits
+    for (int probe = 0; probe < PPR_HASH; ++probe) {
+        const int old = atomicCAS(&hkey[slot], SHADOW_EMPTY, c);
+        if (old == SHADOW_EMPTY) {
+            const int idx = atomicAdd(n_touched, 1);
+            if (idx < PPR_T) tslot[idx] = (unsigned short)slot;                  // (always: |S| + sum deg <= PPR_T before the round ran)
+            return (int)slot;
+        }
+        if (old == c) return (int)slot;
+        slot = (slot + 1) & (PPR_HASH - 1);
+    }
+    return -1;
+}
+
+__global__ __launch_bounds__(SHADOW_THREADS) void shadow_ppr_build_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                                     int N, const int32_t* __restrict__ roots, int m_host,
+                                                                     const int32_t* __restrict__ d_m, int k, uint32_t alpha_q,
+                                                                     uint32_t thr, int max_rounds, int C,
+                                                                     int32_t* __restrict__ set_out, int32_t* __restrict__ cnt_out,
+                                                                     uint32_t* __restrict__ score_out, int32_t* __restrict__ nb,
+                                                                     int32_t* __restrict__ eb, int32_t* __restrict__ rounds_out,
+                                                                     int32_t* __restrict__ stop_out, int32_t* status) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[PPR_LDS_BYTES];
+    __shared__ int scan_lds[51];
+    __shared__ int n_touched, n_long, n_valid;
+    __shared__ uint32_t root_score;
+    int* hkey = (int*)(lds + PPR_O_HKEY);
+    uint32_t* hr = (uint32_t*)(lds + PPR_O_HR);
+    uint32_t* tra = (uint32_t*)(lds + PPR_O_TRA);
+    int* tdeg = (int*)(lds + PPR_O_TDEG);
+    uint32_t* tp = (uint32_t*)(lds + PPR_O_TP);
+    uint32_t* fr = (uint32_t*)(lds + PPR_O_FR);
+    unsigned short* tslot = (unsigned short*)(lds + PPR_O_TSLOT);
+    unsigned short* ft = (unsigned short*)(lds + PPR_O_FT);
+    unsigned short* foff = (unsigned short*)(lds + PPR_O_FOFF);
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int live = eff_count(d_m, m_host);
+    const int root = b < live ? roots[b] : -1;
+    if ((unsigned)root >= (unsigned)N) {                                        // (workgroup-uniform) an empty ego-net
+        if (tid == 0) {
+            nb[b] = 0; eb[b] = 0;
+            if (rounds_out) rounds_out[b] = 0;
+            if (stop_out) stop_out[b] = 0;
+            if (b < live && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+        }
+        return;
+    }
+    for (int i = tid; i < PPR_HASH; i += SHADOW_THREADS) { hkey[i] = SHADOW_EMPTY; hr[i] = 0u; }
+    for (int i = tid; i < PPR_T; i += SHADOW_THREADS) tp[i] = 0u;
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned slot = ((unsigned)root * 0x9E3779B1u) >> 19;
+        hkey[slot] = root; hr[slot] = PPR_ONE; tslot[0] = (unsigned short)slot;    // touched index 0 is the root
+        n_touched = 1; n_long = 0; n_valid = 0;
+    }
+    __syncthreads();
+    bool bad = false;
+
+    // ---- the rounds
+    int known = 0, rounds = 0, stop = 0;
+    for (;;) {
+        const int nT = n_touched < PPR_T ? n_touched : PPR_T;
+        for (int t = known + tid; t < nT; t += SHADOW_THREADS) {                // one round trip for the newly touched nodes' row pointers
+            const int v = hkey[tslot[t]];
+            const int64_t a = rowptr[v], d = rowptr[v + 1] - a;
+            tra[t] = (uint32_t)a;
+            tdeg[t] = d < 0 ? 0 : (d > 0x7fffffffll ? 0x7fffffff : (int)d);
+        }
+        known = nT;
+        __syncthreads();
+        // F, |F| and sum deg: a thread looks at PPR_PER consecutive touched indices.  A degree counts as at most PPR_T + 1 in the sum:
+        // the sum then stays in an int, and "more than PPR_T" is decided as by the exact sum.
+        uint32_t rv[PPR_PER];
+        int dg[PPR_PER], c = 0, ds = 0, z = 0;
+#pragma unroll
+        for (int q = 0; q < PPR_PER; ++q) {
+            const int t = PPR_PER * tid + q;
+            rv[q] = 0u; dg[q] = 0;
+            if (t < nT) {
+                const uint32_t r = hr[tslot[t]];
+                const int deg = tdeg[t];
+                if (r > 0u && (unsigned long long)r >= (unsigned long long)thr * (unsigned long long)deg) {
+                    rv[q] = r; dg[q] = deg;
+                    ++c; ds += deg < PPR_T + 1 ? deg : PPR_T + 1;
+                }
+            }
+        }
+        int nF, E, zz;
+        block_excl_scan3(c, ds, z, scan_lds, &nF, &E, &zz);
+        if (nF == 0) { stop = 0; break; }                                       // (workgroup-uniform, all three)
+        if (rounds == max_rounds) { stop = 1; break; }
+        if (nT + E > PPR_T) { stop = 2; break; }
+        // the snapshot: (touched index, r, first entry) at the frontier position, and r = 0 (every deg <= PPR_T here: E is exact)
+#pragma unroll
+        for (int q = 0; q < PPR_PER; ++q) {
+            if (rv[q]) {
+                const int t = PPR_PER * tid + q;
+                ft[c] = (unsigned short)t; fr[c] = rv[q]; foff[c] = (unsigned short)ds;
+                hr[tslot[t]] = 0u;
+                ++c; ds += dg[q];
+            }
+        }
+        __syncthreads();
+        // p: a thread per frontier node (its own p: no atomic)
+        for (int f = tid; f < nF; f += SHADOW_THREADS) {
+            const int t = ft[f];
+            const uint32_t r = fr[f];
+            tp[t] += tdeg[t] == 0 ? r : (uint32_t)(((unsigned long long)r * alpha_q) >> 16);
+        }
+        // the push: the frontier's E <= PPR_T entries flat over the workgroup, a thread's columns requested together
+        int cj[PPR_PER];
+        uint32_t sh[PPR_PER];
+#pragma unroll
+        for (int q = 0; q < PPR_PER; ++q) {
+            const int e = tid + q * SHADOW_THREADS;
+            cj[q] = 0; sh[q] = 0u;
+            if (e < E) {
+                int lo = 0, hi = nF;                                            // the last frontier position with foff <= e: empty rows
+                while (lo < hi) {                                               // share their successor's offset and are skipped
+                    const int mid = (lo + hi) >> 1;
+                    if ((int)foff[mid] <= e) lo = mid + 1; else hi = mid;
+                }
+                const int f = lo - 1, t = ft[f];
+                const uint32_t r = fr[f], keep = (uint32_t)(((unsigned long long)r * alpha_q) >> 16);
+                sh[q] = (r - keep) / (uint32_t)tdeg[t];
+                cj[q] = col[(size_t)tra[t] + (size_t)(e - (int)foff[f])];
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < PPR_PER; ++q) {
+            if (tid + q * SHADOW_THREADS < E) {
+                if ((unsigned)cj[q] < (unsigned)N) {
+                    const int slot = ppr_insert(hkey, tslot, &n_touched, cj[q]);
+                    if (slot >= 0) atomicAdd(&hr[slot], sh[q]);
+                } else {
+                    bad = true;                                                 // dropped: its share is lost
+                }
+            }
+        }
+        __syncthreads();
+        ++rounds;
+    }
+    // (every thread left the loop behind block_excl_scan3's last barrier: the tables are final and tra / tdeg are dead)
+
+    // ---- the selection: one key per touched node, sorted ascending
+    const int nT = n_touched < PPR_T ? n_touched : PPR_T;
+    unsigned long long* keys = (unsigned long long*)(lds + PPR_O_TRA);
+    int P = 1;
+    while (P < nT) P <<= 1;
+    for (int t = tid; t < P; t += SHADOW_THREADS) {
+        unsigned long long key = ~0ull;
+        if (t < nT) {
+            const int slot = tslot[t];
+            const uint32_t sc = tp[t] + (uint32_t)(((unsigned long long)hr[slot] * alpha_q) >> 16);
+            if (t == 0) root_score = sc;
+            else if (sc > 0u) key = ((unsigned long long)(0xffffffffu - sc) << 32) | (unsigned long long)(uint32_t)hkey[slot];
+        }
+        keys[t] = key;
+    }
+    __syncthreads();
+    for (int kk = 2; kk <= P; kk <<= 1) {
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < P; i += SHADOW_THREADS) {
+                const int x = i ^ j;
+                if (x > i) {
+                    const unsigned long long u = keys[i], w = keys[x];
+                    if ((u > w) == ((i & kk) == 0)) { keys[i] = w; keys[x] = u; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < P; i += SHADOW_THREADS)                               // the candidates are the keys in front of the first ~0
+        if (keys[i] != ~0ull && (i + 1 == P || keys[i + 1] == ~0ull)) n_valid = i + 1;
+    __syncthreads();
+    const int n_sel = n_valid < k ? n_valid : k, n = 1 + n_sel;
+
+    // ---- the members enter the shared stage, whose arrays lie over the id slots (dead: the keys carry the ids)
+    int* nodes = (int*)(lds + PPR_O_HKEY);
+    int* cnt = nodes + SHADOW_MAX_NODES;
+    int* longs = cnt + SHADOW_MAX_NODES;
+    int64_t* ra = (int64_t*)(longs + SHADOW_MAX_NODES);
+    int* rdeg = (int*)(ra + SHADOW_MAX_NODES);
+    for (int i = tid; i < n; i += SHADOW_THREADS) nodes[i] = i == 0 ? root : (int)(uint32_t)keys[i - 1];
+    __syncthreads();
+    shadow_stage(rowptr, col, N, b, C, n, nodes, cnt, longs, ra, rdeg, scan_lds, &n_long, set_out, cnt_out, nb, eb, status, bad);
+    // a member's score at its rank in the sorted set
+    for (int i = tid; i < n; i += SHADOW_THREADS) {
+        const int v = i == 0 ? root : (int)(uint32_t)keys[i - 1];
+        const uint32_t sc = i == 0 ? root_score : 0xffffffffu - (uint32_t)(keys[i - 1] >> 32);
+        const int rk = shadow_rank(nodes, n, v);
+        if (rk >= 0) score_out[(size_t)b * C + rk] = sc;
+    }
+    if (tid == 0) {
+        if (rounds_out) rounds_out[b] = rounds;
+        if (stop_out) stop_out[b] = stop;
+    }
+}
+
+// set int32[m * C] | cnt int32[m * C] | score uint32[m * C] | nb int32[m] | eb int32[m] | eoff int32[m + 1], C = k + 1
+extern "C" size_t grapes_shadow_ppr_sample_workspace_bytes(int32_t m, int32_t k) {
+    if (m < 1 || m > SHADOW_MAX_ROOTS || k < 1 || k > PPR_MAX_K) return 0;
+    return ((size_t)3 * m * (k + 1) + (size_t)3 * m + 1) * 4 + 16;
+}
+
+extern "C" int grapes_shadow_ppr_sample(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* roots, int32_t m,
+                                        const int32_t* d_m, int32_t k, uint32_t alpha_q, uint32_t thr, int32_t max_rounds,
+                                        int32_t n_cap, int32_t e_cap, int32_t* n_id, int32_t* ptr, int32_t* batch, int32_t* root_n_id,
+                                        int32_t* edge_src, int32_t* edge_dst, int64_t* e_id, uint32_t* score, int32_t* rounds,
+                                        int32_t* stop, int32_t* d_n, int32_t* d_e, void* workspace, int32_t* status,
+                                        grapes_stream_t stream) {
+    if (num_nodes <= 0 || m < 1 || m > SHADOW_MAX_ROOTS || k < 1 || k > PPR_MAX_K || n_cap <= 0 || e_cap <= 0) return GRAPES_EINVAL;
+    if (alpha_q < 1u || alpha_q > 65535u || thr < 1u || thr > PPR_ONE || max_rounds < 1 || max_rounds > PPR_MAX_ROUNDS) return GRAPES_EINVAL;
+    if (!rowptr || !col || !roots || !n_id || !ptr || !batch || !root_n_id || !edge_src || !edge_dst || !d_n || !d_e || !workspace)
+        return GRAPES_EINVAL;
+    if ((uintptr_t)workspace & 3) return GRAPES_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    const int C = k + 1;
+    int32_t* set = (int32_t*)workspace;
+    int32_t* cnt = set + (size_t)m * C;
+    uint32_t* sc = (uint32_t*)(cnt + (size_t)m * C);
+    int32_t* nb = (int32_t*)(sc + (size_t)m * C);
+    int32_t* eb = nb + m;
+    int32_t* eoff = eb + m;
+    hipLaunchKernelGGL(shadow_ppr_build_k, dim3(m), dim3(SHADOW_THREADS), 0, s, rowptr, col, num_nodes, roots, m, d_m, k, alpha_q, thr,
+                       max_rounds, C, set, cnt, sc, nb, eb, rounds, stop, status);
+    GRAPES_LAUNCH_CHECK();
+    hipLaunchKernelGGL(shadow_scan_k, dim3(1), dim3(LIST_SCAN_THREADS), 0, s, (const int32_t*)nb, (const int32_t*)eb, m, d_m, 0, n_cap,
+                       e_cap, ptr, eoff, d_n, d_e, (uint64_t*)nullptr, status);
+    GRAPES_LAUNCH_CHECK();
+    hipLaunchKernelGGL(shadow_write_k<true>, dim3(m), dim3(SHADOW_THREADS), 0, s, rowptr, col, num_nodes, roots, C, (const int32_t*)set,
+                       (const int32_t*)cnt, (const int32_t*)nb, (const int32_t*)ptr, (const int32_t*)eoff, n_cap, e_cap, n_id, batch,
+                       root_n_id, edge_src, edge_dst, e_id, score ? (const uint32_t*)sc : (const uint32_t*)nullptr, score);
     GRAPES_LAUNCH_CHECK();
     return 0;
 }

@@ -1,6 +1,6 @@
 """ShaDow-GNN [Zeng et al., NeurIPS 2021; PyG-recall: ShaDowKHopSampler(data, depth, num_neighbors) over torch_sparse's
-ego_k_hop_sample_adj, examples/shadow.py] on the gfx950 kernels of csrc/shadow_kernels.hip (ops.shadow_sample, ops.segment_mean_fwd /
-_bwd).  The paper is recalled, not read: the rule written in include/grapes_hip.h is the contract.
+ego_k_hop_sample_adj, examples/shadow.py] on the gfx950 kernels of csrc/shadow_kernels.hip (ops.shadow_sample, ops.shadow_ppr_sample,
+ops.segment_mean_fwd / _bwd).  The paper is recalled, not read: the rule written in include/grapes_hip.h is the contract.
 
 The method decouples the model's depth from its scope.  Every root gets its OWN small sampled ego-net: `depth` hops from the root,
 each expanding the nodes first reached at the hop before and keeping at most `num_neighbors` entries of an expanded row (Floyd's
@@ -17,6 +17,9 @@ A batch (ShaDowKHopSampler.sample) has
                  target row, then the CSR's order — one tensor, so that every layer of the model shares one cached preparation;
   e_id           int64 [e]: each entry's position in the graph's col.
 sample() reads two counts on the host (n and e): this is the eager form.
+
+ShaDowPPRSampler builds the same batch from the paper's other scope, the k best nodes of an approximate personalised PageRank from the
+root (ops.shadow_ppr_sample: forward push in fixed point, no random numbers), and adds score, rounds and stop to the namespace.
 
 ShaDow is the model: the project's SAGE or GCN as the body, the root's row (and the mean over its ego-net) as the readout, the
 project's Linear as the head.
@@ -94,6 +97,66 @@ class ShaDowKHopSampler:
     def check(self):
         """Reads the status word (synchronises); raises GrapesHipError("ego-net sampler: ...") on a node or edge overflow or a bad id,
         and clears it."""
+        raise_on_status(self.status, "ego-net sampler", hints={1: " (give the sampler a larger e_cap)", 2: " (give it a larger n_cap)"})
+
+
+class ShaDowPPRSampler:
+    """ShaDowPPRSampler(data_or_graph, k, alpha=0.25, eps=2**-14, max_rounds=32, n_cap=None, e_cap=None): ShaDow's other scope.  The
+    ego-net of a root is the root and the k best nodes of an approximate personalised PageRank from it — synchronous forward push in
+    fixed point (the rule of grapes_shadow_ppr_sample in include/grapes_hip.h) — and the subgraph induced on them.  alpha: the teleport
+    probability, taken as alpha_q = round(alpha 2^16) in 1 .. 65535; eps: the push threshold per stored entry (a node pushes while
+    r_v >= eps deg(v)), taken as thr = max(1, round(eps 2^30)) in 1 .. 2^30; max_rounds: 1 .. 1024; k: 1 .. 1023.  Values outside
+    are refused.  There is no seed and no offset: the scope is a function of the graph and the root.  n_cap / e_cap as
+    ShaDowKHopSampler's (n_cap defaults to B (k + 1)).  A batch is ShaDowKHopSampler's namespace and additionally carries score fp32
+    [n] (= the fixed-point score / 2^30: the integer rounded once to fp32, the division exact), rounds int32 [B] and stop int32 [B] (0: no node left to push, 1: max_rounds,
+    2: the next round could overflow the ops.SHADOW_PPR_TOUCHED touched nodes)."""
+
+    def __init__(self, data_or_graph, k: int, alpha: float = 0.25, eps: float = 2 ** -14, max_rounds: int = 32,
+                 n_cap: Optional[int] = None, e_cap: Optional[int] = None):
+        self.k, self.alpha, self.eps, self.max_rounds = int(k), float(alpha), float(eps), int(max_rounds)
+        if not (self.alpha == self.alpha and self.eps == self.eps and 0.0 < self.alpha < 1.0 and 0.0 < self.eps <= 1.0):
+            raise ValueError(f"ShaDowPPRSampler: alpha = {alpha} must lie inside (0, 1) and eps = {eps} inside (0, 1]")
+        self.alpha_q, self.thr = int(round(self.alpha * 2 ** 16)), max(1, int(round(self.eps * 2 ** 30)))
+        self.cap = ops.shadow_ppr_args(self.k, self.alpha_q, self.thr, self.max_rounds)
+        self.n_cap, self.e_cap = (None if n_cap is None else int(n_cap)), (None if e_cap is None else int(e_cap))
+        if (self.n_cap is not None and self.n_cap < 1) or (self.e_cap is not None and self.e_cap < 1):
+            raise ValueError("ShaDowPPRSampler: n_cap and e_cap are at least 1")
+        self.graph, self.data = _graph_of(data_or_graph)
+        g = self.graph
+        if g.nnz >= 2 ** 31:
+            raise ValueError("ego-net sampling over a graph with 2^31 or more entries is not built")
+        self.status = torch.zeros(1, dtype=torch.int32, device=g.device)
+        self._e_hint = _E_FLOOR
+        if ops.csr_symmetric_check(g.rowptr, g.col, g.num_nodes) & 2:
+            raise GrapesHipError("ShaDowPPRSampler: a column id is outside [0, num_nodes)")
+
+    def sample(self, roots) -> SimpleNamespace:
+        """roots: node ids (any integer tensor, at most ops.SHADOW_MAX_ROOTS; taken in the given order; a root listed twice gets two
+        identical ego-nets).  Returns the batch namespace described in the class docstring."""
+        g = self.graph
+        roots = as_targets(roots, g.device, type(self).__name__)
+        B = roots.numel()
+        if B > ops.SHADOW_MAX_ROOTS:
+            raise ValueError(f"ShaDowPPRSampler.sample: at most {ops.SHADOW_MAX_ROOTS} roots per batch")
+        ec = self.e_cap if self.e_cap is not None else self._e_hint
+        while True:
+            n_id, ptr, batch, root_n_id, ei, e_id, d_n, d_e, score, rounds, stop = ops.shadow_ppr_sample(
+                g.rowptr, g.col, g.num_nodes, roots, self.k, self.alpha_q, self.thr, self.max_rounds, n_cap=self.n_cap, e_cap=ec,
+                status=self.status)
+            n, e = int(d_n.item()), int(d_e.item())                  # the batch's rows and entries (host reads)
+            if self.e_cap is not None or e < ec or ec >= _E_CEIL or not int(self.status.item()) & 1:
+                break
+            self.status.bitwise_and_(~1)                             # the buffer was too small: the same scopes into twice the room
+            ec = min(2 * ec, _E_CEIL)
+        if self.e_cap is None:
+            self._e_hint = max(_E_FLOOR, min(e + e // 4, _E_CEIL))
+        return SimpleNamespace(node_idx=n_id[:n], num_nodes=n, targets=roots,
+                               local_targets=torch.arange(B, dtype=torch.int32, device=g.device), ptr=ptr, batch=batch[:n],
+                               root_n_id=root_n_id, edge_index=ei[:, :e], e_id=e_id[:e],
+                               score=score[:n].to(torch.float32) * (2.0 ** -30), rounds=rounds, stop=stop)
+
+    def check(self):
+        """As ShaDowKHopSampler.check."""
         raise_on_status(self.status, "ego-net sampler", hints={1: " (give the sampler a larger e_cap)", 2: " (give it a larger n_cap)"})
 
 

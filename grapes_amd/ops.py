@@ -3159,6 +3159,72 @@ def shadow_sample(rowptr, col, num_nodes: int, roots, depth: int, fanout: int, n
     return n_id, ptr, batch, root_n_id, ei, e_id, d_n, d_e
 
 
+SHADOW_PPR_TOUCHED = 4096    # T, the touched-set capacity of the PPR push: part of the rule, not a tuning knob
+SHADOW_PPR_ONE = 1 << 30     # the unit of mass
+SHADOW_PPR_MAX_K = SHADOW_MAX_NODES - 1
+SHADOW_PPR_MAX_ROUNDS = 1024
+
+
+def shadow_ppr_args(k: int, alpha_q: int, thr: int, max_rounds: int) -> int:
+    """C = k + 1, the most nodes of one PPR ego-net.  ValueError unless 1 <= k <= SHADOW_PPR_MAX_K, 1 <= alpha_q <= 65535,
+    1 <= thr <= 2^30 and 1 <= max_rounds <= SHADOW_PPR_MAX_ROUNDS."""
+    k, alpha_q, thr, max_rounds = int(k), int(alpha_q), int(thr), int(max_rounds)
+    if not 1 <= k <= SHADOW_PPR_MAX_K:
+        raise ValueError(f"shadow_ppr_sample: k = {k} is not built (1 .. {SHADOW_PPR_MAX_K}: the root and k nodes sit in one ego-net)")
+    if not 1 <= alpha_q <= 65535:
+        raise ValueError(f"shadow_ppr_sample: alpha_q = {alpha_q} is outside 1 .. 65535 (the teleport probability in units of 2^-16)")
+    if not 1 <= thr <= SHADOW_PPR_ONE:
+        raise ValueError(f"shadow_ppr_sample: thr = {thr} is outside 1 .. 2^30 (the push threshold per entry in units of 2^-30)")
+    if not 1 <= max_rounds <= SHADOW_PPR_MAX_ROUNDS:
+        raise ValueError(f"shadow_ppr_sample: max_rounds = {max_rounds} is outside 1 .. {SHADOW_PPR_MAX_ROUNDS}")
+    return k + 1
+
+
+def shadow_ppr_sample(rowptr, col, num_nodes: int, roots, k: int, alpha_q: int, thr: int, max_rounds: int, n_cap: Optional[int] = None,
+                      e_cap: Optional[int] = None, d_m=None, want_e_id: bool = True, status=None, out=None):
+    """(n_id int32 [n_cap], ptr int32 [B + 1], batch int32 [n_cap], root_n_id int32 [B], edge_index int32 [2, e_cap], e_id int64 [e_cap] or
+    None, n_count int32 [1], e_count int32 [1], score int32 [n_cap], rounds int32 [B], stop int32 [B]) of grapes_shadow_ppr_sample: one
+    PPR ego-net per root — fixed-point forward push from the root (teleport alpha_q / 2^16, threshold thr / 2^30 per stored entry, at
+    most max_rounds synchronous rounds over at most SHADOW_PPR_TOUCHED touched nodes), the root and the k best-scoring nodes, the
+    induced subgraph — concatenated in root order; the rule is in grapes_hip.h.  The first eight are shadow_sample's, with the ego-net
+    cap C = k + 1; score holds each row's fixed-point score in units of 2^-30 (at most 2^30, so int32 holds it), rounds and stop the
+    rounds run and the stop code (0 no node left to push, 1 max_rounds, 2 the next round could overflow the touched set) of each
+    root.  n_cap defaults to B * C, which cannot overflow; e_cap is required.  No random numbers.  out: the eleven tensors to write
+    (e_id may be None)."""
+    C = shadow_ppr_args(k, alpha_q, thr, max_rounds)
+    N, B = _list_rows("shadow_ppr_sample", rowptr, col, num_nodes, roots, d_m, status, int(num_nodes) < 1 or e_cap is None,
+                      "rowptr holds N + 1 values, roots is not empty and e_cap is given")
+    if B > SHADOW_MAX_ROOTS:
+        raise ValueError(f"shadow_ppr_sample: at most {SHADOW_MAX_ROOTS} roots per call")
+    if col.numel() >= 2 ** 31:
+        raise ValueError("shadow_ppr_sample: a graph with 2^31 or more entries is not built")
+    nc, ec, dev = B * C if n_cap is None else int(n_cap), int(e_cap), roots.device
+    if nc < 1 or ec < 1:
+        raise ValueError("shadow_ppr_sample: n_cap and e_cap are at least 1")
+    if out is None:
+        i32 = lambda *shape: torch.empty(shape, dtype=_i32, device=dev)
+        out = (i32(nc), i32(B + 1), i32(nc), i32(B), i32(2, ec), torch.empty(ec, dtype=_i64, device=dev) if want_e_id else None, i32(1),
+               i32(1), i32(nc), i32(B), i32(B))
+    n_id, ptr, batch, root_n_id, ei, e_id, d_n, d_e, score, rounds, stop = out
+    for t, name in ((n_id, "n_id"), (ptr, "ptr"), (batch, "batch"), (root_n_id, "root_n_id"), (ei, "edge_index"), (d_n, "n_count"),
+                    (d_e, "e_count"), (score, "score"), (rounds, "rounds"), (stop, "stop")):
+        _chk(t, _i32, name)
+    _chk(e_id, _i64, "e_id", True)
+    if (n_id.numel() < nc or batch.numel() < nc or score.numel() < nc or ptr.numel() < B + 1 or root_n_id.numel() < B or
+            rounds.numel() < B or stop.numel() < B or ei.dim() != 2 or ei.shape[0] != 2 or ei.shape[1] < ec or
+            (e_id is not None and e_id.numel() < ec)):
+        raise ValueError("shadow_ppr_sample: n_id, batch and score hold n_cap values, ptr B + 1, root_n_id, rounds and stop B, "
+                         "edge_index [2, e_cap], e_id e_cap")
+    ws = _ws(lib().grapes_shadow_ppr_sample_workspace_bytes(B, int(k)), dev)
+    if col.numel() == 0:
+        col = ws                                                     # (a graph without an entry: any address, never read)
+    _lib.check(lib().grapes_shadow_ppr_sample(_p(rowptr), _p(col), N, _p(roots), B, _p(d_m), int(k), int(alpha_q), int(thr),
+                                              int(max_rounds), nc, ec, _p(n_id), _p(ptr), _p(batch), _p(root_n_id), ei[0].data_ptr(),
+                                              ei[1].data_ptr(), _p(e_id), _p(score), _p(rounds), _p(stop), _p(d_n), _p(d_e), _p(ws),
+                                              _p(status), _stream()), "shadow_ppr_sample")
+    return n_id, ptr, batch, root_n_id, ei, e_id, d_n, d_e, score, rounds, stop
+
+
 def _segments(who, x, ptr, status):
     """The checks of the two segment-mean calls -> (num_segments, n_rows, f)."""
     _chk(x, _f32, who + ": the matrix"); _chk(ptr, _i32, "ptr"); _chk(status, _i32, "status", True)

@@ -66,7 +66,7 @@ extern "C" {
  * grapes_asgcn_variance, grapes_asgcn_logq_bwd; GraphSAGE — grapes_sage_sample_layer(_workspace_bytes),
  * grapes_sage_aggregate_fwd / _bwd, grapes_sage_aggregate_workspace_bytes; VR-GCN — grapes_vrgcn_aggregate_fwd / _bwd,
  * grapes_vrgcn_aggregate_workspace_bytes, grapes_vrgcn_long_row; LABOR — grapes_labor_sample_layer(_workspace_bytes),
- * grapes_labor_importance(_workspace_bytes); ShaDow-GNN — grapes_shadow_sample(_workspace_bytes), grapes_segment_mean_fwd / _bwd;
+ * grapes_labor_importance(_workspace_bytes); ShaDow-GNN — grapes_shadow_sample(_workspace_bytes), grapes_shadow_ppr_sample(_workspace_bytes), grapes_segment_mean_fwd / _bwd;
  * Cluster-GCN — grapes_cluster_batch(_workspace_bytes), grapes_cluster_aggregate_fwd / _bwd, grapes_cluster_aggregate_workspace_bytes; its graph partitioner —
  * grapes_partition_propose, grapes_partition_admit, grapes_partition_cut (+ _workspace_bytes each). */
 #define GRAPES_ABI_VERSION 303
@@ -1662,6 +1662,41 @@ int grapes_labor_importance(const int64_t* rowptr, const int32_t* col, int32_t n
  * workspace: grapes_shadow_sample_workspace_bytes(m, depth, fanout) bytes (0 for arguments outside the rule), 4-byte aligned. */
 size_t grapes_shadow_sample_workspace_bytes(int32_t m, int32_t depth, int32_t fanout);
 int grapes_shadow_sample(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* roots, int32_t m, const int32_t* d_m, int32_t depth, int32_t fanout, const uint32_t* words, uint64_t philox_seed, uint64_t philox_offset, uint64_t* d_philox_offset, int32_t n_cap, int32_t e_cap, int32_t* n_id, int32_t* ptr, int32_t* batch, int32_t* root_n_id, int32_t* edge_src, int32_t* edge_dst, int64_t* e_id, int32_t* d_n, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream);
+/* ShaDow-GNN's other scope: the k best nodes of an approximate personalised PageRank from the root, by synchronous forward push
+ * [Zeng et al., NeurIPS 2021 for the PPR scope; Andersen, Chung, Lang, FOCS 2006 for the push — both recalled].  The push is stated in
+ * FIXED POINT: integer adds commute, so a synchronous round has one result whatever the scheduling.  The rule (integers only,
+ * bit-reproducible on a CPU; ONE = 2^30 is the unit of mass, T = 4096 the touched-set capacity — the result depends on T, so T is
+ * part of the rule and not a tuning knob):
+ *   inputs   the CSR (rowptr int64[N + 1], col int32, fewer than 2^31 entries); roots[b], b < m (*d_m), 1 <= m <= 4096; k, the scope
+ *            size, 1 <= k <= 1023; alpha_q, the teleport probability in units of 2^-16, 1 <= alpha_q <= 65535; thr, the push threshold
+ *            per stored entry in units of 2^-30, 1 <= thr <= 2^30; 1 <= max_rounds <= 1024 (outside: GRAPES_EINVAL).  No random
+ *            numbers: the result is a function of the graph and the root.
+ *   state    per root a set S of touched nodes, each with r_v and p_v (uint32); S = {root}, r_root = ONE, p_root = 0 at the start;
+ *            sum r + sum p <= ONE always, so nothing overflows.  deg(v) is the stored length of row v: loops and duplicates count,
+ *            each by multiplicity.
+ *   round    F = {v in S : r_v > 0 and r_v >= thr * deg(v)} (a 64-bit product).  In this order: F empty — stop, code 0;
+ *            rounds == max_rounds — stop, code 1; |S| + sum over F of deg(v) > T — stop, code 2 (the round could overflow the table,
+ *            so it is not run; all three quantities are fixed at a round boundary, so the stop is reproducible).  Otherwise: snapshot
+ *            (v, r_v) for v in F and set those r_v = 0; a snapshot entry with deg(v) = 0 gives p_v += r_v; every other one gives
+ *            keep = (r_v * alpha_q) >> 16 (a 64-bit product), p_v += keep, share = (r_v - keep) / deg(v) (integer division, the
+ *            remainder is dropped), and every stored entry u of row v joins S if absent (r = p = 0, also when share = 0) and gets
+ *            r_u += share; an entry u = v pays v back.  A column outside [0, N) is dropped, loses its share and raises
+ *            GRAPES_STATUS_BAD_INDEX.  rounds += 1.
+ *   score    score_v = p_v + ((r_v * alpha_q) >> 16) for v in S: what p would be if every node kept once more without spreading;
+ *            it gives residual-only nodes a rank.
+ *   members  the root, and the k nodes v != root with score_v > 0 that have the largest (score_v, -v): score descending, then id
+ *            ascending; fewer when fewer exist.
+ *   edges    the subgraph induced on the members, exactly as grapes_shadow_sample defines it.
+ * Outputs: everything grapes_shadow_sample returns, in the same order and with the same capacity, overflow and bad-root behaviour (the
+ * ego-net cap is C = k + 1); score uint32[n_total] (optional) aligned with n_id, the root's own score included; rounds int32[m] and
+ * stop int32[m] (optional): the rounds run and the stop code of each root, 0 and 0 for an empty ego-net.
+ * Three launches: a workgroup per root runs the rounds with the touched table in LDS (an 8192-slot hash, integer LDS atomics only; a
+ * round is two dependent memory trips whatever the frontier's size), selects by one bitonic sort of 64-bit keys and counts the induced
+ * entries; then the scan and the write of grapes_shadow_sample.  No float, no global atomic beyond the status OR: two runs give the
+ * same bits.
+ * workspace: grapes_shadow_ppr_sample_workspace_bytes(m, k) bytes (0 for arguments outside the rule), 4-byte aligned. */
+size_t grapes_shadow_ppr_sample_workspace_bytes(int32_t m, int32_t k);
+int grapes_shadow_ppr_sample(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* roots, int32_t m, const int32_t* d_m, int32_t k, uint32_t alpha_q, uint32_t thr, int32_t max_rounds, int32_t n_cap, int32_t e_cap, int32_t* n_id, int32_t* ptr, int32_t* batch, int32_t* root_n_id, int32_t* edge_src, int32_t* edge_dst, int64_t* e_id, uint32_t* score, int32_t* rounds, int32_t* stop, int32_t* d_n, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream);
 /* The mean over contiguous row segments, ShaDow's pooled readout: out[b, :f] = the mean of h[ptr[b] .. ptr[b + 1], :f] for b <
  * num_segments, 0 for an empty segment; h is [n_rows, f] row-major, 1 <= f <= 1024.  A thread owns a column and adds the segment's
  * rows in row order, then divides once: n_b - 1 additions and one division in a fixed order, no atomics.  The backward writes
