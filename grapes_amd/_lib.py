@@ -103,6 +103,12 @@ SIGNATURES = {
     "grapes_vrgcn_aggregate_workspace_bytes": (SZ, [I32, I32, I32]),
     "grapes_vrgcn_aggregate_fwd": (I32, [P, I64, P, I32, P, I64, P, P, P, I32, P, P, I32, P, P, P, I64, P, I32, I32, P, P, P]),
     "grapes_vrgcn_aggregate_bwd": (I32, [P, I64, P, P, P, P, I32, P, P, P, I64, I32, I32, I32, P, P]),
+    # GNNAutoScale: the batch's whole neighbourhoods resolved to (local row | history row) codes, and the aggregation over them
+    "grapes_gas_resolve_workspace_bytes": (SZ, [I32]),
+    "grapes_gas_resolve": (I32, [P, P, I32, P, I32, P, P, I32, I32, I32, I32, P, P, P, P, P, P]),
+    "grapes_gas_aggregate_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_gas_aggregate_fwd": (I32, [P, I64, P, I64, P, I32, P, I32, P, P, I32, P, I64, I32, I32, P, P, P]),
+    "grapes_gas_aggregate_bwd": (I32, [P, I64, P, P, I32, P, P, P, I64, I32, I32, P, P]),
     # LABOR: the layer-neighbour sampler with shared per-node variates
     "grapes_labor_sample_layer_workspace_bytes": (SZ, [I32, I32]),
     "grapes_labor_sample_layer": (I32, [P, P, I32, P, I32, P, I32, P, U64, U64, P, P, I32, I32, P, P, P, P, P, P, P, P]),

@@ -15,7 +15,7 @@
 //   vrgcn_items_k     ONE workgroup: rows with more than VRGCN_LONG_ROW entries are cut into chunks of VRGCN_LONG_ROW entries, the
 //                     exclusive prefix of the chunk counts in list order is the row's first work item
 //   vrgcn_chunks_k    a group per work item: the chunk's part of the full walk -> pacc[item]
-//   vrgcn_combine_k   a group per listed row: a long row's items are added in chunk order to what vrgcn_rows_k left, then dinv_u
+//   hist_combine_k    (hist_rows.h) a group per listed row: a long row's items are added in chunk order to what vrgcn_rows_k left, then dinv_u
 // Rows up to VRGCN_LONG_ROW entries never leave vrgcn_rows_k; without long rows (item_cap = 0) it is the only launch.
 //
 // Backward (Hbar is a constant), over the by-source CSR of the same preparation (rowptr_s, csr_dst: row loc v holds the local ids
@@ -23,32 +23,19 @@
 //
 //   dH[loc v] = dinv_v sum_{kept (u, v)} coef[pos[loc u]] dA[pos[loc u]] + dinv_v^2 dA[pos[loc v]]       (the self term for listed v)
 //
-//   vrgcn_bwd_k       a group per local row, entries in the CSR's order
+//   hist_bwd_k        (hist_rows.h, VrBwdTarget) a group per local row, entries in the CSR's order
 // No float atomics anywhere: every sum has a fixed order (entry order inside a row or chunk, chunk order across items), two runs
 // give the same bits.  No kernel waits on another workgroup.  An index outside its table raises GRAPES_STATUS_BAD_INDEX and the
 // entry is dropped; it then contributes 0 times row 0 of the table, so a non-finite value there would reach the sum (as in
 // row_sum.h, where the stand-in is the row itself).
-#include "row_gather.h"
+#include "hist_rows.h"
 #include "row_list.h"
 
-// The long-row threshold (= the chunk length) and the history rows in flight were chosen by measurement on the products-shaped
-// synthetic graph (batch 512, width 256; DESIGN.md has the table): chunks of 512 entries walked four rows at a time leave one group
-// with 128 dependent trips, 114 - 132 us per call; chunks of 64 with 16 rows in flight take 27 - 28 us.
-#ifndef VRGCN_LONG_MULT
-#define VRGCN_LONG_MULT 1
-#endif
-#define VRGCN_LONG_ROW (VRGCN_LONG_MULT * GRAPES_LONG_ROW)
+// (the long-row threshold, the history rows in flight, the combine pass and the backward's body are hist_rows.h's: GNNAutoScale's
+// aggregation shares them)
+#define VRGCN_LONG_ROW HIST_LONG_ROW
 #define VRGCN_SCAN_THREADS 1024
-#ifndef VRGCN_FULL_BUDGET
-#define VRGCN_FULL_BUDGET 64
-#endif
-
-// history rows a group keeps in flight in the full walk: VRGCN_FULL_BUDGET floats per lane (at most that many / 4 rows), and never
-// fewer than the scaffold's RowUnroll
-template <int VEC, int NS> struct VrUnroll {
-    static constexpr int B = VRGCN_FULL_BUDGET / (NS * VEC), M = VRGCN_FULL_BUDGET / 4;
-    static constexpr int U = B > M ? M : (B > RowUnroll<NS>::U ? B : RowUnroll<NS>::U);
-};
+template <int VEC, int NS> using VrUnroll = HistUnroll<VEC, NS>;
 
 struct VrArgs {
     const float* h; long long ld_h; int n_local;
@@ -65,14 +52,6 @@ struct VrArgs {
     int F;
     int32_t* status;
 };
-
-template <int VEC, int NS>
-__device__ __forceinline__ void vr_zero(float (&acc)[NS][VEC]) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
-}
 
 // acc += sum_{t in [beg, end)} dinv[v] Hbar[v], v = col[t]: the rows of the history read in place by global id
 template <int VEC, int LPR, int NS>
@@ -144,14 +123,14 @@ __device__ __forceinline__ void vr_kept_walk(const VrArgs& a, int kb, int ke, in
     }
 }
 
-// skip_long: rows longer than VRGCN_LONG_ROW leave their full walk to vrgcn_chunks_k / vrgcn_combine_k and store the sum so far
+// skip_long: rows longer than VRGCN_LONG_ROW leave their full walk to vrgcn_chunks_k / hist_combine_k and store the sum so far
 template <int VEC, int LPR, int NS>
 __global__ __launch_bounds__(256) void vrgcn_rows_k(VrArgs a, int skip_long) {
     const int l = threadIdx.x % LPR, G = 256 / LPR;
     for (int r = blockIdx.x * G + threadIdx.x / LPR; r < a.m; r += gridDim.x * G) {
         const int u = a.rows_g[r], lu = a.rows_l[r];
         float acc[NS][VEC];
-        vr_zero<VEC, NS>(acc);
+        hist_zero<VEC, NS>(acc);
         if ((unsigned)u >= (unsigned)a.N || (unsigned)lu >= (unsigned)a.n_local) {      // a row that names no node: zeros
             if (l == 0 && a.status) atomicOr(a.status, GRAPES_STATUS_BAD_INDEX);
             if (l == 0 && a.coef) a.coef[r] = 0.f;
@@ -219,7 +198,7 @@ __global__ __launch_bounds__(256) void vrgcn_chunks_k(VrArgs a) {
         const int r = lower_bound<int32_t, int, int>(a.item_off, a.m, it + 1) - 1;
         const ListRow R = list_row(a.rowptr, a.N, a.rows_g, r, a.m, nullptr);
         float acc[NS][VEC];
-        vr_zero<VEC, NS>(acc);
+        hist_zero<VEC, NS>(acc);
         if (R.i >= 0) {
             const long long beg = R.a + (long long)(it - a.item_off[r]) * VRGCN_LONG_ROW, re = R.a + R.deg;
             const long long end = beg + VRGCN_LONG_ROW < re ? beg + VRGCN_LONG_ROW : re;
@@ -229,123 +208,28 @@ __global__ __launch_bounds__(256) void vrgcn_chunks_k(VrArgs a) {
     }
 }
 
-template <int VEC, int LPR, int NS>
-__global__ __launch_bounds__(256) void vrgcn_combine_k(VrArgs a) {
-    const int l = threadIdx.x % LPR, G = 256 / LPR;
-    for (int r = blockIdx.x * G + threadIdx.x / LPR; r < a.m; r += gridDim.x * G) {
-        const int i0 = a.item_off[r], i1 = a.item_off[r + 1];
-        if (i1 <= i0) continue;
-        const int u = a.rows_g[r];
-        if ((unsigned)u >= (unsigned)a.N) continue;
-        constexpr int U = VrUnroll<VEC, NS>::U;
-        float acc[NS][VEC], p[U][NS][VEC];
-        row_load_ld<VEC, LPR, NS>(a.out, r, a.ld_out, a.F, l, acc);
-        int it = i0;
-        for (; it + U <= i1; it += U) {                                       // U partial rows requested together, added in chunk order
-#pragma unroll
-            for (int u = 0; u < U; ++u) row_load<VEC, LPR, NS>(a.pacc, it + u, a.F, l, p[u]);
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int s = 0; s < NS; ++s)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[s][v] += p[u][s][v];
-        }
-        for (; it < i1; ++it) {
-            row_load<VEC, LPR, NS>(a.pacc, it, a.F, l, p[0]);
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[s][v] += p[0][s][v];
-        }
-        const float du = a.dinv[u];
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] *= du;
-        row_store_ld<VEC, LPR, NS>(a.out, r, a.ld_out, a.F, l, acc);
-    }
-}
-
-struct VrBwdArgs {
-    const float* da; long long ld_da;
+// The backward's policy (hist_bwd_k): a target c reads row pos[c] of dA with the factor coef the forward wrote for it; a target that
+// is none of the listed rows raises GRAPES_STATUS_BAD_INDEX and is dropped.
+struct VrBwdTarget {
     const float* coef;
     const int32_t* pos;
-    const int32_t* node_idx;
-    const float* dinv; int N;
-    const int32_t* rowptr_s; const int32_t* csr_dst;
-    float* dh; long long ld_dh;
-    int n_local, m, F;
-    int32_t* status;
-};
-
-template <int VEC, int LPR, int NS>
-__global__ __launch_bounds__(256) void vrgcn_bwd_k(VrBwdArgs a) {
-    constexpr int U = RowUnroll<NS>::U;
-    const int l = threadIdx.x % LPR, G = 256 / LPR;
-    for (int lv = blockIdx.x * G + threadIdx.x / LPR; lv < a.n_local; lv += gridDim.x * G) {
-        float acc[NS][VEC];
-        vr_zero<VEC, NS>(acc);
-        const int gv = a.node_idx[lv];
-        if ((unsigned)gv >= (unsigned)a.N) {
-            if (l == 0 && a.status) atomicOr(a.status, GRAPES_STATUS_BAD_INDEX);
-            row_store_ld<VEC, LPR, NS>(a.dh, lv, a.ld_dh, a.F, l, acc);
-            continue;
-        }
-        const int beg = a.rowptr_s[lv], end = a.rowptr_s[lv + 1];
-        for (int b = beg; b < end; b += LPR) {
-            const int c = batch_entry(a.csr_dst, b + l, end, a.n_local, a.status);
-            int r = -1;
-            if (c >= 0) {
-                r = a.pos[c];
-                if ((unsigned)r >= (unsigned)a.m) {                          // a target that is none of the listed rows
-                    r = -1;
-                    if (a.status) atomicOr(a.status, GRAPES_STATUS_BAD_INDEX);
-                }
-            }
-            const int idx = r < 0 ? 0 : r;
-            const float w = r < 0 ? 0.f : a.coef[r];
-            const int cnt = end - b < LPR ? end - b : LPR;
-            for (int k = 0; k < cnt; k += U) {
-                float gv_[U][NS][VEC], wk[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int ik = __shfl(idx, k + u, LPR);
-                    wk[u] = __shfl(w, k + u, LPR);
-                    row_load_ld<VEC, LPR, NS>(a.da, ik, a.ld_da, a.F, l, gv_[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int s = 0; s < NS; ++s)
-#pragma unroll
-                        for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(wk[u], gv_[u][s][v], acc[s][v]);
-            }
-        }
-        const float dv = a.dinv[gv];
-        const int rs = a.pos[lv];
-        if ((unsigned)rs < (unsigned)a.m) {
-            float g[NS][VEC];
-            row_load_ld<VEC, LPR, NS>(a.da, rs, a.ld_da, a.F, l, g);
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[s][v] = dv * fmaf(dv, g[s][v], acc[s][v]);
-        } else {
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[s][v] *= dv;
-        }
-        row_store_ld<VEC, LPR, NS>(a.dh, lv, a.ld_dh, a.F, l, acc);
+    int m;
+    __device__ __forceinline__ int row(int c, int32_t* status) const {
+        const int r = pos[c];
+        if ((unsigned)r < (unsigned)m) return r;
+        if (status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+        return -1;
     }
-}
+    __device__ __forceinline__ float weight(int r) const { return coef[r]; }
+    __device__ __forceinline__ int self(int lv) const {
+        const int rs = pos[lv];
+        return (unsigned)rs < (unsigned)m ? rs : -1;
+    }
+};
 
 // ------------------------------------------------------------------------------------------------------------ host side
 
 #define VRGCN_ITEM_CAP_MAX (1 << 20)
-
-static inline bool vr_vec_ok(const void* p, int64_t ld) { return grapes_aligned16(p) && ld % 4 == 0; }
 
 extern "C" int32_t grapes_vrgcn_long_row(void) { return VRGCN_LONG_ROW; }
 
@@ -365,7 +249,7 @@ extern "C" int grapes_vrgcn_aggregate_fwd(const float* h, int64_t ld_h, const in
     if (item_cap < 0 || item_cap > VRGCN_ITEM_CAP_MAX || (item_cap > 0 && !workspace)) return GRAPES_EINVAL;
     if (out == h || out == hbar) return GRAPES_EINVAL;
     if (item_cap > 0 && !grapes_aligned16(workspace)) return GRAPES_EALIGN;
-    const int shape = gather_shape(f, vr_vec_ok(h, ld_h) && vr_vec_ok(hbar, ld_hbar) && vr_vec_ok(out, ld_out));
+    const int shape = gather_shape(f, hist_vec_ok(h, ld_h) && hist_vec_ok(hbar, ld_hbar) && hist_vec_ok(out, ld_out));
     if (shape < 0) return shape;
     if (m == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
@@ -386,7 +270,7 @@ extern "C" int grapes_vrgcn_aggregate_fwd(const float* h, int64_t ld_h, const in
     ROW_LAUNCH(vrgcn_rows_k, 4, vec, f, m, s, a, item_cap > 0 ? 1 : 0);
     if (item_cap > 0) {
         ROW_LAUNCH(vrgcn_chunks_k, 4, vec, f, item_cap, s, a);
-        ROW_LAUNCH(vrgcn_combine_k, 4, vec, f, m, s, a);
+        ROW_LAUNCH(hist_combine_k, 4, vec, f, m, s, a);
     }
     return 0;
 }
@@ -397,11 +281,12 @@ extern "C" int grapes_vrgcn_aggregate_bwd(const float* da, int64_t ld_da, const 
                                           int32_t* status, grapes_stream_t stream) {
     if (!da || !coef || !pos || !node_idx || !dinv || !rowptr_s || !csr_dst || !dh) return GRAPES_EINVAL;
     if (n_local < 1 || num_nodes < 1 || m < 1 || f < 1 || ld_da < f || ld_dh < f || dh == da) return GRAPES_EINVAL;
-    const int shape = gather_shape(f, vr_vec_ok(da, ld_da) && vr_vec_ok(dh, ld_dh));
+    const int shape = gather_shape(f, hist_vec_ok(da, ld_da) && hist_vec_ok(dh, ld_dh));
     if (shape < 0) return shape;
-    VrBwdArgs a;
-    a.da = da; a.ld_da = ld_da; a.coef = coef; a.pos = pos; a.node_idx = node_idx; a.dinv = dinv; a.N = num_nodes;
-    a.rowptr_s = rowptr_s; a.csr_dst = csr_dst; a.dh = dh; a.ld_dh = ld_dh; a.n_local = n_local; a.m = m; a.F = f; a.status = status;
-    ROW_LAUNCH(vrgcn_bwd_k, 4, shape == 0, f, n_local, (hipStream_t)stream, a);
+    HistBwdArgs a;
+    a.da = da; a.ld_da = ld_da; a.node_idx = node_idx; a.dinv = dinv; a.N = num_nodes; a.rowptr_s = rowptr_s; a.csr_dst = csr_dst;
+    a.dh = dh; a.ld_dh = ld_dh; a.n_local = n_local; a.F = f; a.status = status;
+    const VrBwdTarget tgt{coef, pos, m};
+    ROW_LAUNCH(hist_bwd_k, 4, shape == 0, f, n_local, (hipStream_t)stream, a, tgt);
     return 0;
 }

@@ -3007,6 +3007,120 @@ def vrgcn_aggregate_bwd(da, coef, pos, node_idx, dinv, prep: PreparedGraph, out=
     return out
 
 
+# ------------------------------------------------------------------------------- GNNAutoScale: cluster batches over histories
+# [Fey, Lenssen, Weichert and Leskovec, ICML 2021; pyg_autoscale-recall] (grapes_hip.h, csrc/gas_kernels.hip)
+GAS_CHUNK = 64               # GRAPES_LONG_ROW: the entries of one work item of the resolve
+GAS_ITEM_CAP_MAX = 1 << 24
+GAS_BAD_CODE = 2 ** 31 - 1   # the code of an entry the resolve had to drop (a bad column or `where` entry)
+
+
+def gas_resolve(rowptr, col, num_nodes: int, node_idx, n: int, where, stamp, serial: int, e_cap: int, item_cap: Optional[int] = None,
+                status=None, out=None):
+    """(rowptr_h int32 [n + 1], code int32 [e_cap], counts int64 [2]) of grapes_gas_resolve, after cluster_batch with the same stamp
+    and serial: for the first n rows of node_idx (the batch's rows) the WHOLE global neighbourhood of each, entry by entry in the
+    CSR's order, as code = the local row of an in-batch neighbour, -1 - v for an out-of-batch neighbour v.  rowptr_h = the prefix sum
+    of the rows' global degrees; rowptr_h[n] is the true total even when it exceeds e_cap (status then carries the edge-overflow bit
+    and nothing is written at or past e_cap).  counts = (in-batch entries, out-of-batch entries).  item_cap: the work items (64
+    entries of one row) the call has room for — default n + nnz / 64 + 1, which cannot overflow but launches 64 threads per item of
+    room: pass the partition's bound, as GasLoader does.  out: the three tensors to write."""
+    _chk(rowptr, _i64, "rowptr")
+    for t, name in ((col, "col"), (node_idx, "node_idx"), (where, "where"), (stamp, "stamp")):
+        _chk(t, _i32, name)
+    _chk(status, _i32, "status", True)
+    N, n, ec, dev = int(num_nodes), int(n), int(e_cap), node_idx.device
+    if rowptr.numel() != N + 1 or N < 1 or tuple(where.shape) != (N, 2) or stamp.dim() != 2 or stamp.shape[1] != 2 or stamp.shape[0] < 1:
+        raise ValueError("gas_resolve: rowptr holds N + 1 values, where is [N, 2] and stamp [P, 2]")
+    if node_idx.dim() != 1 or not 1 <= n <= node_idx.numel():
+        raise ValueError("gas_resolve: node_idx is a flat int32 tensor of at least n >= 1 values")
+    if col.numel() >= 2 ** 31:
+        raise ValueError("gas_resolve: a graph with 2^31 or more entries is not built")
+    if not 1 <= int(serial) <= CLUSTER_MAX_SERIAL:
+        raise ValueError(f"gas_resolve: serial is 1 .. {CLUSTER_MAX_SERIAL}")
+    ic = min(n + col.numel() // GAS_CHUNK + 1, GAS_ITEM_CAP_MAX) if item_cap is None else int(item_cap)
+    if not 1 <= ec <= 2 ** 31 - 1 or not 1 <= ic <= GAS_ITEM_CAP_MAX:
+        raise ValueError(f"gas_resolve: e_cap is 1 .. 2^31 - 1, item_cap 1 .. {GAS_ITEM_CAP_MAX}")
+    if out is None:
+        out = (torch.empty(n + 1, dtype=_i32, device=dev), torch.empty(ec, dtype=_i32, device=dev),
+               torch.empty(2, dtype=_i64, device=dev))
+    rowptr_h, code, counts = out
+    _chk(rowptr_h, _i32, "rowptr_h"); _chk(code, _i32, "code"); _chk(counts, _i64, "counts")
+    if rowptr_h.numel() < n + 1 or code.numel() < ec or counts.numel() < 2:
+        raise ValueError("gas_resolve: rowptr_h holds n + 1 values, code e_cap and counts 2")
+    ws = _ws(lib().grapes_gas_resolve_workspace_bytes(n), dev)
+    if col.numel() == 0:
+        col = ws                                                     # (a graph without an entry: any address, never read)
+    _lib.check(lib().grapes_gas_resolve(_p(rowptr), _p(col), N, _p(node_idx), n, _p(where), _p(stamp), stamp.shape[0], int(serial), ec,
+                                        ic, _p(rowptr_h), _p(code), _p(counts), _p(ws), _p(status), _stream()), "gas_resolve")
+    return rowptr_h, code, counts
+
+
+def gas_item_cap(rowptr_h) -> int:
+    """The chunks of the batch rows with more than VRGCN_LONG_ROW codes (one host read)."""
+    deg = rowptr_h[1:] - rowptr_h[:-1]
+    nc = torch.where(deg > VRGCN_LONG_ROW, (deg + (VRGCN_LONG_ROW - 1)) // VRGCN_LONG_ROW, torch.zeros_like(deg))
+    return int(nc.sum().item())
+
+
+def gas_aggregate_fwd(h, hbar, dinv, node_idx, rowptr_h, code, item_cap: Optional[int] = None, out=None, status=None):
+    """A [n, f] of grapes_gas_aggregate_fwd: for every batch row i, u = node_idx[i],
+      A[i] = dinv_u (dinv_u h[i] + sum_{t in row i of rowptr_h} dinv_{v_t} (code_t >= 0 ? h[code_t] : hbar[-1 - code_t]))
+    with h [n, f] the layer's input on the batch's local rows, hbar [N, f] its history on global rows — both read in place — dinv fp32
+    [N] = (d + 1)^-1/2 and (rowptr_h, code) as gas_resolve wrote them (code may be the whole e_cap buffer: the offsets say what is
+    read).  item_cap: the chunks of the rows longer than VRGCN_LONG_ROW (None: counted here, one host read; 0: every row by one
+    group of lanes).  h, hbar and out may be column blocks of wider matrices."""
+    _chk(dinv, _f32, "dinv"); _chk(status, _i32, "status", True)
+    _vrgcn_ids(node_idx, "node_idx"); _vrgcn_ids(rowptr_h, "rowptr_h"); _vrgcn_ids(code, "code")
+    if h.dim() != 2 or hbar.dim() != 2 or h.shape[1] != hbar.shape[1] or h.shape[0] < 1:
+        raise ValueError("h is [n, f] with n >= 1 and hbar [N, f]")
+    n, f = h.shape
+    N = hbar.shape[0]
+    _gather_width(f, "GAS aggregation")
+    ld_h, ld_hbar = _strided_rows(h, "h", n, f), _strided_rows(hbar, "hbar", N, f)
+    if node_idx.numel() < n or rowptr_h.numel() != n + 1 or dinv.numel() != N or N < 1:
+        raise ValueError("node_idx holds h's n rows, rowptr_h n + 1 values and dinv N, N = hbar's rows")
+    if item_cap is None:
+        item_cap = gas_item_cap(rowptr_h)
+    item_cap = int(item_cap)
+    if not 0 <= item_cap <= VRGCN_ITEM_CAP_MAX:
+        raise ValueError(f"item_cap is 0 .. {VRGCN_ITEM_CAP_MAX}")
+    dev = h.device
+    if out is None:
+        out = torch.empty((n, f), dtype=_f32, device=dev)
+    ld_out = _strided_rows(out, "out", n, f)
+    ws = _ws(lib().grapes_gas_aggregate_workspace_bytes(n, item_cap, f), dev) if item_cap else None
+    if code.numel() == 0:
+        code = rowptr_h                                              # (no entry: any address, never read)
+        e = 0
+    else:
+        e = code.numel()
+    _lib.check(lib().grapes_gas_aggregate_fwd(_p(h), ld_h, _p(hbar), ld_hbar, _p(dinv), N, _p(node_idx), n, _p(rowptr_h), _p(code), e,
+                                              _p(out), ld_out, f, item_cap, _p(ws), _p(status), _stream()), "gas_aggregate_fwd")
+    return out
+
+
+def gas_aggregate_bwd(da, node_idx, dinv, prep, out=None, status=None):
+    """dh [n, f] of grapes_gas_aggregate_bwd from da = d A [n, f]:
+      dh[j] = dinv_{v_j} (dinv_{v_j} da[j] + sum_{i in by-source row j} dinv_{u_i} da[i]),  v_j = node_idx[j]
+    over prep's by-source CSR of the batch's induced entries (prep.rowptr_s, prep.csr_dst; prep.n = n).  hbar is a constant and has
+    no gradient.  Fixed order, no atomics."""
+    _chk(dinv, _f32, "dinv"); _chk(status, _i32, "status", True)
+    _vrgcn_ids(node_idx, "node_idx")
+    if da.dim() != 2 or da.shape[0] < 1:
+        raise ValueError("da is [n, f] with n >= 1")
+    n, f = da.shape
+    _gather_width(f, "GAS aggregation")
+    ld_da = _strided_rows(da, "da", n, f)
+    if prep.n != n or node_idx.numel() < n:
+        raise ValueError("the prepared induced entries and node_idx cover da's n rows")
+    if out is None:
+        out = torch.empty((n, f), dtype=_f32, device=da.device)
+    ld_out = _strided_rows(out, "dh", n, f)
+    st = status if status is not None else prep.status
+    _lib.check(lib().grapes_gas_aggregate_bwd(_p(da), ld_da, _p(node_idx), _p(dinv), dinv.numel(), _p(prep.rowptr_s), _p(prep.csr_dst),
+                                              _p(out), ld_out, n, f, _p(st), _stream()), "gas_aggregate_bwd")
+    return out
+
+
 # ------------------------------------------------------------------------------- LABOR: the layer-neighbour sampler
 # [Balin and Catalyurek, NeurIPS 2023; LABOR-recall: DGL's LaborSampler] (grapes_hip.h, csrc/labor_kernels.hip)
 LABOR_CHUNK = 64             # GRAPES_LONG_ROW: the entries of one work item; a longer row is cut over several wavefronts

@@ -68,7 +68,8 @@ extern "C" {
  * grapes_vrgcn_aggregate_workspace_bytes, grapes_vrgcn_long_row; LABOR — grapes_labor_sample_layer(_workspace_bytes),
  * grapes_labor_importance(_workspace_bytes); ShaDow-GNN — grapes_shadow_sample(_workspace_bytes), grapes_shadow_ppr_sample(_workspace_bytes), grapes_segment_mean_fwd / _bwd;
  * Cluster-GCN — grapes_cluster_batch(_workspace_bytes), grapes_cluster_aggregate_fwd / _bwd, grapes_cluster_aggregate_workspace_bytes; its graph partitioner —
- * grapes_partition_propose, grapes_partition_admit, grapes_partition_cut (+ _workspace_bytes each). */
+ * grapes_partition_propose, grapes_partition_admit, grapes_partition_cut (+ _workspace_bytes each); GNNAutoScale —
+ * grapes_gas_resolve(_workspace_bytes), grapes_gas_aggregate_fwd / _bwd, grapes_gas_aggregate_workspace_bytes. */
 #define GRAPES_ABI_VERSION 303
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1586,6 +1587,52 @@ int grapes_vrgcn_aggregate_fwd(const float* h, int64_t ld_h, const int32_t* node
  * for every local row (rows nothing reaches get zeros).  One launch, a group per local row, entries in the CSR's order: no float
  * atomics, two runs give the same bits.  A target that is none of the listed rows raises GRAPES_STATUS_BAD_INDEX and is dropped. */
 int grapes_vrgcn_aggregate_bwd(const float* da, int64_t ld_da, const float* coef, const int32_t* pos, const int32_t* node_idx, const float* dinv, int32_t num_nodes, const int32_t* rowptr_s, const int32_t* csr_dst, float* dh, int64_t ld_dh, int32_t n_local, int32_t m, int32_t f, int32_t* status, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ GNNAutoScale, "GAS": cluster batches that pull out-of-batch
+ * neighbours from histories (csrc/gas_kernels.hip) [Fey, Lenssen, Weichert and Leskovec, ICML 2021; pyg_autoscale-recall: ScalableGNN,
+ * History, SubgraphLoader — recalled, not read: the rule below is the contract; tests/gas_oracle.py reproduces it].
+ *   graph    a symmetric loop-free CSR (rowptr int64[N + 1], col int32, fewer than 2^31 entries, duplicates counting once each):
+ *            d_u = the stored entries of row u, dinv[u] = (d_u + 1)^-1/2 (float[N], the caller's table), P = D^-1/2 (A + I) D^-1/2.
+ *   batch    grapes_cluster_batch's over that graph: n rows in cluster order, node_idx[i] = the global id of row i.
+ *   history  a model of L layers keeps for l = 1 .. L - 1 a table Hbar^(l), fp32 [N, hidden_l] on global rows, zero at first.
+ *   resolve  once per batch, for every batch row i, u = node_idx[i], and every stored entry v at position t of row u, in the CSR's
+ *            order: code[rowptr_h[i] + t] = the local row of v when v is in the batch (stamp[where[v].cluster].serial == serial:
+ *            stamp[..].base + where[v].position, as grapes_cluster_batch), else -1 - v.  rowptr_h int32[n + 1] = the prefix sum of
+ *            the batch rows' global degrees; counts int64[2] = the in-batch and the out-of-batch entries.
+ *   level 1  exact, the history of X being X: Z1 = (P X)[node_idx] W1^T + b1, P X computed once.
+ *   level l + 1 >= 2, H = H^(l) [n, f] on local rows, Hbar = Hbar^(l) a constant for autograd:
+ *            A[i] = dinv_u (dinv_u H[i] + sum_{t in row i of rowptr_h} dinv_{v_t} (code_t >= 0 ? H[code_t] : Hbar[-1 - code_t])),
+ *            Z = A W^T + b; dinv_{v_t} from the global table (v_t = node_idx[code_t] for an in-batch entry).
+ *   backward over the by-source CSR of the batch's INDUCED entries (grapes_gcn_prepare over the batch's edge list) — exact for any
+ *            stored multiset, the code list is not assumed to be its own transpose:
+ *            dH[j] = dinv_{v_j} (dinv_{v_j} dA[j] + sum_{i in by-source row j} dinv_{u_i} dA[i]);  dHbar = none.
+ *   push     after the step's forward, for every level: Hbar^(l)[node_idx] = H^(l) (post-ReLU, all n rows; grapes_scatter_rows).
+ *            In-batch nodes never read their own history inside a step.
+ * grapes_gas_resolve runs after grapes_cluster_batch with the same stamp (int32[P][2], 8-byte aligned, as `where`) and serial: one
+ * launch scans the degrees, one runs a wavefront per 64 entries of a row and writes the codes one per lane.  Integers only.  e_cap
+ * bounds the code list: a larger total ORs GRAPES_STATUS_EDGE_OVERFLOW, nothing is written at or past e_cap and rowptr_h[n] still
+ * holds the TRUE total, so the caller can retry; item_cap (1 .. 2^24) bounds the sum over the batch rows of ceil(d / 64), more
+ * raise the same bit.  A row id or column id outside [0, N), or a `where` entry outside its table (cluster outside [0, P), local
+ * row outside [0, n)), ORs GRAPES_STATUS_BAD_INDEX; such an entry's code is 2^31 - 1, which the aggregation drops, and neither
+ * count includes it.  The counts cover every entry, also those past e_cap.  workspace:
+ * grapes_gas_resolve_workspace_bytes(n) bytes, 4-byte aligned; counts 8-byte aligned. */
+size_t grapes_gas_resolve_workspace_bytes(int32_t n);
+int grapes_gas_resolve(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* node_idx, int32_t n, const int32_t* where, const int32_t* stamp, int32_t num_parts, int32_t serial, int32_t e_cap, int32_t item_cap, int32_t* rowptr_h, int32_t* code, int64_t* counts, void* workspace, int32_t* status, grapes_stream_t stream);
+/* out [n, f] = A of the rule above from h [n, f] and hbar [N, f], both read in place: no halo is materialised.  e = the entries of
+ * `code` (offsets of rowptr_h beyond it are clamped).  A group of lanes owns a row and keeps one accumulator in registers over one
+ * walk; the source table and row are selected from the code without a branch, so several source rows are in flight; dinv_u is
+ * applied once per row.  item_cap > 0: rows with more than grapes_vrgcn_long_row() codes are cut into chunks of that many, one group
+ * each, whose partial sums are added in chunk order (four launches instead of one); item_cap bounds the chunks of the long rows (at
+ * most 2^20; more raise GRAPES_STATUS_EDGE_OVERFLOW and the result is invalid); item_cap = 0: every row by one group.  No float
+ * atomics: two runs give the same bits.  Widths as grapes_sage_aggregate_fwd: any f <= 256, up to 1024 when f % 4 == 0 and h, hbar,
+ * out are 16-byte aligned with ld % 4 == 0, else GRAPES_EALIGN / GRAPES_EINVAL.  A code outside [-N, n) (or a node_idx outside
+ * [0, N)) raises GRAPES_STATUS_BAD_INDEX and is dropped.  workspace: grapes_gas_aggregate_workspace_bytes(n, item_cap, f), 16-byte
+ * aligned; may be NULL with item_cap = 0. */
+size_t grapes_gas_aggregate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f);
+int grapes_gas_aggregate_fwd(const float* h, int64_t ld_h, const float* hbar, int64_t ld_hbar, const float* dinv, int32_t num_nodes, const int32_t* node_idx, int32_t n, const int32_t* rowptr_h, const int32_t* code, int32_t e, float* out, int64_t ld_out, int32_t f, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
+/* dh [n, f] of the backward above from da = d A [n, f], over rowptr_s int32[n + 1] / csr_dst of the batch's prepared induced entries.
+ * One launch, a group per local row, entries in the CSR's order: no float atomics, two runs give the same bits. */
+int grapes_gas_aggregate_bwd(const float* da, int64_t ld_da, const int32_t* node_idx, const float* dinv, int32_t num_nodes, const int32_t* rowptr_s, const int32_t* csr_dst, float* dh, int64_t ld_dh, int32_t n, int32_t f, int32_t* status, grapes_stream_t stream);
 
 /* ------------------------------------------------------------------ LABOR: the layer-neighbour sampler (csrc/labor_kernels.hip)
  * [Balin and Catalyurek, NeurIPS 2023; LABOR-recall: DGL's LaborSampler].  Neighbour sampling's per-row estimator with ONE variate
