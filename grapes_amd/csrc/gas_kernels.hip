@@ -35,7 +35,7 @@
 //
 // No float atomics: every sum has a fixed order (code order inside a row or chunk, chunk order across items), two runs give the
 // same bits.  No kernel waits on another workgroup.  A code outside [-N, n) raises GRAPES_STATUS_BAD_INDEX and is dropped; it then
-// contributes 0 times row 0 of H, so a non-finite value there would reach the sum (as in vrgcn_kernels.hip).
+// contributes 0 times row 0 of H (gather_batch, row_gather.h).
 #include "hist_rows.h"
 #include "row_list.h"
 
@@ -179,7 +179,6 @@ __device__ __forceinline__ void gas_row_range(const GasArgs& a, int r, int& beg,
 // acc += sum_{t in [beg, end)} dinv[v_t] (code_t >= 0 ? H[code_t] : Hbar[-1 - code_t])
 template <int VEC, int LPR, int NS>
 __device__ __forceinline__ void gas_walk(const GasArgs& a, int beg, int end, int l, float (&acc)[NS][VEC]) {
-    constexpr int U = HistUnroll<VEC, NS>::U;
     for (int b = beg; b < end; b += LPR) {
         const bool live = b + l < end;
         const int c = live ? a.code[b + l] : 0;
@@ -191,28 +190,19 @@ __device__ __forceinline__ void gas_walk(const GasArgs& a, int beg, int end, int
         if (live && !ok && a.status) atomicOr(a.status, GRAPES_STATUS_BAD_INDEX);
         gv = ok ? gv : 0;
         const float dv = a.dinv[gv];
-        const float w = ok ? dv : 0.f;
-        const int cc = ok ? c : 0;
+        const int cc = ok ? c : 0;                              // (a dropped lane points at row 0 of H)
         const int cnt = end - b < LPR ? end - b : LPR;
-        for (int k = 0; k < cnt; k += U) {                      // (lanes past cnt hold cc = 0, w = 0: row 0 of H times 0)
-            float hv[U][NS][VEC], wk[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int ck = __shfl(cc, k + u, LPR);
-                wk[u] = __shfl(w, k + u, LPR);
+        gather_batch<HistUnroll<VEC, NS>::U, VEC, LPR, NS>(
+            ok ? dv : 0.f, cnt,
+            [&](int j, float (&hv)[NS][VEC]) {
+                const int ck = __shfl(cc, j, LPR);
                 const bool in = ck >= 0;                        // selects, not branches: the U row loads leave together
                 const float* base = in ? a.h : a.hbar;
                 const long long ld = in ? a.ld_h : a.ld_hbar;
                 const long long row = in ? ck : -1 - ck;
-                row_load_ld<VEC, LPR, NS>(base, row, ld, a.F, l, hv[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int s = 0; s < NS; ++s)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(wk[u], hv[u][s][v], acc[s][v]);
-        }
+                row_load_ld<VEC, LPR, NS>(base, row, ld, a.F, l, hv);
+            },
+            acc);
     }
 }
 
@@ -225,7 +215,7 @@ __global__ __launch_bounds__(256) void gas_rows_k(GasArgs a, int skip_long) {
         float acc[NS][VEC];
         if ((unsigned)u >= (unsigned)a.N) {                                    // a row that names no node: zeros
             if (l == 0 && a.status) atomicOr(a.status, GRAPES_STATUS_BAD_INDEX);
-            hist_zero<VEC, NS>(acc);
+            slab_zero<VEC, NS>(acc);
             row_store_ld<VEC, LPR, NS>(a.out, r, a.ld_out, a.F, l, acc);
             continue;
         }
@@ -233,16 +223,10 @@ __global__ __launch_bounds__(256) void gas_rows_k(GasArgs a, int skip_long) {
         gas_row_range(a, r, beg, end);
         const float du = a.dinv[u];
         row_load_ld<VEC, LPR, NS>(a.h, r, a.ld_h, a.F, l, acc);
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] *= du;
+        slab_scale<VEC, NS>(acc, du);
         if (!(skip_long && end - beg > HIST_LONG_ROW)) {
             gas_walk<VEC, LPR, NS>(a, beg, end, l, acc);
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[s][v] *= du;
+            slab_scale<VEC, NS>(acc, du);
         }
         row_store_ld<VEC, LPR, NS>(a.out, r, a.ld_out, a.F, l, acc);
     }
@@ -281,7 +265,7 @@ __global__ __launch_bounds__(256) void gas_chunks_k(GasArgs a) {
         const int beg = cb < re ? (int)cb : re;
         const int end = re - beg > HIST_LONG_ROW ? beg + HIST_LONG_ROW : re;
         float acc[NS][VEC];
-        hist_zero<VEC, NS>(acc);
+        slab_zero<VEC, NS>(acc);
         gas_walk<VEC, LPR, NS>(a, beg, end, l, acc);
         row_store<VEC, LPR, NS>(a.pacc, it, a.F, l, acc);
     }
@@ -301,10 +285,8 @@ struct GasBwdTarget {
     __device__ __forceinline__ int self(int lv) const { return lv; }
 };
 
-// workspace: [item_off int32 (n + 1)] [pacc item_cap f]
 extern "C" size_t grapes_gas_aggregate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f) {
-    const size_t M = n > 0 ? (size_t)n : 0, I = item_cap > 0 ? (size_t)item_cap : 0, F = f > 0 ? (size_t)f : 1;
-    return grapes_round16((M + 1) * sizeof(int32_t)) + grapes_round16(I * F * sizeof(float)) + 16;
+    return hist_workspace_bytes(n, item_cap, f);
 }
 
 extern "C" int grapes_gas_aggregate_fwd(const float* h, int64_t ld_h, const float* hbar, int64_t ld_hbar, const float* dinv,
@@ -321,13 +303,11 @@ extern "C" int grapes_gas_aggregate_fwd(const float* h, int64_t ld_h, const floa
     hipStream_t s = (hipStream_t)stream;
     GasArgs a;
     a.h = h; a.ld_h = ld_h; a.hbar = hbar; a.ld_hbar = ld_hbar; a.dinv = dinv; a.N = num_nodes; a.rows_g = node_idx; a.m = n;
-    a.rowptr_h = rowptr_h; a.code = code; a.e = e; a.out = out; a.ld_out = ld_out; a.F = f; a.status = status; a.item_cap = item_cap;
-    int32_t* item_off = item_cap > 0 ? (int32_t*)workspace : nullptr;
-    a.item_off = item_off;
-    a.pacc = item_cap > 0 ? (float*)((char*)workspace + grapes_round16(((size_t)n + 1) * sizeof(int32_t))) : nullptr;
+    a.rowptr_h = rowptr_h; a.code = code; a.e = e; a.out = out; a.ld_out = ld_out; a.F = f; a.status = status;
+    hist_carve(a, workspace, item_cap);
     const bool vec = shape == 0;
     if (item_cap > 0) {
-        hipLaunchKernelGGL(gas_items_k, dim3(1), dim3(LIST_SCAN_THREADS), 0, s, a, item_off);
+        hipLaunchKernelGGL(gas_items_k, dim3(1), dim3(LIST_SCAN_THREADS), 0, s, a, (int32_t*)workspace);
         GRAPES_LAUNCH_CHECK();
     }
     ROW_LAUNCH(gas_rows_k, 4, vec, f, n, s, a, item_cap > 0 ? 1 : 0);

@@ -27,25 +27,14 @@
 
 __device__ __forceinline__ float gat_leaky(float x) { return x > 0.f ? x : GAT_SLOPE * x; }
 
-template <int VEC, int NS>
-__device__ __forceinline__ float gat_dot(const float (&a)[NS][VEC], const float (&b)[NS][VEC]) {
-    float d = 0.f;
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) d = fmaf(a[s][v], b[s][v], d);
-    return d;
-}
-
 // online softmax + weighted gather over entries [beg - with_self, end) of row `row`: (m, sum, acc) are updated in place
 template <int VEC, int LPR, int NS>
 __device__ __forceinline__ void gat_fwd_range(const float* __restrict__ h, const float* __restrict__ s_src,
                                               const int32_t* __restrict__ csr, int row, int n, float sd, int beg, int end,
                                               bool with_self, int F, int l, float& m, float& sum, float (&acc)[NS][VEC],
                                               int32_t* status) {
-    constexpr int U = RowUnroll<NS>::U;
     for (int b = with_self ? beg - 1 : beg; b < end; b += LPR) {
-        int idx;
+        int idx;                                               // (a dropped lane points at `row`)
         const bool ok = gat_entry(csr, b + l, beg, end, row, n, idx, status);
         const float e = ok ? gat_leaky(s_src[idx] + sd) : -INFINITY;
         const float mn = fmaxf(m, grp_max<LPR>(e));
@@ -54,26 +43,10 @@ __device__ __forceinline__ void gat_fwd_range(const float* __restrict__ h, const
         const float p = ok ? expf(e - mn) : 0.f;
         sum = fmaf(sum, sc, grp_sum<LPR>(p));
         m = mn;
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] *= sc;
+        slab_scale<VEC, NS>(acc, sc);
         const int cnt = end - b < LPR ? end - b : LPR;
-        for (int k = 0; k < cnt; k += U) {                     // (lanes past cnt hold idx = row, p = 0: no predicates)
-            float hv[U][NS][VEC], pk[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int ik = __shfl(idx, k + u, LPR);
-                pk[u] = __shfl(p, k + u, LPR);
-                row_load<VEC, LPR, NS>(h, ik, F, l, hv[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int s = 0; s < NS; ++s)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(pk[u], hv[u][s][v], acc[s][v]);
-        }
+        gather_batch<RowUnroll<NS>::U, VEC, LPR, NS>(
+            p, cnt, [&](int j, float (&hv)[NS][VEC]) { row_load<VEC, LPR, NS>(h, __shfl(idx, j, LPR), F, l, hv); }, acc);
     }
 }
 
@@ -89,10 +62,7 @@ __global__ __launch_bounds__(256) void gat_fwd_k(const float* __restrict__ h, co
         const int beg = rowptr[row], end = rowptr[row + 1];
         if (skip_long && end - beg > GRAPES_LONG_ROW) continue;          // gat_fwd_chunks_k + gat_fwd_combine_k
         float m = -INFINITY, sum = 0.f, acc[NS][VEC];
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
+        slab_zero<VEC, NS>(acc);
         gat_fwd_range<VEC, LPR, NS>(h, s_src, csr, row, n, s_dst[row], beg, end, true, F, l, m, sum, acc, status);
         const float inv = 1.f / sum;                                      // (sum >= 1: the entry at the maximum contributes 1)
 #pragma unroll
@@ -123,10 +93,7 @@ __global__ __launch_bounds__(256) void gat_fwd_chunks_k(const float* __restrict_
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
         int row, beg, end;
         float m = -INFINITY, sum = 0.f, acc[NS][VEC];
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
+        slab_zero<VEC, NS>(acc);
         item_range(items, it, rowptr, n, row, beg, end);
         if (beg < end) {
             gat_fwd_range<VEC, LPR, NS>(h, s_src, csr, row, n, s_dst[row], beg, end, false, F, l, m, sum, acc, status);
@@ -204,7 +171,7 @@ __global__ __launch_bounds__(256) void gat_scores_k(const float* __restrict__ h,
     for (int row = blockIdx.x * G + threadIdx.x / LPR; row < n; row += gridDim.x * G) {
         float hv[NS][VEC];
         row_load<VEC, LPR, NS>(h, row, F, l, hv);
-        const float ss = grp_sum<LPR>(gat_dot<VEC, NS>(hv, as)), sd = grp_sum<LPR>(gat_dot<VEC, NS>(hv, ad));
+        const float ss = grp_sum<LPR>(slab_dot<VEC, NS>(hv, as)), sd = grp_sum<LPR>(slab_dot<VEC, NS>(hv, ad));
         if (l == 0) { s_src[row] = ss; s_dst[row] = sd; }
     }
 }
@@ -221,12 +188,7 @@ __global__ __launch_bounds__(256) void gat_bwd_rows_k(const float* __restrict__ 
     const int l = threadIdx.x % LPR, G = 256 / LPR;
     float bv[NS][VEC];
     if (bias) row_load<VEC, LPR, NS>(bias, 0, F, l, bv);
-    else {
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) bv[s][v] = 0.f;
-    }
+    else slab_zero<VEC, NS>(bv);
     for (int row = blockIdx.x * G + threadIdx.x / LPR; row < n; row += gridDim.x * G) {
         float g[NS][VEC], o[NS][VEC];
         row_load<VEC, LPR, NS>(dout, row, F, l, g);
@@ -264,7 +226,7 @@ __device__ __forceinline__ float gat_bwd_dst_range(const float* __restrict__ h, 
 #pragma unroll
             for (int u = 0; u < U; ++u) row_load<VEC, LPR, NS>(h, __shfl(idx, k + u, LPR), F, l, hv[u]);
 #pragma unroll
-            for (int u = 0; u < U; ++u) d[u] = gat_dot<VEC, NS>(g, hv[u]);
+            for (int u = 0; u < U; ++u) d[u] = slab_dot<VEC, NS>(g, hv[u]);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 d[u] = grp_sum<LPR>(d[u]);
@@ -359,7 +321,9 @@ __device__ __forceinline__ float gat_bwd_src_range(const float* __restrict__ gma
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                d[u] = gat_dot<VEC, NS>(gv[u], hreg);
+                d[u] = slab_dot<VEC, NS>(gv[u], hreg);
+                // (bare, not slab_fma: beside the dot product the helper costs the <4, *, 1> kernels 11 - 19 VGPRs and a wave of
+                // occupancy, here and in wg_range: profiles/gather_batch_resources.txt)
 #pragma unroll
                 for (int s = 0; s < NS; ++s)
 #pragma unroll
@@ -383,10 +347,8 @@ __device__ __forceinline__ void gat_bwd_src_epilogue(float (&acc)[NS][VEC], floa
     float as[NS][VEC], ad[NS][VEC];
     row_load<VEC, LPR, NS>(a_src, 0, F, l, as);
     row_load<VEC, LPR, NS>(a_dst, 0, F, l, ad);
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(dsd, ad[s][v], fmaf(dss, as[s][v], acc[s][v]));
+    slab_fma<VEC, NS>(dss, as, acc);
+    slab_fma<VEC, NS>(dsd, ad, acc);
 }
 
 // long rows (skip_long): only the self-loop's terms, without the epilogue (gat_bwd_src_combine_k finishes them)
@@ -407,10 +369,7 @@ __global__ __launch_bounds__(256) void gat_bwd_src_k(const float* __restrict__ h
         if (is_long) end = beg;
         float hreg[NS][VEC], acc[NS][VEC];
         row_load<VEC, LPR, NS>(h, row, F, l, hreg);
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
+        slab_zero<VEC, NS>(acc);
         const float ds = grp_sum<LPR>(gat_bwd_src_range<VEC, LPR, NS>(gmat, row_q, csr, row, n, s_src[row], hreg, beg, end, true, F, l, acc, status));
         if (!is_long) gat_bwd_src_epilogue<VEC, LPR, NS>(acc, ds, ds_dst[row], a_src, a_dst, F, l);
         row_store<VEC, LPR, NS>(dh, row, F, l, acc);
@@ -431,10 +390,7 @@ __global__ __launch_bounds__(256) void gat_bwd_src_chunks_k(const float* __restr
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
         int row, beg, end;
         float ds = 0.f, acc[NS][VEC];
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
+        slab_zero<VEC, NS>(acc);
         item_range(items, it, rowptr, n, row, beg, end);
         if (beg < end) {
             float hreg[NS][VEC];

@@ -79,14 +79,6 @@ __device__ __forceinline__ void head_sum(float (&p)[NV][NS], const int (&hd)[NS]
         for (int s = 0; s < NS; ++s) p[q][s] = r[q][s];
 }
 
-template <int VEC, int NS>
-__device__ __forceinline__ void gv2_zero(float (&a)[NS][VEC]) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) a[s][v] = 0.f;
-}
-
 // this lane's partial of att . LeakyReLU(x_l + x_r) per slab
 template <int VEC, int NS>
 __device__ __forceinline__ void gv2_score(const float (&hv)[NS][VEC], const float (&xr)[NS][VEC], const float (&at)[NS][VEC],
@@ -166,7 +158,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_k(const float* __restrict__ xl,
     float at[NS][VEC], bv[NS][VEC];
     row_load<VEC, LPR, NS>(att, 0, F, l, at);
     if (concat && bias) row_load<VEC, LPR, NS>(bias, 0, F, l, bv);
-    else gv2_zero<VEC, NS>(bv);
+    else slab_zero<VEC, NS>(bv);
     for (int row = blockIdx.x * G + threadIdx.x / LPR; row < n; row += gridDim.x * G) {
         const int beg = rowptr[row];
         int end = rowptr[row + 1];
@@ -174,7 +166,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_k(const float* __restrict__ xl,
         if (is_long) end = beg;
         float xr[NS][VEC], acc[NS][VEC], m[NS], sum[NS];
         row_load<VEC, LPR, NS>(xrm, row, F, l, xr);
-        gv2_zero<VEC, NS>(acc);
+        slab_zero<VEC, NS>(acc);
 #pragma unroll
         for (int s = 0; s < NS; ++s) { m[s] = -INFINITY; sum[s] = 0.f; }
         gv2_fwd_range<VEC, LPR, NS>(xl, csr, row, n, xr, at, hd, H, lh, slope, beg, end, true, F, l, m, sum, acc, status);
@@ -217,7 +209,7 @@ __global__ __launch_bounds__(256) void gatv2_fwd_chunks_k(const float* __restric
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
         int row, beg, end;
         float acc[NS][VEC], m[NS], sum[NS];
-        gv2_zero<VEC, NS>(acc);
+        slab_zero<VEC, NS>(acc);
 #pragma unroll
         for (int s = 0; s < NS; ++s) { m[s] = -INFINITY; sum[s] = 0.f; }
         item_range(items, it, rowptr, n, row, beg, end);
@@ -458,8 +450,8 @@ __global__ __launch_bounds__(256) void gatv2_bwd_dst_k(const float* __restrict__
     gv2_heads<VEC, LPR, NS>(F, C, l, hd, lh);
     float at[NS][VEC], datt[NS][VEC], gsum[NS][VEC];
     row_load<VEC, LPR, NS>(att, 0, F, l, at);
-    gv2_zero<VEC, NS>(datt);
-    gv2_zero<VEC, NS>(gsum);
+    slab_zero<VEC, NS>(datt);
+    slab_zero<VEC, NS>(gsum);
     for (int row = blockIdx.x * G + threadIdx.x / LPR; row < n; row += gridDim.x * G) {
         const int beg = rowptr[row];
         int end = rowptr[row + 1];
@@ -469,7 +461,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_dst_k(const float* __restrict__
         row_load<VEC, LPR, NS>(xrm, row, F, l, xr);
         row_load<VEC, LPR, NS>(gmat, row, F, l, g);
         gv2_row_q<NS>(row_q, row, H, hd, q);
-        gv2_zero<VEC, NS>(dxr);
+        slab_zero<VEC, NS>(dxr);
         gv2_bwd_dst_range<VEC, LPR, NS>(xl, csr, row, n, xr, at, g, q, hd, H, lh, slope, beg, end, true, F, l, dxr, datt, status);
         row_store<VEC, LPR, NS>(dxrm, row, F, l, dxr);
 #pragma unroll
@@ -498,11 +490,11 @@ __global__ __launch_bounds__(256) void gatv2_bwd_dst_chunks_k(const float* __res
     gv2_heads<VEC, LPR, NS>(F, C, l, hd, lh);
     float at[NS][VEC], datt[NS][VEC];
     row_load<VEC, LPR, NS>(att, 0, F, l, at);
-    gv2_zero<VEC, NS>(datt);
+    slab_zero<VEC, NS>(datt);
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
         int row, beg, end;
         float dxr[NS][VEC];
-        gv2_zero<VEC, NS>(dxr);
+        slab_zero<VEC, NS>(dxr);
         item_range(items, it, rowptr, n, row, beg, end);
         if (beg < end) {
             float xr[NS][VEC], g[NS][VEC];
@@ -608,7 +600,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_src_k(const float* __restrict__
         if (skip_long && end - beg > GRAPES_LONG_ROW) end = beg;
         float xlr[NS][VEC], acc[NS][VEC];
         row_load<VEC, LPR, NS>(xl, row, F, l, xlr);
-        gv2_zero<VEC, NS>(acc);
+        slab_zero<VEC, NS>(acc);
         gv2_bwd_src_range<VEC, LPR, NS>(xrm, gmat, row_q, csr, row, n, xlr, at, hd, H, lh, slope, beg, end, true, F, l, acc, status);
         row_store<VEC, LPR, NS>(dxl, row, F, l, acc);
     }
@@ -631,7 +623,7 @@ __global__ __launch_bounds__(256) void gatv2_bwd_src_chunks_k(const float* __res
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
         int row, beg, end;
         float acc[NS][VEC];
-        gv2_zero<VEC, NS>(acc);
+        slab_zero<VEC, NS>(acc);
         item_range(items, it, rowptr, n, row, beg, end);
         if (beg < end) {
             float xlr[NS][VEC];

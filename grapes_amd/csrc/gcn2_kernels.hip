@@ -45,18 +45,12 @@ struct G2Epi {
     }
     template <int VEC, int LPR, int NS>
     __device__ __forceinline__ void finish(float (&acc)[NS][VEC], int row, int, int F, int l) const {
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] *= c_acc;
+        slab_scale<VEC, NS>(acc, c_acc);
         if (out2) row_store<VEC, LPR, NS>(out2, row, F, l, acc);
         if (self_mat) {
             float x0[NS][VEC];
             row_load<VEC, LPR, NS>(self_mat, row, F, l, x0);
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(c_self, x0[s][v], acc[s][v]);
+            slab_fma<VEC, NS>(c_self, x0, acc);
         }
         row_store<VEC, LPR, NS>(out1, row, F, l, acc);
     }

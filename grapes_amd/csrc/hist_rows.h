@@ -5,6 +5,9 @@
 //   hist_combine_k    a group per listed row: the long row's items added in chunk order to what the rows kernel left, then dinv_u
 //   hist_bwd_k        a group per local row over the by-source CSR of a preparation, entries in the CSR's order; WHAT a target
 //                     contributes (which row of dA, which factor) is the caller's policy
+//   hist_workspace_bytes, hist_carve   the forward's workspace [item_off | pacc] and its two pointers.  (The launches after it —
+//                     items, rows, chunks, hist_combine_k — stay written out in the two files: their kernels differ by name, and
+//                     one body for both would be a macro that takes kernel names.)
 // No float atomics: every sum has a fixed order.
 #pragma once
 #include "row_gather.h"
@@ -26,14 +29,6 @@ template <int VEC, int NS> struct HistUnroll {
     static constexpr int B = VRGCN_FULL_BUDGET / (NS * VEC), M = VRGCN_FULL_BUDGET / 4;
     static constexpr int U = B > M ? M : (B > RowUnroll<NS>::U ? B : RowUnroll<NS>::U);
 };
-
-template <int VEC, int NS>
-__device__ __forceinline__ void hist_zero(float (&acc)[NS][VEC]) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
-}
 
 // A: the forward's arguments — item_off int32[m + 1] (a row's first item), m listed rows with global ids rows_g, N, out / ld_out,
 // pacc [items, F], dinv, F.
@@ -66,11 +61,7 @@ __global__ __launch_bounds__(256) void hist_combine_k(A a) {
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) acc[s][v] += p[0][s][v];
         }
-        const float du = a.dinv[u];
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] *= du;
+        slab_scale<VEC, NS>(acc, a.dinv[u]);
         row_store_ld<VEC, LPR, NS>(a.out, r, a.ld_out, a.F, l, acc);
     }
 }
@@ -89,11 +80,10 @@ struct HistBwdArgs {
 // T: row(c, status) = the row of da a target c reads or -1 (dropped), weight(r) = its factor, self(lv) = lv's own row of da or -1.
 template <int VEC, int LPR, int NS, class T>
 __global__ __launch_bounds__(256) void hist_bwd_k(HistBwdArgs a, T tgt) {
-    constexpr int U = RowUnroll<NS>::U;
     const int l = threadIdx.x % LPR, G = 256 / LPR;
     for (int lv = blockIdx.x * G + threadIdx.x / LPR; lv < a.n_local; lv += gridDim.x * G) {
         float acc[NS][VEC];
-        hist_zero<VEC, NS>(acc);
+        slab_zero<VEC, NS>(acc);
         const int gv = a.node_idx[lv];
         if ((unsigned)gv >= (unsigned)a.N) {
             if (l == 0 && a.status) atomicOr(a.status, GRAPES_STATUS_BAD_INDEX);
@@ -104,42 +94,37 @@ __global__ __launch_bounds__(256) void hist_bwd_k(HistBwdArgs a, T tgt) {
         for (int b = beg; b < end; b += LPR) {
             const int c = batch_entry(a.csr_dst, b + l, end, a.n_local, a.status);
             const int r = c >= 0 ? tgt.row(c, a.status) : -1;
-            const int idx = r < 0 ? 0 : r;
-            const float w = r < 0 ? 0.f : tgt.weight(r);
+            const int idx = r < 0 ? 0 : r;                      // (a dropped lane points at row 0 of da)
             const int cnt = end - b < LPR ? end - b : LPR;
-            for (int k = 0; k < cnt; k += U) {
-                float gv_[U][NS][VEC], wk[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const int ik = __shfl(idx, k + u, LPR);
-                    wk[u] = __shfl(w, k + u, LPR);
-                    row_load_ld<VEC, LPR, NS>(a.da, ik, a.ld_da, a.F, l, gv_[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-#pragma unroll
-                    for (int s = 0; s < NS; ++s)
-#pragma unroll
-                        for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(wk[u], gv_[u][s][v], acc[s][v]);
-            }
+            gather_batch<RowUnroll<NS>::U, VEC, LPR, NS>(
+                r < 0 ? 0.f : tgt.weight(r), cnt,
+                [&](int j, float (&g)[NS][VEC]) { row_load_ld<VEC, LPR, NS>(a.da, __shfl(idx, j, LPR), a.ld_da, a.F, l, g); }, acc);
         }
         const float dv = a.dinv[gv];
         const int rs = tgt.self(lv);
         if (rs >= 0) {
             float g[NS][VEC];
             row_load_ld<VEC, LPR, NS>(a.da, rs, a.ld_da, a.F, l, g);
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[s][v] = dv * fmaf(dv, g[s][v], acc[s][v]);
-        } else {
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[s][v] *= dv;
+            slab_fma<VEC, NS>(dv, g, acc);
         }
+        slab_scale<VEC, NS>(acc, dv);
         row_store_ld<VEC, LPR, NS>(a.dh, lv, a.ld_dh, a.F, l, acc);
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------ host side
+
 static inline bool hist_vec_ok(const void* p, int64_t ld) { return grapes_aligned16(p) && ld % 4 == 0; }
+
+// the forward's workspace: [item_off int32 (m + 1)] [pacc item_cap f]
+static inline size_t hist_workspace_bytes(int32_t m, int32_t item_cap, int32_t f) {
+    const size_t M = m > 0 ? (size_t)m : 0, I = item_cap > 0 ? (size_t)item_cap : 0, F = f > 0 ? (size_t)f : 1;
+    return grapes_round16((M + 1) * sizeof(int32_t)) + grapes_round16(I * F * sizeof(float)) + 16;
+}
+// ... carved into A's item_off and pacc (both NULL without long-row items); A::m is set
+template <class A>
+static inline void hist_carve(A& a, void* workspace, int32_t item_cap) {
+    a.item_cap = item_cap;
+    a.item_off = item_cap > 0 ? (const int32_t*)workspace : nullptr;
+    a.pacc = item_cap > 0 ? (float*)((char*)workspace + grapes_round16(((size_t)a.m + 1) * sizeof(int32_t))) : nullptr;
+}

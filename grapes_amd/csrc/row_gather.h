@@ -7,8 +7,11 @@
 //   *_chunks_k    rows longer than GRAPES_LONG_ROW: one group per work item (row, chunk) of the prepared item list (item_range)
 //   *_combine_k   one workgroup per long row, led by its chunk-0 item (item_leads), merges the row's items in chunk order
 //
-// Device side: the slab layout of a row over a group's lanes, the group butterflies, the item-list readers and the batch-entry
-// reader.  Host side: the grids and the launch-by-width dispatch.  What a kernel accumulates, and its epilogue, stay in its file.
+// Device side: the slab layout of a row over a group's lanes and its arithmetic (slab_zero, _scale, _fma, _dot), the group
+// butterflies, the item-list readers, the batch-entry reader and gather_batch, the weighted gather of one batch of entries: a walk
+// says which rows a batch names and with which weights, and how a row is fetched.  Host side: the grids and the launch-by-width
+// dispatch.  What a kernel weighs its entries with, and its epilogue, stay in its file; so does the gather loop of a walk that
+// reduces a per-entry dot product over the group inside it (wg_range, GAT's backward ranges, GATv2's three).
 #pragma once
 #include "common.h"
 
@@ -163,6 +166,58 @@ __device__ __forceinline__ bool gat_entry(const int32_t* __restrict__ csr, int t
 
 // gathered rows a group keeps in flight per step of a gather loop: independent row loads, as many as the registers of NS slabs allow
 template <int NS> struct RowUnroll { static constexpr int U = NS == 1 ? 4 : (NS <= 4 ? 2 : 1); };
+
+// a lane's slabs of a row, a[NS][VEC]: zero, scale, acc += w x, and the dot product as one fmaf chain in (s, v) order
+template <int VEC, int NS>
+__device__ __forceinline__ void slab_zero(float (&a)[NS][VEC]) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) a[s][v] = 0.f;
+}
+template <int VEC, int NS>
+__device__ __forceinline__ void slab_scale(float (&a)[NS][VEC], float c) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) a[s][v] *= c;
+}
+template <int VEC, int NS>
+__device__ __forceinline__ void slab_fma(float w, const float (&x)[NS][VEC], float (&acc)[NS][VEC]) {
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(w, x[s][v], acc[s][v]);
+}
+template <int VEC, int NS>
+__device__ __forceinline__ float slab_dot(const float (&a)[NS][VEC], const float (&b)[NS][VEC]) {
+    float d = 0.f;
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) d = fmaf(a[s][v], b[s][v], d);
+    return d;
+}
+
+// One batch of a weighted gather: lane j < cnt of the group holds the weight w of entry j; load(j, hv) fetches entry j's row
+// (it broadcasts whatever index it needs from lane j).  U rows are requested together, then added in entry order.
+// No load is predicated: a lane past cnt and a lane whose entry was dropped hold weight 0 and the index of a row that is always
+// there (the caller says which), so they add 0 * that row.  Finite operands are unaffected; a non-finite value in that row would
+// put NaN into the sum.  The select form, acc += live ? h : 0, has no such case but costs the small-graph rows kernel of GCN2
+// 3 - 4 %: profiles/row_sum_ab.txt.
+template <int U, int VEC, int LPR, int NS, class LOAD>
+__device__ __forceinline__ void gather_batch(float w, int cnt, LOAD load, float (&acc)[NS][VEC]) {
+    for (int k = 0; k < cnt; k += U) {
+        float hv[U][NS][VEC], wk[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            wk[u] = __shfl(w, k + u, LPR);
+            load(k + u, hv[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) slab_fma<VEC, NS>(wk[u], hv[u], acc);
+    }
+}
 
 // ------------------------------------------------------------------------------------------------------------ host side
 

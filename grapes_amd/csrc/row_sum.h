@@ -16,34 +16,16 @@
 #include "row_gather.h"
 
 // acc += sum of the rows m[csr[t]], t in [beg, end), rows ld floats apart.  An index outside [0, n) raises
-// GRAPES_STATUS_BAD_INDEX and the entry is dropped: its lane keeps the row itself with weight 0, so the loads need no predicate.
-// (Lanes past a batch's end and dropped entries add 0 * m[row]: finite operands are unaffected; a non-finite value in the row's own
-// m would put NaN into its sum.  The select form, acc += live ? h : 0, has no such case but costs the small-graph rows kernel of
-// GCN2 3 - 4 %: profiles/row_sum_ab.txt.)
+// GRAPES_STATUS_BAD_INDEX and the entry is dropped: its lane, like the lanes past a batch's end, points at `row` with weight 0.
 template <int VEC, int LPR, int NS>
 __device__ __forceinline__ void row_sum_gather(const float* __restrict__ m, long long ld, const int32_t* __restrict__ csr, int row,
                                                int n, int beg, int end, int F, int l, float (&acc)[NS][VEC], int32_t* status) {
-    constexpr int U = RowUnroll<NS>::U;
     for (int b = beg; b < end; b += LPR) {
         const int c = batch_entry(csr, b + l, end, n, status);
         const int idx = c < 0 ? row : c;
-        const float w = c < 0 ? 0.f : 1.f;
         const int cnt = end - b < LPR ? end - b : LPR;
-        for (int k = 0; k < cnt; k += U) {                      // (lanes past cnt hold idx = row, w = 0)
-            float hv[U][NS][VEC], wk[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int ik = __shfl(idx, k + u, LPR);
-                wk[u] = __shfl(w, k + u, LPR);
-                row_load_ld<VEC, LPR, NS>(m, ik, ld, F, l, hv[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int s = 0; s < NS; ++s)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(wk[u], hv[u][s][v], acc[s][v]);
-        }
+        gather_batch<RowUnroll<NS>::U, VEC, LPR, NS>(
+            c < 0 ? 0.f : 1.f, cnt, [&](int j, float (&hv)[NS][VEC]) { row_load_ld<VEC, LPR, NS>(m, __shfl(idx, j, LPR), ld, F, l, hv); }, acc);
     }
 }
 
@@ -58,20 +40,13 @@ __global__ __launch_bounds__(256) void row_sum_rows_k(EPI e, const int32_t* __re
         e.template pre<VEC, LPR, NS>(row, F, l);
         if (skip_long && end - beg > GRAPES_LONG_ROW) continue;
         float acc[NS][VEC];
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
+        slab_zero<VEC, NS>(acc);
         row_sum_gather<VEC, LPR, NS>(e.src, e.ld_src, csr, row, n, beg, end, F, l, acc, status);
         const int lp = e.loops ? e.loops[row] : 0;
         if (lp != 0) {
             float xr[NS][VEC];
             row_load_ld<VEC, LPR, NS>(e.src, row, e.ld_src, F, l, xr);
-            const float lf = (float)lp;
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(lf, xr[s][v], acc[s][v]);
+            slab_fma<VEC, NS>((float)lp, xr, acc);
         }
         e.template finish<VEC, LPR, NS>(acc, row, (end - beg) + lp, F, l);
     }
@@ -89,10 +64,7 @@ __global__ __launch_bounds__(256) void row_sum_chunks_k(const float* __restrict_
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
         int row, beg, end;
         float acc[NS][VEC];
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = 0.f;
+        slab_zero<VEC, NS>(acc);
         item_range(items, it, rowptr, n, row, beg, end);
         if (beg < end) row_sum_gather<VEC, LPR, NS>(m, ld, csr, row, n, beg, end, F, l, acc, status);
         row_store<VEC, LPR, NS>(pacc, it, F, l, acc);

@@ -26,8 +26,7 @@
 //   hist_bwd_k        (hist_rows.h, VrBwdTarget) a group per local row, entries in the CSR's order
 // No float atomics anywhere: every sum has a fixed order (entry order inside a row or chunk, chunk order across items), two runs
 // give the same bits.  No kernel waits on another workgroup.  An index outside its table raises GRAPES_STATUS_BAD_INDEX and the
-// entry is dropped; it then contributes 0 times row 0 of the table, so a non-finite value there would reach the sum (as in
-// row_sum.h, where the stand-in is the row itself).
+// entry is dropped; it then contributes 0 times row 0 of the table (gather_batch, row_gather.h).
 #include "hist_rows.h"
 #include "row_list.h"
 
@@ -56,7 +55,6 @@ struct VrArgs {
 // acc += sum_{t in [beg, end)} dinv[v] Hbar[v], v = col[t]: the rows of the history read in place by global id
 template <int VEC, int LPR, int NS>
 __device__ __forceinline__ void vr_full_walk(const VrArgs& a, long long beg, long long end, int l, float (&acc)[NS][VEC]) {
-    constexpr int U = VrUnroll<VEC, NS>::U;
     for (long long b = beg; b < end; b += LPR) {
         int c = -1;
         if (b + l < end) {
@@ -66,31 +64,17 @@ __device__ __forceinline__ void vr_full_walk(const VrArgs& a, long long beg, lon
                 if (a.status) atomicOr(a.status, GRAPES_STATUS_BAD_INDEX);
             }
         }
-        const int idx = c < 0 ? 0 : c;
-        const float w = c < 0 ? 0.f : a.dinv[c];
+        const int idx = c < 0 ? 0 : c;                          // (a dropped lane points at row 0 of Hbar)
         const int cnt = end - b < LPR ? (int)(end - b) : LPR;
-        for (int k = 0; k < cnt; k += U) {                      // (lanes past cnt hold idx = 0, w = 0)
-            float hv[U][NS][VEC], wk[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int ik = __shfl(idx, k + u, LPR);
-                wk[u] = __shfl(w, k + u, LPR);
-                row_load_ld<VEC, LPR, NS>(a.hbar, ik, a.ld_hbar, a.F, l, hv[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int s = 0; s < NS; ++s)
-#pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(wk[u], hv[u][s][v], acc[s][v]);
-        }
+        gather_batch<VrUnroll<VEC, NS>::U, VEC, LPR, NS>(
+            c < 0 ? 0.f : a.dinv[c], cnt,
+            [&](int j, float (&hv)[NS][VEC]) { row_load_ld<VEC, LPR, NS>(a.hbar, __shfl(idx, j, LPR), a.ld_hbar, a.F, l, hv); }, acc);
     }
 }
 
 // acc += sum_{t in [kb, ke)} dinv[v] (H[lv] - Hbar[v]), lv = csr_k[t], v = node_idx[lv]
 template <int VEC, int LPR, int NS>
 __device__ __forceinline__ void vr_kept_walk(const VrArgs& a, int kb, int ke, int l, float (&acc)[NS][VEC]) {
-    constexpr int U = RowUnroll<NS>::U;
     for (int b = kb; b < ke; b += LPR) {
         int lv = batch_entry(a.csr_k, b + l, ke, a.n_local, a.status);
         int gv = 0;
@@ -101,25 +85,20 @@ __device__ __forceinline__ void vr_kept_walk(const VrArgs& a, int kb, int ke, in
                 if (a.status) atomicOr(a.status, GRAPES_STATUS_BAD_INDEX);
             }
         }
-        const int il = lv < 0 ? 0 : lv, ig = lv < 0 ? 0 : gv;
-        const float w = lv < 0 ? 0.f : a.dinv[ig];
+        const int il = lv < 0 ? 0 : lv, ig = lv < 0 ? 0 : gv;   // (a dropped lane points at row 0 of H and of Hbar)
         const int cnt = ke - b < LPR ? ke - b : LPR;
-        for (int k = 0; k < cnt; k += U) {
-            float hv[U][NS][VEC], bv[U][NS][VEC], wk[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int ilk = __shfl(il, k + u, LPR), igk = __shfl(ig, k + u, LPR);
-                wk[u] = __shfl(w, k + u, LPR);
-                row_load_ld<VEC, LPR, NS>(a.h, ilk, a.ld_h, a.F, l, hv[u]);
-                row_load_ld<VEC, LPR, NS>(a.hbar, igk, a.ld_hbar, a.F, l, bv[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u)
+        gather_batch<RowUnroll<NS>::U, VEC, LPR, NS>(
+            lv < 0 ? 0.f : a.dinv[ig], cnt,
+            [&](int j, float (&hv)[NS][VEC]) {
+                float bv[NS][VEC];
+                row_load_ld<VEC, LPR, NS>(a.h, __shfl(il, j, LPR), a.ld_h, a.F, l, hv);
+                row_load_ld<VEC, LPR, NS>(a.hbar, __shfl(ig, j, LPR), a.ld_hbar, a.F, l, bv);
 #pragma unroll
                 for (int s = 0; s < NS; ++s)
 #pragma unroll
-                    for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(wk[u], hv[u][s][v] - bv[u][s][v], acc[s][v]);
-        }
+                    for (int v = 0; v < VEC; ++v) hv[s][v] -= bv[s][v];
+            },
+            acc);
     }
 }
 
@@ -130,7 +109,7 @@ __global__ __launch_bounds__(256) void vrgcn_rows_k(VrArgs a, int skip_long) {
     for (int r = blockIdx.x * G + threadIdx.x / LPR; r < a.m; r += gridDim.x * G) {
         const int u = a.rows_g[r], lu = a.rows_l[r];
         float acc[NS][VEC];
-        hist_zero<VEC, NS>(acc);
+        slab_zero<VEC, NS>(acc);
         if ((unsigned)u >= (unsigned)a.N || (unsigned)lu >= (unsigned)a.n_local) {      // a row that names no node: zeros
             if (l == 0 && a.status) atomicOr(a.status, GRAPES_STATUS_BAD_INDEX);
             if (l == 0 && a.coef) a.coef[r] = 0.f;
@@ -145,16 +124,11 @@ __global__ __launch_bounds__(256) void vrgcn_rows_k(VrArgs a, int skip_long) {
         if (l == 0 && a.coef) a.coef[r] = sc * du;
         float xr[NS][VEC];
         row_load_ld<VEC, LPR, NS>(a.h, lu, a.ld_h, a.F, l, xr);
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) acc[s][v] = fmaf(du, xr[s][v], sc * acc[s][v]);
+        slab_scale<VEC, NS>(acc, sc);
+        slab_fma<VEC, NS>(du, xr, acc);
         if (!(skip_long && re - rb > VRGCN_LONG_ROW)) {
             vr_full_walk<VEC, LPR, NS>(a, rb, re, l, acc);
-#pragma unroll
-            for (int s = 0; s < NS; ++s)
-#pragma unroll
-                for (int v = 0; v < VEC; ++v) acc[s][v] *= du;
+            slab_scale<VEC, NS>(acc, du);
         }
         row_store_ld<VEC, LPR, NS>(a.out, r, a.ld_out, a.F, l, acc);
     }
@@ -198,7 +172,7 @@ __global__ __launch_bounds__(256) void vrgcn_chunks_k(VrArgs a) {
         const int r = lower_bound<int32_t, int, int>(a.item_off, a.m, it + 1) - 1;
         const ListRow R = list_row(a.rowptr, a.N, a.rows_g, r, a.m, nullptr);
         float acc[NS][VEC];
-        hist_zero<VEC, NS>(acc);
+        slab_zero<VEC, NS>(acc);
         if (R.i >= 0) {
             const long long beg = R.a + (long long)(it - a.item_off[r]) * VRGCN_LONG_ROW, re = R.a + R.deg;
             const long long end = beg + VRGCN_LONG_ROW < re ? beg + VRGCN_LONG_ROW : re;
@@ -233,10 +207,8 @@ struct VrBwdTarget {
 
 extern "C" int32_t grapes_vrgcn_long_row(void) { return VRGCN_LONG_ROW; }
 
-// workspace: [item_off int32 (m + 1)] [pacc item_cap f]
 extern "C" size_t grapes_vrgcn_aggregate_workspace_bytes(int32_t m, int32_t item_cap, int32_t f) {
-    const size_t M = m > 0 ? (size_t)m : 0, I = item_cap > 0 ? (size_t)item_cap : 0, F = f > 0 ? (size_t)f : 1;
-    return grapes_round16((M + 1) * sizeof(int32_t)) + grapes_round16(I * F * sizeof(float)) + 16;
+    return hist_workspace_bytes(m, item_cap, f);
 }
 
 extern "C" int grapes_vrgcn_aggregate_fwd(const float* h, int64_t ld_h, const int32_t* node_idx, int32_t n_local, const float* hbar,
@@ -257,14 +229,11 @@ extern "C" int grapes_vrgcn_aggregate_fwd(const float* h, int64_t ld_h, const in
     a.h = h; a.ld_h = ld_h; a.n_local = n_local; a.node_idx = node_idx; a.hbar = hbar; a.ld_hbar = ld_hbar; a.dinv = dinv;
     a.rowptr = rowptr; a.col = col; a.N = num_nodes; a.rows_g = rows_g; a.rows_l = rows_l; a.m = m; a.rowptr_k = rowptr_k;
     a.csr_k = csr_k; a.out = out; a.ld_out = ld_out; a.coef = coef; a.F = f; a.status = status;
-    a.item_cap = item_cap;
-    int32_t* item_off = item_cap > 0 ? (int32_t*)workspace : nullptr;
-    a.item_off = item_off;
-    a.pacc = item_cap > 0 ? (float*)((char*)workspace + grapes_round16(((size_t)m + 1) * sizeof(int32_t))) : nullptr;
+    hist_carve(a, workspace, item_cap);
     const bool vec = shape == 0;
     if (item_cap > 0) {
-        hipLaunchKernelGGL(vrgcn_items_k, dim3(1), dim3(VRGCN_SCAN_THREADS), 0, s, rowptr, num_nodes, rows_g, m, item_cap, item_off,
-                           status);
+        hipLaunchKernelGGL(vrgcn_items_k, dim3(1), dim3(VRGCN_SCAN_THREADS), 0, s, rowptr, num_nodes, rows_g, m, item_cap,
+                           (int32_t*)workspace, status);
         GRAPES_LAUNCH_CHECK();
     }
     ROW_LAUNCH(vrgcn_rows_k, 4, vec, f, m, s, a, item_cap > 0 ? 1 : 0);

@@ -47,28 +47,10 @@ enum { WG_ACC = 0, WG_ACC_DOT = 1, WG_DOT = 2 };
 // the rule for lw and the normalisation: GRAPES_WGCN_LOOP_FILL / _LOOP_SUM / _UNNORMALIZED of the header
 enum { WG_LOOP_FILL = GRAPES_WGCN_LOOP_FILL, WG_LOOP_SUM = GRAPES_WGCN_LOOP_SUM, WG_UNNORM = GRAPES_WGCN_UNNORMALIZED };
 
-template <int VEC, int NS>
-__device__ __forceinline__ float wg_dot(const float (&a)[NS][VEC], const float (&b)[NS][VEC]) {
-    float d = 0.f;
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) d = fmaf(a[s][v], b[s][v], d);
-    return d;
-}
-template <int VEC, int NS>
-__device__ __forceinline__ void wg_zero(float (&a)[NS][VEC]) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-        for (int v = 0; v < VEC; ++v) a[s][v] = 0.f;
-}
-
 // Entries [beg, end) of row `row`: acc += sum_e val_e dinv[col_e] m[col_e] (MODE != WG_DOT) and, MODE != WG_ACC, the dot product
 // p_e = m[col_e] . oth of every entry (stored at its slot when pslot != NULL); returns this lane's share of sum_e val_e dinv[col_e] p_e.
-// An index outside [0, n) raises GRAPES_STATUS_BAD_INDEX and the entry is dropped (its lane keeps the row itself with weight 0).
-// Lanes past a batch's end and dropped entries still load m[row] and add 0 * m[row]: a NON-FINITE value in the row's own m puts NaN
-// into its sums where the exact result holds none (the sibling aggregations do the same; finite operands are unaffected).
+// An index outside [0, n) raises GRAPES_STATUS_BAD_INDEX and the entry is dropped: its lane, like the lanes past a batch's end, points
+// at `row` with weight 0 (as in gather_batch, row_gather.h; the loop stays here for the group reduction inside it).
 // NORM false (GRAPES_WGCN_UNNORMALIZED): the weight of an entry is val_e alone; dinv is never read and the returned share is unused.
 template <int MODE, int VEC, int LPR, int NS, bool NORM = true>
 __device__ __forceinline__ float wg_range(const float* __restrict__ m, const int32_t* __restrict__ csr, const float* __restrict__ val,
@@ -93,8 +75,8 @@ __device__ __forceinline__ float wg_range(const float* __restrict__ m, const int
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-                if (MODE != WG_ACC) d[u] = wg_dot<VEC, NS>(hv[u], oth);
-                if (MODE != WG_DOT) {
+                if (MODE != WG_ACC) d[u] = slab_dot<VEC, NS>(hv[u], oth);
+                if (MODE != WG_DOT) {                           // (bare, not slab_fma: see gat_bwd_src_range, gat_kernels.hip)
 #pragma unroll
                     for (int s = 0; s < NS; ++s)
 #pragma unroll
@@ -161,11 +143,11 @@ __device__ __forceinline__ void wg_rows_body(const WgEpi& e, const float* __rest
         if (MODE == WG_ACC && is_long) continue;
         float self[NS][VEC], oth[NS][VEC], acc[NS][VEC];
         row_load<VEC, LPR, NS>(e.m, row, F, l, self);
-        wg_zero<VEC, NS>(acc);
-        wg_zero<VEC, NS>(oth);
+        slab_zero<VEC, NS>(acc);
+        slab_zero<VEC, NS>(oth);
         if (MODE == WG_ACC_DOT) {
             row_load<VEC, LPR, NS>(oth_m, row, F, l, oth);
-            const float g = grp_sum<LPR>(wg_dot<VEC, NS>(self, oth));
+            const float g = grp_sum<LPR>(slab_dot<VEC, NS>(self, oth));
             if (l == 0) gh[row] = g;
             if (is_long) continue;
         }
@@ -220,8 +202,8 @@ __device__ __forceinline__ void wg_chunks_body(const float* __restrict__ m, cons
     for (int it = blockIdx.x * G + threadIdx.x / LPR; it < n_items; it += gridDim.x * G) {
         int row, beg, end;
         float acc[NS][VEC], oth[NS][VEC], part = 0.f;
-        wg_zero<VEC, NS>(acc);
-        wg_zero<VEC, NS>(oth);
+        slab_zero<VEC, NS>(acc);
+        slab_zero<VEC, NS>(oth);
         item_range(items, it, rowptr, n, row, beg, end);
         if (beg < end) {
             if (MODE == WG_ACC_DOT) row_load<VEC, LPR, NS>(oth_m, row, F, l, oth);
@@ -313,7 +295,7 @@ __device__ __forceinline__ void wg_dst_body(const float* __restrict__ h, const f
         if (skip_long && end - beg > GRAPES_LONG_ROW) continue;
         float g[NS][VEC], none[NS][VEC];
         row_load<VEC, LPR, NS>(gmat, row, F, l, g);
-        wg_zero<VEC, NS>(none);
+        slab_zero<VEC, NS>(none);
         const float mine = wg_range<WG_DOT, VEC, LPR, NS, NORM>(h, csr, val, dinv, row, n, beg, end, F, l, none, g, p_slot, status);
         if (NORM) {
             const float part = grp_sum<LPR>(mine);
@@ -353,7 +335,7 @@ __device__ __forceinline__ void wg_dst_chunks_body(const float* __restrict__ h, 
         if (beg < end) {
             float g[NS][VEC], none[NS][VEC];
             row_load<VEC, LPR, NS>(gmat, row, F, l, g);
-            wg_zero<VEC, NS>(none);
+            slab_zero<VEC, NS>(none);
             part = wg_range<WG_DOT, VEC, LPR, NS, NORM>(h, csr, val, dinv, row, n, beg, end, F, l, none, g, p_slot, status);
             if (NORM) part = grp_sum<LPR>(part);
         }

@@ -8,6 +8,7 @@ gcn2_kernels.hip and pna_kernels.hip, as for the row-gather scaffold.
 
   --files A,B,...  the translation units to compare; then a rise of ANY kernel's count fails, not only a GAT *_chunks_k kernel's
   --no-diffs       list the kernels that differ with their counts, without the instruction diffs
+  --table          before each file's report, one line per kernel whose counts differ, with both sides' counts
 
   - every kernel of the parent must exist in the result, and no new one may appear; kernels are named as the demangler prints
     them, and RENAME maps the parent's names of the kernels that moved into row_sum.h to the result's;
@@ -19,6 +20,7 @@ gcn2_kernels.hip and pna_kernels.hip, as for the row-gather scaffold.
     prints them all);
   - a renamed kernel changed on purpose: its counts in the parent and in the result are listed side by side, with any rise marked,
     and the opcodes whose number changed stand in for the diff.
+The occupancy (waves per SIMD, from -Rpass-analysis=kernel-resource-usage) is listed beside the counts; a fall counts as a rise.
 Exit status 1 when a symbol is missing or new, a count of a GAT *_chunks_k kernel rises or, with --files, any kernel's."""
 import argparse
 import collections
@@ -39,12 +41,34 @@ EXPECTED = ("gat_fwd_chunks_k", "gat_bwd_dst_chunks_k", "gat_bwd_src_chunks_k")
 RENAME = {"gcn2_rows_k": ("row_sum_rows_k", "G2Epi"), "gcn2_chunks_k": ("row_sum_chunks_k", None), "gcn2_combine_k": ("row_sum_combine_k", "G2Epi"),
           "sage_rows_k": ("row_sum_rows_k", "SageEpi"), "sage_chunks_k": ("row_sum_chunks_k", None), "sage_combine_k": ("row_sum_combine_k", "SageEpi")}
 COUNTS = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size")
+OCC = "occupancy"
+
+
+def worse(a, b):
+    """the counts of b that are worse than a's: a resource count that rose, or the occupancy where it fell"""
+    return [c for c in COUNTS if b[c] > a[c]] + [OCC + " FALLS" for _ in (0,) if b[OCC] < a[OCC]]
+
+
+def counts_line(a, b):
+    return ", ".join(f"{c} {a[c]} -> {b[c]}" for c in COUNTS + (OCC,))
 
 
 def assembly(csrc, name, tmp):
+    """(the assembly text, {mangled kernel: occupancy in waves per SIMD as -Rpass-analysis=kernel-resource-usage reports it})"""
     out = os.path.join(tmp, name + ".s")
-    subprocess.run([HIPCC] + FLAGS + EXTRA.get(name, []) + [os.path.join(csrc, name), "-o", out], check=True)
-    return open(out).read()
+    run = subprocess.run([HIPCC] + FLAGS + ["-Rpass-analysis=kernel-resource-usage"] + EXTRA.get(name, []) +
+                         [os.path.join(csrc, name), "-o", out], stderr=subprocess.PIPE, text=True)
+    if run.returncode:
+        sys.stderr.write(run.stderr)
+        raise subprocess.CalledProcessError(run.returncode, run.args)
+    occ, name_now = {}, None
+    for ln in run.stderr.split("\n"):
+        m = re.search(r"remark: +(Function Name: (\S+)|Occupancy \[waves/SIMD\]: (\d+))", ln)
+        if m and m.group(2):
+            name_now = m.group(2)
+        elif m:
+            occ[name_now] = int(m.group(3))
+    return open(out).read(), occ
 
 
 def renamed(key):
@@ -57,12 +81,15 @@ def renamed(key):
     return new + ("<" + ", ".join(targs) + ">" if targs else "")
 
 
-def kernels(text):
-    """{kernel as the demangler prints it, without return type and parameters: (normalised instruction lines, {count: value})}"""
+def kernels(text_occ):
+    """{kernel as the demangler prints it, without return type and parameters: (normalised instruction lines, {count: value})};
+    the counts hold OCC as well, the one that must not FALL"""
+    text, occ = text_occ
     meta = {}
     for blk in text.split("- .agpr_count:")[1:]:
         nm = re.search(r"\.name:\s+(\S+)", blk).group(1)
         meta[nm] = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1)) for k in COUNTS}
+        meta[nm][OCC] = occ[nm]
     body = {}
     for nm in meta:
         m = re.search(r"^%s:[^\n]*\n(.*?)^\s*\.section\s" % re.escape(nm), text, re.S | re.M)
@@ -79,20 +106,38 @@ def kernels(text):
     return {keys[nm]: (body[nm], meta[nm]) for nm in meta}
 
 
-def main(parent, result, all_diffs=False, files=None, no_diffs=False):
+def table_rows(name, a, b):
+    """One line per kernel whose counts differ, in the format of profiles/row_list_resources.txt (SGPR VGPR LDS scratch occupancy,
+    parent | new), then one line for the file's other kernels."""
+    cols = ("sgpr_count", "vgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", OCC)
+    same = 0
+    for k in sorted(set(a) & set(b)):
+        ca, cb = ([m[1][c] for c in cols] for m in (a[k], b[k]))
+        fmt = lambda v: f"{v[0]:4d} {v[1]:4d} {v[2]:5d} {v[3]:7d} {v[4]:3d}"
+        if ca == cb:
+            same += 1
+            continue
+        w = worse(a[k][1], b[k][1])
+        yield f"{name.split('_')[0]:8s} {k:42s} | {fmt(ca)} | {fmt(cb)} |" + (" worse: " + ", ".join(w) if w else "")
+    yield f"{name.split('_')[0]:8s} ({same} other kernels: the same counts on both sides)"
+
+
+def main(parent, result, all_diffs=False, files=None, no_diffs=False, table=False):
     bad, other, shown = 0, 0, set()
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
         for name in files or FILES:
             a, b = kernels(assembly(parent, name, ta)), kernels(assembly(result, name, tb))
             moved = {k: renamed(k) for k in a if k not in b and renamed(k) in b}
+            if table:
+                print("\n".join(table_rows(name, a, b)))
             missing, new = sorted(set(a) - set(b) - set(moved)), sorted(set(b) - set(a) - set(moved.values()))
             same = [k for k in a if k in b and a[k][0] == b[k][0]]
             print(f"== {name}: {len(a)} kernels in the parent, {len(b)} in the result, {len(same)} with identical instruction streams")
             for k, to in sorted(moved.items()):
-                rises = [c for c in COUNTS if b[to][1][c] > a[k][1][c]]
+                rises = worse(a[k][1], b[to][1])
                 print(f"  renamed (changed on purpose): {k} -> {to}")
                 print(f"      instructions {len(a[k][0])} -> {len(b[to][0])}; " +
-                      ", ".join(f"{c} {a[k][1][c]} -> {b[to][1][c]}" for c in COUNTS) + ("; RISES: " + ", ".join(rises) if rises else ""))
+                      counts_line(a[k][1], b[to][1]) + ("; RISES: " + ", ".join(rises) if rises else ""))
                 ha, hb = (collections.Counter(ln.split()[0] for ln in side if not ln.endswith(":")) for side in (a[k][0], b[to][0]))
                 print("      opcodes: " + ", ".join(f"{op} {ha[op]} -> {hb[op]}" for op in sorted(set(ha) | set(hb)) if ha[op] != hb[op]))
             for k in missing:
@@ -104,13 +149,13 @@ def main(parent, result, all_diffs=False, files=None, no_diffs=False):
                 if a[k][0] == b[k][0] and a[k][1] == b[k][1]:
                     continue
                 expected = any(e in k for e in EXPECTED)
-                rises = [c for c in COUNTS if b[k][1][c] > a[k][1][c]]
+                rises = worse(a[k][1], b[k][1])
                 if a[k][0] == b[k][0]:
                     print(f"  same instructions, other counts: {k}")
                 else:
                     print(f"  {'differs (strict item decode)' if expected else 'DIFFERS'}: {k}")
                 print(f"      instructions {len(a[k][0])} -> {len(b[k][0])}; " +
-                      ", ".join(f"{c} {a[k][1][c]} -> {b[k][1][c]}" for c in COUNTS) + ("; RISES: " + ", ".join(rises) if rises else ""))
+                      counts_line(a[k][1], b[k][1]) + ("; RISES: " + ", ".join(rises) if rises else ""))
                 if expected:
                     bad += 1 if rises else 0
                     continue
@@ -136,5 +181,6 @@ if __name__ == "__main__":
     ap.add_argument("parent"); ap.add_argument("result", nargs="?", default=here)
     ap.add_argument("--files", type=lambda v: v.split(","))
     ap.add_argument("--all-diffs", action="store_true"); ap.add_argument("--no-diffs", action="store_true")
+    ap.add_argument("--table", action="store_true")
     a = ap.parse_args()
-    sys.exit(main(a.parent, a.result, all_diffs=a.all_diffs, files=a.files, no_diffs=a.no_diffs))
+    sys.exit(main(a.parent, a.result, all_diffs=a.all_diffs, files=a.files, no_diffs=a.no_diffs, table=a.table))
