@@ -272,6 +272,9 @@ SIGNATURES = {
     "grapes_gflownet_loss": (I32, [P, F32, P, I32, I32, P, F32, I32, P, P]),
     "grapes_step_losses_workspace_bytes": (SZ, [I32]),
     "grapes_step_losses": (I32, [P, I32, I32, P, P, P, P, I32, P, P, P, I32, P, F32, P, I32, I32, F32, I32, P, P, P, P, P]),
+    "grapes_gcn_aggregate_fwd_losses_available": (I32, [P, P, P, I32, I32]),
+    "grapes_gcn_aggregate_fwd_losses": (I32, [P, P, P, P, P, P, I32, P, I32, P, P, P, P, I32, P, P, P, I32, P, F32, P, I32, I32, F32,
+                                              I32, P, P, P, P]),
     "grapes_logit_var_reg": (I32, [P, I32, P, I32, F32, P, P, P]),
     "grapes_dropout_fwd": (I32, [P, P, P, I32, P, I32, F32, U64, U64, P, P]),
     "grapes_dropout_bwd": (I32, [P, P, P, I32, P, I32, F32, P]),

@@ -6,10 +6,9 @@
 //   main.py:268,289 Adam updates of both optimisers (torch.optim.Adam semantics, one launch for all tensors)
 // One workgroup each for the two loss kernels (a few hundred rows); everything is fp32 like the reference.
 #include "common.h"
-#include "row_loss.h"
+#include "step_loss.h"     // the GFlowNet loss, loss_row and the multi-workgroup pieces (shared with the aggregation that carries the losses)
 
 #define LOSS_THREADS 1024
-#define LOSS_MAX_B 4096
 
 // deterministic sum of v[0..n) (n <= LOSS_MAX_B) by the whole workgroup: thread t owns t, t+T, ...; xor tree; waves in order
 __device__ __forceinline__ float block_sum_fixed(const float* v, int n, float* red) {
@@ -22,47 +21,6 @@ __device__ __forceinline__ float block_sum_fixed(const float* v, int n, float* r
     float t = 0.f;
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
     return t;
-}
-
-// main.py:272-282 for one thread.  stats: [hops][stride] floats, stats[h*stride + 4] = sum of hop h's log-probs
-__device__ __forceinline__ void gflownet_loss_eval(bool has_z, float log_z_raw, float log_z_init,
-                                                   const float* __restrict__ stats, int hops, int stride, float cost,
-                                                   float loss_coef, int reinforce, float* __restrict__ out) {
-    float tot = stats[4];
-    for (int h = 1; h < hops; ++h) tot = __fadd_rn(tot, stats[h * stride + 4]);   // main.py:276
-    const float lz = has_z ? __fsub_rn(log_z_raw, log_z_init) : 0.f;
-    float loss, scale;
-    if (reinforce) {
-        loss = __fmul_rn(-tot, cost);                                             // main.py:279
-        scale = -cost;
-    } else {
-        const float inner = __fadd_rn(__fadd_rn(lz, tot), __fmul_rn(loss_coef, cost));
-        loss = __fmul_rn(inner, inner);                                           // main.py:282
-        scale = __fmul_rn(2.0f, inner);
-    }
-    out[0] = loss; out[1] = scale; out[2] = lz; out[3] = tot;
-}
-
-// What grapes_step_losses adds to the classifier loss in the same workgroup: the mean of the log-Z head's output
-// (main.py:228, the sum exactly as reduce_sum_k forms it) and the GFlowNet loss that needs both (main.py:272-282).
-struct GfnTail {
-    float* out4;                    // NULL = classifier loss only
-    const float* zout; int nz; const int32_t* d_nz; float log_z_init;
-    const float* stats; int hops, stride; float loss_coef; int reinforce;
-    const float* loss_extra;        // NULL, or one float added to the classifier loss (the regulariser of main.py:260-261)
-};
-
-// One target row by one wavefront: loss of the row (every lane), its gradient row written.  CrossEntropy or BCE.
-__device__ __forceinline__ float loss_row(const float* __restrict__ logits, float* __restrict__ dlogits, int n_rows, int C,
-                                          int row, long long gid, const int64_t* __restrict__ labels,
-                                          const float* __restrict__ labels_f, int multilabel, float inv, int lane) {
-    float loss = 0.f;
-    if ((unsigned)row < (unsigned)n_rows) {
-        const RowStrided r{logits + (long long)row * C, dlogits + (long long)row * C, C, lane};
-        loss = multilabel ? row_loss_bce(r, labels_f + gid * C, inv)
-                          : row_loss_ce(r, (int)labels[gid], inv);
-    }
-    return loss;
 }
 
 // multilabel == 0: labels = int64 class ids (CrossEntropyLoss, mean over B)
@@ -157,8 +115,6 @@ __global__ __launch_bounds__(LOSS_THREADS) void classifier_loss_k(
 // handles its share of the targets (one wavefront per row, same arithmetic as the single-workgroup kernel); row losses
 // are published (device-scope exchange), the last workgroup to finish sums them in the single-workgroup kernel's
 // order (1024 virtual threads) and evaluates the GFlowNet loss => bit-identical results.
-#define LOSS_MB_THREADS 256
-#define LOSS_MB_MAXROWS 65536
 __global__ __launch_bounds__(LOSS_MB_THREADS) void step_losses_mb_k(
     const float* __restrict__ logits, int n_rows, int C, const int32_t* __restrict__ node_map,
     const int32_t* __restrict__ target_ids, const int64_t* __restrict__ labels, const float* __restrict__ labels_f,
@@ -170,35 +126,10 @@ __global__ __launch_bounds__(LOSS_MB_THREADS) void step_losses_mb_k(
     __shared__ int s_last;
     const int tid = threadIdx.x, lane = lane_id(), wid = tid >> 6;
     const int G = gridDim.x;
-    double* zslot = reinterpret_cast<double*>(row_loss + ((B + 1) & ~1));
+    double* zslot = losses_zslot(row_loss, B);
     const float inv = multilabel ? 1.0f / ((float)B * (float)C) : 1.0f / (float)B;
     if (blockIdx.x == 0) {
-        if (gt.out4 && gt.zout) {     // virtual thread v = tid + 256 q sums x[v], x[v + 1024], ...; virtual wave = v / 64
-            const int nz = eff_count(gt.d_nz, gt.nz);
-            double zs[4] = {0.0, 0.0, 0.0, 0.0};
-            for (int i0 = 0; i0 < nz; i0 += 8 * 1024) {          // 32 independent loads in flight, added in index order
-                float xv[8][4];
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int i = i0 + 1024 * u + tid + 256 * q;
-                        xv[u][q] = gt.zout[i < nz ? i : nz - 1];   // unconditional, clamped
-                    }
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) { if (i0 + 1024 * u + tid + 256 * q < nz) zs[q] += (double)xv[u][q]; }
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { const double w = wave_sum_d(zs[q]); if (lane == 0) dred[wid + 4 * q] = w; }
-            __syncthreads();
-            if (tid == 0) {
-                double t = 0.0;
-                for (int w = 0; w < 16; ++w) t += dred[w];
-                publish_f64(zslot, t);
-            }
-        }
+        losses_z_sum(gt, zslot, dred);
     } else {
         const int nwords = (n_rows + 31) >> 5;
         // this wavefront's first target row is looked up together with the bitmap's ids (two dependent round trips once, not twice)
@@ -246,36 +177,7 @@ __global__ __launch_bounds__(LOSS_MB_THREADS) void step_losses_mb_k(
     if (tid == 0) s_last = (atomicAdd(ticket, 1u) == (unsigned)G - 1) ? 1 : 0;
     __syncthreads();
     if (!s_last) return;
-    // ---- last workgroup: sum of the row losses in block_sum_fixed's order for 1024 threads (virtual thread v owns rows
-    // v, v + 1024, ...; butterfly inside a virtual wave; virtual waves in index order)
-    float ls[4] = {0.f, 0.f, 0.f, 0.f};
-    for (int i0 = 0; i0 < B; i0 += 1024) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = i0 + tid + 256 * q;
-            if (i < B) ls[q] += __int_as_float(__hip_atomic_load((const int*)(row_loss + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { const float w = wave_sum(ls[q]); if (lane == 0) fred[wid + 4 * q] = w; }
-    __syncthreads();
-    if (tid == 0) {
-        float t = 0.f;
-        for (int w = 0; w < 16; ++w) t += fred[w];
-        const float loss = t * inv + (gt.loss_extra ? *gt.loss_extra : 0.f);
-        *loss_out = loss;
-        *ticket = 0u;
-        if (gt.out4) {
-            float zmean = 0.f;
-            if (gt.zout) {
-                const int nz = eff_count(gt.d_nz, gt.nz);
-                const double zt = __longlong_as_double(__hip_atomic_load((const long long*)zslot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                zmean = (float)(nz > 0 ? zt / (double)nz : 0.0 / 0.0);
-            }
-            gflownet_loss_eval(gt.zout != nullptr, zmean, gt.log_z_init, gt.stats, gt.hops, gt.stride, loss, gt.loss_coef,
-                               gt.reinforce, gt.out4);
-        }
-    }
+    losses_finish(row_loss, B, inv, gt, zslot, loss_out, ticket, fred);     // the last workgroup
 }
 
 __global__ void gflownet_loss_k(const float* __restrict__ log_z_raw, float log_z_init, const float* __restrict__ stats,

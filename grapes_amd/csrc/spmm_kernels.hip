@@ -1625,6 +1625,74 @@ __global__ __launch_bounds__(256) void gcn_aggregate_narrow_multi_k(NarrowSegs s
 #undef NSEL
 }
 
+// ---- The classifier's LAST aggregation (gcn_aggregate_k<1, 0>: logits = Â H + b, one wavefront per row, a workgroup owns the rows
+// 4 blockIdx .. 4 blockIdx + 3) that also runs the step's loss launch (loss_kernels.hip: step_losses_mb_k; main.py:259-282) on the
+// rows it has just formed: a TARGET row gets loss_row (its loss, its gradient row), every other row of dlogits its zeros — the
+// wavefront that wrote logits[r] reads it back itself, no other workgroup's progress is waited for.  Which of its four rows are
+// targets, and with which label, every workgroup finds by looking all B targets up (node_map[target_ids[b]], requested in front of
+// the aggregation); the thread that holds target b publishes the row's loss as row_loss[b].  Workgroup nA forms the log-Z sum
+// (losses_z_sum: its inputs date from hop 0); the last workgroup to finish sums the row losses and evaluates the GFlowNet loss
+// (losses_finish, the ticket of step_losses_mb_k).  Same routines, same order => logits, loss_c, dlogits and out4 are bit-identical
+// to the two launches.  n_host <= LOSS_MB_MAXROWS (the grid is not capped: nA = ceil(n_host / 4)); distinct target ids map to
+// distinct rows (node_map is a relabelling), a repeated id repeats its row's loss.
+#include "step_loss.h"
+struct LossFoldArgs {
+    const int32_t* node_map; const int32_t* target_ids; const int64_t* labels; const float* labels_f; int B;
+    float* dlogits; float* loss_out; GfnTail gt; float* row_loss /* [B] + one double (8-byte aligned) */; unsigned* ticket;
+};
+__global__ __launch_bounds__(LOSS_MB_THREADS) void gcn_aggregate_losses_k(AggregateArgs a, LossFoldArgs L, int nA) {
+    __shared__ long long s_gid[4];             // the target id behind each of the workgroup's rows (-1: not a target)
+    __shared__ float s_l[4];
+    __shared__ double dred[16];
+    __shared__ float fred[16];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, lane = lane_id(), wid = tid >> 6;
+    const int n_rows = a.n_host, C = a.F, B = L.B, multilabel = L.labels_f ? 1 : 0;
+    double* zslot = losses_zslot(L.row_loss, B);
+    const float inv = multilabel ? 1.0f / ((float)B * (float)C) : 1.0f / (float)B;
+    if ((int)blockIdx.x == nA) {
+        losses_z_sum(L.gt, zslot, dred);
+    } else {
+        // the first 256 targets' rows are requested here: the second of the two dependent trips is under way while the rows are walked
+        const int tb = tid < B ? tid : 0;
+        const long long gid_t = L.target_ids[tb];
+        const int row_t = L.node_map[gid_t];
+        if (tid < 4) s_gid[tid] = -1;
+        lds_barrier();
+        gcn_aggregate_body<1, 0>(a.h, a.rowptr, a.csr, a.dinv, a.bias, a.out, a.n_host, a.d_n, a.F, a.relu, 0, nullptr,
+                                 R1{nullptr, nullptr}, nullptr, nullptr, (int)blockIdx.x, nA);
+        // (LDS barriers from here on: a lane reads back the logits it stored itself, nothing waits for the stores to drain)
+        for (int b = tid; b < B; b += blockDim.x) {
+            const long long gid = b == tid ? gid_t : (long long)L.target_ids[b];
+            const int row = b == tid ? row_t : L.node_map[gid];
+            if ((unsigned)row < (unsigned)n_rows && (row >> 2) == (int)blockIdx.x) s_gid[row & 3] = gid;
+        }
+        lds_barrier();
+        const int row = 4 * (int)blockIdx.x + wid;
+        if (row < n_rows) {
+            const long long gid = s_gid[wid];
+            if (gid >= 0) {
+                const float l = loss_row(a.out, L.dlogits, n_rows, C, row, gid, L.labels, L.labels_f, multilabel, inv, lane);
+                if (lane == 0) s_l[wid] = l;
+            } else {
+                for (int c = lane; c < C; c += 64) L.dlogits[(long long)row * C + c] = 0.f;
+            }
+        }
+        lds_barrier();
+        for (int b = tid; b < B; b += blockDim.x) {
+            const int r = b == tid ? row_t : L.node_map[L.target_ids[b]];
+            const bool in = (unsigned)r < (unsigned)n_rows;
+            if (in && (r >> 2) == (int)blockIdx.x) publish_f32(&L.row_loss[b], s_l[r & 3]);
+            else if (!in && blockIdx.x == 0) publish_f32(&L.row_loss[b], 0.f);       // (no such row: step_losses_mb_k's zero)
+        }
+    }
+    __syncthreads();
+    if (tid == 0) s_last = (atomicAdd(L.ticket, 1u) == (unsigned)nA) ? 1 : 0;
+    __syncthreads();
+    if (!s_last) return;
+    losses_finish(L.row_loss, B, inv, L.gt, zslot, L.loss_out, L.ticket, fred);      // the last workgroup
+}
+
 #ifndef GRAPES_ALIGNED16_DEFINED
 #define GRAPES_ALIGNED16_DEFINED
 #endif
@@ -2083,6 +2151,36 @@ extern "C" int grapes_gcn_aggregate_fwd(const float* h, const int32_t* rowptr_t,
     if (!h || !rowptr_t || !dinv || !out) return GRAPES_EINVAL;
     return launch_aggregate(h, rowptr_t, csr_src, dinv, bias, out, n, d_n, f, relu, long_items, d_n_items, item_cap,
                             (float*)workspace, (hipStream_t)stream);
+}
+
+/* ... followed, in the same launch, by grapes_step_losses on its output (see gcn_aggregate_losses_k): the shapes that
+ * grapes_gcn_aggregate_fwd hands to the row-per-wavefront kernel with one float per lane (f > 16, and f % 4 != 0 or a row base
+ * that is not 16-byte aligned), no long-row items, n <= 65536. */
+extern "C" int grapes_gcn_aggregate_fwd_losses_available(const float* h, const float* bias, const float* out, int32_t n, int32_t f) {
+    const bool vec = (f % 4 == 0) && grapes_aligned16(h) && grapes_aligned16(out) && (!bias || grapes_aligned16(bias));
+    return (n > 0 && n <= LOSS_MB_MAXROWS && f > 16 && !vec) ? 1 : 0;
+}
+extern "C" int grapes_gcn_aggregate_fwd_losses(const float* h, const int32_t* rowptr_t, const int32_t* csr_src, const float* dinv,
+                                               const float* bias, float* out, int32_t n, const int32_t* d_n, int32_t f,
+                                               const int32_t* node_map, const int32_t* target_ids, const int64_t* labels,
+                                               const float* labels_f, int32_t B, float* dlogits, float* loss_out,
+                                               const float* z_out, int32_t nz, const int32_t* d_nz, float log_z_init,
+                                               const float* hop_stats, int32_t hops, int32_t stats_stride, float loss_coef,
+                                               int32_t reinforce, float* out4, void* workspace, uint32_t* d_ticket,
+                                               grapes_stream_t stream) {
+    if (!h || !rowptr_t || !dinv || !out || !node_map || !target_ids || !dlogits || !loss_out || !out4) return GRAPES_EINVAL;
+    if ((labels == nullptr) == (labels_f == nullptr)) return GRAPES_EINVAL;
+    if (B <= 0 || B > LOSS_MAX_B || !grapes_gcn_aggregate_fwd_losses_available(h, bias, out, n, f)) return GRAPES_EINVAL;
+    if (!hop_stats || hops <= 0 || stats_stride < 5 || nz < 0 || (z_out && nz == 0)) return GRAPES_EINVAL;
+    if (!workspace || !d_ticket) return GRAPES_EINVAL;
+    if (((uintptr_t)workspace) & 7) return GRAPES_EALIGN;
+    const AggregateArgs A{h, rowptr_t, csr_src, dinv, bias, out, n, d_n, f, 0};
+    const GfnTail gt{out4, z_out, nz, d_nz, log_z_init, hop_stats, hops, stats_stride, loss_coef, reinforce, nullptr};
+    const LossFoldArgs L{node_map, target_ids, labels, labels_f, B, dlogits, loss_out, gt, (float*)workspace, d_ticket};
+    const int nA = grapes_div_up(n, 4);
+    hipLaunchKernelGGL(gcn_aggregate_losses_k, dim3(nA + 1), dim3(LOSS_MB_THREADS), 0, (hipStream_t)stream, A, L, nA);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
 }
 
 /* ... that also returns head_out[r] = out[r] . head_w (see gcn_aggregate_k MODE 3): f > 16, f % 4 == 0, 16-byte aligned rows,

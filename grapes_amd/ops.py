@@ -3631,6 +3631,39 @@ def step_losses(logits, node_map, target_ids, labels, hop_stats, loss_coef, z_ou
     return loss, dlogits, out4
 
 
+def gcn_aggregate_fwd_losses(h, prep: PreparedGraph, bias, node_map, target_ids, labels, hop_stats, loss_coef, z_out=None,
+                             d_nz=None, log_z_init=0.0, reinforce=False):
+    """gcn_aggregate_fwd(h, prep, bias) = the logits, and step_losses on them, in ONE launch (main.py:256-282): the wavefront that
+    forms a row runs its loss.  Returns (logits, loss_c [1], d loss_c / d logits, out4), bit-identical to the two calls — or
+    None when the shape is not covered (the caller runs the two launches): it covers the row-per-wavefront aggregation with one
+    float per lane (f > 16, f % 4 != 0 or an unaligned base), n <= 65536 rows, no long-row items."""
+    _chk(h, _f32, "h"); _chk(bias, _f32, "bias", True); _chk(node_map, _i32, "node_map"); _chk(target_ids, _i32, "target_ids")
+    _chk(hop_stats, _f32, "hop_stats"); _chk(z_out, _f32, "z_out", True)
+    n, f = h.shape
+    multi = labels.dim() == 2
+    _chk(labels, _f32 if multi else _i64, "labels")
+    B = target_ids.numel()
+    if (prep.items_fwd and prep.n > _SMALL_GRAPH) or _rec_form(prep, n, f) or not 0 < B <= 4096:
+        return None
+    out = torch.empty_like(h)
+    if not lib().grapes_gcn_aggregate_fwd_losses_available(_p(h), _p(bias), _p(out), n, f):
+        return None
+    hops, stride = hop_stats.shape
+    dlogits = torch.empty_like(h)
+    loss = torch.empty(1, dtype=_f32, device=h.device)
+    out4 = torch.empty(4, dtype=_f32, device=h.device)
+    ws = _ws(lib().grapes_step_losses_workspace_bytes(B), h.device)
+    ticket = _ticket(h.device)[8:9]
+    _lib.check(lib().grapes_gcn_aggregate_fwd_losses(_p(h), _p(prep.rowptr_t), _p(prep.csr_src), _p(prep.dinv), _p(bias), _p(out),
+                                                     n, _p(prep.d_n), f, _p(node_map), _p(target_ids),
+                                                     None if multi else _p(labels), _p(labels) if multi else None, B,
+                                                     _p(dlogits), _p(loss), _p(z_out), 0 if z_out is None else z_out.numel(),
+                                                     _p(d_nz), float(log_z_init), _p(hop_stats), hops, stride, float(loss_coef),
+                                                     1 if reinforce else 0, _p(out4), _p(ws), _p(ticket), _stream()),
+               "gcn_aggregate_fwd_losses")
+    return out, loss, dlogits, out4
+
+
 class FusedAdam:
     """torch.optim.Adam updates of one or more optimisers in ONE launch (main.py:268,289).  Works on the optimisers'
     own state tensors (exp_avg, exp_avg_sq, step), so state_dict() / checkpoints stay those of torch.optim.Adam.

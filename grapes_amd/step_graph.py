@@ -125,7 +125,7 @@ class _Step:
         "batch", "neigh", "nbl", "counts", "cand_pos", "hid", "prep", "ax_pre", "pscr", "bsum", "sstage", "rm_lists",
         "marked", "halo", "halo_code",          # the last expansion made the next hop's marks; the last halo fetch; its indicator words
         # the classifier: all_nodes, its graphs, activations, losses
-        "alln", "d_na", "preps", "layers", "used", "first_relu", "first_fused", "acts", "keeps", "logits",
+        "alln", "d_na", "preps", "layers", "used", "first_relu", "first_fused", "acts", "keeps", "logits", "losses",
         "loss_c", "dl", "loss_gfn", "gscale", "log_z", "tot")
 
     def __init__(self):
@@ -929,13 +929,33 @@ class GraphedTrainer:
             acts = [x_rows]
         else:
             acts = [self.g.assemble(self.g.fetch_halo(alln, d_n=d_na))]
+        # no dropout on the logits, no regulariser: the last aggregation runs the loss launch on the rows it forms (A/B:
+        # GRAPES_LOSS_FOLD=0)
+        fold = (not pdrop and not self.reg_param and not self.evaluate and _sw("GRAPES_LOSS_FOLD", "1") != "0")
         for li in range(len(acts) - 1, len(layers)):
+            if fold and li == len(layers) - 1:
+                logits, s.losses = self._conv_fwd_losses(s, layers[li], acts[-1], used[li])
+                acts.append(drop(logits))
+                break
             acts.append(drop(self._conv_fwd(layers[li], acts[-1], used[li], li < len(layers) - 1)))
         for p in used:
             i = self.hops + next(i for i, q in enumerate(s.preps) if q is p)
             s.agg_w[i] += 1
             s.agg_x[i] += 1
         s.acts, s.keeps, s.logits = acts, keeps, acts[-1]
+
+    def _conv_fwd_losses(self, s, conv, x, prep):
+        """The classifier's last layer with both losses in its aggregation launch (main.py:256-282; see _losses) ->
+        (logits, (logits, loss_c, d logits, out4)), or (logits, None) where that launch does not cover the shape."""
+        rnd = self.random_sampling
+        h = ops.linear_fwd(x, conv.lin.weight, d_n=prep.d_n)
+        r = ops.gcn_aggregate_fwd_losses(h, prep, conv.bias, self.g.node_map, self.targets, self.y, s.hop_stats, self.loss_coef,
+                                         z_out=None if rnd else s.zstate["zout"].view(-1),
+                                         d_nz=None if rnd else s.zstate["d_nb"],
+                                         log_z_init=self.log_z_init, reinforce=self.reinforce)
+        if r is None:
+            return ops.gcn_aggregate_fwd(h, prep, conv.bias, False), None
+        return r[0], r
 
     def _eval_outputs(self, s):
         """eval.py:154-155: predictions = argmax(logits)[node_map.map(target_nodes)] (multi-label: the logit > 0 rows, eval.py:58)
@@ -951,6 +971,10 @@ class GraphedTrainer:
         """Both losses in one launch: main.py:259-260 (+ the gradient loss_c.backward() starts from), the mean of the
         log-Z head (main.py:228) and the GFlowNet loss (main.py:272-282)."""
         rnd, logits, d_na = self.random_sampling, s.logits, s.d_na
+        if s.losses is not None:                         # they came with the logits (_conv_fwd_losses)
+            _, s.loss_c, s.dl, out4 = s.losses
+            s.loss_gfn, s.gscale, s.log_z, s.tot = out4[0], out4[1:2], out4[2], out4[3]
+            return
         # main.py:260-261: + reg_param * sum of the rows' logit variances — part of loss_c and of the GFlowNet cost (main.py:274)
         reg_term = ops.logit_var_reg(logits, self.reg_param, d_n=d_na) if self.reg_param else None
         s.loss_c, s.dl, out4 = ops.step_losses(logits, self.g.node_map, self.targets, self.y, s.hop_stats, self.loss_coef,

@@ -582,6 +582,22 @@ int grapes_gcn_aggregate_fwd(const float* h, const int32_t* rowptr_t, const int3
 int grapes_gcn_aggregate_fwd_head(const float* h, const int32_t* rowptr_t, const int32_t* csr_src, const float* dinv,
                                   const float* bias, float* out, int32_t n, const int32_t* d_n, int32_t f, int32_t relu,
                                   const float* head_w, float* head_out, uint32_t* gate_bits, grapes_stream_t stream);
+/* grapes_gcn_aggregate_fwd (no ReLU, no long-row items) and grapes_step_losses on its output `out` = the logits [n, f] in ONE
+ * launch (main.py:256-282: the classifier's last GCNConv aggregation, loss_c, d loss_c / d logits, the log-Z mean, the GFlowNet
+ * loss): the wavefront that has formed a row runs its loss or zero-fills its gradient row, one more workgroup forms the log-Z
+ * sum, the last workgroup to finish sums the row losses.  out, dlogits, loss_out and out4 are bit-identical to the two calls'.
+ * Covers the shapes grapes_gcn_aggregate_fwd walks with one float per lane: grapes_gcn_aggregate_fwd_losses_available(h, bias,
+ * out, n, f) != 0 (f > 16, f % 4 != 0 or a base that is not 16-byte aligned, n <= 65536); GRAPES_EINVAL otherwise.  Arguments
+ * as those two entry points' (workspace: grapes_step_losses_workspace_bytes(B), 8-byte aligned; d_ticket: one zero word, left
+ * zero; no loss_extra).  Distinct target ids must map to distinct rows. */
+int grapes_gcn_aggregate_fwd_losses_available(const float* h, const float* bias, const float* out, int32_t n, int32_t f);
+int grapes_gcn_aggregate_fwd_losses(const float* h, const int32_t* rowptr_t, const int32_t* csr_src, const float* dinv,
+                                    const float* bias, float* out, int32_t n, const int32_t* d_n, int32_t f,
+                                    const int32_t* node_map, const int32_t* target_ids, const int64_t* labels,
+                                    const float* labels_f, int32_t B, float* dlogits, float* loss_out, const float* z_out,
+                                    int32_t nz, const int32_t* d_nz, float log_z_init, const float* hop_stats, int32_t hops,
+                                    int32_t stats_stride, float loss_coef, int32_t reinforce, float* out4, void* workspace,
+                                    uint32_t* d_ticket, grapes_stream_t stream);
 /* The same two aggregations (head_w NULL: grapes_gcn_aggregate_fwd's, else grapes_gcn_aggregate_fwd_head's) driven by the graph
  * build's per-row head records taken over LOCAL ids (row_head of grapes_gcn_prepare* with head_ids = 0, 1, ..., n - 1): one
  * dependent round trip per row instead of three, pairs of rows per resident wavefront (modules/gcn.py:32,36 on Reddit-shaped
