@@ -106,7 +106,7 @@ __device__ __forceinline__ void row_accumulate(const float* __restrict__ h, cons
 }
 
 // ---- summation order of a HUB row (more than GRAPES_HUB_ROW entries), shared by every aggregation kernel of the per-hop graphs
-// (gcn_aggregate_k, gcn_aggregate_gather_k, gcn_aggregate_gather_head_k) so that their results stay bit-identical:
+// (gcn_aggregate_k, gcn_aggregate_gather_k, gcn_aggregate_gather_head5_k) so that their results stay bit-identical:
 //     sum = ((((s_0 + s_1) + s_2) + ... ) + s_7),   s_g = sum over the entries q = g, g + 8, g + 16, ... in increasing q,
 // then the unit self-loop, then the bias.  Eight independent chains instead of one: a wavefront that owns the row keeps eight
 // loads in flight, and the fused kernel can spread the chains over the eight row groups of a workgroup — a 100-entry hub of
@@ -635,6 +635,9 @@ __global__ __launch_bounds__(256) void gcn_aggregate_chunks_lpr_k(const float* _
 // i.e. Â · [X | ind] computed straight from the resident feature matrix — the gathered frontier
 // feature matrix is never materialised.  LPR lanes serve one destination row (16 B per lane): with
 // F + num_ind = 104 a row needs 26 lanes, so a wavefront carries two rows (LPR = 32).
+__device__ __forceinline__ void gr_fma4(float4& acc, float w, const float4& t) {
+    acc.x = fmaf(w, t.x, acc.x); acc.y = fmaf(w, t.y, acc.y); acc.z = fmaf(w, t.z, acc.z); acc.w = fmaf(w, t.w, acc.w);
+}
 template <int LPR>
 __global__ __launch_bounds__(256) void gcn_aggregate_gather_k(const float* __restrict__ X, int F, int ldx,
                                                               const int32_t* __restrict__ ids,
@@ -677,12 +680,8 @@ __global__ __launch_bounds__(256) void gcn_aggregate_gather_k(const float* __res
                         for (int u = 0; u < 8; ++u) t8[u] = feat_tail_chunk(X, ldx, F, v8[u], c, code, epoch);
                     }
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        if (q0 + u < len) {
-                            a8[u].x = fmaf(w8[u], t8[u].x, a8[u].x); a8[u].y = fmaf(w8[u], t8[u].y, a8[u].y);
-                            a8[u].z = fmaf(w8[u], t8[u].z, a8[u].z); a8[u].w = fmaf(w8[u], t8[u].w, a8[u].w);
-                        }
-                    }
+                    for (int u = 0; u < 8; ++u)
+                        if (q0 + u < len) gr_fma4(a8[u], w8[u], t8[u]);
                 }
                 acc = a8[0];
 #pragma unroll
@@ -690,9 +689,7 @@ __global__ __launch_bounds__(256) void gcn_aggregate_gather_k(const float* __res
                 const int vs = ids[row];
                 const float4 ts = (c < xchunks) ? *reinterpret_cast<const float4*>(X + (long long)vs * ldx + c * 4)
                                                 : feat_tail_chunk(X, ldx, F, vs, c, code, epoch);
-                const float wss = dinv[row] * dc;
-                acc.x = fmaf(wss, ts.x, acc.x); acc.y = fmaf(wss, ts.y, acc.y);
-                acc.z = fmaf(wss, ts.z, acc.z); acc.w = fmaf(wss, ts.w, acc.w);
+                gr_fma4(acc, dinv[row] * dc, ts);
                 *reinterpret_cast<float4*>(out + (long long)row * Fo + c * 4) = acc;
                 continue;
             }
@@ -720,10 +717,7 @@ __global__ __launch_bounds__(256) void gcn_aggregate_gather_k(const float* __res
                     for (int u = 0; u < 4; ++u) t[u] = feat_tail_chunk(X, ldx, F, v[u], c, code, epoch);
                 }
 #pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    acc.x = fmaf(w[u], t[u].x, acc.x); acc.y = fmaf(w[u], t[u].y, acc.y);
-                    acc.z = fmaf(w[u], t[u].z, acc.z); acc.w = fmaf(w[u], t[u].w, acc.w);
-                }
+                for (int u = 0; u < 4; ++u) gr_fma4(acc, w[u], t[u]);
             }
             *reinterpret_cast<float4*>(out + (long long)row * Fo + c * 4) = acc;
         }
@@ -741,222 +735,11 @@ __device__ __forceinline__ float code_bit_f(uint32_t cd, uint32_t epoch, int b) 
     return ((cd >> 8) == epoch && ((cd >> b) & 1u)) ? 1.f : 0.f;
 }
 
-template <int LPR>
-__global__ __launch_bounds__(256) void gcn_aggregate_gather_head_k(const float* __restrict__ X, int F, int ldx,
-                                                                   const int32_t* __restrict__ ids,
-                                                                   const uint32_t* __restrict__ code, uint32_t epoch_host,
-                                                                   const uint32_t* d_epoch, int num_ind,
-                                                                   const int32_t* __restrict__ rowptr,
-                                                                   const int32_t* __restrict__ csr,
-                                                                   const float* __restrict__ dinv,
-                                                                   const int4* __restrict__ head, float* __restrict__ out,
-                                                                   int n_host, const int32_t* d_n, unsigned long long* clk) {
-    const unsigned long long clk0 = grapes_clock_begin(clk);
-    const int Fo = (F + num_ind + 3) & ~3;
-    const int chunks = Fo >> 2;
-    const int xch = F >> 2;                  // chunks wholly inside X: one lane each, four columns, no correction
-    const int tcols = Fo - 4 * xch;          // the columns after them (rest of X, indicators, padding; <= 12): one lane each
-    const int sub = threadIdx.x & (LPR - 1);
-    constexpr int RPB = 256 / LPR;                                  // row groups per workgroup (8 or 4)
-    const int rg = threadIdx.x / LPR;
-    __shared__ int s_hub[3][RPB];
-    __shared__ int s_nhub[3];               // hub-row counters of three consecutive batches: ONE barrier per batch (see below)
-    __shared__ float4 s_part[8][LPR];
-    GRAPES_STAMP(0);
-    // The kernel is priced in vector instructions per row as much as in bytes (a frontier row is ~1 KB of loads), and in
-    // dependent memory round trips per batch of RPB rows: one.  The workgroups are resident and loop.  In a batch every
-    // load is unconditional (clamped) and issued together — feature chunks, the tail lanes' scalars and code words, then
-    // the NEXT batch's records — one wait, arithmetic, stores; the records a batch needs are in registers when it starts,
-    // and the previous batch's stores are acknowledged while this batch's loads travel.  The columns that are not a whole
-    // chunk of X (indicator columns, the last F % 4 features, padding) are one LANE each (lanes 0..tcols-1 of the row group)
-    // instead of a per-lane correction of every chunk: the correction cost more instructions than the product itself.
-    // The first batch's records are requested before the live row count is known (inside the CAPACITY; a stale record past
-    // n is dropped), together with the count and the epoch.
-    int4 h0 = make_int4(0, 0, 0, 0), h1 = h0, h2 = h0;
-    int stamp_it = 0; (void)stamp_it;
-    {
-        const int row0 = blockIdx.x * RPB + rg;
-        const int r0 = row0 < n_host ? row0 : 0;
-        h0 = head[3 * (long long)r0]; h1 = head[3 * (long long)r0 + 1]; h2 = head[3 * (long long)r0 + 2];
-    }
-    const int n = eff_count(d_n, n_host);
-    const uint32_t epoch = d_epoch ? (*d_epoch & 0xffffffu) : epoch_host;
-    // Hub rows of a batch are collected in LDS and shared by the whole workgroup after ONE LDS-only barrier per batch
-    // (lds_barrier: no wait on global memory).  Counter slot b % 3 belongs to batch b; it is cleared right after batch
-    // b - 2's barrier, which every wavefront passes before it can add to the slot (batch b, after barrier b - 1) and after
-    // it has read the slot's previous use (batch b - 3).
-    if (threadIdx.x < 3) s_nhub[threadIdx.x] = 0;
-    lds_barrier();
-    if (n > 0 && (int)blockIdx.x * RPB + rg >= n) {          // a row group past the last row: it repeats row n - 1's loads
-        const long long rl = n - 1;                           // (whose record is valid; the one read above is stale)
-        h0 = head[3 * rl]; h1 = head[3 * rl + 1]; h2 = head[3 * rl + 2];
-    }
-    asm volatile("" :: "v"(h0.x), "v"(h1.x), "v"(h2.x));    // the first records are waited for HERE on every path into the loop
-    int slot = 0;                                            // (else the loop head inherits "maybe pending" and drains the queue every batch)
-    const int tcol = 4 * xch + sub;                          // this lane's tail column (lanes sub < tcols)
-    const int tcol_x = tcol < ldx ? tcol : ldx - 1;          // its column of X when tcol < F (clamped: always a valid load)
-    for (int base = blockIdx.x * RPB; base < n; base += gridDim.x * RPB) {       // uniform per workgroup
-        const bool own = base + rg < n;              // row groups past the last row repeat row n - 1's loads, store nothing
-        const int row = own ? base + rg : n - 1;
-        if (stamp_it < 4) GRAPES_STAMP(stamp_it * 3 + 1);
-        const int len = h0.x;
-        const bool hub = len > GRAPES_HUB_ROW;       // hub row: all row groups of the workgroup share it below
-        if (hub && own && sub == 0) s_hub[slot][atomicAdd(&s_nhub[slot], 1)] = row;
-        const int g[5] = {h1.x, h1.z, h2.x, h2.z, h0.y};                             // four entries, then self
-        const float w[5] = {__int_as_float(h1.y), __int_as_float(h1.w), __int_as_float(h2.y), __int_as_float(h2.w),
-                            __int_as_float(h0.z)};
-        const float dc = __int_as_float(h0.w);
-        const float* xr[5];
-#pragma unroll
-        for (int u = 0; u < 5; ++u) xr[u] = X + (size_t)(uint32_t)g[u] * (size_t)(uint32_t)ldx;
-        const int nrow = base + gridDim.x * RPB + rg;
-        const int nsafe = nrow < n ? nrow : n - 1;
-        const bool store_ok = own && !hub;
-        float tx[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-        uint32_t cw[5] = {0u, 0u, 0u, 0u, 0u};
-        for (int cb = 0; cb < xch || cb == 0; cb += LPR) {
-            const int c = cb + sub;
-            const bool live = c < xch;
-            const int cc = live ? c : (xch > 0 ? xch - 1 : 0);          // lanes past the last whole chunk repeat its load
-            float4 t[5];
-#pragma unroll
-            for (int u = 0; u < 5; ++u) t[u] = *reinterpret_cast<const float4*>(xr[u] + 4 * cc);
-            if (cb == 0) {                           // (uniform) first pass: the tail lanes' operands and the next records
-                if (F & 3) {
-#pragma unroll
-                    for (int u = 0; u < 5; ++u) tx[u] = xr[u][tcol_x];
-                }
-                if (num_ind > 0) {
-#pragma unroll
-                    for (int u = 0; u < 5; ++u) cw[u] = code[g[u]];
-                }
-                // h0..h2 are dead from here: every field was copied out above
-                h0 = head[3 * (long long)nsafe]; h1 = head[3 * (long long)nsafe + 1]; h2 = head[3 * (long long)nsafe + 2];
-            }
-            float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                acc.x = fmaf(w[u], t[u].x, acc.x); acc.y = fmaf(w[u], t[u].y, acc.y);
-                acc.z = fmaf(w[u], t[u].z, acc.z); acc.w = fmaf(w[u], t[u].w, acc.w);
-            }
-            if (len > 4 && !hub) {           // entries 5 .. GRAPES_HUB_ROW through the CSR, two per round trip, in CSR order
-                const int beg = rowptr[row];
-#pragma unroll 1
-                for (int q = 4; q < len; q += 2) {
-                    const int q1 = q + 1 < len ? q + 1 : q;
-                    const int s0 = csr[beg + q], s1 = csr[beg + q1];
-                    const float w0 = dinv[s0] * dc, w1 = dinv[s1] * dc;
-                    const int v0 = ids[s0], v1 = ids[s1];
-                    const float4 t0 = *reinterpret_cast<const float4*>(X + (size_t)(uint32_t)v0 * (size_t)(uint32_t)ldx + 4 * cc);
-                    const float4 t1 = *reinterpret_cast<const float4*>(X + (size_t)(uint32_t)v1 * (size_t)(uint32_t)ldx + 4 * cc);
-                    acc.x = fmaf(w0, t0.x, acc.x); acc.y = fmaf(w0, t0.y, acc.y);
-                    acc.z = fmaf(w0, t0.z, acc.z); acc.w = fmaf(w0, t0.w, acc.w);
-                    if (q + 1 < len) {
-                        acc.x = fmaf(w1, t1.x, acc.x); acc.y = fmaf(w1, t1.y, acc.y);
-                        acc.z = fmaf(w1, t1.z, acc.z); acc.w = fmaf(w1, t1.w, acc.w);
-                    }
-                }
-            }
-            acc.x = fmaf(w[4], t[4].x, acc.x); acc.y = fmaf(w[4], t[4].y, acc.y);   // unit self-loop last
-            acc.z = fmaf(w[4], t[4].z, acc.z); acc.w = fmaf(w[4], t[4].w, acc.w);
-            // the next batch's records are consumed HERE, before the stores: they arrived with the features, and a first use
-            // after a store would wait for the store's acknowledgement as well (one counter, in order)
-            asm volatile("" :: "v"(h0.x), "v"(h1.x), "v"(h2.x));
-            if (live && store_ok) *reinterpret_cast<float4*>(out + (size_t)row * Fo + 4 * c) = acc;
-        }
-        if (sub < tcols && store_ok) {       // tail columns, one lane each: same entry order (head entries, CSR, self-loop)
-            const int ib = tcol - F;         // indicator bit of this column (< 0: a column of X; >= num_ind: padding)
-            const bool isx = ib < 0, isb = ib >= 0 && ib < num_ind;
-            const int ibc = isb ? ib : 0;
-            float acc = 0.f;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc = fmaf(w[u], isx ? tx[u] : (isb ? code_bit_f(cw[u], epoch, ibc) : 0.f), acc);
-            if (len > 4) {
-                const int beg = rowptr[row];
-#pragma unroll 1
-                for (int q = 4; q < len; ++q) {
-                    const int s0 = csr[beg + q];
-                    const float w0 = dinv[s0] * dc;
-                    const int v0 = ids[s0];
-                    const float f0 = isx ? X[(size_t)(uint32_t)v0 * (size_t)(uint32_t)ldx + tcol_x]
-                                         : (isb ? code_bit_f(code[v0], epoch, ibc) : 0.f);
-                    acc = fmaf(w0, f0, acc);
-                }
-            }
-            acc = fmaf(w[4], isx ? tx[4] : (isb ? code_bit_f(cw[4], epoch, ibc) : 0.f), acc);
-            out[(size_t)row * Fo + tcol] = acc;
-        }
-        if (stamp_it < 4) GRAPES_STAMP(stamp_it * 3 + 2);
-        lds_barrier();
-        if (stamp_it < 4) GRAPES_STAMP(stamp_it * 3 + 3);
-        ++stamp_it;
-        const int cur = slot;
-        slot = slot == 2 ? 0 : slot + 1;
-        if (threadIdx.x == 0) s_nhub[slot == 2 ? 0 : slot + 1] = 0;        // the slot of the batch after next
-        // ---- hub rows of this batch of rows: the row groups take the eight strided chains of row_accumulate_hub between them
-        // (group rg: chains rg, rg + RPB, ...), the chains are combined in chain order, then the self-loop — by the row's OWN
-        // group: its earlier store to the same addresses (above) is then older in the same wavefront
-        const int nh = s_nhub[cur];
-        for (int i = 0; i < nh; ++i) {
-            const int hrow = s_hub[cur][i];      // list order varies run to run; each row's result does not depend on it
-            const int beg = rowptr[hrow], hlen = rowptr[hrow + 1] - beg;
-            const float hdc = dinv[hrow];
-            for (int cb = 0; cb < chunks; cb += LPR) {
-                const int c = cb + sub;
-                const bool live = c < chunks;
-                for (int r = rg; r < 8; r += RPB) {
-                    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if (live) {
-#pragma unroll 1
-                        for (int q = r; q < hlen; q += 16) {          // two entries of the chain per round trip
-                            const int q1 = q + 8 < hlen ? q + 8 : q;
-                            const int s0 = csr[beg + q], s1 = csr[beg + q1];
-                            const float w0 = dinv[s0] * hdc, w1 = dinv[s1] * hdc;
-                            const int v0 = ids[s0], v1 = ids[s1];
-                            float4 t0 = feat_chunk_load(X, ldx, v0, c), t1 = feat_chunk_load(X, ldx, v1, c);
-                            uint32_t c0 = 0u, c1 = 0u;
-                            if (num_ind > 0) { c0 = code[v0]; c1 = code[v1]; }
-                            t0 = feat_chunk_fix(t0, c0, c, F, epoch); t1 = feat_chunk_fix(t1, c1, c, F, epoch);
-                            acc.x = fmaf(w0, t0.x, acc.x); acc.y = fmaf(w0, t0.y, acc.y);
-                            acc.z = fmaf(w0, t0.z, acc.z); acc.w = fmaf(w0, t0.w, acc.w);
-                            if (q + 8 < hlen) {
-                                acc.x = fmaf(w1, t1.x, acc.x); acc.y = fmaf(w1, t1.y, acc.y);
-                                acc.z = fmaf(w1, t1.z, acc.z); acc.w = fmaf(w1, t1.w, acc.w);
-                            }
-                        }
-                    }
-                    s_part[r][sub] = acc;
-                }
-                __syncthreads();
-                if (rg == hrow - base && live) {
-                    float4 acc = s_part[0][sub];
-#pragma unroll
-                    for (int r = 1; r < 8; ++r) { const float4 p = s_part[r][sub]; acc.x += p.x; acc.y += p.y; acc.z += p.z; acc.w += p.w; }
-                    const int vs = ids[hrow];
-                    uint32_t cs = 0u;
-                    if (num_ind > 0) cs = code[vs];
-                    const float4 ts = feat_chunk_fix(feat_chunk_load(X, ldx, vs, c), cs, c, F, epoch);
-                    const float wss = hdc * hdc;
-                    acc.x = fmaf(wss, ts.x, acc.x); acc.y = fmaf(wss, ts.y, acc.y);
-                    acc.z = fmaf(wss, ts.z, acc.z); acc.w = fmaf(wss, ts.w, acc.w);
-                    *reinterpret_cast<float4*>(out + (long long)hrow * Fo + c * 4) = acc;
-                }
-                __syncthreads();
-            }
-        }
-    }
-    GRAPES_STAMP(14);
-    grapes_clock_end(clk, clk0);
-}
-
-__device__ __forceinline__ void gr_fma4(float4& acc, float w, const float4& t) {
-    acc.x = fmaf(w, t.x, acc.x); acc.y = fmaf(w, t.y, acc.y); acc.z = fmaf(w, t.z, acc.z); acc.w = fmaf(w, t.w, acc.w);
-}
-
-// ---- the production form of the head-record kernel.  What the measurements said (profiles/gather_bound_probe.py): a
+// ---- the head-record kernel.  What the measurements said (profiles/gather_bound_probe.py): a
 // stripped gather over the same records — every lane of a 32-lane row group loads the 48-byte record itself, five feature
 // rows, one FMA pass, one store, ~40 registers — runs the hop-2 shape in 7.6 us warm / 14 us cold, HALF the time of the
-// earlier forms, and the number of row loads (two or five) or who loads the record hardly matters.  What cost the other
+// earlier record forms (one batch loop for every row; since removed), and the number of row loads (two or five) or who
+// loads the record hardly matters.  What cost those forms the other
 // half was everything around it: a workgroup barrier and LDS traffic per batch for hub rows, per-lane chunk correction for
 // the indicator columns (more vector instructions than the product), 85-115 registers (5 wavefronts per SIMD instead of
 // 7-8) — and the rows LONGER than the record: 0.4 % of a frontier's rows, each a chain of ~10-25 dependent memory round
@@ -1180,33 +963,36 @@ __device__ __forceinline__ void gcn_aggregate_gather_head5_body(const float* __r
     grapes_clock_end(clk, clk0);
 }
 
-template <int LPR, bool PEER = false>
-__global__ __launch_bounds__(256) void gcn_aggregate_gather_head5_k(const float* __restrict__ X, int F, int ldx,
-                                                                    const int32_t* __restrict__ ids,
-                                                                    const uint32_t* __restrict__ code, uint32_t epoch_host,
-                                                                    const uint32_t* d_epoch, int num_ind,
-                                                                    const int32_t* __restrict__ rowptr,
-                                                                    const int32_t* __restrict__ csr,
-                                                                    const float* __restrict__ dinv,
-                                                                    const int4* __restrict__ head, float* __restrict__ out,
-                                                                    int n_host, const int32_t* d_n, int NL, unsigned long long* clk,
-                                                                    PeerX px = PeerX()) {
-    gcn_aggregate_gather_head5_body<LPR, PEER>(X, F, ldx, ids, code, epoch_host, d_epoch, num_ind, rowptr, csr, dinv, head, out, n_host,
-                                               d_n, NL, clk, px, (int)blockIdx.x, (int)gridDim.x);
-}
-// two gather-SpMMs side by side in one launch (riders: common.h): workgroups [0, nA) work on `a`, the rest on `b`; no clock stamps
+// the body's arguments as one block: what the host builds once per call, a rider record stores and every kernel below takes
 struct GatherHead5Args {
     const float* X; int F; int ldx; const int32_t* ids; const uint32_t* code; uint32_t epoch_host; const uint32_t* d_epoch; int num_ind;
     const int32_t* rowptr; const int32_t* csr; const float* dinv; const int4* head; float* out; int n_host; const int32_t* d_n; int NL;
 };
 struct GatherPeerArgs { GatherHead5Args a; PeerX px; };      // a recorded peer-form gather: the shard table rides behind the arguments
+// The one way from the block to the body, inside a kernel template <int LPR, bool PEER> (like SORT_ROWS_CALL).  Not a function:
+// the block's address would escape into the call, and the kernels that take the block then compile to other, larger code
+// (profiles/gather_launch_resources.txt).  The body's own parameter list carries the __restrict__ facts the compiler sees.
+#define GATHER_HEAD5_CALL(A, clk, px, bid, nblk)                                                                                     \
+    gcn_aggregate_gather_head5_body<LPR, PEER>((A).X, (A).F, (A).ldx, (A).ids, (A).code, (A).epoch_host, (A).d_epoch, (A).num_ind,   \
+                                               (A).rowptr, (A).csr, (A).dinv, (A).head, (A).out, (A).n_host, (A).d_n, (A).NL, clk,  \
+                                               px, bid, nblk)
+// (the launch on its own keeps its loose parameters — the block in their place changes its code, same file — and is launched
+// from the block's fields in one place: gather_fwd_impl)
+template <int LPR, bool PEER>
+__global__ __launch_bounds__(256) void gcn_aggregate_gather_head5_k(
+        const float* __restrict__ X, int F, int ldx, const int32_t* __restrict__ ids, const uint32_t* __restrict__ code,
+        uint32_t epoch_host, const uint32_t* d_epoch, int num_ind, const int32_t* __restrict__ rowptr,
+        const int32_t* __restrict__ csr, const float* __restrict__ dinv, const int4* __restrict__ head, float* __restrict__ out,
+        int n_host, const int32_t* d_n, int NL, unsigned long long* clk, PeerX px) {
+    gcn_aggregate_gather_head5_body<LPR, PEER>(X, F, ldx, ids, code, epoch_host, d_epoch, num_ind, rowptr, csr, dinv, head, out, n_host,
+                                               d_n, NL, clk, px, (int)blockIdx.x, (int)gridDim.x);
+}
+// two gather-SpMMs side by side in one launch (riders: common.h): workgroups [0, nA) work on `a`, the rest on `b`; no clock stamps
 template <int LPR, bool PEER>
 __global__ __launch_bounds__(256) void gcn_aggregate_gather_head5_pair_k(GatherHead5Args a, GatherHead5Args b, int nA, PeerX px) {
     const bool first = (int)blockIdx.x < nA;
     const GatherHead5Args& p = first ? a : b;
-    gcn_aggregate_gather_head5_body<LPR, PEER>(p.X, p.F, p.ldx, p.ids, p.code, p.epoch_host, p.d_epoch, p.num_ind, p.rowptr, p.csr, p.dinv,
-                                               p.head, p.out, p.n_host, p.d_n, p.NL, nullptr, px, first ? (int)blockIdx.x : (int)blockIdx.x - nA,
-                                               first ? nA : (int)gridDim.x - nA);
+    GATHER_HEAD5_CALL(p, nullptr, px, first ? (int)blockIdx.x : (int)blockIdx.x - nA, first ? nA : (int)gridDim.x - nA);
 }
 
 // ---- cross-kernel riders (common.h): the classifier's forward launches have a handful of workgroups on an idle chip, and the
@@ -1219,8 +1005,7 @@ __global__ __launch_bounds__(256) void gcn_aggregate_gather_head5_pair_k(GatherH
 template <int LPR, bool PEER>
 __global__ __launch_bounds__(256) void gather_head5_sort_pair_k(GatherHead5Args a, SortRowsArgs b, int nA, PeerX px) {
     if ((int)blockIdx.x < nA)
-        gcn_aggregate_gather_head5_body<LPR, PEER>(a.X, a.F, a.ldx, a.ids, a.code, a.epoch_host, a.d_epoch, a.num_ind, a.rowptr, a.csr, a.dinv,
-                                                   a.head, a.out, a.n_host, a.d_n, a.NL, nullptr, px, (int)blockIdx.x, nA);
+        GATHER_HEAD5_CALL(a, nullptr, px, (int)blockIdx.x, nA);
     else
         SORT_ROWS_CALL(b, (int)blockIdx.x - nA, (int)gridDim.x - nA);
 }
@@ -1235,9 +1020,7 @@ __global__ __launch_bounds__(256) void gcn_aggregate_gather_pair_k(AggregateArgs
         gcn_aggregate_body<4, 0>(a.h, a.rowptr, a.csr, a.dinv, a.bias, a.out, a.n_host, a.d_n, a.F, a.relu, 0, nullptr, R1{nullptr, nullptr},
                                  nullptr, nullptr, (int)blockIdx.x, nA);
     else
-        gcn_aggregate_gather_head5_body<LPR, PEER>(b.X, b.F, b.ldx, b.ids, b.code, b.epoch_host, b.d_epoch, b.num_ind, b.rowptr, b.csr, b.dinv,
-                                                   b.head, b.out, b.n_host, b.d_n, b.NL, nullptr, px, (int)blockIdx.x - nA,
-                                                   (int)gridDim.x - nA);
+        GATHER_HEAD5_CALL(b, nullptr, px, (int)blockIdx.x - nA, (int)gridDim.x - nA);
 }
 
 #ifdef GRAPES_HOP_UNITY
@@ -1313,6 +1096,27 @@ extern "C" int grapes_debug_gather_probe(const float* X, int32_t ldx, const int3
 #endif  // GRAPES_DIAG
 
 GRAPES_STAMP_SETTER(grapes_stamp_set_spmm)
+// ---- the variant of a gather's rider record (GRAPES_RK_GATHER): 1 / 2 = 32 / 64 lanes per row over the local matrix;
+// 0x4... / 0x2... = the same through a shard table, whose hash fills the low 28 bits (a rider and the gather that hosts it
+// read through ONE table) and which follows the arguments in the record (GatherPeerArgs)
+static int gather_variant(bool narrow, const PeerX* px) {
+    if (!px) return narrow ? 1 : 2;
+    uint32_t hv = 2166136261u;
+    for (size_t q = 0; q < sizeof(PeerX); ++q) hv = (hv ^ reinterpret_cast<const unsigned char*>(px)[q]) * 16777619u;
+    return (int)((narrow ? 0x40000000u : 0x20000000u) | (hv & 0x0fffffffu));
+}
+static void gather_variant_read(int variant, bool& narrow, bool& peer) {
+    peer = (variant & 0x60000000) != 0;
+    narrow = peer ? (variant & 0x40000000) != 0 : variant == 1;
+}
+// the run-time pair (narrow, peer) as the template pair <32 | 64 lanes per row, PEER>: f(integral_constant<int, LPR>, bool_constant<PEER>)
+template <class Fn>
+static void gather_lanes_peer(bool narrow, bool peer, Fn&& f) {
+    using L32 = std::integral_constant<int, 32>; using L64 = std::integral_constant<int, 64>;
+    if (peer) { if (narrow) f(L32{}, std::true_type{}); else f(L64{}, std::true_type{}); }
+    else      { if (narrow) f(L32{}, std::false_type{}); else f(L64{}, std::false_type{}); }
+}
+
 static int gather_fwd_impl(const float* X, int32_t F, int32_t x_stride, const int32_t* ids,
                            const uint32_t* ind_code, uint32_t epoch, const uint32_t* d_epoch,
                            int32_t num_ind, const int32_t* rowptr_t, const int32_t* csr_src,
@@ -1336,101 +1140,49 @@ static int gather_fwd_impl(const float* X, int32_t F, int32_t x_stride, const in
         // 32 lanes per row whenever the WHOLE chunks of X fit them (F <= 131): the columns after them — indicators, the last
         // F % 4 features, padding: at most 12 — are the tail lanes' scalar columns either way.  (F = 128 + 3 indicators is 33
         // chunks: by the chunk count it went to the 64-lane form with 31 of a row group's lanes idle — arxiv, papers100M.)
-        static int narrow_rule = -1;
-        if (narrow_rule < 0) { const char* e = grapes_tune_env("GRAPES_GATHER_NARROW_BY_CHUNKS"); narrow_rule = (e && atoi(e)) ? 1 : 0; }
-        const bool narrow = narrow_rule ? chunks <= 32 : (F >> 2) <= 32;
-        static int form = -1, nlong = 0;
-        if (form < 0) {
-            const char* e = grapes_tune_env("GRAPES_GATHER_FORM"); form = e ? atoi(e) : 5;      // 5 (default); 2: the earlier form
-            const char* l = grapes_tune_env("GRAPES_GATHER_LONG_WGS"); nlong = l ? atoi(l) : 128; if (nlong < 1) nlong = 128;
+        const bool narrow = (F >> 2) <= 32;
+        const bool peer = px != nullptr;             // rows read from the peers' shards
+        // resident workgroups that loop over the short rows + `NL` workgroups for the long rows
+        const int rpb = narrow ? 8 : 4;
+        int grid = grapes_div_up(n, rpb); if (grid > gcap) grid = gcap;
+        int NL = 128; if (NL > grid) NL = grid;
+        if (grapes_rider_recording()) { grid = grapes_rider_grid(grid) * 4; NL = grapes_rider_grid(NL) / 4; if (NL < 1) NL = 1; }
+        grid += NL;
+        const GatherHead5Args GA{X, F, ldx, ids, ind_code, epoch, d_epoch, num_ind, rowptr_t, csr_src, dinv, hd, out, n, d_n, NL};
+        const PeerX pxv = peer ? *px : PeerX();
+        const int variant = gather_variant(narrow, px);
+        auto single = [=](hipStream_t s_) {
+            unsigned long long* clk = grapes_clock_reserve(narrow ? "gcn_aggregate_gather_head5_k<32>" : "gcn_aggregate_gather_head5_k<64>", grid, 4);
+            gather_lanes_peer(narrow, peer, [&](auto L, auto P) {
+                hipLaunchKernelGGL((gcn_aggregate_gather_head5_k<decltype(L)::value, decltype(P)::value>), dim3(grid), dim3(256), 0, s_, GA.X, GA.F,
+                                   GA.ldx, GA.ids, GA.code, GA.epoch_host, GA.d_epoch, GA.num_ind, GA.rowptr, GA.csr, GA.dinv, GA.head, GA.out,
+                                   GA.n_host, GA.d_n, GA.NL, clk, pxv);
+            });
+        };
+        if (grapes_rider_recording()) {
+            // (a peer-form record carries the shard table behind the arguments: a host of another kernel launches the rider with it)
+            if (peer) grapes_rider_record(grapes_rider_make(GRAPES_RK_GATHER, variant, grid, 256, GatherPeerArgs{GA, pxv}, single));
+            else grapes_rider_record(grapes_rider_make(GRAPES_RK_GATHER, variant, grid, 256, GA, single));
+            return 0;
         }
-        if (px) {       // rows read from the peers' shards (always the production form)
-            const int rpb = narrow ? 8 : 4;
-            int grid = grapes_div_up(n, rpb); if (grid > gcap) grid = gcap;
-            int NL = nlong; if (NL > grid) NL = grid;
-            if (grapes_rider_recording()) { grid = grapes_rider_grid(grid) * 4; NL = grapes_rider_grid(NL) / 4; if (NL < 1) NL = 1; }
-            grid += NL;
-            const GatherHead5Args GA{X, F, ldx, ids, ind_code, epoch, d_epoch, num_ind, rowptr_t, csr_src, dinv, hd, out, n, d_n, NL};
-            const PeerX pxv = *px;
-            // (a rider of this launch — or this launch as a rider — reads through the SAME shard table: the variant carries its hash)
-            uint32_t hv = 2166136261u;
-            for (size_t q = 0; q < sizeof(PeerX); ++q) hv = (hv ^ reinterpret_cast<const unsigned char*>(&pxv)[q]) * 16777619u;
-            const int variant = (int)((narrow ? 0x40000000u : 0x20000000u) | (hv & 0x0fffffffu));
-            auto single = [=](hipStream_t s_) {
-                if (narrow)
-                    hipLaunchKernelGGL((gcn_aggregate_gather_head5_k<32, true>), dim3(grid), dim3(256), 0, s_, X, F, ldx, ids, ind_code, epoch, d_epoch,
-                                       num_ind, rowptr_t, csr_src, dinv, hd, out, n, d_n, NL, grapes_clock_reserve("gcn_aggregate_gather_head5_k<32>", grid, 4), pxv);
-                else
-                    hipLaunchKernelGGL((gcn_aggregate_gather_head5_k<64, true>), dim3(grid), dim3(256), 0, s_, X, F, ldx, ids, ind_code, epoch, d_epoch,
-                                       num_ind, rowptr_t, csr_src, dinv, hd, out, n, d_n, NL, grapes_clock_reserve("gcn_aggregate_gather_head5_k<64>", grid, 4), pxv);
-            };
-            if (grapes_rider_recording()) {
-                // (the record carries the shard table behind the arguments: a host of another kernel launches the rider with it)
-                const GatherPeerArgs GP{GA, pxv};
-                grapes_rider_record(grapes_rider_make(GRAPES_RK_GATHER, variant, grid, 256, GP, single));
-                return 0;
-            }
+        // (with the kernel clock table enabled every launch keeps its own stamps: nothing rides)
+        const bool ride = !grapes_clock_enabled();
 #ifdef GRAPES_HOP_UNITY
-            if (const GrapesRiderRecord* rs = grapes_clock_enabled() ? nullptr : grapes_rider_match(GRAPES_RK_SORT, 0, 256, s)) {
-                SortRowsArgs Sq; memcpy(&Sq, rs->args, sizeof Sq);
-                if (narrow) hipLaunchKernelGGL((gather_head5_sort_pair_k<32, true>), dim3(grid + rs->grid), dim3(256), 0, s, GA, Sq, grid, pxv);
-                else hipLaunchKernelGGL((gather_head5_sort_pair_k<64, true>), dim3(grid + rs->grid), dim3(256), 0, s, GA, Sq, grid, pxv);
-                GRAPES_LAUNCH_CHECK();
-                return 0;
-            }
+        if (const GrapesRiderRecord* rs = ride ? grapes_rider_match(GRAPES_RK_SORT, 0, 256, s) : nullptr) {
+            SortRowsArgs Sq; memcpy(&Sq, rs->args, sizeof Sq);
+            gather_lanes_peer(narrow, peer, [&](auto L, auto P) {
+                hipLaunchKernelGGL((gather_head5_sort_pair_k<decltype(L)::value, decltype(P)::value>), dim3(grid + rs->grid), dim3(256), 0, s, GA, Sq, grid, pxv);
+            });
+        } else
 #endif
-            const GrapesRiderRecord* r = grapes_clock_enabled() ? nullptr : grapes_rider_match(GRAPES_RK_GATHER, variant, 256, s);
-            if (r) {
-                GatherHead5Args Bq; memcpy(&Bq, r->args, sizeof Bq);
-                if (narrow) hipLaunchKernelGGL((gcn_aggregate_gather_head5_pair_k<32, true>), dim3(grid + r->grid), dim3(256), 0, s, GA, Bq, grid, pxv);
-                else hipLaunchKernelGGL((gcn_aggregate_gather_head5_pair_k<64, true>), dim3(grid + r->grid), dim3(256), 0, s, GA, Bq, grid, pxv);
-            } else {
-                single(s);
-            }
-        } else if (form != 2) {
-            // resident workgroups that loop over the short rows + `NL` workgroups for the long rows
-            const int rpb = narrow ? 8 : 4;
-            int grid = grapes_div_up(n, rpb); if (grid > gcap) grid = gcap;
-            int NL = nlong; if (NL > grid) NL = grid;
-            if (grapes_rider_recording()) { grid = grapes_rider_grid(grid) * 4; NL = grapes_rider_grid(NL) / 4; if (NL < 1) NL = 1; }
-            grid += NL;
-            const GatherHead5Args GA{X, F, ldx, ids, ind_code, epoch, d_epoch, num_ind, rowptr_t, csr_src, dinv, hd, out, n, d_n, NL};
-            const int variant = narrow ? 1 : 2;
-            auto single = [=](hipStream_t s_) {
-                if (narrow)
-                    hipLaunchKernelGGL((gcn_aggregate_gather_head5_k<32>), dim3(grid), dim3(256), 0, s_, X, F, ldx, ids, ind_code, epoch, d_epoch,
-                                       num_ind, rowptr_t, csr_src, dinv, hd, out, n, d_n, NL, grapes_clock_reserve("gcn_aggregate_gather_head5_k<32>", grid, 4));
-                else
-                    hipLaunchKernelGGL((gcn_aggregate_gather_head5_k<64>), dim3(grid), dim3(256), 0, s_, X, F, ldx, ids, ind_code, epoch, d_epoch,
-                                       num_ind, rowptr_t, csr_src, dinv, hd, out, n, d_n, NL, grapes_clock_reserve("gcn_aggregate_gather_head5_k<64>", grid, 4));
-            };
-            if (grapes_rider_recording()) { grapes_rider_record(grapes_rider_make(GRAPES_RK_GATHER, variant, grid, 256, GA, single)); return 0; }
-            // (with the kernel clock table enabled every launch keeps its own stamps: nothing rides)
-#ifdef GRAPES_HOP_UNITY
-            if (const GrapesRiderRecord* rs = grapes_clock_enabled() ? nullptr : grapes_rider_match(GRAPES_RK_SORT, 0, 256, s)) {
-                SortRowsArgs Sq; memcpy(&Sq, rs->args, sizeof Sq);
-                if (narrow) hipLaunchKernelGGL((gather_head5_sort_pair_k<32, false>), dim3(grid + rs->grid), dim3(256), 0, s, GA, Sq, grid, PeerX());
-                else hipLaunchKernelGGL((gather_head5_sort_pair_k<64, false>), dim3(grid + rs->grid), dim3(256), 0, s, GA, Sq, grid, PeerX());
-                GRAPES_LAUNCH_CHECK();
-                return 0;
-            }
-#endif
-            const GrapesRiderRecord* r = grapes_clock_enabled() ? nullptr : grapes_rider_match(GRAPES_RK_GATHER, variant, 256, s);
-            if (r) {
-                GatherHead5Args Bq; memcpy(&Bq, r->args, sizeof Bq);
-                if (narrow) hipLaunchKernelGGL((gcn_aggregate_gather_head5_pair_k<32, false>), dim3(grid + r->grid), dim3(256), 0, s, GA, Bq, grid, PeerX());
-                else hipLaunchKernelGGL((gcn_aggregate_gather_head5_pair_k<64, false>), dim3(grid + r->grid), dim3(256), 0, s, GA, Bq, grid, PeerX());
-            } else {
-                single(s);
-            }
-        } else if (chunks <= 32) {
-            int grid = grapes_div_up(n, 8); if (grid > gcap) grid = gcap;
-            hipLaunchKernelGGL((gcn_aggregate_gather_head_k<32>), dim3(grid), dim3(256), 0, s, X, F, ldx, ids, ind_code, epoch, d_epoch,
-                               num_ind, rowptr_t, csr_src, dinv, hd, out, n, d_n, grapes_clock_reserve("gcn_aggregate_gather_head_k<32>", grid, 4));
+        // (a gather that rides here reads through the SAME shard table: the variant carries its hash)
+        if (const GrapesRiderRecord* r = ride ? grapes_rider_match(GRAPES_RK_GATHER, variant, 256, s) : nullptr) {
+            GatherHead5Args Bq; memcpy(&Bq, r->args, sizeof Bq);
+            gather_lanes_peer(narrow, peer, [&](auto L, auto P) {
+                hipLaunchKernelGGL((gcn_aggregate_gather_head5_pair_k<decltype(L)::value, decltype(P)::value>), dim3(grid + r->grid), dim3(256), 0, s, GA, Bq, grid, pxv);
+            });
         } else {
-            int grid = grapes_div_up(n, 4); if (grid > 2048) grid = 2048;
-            hipLaunchKernelGGL((gcn_aggregate_gather_head_k<64>), dim3(grid), dim3(256), 0, s, X, F, ldx, ids, ind_code, epoch, d_epoch,
-                               num_ind, rowptr_t, csr_src, dinv, hd, out, n, d_n, grapes_clock_reserve("gcn_aggregate_gather_head_k<64>", grid, 4));
+            single(s);
         }
         GRAPES_LAUNCH_CHECK();
         return 0;
@@ -1744,18 +1496,14 @@ static int launch_aggregate_t(const float* h, const int32_t* rowptr, const int32
         } else
 #endif
         if (r) {
-            // variant: 1 / 2 = 32 / 64 lanes per row over the local matrix; 0x4... / 0x2... = the same through a shard table,
-            // which then follows the arguments in the record
-            GatherHead5Args Bq; memcpy(&Bq, r->args, sizeof Bq);
-            PeerX pq = PeerX();
-            const bool peer = (r->variant & 0x60000000) != 0;
-            const bool narrow = peer ? (r->variant & 0x40000000) != 0 : r->variant == 1;
-            if (peer) { GatherPeerArgs gp; memcpy(&gp, r->args, sizeof gp); pq = gp.px; }
+            bool narrow, peer;
+            gather_variant_read(r->variant, narrow, peer);
+            GatherPeerArgs gp{};                     // (a local record holds the arguments alone: no shard table behind them)
+            memcpy(&gp, r->args, peer ? sizeof gp : sizeof gp.a);
             const AggregateArgs A{h, rowptr, csr, dinv, bias, out, n, d_n, f, relu};
-            if (peer && narrow) hipLaunchKernelGGL((gcn_aggregate_gather_pair_k<32, true>), dim3(grid + r->grid), dim3(256), 0, s, A, Bq, grid, pq);
-            else if (peer) hipLaunchKernelGGL((gcn_aggregate_gather_pair_k<64, true>), dim3(grid + r->grid), dim3(256), 0, s, A, Bq, grid, pq);
-            else if (narrow) hipLaunchKernelGGL((gcn_aggregate_gather_pair_k<32, false>), dim3(grid + r->grid), dim3(256), 0, s, A, Bq, grid, pq);
-            else hipLaunchKernelGGL((gcn_aggregate_gather_pair_k<64, false>), dim3(grid + r->grid), dim3(256), 0, s, A, Bq, grid, pq);
+            gather_lanes_peer(narrow, peer, [&](auto L, auto P) {
+                hipLaunchKernelGGL((gcn_aggregate_gather_pair_k<decltype(L)::value, decltype(P)::value>), dim3(grid + r->grid), dim3(256), 0, s, A, gp.a, grid, gp.px);
+            });
         } else {
             hipLaunchKernelGGL((gcn_aggregate_k<4, WMODE>), dim3(grid), dim3(256), 0, s, h, rowptr, csr, dinv, bias, out, n, d_n, f, relu, skip,
                                f >= 64 ? grapes_clock_reserve("gcn_aggregate_k<4>", grid, 4) : nullptr);
