@@ -119,6 +119,14 @@ SIGNATURES = {
     "grapes_shadow_sample": (I32, [P, P, I32, P, I32, P, I32, I32, P, U64, U64, P, I32, I32, P, P, P, P, P, P, P, P, P, P, P, P]),
     "grapes_shadow_ppr_sample_workspace_bytes": (SZ, [I32, I32]),
     "grapes_shadow_ppr_sample": (I32, [P, P, I32, P, I32, P, I32, U32, U32, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    # PPRGo: the top-k PPR slot tables, the batch structure and the weighted gathers
+    "grapes_pprgo_topk": (I32, [P, P, I32, P, I32, P, I32, U32, U32, I32, P, P, P, P, P, P, P]),
+    "grapes_pprgo_batch_workspace_bytes": (SZ, [I32, I32]),
+    "grapes_pprgo_batch": (I32, [P, P, I32, I32, I32, P, P, I32, I32, P, P, P, P, P, P, P, P, P, P]),
+    "grapes_pprgo_aggregate_fwd_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_pprgo_aggregate_fwd": (I32, [P, I32, P, P, P, I32, I32, I32, P, P, P, P]),
+    "grapes_pprgo_aggregate_bwd_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_pprgo_aggregate_bwd": (I32, [P, I32, P, I32, P, P, I32, I32, I32, P, I32, P, P, P]),
     "grapes_segment_mean_fwd": (I32, [P, P, I32, I32, I32, P, P, P]),
     "grapes_segment_mean_bwd": (I32, [P, P, I32, I32, I32, P, P, P]),
     # Cluster-GCN: the cluster-union batch and ClusterGCNConv's propagation

@@ -454,6 +454,13 @@ extern "C" int grapes_shadow_sample(const int64_t* rowptr, const int32_t* col, i
 //   shadow_scan_k / shadow_write_k as above (depth 0: there is no stream to advance); the write copies the staged scores.
 // Integer code only, no float, no global atomic beyond the status OR, no kernel waits on another workgroup.  Which lane wins a slot or
 // which touched index a node gets changes nothing: r and p are sums of integers, and the keys are distinct.
+//
+// The rounds and the selection are ppr_push_select, a __device__ function (as shadow_stage is the other half): PPRGo's
+// grapes_pprgo_topk (pprgo_topk_k, below the build kernel) enters it too and then writes the sorted keys' prefix straight out in rank
+// order — no sort by id, no induced-entry count, no scan, no edge write: one launch.  Compiler's remarks for gfx950
+// (-Rpass-analysis=kernel-resource-usage): shadow_ppr_build_k 155 868 B LDS, 56 VGPRs, occupancy 4 waves per SIMD (one workgroup of 16
+// wavefronts per CU, bound by the LDS block), 2 890 instructions (2 889 before the function was cut out; shadow_build_k 1 147 both
+// times); pprgo_topk_k 155 864 B LDS, 50 VGPRs, occupancy 4, 2 090 instructions.
 #define PPR_T 4096                      // the touched-set capacity: part of the rule
 #define PPR_HASH 8192
 #define PPR_ONE (1u << 30)
@@ -491,18 +498,15 @@ __device__ __forceinline__ int ppr_insert(int* hkey, unsigned short* tslot, int*
     return -1;
 }
 
-__global__ __launch_bounds__(SHADOW_THREADS) void shadow_ppr_build_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                                                     int N, const int32_t* __restrict__ roots, int m_host,
-                                                                     const int32_t* __restrict__ d_m, int k, uint32_t alpha_q,
-                                                                     uint32_t thr, int max_rounds, int C,
-                                                                     int32_t* __restrict__ set_out, int32_t* __restrict__ cnt_out,
-                                                                     uint32_t* __restrict__ score_out, int32_t* __restrict__ nb,
-                                                                     int32_t* __restrict__ eb, int32_t* __restrict__ rounds_out,
-                                                                     int32_t* __restrict__ stop_out, int32_t* status) {
-    __shared__ __attribute__((aligned(16))) unsigned char lds[PPR_LDS_BYTES];
-    __shared__ int scan_lds[51];
-    __shared__ int n_touched, n_long, n_valid;
-    __shared__ uint32_t root_score;
+// The first half of a PPR kernel, shared by shadow_ppr_build_k and pprgo_topk_k: the rounds of root `root` (inside [0, N)) and the
+// selection.  Leaves the sorted keys at lds + PPR_O_TRA — key i < n_valid is the i-th best node, (2^32 - 1 - score) << 32 | id — and
+// returns min(n_valid, k); rounds, stop and the root's score go to the caller's variables, `bad` is set by a thread that met a column
+// outside [0, N).  The caller hands over the carved LDS block, block_excl_scan3's 51 ints and the three shared words (n_long = 0 is
+// the stage's and is set here with the others).  Every thread of the workgroup calls it and leaves it behind a barrier.
+__device__ __forceinline__ int ppr_push_select(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N, int root, int k,
+                                               uint32_t alpha_q, uint32_t thr, int max_rounds, unsigned char* lds, int* scan_lds,
+                                               int& n_touched, int& n_long, int& n_valid, uint32_t& root_score, int& rounds_ret,
+                                               int& stop_ret, bool& bad) {
     int* hkey = (int*)(lds + PPR_O_HKEY);
     uint32_t* hr = (uint32_t*)(lds + PPR_O_HR);
     uint32_t* tra = (uint32_t*)(lds + PPR_O_TRA);
@@ -512,18 +516,7 @@ __global__ __launch_bounds__(SHADOW_THREADS) void shadow_ppr_build_k(const int64
     unsigned short* tslot = (unsigned short*)(lds + PPR_O_TSLOT);
     unsigned short* ft = (unsigned short*)(lds + PPR_O_FT);
     unsigned short* foff = (unsigned short*)(lds + PPR_O_FOFF);
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const int live = eff_count(d_m, m_host);
-    const int root = b < live ? roots[b] : -1;
-    if ((unsigned)root >= (unsigned)N) {                                        // (workgroup-uniform) an empty ego-net
-        if (tid == 0) {
-            nb[b] = 0; eb[b] = 0;
-            if (rounds_out) rounds_out[b] = 0;
-            if (stop_out) stop_out[b] = 0;
-            if (b < live && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
-        }
-        return;
-    }
+    const int tid = threadIdx.x;
     for (int i = tid; i < PPR_HASH; i += SHADOW_THREADS) { hkey[i] = SHADOW_EMPTY; hr[i] = 0u; }
     for (int i = tid; i < PPR_T; i += SHADOW_THREADS) tp[i] = 0u;
     __syncthreads();
@@ -533,7 +526,6 @@ __global__ __launch_bounds__(SHADOW_THREADS) void shadow_ppr_build_k(const int64
         n_touched = 1; n_long = 0; n_valid = 0;
     }
     __syncthreads();
-    bool bad = false;
 
     // ---- the rounds
     int known = 0, rounds = 0, stop = 0;
@@ -652,7 +644,40 @@ __global__ __launch_bounds__(SHADOW_THREADS) void shadow_ppr_build_k(const int64
     for (int i = tid; i < P; i += SHADOW_THREADS)                               // the candidates are the keys in front of the first ~0
         if (keys[i] != ~0ull && (i + 1 == P || keys[i + 1] == ~0ull)) n_valid = i + 1;
     __syncthreads();
-    const int n_sel = n_valid < k ? n_valid : k, n = 1 + n_sel;
+    rounds_ret = rounds; stop_ret = stop;
+    return n_valid < k ? n_valid : k;
+}
+
+__global__ __launch_bounds__(SHADOW_THREADS) void shadow_ppr_build_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                                     int N, const int32_t* __restrict__ roots, int m_host,
+                                                                     const int32_t* __restrict__ d_m, int k, uint32_t alpha_q,
+                                                                     uint32_t thr, int max_rounds, int C,
+                                                                     int32_t* __restrict__ set_out, int32_t* __restrict__ cnt_out,
+                                                                     uint32_t* __restrict__ score_out, int32_t* __restrict__ nb,
+                                                                     int32_t* __restrict__ eb, int32_t* __restrict__ rounds_out,
+                                                                     int32_t* __restrict__ stop_out, int32_t* status) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[PPR_LDS_BYTES];
+    __shared__ int scan_lds[51];
+    __shared__ int n_touched, n_long, n_valid;
+    __shared__ uint32_t root_score;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int live = eff_count(d_m, m_host);
+    const int root = b < live ? roots[b] : -1;
+    if ((unsigned)root >= (unsigned)N) {                                        // (workgroup-uniform) an empty ego-net
+        if (tid == 0) {
+            nb[b] = 0; eb[b] = 0;
+            if (rounds_out) rounds_out[b] = 0;
+            if (stop_out) stop_out[b] = 0;
+            if (b < live && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+        }
+        return;
+    }
+    bool bad = false;
+    int rounds, stop;
+    const int n_sel = ppr_push_select(rowptr, col, N, root, k, alpha_q, thr, max_rounds, lds, scan_lds, n_touched, n_long, n_valid, root_score,
+                                      rounds, stop, bad);
+    const int n = 1 + n_sel;
+    const unsigned long long* keys = (const unsigned long long*)(lds + PPR_O_TRA);
 
     // ---- the members enter the shared stage, whose arrays lie over the id slots (dead: the keys carry the ids)
     int* nodes = (int*)(lds + PPR_O_HKEY);
@@ -674,6 +699,65 @@ __global__ __launch_bounds__(SHADOW_THREADS) void shadow_ppr_build_k(const int64
         if (rounds_out) rounds_out[b] = rounds;
         if (stop_out) stop_out[b] = stop;
     }
+}
+
+// grapes_pprgo_topk: the same push and selection WITHOUT the ego-net — a workgroup per root writes the root and the sorted keys'
+// prefix straight into the fixed slots nbr / score [m][K], K = k + 1, in rank order: no sort by id, no induced-entry count, no scan
+// and no edge write, so one launch and no workspace.  Slots at or past cnt[b] hold (root, 0); a root that names no node leaves
+// (-1, 0) and cnt = 0.
+__global__ __launch_bounds__(SHADOW_THREADS) void pprgo_topk_k(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int N,
+                                                               const int32_t* __restrict__ roots, int m_host,
+                                                               const int32_t* __restrict__ d_m, int k, uint32_t alpha_q, uint32_t thr,
+                                                               int max_rounds, int32_t* __restrict__ nbr, uint32_t* __restrict__ score,
+                                                               int32_t* __restrict__ cnt_out, int32_t* __restrict__ rounds_out,
+                                                               int32_t* __restrict__ stop_out, int32_t* status) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds[PPR_LDS_BYTES];
+    __shared__ int scan_lds[51];
+    __shared__ int n_touched, n_long, n_valid;
+    __shared__ uint32_t root_score;
+    const int b = blockIdx.x, tid = threadIdx.x, K = k + 1;
+    const int live = eff_count(d_m, m_host);
+    const int root = b < live ? roots[b] : -1;
+    if ((unsigned)root >= (unsigned)N) {                                        // (workgroup-uniform) no node: empty slots
+        for (int i = tid; i < K; i += SHADOW_THREADS) { nbr[(size_t)b * K + i] = -1; score[(size_t)b * K + i] = 0u; }
+        if (tid == 0) {
+            cnt_out[b] = 0;
+            if (rounds_out) rounds_out[b] = 0;
+            if (stop_out) stop_out[b] = 0;
+            if (b < live && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+        }
+        return;
+    }
+    bool bad = false;
+    int rounds, stop;
+    const int n_sel = ppr_push_select(rowptr, col, N, root, k, alpha_q, thr, max_rounds, lds, scan_lds, n_touched, n_long, n_valid, root_score,
+                                      rounds, stop, bad);
+    const unsigned long long* keys = (const unsigned long long*)(lds + PPR_O_TRA);
+    for (int i = tid; i < K; i += SHADOW_THREADS) {
+        int v = root;
+        uint32_t sc = 0u;
+        if (i == 0) sc = root_score;
+        else if (i <= n_sel) { const unsigned long long key = keys[i - 1]; v = (int)(uint32_t)key; sc = 0xffffffffu - (uint32_t)(key >> 32); }
+        nbr[(size_t)b * K + i] = v; score[(size_t)b * K + i] = sc;
+    }
+    if (tid == 0) {
+        cnt_out[b] = 1 + n_sel;
+        if (rounds_out) rounds_out[b] = rounds;
+        if (stop_out) stop_out[b] = stop;
+    }
+    if (bad && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
+}
+
+extern "C" int grapes_pprgo_topk(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* roots, int32_t m,
+                                 const int32_t* d_m, int32_t k, uint32_t alpha_q, uint32_t thr, int32_t max_rounds, int32_t* nbr,
+                                 uint32_t* score, int32_t* cnt, int32_t* rounds, int32_t* stop, int32_t* status, grapes_stream_t stream) {
+    if (num_nodes <= 0 || m < 1 || m > SHADOW_MAX_ROOTS || k < 1 || k > PPR_MAX_K) return GRAPES_EINVAL;
+    if (alpha_q < 1u || alpha_q > 65535u || thr < 1u || thr > PPR_ONE || max_rounds < 1 || max_rounds > PPR_MAX_ROUNDS) return GRAPES_EINVAL;
+    if (!rowptr || !col || !roots || !nbr || !score || !cnt) return GRAPES_EINVAL;
+    hipLaunchKernelGGL(pprgo_topk_k, dim3(m), dim3(SHADOW_THREADS), 0, (hipStream_t)stream, rowptr, col, num_nodes, roots, m, d_m, k,
+                       alpha_q, thr, max_rounds, nbr, score, cnt, rounds, stop, status);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
 }
 
 // set int32[m * C] | cnt int32[m * C] | score uint32[m * C] | nb int32[m] | eb int32[m] | eoff int32[m + 1], C = k + 1

@@ -3376,6 +3376,141 @@ def segment_mean_bwd(g, ptr, n_rows: int, status=None, out=None):
     return out
 
 
+# ------------------------------------------------------------------------------- PPRGo: top-k PPR slot tables and the weighted gathers
+# [Bojchevski et al., KDD 2020 — recalled] (grapes_hip.h, csrc/shadow_kernels.hip for the push, csrc/pprgo_kernels.hip)
+PPRGO_MAX_ROOTS = SHADOW_MAX_ROOTS
+PPRGO_MAX_SLOTS = SHADOW_PPR_MAX_K + 1       # K = k + 1
+PPRGO_ITEM_CAP_MAX = 1 << 22
+
+
+def pprgo_topk(rowptr, col, num_nodes: int, roots, k: int, alpha_q: int, thr: int, max_rounds: int, d_m=None, status=None, out=None):
+    """(nbr int32 [B, K], score int32 [B, K], cnt int32 [B], rounds int32 [B], stop int32 [B]) of grapes_pprgo_topk, K = k + 1: the push
+    and the selection of shadow_ppr_sample without the ego-net, in fixed slots — slot 0 the root, then the best nodes by score
+    descending, id ascending; slots at or past cnt[b] hold (root, 0).  score is the fixed-point score in units of 2^-30 (at most 2^30,
+    so int32 holds the library's uint32).  One launch, no workspace, no random numbers.  out: the five tensors to write."""
+    K = shadow_ppr_args(k, alpha_q, thr, max_rounds)
+    N, B = _list_rows("pprgo_topk", rowptr, col, num_nodes, roots, d_m, status, int(num_nodes) < 1)
+    if B > PPRGO_MAX_ROOTS:
+        raise ValueError(f"pprgo_topk: at most {PPRGO_MAX_ROOTS} roots per call")
+    if col.numel() >= 2 ** 31:
+        raise ValueError("pprgo_topk: a graph with 2^31 or more entries is not built")
+    dev = roots.device
+    if out is None:
+        i32 = lambda *shape: torch.empty(shape, dtype=_i32, device=dev)
+        out = (i32(B, K), i32(B, K), i32(B), i32(B), i32(B))
+    nbr, score, cnt, rounds, stop = out
+    for t, name in ((nbr, "nbr"), (score, "score"), (cnt, "cnt"), (rounds, "rounds"), (stop, "stop")):
+        _chk(t, _i32, name)
+    if nbr.numel() < B * K or score.numel() < B * K or cnt.numel() < B or rounds.numel() < B or stop.numel() < B:
+        raise ValueError("pprgo_topk: nbr and score hold B * (k + 1) values, cnt, rounds and stop B")
+    if col.numel() == 0:
+        col = _ws(16, dev)                                           # (a graph without an entry: any address, never read)
+    _lib.check(lib().grapes_pprgo_topk(_p(rowptr), _p(col), N, _p(roots), B, _p(d_m), int(k), int(alpha_q), int(thr), int(max_rounds),
+                                       _p(nbr), _p(score), _p(cnt), _p(rounds), _p(stop), _p(status), _stream()), "pprgo_topk")
+    return nbr, score, cnt, rounds, stop
+
+
+def pprgo_scratch(num_nodes: int, device):
+    """(bits int64 [ceil(N / 64)] zeroed, node_map int32 [N]): pprgo_batch's scratch, made once per graph.  bits is zero at rest —
+    every call returns it so; node_map may hold anything."""
+    N = int(num_nodes)
+    return torch.zeros((N + 63) // 64, dtype=_i64, device=device), torch.empty(N, dtype=_i32, device=device)
+
+
+def _pprgo_slots(who, nbr_like, cnt, names):
+    _chk(cnt, _i32, "cnt")
+    if nbr_like.dim() != 2 or cnt.numel() != nbr_like.shape[0] or not 1 <= nbr_like.shape[0] <= PPRGO_MAX_ROOTS or \
+            not 2 <= nbr_like.shape[1] <= PPRGO_MAX_SLOTS:
+        raise ValueError(f"{who}: {names} is [m, K] with 1 <= m <= {PPRGO_MAX_ROOTS}, 2 <= K <= {PPRGO_MAX_SLOTS}, and cnt holds m values")
+    return int(nbr_like.shape[0]), int(nbr_like.shape[1])
+
+
+def pprgo_batch(nbr, cnt, num_nodes: int, scratch, n_cap: Optional[int] = None, e_cap: Optional[int] = None, status=None, out=None):
+    """(node_idx int32 [n_cap], loc int32 [m, K], tptr int32 [n_cap + 1], tslot int32 [e_cap], counts int32 [3]) of grapes_pprgo_batch
+    over the slot tables nbr / cnt: the ascending union of the live slots' ids, each slot's rank in it (a dead slot repeats slot
+    0's), and the by-source inverted index with ascending flat slot indices; counts = (n, E, the longest segment), one host read;
+    the rule is in grapes_hip.h.  scratch: ops.pprgo_scratch(N, device), returned as it must be on entry.  n_cap and e_cap default to
+    m * K, which cannot overflow.  out: the five tensors to write."""
+    _chk(nbr, _i32, "nbr"); _chk(status, _i32, "status", True)
+    m, K = _pprgo_slots("pprgo_batch", nbr, cnt, "nbr")
+    bits, node_map = scratch
+    _chk(bits, _i64, "scratch bits"); _chk(node_map, _i32, "scratch node_map")
+    N, dev = int(num_nodes), nbr.device
+    if N < 1 or bits.numel() < (N + 63) // 64 or node_map.numel() < N:
+        raise ValueError("pprgo_batch: scratch is ops.pprgo_scratch(num_nodes, device)")
+    nc, ec = (m * K if n_cap is None else int(n_cap)), (m * K if e_cap is None else int(e_cap))
+    if nc < 1 or ec < 1:
+        raise ValueError("pprgo_batch: n_cap and e_cap are at least 1")
+    if out is None:
+        i32 = lambda *shape: torch.empty(shape, dtype=_i32, device=dev)
+        out = (i32(nc), i32(m, K), i32(nc + 1), i32(ec), i32(3))
+    node_idx, loc, tptr, tslot, counts = out
+    for t, name in ((node_idx, "node_idx"), (loc, "loc"), (tptr, "tptr"), (tslot, "tslot"), (counts, "counts")):
+        _chk(t, _i32, name)
+    if node_idx.numel() < nc or loc.numel() < m * K or tptr.numel() < nc + 1 or tslot.numel() < ec or counts.numel() < 3:
+        raise ValueError("pprgo_batch: node_idx holds n_cap values, loc m * K, tptr n_cap + 1, tslot e_cap, counts 3")
+    ws = _ws(lib().grapes_pprgo_batch_workspace_bytes(nc, N), dev)
+    _lib.check(lib().grapes_pprgo_batch(_p(nbr), _p(cnt), m, K, N, _p(bits), _p(node_map), nc, ec, _p(node_idx), _p(loc), _p(tptr),
+                                        _p(tslot), counts.data_ptr(), counts.data_ptr() + 4, counts.data_ptr() + 8, _p(ws), _p(status),
+                                        _stream()), "pprgo_batch")
+    return node_idx, loc, tptr, tslot, counts
+
+
+def pprgo_aggregate_fwd(z, w, loc, cnt, status=None, out=None):
+    """out fp32 [m, f]: out[b] = sum_{t < cnt[b]} w[b, t] z[loc[b, t]] — PPRGo's readout over z fp32 [n, f], w fp32 [m, K], loc int32
+    [m, K].  Slots at or past cnt[b] are never read.  A fixed order of additions, no atomics."""
+    _chk(z, _f32, "z"); _chk(w, _f32, "w"); _chk(loc, _i32, "loc"); _chk(status, _i32, "status", True)
+    m, K = _pprgo_slots("pprgo_aggregate_fwd", w, cnt, "w")
+    if z.dim() != 2 or z.shape[0] < 1 or tuple(loc.shape) != (m, K):
+        raise ValueError("pprgo_aggregate_fwd: z is [n, f] with n >= 1 and loc is [m, K] like w")
+    n, f = int(z.shape[0]), int(z.shape[1])
+    _gather_width(f, "pprgo_aggregate_fwd")
+    if out is None:
+        out = torch.empty((m, f), dtype=_f32, device=z.device)
+    _chk(out, _f32, "out")
+    if tuple(out.shape) != (m, f):
+        raise ValueError("pprgo_aggregate_fwd: out is [m, f]")
+    ws = _ws(lib().grapes_pprgo_aggregate_fwd_workspace_bytes(m, K, f), z.device)
+    _lib.check(lib().grapes_pprgo_aggregate_fwd(_p(z), n, _p(w), _p(loc), _p(cnt), m, K, f, _p(out), _p(ws), _p(status), _stream()),
+               "pprgo_aggregate_fwd")
+    return out
+
+
+def pprgo_item_cap(e: int, seg_max: Optional[int] = None) -> int:
+    """A bound on the chunks behind the first of the segments longer than VRGCN_LONG_ROW among e entries: such a segment of L entries
+    has ceil(L / 64) - 1 <= L / 64 of them.  seg_max: the longest segment where the caller knows it (pprgo_batch's third count) —
+    0 chunks when none is long, and the backward is then one launch."""
+    if seg_max is not None and int(seg_max) <= VRGCN_LONG_ROW:
+        return 0
+    return min(int(e) // VRGCN_LONG_ROW, PPRGO_ITEM_CAP_MAX)
+
+
+def pprgo_aggregate_bwd(g, w, tptr, tslot, n: int, e: int, item_cap: Optional[int] = None, status=None, out=None):
+    """dz fp32 [n, f] of pprgo_aggregate_fwd from g = d out [m, f]: dz[u] = sum of w[s] g[s // K] over the slots s of
+    tslot[tptr[u] : tptr[u + 1]] in ascending s, every row u < n written; n and e = tptr[n] are host values (the batch's one read).
+    item_cap: the room for long segments' chunks, default ops.pprgo_item_cap(e), which cannot overflow.  No float atomics."""
+    _chk(g, _f32, "g"); _chk(w, _f32, "w"); _chk(tptr, _i32, "tptr"); _chk(tslot, _i32, "tslot"); _chk(status, _i32, "status", True)
+    n, e = int(n), int(e)
+    if g.dim() != 2 or w.dim() != 2 or w.shape[0] != g.shape[0] or not 1 <= w.shape[0] <= PPRGO_MAX_ROOTS or \
+            not 2 <= w.shape[1] <= PPRGO_MAX_SLOTS or n < 1 or e < 0 or tptr.numel() < n + 1 or tslot.numel() < e:
+        raise ValueError(f"pprgo_aggregate_bwd: g is [m, f], w [m, K] (m <= {PPRGO_MAX_ROOTS}, 2 <= K <= {PPRGO_MAX_SLOTS}), tptr holds "
+                         "n + 1 values and tslot e")
+    m, K, f = int(w.shape[0]), int(w.shape[1]), int(g.shape[1])
+    _gather_width(f, "pprgo_aggregate_bwd")
+    ic = pprgo_item_cap(e) if item_cap is None else int(item_cap)
+    if not 0 <= ic <= PPRGO_ITEM_CAP_MAX:
+        raise ValueError(f"pprgo_aggregate_bwd: item_cap is 0 .. {PPRGO_ITEM_CAP_MAX}")
+    if out is None:
+        out = torch.empty((n, f), dtype=_f32, device=g.device)
+    _chk(out, _f32, "dz")
+    if tuple(out.shape) != (n, f):
+        raise ValueError("pprgo_aggregate_bwd: dz is [n, f]")
+    ws = _ws(lib().grapes_pprgo_aggregate_bwd_workspace_bytes(n, ic, f), g.device)
+    _lib.check(lib().grapes_pprgo_aggregate_bwd(_p(g), m, _p(w), K, _p(tptr), _p(tslot), n, e, f, _p(out), ic, _p(ws), _p(status),
+                                                _stream()), "pprgo_aggregate_bwd")
+    return out
+
+
 # ------------------------------------------------------------------------------- Cluster-GCN: cluster-union batches, ClusterGCNConv
 # [Chiang et al., KDD 2019; PyG-recall: ClusterData, ClusterLoader, ClusterGCNConv] (grapes_hip.h, csrc/cluster_kernels.hip)
 CLUSTER_MAX_BATCH_PARTS = 1 << 20        # clusters of one batch

@@ -69,7 +69,8 @@ extern "C" {
  * grapes_labor_importance(_workspace_bytes); ShaDow-GNN — grapes_shadow_sample(_workspace_bytes), grapes_shadow_ppr_sample(_workspace_bytes), grapes_segment_mean_fwd / _bwd;
  * Cluster-GCN — grapes_cluster_batch(_workspace_bytes), grapes_cluster_aggregate_fwd / _bwd, grapes_cluster_aggregate_workspace_bytes; its graph partitioner —
  * grapes_partition_propose, grapes_partition_admit, grapes_partition_cut (+ _workspace_bytes each); GNNAutoScale —
- * grapes_gas_resolve(_workspace_bytes), grapes_gas_aggregate_fwd / _bwd, grapes_gas_aggregate_workspace_bytes. */
+ * grapes_gas_resolve(_workspace_bytes), grapes_gas_aggregate_fwd / _bwd, grapes_gas_aggregate_workspace_bytes; PPRGo — grapes_pprgo_topk,
+ * grapes_pprgo_batch(_workspace_bytes), grapes_pprgo_aggregate_fwd / _bwd (+ _workspace_bytes each). */
 #define GRAPES_ABI_VERSION 303
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1760,6 +1761,47 @@ int grapes_shadow_sample(const int64_t* rowptr, const int32_t* col, int32_t num_
  * workspace: grapes_shadow_ppr_sample_workspace_bytes(m, k) bytes (0 for arguments outside the rule), 4-byte aligned. */
 size_t grapes_shadow_ppr_sample_workspace_bytes(int32_t m, int32_t k);
 int grapes_shadow_ppr_sample(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* roots, int32_t m, const int32_t* d_m, int32_t k, uint32_t alpha_q, uint32_t thr, int32_t max_rounds, int32_t n_cap, int32_t e_cap, int32_t* n_id, int32_t* ptr, int32_t* batch, int32_t* root_n_id, int32_t* edge_src, int32_t* edge_dst, int64_t* e_id, uint32_t* score, int32_t* rounds, int32_t* stop, int32_t* d_n, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream);
+/* PPRGo [Bojchevski et al., KDD 2020 — recalled]: logits_b = sum_t w[b][t] MLP(x)[nbr[b][t]] over the root and its k best PPR nodes.
+ * There is no graph between a batch's nodes, so the ego-net half of grapes_shadow_ppr_sample is not run.
+ * grapes_pprgo_topk: the arguments of grapes_shadow_ppr_sample up to max_rounds with the same ranges; the push, the three stops, score
+ * and the member order are THAT rule word for word (T = 4096 included).  Outputs in fixed slots, K = k + 1: nbr int32[m][K], score
+ * uint32[m][K], cnt int32[m], rounds / stop int32[m] (optional).  Slot 0 is the root with its own score; slots 1 .. cnt[b] - 1 the best
+ * nodes, score descending, then id ascending; slots t >= cnt[b] hold nbr = root, score = 0 (a union over all slots may ignore cnt;
+ * nothing else reads them).  A root outside [0, N) raises GRAPES_STATUS_BAD_INDEX and gives cnt = 0, nbr = -1, score = 0, rounds = stop
+ * = 0; a root at or past *d_m the same without the bit.  One launch (a workgroup per root writes the sorted keys' prefix in rank
+ * order), no workspace, no scan, integers only, no global atomic beyond the status OR: two runs give the same bits. */
+int grapes_pprgo_topk(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* roots, int32_t m, const int32_t* d_m, int32_t k, uint32_t alpha_q, uint32_t thr, int32_t max_rounds, int32_t* nbr, uint32_t* score, int32_t* cnt, int32_t* rounds, int32_t* stop, int32_t* status, grapes_stream_t stream);
+/* grapes_pprgo_batch: the batch structure of slot tables nbr / cnt [m][K] (1 <= m <= 4096, 2 <= K <= 1024; a slot t < cnt[b] is live,
+ * cnt is clamped to [0, K], dead slots are not read).
+ *   node_idx int32[n]   the ascending, duplicate-free union of the live slots' ids; *d_n = n
+ *   loc int32[m][K]     the rank of nbr[b][t] in node_idx for a live slot; a dead slot repeats slot 0's value (-1 where cnt[b] = 0)
+ *   tptr int32[n + 1], tslot int32[E]   the by-source inverted index: for local row u the flat slot indices s = b K + t of the live
+ *                       slots with loc = u, ASCENDING; *d_e = E = the live slots; *d_seg_max (optional) = the longest segment, so
+ *                       that a caller who reads it beside n and E can spare the backward its chunked form (item_cap = 0)
+ * More than n_cap nodes raise GRAPES_STATUS_NODE_OVERFLOW, more than e_cap slots GRAPES_STATUS_EDGE_OVERFLOW: the counts (and tptr) are
+ * clamped, nothing is written at or past a capacity, and the structure is then incomplete (a slot of a dropped node has loc = -1).  A
+ * live id outside [0, N) raises GRAPES_STATUS_BAD_INDEX, gets loc = -1 and is in no segment; so does a source listed more than 4096
+ * times, whose segment stays unordered.
+ * The caller's scratch: bits uint64[ceil(N / 64)], ZERO on entry and zero again on return; node_map int32[N], any state on entry (it
+ * holds the ranks of this batch's ids afterwards).  Integers only; two runs give the same bits.
+ * workspace: grapes_pprgo_batch_workspace_bytes(n_cap, num_nodes) bytes, 4-byte aligned. */
+size_t grapes_pprgo_batch_workspace_bytes(int32_t n_cap, int32_t num_nodes);
+int grapes_pprgo_batch(const int32_t* nbr, const int32_t* cnt, int32_t m, int32_t K, int32_t num_nodes, uint64_t* bits, int32_t* node_map, int32_t n_cap, int32_t e_cap, int32_t* node_idx, int32_t* loc, int32_t* tptr, int32_t* tslot, int32_t* d_n, int32_t* d_e, int32_t* d_seg_max, void* workspace, int32_t* status, grapes_stream_t stream);
+/* The weighted gathers of PPRGo's readout, row-major fp32, widths as the row gathers (f % 4 == 0 with 16-byte aligned rows up to 1024,
+ * any f up to 256).
+ *   forward   out[b, :f] = sum_{t < cnt[b]} w[b][t] z[loc[b][t], :f], b < m; w fp32[m][K], z [n, f].  Slots at or past cnt[b] are never
+ *             read, neither w nor loc.
+ *   backward  dz[u, :f] = sum_{s in tslot[tptr[u] .. tptr[u + 1])} w[s] g[s / K, :f] in ascending s, for EVERY u < n (e = tptr[n]);
+ *             w carries no gradient.
+ * A row of more than grapes_vrgcn_long_row() entries (the forward: K above it) is cut into chunks of that many, one group of lanes each,
+ * and the partial sums are added in chunk order.  No float atomics: every sum has a fixed order, two runs give the same bits.  An index
+ * outside its table raises GRAPES_STATUS_BAD_INDEX and the entry is dropped.  item_cap (backward): the chunks behind the first of the
+ * long segments the call has room for, at most 2^22 (0: every segment by one group); more raise GRAPES_STATUS_EDGE_OVERFLOW.
+ * workspace: the _workspace_bytes of the direction (forward: may be NULL while K is no long row), 16-byte aligned. */
+size_t grapes_pprgo_aggregate_fwd_workspace_bytes(int32_t m, int32_t K, int32_t f);
+int grapes_pprgo_aggregate_fwd(const float* z, int32_t n, const float* w, const int32_t* loc, const int32_t* cnt, int32_t m, int32_t K, int32_t f, float* out, void* workspace, int32_t* status, grapes_stream_t stream);
+size_t grapes_pprgo_aggregate_bwd_workspace_bytes(int32_t n, int32_t item_cap, int32_t f);
+int grapes_pprgo_aggregate_bwd(const float* g, int32_t m, const float* w, int32_t K, const int32_t* tptr, const int32_t* tslot, int32_t n, int32_t e, int32_t f, float* dz, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
 /* The mean over contiguous row segments, ShaDow's pooled readout: out[b, :f] = the mean of h[ptr[b] .. ptr[b + 1], :f] for b <
  * num_segments, 0 for an empty segment; h is [n_rows, f] row-major, 1 <= f <= 1024.  A thread owns a column and adds the segment's
  * rows in row order, then divides once: n_b - 1 additions and one division in a fixed order, no atomics.  The backward writes
