@@ -247,8 +247,9 @@ extern "C" int grapes_exchange_serve_rows(const int64_t* rowptr_local, const int
                                           const int32_t* req, int32_t n_peers, int32_t cap, int32_t lo, int32_t hi,
                                           int32_t* reply, int64_t reply_stride, int32_t e_slot, int32_t* eoff,
                                           int32_t* status, grapes_stream_t stream) {
-    if (!rowptr_local || !col_local || !req || !reply || !eoff) return GRAPES_EINVAL;
+    if (!rowptr_local || !req || !reply || !eoff) return GRAPES_EINVAL;
     if (n_peers <= 0 || n_peers > XCH_MAX_PEERS || cap <= 0 || e_slot < 0 || lo < 0 || hi < lo) return GRAPES_EINVAL;
+    if (!col_local && hi > lo) return GRAPES_EINVAL;          // an empty shard owns no id: every length is 0, no column is read
     if (reply_stride < 2LL * cap + e_slot) return GRAPES_EINVAL;
     if ((int64_t)n_peers * cap >= 0x7fffffffLL) return GRAPES_EINVAL;
     hipStream_t s = (hipStream_t)stream;
@@ -271,6 +272,9 @@ extern "C" int grapes_exchange_recv_rows(const int32_t* back, int64_t reply_stri
     if (!back || !nodes || !bounds || !eoff || !rowstart || !src || !dst) return GRAPES_EINVAL;
     if (n_peers <= 0 || n_peers > XCH_MAX_PEERS || cap <= 0 || e_cap < 0) return GRAPES_EINVAL;
     if (reply_stride * n_peers >= 0x7fffffffLL) return GRAPES_EINVAL;
+    // recv_expand_k reads in-slot indices up to e_cap - 1 unguarded (after an owner's overflow the headers promise more columns
+    // than the slot holds): the slot must be at least that long
+    if (reply_stride < 2LL * cap + e_cap) return GRAPES_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(recv_offsets_k, dim3(1), dim3(1024), 0, s, back, (long long)reply_stride, nodes, cap, d_m,
                        bounds, n_peers, eoff, rowstart, d_e);
@@ -287,7 +291,8 @@ extern "C" int grapes_exchange_recv_rows(const int32_t* back, int64_t reply_stri
 extern "C" int grapes_exchange_serve_features(const float* X_local, int32_t F, const int32_t* req, int32_t n_peers,
                                               int32_t cap, int32_t lo, int32_t hi, float* reply, int32_t n_slot,
                                               int32_t* status, grapes_stream_t stream) {
-    if (!X_local || !req || !reply || F <= 0 || cap <= 0 || n_slot <= 0 || lo < 0 || hi < lo) return GRAPES_EINVAL;
+    if (!req || !reply || F <= 0 || cap <= 0 || n_slot <= 0 || lo < 0 || hi < lo) return GRAPES_EINVAL;
+    if (!X_local && hi > lo) return GRAPES_EINVAL;            // an empty shard: every run is empty, no row is read
     if (n_peers <= 0 || n_peers > XCH_MAX_PEERS) return GRAPES_EINVAL;
     const bool vec = (F % 4 == 0) && (((uintptr_t)X_local & 15) == 0) && (((uintptr_t)reply & 15) == 0);
     const int ipr = vec ? F / 4 : F;

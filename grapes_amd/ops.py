@@ -2280,6 +2280,8 @@ def exchange_serve_rows(rowptr_local, col_local, req, n_peers, cap, lo, hi, repl
     if req.numel() != n_peers * (cap + 1) or reply.numel() != n_peers * reply_stride:
         raise ValueError("exchange_serve_rows: req / reply do not match (n_peers, cap, reply_stride)")
     eoff = torch.empty(n_peers * cap + 1, dtype=_i32, device=req.device)
+    if col_local.numel() == 0 and hi > lo:     # a shard of nodes without any edge: every length is 0 and no column is read,
+        col_local = eoff                       # but the call takes no NULL there (an empty tensor has no address)
     _lib.check(lib().grapes_exchange_serve_rows(_p(rowptr_local), _p(col_local), _p(req), n_peers, cap, lo, hi, _p(reply),
                                                 reply_stride, e_slot, _p(eoff), _p(status), _stream()),
                "exchange_serve_rows")

@@ -1118,7 +1118,18 @@ int grapes_adam_step_slabs(const void* d_desc, int32_t n_tensors, int64_t max_nu
  * The owner writes, for each peer p, reply[p] = int32[reply_stride]:
  *   [0,cap) row length of query j (0 if not owned / beyond the count), [cap,2cap) offset of that row inside the
  *   slot's column area, [2cap, 2cap+e_slot) the columns (query order, ascending inside a row).
- * eoff int32[n_peers*cap+1] is scratch.  A slot that would exceed e_slot raises GRAPES_STATUS_EDGE_OVERFLOW. */
+ * eoff int32[n_peers*cap+1] is scratch.  A rank may own nothing (lo == hi): its replies hold zero lengths / empty runs, and
+ * col_local (X_local in grapes_exchange_serve_features) may then be NULL.  Words of a slot outside these three areas, and columns past the slot's total, are
+ * not written; the padding of a query list beyond its count (clamped to [0, cap]) may hold anything.
+ *
+ * Edge overflow.  A slot whose rows hold more than e_slot columns raises GRAPES_STATUS_EDGE_OVERFLOW on the owner: every column
+ * whose index inside the slot is below e_slot is written, nothing at or past it, and the len / off headers stay those of the
+ * FULL rows.  The requester adds the lengths it reads: a total above e_cap raises GRAPES_STATUS_EDGE_OVERFLOW there, *d_e and
+ * eoff are the TRUE (unclamped) totals, and (src, dst)[0 .. e_cap) is the exact prefix of the true edge list — edge t of the
+ * list sits at an in-slot index <= t < e_cap, so with e_cap <= e_slot every column that prefix reads was written.
+ * A requester's e_cap MUST NOT exceed the owners' e_slot: the requester does not know e_slot and reads in-slot indices up to
+ * e_cap - 1 unguarded, which after an owner's overflow lie past the columns written and, for the last peer, past `back`.
+ * grapes_exchange_recv_rows refuses reply_stride < 2 cap + e_cap (GRAPES_EINVAL) — all it can check of that rule. */
 /* This rank's query message: query[0..n) = ids, query[cap] = min(*d_n, n) (n when d_n is NULL); query[n..cap) is padding
  * and is left as it is. */
 int grapes_exchange_pack_query(const int32_t* ids, int32_t n, const int32_t* d_n, int32_t cap, int32_t* query,
@@ -1135,12 +1146,19 @@ int grapes_exchange_recv_rows(const int32_t* back, int64_t reply_stride, const i
                               int32_t* eoff, int32_t* rowstart, int32_t* src, int32_t* dst, int32_t* d_e,
                               int32_t* status, grapes_stream_t stream);
 /* Halo feature rows.  req = all-gathered ASCENDING id lists int32[n_peers][cap+1]; the ids of [lo,hi) form one run of
- * each list; reply[p] = fp32[n_slot][F] holds the rows of peer p's run (GRAPES_STATUS_NODE_OVERFLOW if longer). */
+ * each list; reply[p] = fp32[n_slot][F] holds the rows of peer p's run; slot rows past the run are not written.
+ *
+ * Node overflow.  A run longer than n_slot raises GRAPES_STATUS_NODE_OVERFLOW on the owner, which sends the run's first n_slot
+ * rows.  The requester (grapes_exchange_assemble_features and grapes_exchange_halo_positions alike) clamps a row's position
+ * inside its run to n_slot - 1, so every read stays inside the slot: rows among the first n_slot of their run are exact, every
+ * later row of the run is a copy of the slot's last row (in the in-place form: has that row's position; the several ids that
+ * share it then all write code_pos there and which of their words stays is unspecified).  The status word says so. */
 int grapes_exchange_serve_features(const float* X_local, int32_t F, const int32_t* req, int32_t n_peers,
                                    int32_t cap, int32_t lo, int32_t hi, float* reply, int32_t n_slot,
                                    int32_t* status, grapes_stream_t stream);
 /* Requester: out[i, 0:F] = row of ids[i] taken from back = fp32[n_peers][n_slot][F], out[i, F+j] = indicator j
- * (same packing as grapes_gather_rows); ids ascending, first *d_n live. */
+ * (same packing as grapes_gather_rows); ids ascending, first *d_n live; rows of out past *d_n are not written.  The epoch an
+ * indicator word (bits 8..31) is compared with is *d_epoch & 0xffffff when d_epoch is given, else `epoch`. */
 int grapes_exchange_assemble_features(const float* back, int32_t F, int32_t n_slot, const int32_t* ids,
                                       int32_t n, const int32_t* d_n, const int32_t* bounds,
                                       int32_t n_peers, const uint32_t* ind_code, uint32_t epoch,
@@ -1176,7 +1194,9 @@ int grapes_gcn_aggregate_gather_fwd_peers(const float* const* shard_base, const 
 
 /* Requester, in-place form: pos[i] = row of ids[i] inside back viewed as fp32[n_peers * n_slot][F] (rows past *d_n: 0) and,
  * with ind_code, code_pos[pos[i]] = ind_code[ids[i]] — grapes_gcn_aggregate_gather_fwd(X = back, ids = pos, ind_code =
- * code_pos, head records built with head_ids = pos) then aggregates the exchanged rows where they arrived.  dist.py. */
+ * code_pos, head records built with head_ids = pos) then aggregates the exchanged rows where they arrived.  Words of code_pos
+ * that no live row maps to are not written; ind_code and code_pos come together or not at all (GRAPES_EINVAL); n = 0 writes
+ * nothing.  dist.py. */
 int grapes_exchange_halo_positions(const int32_t* ids, int32_t n, const int32_t* d_n, const int32_t* bounds,
                                    int32_t n_peers, int32_t n_slot, const uint32_t* ind_code, int32_t* pos,
                                    uint32_t* code_pos, grapes_stream_t stream);

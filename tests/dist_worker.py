@@ -30,16 +30,16 @@ class OracleLocalOps:
             ids = req[p, :cap].long()
             owned = (torch.arange(cap) < m) & (ids >= lo) & (ids < hi)
             loc = torch.where(owned, ids - lo, torch.zeros_like(ids))
-            lens = torch.where(owned, rowptr[loc + 1] - rowptr[loc], torch.zeros_like(ids))
+            lens = torch.where(owned, rowptr[loc + 1] - rowptr[loc], torch.zeros_like(ids)) if hi > lo else torch.zeros_like(ids)
             offs = torch.cumsum(lens, 0) - lens
             reply[p, :cap] = lens.to(torch.int32)
             reply[p, cap:2 * cap] = offs.to(torch.int32)
-            if int(lens.sum()) > e_slot:
+            if int(lens.sum()) > e_slot:                   # the columns below e_slot are still written, the headers stay whole
                 status |= 1
-                continue
             nodes = loc[owned].numpy()
             edges = O.get_neighborhoods(nodes, rowptr.numpy(), col.numpy().astype(np.int64))   # utils.py:74-82
-            reply[p, 2 * cap:2 * cap + edges.shape[1]] = torch.from_numpy(edges[1].astype(np.int32))
+            k = min(edges.shape[1], e_slot)
+            reply[p, 2 * cap:2 * cap + k] = torch.from_numpy(edges[1, :k].astype(np.int32))
 
     def recv_rows(self, back, stride, nodes32, bounds32, n_peers, e_cap, d_m, status):
         cap = nodes32.numel()
@@ -53,9 +53,9 @@ class OracleLocalOps:
         eoff[1:m + 1] = torch.cumsum(lens, 0).to(torch.int32)
         e = int(lens.sum())
         src = torch.zeros(e_cap, dtype=torch.int32); dst = torch.zeros(e_cap, dtype=torch.int32)
-        if e > e_cap:
+        if e > e_cap:                                      # the exact prefix of the true list; d_e and eoff stay unclamped
             status |= 1
-            e = 0
+            e = e_cap
         rep = torch.repeat_interleave(i, lens)[:e]
         within = torch.arange(e) - eoff[:m].long()[rep]
         src[:e] = nodes32[rep]
@@ -100,8 +100,15 @@ class OracleLocalOps:
         cuts = torch.searchsorted(ids, bounds32.long())
         owner = torch.bucketize(ids, bounds32[1:-1].long(), right=True)
         r = (torch.arange(n) - cuts[owner]).clamp(max=n_slot - 1)
+        if ids32.numel() == 0:
+            return pos, code_pos
+        if (ind_code is None) != (code_pos is None):
+            raise ValueError("halo_positions: ind_code and code_pos come together")
         pos.zero_()
         pos[:n] = (owner * n_slot + r).to(torch.int32)
+        if code_pos is not None:
+            code_pos[pos[:n].long()] = ind_code[ids]
+        return pos, code_pos
 
     def note_rows(self, loc, ids32, d_n, pos, base, node_map, batch, d_n_batch, idx_a, idx_b):
         n = ids32.numel() if d_n is None else int(d_n.clamp(0, ids32.numel()))

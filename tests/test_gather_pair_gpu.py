@@ -36,13 +36,15 @@ def _edges(rng, n, lens):
 class _Problem:
     """one local graph of N_ROWS rows built with head_ids: rows of 0, 1-4 and 5-16 entries and one hub row of 40 (GRAPES_HUB_ROW = 16)"""
 
-    def __init__(self, seed):
+    def __init__(self, seed, must=()):
+        """must: feature-matrix rows that are to be among the head ids (they take the first local rows)"""
         from grapes_amd import ops
         rng = np.random.default_rng(seed)
         lens = rng.choice([0, 1, 2, 3, 4, 5, 9, 16], N_ROWS, p=[.1, .25, .2, .15, .1, .08, .07, .05])
         lens[:4] = [0, 4, 5, 16]
         lens[int(rng.integers(4, N_ROWS))] = 40
-        self.ids = _t(rng.permutation(N_X)[:N_ROWS], torch.int32)
+        ids = rng.permutation(N_X)
+        self.ids = _t(np.concatenate([np.asarray(must, dtype=ids.dtype), ids[~np.isin(ids, must)]])[:N_ROWS], torch.int32)
         self.code = _t(((EPOCH << 8) | rng.integers(0, 1 << NUM_IND, N_X)).astype(np.int32))
         self.prep = ops.PreparedGraph(*_edges(rng, N_ROWS, lens), N_ROWS, head_ids=self.ids)
         got = (self.prep.rowptr_t[1:] - self.prep.rowptr_t[:-1]).cpu().numpy()
@@ -162,3 +164,25 @@ def test_program_on_its_own(case, table):
     finally:
         L.grapes_rider_free(prog)
     assert torch.equal(out_b, case.solo[32][1])
+
+
+@pytest.mark.parametrize("lanes", [32, 64])
+def test_eight_shards_with_empty_ends(lanes):
+    """GRAPES_MAX_PEER_SHARDS shards, the first and the last of them empty, head ids on the first and the last row of every
+    shard that has rows: the table path picks each row's shard by its bounds and equals the local gather bit for bit"""
+    _cuda()
+    from grapes_amd import ops
+    from grapes_amd.peer import MAX_SHARDS, PeerFeatures
+    cuts = [0, 0, 1, 400, 401, 1100, 1500, N_X, N_X]           # (shards of one row among them)
+    assert len(cuts) == MAX_SHARDS + 1
+    edge_rows = sorted({r for a, z in zip(cuts, cuts[1:]) if a < z for r in (a, z - 1)})
+    prob = _Problem(13, must=edge_rows)
+    assert set(edge_rows) <= set(prob.ids.cpu().tolist())
+    F = WIDTHS[lanes]
+    X = _t(np.random.default_rng(6).standard_normal((N_X, F)).astype(np.float32))
+    pf = PeerFeatures.from_shards([X[a:z].clone() for a, z in zip(cuts, cuts[1:])], rank=1)
+    assert pf.P == MAX_SHARDS and pf.bounds == cuts
+    want = prob.gather(ops.pad_features(X)[0], F, None)
+    got = torch.full_like(want, float("nan"))
+    prob.gather(pf, F, got)
+    assert torch.equal(got, want)
