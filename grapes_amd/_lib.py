@@ -127,6 +127,10 @@ SIGNATURES = {
     "grapes_pprgo_aggregate_fwd": (I32, [P, I32, P, P, P, I32, I32, I32, P, P, P, P]),
     "grapes_pprgo_aggregate_bwd_workspace_bytes": (SZ, [I32, I32, I32]),
     "grapes_pprgo_aggregate_bwd": (I32, [P, I32, P, I32, P, P, I32, I32, I32, P, I32, P, P, P]),
+    # PinSAGE: the random-walk importance neighbourhoods and the layer's relu + L2 normalisation
+    "grapes_pinsage_neighbors": (I32, [P, P, I32, P, I32, P, I32, I32, U32, I32, U64, U64, P, P, P, P, P, P]),
+    "grapes_relu_l2norm_fwd": (I32, [P, I64, I32, I32, F32, P, I64, P, P]),
+    "grapes_relu_l2norm_bwd": (I32, [P, I64, P, I64, P, P, I64, I32, I32, F32, P, I64, P]),
     "grapes_segment_mean_fwd": (I32, [P, P, I32, I32, I32, P, P, P]),
     "grapes_segment_mean_bwd": (I32, [P, P, I32, I32, I32, P, P, P]),
     # Cluster-GCN: the cluster-union batch and ClusterGCNConv's propagation

@@ -3513,6 +3513,111 @@ def pprgo_aggregate_bwd(g, w, tptr, tslot, n: int, e: int, item_cap: Optional[in
     return out
 
 
+# ------------------------------------------------------------------------------- PinSAGE: random-walk importance neighbourhoods
+# [Ying et al., KDD 2018 — recalled; DGL-recall: RandomWalkNeighborSampler / PinSAGESampler] (grapes_hip.h, csrc/pinsage_kernels.hip)
+PINSAGE_MAX_VISITS = 1024                    # V = R L, the visit slots of one root
+PINSAGE_MAX_NEIGHBORS = PPRGO_MAX_SLOTS - 1  # T: K = T + 1 slots fit pprgo_batch
+
+
+def pinsage_term_q(p: float) -> int:
+    """The termination probability 0 <= p < 1 in units of 2^-32: min(2^32 - 1, round(p 2^32))."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"pinsage_neighbors: the termination probability {p} is outside [0, 1)")
+    return min(2 ** 32 - 1, int(round(p * 2 ** 32)))
+
+
+def pinsage_args(R: int, L: int, T: int) -> int:
+    """K = T + 1, the slots of a root.  ValueError unless 1 <= R, 1 <= L, R L <= PINSAGE_MAX_VISITS and 1 <= T <=
+    PINSAGE_MAX_NEIGHBORS."""
+    R, L, T = int(R), int(L), int(T)
+    if R < 1 or L < 1 or R * L > PINSAGE_MAX_VISITS:
+        raise ValueError(f"pinsage_neighbors: {R} walks of {L} steps are not built (each at least 1, and R L <= {PINSAGE_MAX_VISITS}: "
+                         "a root's visits sit in one workgroup's LDS)")
+    if not 1 <= T <= PINSAGE_MAX_NEIGHBORS:
+        raise ValueError(f"pinsage_neighbors: T = {T} neighbours are not built (1 .. {PINSAGE_MAX_NEIGHBORS})")
+    return T + 1
+
+
+def pinsage_neighbors(rowptr, col, num_nodes: int, roots, R: int, L: int, term_q: int, T: int, philox_seed: int = 0,
+                      philox_offset: int = 0, d_philox_offset=None, d_m=None, status=None, out=None):
+    """(nbr int32 [m, K], visits int32 [m, K], cnt int32 [m]) of grapes_pinsage_neighbors, K = T + 1: per root the T nodes that R
+    restarting walks of at most L steps visit most often (term_q: ops.pinsage_term_q(p)), with their visit counts, in pprgo_topk's
+    slot convention — slot 0 the root, then count descending, id ascending; slots at or past cnt[b] hold (root, 0).  visits is at
+    most 1024, so int32 holds the library's uint32.  d_philox_offset: int64 [1] device stream offset, used instead of philox_offset
+    and advanced by ceil(L / 2).  One launch (two with the device offset), no workspace.  out: the three tensors to write."""
+    _chk(d_philox_offset, _i64, "d_philox_offset", True)
+    K = pinsage_args(R, L, T)
+    N, m = _list_rows("pinsage_neighbors", rowptr, col, num_nodes, roots, d_m, status, int(num_nodes) < 1)
+    if col.numel() >= 2 ** 31 or m * K >= 2 ** 31:
+        raise ValueError("pinsage_neighbors: a graph, or slot tables, with 2^31 or more entries are not built")
+    if not 0 <= int(term_q) <= 2 ** 32 - 1:
+        raise ValueError("pinsage_neighbors: term_q is a uint32 (ops.pinsage_term_q)")
+    dev = roots.device
+    if out is None:
+        out = (torch.empty((m, K), dtype=_i32, device=dev), torch.empty((m, K), dtype=_i32, device=dev),
+               torch.empty(m, dtype=_i32, device=dev))
+    nbr, visits, cnt = out
+    for t, name in ((nbr, "nbr"), (visits, "visits"), (cnt, "cnt")):
+        _chk(t, _i32, name)
+    if nbr.numel() < m * K or visits.numel() < m * K or cnt.numel() < m:
+        raise ValueError("pinsage_neighbors: nbr and visits hold m * (T + 1) values, cnt m")
+    if col.numel() == 0:
+        col = _ws(16, dev)                                           # (a graph without an entry: any address, never read)
+    _lib.check(lib().grapes_pinsage_neighbors(_p(rowptr), _p(col), N, _p(roots), m, _p(d_m), int(R), int(L), int(term_q), int(T),
+                                              int(philox_seed) & (2 ** 64 - 1), int(philox_offset) & (2 ** 64 - 1),
+                                              _p(d_philox_offset), _p(nbr), _p(visits), _p(cnt), _p(status), _stream()),
+               "pinsage_neighbors")
+    return nbr, visits, cnt
+
+
+def _row_matrix(t, name, m=None, f=None):
+    """A float32 device matrix with unit column stride (a column block of a wider one is fine) -> its row stride."""
+    if t is None or not t.is_cuda:
+        raise _lib.GrapesHipError(f"{name} must live in HBM (cuda tensor); grapes_amd has no CPU path")
+    if t.dtype != _f32 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1 or (t.shape[1] > 1 and t.stride(1) != 1) or \
+            (m is not None and tuple(t.shape) != (m, f)):
+        raise ValueError(f"{name}: a float32 matrix [m, f] with unit column stride" + ("" if m is None else f", here [{m}, {f}]"))
+    return int(t.stride(0)) if t.shape[0] > 1 else max(int(t.stride(0)), int(t.shape[1]))
+
+
+def relu_l2norm_fwd(s, eps: float = 1e-12, out=None):
+    """(out fp32 [m, f], nrm fp32 [m]) of grapes_relu_l2norm_fwd: z = max(s, 0), nrm[b] = |z[b]|_2, out = z / max(nrm, eps) — PinSAGE's
+    layer epilogue in one launch; f as the row gathers take it."""
+    ld_s = _row_matrix(s, "s")
+    m, f = int(s.shape[0]), int(s.shape[1])
+    _gather_width(f, "relu_l2norm_fwd")
+    if not float(eps) > 0.0:
+        raise ValueError("relu_l2norm_fwd: eps is positive")
+    if out is None:
+        out = (torch.empty((m, f), dtype=_f32, device=s.device), torch.empty(m, dtype=_f32, device=s.device))
+    o, nrm = out
+    ld_o = _row_matrix(o, "out", m, f)
+    _chk(nrm, _f32, "nrm")
+    if nrm.numel() < m:
+        raise ValueError("relu_l2norm_fwd: nrm holds m values")
+    _lib.check(lib().grapes_relu_l2norm_fwd(_p(s), ld_s, m, f, float(eps), _p(o), ld_o, _p(nrm), _stream()), "relu_l2norm_fwd")
+    return o, nrm
+
+
+def relu_l2norm_bwd(g, out, nrm, s, eps: float = 1e-12, ds=None):
+    """ds fp32 [m, f] of relu_l2norm_fwd from g = d out: ds = [s > 0] (g - out <g, out> [nrm >= eps]) / max(nrm, eps); out and nrm as
+    the forward returned them."""
+    ld_g = _row_matrix(g, "g")
+    m, f = int(g.shape[0]), int(g.shape[1])
+    _gather_width(f, "relu_l2norm_bwd")
+    ld_o, ld_s = _row_matrix(out, "out", m, f), _row_matrix(s, "s", m, f)
+    _chk(nrm, _f32, "nrm")
+    if nrm.numel() < m or not float(eps) > 0.0:
+        raise ValueError("relu_l2norm_bwd: nrm holds m values and eps is positive")
+    if ds is None:
+        ds = torch.empty((m, f), dtype=_f32, device=g.device)
+    ld_d = _row_matrix(ds, "ds", m, f)
+    _lib.check(lib().grapes_relu_l2norm_bwd(_p(g), ld_g, _p(out), ld_o, _p(nrm), _p(s), ld_s, m, f, float(eps), _p(ds), ld_d, _stream()),
+               "relu_l2norm_bwd")
+    return ds
+
+
 # ------------------------------------------------------------------------------- Cluster-GCN: cluster-union batches, ClusterGCNConv
 # [Chiang et al., KDD 2019; PyG-recall: ClusterData, ClusterLoader, ClusterGCNConv] (grapes_hip.h, csrc/cluster_kernels.hip)
 CLUSTER_MAX_BATCH_PARTS = 1 << 20        # clusters of one batch

@@ -70,7 +70,8 @@ extern "C" {
  * Cluster-GCN — grapes_cluster_batch(_workspace_bytes), grapes_cluster_aggregate_fwd / _bwd, grapes_cluster_aggregate_workspace_bytes; its graph partitioner —
  * grapes_partition_propose, grapes_partition_admit, grapes_partition_cut (+ _workspace_bytes each); GNNAutoScale —
  * grapes_gas_resolve(_workspace_bytes), grapes_gas_aggregate_fwd / _bwd, grapes_gas_aggregate_workspace_bytes; PPRGo — grapes_pprgo_topk,
- * grapes_pprgo_batch(_workspace_bytes), grapes_pprgo_aggregate_fwd / _bwd (+ _workspace_bytes each). */
+ * grapes_pprgo_batch(_workspace_bytes), grapes_pprgo_aggregate_fwd / _bwd (+ _workspace_bytes each); PinSAGE — grapes_pinsage_neighbors,
+ * grapes_relu_l2norm_fwd / _bwd. */
 #define GRAPES_ABI_VERSION 303
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1822,6 +1823,41 @@ size_t grapes_pprgo_aggregate_fwd_workspace_bytes(int32_t m, int32_t K, int32_t 
 int grapes_pprgo_aggregate_fwd(const float* z, int32_t n, const float* w, const int32_t* loc, const int32_t* cnt, int32_t m, int32_t K, int32_t f, float* out, void* workspace, int32_t* status, grapes_stream_t stream);
 size_t grapes_pprgo_aggregate_bwd_workspace_bytes(int32_t n, int32_t item_cap, int32_t f);
 int grapes_pprgo_aggregate_bwd(const float* g, int32_t m, const float* w, int32_t K, const int32_t* tptr, const int32_t* tslot, int32_t n, int32_t e, int32_t f, float* dz, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
+/* PinSAGE [Ying et al., KDD 2018 — recalled; DGL-recall: RandomWalkNeighborSampler / PinSAGESampler]: a root's neighbourhood is the T
+ * nodes that R restarting walks of at most L steps from it visit most often; the visit counts are the aggregation weights.
+ * grapes_pinsage_neighbors — the rule, integers only (a CPU reproduces every output bit):
+ *   Ranges (else GRAPES_EINVAL): 1 <= R, 1 <= L, V = R L <= 1024; 1 <= T <= 1023, K = T + 1 (the tables fit grapes_pprgo_batch);
+ *   m >= 1 and m K < 2^31; the graph holds fewer than 2^31 entries; term_q is any uint32 — the termination probability in units of
+ *   2^-32, min(2^32 - 1, round(p 2^32)) for 0 <= p < 1.
+ *   Stream offset: off = *d_philox_offset when that pointer is non-NULL, else philox_offset.  A non-NULL *d_philox_offset advances by
+ *   ceil(L / 2) per call, in a ONE-THREAD TAIL launch behind the kernel (every workgroup has read the offset by then); without the
+ *   pointer the call is one launch.
+ *   One step: walk j < R of a root with global id v, step t < L, from the current node c (c = v at t = 0):
+ *     P = philox4x32_10 over the 128-bit counter (low 64 bits = uint64(v) | uint64(j) << 32, high 64 bits = off + (t >> 1)) under the
+ *     key philox_seed; a = P.v[2 (t & 1)], s = P.v[2 (t & 1) + 1].  The walk ENDS before the move if a < term_q or deg(c) = 0 (deg =
+ *     rowptr[c + 1] - rowptr[c]); otherwise c <- col[rowptr[c] + ((uint64(s) deg(c)) >> 32)].  The new c is one VISIT unless c = v:
+ *     returns to the root are not counted, the root has its own term in the layer (DGL keeps them: a stated deviation).  A col entry
+ *     outside [0, N) ends the walk uncounted and raises GRAPES_STATUS_BAD_INDEX.
+ *   A draw depends on (v, j, t, off, seed) alone — not on the root's position, on m, or on how the kernel tiles the roots: a repeated
+ *   root gets identical rows.
+ *   Selection: count[u] = the visits to u over the root's R walks; kept are the min(T, distinct) nodes with the smallest key
+ *   ((V - count[u]) << 32) | u: count descending, then id ascending.
+ *   Outputs, in grapes_pprgo_topk's slot convention (grapes_pprgo_batch runs on them unchanged): nbr int32[m][K], visits uint32[m][K],
+ *   cnt int32[m].  Slot 0 is (root, 0); slots 1 .. cnt[b] - 1 the kept nodes in key order with their counts; slots t >= cnt[b] hold
+ *   (root, 0).  A root outside [0, N) raises GRAPES_STATUS_BAD_INDEX and gets cnt = 0, nbr = -1, visits = 0; a root at or past *d_m
+ *   (optional, clamped to m) the same without the bit.
+ * No float, no global atomic beyond the status OR, no workspace: two runs give the same bits. */
+int grapes_pinsage_neighbors(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* roots, int32_t m, const int32_t* d_m, int32_t R, int32_t L, uint32_t term_q, int32_t T, uint64_t philox_seed, uint64_t philox_offset, uint64_t* d_philox_offset, int32_t* nbr, uint32_t* visits, int32_t* cnt, int32_t* status, grapes_stream_t stream);
+/* PinSAGE's layer epilogue over the rows of s [m, f] (rows ld_s floats apart; every ld >= f), eps > 0:
+ *   forward   z = max(s, 0) (a NaN reads as 0); nrm[b] = sqrtf(sum_c z[b, c]^2); out[b, c] = z[b, c] / max(nrm[b], eps)
+ *   backward  ds[b, c] = [s[b, c] > 0] (g[b, c] - out[b, c] <g[b], out[b]> [nrm[b] >= eps]) / max(nrm[b], eps), with out and nrm as
+ *             the forward wrote them
+ * Widths as the row gathers: f % 4 == 0 up to 1024 where every matrix is 16-byte aligned with ld % 4 == 0, any f up to 256 otherwise
+ * (GRAPES_EALIGN where alignment alone stands in the way).  A group of lanes owns a row; the sums are an fma chain over a lane's
+ * columns and a butterfly over the group — a fixed order, no atomics, two runs give the same bits; IEEE sqrtf and division.  Columns
+ * at or past f of a row are neither read nor written.  One launch each, no workspace. */
+int grapes_relu_l2norm_fwd(const float* s, int64_t ld_s, int32_t m, int32_t f, float eps, float* out, int64_t ld_out, float* nrm, grapes_stream_t stream);
+int grapes_relu_l2norm_bwd(const float* g, int64_t ld_g, const float* out, int64_t ld_out, const float* nrm, const float* s, int64_t ld_s, int32_t m, int32_t f, float eps, float* ds, int64_t ld_ds, grapes_stream_t stream);
 /* The mean over contiguous row segments, ShaDow's pooled readout: out[b, :f] = the mean of h[ptr[b] .. ptr[b + 1], :f] for b <
  * num_segments, 0 for an empty segment; h is [n_rows, f] row-major, 1 <= f <= 1024.  A thread owns a column and adds the segment's
  * rows in row order, then divides once: n_b - 1 additions and one division in a fixed order, no atomics.  The backward writes
