@@ -21,7 +21,9 @@ The data generators below are shared by tests/test_accuracy_criterion_cpu.py (a 
 faithful and with defects, which shows the criterion rejects a lost plane) and tests/test_split_dw_accuracy_gpu.py /
 tests/test_tsplit_accuracy_gpu.py (the kernels themselves), so the two cannot drift apart.  The emulations of the tiled
 gathered-operand GEMMs (emulate_tsplit_fwd / emulate_tsplit_dw) live here too: the GPU tests check an output that exceeds
-the factors against them.  Only tests import this module.
+the factors against them.  The plain fp32 dense GEMMs have their own section at the end (dense_problem, DENSE_CASES, the
+sequential-chain baseline and the emulations of their summation orders), shared by tests/test_dense_gemm_accuracy_cpu.py and
+tests/test_dense_gemm_accuracy_gpu.py.  Only tests import this module.
 """
 from __future__ import annotations
 
@@ -1335,3 +1337,453 @@ def gatv2_backward_reference(w: Gatv2Weights, rowptr_s, csr_dst, dout, out, agg_
         db = (db[0], db[1], t(np.add.accumulate(np.tile(part, (H, 1)), axis=0, dtype=f32)[-1].copy()))
     res["dbias"] = (db[0], db[1], db[2], float(n + H + 2) * db[1])
     return res
+
+
+# --------------------------------------------------------------------------------------------- plain fp32 dense GEMMs
+# grapes_amd/csrc/gemm_kernels.hip: grapes_linear_fwd / _fwd_row_scaled / _bias_act_fwd / _bwd_input / _bwd_weight and the
+# few-row slab path (grapes_linear_bwd_weight_slabs[_and_input] + grapes_slab_reduce_sets).  Same criterion as above: each
+# output relative to the fp64 sum of |a||b| of ITS OWN terms, the ratio test against a fixed-order fp32 baseline, and beside it
+# the hard cap |got - ref| <= (L + extra) 2^-24 mag (hard_cap_excess with a scalar L: the contraction length).
+#   baseline of the forward forms and the input gradient: ONE sequential fp32 chain in k order (product rounded, then added) —
+#     the order of the tiled kernel's single accumulator.  fp32_contract's 128-blocks are 4-6x more accurate than that chain at
+#     K = 1433, so under them a correct tiled kernel would miss RMS_FACTOR;
+#   baseline of the weight gradient (the contraction runs over the rows): fp32_contract, as for every dW test here.
+GB_TILE, GB_K = 128, 16                 # gemm_mfma_f32_k: tile edge, K step
+SK_KMAX, SK_MAX_ROWS = 256, 4096        # gemm_skinny_f32_k takes host row counts <= 4096 and 1 <= K <= 256
+DWS_ROWS = 128                          # rows per slab of gemm_dw_small_k
+DW_BLOCKS_TARGET = 512                  # dw_nslab: slabs x output tiles
+
+
+def skinny_ok(rows: int, K: int) -> bool:
+    return rows <= SK_MAX_ROWS and 1 <= K <= SK_KMAX
+
+
+def dw_nslab(f_out: int, f_in: int) -> int:
+    return max(1, DW_BLOCKS_TARGET // (-(-f_out // GB_TILE) * -(-f_in // GB_TILE)))
+
+
+def dw_small_ok(rows: int, f_out: int, f_in: int) -> bool:
+    return rows <= SK_MAX_ROWS and -(-rows // DWS_ROWS) <= dw_nslab(f_out, f_in)
+
+
+def auto_kchunk(K: int, nslab: int) -> int:
+    kc = -(-K // nslab)
+    kc = (kc + 1) & ~1
+    return max(kc, 16)
+
+
+def wsplit_ok(K: int, N: int) -> bool:
+    """Shapes of the bf16x3 forward (aligned operands taken for granted): grapes_linear_bias_act_fwd takes it at >= 2048 rows."""
+    return K % 4 == 0 and 4 <= K <= 192 and N % 32 == 0 and 32 <= N <= 256
+
+
+def dense_route(entry: str, rows: int, f_in: int, f_out: int) -> str:
+    """The kernel an entry point hands a HOST row count `rows` (the capacity: dispatch never sees the device-side count) to."""
+    if entry in ("fwd", "fwd_row_scaled", "bias_act"):
+        if entry == "fwd" and f_out == 1:
+            return "gemv"
+        if entry == "bias_act" and rows >= 2048 and wsplit_ok(f_in, f_out):
+            return "wsplit"
+        return "skinny" if skinny_ok(rows, f_in) else "tiled"
+    if entry == "bwd_input":
+        if f_out == 1:
+            return "outer"
+        return "skinny" if skinny_ok(rows, f_out) else "tiled"
+    if entry == "bwd_weight":
+        if f_out == 1:
+            return "colsum"
+        return "dw_small" if dw_small_ok(rows, f_out, f_in) else "split_k"
+    raise ValueError(entry)
+
+
+def dense_vec(entry: str, f_in: int, f_out: int, aligned: bool = True) -> bool:
+    """launch_gemm's `vec` for the tiled kernels of an entry point: both leading dimensions % 4 == 0 and 16-byte bases."""
+    lda, ldb = {"bwd_input": (f_out, f_in), "bwd_weight": (f_out, f_in)}.get(entry, (f_in, f_in))
+    return aligned and lda % 4 == 0 and ldb % 4 == 0
+
+
+class DenseCase:
+    """One shape of the dense accuracy tests: (rows live on the device, f_in, f_out), `pad` capacity rows past them (the host
+    count is rows + pad), the kernel the host count must reach, the kinds it runs on and an operand to misalign."""
+
+    def __init__(self, entry, kernel, rows, f_in, f_out, pad=3, kinds=KINDS, unaligned=None, vec=None, note=""):
+        self.entry, self.kernel, self.rows, self.f_in, self.f_out = entry, kernel, rows, f_in, f_out
+        self.pad, self.kinds, self.unaligned, self.vec, self.note = pad, tuple(kinds), unaligned, vec, note
+
+    @property
+    def cap(self) -> int:
+        return self.rows + self.pad
+
+    @property
+    def id(self) -> str:
+        s = f"{self.kernel}-{self.rows}x{self.f_in}x{self.f_out}"
+        if self.pad != 3:
+            s += f"+{self.pad}"
+        return s + (f"-off_{self.unaligned}" if self.unaligned else "")
+
+    def check_route(self):
+        """The shape is on the intended side of every dispatch boundary."""
+        got = dense_route(self.entry, self.cap, self.f_in, self.f_out)
+        assert got == self.kernel, f"{self.id}: host count {self.cap} reaches {got}, not {self.kernel}"
+        if self.vec is not None:
+            assert dense_vec(self.entry, self.f_in, self.f_out, self.unaligned is None) == self.vec, self.id
+        if self.kernel == "tiled" and self.note.startswith("mt"):
+            mt = -(-self.cap // GB_TILE)
+            assert (mt >= 8) == (self.note == "mt>=8"), f"{self.id}: mt = {mt}"
+
+
+def _dc(entry, kernel, shapes, **kw):
+    return [DenseCase(entry, kernel, *s, **kw) for s in shapes]
+
+
+DENSE_CASES: Dict[str, list] = {
+    # ---- grapes_linear_fwd
+    "fwd": (
+        # gemv_rows_k: the float4 loop's trip count (260: a second trip), the scalar loop, the grid cap's stride loop
+        _dc("fwd", "gemv", [(1029, 1, 1), (1029, 3, 1), (1029, 8, 1), (1029, 103, 1), (1029, 256, 1), (1029, 260, 1),
+                            (1, 103, 1), (4, 103, 1), (5, 103, 1)])
+        + _dc("fwd", "gemv", [(1029, 256, 1)], unaligned="x")
+        + _dc("fwd", "gemv", [(32773, 8, 1)])
+        # gemm_skinny_f32_k<false>: K around the quarter split, rows around a 32-row tile, f_out around a 64-column tile
+        + _dc("fwd", "skinny", [(33, 1, 2), (31, 3, 63), (32, 4, 64), (33, 5, 65), (1, 13, 130), (33, 13, 7), (31, 47, 65),
+                                (130, 47, 2), (33, 255, 63), (32, 256, 64), (1, 256, 65), (259, 255, 130)])
+        + _dc("fwd", "skinny", [(4096, 256, 64), (4096, 47, 65)], pad=0)
+        + _dc("fwd", "skinny", [(33, 48, 65)], unaligned="x") + _dc("fwd", "skinny", [(33, 48, 66)], unaligned="w")
+        # gemm_mfma_f32_k<false, false>
+        + _dc("fwd", "tiled", [(130, 260, 130)], vec=True, note="mt<8")           # 17 K-steps, mt = 2
+        + _dc("fwd", "tiled", [(129, 1433, 7)], vec=False, note="mt<8")            # scalar loads, 90 K-steps
+        + _dc("fwd", "tiled", [(1030, 272, 136)], vec=True, note="mt>=8")          # mt = 9: the XCD-aware map, idle padded blocks
+        + _dc("fwd", "tiled", [(4100, 16, 130), (4100, 20, 64), (4100, 48, 40)], vec=True, note="mt>=8")  # 1, 2, 3 K-steps
+        + _dc("fwd", "tiled", [(100, 20, 64)], pad=4100, vec=True, note="mt>=8")   # capacity 4200, 100 live: most blocks return
+    ),
+    # ---- grapes_linear_fwd_row_scaled
+    "fwd_row_scaled": (
+        _dc("fwd_row_scaled", "skinny", [(33, 47, 65)]) + _dc("fwd_row_scaled", "skinny", [(4096, 256, 64)], pad=0)
+        + _dc("fwd_row_scaled", "tiled", [(4100, 20, 64)], vec=True) + _dc("fwd_row_scaled", "tiled", [(130, 260, 130)], vec=True)
+    ),
+    # ---- grapes_linear_bias_act_fwd (each with bias on/off x ReLU on/off)
+    "bias_act": (
+        _dc("bias_act", "skinny", [(33, 47, 65)]) + _dc("bias_act", "skinny", [(2047, 104, 256)], pad=0)
+        + _dc("bias_act", "tiled", [(4100, 20, 72)], vec=True) + _dc("bias_act", "tiled", [(130, 260, 130)], vec=True)
+    ),
+    # ---- grapes_linear_bwd_input
+    "bwd_input": (
+        _dc("bwd_input", "outer", [(5, 7, 1)]) + _dc("bwd_input", "outer", [(8200, 257, 1)])
+        # gemm_skinny_f32_k<true>: K = f_out; f_in % 4 decides the k-major B tile's vector / scalar loads
+        + _dc("bwd_input", "skinny", [(33, 3, 2), (31, 64, 5), (33, 65, 47), (130, 130, 256), (1, 64, 47), (259, 64, 256),
+                                      (32, 3, 256), (33, 130, 5)])
+        + _dc("bwd_input", "tiled", [(4100, 130, 20)], vec=False)
+        + _dc("bwd_input", "tiled", [(130, 100, 260)], vec=True) + _dc("bwd_input", "tiled", [(129, 103, 262)], vec=False)
+    ),
+    # ---- grapes_linear_bwd_weight (each fresh and accumulated)
+    "bwd_weight": (
+        _dc("bwd_weight", "colsum", [(1, 103, 1), (129, 1, 1), (129, 256, 1), (9000, 103, 1), (9000, 256, 1), (1, 1, 1)])
+        # gemm_dw_small_k + slab_reduce_k: 1 .. 32 slabs, ragged last slab, tiles around 32 x 64
+        + _dc("bwd_weight", "dw_small", [(1, 13, 7), (127, 63, 31), (128, 64, 32), (129, 65, 33), (1022, 256, 256), (1022, 64, 32),
+                                         (129, 256, 256), (127, 13, 7), (128, 65, 33)])
+        + _dc("bwd_weight", "dw_small", [(4096, 13, 7), (4096, 256, 256)], pad=0)
+        # gemm_mfma_f32_k<true, true> in split-K form + slab_reduce_k
+        + _dc("bwd_weight", "split_k", [(4100, 20, 8)], vec=True)        # chunk floor 16: 257 live slabs of 512
+        + _dc("bwd_weight", "split_k", [(8200, 20, 8)], vec=True)        # chunk 18: a second K-step of 2 rows
+        + _dc("bwd_weight", "split_k", [(4097, 260, 130)], vec=False)    # 6 tiles -> 85 slabs
+        + _dc("bwd_weight", "split_k", [(4100, 103, 7)], vec=False)      # scalar loads
+        + _dc("bwd_weight", "split_k", [(100, 20, 8)], pad=4100, vec=True)         # capacity 4200, 100 live
+    ),
+}
+# the deferred slab path: layers (f_in, f_out, form) over one row count; form: plain dW, gated dW + dbias, dW + dx (pair launch)
+SLAB_ROWS = (129, 1022)
+SLAB_LAYERS = ((65, 33, "dw"), (64, 32, "gated"), (13, 7, "pair"))
+SLAB_MANY = (129, 13, 7, 9)     # (rows, f_in, f_out, layers): more than 8 sets force DeferredSlabs' internal flush
+
+
+def dense_problem(n: int, K: int, N: int, kind: str, seed: int, n_pad: int = 0) -> Dict[str, np.ndarray]:
+    """The operands of every dense entry point over n live rows (capacity n + n_pad), fp32:
+      forward           x [cap, K], w [N, K], bias [N], row_scale [cap] (signs mixed, magnitudes 10^[-6, 6]);
+      input gradient    dh_in [cap, N], w_in [N, K]                       (dx = dh_in w_in, contraction over N);
+      weight gradient   dh [cap, N], x_dw [cap, K], gate [cap, N] (an input: kept where > 0), prior_dw [N, K], prior_db [N].
+    kind:
+      normal  N(0,1); the three roles share x = x_dw, w = w_in, dh = dh_in.
+      mixed   the contraction index carries the magnitude, products stay within 10^[-3, 3]:
+              forward: column k of x at 10^a_k and column k of w at 10^(-a_k + c_k); input gradient: column j of dh_in at 10^a_j,
+              row j of w_in at 10^(-a_j + c_j); weight gradient: row r of x_dw at 10^a_r, row r of dh at 10^(-a_r + c_r);
+              a in [-20, 20], c in [-3, 3], each role its own draw (one array cannot carry two roles' scales: 10^40 overflows).
+      zeros   N(0,1) with exact zeros: whole rows of x / dh (n >= 3), a column of x and of dh (K, N >= 3), single entries, one
+              row and one column of w (N, K >= 3), entries of row_scale and gate.  Outputs whose terms all vanish must be 0.
+    Rows past n are NaN in x, x_dw, dh, dh_in, row_scale and gate."""
+    if kind not in KINDS:
+        raise ValueError(kind)
+    rng = np.random.default_rng(seed)
+    cap = n + n_pad
+    g = lambda *s: rng.standard_normal(s)
+    x, w, dh = g(cap, K), g(N, K) / np.sqrt(K), g(cap, N)
+    x_dw, w_in, dh_in = x, w, dh
+    if kind == "mixed":
+        a = rng.uniform(-20, 20, K)
+        x = x * 10.0 ** a
+        w = w * 10.0 ** (-a + rng.uniform(-3, 3, K))
+        a = rng.uniform(-20, 20, N)
+        dh_in = g(cap, N) * 10.0 ** a
+        w_in = (g(N, K) / np.sqrt(K)) * (10.0 ** (-a + rng.uniform(-3, 3, N)))[:, None]
+        a = rng.uniform(-20, 20, cap)
+        x_dw = g(cap, K) * (10.0 ** a)[:, None]
+        dh = dh * (10.0 ** (-a + rng.uniform(-3, 3, cap)))[:, None]
+    row_scale = rng.choice([-1.0, 1.0], cap) * 10.0 ** rng.uniform(-6, 6, cap)
+    gate = g(cap, N)
+    if kind == "zeros":
+        if n >= 3:
+            x[rng.integers(0, n, max(1, n // 50))] = 0.0
+            dh[rng.integers(0, n, max(1, n // 50))] = 0.0
+            row_scale[rng.integers(0, n, max(1, n // 50))] = 0.0
+        x[rng.integers(0, n, n), rng.integers(0, K, n)] = 0.0
+        dh[rng.integers(0, n, n), rng.integers(0, N, n)] = 0.0
+        gate[rng.integers(0, n, n), rng.integers(0, N, n)] = 0.0
+        if K >= 3:
+            x[:, K // 2] = 0.0
+            w[:, K - 1] = 0.0
+        if N >= 3:
+            dh[:, N // 2] = 0.0
+            w[N - 1] = 0.0
+    for v in (x, x_dw, dh, dh_in, gate):
+        v[n:] = np.nan
+    row_scale[n:] = np.nan
+    f = lambda v: np.ascontiguousarray(v, dtype=np.float32)
+    return {"x": f(x), "w": f(w), "bias": f(g(N) * 0.5), "row_scale": f(row_scale), "dh_in": f(dh_in), "w_in": f(w_in),
+            "dh": f(dh), "x_dw": f(x_dw), "gate": f(gate), "prior_dw": f(g(N, K)), "prior_db": f(g(N)), "n": n, "cap": cap}
+
+
+def _seq_chain(a: torch.Tensor, bt: torch.Tensor, k0: int, k1: int, fma: bool = False) -> torch.Tensor:
+    """sum_{k0 <= k < k1} a[:, k] (x) bt[:, k] as ONE fp32 chain in k order, element-wise ops only.  fma: each step one fused
+    multiply-add (the product exact in fp64, one rounding per step; the double rounding moves tie cases only)."""
+    acc = torch.zeros(a.shape[0], bt.shape[0])
+    if fma:
+        a, bt = a.double(), bt.double()
+        for k in range(k0, k1):
+            acc = (acc.double() + a[:, k, None] * bt[None, :, k]).float()
+        return acc
+    for k in range(k0, k1):
+        acc += a[:, k, None] * bt[None, :, k]
+    return acc
+
+
+def dense_epilogue(out: torch.Tensor, bias=None, relu=False, row_scale=None, bias_twice=False, scale_shift=False):
+    """+ bias, ReLU, x row_scale in the kernels' order, in out's precision (fp32 emulation / baseline, or fp64 reference)."""
+    if bias is not None:
+        b = torch.as_tensor(np.asarray(bias, dtype=np.float32)).to(out.dtype)
+        out = out + b
+        if bias_twice:
+            out = out + b
+    if relu:
+        out = out.clamp(min=0)
+    if row_scale is not None:
+        s = torch.as_tensor(np.asarray(row_scale, dtype=np.float32)).to(out.dtype)
+        out = out * (torch.roll(s, 1) if scale_shift else s)[:, None]
+    return out
+
+
+def dense_fwd_reference(a, bt, bias=None, relu=False, row_scale=None):
+    """out = rowscale ⊙ act(a btᵀ + bias) for a [n, K], bt [N, K] (the forward forms; the input gradient with a = dh,
+    bt = wᵀ) -> (ref, mag, base): mag = |a||bt|ᵀ + |bias|, times |row_scale| (the pre-activation's: ReLU is 1-Lipschitz);
+    base = the sequential fp32 chain in k order, then the same epilogue in fp32."""
+    a64, b64 = _t64(a), _t64(bt)
+    ref = dense_epilogue(a64 @ b64.T, bias, relu, row_scale)
+    mag = dense_epilogue(a64.abs() @ b64.abs().T, None if bias is None else np.abs(bias), False,
+                         None if row_scale is None else np.abs(row_scale))
+    base = dense_epilogue(_seq_chain(_f32(a), _f32(bt), 0, a64.shape[1]), bias, relu, row_scale)
+    return ref, mag, base
+
+
+def dense_dw_reference(dh, x, gate=None, prior_dw=None, prior_db=None):
+    """dW = (dh ⊙ [gate > 0])ᵀ x and db = its column sums over the rows given (+ priors) -> {"dw" | "db": (ref, mag, base)};
+    base = fp32_contract (+ prior in fp32, the buffer first: o + t)."""
+    d32 = np.asarray(dh, dtype=np.float32)
+    if gate is not None:
+        d32 = np.where(np.asarray(gate) > 0, d32, np.float32(0))
+    d64, x64 = _t64(d32), _t64(x)
+    ones = np.ones((d32.shape[0], 1), np.float32)
+    out = {"dw": [d64.T @ x64, d64.abs().T @ x64.abs(), fp32_contract(d32, x)],
+           "db": [d64.sum(0), d64.abs().sum(0), fp32_contract(d32, ones).view(-1)]}
+    for k, p in (("dw", prior_dw), ("db", prior_db)):
+        if p is not None:
+            p64, p32 = _t64(p), _f32(p)
+            out[k] = [out[k][0] + p64, out[k][1] + p64.abs(), p32 + out[k][2]]
+    return {k: tuple(v) for k, v in out.items()}
+
+
+def dense_accuracy(got, ref, mag, base, L: int, extra: int = 4) -> Tuple[Accuracy, float]:
+    """(the ratio criterion's numbers, worst |got - ref| / ((L + extra) 2^-24 mag)) of one output tensor: the two pass conditions
+    of the dense GEMMs (dense_ok).  L is the contraction length (K, or the live row count of a weight gradient): the gamma_L bound
+    of an L-term fp32 dot product in any order, with room for bias, row scale, accumulation and the store."""
+    return Accuracy(got, ref, mag, base), hard_cap_excess(got, ref, mag, float(L), extra)
+
+
+def dense_ok(a: Accuracy, cap: float) -> bool:
+    return a.ok() and cap <= 1.0
+
+
+def normwise_ok(got, ref, tol: float = 2e-5) -> bool:
+    """The bound of test_hip_parity.py's dense tests: max|got - ref| <= tol max(1, max|ref|)."""
+    got, ref = torch.as_tensor(got).double(), torch.as_tensor(ref).double()
+    return bool((got - ref).abs().max() <= tol * max(1.0, float(ref.abs().max())))
+
+
+# ---- the kernels' summation orders, plain torch fp32.  defect= seeds one fault (tests/test_dense_gemm_accuracy_cpu.py)
+def emulate_tiled(a, bt, bias=None, relu=False, row_scale=None, defect=None, fma=False) -> torch.Tensor:
+    """gemm_mfma_f32_k: one accumulator per output, K streamed in order -> one chain over k; bias, ReLU, row scale after it.
+    defect: "drop_partial_kstep" (the K % 16 terms of the last, partial K-step lost), "bias_twice", "scale_shift"."""
+    a, bt = _f32(a), _f32(bt)
+    K = a.shape[1]
+    k1 = K - K % GB_K if defect == "drop_partial_kstep" else K
+    return dense_epilogue(_seq_chain(a, bt, 0, k1, fma), bias, relu, row_scale, defect == "bias_twice", defect == "scale_shift")
+
+
+def emulate_gemv(a, w, vec: bool) -> torch.Tensor:
+    """gemv_rows_k: a wavefront per row; lane l chains fused multiply-adds over its elements (vec: the float4s at 4 l + 256 t,
+    else the floats at l + 64 t), then the xor butterfly 32, 16, .. 1, of which lane 0's value is stored.  -> [n, 1]"""
+    a, w = _f32(a), _f32(w).view(-1)
+    n, F = a.shape
+    step = 256 if vec else 64
+    Fp = -(-F // step) * step
+    p = torch.nn.functional.pad(a.double() * w.double(), (0, Fp - F))         # exact products
+    p = p.view(n, Fp // step, 64, 4) if vec else p.view(n, Fp // step, 64, 1)
+    acc = torch.zeros(n, 64)
+    for t in range(p.shape[1]):
+        for j in range(p.shape[3]):
+            acc = (acc.double() + p[:, t, :, j]).float()
+    lanes = torch.arange(64)
+    for d in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[:, lanes ^ d]
+    return acc[:, :1].clone()
+
+
+def skinny_quarters(K: int):
+    """[(k0, k1)] x 4: the k ranges of gemm_skinny_body's four wavefront groups (quads of 4 k, ceil(KQ / 4) quads each)."""
+    KQ = -(-K // 4)
+    per = -(-KQ // 4)
+    return [(min(4 * q * per, K), min(4 * min((q + 1) * per, KQ), K)) for q in range(4)]
+
+
+def _skinny_sum(a, bt, defect=None, fma=False) -> torch.Tensor:
+    qs = skinny_quarters(a.shape[1])
+    if defect == "drop_quad":           # the last quad of the last non-empty quarter never reaches the accumulator
+        j = max(i for i, (k0, k1) in enumerate(qs) if k1 > k0)
+        k0, k1 = qs[j]
+        qs[j] = (k0, max(k0, k1 - ((k1 - k0 - 1) % 4 + 1)))
+    p = [_seq_chain(a, bt, k0, k1, fma) for k0, k1 in qs]
+    return ((p[0] + p[1]) + p[2]) + p[3]
+
+
+def emulate_skinny(a, bt, bias=None, relu=False, row_scale=None, defect=None, fma=False) -> torch.Tensor:
+    """gemm_skinny_f32_k: four k ranges (skinny_quarters), each one chain, combined ((q0 + q1) + q2) + q3, then bias and ReLU;
+    the row scale is scale_rows_few_k's pass over the stored product.  defect: "drop_quad", "bias_twice", "scale_shift"."""
+    out = _skinny_sum(_f32(a), _f32(bt), defect, fma)
+    return dense_epilogue(out, bias, relu, row_scale, defect == "bias_twice", defect == "scale_shift")
+
+
+def emulate_slab_reduce(slabs: torch.Tensor, prior=None, defect=None) -> torch.Tensor:
+    """slab_reduce_k / slab_reduce_sets_k over slabs [ns, ...]: four contiguous quarters of ceil(ns / 4) slabs, each added in slab
+    order from 0, combined (p0 + p1) + (p2 + p3), then prior + t.  defect: "drop_last_slab" (the last slab of the first
+    quarter), "slab_twice" (slab 0 added again), "overwrite" (the prior lost)."""
+    ns = slabs.shape[0]
+    per = -(-ns // 4)
+    p = []
+    for g in range(4):
+        z0, z1 = min(g * per, ns), min(g * per + per, ns)
+        if defect == "drop_last_slab" and g == 0:
+            z1 -= 1
+        acc = torch.zeros(slabs.shape[1:])
+        for z in range(z0, z1):
+            acc = acc + slabs[z]
+        if defect == "slab_twice" and g == 0:
+            acc = acc + slabs[0]
+        p.append(acc)
+    t = (p[0] + p[1]) + (p[2] + p[3])
+    if prior is None or defect == "overwrite":
+        return t
+    return _f32(prior) + t
+
+
+def _live(dh, x, gate, n, defect):
+    """The live rows' operands (the gate applied); "read_capacity": the first capacity row taken as live."""
+    m = n + 1 if defect == "read_capacity" else n
+    d = _f32(np.asarray(dh)[:m])
+    if gate is not None:
+        d = torch.where(_f32(np.asarray(gate)[:m]) > 0, d, torch.zeros(()))
+    return d, _f32(np.asarray(x)[:m]), m
+
+
+def emulate_dw_small(dh, x, n: int, gate=None, prior=None, defect=None, fma=False, want="dw") -> torch.Tensor:
+    """gemm_dw_small_k + the slab reduction: 128-row slabs, each summed over its rows in the skinny order (four quarters of 32
+    rows; rows past the live count are zeros), the slabs then by emulate_slab_reduce.  want = "db": the column sums that ride
+    along (an MFMA against ones: the same order).  dh, x: the capacity arrays (their first n rows are read)."""
+    d, xs, m = _live(dh, x, gate, n, defect)
+    if want == "db":
+        xs = torch.ones(m, 1)
+    ns = -(-m // DWS_ROWS)
+    pad = ns * DWS_ROWS - m
+    A = torch.nn.functional.pad(d, (0, 0, 0, pad)).view(ns, DWS_ROWS, -1)
+    B = torch.nn.functional.pad(xs, (0, 0, 0, pad)).view(ns, DWS_ROWS, -1)
+    q = []
+    for k0 in range(0, DWS_ROWS, DWS_ROWS // 4):
+        acc = torch.zeros(ns, A.shape[2], B.shape[2])
+        for k in range(k0, k0 + DWS_ROWS // 4):
+            t = A[:, k, :, None].double() * B[:, k, None, :].double() if fma else A[:, k, :, None] * B[:, k, None, :]
+            acc = (acc.double() + t).float() if fma else acc + t
+        q.append(acc)
+    slabs = ((q[0] + q[1]) + q[2]) + q[3]
+    out = emulate_slab_reduce(slabs, prior, defect)
+    return out.view(-1) if want == "db" else out
+
+
+def emulate_split_k(dh, x, n: int, prior=None, defect=None, fma=False) -> torch.Tensor:
+    """grapes_linear_bwd_weight's tiled split-K form: nslab = max(1, 512 // tiles) slabs requested, the chunk from the live
+    count (auto_kchunk), every live slab one chain over its rows, then the slab reduction.  defect "drop_partial_kstep": each
+    chunk loses the rows of its last, partial 16-row step."""
+    d, xs, m = _live(dh, x, None, n, defect)
+    N, K = d.shape[1], xs.shape[1]
+    kc = auto_kchunk(m, dw_nslab(N, K))
+    ns = -(-m // kc)
+    pad = ns * kc - m
+    A = torch.nn.functional.pad(d, (0, 0, 0, pad)).view(ns, kc, N)
+    B = torch.nn.functional.pad(xs, (0, 0, 0, pad)).view(ns, kc, K)
+    steps = kc - kc % GB_K if defect == "drop_partial_kstep" else kc
+    acc = torch.zeros(ns, N, K)
+    for k in range(steps):
+        t = A[:, k, :, None].double() * B[:, k, None, :].double() if fma else A[:, k, :, None] * B[:, k, None, :]
+        acc = (acc.double() + t).float() if fma else acc + t
+    return emulate_slab_reduce(acc, prior, defect)
+
+
+def dense_case_refs(case: DenseCase, p, bias=False, relu=False, accumulate=False):
+    """{output: (ref, mag, base, L, extra)} of one DenseCase on dense_problem p: L the contraction length of the hard cap."""
+    n, e = p["n"], case.entry
+    if e in ("fwd", "fwd_row_scaled", "bias_act"):
+        scaled = e == "fwd_row_scaled"
+        r = dense_fwd_reference(p["x"][:n], p["w"], p["bias"] if bias else None, relu, p["row_scale"][:n] if scaled else None)
+        return {"out": r + (case.f_in, 5 if scaled else 4)}
+    if e == "bwd_input":
+        return {"dx": dense_fwd_reference(p["dh_in"][:n], np.ascontiguousarray(p["w_in"].T)) + (case.f_out, 4)}
+    r = dense_dw_reference(p["dh"][:n], p["x_dw"][:n], None, p["prior_dw"] if accumulate else None)
+    return {"dw": r["dw"] + (n, 4)}
+
+
+def dense_case_emulation(case: DenseCase, p, bias=False, relu=False, accumulate=False, defect=None, fma=False):
+    """{output: fp32 tensor} in the summation order of the kernel the case reaches, or None where this module has none (the
+    weighted column sum behind f_out == 1: tests/test_spmm_accuracy_cpu.py emulates the column sums' blocking)."""
+    n, e, k = p["n"], case.entry, case.kernel
+    if e in ("fwd", "fwd_row_scaled", "bias_act"):
+        a, bt = p["x"][:n], p["w"]
+        if k == "gemv":
+            return {"out": emulate_gemv(a, bt, case.f_in % 4 == 0 and case.unaligned is None)}
+        f = emulate_skinny if k == "skinny" else emulate_tiled
+        return {"out": f(a, bt, p["bias"] if bias else None, relu, p["row_scale"][:n] if e == "fwd_row_scaled" else None, defect, fma)}
+    if e == "bwd_input":
+        a, bt = p["dh_in"][:n], np.ascontiguousarray(p["w_in"].T)
+        if k == "outer":
+            return {"dx": _f32(a) * _f32(bt).view(1, -1)}
+        return {"dx": (emulate_skinny if k == "skinny" else emulate_tiled)(a, bt, defect=defect, fma=fma)}
+    if k == "colsum":
+        return None
+    prior = p["prior_dw"] if accumulate else None
+    if k == "dw_small":
+        return {"dw": emulate_dw_small(p["dh"], p["x_dw"], n, None, prior, defect, fma)}
+    return {"dw": emulate_split_k(p["dh"], p["x_dw"], n, prior, defect, fma)}
