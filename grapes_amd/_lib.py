@@ -16,7 +16,7 @@ DIAG_LIB_PATH = os.path.join(_HERE, "libgrapes_hip_diag.so")
 # switches on (diag_switch below).  GRAPES_LIB_PATH overrides the path (other diagnostic builds: stamps, lb768).
 DIAG = os.environ.get("GRAPES_DIAG", "0") == "1"
 LIB_PATH = os.environ.get("GRAPES_LIB_PATH") or (DIAG_LIB_PATH if DIAG else os.path.join(_HERE, "libgrapes_hip.so"))
-ABI_MAJOR, ABI_MINOR = 3, 3          # include/grapes_hip.h: GRAPES_ABI_VERSION = 100 * MAJOR + MINOR
+ABI_MAJOR, ABI_MINOR = 3, 4          # include/grapes_hip.h: GRAPES_ABI_VERSION = 100 * MAJOR + MINOR
 
 
 def diag_switch(name: str, default: str) -> str:
@@ -92,12 +92,13 @@ SIGNATURES = {
     "grapes_asgcn_rows_workspace_bytes": (SZ, [I32, I32]),
     "grapes_asgcn_variance": (I32, [P, P, P, I32, P, I32, P, I32, I32, P, P, P, P, P, P]),
     "grapes_asgcn_logq_bwd": (I32, [P, P, P, P, I32, P, I32, I32, P, P, P, P]),
-    # GraphSAGE: node-wise neighbour sampler, SAGEConv aggregation
+    # GraphSAGE: node-wise neighbour sampler; the aggregation SAGEConv and ClusterGCNConv share
     "grapes_sage_sample_layer_workspace_bytes": (SZ, [I32]),
     "grapes_sage_sample_layer": (I32, [P, P, I32, P, I32, P, I32, P, I64, U64, U64, P, I32, P, P, P, P, P, P, P]),
-    "grapes_sage_aggregate_workspace_bytes": (SZ, [I32, I32, I32]),
-    "grapes_sage_aggregate_fwd": (I32, [P, I64, P, I64, P, P, P, P, I32, I32, P, I64, P, I64, I32, P, I32, P, P, I32, P, P, P]),
-    "grapes_sage_aggregate_bwd": (I32, [P, I64, P, I64, P, P, P, P, I32, P, I64, P, I64, P, I64, P, I32, P, I32, P, P, I32, P, P, P]),
+    "grapes_rootsum_aggregate_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_rootsum_aggregate_fwd": (I32, [P, I64, P, I64, P, P, P, P, F32, I32, I32, I32, P, I64, P, I64, I32, P, I32, P, P, I32, P, P, P]),
+    "grapes_rootsum_aggregate_bwd": (I32, [P, I64, P, I64, P, P, P, P, F32, I32, I32, P, I64, P, I64, P, I64, P, I32, P, I32, P, P, I32, P, P,
+                                           P]),
     # VR-GCN: the control-variate aggregation over historical activations
     "grapes_vrgcn_long_row": (I32, []),
     "grapes_vrgcn_aggregate_workspace_bytes": (SZ, [I32, I32, I32]),
@@ -133,12 +134,9 @@ SIGNATURES = {
     "grapes_relu_l2norm_bwd": (I32, [P, I64, P, I64, P, P, I64, I32, I32, F32, P, I64, P]),
     "grapes_segment_mean_fwd": (I32, [P, P, I32, I32, I32, P, P, P]),
     "grapes_segment_mean_bwd": (I32, [P, P, I32, I32, I32, P, P, P]),
-    # Cluster-GCN: the cluster-union batch and ClusterGCNConv's propagation
+    # Cluster-GCN: the cluster-union batch
     "grapes_cluster_batch_workspace_bytes": (SZ, [I32, I32]),
     "grapes_cluster_batch": (I32, [P, P, I32, P, P, P, I32, P, I32, P, I32, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P]),
-    "grapes_cluster_aggregate_workspace_bytes": (SZ, [I32, I32, I32]),
-    "grapes_cluster_aggregate_fwd": (I32, [P, I64, P, I64, P, P, P, F32, I32, P, I64, P, I64, I32, P, I32, P, P, I32, P, P, P]),
-    "grapes_cluster_aggregate_bwd": (I32, [P, I64, P, I64, P, P, P, F32, P, I64, P, I64, P, I64, P, I32, P, I32, P, P, I32, P, P, P]),
     # Cluster-GCN's graph partitioner: size-constrained synchronous label propagation
     "grapes_partition_propose_workspace_bytes": (SZ, [I32, I32]),
     "grapes_partition_propose": (I32, [P, P, I32, P, I32, P, P, P, P, P]),

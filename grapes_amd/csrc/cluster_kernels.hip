@@ -20,13 +20,7 @@
 //                    rowptr_l: off[item_off[i]] for a live row, e for every slot from n to n_cap
 // Integer code only, no global atomic beyond the status OR and the stamps, bit-identical runs, six launches, no host read.
 //
-// ---- the aggregation (grapes_cluster_aggregate_fwd / _bwd), PyG's ClusterGCNConv propagation on the shared plain-sum gather
-// (row_sum.h) over the loop-free CSRs grapes_gcn_prepare builds (duplicates by multiplicity):
-//   out[i] = act(s_i (sum_{j in row i} src[j] + self_weight src[i]) + add[i] + bias),  s_i = 1 / (1 + deg_i),  self_weight = 1 + lambda
-// The backward is the row-local gate pass of row_gate.h (gs = s g) and the SAME gather over the by-source CSR with s = 1.  No float
-// atomics: every sum has a fixed order.  No kernel waits on another workgroup.
-#include "row_sum.h"
-#include "row_gate.h"
+// ClusterGCNConv's propagation is grapes_rootsum_aggregate_fwd / _bwd (rootsum_kernels.hip).
 #include "row_list.h"
 
 #define CLUSTER_CHUNK GRAPES_LONG_ROW
@@ -259,124 +253,4 @@ extern "C" int grapes_cluster_batch(const int64_t* rowptr, const int32_t* col, i
                        e_cap, rowptr_l, edge_src, edge_dst, edge_id);
     GRAPES_LAUNCH_CHECK();
     return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------ the aggregation
-
-// s of a row: 1 / (1 + its entries) — the added self-loop makes every degree positive
-__device__ __forceinline__ float cluster_scale(int deg) { return 1.0f / (float)(1 + deg); }
-
-// The epilogue of the shared row sum (row_sum.h), p = the row's sum (the CSRs are loop-free: loops stays NULL):
-//   out[row] = act(s (p + self_weight src[row]) + add[row] + bias),  s = 1 / (1 + deg) when scaled else 1;  copy[row] = src[row] (every
-//   row, long or not).  add, bias and copy are optional.
-struct ClusterEpi {
-    const float* src; long long ld_src;
-    const int32_t* loops;
-    const float* add; long long ld_add;
-    const float* bias;
-    float* out; long long ld_out;
-    float* copy; long long ld_copy;
-    float self_weight;
-    int scaled, relu;
-
-    template <int VEC, int LPR, int NS>
-    __device__ __forceinline__ void pre(int row, int F, int l) const {
-        if (!copy) return;
-        float xr[NS][VEC];
-        row_load_ld<VEC, LPR, NS>(src, row, ld_src, F, l, xr);
-        row_store_ld<VEC, LPR, NS>(copy, row, ld_copy, F, l, xr);
-    }
-    template <int VEC, int LPR, int NS>
-    __device__ __forceinline__ void finish(float (&acc)[NS][VEC], int row, int deg, int F, int l) const {
-        const float sc = scaled ? cluster_scale(deg) : 1.f;
-        float xr[NS][VEC], ad[NS][VEC];
-        row_load_ld<VEC, LPR, NS>(src, row, ld_src, F, l, xr);
-        if (add) row_load_ld<VEC, LPR, NS>(add, row, ld_add, F, l, ad);
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) {
-                float o = fmaf(self_weight, xr[s][v], acc[s][v]) * sc;
-                if (add) o += ad[s][v];
-                const int f = (s * LPR + l) * VEC + v;
-                if (bias && f < F) o += bias[f];
-                acc[s][v] = relu ? fmaxf(o, 0.f) : o;
-            }
-        row_store_ld<VEC, LPR, NS>(out, row, ld_out, F, l, acc);
-    }
-    __device__ __forceinline__ void finish_col(float a, int row, int deg, int, int f) const {
-        float o = fmaf(self_weight, src[(long long)row * ld_src + f], a) * (scaled ? cluster_scale(deg) : 1.f);
-        if (add) o += add[(long long)row * ld_add + f];
-        if (bias) o += bias[f];
-        out[(long long)row * ld_out + f] = relu ? fmaxf(o, 0.f) : o;
-    }
-};
-
-// s of a row for the backward's gate pass (row_gate.h)
-struct ClusterScale {
-    const int32_t* rowptr_t;
-    __device__ __forceinline__ float operator()(int row) const { return cluster_scale(rowptr_t[row + 1] - rowptr_t[row]); }
-};
-
-static inline bool cluster_vec_ok(const void* p, int64_t ld) { return !p || (grapes_aligned16(p) && ld % 4 == 0); }
-
-// workspace: [pacc item_cap f] [gs n f] [part slabs f]
-extern "C" size_t grapes_cluster_aggregate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f) {
-    const size_t N = n > 0 ? (size_t)n : 0, I = item_cap > 0 ? (size_t)item_cap : 0, F = f > 0 ? (size_t)f : 1;
-    return grapes_round16(I * F * sizeof(float)) + grapes_round16(N * F * sizeof(float)) +
-           grapes_round16(row_gate_slabs(n) * F * sizeof(float)) + 16;
-}
-
-extern "C" int grapes_cluster_aggregate_fwd(const float* src, int64_t ld_src, const float* add, int64_t ld_add, const float* bias,
-                                            const int32_t* rowptr_t, const int32_t* csr_src, float diag_lambda, int32_t relu, float* out,
-                                            int64_t ld_out, float* copy_out, int64_t ld_copy, int32_t n, const int32_t* d_n, int32_t f,
-                                            const int32_t* long_items, const int32_t* d_n_items, int32_t item_cap, void* workspace,
-                                            int32_t* status, grapes_stream_t stream) {
-    if (!src || !rowptr_t || !csr_src || !out || n < 0 || f < 1) return GRAPES_EINVAL;
-    if (ld_src < f || ld_out < f || (add && ld_add < f) || (copy_out && ld_copy < f)) return GRAPES_EINVAL;
-    if (out == src || copy_out == src || (copy_out && copy_out == out)) return GRAPES_EINVAL;
-    const bool use_items = long_items && d_n_items && workspace && item_cap > 0;
-    if (use_items && !grapes_aligned16(workspace)) return GRAPES_EALIGN;
-    const int shape = gather_shape(f, cluster_vec_ok(src, ld_src) && cluster_vec_ok(add, ld_add) && cluster_vec_ok(out, ld_out) &&
-                                    cluster_vec_ok(copy_out, ld_copy) && (!bias || grapes_aligned16(bias)));
-    if (shape < 0) return shape;
-    if (n == 0) return 0;
-    ClusterEpi epi;
-    epi.src = src; epi.ld_src = ld_src; epi.loops = nullptr; epi.add = add; epi.ld_add = ld_add; epi.bias = bias;
-    epi.out = out; epi.ld_out = ld_out; epi.copy = copy_out; epi.ld_copy = ld_copy; epi.self_weight = 1.0f + diag_lambda;
-    epi.scaled = 1; epi.relu = relu ? 1 : 0;
-    return row_sum_propagate<4>(epi, rowptr_t, csr_src, n, d_n, f, shape == 0, use_items ? long_items : nullptr, d_n_items, item_cap,
-                                (float*)workspace, status, (hipStream_t)stream);
-}
-
-extern "C" int grapes_cluster_aggregate_bwd(const float* dout, int64_t ld_dout, const float* relu_out, int64_t ld_relu,
-                                            const int32_t* rowptr_t, const int32_t* rowptr_s, const int32_t* csr_dst, float diag_lambda,
-                                            const float* add, int64_t ld_add, float* dsrc, int64_t ld_dsrc, float* dadd, int64_t ld_dadd,
-                                            float* dbias, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_s,
-                                            const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status,
-                                            grapes_stream_t stream) {
-    if (!dout || !rowptr_t || n < 0 || f < 1 || ld_dout < f || !workspace) return GRAPES_EINVAL;
-    if (dsrc && (!rowptr_s || !csr_dst || ld_dsrc < f || dsrc == dout || dsrc == dadd)) return GRAPES_EINVAL;
-    if ((relu_out && ld_relu < f) || (add && ld_add < f) || (dadd && (ld_dadd < f || dadd == dout))) return GRAPES_EINVAL;
-    if (!grapes_aligned16(workspace)) return GRAPES_EALIGN;
-    const bool use_items = dsrc && items_s && d_n_items_s && item_cap > 0;
-    const int shape = gather_shape(f, cluster_vec_ok(add, ld_add) && cluster_vec_ok(dsrc, ld_dsrc));
-    if (shape < 0) return shape;
-    if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t I = item_cap > 0 ? (size_t)item_cap : 0;
-    float* pacc = (float*)workspace;
-    float* gs = (float*)((char*)workspace + grapes_round16(I * f * sizeof(float)));
-    float* part = (float*)((char*)gs + grapes_round16((size_t)n * f * sizeof(float)));
-    const ClusterScale scale{rowptr_t};
-    const int rc = row_gate_launch(dout, (long long)ld_dout, relu_out, (long long)ld_relu, scale, dsrc ? gs : (float*)nullptr, dadd,
-                                   (long long)ld_dadd, part, dbias, n, d_n, f, s);
-    if (rc) return rc;
-    if (!dsrc) return 0;
-    ClusterEpi epi;
-    epi.src = gs; epi.ld_src = f; epi.loops = nullptr; epi.add = add; epi.ld_add = ld_add; epi.bias = nullptr;
-    epi.out = dsrc; epi.ld_out = ld_dsrc; epi.copy = nullptr; epi.ld_copy = 0; epi.self_weight = 1.0f + diag_lambda;
-    epi.scaled = 0; epi.relu = 0;
-    return row_sum_propagate<4>(epi, rowptr_s, csr_dst, n, d_n, f, shape == 0, use_items ? items_s : nullptr, d_n_items_s, item_cap, pacc,
-                                status, s);
 }

@@ -1,7 +1,7 @@
-// The row-local pass that opens the backward of a plain-sum aggregation (sage_kernels.hip, cluster_kernels.hip):
+// The row-local pass that opens the backward of a plain-sum aggregation (rootsum_kernels.hip):
 //   g = dout gated by relu_out > 0;  dadd = g;  gs = s_row g (rows F floats apart);  dbias = the column sums of g.
-// The layers differ in s_row alone: SCALE is a small functor, scale(row) -> float (SageScale, ClusterScale: each in its layer's
-// file).  No float atomics: the column sums are per-slab partials (ROW_GATE_SLAB rows each) added in a fixed order.
+// SCALE is a small functor, scale(row) -> float (RootSumScale: none, mean or mean-plus-one).  No float atomics: the column
+// sums are per-slab partials (ROW_GATE_SLAB rows each) added in a fixed order.
 #pragma once
 #include "common.h"
 

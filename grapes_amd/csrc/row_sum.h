@@ -1,13 +1,13 @@
-// The plain-sum gather GCN2Conv, SAGEConv and ClusterGCNConv share (gcn2_kernels.hip, sage_kernels.hip, cluster_kernels.hip), on the
-// row-gather scaffold:
+// The plain-sum gather GCN2Conv and the aggregation of SAGEConv and ClusterGCNConv share (gcn2_kernels.hip, rootsum_kernels.hip), on
+// the row-gather scaffold:
 //
 //   p[row] = sum_{t in row} src[csr[t]] + loops[row] src[row]          then a row-local epilogue, the one thing the layers differ in
 //
-// An epilogue type EPI (G2Epi, SageEpi, ClusterEpi: each in its layer's file) carries
+// An epilogue type EPI (G2Epi, RootSumEpi: each in its file) carries
 //   src, ld_src, loops                          the gathered matrix, rows ld_src floats apart, and the optional stored-loop counts
-//                                               (ld_src: 32 bits in G2Epi, where it is the width; 64 in SageEpi and ClusterEpi, a caller's
-//                                               stride; ClusterEpi's CSRs are loop-free and its loops stays NULL)
-//   pre<VEC, LPR, NS>(row, F, l)                the row-local step of EVERY row, long or not (GCN2's aux, SAGE's copy)
+//                                               (ld_src: 32 bits in G2Epi, where it is the width; 64 in RootSumEpi, a caller's stride;
+//                                               ClusterGCNConv's CSRs are loop-free and its loops stays NULL)
+//   pre<VEC, LPR, NS>(row, F, l)                the row-local step of EVERY row, long or not (GCN2's aux, RootSumEpi's copy)
 //   finish<VEC, LPR, NS>(p, row, deg, F, l)     a lane's slabs of p -> the outputs; deg = the row's entries + loops[row]
 //   finish_col(p, row, deg, F, f)               the same arithmetic for column f alone (row_sum_combine_k)
 // The kernels deduce EPI from their first argument, so ROW_LAUNCH dispatches them by width like any other kernel.  Every sum has

@@ -1,6 +1,5 @@
 // GraphSAGE [Hamilton et al., NeurIPS 2017; PyG-recall: torch_geometric 2.5.2 SAGEConv, NeighborLoader]: the node-wise uniform
-// neighbour sampler over the DeviceGraph CSR, and SAGEConv's mean / sum aggregation, forward and backward, over the CSRs
-// grapes_gcn_prepare builds.
+// neighbour sampler over the DeviceGraph CSR.
 //
 // ---- the sampler (grapes_sage_sample_layer): for every list row r keep min(deg, fanout) of the entries of CSR row rows[r],
 // uniformly without replacement.  The rule, bit-reproducible on a CPU (tests/sage_oracle.py):
@@ -23,19 +22,7 @@
 //                  word < T and the first positions with word == T.  Two to five generations of the keys: linear in deg, no sort,
 //                  nothing through global memory.  Integer arithmetic only.
 //
-// ---- the aggregation (grapes_sage_aggregate_fwd / _bwd), the plain-sum gather shared with GCN2Conv (row_sum.h):
-//   out[i] = act(s_i (sum_{j in row i} src[j] + loops[i] src[i]) + add[i] + bias),  s_i = 1 / deg_i (mean) or 1 (sum),
-//   deg_i = (rowptr[i + 1] - rowptr[i]) + loops[i]: the scale is applied ONCE per row, there is no per-edge weight; an empty row
-//   aggregates to 0.  src, add, out (and copy: copy[i] = src[i], the root operand of the aggregate-first form) have their own
-//   leading dimensions, so halves of one GEMM output are used in place.
-//   row_sum_rows_k / row_sum_chunks_k / row_sum_combine_k   the shared kernels; SageEpi below is their epilogue
-//   row_gate_k / row_colsum_k      backward (row_gate.h): g = dout gated by relu_out > 0, dadd = g, gs = s g, and the column sums of g as
-//                                  per-slab partials added in a fixed order
-// The backward propagation is the SAME gather over the by-source CSR on the pre-scaled rows gs.  No float atomics: every sum has a
-// fixed order (entry order inside a row, chunk order across work items, slab order for the bias), two runs are bit-identical.
-// No kernel waits on another workgroup.
-#include "row_sum.h"
-#include "row_gate.h"
+// SAGEConv's aggregation is grapes_rootsum_aggregate_fwd / _bwd (rootsum_kernels.hip).
 #include "philox.h"
 #include "row_list.h"
 
@@ -305,132 +292,4 @@ extern "C" int grapes_sage_sample_layer(const int64_t* rowptr, const int32_t* co
                        (const int32_t*)off_e, e_cap, edge_src, edge_dst, edge_pos, status);
     GRAPES_LAUNCH_CHECK();
     return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------ the aggregation
-
-__device__ __forceinline__ float sage_scale(int mean, int deg) {
-    return mean ? (deg > 0 ? 1.0f / (float)deg : 0.f) : 1.f;
-}
-
-// The epilogue of the shared row sum (row_sum.h), p = the row's sum + loops[row] src[row]:
-//   out[row] = act(s p + add[row] + bias),  s = 1 / deg when mean (0 for an empty row) else 1;  copy[row] = src[row] (every row, long or
-//   not).  add, bias, loops and copy are optional.
-struct SageEpi {
-    const float* src; long long ld_src;
-    const int32_t* loops;
-    const float* add; long long ld_add;
-    const float* bias;
-    float* out; long long ld_out;
-    float* copy; long long ld_copy;
-    int mean, relu;
-
-    template <int VEC, int LPR, int NS>
-    __device__ __forceinline__ void pre(int row, int F, int l) const {
-        if (!copy) return;
-        float xr[NS][VEC];
-        row_load_ld<VEC, LPR, NS>(src, row, ld_src, F, l, xr);
-        row_store_ld<VEC, LPR, NS>(copy, row, ld_copy, F, l, xr);
-    }
-    template <int VEC, int LPR, int NS>
-    __device__ __forceinline__ void finish(float (&acc)[NS][VEC], int row, int deg, int F, int l) const {
-        const float sc = sage_scale(mean, deg);
-        float ad[NS][VEC];
-        if (add) row_load_ld<VEC, LPR, NS>(add, row, ld_add, F, l, ad);
-#pragma unroll
-        for (int s = 0; s < NS; ++s)
-#pragma unroll
-            for (int v = 0; v < VEC; ++v) {
-                float o = acc[s][v] * sc;
-                if (add) o += ad[s][v];
-                const int f = (s * LPR + l) * VEC + v;
-                if (bias && f < F) o += bias[f];
-                acc[s][v] = relu ? fmaxf(o, 0.f) : o;
-            }
-        row_store_ld<VEC, LPR, NS>(out, row, ld_out, F, l, acc);
-    }
-    __device__ __forceinline__ void finish_col(float a, int row, int deg, int, int f) const {
-        float o = a * sage_scale(mean, deg);
-        if (add) o += add[(long long)row * ld_add + f];
-        if (bias) o += bias[f];
-        out[(long long)row * ld_out + f] = relu ? fmaxf(o, 0.f) : o;
-    }
-};
-
-// Backward, row-local (row_gate.h): g = dout gated by relu_out > 0;  dadd = g;  gs = s g;  the column sums of g.  s of a row:
-struct SageScale {
-    const int32_t* loops; const int32_t* rowptr_t; int mean;
-    __device__ __forceinline__ float operator()(int row) const {
-        float sc = 1.f;
-        if (mean) sc = sage_scale(1, (rowptr_t[row + 1] - rowptr_t[row]) + (loops ? loops[row] : 0));
-        return sc;
-    }
-};
-
-// ------------------------------------------------------------------------------------------------------------ host side
-
-static inline bool sage_vec_ok(const void* p, int64_t ld) { return !p || (grapes_aligned16(p) && ld % 4 == 0); }
-
-// workspace: [pacc item_cap f] [gs n f] [part slabs f]
-extern "C" size_t grapes_sage_aggregate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f) {
-    const size_t N = n > 0 ? (size_t)n : 0, I = item_cap > 0 ? (size_t)item_cap : 0, F = f > 0 ? (size_t)f : 1;
-    return grapes_round16(I * F * sizeof(float)) + grapes_round16(N * F * sizeof(float)) +
-           grapes_round16(row_gate_slabs(n) * F * sizeof(float)) + 16;
-}
-
-extern "C" int grapes_sage_aggregate_fwd(const float* src, int64_t ld_src, const float* add, int64_t ld_add, const float* bias,
-                                         const int32_t* loops, const int32_t* rowptr_t, const int32_t* csr_src, int32_t mean,
-                                         int32_t relu, float* out, int64_t ld_out, float* copy_out, int64_t ld_copy, int32_t n,
-                                         const int32_t* d_n, int32_t f, const int32_t* long_items, const int32_t* d_n_items,
-                                         int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream) {
-    if (!src || !rowptr_t || !csr_src || !out || n < 0 || f < 1) return GRAPES_EINVAL;
-    if (ld_src < f || ld_out < f || (add && ld_add < f) || (copy_out && ld_copy < f)) return GRAPES_EINVAL;
-    if (out == src || copy_out == src || (copy_out && copy_out == out)) return GRAPES_EINVAL;
-    const bool use_items = long_items && d_n_items && workspace && item_cap > 0;
-    if (use_items && !grapes_aligned16(workspace)) return GRAPES_EALIGN;
-    const int shape = gather_shape(f, sage_vec_ok(src, ld_src) && sage_vec_ok(add, ld_add) && sage_vec_ok(out, ld_out) &&
-                                    sage_vec_ok(copy_out, ld_copy) && (!bias || grapes_aligned16(bias)));
-    if (shape < 0) return shape;
-    if (n == 0) return 0;
-    SageEpi epi;
-    epi.src = src; epi.ld_src = ld_src; epi.add = add; epi.ld_add = ld_add; epi.bias = bias; epi.loops = loops;
-    epi.out = out; epi.ld_out = ld_out; epi.copy = copy_out; epi.ld_copy = ld_copy; epi.mean = mean ? 1 : 0; epi.relu = relu ? 1 : 0;
-    return row_sum_propagate<4>(epi, rowptr_t, csr_src, n, d_n, f, shape == 0, use_items ? long_items : nullptr, d_n_items, item_cap,
-                          (float*)workspace, status, (hipStream_t)stream);
-}
-
-extern "C" int grapes_sage_aggregate_bwd(const float* dout, int64_t ld_dout, const float* relu_out, int64_t ld_relu,
-                                         const int32_t* loops, const int32_t* rowptr_t, const int32_t* rowptr_s,
-                                         const int32_t* csr_dst, int32_t mean, const float* add, int64_t ld_add, float* dsrc,
-                                         int64_t ld_dsrc, float* dadd, int64_t ld_dadd, float* dbias, int32_t n, const int32_t* d_n,
-                                         int32_t f, const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap,
-                                         void* workspace, int32_t* status, grapes_stream_t stream) {
-    if (!dout || !rowptr_t || n < 0 || f < 1 || ld_dout < f) return GRAPES_EINVAL;
-    if (dsrc && (!rowptr_s || !csr_dst || ld_dsrc < f || dsrc == dout || dsrc == dadd)) return GRAPES_EINVAL;
-    if ((relu_out && ld_relu < f) || (add && ld_add < f) || (dadd && (ld_dadd < f || dadd == dout))) return GRAPES_EINVAL;
-    const bool pass = mean || relu_out || dadd || dbias;                      // the row-local pass; without it dsrc gathers dout itself
-    const bool use_items = dsrc && items_s && d_n_items_s && item_cap > 0;
-    if ((pass || use_items) && !workspace) return GRAPES_EINVAL;
-    if (workspace && !grapes_aligned16(workspace)) return GRAPES_EALIGN;
-    const bool src_ok = pass ? true : sage_vec_ok(dout, ld_dout);
-    const int shape = gather_shape(f, src_ok && sage_vec_ok(add, ld_add) && sage_vec_ok(dsrc, ld_dsrc));
-    if (shape < 0) return shape;
-    if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t I = item_cap > 0 ? (size_t)item_cap : 0;
-    float* pacc = (float*)workspace;
-    float* gs = workspace ? (float*)((char*)workspace + grapes_round16(I * f * sizeof(float))) : nullptr;
-    float* part = workspace ? (float*)((char*)gs + grapes_round16((size_t)n * f * sizeof(float))) : nullptr;
-    if (pass) {
-        const SageScale scale{loops, rowptr_t, mean ? 1 : 0};
-        const int rc = row_gate_launch(dout, (long long)ld_dout, relu_out, (long long)ld_relu, scale, dsrc ? gs : (float*)nullptr, dadd,
-                                       (long long)ld_dadd, part, dbias, n, d_n, f, s);
-        if (rc) return rc;
-    }
-    if (!dsrc) return 0;
-    SageEpi epi;
-    epi.src = pass ? gs : dout; epi.ld_src = pass ? f : ld_dout; epi.add = add; epi.ld_add = ld_add; epi.bias = nullptr;
-    epi.loops = loops; epi.out = dsrc; epi.ld_out = ld_dsrc; epi.copy = nullptr; epi.ld_copy = 0; epi.mean = 0; epi.relu = 0;
-    return row_sum_propagate<4>(epi, rowptr_s, csr_dst, n, d_n, f, shape == 0, use_items ? items_s : nullptr, d_n_items_s, item_cap, pacc,
-                          status, s);
 }

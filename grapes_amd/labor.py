@@ -18,7 +18,7 @@ project's SAGE stack — neighbour sampling's estimator on a far smaller batch, 
   --eval_frequency 1, --dropout 0, --runs 1, --seed; --num_layers defaults to the number of fanouts and must equal it.  The aggregation
   is the mean: there is no --aggr.
 * Not built: a captured (hipGraph) step, partitioned / multi-GPU forms, DGL's batch_dependency, sequential Poisson (exact-k) sampling,
-  a per-edge-weight form of grapes_sage_aggregate_*, graphs with 2^31 or more entries.  `--classifier` / `--model_type` routes in
+  a per-edge-weight form of grapes_rootsum_aggregate_*, graphs with 2^31 or more entries.  `--classifier` / `--model_type` routes in
   grapes_amd.main and grapes_amd.full_batch do not take this sampler.
 
 Datasets as in grapes_amd.main: a synthetic stand-in by name, or `module:function`.

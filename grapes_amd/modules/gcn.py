@@ -946,36 +946,39 @@ class PNA(nn.Module):
         return self.conv[n_conv - 1](x, edges)
 
 
-# ------------------------------------------------------------------------------------------------ GraphSAGE (PyG SAGEConv)
-class _SAGEConvFn(torch.autograd.Function):
-    """out = act(W_l aggr_{j -> i} x_j + W_r x_i + b), aggr = mean or sum — both linear, so either operand form computes it:
-      transform-first   H = x [W_l ; W_r]ᵀ in ONE GEMM ([n, 2 out]), then grapes_sage_aggregate_fwd gathers the left half with the
-                        right half, the bias and the ReLU in its epilogue; backward: the gated gather of dout over the by-source
-                        CSR into the left half of dH with g in its right half, then dW = dHᵀ x and dx = dH W, one GEMM each.
-      aggregate-first   Z = [aggr x | x] from one gather of x itself ([n, 2 in]), then ONE GEMM act(Z [W_l | W_r]ᵀ + b);
+# ------------------------------------------------------------------------- GraphSAGE and Cluster-GCN (PyG SAGEConv, ClusterGCNConv)
+class _RootSumConvFn(torch.autograd.Function):
+    """out = act(W_a (A^ x)_i + W_r x_i + b) for a row-scaled plain-sum aggregation A^ (ops.sage_aggregate_* or ops.cluster_aggregate_*,
+    handed in as `agg` = (fwd, bwd, the layer's aggr / diag_lambda: their third argument)) — linear in x, so either operand form
+    computes it:
+      transform-first   H = x [W_a ; W_r]ᵀ in ONE GEMM ([n, 2 out]), then the aggregation gathers the left half with the right half,
+                        the bias and the ReLU in its epilogue; backward: the gated gather of dout over the by-source CSR into the
+                        left half of dH with g in its right half, then dW = dHᵀ x and dx = dH W, one GEMM each.
+      aggregate-first   Z = [A^ x | x] from one gather of x itself ([n, 2 in]), then ONE GEMM act(Z [W_a | W_r]ᵀ + b);
                         backward: dW and db from one gated GEMM, dZ = g W, dx = the gather of dZ's left half plus its right half.
-    Saved: x or Z, the stacked weight and, with ReLU, the output; nothing of size e."""
+    W_r may be None (SAGEConv's root_weight=False): the right halves are then absent.  Saved: x or Z, the stacked weight and, with
+    ReLU, the output; nothing of size e."""
 
     @staticmethod
-    def forward(ctx, x, w_l, w_r, bias, prep, aggr, relu, agg_first, long_rows):
+    def forward(ctx, x, w_a, w_r, bias, prep, agg, relu, agg_first, long_rows):
         d_n, n = prep.d_n, x.shape[0]
-        f_out, f_in = w_l.shape
-        ctx.prep, ctx.aggr, ctx.relu, ctx.agg_first, ctx.root, ctx.long_rows = prep, aggr, relu, agg_first, w_r is not None, long_rows
+        f_out, f_in = w_a.shape
+        ctx.prep, ctx.agg, ctx.relu, ctx.agg_first, ctx.root, ctx.long_rows = prep, agg, relu, agg_first, w_r is not None, long_rows
         ctx.f_in, ctx.f_out = f_in, f_out
         if agg_first:
             if w_r is not None:
                 z = torch.empty((n, 2 * f_in), dtype=torch.float32, device=x.device)
-                ops.sage_aggregate_fwd(x, prep, aggr, out=z[:, :f_in], copy_out=z[:, f_in:], long_rows=long_rows)
-                w = torch.cat([w_l, w_r], 1)                                   # [W_l | W_r]: [out, 2 in]
+                agg[0](x, prep, agg[2], out=z[:, :f_in], copy_out=z[:, f_in:], long_rows=long_rows)
+                w = torch.cat([w_a, w_r], 1)                                   # [W_a | W_r]: [out, 2 in]
             else:
-                z, w = ops.sage_aggregate_fwd(x, prep, aggr, long_rows=long_rows), w_l
+                z, w = agg[0](x, prep, agg[2], long_rows=long_rows), w_a
             out = ops.linear_bias_act_fwd(z, w, bias, relu, d_n=d_n)
             ctx.save_for_backward(z, w, out if relu else None)
             return out
-        w = torch.cat([w_l, w_r], 0) if w_r is not None else w_l               # [W_l ; W_r]: [2 out, in]
+        w = torch.cat([w_a, w_r], 0) if w_r is not None else w_a               # [W_a ; W_r]: [2 out, in]
         h = ops.linear_fwd(x, w, d_n=d_n)
-        out = ops.sage_aggregate_fwd(h[:, :f_out], prep, aggr, add=h[:, f_out:] if w_r is not None else None, bias=bias, relu=relu,
-                                     long_rows=long_rows)
+        out = agg[0](h[:, :f_out], prep, agg[2], add=h[:, f_out:] if w_r is not None else None, bias=bias, relu=relu,
+                     long_rows=long_rows)
         ctx.save_for_backward(x, w, out if relu else None)
         return out
 
@@ -991,17 +994,16 @@ class _SAGEConvFn(torch.autograd.Function):
             if ctx.needs_input_grad[0]:
                 g = ops.gcn2_mix_bwd(dout, out, True, 1.0, d_n=d_n)[0] if ctx.relu else dout
                 dz = ops.linear_bwd_input(g, w, d_n=d_n)
-                dx = ops.sage_aggregate_bwd(dz[:, :f_in], prep, ctx.aggr, add=dz[:, f_in:] if ctx.root else None,
-                                            long_rows=ctx.long_rows)[0]
-            dw_l, dw_r = (dw[:, :f_in].contiguous(), dw[:, f_in:].contiguous()) if ctx.root else (dw, None)
-            return dx, dw_l, dw_r, dbias if want_b else None, None, None, None, None, None
+                dx = ctx.agg[1](dz[:, :f_in], prep, ctx.agg[2], add=dz[:, f_in:] if ctx.root else None, long_rows=ctx.long_rows)[0]
+            dw_a, dw_r = (dw[:, :f_in].contiguous(), dw[:, f_in:].contiguous()) if ctx.root else (dw, None)
+            return dx, dw_a, dw_r, dbias if want_b else None, None, None, None, None, None
         dh = torch.empty((dout.shape[0], w.shape[0]), dtype=torch.float32, device=dout.device)
-        _, _, dbias = ops.sage_aggregate_bwd(dout, prep, ctx.aggr, relu_out=out if ctx.relu else None, dsrc=dh[:, :f_out],
-                                             dadd=dh[:, f_out:] if ctx.root else None, want_bias=want_b, long_rows=ctx.long_rows)
+        _, _, dbias = ctx.agg[1](dout, prep, ctx.agg[2], relu_out=out if ctx.relu else None, dsrc=dh[:, :f_out],
+                                 dadd=dh[:, f_out:] if ctx.root else None, want_bias=want_b, long_rows=ctx.long_rows)
         dw = ops.linear_bwd_weight(dh, a, d_n=d_n)
         dx = ops.linear_bwd_input(dh, w, d_n=d_n) if ctx.needs_input_grad[0] else None
-        dw_l, dw_r = (dw[:f_out], dw[f_out:]) if ctx.root else (dw, None)
-        return dx, dw_l, dw_r, dbias, None, None, None, None, None
+        dw_a, dw_r = (dw[:f_out], dw[f_out:]) if ctx.root else (dw, None)
+        return dx, dw_a, dw_r, dbias, None, None, None, None, None
 
 
 class _SAGELin(nn.Module):
@@ -1024,41 +1026,25 @@ class _SAGELin(nn.Module):
             nn.init.uniform_(self.bias, -bound, bound)
 
 
-class SAGEConv(nn.Module):
-    """PyG SAGEConv(in_channels, out_channels, aggr="mean" | "sum", root_weight=True, bias=True) [PyG-recall: torch_geometric 2.5.2]:
-    out_i = W_l aggr_{j -> i} x_j + W_r x_i + b, keys `lin_l.weight`, `lin_l.bias`, `lin_r.weight` (absent with root_weight=False).
-    The adjacency is used as stored: duplicates by multiplicity, stored loops are ordinary neighbours, none added; a node without a
-    neighbour aggregates 0.  Not built: aggr="max" / "lstm", project=True, normalize=True, the bipartite (x_src, x_dst) call.
+class _RootSumConv(nn.Module):
+    """What SAGEConv and ClusterGCNConv share: the widths and their refusals, the choice of the operand form, forward.  A layer
+    supplies its two _SAGELin maps (_lins: the aggregate's, which carries the bias, and the root's, which may be None), the graph it
+    asks _layer_graph for (_GRAPH, _LOOPS) and its aggregation (_aggregation: _RootSumConvFn's `agg`)."""
+    _GRAPH, _LOOPS = None, None
 
-    The operand form is chosen by width (both compute the same map, see _SAGEConvFn): aggregate-first when in_channels <
-    out_channels and in_channels is a width the gather is built for (any up to 256, multiples of 4 up to 1024) — the gather then
-    moves the narrower rows; transform-first otherwise, which needs out_channels to be such a width.  forward's private `_form`
-    ("transform" / "aggregate") forces one; `_long_rows` is ops.sage_aggregate_fwd's long_rows."""
-
-    def __init__(self, in_channels: int, out_channels: int, aggr: str = "mean", normalize: bool = False, root_weight: bool = True,
-                 project: bool = False, bias: bool = True):
-        super().__init__()
-        if aggr not in ops.SAGE_AGGRS:
-            raise NotImplementedError(f"SAGEConv: aggr={aggr!r} is not built (built: {', '.join(ops.SAGE_AGGRS)}; max is not linear "
-                                      "and needs its own gather)")
-        if normalize or project:
-            raise NotImplementedError("SAGEConv: normalize=True and project=True are not built")
+    def _set_widths(self, in_channels: int, out_channels: int):
+        who = type(self).__name__
         if int(in_channels) < 1 or int(out_channels) < 1:
-            raise ValueError("SAGEConv: in_channels and out_channels are at least 1")
-        self.in_channels, self.out_channels, self.aggr, self.root_weight = int(in_channels), int(out_channels), aggr, bool(root_weight)
+            raise ValueError(f"{who}: in_channels and out_channels are at least 1")
+        self.in_channels, self.out_channels = int(in_channels), int(out_channels)
         if not self.form_ok("transform") and not self.form_ok("aggregate"):
-            raise ValueError(f"SAGEConv: {in_channels} -> {out_channels} is not built: the gather takes any width up to 256 and "
+            raise ValueError(f"{who}: {in_channels} -> {out_channels} is not built: the gather takes any width up to 256 and "
                              "multiples of 4 up to 1024 (out_channels, or in_channels when it is the smaller)")
-        self.lin_l = _SAGELin(self.in_channels, self.out_channels, bias)
-        if root_weight:
-            self.lin_r = _SAGELin(self.in_channels, self.out_channels, False)
-        else:
-            self.register_module("lin_r", None)
 
     def reset_parameters(self):
-        self.lin_l.reset_parameters()
-        if self.lin_r is not None:
-            self.lin_r.reset_parameters()
+        for lin in self._lins():
+            if lin is not None:
+                lin.reset_parameters()
 
     def form_ok(self, form: str) -> bool:
         """Whether an operand form can run these widths (aggregate-first also needs two output columns for its fused GEMM)."""
@@ -1072,22 +1058,101 @@ class SAGEConv(nn.Module):
         return "transform" if self.form_ok("transform") else "aggregate"
 
     def forward(self, x, edge_index, relu: bool = False, _form: Optional[str] = None, _long_rows: Optional[bool] = None):
-        x = _cuda_f32(x, "SAGEConv")
+        who = type(self).__name__
+        x = _cuda_f32(x, who)
         if x.dim() != 2 or x.shape[1] != self.in_channels:
-            raise ValueError(f"SAGEConv: width {tuple(x.shape)[-1]} != in_channels {self.in_channels}")
+            raise ValueError(f"{who}: width {tuple(x.shape)[-1]} != in_channels {self.in_channels}")
         form = self.default_form() if _form is None else _form
         if form not in ("transform", "aggregate") or not self.form_ok(form):
-            raise ValueError(f"SAGEConv: the {form!r} form is not built for {self.in_channels} -> {self.out_channels}")
-        prep = _layer_graph(edge_index, x.shape[0], "SAGE", loops=True)
-        return _SAGEConvFn.apply(x, self.lin_l.weight, self.lin_r.weight if self.lin_r is not None else None, self.lin_l.bias, prep,
-                                 self.aggr, relu, form == "aggregate", _long_rows)
+            raise ValueError(f"{who}: the {form!r} form is not built for {self.in_channels} -> {self.out_channels}")
+        prep = _layer_graph(edge_index, x.shape[0], self._GRAPH, loops=self._LOOPS)
+        lin_a, lin_r = self._lins()
+        return _RootSumConvFn.apply(x, lin_a.weight, lin_r.weight if lin_r is not None else None, lin_a.bias, prep, self._aggregation(),
+                                    relu, form == "aggregate", _long_rows)
 
 
-class SAGE(nn.Module):
-    """GraphSAGE(in_features, hidden_dims, dropout=0., aggr="mean") with GCN's routing: SAGEConv(dims[i], dims[i + 1]) layers in
-    `convs` [PyG-recall: GraphSAGE's name], ReLU (fused into the layer) and dropout between them, edge_index[-i] for hidden layer i
-    and [0] for the last when a list is given, a single tensor / DeviceGraph for every layer otherwise; logits ONLY.  Every layer
-    runs over the batch's node_idx rows (no bipartite trimming)."""
+class SAGEConv(_RootSumConv):
+    """PyG SAGEConv(in_channels, out_channels, aggr="mean" | "sum", root_weight=True, bias=True) [PyG-recall: torch_geometric 2.5.2]:
+    out_i = W_l aggr_{j -> i} x_j + W_r x_i + b, keys `lin_l.weight`, `lin_l.bias`, `lin_r.weight` (absent with root_weight=False).
+    The adjacency is used as stored: duplicates by multiplicity, stored loops are ordinary neighbours, none added; a node without a
+    neighbour aggregates 0.  Not built: aggr="max" / "lstm", project=True, normalize=True, the bipartite (x_src, x_dst) call.
+
+    The operand form is chosen by width (both compute the same map, see _RootSumConvFn): aggregate-first when in_channels <
+    out_channels and in_channels is a width the gather is built for (any up to 256, multiples of 4 up to 1024) — the gather then
+    moves the narrower rows; transform-first otherwise, which needs out_channels to be such a width.  forward's private `_form`
+    ("transform" / "aggregate") forces one; `_long_rows` is ops.sage_aggregate_fwd's long_rows."""
+    _GRAPH, _LOOPS = "SAGE", True
+
+    def __init__(self, in_channels: int, out_channels: int, aggr: str = "mean", normalize: bool = False, root_weight: bool = True,
+                 project: bool = False, bias: bool = True):
+        super().__init__()
+        if aggr not in ops.SAGE_AGGRS:
+            raise NotImplementedError(f"SAGEConv: aggr={aggr!r} is not built (built: {', '.join(ops.SAGE_AGGRS)}; max is not linear "
+                                      "and needs its own gather)")
+        if normalize or project:
+            raise NotImplementedError("SAGEConv: normalize=True and project=True are not built")
+        self.aggr, self.root_weight = aggr, bool(root_weight)
+        self._set_widths(in_channels, out_channels)
+        self.lin_l = _SAGELin(self.in_channels, self.out_channels, bias)
+        if root_weight:
+            self.lin_r = _SAGELin(self.in_channels, self.out_channels, False)
+        else:
+            self.register_module("lin_r", None)
+
+    def _lins(self):
+        return self.lin_l, self.lin_r
+
+    def _aggregation(self):
+        return ops.sage_aggregate_fwd, ops.sage_aggregate_bwd, self.aggr
+
+
+class ClusterGCNConv(_RootSumConv):
+    """PyG ClusterGCNConv(in_channels, out_channels, diag_lambda=0., add_self_loops=True, bias=True) [PyG-recall]:
+    out_i = W_out (A^ x)_i + b + W_root x_i with A^ = D⁻¹(A + I) + diag_lambda diag(D⁻¹), D the degrees of A + I; keys `lin_out.weight`,
+    `lin_out.bias`, `lin_root.weight`.  Stored self-loops are dropped before the one loop per node is added and duplicates count by
+    multiplicity (PyG's remove_self_loops, add_self_loops).  Not built: add_self_loops=False.
+
+    The operand form is chosen by width as SAGEConv's.  forward's private `_form` ("transform" / "aggregate") forces one;
+    `_long_rows` is ops.cluster_aggregate_fwd's."""
+    _GRAPH, _LOOPS = "ClusterGCN", False
+
+    def __init__(self, in_channels: int, out_channels: int, diag_lambda: float = 0., add_self_loops: bool = True, bias: bool = True):
+        super().__init__()
+        if not add_self_loops:
+            raise NotImplementedError("ClusterGCNConv: add_self_loops=False is not built (the kernels' scale is 1 / (1 + deg))")
+        self.diag_lambda = float(diag_lambda)
+        self._set_widths(in_channels, out_channels)
+        self.lin_out = _SAGELin(self.in_channels, self.out_channels, bias)
+        self.lin_root = _SAGELin(self.in_channels, self.out_channels, False)
+
+    def _lins(self):
+        return self.lin_out, self.lin_root
+
+    def _aggregation(self):
+        return ops.cluster_aggregate_fwd, ops.cluster_aggregate_bwd, self.diag_lambda
+
+
+class _RootSumNet(nn.Module):
+    """GCN's routing over `convs`: ReLU (fused into the layer) and dropout between the layers, edge_index[-i] for hidden layer i and
+    [0] for the last when a list is given, a single tensor / DeviceGraph for every layer otherwise; logits ONLY."""
+    _drop = GCN._drop
+
+    def forward(self, x: torch.Tensor, edge_index: Union[torch.Tensor, "list[torch.Tensor]"]) -> torch.Tensor:
+        if not x.is_cuda:
+            raise ops._lib.GrapesHipError(f"{type(self).__name__} input must be a cuda tensor (grapes_amd has no CPU path)")
+        layerwise_adjacency = type(edge_index) == list
+        n_conv = len(self.convs)
+        for i in range(1, n_conv):
+            edges = edge_index[-i] if layerwise_adjacency else edge_index
+            x = self.convs[i - 1](x, edges, relu=True)
+            x = self._drop(x)
+        edges = edge_index[0] if layerwise_adjacency else edge_index
+        return self.convs[n_conv - 1](x, edges)
+
+
+class SAGE(_RootSumNet):
+    """GraphSAGE(in_features, hidden_dims, dropout=0., aggr="mean") with GCN's routing (_RootSumNet): SAGEConv(dims[i], dims[i + 1])
+    layers in `convs` [PyG-recall: GraphSAGE's name].  Every layer runs over the batch's node_idx rows (no bipartite trimming)."""
 
     def __init__(self, in_features: int, hidden_dims: "list[int]", dropout: float = 0., aggr: str = "mean"):
         super(SAGE, self).__init__()
@@ -1096,118 +1161,10 @@ class SAGE(nn.Module):
         self.dropout, self.aggr = dropout, aggr
         self.philox_dropout = None          # as GCN: a callable n_elements -> (seed, offset)
 
-    _drop = GCN._drop
 
-    def forward(self, x: torch.Tensor, edge_index: Union[torch.Tensor, "list[torch.Tensor]"]) -> torch.Tensor:
-        if not x.is_cuda:
-            raise ops._lib.GrapesHipError("SAGE input must be a cuda tensor (grapes_amd has no CPU path)")
-        layerwise_adjacency = type(edge_index) == list
-        n_conv = len(self.convs)
-        for i in range(1, n_conv):
-            edges = edge_index[-i] if layerwise_adjacency else edge_index
-            x = self.convs[i - 1](x, edges, relu=True)
-            x = self._drop(x)
-        edges = edge_index[0] if layerwise_adjacency else edge_index
-        return self.convs[n_conv - 1](x, edges)
-
-
-# ------------------------------------------------------------------------------------------------ Cluster-GCN (PyG ClusterGCNConv)
-class _ClusterGCNConvFn(torch.autograd.Function):
-    """out = act(W_out (A^ x)_i + b + W_root x_i), (A^ x)_i = s_i (sum_{j -> i} x_j + (1 + lambda) x_i), s_i = 1 / (1 + deg_i) over the
-    loop-free adjacency — linear in x, so either operand form computes it, as _SAGEConvFn:
-      transform-first   H = x [W_out ; W_root]ᵀ in ONE GEMM ([n, 2 out]), then grapes_cluster_aggregate_fwd propagates the left half
-                        with the right half, the bias and the ReLU in its epilogue; backward: the gated propagation of dout over the
-                        by-source CSR into the left half of dH with g in its right half, then dW = dHᵀ x and dx = dH W.
-      aggregate-first   Z = [A^ x | x] from one propagation of x itself ([n, 2 in]), then ONE GEMM act(Z [W_out | W_root]ᵀ + b);
-                        backward: dW and db from one gated GEMM, dZ = g W, dx = the propagation of dZ's left half plus its right half.
-    Saved: x or Z, the stacked weight and, with ReLU, the output; nothing of size e."""
-
-    @staticmethod
-    def forward(ctx, x, w_out, w_root, bias, prep, lam, relu, agg_first, long_rows):
-        d_n, n = prep.d_n, x.shape[0]
-        f_out, f_in = w_out.shape
-        ctx.prep, ctx.lam, ctx.relu, ctx.agg_first, ctx.long_rows, ctx.f_in, ctx.f_out = prep, lam, relu, agg_first, long_rows, f_in, f_out
-        if agg_first:
-            z = torch.empty((n, 2 * f_in), dtype=torch.float32, device=x.device)
-            ops.cluster_aggregate_fwd(x, prep, lam, out=z[:, :f_in], copy_out=z[:, f_in:], long_rows=long_rows)
-            w = torch.cat([w_out, w_root], 1)                                  # [W_out | W_root]: [out, 2 in]
-            out = ops.linear_bias_act_fwd(z, w, bias, relu, d_n=d_n)
-            ctx.save_for_backward(z, w, out if relu else None)
-            return out
-        w = torch.cat([w_out, w_root], 0)                                      # [W_out ; W_root]: [2 out, in]
-        h = ops.linear_fwd(x, w, d_n=d_n)
-        out = ops.cluster_aggregate_fwd(h[:, :f_out], prep, lam, add=h[:, f_out:], bias=bias, relu=relu, long_rows=long_rows)
-        ctx.save_for_backward(x, w, out if relu else None)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        a, w, out = ctx.saved_tensors
-        prep, d_n, f_in, f_out = ctx.prep, ctx.prep.d_n, ctx.f_in, ctx.f_out
-        dout = dout.contiguous()
-        want_b = ctx.needs_input_grad[3]
-        if ctx.agg_first:
-            dw, dbias = ops.linear_bwd_weight_gated(dout, a, gate=out if ctx.relu else None, d_n=d_n, want_bias=want_b)
-            dx = None
-            if ctx.needs_input_grad[0]:
-                g = ops.gcn2_mix_bwd(dout, out, True, 1.0, d_n=d_n)[0] if ctx.relu else dout
-                dz = ops.linear_bwd_input(g, w, d_n=d_n)
-                dx = ops.cluster_aggregate_bwd(dz[:, :f_in], prep, ctx.lam, add=dz[:, f_in:], long_rows=ctx.long_rows)[0]
-            return dx, dw[:, :f_in].contiguous(), dw[:, f_in:].contiguous(), dbias if want_b else None, None, None, None, None, None
-        dh = torch.empty((dout.shape[0], w.shape[0]), dtype=torch.float32, device=dout.device)
-        _, _, dbias = ops.cluster_aggregate_bwd(dout, prep, ctx.lam, relu_out=out if ctx.relu else None, dsrc=dh[:, :f_out],
-                                                dadd=dh[:, f_out:], want_bias=want_b, long_rows=ctx.long_rows)
-        dw = ops.linear_bwd_weight(dh, a, d_n=d_n)
-        dx = ops.linear_bwd_input(dh, w, d_n=d_n) if ctx.needs_input_grad[0] else None
-        return dx, dw[:f_out], dw[f_out:], dbias, None, None, None, None, None
-
-
-class ClusterGCNConv(nn.Module):
-    """PyG ClusterGCNConv(in_channels, out_channels, diag_lambda=0., add_self_loops=True, bias=True) [PyG-recall]:
-    out_i = W_out (A^ x)_i + b + W_root x_i with A^ = D⁻¹(A + I) + diag_lambda diag(D⁻¹), D the degrees of A + I; keys `lin_out.weight`,
-    `lin_out.bias`, `lin_root.weight`.  Stored self-loops are dropped before the one loop per node is added and duplicates count by
-    multiplicity (PyG's remove_self_loops, add_self_loops).  Not built: add_self_loops=False.
-
-    The operand form is chosen by width as SAGEConv's: aggregate-first when in_channels < out_channels and in_channels is a width
-    the gather is built for (any up to 256, multiples of 4 up to 1024), transform-first otherwise, which needs out_channels to be
-    such a width.  forward's private `_form` ("transform" / "aggregate") forces one; `_long_rows` is ops.cluster_aggregate_fwd's."""
-
-    def __init__(self, in_channels: int, out_channels: int, diag_lambda: float = 0., add_self_loops: bool = True, bias: bool = True):
-        super().__init__()
-        if not add_self_loops:
-            raise NotImplementedError("ClusterGCNConv: add_self_loops=False is not built (the kernels' scale is 1 / (1 + deg))")
-        if int(in_channels) < 1 or int(out_channels) < 1:
-            raise ValueError("ClusterGCNConv: in_channels and out_channels are at least 1")
-        self.in_channels, self.out_channels, self.diag_lambda = int(in_channels), int(out_channels), float(diag_lambda)
-        if not self.form_ok("transform") and not self.form_ok("aggregate"):
-            raise ValueError(f"ClusterGCNConv: {in_channels} -> {out_channels} is not built: the gather takes any width up to 256 and "
-                             "multiples of 4 up to 1024 (out_channels, or in_channels when it is the smaller)")
-        self.lin_out = _SAGELin(self.in_channels, self.out_channels, bias)
-        self.lin_root = _SAGELin(self.in_channels, self.out_channels, False)
-
-    def reset_parameters(self):
-        self.lin_out.reset_parameters()
-        self.lin_root.reset_parameters()
-
-    form_ok = SAGEConv.form_ok
-    default_form = SAGEConv.default_form
-
-    def forward(self, x, edge_index, relu: bool = False, _form: Optional[str] = None, _long_rows: Optional[bool] = None):
-        x = _cuda_f32(x, "ClusterGCNConv")
-        if x.dim() != 2 or x.shape[1] != self.in_channels:
-            raise ValueError(f"ClusterGCNConv: width {tuple(x.shape)[-1]} != in_channels {self.in_channels}")
-        form = self.default_form() if _form is None else _form
-        if form not in ("transform", "aggregate") or not self.form_ok(form):
-            raise ValueError(f"ClusterGCNConv: the {form!r} form is not built for {self.in_channels} -> {self.out_channels}")
-        prep = _layer_graph(edge_index, x.shape[0], "ClusterGCN", loops=False)
-        return _ClusterGCNConvFn.apply(x, self.lin_out.weight, self.lin_root.weight, self.lin_out.bias, prep, self.diag_lambda, relu,
-                                       form == "aggregate", _long_rows)
-
-
-class ClusterGCN(nn.Module):
-    """ClusterGCN(in_features, hidden_dims, dropout=0., diag_lambda=0.) with SAGE's routing: ClusterGCNConv(dims[i], dims[i + 1])
-    layers in `convs`, ReLU (fused into the layer) and dropout between them, edge_index[-i] for hidden layer i and [0] for the last
-    when a list is given, a single tensor / DeviceGraph for every layer otherwise; logits ONLY."""
+class ClusterGCN(_RootSumNet):
+    """ClusterGCN(in_features, hidden_dims, dropout=0., diag_lambda=0.) with SAGE's routing (_RootSumNet): ClusterGCNConv(dims[i],
+    dims[i + 1]) layers in `convs`."""
 
     def __init__(self, in_features: int, hidden_dims: "list[int]", dropout: float = 0., diag_lambda: float = 0.):
         super(ClusterGCN, self).__init__()
@@ -1215,20 +1172,6 @@ class ClusterGCN(nn.Module):
         self.convs = nn.ModuleList([ClusterGCNConv(dims[i], dims[i + 1], diag_lambda=diag_lambda) for i in range(len(hidden_dims))])
         self.dropout, self.diag_lambda = dropout, float(diag_lambda)
         self.philox_dropout = None          # as GCN: a callable n_elements -> (seed, offset)
-
-    _drop = GCN._drop
-
-    def forward(self, x: torch.Tensor, edge_index: Union[torch.Tensor, "list[torch.Tensor]"]) -> torch.Tensor:
-        if not x.is_cuda:
-            raise ops._lib.GrapesHipError("ClusterGCN input must be a cuda tensor (grapes_amd has no CPU path)")
-        layerwise_adjacency = type(edge_index) == list
-        n_conv = len(self.convs)
-        for i in range(1, n_conv):
-            edges = edge_index[-i] if layerwise_adjacency else edge_index
-            x = self.convs[i - 1](x, edges, relu=True)
-            x = self._drop(x)
-        edges = edge_index[0] if layerwise_adjacency else edge_index
-        return self.convs[n_conv - 1](x, edges)
 
 
 def classifier_layers(model) -> nn.ModuleList:

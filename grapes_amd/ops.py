@@ -2862,50 +2862,47 @@ def _strided_rows(t, name: str, n: int, f: int, allow_none: bool = False):
     return ld
 
 
+ROOTSUM_SCALE_NONE, ROOTSUM_SCALE_MEAN, ROOTSUM_SCALE_MEAN_PLUS_ONE = 0, 1, 2          # GRAPES_ROOTSUM_SCALE_*
+_ROOTSUM_LAYERS = {"sage": "SAGE aggregation", "cluster": "Cluster-GCN aggregation"}  # who -> the layer's name in a width refusal
+
+
 def _sage_aggr(aggr: str) -> int:
     if aggr not in SAGE_AGGRS:
         raise NotImplementedError(f"SAGE aggregation {aggr!r} is not built (built: {', '.join(SAGE_AGGRS)})")
-    return 1 if aggr == "mean" else 0
+    return ROOTSUM_SCALE_MEAN if aggr == "mean" else ROOTSUM_SCALE_NONE
 
 
-def sage_aggregate_fwd(src, prep: PreparedGraph, aggr: str = "mean", add=None, bias=None, relu: bool = False, out=None, copy_out=None,
-                       long_rows: Optional[bool] = None):
-    """out[i] = act(s_i (sum_{j -> i} src[j] + loops[i] src[i]) + add[i] + bias) over prep's by-target CSR and its stored loops,
-    s_i = 1 / deg_i (mean; an empty row gives 0) or 1 (sum).  src, add, out and copy_out ([n, f]) may be column blocks of wider
-    matrices (rows contiguous); copy_out[i] = src[i].  long_rows: see _long_items (tests force either form)."""
+def _rootsum_fwd(who: str, scale: int, self_weight: float, self_term: bool, loops, src, prep: PreparedGraph, add, bias, relu, out,
+                 copy_out, long_rows):
+    """grapes_rootsum_aggregate_fwd for {who}_aggregate_fwd, who = "sage" or "cluster" (the name a refusal carries):
+    out[i] = act(s_i (sum_{j -> i} src[j] + (loops[i] + [self_term] self_weight) src[i]) + add[i] + bias), s_i by `scale`."""
     n, f = src.shape
-    _gather_width(f, "SAGE aggregation")
-    mean = _sage_aggr(aggr)
+    _gather_width(f, _ROOTSUM_LAYERS[who])
     if n != prep.n:
         raise ValueError("src must be [n, f] over the prepared graph's nodes")
     _chk(bias, _f32, "bias", True)
     if bias is not None and bias.numel() != f:
         raise ValueError("bias must hold f values")
-    loops = gcn2_loops(prep)
     if out is None:
         out = torch.empty((n, f), dtype=_f32, device=src.device)
     ld_src, ld_add = _strided_rows(src, "src", n, f), _strided_rows(add, "add", n, f, True)
     ld_out, ld_copy = _strided_rows(out, "out", n, f), _strided_rows(copy_out, "copy_out", n, f, True)
     items, n_items, cap = _long_items(prep, True, True, long_rows)
-    ws = _ws(lib().grapes_sage_aggregate_workspace_bytes(0, cap, f), src.device) if cap else None
-    _lib.check(lib().grapes_sage_aggregate_fwd(_p(src), ld_src, _p(add), ld_add, _p(bias), _p(loops), _p(prep.rowptr_t),
-                                               _p(prep.csr_src), mean, 1 if relu else 0, _p(out), ld_out, _p(copy_out), ld_copy, n,
-                                               _p(prep.d_n), f, items, n_items, cap, _p(ws), _p(prep.status), _stream()),
-               "sage_aggregate_fwd")
+    ws = _ws(lib().grapes_rootsum_aggregate_workspace_bytes(0, cap, f), src.device) if cap else None
+    _lib.check(lib().grapes_rootsum_aggregate_fwd(_p(src), ld_src, _p(add), ld_add, _p(bias), _p(loops), _p(prep.rowptr_t),
+                                                  _p(prep.csr_src), float(self_weight), 1 if self_term else 0, scale, 1 if relu else 0,
+                                                  _p(out), ld_out, _p(copy_out), ld_copy, n, _p(prep.d_n), f, items, n_items, cap, _p(ws),
+                                                  _p(prep.status), _stream()), who + "_aggregate_fwd")
     return out
 
 
-def sage_aggregate_bwd(dout, prep: PreparedGraph, aggr: str = "mean", relu_out=None, add=None, want_src: bool = True,
-                       want_add: bool = False, want_bias: bool = False, dsrc=None, dadd=None, long_rows: Optional[bool] = None):
-    """(dsrc, dadd, dbias) of sage_aggregate_fwd from dout = d out: g = dout gated by relu_out > 0 (the forward's output, when the
-    ReLU was fused); dsrc[j] = sum_{i <- j} s_i g_i + loops[j] s_j g_j (+ add[j]) over the by-source CSR; dadd = g; dbias = the
-    column sums of g.  dsrc / dadd: tensors (column blocks allowed) to write; want_*: allocate them.  Fixed order, no atomics."""
+def _rootsum_bwd(who: str, scale: int, self_weight: float, self_term: bool, loops, dout, prep: PreparedGraph, relu_out, add, want_src,
+                 want_add, want_bias, dsrc, dadd, long_rows):
+    """(dsrc, dadd, dbias) of grapes_rootsum_aggregate_bwd for {who}_aggregate_bwd."""
     n, f = dout.shape
-    _gather_width(f, "SAGE aggregation")
-    mean = _sage_aggr(aggr)
+    _gather_width(f, _ROOTSUM_LAYERS[who])
     if n != prep.n:
         raise ValueError("dout must be [n, f] over the prepared graph's nodes")
-    loops = gcn2_loops(prep)
     dev = dout.device
     if dsrc is None and want_src:
         dsrc = torch.empty((n, f), dtype=_f32, device=dev)
@@ -2916,12 +2913,29 @@ def sage_aggregate_bwd(dout, prep: PreparedGraph, aggr: str = "mean", relu_out=N
     ld_add, ld_dsrc = _strided_rows(add, "add", n, f, True), _strided_rows(dsrc, "dsrc", n, f, True)
     ld_dadd = _strided_rows(dadd, "dadd", n, f, True)
     items, n_items, cap = _long_items(prep, False, False, long_rows) if dsrc is not None else (None, None, 0)
-    ws = _ws(lib().grapes_sage_aggregate_workspace_bytes(n, cap, f), dev)
-    _lib.check(lib().grapes_sage_aggregate_bwd(_p(dout), ld_dout, _p(relu_out), ld_relu, _p(loops), _p(prep.rowptr_t),
-                                               _p(prep.rowptr_s), _p(prep.csr_dst), mean, _p(add), ld_add, _p(dsrc), ld_dsrc,
-                                               _p(dadd), ld_dadd, _p(dbias), n, _p(prep.d_n), f, items, n_items, cap, _p(ws),
-                                               _p(prep.status), _stream()), "sage_aggregate_bwd")
+    ws = _ws(lib().grapes_rootsum_aggregate_workspace_bytes(n, cap, f), dev)
+    _lib.check(lib().grapes_rootsum_aggregate_bwd(_p(dout), ld_dout, _p(relu_out), ld_relu, _p(loops), _p(prep.rowptr_t),
+                                                  _p(prep.rowptr_s), _p(prep.csr_dst), float(self_weight), 1 if self_term else 0, scale,
+                                                  _p(add), ld_add, _p(dsrc), ld_dsrc, _p(dadd), ld_dadd, _p(dbias), n, _p(prep.d_n), f,
+                                                  items, n_items, cap, _p(ws), _p(prep.status), _stream()), who + "_aggregate_bwd")
     return dsrc, dadd, dbias
+
+
+def sage_aggregate_fwd(src, prep: PreparedGraph, aggr: str = "mean", add=None, bias=None, relu: bool = False, out=None, copy_out=None,
+                       long_rows: Optional[bool] = None):
+    """out[i] = act(s_i (sum_{j -> i} src[j] + loops[i] src[i]) + add[i] + bias) over prep's by-target CSR and its stored loops,
+    s_i = 1 / deg_i (mean; an empty row gives 0) or 1 (sum).  src, add, out and copy_out ([n, f]) may be column blocks of wider
+    matrices (rows contiguous); copy_out[i] = src[i].  long_rows: see _long_items (tests force either form)."""
+    return _rootsum_fwd("sage", _sage_aggr(aggr), 0.0, False, gcn2_loops(prep), src, prep, add, bias, relu, out, copy_out, long_rows)
+
+
+def sage_aggregate_bwd(dout, prep: PreparedGraph, aggr: str = "mean", relu_out=None, add=None, want_src: bool = True,
+                       want_add: bool = False, want_bias: bool = False, dsrc=None, dadd=None, long_rows: Optional[bool] = None):
+    """(dsrc, dadd, dbias) of sage_aggregate_fwd from dout = d out: g = dout gated by relu_out > 0 (the forward's output, when the
+    ReLU was fused); dsrc[j] = sum_{i <- j} s_i g_i + loops[j] s_j g_j (+ add[j]) over the by-source CSR; dadd = g; dbias = the
+    column sums of g.  dsrc / dadd: tensors (column blocks allowed) to write; want_*: allocate them.  Fixed order, no atomics."""
+    return _rootsum_bwd("sage", _sage_aggr(aggr), 0.0, False, gcn2_loops(prep), dout, prep, relu_out, add, want_src, want_add,
+                        want_bias, dsrc, dadd, long_rows)
 
 
 # ------------------------------------------------------------------------------- VR-GCN: control variates on historical activations
@@ -3739,6 +3753,11 @@ def partition_cut(rowptr, col, num_nodes: int, part, num_parts: int, status=None
     return cut
 
 
+def _cluster_self_weight(diag_lambda: float) -> float:
+    """1 + diag_lambda as fp32 adds them (diag_lambda rounded to fp32 first; the sum of two fp32 values rounds once through fp64)."""
+    return 1.0 + _C.c_float(float(diag_lambda)).value
+
+
 def cluster_aggregate_fwd(src, prep: PreparedGraph, diag_lambda: float = 0.0, add=None, bias=None, relu: bool = False, out=None,
                           copy_out=None, long_rows: Optional[bool] = None):
     """out[i] = act(s_i (sum_{j -> i} src[j] + (1 + diag_lambda) src[i]) + add[i] + bias) over prep's loop-free by-target CSR,
@@ -3746,24 +3765,8 @@ def cluster_aggregate_fwd(src, prep: PreparedGraph, diag_lambda: float = 0.0, ad
     (rows contiguous); copy_out[i] = src[i].  long_rows: see _long_items (tests force either form)."""
     if not src.is_cuda:
         raise _lib.GrapesHipError("cluster_aggregate_fwd: src must live in HBM (cuda tensor); grapes_amd has no CPU path")
-    n, f = src.shape
-    _gather_width(f, "Cluster-GCN aggregation")
-    if n != prep.n:
-        raise ValueError("src must be [n, f] over the prepared graph's nodes")
-    _chk(bias, _f32, "bias", True)
-    if bias is not None and bias.numel() != f:
-        raise ValueError("bias must hold f values")
-    if out is None:
-        out = torch.empty((n, f), dtype=_f32, device=src.device)
-    ld_src, ld_add = _strided_rows(src, "src", n, f), _strided_rows(add, "add", n, f, True)
-    ld_out, ld_copy = _strided_rows(out, "out", n, f), _strided_rows(copy_out, "copy_out", n, f, True)
-    items, n_items, cap = _long_items(prep, True, True, long_rows)
-    ws = _ws(lib().grapes_cluster_aggregate_workspace_bytes(0, cap, f), src.device) if cap else None
-    _lib.check(lib().grapes_cluster_aggregate_fwd(_p(src), ld_src, _p(add), ld_add, _p(bias), _p(prep.rowptr_t), _p(prep.csr_src),
-                                                  float(diag_lambda), 1 if relu else 0, _p(out), ld_out, _p(copy_out), ld_copy, n,
-                                                  _p(prep.d_n), f, items, n_items, cap, _p(ws), _p(prep.status), _stream()),
-               "cluster_aggregate_fwd")
-    return out
+    return _rootsum_fwd("cluster", ROOTSUM_SCALE_MEAN_PLUS_ONE, _cluster_self_weight(diag_lambda), True, None, src, prep, add, bias,
+                        relu, out, copy_out, long_rows)
 
 
 def cluster_aggregate_bwd(dout, prep: PreparedGraph, diag_lambda: float = 0.0, relu_out=None, add=None, want_src: bool = True,
@@ -3773,26 +3776,8 @@ def cluster_aggregate_bwd(dout, prep: PreparedGraph, diag_lambda: float = 0.0, r
     the column sums of g.  dsrc / dadd: tensors (column blocks allowed) to write; want_*: allocate them.  Fixed order, no atomics."""
     if not dout.is_cuda:
         raise _lib.GrapesHipError("cluster_aggregate_bwd: dout must live in HBM (cuda tensor); grapes_amd has no CPU path")
-    n, f = dout.shape
-    _gather_width(f, "Cluster-GCN aggregation")
-    if n != prep.n:
-        raise ValueError("dout must be [n, f] over the prepared graph's nodes")
-    dev = dout.device
-    if dsrc is None and want_src:
-        dsrc = torch.empty((n, f), dtype=_f32, device=dev)
-    if dadd is None and want_add:
-        dadd = torch.empty((n, f), dtype=_f32, device=dev)
-    dbias = torch.empty(f, dtype=_f32, device=dev) if want_bias else None
-    ld_dout, ld_relu = _strided_rows(dout, "dout", n, f), _strided_rows(relu_out, "relu_out", n, f, True)
-    ld_add, ld_dsrc = _strided_rows(add, "add", n, f, True), _strided_rows(dsrc, "dsrc", n, f, True)
-    ld_dadd = _strided_rows(dadd, "dadd", n, f, True)
-    items, n_items, cap = _long_items(prep, False, False, long_rows) if dsrc is not None else (None, None, 0)
-    ws = _ws(lib().grapes_cluster_aggregate_workspace_bytes(n, cap, f), dev)
-    _lib.check(lib().grapes_cluster_aggregate_bwd(_p(dout), ld_dout, _p(relu_out), ld_relu, _p(prep.rowptr_t), _p(prep.rowptr_s),
-                                                  _p(prep.csr_dst), float(diag_lambda), _p(add), ld_add, _p(dsrc), ld_dsrc, _p(dadd),
-                                                  ld_dadd, _p(dbias), n, _p(prep.d_n), f, items, n_items, cap, _p(ws),
-                                                  _p(prep.status), _stream()), "cluster_aggregate_bwd")
-    return dsrc, dadd, dbias
+    return _rootsum_bwd("cluster", ROOTSUM_SCALE_MEAN_PLUS_ONE, _cluster_self_weight(diag_lambda), True, None, dout, prep, relu_out,
+                        add, want_src, want_add, want_bias, dsrc, dadd, long_rows)
 
 
 def classifier_loss(logits, local_rows, target_ids, labels, out_grad=None):

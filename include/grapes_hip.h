@@ -71,8 +71,11 @@ extern "C" {
  * grapes_partition_propose, grapes_partition_admit, grapes_partition_cut (+ _workspace_bytes each); GNNAutoScale —
  * grapes_gas_resolve(_workspace_bytes), grapes_gas_aggregate_fwd / _bwd, grapes_gas_aggregate_workspace_bytes; PPRGo — grapes_pprgo_topk,
  * grapes_pprgo_batch(_workspace_bytes), grapes_pprgo_aggregate_fwd / _bwd (+ _workspace_bytes each); PinSAGE — grapes_pinsage_neighbors,
- * grapes_relu_l2norm_fwd / _bwd. */
-#define GRAPES_ABI_VERSION 303
+ * grapes_relu_l2norm_fwd / _bwd.
+ * 304: grapes_sage_aggregate_fwd / _bwd and grapes_cluster_aggregate_fwd / _bwd were one layer written twice and left, with their two
+ * _workspace_bytes: grapes_rootsum_aggregate_fwd / _bwd (loops, self_weight, self_term, scale) and
+ * grapes_rootsum_aggregate_workspace_bytes compute both. */
+#define GRAPES_ABI_VERSION 304
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
 #define GRAPES_EALIGN (-2)   /* pointer not aligned as required */
@@ -1573,10 +1576,17 @@ int grapes_asgcn_logq_bwd(const int32_t* edge_src, const int32_t* edge_dst, cons
  * arithmetic.  workspace: grapes_sage_sample_layer_workspace_bytes(m), 8-byte aligned. */
 size_t grapes_sage_sample_layer_workspace_bytes(int32_t m);
 int grapes_sage_sample_layer(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* rows, int32_t m, const int32_t* d_m, int32_t fanout, const uint32_t* keys, int64_t n_keys, uint64_t philox_seed, uint64_t philox_offset, uint64_t* d_philox_offset, int32_t e_cap, int32_t* edge_src, int32_t* edge_dst, int64_t* edge_pos, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream);
-/* SAGEConv's aggregation over the CSRs grapes_gcn_prepare builds, used as stored: no self-loop is added, duplicate entries count
- * by multiplicity, and the stored self-loops the build drops come back through loops[i] (grapes_gcn2_loop_counts; NULL: none):
- *   out[i, :f] = act(s_i (sum_{j in row i of the by-target CSR} src[j, :f] + loops[i] src[i, :f]) + add[i, :f] + bias)
- *   s_i = 1 / deg_i (mean != 0) or 1 (sum), deg_i = (rowptr_t[i + 1] - rowptr_t[i]) + loops[i]; an empty row aggregates to 0.
+/* The aggregation SAGEConv and ClusterGCNConv share, over the CSRs grapes_gcn_prepare builds, used as stored: duplicate entries
+ * count by multiplicity, and the stored self-loops the build drops come back through loops[i] (grapes_gcn2_loop_counts; NULL: none):
+ *   out[i, :f] = act(s_i (sum_{j in row i of the by-target CSR} src[j, :f] + c_i src[i, :f]) + add[i, :f] + bias)
+ *   c_i = loops[i] + (self_term != 0 ? self_weight : 0);  deg_i = (rowptr_t[i + 1] - rowptr_t[i]) + loops[i];
+ *   s_i = 1 (scale = GRAPES_ROOTSUM_SCALE_NONE), 1 / deg_i (_MEAN; an empty row aggregates to 0) or 1 / (1 + deg_i) (_MEAN_PLUS_ONE);
+ *   any other scale is GRAPES_EINVAL.
+ * SAGEConv: the stored loops, self_term = 0, _MEAN (mean) or _NONE (sum) — no self-loop is added.  ClusterGCNConv [PyG-recall:
+ * remove_self_loops followed by add_self_loops]: loops = NULL, self_term = 1 with self_weight = 1 + diag_lambda, _MEAN_PLUS_ONE.
+ * The self term is computed whenever self_term != 0, whatever self_weight holds (0 still multiplies src[i]), and src[i] is not
+ * read for it otherwise.  In fp32: p = the row's sum in entry order, p = fma(loops[i], src[i], p), p = fma(self_weight, src[i], p),
+ * o = p s_i, o += add, o += bias, ReLU.
  * The scale is applied once per row: there is no per-edge weight.  add, bias and the ReLU (relu != 0) are optional.  copy_out
  * (optional): copy_out[i, :f] = src[i, :f], the root operand beside the aggregate in the aggregate-first form.  src, add, out and
  * copy_out are row-major with their own leading dimensions (ld_* >= f floats), so column blocks of one GEMM output are used in
@@ -1585,19 +1595,22 @@ int grapes_sage_sample_layer(const int64_t* rowptr, const int32_t* col, int32_t 
  * grapes_gcn2_propagate_fwd (NULL: every row by one group of lanes): rows longer than GRAPES_LONG_ROW are cut into items whose
  * partial sums are merged in chunk order.  Every sum has a fixed order, no floating-point atomics: two runs give the same bits.
  * status: GRAPES_STATUS_BAD_INDEX when a CSR entry is outside [0, n) (the entry is dropped).
- * workspace: grapes_sage_aggregate_workspace_bytes(0, item_cap, f) for the forward, (n, item_cap, f) for the backward; 16-byte
+ * workspace: grapes_rootsum_aggregate_workspace_bytes(0, item_cap, f) for the forward, (n, item_cap, f) for the backward; 16-byte
  * aligned. */
-size_t grapes_sage_aggregate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f);
-int grapes_sage_aggregate_fwd(const float* src, int64_t ld_src, const float* add, int64_t ld_add, const float* bias, const int32_t* loops, const int32_t* rowptr_t, const int32_t* csr_src, int32_t mean, int32_t relu, float* out, int64_t ld_out, float* copy_out, int64_t ld_copy, int32_t n, const int32_t* d_n, int32_t f, const int32_t* long_items, const int32_t* d_n_items, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
+#define GRAPES_ROOTSUM_SCALE_NONE 0
+#define GRAPES_ROOTSUM_SCALE_MEAN 1
+#define GRAPES_ROOTSUM_SCALE_MEAN_PLUS_ONE 2
+size_t grapes_rootsum_aggregate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f);
+int grapes_rootsum_aggregate_fwd(const float* src, int64_t ld_src, const float* add, int64_t ld_add, const float* bias, const int32_t* loops, const int32_t* rowptr_t, const int32_t* csr_src, float self_weight, int32_t self_term, int32_t scale, int32_t relu, float* out, int64_t ld_out, float* copy_out, int64_t ld_copy, int32_t n, const int32_t* d_n, int32_t f, const int32_t* long_items, const int32_t* d_n_items, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
 /* Backward of the above.  g = dout, gated by relu_out > 0 when relu_out (the forward's output) is given:
- *   dsrc[j] = sum_{i in row j of the by-source CSR} s_i g_i + loops[j] s_j g_j (+ add[j]);   dadd = g;   dbias = column sums of g.
+ *   dsrc[j] = sum_{i in row j of the by-source CSR} s_i g_i + c_j s_j g_j (+ add[j]);   dadd = g;   dbias = column sums of g.
  * One row-local pass writes dadd, the pre-scaled rows s g and per-128-row partial column sums (added in a fixed order by a second
- * launch); dsrc is then the forward's gather over rowptr_s / csr_dst on the pre-scaled rows, with the by-source items.  The pass is
- * left out when nothing needs it (sum, no gate, no dadd, no dbias): dsrc gathers dout itself.  add (optional) is a gradient that
- * reaches the source rows directly (the root half of the aggregate-first form).  dsrc, dadd and dbias may each be NULL; dsrc and
- * dadd must not alias dout.  s_i always comes from the by-target row pointers rowptr_t.  workspace: required unless the pass is
- * left out and there are no items. */
-int grapes_sage_aggregate_bwd(const float* dout, int64_t ld_dout, const float* relu_out, int64_t ld_relu, const int32_t* loops, const int32_t* rowptr_t, const int32_t* rowptr_s, const int32_t* csr_dst, int32_t mean, const float* add, int64_t ld_add, float* dsrc, int64_t ld_dsrc, float* dadd, int64_t ld_dadd, float* dbias, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
+ * launch); dsrc is then the forward's gather over rowptr_s / csr_dst on the pre-scaled rows with scale = _NONE and the caller's
+ * loops, self_weight and self_term, with the by-source items.  The pass is left out when nothing needs it (scale = _NONE, no gate,
+ * no dadd, no dbias): dsrc gathers dout itself.  add (optional) is a gradient that reaches the source rows directly (the root half
+ * of the aggregate-first form).  dsrc, dadd and dbias may each be NULL; dsrc and dadd must not alias dout.  s_i always comes from
+ * the by-target row pointers rowptr_t.  workspace: required unless the pass is left out and there are no items. */
+int grapes_rootsum_aggregate_bwd(const float* dout, int64_t ld_dout, const float* relu_out, int64_t ld_relu, const int32_t* loops, const int32_t* rowptr_t, const int32_t* rowptr_s, const int32_t* csr_dst, float self_weight, int32_t self_term, int32_t scale, const float* add, int64_t ld_add, float* dsrc, int64_t ld_dsrc, float* dadd, int64_t ld_dadd, float* dbias, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
 
 /* ------------------------------------------------------------------ VR-GCN: the control-variate aggregation over historical
  * activations (csrc/vrgcn_kernels.hip) [Chen, Zhu and Song, ICML 2018].  The graph is a loop-free CSR (rowptr int64[N + 1], col
@@ -1612,7 +1625,7 @@ int grapes_sage_aggregate_bwd(const float* dout, int64_t ld_dout, const float* r
  * with more than grapes_vrgcn_long_row() entries (a multiple of GRAPES_LONG_ROW) are cut into chunks of that many entries, one
  * group each, whose partial sums are added in chunk order (four launches instead of one); item_cap bounds the chunks of the
  * listed long rows (at most 2^20; more raise GRAPES_STATUS_EDGE_OVERFLOW and the result is invalid); item_cap = 0: every row by
- * one group.  No float atomics: two runs give the same bits.  Widths as grapes_sage_aggregate_fwd: any f <= 256, up to 1024 when
+ * one group.  No float atomics: two runs give the same bits.  Widths as grapes_rootsum_aggregate_fwd: any f <= 256, up to 1024 when
  * f % 4 == 0 and h, hbar, out are 16-byte aligned with ld % 4 == 0, else GRAPES_EALIGN / GRAPES_EINVAL.  An index outside its table
  * (a listed row, a kept source, its node_idx, a column) raises GRAPES_STATUS_BAD_INDEX and is dropped (a bad listed row gives
  * zeros).  workspace: grapes_vrgcn_aggregate_workspace_bytes(m, item_cap, f), 16-byte aligned; may be NULL with item_cap = 0. */
@@ -1662,7 +1675,7 @@ int grapes_gas_resolve(const int64_t* rowptr, const int32_t* col, int32_t num_no
  * applied once per row.  item_cap > 0: rows with more than grapes_vrgcn_long_row() codes are cut into chunks of that many, one group
  * each, whose partial sums are added in chunk order (four launches instead of one); item_cap bounds the chunks of the long rows (at
  * most 2^20; more raise GRAPES_STATUS_EDGE_OVERFLOW and the result is invalid); item_cap = 0: every row by one group.  No float
- * atomics: two runs give the same bits.  Widths as grapes_sage_aggregate_fwd: any f <= 256, up to 1024 when f % 4 == 0 and h, hbar,
+ * atomics: two runs give the same bits.  Widths as grapes_rootsum_aggregate_fwd: any f <= 256, up to 1024 when f % 4 == 0 and h, hbar,
  * out are 16-byte aligned with ld % 4 == 0, else GRAPES_EALIGN / GRAPES_EINVAL.  A code outside [-N, n) (or a node_idx outside
  * [0, N)) raises GRAPES_STATUS_BAD_INDEX and is dropped.  workspace: grapes_gas_aggregate_workspace_bytes(n, item_cap, f), 16-byte
  * aligned; may be NULL with item_cap = 0. */
@@ -1899,20 +1912,6 @@ int grapes_segment_mean_bwd(const float* g, const int32_t* ptr, int32_t num_segm
  * workspace: grapes_cluster_batch_workspace_bytes(n_cap, item_cap) bytes, 8-byte aligned. */
 size_t grapes_cluster_batch_workspace_bytes(int32_t n_cap, int32_t item_cap);
 int grapes_cluster_batch(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* perm, const int32_t* partptr, const int32_t* where, int32_t num_parts, const int32_t* clusters, int32_t q, int32_t* stamp, int32_t serial, int32_t n_cap, int32_t item_cap, int32_t e_cap, int32_t* cptr, int32_t* node_idx, int32_t* rowptr_l, int32_t* edge_src, int32_t* edge_dst, int64_t* edge_id, int32_t* d_n, int32_t* d_e, void* workspace, int32_t* status, grapes_stream_t stream);
-/* ClusterGCNConv's propagation [PyG-recall: torch_geometric ClusterGCNConv] over the loop-free CSRs of grapes_gcn_prepare (duplicates
- * count by multiplicity: PyG's remove_self_loops followed by add_self_loops):
- *   d_i = 1 + (rowptr_t[i + 1] - rowptr_t[i]),  s_i = 1 / d_i,  self_weight = 1 + diag_lambda
- *   out[i] = act(s_i (sum_{j in row i} src[j] + self_weight src[i]) + add[i] + bias)
- * and its backward from dout: g = dout gated by relu_out > 0; dsrc[j] = sum_{i in row j of the by-source CSR} s_i g_i + self_weight
- * s_j g_j (+ add[j]); dadd = g; dbias = the column sums of g.  Leading dimensions, copy_out (copy_out[i] = src[i]), the long-row items,
- * the widths (any f <= 256, multiples of 4 up to 1024 with 16-byte aligned operands), the status word and the optional arguments are
- * those of grapes_sage_aggregate_fwd / _bwd; with diag_lambda = 0 the forward equals grapes_sage_aggregate_fwd(mean, loops = ones).
- * Fixed summation order, no float atomics.  The backward always needs its workspace (gs = s g).
- * workspace: grapes_cluster_aggregate_workspace_bytes(0, item_cap, f) for the forward, (n, item_cap, f) for the backward; 16-byte
- * aligned. */
-size_t grapes_cluster_aggregate_workspace_bytes(int32_t n, int32_t item_cap, int32_t f);
-int grapes_cluster_aggregate_fwd(const float* src, int64_t ld_src, const float* add, int64_t ld_add, const float* bias, const int32_t* rowptr_t, const int32_t* csr_src, float diag_lambda, int32_t relu, float* out, int64_t ld_out, float* copy_out, int64_t ld_copy, int32_t n, const int32_t* d_n, int32_t f, const int32_t* long_items, const int32_t* d_n_items, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
-int grapes_cluster_aggregate_bwd(const float* dout, int64_t ld_dout, const float* relu_out, int64_t ld_relu, const int32_t* rowptr_t, const int32_t* rowptr_s, const int32_t* csr_dst, float diag_lambda, const float* add, int64_t ld_add, float* dsrc, int64_t ld_dsrc, float* dadd, int64_t ld_dadd, float* dbias, int32_t n, const int32_t* d_n, int32_t f, const int32_t* items_s, const int32_t* d_n_items_s, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
 
 /* ------------------------------------------------------------------ the graph partitioner of Cluster-GCN (csrc/partition_kernels.hip)
  * Size-constrained SYNCHRONOUS label propagation that refines a starting assignment.  Integers only, bit-reproducible on a CPU

@@ -11,7 +11,10 @@ gcn2_kernels.hip and pna_kernels.hip, as for the row-gather scaffold.
   --table          before each file's report, one line per kernel whose counts differ, with both sides' counts
 
   - every kernel of the parent must exist in the result, and no new one may appear; kernels are named as the demangler prints
-    them, and RENAME maps the parent's names of the kernels that moved into row_sum.h to the result's;
+    them, RENAME maps the parent's names of the kernels that moved into row_sum.h to the result's, and TYPE_RENAME the epilogue
+    and scale types of SAGEConv's and ClusterGCNConv's aggregation to the one type that replaced each pair;
+  - a file that one tree lacks holds no kernel there, and a parent's kernel is looked for in every compared file of the result:
+    the aggregation moved from sage_kernels.hip and cluster_kernels.hip to rootsum_kernels.hip;
   - a kernel's instruction stream is compared after comments are dropped and basic-block labels renumbered in order of appearance;
   - the three GAT *_chunks_k families took the strict item decode on purpose: for them the register, scratch and LDS counts of
     the code object's metadata must not rise;
@@ -40,6 +43,8 @@ EXPECTED = ("gat_fwd_chunks_k", "gat_bwd_dst_chunks_k", "gat_bwd_src_chunks_k")
 # parent kernel -> (result kernel, trailing template argument): the plain-sum gather GCN2Conv and SAGEConv share (row_sum.h)
 RENAME = {"gcn2_rows_k": ("row_sum_rows_k", "G2Epi"), "gcn2_chunks_k": ("row_sum_chunks_k", None), "gcn2_combine_k": ("row_sum_combine_k", "G2Epi"),
           "sage_rows_k": ("row_sum_rows_k", "SageEpi"), "sage_chunks_k": ("row_sum_chunks_k", None), "sage_combine_k": ("row_sum_combine_k", "SageEpi")}
+# parent template argument -> the result's: SageEpi and ClusterEpi became RootSumEpi, their row-scale functors RootSumScale
+TYPE_RENAME = {"SageEpi": "RootSumEpi", "ClusterEpi": "RootSumEpi", "SageScale": "RootSumScale", "ClusterScale": "RootSumScale"}
 COUNTS = ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "group_segment_fixed_size")
 OCC = "occupancy"
 
@@ -56,6 +61,8 @@ def counts_line(a, b):
 def assembly(csrc, name, tmp):
     """(the assembly text, {mangled kernel: occupancy in waves per SIMD as -Rpass-analysis=kernel-resource-usage reports it})"""
     out = os.path.join(tmp, name + ".s")
+    if not os.path.exists(os.path.join(csrc, name)):                        # (a file of the other tree alone)
+        return "", {}
     run = subprocess.run([HIPCC] + FLAGS + ["-Rpass-analysis=kernel-resource-usage"] + EXTRA.get(name, []) +
                          [os.path.join(csrc, name), "-o", out], stderr=subprocess.PIPE, text=True)
     if run.returncode:
@@ -75,7 +82,8 @@ def renamed(key):
     """The result's name of the parent's kernel `key` ('name' or 'name<args>'), or None where it keeps its name."""
     name, _, args = key.partition("<")
     if name not in RENAME:
-        return None
+        to = re.sub(r"\b(%s)\b" % "|".join(TYPE_RENAME), lambda t: TYPE_RENAME[t.group(0)], key)
+        return to if to != key else None
     new, last = RENAME[name]
     targs = [t for t in (args[:-1], last) if t]
     return new + ("<" + ", ".join(targs) + ">" if targs else "")
@@ -125,8 +133,15 @@ def table_rows(name, a, b):
 def main(parent, result, all_diffs=False, files=None, no_diffs=False, table=False):
     bad, other, shown = 0, 0, set()
     with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
-        for name in files or FILES:
-            a, b = kernels(assembly(parent, name, ta)), kernels(assembly(result, name, tb))
+        both = {name: (kernels(assembly(parent, name, ta)), kernels(assembly(result, name, tb))) for name in files or FILES}
+        pool = {k: v for _, b in both.values() for k, v in b.items()}      # (a template two files instantiate is one kernel)
+        wanted = {name: {to for k in a for to in (k, renamed(k)) if to} for name, (a, _) in both.items()}
+        for name, (a, own) in both.items():
+            # the result's side of this file: its own kernels but those that only another file's parent accounts for, and the
+            # kernels this file's parent names that another compared file of the result holds
+            others = set().union(*(w for n, w in wanted.items() if n != name))
+            b = {k: v for k, v in own.items() if k in wanted[name] or k not in others}
+            b.update({k: pool[k] for k in wanted[name] if k not in own and k in pool})
             moved = {k: renamed(k) for k in a if k not in b and renamed(k) in b}
             if table:
                 print("\n".join(table_rows(name, a, b)))

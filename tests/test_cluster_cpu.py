@@ -10,8 +10,8 @@ import torch
 from tests import cluster_oracle as CO
 
 F64 = np.float64
-ENTRY_POINTS = ("grapes_cluster_batch", "grapes_cluster_batch_workspace_bytes", "grapes_cluster_aggregate_fwd",
-                "grapes_cluster_aggregate_bwd", "grapes_cluster_aggregate_workspace_bytes")
+ENTRY_POINTS = ("grapes_cluster_batch", "grapes_cluster_batch_workspace_bytes", "grapes_rootsum_aggregate_fwd",
+                "grapes_rootsum_aggregate_bwd", "grapes_rootsum_aggregate_workspace_bytes")
 
 
 @pytest.fixture(scope="module")
@@ -29,7 +29,7 @@ def test_both_libraries_carry_the_entry_points_and_the_abi_stays(built_lib):
     for name in ENTRY_POINTS:
         assert name in built_lib.SIGNATURES and hasattr(prod, name) and hasattr(diag, name)
     lib = built_lib.load()
-    assert lib.grapes_abi_version() == 303
+    assert lib.grapes_abi_version() == 304
     assert lib.grapes_cluster_batch_workspace_bytes(2000, 500) > lib.grapes_cluster_batch_workspace_bytes(1000, 500) >= 1001 * 4 + 500 * 16
 
 

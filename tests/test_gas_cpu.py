@@ -176,9 +176,9 @@ def test_header_ctypes_makefile_and_both_libraries_agree():
         assert len(m.group(1).strip().split(",")) == nargs, name
         assert len(_lib.SIGNATURES[name][1]) == nargs, name
         assert all(hasattr(lib, name) for lib in libs), name
-    assert "#define GRAPES_ABI_VERSION 303" in src
+    assert "#define GRAPES_ABI_VERSION 304" in src
     bound = _lib.load()
-    assert bound.grapes_abi_version() == 303
+    assert bound.grapes_abi_version() == 304
     assert bound.grapes_gas_resolve_workspace_bytes(10) >= 11 * 4                       # host helpers: callable without a GPU
     assert bound.grapes_gas_aggregate_workspace_bytes(10, 3, 8) >= 11 * 4 + 3 * 8 * 4
     assert ops.GAS_CHUNK == 64 and ops.GAS_BAD_CODE == GO.BAD_CODE

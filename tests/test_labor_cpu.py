@@ -34,7 +34,7 @@ def test_header_table_and_both_libraries_carry_the_entry_points(built_lib):
         assert re.search(r"\b" + name + r"\s*\(", header), f"{name} is not declared in grapes_hip.h"
         assert name in built_lib.SIGNATURES, f"{name} is not in _lib.SIGNATURES"
         assert hasattr(prod, name) and hasattr(diag, name), f"{name} is not exported"
-    assert built_lib.load().grapes_abi_version() == 303
+    assert built_lib.load().grapes_abi_version() == 304
 
 
 def test_workspaces_and_argument_checks_are_host_calls(built_lib):

@@ -33,7 +33,7 @@ def test_both_libraries_carry_the_entry_points_with_their_argument_counts(built_
         decl = header.split(f" {name}(")[1].split(");")[0]
         assert decl.count(",") + 1 == n_args
     lib = built_lib.load()
-    assert lib.grapes_abi_version() == 303
+    assert lib.grapes_abi_version() == 304
     assert lib.grapes_partition_propose_workspace_bytes(1000, 10) >= 4 * 1000
     assert lib.grapes_partition_admit_workspace_bytes(1000, 10) >= 8 * 1000 + 8 * 10 + 4 * 41
     assert lib.grapes_partition_cut_workspace_bytes(1000) >= 4 * 1000 + 8 * 64

@@ -41,7 +41,7 @@ def test_header_table_and_both_libraries_carry_the_entry_points(built_lib):
         assert name in built_lib.SIGNATURES and len(built_lib.SIGNATURES[name][1]) == nargs, name
         assert built_lib.SIGNATURES[name][0] in (built_lib.I32, built_lib.SZ)
         assert hasattr(prod, name) and hasattr(diag, name), f"{name} is not exported"
-    assert "#define GRAPES_ABI_VERSION 303" in text and built_lib.load().grapes_abi_version() == 303
+    assert "#define GRAPES_ABI_VERSION 304" in text and built_lib.load().grapes_abi_version() == 304
     history = text[:text.index("#define GRAPES_ABI_VERSION")]
     assert "grapes_pinsage_neighbors" in history and "grapes_relu_l2norm_fwd" in history
 

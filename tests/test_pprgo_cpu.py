@@ -1,5 +1,5 @@
 """PPRGo without a GPU: tests/pprgo_oracle.py against dense restatements; the C surface (the header declares the entry points, the
-version stays 303, the signature table); the host-side argument checks; the trainer's refusals; the command line's namespace; and
+version stays 304, the signature table); the host-side argument checks; the trainer's refusals; the command line's namespace; and
 the theorem that ties the training form to the power-iteration inference, in fp64."""
 import ctypes
 import os
@@ -40,7 +40,7 @@ def test_header_table_and_both_libraries_carry_the_entry_points(built_lib):
         assert len([a for a in m.group(1).split(",") if a.strip()]) == nargs, name
         assert name in built_lib.SIGNATURES and len(built_lib.SIGNATURES[name][1]) == nargs, name
         assert hasattr(prod, name) and hasattr(diag, name), f"{name} is not exported"
-    assert "#define GRAPES_ABI_VERSION 303" in text and built_lib.load().grapes_abi_version() == 303
+    assert "#define GRAPES_ABI_VERSION 304" in text and built_lib.load().grapes_abi_version() == 304
     history = text[:text.index("#define GRAPES_ABI_VERSION")]
     assert "grapes_pprgo_topk" in history and "grapes_pprgo_batch" in history and "grapes_pprgo_aggregate_fwd" in history
 

@@ -1,5 +1,5 @@
 """The plain-sum gather GCN2Conv and SAGEConv share (grapes_amd/csrc/row_sum.h) on the MI355X, through the four entry points that
-launch it — grapes_gcn2_propagate_fwd / _bwd and grapes_sage_aggregate_fwd / _bwd — against the fp64 oracles of tests/gcn2_oracle.py
+launch it — grapes_gcn2_propagate_fwd / _bwd and grapes_rootsum_aggregate_fwd / _bwd — against the fp64 oracles of tests/gcn2_oracle.py
 and tests/sage_oracle.py at the project's tolerances (activations 1e-5, gradients 1e-4 in max|a − ref| / max(1, max|ref|)).
 
 One graph of 300 allocated rows, 260 of them live (d_n): node 5 is a hub as target AND as source (more than 3 GRAPES_LONG_ROW
@@ -92,7 +92,7 @@ def test_shared_gather_through_the_four_entry_points(f, off):
     want_dx, want_dx0 = (1 - ALPHA) * At_g, ALPHA * g[:m].astype(F64)
     sage_ok = f <= 256 or (f % 4 == 0 and off == 0)
     ws = ops._ws(max(L.grapes_gcn2_propagate_workspace_bytes(N_ALLOC, prep.item_cap, f),
-                     L.grapes_sage_aggregate_workspace_bytes(N_ALLOC, prep.item_cap, f)), "cuda")
+                     L.grapes_rootsum_aggregate_workspace_bytes(N_ALLOC, prep.item_cap, f)), "cuda")
     for long_rows in (True, False):
         tag = f"f={f} off={off} long_rows={long_rows}"
         it_t, nt, it_s, ns, cap = (P_(prep.items_t), P_(prep.n_items_t), P_(prep.items_s), P_(prep.n_items_s), prep.item_cap) \
@@ -108,12 +108,12 @@ def test_shared_gather_through_the_four_entry_points(f, off):
             out = _marked(f, off)
             with pytest.raises(ValueError, match="not built"):
                 ops.sage_aggregate_fwd(xd, prep, "mean", out=out, long_rows=long_rows)
-            assert L.grapes_sage_aggregate_fwd(P_(xd), f, None, 0, None, P_(prep.loops), P_(prep.rowptr_t), P_(prep.csr_src), 1, 0,
-                                               P_(out), f, None, 0, N_ALLOC, P_(d_n), f, it_t, nt, cap, P_(ws), P_(prep.status),
-                                               ops._stream()) < 0
-            assert L.grapes_sage_aggregate_bwd(P_(gd), f, None, 0, P_(prep.loops), P_(prep.rowptr_t), P_(prep.rowptr_s),
-                                               P_(prep.csr_dst), 0, None, 0, P_(out), f, None, 0, None, N_ALLOC, P_(d_n), f, it_s, ns,
-                                               cap, P_(ws), P_(prep.status), ops._stream()) < 0
+            assert L.grapes_rootsum_aggregate_fwd(P_(xd), f, None, 0, None, P_(prep.loops), P_(prep.rowptr_t), P_(prep.csr_src), 0.0, 0,
+                                                  ops.ROOTSUM_SCALE_MEAN, 0, P_(out), f, None, 0, N_ALLOC, P_(d_n), f, it_t, nt, cap,
+                                                  P_(ws), P_(prep.status), ops._stream()) < 0
+            assert L.grapes_rootsum_aggregate_bwd(P_(gd), f, None, 0, P_(prep.loops), P_(prep.rowptr_t), P_(prep.rowptr_s),
+                                                  P_(prep.csr_dst), 0.0, 0, ops.ROOTSUM_SCALE_NONE, None, 0, P_(out), f, None, 0, None,
+                                                  N_ALLOC, P_(d_n), f, it_s, ns, cap, P_(ws), P_(prep.status), ops._stream()) < 0
             assert bool((out == FMARK).all())
             continue
         for aggr in ("mean", "sum"):

@@ -11,8 +11,8 @@ import torch
 from tests import sage_oracle as SO
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ENTRY_POINTS = ("grapes_sage_sample_layer", "grapes_sage_sample_layer_workspace_bytes", "grapes_sage_aggregate_fwd",
-                "grapes_sage_aggregate_bwd", "grapes_sage_aggregate_workspace_bytes")
+ENTRY_POINTS = ("grapes_sage_sample_layer", "grapes_sage_sample_layer_workspace_bytes", "grapes_rootsum_aggregate_fwd",
+                "grapes_rootsum_aggregate_bwd", "grapes_rootsum_aggregate_workspace_bytes")
 UNIFORM_SEED = 2                       # the seed tests/test_sage_gpu.py fixes for its uniformity check
 
 
@@ -32,16 +32,16 @@ def test_header_table_and_both_libraries_carry_the_entry_points(built_lib):
         assert re.search(r"\b" + name + r"\s*\(", header), f"{name} is not declared in grapes_hip.h"
         assert name in built_lib.SIGNATURES, f"{name} is not in _lib.SIGNATURES"
         assert hasattr(prod, name) and hasattr(diag, name), f"{name} is not exported"
-    assert built_lib.load().grapes_abi_version() == 303
-    assert int(re.search(r"#define\s+GRAPES_ABI_VERSION\s+(\d+)", header).group(1)) == 303
+    assert built_lib.load().grapes_abi_version() == 304
+    assert int(re.search(r"#define\s+GRAPES_ABI_VERSION\s+(\d+)", header).group(1)) == 304
 
 
 def test_workspaces_are_host_calls_that_grow(built_lib):
     lib = built_lib.load()
     sizes = [lib.grapes_sage_sample_layer_workspace_bytes(m) for m in (1, 64, 4096)]
     assert sizes[0] > 0 and sizes[0] < sizes[1] < sizes[2] and sizes[2] >= 12 * 4096
-    assert lib.grapes_sage_aggregate_workspace_bytes(0, 0, 64) < lib.grapes_sage_aggregate_workspace_bytes(100, 0, 64) \
-        < lib.grapes_sage_aggregate_workspace_bytes(100, 10, 64)
+    assert lib.grapes_rootsum_aggregate_workspace_bytes(0, 0, 64) < lib.grapes_rootsum_aggregate_workspace_bytes(100, 0, 64) \
+        < lib.grapes_rootsum_aggregate_workspace_bytes(100, 10, 64)
 
 
 def test_entry_points_refuse_bad_arguments_on_the_host(built_lib):
@@ -54,10 +54,15 @@ def test_entry_points_refuse_bad_arguments_on_the_host(built_lib):
     assert lib.grapes_sage_sample_layer(one, one, 10, one, 4, None, 3, None, 0, 0, 0, None, 0, one, one, None, one, one, None,
                                         None) == -1                      # e_cap 0
     for f in (0, 1025, 260 + 1):                                         # no width, too wide, wide and not a multiple of 4
-        assert lib.grapes_sage_aggregate_fwd(one, 2048, None, 0, None, None, one, one, 1, 0, ctypes.c_void_p(32), 2048, None, 0, 4,
-                                             None, f, None, None, 0, None, None, None) == -1
-    assert lib.grapes_sage_aggregate_fwd(one, 64, None, 0, None, None, one, one, 1, 0, one, 64, None, 0, 4, None, 64, None, None, 0,
-                                         None, None, None) == -1          # out aliases src
+        assert lib.grapes_rootsum_aggregate_fwd(one, 2048, None, 0, None, None, one, one, 0.0, 0, 1, 0, ctypes.c_void_p(32), 2048, None,
+                                                0, 4, None, f, None, None, 0, None, None, None) == -1
+    assert lib.grapes_rootsum_aggregate_fwd(one, 64, None, 0, None, None, one, one, 0.0, 0, 1, 0, one, 64, None, 0, 4, None, 64, None,
+                                            None, 0, None, None, None) == -1   # out aliases src
+    for scale in (3, -1):                                                # not one of GRAPES_ROOTSUM_SCALE_*
+        assert lib.grapes_rootsum_aggregate_fwd(one, 64, None, 0, None, None, one, one, 0.0, 0, scale, 0, ctypes.c_void_p(32), 64, None,
+                                                0, 4, None, 64, None, None, 0, None, None, None) == -1
+        assert lib.grapes_rootsum_aggregate_bwd(one, 64, None, 0, None, one, one, one, 0.0, 0, scale, None, 0, ctypes.c_void_p(32), 64,
+                                                None, 0, None, 4, None, 64, None, None, 0, one, None, None) == -1
 
 
 # ---------------------------------------------------------------------------------------------------- the selection rule

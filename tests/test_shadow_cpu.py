@@ -38,7 +38,7 @@ def test_header_table_makefile_and_both_libraries_carry_the_entry_points(built_l
         assert name in built_lib.SIGNATURES, f"{name} is not in _lib.SIGNATURES"
         assert len(built_lib.SIGNATURES[name][1]) == nargs, name
         assert hasattr(prod, name) and hasattr(diag, name), f"{name} is not exported"
-    assert built_lib.load().grapes_abi_version() == 303
+    assert built_lib.load().grapes_abi_version() == 304
     makefile = open(os.path.join(ROOT, "grapes_amd", "csrc", "Makefile")).read()
     objs = re.search(r"^OBJS := (.*)$", makefile, flags=re.M).group(1).split()
     assert "build/shadow_kernels.o" in objs

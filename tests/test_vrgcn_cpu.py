@@ -220,7 +220,7 @@ def test_header_ctypes_and_exports_agree():
         args = m.group(1).strip()
         assert (0 if args in ("", "void") else len(args.split(","))) == nargs, name
         assert len(_lib.SIGNATURES[name][1]) == nargs and hasattr(lib, name), name
-    assert "#define GRAPES_ABI_VERSION 303" in src
+    assert "#define GRAPES_ABI_VERSION 304" in src
     bound = _lib.load()
     long_row = bound.grapes_vrgcn_long_row()                             # host helpers: callable without a GPU
     assert long_row == ops.VRGCN_LONG_ROW and long_row % 64 == 0 and long_row >= 64
