@@ -134,6 +134,14 @@ SIGNATURES = {
     "grapes_relu_l2norm_bwd": (I32, [P, I64, P, I64, P, P, I64, I32, I32, F32, P, I64, P]),
     "grapes_segment_mean_fwd": (I32, [P, P, I32, I32, I32, P, P, P]),
     "grapes_segment_mean_bwd": (I32, [P, P, I32, I32, I32, P, P, P]),
+    # LINKX: the adjacency embedding bag — batch tables, forward, row-sparse backward and the fused row-sparse Adam
+    "grapes_bag_batch_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_bag_batch": (I32, [P, P, I32, P, I32, P, P, I32, I32, P, P, P, P, P, P, P, P]),
+    "grapes_bag_fwd_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_bag_fwd": (I32, [P, P, I32, P, I32, P, I64, P, I32, P, I64, I32, P, P, P]),
+    "grapes_bag_bwd_workspace_bytes": (SZ, [I32, I32, I32]),
+    "grapes_bag_bwd": (I32, [P, I64, I32, P, P, I32, I32, I32, P, I64, I32, P, P, P]),
+    "grapes_bag_bwd_adam": (I32, [P, I64, I32, P, P, P, I32, I32, I32, I32, P, I64, P, P, I64, F32, F32, F32, F32, I32, P, P, P]),
     # Cluster-GCN: the cluster-union batch
     "grapes_cluster_batch_workspace_bytes": (SZ, [I32, I32]),
     "grapes_cluster_batch": (I32, [P, P, I32, P, P, P, I32, P, I32, P, I32, I32, I32, I32, P, P, P, P, P, P, P, P, P, P, P]),

@@ -14,9 +14,9 @@
 //                     a caller that reads it with n and E knows whether the backward needs its chunked form at all)
 //   pprgo_scatter_k   slot s behind its source's offset; the cursor is the histogram counted back down, so the counters end at zero
 //                     (the order inside a segment is whatever the atomics gave: the next kernel fixes it)
-//   pprgo_order_k     every segment ascending: at most 64 entries in a wavefront's registers (a bitonic network on shuffles, 21
-//                     steps), longer ones — a hub is in up to m = 4096 lists — by the workgroup in LDS on the network shadow_stage
-//                     runs; nothing ranks a segment against itself entry by entry.
+//   pprgo_order_k     every segment ascending (seg_order.h): at most 64 entries in a wavefront's registers (a bitonic network on
+//                     shuffles, 21 steps), longer ones — a hub is in up to m = 4096 lists — by the workgroup in LDS on the network
+//                     shadow_stage runs; nothing ranks a segment against itself entry by entry.
 // Integers only; two runs give the same bits.  Scratch of the caller: bits uint64[ceil(N / 64)], zero on entry and zero again on
 // return; node_map int32[N], any state on entry (it holds the ranks of this batch's ids afterwards).
 //
@@ -40,12 +40,10 @@
 // kernel alone.
 #include "hist_rows.h"
 #include "row_list.h"
+#include "seg_order.h"
 
 #define PPRGO_MAX_ROOTS 4096
 #define PPRGO_MAX_K 1024                 // K = k + 1 slots
-#define PPRGO_ORDER_THREADS 1024
-#define PPRGO_ORDER_ROWS 64              // segments one workgroup looks at per trip: four per wavefront
-#define PPRGO_SEG_MAX 4096               // the longest segment the LDS sort holds: a source is in at most m lists
 #define PPRGO_ITEM_CAP_MAX (1 << 22)
 
 __device__ __forceinline__ int pprgo_live(const int32_t* __restrict__ cnt, int b, int K) {
@@ -132,65 +130,10 @@ __global__ __launch_bounds__(256) void pprgo_scatter_k(const int32_t* __restrict
     }
 }
 
-__global__ __launch_bounds__(PPRGO_ORDER_THREADS) void pprgo_order_k(const int32_t* __restrict__ tptr, const int32_t* __restrict__ d_n,
-                                                                     int n_cap, int e_cap, int32_t* __restrict__ tslot, int32_t* status) {
-    __shared__ int keys[PPRGO_SEG_MAX];
-    __shared__ int longs[PPRGO_ORDER_ROWS];
-    __shared__ int n_long;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int n = *d_n < n_cap ? *d_n : n_cap;
-    for (int r0 = blockIdx.x * PPRGO_ORDER_ROWS; r0 < n; r0 += gridDim.x * PPRGO_ORDER_ROWS) {   // (workgroup-uniform)
-        if (tid == 0) n_long = 0;
-        __syncthreads();
-        for (int r = r0 + wid; r < n && r < r0 + PPRGO_ORDER_ROWS; r += PPRGO_ORDER_THREADS / 64) {
-            const int beg = tptr[r], end = tptr[r + 1] < e_cap ? tptr[r + 1] : e_cap, len = end - beg;
-            if (beg < 0 || len <= 1) continue;
-            if (len > 64) {
-                if (lane == 0) longs[atomicAdd(&n_long, 1)] = r;
-                continue;
-            }
-            int v = lane < len ? tslot[beg + lane] : 0x7fffffff;
-#pragma unroll
-            for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-                for (int j = k >> 1; j > 0; j >>= 1) {
-                    const int p = __shfl_xor(v, j, 64);
-                    const bool lower = (lane & j) == 0, asc = (lane & k) == 0;
-                    v = lower == asc ? (v < p ? v : p) : (v > p ? v : p);
-                }
-            }
-            if (lane < len) tslot[beg + lane] = v;
-        }
-        __syncthreads();
-        const int nl = n_long;
-        for (int q = 0; q < nl; ++q) {                                          // the long segments, each by the whole workgroup
-            const int r = longs[q];
-            const int beg = tptr[r], end = tptr[r + 1] < e_cap ? tptr[r + 1] : e_cap, len = end - beg;
-            if (len > PPRGO_SEG_MAX) {                                          // (workgroup-uniform) a slot table that lists a source twice per root
-                if (tid == 0 && status) atomicOr(status, GRAPES_STATUS_BAD_INDEX);
-                continue;
-            }
-            int P = 1;
-            while (P < len) P <<= 1;
-            for (int i = tid; i < P; i += PPRGO_ORDER_THREADS) keys[i] = i < len ? tslot[beg + i] : 0x7fffffff;
-            __syncthreads();
-            for (int kk = 2; kk <= P; kk <<= 1) {
-                for (int j = kk >> 1; j > 0; j >>= 1) {
-                    for (int i = tid; i < P; i += PPRGO_ORDER_THREADS) {
-                        const int x = i ^ j;
-                        if (x > i) {
-                            const int u = keys[i], w = keys[x];
-                            if ((u > w) == ((i & kk) == 0)) { keys[i] = w; keys[x] = u; }
-                        }
-                    }
-                    __syncthreads();
-                }
-            }
-            for (int i = tid; i < len; i += PPRGO_ORDER_THREADS) tslot[beg + i] = keys[i];
-            __syncthreads();                                                    // (keys is refilled by the next segment)
-        }
-        __syncthreads();                                                        // (n_long is reset by the next trip)
-    }
+// (seg_order.h: the pass itself, shared with bag_kernels.hip)
+__global__ __launch_bounds__(SEG_ORDER_THREADS) void pprgo_order_k(const int32_t* __restrict__ tptr, const int32_t* __restrict__ d_n,
+                                                                   int n_cap, int e_cap, int32_t* __restrict__ tslot, int32_t* status) {
+    seg_order(tptr, d_n, n_cap, e_cap, tslot, status);
 }
 
 // cur int32[n_cap] | two int32[n_cap] lists the compaction wants | counts int32[4] | the compaction's workspace
@@ -230,9 +173,7 @@ extern "C" int grapes_pprgo_batch(const int32_t* nbr, const int32_t* cnt, int32_
     hipLaunchKernelGGL(pprgo_scatter_k, dim3(grid), dim3(256), 0, s, cnt, m, K, (const int32_t*)loc, (const int32_t*)tptr, e_cap, cur,
                        tslot);
     GRAPES_LAUNCH_CHECK();
-    int og = grapes_div_up(n_cap, PPRGO_ORDER_ROWS);
-    if (og > 1024) og = 1024;
-    hipLaunchKernelGGL(pprgo_order_k, dim3(og), dim3(PPRGO_ORDER_THREADS), 0, s, (const int32_t*)tptr, (const int32_t*)d_n, n_cap, e_cap,
+    hipLaunchKernelGGL(pprgo_order_k, dim3(seg_order_grid(n_cap)), dim3(SEG_ORDER_THREADS), 0, s, (const int32_t*)tptr, (const int32_t*)d_n, n_cap, e_cap,
                        tslot, status);
     GRAPES_LAUNCH_CHECK();
     return 0;

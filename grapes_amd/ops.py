@@ -3527,6 +3527,153 @@ def pprgo_aggregate_bwd(g, w, tptr, tslot, n: int, e: int, item_cap: Optional[in
     return out
 
 
+# ------------------------------------------------------------------------------- LINKX: the adjacency embedding bag
+# [Lim et al., NeurIPS 2021; PyG-recall: LINKX, SparseLinear] (grapes_hip.h, csrc/bag_kernels.hip)
+BAG_MAX_ROWS = 4096
+BAG_ITEM_CAP_MAX = 1 << 22
+
+
+def _bag_graph(who, rowptr, col, num_nodes, rows, status):
+    N, m = _list_rows(who, rowptr, col, num_nodes, rows, None, status, int(num_nodes) < 1)
+    if m > BAG_MAX_ROWS:
+        raise ValueError(f"{who}: at most {BAG_MAX_ROWS} rows per call")
+    if col.numel() >= 2 ** 31:
+        raise ValueError(f"{who}: a graph with 2^31 or more entries is not built")
+    if col.numel() == 0:
+        col = _ws(16, rows.device)                                   # (a graph without an entry: any address, never read)
+    return N, m, col
+
+
+def bag_batch(rowptr, col, num_nodes: int, rows, scratch, u_cap: int, e_cap: int, status=None, out=None):
+    """(bptr int32 [m + 1], uniq int32 [u_cap], tptr int32 [u_cap + 1], trow int32 [e_cap], counts int32 [4]) of grapes_bag_batch over
+    the rows `rows` of the CSR: the prefix of their stored lengths, the ascending distinct column ids, and per column the batch rows
+    that store it, ascending; counts = (n_u, e, the longest segment, the longest row) — the TRUE totals also past a capacity, which
+    raises the status bits and leaves the tables incomplete: the caller retries with them (modules.linkx.BagBatcher).  scratch:
+    ops.pprgo_scratch(N, device) (or a DeviceGraph's bits and node_map): the bitmap zero on entry and on return.  The rule is in
+    grapes_hip.h.  out: the five tensors to write."""
+    N, m, col = _bag_graph("bag_batch", rowptr, col, num_nodes, rows, status)
+    bits, node_map = scratch
+    _chk(bits, _i64, "scratch bits"); _chk(node_map, _i32, "scratch node_map")
+    if bits.numel() < (N + 63) // 64 or node_map.numel() < N:
+        raise ValueError("bag_batch: scratch is ops.pprgo_scratch(num_nodes, device)")
+    uc, ec, dev = int(u_cap), int(e_cap), rows.device
+    if uc < 1 or ec < 1:
+        raise ValueError("bag_batch: u_cap and e_cap are at least 1")
+    if out is None:
+        i32 = lambda *shape: torch.empty(shape, dtype=_i32, device=dev)
+        out = (i32(m + 1), i32(uc), i32(uc + 1), i32(ec), i32(4))
+    bptr, uniq, tptr, trow, counts = out
+    for t, name in ((bptr, "bptr"), (uniq, "uniq"), (tptr, "tptr"), (trow, "trow"), (counts, "counts")):
+        _chk(t, _i32, name)
+    if bptr.numel() < m + 1 or uniq.numel() < uc or tptr.numel() < uc + 1 or trow.numel() < ec or counts.numel() < 4:
+        raise ValueError("bag_batch: bptr holds m + 1 values, uniq u_cap, tptr u_cap + 1, trow e_cap, counts 4")
+    ws = _ws(lib().grapes_bag_batch_workspace_bytes(m, uc, N), dev)
+    _lib.check(lib().grapes_bag_batch(_p(rowptr), _p(col), N, _p(rows), m, _p(bits), _p(node_map), uc, ec, _p(bptr), _p(uniq), _p(tptr),
+                                      _p(trow), _p(counts), _p(ws), _p(status), _stream()), "bag_batch")
+    return bptr, uniq, tptr, trow, counts
+
+
+def bag_fwd_item_cap(e: int, row_max: Optional[int] = None) -> int:
+    """A bound on the chunks behind the first of the rows longer than VRGCN_LONG_ROW among e entries (such a row of L entries has
+    ceil(L / 64) - 1 <= L / 64); 0 where the longest row, if known, is no long row."""
+    if row_max is not None and int(row_max) <= VRGCN_LONG_ROW:
+        return 0
+    return min(int(e) // VRGCN_LONG_ROW, BAG_ITEM_CAP_MAX)
+
+
+def bag_bwd_item_cap(e: int, seg_max: Optional[int] = None) -> int:
+    """A bound on the chunks of the segments longer than VRGCN_LONG_ROW among e entries, the first chunk included (such a segment of
+    L >= 65 entries has ceil(L / 64) <= L / 32); 0 where the longest segment, if known, is not long."""
+    if seg_max is not None and int(seg_max) <= VRGCN_LONG_ROW:
+        return 0
+    return min(int(e) // (VRGCN_LONG_ROW // 2), BAG_ITEM_CAP_MAX)
+
+
+def bag_fwd(rowptr, col, num_nodes: int, rows, weight, bias=None, item_cap: Optional[int] = None, status=None, out=None):
+    """out fp32 [m, H]: out[b] = bias + sum of weight[col[t]] over the stored entries of row rows[b], in stored order — LINKX's
+    adjacency embedding (grapes_bag_fwd).  weight fp32 [N, H], rows any leading dimension apart; an empty row gives bias.  item_cap:
+    the room for the long rows' chunks; the default reads the rows' entry count from the device (one host read) — a caller who
+    knows the batch's entries and longest row passes ops.bag_fwd_item_cap of them.  A fixed order of additions, no atomics."""
+    N, m, col = _bag_graph("bag_fwd", rowptr, col, num_nodes, rows, status)
+    if weight is None or weight.dim() != 2 or weight.shape[0] != N:
+        raise ValueError("bag_fwd: weight is [N, H]")
+    H = int(weight.shape[1])
+    ld_w = _strided_rows(weight, "weight", N, H)
+    _gather_width(H, "bag_fwd")
+    if bias is not None:
+        _chk(bias, _f32, "bias")
+        if bias.numel() != H:
+            raise ValueError("bag_fwd: bias holds H values")
+    if out is None:
+        out = torch.empty((m, H), dtype=_f32, device=rows.device)
+    ld_out = _strided_rows(out, "out", m, H)
+    if item_cap is None:                                             # (one host read: the rows' entries)
+        r = rows.long().clamp(0, N - 1)
+        item_cap = bag_fwd_item_cap(int((rowptr[r + 1] - rowptr[r]).sum()))
+    ic = int(item_cap)
+    if not 0 <= ic <= BAG_ITEM_CAP_MAX:
+        raise ValueError(f"bag_fwd: item_cap is 0 .. {BAG_ITEM_CAP_MAX}")
+    ws = _ws(lib().grapes_bag_fwd_workspace_bytes(m, ic, H), rows.device)
+    _lib.check(lib().grapes_bag_fwd(_p(rowptr), _p(col), N, _p(rows), m, _p(weight), ld_w, _p(bias), H, _p(out), ld_out, ic, _p(ws),
+                                    _p(status), _stream()), "bag_fwd")
+    return out
+
+
+def _bag_segments(who, g, tptr, trow, n_u, e, item_cap, status):
+    _chk(tptr, _i32, "tptr"); _chk(trow, _i32, "trow"); _chk(status, _i32, "status", True)
+    n_u, e = int(n_u), int(e)
+    if g is None or g.dim() != 2 or not 1 <= g.shape[0] <= BAG_MAX_ROWS or n_u < 1 or e < 0 or tptr.numel() < n_u + 1 or trow.numel() < e:
+        raise ValueError(f"{who}: g is [m, H] with 1 <= m <= {BAG_MAX_ROWS}, n_u >= 1, tptr holds n_u + 1 values and trow e")
+    m, H = int(g.shape[0]), int(g.shape[1])
+    ld_g = _strided_rows(g, "g", m, H)
+    _gather_width(H, who)
+    ic = bag_bwd_item_cap(e) if item_cap is None else int(item_cap)
+    if not 0 <= ic <= BAG_ITEM_CAP_MAX:
+        raise ValueError(f"{who}: item_cap is 0 .. {BAG_ITEM_CAP_MAX}")
+    return n_u, e, m, H, ld_g, ic
+
+
+def bag_bwd(g, tptr, trow, n_u: int, e: int, item_cap: Optional[int] = None, status=None, out=None):
+    """values fp32 [n_u, H] of the row-sparse gradient of bag_fwd's weight from g = d out [m, H]: values[s] = the sum of g[trow[q]]
+    over segment s in segment order; uniq[:n_u] are its indices (grapes_bag_bwd).  item_cap: the room for long segments' chunks,
+    default ops.bag_bwd_item_cap(e), which cannot overflow.  No float atomics."""
+    n_u, e, m, H, ld_g, ic = _bag_segments("bag_bwd", g, tptr, trow, n_u, e, item_cap, status)
+    if out is None:
+        out = torch.empty((n_u, H), dtype=_f32, device=g.device)
+    ld_o = _strided_rows(out, "values", n_u, H)
+    ws = _ws(lib().grapes_bag_bwd_workspace_bytes(n_u, ic, H), g.device)
+    _lib.check(lib().grapes_bag_bwd(_p(g), ld_g, m, _p(tptr), _p(trow), n_u, e, H, _p(out), ld_o, ic, _p(ws), _p(status), _stream()),
+               "bag_bwd")
+    return out
+
+
+def bag_adam_step_size(lr: float, beta1: float, beta2: float, t: int) -> float:
+    """torch.optim.SparseAdam's step size at step t >= 1, in double: lr sqrt(1 - beta2^t) / (1 - beta1^t)."""
+    import math
+    return float(lr) * math.sqrt(1.0 - float(beta2) ** int(t)) / (1.0 - float(beta1) ** int(t))
+
+
+def bag_bwd_adam(g, tptr, trow, uniq, n_u: int, e: int, weight, exp_avg, exp_avg_sq, lr: float, beta1: float, beta2: float, eps: float,
+                 t: int, item_cap: Optional[int] = None, status=None):
+    """The backward of bag_fwd and torch.optim.SparseAdam's update of the touched rows in one pass (grapes_bag_bwd_adam): no gradient
+    is written; rows uniq[:n_u] of weight, exp_avg and exp_avg_sq [N, H] are updated in place with the segment sums, every other row
+    is neither read nor written (lazy semantics).  t >= 1 is the number of this call, not of a row's touches.  Returns weight."""
+    n_u, e, m, H, ld_g, ic = _bag_segments("bag_bwd_adam", g, tptr, trow, n_u, e, item_cap, status)
+    _chk(uniq, _i32, "uniq")
+    if weight is None or weight.dim() != 2 or weight.shape[1] != H or uniq.numel() < n_u or int(t) < 1:
+        raise ValueError("bag_bwd_adam: weight is [N, H] like g's width, uniq holds n_u ids and t is at least 1")
+    N = int(weight.shape[0])
+    ld_w = _strided_rows(weight, "weight", N, H)
+    ld_a, ld_b = _strided_rows(exp_avg, "exp_avg", N, H), _strided_rows(exp_avg_sq, "exp_avg_sq", N, H)
+    if ld_a != ld_b:
+        raise ValueError("bag_bwd_adam: exp_avg and exp_avg_sq share one leading dimension")
+    ws = _ws(lib().grapes_bag_bwd_workspace_bytes(n_u, ic, H), g.device)
+    _lib.check(lib().grapes_bag_bwd_adam(_p(g), ld_g, m, _p(tptr), _p(trow), _p(uniq), n_u, e, N, H, _p(weight), ld_w, _p(exp_avg),
+                                         _p(exp_avg_sq), ld_a, 1.0 - float(beta1), 1.0 - float(beta2), float(eps),
+                                         bag_adam_step_size(lr, beta1, beta2, t), ic, _p(ws), _p(status), _stream()), "bag_bwd_adam")
+    return weight
+
+
 # ------------------------------------------------------------------------------- PinSAGE: random-walk importance neighbourhoods
 # [Ying et al., KDD 2018 — recalled; DGL-recall: RandomWalkNeighborSampler / PinSAGESampler] (grapes_hip.h, csrc/pinsage_kernels.hip)
 PINSAGE_MAX_VISITS = 1024                    # V = R L, the visit slots of one root

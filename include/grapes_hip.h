@@ -74,7 +74,8 @@ extern "C" {
  * grapes_relu_l2norm_fwd / _bwd.
  * 304: grapes_sage_aggregate_fwd / _bwd and grapes_cluster_aggregate_fwd / _bwd were one layer written twice and left, with their two
  * _workspace_bytes: grapes_rootsum_aggregate_fwd / _bwd (loops, self_weight, self_term, scale) and
- * grapes_rootsum_aggregate_workspace_bytes compute both. */
+ * grapes_rootsum_aggregate_workspace_bytes compute both; added within 304 (no signature of an earlier entry point changed): LINKX's
+ * adjacency embedding bag — grapes_bag_batch, grapes_bag_fwd, grapes_bag_bwd (+ _workspace_bytes each), grapes_bag_bwd_adam. */
 #define GRAPES_ABI_VERSION 304
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -1879,6 +1880,67 @@ int grapes_relu_l2norm_bwd(const float* g, int64_t ld_g, const float* out, int64
  * counts as empty.  One launch each. */
 int grapes_segment_mean_fwd(const float* h, const int32_t* ptr, int32_t num_segments, int32_t n_rows, int32_t f, float* out, int32_t* status, grapes_stream_t stream);
 int grapes_segment_mean_bwd(const float* g, const int32_t* ptr, int32_t num_segments, int32_t n_rows, int32_t f, float* dh, int32_t* status, grapes_stream_t stream);
+
+/* ------------------------------------------------------------------ LINKX: the adjacency embedding bag (csrc/bag_kernels.hip)
+ * [Lim et al., NeurIPS 2021; PyG-recall: LINKX, SparseLinear].  A node's row of the adjacency matrix is a feature vector of length N
+ * pushed through a learned table W fp32 [N, H]:  h_A[i] = b + sum_{t in row(i)} W[col[t]].  Nothing is sampled; a batch is m rows of A.
+ * The graph is the CSR as stored (rowptr int64[N + 1], col int32, fewer than 2^31 entries): directed graphs are allowed, and
+ * duplicates and loops count as often as they are stored.
+ * grapes_bag_batch — the batch tables of rows[m], 1 <= m <= 4096; ids may repeat, each occurrence is its own batch row.  Integers only:
+ *   bptr int32[m + 1]   the exclusive prefix of the batch rows' stored lengths in batch order; bptr[m] = e, the TRUE total whatever e_cap
+ *   uniq int32[n_u]     the distinct column ids over all batch rows, ascending
+ *   tptr int32[n_u + 1], trow int32[e]   for column uniq[s] the batch-row indices b whose row stores it, ASCENDING in b; a column
+ *                       stored c times in one row appears c times, adjacent
+ *   d_counts int32[4]   (n_u, e, the longest segment, the longest batch row): the TRUE totals also past a capacity.  e = bptr[m]
+ *                       counts every stored entry; tptr[n_u] counts the entries that sit in a segment.  The two are equal unless
+ *                       GRAPES_STATUS_BAD_INDEX was raised for a column id (such an entry is in no segment: tptr[n_u] < e) or a
+ *                       capacity was passed
+ * More than u_cap distinct columns raise GRAPES_STATUS_NODE_OVERFLOW, more than e_cap entries GRAPES_STATUS_EDGE_OVERFLOW: nothing is
+ * written at or past a capacity (uniq holds u_cap ids, tptr u_cap + 1 offsets clamped to e_cap, trow e_cap values), the structure is
+ * then incomplete, and the caller retries with the totals d_counts reports.  A row id outside [0, N) raises GRAPES_STATUS_BAD_INDEX
+ * and is an empty row; so does a column id outside [0, N), which is in no segment, and a column stored more than 4096 times over
+ * the batch, whose segment stays unordered.
+ * The caller's scratch: bits uint64[ceil(N / 64)], ZERO on entry and zero again on return; node_map int32[N], any state on entry —
+ * the entries this call wrote (those of uniq) are put back to 0, so a map that was zero is returned zero.  Two runs give the same
+ * bits.  workspace: grapes_bag_batch_workspace_bytes(m, u_cap, num_nodes) bytes, 4-byte aligned. */
+size_t grapes_bag_batch_workspace_bytes(int32_t m, int32_t u_cap, int32_t num_nodes);
+int grapes_bag_batch(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* rows, int32_t m, uint64_t* bits, int32_t* node_map, int32_t u_cap, int32_t e_cap, int32_t* bptr, int32_t* uniq, int32_t* tptr, int32_t* trow, int32_t* d_counts, void* workspace, int32_t* status, grapes_stream_t stream);
+/* grapes_bag_fwd: out[b, :h] = bias + sum_t W[col[t], :h] over the stored entries t of row rows[b], b < m, in stored order: the
+ * accumulator starts at bias (0 without one) and the rows are added one after the other.  W rows ld_w floats apart, out ld_out.
+ * Widths as the row gathers: h % 4 == 0 up to 1024 where W, out and bias are 16-byte aligned with ld % 4 == 0, any h up to 256 otherwise
+ * (GRAPES_EALIGN where alignment alone stands in the way).  item_cap > 0: a row of more than grapes_vrgcn_long_row() entries is cut
+ * into chunks of that many, one group of lanes each; chunk 0 starts at bias, the further chunks at 0, and their partial sums are added
+ * to chunk 0's in chunk order.  item_cap bounds the chunks behind the first (at most 2^22; more raise GRAPES_STATUS_EDGE_OVERFLOW);
+ * 0: every row by one group.  An empty row gives bias; so does a row id outside [0, N), which raises GRAPES_STATUS_BAD_INDEX; a column
+ * id outside [0, N) raises it and is dropped.  No float atomics, two runs give the same bits.
+ * workspace: grapes_bag_fwd_workspace_bytes(m, item_cap, h) bytes, 16-byte aligned (may be NULL with item_cap = 0). */
+size_t grapes_bag_fwd_workspace_bytes(int32_t m, int32_t item_cap, int32_t h);
+int grapes_bag_fwd(const int64_t* rowptr, const int32_t* col, int32_t num_nodes, const int32_t* rows, int32_t m, const float* w, int64_t ld_w, const float* bias, int32_t h, float* out, int64_t ld_out, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
+/* The backward over the batch tables, G = d out fp32 [m, h] (rows ld_g apart):  g_s = sum_{q in [tptr[s], tptr[s + 1])} G[trow[q]]
+ * for every s < n_u, in segment order and COMPENSATED: with the sum S = 0 and its error term c = 0, every entry x does
+ * y = x - c; t = S + y; c = (t - S) - y; S = t (Kahan), each operation rounded once to fp32, and g_s = S.  item_cap > 0: a segment of
+ * more than grapes_vrgcn_long_row() entries is cut into chunks of that many, each summed so by its own group, and the chunks' sums are
+ * added in chunk order by the same rule from (0, 0); item_cap bounds the chunks of such segments, the first included (at most 2^22;
+ * floor(e / 32) cannot overflow).  The compensation is what keeps a long segment's sum within an ulp of the exact one: the plain
+ * fixed-order sum of 300 entries measured up to 12.7 times the error of a correctly rounded fp32 sum in the update below.
+ * The argument e of the two calls bounds what is read of trow: every segment must lie inside [0, e], else it is refused with
+ * GRAPES_STATUS_BAD_INDEX and counts as empty.  tptr[n_u] is the exact value; grapes_bag_batch's e = bptr[m] is never below it, and
+ * trow holds at least that many values, so either may be passed.  No float atomics; widths and alignment as the forward.
+ *   grapes_bag_bwd       grad[s, :h] = g_s: the values of the row-sparse gradient of W whose indices are uniq.
+ *   grapes_bag_bwd_adam  writes no gradient.  With g = g_s in registers, row j = uniq[s] of W (p), exp_avg (m) and exp_avg_sq (v) is
+ *                        read once and written once, each operation rounded once to fp32 (no contraction), IEEE sqrtf and division:
+ *                            m' = m + one_minus_beta1 (g - m);   v' = v + one_minus_beta2 (g g - v);
+ *                            p' = p - step_size (m' / (sqrtf(v') + eps))
+ *                        which is torch.optim.SparseAdam's rule with step_size = lr sqrt(1 - beta2^t) / (1 - beta1^t) formed by the
+ *                        caller in double and passed as one fp32; t counts calls, not touches.  LAZY semantics: rows outside uniq are
+ *                        neither read nor written — their moments do not decay.  A row is updated exactly once: uniq is
+ *                        duplicate-free, a short segment is finished by the rows kernel and a long one by the combine pass.  An
+ *                        entry of uniq outside [0, N) raises GRAPES_STATUS_BAD_INDEX and is skipped.  exp_avg and exp_avg_sq rows
+ *                        are ld_state floats apart.
+ * workspace: grapes_bag_bwd_workspace_bytes(n_u, item_cap, h) bytes, 16-byte aligned (may be NULL with item_cap = 0). */
+size_t grapes_bag_bwd_workspace_bytes(int32_t n_u, int32_t item_cap, int32_t h);
+int grapes_bag_bwd(const float* g, int64_t ld_g, int32_t m, const int32_t* tptr, const int32_t* trow, int32_t n_u, int32_t e, int32_t h, float* grad, int64_t ld_grad, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
+int grapes_bag_bwd_adam(const float* g, int64_t ld_g, int32_t m, const int32_t* tptr, const int32_t* trow, const int32_t* uniq, int32_t n_u, int32_t e, int32_t num_nodes, int32_t h, float* w, int64_t ld_w, float* exp_avg, float* exp_avg_sq, int64_t ld_state, float one_minus_beta1, float one_minus_beta2, float eps, float step_size, int32_t item_cap, void* workspace, int32_t* status, grapes_stream_t stream);
 
 /* ------------------------------------------------------------------ Cluster-GCN: cluster-union batches (csrc/cluster_kernels.hip)
  * [Chiang et al., KDD 2019; PyG-recall: ClusterData, ClusterLoader, ClusterGCNConv].  The graph is cut into P clusters once; a batch is
