@@ -253,6 +253,7 @@ SIGNATURES = {
     "grapes_linear_bwd_weight_slabs_bytes": (SZ, [I32, I32, I32]),
     "grapes_linear_bwd_weight_slabs": (I32, [P, P, P, I32, P, I32, I32, I32, P, P]),
     "grapes_linear_bwd_weight_slabs_and_input": (I32, [P, P, P, P, P, I32, P, I32, I32, I32, P, P]),
+    "grapes_linear_bwd_weight_slabs_multi": (I32, [I32, P, P, P, I32, P, P, P, P, P, P]),
     "grapes_slab_reduce_sets": (I32, [I32, P, P, P, I32, P, I32, P]),
     "grapes_gcn_aggregate_narrow_pair": (I32, [P, P, P, P, P, P, P, P, P, I32, P, P]),
     "grapes_linear_relu_head_fwd_bits": (I32, [P, I32, P, P, P, P, P, I32, P, I32, I32, P]),
@@ -276,6 +277,8 @@ SIGNATURES = {
     "grapes_gcn_aggregate_bwd_rank1_bits_multi": (I32, [I32, P, P, P, P, P, P, P, P, P, P, P, P, P, I32, P, P, P, P, P]),
     "grapes_gcn_aggregate_bwd_workspace_bytes": (SZ, [I32, I32]),
     "grapes_gcn_aggregate_bwd": (I32, [P, P, P, P, P, P, P, P, I32, I32, P, I32, P, P, I32, P, P, P]),
+    "grapes_gcn_aggregate_bwd_input_available": (I32, [P, P, P, I32, I32, I32]),
+    "grapes_gcn_aggregate_bwd_input": (I32, [P, P, P, P, P, P, P, P, P, I32, I32, P, I32, I32, P, P, P]),
     "grapes_sampler_workspace_bytes": (SZ, [I32]),
     "grapes_gumbel_topk": (I32, [P, P, P, U64, U64, P, I32, P, I32, I32, P, P, P, P, P, P, P, P, P, I32, P, P, P, P]),
     "grapes_gumbel_topk_hist": (I32, [P, P, P, U64, U64, P, I32, P, I32, I32, P, P, P, P, P, P, P, P, P, I32, P, P, P, P, P]),

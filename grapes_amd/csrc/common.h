@@ -433,7 +433,8 @@ __device__ __forceinline__ void draw_finish_body(const grapes_draw_finish_args& 
 #include <string.h>
 enum GrapesRiderKind { GRAPES_RK_OTHER = 0, GRAPES_RK_EXPAND, GRAPES_RK_COMPACT, GRAPES_RK_FILL, GRAPES_RK_SORT, GRAPES_RK_GATHER,
                        GRAPES_RK_BEGIN /* grapes_step_begin: rides as one extra workgroup of an expansion, also while the rest is held */,
-                       GRAPES_RK_AGGBWD /* few-row backward aggregation (variant = vector width): rides in the sampler heads' backward launches */ };
+                       GRAPES_RK_AGGBWD /* few-row backward aggregation (variant = vector width): rides in the sampler heads' backward launches */,
+                       GRAPES_RK_AGGBWD_DX /* ... with the layer's input gradient formed from its rows (grapes_gcn_aggregate_bwd_input): same hosts */ };
 struct GrapesRiderRecord {
     int kind = GRAPES_RK_OTHER, variant = 0, grid = 0, block = 0;
     size_t arg_bytes = 0;

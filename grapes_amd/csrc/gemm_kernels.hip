@@ -1603,6 +1603,23 @@ __global__ __launch_bounds__(SK_T) void gemm_dw_small_dx_pair_k(DwSmallArgs a, S
         gemm_skinny_body<true>(b.A, b.B, b.C, n_host, d_n, b.N, b.K, b.lda, b.ldb, b.ldc, nullptr, 0, j % nb_x, j / nb_x, sk_smem);
     }
 }
+// The few-row weight-gradient slabs of up to DWS_MULTI_MAX layers over the SAME rows side by side in one launch (the end of the
+// classifier's backward pass, once every layer's dT is known): problem q owns the workgroups [start[q], start[q + 1]), each runs
+// gemm_dw_small_body as gemm_dw_small_k would.  Same slabs, same values.
+#define DWS_MULTI_MAX 4
+struct DwSmallSet { int count; DwSmallArgs p[DWS_MULTI_MAX]; int na_x[DWS_MULTI_MAX]; int start[DWS_MULTI_MAX + 1]; };
+__global__ __launch_bounds__(SK_T) void gemm_dw_small_multi_k(DwSmallSet st, int n_host, const int32_t* d_n) {
+    __shared__ __attribute__((aligned(16))) float dws_smem[DWS_SMEM_FLOATS];
+    const int id = blockIdx.x;
+    int q = 0;
+#pragma unroll
+    for (int u = 1; u < DWS_MULTI_MAX; ++u) if (u < st.count && id >= st.start[u]) q = u;
+#define DSEL(f) (q == 0 ? st.f[0] : (q == 1 ? st.f[1] : (q == 2 ? st.f[2] : st.f[3])))
+    const DwSmallArgs a = DSEL(p);
+    const int na_x = DSEL(na_x), j = id - DSEL(start);
+#undef DSEL
+    gemm_dw_small_body(a.A, a.gate, a.X, a.slabs, a.cs_slabs, n_host, d_n, a.M, a.N, a.lda, a.ldb, j % na_x, j / na_x, dws_smem);
+}
 static inline int dw_nslab(int f_out, int f_in);
 static inline bool dw_small_ok(int n, int f_out, int f_in) {
     return n <= 4096 && grapes_div_up(n, DWS_ROWS) <= dw_nslab(f_out, f_in);
@@ -1710,6 +1727,35 @@ extern "C" int grapes_linear_bwd_weight_slabs_and_input(const float* dout, const
     SkinnyArgs b{dout, w, dx, f_in, f_out, (long long)f_out, (long long)f_in, (long long)f_in};
     hipLaunchKernelGGL(gemm_dw_small_dx_pair_k, dim3(na_x * na_y + nb_x * nb_y), dim3(SK_T), lds_use, (hipStream_t)stream, a, b, n, d_n,
                        na_x, na_y, nb_x);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}
+/* grapes_linear_bwd_weight_slabs for 1..4 layers over the same n rows (one d_n) in ONE launch: problem q = (dout[q], gate[q] or
+ * NULL, x[q], f_in[q], f_out[q], want_bias[q], workspace[q]), each exactly as that entry point takes them.  GRAPES_EINVAL when a
+ * shape is not one of the few-row kernel (nothing is launched then). */
+extern "C" int grapes_linear_bwd_weight_slabs_multi(int32_t count, const float* const* dout, const float* const* gate,
+                                                    const float* const* x, int32_t n, const int32_t* d_n, const int32_t* f_in,
+                                                    const int32_t* f_out, const int32_t* want_bias, void* const* workspace,
+                                                    grapes_stream_t stream) {
+    if (count < 1 || count > DWS_MULTI_MAX || !dout || !gate || !x || !f_in || !f_out || !want_bias || !workspace || n <= 0)
+        return GRAPES_EINVAL;
+    DwSmallSet st{}; st.count = count;
+    const size_t ns = (size_t)grapes_div_up(n, DWS_ROWS);
+    int total = 0;
+    for (int q = 0; q < DWS_MULTI_MAX; ++q) {
+        const int r = q < count ? q : 0;
+        if (q < count) {
+            if (f_in[r] <= 0 || f_out[r] <= 1 || !dout[r] || !x[r] || !workspace[r] || !dw_small_ok(n, f_out[r], f_in[r])) return GRAPES_EINVAL;
+        }
+        float* w_dw = (float*)workspace[r];
+        float* w_db = w_dw + ns * (size_t)f_in[r] * f_out[r];
+        st.p[q] = DwSmallArgs{dout[r], gate[r], x[r], w_dw, want_bias[r] ? w_db : nullptr, f_out[r], f_in[r], (long long)f_out[r], (long long)f_in[r]};
+        st.na_x[q] = grapes_div_up(f_out[r], SK_ROWS) * grapes_div_up(f_in[r], SK_COLS);
+        st.start[q] = total;
+        if (q < count) total += st.na_x[q] * (int)ns;
+    }
+    st.start[DWS_MULTI_MAX] = total;
+    hipLaunchKernelGGL(gemm_dw_small_multi_k, dim3(total), dim3(SK_T), 0, (hipStream_t)stream, st, n, d_n);
     GRAPES_LAUNCH_CHECK();
     return 0;
 }

@@ -1860,6 +1860,207 @@ __global__ __launch_bounds__(256) void gcn_aggregate_bwd_small_k(AggBwdSmallArgs
     gcn_aggregate_bwd_small_body<VEC>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 
+// ---- The few-row backward aggregation WITH the layer's input gradient:  dT = Â^T (dout (.) [relu_out > 0]) as above, and
+// dX[n, N] = dT · W  (W [F][N], rows are k) from the rows while the workgroup holds them.  dX is row-local on dT, and W depends on
+// nothing in the backward chain: a workgroup owns one 32-row x 64-column tile of dX (the tile of gemm_skinny_body<true>,
+// gemm_kernels.hip), requests its part of W at once, forms its 32 rows of dT into the A image in LDS and runs that body's tile
+// arithmetic on them: four K quarters — one per wavefront, both column halves — each an ascending chain of 32x32x2 fp32 MFMAs,
+// combined as ((q0 + q1) + q2) + q3.  Every element of dT and dX is therefore the same bits as from the two launches.  The
+// workgroups of one row tile (one per column tile of dX) each repeat its aggregation (a few KB of L2 hits); column tile 0 stores dT.
+//   The rows of a wavefront (8 of the tile) are not walked one after the other — that would be 8 x (row pointer -> source ->
+// gathered row) dependent trips: the wavefront flattens them into ITEMS (a row's sources in CSR order, then the row itself), one
+// lane per item loads its source index and weight, and the items are then taken in order, AD_IB gathered rows in flight, each
+// row's fmaf chain exactly gcn_aggregate_bwd_small_body's (sources in CSR order, the row's own term last).
+#define AD_ROWS 32                  // = SK_ROWS, SK_COLS, SK_LDA of gemm_kernels.hip
+#define AD_COLS 64
+#define AD_LDA (2 * AD_ROWS + 2)
+#define AD_PS_FLOATS (4 * 2 * 16 * 64)
+typedef float ad_f32x16 __attribute__((ext_vector_type(16)));
+struct AggBwdDxArgs { AggBwdSmallArgs a; const float* W; float* dx; int N; };
+static inline size_t agg_bwd_dx_lds_bytes(int F) {
+    const size_t img = (size_t)((F + 3) / 4) * 2 * AD_LDA;
+    return (img > AD_PS_FLOATS ? img : (size_t)AD_PS_FLOATS) * sizeof(float);
+}
+static inline int agg_bwd_dx_grid(const AggBwdDxArgs& p) {
+    return (p.a.dbias ? p.a.ncb * p.a.R : 0) + grapes_div_up(p.a.n_host, AD_ROWS) * grapes_div_up(p.N, AD_COLS);
+}
+// (BID: this problem's workgroup index — the launch's own, or its share of a pair launch; indices past the problem's count return)
+template <int VEC>
+__device__ __forceinline__ void gcn_aggregate_bwd_dx_body(const AggBwdDxArgs& p, int BID, float* __restrict__ smem) {
+    const AggBwdSmallArgs& a = p.a;
+    const int F = a.F, N = p.N;
+    const int ncs = a.dbias ? a.ncb * a.R : 0;
+    if (BID < ncs) {
+        colsum_ticket_body(a.dout, a.gate, nullptr, nullptr, a.partials, a.dbias, a.n_host, a.d_n, F, a.accumulate_bias, a.ticket,
+                           BID % a.ncb, BID / a.ncb, a.R);
+        return;
+    }
+    constexpr int PER = VEC == 4 ? 16 : 4;          // k-groups of four per K quarter: F <= 256 / F <= 64
+    constexpr int IB = VEC == 4 ? 4 : 8;            // gathered rows in flight
+    const int nct = (N + AD_COLS - 1) / AD_COLS;
+    const int id = BID - ncs;
+    const int rt = id / nct, ctile = id - rt * nct;
+    const int m0 = rt * AD_ROWS, n0 = ctile * AD_COLS;
+    if (m0 >= a.n_host) return;                      // (uniform) padding of a pair launch's grid
+    const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int li = lane & 31, h = lane >> 5;
+    const int KQ = (F + 3) >> 2;
+    const int per = (KQ + 3) >> 2;
+    const int kq0 = wid * per, kq1 = (kq0 + per < KQ) ? kq0 + per : KQ;
+    const float* __restrict__ W = p.W;
+    // ---- this wavefront's K quarter of the W tile, both column halves: requested first, used after the aggregation (addresses
+    // clamped inside W, the values outside the tile replaced by zero where they are used)
+    float bx[PER][2], by[PER][2];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+        const int kq = kq0 + i < KQ ? kq0 + i : KQ - 1;
+        const int k0 = 4 * kq + h, k1 = k0 + 2;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            const int gn = n0 + 32 * c + li;
+            const int gc = gn < N ? gn : 0;
+            bx[i][c] = W[(long long)(k0 < F ? k0 : 0) * N + gc];
+            by[i][c] = W[(long long)(k1 < F ? k1 : 0) * N + gc];
+        }
+    }
+    const int n = eff_count(a.d_n, a.n_host);
+    if (m0 >= n) return;                             // (uniform)
+    const float* __restrict__ dout = a.dout;
+    const int32_t* __restrict__ rowptr = a.rowptr; const int32_t* __restrict__ csr = a.csr; const float* __restrict__ dinv = a.dinv;
+    const bool has_g = a.gate != nullptr;
+    const float* __restrict__ gp = has_g ? a.gate : a.dout;       // (an absent gate is read from dout and ignored: no branch between the loads)
+    float* As = smem;                                // [KQ][2][32][2 (+pad)]: element (m, k) -> As[((k>>2)*2 + (k&1)) * AD_LDA + m*2 + ((k>>1)&1)]
+    const int f0 = lane * VEC;
+    const bool fl = f0 < F;
+    const int fc = fl ? f0 : 0;
+    // ---- the wavefront's rows m0 + wid + 4 i: bounds and scales of all eight in one trip
+    int beg[8], P[9]; float dc[8];
+    P[0] = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int r = m0 + wid + 4 * i;
+        const bool ok = r < n;
+        const int rc = ok ? r : 0;
+        const int b = rowptr[rc], e = rowptr[rc + 1];
+        dc[i] = dinv[rc];
+        beg[i] = b;
+        P[i + 1] = P[i] + (ok ? e - b + 1 : 0);      // a row's items: its sources, then itself
+    }
+    const int L = P[8];
+    auto emit = [&](int m, const float (&v)[VEC]) {
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) {
+            const int k = f0 + q;
+            if (k < KQ * 4) As[((k >> 2) * 2 + (k & 1)) * AD_LDA + m * 2 + ((k >> 1) & 1)] = v[q];
+        }
+        if (ctile == 0 && fl) {
+            float* o = a.dh + (long long)(m0 + m) * F + f0;
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) o[q] = v[q];
+        }
+    };
+    float acc[VEC];
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) acc[q] = 0.f;
+    for (int c0 = 0; c0 < L; c0 += 64) {
+        // lane -> item c0 + lane: its row (the last i with P[i] <= t), source and weight
+        const int t = c0 + lane;
+        int ri = 0, base = 0, rb = beg[0]; float rdc = dc[0];
+#pragma unroll
+        for (int i = 1; i < 8; ++i)
+            if (t >= P[i]) { ri = i; base = P[i]; rb = beg[i]; rdc = dc[i]; }
+        int rend = P[1];
+#pragma unroll
+        for (int i = 1; i < 8; ++i) if (ri == i) rend = P[i + 1];
+        const bool live = t < L;
+        const bool self = live && t == rend - 1;
+        const bool nb = live && !self;
+        int s = nb ? csr[rb + (t - base)] : (live ? m0 + wid + 4 * ri : 0);
+        float w = rdc * rdc;
+        if (nb) w = dinv[s] * rdc;
+        const int meta = ri | (self ? 8 : 0);
+        const int cnt = L - c0 < 64 ? L - c0 : 64;
+        for (int b0 = 0; b0 < cnt; b0 += IB) {
+            float val[IB][VEC], g[IB][VEC];
+#pragma unroll
+            for (int u = 0; u < IB; ++u) {
+                const int l = b0 + u < cnt ? b0 + u : b0;          // (past the last item: the batch's first row again, not added)
+                const int su = __builtin_amdgcn_readlane(s, l);
+                ld_vec<VEC>(dout + (long long)su * F + fc, val[u]);
+                ld_vec<VEC>(gp + (long long)su * F + fc, g[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < IB; ++u) {
+                if (b0 + u < cnt) {                                // (uniform)
+                    const float wu = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w), b0 + u));
+                    const int mu = __builtin_amdgcn_readlane(meta, b0 + u);
+#pragma unroll
+                    for (int q = 0; q < VEC; ++q) {
+                        const float x = (fl && (!has_g || g[u][q] > 0.f)) ? val[u][q] : 0.f;
+                        acc[q] = fmaf(wu, x, acc[q]);
+                    }
+                    if (mu & 8) {                                  // the row's own term was its last: the row is complete
+                        emit(wid + 4 * (mu & 7), acc);
+#pragma unroll
+                        for (int q = 0; q < VEC; ++q) acc[q] = 0.f;
+                    }
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i)                      // rows past the live count: zeros in the image (never stored)
+        if (m0 + wid + 4 * i >= n) {
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) {
+                const int k = f0 + q;
+                if (k < KQ * 4) As[((k >> 2) * 2 + (k & 1)) * AD_LDA + (wid + 4 * i) * 2 + ((k >> 1) & 1)] = 0.f;
+            }
+        }
+    __syncthreads();
+    // ---- wavefront w: K quarter w, both column halves (gemm_skinny_body: wavefront (half, quarter))
+    ad_f32x16 acc0 = {0}, acc1 = {0};
+    {
+        const float* Ap = As + h * AD_LDA + li * 2;
+        const bool c0ok = n0 + li < N, c1ok = n0 + 32 + li < N;
+#pragma unroll
+        for (int i = 0; i < PER; ++i) {
+            const int kq = kq0 + i;
+            if (kq < kq1) {                                        // (uniform)
+                const float2 av = *reinterpret_cast<const float2*>(Ap + (size_t)kq * 2 * AD_LDA);
+                const bool k0ok = 4 * kq + h < F, k1ok = 4 * kq + h + 2 < F;
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, (k0ok && c0ok) ? bx[i][0] : 0.f, acc0, 0, 0, 0);
+                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, (k1ok && c0ok) ? by[i][0] : 0.f, acc0, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, (k0ok && c1ok) ? bx[i][1] : 0.f, acc1, 0, 0, 0);
+                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, (k1ok && c1ok) ? by[i][1] : 0.f, acc1, 0, 0, 0);
+            }
+        }
+    }
+    __syncthreads();                                 // every wavefront has read the image: it becomes the partial tiles
+    float* Ps = smem;                                // [4 K quarters][2 column halves][16][64]
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        Ps[((wid * 2 + 0) * 16 + r) * 64 + lane] = acc0[r];
+        Ps[((wid * 2 + 1) * 16 + r) * 64 + lane] = acc1[r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int o = tid + 256 * u;                 // (column half, register index, lane) of one output element
+        const int ln = o & 63, r = (o >> 6) & 15, ct = o >> 10;
+        const float v0 = Ps[((0 * 2 + ct) * 16 + r) * 64 + ln], v1 = Ps[((1 * 2 + ct) * 16 + r) * 64 + ln];
+        const float v2 = Ps[((2 * 2 + ct) * 16 + r) * 64 + ln], v3 = Ps[((3 * 2 + ct) * 16 + r) * 64 + ln];
+        const int gn = n0 + 32 * ct + (ln & 31);
+        const int gm = m0 + (r & 3) + 8 * (r >> 2) + 4 * (ln >> 5);
+        if (gm < n && gn < N) p.dx[(long long)gm * N + gn] = ((v0 + v1) + v2) + v3;
+    }
+}
+template <int VEC>
+__global__ __launch_bounds__(256) void gcn_aggregate_bwd_dx_k(AggBwdDxArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float ad_smem[];
+    gcn_aggregate_bwd_dx_body<VEC>(p, (int)blockIdx.x, ad_smem);
+}
+
 size_t grapes_colsum_workspace_bytes(int F) { return (size_t)CS_BLOCKS * (F > 0 ? F : 1) * sizeof(float); }
 
 // ticket (optional): GRAPES_COLSUM_TICKETS zero words, left zero — few-row inputs then take one launch
@@ -2356,6 +2557,40 @@ extern "C" int grapes_gcn_aggregate_bwd(const float* dout, const float* relu_out
                             partials, s);
 }
 
+/* grapes_gcn_aggregate_bwd's few-row launch AND grapes_linear_bwd_input on its output in ONE launch (gcn_aggregate_bwd_dx_body):
+ * dt = Â^T (dout (.) [relu_out > 0]) [n, f],  dx = dt · w [n, f_in]  (w [f, f_in]),  dbias (+)= the gated column sums.  Bit for bit
+ * what the two calls give.  Shapes: 0 < n <= 2048 (the graphs whose rows grapes_gcn_aggregate_bwd's callers walk without long-row items), 16 < f <= 256 (f <= 64 unless f % 4 == 0 and dout, relu_out, dt are 16-byte
+ * aligned), no long-row items (every row is walked by one wavefront).  Recorded (riders) like grapes_gcn_aggregate_bwd. */
+extern "C" int grapes_gcn_aggregate_bwd_input_available(const float* dout, const float* relu_out, const float* dt, int32_t n,
+                                                        int32_t f, int32_t f_in) {
+    const bool vec = (f % 4 == 0) && grapes_aligned16(dout) && grapes_aligned16(dt) && (!relu_out || grapes_aligned16(relu_out));
+    return (n > 0 && n <= 2048 && f > 16 && f <= 64 * (vec ? 4 : 1) && f_in >= 1) ? 1 : 0;
+}
+extern "C" int grapes_gcn_aggregate_bwd_input(const float* dout, const float* relu_out, const int32_t* rowptr_s,
+                                              const int32_t* csr_dst, const float* dinv, const float* w, float* dt, float* dx,
+                                              float* dbias, int32_t accumulate_bias, int32_t n, const int32_t* d_n, int32_t f,
+                                              int32_t f_in, void* workspace, uint32_t* d_ticket, grapes_stream_t stream) {
+    if (!dout || !rowptr_s || !csr_dst || !dinv || !w || !dt || !dx) return GRAPES_EINVAL;
+    if (!grapes_gcn_aggregate_bwd_input_available(dout, relu_out, dt, n, f, f_in)) return GRAPES_EINVAL;
+    if (dbias && (!workspace || !d_ticket)) return GRAPES_EINVAL;
+    const bool vec = (f % 4 == 0) && grapes_aligned16(dout) && grapes_aligned16(dt) && (!relu_out || grapes_aligned16(relu_out));
+    const int VECW = vec ? 4 : 1;
+    const int ncb = grapes_div_up(f, 64);
+    int R = grapes_div_up(n, 64); if (R > CS_SMALL_R) R = CS_SMALL_R; if (R < 1) R = 1;
+    const AggBwdDxArgs A{{dout, relu_out, rowptr_s, csr_dst, dinv, dt, n, d_n, f, dbias, accumulate_bias, (float*)workspace,
+                          (unsigned*)d_ticket, ncb, R}, w, dx, f_in};
+    const int grid = agg_bwd_dx_grid(A);
+    const size_t lds = agg_bwd_dx_lds_bytes(f);
+    auto single = [=](hipStream_t st) {
+        if (vec) hipLaunchKernelGGL((gcn_aggregate_bwd_dx_k<4>), dim3(grid), dim3(256), lds, st, A);
+        else hipLaunchKernelGGL((gcn_aggregate_bwd_dx_k<1>), dim3(grid), dim3(256), lds, st, A);
+    };
+    if (grapes_rider_recording()) { grapes_rider_record(grapes_rider_make(GRAPES_RK_AGGBWD_DX, VECW, grid, 256, A, single)); return 0; }
+    single((hipStream_t)stream);
+    GRAPES_LAUNCH_CHECK();
+    return 0;
+}
+
 
 // ============================================================================ backward of the sampler's 1-wide head, all hops
 // d log_prob / d logit of hop q, DENSE over the hop's batch rows (zero for rows that were not candidates; cand_pos is
@@ -2444,6 +2679,26 @@ __global__ __launch_bounds__(256) void narrow_multi_aggbwd_pair_k(NarrowSegs sg,
     }
 }
 
+// ... and carrying a recorded backward aggregation WITH its input gradient (gcn_aggregate_bwd_dx_body; dynamic LDS = the rider's)
+template <int VEC>
+__global__ __launch_bounds__(256) void bernoulli_aggdx_pair_k(BernSegs sg, BernArgs ba, int gx, AggBwdDxArgs b) {
+    extern __shared__ __attribute__((aligned(16))) float ad_smem[];
+    if ((int)blockIdx.x < gx) bernoulli_dense_multi_body(sg, ba, (int)blockIdx.x, gx);
+    else gcn_aggregate_bwd_dx_body<VEC>(b, ((int)blockIdx.x - gx) + (int)blockIdx.y * ((int)gridDim.x - gx), ad_smem);
+}
+template <int VEC>
+__global__ __launch_bounds__(256) void narrow_multi_aggdx_pair_k(NarrowSegs sg, int F, int narrow_lane_rows, int gx, AggBwdDxArgs b) {
+    extern __shared__ __attribute__((aligned(16))) float ad_smem[];
+    if ((int)blockIdx.x < gx) {
+        const int q = blockIdx.y;
+#define NSEL(f) (q == 0 ? sg.f[0] : (q == 1 ? sg.f[1] : (q == 2 ? sg.f[2] : sg.f[3])))
+        narrow_body(NSEL(h), NSEL(rowptr), NSEL(csr), NSEL(dinv), NSEL(bias), NSEL(out), NSEL(n_cap), NSEL(d_n), F, 0,
+                    narrow_lane_rows, (int)blockIdx.x, gx);
+#undef NSEL
+    } else
+        gcn_aggregate_bwd_dx_body<VEC>(b, ((int)blockIdx.x - gx) + (int)blockIdx.y * ((int)gridDim.x - gx), ad_smem);
+}
+
 extern "C" size_t grapes_sampler_head_bwd_multi_workspace_bytes(void) { return (size_t)4 * 32 * sizeof(float); }
 
 extern "C" int grapes_sampler_head_bwd_multi_phase(int32_t count, const float* const* logits, const float* const* mask,
@@ -2481,10 +2736,24 @@ extern "C" int grapes_sampler_head_bwd_multi_phase(int32_t count, const float* c
         rx = grapes_div_up(r->grid, count);
         return true;
     };
-    AggBwdSmallArgs B; int vecw = 0, rx = 0;
+    // ... or one with its input gradient (grapes_gcn_aggregate_bwd_input)
+    auto rider_dx = [&](AggBwdDxArgs& D, int& vecw, int& rx) -> bool {
+        const GrapesRiderRecord* r = grapes_rider_match(GRAPES_RK_AGGBWD_DX, 4, 256, s);
+        vecw = 4;
+        if (!r) { r = grapes_rider_match(GRAPES_RK_AGGBWD_DX, 1, 256, s); vecw = 1; }
+        if (!r) return false;
+        memcpy(&D, r->args, sizeof D);
+        rx = grapes_div_up(r->grid, count);
+        return true;
+    };
+    AggBwdSmallArgs B; AggBwdDxArgs D; int vecw = 0, rx = 0;
     if (phase != 2) {
         const BernArgs ba{d_grad_scale, sum_out, accumulate_sum, (float*)workspace, (unsigned*)d_ticket, mean_sum_out};
-        if (rider(B, vecw, rx)) {
+        if (rider_dx(D, vecw, rx)) {
+            const size_t lds = agg_bwd_dx_lds_bytes(D.a.F);
+            if (vecw == 4) hipLaunchKernelGGL((bernoulli_aggdx_pair_k<4>), dim3(g1 + rx, count), dim3(256), lds, s, bs, ba, g1, D);
+            else hipLaunchKernelGGL((bernoulli_aggdx_pair_k<1>), dim3(g1 + rx, count), dim3(256), lds, s, bs, ba, g1, D);
+        } else if (rider(B, vecw, rx)) {
             if (vecw == 4) hipLaunchKernelGGL((bernoulli_aggbwd_pair_k<4>), dim3(g1 + rx, count), dim3(256), 0, s, bs, ba, g1, B);
             else hipLaunchKernelGGL((bernoulli_aggbwd_pair_k<1>), dim3(g1 + rx, count), dim3(256), 0, s, bs, ba, g1, B);
         } else
@@ -2493,7 +2762,11 @@ extern "C" int grapes_sampler_head_bwd_multi_phase(int32_t count, const float* c
     }
     if (phase != 1) {
         int g2 = grapes_div_up(nmax, 256); if (g2 > 4096) g2 = 4096;
-        if (rider(B, vecw, rx)) {
+        if (rider_dx(D, vecw, rx)) {
+            const size_t lds = agg_bwd_dx_lds_bytes(D.a.F);
+            if (vecw == 4) hipLaunchKernelGGL((narrow_multi_aggdx_pair_k<4>), dim3(g2 + rx, count), dim3(256), lds, s, ns, 1, narrow_lane_rows_cfg(), g2, D);
+            else hipLaunchKernelGGL((narrow_multi_aggdx_pair_k<1>), dim3(g2 + rx, count), dim3(256), lds, s, ns, 1, narrow_lane_rows_cfg(), g2, D);
+        } else if (rider(B, vecw, rx)) {
             if (vecw == 4) hipLaunchKernelGGL((narrow_multi_aggbwd_pair_k<4>), dim3(g2 + rx, count), dim3(256), 0, s, ns, 1, narrow_lane_rows_cfg(), g2, B);
             else hipLaunchKernelGGL((narrow_multi_aggbwd_pair_k<1>), dim3(g2 + rx, count), dim3(256), 0, s, ns, 1, narrow_lane_rows_cfg(), g2, B);
         } else

@@ -917,6 +917,38 @@ class DeferredSlabs:
             self.sets.append((ws, ws.data_ptr() + ns * fo * fi * 4, dbias, fo))
         return True
 
+    def try_add_multi(self, problems):
+        """problems: 1..4 tuples (dout, gate, x, dw, dbias, d_n) over the same rows (n, d_n), not accumulating: their slab launches
+        as ONE launch (grapes_linear_bwd_weight_slabs_multi), their sets registered in the order given — or nothing is launched
+        and False is returned when a shape is outside the few-row kernel."""
+        import ctypes as C
+        k = len(problems)
+        n, d_n = problems[0][2].shape[0], problems[0][5]
+        nsets = sum(2 if p[4] is not None else 1 for p in problems)
+        if not (1 <= k <= 4) or any(p[2].shape[0] != n or p[5] is not d_n for p in problems):
+            return False
+        if len(self.sets) + nsets > 8:
+            self.flush()
+        if self.sets and (self.n != n or (self.d_n is None) != (d_n is None) or
+                          (d_n is not None and self.d_n.data_ptr() != d_n.data_ptr()) or self.acc):
+            self.flush()
+        fis, fos = [p[2].shape[1] for p in problems], [p[0].shape[1] for p in problems]
+        wss = [_ws(lib().grapes_linear_bwd_weight_slabs_bytes(n, fi, fo), problems[0][2].device) for fi, fo in zip(fis, fos)]
+        arr = lambda ts: (C.c_void_p * k)(*[None if t is None else t.data_ptr() for t in ts])
+        ints = lambda vs: (C.c_int32 * k)(*vs)
+        rc = lib().grapes_linear_bwd_weight_slabs_multi(k, arr([p[0] for p in problems]), arr([p[1] for p in problems]),
+                                                        arr([p[2] for p in problems]), n, _p(d_n), ints(fis), ints(fos),
+                                                        ints([1 if p[4] is not None else 0 for p in problems]), arr(wss), _stream())
+        if rc != 0:
+            return False
+        ns = (n + 127) // 128
+        self.n, self.d_n, self.acc = n, d_n, False
+        for (dout, gate, x, dw, dbias, _), ws, fi, fo in zip(problems, wss, fis, fos):
+            self.sets.append((ws, ws.data_ptr(), dw, fo * fi))
+            if dbias is not None:
+                self.sets.append((ws, ws.data_ptr() + ns * fo * fi * 4, dbias, fo))
+        return True
+
     def flush(self):
         if not self.sets:
             return
@@ -1432,6 +1464,7 @@ def gcn_aggregate_narrow_pair(h_a, h_b, prep: PreparedGraph, bias_a=None, bias_b
 
 
 _BWD_HOSTS: List = []     # launches waiting to carry a few-row backward aggregation (carry_backward_aggregations)
+_BWD_ALONE = [0]          # recorded gcn_aggregate_bwd_input launches a host did NOT carry (issued on their own): tests read it
 
 
 def carry_backward_aggregations(hosts):
@@ -1487,6 +1520,53 @@ def gcn_aggregate_bwd(dout, prep: PreparedGraph, relu_out=None, want_bias=True, 
         if alone < 0:
             raise _lib.GrapesHipError(f"rider_detach failed ({alone})")
     return dh, dbias
+
+
+def gcn_aggregate_bwd_input(dout, prep: PreparedGraph, w, relu_out=None, dbias=None, accumulate_bias=False, dt=None, dx=None):
+    """gcn_aggregate_bwd and linear_bwd_input on its output as ONE launch (include/grapes_hip.h: grapes_gcn_aggregate_bwd_input):
+    -> (dt, dx) with dt = Âᵀ(dout ⊙ [relu_out > 0]) and dx = dt w, bit for bit what the two calls give, dbias (+)= the gated
+    column sums — or None where that launch does not take the shape (nothing is launched then).  Carried by a waiting host
+    launch like gcn_aggregate_bwd (carry_backward_aggregations)."""
+    _chk(dout, _f32, "dout"); _chk(relu_out, _f32, "relu_out", True); _chk(w, _f32, "w"); _chk(dbias, _f32, "dbias", True)
+    n, f = dout.shape
+    fi = w.shape[1]
+    dev = dout.device
+    if w.shape[0] != f or prep.n > _SMALL_GRAPH:
+        return None
+    _chk(dt, _f32, "dt", True); _chk(dx, _f32, "dx", True)
+    if dt is None:
+        dt = torch.empty_like(dout)
+    L = lib()
+    if not L.grapes_gcn_aggregate_bwd_input_available(_p(dout), _p(relu_out), _p(dt), n, f, fi):
+        return None
+    if dx is None:
+        dx = torch.empty((n, fi), dtype=_f32, device=dev)
+    if tuple(dt.shape) != (n, f) or tuple(dx.shape) != (n, fi):
+        raise ValueError("gcn_aggregate_bwd_input: dt [n, f], dx [n, f_in]")
+    ws = _ws(L.grapes_gcn_aggregate_bwd_workspace_bytes(0, f), dev)
+    host = _BWD_HOSTS.pop(0) if _BWD_HOSTS else None
+    if host is not None:
+        _lib.check(L.grapes_rider_record_begin(), "rider_record_begin")
+    prog = -1
+    try:
+        rc = L.grapes_gcn_aggregate_bwd_input(_p(dout), _p(relu_out), _p(prep.rowptr_s), _p(prep.csr_dst), _p(prep.dinv), _p(w),
+                                              _p(dt), _p(dx), _p(dbias), 1 if accumulate_bias else 0, n, _p(prep.d_n), f, fi,
+                                              _p(ws), _p(_ticket(dev)[16:32]), _stream())
+    finally:
+        if host is not None:
+            prog = int(L.grapes_rider_record_end())
+    _lib.check(rc, "gcn_aggregate_bwd_input")
+    if host is not None:
+        _lib.check(L.grapes_rider_attach(prog, 0, _stream()), "rider_attach")
+        try:
+            host()
+        finally:
+            alone = L.grapes_rider_detach(_stream(), None)
+            L.grapes_rider_free(prog)
+        if alone < 0:
+            raise _lib.GrapesHipError(f"rider_detach failed ({alone})")
+        _BWD_ALONE[0] += alone
+    return dt, dx
 
 
 # ------------------------------------------------------------------------------- GATConv aggregation (modules/gcn.py:45-72)

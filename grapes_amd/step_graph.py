@@ -990,9 +990,41 @@ class GraphedTrainer:
         d = s.dl
         # the layers' few-row weight gradients leave their slab sums to ONE launch at the end (ops.DeferredSlabs)
         deferred = ops.DeferredSlabs() if _sw("GRAPES_DEFER_SLABS", "1") != "0" else None
+        # no dropout between the layers, no embedding gradient: a layer's input gradient comes out of its backward aggregation's
+        # launch (ops.gcn_aggregate_bwd_input) and the layers' weight-gradient slabs run side by side in ONE launch at the end —
+        # three launches instead of five on a three-layer classifier (A/B: GRAPES_CLS_BWD_FOLD=0)
+        fold = (deferred is not None and not self.embed and all(k is None for k in keeps) and
+                _sw("GRAPES_CLS_BWD_FOLD", "1") != "0")
+        slab_jobs = []                                 # (dout, gate, x, dw, dbias, d_n) in the order the separate launches ran
+
+        def flush_jobs():
+            if slab_jobs and not deferred.try_add_multi(slab_jobs):
+                for dout, gate, x, dw, dbias, dn in slab_jobs:
+                    if gate is None and dbias is None:
+                        ops.linear_bwd_weight(dout, x, d_n=dn, out=dw, accumulate=False, defer=deferred)
+                    else:
+                        ops.linear_bwd_weight_gated(dout, x, gate=gate, d_n=dn, dw=dw, dbias=dbias, accumulate=False,
+                                                    want_bias=dbias is not None, defer=deferred)
+            del slab_jobs[:]
+
         for i in range(len(layers) - 1, -1, -1):
             if keeps[i] is not None:                   # d (layer i's output before dropout)
                 d = ops.dropout_bwd(d, keeps[i], self.dropout, d_n=d_na)
+            if fold and i == 0 and s.first_fused and self._fl[id(layers[0])].agg_first and slab_jobs:
+                # (the first layer's weight gradient, gated by its activations, reads ÂX: _first_bwd's operands)
+                fl0 = self._fl[id(layers[0])]
+                slab_jobs.append((d, acts[1] if s.first_relu else None, acts[0], fl0.grad, layers[0].bias.grad, used[0].d_n))
+                continue
+            if fold and i > 0:
+                conv = layers[i]
+                if not slab_jobs or slab_jobs[-1][5] is used[i].d_n:
+                    r = ops.gcn_aggregate_bwd_input(d, used[i], conv.lin.weight, relu_out=acts[i + 1] if i < len(layers) - 1 else None,
+                                                    dbias=conv.bias.grad, accumulate_bias=False)
+                    if r is not None:
+                        slab_jobs.append((r[0], None, acts[i], conv.lin.weight.grad, None, used[i].d_n))
+                        d = r[1]
+                        continue
+            flush_jobs()
             if i == 0 and s.first_fused:
                 self._first_bwd(layers[0], acts[0], acts[1], d, used[0], False, relu=s.first_relu, defer=deferred)
                 if self.embed:
@@ -1007,6 +1039,7 @@ class GraphedTrainer:
             else:
                 d = self._conv_bwd(layers[i], acts[i], acts[i + 1], d, used[i], i < len(layers) - 1, i > 0, False,
                                    defer=deferred)
+        flush_jobs()
         if deferred is not None:
             # one GPU, fused Adam, no padded first-layer gradient to publish: the slab sums ride in the optimiser launch
             if (self.grad_sync is None and self._fused_adam is not False and self.opt_c is not None and

@@ -75,7 +75,8 @@ extern "C" {
  * 304: grapes_sage_aggregate_fwd / _bwd and grapes_cluster_aggregate_fwd / _bwd were one layer written twice and left, with their two
  * _workspace_bytes: grapes_rootsum_aggregate_fwd / _bwd (loops, self_weight, self_term, scale) and
  * grapes_rootsum_aggregate_workspace_bytes compute both; added within 304 (no signature of an earlier entry point changed): LINKX's
- * adjacency embedding bag — grapes_bag_batch, grapes_bag_fwd, grapes_bag_bwd (+ _workspace_bytes each), grapes_bag_bwd_adam. */
+ * adjacency embedding bag — grapes_bag_batch, grapes_bag_fwd, grapes_bag_bwd (+ _workspace_bytes each), grapes_bag_bwd_adam; the classifier's backward pass in three launches —
+ * grapes_gcn_aggregate_bwd_input(_available), grapes_linear_bwd_weight_slabs_multi. */
 #define GRAPES_ABI_VERSION 304
 
 #define GRAPES_EINVAL (-1)   /* bad size / NULL pointer / unsupported shape */
@@ -470,6 +471,12 @@ int grapes_linear_bwd_weight_slabs(const float* dout, const float* gate, const f
 int grapes_linear_bwd_weight_slabs_and_input(const float* dout, const float* gate, const float* x, const float* w, float* dx,
                                              int32_t n, const int32_t* d_n, int32_t f_in, int32_t f_out, int32_t want_bias,
                                              void* workspace, grapes_stream_t stream);
+/* grapes_linear_bwd_weight_slabs for 1..4 layers over the SAME n rows (one d_n) as ONE launch, each layer's workgroups side by
+ * side: problem q = (dout[q], gate[q] or NULL, x[q], f_in[q], f_out[q], want_bias[q], workspace[q]) exactly as that entry point
+ * takes them; the same slabs.  GRAPES_EINVAL (nothing launched) when a shape is not one of the few-row kernel. */
+int grapes_linear_bwd_weight_slabs_multi(int32_t count, const float* const* dout, const float* const* gate, const float* const* x,
+                                         int32_t n, const int32_t* d_n, const int32_t* f_in, const int32_t* f_out,
+                                         const int32_t* want_bias, void* const* workspace, grapes_stream_t stream);
 int grapes_slab_reduce_sets(int32_t nsets, const float* const* slabs, float* const* outs, const int64_t* counts, int32_t n,
                             const int32_t* d_n, int32_t accumulate, grapes_stream_t stream);
 /* Gate-word forms of  layer -> ReLU -> 1-wide head  (reference modules/gcn.py:31-36 with hidden_dims = [H, 1]: the sampler
@@ -679,6 +686,19 @@ int grapes_gcn_aggregate_bwd(const float* dout, const float* relu_out, const int
                              const int32_t* d_n, int32_t f, const int32_t* long_items,
                              const int32_t* d_n_items, int32_t item_cap, void* workspace,
                              uint32_t* d_ticket, grapes_stream_t stream);
+/* The few-row launch of grapes_gcn_aggregate_bwd AND grapes_linear_bwd_input on its output as ONE launch: dt [n, f] = what
+ * grapes_gcn_aggregate_bwd writes to dh, dx [n, f_in] = dt w (w [f, f_in]), dbias (+)= the gated column sums (NULL: none; else
+ * workspace of grapes_gcn_aggregate_bwd_workspace_bytes(0, f) and d_ticket as above).  A workgroup forms 32 rows of dt and runs
+ * the 32 x 64 tile of the few-row dx GEMM on them: every value is bit for bit the two calls'.  _available: 0 < n <= 2048 (graphs small enough that no row is split into long-row items),
+ * 16 < f <= 256 (f <= 64 unless f % 4 == 0 with 16-byte aligned dout, relu_out and dt); rows of any length are walked by one
+ * wavefront (no long-row items).  Recorded while a rider recording is open, like grapes_gcn_aggregate_bwd, and carried by the same
+ * launches (grapes_sampler_head_bwd_multi_phase). */
+int grapes_gcn_aggregate_bwd_input_available(const float* dout, const float* relu_out, const float* dt, int32_t n, int32_t f,
+                                             int32_t f_in);
+int grapes_gcn_aggregate_bwd_input(const float* dout, const float* relu_out, const int32_t* rowptr_s, const int32_t* csr_dst,
+                                   const float* dinv, const float* w, float* dt, float* dx, float* dbias,
+                                   int32_t accumulate_bias, int32_t n, const int32_t* d_n, int32_t f, int32_t f_in,
+                                   void* workspace, uint32_t* d_ticket, grapes_stream_t stream);
 
 /* ------------------------------------------------------------------ GATConv aggregation (csrc/gat_kernels.hip)
  * modules/gcn.py:45-72: GAT stacks GATConv(in_channels, out_channels) layers with PyG's defaults (torch_geometric 2.5.2, not in
